@@ -9,7 +9,10 @@ per-GPU workload on its own reads (weak scaling), with no data-path collective.
 
     python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line (with the roofline and per-kernel
+figures the timed steps' own HIP events give).  --full adds what takes runs of its own, beside `value`: the host-buffer (h2d) leg, the
+flappie binary's host-fed and length-mix legs and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (float32 / float64, at most 64 MB: a seeded sample of the reads when all of them would not fit).
 """
 import argparse
 import json
@@ -190,10 +193,31 @@ def self_launch(ngpus, argv):
 
 class _StubBatch:
     """FFHIP_BENCH_STUB=1 (CPU tests of the launch / timing / reduction plumbing): stands where a batch of the HIP engine stands."""
-    nblock = 800
+    nblock, P, nstate = 800, 40, 8
 
     def __init__(self, *a):
         pass
+
+    def read_nblock(self, read):
+        return self.nblock
+
+    def transitions(self, read):
+        return np.full((self.nblock, self.P), read, dtype=np.float32)
+
+    def path(self, read):
+        return np.arange(self.nblock + 1, dtype=np.int32) % self.nstate, np.zeros(self.nblock + 1, dtype=np.float32)
+
+    def trace(self, read):
+        return np.zeros((self.nblock + 1, self.nstate), dtype=np.int32)
+
+    def basecall(self, read):
+        return "ACGT"[read % 4] * (1 + read % 7)
+
+    def quality(self, read):
+        return "5" * (1 + read % 7)
+
+    def score(self, read):
+        return float(read)
 
     def set_signals(self, sig):
         pass
@@ -385,6 +409,40 @@ def length_mix_leg(cfg, local_rank, nfiles=None):
         shutil.rmtree(d, ignore_errors=True)
 
 
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(d, b, nread, with_trace):
+    """What a caller of the timed path receives from batch `b` (the one that ran the last timed step), as d/<name>.npy: transitions
+    (read, block, P), path (read, block + 1), trace (read, block + 1, state; the run-length model computes none), score (read),
+    basecall and quality (read, longest string: character codes, 0 past a string's end) and reads (the batch slots written).  Every read
+    when they fit in DUMP_BYTES, else a sample of the slots drawn with a fixed seed, so that the same arguments give the same files.
+    A flip-flop call has at most one base a block: nblock + 1 bounds a string.  (qpath is left out: its first entry is NaN by design, and
+    the quality string is made of it.)"""
+    nb = b.read_nblock(0)          # every read of a bench batch has the same length
+    per_read = 4 * (nb * b.P + 3 * (nb + 1) + ((nb + 1) * b.nstate if with_trace else 0)) + 8 * 2
+    k = min(nread, max(1, (DUMP_BYTES - 64000) // per_read))          # (64 kB: the .npy headers)
+    reads = np.arange(nread) if k == nread else np.sort(np.random.default_rng(0).choice(nread, k, replace=False))
+
+    def codes(strs):
+        out = np.zeros((len(strs), max([len(s) for s in strs] + [0])), dtype=np.float32)
+        for i, s in enumerate(strs):
+            out[i, :len(s)] = np.frombuffer(s.encode(), dtype=np.uint8)
+        return out
+
+    arrays = {"reads": reads.astype(np.float64),
+              "transitions": np.stack([b.transitions(int(r)) for r in reads]),
+              "path": np.stack([b.path(int(r))[0] for r in reads]).astype(np.float32),
+              "score": np.array([b.score(int(r)) for r in reads], dtype=np.float64),
+              "basecall": codes([b.basecall(int(r)) for r in reads]),
+              "quality": codes([b.quality(int(r)) for r in reads])}
+    if with_trace:
+        arrays["trace"] = np.stack([b.trace(int(r)) for r in reads]).astype(np.float32)
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -396,11 +454,16 @@ def main():
                     help="batches in flight per GPU, each on its own HIP stream (default: the workload's measured best -- 2 where one workgroup "
                          "per CU runs the layers and the other batch's convolution / decode kernels fit beside them: c2 +2.9 %%, rle +24 %%; 1 where two "
                          "workgroups per CU already fill the CUs: there a second batch costs up to 10 %%)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs reported beside `value`: h2d-inclusive steps, the flappie binary's host-fed and "
+                         "length-mix runs, the CPU baseline (each can be left out with its --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-pair", action="store_true", help="c2 / rle: submit the batches one by one (ffhip_batch_run) instead of in pairs (ffhip_batch_run_pair)")
-    ap.add_argument("--no-h2d-leg", action="store_true")
-    ap.add_argument("--no-host-fed-leg", action="store_true", help="skip the per-rank run of the flappie binary over generated fast5 files")
-    ap.add_argument("--no-length-mix-leg", action="store_true", help="skip the run of the flappie binary over generated fast5 files of mixed lengths (one GPU only)")
+    ap.add_argument("--no-h2d-leg", action="store_true", help="--full: skip the h2d-inclusive steps")
+    ap.add_argument("--no-host-fed-leg", action="store_true", help="--full: skip the per-rank run of the flappie binary over generated fast5 files")
+    ap.add_argument("--no-length-mix-leg", action="store_true", help="--full: skip the run of the flappie binary over generated fast5 files of mixed lengths (one GPU only)")
     ap.add_argument("--hidden", type=int, default=None, help="override the config's hidden size")
     ap.add_argument("--nread", type=int, default=int(os.environ.get("FFHIP_BENCH_NREAD", "0")) or None, help="override the config's reads per batch")
     args = ap.parse_args()
@@ -433,13 +496,14 @@ def main():
     # FFHIP_BENCH_SYSFS: a fake sysfs tree for the CPU tests; FFHIP_BENCH_NO_NUMA_BIND=1: off)
     from flappie_amd import shard as _shard
     numa_bound = (-1, 0) if os.environ.get("FFHIP_BENCH_NO_NUMA_BIND") else _shard.bind_to_gpu_numa(local_rank, os.environ.get("FFHIP_BENCH_SYSFS", "/sys"))
-    import torch
-    import torch.distributed as dist
     # FFHIP_BENCH_FORCE_DIST=1: take the RCCL code path (init, barrier, MAX all-reduce) with a single rank too --
     # lets a 1-GPU box exercise exactly what the N > 1 launches run
     dist_on = world > 1 or bool(os.environ.get("FFHIP_BENCH_FORCE_DIST"))
     stub = bool(os.environ.get("FFHIP_BENCH_STUB"))          # CPU tests: gloo, no engine (tests/test_bench_launch.py)
-    if dist_on:
+    dist = None
+    if dist_on:          # torch is the distributed plumbing only: a single rank never imports it (its start-up is not the benchmark's)
+        import torch
+        import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29533")
         os.environ.setdefault("RANK", str(rank))
@@ -477,10 +541,11 @@ def main():
         if dist_on:
             dist.barrier()
         eng.synchronize()
-        if torch.cuda.is_available() and not stub:
+        if dist_on and not stub:
             torch.cuda.synchronize()
 
     def run_steps(n, upload=False):
+        """n steps; returns the batch that ran the last one"""
         pending = []
         if pair:
             for i in range(0, n, 2):
@@ -501,7 +566,7 @@ def main():
             for bs in pending:
                 for b in bs:
                     b.finish()
-            return
+            return pending[-1][-1] if pending else None
         for i in range(n):
             b = batches[i % nfl]
             if len(pending) == nfl:
@@ -512,25 +577,28 @@ def main():
             pending.append(b)
         for b in pending:
             b.finish()
+        return pending[-1] if pending else None
 
     run_steps(warmup)
     eng.set_profiling(True)              # HIP events on the kernels' own stream; no host synchronisation added
     barrier()
     t0 = time.perf_counter()
-    run_steps(steps)
+    last = run_steps(steps)
     barrier()
     dt = time.perf_counter() - t0
-    prof = [b.profile() for b in batches]
+    prof = [last.profile()]               # the last timed step's batch: with few steps, not every batch in flight has run
     eng.set_profiling(False)
-    nblock_, rnn_path_ = batches[0].nblock, batches[-1].rnn_path()      # (the batches are closed before the line is put together)
-    paired_ = (not stub) and pair and batches[0].paired()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, NREAD, with_trace=cfg["kind"] != M.NET_LSTM5_RLE)
+    nblock_, rnn_path_ = batches[0].nblock, last.rnn_path()      # (the batches are closed before the line is put together)
+    paired_ = (not stub) and pair and last.paired()
     # GRUmod at H = 256 in batches of whole 1024-read launches: the packed form of the layer kernel (ffhip_rnn_split.hip, PACK)
     packed_ = (not stub) and cfg["kind"] in (M.NET_GRUMOD5, M.NET_LSTM5) and H == 256 and dm is not None and dm.launch_reads == 1024 and NREAD % 1024 == 0
 
     # second leg, reported beside `value`, never as it: the same steps with the batch's signal handed over as a HOST buffer
     # every step (SURVEY.md section 8d counts "from first H2D")
     dt_h2d, steps_h2d = None, 0
-    if not args.no_h2d_leg:
+    if args.full and not args.no_h2d_leg:
         steps_h2d = steps                # the same K steps as `value`
         barrier()
         t1 = time.perf_counter()
@@ -556,13 +624,13 @@ def main():
         dm.close()
     eng.close()
     hostfed = None
-    if not args.no_host_fed_leg and not stub:
+    if args.full and not args.no_host_fed_leg and not stub:
         try:
-            hostfed = host_fed_leg(cfg, rank, local_rank, world, dist if dist_on else None)
+            hostfed = host_fed_leg(cfg, rank, local_rank, world, dist)
         except Exception as e:      # a reported leg, not the benchmark: its failure must not lose the line
             hostfed = {"skipped": "host-fed leg failed: %r" % (e,)} if rank == 0 else None
     lenmix = None
-    if world == 1 and rank == 0 and not stub and not args.no_length_mix_leg and not args.no_host_fed_leg:
+    if args.full and world == 1 and rank == 0 and not stub and not args.no_length_mix_leg and not args.no_host_fed_leg:
         try:
             lenmix = length_mix_leg(cfg, local_rank)
         except Exception as e:
@@ -669,7 +737,7 @@ def main():
             out["h2d_inclusive"] = {"value": round(world * steps_h2d * NREAD * NSAMPLE / dt_h2d / 1e6, 4), "unit": "Msamples/s",
                                     "ms_per_step": round(dt_h2d / steps_h2d * 1e3, 4), "steps": steps_h2d,
                                     "note": "the same step with the batch's %.1f MB of signal copied from a host buffer inside it (never `value`)" % (NREAD * NSAMPLE * 4 / 1e6)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
 

@@ -49,9 +49,71 @@ def test_world_size_mismatch_is_an_error_message_not_an_assertion():
     assert r.returncode != 0 and "WORLD_SIZE 1 != --gpus 2" in r.stderr and "Traceback" not in r.stderr
 
 
+def test_plain_line_and_dumped_outputs_with_a_stub_engine(tmp_path):
+    """a plain run times its steps and nothing else (the legs beside `value` are --full's); --dump-outputs writes float32 / float64 arrays of
+    at most 64 MB, every read when they fit and else the same seeded sample of reads from run to run"""
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")], {"FFHIP_BENCH_STUB": "1"})
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and not {"cpu_baseline", "h2d_inclusive", "host_fed", "length_mix"} & set(d)
+    import numpy as np
+    a = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert set(a) == {"reads", "transitions", "path", "trace", "score", "basecall", "quality"}
+    assert all(x.dtype in (np.float32, np.float64) and np.isfinite(x).all() for x in a.values())
+    nread = d["config"]["reads_per_step"]
+    assert a["transitions"].shape == (nread, d["config"]["blocks_per_read"], 40) and np.array_equal(a["reads"], np.arange(nread))
+    assert np.array_equal(a["transitions"][:, 0, 0], a["reads"]) and a["basecall"][5, 0] == ord("C")      # (the stub's read r: transitions r, bases "ACGT"[r % 4])
+    for k in "bc":
+        r = _run(["--steps", "2", "--warmup", "0", "--nread", "4096", "--dump-outputs", str(tmp_path / k)], {"FFHIP_BENCH_STUB": "1"})
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert sum(os.path.getsize(str(tmp_path / k / f)) for f in os.listdir(str(tmp_path / k))) <= 64 * 10 ** 6
+    reads = np.load(str(tmp_path / "b" / "reads.npy"))
+    assert 1 < len(reads) < 4096 and np.all(np.diff(reads) > 0) and reads[-1] < 4096
+    for f in os.listdir(str(tmp_path / "b")):
+        assert np.array_equal(np.load(str(tmp_path / "b" / f)), np.load(str(tmp_path / "c" / f))), f
+
+
+@pytest.mark.gpu
+def test_dumped_outputs_are_what_the_timed_path_computed(tmp_path, engine):
+    """--dump-outputs of the headline workload holds the last timed step's results: the bench's seeded signal through a pair of batches in this
+    process (the last of an even number of steps is the second batch of a pair) gives the same transition scores, paths, scores and strings"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from flappie_amd import binding as B
+    from flappie_amd import model as M
+    r = _run(["--gpus", "1", "--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path)], {}, timeout=600)      # (two steps: one of the two pairs in flight runs)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _line(r)
+    a = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert all(np.isfinite(x).all() for x in a.values())
+    cfg = bench.CONFIGS["c2"]
+    assert len(a["reads"]) == cfg["nread"] and a["transitions"].shape == (cfg["nread"], d["config"]["blocks_per_read"], 40)
+    sig = np.random.default_rng(20260928).standard_normal((cfg["nread"], cfg["nsample"])).astype(np.float32)
+    dm = B.DeviceModel(engine, M.synthetic_model(cfg["kind"], cfg["hidden"], seed=1, ident=cfg["ident"]))
+    bs = [B.Batch(dm, cfg["nread"], cfg["nsample"]) for _ in range(2)]
+    try:
+        for b in bs:
+            b.set_signals(sig)
+        bs[0].run_pair(bs[1], 1.0, 0)
+        for b in bs:
+            b.finish()
+        b = bs[1]
+        for i, rd in enumerate(a["reads"].astype(int)):
+            assert np.abs(a["transitions"][i] - b.transitions(rd)).max() <= 1e-5, rd
+            assert np.array_equal(a["path"][i], b.path(rd)[0]) and np.array_equal(a["trace"][i], b.trace(rd)), rd
+            assert abs(a["score"][i] - b.score(rd)) <= 1e-5 * max(1.0, abs(b.score(rd))), rd
+            call, qual = (bytes(x[x > 0].astype(np.uint8)).decode() for x in (a["basecall"][i], a["quality"][i]))
+            assert call == b.basecall(rd) and qual == b.quality(rd) and len(call) > 0, rd
+    finally:
+        for b in bs:
+            b.close()
+        dm.close()
+
+
 @pytest.mark.gpu
 def test_real_line_through_the_distributed_path_with_host_fed_leg():
-    r = _run(["--steps", "4", "--warmup", "1", "--no-cpu-baseline"], {"FFHIP_BENCH_FORCE_DIST": "1", "FFHIP_BENCH_HOSTFED_FILES": "1536", "FFHIP_BENCH_LENMIX_FILES": "1024"}, timeout=900)
+    r = _run(["--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"], {"FFHIP_BENCH_FORCE_DIST": "1", "FFHIP_BENCH_HOSTFED_FILES": "1536", "FFHIP_BENCH_LENMIX_FILES": "1024"}, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r)
     assert d["n_gpus"] == 1 and d["value"] > 1.0 and "roofline" in d and len(d["per_rank_Msamples_per_s"]) == 1

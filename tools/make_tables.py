@@ -5,11 +5,11 @@
     tools/make_tables.py [r06] --write    and puts it between the markers <!-- results:r06 --> ... <!-- /results:r06 --> of DESIGN.md, README.md and BASELINE.md
 
 tests/test_docs_tables.py fails when a document's block differs from what the records give.  Every cell names where it comes from in the header row's legend:
-  value, ms per step, exposed ms, roofline.frac, layer launch (HIP events), cpu_baseline     profiles/TAG_<config>_bench.json   (`python bench.py --config <config> --no-host-fed-leg`)
+  value, ms per step, exposed ms, roofline.frac, layer launch (HIP events), cpu_baseline     profiles/TAG_<config>_bench.json   (`python bench.py --full --config <config> --no-host-fed-leg`)
   layer launch (rocprofv3)                                                                   profiles/TAG_<config>_kernel_stats.csv (the dominant recurrent kernel's avg_us)
   matrix pipe busy, VALU instructions                                                        profiles/TAG_<config>_sq_pmc.csv
   HBM traffic per layer launch, measured / algorithmic                                       profiles/TAG_<config>_traffic.json
-  the driver's command                                                                       profiles/TAG_bench_default.json"""
+  the full line of the default workload (`python bench.py --full`)                          profiles/TAG_bench_default.json"""
 import csv
 import json
 import os
@@ -49,7 +49,7 @@ def table(tag):
         dk = [x for x in csv.DictReader(ln for ln in fh if not ln.startswith("#")) if any(n in x["Name"] for n in RECURRENT)]
     dk = max(dk, key=lambda x: float(x["TotalDurationNs"]))
     out.append("")
-    out.append("The driver's command (`python bench.py`, `profiles/%s_bench_default.json`): **%.1f Msamples/s**, %.3f ms per step, layer launch %.3f ms by HIP events (rocprofv3 `--stats` of the same command, `%s_bench_default_kernel_stats.csv`: %.3f ms over %s calls), `roofline.frac` %.4f, "
+    out.append("The full line of the default workload (`python bench.py --full`, `profiles/%s_bench_default.json`): **%.1f Msamples/s**, %.3f ms per step, layer launch %.3f ms by HIP events (rocprofv3 `--stats` of the same command, `%s_bench_default_kernel_stats.csv`: %.3f ms over %s calls), `roofline.frac` %.4f, "
                "`exposed_ms` %.3f, `decode_hbm` %.0f GB/s, `h2d_inclusive` %.1f, `host_fed` %s Msamples/s (the `flappie` binary from fast5 files of 3500-5500 samples), `length_mix` %s (the same binary on log-normal read lengths, 1000 … 200 000 samples: its steady state by its own time stamps, its padding efficiency), `cpu_baseline` %.3f Msamples/s on %d CPUs (`%s`)."
                % (tag, d["value"], d["ms_per_step"], d["roofline"]["avg_launch_ms"], tag, float(dk["AverageNs"]) / 1e6, dk["Calls"], d["roofline"]["frac"], d["exposed_ms"], d["decode_hbm"]["achieved"],
                   (d.get("h2d_inclusive") or {}).get("value", float("nan")), ("%.1f" % hf["value"]) if hf.get("value") else "-",

@@ -11,8 +11,9 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd /tmp && export TMPDIR=/tmp
 cd "$R"
 O=gpurun_out/profiles; mkdir -p $O
+W=$(dirname $O)          # the run's output directory
 S="--config $cfg --steps ${PROFILE_STEPS:-4} --warmup 2 --inflight 1 --no-cpu-baseline --no-h2d-leg --no-host-fed-leg $*"      # one batch in flight: clean per-kernel times
-python bench.py --config $cfg --no-host-fed-leg "$@" > $O/${tag}_bench.json 2> gpurun_out/${tag}_bench.err || tail -5 gpurun_out/${tag}_bench.err
+python bench.py --full --config $cfg --no-host-fed-leg "$@" > $O/${tag}_bench.json 2> $W/${tag}_bench.err || tail -5 $W/${tag}_bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${tag}_trace -- python bench.py $S > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/prof_${tag}_fetch -- python bench.py $S > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/prof_${tag}_write -- python bench.py $S > /dev/null 2>&1
