@@ -188,7 +188,8 @@ __device__ __forceinline__ void wait_vmcnt_upto(int n) {
 // launches of two batches in flight -- share a CU: four independent 16-read recurrences per CU.  The sweep of h(t-1) lands in
 // LDS (as in the one-tile form at N = 3) one tile after the other through ONE set of accumulators, the recurrent partials are
 // written over the landing zone they came from, the projection partials are single-buffered behind a per-(K quarter, tile)
-// "consumed" flag, and the x waves load x(t+1) just in time (it is L2-warm) instead of a step ahead across the gate phase.
+// "consumed" flag, and the x waves load x(t+1) (it is L2-warm) in pieces of one (tile, chunk) through two register buffers, the first
+// piece of the next step in flight across the gate phase (LSTM at N = 3, round 7; the N = 2 dense forms: a whole tile just in time).
 // PACK (GRUmod, H = 256, dense): the cell has three gates, and a unit tile of 4 units x 4 rows carries an empty row per unit -- a quarter of the
 // MFMAs of both products.  Here a member owns 16 units (groups of 16) as THREE gate-major row tiles (z, r, candidate; no empty rows); inside a
 // tile row 4 q + c is unit 4 c + q, so that lane (q, read) of a tile's accumulator holds units q, 4 + q, 8 + q, 12 + q in its components: gate wave
@@ -578,9 +579,9 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
     // The two roles run their own step loop (two barriers per step each), so that the register allocator sees each
     // role's live ranges alone.
     if (xw && DN) {
-        // ---- x waves, dense form: per step and tile -- load x(step i+1) of my K quarter (24 registers; an L2 hit: the group touched
-        // these lines three steps ago), project, wait until h wave kw has taken the previous partial of that tile (it always has), write
-        // the new one.  Nothing is in flight across the gate phase, where x waves 0-3 work gate tiles 4 and 5.
+        // ---- x waves, dense form: per step and tile -- load x(step i+1) of my K quarter (an L2 hit: the group touched these lines three
+        // steps ago), project, wait until h wave kw has taken the previous partial of that tile (it always has), write the new one.
+        // x comes a whole tile at a time (24 registers) in the N = 2 forms; in pieces (XP below) in the packed forms and at N = 3.
         if constexpr (DN) {
         v4u xb[N][NS];
         auto load_x_tile = [&](int i, int ts) {
@@ -597,6 +598,11 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
         // pieces of the NEXT step that leave behind the last MFMAs of this one, in flight across the gate phase: both where the registers
         // are there (GRUmod: 124), the first one otherwise (the LSTM form spills 9 registers with both)
         constexpr int XPRE = KIND == 1 ? 2 : 1;
+        // XP: x(t) in pieces through two buffers -- the packed forms, and (round 7) the LSTM pair form at H = 384 (N = 3), whose x waves loaded a
+        // whole tile of x before its first MFMA: two exposed L2 round trips a step, and the h waves waited 2700 of 10 100 cycles at barrier 1 for
+        // them.  In pieces: x waves' matrix phase 7050 -> 5550 cycles, the step 10 100 -> 8900, c2 +4.7 % (profiles/r07_phases_*.txt).  One
+        // piece across the gate phase (two: 8 spilled registers); same products in the same order, bit-identical.
+        constexpr bool XP = PACK || (KIND == 0 && N == 3);
         v4u xq[2][NS];
         auto ldq = [&](int i, int k, v4u (&dst)[NS]) {      // piece k = (tile, chunk) of x(step i)
             const int ts = (k / N < ntl) ? k / N : 0, cc = k % N;
@@ -606,7 +612,7 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
         };
         auto project_step = [&](int i, int want) {           // x(step i) of both tiles -> px[0][kw][*]; want = the step (+1) whose partials must have been consumed (0: none)
             v4f acc[TS][NRT];
-            if constexpr (PACK) {
+            if constexpr (XP) {
                 // x(t) of the four (tile, chunk) pieces through TWO 8-register buffers, the load of piece k + 2 issued behind the MFMAs of piece k: two exposed L2
                 // round trips a step instead of four (the x waves closed every step of this form: the h waves waited 2960 of 11 640 cycles for them,
                 // profiles/r05_phases.txt).  An absent second tile re-reads the first and its products are dropped: the outstanding-load count stays static.
@@ -661,14 +667,14 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
         unsigned touched = 0, sink = 0;
         auto touch_x = [&](int i) {                          // L2 warming, spread over the group (see the classic loop below)
             unsigned lt = (unsigned)lane;
-            if constexpr (PACK && KIND == 0) asm volatile("" : "+v"(lt));      // (an opaque copy: no 64-bit lane address held -- spilled -- across the step)
+            if constexpr (XP && KIND == 0) asm volatile("" : "+v"(lt));      // (an opaque copy: no 64-bit lane address held -- spilled -- across the step)
             const int line = m * LPM + (int)lt;
             unsigned t = 0;
             if (wave == 3 && lane < LPM && line < ntl * Hc * NS * 8 && i < Tb)
                 t = *(const unsigned *)(tile_ptr(a.xin, step_t(i), 0) + (size_t)line * 128);
             touched = t;
         };
-        if constexpr (PACK) { if constexpr (XPRE >= 1) ldq(0, 0, xq[0]); if constexpr (XPRE >= 2) ldq(0, 1, xq[1]); }
+        if constexpr (XP) { if constexpr (XPRE >= 1) ldq(0, 0, xq[0]); if constexpr (XPRE >= 2) ldq(0, 1, xq[1]); }
         project_step(0, 0);
         touch_x(1);
         sink ^= touched;
