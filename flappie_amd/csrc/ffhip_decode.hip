@@ -9,7 +9,7 @@
 //   k_viterbi8x<1>               decode_crf_runlength (decode.c:927-1013)
 //
 // Both are recursions over the blocks of one read, one wavefront per read and direction: what bounds them is the dependent chain
-// of one block, not bytes or flops.  Round 2's kernels in ffhip_kernels.hip (k_crf_chain8, k_transpost8, k_viterbi8) hold the 40
+// of one block, not bytes or flops.  Round 2's kernels in ffhip_kernels.hip (k_crf_chain8, k_transpost8, the retired k_viterbi8) hold the 40
 // transition entries of a block one per lane, reduce per destination state with DPP moves and then GATHER the new state vector
 // back to the entries' source lanes with a ds_bpermute (an LDS-crossbar round trip) -- every block.  Here the 8 x 8 (to, from)
 // square of a block covers the 64 lanes and the lane <-> entry map ALTERNATES between blocks:

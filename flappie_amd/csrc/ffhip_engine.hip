@@ -84,26 +84,16 @@ static int gate_level(unsigned flags) {
 
 // ---- development switches: FFHIP_DEBUG=token[,token=value ...] (ffhip_internal.hpp) ---------------------------
 namespace ffhip {
+// every token the library reads: a script that still sets a retired one (decode_r2, conv_ws, ...: tools/dev/experiments/README.md) is told so
+// instead of comparing the default with itself (tests/test_cabi_and_model.py checks this list against the dbg() calls and INTEGRATION.md)
+static const char *const kDebugTokens[] = { "blocking_sync", "crf_logspace", "exact_order", "force_abort", "front_order", "no_dense", "no_fuse",
+                                            "no_pack", "no_pair", "no_split", "no_split_conv", "no_split_head", "pack_first_fit", "streams" };
 const char *dbg(const char *token) {
     static std::mutex mu;
     static std::string seen;                                  // the variable's text the table below was built from
     static std::vector<std::pair<std::string, std::string>> table;
+    static std::vector<std::string> warned;                   // unknown tokens reported so far
     std::lock_guard<std::mutex> lock(mu);                     // (getenv inside: a test's setenv in another thread must not race the read)
-    static bool legacy_checked = false;
-    if (!legacy_checked) {
-        // rounds 1-4 had one variable per switch; a script that still sets one now compares the default with itself -- say so, once
-        legacy_checked = true;
-        static const char *const legacy[] = { "FFHIP_NO_SPLIT_HEAD", "FFHIP_CONV_WS", "FFHIP_CONV_SMALL_U", "FFHIP_STREAMS", "FFHIP_FRONT_ORDER", "FFHIP_NO_DECODE_WAIT",
-            "FFHIP_CONV1_TN", "FFHIP_NO_PACK", "FFHIP_NO_SPLIT", "FFHIP_NO_FUSE", "FFHIP_NO_PAIR", "FFHIP_NO_DENSE", "FFHIP_PERSIST_MODE", "FFHIP_LEAN_CONV",
-            "FFHIP_NO_SPLIT_CONV", "FFHIP_NO_BATCH_ORDER", "FFHIP_CRF_LOGSPACE", "FFHIP_DECODE_R2", "FFHIP_EXACT_ORDER", "FFHIP_CRF_GENERIC", "FFHIP_SPLIT_TS",
-            "FFHIP_SPLIT_DENSE", "FFHIP_DENSE256", "FFHIP_NO_SPLIT_GATE", "FFHIP_NO_HEAD_EXP", "FFHIP_FORCE_ABORT" };
-        for (const char *name : legacy)
-            if (getenv(name)) {
-                std::string tok(name + 6);
-                for (auto &c : tok) c = (char)tolower((unsigned char)c);
-                fprintf(stderr, "libffhip: %s is no longer read (one variable since round 5: FFHIP_DEBUG=%s[=value], INTEGRATION.md section 6)\n", name, tok.c_str());
-            }
-    }
     const char *e = getenv("FFHIP_DEBUG");
     if (!e || !e[0]) return nullptr;
     if (seen != e) {                                          // (tests change the variable between runs of one process)
@@ -117,6 +107,11 @@ const char *dbg(const char *token) {
                 const std::string item = seen.substr(i, j - i);
                 const size_t eq = item.find('=');
                 t.emplace_back(eq == std::string::npos ? item : item.substr(0, eq), eq == std::string::npos ? std::string() : item.substr(eq + 1));
+                const std::string &tok = t.back().first;
+                if (std::find(std::begin(kDebugTokens), std::end(kDebugTokens), tok) == std::end(kDebugTokens) && std::find(warned.begin(), warned.end(), tok) == warned.end()) {
+                    warned.push_back(tok);
+                    fprintf(stderr, "libffhip: FFHIP_DEBUG token '%s' is not read by this library (INTEGRATION.md section 6 lists the tokens)\n", tok.c_str());
+                }
             }
             i = j + 1;
         }
@@ -613,6 +608,59 @@ extern "C" size_t ffhip_model_nblock(const ffhip_model *m, size_t nsample) {
     return n;
 }
 
+// ------------------------------------------------------------------------------------ a run's path
+// Decided in two places only: model_path (what the default path, packed batches and paired layer launches need of the model and the run's flags)
+// and plan_run (the whole path of a run, once, at its front).  What the engine is doing -- batches in flight, its last layer launch -- is an input
+// of neither: those decisions stay where they fall in the enqueue sequence (run_front, run_layers, ffhip_batch_run_pair).
+static bool flipflop8_10(const ffhip_model *m) { return (m->nbase == 4 && m->Ps == 40) || (m->nbase == 5 && m->Ps == 60); }
+// split: the split-operand layer kernel with the fused projection (ffhip_rnn_split.hip), the default wherever it exists; packable: ... and a packed batch may take
+// the run at an ordinary temperature (RunPath::post_done); pairable: ... and two batches of pair_tiles read tiles each may share layer launches (split_pair_ok)
+struct ModelPath { bool split, packable, pairable; };
+static ModelPath model_path(const ffhip_model *m, unsigned flags, int ncu, int pair_tiles = 0) {
+    ModelPath p;
+    p.split = !(flags & (FFHIP_RUN_STEPWISE_RNN | FFHIP_RUN_UNFUSED_RNN | FFHIP_RUN_F32_RNN)) && persist_supported(m->cell, m->Hp, ncu) &&
+              split_supported(m->cell, m->Hp) && m->rnn[0].Wsplit != nullptr && !dbg("no_split") && !dbg("no_fuse");
+    const bool lean = p.split && !(flags & FFHIP_RUN_KEEP_ACTS);
+    p.packable = lean && m->conv[m->nconv - 1].Mpad == m->Hp && m->kind != FFHIP_NET_LSTM5_RLE && flipflop8_10(m);
+    p.pairable = lean && split_pair_ok(m->cell, m->Hp, pair_tiles, ncu);
+    return p;
+}
+struct RunPath {
+    bool keep = false, persist = false, fused = false;           // FFHIP_RUN_KEEP_ACTS; one launch per layer (and chunk of read tiles); the f32 layer kernel with the projection inside
+    bool proj_split = false, split = false, split2 = false;      // projections on split operands; ModelPath::split; H = 512 (and FFHIP_RUN_UNFUSED_RNN at H = 256):
+                                                                 // projection GEMM + recurrence-only layer kernel, both on split operands
+    bool conv_split = false, conv_f16 = false;                   // the last convolution writes the split layout / runs on split operands (its predecessor writes fp16 slices)
+    bool split_head = false, packable = false;                   // the CRF head reads the last layer's split output (k_head_split: no fp32 copy of it); a packed batch may take the run
+    bool post_done = false, head_e = false, rle_post8 = false;   // 8- / 10-state flip-flop models, a block's scores spanning at most kFbRange: ONE pair of fp64 linear-space chains
+                                                                 // per read gives logZ, the normalised scores and the posterior (k_crf_fb); head_e: their input exp(S - block max)
+                                                                 // comes from the split head's epilogue; rle_post8: the run-length model's posterior from such chains (k_rle_post8)
+    int R = 0, gates = 2, persist_mode = 0, rnn_path = 0;       // rescaling interval of the linear-space CRF normalisation (0: log space); gate_level; hand-off of the persistent
+                                                                 // layer kernels (0: write-through where a group spans XCDs); ffhip_batch_rnn_path
+};
+static RunPath plan_run(const ffhip_model *m, unsigned flags, float temperature, int ncu) {
+    const int Hp = m->Hp;
+    const ModelPath mp = model_path(m, flags, ncu);
+    RunPath p;
+    p.keep = (flags & FFHIP_RUN_KEEP_ACTS) != 0;
+    p.persist = !(flags & FFHIP_RUN_STEPWISE_RNN) && persist_supported(m->cell, Hp, ncu);
+    p.fused = !(flags & FFHIP_RUN_UNFUSED_RNN) && !dbg("no_fuse") && fused_supported(m->cell, Hp);
+    p.proj_split = !(flags & FFHIP_RUN_F32_RNN) && !dbg("no_split");
+    p.split = mp.split;
+    p.split2 = !p.split && p.persist && p.proj_split && rnn_split_supported(m->cell, Hp) && m->rnn[0].Wsplit != nullptr;
+    p.conv_split = (p.split || p.split2) && !p.keep && m->conv[m->nconv - 1].Mpad == Hp;
+    p.conv_f16 = m->conv[m->nconv - 1].Wsplit != nullptr && !dbg("no_split_conv") && !(flags & FFHIP_RUN_F32_RNN);
+    p.split_head = p.split && !p.keep && m->FFsplit != nullptr && !dbg("no_split_head");
+    // |score| <= 5/temperature (tanh bounded by 1): picks the rescaling interval of the linear-space form
+    p.R = dbg("crf_logspace") ? 0 : crf_rescale_interval(5.0f / temperature);
+    p.post_done = m->kind != FFHIP_NET_LSTM5_RLE && p.R > 0 && flipflop8_10(m) && 10.0f / temperature <= kFbRange;
+    p.head_e = p.split_head && p.post_done && head_split_writes_E(m->P);
+    p.rle_post8 = m->kind == FFHIP_NET_LSTM5_RLE && m->nbase == 4 && m->Ps == 40 && 10.0f / temperature <= kFbRange;
+    p.packable = mp.packable && p.post_done;
+    p.gates = gate_level(flags);
+    p.rnn_path = p.split ? 3 : (p.split2 ? 4 : (p.persist ? (p.fused ? 2 : 1) : 0));
+    return p;
+}
+
 // ------------------------------------------------------------------------------------ batch
 struct ConvPlan { int Tin = 0, Tout = 0; int *x0a = nullptr, *x0b = nullptr; };
 
@@ -695,6 +743,7 @@ struct ffhip_batch {
     float last_temperature = 1.0f;
     int ran = 0, finished = 0;
     int final_act = 0;                  // which act[] holds the last recurrent layer's output
+    RunPath run_path;                   // the run's path, decided at its front (plan_run)
     int rnn_path = 0;                   // what the last run used: 0 launch per step, 1 persistent recurrence behind a projection GEMM, 2 fused f32 layer kernel, 3 split-operand layer kernel, 4 split-operand projection GEMM + recurrence-only layer kernel
     hipEvent_t ev[FFHIP_NGROUP + 1];
     int have_ev = 0;
@@ -707,7 +756,6 @@ struct ffhip_batch {
     ffhip_batch *prof_mate = nullptr;   // second batch of a profiled pair: the batch whose lev[][] events bracket the paired launches (two event records
                                         // per launch instead of six: each is a packet between two layer launches, ~5 us of idle chip)
     ffhip_batch *prof_ref = nullptr;    // ... and the first batch's way back, so that either can go first
-    int pair_front = 0;                 // set by ffhip_batch_run_pair around the front phase: the layers to come are a paired (chip-filling) launch
     int profiled = 0;
 };
 
@@ -872,13 +920,12 @@ extern "C" int ffhip_batch_nreads(const ffhip_batch *b) { return b ? batch_nread
 static inline size_t read_row0(const ffhip_batch *b, int read) { return b->packed ? (size_t)b->v_slot[read] * b->Tb + b->v_off[read] : (size_t)read * b->Tb; }
 static inline size_t read_row1(const ffhip_batch *b, int read) { return b->packed ? (size_t)b->v_slot[read] * (b->Tb + 1) + b->v_off[read] : (size_t)read * (b->Tb + 1); }
 static int total_stride(const ffhip_model *m) { int st = 1; for (int l = 0; l < m->nconv; l++) st *= m->conv[l].stride; return st; }
-// does this model's default path take packed batches?  (what batch_run_impl asks of a packed batch, on the model's side)
+// does this model's default path take packed batches?  (what a packed batch's run asks of the model: model_path)
 extern "C" int ffhip_model_packable(const ffhip_model *m) {
-    if (!m || m->kind == FFHIP_NET_LSTM5_RLE || !((m->nbase == 4 && m->Ps == 40) || (m->nbase == 5 && m->Ps == 60))) return 0;
+    if (!m) return 0;
     int ncu = 256, dev = 0;
     if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    return (persist_supported(m->cell, m->Hp, ncu) && split_supported(m->cell, m->Hp) && m->rnn[0].Wsplit != nullptr && m->conv[m->nconv - 1].Mpad == m->Hp &&
-            !dbg("no_split") && !dbg("no_fuse")) ? 1 : 0;
+    return model_path(m, 0, ncu).packable ? 1 : 0;
 }
 // Blocks that stay free behind every read of a packed slot: the widest convolution window of the model either side of a read must see the zero padding the
 // reference gives it (layers.c:216-271), in every layer's coordinates, and the dead block behind a read is the next one's zero recurrent state.
@@ -891,7 +938,7 @@ extern "C" size_t ffhip_model_pack_gap(const ffhip_model *m) {
 }
 // Rows (a multiple of 16, at most want_rows) of a packed batch of `nsample`-sample rows whose workspace takes at most 72 % / nobjects of the device's memory (512 rows of 228 352 samples at 384 hidden units: 103 GB of 288):
 // `nobjects` such objects are alive in a pipeline (two: one runs, one is set up; one: the caller collects a batch before it sets up the next) beside the prepared signals.  What a row costs is what batch_create_impl and the default path of
-// batch_run_impl allocate per block and per sample.
+// a run allocate per block and per sample.
 extern "C" int ffhip_pack_rows_for(const ffhip_model *m, int want_rows, size_t nsample, int nobjects) {
     if (!m || want_rows <= 0 || nsample == 0 || nobjects < 1) return 0;
     const size_t nb = ffhip_model_nblock(m, nsample) + 1;
@@ -1069,8 +1116,7 @@ static int apply_packed(ffhip_batch *b, int nv, const std::vector<int> &lens, co
     if (b->eng->persist_chained) HIP_TRY(hipStreamWaitEvent(b->stream, b->eng->persist_done, 0), FFHIP_EHIP);
     // ... and behind the CRF head of the packed batch that ran last (round 6, third session): the head is a throughput kernel (12 ms alone for a 100 M-sample batch) that k_conv_split_ws
     // beside it stretches to 47 ms, and the chains wait for it -- with the head first they run under the convolutions instead of behind them (profiles/r06_pack_trace.txt).
-    // FFHIP_DEBUG=no_pack_behind_head: both start with the gap.
-    if (b->eng->head_done_rec && !dbg("no_pack_behind_head")) HIP_TRY(hipStreamWaitEvent(b->stream, b->eng->head_done, 0), FFHIP_EHIP);
+    if (b->eng->head_done_rec) HIP_TRY(hipStreamWaitEvent(b->stream, b->eng->head_done, 0), FFHIP_EHIP);
     std::vector<int> cur(lens);
     int nstrided = 0;
     for (int l = 0; l < nconv; l++) {
@@ -1334,307 +1380,271 @@ extern "C" int ffhip_batch_set_prepared_packed(ffhip_batch *b, const ffhip_prep 
     return FFHIP_OK;
 }
 
-static void mark(ffhip_batch *b, int i) {
-    if (b->eng->profiling) hipEventRecord(b->ev[i], b->stream);
+static void mark(ffhip_batch *b, int i) { if (b->eng->profiling) hipEventRecord(b->ev[i], b->stream); }
+
+// The chaining of layer launches: every workgroup of a persistent layer launch must be resident, so a launch follows the engine's last one
+// unless both are half-chip ones (`chain` false: a twin of its size fits beside it) -- then they run beside each other.
+static int layer_wait(ffhip_engine *e, hipStream_t s, bool chain) {
+    if (e->persist_chained && (chain || !e->persist_last_half)) HIP_TRY(hipStreamWaitEvent(s, e->persist_done, 0), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+static int layer_launched(ffhip_engine *e, hipStream_t s, bool chain) {
+    HIP_TRY(hipEventRecord(e->persist_done, s), FFHIP_EHIP);
+    e->persist_chained = 1; e->persist_last_half = chain ? 0 : 1;
+    return FFHIP_OK;
+}
+
+// FFHIP_RUN_KEEP_ACTS: the fp32 activations after the convolutions (slot 0) and after every layer
+static int keep_copy(ffhip_batch *b, int slot, const float *src) {
+    if (!b->run_path.keep) return FFHIP_OK;
+    const size_t bytes = (size_t)b->Tb * b->Bp * b->mdl->Hp * 4;
+    if (!b->keep[slot] && !(b->keep[slot] = (float *)dalloc(b, bytes, false))) return FFHIP_ENOMEM;
+    HIP_TRY(hipMemcpyAsync(b->keep[slot], src, bytes, hipMemcpyDeviceToDevice, b->stream), FFHIP_EHIP);
+    return FFHIP_OK;
 }
 
 // One run of a batch is enqueued in three phases -- front (convolutions), the recurrent stack, back (head, CRF, decode) -- so that
-// ffhip_batch_run_pair can put the layer launches of TWO batches into one grid between their fronts and backs.
-enum { PH_FRONT = 1, PH_LAYERS = 2, PH_BACK = 4, PH_ALL = 7 };
-static int batch_run_impl(ffhip_batch *b, float temperature, unsigned flags, int phases) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+// ffhip_batch_run_pair can put the layer launches of TWO batches into one grid between their fronts and backs (`paired`).  The front
+// decides the run's path (b->run_path); the layers and the back follow it.
+static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool paired) {
     const ffhip_model *m = b->mdl;
-    hipSetDevice(b->eng->device);
+    ffhip_engine *eng = b->eng;
     hipStream_t s = b->stream;
-    const int Tb = b->Tb, B16 = b->B16, Bp = b->Bp, Hp = m->Hp;
-    if (phases & PH_FRONT) {
-        if (b->eng->stepwise_batches > 0 && !(flags & FFHIP_RUN_STEPWISE_RNN)) {      // a co-tenant was seen recently (ffhip_batch_finish)
-            flags |= FFHIP_RUN_STEPWISE_RNN;
-            b->eng->stepwise_batches--;
-        }
-        b->run_flags = flags;
-        b->last_temperature = temperature;
-        memset(b->launches, 0, sizeof(b->launches));
-    } else {
-        flags = b->run_flags;
-        temperature = b->last_temperature;
+    const int Tb = b->Tb, B16 = b->B16, Bp = b->Bp, Hp = m->Hp, ncu = eng->prop.multiProcessorCount;
+    if (eng->stepwise_batches > 0 && !(flags & FFHIP_RUN_STEPWISE_RNN)) {      // a co-tenant was seen recently (ffhip_batch_finish)
+        flags |= FFHIP_RUN_STEPWISE_RNN;
+        eng->stepwise_batches--;
     }
-    const bool keep = (flags & FFHIP_RUN_KEEP_ACTS) != 0;
-    const int *tbs = b->ragged ? b->d_tbs : nullptr, *tbt = b->ragged ? b->d_tbt : nullptr;      // ragged batch: per-read / per-tile block counts
-    // packed batch: tbs / tbt above are the ROWS' extents (what the layer kernels walk); the per-read kernels take the reads' own tables
-    const int nR = b->packed ? b->nvirt : b->nread;
-    const int *tbr = b->packed ? b->d_vtb : tbs;
-    ReadMap rmap;
-    if (b->packed) { rmap.b0 = b->d_vb0; rmap.b1 = b->d_vb1; rmap.nslot = b->nread; }
-    const unsigned *live = b->packed ? b->d_live : nullptr;
-    auto keep_copy = [&](int slot, const float *src) -> int {
-        if (!keep) return FFHIP_OK;
-        if (!b->keep[slot] && !(b->keep[slot] = (float *)dalloc(b, (size_t)Tb * Bp * Hp * 4, false))) return FFHIP_ENOMEM;
-        HIP_TRY(hipMemcpyAsync(b->keep[slot], src, (size_t)Tb * Bp * Hp * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-        return FFHIP_OK;
-    };
-
-    // split-operand layer kernel (ffhip_rnn_split.hip): the default wherever it exists (LSTM H = 128..512, GRUmod H = 128..384)
-    const bool use_persist = !(flags & FFHIP_RUN_STEPWISE_RNN) && persist_supported(m->cell, Hp, b->eng->prop.multiProcessorCount);
-    const bool use_fused = !(flags & FFHIP_RUN_UNFUSED_RNN) && !dbg("no_fuse") && fused_supported(m->cell, Hp);
-    const bool want_fused = !(flags & FFHIP_RUN_UNFUSED_RNN) && !dbg("no_fuse");      // (use_fused also asks whether the f32 layer kernel takes the shape)
-    const bool use_split = use_persist && want_fused && !(flags & FFHIP_RUN_F32_RNN) && !dbg("no_split") &&
-                           split_supported(m->cell, Hp) && m->rnn[0].Wsplit != nullptr;
-    // shapes whose two weight matrices do not fit a CU's registers (H = 512): projection GEMM + recurrence-only layer kernel, both
-    // on split operands (also what FFHIP_RUN_UNFUSED_RNN selects at H = 256)
-    const bool use_split2 = !use_split && use_persist && !(flags & FFHIP_RUN_F32_RNN) && !dbg("no_split") &&
-                            rnn_split_supported(m->cell, Hp) && m->rnn[0].Wsplit != nullptr;
-    // the last convolution writes the split layout directly unless the fp32 activations are wanted as well
-    const bool conv_split = (use_split || use_split2) && !keep && m->conv[m->nconv - 1].Mpad == Hp;
-    // the CRF head reads the last layer's SPLIT output (k_head_split): that layer then writes no fp32 copy (315 MB per headline batch, ~65 us of
-    // its launch) and the batch needs no fp32 activation buffer at all (FFHIP_NO_SPLIT_HEAD: the f32-MFMA head on the fp32 copy)
-    const bool split_head = use_split && !keep && m->FFsplit != nullptr && !dbg("no_split_head");
-    const bool prof = b->eng->profiling != 0;
-    const int fast_gates = gate_level(flags);
-    const char *pm_env = dbg("persist_mode");      // 1 = always use the write-through hand-off
-    const int persist_mode = pm_env ? atoi(pm_env) : 0;
-    // A packed batch runs on the default path only: the split layer kernels know the live mask, the chain / Viterbi / assembly / trace kernels the read map
-    if (b->packed && !(use_split && conv_split && !keep && m->kind != FFHIP_NET_LSTM5_RLE && ((m->nbase == 4 && m->Ps == 40) || (m->nbase == 5 && m->Ps == 60)) &&
-                       !dbg("decode_r2") && !dbg("crf_logspace") && 10.0f / temperature <= kFbRange && crf_rescale_interval(5.0f / temperature) > 0))
+    b->run_flags = flags; b->last_temperature = temperature;
+    memset(b->launches, 0, sizeof(b->launches));
+    b->run_path = plan_run(m, flags, temperature, ncu);
+    const RunPath &p = b->run_path;
+    if (b->packed && !p.packable)
         return set_err(FFHIP_EINVAL, "packed batches take the default path only (flip-flop model with 128 .. 512 hidden units, no kept activations, no f32 / stepwise / unfused flags, ordinary temperature)");
-    int cur = b->run_cur;
-    {
-        const bool need0 = !conv_split;           // the convolution's fp32 output (every path but split layers behind a split-writing convolution)
-        for (int i = need0 ? 0 : 1; i < ((split_head && !need0) ? 1 : 2); i++)      // (act[1]: the last layer's fp32 copy for the f32 head)
-            if (!b->act[i] && !(b->act[i] = (float *)dalloc(b, (size_t)Tb * Bp * Hp * 4, false))) return FFHIP_ENOMEM;
-    }
-  if (phases & PH_FRONT) {
-    if (use_split || use_split2) {
+    // act[0]: the convolution's fp32 output (every path but split layers behind a split-writing convolution); act[1]: the last layer's fp32 copy for the f32 head
+    for (int i = p.conv_split ? 1 : 0; i < ((p.split_head && p.conv_split) ? 1 : 2); i++)
+        if (!b->act[i] && !(b->act[i] = (float *)dalloc(b, (size_t)Tb * Bp * Hp * 4, false))) return FFHIP_ENOMEM;
+    if (p.split || p.split2) {
         const size_t bytes = split_bytes((size_t)Tb * B16, Hp);
         for (int i = 0; i < 2; i++)
             if (!b->actS[i] && !(b->actS[i] = dalloc(b, bytes, false))) return FFHIP_ENOMEM;
     }
     // ---- convolutions (layers.c:189-276, activations :24-49)
-    // the last convolution runs on split operands when the model has them (16 input features): its predecessor then writes fp16 slices
-    const bool conv_f16 = m->conv[m->nconv - 1].Wsplit != nullptr && !dbg("no_split_conv") && !(flags & FFHIP_RUN_F32_RNN);
     // another batch is between run and finish: its layer launches hold 384 of every SIMD's 512 registers, so this batch's last
-    // convolution takes the shape that fits in what is left (FFHIP_LEAN_CONV=0 / 1 forces one)
-    const char *lean_env = dbg("lean_conv");
+    // convolution takes the shape that fits in what is left ...
     // ... unless this batch's own layer launches fill the chip (a paired launch; a full launch of the dense forms; H = 512): the layer
     // launches of whatever else is in flight do too, the convolution only ever shares the chip with other batches' convolutions and
     // decodes, and the fat shape is the faster one there (in pairs at H = 384: 0.98 -> 0.6 ms per batch)
-    bool full_chip = b->pair_front != 0 || use_split2;
-    if (use_split && !full_chip) {
-        const int ncu_ = b->eng->prop.multiProcessorCount, beside_ = (b->eng->in_flight - (b->counted ? 1 : 0) > 0) ? 1 : 0;
-        const int nrt_ = split_next_launch_tiles(m->cell, Hp, B16, ncu_);
-        full_chip = 2 * split_launch_workgroups(m->cell, Hp, nrt_, ncu_, beside_) > ncu_ * split_workgroups_per_cu(m->cell, Hp, nrt_, ncu_, beside_);
+    bool full_chip = paired || p.split2;
+    if (p.split && !full_chip) {
+        const int beside_ = (eng->in_flight - (b->counted ? 1 : 0) > 0) ? 1 : 0;
+        const int nrt_ = split_next_launch_tiles(m->cell, Hp, B16, ncu);
+        full_chip = 2 * split_launch_workgroups(m->cell, Hp, nrt_, ncu, beside_) > ncu * split_workgroups_per_cu(m->cell, Hp, nrt_, ncu, beside_);
     }
-    const int lean_conv = lean_env ? (lean_env[0] == '1') : (!full_chip && b->eng->in_flight - (b->counted ? 1 : 0) > 0);
+    const int lean_conv = !full_chip && eng->in_flight - (b->counted ? 1 : 0) > 0;
     // Whole batches one after the other when this batch's layer launches fill the chip and it is not half of a pair: its convolutions
     // would otherwise run beside the other batch's layer launches, whose workgroups then wait for slots (h256 with two 768-read batches
     // in flight: 160 against 179 Msamples/s one at a time; c4: 65.5 against 75).  The host side still overlaps: this only orders the GPU.
     // Round 4: the order is taken from the other batch's LAST LAYER LAUNCH instead of its last kernel -- this batch's convolutions then run
     // beside that batch's head and decode (dependent chains of one wave a read: they leave the chip nearly empty), and a pair's front, on
     // streams of its own (the engine hands out four), no longer queues behind the previous pair's decode: between two pairs' layer launches
-    // 1.33 ms of head + decode + copies + convolutions one after the other became max(...) of the two sides.  FFHIP_FRONT_ORDER=batch: round 3's.
+    // 1.33 ms of head + decode + copies + convolutions one after the other became max(...) of the two sides.  front_order=batch: round 3's.
     const char *fo = dbg("front_order");
-    if (dbg("no_batch_order")) fo = "none";
     const bool by_layers = !fo || fo[0] == 'l';
-    {
-        if (full_chip && by_layers && b->eng->persist_chained) HIP_TRY(hipStreamWaitEvent(s, b->eng->persist_done, 0), FFHIP_EHIP);
-        else if (full_chip && !by_layers && fo[0] == 'b' && !b->pair_front && b->eng->batch_done_rec) HIP_TRY(hipStreamWaitEvent(s, b->eng->batch_done, 0), FFHIP_EHIP);
-    }
+    if (full_chip && by_layers && eng->persist_chained) HIP_TRY(hipStreamWaitEvent(s, eng->persist_done, 0), FFHIP_EHIP);
+    else if (full_chip && !by_layers && fo[0] == 'b' && !paired && eng->batch_done_rec) HIP_TRY(hipStreamWaitEvent(s, eng->batch_done, 0), FFHIP_EHIP);
     mark(b, 0);                                        // (behind the wait: the convolution group's time is its kernels')
     HIP_TRY(hipMemsetAsync(b->sat, 0, (size_t)Bp * sizeof(unsigned), s), FFHIP_EHIP);
     for (int l = 0; l < m->nconv; l++) {
         const ConvDev &c = m->conv[l];
-        if (l < m->nconv - 1) {
-            launch_conv_small(s, b->sbuf[l], b->sbuf[l + 1], c.taps, c.bias, b->ragged ? b->rag_x0a[l] : b->plan[l].x0a,
-                              b->ragged ? b->rag_x0b[l] : b->plan[l].x0b, Bp, b->plan[l].Tout, c.winlen, m->act, b->ragged ? b->plan[l].Tout : 0,
-                              (b->ragged && !b->packed) ? b->rag_tin[l] : nullptr, (conv_f16 && l == m->nconv - 2) ? kSplitExpX : -100000, b->sat,
-                              (b->packed && m->conv[l].stride == 1) ? b->rag_seg[l] : nullptr);
-        } else if (conv_f16) {
-            launch_conv_split(s, b->sbuf[l], b->act[0], c.Wsplit, c.bias, b->ragged ? b->rag_x0a[l] : b->plan[l].x0a,
-                              b->ragged ? b->rag_x0b[l] : b->plan[l].x0b, B16, Tb, c.Mpad, c.winlen, m->act, b->ragged ? b->plan[l].Tout : 0,
-                              conv_split ? b->actS[0] : nullptr, kSplitExpX, c.split_S, lean_conv, b->sat);
-        } else {
-            launch_conv_mfma(s, b->sbuf[l], b->act[0], c.Wp, c.bias, b->ragged ? b->rag_x0a[l] : b->plan[l].x0a,
-                             b->ragged ? b->rag_x0b[l] : b->plan[l].x0b, B16, Tb, c.Mpad, c.K16, m->act, b->ragged ? b->plan[l].Tout : 0,
-                             conv_split ? b->actS[0] : nullptr, m->act == ACT_SWISH ? kSplitExpX : kSplitExpH, b->sat);
-        }
+        const int *x0a = b->ragged ? b->rag_x0a[l] : b->plan[l].x0a, *x0b = b->ragged ? b->rag_x0b[l] : b->plan[l].x0b, ldp = b->ragged ? b->plan[l].Tout : 0;
+        if (l < m->nconv - 1)
+            launch_conv_small(s, b->sbuf[l], b->sbuf[l + 1], c.taps, c.bias, x0a, x0b, Bp, b->plan[l].Tout, c.winlen, m->act, ldp, (b->ragged && !b->packed) ? b->rag_tin[l] : nullptr,
+                              (p.conv_f16 && l == m->nconv - 2) ? kSplitExpX : -100000, b->sat, (b->packed && m->conv[l].stride == 1) ? b->rag_seg[l] : nullptr);
+        else if (p.conv_f16)
+            launch_conv_split(s, b->sbuf[l], b->act[0], c.Wsplit, c.bias, x0a, x0b, B16, Tb, c.Mpad, c.winlen, m->act, ldp, p.conv_split ? b->actS[0] : nullptr,
+                              kSplitExpX, c.split_S, lean_conv, b->sat);
+        else
+            launch_conv_mfma(s, b->sbuf[l], b->act[0], c.Wp, c.bias, x0a, x0b, B16, Tb, c.Mpad, c.K16, m->act, ldp, p.conv_split ? b->actS[0] : nullptr,
+                             m->act == ACT_SWISH ? kSplitExpX : kSplitExpH, b->sat);
         b->launches[0]++;
     }
-    if (int rc = keep_copy(0, b->act[0])) return rc;
+    if (int rc = keep_copy(b, 0, b->act[0])) return rc;
     mark(b, 1);
-    // ---- recurrent stack: B,F,B,F,B (networks.c:556-580 / :459-483)
-    // profiling groups 1 (in-projection) and 2 (recurrent) interleave; their events bracket the
-    // whole stack and the split is measured with per-layer events when profiling is on.
-    cur = 0;
-    HIP_TRY(hipMemsetAsync(b->pabort, (use_persist && dbg("force_abort")) ? 1 : 0, sizeof(unsigned), s), FFHIP_EHIP);      // (debug: pretend a wait timed out)
-    if ((use_split || use_split2) && !conv_split) {
+    HIP_TRY(hipMemsetAsync(b->pabort, (p.persist && dbg("force_abort")) ? 1 : 0, sizeof(unsigned), s), FFHIP_EHIP);      // (debug: pretend a wait timed out)
+    if ((p.split || p.split2) && !p.conv_split) {
         launch_split_from_f32(s, b->act[0], b->actS[0], (size_t)Tb * B16, Hp, m->act == ACT_SWISH ? kSplitExpX : kSplitExpH, b->sat, B16);
         b->launches[0]++;
     }
-    b->run_cur = cur;
+    b->run_cur = 0;
     // ... and this batch's LAYER launches follow the decode of the batches before it (the last two: a pair): a persistent launch that becomes
     // resident piecemeal beside a running chain of decode kernels squeezes those onto the CUs it has not taken yet and cannot start before
     // they are through (the run-length shape, whose head and decode are the longer side: 88 against 98 Msamples/s without this wait)
-    if (full_chip && by_layers && !dbg("no_decode_wait"))
-        for (unsigned k = 1; k <= 2 && k <= b->eng->done_head; k++) HIP_TRY(hipStreamWaitEvent(s, b->eng->done_ring[(b->eng->done_head - k) & 3u], 0), FFHIP_EHIP);
-  }      // PH_FRONT
-  if (phases & PH_LAYERS) {
+    if (full_chip && by_layers)
+        for (unsigned k = 1; k <= 2 && k <= eng->done_head; k++) HIP_TRY(hipStreamWaitEvent(s, eng->done_ring[(eng->done_head - k) & 3u], 0), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+
+// ---- recurrent stack: B,F,B,F,B (networks.c:556-580 / :459-483).  Profiling groups 1 (in-projection) and 2 (recurrent) interleave:
+// per-layer events split them when profiling is on.
+static int run_layers(ffhip_batch *b) {
+    const ffhip_model *m = b->mdl;
+    ffhip_engine *eng = b->eng;
+    const RunPath &p = b->run_path;
+    hipStream_t s = b->stream;
+    const int Tb = b->Tb, B16 = b->B16, Bp = b->Bp, Hp = m->Hp, ncu = eng->prop.multiProcessorCount;
+    const int *tbs = b->ragged ? b->d_tbs : nullptr, *tbt = b->ragged ? b->d_tbt : nullptr;      // ragged batch: per-read / per-tile block counts (packed: the ROWS' extents)
+    const unsigned *live = b->packed ? b->d_live : nullptr;
+    const bool prof = eng->profiling != 0;
+    int cur = b->run_cur;
     for (int l = 0; l < 5; l++) {
         const RnnDev &r = m->rnn[l];
         const bool backward = (l % 2 == 0);
         float *in = b->act[cur], *out = b->act[cur ^ 1];
-        const bool fuse = use_persist && use_fused;
         if (prof) hipEventRecord(b->lev[l][0], s);
-        if (use_split2) {
+        if (p.split2) {
             if (!b->xa && !(b->xa = (float *)dalloc(b, (size_t)Tb * Bp * Hp * 4 * 4, false))) return FFHIP_ENOMEM;
             launch_inproj_split(s, b->actS[cur], b->xa, r.Wsplit, r.bias, Tb * B16, Hp, r.split_S);
             b->launches[1]++;
             if (prof) hipEventRecord(b->lev[l][1], s);
-            const int maxt = split_max_tiles(b->eng->prop.multiProcessorCount);
-            float *out_f32 = (l == 4 || keep) ? out : nullptr;
+            const int maxt = split_max_tiles(ncu);
+            float *out_f32 = (l == 4 || p.keep) ? out : nullptr;
             for (int rt0 = 0; rt0 < B16; rt0 += maxt) {
                 const int nrt = (B16 - rt0 < maxt) ? B16 - rt0 : maxt;
                 HIP_TRY(hipMemsetAsync(b->pflags, 0, split_flag_words(nrt) * sizeof(unsigned), s), FFHIP_EHIP);
-                const bool chain = 2 * ((B16 + 1) / 2) * 32 > b->eng->prop.multiProcessorCount;
-                if (b->eng->persist_chained && (chain || !b->eng->persist_last_half)) HIP_TRY(hipStreamWaitEvent(s, b->eng->persist_done, 0), FFHIP_EHIP);      // beside another launch only if BOTH are half-chip ones
+                const bool chain = 2 * ((B16 + 1) / 2) * 32 > ncu;
+                if (int rc = layer_wait(eng, s, chain)) return rc;
                 if (!launch_rnn_split(s, r.Wsplit, b->xa, b->actS[cur ^ 1], out_f32, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt,
-                                      backward, persist_mode, r.split_S, tbs, tbt))
+                                      backward, p.persist_mode, r.split_S, tbs, tbt))
                     return set_err(FFHIP_EINVAL, "split recurrent kernel: unsupported shape");
-                { HIP_TRY(hipEventRecord(b->eng->persist_done, s), FFHIP_EHIP); b->eng->persist_chained = 1; b->eng->persist_last_half = chain ? 0 : 1; }
+                if (int rc = layer_launched(eng, s, chain)) return rc;
                 b->launches[2]++;
             }
-            if (prof) hipEventRecord(b->lev[l][2], s);
-            cur ^= 1;
-            if (int rc = keep_copy(l + 1, b->act[cur])) return rc;
-            continue;
-        }
-        if (use_split) {
-            // H <= 256: a launch of the dense form (pairs of tiles, two workgroups per CU) takes twice the tiles; it is used for FULL
-            // launches only -- a partly filled one has a group count that is no multiple of 8 XCDs and loses the one-L2 hand-off
-            const int maxt1 = split_max_tiles(b->eng->prop.multiProcessorCount), maxt2 = split_max_tiles(b->eng->prop.multiProcessorCount, Hp);
+        } else if (p.split) {
             void *outS = b->actS[cur ^ 1];
             // (the output doubles as the hand-off flag; the kernel arms it itself a few steps ahead of its stores -- no fill)
             // the fp32 copy of a layer's output is needed by the CRF head (last layer) and by FFHIP_RUN_KEEP_ACTS
-            float *out_f32 = ((l == 4 && !split_head) || keep) ? out : nullptr;
+            float *out_f32 = ((l == 4 && !p.split_head) || p.keep) ? out : nullptr;
             for (int rt0 = 0, nrt = 0; rt0 < B16; rt0 += nrt) {
-                nrt = split_next_launch_tiles(m->cell, Hp, B16 - rt0, b->eng->prop.multiProcessorCount);
-                (void)maxt1; (void)maxt2;
+                nrt = split_next_launch_tiles(m->cell, Hp, B16 - rt0, ncu);
                 // (the check-in words carry the launch's epoch: no fill between launches)
                 b->split_epoch = (b->split_epoch % 0x3FFFFFFu) + 1u;
-                // two such launches (this batch's and another's in flight) run beside each other only if ALL their workgroups fit on the chip together
-                const int ncu_ = b->eng->prop.multiProcessorCount;
-                // another batch is between run and finish: at H = 384 this batch's launches take the dense form, which fits beside that batch's
-                const int beside = (b->eng->in_flight - (b->counted ? 1 : 0) > 0) ? 1 : 0;
-                const bool chain = 2 * split_launch_workgroups(m->cell, Hp, nrt, ncu_, beside) > ncu_ * split_workgroups_per_cu(m->cell, Hp, nrt, ncu_, beside);
-                if (b->eng->persist_chained && (chain || !b->eng->persist_last_half)) HIP_TRY(hipStreamWaitEvent(s, b->eng->persist_done, 0), FFHIP_EHIP);      // beside another launch only if BOTH are half-chip ones
+                // another batch is between run and finish: at H = 384 this batch's launches take the dense form, which fits beside that batch's;
+                // two such launches run beside each other only if ALL their workgroups fit on the chip together
+                const int beside = (eng->in_flight - (b->counted ? 1 : 0) > 0) ? 1 : 0;
+                const bool chain = 2 * split_launch_workgroups(m->cell, Hp, nrt, ncu, beside) > ncu * split_workgroups_per_cu(m->cell, Hp, nrt, ncu, beside);
+                if (int rc = layer_wait(eng, s, chain)) return rc;
                 if (prof && rt0 == 0) hipEventRecord(b->lev[l][1], s);      // behind the wait: the layer's time is its kernels', not the other batch's
                 if (!launch_lstm_split(s, m->cell, r.Wsplit, r.bias, b->actS[cur], outS, out_f32, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt,
-                                       backward, persist_mode, r.split_S, fast_gates, tbs, tbt, b->eng->prop.multiProcessorCount, b->split_epoch, beside, live))
+                                       backward, p.persist_mode, r.split_S, p.gates, tbs, tbt, ncu, b->split_epoch, beside, live))
                     return set_err(FFHIP_EINVAL, "split recurrent kernel: unsupported shape");
-                { HIP_TRY(hipEventRecord(b->eng->persist_done, s), FFHIP_EHIP); b->eng->persist_chained = 1; b->eng->persist_last_half = chain ? 0 : 1; }
+                if (int rc = layer_launched(eng, s, chain)) return rc;
                 b->launches[2]++;
             }
-            if (prof) hipEventRecord(b->lev[l][2], s);
-            cur ^= 1;
-            if (int rc = keep_copy(l + 1, b->act[cur])) return rc;
-            continue;
-        }
-        if (!fuse) {
-            if (!b->xa && !(b->xa = (float *)dalloc(b, (size_t)Tb * Bp * Hp * 4 * 4, false))) return FFHIP_ENOMEM;
-            if (r.Wsplit && !(flags & FFHIP_RUN_F32_RNN) && !dbg("no_split")) {
-                // projection on the bf16 pipes over split operands (fp32-exact products): the layer input is
-                // converted to the split layout first
-                if (!b->actS[0] && !(b->actS[0] = dalloc(b, split_bytes((size_t)Tb * B16, Hp), false))) return FFHIP_ENOMEM;
-                launch_split_from_f32(s, in, b->actS[0], (size_t)Tb * B16, Hp, (l == 0 && m->act == ACT_SWISH) ? kSplitExpX : kSplitExpH, b->sat, B16);
-                launch_inproj_split(s, b->actS[0], b->xa, r.Wsplit, r.bias, Tb * B16, Hp, r.split_S);
-                b->launches[1] += 2;
+        } else {
+            const bool fuse = p.persist && p.fused;
+            if (!fuse) {
+                if (!b->xa && !(b->xa = (float *)dalloc(b, (size_t)Tb * Bp * Hp * 4 * 4, false))) return FFHIP_ENOMEM;
+                if (r.Wsplit && p.proj_split) {
+                    // projection on the bf16 pipes over split operands (fp32-exact products): the layer input is
+                    // converted to the split layout first
+                    if (!b->actS[0] && !(b->actS[0] = dalloc(b, split_bytes((size_t)Tb * B16, Hp), false))) return FFHIP_ENOMEM;
+                    launch_split_from_f32(s, in, b->actS[0], (size_t)Tb * B16, Hp, (l == 0 && m->act == ACT_SWISH) ? kSplitExpX : kSplitExpH, b->sat, B16);
+                    launch_inproj_split(s, b->actS[0], b->xa, r.Wsplit, r.bias, Tb * B16, Hp, r.split_S);
+                    b->launches[1] += 2;
+                } else {
+                    launch_inproj(s, in, b->xa, r.iWp, r.bias, Tb * B16, 4 * Hp, r.Kin16);
+                    b->launches[1]++;
+                }
+            }
+            if (prof) hipEventRecord(b->lev[l][1], s);
+            const size_t xa_step = (size_t)Bp * Hp * 4, h_step = (size_t)Bp * Hp;
+            if (p.persist) {
+                // one launch per layer (and per chunk of read tiles that fits co-resident on the chip)
+                const int maxt = persist_max_tiles(m->cell, Hp, ncu, fuse);
+                // the output doubles as the hand-off flag: pre-fill with the NaN sentinel
+                HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out, (int)0xFFFFFFFF, (size_t)Tb * Bp * Hp, s), FFHIP_EHIP);
+                for (int rt0 = 0; rt0 < B16; rt0 += maxt) {
+                    const int nrt = (B16 - rt0 < maxt) ? B16 - rt0 : maxt;
+                    HIP_TRY(hipMemsetAsync(b->pflags, 0, persist_flag_words(Hp, nrt) * sizeof(unsigned), s), FFHIP_EHIP);
+                    const bool chain = !b->persist_concurrent_ok;
+                    if (int rc = layer_wait(eng, s, chain)) return rc;
+                    const bool okl = fuse
+                        ? launch_lstm_fused(s, m->cell, r.sWp, r.iWp, r.bias, in, out, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt, backward, p.persist_mode, tbs, tbt)
+                        : launch_rnn_persist(s, m->cell, r.sWp, b->xa, out, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt, backward, p.persist_mode, tbs, tbt);
+                    if (!okl) return set_err(FFHIP_EINVAL, "persistent recurrent kernel: unsupported shape");
+                    if (int rc = layer_launched(eng, s, chain)) return rc;
+                    b->launches[2]++;
+                }
             } else {
-                launch_inproj(s, in, b->xa, r.iWp, r.bias, Tb * B16, 4 * Hp, r.Kin16);
-                b->launches[1]++;
+                for (int i = 0; i < Tb; i++) {
+                    const int t = backward ? Tb - 1 - i : i;
+                    const int tp = backward ? t + 1 : t - 1;
+                    const float *hp = (i == 0) ? nullptr : out + (size_t)tp * h_step;
+                    if (m->cell == 0)
+                        launch_lstm_step(s, r.sWp, b->xa + (size_t)t * xa_step, hp, out + (size_t)t * h_step, b->cstate, B16, Hp, i == 0, t, tbs);
+                    else
+                        launch_gru_step(s, r.sWp, b->xa + (size_t)t * xa_step, hp, out + (size_t)t * h_step, B16, Hp, i == 0, t, tbs);
+                }
+                b->launches[2] += Tb;
             }
         }
-        if (prof) hipEventRecord(b->lev[l][1], s);
-        const size_t xa_step = (size_t)Bp * Hp * 4, h_step = (size_t)Bp * Hp;
-        if (use_persist) {
-            // one launch per layer (and per chunk of read tiles that fits co-resident on the chip)
-            const int maxt = persist_max_tiles(m->cell, Hp, b->eng->prop.multiProcessorCount, fuse);
-            // the output doubles as the hand-off flag: pre-fill with the NaN sentinel
-            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out, (int)0xFFFFFFFF, (size_t)Tb * Bp * Hp, s), FFHIP_EHIP);
-            for (int rt0 = 0; rt0 < B16; rt0 += maxt) {
-                const int nrt = (B16 - rt0 < maxt) ? B16 - rt0 : maxt;
-                HIP_TRY(hipMemsetAsync(b->pflags, 0, persist_flag_words(Hp, nrt) * sizeof(unsigned), s), FFHIP_EHIP);
-                const bool chain = !b->persist_concurrent_ok;
-                if (b->eng->persist_chained && (chain || !b->eng->persist_last_half)) HIP_TRY(hipStreamWaitEvent(s, b->eng->persist_done, 0), FFHIP_EHIP);      // beside another launch only if BOTH are half-chip ones
-                const bool okl = fuse
-                    ? launch_lstm_fused(s, m->cell, r.sWp, r.iWp, r.bias, in, out, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt, backward, persist_mode, tbs, tbt)
-                    : launch_rnn_persist(s, m->cell, r.sWp, b->xa, out, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt, backward, persist_mode, tbs, tbt);
-                if (!okl) return set_err(FFHIP_EINVAL, "persistent recurrent kernel: unsupported shape");
-                { HIP_TRY(hipEventRecord(b->eng->persist_done, s), FFHIP_EHIP); b->eng->persist_chained = 1; b->eng->persist_last_half = chain ? 0 : 1; }
-                b->launches[2]++;
-            }
-        } else
-        for (int i = 0; i < Tb; i++) {
-            const int t = backward ? Tb - 1 - i : i;
-            const int tp = backward ? t + 1 : t - 1;
-            const float *hp = (i == 0) ? nullptr : out + (size_t)tp * h_step;
-            if (m->cell == 0)
-                launch_lstm_step(s, r.sWp, b->xa + (size_t)t * xa_step, hp, out + (size_t)t * h_step, b->cstate, B16, Hp, i == 0, t, tbs);
-            else
-                launch_gru_step(s, r.sWp, b->xa + (size_t)t * xa_step, hp, out + (size_t)t * h_step, B16, Hp, i == 0, t, tbs);
-        }
-        if (!use_persist) b->launches[2] += Tb;
         if (prof) hipEventRecord(b->lev[l][2], s);
         cur ^= 1;
-        if (int rc = keep_copy(l + 1, b->act[cur])) return rc;
+        if (int rc = keep_copy(b, l + 1, b->act[cur])) return rc;
     }
     b->run_cur = cur;
-  }      // PH_LAYERS
-  if (!(phases & PH_BACK)) return FFHIP_OK;
-    b->profiled = prof;
+    return FFHIP_OK;
+}
+
+// ---- CRF head, normalisation, posterior, Viterbi, strings; the result block's copy of a packed batch
+static int run_back(ffhip_batch *b) {
+    const ffhip_model *m = b->mdl;
+    ffhip_engine *eng = b->eng;
+    const RunPath &p = b->run_path;
+    hipStream_t s = b->stream;
+    const unsigned flags = b->run_flags;
+    const float temperature = b->last_temperature;
+    const int Tb = b->Tb, B16 = b->B16, Hp = m->Hp, cur = b->run_cur, nR = b->packed ? b->nvirt : b->nread;      // (packed: per READ results)
+    const int *tbs = b->ragged ? b->d_tbs : nullptr, *tbr = b->packed ? b->d_vtb : tbs;
+    ReadMap rmap;
+    if (b->packed) { rmap.b0 = b->d_vb0; rmap.b1 = b->d_vb1; rmap.nslot = b->nread; }
+    b->profiled = eng->profiling != 0;
     b->final_act = cur;
-    b->rnn_path = use_split ? 3 : (use_split2 ? 4 : (use_persist ? (use_fused ? 2 : 1) : 0));
+    b->rnn_path = p.rnn_path;
     mark(b, 3);
     const bool rle = (m->kind == FFHIP_NET_LSTM5_RLE);
-    bool post_done = false;                       // the posterior came out of the partition function's launch
     if (rle) {
         // ---- globalnorm_runlengthV2 (layers.c:1325-1358)
-        if (split_head) launch_head_split(s, b->actS[cur], b->trans, m->FFsplit, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 32, 1.0f, m->FF_split_S, 1);
+        if (p.split_head) launch_head_split(s, b->actS[cur], b->trans, m->FFsplit, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 32, 1.0f, m->FF_split_S, 1);
         else launch_head(s, b->act[cur], b->trans, m->FFp, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 16, 1.0f, 1);
         launch_rle_head_finish(s, b->trans, b->crf_logz, b->nread, Tb, m->nbase, m->Ps, temperature, tbs);
         b->launches[3] += 4;
     } else {
         // ---- globalnorm_flipflop (layers.c:1082-1106)
-        // |score| <= 5/temperature (tanh bounded by 1): picks the rescaling interval of the linear-space form;
-        // extreme temperatures (or FFHIP_CRF_LOGSPACE=1) take the log-space recursion
-        const int R = dbg("crf_logspace") ? 0 : crf_rescale_interval(5.0f / temperature);
-        // 8-state models, a block's scores spanning at most kFbRange: ONE pair of fp64 linear-space chains per read gives logZ, the
-        // normalised scores and (when asked for) the posterior (k_crf_fb8, ffhip_decode.hip)
-        post_done = R > 0 && ((m->nbase == 4 && m->Ps == 40) || (m->nbase == 5 && m->Ps == 60)) && 10.0f / temperature <= kFbRange && !dbg("decode_r2");
-        // ... whose input E = exp(S - block max) the split head leaves behind from its own epilogue (round 5: k_crf_exp's launch and its pass over the scores are gone)
-        const bool head_e = split_head && post_done && head_split_writes_E(m->P);
-        if (split_head) launch_head_split(s, b->actS[cur], b->trans, m->FFsplit, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 32, temperature / 5.0f, m->FF_split_S, 0, head_e ? b->crf_e : nullptr);
+        if (p.split_head) launch_head_split(s, b->actS[cur], b->trans, m->FFsplit, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 32, temperature / 5.0f, m->FF_split_S, 0, p.head_e ? b->crf_e : nullptr);
         else launch_head(s, b->act[cur], b->trans, m->FFp, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 16, temperature / 5.0f);
-        if (b->packed) { HIP_TRY(hipEventRecord(b->eng->head_done, s), FFHIP_EHIP); b->eng->head_done_rec = 1; }      // (the next packed batch's set-up and convolutions start behind it: apply_packed)
-        if (post_done) {
+        if (b->packed) { HIP_TRY(hipEventRecord(eng->head_done, s), FFHIP_EHIP); eng->head_done_rec = 1; }      // (the next packed batch's set-up and convolutions start behind it: apply_packed)
+        if (p.post_done) {
             const bool want_post = !(flags & FFHIP_RUN_NO_DECODE) && !(flags & FFHIP_RUN_VITERBI_ONLY);
-            if (!head_e) launch_crf_exp(s, b->trans, b->crf_e, b->nread, Tb, m->nbase, m->Ps, tbs, nullptr, 0.0f);
+            if (!p.head_e) launch_crf_exp(s, b->trans, b->crf_e, b->nread, Tb, m->nbase, m->Ps, tbs, nullptr, 0.0f);
             mark(b, 4);       // the profile's "posterior" slot times the chain launch: partition function + normalisation + posterior together
             launch_crf_fb(s, m->nbase, b->crf_e, b->trans, b->post, (double *)b->fwd, nR, Tb, b->crf_logz, tbr, want_post ? 3 : 1, nullptr, rmap);
             b->launches[3] += want_post ? 4 : 3;      // head, exp, chains, assembly (the subtraction alone: three)
         } else {
-            if (R > 0) launch_crf_norm_linear(s, b->trans, b->crf_e, b->nread, Tb, m->nbase, m->Ps, R, b->crf_logz, 1, tbs);
+            if (p.R > 0) launch_crf_norm_linear(s, b->trans, b->crf_e, b->nread, Tb, m->nbase, m->Ps, p.R, b->crf_logz, 1, tbs);
             else launch_crf_norm(s, b->trans, b->nread, Tb, m->nbase, m->Ps, b->crf_logz, 1, tbs);
             b->launches[3] += 3;
         }
     }
-    if (!post_done) mark(b, 4);
+    if (!p.post_done) mark(b, 4);
     b->last_flags = flags;
     if (!(flags & FFHIP_RUN_NO_DECODE)) {
         const float *scores = b->trans;
         if (!(flags & FFHIP_RUN_VITERBI_ONLY)) {
-            if (rle && m->nbase == 4 && m->Ps == 40 && 10.0f / temperature <= kFbRange && !dbg("decode_r2"))
-                launch_rle_post8(s, b->trans, b->post, b->crf_e, (double *)b->fwd, b->nread, Tb, tbs);              // fp64 linear-space chains (ffhip_decode.hip)
+            if (p.rle_post8) launch_rle_post8(s, b->trans, b->post, b->crf_e, (double *)b->fwd, b->nread, Tb, tbs);      // fp64 linear-space chains (ffhip_decode.hip)
             else if (rle) launch_rle_transpost(s, b->trans, b->post, b->fwd, b->nread, Tb, m->nbase, m->Ps, tbs);       // decode.c:1037-1159
-            else if (!post_done) launch_transpost(s, b->trans, b->post, b->fwd, b->nread, Tb, m->nbase, m->Ps, tbs);
+            else if (!p.post_done) launch_transpost(s, b->trans, b->post, b->fwd, b->nread, Tb, m->nbase, m->Ps, tbs);
             scores = b->post;
             b->launches[4]++;
         }
@@ -1664,17 +1674,24 @@ static int batch_run_impl(ffhip_batch *b, float temperature, unsigned flags, int
     // already running: the copy's blit kernel then crawls beside them (193 ms in a kernel trace) and holds a layer launch up as long.  It goes here, behind the decode
     // and in front of the events the next batch's layer launches wait for.
     b->res_copied = 0;
-    if (b->packed && (phases & PH_BACK)) {
+    if (b->packed) {
         HIP_TRY(hipMemcpyAsync(b->res_host, b->res_dev, (flags & FFHIP_RUN_NO_DECODE) ? b->res_head : b->res_bytes, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
         b->res_copied = 1;
     }
-    HIP_TRY(hipEventRecord(b->eng->batch_done, s), FFHIP_EHIP);
-    b->eng->batch_done_rec = 1;
-    if (phases & PH_BACK) { HIP_TRY(hipEventRecord(b->eng->done_ring[b->eng->done_head & 3u], s), FFHIP_EHIP); b->eng->done_head++; }
+    HIP_TRY(hipEventRecord(eng->batch_done, s), FFHIP_EHIP); eng->batch_done_rec = 1;
+    HIP_TRY(hipEventRecord(eng->done_ring[eng->done_head & 3u], s), FFHIP_EHIP); eng->done_head++;
     HIP_TRY(hipGetLastError(), FFHIP_EHIP);
     b->ran = 1; b->finished = 0;
-    if (!b->counted) { b->counted = 1; b->eng->in_flight++; }
+    if (!b->counted) { b->counted = 1; eng->in_flight++; }
     return FFHIP_OK;
+}
+
+static int batch_run_impl(ffhip_batch *b, float temperature, unsigned flags) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    hipSetDevice(b->eng->device);
+    if (int rc = run_front(b, temperature, flags, false)) return rc;
+    if (int rc = run_layers(b)) return rc;
+    return run_back(b);
 }
 
 // ---- host-load rehearsal: the run side (see rehearsal_rate() at the top of this file)
@@ -1720,7 +1737,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
 extern "C" int ffhip_batch_run(ffhip_batch *b, float temperature, unsigned flags) {
     if (b) b->paired_last = 0;
     if (b && rehearsal_rate() > 0) return rehearsal_run(b, temperature, flags);
-    return batch_run_impl(b, temperature, flags, PH_ALL);
+    return batch_run_impl(b, temperature, flags);
 }
 
 // Two batches of the same model and shape, their recurrent layers as ONE launch per layer (k_lstm_split_pair: the dense form of the
@@ -1731,61 +1748,45 @@ extern "C" int ffhip_batch_run_pair(ffhip_batch *b0, ffhip_batch *b1, float temp
     if (!b0 || !b1 || b0 == b1) return set_err(FFHIP_EINVAL, "two distinct batches are needed");
     const ffhip_model *m = b0->mdl;
     ffhip_engine *eng = b0->eng;
-    const int ncu = eng->prop.multiProcessorCount;
-    const bool pairable = b1->mdl == m && b1->eng == eng && b0->Tb == b1->Tb && b0->B16 == b1->B16 && b0->packed == b1->packed && b0->B16 <= 2 * (ncu / 32) && (((b0->B16 + 1) / 2) & 7) == 0 &&
-                          !(flags & (FFHIP_RUN_KEEP_ACTS | FFHIP_RUN_STEPWISE_RNN | FFHIP_RUN_F32_RNN | FFHIP_RUN_UNFUSED_RNN)) && eng->stepwise_batches == 0 &&
-                          m->cell == 0 && m->Hp == 384 && split_supported(m->cell, m->Hp) && m->rnn[0].Wsplit != nullptr && !dbg("no_split") &&
-                          !dbg("no_fuse") && !dbg("no_pair") && persist_supported(m->cell, m->Hp, ncu);
-    if (!pairable) {
-        if (int rc = ffhip_batch_run(b0, temperature, flags)) return rc;
-        return ffhip_batch_run(b1, temperature, flags);
-    }
+    // (the two batches' launch arguments must agree: launch_lstm_split_pair)
+    const bool pairable = b1->mdl == m && b1->eng == eng && b0->Tb == b1->Tb && b0->B16 == b1->B16 && b0->packed == b1->packed && b0->ragged == b1->ragged &&
+                          eng->stepwise_batches == 0 && model_path(m, flags, eng->prop.multiProcessorCount, b0->B16).pairable;
+    if (!pairable) { if (int rc = ffhip_batch_run(b0, temperature, flags)) return rc; return ffhip_batch_run(b1, temperature, flags); }
     hipSetDevice(eng->device);
-    b0->pair_front = b1->pair_front = 1;
-    const int rc0 = batch_run_impl(b0, temperature, flags, PH_FRONT), rc1 = rc0 ? rc0 : batch_run_impl(b1, temperature, flags, PH_FRONT);
-    b0->pair_front = b1->pair_front = 0;
+    const int rc0 = run_front(b0, temperature, flags, true), rc1 = rc0 ? rc0 : run_front(b1, temperature, flags, true);
     if (rc1) return rc1;
     hipStream_t s = b0->stream;
     HIP_TRY(hipEventRecord(b1->pair_ev, b1->stream), FFHIP_EHIP);
     HIP_TRY(hipStreamWaitEvent(s, b1->pair_ev, 0), FFHIP_EHIP);              // the second batch's convolutions are done before the first paired layer
     const bool prof = eng->profiling != 0;
-    const int fast_gates = gate_level(flags);
-    const char *pm_env = dbg("persist_mode");
-    const int persist_mode = pm_env ? atoi(pm_env) : 0;
+    const RunPath &p = b0->run_path;                                              // (b1's is the same: same model, flags and temperature)
     ffhip_batch *bb[2] = { b0, b1 };
-    const bool split_head_pair = m->FFsplit != nullptr && !dbg("no_split_head");      // as batch_run_impl's split_head (a pair never keeps activations)
-    bool paired = true;
-    for (int l = 0; l < 5 && paired; l++) {
+    for (int l = 0; l < 5; l++) {
         const RnnDev &r = m->rnn[l];
-        SplitLaunch p[2];
+        SplitLaunch sl[2];
         for (int k = 0; k < 2; k++) {
             ffhip_batch *b = bb[k];
             const int cur = b->run_cur;
             b->split_epoch = (b->split_epoch % 0x3FFFFFFu) + 1u;
-            p[k] = SplitLaunch{ r.Wsplit, r.bias, b->actS[cur], b->actS[cur ^ 1], (l == 4 && !split_head_pair) ? b->act[cur ^ 1] : nullptr, b->pflags, b->pabort,
-                                b->Tb, b->B16, 0, b->B16, (l % 2 == 0) ? 1 : 0, persist_mode, r.split_S, fast_gates,
-                                b->ragged ? b->d_tbs : nullptr, b->ragged ? b->d_tbt : nullptr, b->split_epoch, b->packed ? b->d_live : nullptr };
+            sl[k] = SplitLaunch{ r.Wsplit, r.bias, b->actS[cur], b->actS[cur ^ 1], (l == 4 && !p.split_head) ? b->act[cur ^ 1] : nullptr, b->pflags, b->pabort,
+                                 b->Tb, b->B16, 0, b->B16, (l % 2 == 0) ? 1 : 0, p.persist_mode, r.split_S, p.gates,
+                                 b->ragged ? b->d_tbs : nullptr, b->ragged ? b->d_tbt : nullptr, b->split_epoch, b->packed ? b->d_live : nullptr };
         }
         if (prof) hipEventRecord(b0->lev[l][1], s);
-        if (eng->persist_chained) HIP_TRY(hipStreamWaitEvent(s, eng->persist_done, 0), FFHIP_EHIP);      // a paired launch fills the chip: after any other layer launch
-        if (!launch_lstm_split_pair(s, m->cell, m->Hp, ncu, p[0], p[1])) { paired = false; break; }
-        HIP_TRY(hipEventRecord(eng->persist_done, s), FFHIP_EHIP);
-        eng->persist_chained = 1;
-        eng->persist_last_half = 0;
+        if (int rc = layer_wait(eng, s, true)) return rc;      // a paired launch fills the chip: after any other layer launch
+        if (!launch_lstm_split_pair(s, m->cell, m->Hp, eng->prop.multiProcessorCount, sl[0], sl[1]))
+            return set_err(FFHIP_EINVAL, "paired layer launch refused a shape ffhip_batch_run_pair had accepted");
+        if (int rc = layer_launched(eng, s, true)) return rc;
         if (prof) hipEventRecord(b0->lev[l][2], s);
-        for (int k = 0; k < 2; k++) {
-            bb[k]->launches[2]++;
-            bb[k]->run_cur ^= 1;
-        }
+        for (ffhip_batch *b : bb) { b->launches[2]++; b->run_cur ^= 1; }
     }
-    if (!paired) return set_err(FFHIP_EINVAL, "paired layer launch refused a shape ffhip_batch_run_pair had accepted");
     HIP_TRY(hipEventRecord(b0->pair_ev, s), FFHIP_EHIP);
     HIP_TRY(hipStreamWaitEvent(b1->stream, b0->pair_ev, 0), FFHIP_EHIP);     // the second batch's head and decode follow the paired layers
     b0->paired_last = b1->paired_last = 1;
     prof_unlink(b0); prof_unlink(b1);                  // (whatever pairs they were part of before, in either role)
     if (prof) { b1->prof_mate = b0; b0->prof_ref = b1; }
-    if (int rc = batch_run_impl(b0, temperature, flags, PH_BACK)) return rc;
-    return batch_run_impl(b1, temperature, flags, PH_BACK);
+    if (int rc = run_back(b0)) return rc;
+    return run_back(b1);
 }
 
 extern "C" int ffhip_batch_paired(const ffhip_batch *b) { return (b && b->paired_last) ? 1 : 0; }
@@ -1850,7 +1851,6 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
     if (!b) return set_err(FFHIP_EINVAL, "null batch");
     if (!b->ran) return set_err(FFHIP_EINVAL, "ffhip_batch_run has not been called");
     hipSetDevice(b->eng->device);
-    const size_t n = (size_t)b->nread, L = (size_t)b->Tb + 1;
     if (rehearsal_nogpu()) {                                 // test hook (top of this file): the results are on the host already
         const double left = b->rehearsal_done_at - now_seconds();
         if (left > 0) { struct timespec ts = { (time_t)left, (long)((left - (double)(time_t)left) * 1e9) }; nanosleep(&ts, nullptr); }
@@ -1861,7 +1861,6 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
     // one copy: [sat | abort] and, when the batch was decoded, [lens | score | bases | quals] behind them (the block of ffhip_batch_create)
     if (!b->res_copied) HIP_TRY(hipMemcpyAsync(b->res_host, b->res_dev, (b->last_flags & FFHIP_RUN_NO_DECODE) ? b->res_head : b->res_bytes, hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
     b->res_copied = 0;
-    (void)n; (void)L;
     HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
     if (rehearsal_rate() > 0) {                              // (test hook above: the emulated GPU finishes this batch at rehearsal_done_at)
         const double left = b->rehearsal_done_at - now_seconds();
@@ -1973,7 +1972,7 @@ extern "C" int ffhip_batch_get_activation(ffhip_batch *b, int layer, int read, f
     const ffhip_model *m = b->mdl;
     const float *src = b->keep[layer + 1];
     if (!src) {
-        if (layer == 4 && b->act[b->final_act] && !(b->rnn_path == 3 && b->mdl->FFsplit && !dbg("no_split_head"))) src = b->act[b->final_act];      // (the default path keeps no fp32 copy of the last layer: k_head_split)
+        if (layer == 4 && b->act[b->final_act] && !b->run_path.split_head) src = b->act[b->final_act];      // (the default path keeps no fp32 copy of the last layer: k_head_split)
         else return set_err(FFHIP_EINVAL, "activation of layer %d was not kept (run with flag 16)", layer);
     }
     hipSetDevice(b->eng->device);

@@ -9,8 +9,9 @@
 namespace ffhip {
 
 // Development switches live in ONE environment variable: FFHIP_DEBUG=token[,token=value ...] (INTEGRATION.md section 6 lists them).
-// dbg("token"): nullptr when the token is absent, otherwise its value ("" for a bare token) -- what getenv gave when every switch
+// dbg(token): nullptr when the token is absent, otherwise its value ("" for a bare token) -- what getenv gave when every switch
 // had a variable of its own (rounds 1-4: 41 of them).  Looked up per call: tests flip switches between runs of one process.
+// A token the library does not read is reported once on stderr (ffhip_engine.hip kDebugTokens).
 const char *dbg(const char *token);
 
 // ---------------------------------------------------------------------------------------------
@@ -124,6 +125,7 @@ struct SplitLaunch {          // one batch's share of a paired layer launch
     int Tb, B16, rt0, nrt, backward, mode, scale_exp, fast_gates; const int *tbs, *tbt; unsigned epoch;
     const unsigned *live = nullptr;      // packed batch: bit r of word [t][read tile] = slot r holds a block of a read at step t (ffhip_rnn_split.hip SplitArgs)
 };
+bool split_pair_ok(int kind, int H, int nrt, int ncu);      // two batches of nrt read tiles each can share a layer launch: what launch_lstm_split_pair takes
 bool launch_lstm_split_pair(hipStream_t s, int kind, int H, int ncu, const SplitLaunch &p0, const SplitLaunch &p1);
 bool launch_lstm_split(hipStream_t s, int kind, const void *Wp, const float *bias, const void *xin, void *hout, float *hout_f32,
                        unsigned *flags, unsigned *abort_word, int Tb, int B16, int H, int rt0, int nrt, int backward, int mode,

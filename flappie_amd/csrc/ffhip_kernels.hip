@@ -19,7 +19,7 @@
 #include "ffhip_math.hpp"
 #include <stdlib.h>
 
-// Head and decode kernels run beside the NEXT batch's convolutions (batch_run_impl, FFHIP_DEBUG=front_order=...) and the next layer launches wait for them:
+// Head and decode kernels run beside the NEXT batch's convolutions (run_front in ffhip_engine.hip, FFHIP_DEBUG=front_order=...) and the next layer launches wait for them:
 // their waves go first on a shared SIMD (the convolutions stay at priority 0)
 #ifndef FFHIP_DECODE_PRIO
 #define FFHIP_DECODE_PRIO 2
@@ -175,11 +175,9 @@ void launch_conv_small(hipStream_t s, SampleBuf in, SampleBuf out, const float *
     dim3 grid((Tout + 255) / 256, Bp), block(256);
     const float split_scale = (split_exp > -1000 && out.F == 16 && kSplitNS == 2) ? split_pow2(split_exp) : 0.0f;
     const size_t lds = (size_t)(out.F * winlen * in.F + out.F) * sizeof(float);
-    const char *su_env = dbg("conv_small_u");
-    const bool unrolled = !(su_env && su_env[0] == '0');      // (=0: the round-3 loops, for comparison)
-    if (unrolled && out.F == 4 && in.F == 1 && winlen == 5)
+    if (out.F == 4 && in.F == 1 && winlen == 5)
         hipLaunchKernelGGL((k_conv_small<4, 5>), grid, block, lds, s, in, out, W, bias, x0a, x0b, Tout, winlen, act, ldp, tin, 0.0f, sat, seg);
-    else if (unrolled && out.F == 16 && in.F == 4 && winlen == 5)
+    else if (out.F == 16 && in.F == 4 && winlen == 5)
         hipLaunchKernelGGL((k_conv_small<16, 20>), grid, block, lds, s, in, out, W, bias, x0a, x0b, Tout, winlen, act, ldp, tin, split_scale, sat, seg);
     else if (out.F <= 4)
         hipLaunchKernelGGL(k_conv_small<4>, grid, block, lds, s, in, out, W, bias, x0a, x0b, Tout, winlen, act, ldp, tin, 0.0f, sat, seg);
@@ -235,9 +233,10 @@ __device__ __forceinline__ void mma_tiles(const v4f *(&ap)[TM], const float *(&b
 // N tile = (output column c, read tile rt); all 16 reads share the window start.  Columns with a
 // second window (or none) are irregular and rare: handled by re-running the loop for window b.
 // TN (column tiles a wave; round 4).  A one-feature input (the r941_5mC model's only convolution: 19 taps, K16 = 2) has 8 MFMAs a tile against ~130
-// VALU instructions of swish + split in the epilogue, and at TN = 4 the kernel holds 230 registers: two waves a SIMD.  FFHIP_DEBUG=conv1_tn=2 (156 registers,
-// three waves) is 13 % faster ALONE (1.00 -> 0.88 ms for a 1024-read batch) -- and slower in the pipeline, where this convolution runs beside the previous
-// batch's head and decode and the next layer launches wait for THOSE: 100.3 -> 99.0 Msamples/s at `c4` (TN = 1: 98.7).  Default 4; bit-identical all three.
+// VALU instructions of swish + split in the epilogue, and at TN = 4 the kernel holds 230 registers: two waves a SIMD.  TN = 2 (156 registers,
+// three waves) was 13 % faster ALONE (1.00 -> 0.88 ms for a 1024-read batch) -- and slower in the pipeline, where this convolution runs beside the previous
+// batch's head and decode and the next layer launches wait for THOSE: 100.3 -> 99.0 Msamples/s at `c4` (TN = 1: 98.7).  Every launch takes TN = 4; the thinner
+// forms were retired (tools/dev/experiments/README.md).
 template <bool BVEC, int TN = 4, int WPS = 1>
 __global__ void __launch_bounds__(256, WPS)
 k_conv_mfma(SampleBuf in, float *__restrict__ out, const v4f *__restrict__ Wp, const float *__restrict__ bias,
@@ -317,17 +316,7 @@ void launch_conv_mfma(hipStream_t s, SampleBuf in, float *out, const float4 *Wp,
     const int Mt = M / 16;
     const int nMblk = (Mt + 7) / 8, nNblk = (Tout * B16 + 7) / 8;
     const bool vec = (in.F % 4 == 0);
-    const char *tn_env = dbg("conv1_tn");
-    const int thin_tn = tn_env ? atoi(tn_env) : 4;
-    if (!vec && K16 <= 2 && thin_tn < 4) {
-        const int tn = thin_tn <= 1 ? 1 : 2, nNb = (Tout * B16 + 2 * tn - 1) / (2 * tn);
-        if (tn == 1)
-            hipLaunchKernelGGL((k_conv_mfma<false, 1, 4>), dim3(nMblk * nNb), dim3(256), 0, s, in, out, (const v4f *)Wp, bias,
-                               x0a, x0b, B16, Tout, Mt, K16, act, ldp, (unsigned char *)out_split, split_pow2(split_exp), sat);
-        else
-            hipLaunchKernelGGL((k_conv_mfma<false, 2, 3>), dim3(nMblk * nNb), dim3(256), 0, s, in, out, (const v4f *)Wp, bias,
-                               x0a, x0b, B16, Tout, Mt, K16, act, ldp, (unsigned char *)out_split, split_pow2(split_exp), sat);
-    } else if (vec)
+    if (vec)
         hipLaunchKernelGGL(k_conv_mfma<true>, dim3(nMblk * nNblk), dim3(256), 0, s, in, out, (const v4f *)Wp, bias,
                            x0a, x0b, B16, Tout, Mt, K16, act, ldp, (unsigned char *)out_split, split_pow2(split_exp), sat);
     else
@@ -600,10 +589,8 @@ k_conv_split_ws(SampleBuf in, const v4u_t *__restrict__ Wp, const float *__restr
 void launch_conv_split(hipStream_t s, SampleBuf in, float *out, const void *Wp, const float *bias, const int *x0a, const int *x0b,
                        int B16, int Tout, int M, int winlen, int act, int ldp, void *out_split, int split_exp, int acc_exp, int lean, unsigned *sat) {
     const int Mt = M / 16, NC = (winlen + 1) / 2;
-    // the weights-stationary form: split output, the chip to itself, shapes it is built for (FFHIP_DEBUG=conv_ws=0: the round-3 kernel)
-    const char *ws_txt = dbg("conv_ws");
-    const int ws_env = ws_txt ? atoi(ws_txt) : 1;
-    if (!lean && out_split && kSplitNS == 2 && ws_env && act == ACT_SWISH && Mt % 8 == 0 && NC == 10 && (size_t)in.rs * 4 * 16 < ((size_t)1 << 32)) {
+    // the weights-stationary form: split output, the chip to itself, shapes it is built for
+    if (!lean && out_split && kSplitNS == 2 && act == ACT_SWISH && Mt % 8 == 0 && NC == 10 && (size_t)in.rs * 4 * 16 < ((size_t)1 << 32)) {
         // (per call, of the CURRENT device -- the caller's engine has set it: a value cached from the first call would size the groups of an engine on
         // another device of the process by the wrong chip)
         int ncu = 256;
@@ -989,7 +976,7 @@ void launch_head_split(hipStream_t s, const void *in_split, float *trans, const 
                            nread, P, Ps, Mt, Hc, scale, split_pow2(acc_exp), raw, E, Pd);
 }
 // the head's epilogue can leave E = exp(S - max S) for the chains of ffhip_decode.hip: a block's row of crf_exp_stride(P) doubles must fit the head's row tiles
-bool head_split_writes_E(int P) { const int Mt = (P + 15) / 16; return !dbg("no_head_exp") && crf_exp_stride(P) <= 16 * (Mt <= 3 ? 3 : 4) && Mt <= 4; }
+bool head_split_writes_E(int P) { const int Mt = (P + 15) / 16; return crf_exp_stride(P) <= 16 * (Mt <= 3 ? 3 : 4) && Mt <= 4; }
 
 void launch_head(hipStream_t s, const float *in, float *trans, const float4 *Wp, const float *bias,
                  int Tb, int B16, int nread, int P, int Ps, int K16, float scale, int raw) {
@@ -1408,9 +1395,9 @@ void launch_crf_norm_linear(hipStream_t s, float *trans, double *E, int nread, i
     const size_t nblk = (size_t)nread * Tb;
     hipLaunchKernelGGL(k_crf_exp, dim3((unsigned)((nblk + kExpBlocks - 1) / kExpBlocks)), dim3(256), 0, s, trans, E, nblk, P, Ps, Pd, Tb, tbs, (int *)nullptr, 0.0f, 0);
     const int Rr = R < 1 ? 1 : R;
-    if (nbase == 4 && !dbg("crf_generic")) {
+    if (nbase == 4) {
         hipLaunchKernelGGL(k_crf_chain8, dim3(nread), dim3(64), 0, s, E, Tb, Pd, Rr, logz, tbs);
-    } else if (nbase == 5 && Pd <= 64 && !dbg("crf_generic")) {
+    } else if (nbase == 5 && Pd <= 64) {
         hipLaunchKernelGGL(k_crf_chain10, dim3(nread), dim3(64), 0, s, E, Tb, Pd, Rr, logz, tbs);
     } else
     switch (2 * nbase) {
@@ -1947,7 +1934,7 @@ k_transpost10(const float *__restrict__ trans, float *__restrict__ post, float *
 void launch_transpost(hipStream_t s, const float *trans, float *post, float *fwd, int nread, int Tb, int nbase, int Ps, const int *tbs,
                       double *E, int *wide) {
     const int P = 2 * nbase * (nbase + 1);
-    if (((nbase == 4 && Ps == 40) || (nbase == 5 && Ps == 60)) && E && wide && !dbg("exact_order") && !dbg("decode_r2")) {
+    if (((nbase == 4 && Ps == 40) || (nbase == 5 && Ps == 60)) && E && wide && !dbg("exact_order")) {
         // linear-space fp64 recursions on exp(score - block max) (ffhip_decode.hip); reads whose scores span too much keep the log-space kernel
         hipMemsetAsync(wide, 0, (size_t)nread * sizeof(int), s);
         launch_crf_exp(s, trans, E, nread, Tb, nbase, Ps, tbs, wide, kFbRange);
@@ -1958,7 +1945,7 @@ void launch_transpost(hipStream_t s, const float *trans, float *post, float *fwd
             hipLaunchKernelGGL(k_transpost10, dim3(nread), dim3(256), 0, s, trans, post, fwd, fwd + (size_t)nread * (Tb + 1) * kMaxState, Tb, Ps, tbs, (const int *)wide);
     } else if (nbase == 4 && Ps == 40 && !dbg("exact_order"))
         hipLaunchKernelGGL(k_transpost8, dim3(nread), dim3(256), 0, s, trans, post, fwd, fwd + (size_t)nread * (Tb + 1) * kMaxState, Tb, tbs, (const int *)nullptr);
-    else if (nbase == 5 && !dbg("exact_order") && !dbg("crf_generic"))
+    else if (nbase == 5 && !dbg("exact_order"))
         hipLaunchKernelGGL(k_transpost10, dim3(nread), dim3(256), 0, s, trans, post, fwd, fwd + (size_t)nread * (Tb + 1) * kMaxState, Tb, Ps, tbs, (const int *)nullptr);
     else if (!dbg("exact_order"))
         hipLaunchKernelGGL(k_transpost_lds, dim3(nread), dim3(256), 0, s, trans, post, fwd, fwd + (size_t)nread * (Tb + 1) * kMaxState, Tb, nbase, P, Ps, tbs);
@@ -1995,7 +1982,7 @@ k_viterbi(const float *__restrict__ M, uint8_t *__restrict__ tbbuf, int *__restr
     // Forward recursion, one wave.  Every entry's candidate s + prev[from] in parallel; each state then scans its entries in
     // the reference's order (flip: from-state 0..ns-1, first maximum; flop: stay unless move is strictly greater) -- the
     // same comparisons on the same values as a lane-exchange chain, without 2*ns+4 dependent exchanges per block.  As in
-    // k_viterbi8 the traceback bytes stay in LDS (earlier chunks of longer reads are flushed) and the scores of the next
+    // k_viterbi10 the traceback bytes stay in LDS (earlier chunks of longer reads are flushed) and the scores of the next
     // kDepth blocks are in flight: nothing on the chain waits for memory.
     constexpr int kDepth = 8;
     float ring[kDepth];
@@ -2083,128 +2070,9 @@ k_viterbi(const float *__restrict__ M, uint8_t *__restrict__ tbbuf, int *__restr
     }
 }
 
-// Viterbi for nstate == 8: same lane layout; bit-identical to the sequential scan because max is
-// exact and the tie rules are reproduced (flip: lowest from-state wins; flop: stay unless move is
-// strictly greater).
-__global__ void __launch_bounds__(64)
-k_viterbi8(const float *__restrict__ M, uint8_t *__restrict__ tbbuf, int *__restrict__ path,
-           float *__restrict__ qpath, float *__restrict__ score_out, int TbS, const int *__restrict__ tbs) {
-    constexpr int P = 40, Ps = 40, ns = 8, nbase = 4, off = 32;
-    __shared__ uint8_t tb_lds[kTbChunk * kMaxState];
-    __shared__ int path_lds[kTbChunk + 1];
-    const int lane = threadIdx.x;
-    const float *T = M + (size_t)blockIdx.x * TbS * Ps;
-    uint8_t *tb = tbbuf + (size_t)blockIdx.x * TbS * kMaxState;
-    int *pth = path + (size_t)blockIdx.x * (TbS + 1);
-    float *qp = qpath + (size_t)blockIdx.x * (TbS + 1);
-    const int Tb = tbs ? tbs[blockIdx.x] : TbS;          // this read's blocks; TbS is the batch's stride
-    if (Tb <= 0) return;                                 // an empty slot: nothing to read, and Tb - 1 must not index
-    const bool valid = lane < P, flip = lane < 32;
-    const int st = lane & 7;
-    const float NEG = -INFINITY;
-
-    // Forward recursion.  The chain is ~150 cycles of work per block, so nothing on it may wait for memory:
-    //  * the traceback bytes go to LDS (a chunk of kTbChunk blocks; earlier chunks of longer reads are flushed to HBM with wide
-    //    stores) -- a global store per block shares the wave's memory counter with the loads, and the compiler then waits for
-    //    the store's acknowledgement (~700 cycles) before it may use the next block's scores;
-    //  * the scores of the next kDepth blocks are in flight while kDepth blocks are processed.
-    constexpr int kDepth = 8;
-    float ring[kDepth];
-    // (clamped, never predicated: a branch around a load makes the compiler drain the whole queue before the next use)
-    const int lane_c = valid ? lane : P - 1;
-    auto fetch = [&](int blk) { return T[(size_t)min(blk, Tb - 1) * Ps + lane_c]; };
-#pragma unroll
-    for (int k = 0; k < kDepth; k++) ring[k] = fetch(k);
-    float pv = 0.0f;
-    const int nchunk = (Tb + kTbChunk - 1) / kTbChunk;
-    for (int c = 0; c < nchunk; c++) {
-        const int c0 = c * kTbChunk, n = min(kTbChunk, Tb - c0);
-        for (int b0 = 0; b0 < n; b0 += kDepth) {
-            float cur[kDepth];
-#pragma unroll
-            for (int k = 0; k < kDepth; k++) cur[k] = ring[k];
-#pragma unroll
-            for (int k = 0; k < kDepth; k++) ring[k] = fetch(c0 + b0 + kDepth + k);
-#pragma unroll
-            for (int k = 0; k < kDepth; k++) {
-                if (b0 + k >= n) break;
-                // The chain carries the VALUE only: max is exact, so the winner can be identified afterwards as the lowest
-                // from-state whose candidate equals the maximum (= the reference's scan with its strict >), from a ballot, off
-                // the critical path.  Chain per block: one add, three max over DPP partners, one ds_bpermute.
-                const float cand = valid ? cur[k] + pv : NEG;
-                float v = cand;
-                const float o4 = xor4_f(v);
-                bool moved = false;
-                if (!flip) {
-                    // flop pair (lanes 32..39): partner = lane ^ 4; the stay entry is the one with from >= 4; stay unless move is strictly greater
-                    const bool i_am_stay = (lane & 4) != 0;
-                    const float stay = i_am_stay ? v : o4, move = i_am_stay ? o4 : v;
-                    moved = move > stay;
-                    v = moved ? move : stay;
-                } else {
-                    v = fmaxf(v, o4);
-                    v = fmaxf(v, xor1_f(v));
-                    v = fmaxf(v, xor2_f(v));
-                }
-                // NaN scores (never produced by the network, possible through ffhip_viterbi): the reference's scan starts from
-                // the from-state-0 candidate and replaces it only on a strict >, so a NaN there stays the maximum while NaNs
-                // elsewhere are skipped; fmaxf skips them all.  Rare and wave-uniform, so the chain pays one scalar branch.
-                if (__builtin_expect(__ballot(cand != cand) != 0ull, 0)) {
-                    const float c0 = __shfl(cand, lane & ~7);
-                    if (flip && c0 != c0) v = c0;
-                }
-                const unsigned eq = (unsigned)__ballot(flip && cand == v);                  // bit 8*to + from
-                const unsigned mv = (unsigned)(__ballot(!flip && valid && moved) >> 32);    // bit (b2 - 4) [and bit b2] of flop state b2
-                const int src = ff8_src_lane(st);
-                pv = __shfl(v, src);
-                int arg = 0;
-                if (lane < nbase) { const unsigned m = (eq >> (8 * lane)) & 0xffu; arg = m ? __builtin_ctz(m) : 0; }    // empty (NaN maximum): state 0, as the reference's scan
-                else if (lane < ns) arg = ((mv >> (lane - nbase)) & 1u) ? lane - nbase : lane;
-                if (lane < ns) tb_lds[(b0 + k) * kMaxState + lane] = (uint8_t)arg;
-            }
-        }
-        if (c + 1 < nchunk) {             // a longer read: this chunk's bytes leave LDS (kTbChunk is a multiple of kDepth: the ring stays aligned)
-            __syncthreads();
-            for (int i = lane; i < n * (kMaxState / 4); i += 64)
-                ((uint32_t *)(tb + (size_t)c0 * kMaxState))[i] = ((const uint32_t *)tb_lds)[i];
-            __syncthreads();
-        }
-    }
-    float score = __shfl(pv, 0);
-    int last = 0;
-    for (int s2 = 1; s2 < ns; s2++) {
-        const float v = __shfl(pv, s2);
-        if (v > score) { score = v; last = s2; }
-    }
-    if (lane == 0) { score_out[blockIdx.x] = score; qp[0] = NAN; }
-    __syncthreads();
-    // traceback, last chunk first (it is still in LDS)
-    for (int c = nchunk - 1; c >= 0; c--) {
-        const int c0 = c * kTbChunk, n = min(kTbChunk, Tb - c0), c1 = c0 + n;
-        if (c != nchunk - 1) {
-            for (int i = lane; i < n * (kMaxState / 4); i += 64)
-                ((uint32_t *)tb_lds)[i] = ((const uint32_t *)(tb + (size_t)c0 * kMaxState))[i];
-            __syncthreads();
-        }
-        if (lane == 0) {
-            int p = last;
-            path_lds[n] = p;
-            for (int i = n; i > 0; i--) { p = tb_lds[(i - 1) * kMaxState + p]; path_lds[i - 1] = p; }
-        }
-        __syncthreads();
-        if (c1 == Tb && lane == 0) pth[Tb] = path_lds[n];
-        for (int i = lane; i < n; i += 64) {
-            const int from = path_lds[i], to = path_lds[i + 1];
-            pth[c0 + i] = from;
-            const int idx = (to < nbase) ? (to * ns + from) : (off + from);
-            qp[c0 + i + 1] = T[(size_t)(c0 + i) * Ps + idx];
-        }
-        last = path_lds[0];
-        __syncthreads();
-    }
-}
-
-// Viterbi for nstate == 10 (the 5-base models, r941_5mC): the scheme of k_viterbi8 with two candidates per lane.  Flip
+// Viterbi for nstate == 10 (the 5-base models, r941_5mC) at a score stride other than 60 (launch_viterbi10x takes Ps = 60).  Nothing on the
+// chain waits for memory: the traceback bytes go to LDS (chunks of kTbChunk blocks; earlier chunks of longer reads are flushed to HBM
+// with wide stores) and the scores of the next kDepth blocks are in flight.  Two candidates per lane.  Flip
 // destination g (0..4) owns lanes 8g..8g+7, lane j holding its candidates from states j and j+8 (j < 2); lanes 40..44 hold
 // the stay / move pair of flop state 5+j.  The chain carries the value only (local max, three DPP exchanges, two
 // ds_bpermute to hand the new vector out); the winner -- lowest from-state among equals for a flip, stay unless the move is
@@ -2264,7 +2132,9 @@ k_viterbi10(const float *__restrict__ M, uint8_t *__restrict__ tbbuf, int *__res
                     moved = a1 > a0;                              // stay unless the move is strictly greater
                     v = moved ? a1 : a0;
                 }
-                if (__builtin_expect(__ballot(a0 != a0 || a1 != a1) != 0ull, 0)) {      // NaN scores: see k_viterbi8
+                // NaN scores (never produced by the network, possible through ffhip_viterbi): the reference's scan starts from the from-state-0
+                // candidate and replaces it only on a strict >, so a NaN there stays the maximum while NaNs elsewhere are skipped; fmaxf skips them all
+                if (__builtin_expect(__ballot(a0 != a0 || a1 != a1) != 0ull, 0)) {
                     const float c0 = __shfl(a0, lane & ~7);
                     if (flip && c0 != c0) v = c0;
                 }
@@ -2327,11 +2197,9 @@ k_viterbi10(const float *__restrict__ M, uint8_t *__restrict__ tbbuf, int *__res
 void launch_viterbi(hipStream_t s, const float *score_mat, uint8_t *tb, int *path, float *qpath, float *score,
                     int nread, int Tb, int nbase, int Ps, const int *tbs, ReadMap map) {
     const int P = 2 * nbase * (nbase + 1);
-    if (nbase == 4 && Ps == 40 && !dbg("decode_r2"))
+    if (nbase == 4 && Ps == 40)
         launch_viterbi8x(s, score_mat, tb, path, qpath, score, nread, Tb, tbs, map);
-    else if (nbase == 4 && Ps == 40)
-        hipLaunchKernelGGL(k_viterbi8, dim3(nread), dim3(64), 0, s, score_mat, tb, path, qpath, score, Tb, tbs);
-    else if (nbase == 5 && Ps == 60 && !dbg("exact_order") && !dbg("decode_r2"))
+    else if (nbase == 5 && Ps == 60 && !dbg("exact_order"))
         launch_viterbi10x(s, score_mat, tb, path, qpath, score, nread, Tb, tbs, map);
     else if (nbase == 5 && !dbg("exact_order"))
         hipLaunchKernelGGL(k_viterbi10, dim3(nread), dim3(64), 0, s, score_mat, tb, path, qpath, score, Tb, Ps, tbs);

@@ -1520,17 +1520,11 @@ bool split_supported(int kind, int H) { return (kind == 0 || kind == 1) && H % 1
 // L2, sweep, gate math), so the reads in flight per launch are what sets its throughput.
 // H = 384 (LSTM): the dense pair form k_lstm_split<0, 3, 2, true> -- 128 registers, 77 KiB of LDS, two workgroups per CU: a launch takes
 // 512 reads, and the launches of two 256-read batches in flight run BESIDE each other instead of one after the other
-// (FFHIP_SPLIT_DENSE=0: the one-tile form)
-static bool split_dense3(int kind, int H) {
-    const char *e = dbg("split_dense");
-    return kind == 0 && H == 384 && kSplitF16 && !(e && e[0] == '0') && !dbg("split_ts");
-}
+// (FFHIP_DEBUG=no_dense: no launch takes a dense form, paired launches included)
+static bool split_dense3(int kind, int H) { return kind == 0 && H == 384 && kSplitF16 && !dbg("no_dense"); }
 // H = 256 (LSTM and GRUmod): the dense pair form needs 79 registers and 53 KiB there -- THREE workgroups per CU, six 16-read recurrences,
-// 768 reads per launch (FFHIP_DENSE256=0: at most the two-workgroup form of round 2, 512 reads)
-static bool split_dense256(int H) {
-    const char *e = dbg("dense256");
-    return H == 256 && kSplitF16 && !(e && e[0] == '0') && !dbg("split_ts") && !dbg("no_dense");
-}
+// 768 reads per launch
+static bool split_dense256(int H) { return H == 256 && kSplitF16 && !dbg("no_dense"); }
 // H = 256: the packed forms (lstm_split_body's PACK; k_grumod_pack, k_lstm_pack) -- 16 members a group, 128 registers, two workgroups a CU: a
 // FULL launch takes 8 * (ncu / 32) tiles, 1024 reads on 256 CUs; their weights are the second half of the layer's pack (FFHIP_NO_PACK: never)
 static bool split_pack256(int kind, int H) { return (kind == 0 || kind == 1) && split_dense256(H) && !dbg("no_pack"); }
@@ -1552,7 +1546,7 @@ int split_next_launch_tiles(int kind, int H, int remaining, int ncu) {
 // `beside`: another batch is between run and finish -- its layer launches are on the chip; the dense form runs BESIDE them
 static bool split_launch_dense256(int H, int nrt, int ncu) { return split_dense256(H) && nrt > 4 * (ncu / 32); }
 static bool split_launch_dense3(int kind, int H, int nrt, int ncu, int beside) {
-    return split_dense3(kind, H) && (nrt > 2 * (ncu / 32) || beside || dbg("split_dense_always"));      // (the variable: development)
+    return split_dense3(kind, H) && (nrt > 2 * (ncu / 32) || beside);
 }
 static int split_launch_ts(int kind, int H, int nrt, int ncu, int beside) {
     // the dense forms (two workgroups per CU, a pair of tiles each) take launches with more tiles than the one-tile form can:
@@ -1578,11 +1572,7 @@ size_t split_flag_words(int nrt) { return (size_t)nrt * 32; }
 // 16-byte pieces of a layer's classic pack [2 matrices][H / 4 unit tiles][H / 32 chunks][slices][64 lanes]: the gate-major pack of the packed
 // GRUmod form ([2][3 H / 16 row tiles][H / 32][slices][64]) follows it
 size_t split_pack_offset(int H) { return (size_t)2 * (H / 4) * (H / 32) * NS * 64; }
-int split_tiles_per_group(int kind, int H) {
-    const char *force = dbg("split_ts");      // development: 1 or 2
-    if (force && (force[0] == '1' || force[0] == '2') && H < 512) return force[0] - '0';
-    return kSplitTS[kind & 1][H / 128 - 1];
-}
+int split_tiles_per_group(int kind, int H) { return kSplitTS[kind & 1][H / 128 - 1]; }
 
 unsigned long long *g_split_dbg = nullptr;
 #ifdef FFHIP_PHASES
@@ -1600,16 +1590,26 @@ extern "C" int ffhip_debug_phases(unsigned long long *out, int reset) {
 namespace ffhip {
 #endif
 
-// one launch for the layers of two batches (the dense form at H = 384 only); false: shapes this does not take -- launch them one by one
+// paired launches (k_lstm_split_pair, the dense form at H = 384 only) of two batches of nrt read tiles each: the second batch's block indices
+// start at a multiple of the 8 XCDs
+bool split_pair_ok(int kind, int H, int nrt, int ncu) {
+#ifdef FFHIP_SPLIT_BF16X3
+    return false;
+#else
+    return split_dense3(kind, H) && !dbg("no_pair") && nrt >= 1 && nrt <= 2 * (ncu / 32) && (((nrt + 1) / 2) & 7) == 0;
+#endif
+}
+
+// one launch for the layers of two batches; false: shapes split_pair_ok refuses -- launch them one by one
 bool launch_lstm_split_pair(hipStream_t s, int kind, int H, int ncu, const SplitLaunch &p0, const SplitLaunch &p1) {
 #ifdef FFHIP_SPLIT_BF16X3
     return false;
 #else
-    if (!split_dense3(kind, H) || dbg("no_pair") || p0.nrt > 2 * (ncu / 32) || p1.nrt > 2 * (ncu / 32) || p0.nrt < 1 || p1.nrt < 1) return false;
+    if (!split_pair_ok(kind, H, p0.nrt, ncu)) return false;
     auto mk = [&](const SplitLaunch &p) {
         SplitArgs a;
         a.epoch = p.epoch; a.acc_scale = split_pow2(p.scale_exp); a.scale_exp = p.scale_exp; a.fast_gates = p.fast_gates;
-        a.split_gate = dbg("no_split_gate") ? 0 : 1;
+        a.split_gate = 1;
         a.Wp = (const v4u *)p.Wp; a.bias = p.bias; a.xin = (const unsigned char *)p.xin; a.hout = (unsigned char *)p.hout; a.hout_f32 = p.hout_f32;
         a.flags = p.flags; a.abort_word = p.abort_word;
         a.Tb = p.Tb; a.B16 = p.B16; a.H = H; a.rt0 = p.rt0; a.nrt = p.nrt; a.backward = p.backward; a.mode = p.mode;
@@ -1617,7 +1617,6 @@ bool launch_lstm_split_pair(hipStream_t s, int kind, int H, int ncu, const Split
         return a;
     };
     const int g0 = (p0.nrt + 1) / 2, g1 = (p1.nrt + 1) / 2;
-    if ((g0 & 7) != 0) return false;              // (the second batch's block indices must start at a multiple of the 8 XCDs)
     // the two batches share everything but their buffers: same model (weights, exponents), same capacity and tile count
     if (p0.Wp != p1.Wp || p0.bias != p1.bias || p0.Tb != p1.Tb || p0.B16 != p1.B16 || p0.rt0 != p1.rt0 || p0.nrt != p1.nrt || p0.backward != p1.backward ||
         p0.mode != p1.mode || p0.scale_exp != p1.scale_exp || p0.fast_gates != p1.fast_gates || (p0.hout_f32 == nullptr) != (p1.hout_f32 == nullptr) ||
@@ -1641,7 +1640,7 @@ bool launch_lstm_split(hipStream_t s, int kind, const void *Wp, const float *bia
     a.acc_scale = split_pow2(scale_exp);
     a.scale_exp = scale_exp;
     a.fast_gates = fast_gates;
-    a.split_gate = dbg("no_split_gate") ? 0 : 1;
+    a.split_gate = 1;
     a.Wp = (const v4u *)Wp; a.bias = bias; a.xin = (const unsigned char *)xin; a.hout = (unsigned char *)hout; a.hout_f32 = hout_f32;
     a.flags = flags; a.abort_word = abort_word;
     a.Tb = Tb; a.B16 = B16; a.H = H; a.rt0 = rt0; a.nrt = nrt; a.backward = backward; a.mode = mode;

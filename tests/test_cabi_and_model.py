@@ -91,6 +91,32 @@ def test_release_library_has_no_test_hook_and_few_switches():
         assert b"FFHIP_DEBUG_HOST_REHEARSAL_MSPS" in open(hooks, "rb").read()
 
 
+def test_debug_tokens_are_the_documented_few():
+    """FFHIP_DEBUG keeps only the switches that cross-check a path, that tests use or that bench.py sets: the dbg("...") calls of the library,
+    dbg()'s table of known tokens (an unknown one is reported on stderr) and INTEGRATION.md's token table name the same tokens, at most 14."""
+    import re
+    csrc = os.path.join(ROOT, "flappie_amd", "csrc")
+    used = set()
+    for fn in os.listdir(csrc):
+        if fn.endswith((".hip", ".hpp")):
+            used |= set(re.findall(r'dbg\("([a-z_0-9]+)"\)', open(os.path.join(csrc, fn)).read()))
+    engine = open(os.path.join(csrc, "ffhip_engine.hip")).read()
+    known = set(re.findall(r'"([a-z_0-9]+)"', re.search(r"kDebugTokens\[\] = \{(.*?)\};", engine, re.S).group(1)))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read().split("`FFHIP_DEBUG` tokens", 1)[1].splitlines()[1:]
+    rows = []
+    for line in doc:
+        if rows and not line.startswith("|"):
+            break
+        if line.startswith("|"):
+            rows.append(line)
+    documented = set()
+    for row in rows[2:]:                      # (header and rule)
+        documented |= set(re.findall(r"`([a-z_0-9]+)[^`]*`", re.split(r"(?<!\\)\|", row)[1]))
+    assert used == known, (sorted(used - known), sorted(known - used))
+    assert used == documented, (sorted(used - documented), sorted(documented - used))
+    assert len(used) <= 14, sorted(used)
+
+
 @pytest.mark.parametrize("kind,hidden", [(M.NET_LSTM5, 32), (M.NET_GRUMOD5, 48)])
 def test_mdl_roundtrip(tmp_path, kind, hidden):
     mdl = M.synthetic_model(kind, hidden, seed=3, ident="r941native" if kind == M.NET_LSTM5 else "r941native5mC")

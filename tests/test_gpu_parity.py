@@ -290,7 +290,7 @@ def test_other_baseline_configs_properties(B, engine, label, kind, H, nread, T, 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind,hidden", [(M.NET_GRUMOD5, 64), (M.NET_LSTM5, 64)])
 def test_decode_kernels_agree_with_their_chain_order_forms(B, engine, kind, hidden):
-    """The butterfly decode kernels (k_transpost8/10, k_viterbi8/10) against the chain-order / generic forms selected by
+    """The decode kernels of the default path (k_crf_fb, k_viterbi8x / k_viterbi10x) against the chain-order / generic forms selected by
     FFHIP_DEBUG=exact_order: the same Viterbi paths, qualities and calls; posteriors equal up to the rounding of the summation order."""
     mdl = M.synthetic_model(kind, hidden, seed=21)
     dm = B.DeviceModel(engine, mdl)

@@ -92,7 +92,7 @@ def test_paired_headline_launches_repeat_bit_for_bit(eng):
             out.append(_results(bs[k], nread))
         return out
 
-    ref = _with_debug("no_dense,no_pair,split_dense=0", alone)
+    ref = _with_debug("no_dense,no_pair", alone)
     deviating = []
     for rep in range(REPS):
         for k in (0, 1):
@@ -137,7 +137,7 @@ def test_paired_launches_of_packed_batches_repeat_bit_for_bit(eng):
             out.append(_results(bs[k], bs[k].nreads()))
         return out
 
-    ref = _with_debug("no_dense,no_pair,split_dense=0", alone)
+    ref = _with_debug("no_dense,no_pair", alone)
     deviating = []
     for rep in range(REPS):
         for k in (0, 1):

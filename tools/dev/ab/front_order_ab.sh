@@ -10,7 +10,6 @@ PY
 }
 for rep in 1 2; do
 one "c2 batch-order, 2 streams" "FFHIP_DEBUG=front_order=batch,streams=2" "--config c2"
-one "c2 layer-order, no decode wait" "FFHIP_DEBUG=no_decode_wait" "--config c2"
 one "c2 layer-order, 4 streams" "FFHIP_DEBUG=streams=4" "--config c2"
 one "rle layer-order, 4 streams" "FFHIP_DEBUG=streams=4" "--config rle"
 one "rle batch-order, 2 streams" "FFHIP_DEBUG=front_order=batch,streams=2" "--config rle"
