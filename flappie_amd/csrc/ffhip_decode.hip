@@ -363,13 +363,13 @@ k_post_fb(float *__restrict__ trans, float *__restrict__ post, const double *__r
 // its own base; fwd / bwd = log of the stored vector + its offset, formed in fp64 and rounded once
 __global__ void __launch_bounds__(256)
 k_rle_post8(const float *__restrict__ param, float *__restrict__ post, const double *__restrict__ fwdbuf, const double *__restrict__ bwdbuf, int TbS,
-            const int *__restrict__ tbs) {
+            const int *__restrict__ tbs, ReadMap map) {
     FFHIP_DECODE_PRIO_SET();
     constexpr int Ps = 40, RS = 10;
     const int read = blockIdx.y;
+    const size_t row0 = map.row0(read, TbS), row1 = map.row1(read, TbS);
     const int Tb = tbs ? tbs[read] : TbS;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane >> 4, sub = lane & 15;
-    if ((int)blockIdx.x * kPostBlocks >= Tb) return;
     const bool has = sub < 10;
     int lf_src[4], lb_src[4];
 #pragma unroll
@@ -378,13 +378,15 @@ k_rle_post8(const float *__restrict__ param, float *__restrict__ post, const dou
         const int to = ((from & 3) != tb) ? tb : tb + 4;
         lf_src[e] = 4 * (16 * grp + from); lb_src[e] = 4 * (16 * grp + to);
     }
+    // (one pass but in a packed batch, whose grid is sized for its mean read: a longer read's workgroups stride over it)
+    for (int b0 = (int)blockIdx.x * kPostBlocks; b0 < Tb; b0 += (int)gridDim.x * kPostBlocks)
     for (int round = 0; round < 4; round++) {
-        const int blk = blockIdx.x * kPostBlocks + (round * 4 + wave) * 4 + grp;
+        const int blk = b0 + (round * 4 + wave) * 4 + grp;
         const bool live = blk < Tb;
         const int bc = min(blk, Tb - 1);
-        const float4 x = *((const float4 *)(param + ((size_t)read * TbS + bc) * Ps) + min(sub, 9));
+        const float4 x = *((const float4 *)(param + (row0 + bc) * Ps) + min(sub, 9));
         const int st = min(sub, 7);
-        const double *fr = fwdbuf + ((size_t)read * (TbS + 1) + bc) * RS, *br = bwdbuf + ((size_t)read * (TbS + 1) + bc + 1) * RS;
+        const double *fr = fwdbuf + (row1 + bc) * RS, *br = bwdbuf + (row1 + bc + 1) * RS;
         const double va = fr[st], vb = br[st], ca = fr[8], cb = br[8];
         // log(v) = log(mantissa) + e ln2 (a zero: -inf, an unreachable state)
         const float lf = va > 0.0 ? (float)((double)__builtin_amdgcn_frexp_exp(va) * 0.693147180559945309417232121458 + (double)logf((float)__builtin_amdgcn_frexp_mant(va)) + ca) : -INFINITY;
@@ -397,16 +399,19 @@ k_rle_post8(const float *__restrict__ param, float *__restrict__ post, const dou
             const float b = __int_as_float(__builtin_amdgcn_ds_bpermute(lb_src[e], __float_as_int(lb)));
             v[e] = (4 * sub + e < 8) ? xs[e] : (f + b) + xs[e];
         }
-        if (live && has) *((float4 *)(post + ((size_t)read * TbS + blk) * Ps) + sub) = make_float4(v[0], v[1], v[2], v[3]);
+        if (live && has) *((float4 *)(post + (row0 + blk) * Ps) + sub) = make_float4(v[0], v[1], v[2], v[3]);
     }
 }
 
-// run-length posterior of nbase = 4, stride-40 reads: E (k_crf_exp of the 32 transition rows, stride 40 doubles), the two chains, the assembly
-void launch_rle_post8(hipStream_t s, const float *param, float *post, double *E, double *fwd, int nread, int Tb, const int *tbs) {
-    launch_crf_exp(s, param, E, nread, Tb, 4, 40, tbs, nullptr, 0.0f, 8, 32);
-    double *bwd = fwd + (size_t)nread * (Tb + 1) * 10;
-    hipLaunchKernelGGL((k_crf_fb<8, 1>), dim3(nread), dim3(128), 0, s, E, fwd, bwd, Tb, (double *)nullptr, tbs, 2, (const int *)nullptr, ReadMap());
-    hipLaunchKernelGGL(k_rle_post8, dim3((Tb + kPostBlocks - 1) / kPostBlocks, nread), dim3(256), 0, s, param, post, fwd, bwd, Tb, tbs);
+// run-length posterior of nbase = 4, stride-40 reads: E (k_crf_exp of the 32 transition rows, stride 40 doubles), the two chains, the assembly.  E goes row-wise over
+// the nrow rows (a packed batch's gap blocks are computed and never read); the chains and the assembly go per read
+void launch_rle_post8(hipStream_t s, const float *param, float *post, double *E, double *fwd, int nrow, int Tb, const int *tbs,
+                      int nread, const int *tbr, ReadMap map, int gblk) {
+    if (nread <= 0) { nread = nrow; tbr = tbs; gblk = Tb; }
+    launch_crf_exp(s, param, E, nrow, Tb, 4, 40, tbs, nullptr, 0.0f, 8, 32);
+    double *bwd = fwd + (size_t)nrow * (Tb + 1) * 10;
+    hipLaunchKernelGGL((k_crf_fb<8, 1>), dim3(nread), dim3(128), 0, s, E, fwd, bwd, Tb, (double *)nullptr, tbr, 2, (const int *)nullptr, map);
+    hipLaunchKernelGGL(k_rle_post8, dim3((gblk + kPostBlocks - 1) / kPostBlocks, nread), dim3(256), 0, s, param, post, fwd, bwd, Tb, tbr, map);
 }
 
 // ---- runlengthV2_partition_function (layers.c:1255-1302) on the alternating layouts, in LOG space -----------------------------------------------
@@ -428,11 +433,11 @@ __device__ __forceinline__ double fmax_hi3_d(double v) {
 }
 
 __global__ void __launch_bounds__(64)
-k_rle_partition8x(const float *__restrict__ param, int TbS, double *__restrict__ logz, const int *__restrict__ tbs) {
+k_rle_partition8x(const float *__restrict__ param, int TbS, double *__restrict__ logz, const int *__restrict__ tbs, ReadMap map) {
     FFHIP_CHAIN_PRIO_SET();
     constexpr int Ps = 40, nbase = 4;
     const int lane = threadIdx.x, g = lane >> 3, j = lane & 7;
-    const float *T = param + (size_t)blockIdx.x * TbS * Ps + 2 * nbase;
+    const float *T = param + map.row0(blockIdx.x, TbS) * Ps + 2 * nbase;
     const int Tb = tbs ? tbs[blockIdx.x] : TbS;
     if (Tb <= 0) return;
     const double NEG = -HUGE_VAL;
@@ -492,8 +497,8 @@ k_rle_partition8x(const float *__restrict__ param, int TbS, double *__restrict__
     if (lane == 0) logz[blockIdx.x] = z;
 }
 
-void launch_rle_partition8x(hipStream_t s, const float *param, double *logz, int nread, int Tb, const int *tbs) {
-    hipLaunchKernelGGL(k_rle_partition8x, dim3(nread), dim3(64), 0, s, param, Tb, logz, tbs);
+void launch_rle_partition8x(hipStream_t s, const float *param, double *logz, int nread, int Tb, const int *tbs, ReadMap map) {
+    hipLaunchKernelGGL(k_rle_partition8x, dim3(nread), dim3(64), 0, s, param, Tb, logz, tbs, map);
 }
 
 // flags: 1 = subtract (float)(logZ / Tb) from the scores, 2 = posterior wanted; logz: device doubles per read (required with flags & 1)
@@ -988,8 +993,8 @@ void launch_viterbi8x(hipStream_t s, const float *score_mat, uint8_t *tb, int *p
     hipLaunchKernelGGL(k_viterbi8x<0>, dim3(nread), dim3(64), 0, s, score_mat, tb, path, qpath, score, Tb, tbs, map);
 }
 // decode_crf_runlength for nbase = 4, stride 40 (param: shape / scale rows + 32 transition scores a block)
-void launch_rle_viterbi8x(hipStream_t s, const float *param, uint8_t *tb, int *path, float *qpath, float *score, int nread, int Tb, const int *tbs) {
-    hipLaunchKernelGGL(k_viterbi8x<1>, dim3(nread), dim3(64), 0, s, param, tb, path, qpath, score, Tb, tbs, ReadMap());
+void launch_rle_viterbi8x(hipStream_t s, const float *param, uint8_t *tb, int *path, float *qpath, float *score, int nread, int Tb, const int *tbs, ReadMap map) {
+    hipLaunchKernelGGL(k_viterbi8x<1>, dim3(nread), dim3(64), 0, s, param, tb, path, qpath, score, Tb, tbs, map);
 }
 
 }  // namespace ffhip

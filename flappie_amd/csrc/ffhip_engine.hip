@@ -613,15 +613,17 @@ extern "C" size_t ffhip_model_nblock(const ffhip_model *m, size_t nsample) {
 // and plan_run (the whole path of a run, once, at its front).  What the engine is doing -- batches in flight, its last layer launch -- is an input
 // of neither: those decisions stay where they fall in the enqueue sequence (run_front, run_layers, ffhip_batch_run_pair).
 static bool flipflop8_10(const ffhip_model *m) { return (m->nbase == 4 && m->Ps == 40) || (m->nbase == 5 && m->Ps == 60); }
+static bool rle8(const ffhip_model *m) { return m->kind == FFHIP_NET_LSTM5_RLE && m->nbase == 4 && m->Ps == 40; }      // the run-length model of the fp64 chains (ffhip_decode.hip)
 // split: the split-operand layer kernel with the fused projection (ffhip_rnn_split.hip), the default wherever it exists; packable: ... and a packed batch may take
-// the run at an ordinary temperature (RunPath::post_done); pairable: ... and two batches of pair_tiles read tiles each may share layer launches (split_pair_ok)
+// the run at an ordinary temperature (RunPath::post_done, or rle_post8 for the run-length model); pairable: ... and two batches of pair_tiles read tiles each may share
+// layer launches (split_pair_ok)
 struct ModelPath { bool split, packable, pairable; };
 static ModelPath model_path(const ffhip_model *m, unsigned flags, int ncu, int pair_tiles = 0) {
     ModelPath p;
     p.split = !(flags & (FFHIP_RUN_STEPWISE_RNN | FFHIP_RUN_UNFUSED_RNN | FFHIP_RUN_F32_RNN)) && persist_supported(m->cell, m->Hp, ncu) &&
               split_supported(m->cell, m->Hp) && m->rnn[0].Wsplit != nullptr && !dbg("no_split") && !dbg("no_fuse");
     const bool lean = p.split && !(flags & FFHIP_RUN_KEEP_ACTS);
-    p.packable = lean && m->conv[m->nconv - 1].Mpad == m->Hp && m->kind != FFHIP_NET_LSTM5_RLE && flipflop8_10(m);
+    p.packable = lean && m->conv[m->nconv - 1].Mpad == m->Hp && (m->kind == FFHIP_NET_LSTM5_RLE ? rle8(m) : flipflop8_10(m));
     p.pairable = lean && split_pair_ok(m->cell, m->Hp, pair_tiles, ncu);
     return p;
 }
@@ -654,8 +656,8 @@ static RunPath plan_run(const ffhip_model *m, unsigned flags, float temperature,
     p.R = dbg("crf_logspace") ? 0 : crf_rescale_interval(5.0f / temperature);
     p.post_done = m->kind != FFHIP_NET_LSTM5_RLE && p.R > 0 && flipflop8_10(m) && 10.0f / temperature <= kFbRange;
     p.head_e = p.split_head && p.post_done && head_split_writes_E(m->P);
-    p.rle_post8 = m->kind == FFHIP_NET_LSTM5_RLE && m->nbase == 4 && m->Ps == 40 && 10.0f / temperature <= kFbRange;
-    p.packable = mp.packable && p.post_done;
+    p.rle_post8 = rle8(m) && 10.0f / temperature <= kFbRange;
+    p.packable = mp.packable && (m->kind == FFHIP_NET_LSTM5_RLE ? p.rle_post8 : p.post_done);      // (no packed form of k_rle_transpost / k_rle_partition)
     p.gates = gate_level(flags);
     p.rnn_path = p.split ? 3 : (p.split2 ? 4 : (p.persist ? (p.fused ? 2 : 1) : 0));
     return p;
@@ -1420,7 +1422,7 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
     b->run_path = plan_run(m, flags, temperature, ncu);
     const RunPath &p = b->run_path;
     if (b->packed && !p.packable)
-        return set_err(FFHIP_EINVAL, "packed batches take the default path only (flip-flop model with 128 .. 512 hidden units, no kept activations, no f32 / stepwise / unfused flags, ordinary temperature)");
+        return set_err(FFHIP_EINVAL, "packed batches take the default path only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / stepwise / unfused flags, ordinary temperature)");
     // act[0]: the convolution's fp32 output (every path but split layers behind a split-writing convolution); act[1]: the last layer's fp32 copy for the f32 head
     for (int i = p.conv_split ? 1 : 0; i < ((p.split_head && p.conv_split) ? 1 : 2); i++)
         if (!b->act[i] && !(b->act[i] = (float *)dalloc(b, (size_t)Tb * Bp * Hp * 4, false))) return FFHIP_ENOMEM;
@@ -1609,6 +1611,8 @@ static int run_back(ffhip_batch *b) {
     const int *tbs = b->ragged ? b->d_tbs : nullptr, *tbr = b->packed ? b->d_vtb : tbs;
     ReadMap rmap;
     if (b->packed) { rmap.b0 = b->d_vb0; rmap.b1 = b->d_vb1; rmap.nslot = b->nread; }
+    int gblk = Tb;                      // blocks per read the grids of the run-length model's per-read block kernels are sized for (a packed batch: its mean read)
+    if (b->packed && nR > 0) { size_t sum = 0; for (int v = 0; v < nR; v++) sum += (size_t)b->hTb[v]; gblk = (int)((sum + nR - 1) / nR); }
     b->profiled = eng->profiling != 0;
     b->final_act = cur;
     b->rnn_path = p.rnn_path;
@@ -1618,7 +1622,9 @@ static int run_back(ffhip_batch *b) {
         // ---- globalnorm_runlengthV2 (layers.c:1325-1358)
         if (p.split_head) launch_head_split(s, b->actS[cur], b->trans, m->FFsplit, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 32, 1.0f, m->FF_split_S, 1);
         else launch_head(s, b->act[cur], b->trans, m->FFp, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 16, 1.0f, 1);
-        launch_rle_head_finish(s, b->trans, b->crf_logz, b->nread, Tb, m->nbase, m->Ps, temperature, tbs);
+        if (b->packed) { HIP_TRY(hipEventRecord(eng->head_done, s), FFHIP_EHIP); eng->head_done_rec = 1; }      // (as below: apply_packed)
+        // activation over the slots' rows; partition function and subtraction per read
+        launch_rle_head_finish(s, b->trans, b->crf_logz, b->nread, Tb, m->nbase, m->Ps, temperature, tbs, nR, tbr, rmap, gblk);
         b->launches[3] += 4;
     } else {
         // ---- globalnorm_flipflop (layers.c:1082-1106)
@@ -1642,7 +1648,7 @@ static int run_back(ffhip_batch *b) {
     if (!(flags & FFHIP_RUN_NO_DECODE)) {
         const float *scores = b->trans;
         if (!(flags & FFHIP_RUN_VITERBI_ONLY)) {
-            if (p.rle_post8) launch_rle_post8(s, b->trans, b->post, b->crf_e, (double *)b->fwd, b->nread, Tb, tbs);      // fp64 linear-space chains (ffhip_decode.hip)
+            if (p.rle_post8) launch_rle_post8(s, b->trans, b->post, b->crf_e, (double *)b->fwd, b->nread, Tb, tbs, nR, tbr, rmap, gblk);      // fp64 linear-space chains (ffhip_decode.hip)
             else if (rle) launch_rle_transpost(s, b->trans, b->post, b->fwd, b->nread, Tb, m->nbase, m->Ps, tbs);       // decode.c:1037-1159
             else if (!p.post_done) launch_transpost(s, b->trans, b->post, b->fwd, b->nread, Tb, m->nbase, m->Ps, tbs);
             scores = b->post;
@@ -1652,8 +1658,8 @@ static int run_back(ffhip_batch *b) {
         if (rle) {
             // decode_crf_runlength (decode.c:927-1013); the run records are formed from the path by the caller
             // (runnie.c:282-313), there are no base/quality strings or trace for this model
-            launch_rle_viterbi(s, scores, b->tb, b->path, b->qpath, b->score, b->nread, Tb, m->nbase, m->Ps, tbs);
-            HIP_TRY(hipMemsetAsync(b->lens, 0, (size_t)b->nread * 4, s), FFHIP_EHIP);
+            launch_rle_viterbi(s, scores, b->tb, b->path, b->qpath, b->score, nR, Tb, m->nbase, m->Ps, tbr, rmap);
+            HIP_TRY(hipMemsetAsync(b->lens, 0, (size_t)nR * 4, s), FFHIP_EHIP);
             HIP_TRY(hipMemsetAsync(b->bases, 0, (size_t)b->nread * (Tb + 1), s), FFHIP_EHIP);
             HIP_TRY(hipMemsetAsync(b->quals, 0, (size_t)b->nread * (Tb + 1), s), FFHIP_EHIP);
             b->launches[5]++;

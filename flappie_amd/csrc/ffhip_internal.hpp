@@ -172,13 +172,17 @@ constexpr size_t kFwdRowBytes = 10 * sizeof(double);   // per block and directio
 constexpr float kFbRange = 100.0f;       // max - min of a block's scores the scaled linear-space recursions take (fp64 range, scaling one pair of blocks behind)
 // row_off / P_override: the run-length model's 32 transition scores sit behind 8 other rows of its 40-float blocks
 void launch_crf_exp(hipStream_t s, const float *trans, double *E, int nread, int Tb, int nbase, int Ps, const int *tbs, int *wide, float limit, int row_off = 0, int P_override = 0);
-void launch_rle_partition8x(hipStream_t s, const float *param, double *logz, int nread, int Tb, const int *tbs);
-void launch_rle_post8(hipStream_t s, const float *param, float *post, double *E, double *fwd, int nread, int Tb, const int *tbs);
+// The run-length model's per-read kernels (nbase 4, stride 40).  nrow rows of Tb blocks (extents tbs) hold the head's output; the reads are nread = nrow reads a row
+// (tbr = tbs) unless given: a packed batch's reads, their blocks tbr and their rows (map); gblk = the blocks per read the grids of the block-parallel kernels (k_rle_sub,
+// k_rle_post8) are sized for -- Tb, or a packed batch's mean read: a longer read's workgroups stride over it.
+void launch_rle_partition8x(hipStream_t s, const float *param, double *logz, int nread, int Tb, const int *tbs, ReadMap map = ReadMap());
+void launch_rle_post8(hipStream_t s, const float *param, float *post, double *E, double *fwd, int nrow, int Tb, const int *tbs,
+                      int nread = 0, const int *tbr = nullptr, ReadMap map = ReadMap(), int gblk = 0);
 // ffhip_decode.hip: partition function (+ subtraction, flags & 1) and posterior (flags & 2) of 8- or 10-state reads from E in one launch; fwd = 2*nread*(Tb+1)*(2*nbase) doubles
 void launch_crf_fb(hipStream_t s, int nbase, const double *E, float *trans, float *post, double *fwd, int nread, int Tb, double *logz, const int *tbs,
                     int flags, const int *wide, ReadMap map = ReadMap());
 void launch_viterbi10x(hipStream_t s, const float *score_mat, uint8_t *tb, int *path, float *qpath, float *score, int nread, int Tb, const int *tbs, ReadMap map = ReadMap());
-void launch_rle_viterbi8x(hipStream_t s, const float *param, uint8_t *tb, int *path, float *qpath, float *score, int nread, int Tb, const int *tbs);
+void launch_rle_viterbi8x(hipStream_t s, const float *param, uint8_t *tb, int *path, float *qpath, float *score, int nread, int Tb, const int *tbs, ReadMap map = ReadMap());
 void launch_viterbi8x(hipStream_t s, const float *score_mat, uint8_t *tb, int *path, float *qpath, float *score, int nread, int Tb, const int *tbs, ReadMap map = ReadMap());
 // Viterbi + traceback + qpath
 void launch_viterbi(hipStream_t s, const float *score_mat, uint8_t *tb, int *path, float *qpath, float *score,
@@ -190,10 +194,13 @@ void launch_assemble(hipStream_t s, const int *path, const float *qpath, char *b
 void launch_trace(hipStream_t s, const float *post, int32_t *trace, int nread, int Tb, int nbase, int Ps, int is_log, const int *tbs = nullptr, ReadMap map = ReadMap());
 void launch_exp_inplace(hipStream_t s, float *x, size_t n);
 // run-length (runnie) head and decoders, ffhip_rle.hip: activation rows + runlengthV2 partition function + subtraction
-void launch_rle_head_finish(hipStream_t s, float *param, double *logz, int nread, int Tb, int nbase, int Ps, float temperature, const int *tbs = nullptr);
+// (a packed batch -- nread, tbr, map, gblk as for launch_rle_post8 -- needs nbase 4, stride 40)
+void launch_rle_head_finish(hipStream_t s, float *param, double *logz, int nrow, int Tb, int nbase, int Ps, float temperature, const int *tbs = nullptr,
+                            int nread = 0, const int *tbr = nullptr, ReadMap map = ReadMap(), int gblk = 0);
 void launch_rle_partition(hipStream_t s, const float *param, double *logz, int nread, int Tb, int nbase, int Ps, const int *tbs = nullptr);
 void launch_rle_transpost(hipStream_t s, const float *param, float *post, float *fwd, int nread, int Tb, int nbase, int Ps, const int *tbs = nullptr);
-void launch_rle_viterbi(hipStream_t s, const float *param, uint8_t *tb, int *path, float *qpath, float *score, int nread, int Tb, int nbase, int Ps, const int *tbs = nullptr);
+void launch_rle_viterbi(hipStream_t s, const float *param, uint8_t *tb, int *path, float *qpath, float *score, int nread, int Tb, int nbase, int Ps, const int *tbs = nullptr,
+                        ReadMap map = ReadMap());      // map: a packed batch's reads (nbase 4, stride 40)
 // first-generation run-length decoders (decode.c:552-892) on one matrix of 4 nbase rows; tb: 8 bytes a block, fwd / bwd: 8 floats a block (+1)
 void launch_rl1_viterbi(hipStream_t s, const float *param, uint8_t *tb, int *path, float *score, int nblk, int nbase, int Ps);
 void launch_rl1_posterior(hipStream_t s, const float *param, float *post, float *fwd, float *bwd, int nblk, int nbase, int Ps);

@@ -129,14 +129,18 @@ k_rle_partition(const float *__restrict__ param, int TbS, int nbase, int Ps, dou
     }
 }
 
-// rows [2*nbase, P) -= (float)(logZ / Tb)   (layers.c:1349-1356: `const float logZ = partition / (float)nc`)
+// rows [2*nbase, P) -= (float)(logZ / Tb)   (layers.c:1349-1356: `const float logZ = partition / (float)nc`); grid: blocks / 4, READ (a packed batch: its rows from the
+// map, and a grid sized for its mean read -- a longer read's workgroups stride over it; one pass otherwise)
 __global__ void __launch_bounds__(256)
-k_rle_sub(float *__restrict__ param, const double *__restrict__ logz, int TbS, int nbase, int P, int Ps, const int *__restrict__ tbs) {
-    const int blk = (int)blockIdx.x * 4 + (int)threadIdx.y, r = (int)blockIdx.y;      // (as k_rle_activate)
+k_rle_sub(float *__restrict__ param, const double *__restrict__ logz, int TbS, int nbase, int P, int Ps, const int *__restrict__ tbs, ReadMap map) {
+    const int blk0 = (int)blockIdx.x * 4 + (int)threadIdx.y, r = (int)blockIdx.y;      // (as k_rle_activate)
     const int Tb = tbs ? tbs[r] : TbS;
-    if (blk >= Tb) return;
+    if (blk0 >= Tb) return;
     const float z = (float)(logz[r] / (double)(float)Tb);
-    for (int p = 2 * nbase + (int)threadIdx.x; p < P; p += 64) param[((size_t)r * TbS + blk) * Ps + p] -= z;
+    for (int blk = blk0; blk < Tb; blk += (int)gridDim.x * 4) {
+        float *row = param + (map.row0(r, TbS) + blk) * Ps;
+        for (int p = 2 * nbase + (int)threadIdx.x; p < P; p += 64) row[p] -= z;
+    }
 }
 
 // transpost_crf_runlength: wave 0 forward, wave 1 backward, then one block per thread
@@ -606,12 +610,15 @@ k_rl1_mean(const float *__restrict__ param, const int *__restrict__ path, int *_
 
 }  // namespace
 
-void launch_rle_head_finish(hipStream_t s, float *param, double *logz, int nread, int Tb, int nbase, int Ps, float temperature, const int *tbs) {
+// the activation goes row-wise over the nrow rows (elementwise: a packed batch's gap blocks are computed and never read), the partition function and the subtraction per read
+void launch_rle_head_finish(hipStream_t s, float *param, double *logz, int nrow, int Tb, int nbase, int Ps, float temperature, const int *tbs,
+                            int nread, const int *tbr, ReadMap map, int gblk) {
     const int P = 2 * nbase * (nbase + 1);
-    hipLaunchKernelGGL(k_rle_activate, dim3((unsigned)((Tb + 7) / 8), (unsigned)nread), dim3(256), 0, s, param, Tb, nbase, P, Ps, temperature);
-    if (nbase == 4 && Ps == 40) launch_rle_partition8x(s, param, logz, nread, Tb, tbs);      // ffhip_decode.hip
-    else hipLaunchKernelGGL(k_rle_partition, dim3(nread), dim3(64), 0, s, param, Tb, nbase, Ps, logz, tbs);
-    hipLaunchKernelGGL(k_rle_sub, dim3((unsigned)((Tb + 3) / 4), (unsigned)nread), dim3(64, 4), 0, s, param, logz, Tb, nbase, P, Ps, tbs);
+    if (nread <= 0) { nread = nrow; tbr = tbs; gblk = Tb; }
+    hipLaunchKernelGGL(k_rle_activate, dim3((unsigned)((Tb + 7) / 8), (unsigned)nrow), dim3(256), 0, s, param, Tb, nbase, P, Ps, temperature);
+    if (nbase == 4 && Ps == 40) launch_rle_partition8x(s, param, logz, nread, Tb, tbr, map);      // ffhip_decode.hip
+    else hipLaunchKernelGGL(k_rle_partition, dim3(nread), dim3(64), 0, s, param, Tb, nbase, Ps, logz, tbr);      // (no packed form: the engine packs nbase 4, stride 40 only)
+    hipLaunchKernelGGL(k_rle_sub, dim3((unsigned)((gblk + 3) / 4), (unsigned)nread), dim3(64, 4), 0, s, param, logz, Tb, nbase, P, Ps, tbr, map);
 }
 
 void launch_rle_partition(hipStream_t s, const float *param, double *logz, int nread, int Tb, int nbase, int Ps, const int *tbs) {
@@ -624,8 +631,8 @@ void launch_rle_transpost(hipStream_t s, const float *param, float *post, float 
     hipLaunchKernelGGL(k_rle_transpost, dim3(nread), dim3(256), 0, s, param, post, fwd, fwd + (size_t)nread * (Tb + 1) * kMaxState, Tb, nbase, P, Ps, tbs);
 }
 
-void launch_rle_viterbi(hipStream_t s, const float *param, uint8_t *tb, int *path, float *qpath, float *score, int nread, int Tb, int nbase, int Ps, const int *tbs) {
-    if (nbase == 4 && Ps == 40) { launch_rle_viterbi8x(s, param, tb, path, qpath, score, nread, Tb, tbs); return; }      // ffhip_decode.hip
+void launch_rle_viterbi(hipStream_t s, const float *param, uint8_t *tb, int *path, float *qpath, float *score, int nread, int Tb, int nbase, int Ps, const int *tbs, ReadMap map) {
+    if (nbase == 4 && Ps == 40) { launch_rle_viterbi8x(s, param, tb, path, qpath, score, nread, Tb, tbs, map); return; }      // ffhip_decode.hip
     hipLaunchKernelGGL(k_rle_viterbi, dim3(nread), dim3(64), 0, s, param, tb, path, qpath, score, Tb, nbase, Ps, tbs);
 }
 

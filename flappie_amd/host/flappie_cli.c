@@ -524,6 +524,9 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
                 dwell = 1;
             }
             its[i]->rle_text = text;
+            n_called_reads++;                                  /* (FLAPPIE_CLI_TIMING's "basecalled:" line) */
+            n_called_samples += its[i]->res.rt.end - its[i]->res.rt.start;
+            n_raw_samples += its[i]->res.rt.n;
             its[i]->res.score = ffhip_batch_score(b, i);
             its[i]->res.nblock = nblock;
         }
@@ -714,7 +717,7 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
 #define NCHUNKBUF 4
 #define PACK_ROW_MAX ((size_t)1 << 18)      /* samples a row of a packed batch holds at most (262 144: workspace of a 512-row batch ~45 GB at 384 hidden units) */
 static int rs_chunk_cap = 0;                 /* reads a chunk holds at most (= reads a packed batch must take) */
-/* packed batches: models whose default path takes them (ffhip_model_packable), ordinary temperatures, the flip-flop caller (runnie's model has no packed form);
+/* packed batches: models whose default path takes them (ffhip_model_packable: the flip-flop models, and runnie's run-length model), ordinary temperatures;
  * FLAPPIE_DEBUG=no_pack keeps the one-read-a-row batches */
 static int pack_allowed(const struct ffhip_model *mdl) {
     static int v = -1;

@@ -320,8 +320,10 @@ int ffhip_batch_set_prepared(ffhip_batch *b, const ffhip_prep *prep, const int *
  * starting at a block offset of the caller's choice with at least ffhip_model_pack_gap() free blocks behind it.  Every read is still evaluated whole and
  * exactly as if it were alone (bit for bit what the one-read-a-row batch gives): the convolutions see zero padding either side of it, the recurrent
  * layers start from a zero state at its first block and, in the reverse layers, at its last; partition function, posterior, Viterbi, strings and trace
- * are per read.  Results are indexed by READ, 0 .. nread - 1 in the order of the set call.  The default path only (flip-flop models with 128 .. 512 hidden units;
- * no FFHIP_RUN_KEEP_ACTS / _F32_RNN / _STEPWISE_RNN / _UNFUSED_RNN): ffhip_batch_run says so otherwise.  ffhip_batch_run_pair takes packed batches too. */
+ * are per read.  Results are indexed by READ, 0 .. nread - 1 in the order of the set call.  The default path only (the 8- and 10-state flip-flop models and the
+ * run-length model FFHIP_NET_LSTM5_RLE of nbase 4, with 128 .. 512 hidden units; no FFHIP_RUN_KEEP_ACTS / _F32_RNN / _STEPWISE_RNN / _UNFUSED_RNN; a temperature of at
+ * least 0.1): ffhip_batch_run says so otherwise.  A packed run-length batch gives per read what one read a row gives: path, qpath, score, transitions and posterior, and
+ * no base / quality strings or trace.  ffhip_batch_run_pair takes packed batches too. */
 int ffhip_model_packable(const ffhip_model *mdl);         /* 1: this model's default path takes packed batches on this device */
 size_t ffhip_model_pack_gap(const ffhip_model *mdl);      /* free blocks a read of a packed row needs behind it */
 /* plan of a packed batch: slot[i] / block_off[i] for every read (slot -1: it did not fit into nslot rows of nsample_cap samples); returns the reads placed.  Longest read first,

@@ -9,7 +9,9 @@ same number of samples:
 each through `flappie --readers R` at --limit N/2 and N; the rate is MARGINAL (long run minus short run, as bench.py's host_fed: the batch objects of a
 packed run -- up to 90 GB each at 384 hidden units -- are allocated once, in the first chunks), the
 padding efficiency is the binary's own account (FLAPPIE_CLI_TIMING: samples / (slots x longest read) by batch and by 16-read tile).
-Run on the GPU box.   usage: tools/length_mix.py [hidden=384] [nfiles=65536] [readers=4] [env NAME=VALUE ...: extra environment for the mixed runs]"""
+--runnie: the same two directories through `runnie` with a synthetic run-length model (runlength5_r941native.h), each twice: packed batches and one read a row
+(FLAPPIE_DEBUG=no_pack).
+Run on the GPU box.   usage: tools/length_mix.py [--runnie] [hidden=384] [nfiles=65536] [readers=4] [env NAME=VALUE ...: extra environment for the mixed runs]"""
 import os
 import shutil
 import subprocess
@@ -21,15 +23,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from flappie_amd import model as M  # noqa: E402
 
-hidden = int(sys.argv[1]) if len(sys.argv) > 1 else 384
-nfiles = int(sys.argv[2]) if len(sys.argv) > 2 else 65536
-readers = sys.argv[3] if len(sys.argv) > 3 else "4"
-extra = dict(a.split("=", 1) for a in sys.argv[4:])
+runnie = "--runnie" in sys.argv[1:]
+argv = [a for a in sys.argv if a != "--runnie"]
+hidden = int(argv[1]) if len(argv) > 1 else 384
+nfiles = int(argv[2]) if len(argv) > 2 else 65536
+readers = argv[3] if len(argv) > 3 else "4"
+extra = dict(a.split("=", 1) for a in argv[4:])
 base = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
 d = tempfile.mkdtemp(prefix="ffhip_lenmix_", dir=base)
-exe, tool = os.path.join(ROOT, "flappie_amd", "flappie"), os.path.join(ROOT, "flappie_amd", "fast5_tool")
+exe, tool = os.path.join(ROOT, "flappie_amd", "runnie" if runnie else "flappie"), os.path.join(ROOT, "flappie_amd", "fast5_tool")
+# runs: (label, environment) -- runnie: packed batches, then one read a row
+modes = [("packed", {}), ("no_pack", {"FLAPPIE_DEBUG": "no_pack"})] if runnie else [("", {})]
 try:
-    M.write_mdl(os.path.join(d, "flipflop5_r941native.h"), M.synthetic_model(M.NET_LSTM5, hidden, seed=1, ident="r941native"))
+    if runnie:
+        M.write_mdl(os.path.join(d, "runlength5_r941native.h"), M.synthetic_model(M.NET_LSTM5_RLE, hidden, seed=1, ident="r941native"))
+    else:
+        M.write_mdl(os.path.join(d, "flipflop5_r941native.h"), M.synthetic_model(M.NET_LSTM5, hidden, seed=1, ident="r941native"))
     mixes = {}
     os.mkdir(os.path.join(d, "mixed"))
     out = subprocess.run([tool, "synthln", os.path.join(d, "mixed"), str(nfiles), "8000", "1.0", "1000", "200000", "20260929"], check=True, capture_output=True, text=True).stdout.split()
@@ -38,11 +47,11 @@ try:
     os.mkdir(os.path.join(d, "uniform"))
     out = subprocess.run([tool, "synth", os.path.join(d, "uniform"), str(n_uni), "3500", "5500", "20260929"], check=True, capture_output=True, text=True).stdout.split()
     mixes["uniform"] = (n_uni, int(out[3]))
-    print("H = %d, --readers %s; mixed: %d files, %.1f Msamples (log-normal, median 8000, sigma 1, 1000 .. 200 000); uniform: %d files, %.1f Msamples (3500 .. 5500)"
-          % (hidden, readers, nfiles, mixes["mixed"][1] / 1e6, n_uni, mixes["uniform"][1] / 1e6), flush=True)
-    for name in ("uniform", "mixed"):
+    print("%sH = %d, --readers %s; mixed: %d files, %.1f Msamples (log-normal, median 8000, sigma 1, 1000 .. 200 000); uniform: %d files, %.1f Msamples (3500 .. 5500)"
+          % ("runnie, " if runnie else "", hidden, readers, nfiles, mixes["mixed"][1] / 1e6, n_uni, mixes["uniform"][1] / 1e6), flush=True)
+    for name, (mode, menv) in [(nm, md) for nm in ("uniform", "mixed") for md in modes]:
         n = mixes[name][0]
-        env = dict(os.environ, FLAPPIE_MODEL_DIR=d, FLAPPIE_CLI_TIMING="1")
+        env = dict(os.environ, FLAPPIE_MODEL_DIR=d, FLAPPIE_CLI_TIMING="1", **menv)
         if name == "mixed":
             env.update(extra)
         res = {}
@@ -63,7 +72,7 @@ try:
                 if lim not in res or dt < res[lim][0]:
                     res[lim] = (dt, raw, pad[-1] if pad else "")
         (t0_, r0, _), (t1_, r1, pad) = res[n // 2], res[n]
-        print("%-8s %6d files: %.2f s, %6d files: %.2f s -> marginal %.1f Msamples/s (whole long run: %.1f)   %s%s"
-              % (name, n // 2, t0_, n, t1_, (r1 - r0) / (t1_ - t0_) / 1e6, r1 / t1_ / 1e6, pad, ("   [" + " ".join("%s=%s" % kv for kv in extra.items()) + "]") if extra and name == "mixed" else ""), flush=True)
+        print("%-16s %6d files: %.2f s, %6d files: %.2f s -> marginal %.1f Msamples/s (whole long run: %.1f)   %s%s"
+              % ((name + " " + mode).strip(), n // 2, t0_, n, t1_, (r1 - r0) / (t1_ - t0_) / 1e6, r1 / t1_ / 1e6, pad, ("   [" + " ".join("%s=%s" % kv for kv in extra.items()) + "]") if extra and name == "mixed" else ""), flush=True)
 finally:
     shutil.rmtree(d, ignore_errors=True)
