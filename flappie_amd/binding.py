@@ -26,6 +26,9 @@ RUN_F32_RNN = 64
 RUN_FAST_GATES = 128
 RUN_FAST_GATES2 = 256
 RUN_EXACT_GATES = 512
+# ffhip_debug_gate_math forms (include/ffhip.h)
+GATE_FORMS = ("logistic_ref", "tanh_ref", "logistic_ref4_lean", "logistic_ref2_lean", "logistic_ref_lean", "tanh_ref_lean",
+              "swish_act4", "tanh_act4", "logistic_hw1", "tanh_hw1", "logistic_hw2", "tanh_hw2")
 NGROUP = 6
 GROUP_NAMES = ("conv", "inproj", "recurrent", "head_crf", "posterior", "viterbi_assembly")
 
@@ -172,6 +175,16 @@ class Engine:
 
     def f32_reruns(self) -> int:
         return int(lib().ffhip_engine_f32_reruns(self.h))
+
+    def gate_math(self, form: str, x: np.ndarray) -> np.ndarray:
+        """ffhip_debug_gate_math: the layer kernels' gate function `form` (GATE_FORMS) of every element of x, on the device"""
+        x = np.ascontiguousarray(x, dtype=np.float32).ravel()
+        out = np.empty_like(x)
+        L = lib()
+        L.ffhip_debug_gate_math.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]
+        if x.size:
+            _check(L.ffhip_debug_gate_math(self.h, GATE_FORMS.index(form), _fptr(x), _fptr(out), x.size))
+        return out
 
     def set_profiling(self, on: bool):
         _check(lib().ffhip_engine_set_profiling(self.h, int(on)))

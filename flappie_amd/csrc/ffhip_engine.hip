@@ -72,13 +72,16 @@ extern "C" ffhip_engine *ffhip_engine_create(int device) {
 
 // gate arithmetic of the split layer kernels: 0 = the reference's exp_ps / division replayed bit for bit, 1 = v_exp_f32 / v_rcp_f32, 2 = those with a
 // two-word exponent and a Newton step (ffhip_math.hpp logistic_hw) -- the default since round 6 (include/ffhip.h, profiles/r06_gates_*.txt); run flags first,
-// then FFHIP_FAST_GATES=0|1|2 for a whole process
+// then FFHIP_FAST_GATES=0|1|2 for a whole process (exactly one of those three texts: anything else is reported once on stderr and gives the default)
 static int gate_level(unsigned flags) {
     if (flags & FFHIP_RUN_EXACT_GATES) return 0;
     if (flags & FFHIP_RUN_FAST_GATES2) return 2;
     if (flags & FFHIP_RUN_FAST_GATES) return 1;
     const char *e = getenv("FFHIP_FAST_GATES");
-    if (e && e[0]) return atoi(e) >= 2 ? 2 : (e[0] == '0' ? 0 : 1);
+    if (!e || !e[0]) return 2;
+    if ((e[0] == '0' || e[0] == '1' || e[0] == '2') && e[1] == 0) return e[0] - '0';
+    static std::atomic<int> warned{ 0 };
+    if (!warned.exchange(1)) fprintf(stderr, "ffhip: FFHIP_FAST_GATES=%s is not 0, 1 or 2; using the default gate level 2\n", e);
     return 2;
 }
 
@@ -2011,6 +2014,19 @@ extern "C" int ffhip_debug_lean_math_check(ffhip_engine *eng, int exponent, int 
     launch_lean_math_check(nullptr, exponent, steps, d);
     HIP_TRY(hipDeviceSynchronize(), FFHIP_EHIP);
     HIP_TRY(hipMemcpy(mismatches, d, 8, hipMemcpyDeviceToHost), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+
+extern "C" int ffhip_debug_gate_math(ffhip_engine *eng, int form, const float *x, float *out, size_t n) {
+    if (!eng || !x || !out || form < 0 || form >= kGateForms || n == 0 || n > ((size_t)1 << 30)) return set_err(FFHIP_EINVAL, "gate math: bad arguments");
+    hipSetDevice(eng->device);
+    TmpDev tmp;
+    float *d_x = (float *)tmp.get(n * 4), *d_y = (float *)tmp.get(n * 4);
+    if (!d_x || !d_y) return set_err(FFHIP_ENOMEM, "device allocation failed");
+    HIP_TRY(hipMemcpy(d_x, x, n * 4, hipMemcpyHostToDevice), FFHIP_EHIP);
+    launch_gate_math(nullptr, form, d_x, d_y, n);
+    HIP_TRY(hipDeviceSynchronize(), FFHIP_EHIP);
+    HIP_TRY(hipMemcpy(out, d_y, n * 4, hipMemcpyDeviceToHost), FFHIP_EHIP);
     return FFHIP_OK;
 }
 

@@ -140,6 +140,10 @@ void launch_inproj_split(hipStream_t s, const void *in_split, float *xa, const v
 void launch_split_from_f32(hipStream_t s, const float *in, void *out, size_t ntile, int H, int act_exp, unsigned *sat = nullptr, int B16 = 1);      // tile-interleaved fp32 -> split of in * 2^act_exp
 void launch_f32_from_split(hipStream_t s, const void *in, float *out, size_t ntile, int H, int act_exp);
 void launch_lean_math_check(hipStream_t s, int exponent, int steps, unsigned long long *bad);      // adds the mismatch count to *bad
+// the gate functions of ffhip_math.hpp one element at a time (ffhip_debug_gate_math): the numbering of include/ffhip.h
+enum GateForm { kGateLogisticRef = 0, kGateTanhRef, kGateLogisticRef4Lean, kGateLogisticRef2Lean, kGateLogisticRefLean, kGateTanhRefLean, kGateSwishAct4,
+                kGateTanhAct4, kGateLogisticHw1, kGateTanhHw1, kGateLogisticHw2, kGateTanhHw2, kGateForms };
+void launch_gate_math(hipStream_t s, int form, const float *x, float *out, size_t n);
 
 // the same head on the last layer's split output (ffhip_rnn_split.hip layout), weights as fp16 slices scaled by 2^(acc_exp - kSplitExpH)
 void launch_head_split(hipStream_t s, const void *in_split, float *trans, const void *Wsplit, const float *bias,

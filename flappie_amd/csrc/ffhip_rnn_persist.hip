@@ -63,7 +63,8 @@ struct PersistArgs {
     unsigned *flags;       // [nrt][G] XCC ids (zeroed before launch)
     unsigned *abort_word;  // != 0 -> a wait timed out
     int Tb, B16, Ut, K16, G, rt0, nrt, backward;
-    int fast_gates;        // opt-in (FFHIP_FAST_GATES=1): hardware exp2/rcp gate math, NOT bit-compatible with the reference's exp_ps
+                           // (no gate level: these kernels replay the reference's exp_ps and division bit for bit at every level -- FFHIP_RUN_*_GATES and
+                           // FFHIP_FAST_GATES govern the split layer kernels only)
     const int *tbs;        // ragged batch: blocks of each read [16*B16] (nullptr = all Tb); a read's steps t >= tbs[r] give h = c = 0,
                            // which is a fresh start for backward layers and inert padding for forward ones
     const int *tbt;        // ragged batch: max blocks per read tile [B16]
@@ -452,14 +453,6 @@ k_lstm_fused(PersistArgs a) {
                 hbar = tanh_ref(hbar);
                 h = z * hprev_own + (1.0f - z) * hbar;
                 hprev_own = h;
-            } else if (a.fast_gates) {
-                s = s + bias;
-                // hardware exp2/rcp (1 ulp each): ~6x fewer VALU instructions than the cephes-exact path
-                auto sg = [](float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f)); };
-                const float si = sg(s.x), sf = sg(s.y), so = sg(s.w);
-                const float tg = 2.0f * sg(s.z + s.z) - 1.0f;
-                c = sf * c + si * tg;
-                h = so * (2.0f * sg(c + c) - 1.0f);
             } else {
                 s = s + bias;
                 const ffv4 L = logistic_ref4_lean((ffv4){ s.x, s.y, s.z + s.z, s.w });      // bit-identical to logistic_ref4, fewer instructions (ffhip_math.hpp)
@@ -614,7 +607,6 @@ bool launch_lstm_fused(hipStream_t s, int kind, const float4 *sWp, const float4 
     a.Tb = Tb; a.B16 = B16; a.Ut = H / 4; a.K16 = H / 16; a.G = pick_group(a.Ut); a.rt0 = rt0; a.nrt = nrt;
     a.backward = backward; a.mode = mode;
     a.tbs = tbs; a.tbt = tbt;
-    a.fast_gates = getenv("FFHIP_FAST_GATES") ? 1 : 0;
     const int UPC = a.Ut / a.G, kpw = pick_kpw(a.K16);
     if (kind == 0) {
         switch (UPC) {
@@ -645,8 +637,6 @@ bool launch_rnn_persist(hipStream_t s, int kind, const float4 *sWp, const float 
     a.backward = backward;
     a.mode = mode;
     a.tbs = tbs; a.tbt = tbt;
-    a.fast_gates = 0;
-   
     const int UPC = a.Ut / a.G, kpw = pick_kpw(a.K16);
     if (kind == 0) {
         switch (UPC) {

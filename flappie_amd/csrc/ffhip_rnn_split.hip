@@ -1499,6 +1499,48 @@ void launch_lean_math_check(hipStream_t s, int exponent, int steps, unsigned lon
     hipLaunchKernelGGL(k_lean_math_check, dim3(1u << 15), dim3(256), 0, s, exponent, steps, bad);
 }
 
+// the gate functions of ffhip_math.hpp, element by element, for tests against fp64 and the reference (ffhip_debug_gate_math; the form numbers are
+// GateForm in ffhip_internal.hpp).  Four elements a thread, so that each component of the 4-vector forms sees its own input; the levels of the
+// hardware forms are literals, as the layer kernels' GL template parameter makes them.  Elements at or past n read 0 and are not stored.
+__global__ void __launch_bounds__(256)
+k_gate_math(int form, const float *x, float *out, size_t n) {
+    const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i0 >= n) return;
+    ffv4 v = { 0.f, 0.f, 0.f, 0.f };
+    v.x = x[i0];
+    if (i0 + 1 < n) v.y = x[i0 + 1];
+    if (i0 + 2 < n) v.z = x[i0 + 2];
+    if (i0 + 3 < n) v.w = x[i0 + 3];
+    ffv4 r;
+    switch (form) {
+    case kGateLogisticRef: r = (ffv4){ logistic_ref(v.x), logistic_ref(v.y), logistic_ref(v.z), logistic_ref(v.w) }; break;
+    case kGateTanhRef: r = (ffv4){ tanh_ref(v.x), tanh_ref(v.y), tanh_ref(v.z), tanh_ref(v.w) }; break;
+    case kGateLogisticRef4Lean: r = logistic_ref4_lean(v); break;
+    case kGateLogisticRef2Lean: {
+        const ffv2 a = logistic_ref2_lean((ffv2){ v.x, v.y }), b = logistic_ref2_lean((ffv2){ v.z, v.w });
+        r = (ffv4){ a.x, a.y, b.x, b.y };
+        break;
+    }
+    case kGateLogisticRefLean: r = (ffv4){ logistic_ref_lean(v.x), logistic_ref_lean(v.y), logistic_ref_lean(v.z), logistic_ref_lean(v.w) }; break;
+    case kGateTanhRefLean: r = (ffv4){ tanh_ref_lean(v.x), tanh_ref_lean(v.y), tanh_ref_lean(v.z), tanh_ref_lean(v.w) }; break;
+    case kGateSwishAct4: r = apply_act4(v, 1); break;
+    case kGateTanhAct4: r = apply_act4(v, 2); break;
+    case kGateLogisticHw1: r = (ffv4){ logistic_hw(v.x, 1), logistic_hw(v.y, 1), logistic_hw(v.z, 1), logistic_hw(v.w, 1) }; break;
+    case kGateTanhHw1: r = (ffv4){ tanh_hw(v.x, 1), tanh_hw(v.y, 1), tanh_hw(v.z, 1), tanh_hw(v.w, 1) }; break;
+    case kGateLogisticHw2: r = (ffv4){ logistic_hw(v.x, 2), logistic_hw(v.y, 2), logistic_hw(v.z, 2), logistic_hw(v.w, 2) }; break;
+    case kGateTanhHw2: r = (ffv4){ tanh_hw(v.x, 2), tanh_hw(v.y, 2), tanh_hw(v.z, 2), tanh_hw(v.w, 2) }; break;
+    default: return;
+    }
+    out[i0] = r.x;
+    if (i0 + 1 < n) out[i0 + 1] = r.y;
+    if (i0 + 2 < n) out[i0 + 2] = r.z;
+    if (i0 + 3 < n) out[i0 + 3] = r.w;
+}
+void launch_gate_math(hipStream_t s, int form, const float *x, float *out, size_t n) {
+    const size_t threads = (n + 3) / 4;
+    hipLaunchKernelGGL(k_gate_math, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, form, x, out, n);
+}
+
 // ---- host side ---------------------------------------------------------------------------------
 // largest H / 128 whose two weight matrices fit one CU's registers: 16N rows x 256N k x 2 B x slices per CU
 // (three bf16 slices: 221 KiB at N = 3; two fp16 slices: 147 KiB at N = 3, 256 KiB at N = 4; the file holds 512 KiB)

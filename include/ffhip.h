@@ -166,6 +166,10 @@ int ffhip_debug_split_round_trip(ffhip_engine *eng, const float *in, float *out,
  * exponent `exponent` (0..125); `steps` = Newton steps before the closing step (the kernels use 1).  Counts mismatching bit
  * patterns: 0 means bit-identical */
 int ffhip_debug_lean_math_check(ffhip_engine *eng, int exponent, int steps, unsigned long long *mismatches);
+/* debug tap: y[i] = f(x[i]) for the gate function `form` of the layer kernels, the same inline code they run:
+ * 0 logistic_ref, 1 tanh_ref (the reference's exp_ps and division), 2 logistic_ref4_lean (four inputs a vector), 3 logistic_ref2_lean,
+ * 4 logistic_ref_lean, 5 tanh_ref_lean, 6 / 7 apply_act4 swish / tanh, 8 / 9 logistic_hw / tanh_hw at level 1, 10 / 11 at level 2 */
+int ffhip_debug_gate_math(ffhip_engine *eng, int form, const float *x, float *out, size_t n);
 
 /* debug tap: every op_sel / op_sel_hi form of the packed-fp32 VALU instructions checked against the scalar
  * instructions in a loop on a stream of its own, so that it can run beside a batch's kernels; counts[4][16][2][4] mismatches by
