@@ -30,6 +30,9 @@ RUN_EXACT_GATES = 512
 GATE_FORMS = ("logistic_ref", "tanh_ref", "logistic_ref4_lean", "logistic_ref2_lean", "logistic_ref_lean", "tanh_ref_lean",
               "swish_act4", "tanh_act4", "logistic_hw1", "tanh_hw1", "logistic_hw2", "tanh_hw2")
 NGROUP = 6
+# ffhip_debug_batch_forms: kernel form ids (include/ffhip.h FFHIP_FORM_*)
+FORMS = {1: "small<4,5>", 2: "small<16,20>", 3: "small<4>", 4: "small<16>", 5: "small<32>", 6: "mfma<true>", 7: "mfma<false>",
+         8: "split_ws<10>", 9: "split<4,4>", 10: "split<2,2>", 11: "head<3>", 12: "head<4>", 13: "head_split<3>", 14: "head_split<4>"}
 GROUP_NAMES = ("conv", "inproj", "recurrent", "head_crf", "posterior", "viterbi_assembly")
 
 
@@ -142,6 +145,10 @@ def lib():
     L.ffhip_batch_f32_reruns.argtypes = [vp]
     L.ffhip_engine_f32_reruns.restype = C.c_ulonglong
     L.ffhip_engine_f32_reruns.argtypes = [vp]
+    L.ffhip_debug_batch_keep_front.argtypes = [vp, C.c_int]
+    L.ffhip_debug_batch_front.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    L.ffhip_debug_batch_head_input.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
+    L.ffhip_debug_batch_forms.argtypes = [vp, C.POINTER(C.c_int)]
     _LIB = L
     return L
 
@@ -297,11 +304,13 @@ class Batch:
         self.nblock = int(lib().ffhip_batch_nblock(self.h))
         self.P = dmodel.model.nparam
         self.nstate = dmodel.model.nstate
+        self._place = None          # where each read stands: [(row, first sample, samples)] (front / head_input)
 
     def set_signals(self, signals: np.ndarray):
         s = np.ascontiguousarray(signals, dtype=np.float32)
         assert s.shape == (self.nread, self.nsample), s.shape
         _check(lib().ffhip_batch_set_signals(self.h, _fptr(s), s.shape[1]))
+        self._place = [(r, 0, self.nsample) for r in range(self.nread)]
 
     def set_signals_ragged(self, signals: List[np.ndarray]):
         """reads of different lengths (each <= the batch's nsample); results are then per-read sized"""
@@ -313,6 +322,7 @@ class Batch:
             buf[i, :x.size] = x
             lens[i] = x.size
         _check(lib().ffhip_batch_set_signals_ragged(self.h, _fptr(buf), ld, lens))
+        self._place = [(r, 0, int(x.size)) for r, x in enumerate(signals)]
 
     def read_nblock(self, read: int) -> int:
         return int(lib().ffhip_batch_read_nblock(self.h, read))
@@ -350,6 +360,8 @@ class Batch:
         ptrs = (C.POINTER(C.c_float) * n)(*[_fptr(x) for x in keep])
         ns = (C.c_size_t * n)(*[x.size for x in keep])
         _check(lib().ffhip_batch_set_signals_packed(self.h, n, ptrs, ns, (C.c_int * n)(*slots), (C.c_int * n)(*offs)))
+        st = self.dmodel.model.total_stride
+        self._place = [(int(slots[i]), int(offs[i]) * st, int(keep[i].size)) for i in range(n)]
 
     def set_prepared_packed(self, prep: "Prepared", reads: List[int], slots: List[int], offs: List[int]):
         n = len(reads)
@@ -419,6 +431,50 @@ class Batch:
         L.ffhip_batch_rnn_path.argtypes = [C.c_void_p]
         L.ffhip_batch_rnn_path.restype = C.c_int
         return int(L.ffhip_batch_rnn_path(self.h))
+
+    # ---- debug read-outs (ffhip_debug_batch_*): the convolutions' and the head's own outputs and inputs; they change nothing a run launches
+    def keep_front(self, on: bool = True):
+        """from the next run on, keep the last convolution's output for front() (one device-to-device copy behind the convolution group)"""
+        _check(lib().ffhip_debug_batch_keep_front(self.h, int(on)))
+
+    def _span(self, layer: int, read: int):
+        """(row, first column, columns) of `read` in the output of convolution `layer` (layer = nconv: the blocks)"""
+        row, x0, n = self._place[read]
+        convs = self.dmodel.model.convs
+        before = int(np.prod([c.stride for c in convs[:layer + 1]])) if layer >= 0 else 1
+        return row, x0 // before, -(-n // before)
+
+    def front_row(self, layer: int, row: int) -> np.ndarray:
+        """convolution `layer`'s output over the whole batch row, padding columns included: [Tout][filters]"""
+        cv = self.dmodel.model.convs[layer]
+        tout = self.nsample
+        for c in self.dmodel.model.convs[:layer + 1]:
+            tout = -(-tout // c.stride)
+        out = np.zeros((tout, cv.W.nc), dtype=np.float32)
+        _check(lib().ffhip_debug_batch_front(self.h, layer, row, _fptr(out)))
+        return out
+
+    def front(self, layer: int, read: int) -> np.ndarray:
+        """convolution `layer`'s output for `read` alone (its columns of its row)"""
+        row, c0, n = self._span(layer, read)
+        return self.front_row(layer, row)[c0:c0 + n]
+
+    def head_input_row(self, row: int) -> np.ndarray:
+        """the last recurrent layer's output over the whole batch row, as the CRF head read it: [nblock][hidden]"""
+        out = np.zeros((self.nblock, self.dmodel.model.hidden), dtype=np.float32)
+        _check(lib().ffhip_debug_batch_head_input(self.h, row, _fptr(out)))
+        return out
+
+    def head_input(self, read: int) -> np.ndarray:
+        row, c0, n = self._span(len(self.dmodel.model.convs) - 1, read)
+        return self.head_input_row(row)[c0:c0 + n]
+
+    def forms(self):
+        """kernel forms of the last run: [form of each convolution], form of the head (names of FORMS)"""
+        out = (C.c_int * 4)()
+        _check(lib().ffhip_debug_batch_forms(self.h, out))
+        nconv = len(self.dmodel.model.convs)
+        return [FORMS.get(out[i], out[i]) for i in range(nconv)], FORMS.get(out[3], out[3])
 
     def f32_reruns(self) -> int:
         """reads of the last run that left the split operand format's range and were run again on the f32 path (ffhip_batch_finish)"""

@@ -762,6 +762,11 @@ struct ffhip_batch {
                                         // per launch instead of six: each is a packet between two layer launches, ~5 us of idle chip)
     ffhip_batch *prof_ref = nullptr;    // ... and the first batch's way back, so that either can go first
     int profiled = 0;
+    // debug read-outs (ffhip_debug_batch_keep_front / _front / _head_input / _forms): none of them changes what a run launches
+    bool keep_front = false;            // the next runs copy the last convolution's output to front_keep
+    void *front_keep = nullptr;         // [Tb][B16] tiles in the split layout (front_exp: values * 2^front_exp) or fp32 tile-interleaved (front_exp < -1000)
+    int front_kept = 0, front_exp = -100000, front_f16 = -1;       // the last run kept it; the thin layer whose output was fp16 slices (-1: none)
+    int forms[4] = { -1, -1, -1, -1 };  // kernel forms of the last run's convolution launches and its head launch (KernelForm)
 };
 
 static void *dalloc(ffhip_batch *b, size_t bytes, bool zero) {
@@ -1460,21 +1465,31 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
     else if (full_chip && !by_layers && fo[0] == 'b' && !paired && eng->batch_done_rec) HIP_TRY(hipStreamWaitEvent(s, eng->batch_done, 0), FFHIP_EHIP);
     mark(b, 0);                                        // (behind the wait: the convolution group's time is its kernels')
     HIP_TRY(hipMemsetAsync(b->sat, 0, (size_t)Bp * sizeof(unsigned), s), FFHIP_EHIP);
+    for (int i = 0; i < 4; i++) b->forms[i] = kFormNone;
     for (int l = 0; l < m->nconv; l++) {
         const ConvDev &c = m->conv[l];
         const int *x0a = b->ragged ? b->rag_x0a[l] : b->plan[l].x0a, *x0b = b->ragged ? b->rag_x0b[l] : b->plan[l].x0b, ldp = b->ragged ? b->plan[l].Tout : 0;
         if (l < m->nconv - 1)
-            launch_conv_small(s, b->sbuf[l], b->sbuf[l + 1], c.taps, c.bias, x0a, x0b, Bp, b->plan[l].Tout, c.winlen, m->act, ldp, (b->ragged && !b->packed) ? b->rag_tin[l] : nullptr,
+            b->forms[l] = launch_conv_small(s, b->sbuf[l], b->sbuf[l + 1], c.taps, c.bias, x0a, x0b, Bp, b->plan[l].Tout, c.winlen, m->act, ldp, (b->ragged && !b->packed) ? b->rag_tin[l] : nullptr,
                               (p.conv_f16 && l == m->nconv - 2) ? kSplitExpX : -100000, b->sat, (b->packed && m->conv[l].stride == 1) ? b->rag_seg[l] : nullptr);
         else if (p.conv_f16)
-            launch_conv_split(s, b->sbuf[l], b->act[0], c.Wsplit, c.bias, x0a, x0b, B16, Tb, c.Mpad, c.winlen, m->act, ldp, p.conv_split ? b->actS[0] : nullptr,
+            b->forms[l] = launch_conv_split(s, b->sbuf[l], b->act[0], c.Wsplit, c.bias, x0a, x0b, B16, Tb, c.Mpad, c.winlen, m->act, ldp, p.conv_split ? b->actS[0] : nullptr,
                               kSplitExpX, c.split_S, lean_conv, b->sat);
         else
-            launch_conv_mfma(s, b->sbuf[l], b->act[0], c.Wp, c.bias, x0a, x0b, B16, Tb, c.Mpad, c.K16, m->act, ldp, p.conv_split ? b->actS[0] : nullptr,
-                             m->act == ACT_SWISH ? kSplitExpX : kSplitExpH, b->sat);
+            b->forms[l] = launch_conv_mfma(s, b->sbuf[l], b->act[0], c.Wp, c.bias, x0a, x0b, B16, Tb, c.Mpad, c.K16, m->act, ldp, p.conv_split ? b->actS[0] : nullptr,
+                             m->act == ACT_SWISH ? kSplitExpX : kSplitExpH, b->sat, c.winlen * c.Fin);
         b->launches[0]++;
     }
     if (int rc = keep_copy(b, 0, b->act[0])) return rc;
+    b->front_kept = 0;
+    if (b->keep_front) {      // (debug: ffhip_debug_batch_front) the last convolution's output as it left the kernel
+        const size_t f32_bytes = (size_t)Tb * Bp * Hp * 4, split_b = split_bytes((size_t)Tb * B16, Hp);
+        if (!b->front_keep && !(b->front_keep = dalloc(b, std::max(f32_bytes, split_b), false))) return FFHIP_ENOMEM;
+        HIP_TRY(hipMemcpyAsync(b->front_keep, p.conv_split ? b->actS[0] : (const void *)b->act[0], p.conv_split ? split_b : f32_bytes, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+        b->front_exp = p.conv_split ? (m->act == ACT_SWISH ? kSplitExpX : kSplitExpH) : -100000;
+        b->front_f16 = (p.conv_f16 && m->nconv >= 2) ? m->nconv - 2 : -1;
+        b->front_kept = 1;
+    }
     mark(b, 1);
     HIP_TRY(hipMemsetAsync(b->pabort, (p.persist && dbg("force_abort")) ? 1 : 0, sizeof(unsigned), s), FFHIP_EHIP);      // (debug: pretend a wait timed out)
     if ((p.split || p.split2) && !p.conv_split) {
@@ -1623,16 +1638,17 @@ static int run_back(ffhip_batch *b) {
     const bool rle = (m->kind == FFHIP_NET_LSTM5_RLE);
     if (rle) {
         // ---- globalnorm_runlengthV2 (layers.c:1325-1358)
-        if (p.split_head) launch_head_split(s, b->actS[cur], b->trans, m->FFsplit, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 32, 1.0f, m->FF_split_S, 1);
-        else launch_head(s, b->act[cur], b->trans, m->FFp, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 16, 1.0f, 1);
+        b->forms[3] = p.split_head ? launch_head_split(s, b->actS[cur], b->trans, m->FFsplit, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 32, 1.0f, m->FF_split_S, 1)
+                                   : launch_head(s, b->act[cur], b->trans, m->FFp, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 16, 1.0f, 1);
         if (b->packed) { HIP_TRY(hipEventRecord(eng->head_done, s), FFHIP_EHIP); eng->head_done_rec = 1; }      // (as below: apply_packed)
         // activation over the slots' rows; partition function and subtraction per read
         launch_rle_head_finish(s, b->trans, b->crf_logz, b->nread, Tb, m->nbase, m->Ps, temperature, tbs, nR, tbr, rmap, gblk);
         b->launches[3] += 4;
     } else {
         // ---- globalnorm_flipflop (layers.c:1082-1106)
-        if (p.split_head) launch_head_split(s, b->actS[cur], b->trans, m->FFsplit, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 32, temperature / 5.0f, m->FF_split_S, 0, p.head_e ? b->crf_e : nullptr);
-        else launch_head(s, b->act[cur], b->trans, m->FFp, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 16, temperature / 5.0f);
+        b->forms[3] = p.split_head ? launch_head_split(s, b->actS[cur], b->trans, m->FFsplit, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 32, temperature / 5.0f, m->FF_split_S, 0,
+                                                       p.head_e ? b->crf_e : nullptr)
+                                   : launch_head(s, b->act[cur], b->trans, m->FFp, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 16, temperature / 5.0f);
         if (b->packed) { HIP_TRY(hipEventRecord(eng->head_done, s), FFHIP_EHIP); eng->head_done_rec = 1; }      // (the next packed batch's set-up and convolutions start behind it: apply_packed)
         if (p.post_done) {
             const bool want_post = !(flags & FFHIP_RUN_NO_DECODE) && !(flags & FFHIP_RUN_VITERBI_ONLY);
@@ -1994,6 +2010,63 @@ extern "C" int ffhip_batch_get_activation(ffhip_batch *b, int layer, int read, f
 }
 
 extern "C" int ffhip_batch_rnn_path(const ffhip_batch *b) { return b ? b->rnn_path : -1; }
+
+// ---- debug read-outs of the convolutions' and the head's own inputs and outputs (include/ffhip.h)
+static_assert(kFormConvSmall4x5 == FFHIP_FORM_CONV_SMALL_4_5 && kFormConvMfmaVec == FFHIP_FORM_CONV_MFMA_VEC && kFormConvSplitWs10 == FFHIP_FORM_CONV_SPLIT_WS10 &&
+              kFormConvSplit22 == FFHIP_FORM_CONV_SPLIT_2_2 && kFormHead3 == FFHIP_FORM_HEAD_3 && kFormHeadSplit4 == FFHIP_FORM_HEAD_SPLIT_4, "form numbering of include/ffhip.h");
+extern "C" int ffhip_debug_batch_keep_front(ffhip_batch *b, int on) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    b->keep_front = on != 0;
+    return FFHIP_OK;
+}
+extern "C" int ffhip_debug_batch_forms(const ffhip_batch *b, int out[4]) {
+    if (!b || !out || !b->ran) return set_err(FFHIP_EINVAL, "the batch has not run");
+    for (int i = 0; i < 4; i++) out[i] = b->forms[i];
+    return FFHIP_OK;
+}
+// dense [Tb][H] fp32 of batch row `row` from [Tb][B16] tiles: split layout of values * 2^ex (ex > -1000) or fp32 tile-interleaved
+static int tiles_to_dense(ffhip_batch *b, const void *src, int ex, int row, float *out) {
+    const ffhip_model *m = b->mdl;
+    hipSetDevice(b->eng->device);
+    TmpDev tmp;
+    const float *tiles = (const float *)src;
+    if (ex > -1000) {
+        float *f = (float *)tmp.get((size_t)b->Tb * b->Bp * m->Hp * 4);
+        if (!f) return set_err(FFHIP_ENOMEM, "device allocation failed");
+        launch_f32_from_split(b->stream, src, f, (size_t)b->Tb * b->B16, m->Hp, ex);      // (h1 + h0) * 2^-ex
+        tiles = f;
+    }
+    if (!b->scratch && !(b->scratch = (float *)dalloc(b, (size_t)b->Tb * m->Hp * 4, false))) return FFHIP_ENOMEM;
+    launch_untile(b->stream, tiles, b->scratch, row, b->Tb, b->B16, m->Hp);
+    std::vector<float> dense((size_t)b->Tb * m->Hp);
+    if (int rc = d2h(b, dense.data(), b->scratch, dense.size() * 4)) return rc;
+    for (int t = 0; t < b->Tb; t++) memcpy(out + (size_t)t * m->H, dense.data() + (size_t)t * m->Hp, (size_t)m->H * 4);
+    return FFHIP_OK;
+}
+extern "C" int ffhip_debug_batch_front(ffhip_batch *b, int layer, int row, float *out) {
+    if (!b || !out || !b->ran || row < 0 || row >= b->nread || layer < 0 || layer >= b->mdl->nconv) return set_err(FFHIP_EINVAL, "front: bad arguments");
+    if (!b->front_kept) return set_err(FFHIP_EINVAL, "front: the last run did not keep the convolutions' output (ffhip_debug_batch_keep_front)");
+    const ffhip_model *m = b->mdl;
+    if (layer == m->nconv - 1) return tiles_to_dense(b, b->front_keep, b->front_exp, row, out);
+    const SampleBuf &sb = b->sbuf[layer + 1];
+    const size_t n = (size_t)b->plan[layer].Tout * sb.F;
+    if (int rc = d2h(b, out, sb.row(row, 0), n * 4)) return rc;
+    if (layer == b->front_f16) {
+        // fp16 slices of value * 2^kSplitExpX for k_conv_split: a sample's 64 bytes are [slice][16 features]
+        const float inv = split_pow2(-kSplitExpX);
+        std::vector<uint16_t> h(n * 2);
+        memcpy(h.data(), out, n * 4);
+        for (size_t t = 0; t < n / 16; t++)
+            for (int f = 0; f < 16; f++) out[t * 16 + f] = (split_host_f16_value(h[t * 32 + f]) + split_host_f16_value(h[t * 32 + 16 + f])) * inv;
+    }
+    return FFHIP_OK;
+}
+extern "C" int ffhip_debug_batch_head_input(ffhip_batch *b, int row, float *out) {
+    if (!b || !out || !b->ran || row < 0 || row >= b->nread) return set_err(FFHIP_EINVAL, "head input: bad arguments");
+    if (b->run_path.split_head) return tiles_to_dense(b, b->actS[b->final_act], kSplitExpH, row, out);
+    if (!b->act[b->final_act]) return set_err(FFHIP_EINVAL, "head input: no fp32 copy of the last layer");
+    return tiles_to_dense(b, b->act[b->final_act], -100000, row, out);
+}
 
 extern "C" int ffhip_debug_fallback_count(const ffhip_engine *eng) { return eng ? eng->fallbacks : -1; }
 

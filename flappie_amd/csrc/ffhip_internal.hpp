@@ -63,10 +63,13 @@ struct ReadMap {
 };
 
 // ---- kernel launchers (ffhip_kernels.hip) ----------------------------------------------------
+// The launchers of the convolutions and of the CRF head return the kernel form they took (ffhip_debug_batch_forms; the numbering of include/ffhip.h)
+enum KernelForm { kFormNone = -1, kFormConvSmall4x5 = 1, kFormConvSmall16x20, kFormConvSmall4, kFormConvSmall16, kFormConvSmall32, kFormConvMfmaVec, kFormConvMfmaScalar,
+                  kFormConvSplitWs10, kFormConvSplit44, kFormConvSplit22, kFormHead3, kFormHead4, kFormHeadSplit3, kFormHeadSplit4 };
 void launch_pack_signal(hipStream_t s, const float *src, size_t ld, SampleBuf dst, int nread);
 
 // VALU convolution for the thin front layers; W dense taps [Fout][winlen][Fin]
-void launch_conv_small(hipStream_t s, SampleBuf in, SampleBuf out, const float *W, const float *bias,
+int launch_conv_small(hipStream_t s, SampleBuf in, SampleBuf out, const float *W, const float *bias,
                        const int *x0a, const int *x0b, int Bp, int Tout, int winlen, int act, int ldp = 0,     // ldp: entries per read of a per-read window table (0 = shared)
                        const int *tin = nullptr,                                  // stride-1 layer of a ragged batch: per-read input lengths instead of a table
                        int split_exp = -100000,                                   // > -1000 (16 output features): write fp16 slices of value * 2^split_exp for launch_conv_split
@@ -74,13 +77,14 @@ void launch_conv_small(hipStream_t s, SampleBuf in, SampleBuf out, const float *
                        const int *seg = nullptr);                                 // stride-1 layer of a packed batch: [Bp + 1] offsets, then every row's sorted read boundaries {start, end, ...} in columns
 
 // MFMA convolution of the last conv layer: sample-major in, tile-interleaved out [Tout][B16][M/4][16][4]
-void launch_conv_mfma(hipStream_t s, SampleBuf in, float *out, const float4 *Wp, const float *bias,
+int launch_conv_mfma(hipStream_t s, SampleBuf in, float *out, const float4 *Wp, const float *bias,
                       const int *x0a, const int *x0b, int B16, int Tout, int M, int K16, int act, int ldp = 0,
-                      void *out_split = nullptr, int split_exp = 0, unsigned *sat = nullptr);      // != nullptr: write the split layout of ffhip_rnn_split.hip (values * 2^split_exp) INSTEAD of `out` (M % 128 == 0)
+                      void *out_split = nullptr, int split_exp = 0, unsigned *sat = nullptr,      // out_split != nullptr: write the split layout of ffhip_rnn_split.hip (values * 2^split_exp) INSTEAD of `out` (M % 128 == 0)
+                      int K = 0);      // values of a window (winlen * Fin; 0: 16 K16): the fragment's elements behind it read as zero
 
 // the same convolution on split operands (16 input features): `in` holds fp16 slices (launch_conv_small with split_exp = kSplitExpX),
 // Wp the split weight pack [M/16][ceil(winlen/2)][2][64] x 16 B scaled by 2^(acc_exp - kSplitExpX)
-void launch_conv_split(hipStream_t s, SampleBuf in, float *out, const void *Wp, const float *bias, const int *x0a, const int *x0b,
+int launch_conv_split(hipStream_t s, SampleBuf in, float *out, const void *Wp, const float *bias, const int *x0a, const int *x0b,
                        int B16, int Tout, int M, int winlen, int act, int ldp, void *out_split, int split_exp, int acc_exp, int lean = 0, unsigned *sat = nullptr);      // lean: the <= 128-VGPR shape
 
 // Xa = Wi^T x + b for every (t, read); in tile-interleaved, out D-fragment order
@@ -146,11 +150,11 @@ enum GateForm { kGateLogisticRef = 0, kGateTanhRef, kGateLogisticRef4Lean, kGate
 void launch_gate_math(hipStream_t s, int form, const float *x, float *out, size_t n);
 
 // the same head on the last layer's split output (ffhip_rnn_split.hip layout), weights as fp16 slices scaled by 2^(acc_exp - kSplitExpH)
-void launch_head_split(hipStream_t s, const void *in_split, float *trans, const void *Wsplit, const float *bias,
+int launch_head_split(hipStream_t s, const void *in_split, float *trans, const void *Wsplit, const float *bias,
                        int Tb, int B16, int nread, int P, int Ps, int Hc, float scale, int acc_exp, int raw, double *E = nullptr);
 bool head_split_writes_E(int P);       // the head can leave exp(S - block max) for the linear-space chains (drops k_crf_exp)
 // head: trans = tanh(W^T h + b) / (temperature/5)
-void launch_head(hipStream_t s, const float *in, float *trans, const float4 *Wp, const float *bias,
+int launch_head(hipStream_t s, const float *in, float *trans, const float4 *Wp, const float *bias,
                  int Tb, int B16, int nread, int P, int Ps, int K16, float scale, int raw = 0);      // raw = 1: W^T h + b only
 // CRF partition function (fp64) + subtraction of (float)(logZ/Tb)
 // logz: device buffer of nread doubles, receives the fp64 partition function per read; subtract = 0 leaves `trans` untouched

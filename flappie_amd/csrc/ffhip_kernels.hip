@@ -170,21 +170,29 @@ k_conv_small(SampleBuf in, SampleBuf out, const float *__restrict__ W, const flo
     }
 }
 
-void launch_conv_small(hipStream_t s, SampleBuf in, SampleBuf out, const float *W, const float *bias,
-                       const int *x0a, const int *x0b, int Bp, int Tout, int winlen, int act, int ldp, const int *tin, int split_exp, unsigned *sat, const int *seg) {
+int launch_conv_small(hipStream_t s, SampleBuf in, SampleBuf out, const float *W, const float *bias,
+                      const int *x0a, const int *x0b, int Bp, int Tout, int winlen, int act, int ldp, const int *tin, int split_exp, unsigned *sat, const int *seg) {
     dim3 grid((Tout + 255) / 256, Bp), block(256);
     const float split_scale = (split_exp > -1000 && out.F == 16 && kSplitNS == 2) ? split_pow2(split_exp) : 0.0f;
     const size_t lds = (size_t)(out.F * winlen * in.F + out.F) * sizeof(float);
-    if (out.F == 4 && in.F == 1 && winlen == 5)
+    if (out.F == 4 && in.F == 1 && winlen == 5) {
         hipLaunchKernelGGL((k_conv_small<4, 5>), grid, block, lds, s, in, out, W, bias, x0a, x0b, Tout, winlen, act, ldp, tin, 0.0f, sat, seg);
-    else if (out.F == 16 && in.F == 4 && winlen == 5)
+        return kFormConvSmall4x5;
+    }
+    if (out.F == 16 && in.F == 4 && winlen == 5) {
         hipLaunchKernelGGL((k_conv_small<16, 20>), grid, block, lds, s, in, out, W, bias, x0a, x0b, Tout, winlen, act, ldp, tin, split_scale, sat, seg);
-    else if (out.F <= 4)
+        return kFormConvSmall16x20;
+    }
+    if (out.F <= 4) {
         hipLaunchKernelGGL(k_conv_small<4>, grid, block, lds, s, in, out, W, bias, x0a, x0b, Tout, winlen, act, ldp, tin, 0.0f, sat, seg);
-    else if (out.F <= 16)
+        return kFormConvSmall4;
+    }
+    if (out.F <= 16) {
         hipLaunchKernelGGL(k_conv_small<16>, grid, block, lds, s, in, out, W, bias, x0a, x0b, Tout, winlen, act, ldp, tin, split_scale, sat, seg);
-    else
-        hipLaunchKernelGGL(k_conv_small<32>, grid, block, lds, s, in, out, W, bias, x0a, x0b, Tout, winlen, act, ldp, tin, 0.0f, sat, seg);
+        return kFormConvSmall16;
+    }
+    hipLaunchKernelGGL(k_conv_small<32>, grid, block, lds, s, in, out, W, bias, x0a, x0b, Tout, winlen, act, ldp, tin, 0.0f, sat, seg);
+    return kFormConvSmall32;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -195,10 +203,13 @@ void launch_conv_small(hipStream_t s, SampleBuf in, SampleBuf out, const float *
 // 1 KiB per k16; convolution windows: 16 consecutive floats of the window per k16).
 // Loads are register double-buffered; the f32 MFMA is slow enough (32 cycles per instruction)
 // that 8 coalesced 1 KiB loads per 64 MFMAs hide behind the matrix pipe.
+// kvalid: B elements at k >= kvalid read as zero.  The convolution's window is K = winlen * Fin values of a 16 K16 fragment; the
+// ones behind it are live samples of the read whose weights are zero, and 0 x NaN would carry a NaN there into this column
+// (the reference's window ends at its last tap).  Uniform per wave and folded away where it is the default.
 // ------------------------------------------------------------------------------------------
 template <int TM, int TN, bool BVEC>
 __device__ __forceinline__ void mma_tiles(const v4f *(&ap)[TM], const float *(&bp)[TN], size_t bstep, int K16,
-                                          v4f (&acc)[TM][TN]) {
+                                          v4f (&acc)[TM][TN], int kvalid = 1 << 30) {
     v4f a0[TM], b0[TN], a1[TM], b1[TN];
     auto loadA = [&](v4f(&a)[TM], int k16) {
 #pragma unroll
@@ -210,6 +221,16 @@ __device__ __forceinline__ void mma_tiles(const v4f *(&ap)[TM], const float *(&b
             const float *p = bp[j] + (size_t)k16 * bstep;
             if (BVEC) b[j] = *(const v4f *)p;
             else { b[j].x = p[0]; b[j].y = p[1]; b[j].z = p[2]; b[j].w = p[3]; }
+        }
+        if (16 * k16 + 16 > kvalid) {
+            const int k0 = 16 * k16 + 4 * ((int)(threadIdx.x & 63) >> 4);
+#pragma unroll
+            for (int j = 0; j < TN; j++) {
+                if (k0 + 0 >= kvalid) b[j].x = 0.0f;
+                if (k0 + 1 >= kvalid) b[j].y = 0.0f;
+                if (k0 + 2 >= kvalid) b[j].z = 0.0f;
+                if (k0 + 3 >= kvalid) b[j].w = 0.0f;
+            }
         }
     };
     auto mma = [&](v4f(&a)[TM], v4f(&b)[TN]) {
@@ -240,7 +261,7 @@ __device__ __forceinline__ void mma_tiles(const v4f *(&ap)[TM], const float *(&b
 template <bool BVEC, int TN = 4, int WPS = 1>
 __global__ void __launch_bounds__(256, WPS)
 k_conv_mfma(SampleBuf in, float *__restrict__ out, const v4f *__restrict__ Wp, const float *__restrict__ bias,
-            const int *__restrict__ x0a, const int *__restrict__ x0b, int B16, int Tout, int Mt, int K16, int act, int ldp,
+            const int *__restrict__ x0a, const int *__restrict__ x0b, int B16, int Tout, int Mt, int K16, int K, int act, int ldp,
             unsigned char *__restrict__ out_split, float split_scale, unsigned *__restrict__ sat) {
     constexpr int TM = 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -280,7 +301,7 @@ k_conv_mfma(SampleBuf in, float *__restrict__ out, const v4f *__restrict__ Wp, c
         }
         // skip the whole second pass when no lane of the wave has a second window
         if (pass == 1 && !__any(any)) break;
-        mma_tiles<TM, TN, BVEC>(ap, bp, 16, K16, acc);
+        mma_tiles<TM, TN, BVEC>(ap, bp, 16, K16, acc, K);
     }
 #pragma unroll
     for (int i = 0; i < TM; i++) {
@@ -311,17 +332,19 @@ k_conv_mfma(SampleBuf in, float *__restrict__ out, const v4f *__restrict__ Wp, c
     }
 }
 
-void launch_conv_mfma(hipStream_t s, SampleBuf in, float *out, const float4 *Wp, const float *bias,
-                      const int *x0a, const int *x0b, int B16, int Tout, int M, int K16, int act, int ldp, void *out_split, int split_exp, unsigned *sat) {
+int launch_conv_mfma(hipStream_t s, SampleBuf in, float *out, const float4 *Wp, const float *bias,
+                     const int *x0a, const int *x0b, int B16, int Tout, int M, int K16, int act, int ldp, void *out_split, int split_exp, unsigned *sat, int K) {
     const int Mt = M / 16;
+    if (K <= 0 || K > 16 * K16) K = 16 * K16;
     const int nMblk = (Mt + 7) / 8, nNblk = (Tout * B16 + 7) / 8;
     const bool vec = (in.F % 4 == 0);
     if (vec)
         hipLaunchKernelGGL(k_conv_mfma<true>, dim3(nMblk * nNblk), dim3(256), 0, s, in, out, (const v4f *)Wp, bias,
-                           x0a, x0b, B16, Tout, Mt, K16, act, ldp, (unsigned char *)out_split, split_pow2(split_exp), sat);
+                           x0a, x0b, B16, Tout, Mt, K16, K, act, ldp, (unsigned char *)out_split, split_pow2(split_exp), sat);
     else
         hipLaunchKernelGGL(k_conv_mfma<false>, dim3(nMblk * nNblk), dim3(256), 0, s, in, out, (const v4f *)Wp, bias,
-                           x0a, x0b, B16, Tout, Mt, K16, act, ldp, (unsigned char *)out_split, split_pow2(split_exp), sat);
+                           x0a, x0b, B16, Tout, Mt, K16, K, act, ldp, (unsigned char *)out_split, split_pow2(split_exp), sat);
+    return vec ? kFormConvMfmaVec : kFormConvMfmaScalar;
 }
 
 // ---- last convolution on split operands ---------------------------------------------------------------------------
@@ -586,8 +609,8 @@ k_conv_split_ws(SampleBuf in, const v4u_t *__restrict__ Wp, const float *__restr
     }
 }
 
-void launch_conv_split(hipStream_t s, SampleBuf in, float *out, const void *Wp, const float *bias, const int *x0a, const int *x0b,
-                       int B16, int Tout, int M, int winlen, int act, int ldp, void *out_split, int split_exp, int acc_exp, int lean, unsigned *sat) {
+int launch_conv_split(hipStream_t s, SampleBuf in, float *out, const void *Wp, const float *bias, const int *x0a, const int *x0b,
+                      int B16, int Tout, int M, int winlen, int act, int ldp, void *out_split, int split_exp, int acc_exp, int lean, unsigned *sat) {
     const int Mt = M / 16, NC = (winlen + 1) / 2;
     // the weights-stationary form: split output, the chip to itself, shapes it is built for
     if (!lean && out_split && kSplitNS == 2 && act == ACT_SWISH && Mt % 8 == 0 && NC == 10 && (size_t)in.rs * 4 * 16 < ((size_t)1 << 32)) {
@@ -609,17 +632,18 @@ void launch_conv_split(hipStream_t s, SampleBuf in, float *out, const void *Wp, 
         if (ngroup > ((ntile + 7) & ~7)) ngroup = (ntile + 7) & ~7;
         hipLaunchKernelGGL((k_conv_split_ws<10>), dim3(NMB * ngroup), dim3(256), 0, s, in, (const v4u_t *)Wp, bias, x0a, x0b, B16, Tout, Mt, winlen, ldp,
                            (unsigned char *)out_split, split_pow2(split_exp), split_pow2(acc_exp), sat, ngroup);
-        return;
+        return kFormConvSplitWs10;
     }
     if (lean) {
         const int nMblk = (Mt + 3) / 4, nNblk = (Tout * B16 + 3) / 4;
         hipLaunchKernelGGL((k_conv_split<2, 2>), dim3(nMblk * nNblk), dim3(256), 0, s, in, out, (const v4u_t *)Wp, bias, x0a, x0b, B16, Tout, Mt, NC, winlen, act, ldp,
                            (unsigned char *)out_split, split_pow2(split_exp), split_pow2(acc_exp), sat);
-        return;
+        return kFormConvSplit22;
     }
     const int nMblk = (Mt + 7) / 8, nNblk = (Tout * B16 + 7) / 8;
     hipLaunchKernelGGL((k_conv_split<4, 4>), dim3(nMblk * nNblk), dim3(256), 0, s, in, out, (const v4u_t *)Wp, bias, x0a, x0b, B16, Tout, Mt, NC, winlen, act, ldp,
                        (unsigned char *)out_split, split_pow2(split_exp), split_pow2(acc_exp), sat);
+    return kFormConvSplit44;
 }
 
 // ---- input projection: Xa[nt][mt] = Wp[mt] . act[nt] + b ----------------------------------
@@ -962,8 +986,8 @@ k_head_split(const unsigned char *__restrict__ in, float *__restrict__ trans, co
     }
 }
 
-void launch_head_split(hipStream_t s, const void *in_split, float *trans, const void *Wsplit, const float *bias,
-                       int Tb, int B16, int nread, int P, int Ps, int Hc, float scale, int acc_exp, int raw, double *E) {
+int launch_head_split(hipStream_t s, const void *in_split, float *trans, const void *Wsplit, const float *bias,
+                      int Tb, int B16, int nread, int P, int Ps, int Hc, float scale, int acc_exp, int raw, double *E) {
     const int Mt = (P + 15) / 16;
     const int ntile = Tb * B16;
     const int Pd = crf_exp_stride(P);
@@ -974,12 +998,13 @@ void launch_head_split(hipStream_t s, const void *in_split, float *trans, const 
     else
         hipLaunchKernelGGL(k_head_split<4>, dim3((ntile + 15) / 16), dim3(256), 0, s, (const unsigned char *)in_split, trans, (const v4u_t *)Wsplit, bias, Tb, B16,
                            nread, P, Ps, Mt, Hc, scale, split_pow2(acc_exp), raw, E, Pd);
+    return Mt <= 3 ? kFormHeadSplit3 : kFormHeadSplit4;
 }
 // the head's epilogue can leave E = exp(S - max S) for the chains of ffhip_decode.hip: a block's row of crf_exp_stride(P) doubles must fit the head's row tiles
 bool head_split_writes_E(int P) { const int Mt = (P + 15) / 16; return crf_exp_stride(P) <= 16 * (Mt <= 3 ? 3 : 4) && Mt <= 4; }
 
-void launch_head(hipStream_t s, const float *in, float *trans, const float4 *Wp, const float *bias,
-                 int Tb, int B16, int nread, int P, int Ps, int K16, float scale, int raw) {
+int launch_head(hipStream_t s, const float *in, float *trans, const float4 *Wp, const float *bias,
+                int Tb, int B16, int nread, int P, int Ps, int K16, float scale, int raw) {
     const int Mt = (P + 15) / 16;
     const int ntile = Tb * B16;
     if (Mt <= 3)
@@ -988,6 +1013,7 @@ void launch_head(hipStream_t s, const float *in, float *trans, const float4 *Wp,
     else
         hipLaunchKernelGGL(k_head<4>, dim3((ntile + 15) / 16), dim3(256), 0, s, in, trans, (const v4f *)Wp, bias, Tb, B16,
                            nread, P, Ps, Mt, K16, scale, raw);
+    return Mt <= 3 ? kFormHead3 : kFormHead4;
 }
 
 // ---- CRF partition function + global normalisation -------------------------------------------

@@ -299,7 +299,7 @@ extern "C" int ffhip_op_convolution(ffhip_engine *eng, ffhip_mat X, ffhip_mat W,
         float *d_b = (float *)tmp.upload(bias.data(), bias.size() * 4, s);
         float *d_out = (float *)tmp.get((size_t)Tout * Mpad * 16 * 4);
         if (!d_w || !d_b || !d_out) OP_NOMEM();
-        launch_conv_mfma(s, in, d_out, (const float4 *)d_w, d_b, d_pa, d_pb, 1, Tout, Mpad, K16, ACT_NONE);
+        launch_conv_mfma(s, in, d_out, (const float4 *)d_w, d_b, d_pa, d_pb, 1, Tout, Mpad, K16, ACT_NONE, 0, nullptr, 0, nullptr, (int)K);
         hipLaunchKernelGGL(k_tiles_to_img, dim3(nblk((size_t)Tout * Fout)), dim3(256), 0, s, d_out, Mpad, Fout, Tout, d_c, C.stride);
     }
     HIP_TRY(mat_done(C, d_c, lazy_, s), FFHIP_EHIP);

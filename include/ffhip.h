@@ -158,6 +158,32 @@ int ffhip_batch_get_activation(ffhip_batch *b, int layer, int read, float *out);
  * projection GEMM, 2 = fused f32-MFMA layer kernel, 3 = split-operand layer kernel (two fp16 slices per operand; hidden 128/256/384/512), 4 = split-operand projection GEMM +
  * recurrence-only split-operand layer kernel (LSTM, hidden 256/512 under FFHIP_RUN_UNFUSED_RNN) */
 int ffhip_batch_rnn_path(const ffhip_batch *b);
+/* debug read-outs of the kernels on either side of the recurrent stack (tests/test_front_head_fp64_gpu.py).  None changes a run's path, kernel forms or
+ * launch shapes.
+ * keep_front(b, on): from the next run on, one device-to-device copy right behind the convolution group keeps the last convolution's output (the split
+ *   layout on the default path, fp32 otherwise); the thin convolutions' outputs stay in their buffers anyway.  Off: nothing is copied.
+ * front(b, layer, row, out): the output of convolution `layer` in batch row `row` as dense fp32 [Tout_layer][filters], the whole row, padding columns
+ *   included; split slices and fp16-slice intermediates are decoded as (h0 + h1) * 2^-e.  Needs a finished run with keep_front on.
+ * head_input(b, row, out): the last recurrent layer's output as the CRF head read it, dense fp32 [nblock][hidden] of the whole row.
+ * forms(b, out[4]): the kernel form each convolution launch (out[0 .. nconv-1]) and the head launch (out[3]) of the last run took: FFHIP_FORM_*, -1 none */
+#define FFHIP_FORM_CONV_SMALL_4_5     1   /* k_conv_small<4, 5>: 1 -> 4 features, 5 taps               */
+#define FFHIP_FORM_CONV_SMALL_16_20   2   /* k_conv_small<16, 20>: 4 -> 16 features, 5 taps             */
+#define FFHIP_FORM_CONV_SMALL_4       3   /* k_conv_small<4>: generic, at most 4 filters                */
+#define FFHIP_FORM_CONV_SMALL_16      4   /* k_conv_small<16>: generic, at most 16 filters              */
+#define FFHIP_FORM_CONV_SMALL_32      5   /* k_conv_small<32>: generic, at most 32 filters              */
+#define FFHIP_FORM_CONV_MFMA_VEC      6   /* k_conv_mfma<true>: f32 MFMA, input features a multiple of 4 */
+#define FFHIP_FORM_CONV_MFMA_SCALAR   7   /* k_conv_mfma<false>                                         */
+#define FFHIP_FORM_CONV_SPLIT_WS10    8   /* k_conv_split_ws<10>: split operands, weights stationary    */
+#define FFHIP_FORM_CONV_SPLIT_4_4     9   /* k_conv_split<4, 4>                                         */
+#define FFHIP_FORM_CONV_SPLIT_2_2    10   /* k_conv_split<2, 2>: the shape that fits beside another batch's layer launches */
+#define FFHIP_FORM_HEAD_3            11   /* k_head<3>: f32 MFMA head, at most 48 outputs                */
+#define FFHIP_FORM_HEAD_4            12   /* k_head<4>                                                  */
+#define FFHIP_FORM_HEAD_SPLIT_3      13   /* k_head_split<3>: head on the last layer's split output     */
+#define FFHIP_FORM_HEAD_SPLIT_4      14   /* k_head_split<4>                                            */
+int ffhip_debug_batch_keep_front(ffhip_batch *b, int on);
+int ffhip_debug_batch_front(ffhip_batch *b, int layer, int row, float *out);
+int ffhip_debug_batch_head_input(ffhip_batch *b, int row, float *out);
+int ffhip_debug_batch_forms(const ffhip_batch *b, int out[4]);
 /* debug tap: `ntile` tiles of 16 reads x `hidden` values (hidden % 128 == 0) through the split activation layout of
  * the recurrent layer kernel and back; two fp16 slices of value * 2^12 hold 22 bits: |out - in| <= 2^-22 for |in| <= 1 (the bf16x3 build: bit for bit) */
 int ffhip_debug_split_round_trip(ffhip_engine *eng, const float *in, float *out, size_t ntile, int hidden);

@@ -9,6 +9,7 @@ import pytest
 
 from flappie_amd import model as M
 from oracle import ffo
+from fp64_ref import numpy_conv_recipe
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -137,38 +138,6 @@ def test_identity_convolution():
 
 
 # ---- convolution: independent numpy restatement of SURVEY.md section 8a row A3 --------------------
-def numpy_conv_recipe(x, taps, bias, stride):
-    """x[T, nf]; taps[nfilter, winlen, nf].  float64 evaluation of the reference's three regions."""
-    T, nf = x.shape
-    nfilter, winlen, _ = taps.shape
-    s = stride
-    padL, padR = (winlen - 1) // 2, winlen // 2
-    Tout = -(-T // s)
-    ncolsL = -(-padL // s)
-    shiftX = ncolsL * s - padL
-    nstepC = -(-winlen // s)
-    nstepX = s * nstepC
-    xp = np.zeros((T + 2 * winlen, nf))
-    xp[winlen:winlen + T] = x
-    out = np.tile(bias.astype(np.float64), (Tout, 1))
-
-    def add(col, x0):
-        if 0 <= col < Tout:
-            win = xp[x0 + winlen: x0 + winlen + winlen]            # zero outside [0, T)
-            out[col] += np.einsum("fwj,wj->f", taps.astype(np.float64), win)
-    for w in range(0, padL, s):
-        add(w // s, w - padL)
-    for w in range(0, winlen, s):
-        for k in range((T - shiftX - w) // nstepX):
-            add(ncolsL + w // s + nstepC * k, shiftX + w + nstepX * k)
-    maxCol, rem = (T - shiftX) // nstepX, (T - shiftX) % nstepX
-    colR = ncolsL + nstepC * (maxCol - 1) + rem // s + 1
-    startR = s - (padL + T - winlen) % s - 1
-    for w in range(startR, padR, s):
-        add(colR + w // s, T - winlen + 1 + w)
-    return out
-
-
 def naive_conv(x, taps, bias, stride):
     T, nf = x.shape
     nfilter, winlen, _ = taps.shape
