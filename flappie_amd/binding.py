@@ -149,6 +149,8 @@ def lib():
     L.ffhip_debug_batch_front.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.ffhip_debug_batch_head_input.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
     L.ffhip_debug_batch_forms.argtypes = [vp, C.POINTER(C.c_int)]
+    L.ffhip_debug_batch_device_bytes.restype = C.c_size_t
+    L.ffhip_debug_batch_device_bytes.argtypes = [vp]
     _LIB = L
     return L
 
@@ -475,6 +477,10 @@ class Batch:
         _check(lib().ffhip_debug_batch_forms(self.h, out))
         nconv = len(self.dmodel.model.convs)
         return [FORMS.get(out[i], out[i]) for i in range(nconv)], FORMS.get(out[3], out[3])
+
+    def device_bytes(self) -> int:
+        """device memory the batch object holds (ffhip_debug_batch_device_bytes): its buffers, grown on first use by the paths its runs took"""
+        return int(lib().ffhip_debug_batch_device_bytes(self.h))
 
     def f32_reruns(self) -> int:
         """reads of the last run that left the split operand format's range and were run again on the f32 path (ffhip_batch_finish)"""

@@ -660,7 +660,9 @@ static RunPath plan_run(const ffhip_model *m, unsigned flags, float temperature,
     p.post_done = m->kind != FFHIP_NET_LSTM5_RLE && p.R > 0 && flipflop8_10(m) && 10.0f / temperature <= kFbRange;
     p.head_e = p.split_head && p.post_done && head_split_writes_E(m->P);
     p.rle_post8 = rle8(m) && 10.0f / temperature <= kFbRange;
-    p.packable = mp.packable && (m->kind == FFHIP_NET_LSTM5_RLE ? p.rle_post8 : p.post_done);      // (no packed form of k_rle_transpost / k_rle_partition)
+    // a packed batch takes the default path and, wherever that one takes it, the launch-per-step kernels (their LIVE forms; not with kept activations, the f32 or unfused flags)
+    const bool pack_model = mp.packable || ((flags & FFHIP_RUN_STEPWISE_RNN) && model_path(m, flags & ~(unsigned)FFHIP_RUN_STEPWISE_RNN, ncu).packable);
+    p.packable = pack_model && (m->kind == FFHIP_NET_LSTM5_RLE ? p.rle_post8 : p.post_done);      // (no packed form of k_rle_transpost / k_rle_partition)
     p.gates = gate_level(flags);
     p.rnn_path = p.split ? 3 : (p.split2 ? 4 : (p.persist ? (p.fused ? 2 : 1) : 0));
     return p;
@@ -717,6 +719,10 @@ struct ffhip_batch {
     void *actS[2] = { nullptr, nullptr };      // the same two buffers in the split-operand layout (ffhip_rnn_split.hip), allocated on first use
     float *keep[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
     float *xa = nullptr, *cstate = nullptr;
+    float *fa[2] = { nullptr, nullptr };       // the fp32 activations of the run in progress: act[], or -- a packed batch's launch-per-step run -- the memory of actS[]
+    float *xa_win = nullptr;            // the launch-per-step run's in-projection, kStepWindow steps of it (run_layers); allocated on first use
+    void *split_win = nullptr;          // ... and its input in the split layout
+    size_t dev_bytes = 0;               // what dalloc holds for the batch (ffhip_debug_batch_device_bytes)
     float *trans = nullptr, *post = nullptr, *fwd = nullptr;
     double *crf_logz = nullptr;         // fp64 partition function per read
     double *crf_e = nullptr;            // exp(score - block max), workspace of the linear-space partition function
@@ -780,6 +786,7 @@ static void *dalloc(ffhip_batch *b, size_t bytes, bool zero) {
         if (e != hipSuccess || (!b->stream && hipDeviceSynchronize() != hipSuccess)) { hipFree(d); set_err(FFHIP_EHIP, "hipMemset failed"); return nullptr; }
     }
     b->owned.push_back(d);
+    b->dev_bytes += bytes ? bytes : 4;
     return d;
 }
 
@@ -1430,14 +1437,22 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
     b->run_path = plan_run(m, flags, temperature, ncu);
     const RunPath &p = b->run_path;
     if (b->packed && !p.packable)
-        return set_err(FFHIP_EINVAL, "packed batches take the default path only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / stepwise / unfused flags, ordinary temperature)");
-    // act[0]: the convolution's fp32 output (every path but split layers behind a split-writing convolution); act[1]: the last layer's fp32 copy for the f32 head
-    for (int i = p.conv_split ? 1 : 0; i < ((p.split_head && p.conv_split) ? 1 : 2); i++)
-        if (!b->act[i] && !(b->act[i] = (float *)dalloc(b, (size_t)Tb * Bp * Hp * 4, false))) return FFHIP_ENOMEM;
-    if (p.split || p.split2) {
+        return set_err(FFHIP_EINVAL, "packed batches take the default path and the launch-per-step kernels only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / unfused flags, ordinary temperature)");
+    // A packed batch's launch-per-step run keeps its two fp32 activations in the memory of the two split buffers its default run has (the same size at two
+    // slices): a packed batch's rows are long (512 of 45 670 blocks at H = 384), and the object holds no other activation buffer on either path
+    static_assert(kSplitNS >= 2, "a split buffer holds an fp32 activation buffer");
+    const bool f32_in_split = b->packed && !(p.split || p.split2);
+    if (p.split || p.split2 || f32_in_split) {
         const size_t bytes = split_bytes((size_t)Tb * B16, Hp);
         for (int i = 0; i < 2; i++)
             if (!b->actS[i] && !(b->actS[i] = dalloc(b, bytes, false))) return FFHIP_ENOMEM;
+    }
+    // act[0]: the convolution's fp32 output (every path but split layers behind a split-writing convolution); act[1]: the last layer's fp32 copy for the f32 head
+    for (int i = 0; i < 2; i++) {
+        b->fa[i] = f32_in_split ? (float *)b->actS[i] : b->act[i];
+        if (f32_in_split || i < (p.conv_split ? 1 : 0) || i >= ((p.split_head && p.conv_split) ? 1 : 2)) continue;
+        if (!b->act[i] && !(b->act[i] = (float *)dalloc(b, (size_t)Tb * Bp * Hp * 4, false))) return FFHIP_ENOMEM;
+        b->fa[i] = b->act[i];
     }
     // ---- convolutions (layers.c:189-276, activations :24-49)
     // another batch is between run and finish: its layer launches hold 384 of every SIMD's 512 registers, so this batch's last
@@ -1473,19 +1488,19 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
             b->forms[l] = launch_conv_small(s, b->sbuf[l], b->sbuf[l + 1], c.taps, c.bias, x0a, x0b, Bp, b->plan[l].Tout, c.winlen, m->act, ldp, (b->ragged && !b->packed) ? b->rag_tin[l] : nullptr,
                               (p.conv_f16 && l == m->nconv - 2) ? kSplitExpX : -100000, b->sat, (b->packed && m->conv[l].stride == 1) ? b->rag_seg[l] : nullptr);
         else if (p.conv_f16)
-            b->forms[l] = launch_conv_split(s, b->sbuf[l], b->act[0], c.Wsplit, c.bias, x0a, x0b, B16, Tb, c.Mpad, c.winlen, m->act, ldp, p.conv_split ? b->actS[0] : nullptr,
+            b->forms[l] = launch_conv_split(s, b->sbuf[l], b->fa[0], c.Wsplit, c.bias, x0a, x0b, B16, Tb, c.Mpad, c.winlen, m->act, ldp, p.conv_split ? b->actS[0] : nullptr,
                               kSplitExpX, c.split_S, lean_conv, b->sat);
         else
-            b->forms[l] = launch_conv_mfma(s, b->sbuf[l], b->act[0], c.Wp, c.bias, x0a, x0b, B16, Tb, c.Mpad, c.K16, m->act, ldp, p.conv_split ? b->actS[0] : nullptr,
+            b->forms[l] = launch_conv_mfma(s, b->sbuf[l], b->fa[0], c.Wp, c.bias, x0a, x0b, B16, Tb, c.Mpad, c.K16, m->act, ldp, p.conv_split ? b->actS[0] : nullptr,
                              m->act == ACT_SWISH ? kSplitExpX : kSplitExpH, b->sat, c.winlen * c.Fin);
         b->launches[0]++;
     }
-    if (int rc = keep_copy(b, 0, b->act[0])) return rc;
+    if (int rc = keep_copy(b, 0, b->fa[0])) return rc;
     b->front_kept = 0;
     if (b->keep_front) {      // (debug: ffhip_debug_batch_front) the last convolution's output as it left the kernel
         const size_t f32_bytes = (size_t)Tb * Bp * Hp * 4, split_b = split_bytes((size_t)Tb * B16, Hp);
         if (!b->front_keep && !(b->front_keep = dalloc(b, std::max(f32_bytes, split_b), false))) return FFHIP_ENOMEM;
-        HIP_TRY(hipMemcpyAsync(b->front_keep, p.conv_split ? b->actS[0] : (const void *)b->act[0], p.conv_split ? split_b : f32_bytes, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+        HIP_TRY(hipMemcpyAsync(b->front_keep, p.conv_split ? b->actS[0] : (const void *)b->fa[0], p.conv_split ? split_b : f32_bytes, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
         b->front_exp = p.conv_split ? (m->act == ACT_SWISH ? kSplitExpX : kSplitExpH) : -100000;
         b->front_f16 = (p.conv_f16 && m->nconv >= 2) ? m->nconv - 2 : -1;
         b->front_kept = 1;
@@ -1493,7 +1508,7 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
     mark(b, 1);
     HIP_TRY(hipMemsetAsync(b->pabort, (p.persist && dbg("force_abort")) ? 1 : 0, sizeof(unsigned), s), FFHIP_EHIP);      // (debug: pretend a wait timed out)
     if ((p.split || p.split2) && !p.conv_split) {
-        launch_split_from_f32(s, b->act[0], b->actS[0], (size_t)Tb * B16, Hp, m->act == ACT_SWISH ? kSplitExpX : kSplitExpH, b->sat, B16);
+        launch_split_from_f32(s, b->fa[0], b->actS[0], (size_t)Tb * B16, Hp, m->act == ACT_SWISH ? kSplitExpX : kSplitExpH, b->sat, B16);
         b->launches[0]++;
     }
     b->run_cur = 0;
@@ -1504,6 +1519,31 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
         for (unsigned k = 1; k <= 2 && k <= eng->done_head; k++) HIP_TRY(hipStreamWaitEvent(s, eng->done_ring[(eng->done_head - k) & 3u], 0), FFHIP_EHIP);
     return FFHIP_OK;
 }
+
+// The in-projection of layer l for n steps (in: the activations of their first step, fp32 tile-interleaved; tiles are step-major, so the steps are one tile
+// range) into xa: on the bf16 pipes over split operands where the layer has them (fp32-exact products) -- the input is converted to
+// the split layout in *split first, allocated on first use at n steps --, else the f32 GEMM.
+static int project(ffhip_batch *b, int l, const float *in, int n, float *xa, void **split) {
+    const ffhip_model *m = b->mdl;
+    const RnnDev &r = m->rnn[l];
+    hipStream_t s = b->stream;
+    const int B16 = b->B16, Hp = m->Hp;
+    if (r.Wsplit && b->run_path.proj_split) {
+        if (!*split && !(*split = dalloc(b, split_bytes((size_t)n * B16, Hp), false))) return FFHIP_ENOMEM;
+        // (sat: the flag is the read tile's, tile % B16 -- a range of whole steps keeps it)
+        launch_split_from_f32(s, in, *split, (size_t)n * B16, Hp, (l == 0 && m->act == ACT_SWISH) ? kSplitExpX : kSplitExpH, b->sat, B16);
+        launch_inproj_split(s, *split, xa, r.Wsplit, r.bias, n * B16, Hp, r.split_S);
+        b->launches[1] += 2;
+    } else {
+        launch_inproj(s, in, xa, r.iWp, r.bias, n * B16, 4 * Hp, r.Kin16);
+        b->launches[1]++;
+    }
+    return FFHIP_OK;
+}
+
+// steps of in-projection the launch-per-step path computes ahead of its step launches (run_layers): 128 steps of 512 reads at H = 384 are 0.5 GB
+// (projection and its split input), two launches per 128 step launches
+constexpr int kStepWindow = 128;
 
 // ---- recurrent stack: B,F,B,F,B (networks.c:556-580 / :459-483).  Profiling groups 1 (in-projection) and 2 (recurrent) interleave:
 // per-layer events split them when profiling is on.
@@ -1520,7 +1560,7 @@ static int run_layers(ffhip_batch *b) {
     for (int l = 0; l < 5; l++) {
         const RnnDev &r = m->rnn[l];
         const bool backward = (l % 2 == 0);
-        float *in = b->act[cur], *out = b->act[cur ^ 1];
+        float *in = b->fa[cur], *out = b->fa[cur ^ 1];
         if (prof) hipEventRecord(b->lev[l][0], s);
         if (p.split2) {
             if (!b->xa && !(b->xa = (float *)dalloc(b, (size_t)Tb * Bp * Hp * 4 * 4, false))) return FFHIP_ENOMEM;
@@ -1561,57 +1601,57 @@ static int run_layers(ffhip_batch *b) {
                 if (int rc = layer_launched(eng, s, chain)) return rc;
                 b->launches[2]++;
             }
-        } else {
-            const bool fuse = p.persist && p.fused;
+        } else if (p.persist) {
+            const bool fuse = p.fused;
             if (!fuse) {
                 if (!b->xa && !(b->xa = (float *)dalloc(b, (size_t)Tb * Bp * Hp * 4 * 4, false))) return FFHIP_ENOMEM;
-                if (r.Wsplit && p.proj_split) {
-                    // projection on the bf16 pipes over split operands (fp32-exact products): the layer input is
-                    // converted to the split layout first
-                    if (!b->actS[0] && !(b->actS[0] = dalloc(b, split_bytes((size_t)Tb * B16, Hp), false))) return FFHIP_ENOMEM;
-                    launch_split_from_f32(s, in, b->actS[0], (size_t)Tb * B16, Hp, (l == 0 && m->act == ACT_SWISH) ? kSplitExpX : kSplitExpH, b->sat, B16);
-                    launch_inproj_split(s, b->actS[0], b->xa, r.Wsplit, r.bias, Tb * B16, Hp, r.split_S);
-                    b->launches[1] += 2;
-                } else {
-                    launch_inproj(s, in, b->xa, r.iWp, r.bias, Tb * B16, 4 * Hp, r.Kin16);
-                    b->launches[1]++;
-                }
+                if (int rc = project(b, l, in, Tb, b->xa, &b->actS[0])) return rc;
             }
             if (prof) hipEventRecord(b->lev[l][1], s);
+            // one launch per layer (and per chunk of read tiles that fits co-resident on the chip)
+            const int maxt = persist_max_tiles(m->cell, Hp, ncu, fuse);
+            // the output doubles as the hand-off flag: pre-fill with the NaN sentinel
+            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out, (int)0xFFFFFFFF, (size_t)Tb * Bp * Hp, s), FFHIP_EHIP);
+            for (int rt0 = 0; rt0 < B16; rt0 += maxt) {
+                const int nrt = (B16 - rt0 < maxt) ? B16 - rt0 : maxt;
+                HIP_TRY(hipMemsetAsync(b->pflags, 0, persist_flag_words(Hp, nrt) * sizeof(unsigned), s), FFHIP_EHIP);
+                const bool chain = !b->persist_concurrent_ok;
+                if (int rc = layer_wait(eng, s, chain)) return rc;
+                const bool okl = fuse
+                    ? launch_lstm_fused(s, m->cell, r.sWp, r.iWp, r.bias, in, out, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt, backward, p.persist_mode, tbs, tbt)
+                    : launch_rnn_persist(s, m->cell, r.sWp, b->xa, out, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt, backward, p.persist_mode, tbs, tbt);
+                if (!okl) return set_err(FFHIP_EINVAL, "persistent recurrent kernel: unsupported shape");
+                if (int rc = layer_launched(eng, s, chain)) return rc;
+                b->launches[2]++;
+            }
+        } else {
+            // launch per step.  The in-projection is computed a window of kStepWindow steps at a time, in the order the steps run (a reverse
+            // layer: from the row's end down), into buffers of one window: what this path holds beside the two activations does not grow with the row.
+            // (The projections are per tile: a window's values are the bits the whole layer's projection has.)
+            const int W = std::min(kStepWindow, Tb);
+            if (!b->xa_win && !(b->xa_win = (float *)dalloc(b, (size_t)W * Bp * Hp * 4 * 4, false))) return FFHIP_ENOMEM;
             const size_t xa_step = (size_t)Bp * Hp * 4, h_step = (size_t)Bp * Hp;
-            if (p.persist) {
-                // one launch per layer (and per chunk of read tiles that fits co-resident on the chip)
-                const int maxt = persist_max_tiles(m->cell, Hp, ncu, fuse);
-                // the output doubles as the hand-off flag: pre-fill with the NaN sentinel
-                HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out, (int)0xFFFFFFFF, (size_t)Tb * Bp * Hp, s), FFHIP_EHIP);
-                for (int rt0 = 0; rt0 < B16; rt0 += maxt) {
-                    const int nrt = (B16 - rt0 < maxt) ? B16 - rt0 : maxt;
-                    HIP_TRY(hipMemsetAsync(b->pflags, 0, persist_flag_words(Hp, nrt) * sizeof(unsigned), s), FFHIP_EHIP);
-                    const bool chain = !b->persist_concurrent_ok;
-                    if (int rc = layer_wait(eng, s, chain)) return rc;
-                    const bool okl = fuse
-                        ? launch_lstm_fused(s, m->cell, r.sWp, r.iWp, r.bias, in, out, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt, backward, p.persist_mode, tbs, tbt)
-                        : launch_rnn_persist(s, m->cell, r.sWp, b->xa, out, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt, backward, p.persist_mode, tbs, tbt);
-                    if (!okl) return set_err(FFHIP_EINVAL, "persistent recurrent kernel: unsupported shape");
-                    if (int rc = layer_launched(eng, s, chain)) return rc;
-                    b->launches[2]++;
-                }
-            } else {
-                for (int i = 0; i < Tb; i++) {
+            for (int w0 = 0; w0 < Tb; w0 += W) {
+                const int n = std::min(W, Tb - w0);
+                const int ta = backward ? Tb - w0 - n : w0;                 // the window's first step in memory order
+                if (int rc = project(b, l, in + (size_t)ta * h_step, n, b->xa_win, &b->split_win)) return rc;
+                if (prof && w0 == 0) hipEventRecord(b->lev[l][1], s);
+                for (int i = w0; i < w0 + n; i++) {
                     const int t = backward ? Tb - 1 - i : i;
                     const int tp = backward ? t + 1 : t - 1;
                     const float *hp = (i == 0) ? nullptr : out + (size_t)tp * h_step;
+                    const float *xa_t = b->xa_win + (size_t)(t - ta) * xa_step;
                     if (m->cell == 0)
-                        launch_lstm_step(s, r.sWp, b->xa + (size_t)t * xa_step, hp, out + (size_t)t * h_step, b->cstate, B16, Hp, i == 0, t, tbs);
+                        launch_lstm_step(s, r.sWp, xa_t, hp, out + (size_t)t * h_step, b->cstate, B16, Hp, i == 0, t, tbs, live);
                     else
-                        launch_gru_step(s, r.sWp, b->xa + (size_t)t * xa_step, hp, out + (size_t)t * h_step, B16, Hp, i == 0, t, tbs);
+                        launch_gru_step(s, r.sWp, xa_t, hp, out + (size_t)t * h_step, B16, Hp, i == 0, t, tbs, live);
                 }
-                b->launches[2] += Tb;
             }
+            b->launches[2] += Tb;
         }
         if (prof) hipEventRecord(b->lev[l][2], s);
         cur ^= 1;
-        if (int rc = keep_copy(b, l + 1, b->act[cur])) return rc;
+        if (int rc = keep_copy(b, l + 1, b->fa[cur])) return rc;
     }
     b->run_cur = cur;
     return FFHIP_OK;
@@ -1639,7 +1679,7 @@ static int run_back(ffhip_batch *b) {
     if (rle) {
         // ---- globalnorm_runlengthV2 (layers.c:1325-1358)
         b->forms[3] = p.split_head ? launch_head_split(s, b->actS[cur], b->trans, m->FFsplit, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 32, 1.0f, m->FF_split_S, 1)
-                                   : launch_head(s, b->act[cur], b->trans, m->FFp, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 16, 1.0f, 1);
+                                   : launch_head(s, b->fa[cur], b->trans, m->FFp, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 16, 1.0f, 1);
         if (b->packed) { HIP_TRY(hipEventRecord(eng->head_done, s), FFHIP_EHIP); eng->head_done_rec = 1; }      // (as below: apply_packed)
         // activation over the slots' rows; partition function and subtraction per read
         launch_rle_head_finish(s, b->trans, b->crf_logz, b->nread, Tb, m->nbase, m->Ps, temperature, tbs, nR, tbr, rmap, gblk);
@@ -1648,7 +1688,7 @@ static int run_back(ffhip_batch *b) {
         // ---- globalnorm_flipflop (layers.c:1082-1106)
         b->forms[3] = p.split_head ? launch_head_split(s, b->actS[cur], b->trans, m->FFsplit, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 32, temperature / 5.0f, m->FF_split_S, 0,
                                                        p.head_e ? b->crf_e : nullptr)
-                                   : launch_head(s, b->act[cur], b->trans, m->FFp, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 16, temperature / 5.0f);
+                                   : launch_head(s, b->fa[cur], b->trans, m->FFp, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 16, temperature / 5.0f);
         if (b->packed) { HIP_TRY(hipEventRecord(eng->head_done, s), FFHIP_EHIP); eng->head_done_rec = 1; }      // (the next packed batch's set-up and convolutions start behind it: apply_packed)
         if (p.post_done) {
             const bool want_post = !(flags & FFHIP_RUN_NO_DECODE) && !(flags & FFHIP_RUN_VITERBI_ONLY);
@@ -1894,7 +1934,7 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
     if (b->counted) { b->counted = 0; b->eng->in_flight--; }
     HIP_TRY(hipGetLastError(), FFHIP_EHIP);
     if (*b->h_abort != 0) {
-        if ((b->last_flags & FFHIP_RUN_STEPWISE_RNN) || getenv("FFHIP_NO_FALLBACK") || b->packed)      // (a packed batch has no launch-per-step form: the caller sets its reads again, one to a row)
+        if ((b->last_flags & FFHIP_RUN_STEPWISE_RNN) || getenv("FFHIP_NO_FALLBACK"))
             return set_err(FFHIP_ETIMEOUT, "persistent recurrent kernel: an inter-workgroup wait timed out; results are invalid");
         // Not every workgroup of a persistent layer launch became resident -- something else holds part of the GPU.  The
         // launch-per-step kernels have no such requirement: run this batch again on them, and stay there for a while.
@@ -2069,6 +2109,7 @@ extern "C" int ffhip_debug_batch_head_input(ffhip_batch *b, int row, float *out)
 }
 
 extern "C" int ffhip_debug_fallback_count(const ffhip_engine *eng) { return eng ? eng->fallbacks : -1; }
+extern "C" size_t ffhip_debug_batch_device_bytes(const ffhip_batch *b) { return b ? b->dev_bytes : 0; }
 
 // development counter next to the abort word (e.g. re-sweeps of the split layer kernel in builds that count them)
 extern "C" unsigned ffhip_debug_batch_counter(ffhip_batch *b) {

@@ -91,11 +91,11 @@ int launch_conv_split(hipStream_t s, SampleBuf in, float *out, const void *Wp, c
 void launch_inproj(hipStream_t s, const float *in, float *xa, const float4 *Wp, const float *bias,
                    int ntile /*Tb*B16*/, int M /*rows, mult of 16*/, int K16);
 
-// one recurrent step for all reads (launch-per-step path)
+// one recurrent step for all reads (launch-per-step path); live: a packed batch's mask [t][read tile] (tbs is not read then)
 void launch_lstm_step(hipStream_t s, const float4 *sWp, const float *xa_t, const float *h_prev, float *h_out,
-                      float *cstate, int B16, int H, int first, int t = 0, const int *tbs = nullptr);
+                      float *cstate, int B16, int H, int first, int t = 0, const int *tbs = nullptr, const unsigned *live = nullptr);
 void launch_gru_step(hipStream_t s, const float4 *sWp, const float *xa_t, const float *h_prev, float *h_out,
-                     int B16, int H, int first, int t = 0, const int *tbs = nullptr);
+                     int B16, int H, int first, int t = 0, const int *tbs = nullptr, const unsigned *live = nullptr);
 
 // persistent recurrent layer (ffhip_rnn_persist.hip): one launch per layer and chunk of read tiles
 bool persist_supported(int kind, int H, int ncu);

@@ -703,9 +703,14 @@ void launch_inproj(hipStream_t s, const float *in, float *xa, const float4 *Wp, 
 // read tile.  After the MFMA chain lane l = (q = l>>4, r = l&15) holds the four gate
 // pre-activations of hidden unit 4*ut+q for read r: the gate math is lane-local and the cell
 // state never leaves its lane's slot.
+// LIVE: the packed-batch form (live = the batch's mask, word [t][read tile], bit r = slot r of the tile holds a block of a read at step t).  Where the
+// bit is clear -- the gaps between two reads of a slot, its tail -- h and c are forced to zero: the next read's zero start in either direction, as in
+// the split kernels' LIVE forms.  Its own instantiation: the one-read-a-slot kernel stays what it was.
+template <bool LIVE>
 __global__ void __launch_bounds__(256)
 k_lstm_step(const v4f *__restrict__ sWp, const v4f *__restrict__ xa_t, const float *__restrict__ h_prev,
-            float *__restrict__ h_out, float *__restrict__ cstate, int Ut, int K16, int first, int t, const int *__restrict__ tbs) {
+            float *__restrict__ h_out, float *__restrict__ cstate, int Ut, int K16, int first, int t, const int *__restrict__ tbs,
+            const unsigned *__restrict__ live) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ut = blockIdx.x * 4 + wave, rt = blockIdx.y;
     if (ut >= Ut) return;
@@ -730,24 +735,32 @@ k_lstm_step(const v4f *__restrict__ sWp, const v4f *__restrict__ xa_t, const flo
     c = forget + update;
     float h = logistic_ref(acc.w) * tanh_ref(c);
     const int q = lane >> 4, rl = lane & 15;
-    if (tbs && t >= tbs[rt * 16 + rl]) { h = 0.0f; c = 0.0f; }        // beyond this read's end (ragged batch)
+    if constexpr (LIVE) {
+        if (!((live[(size_t)t * gridDim.y + rt] >> rl) & 1u)) { h = 0.0f; c = 0.0f; }      // between two reads of the slot, or behind its last
+    } else {
+        if (tbs && t >= tbs[rt * 16 + rl]) { h = 0.0f; c = 0.0f; }        // beyond this read's end (ragged batch)
+    }
     cstate[((size_t)rt * Ut + ut) * 64 + lane] = c;
     h_out[((size_t)rt * Ut + ut) * 64 + rl * 4 + q] = h;
 }
 
 void launch_lstm_step(hipStream_t s, const float4 *sWp, const float *xa_t, const float *h_prev, float *h_out,
-                      float *cstate, int B16, int H, int first, int t, const int *tbs) {
+                      float *cstate, int B16, int H, int first, int t, const int *tbs, const unsigned *live) {
     const int Ut = H / 4, K16 = H / 16;
-    hipLaunchKernelGGL(k_lstm_step, dim3((Ut + 3) / 4, B16), dim3(256), 0, s, (const v4f *)sWp, (const v4f *)xa_t,
-                       h_prev, h_out, cstate, Ut, K16, first, t, tbs);
+    if (live) hipLaunchKernelGGL(k_lstm_step<true>, dim3((Ut + 3) / 4, B16), dim3(256), 0, s, (const v4f *)sWp, (const v4f *)xa_t,
+                                 h_prev, h_out, cstate, Ut, K16, first, t, nullptr, live);
+    else hipLaunchKernelGGL(k_lstm_step<false>, dim3((Ut + 3) / 4, B16), dim3(256), 0, s, (const v4f *)sWp, (const v4f *)xa_t,
+                            h_prev, h_out, cstate, Ut, K16, first, t, tbs, nullptr);
 }
 
 // grumod_step, layers.c:664-715.  Gate rows per unit: z, r, candidate, (unused).  The recurrent
 // weights of row 3 are zero; Xa row 2 (candidate input) is kept out of the accumulator because
 // the reference zeroes that chunk before the GEMV (:691) and adds x afterwards (:705).
+// (LIVE: as k_lstm_step's)
+template <bool LIVE>
 __global__ void __launch_bounds__(256)
 k_gru_step(const v4f *__restrict__ sWp, const v4f *__restrict__ xa_t, const float *__restrict__ h_prev,
-           float *__restrict__ h_out, int Ut, int K16, int first, int t, const int *__restrict__ tbs) {
+           float *__restrict__ h_out, int Ut, int K16, int first, int t, const int *__restrict__ tbs, const unsigned *__restrict__ live) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ut = blockIdx.x * 4 + wave, rt = blockIdx.y;
     if (ut >= Ut) return;
@@ -773,15 +786,21 @@ k_gru_step(const v4f *__restrict__ sWp, const v4f *__restrict__ xa_t, const floa
     float hbar = r * acc.z + x.z;
     hbar = tanh_ref(hbar);
     float h = z * hp + (1.0f - z) * hbar;
-    if (tbs && t >= tbs[rt * 16 + rl]) h = 0.0f;                        // beyond this read's end (ragged batch)
+    if constexpr (LIVE) {
+        if (!((live[(size_t)t * gridDim.y + rt] >> rl) & 1u)) h = 0.0f;                  // between two reads of the slot, or behind its last
+    } else {
+        if (tbs && t >= tbs[rt * 16 + rl]) h = 0.0f;                        // beyond this read's end (ragged batch)
+    }
     h_out[((size_t)rt * Ut + ut) * 64 + rl * 4 + q] = h;
 }
 
 void launch_gru_step(hipStream_t s, const float4 *sWp, const float *xa_t, const float *h_prev, float *h_out,
-                     int B16, int H, int first, int t, const int *tbs) {
+                     int B16, int H, int first, int t, const int *tbs, const unsigned *live) {
     const int Ut = H / 4, K16 = H / 16;
-    hipLaunchKernelGGL(k_gru_step, dim3((Ut + 3) / 4, B16), dim3(256), 0, s, (const v4f *)sWp, (const v4f *)xa_t,
-                       h_prev, h_out, Ut, K16, first, t, tbs);
+    if (live) hipLaunchKernelGGL(k_gru_step<true>, dim3((Ut + 3) / 4, B16), dim3(256), 0, s, (const v4f *)sWp, (const v4f *)xa_t,
+                                 h_prev, h_out, Ut, K16, first, t, nullptr, live);
+    else hipLaunchKernelGGL(k_gru_step<false>, dim3((Ut + 3) / 4, B16), dim3(256), 0, s, (const v4f *)sWp, (const v4f *)xa_t,
+                            h_prev, h_out, Ut, K16, first, t, tbs, nullptr);
 }
 
 // ---- CRF head: trans[r][blk][p] = tanh(W^T h + b) / (temperature/5) --------------------------

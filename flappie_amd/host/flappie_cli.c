@@ -318,6 +318,7 @@ static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &
 static double t_program_start;          /* main's first statement (FLAPPIE_DEBUG=pack_log's time stamps) */
 /* what the run basecalled: reads, samples of their trimmed ranges (the metric of SURVEY.md section 8d), samples read from the files */
 static unsigned long long n_called_reads, n_called_samples, n_raw_samples;
+static unsigned long long n_lost_reads;  /* reads of batches that failed and could not be called another way: the exit status says so */
 /* what the batches cost: a batch (a launch per layer) takes as long as its longest read needs whatever the others' lengths, a read tile of 16 as long as
  * ITS longest read holds its workgroups -- samples submitted against samples x slots paid for, at both grains (FLAPPIE_CLI_TIMING prints them) */
 static unsigned long long n_batches, n_packed_batches, n_batch_samples, n_batch_slot_samples, n_tile_slot_samples;
@@ -386,12 +387,13 @@ static size_t pack_row_cap(size_t want) {
 /* A group of prepared reads in flight: submitted (upload + network + decode enqueued on the batch's stream), collected
  * later (flappie.c:264-316 after normalisation) -- so the host side of the next group overlaps the GPU side of this one. */
 struct chunk_ctx;
-typedef struct { ffhip_batch *b; int cached, n, *idx; item **its; const ffhip_prep *prep; struct chunk_ctx *owner; } pending_batch;
+typedef struct { ffhip_batch *b; int cached, n, *idx; item **its; const ffhip_prep *prep; struct chunk_ctx *owner; int packed; } pending_batch;
+static unsigned run_flags(void) { return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE); }
 
 /* n reads in the rows of one packed batch: slot_of / off_of from ffhip_pack_plan, `cap` the row capacity it was made for */
 static pending_batch submit_packed(struct ffhip_engine *eng, const struct ffhip_model *mdl, const ffhip_prep *prep, item **its, int n, const int *slot_of, const int *off_of,
                                    int rows, int rows_full, size_t cap, size_t cap_obj, int max_reads, int slot, int single) {
-    pending_batch pb = { NULL, 1, n, malloc((n > 0 ? n : 1) * sizeof(int)), malloc((n > 0 ? n : 1) * sizeof(item *)), prep, NULL };
+    pending_batch pb = { NULL, 1, n, malloc((n > 0 ? n : 1) * sizeof(int)), malloc((n > 0 ? n : 1) * sizeof(item *)), prep, NULL, 1 };
     memcpy(pb.its, its, n * sizeof(item *));
     size_t longest = 0;
     unsigned long long samples = 0;
@@ -423,7 +425,7 @@ static pending_batch submit_packed(struct ffhip_engine *eng, const struct ffhip_
     double t0 = now_s();
     pb.b = acquire_packed(eng, mdl, rows, rows_full, cap_obj, max_reads, slot, single);      /* (the object's rows come in steps; the plan was made for rows of `cap` samples) */
     t_phase[2] += now_s() - t0; t0 = now_s();
-    const unsigned flags = (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE);
+    const unsigned flags = run_flags();
     if (getenv("FLAPPIE_CLI_TIMING")) fprintf(stderr, "packed batch: %d reads, %.1f Msamples in %d rows planned for %zu samples (longest row %zu)\n", n, (double)samples / 1e6, rows, cap, longest * spb);
     int rc_sub = (NULL == pb.b) ? -1 : ffhip_batch_set_prepared_packed(pb.b, prep, n, pb.idx, slot_of, off_of);
     t_phase[6] += now_s() - t0;
@@ -437,7 +439,7 @@ static pending_batch submit_packed(struct ffhip_engine *eng, const struct ffhip_
 
 static pending_batch submit_batch(struct ffhip_engine *eng, const struct ffhip_model *mdl, const ffhip_prep *prep, item **its, int n, int slot) {
     const int nmax = (n > args.batch) ? n : args.batch;
-    pending_batch pb = { NULL, 0, n, malloc(nmax * sizeof(int)), malloc(n * sizeof(item *)), prep, NULL };
+    pending_batch pb = { NULL, 0, n, malloc(nmax * sizeof(int)), malloc(n * sizeof(item *)), prep, NULL, 0 };
     memcpy(pb.its, its, n * sizeof(item *));
     for (int i = 0; i < nmax; i++) pb.idx[i] = (i < n) ? its[i]->prepared : -1;             /* -1: empty slot */
     size_t len = 0;                                          /* capacity = the longest read of the (sorted) group */
@@ -458,7 +460,7 @@ static pending_batch submit_batch(struct ffhip_engine *eng, const struct ffhip_m
     pb.b = acquire_batch(eng, mdl, n, len, slot, &pb.cached, &nslot);
     (void)nslot;
     t_phase[2] += now_s() - t0; t0 = now_s();
-    const unsigned flags = (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE);
+    const unsigned flags = run_flags();
     int rc_sub = (NULL == pb.b) ? -1 : ffhip_batch_set_prepared(pb.b, prep, pb.idx);
     t_phase[6] += now_s() - t0;
     const double t1 = now_s();
@@ -473,6 +475,33 @@ static pending_batch submit_batch(struct ffhip_engine *eng, const struct ffhip_m
     return pb;
 }
 
+static int by_length_desc(const void *x, const void *y);
+static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb);
+/* A packed batch that failed, at submit or at collect: its reads are called again one read a row, here and now, in batch objects of their own (the cached ones
+ * may be in flight) -- no read is dropped for it.  Rare by construction (the engine itself re-runs a batch whose layer launch timed out): written for clarity. */
+static void call_one_read_a_row(const struct ffhip_model *mdl, const pending_batch *failed) {
+    item **its = failed->its;
+    const int n = failed->n;
+    warnx("a packed batch of %d read(s) failed; its reads go to one-read-a-row batches", n);
+    qsort(its, n, sizeof(item *), by_length_desc);
+    for (int i = 0; i < n; ) {
+        const size_t longest = its[i]->res.rt.end - its[i]->res.rt.start;
+        int g = 1;
+        while (i + g < n && g < args.batch && 4 * (its[i + g]->res.rt.end - its[i + g]->res.rt.start) >= 3 * longest) g++;
+        pending_batch one = { NULL, 0, g, malloc(g * sizeof(int)), malloc(g * sizeof(item *)), failed->prep, NULL, 0 };
+        if (one.idx && one.its) {
+            memcpy(one.its, its + i, g * sizeof(item *));
+            for (int k = 0; k < g; k++) one.idx[k] = its[i + k]->prepared;
+            one.b = ffhip_batch_create(flappie_hip_engine(), mdl, g, longest);
+            int rc = (NULL == one.b) ? -1 : ffhip_batch_set_prepared(one.b, failed->prep, one.idx);
+            if (0 == rc) rc = ffhip_batch_run(one.b, args.temperature, run_flags());
+            if (0 != rc) { warnx("%s", ffhip_last_error()); if (one.b) ffhip_batch_destroy(one.b); one.b = NULL; }
+        }
+        collect_batch(mdl, &one);                      /* (a failure there counts the group's reads as not called) */
+        i += g;
+    }
+}
+
 static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
     ffhip_batch *b = pb->b;
     item **its = pb->its;
@@ -481,6 +510,8 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
     double t0 = now_s();
     if (NULL == b || 0 != ffhip_batch_finish(b)) {
         if (b) { warnx("%s", ffhip_last_error()); if (!cached) ffhip_batch_destroy(b); }
+        if (pb->packed && its) call_one_read_a_row(mdl, pb);
+        else n_lost_reads += (unsigned long long)n;
         free(pb->idx); free(pb->its);
         pb->b = NULL;
         return;
@@ -922,7 +953,11 @@ static void pipe_chunk(struct ffhip_engine *eng, const struct ffhip_model *mdl, 
                 cap = ((size_t)((double)cap * 1.06) + 1023) & ~(size_t)1023;
                 if (cap > cap_obj) cap = cap_obj;
             }
-            if (placed <= 0) { warnx("packed batch: no read fits a row of %zu samples", cap); break; }
+            if (placed <= 0) {                             /* (no read is dropped for it: what is left of the chunk goes one read a row) */
+                warnx("packed batch: no read fits a row of %zu samples; the chunk's %d remaining read(s) go to one-read-a-row batches", cap, nleft);
+                run_groups(eng, mdl, c, rest, nleft, hdf5out, depth);
+                break;
+            }
             int nsel = 0, nrest = 0;
             for (int i = 0; i < nleft; i++) {
                 if (slot_of[i] >= 0) { sel[nsel] = rest[i]; sl2[nsel] = slot_of[i]; of2[nsel] = off_of[i]; nsel++; }
@@ -1366,5 +1401,6 @@ int main(int argc, char *argv[]) {
         warnx("%llu read(s) held samples beyond the range of the default kernels' operand format and were evaluated on the f32 kernels", ffhip_engine_f32_reruns(eng));
     flappie_hip_shutdown();
     if (reader_failures) { warnx("%d reader process(es) failed; see the warnings above", reader_failures); return EXIT_FAILURE; }
+    if (n_lost_reads > 0) { warnx("%llu read(s) were not called: their batches failed (see the warnings above)", n_lost_reads); return EXIT_FAILURE; }
     return EXIT_SUCCESS;
 }

@@ -350,9 +350,10 @@ int ffhip_batch_set_prepared(ffhip_batch *b, const ffhip_prep *prep, const int *
  * starting at a block offset of the caller's choice with at least ffhip_model_pack_gap() free blocks behind it.  Every read is still evaluated whole and
  * exactly as if it were alone (bit for bit what the one-read-a-row batch gives): the convolutions see zero padding either side of it, the recurrent
  * layers start from a zero state at its first block and, in the reverse layers, at its last; partition function, posterior, Viterbi, strings and trace
- * are per read.  Results are indexed by READ, 0 .. nread - 1 in the order of the set call.  The default path only (the 8- and 10-state flip-flop models and the
- * run-length model FFHIP_NET_LSTM5_RLE of nbase 4, with 128 .. 512 hidden units; no FFHIP_RUN_KEEP_ACTS / _F32_RNN / _STEPWISE_RNN / _UNFUSED_RNN; a temperature of at
- * least 0.1): ffhip_batch_run says so otherwise.  A packed run-length batch gives per read what one read a row gives: path, qpath, score, transitions and posterior, and
+ * are per read.  Results are indexed by READ, 0 .. nread - 1 in the order of the set call.  The default path and the launch-per-step kernels (FFHIP_RUN_STEPWISE_RNN,
+ * and the fall-back of ffhip_batch_finish when a persistent layer launch timed out) only: the 8- and 10-state flip-flop models and the run-length model
+ * FFHIP_NET_LSTM5_RLE of nbase 4, with 128 .. 512 hidden units; no FFHIP_RUN_KEEP_ACTS / _F32_RNN / _UNFUSED_RNN; a temperature of at least 0.1 --
+ * ffhip_batch_run says so otherwise.  A packed run-length batch gives per read what one read a row gives: path, qpath, score, transitions and posterior, and
  * no base / quality strings or trace.  ffhip_batch_run_pair takes packed batches too. */
 int ffhip_model_packable(const ffhip_model *mdl);         /* 1: this model's default path takes packed batches on this device */
 size_t ffhip_model_pack_gap(const ffhip_model *mdl);      /* free blocks a read of a packed row needs behind it */
@@ -387,6 +388,9 @@ int ffhip_batch_profile(const ffhip_batch *b, float ms[FFHIP_NGROUP], int launch
  * its peer workgroups (another tenant on the GPU); each occurrence also warns on stderr once per process and sends the next 64 runs
  * to those kernels directly */
 int ffhip_debug_fallback_count(const ffhip_engine *eng);
+/* device memory the batch holds (its buffers, grown on first use by the paths its runs took): a packed batch's launch-per-step run adds less than one
+ * activation buffer to what its default run holds -- the in-projection is computed a window of steps at a time */
+size_t ffhip_debug_batch_device_bytes(const ffhip_batch *b);
 /* Reads whose swish-convolution outputs left the range of the default path's operand format (two fp16 slices of value * 2^4: +-4094;
  * the reference's swish_activation_inplace, layers.c:24-33, has no bound): the producing kernels flag them, ffhip_batch_finish runs
  * them again through the all-f32 kernels (FFHIP_RUN_F32_RNN, no bound) and puts those results in place -- no read is returned
