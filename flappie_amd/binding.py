@@ -26,6 +26,9 @@ RUN_F32_RNN = 64
 RUN_FAST_GATES = 128
 RUN_FAST_GATES2 = 256
 RUN_EXACT_GATES = 512
+RUN_RLE_RUNS = 1024       # run-length model: run bases + run-length estimates made on the device (Batch.rle_runs)
+RUN_RLE_RECORDS = 2048    # ... and every run's shape, scale and dwell
+RLE_SCALE_DEFAULT = (1.02, 1.04, 1.04, 1.02)      # decode_runnie.py's default --scale (A, C, G, T)
 # ffhip_debug_gate_math forms (include/ffhip.h)
 GATE_FORMS = ("logistic_ref", "tanh_ref", "logistic_ref4_lean", "logistic_ref2_lean", "logistic_ref_lean", "tanh_ref_lean",
               "swish_act4", "tanh_act4", "logistic_hw1", "tanh_hw1", "logistic_hw2", "tanh_hw2")
@@ -53,6 +56,19 @@ class CModelDesc(C.Structure):
                 ("rnn_iW", C.POINTER(CMat) * 5), ("rnn_sW", C.POINTER(CMat) * 5),
                 ("rnn_b", C.POINTER(CMat) * 5),
                 ("FF_W", C.POINTER(CMat)), ("FF_b", C.POINTER(CMat))]
+
+
+class CFMat(C.Structure):
+    """`ffhip_mat` of include/ffhip.h, a plain host array (no device image)"""
+    _fields_ = [("data", C.POINTER(C.c_float)), ("nr", C.c_size_t), ("nc", C.c_size_t), ("stride", C.c_size_t),
+                ("dev", C.c_void_p), ("dev_state", C.c_void_p)]
+
+
+class CRleRuns(C.Structure):
+    """`ffhip_rle_runs` of include/ffhip.h"""
+    _fields_ = [("nrun", C.c_size_t), ("length", C.c_ulonglong), ("failed", C.c_int),
+                ("base", C.POINTER(C.c_uint8)), ("est", C.POINTER(C.c_int32)),
+                ("shape", C.POINTER(C.c_float)), ("scale", C.POINTER(C.c_float)), ("dwell", C.POINTER(C.c_int32))]
 
 
 class CRawTable(C.Structure):
@@ -151,6 +167,11 @@ def lib():
     L.ffhip_debug_batch_forms.argtypes = [vp, C.POINTER(C.c_int)]
     L.ffhip_debug_batch_device_bytes.restype = C.c_size_t
     L.ffhip_debug_batch_device_bytes.argtypes = [vp]
+    L.ffhip_batch_set_run_scale.argtypes = [vp, C.POINTER(C.c_double)]
+    L.ffhip_batch_rle_runs.argtypes = [vp, C.c_int, C.POINTER(CRleRuns)]
+    L.ffhip_op_rle_runs.argtypes = [vp, CFMat, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8),
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_ulonglong)]
     _LIB = L
     return L
 
@@ -407,6 +428,19 @@ class Batch:
         _check(lib().ffhip_batch_get_path(self.h, read, path.ctypes.data_as(C.POINTER(C.c_int)), _fptr(qpath)))
         return path, qpath
 
+    def set_run_scale(self, factors):
+        """the four run-length scale factors (A, C, G, T) of the batch's later runs (ffhip_batch_set_run_scale)"""
+        f = np.ascontiguousarray(factors, dtype=np.float64)
+        assert f.shape == (4,)
+        _check(lib().ffhip_batch_set_run_scale(self.h, f.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def rle_runs(self, read: int) -> dict:
+        """run records of a run with RUN_RLE_RUNS / RUN_RLE_RECORDS (ffhip_batch_rle_runs): base (0..3), est, failed, length, and shape / scale /
+        dwell (None unless the records came down)"""
+        r = CRleRuns()
+        _check(lib().ffhip_batch_rle_runs(self.h, read, C.byref(r)))
+        return _runs_dict(r.nrun, r.base, r.est, r.shape, r.scale, r.dwell, r.failed, r.length)
+
     def transitions(self, read: int) -> np.ndarray:
         out = np.zeros((self.read_nblock(read), self.P), dtype=np.float32)
         _check(lib().ffhip_batch_get_transitions(self.h, read, _fptr(out)))
@@ -496,6 +530,36 @@ class Batch:
         if self.h:
             lib().ffhip_batch_destroy(self.h)
             self.h = None
+
+
+def _runs_dict(n, base, est, shape, scale, dwell, failed, length) -> dict:
+    def arr(p, dt):
+        return None if not p else np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
+    return dict(base=arr(base, np.uint8), est=arr(est, np.int32), shape=arr(shape, np.float32), scale=arr(scale, np.float32),
+                dwell=arr(dwell, np.int32), failed=bool(failed), length=int(length))
+
+
+def rle_runs_op(engine: Engine, param: np.ndarray, path: np.ndarray, factors=None, records: bool = True) -> dict:
+    """ffhip_op_rle_runs: run records of ONE run-length matrix param [nblock][nparam] (the layout Batch.posterior returns) and its path (nblock
+    entries, states 0 .. 2 nbase - 1); factors None: the defaults"""
+    param = np.ascontiguousarray(param, dtype=np.float32)
+    nblock, nparam = param.shape
+    path = np.ascontiguousarray(path[:nblock], dtype=np.int32)
+    assert path.shape == (nblock,)
+    n = max(nblock, 1)
+    base, est = np.zeros(n, np.uint8), np.zeros(n, np.int32)
+    shape, scale, dwell = (np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)) if records else (None, None, None)
+    f = None if factors is None else np.ascontiguousarray(factors, dtype=np.float64)
+    nrun, failed, length = C.c_size_t(), C.c_int(), C.c_ulonglong()
+
+    def ptr(a, t):
+        return None if a is None else a.ctypes.data_as(C.POINTER(t))
+    _check(lib().ffhip_op_rle_runs(engine.h, CFMat(_fptr(param), nparam, nblock, nparam), ptr(path, C.c_int), ptr(f, C.c_double), C.byref(nrun),
+                                   ptr(base, C.c_uint8), ptr(est, C.c_int32), ptr(shape, C.c_float), ptr(scale, C.c_float), ptr(dwell, C.c_int32),
+                                   C.byref(failed), C.byref(length)))
+    k = nrun.value
+    return dict(base=base[:k].copy(), est=est[:k].copy(), shape=None if shape is None else shape[:k].copy(), scale=None if scale is None else scale[:k].copy(),
+                dwell=None if dwell is None else dwell[:k].copy(), failed=bool(failed.value), length=int(length.value))
 
 
 def basecall_reads(dmodel: DeviceModel, signals: np.ndarray, temperature: float = 1.0, flags: int = 0):

@@ -749,6 +749,12 @@ struct ffhip_batch {
     // what ffhip_batch_finish brings down is ONE block on the device and one pinned block on the host, [sat | abort | lens | score | bases | quals]: one copy
     // instead of six (round 5; a batch that was not decoded takes the first two parts only)
     unsigned char *res_dev = nullptr, *res_host = nullptr; size_t res_bytes = 0, res_head = 0;
+    // Run records of a run-length batch (FFHIP_RUN_RLE_RUNS / _RECORDS, k_rle_runs): a section behind [.. | quals] of the same block, added on the first run that asks
+    // for it -- [nrun | fail | len | base | est] (5 bytes a block), [shape | scale | dwell] (12 more) for the records; res_cap: what the block holds now
+    size_t res_cap = 0, res_runs_end = 0, res_rec_end = 0;
+    RleRunOut runs_dev{}, runs_host{};
+    RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
+    int runs_valid = 0;                 // the last run made run records: 1 base and est, 2 with shape / scale / dwell
     std::vector<void *> owned;
     unsigned last_flags = 0;
     float last_temperature = 1.0f;
@@ -774,6 +780,41 @@ struct ffhip_batch {
     int front_kept = 0, front_exp = -100000, front_f16 = -1;       // the last run kept it; the thin layer whose output was fp16 slices (-1: none)
     int forms[4] = { -1, -1, -1, -1 };  // kernel forms of the last run's convolution launches and its head launch (KernelForm)
 };
+
+// The result block's layout, in one place: [sat | abort | lens | score | bases | quals] (what every decoded run brings down), then the run section of a run-length
+// batch, [nrun | fail | len | base | est] and [shape | scale | dwell] (present once a run asked for it: ensure_run_block).  Offsets in bytes, each part 256-aligned.
+struct ResLayout { size_t sat, abort, lens, score, bases, quals, end, nrun, fail, len, base, est, runs_end, shape, scale, dwell, rec_end; };
+static ResLayout res_layout(const ffhip_batch *b) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t nres = (size_t)b->cap_reads, n1 = (size_t)b->nread * ((size_t)b->Tb + 1);
+    ResLayout o;
+    o.sat = 0; o.abort = up((size_t)b->Bp * 4); o.lens = o.abort + 256; o.score = o.lens + up(nres * 4);
+    o.bases = o.score + up(nres * 4); o.quals = o.bases + up(n1); o.end = o.quals + up(n1);
+    o.nrun = o.end; o.fail = o.nrun + up(nres * 4); o.len = o.fail + up(nres * 4); o.base = o.len + up(nres * 8); o.est = o.base + up(n1);
+    o.runs_end = o.est + up(n1 * 4);
+    o.shape = o.runs_end; o.scale = o.shape + up(n1 * 4); o.dwell = o.scale + up(n1 * 4); o.rec_end = o.dwell + up(n1 * 4);
+    return o;
+}
+// every pointer into the result block, device and pinned host side, from res_dev / res_host and the layout (the run section's when the block holds it; shape,
+// scale and dwell when it holds them and `records`)
+static void res_point(ffhip_batch *b, bool records) {
+    const ResLayout o = res_layout(b);
+    unsigned char *d = b->res_dev, *h = b->res_host;
+    b->sat = (unsigned *)(d + o.sat); b->pabort = (unsigned *)(d + o.abort); b->lens = (int *)(d + o.lens);
+    b->score = (float *)(d + o.score); b->bases = (char *)(d + o.bases); b->quals = (char *)(d + o.quals);
+    b->h_sat = (unsigned *)(h + o.sat); b->h_abort = (unsigned *)(h + o.abort); b->h_lens = (int *)(h + o.lens);
+    b->h_score = (float *)(h + o.score); b->h_bases = (char *)(h + o.bases); b->h_quals = (char *)(h + o.quals);
+    const bool runs = b->res_cap >= o.runs_end, rec = records && b->res_cap >= o.rec_end;
+    auto set = [&](unsigned char *base, RleRunOut &r) {
+        r = RleRunOut{};
+        if (!runs) return;
+        r.nrun = (int *)(base + o.nrun); r.fail = (int *)(base + o.fail); r.len = (unsigned long long *)(base + o.len);
+        r.base = base + o.base; r.est = (int *)(base + o.est);
+        if (rec) { r.shape = (float *)(base + o.shape); r.scale = (float *)(base + o.scale); r.dwell = (int *)(base + o.dwell); }
+    };
+    set(d, b->runs_dev);
+    set(h, b->runs_host);
+}
 
 static void *dalloc(ffhip_batch *b, size_t bytes, bool zero) {
     void *d = nullptr;
@@ -896,18 +937,15 @@ static ffhip_batch *batch_create_impl(ffhip_engine *eng, const ffhip_model *m, i
     if (!(b->path = (int *)dalloc(b, (size_t)nread * (Tb + 1) * 4, true))) BFAIL();
     if (!(b->qpath = (float *)dalloc(b, (size_t)nread * (Tb + 1) * 4, true))) BFAIL();
     {
-        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        const size_t o_sat = 0, o_abort = up((size_t)b->Bp * 4), o_lens = o_abort + 256, o_score = o_lens + up(nres * 4),
-                     o_bases = o_score + up(nres * 4), o_quals = o_bases + up((size_t)nread * (Tb + 1));
-        b->res_head = o_lens;
-        b->res_bytes = o_quals + up((size_t)nread * (Tb + 1));
+        const ResLayout o = res_layout(b);
+        b->res_head = o.lens;
+        b->res_bytes = o.end;
+        b->res_runs_end = o.runs_end; b->res_rec_end = o.rec_end;
+        b->res_cap = b->res_bytes;
         if (!(b->res_dev = (unsigned char *)dalloc(b, b->res_bytes, true))) BFAIL();
         if (hipHostMalloc((void **)&b->res_host, b->res_bytes) != hipSuccess) { set_err(FFHIP_ENOMEM, "pinned host allocation failed"); BFAIL(); }
         memset(b->res_host, 0, b->res_bytes);
-        b->sat = (unsigned *)(b->res_dev + o_sat); b->pabort = (unsigned *)(b->res_dev + o_abort); b->lens = (int *)(b->res_dev + o_lens);
-        b->score = (float *)(b->res_dev + o_score); b->bases = (char *)(b->res_dev + o_bases); b->quals = (char *)(b->res_dev + o_quals);
-        b->h_sat = (unsigned *)(b->res_host + o_sat); b->h_abort = (unsigned *)(b->res_host + o_abort); b->h_lens = (int *)(b->res_host + o_lens);
-        b->h_score = (float *)(b->res_host + o_score); b->h_bases = (char *)(b->res_host + o_bases); b->h_quals = (char *)(b->res_host + o_quals);
+        res_point(b, false);
     }
     if (!(b->trace = (int32_t *)dalloc(b, (size_t)nread * (Tb + 1) * ns * 4, true))) BFAIL();
     if (!(b->pflags = (unsigned *)dalloc(b, persist_flag_words((int)Hp, b->B16) * sizeof(unsigned), true))) BFAIL();
@@ -932,6 +970,38 @@ extern "C" ffhip_batch *ffhip_batch_create_packed(ffhip_engine *eng, const ffhip
     return batch_create_impl(eng, m, nslot, nsample, max_reads);
 }
 static inline int batch_nreads(const ffhip_batch *b) { return b->packed ? b->nvirt : b->nread; }
+
+// The result block's run section (ffhip_batch::res_runs_end): grown on the first run that asks for it, the block's contents kept (a packed batch's set-up writes
+// into it before the run); pointers into the block are set again.  Returns 0 or an FFHIP_E* code.
+static int ensure_run_block(ffhip_batch *b, bool records) {
+    const ResLayout o = res_layout(b);
+    const size_t need = records ? o.rec_end : o.runs_end;
+    if (b->res_cap < need) {
+        HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
+        unsigned char *d = nullptr, *h = nullptr;
+        if (hipMalloc((void **)&d, need) != hipSuccess) return set_err(FFHIP_ENOMEM, "hipMalloc of %zu bytes failed", need);
+        if (hipHostMalloc((void **)&h, need) != hipSuccess) { hipFree(d); return set_err(FFHIP_ENOMEM, "pinned host allocation failed"); }
+        memset(h + b->res_cap, 0, need - b->res_cap);
+        memcpy(h, b->res_host, b->res_cap);
+        if (hipMemsetAsync(d + b->res_cap, 0, need - b->res_cap, b->stream) != hipSuccess ||
+            hipMemcpyAsync(d, b->res_dev, b->res_cap, hipMemcpyDeviceToDevice, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess) {
+            hipFree(d); hipHostFree(h); return set_err(FFHIP_EHIP, "copy of the result block failed");
+        }
+        for (void *&p : b->owned) if (p == b->res_dev) { hipFree(p); p = d; }
+        hipHostFree(b->res_host);
+        b->dev_bytes += need - b->res_cap;
+        b->res_dev = d; b->res_host = h; b->res_cap = need;
+    }
+    res_point(b, records);
+    return FFHIP_OK;
+}
+// bytes of the result block a finished run brings down: [sat | abort] alone without a decode, the run section when the run made one
+static size_t res_copy_bytes(const ffhip_batch *b, unsigned flags) {
+    if (flags & FFHIP_RUN_NO_DECODE) return b->res_head;
+    if (flags & FFHIP_RUN_RLE_RECORDS) return b->res_rec_end;
+    if (flags & FFHIP_RUN_RLE_RUNS) return b->res_runs_end;
+    return b->res_bytes;
+}
 extern "C" int ffhip_batch_nreads(const ffhip_batch *b) { return b ? batch_nreads(b) : 0; }
 // first row of a read in the buffers of Tb / Tb + 1 rows a slot
 static inline size_t read_row0(const ffhip_batch *b, int read) { return b->packed ? (size_t)b->v_slot[read] * b->Tb + b->v_off[read] : (size_t)read * b->Tb; }
@@ -1436,6 +1506,12 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
     memset(b->launches, 0, sizeof(b->launches));
     b->run_path = plan_run(m, flags, temperature, ncu);
     const RunPath &p = b->run_path;
+    b->runs_valid = 0;
+    if (flags & (FFHIP_RUN_RLE_RUNS | FFHIP_RUN_RLE_RECORDS)) {
+        if (m->kind != FFHIP_NET_LSTM5_RLE || m->nbase != 4 || (flags & FFHIP_RUN_NO_DECODE))
+            return set_err(FFHIP_EINVAL, "run records: a decoded run of the run-length model (nbase 4) only");
+        if (int rc = ensure_run_block(b, (flags & FFHIP_RUN_RLE_RECORDS) != 0)) return rc;
+    }
     if (b->packed && !p.packable)
         return set_err(FFHIP_EINVAL, "packed batches take the default path and the launch-per-step kernels only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / unfused flags, ordinary temperature)");
     // A packed batch's launch-per-step run keeps its two fp32 activations in the memory of the two split buffers its default run has (the same size at two
@@ -1718,6 +1794,11 @@ static int run_back(ffhip_batch *b) {
             // decode_crf_runlength (decode.c:927-1013); the run records are formed from the path by the caller
             // (runnie.c:282-313), there are no base/quality strings or trace for this model
             launch_rle_viterbi(s, scores, b->tb, b->path, b->qpath, b->score, nR, Tb, m->nbase, m->Ps, tbr, rmap);
+            if (flags & (FFHIP_RUN_RLE_RUNS | FFHIP_RUN_RLE_RECORDS)) {      // run records from the path and the matrix the host loop reads (runnie.c:282-313)
+                launch_rle_runs(s, scores, b->path, nR, Tb, m->nbase, m->Ps, tbr, rmap, b->run_scale, b->runs_dev);
+                b->runs_valid = (flags & FFHIP_RUN_RLE_RECORDS) ? 2 : 1;
+                b->launches[5]++;
+            }
             HIP_TRY(hipMemsetAsync(b->lens, 0, (size_t)nR * 4, s), FFHIP_EHIP);
             HIP_TRY(hipMemsetAsync(b->bases, 0, (size_t)b->nread * (Tb + 1), s), FFHIP_EHIP);
             HIP_TRY(hipMemsetAsync(b->quals, 0, (size_t)b->nread * (Tb + 1), s), FFHIP_EHIP);
@@ -1740,7 +1821,7 @@ static int run_back(ffhip_batch *b) {
     // and in front of the events the next batch's layer launches wait for.
     b->res_copied = 0;
     if (b->packed) {
-        HIP_TRY(hipMemcpyAsync(b->res_host, b->res_dev, (flags & FFHIP_RUN_NO_DECODE) ? b->res_head : b->res_bytes, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+        HIP_TRY(hipMemcpyAsync(b->res_host, b->res_dev, res_copy_bytes(b, flags), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
         b->res_copied = 1;
     }
     HIP_TRY(hipEventRecord(eng->batch_done, s), FFHIP_EHIP); eng->batch_done_rec = 1;
@@ -1779,7 +1860,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
         const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
         b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
         b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-        b->ran = 1; b->finished = 0; b->paired_last = 0;
+        b->ran = 1; b->finished = 0; b->paired_last = 0; b->runs_valid = 0;
         return FFHIP_OK;
     }
     HIP_TRY(hipMemsetAsync(b->bases, 0, n * L, s), FFHIP_EHIP);
@@ -1795,7 +1876,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
     const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
     b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
     b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-    b->ran = 1; b->finished = 0; b->paired_last = 0;
+    b->ran = 1; b->finished = 0; b->paired_last = 0; b->runs_valid = 0;
     return FFHIP_OK;
 }
 
@@ -1883,6 +1964,7 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
             HIP_TRY(hipMemcpyAsync(sd->sbuf[0].p + (size_t)k * sd->sbuf[0].rs + kSamplePad, from, (size_t)lens[k] * 4, hipMemcpyDeviceToDevice, sd->stream), FFHIP_EHIP);
         }
         sd->ran = sd->finished = 0;
+        sd->run_scale = b->run_scale;
         if (int rc = ffhip_batch_run(sd, b->last_temperature, (fl & ~(unsigned)FFHIP_RUN_KEEP_ACTS) | FFHIP_RUN_F32_RNN)) return rc;
         if (int rc = ffhip_batch_finish(sd)) return rc;
         hipStream_t s = b->stream;
@@ -1900,6 +1982,20 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
             HIP_TRY(hipMemcpyAsync(b->lens + r, sd->lens + k, 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
             if (!(fl & FFHIP_RUN_NO_TRACE) && m->kind != FFHIP_NET_LSTM5_RLE)
                 HIP_TRY(hipMemcpyAsync(b->trace + r1 * ns, sd->trace + (size_t)k * L * ns, nb1 * ns * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+            if (b->runs_valid && sd->runs_valid) {      // the run records of the f32 run (its own copy came down in its result block)
+                const size_t k1 = (size_t)k * L;
+                const RleRunOut &dd = b->runs_dev, &sdd = sd->runs_dev, &hh = b->runs_host, &sh = sd->runs_host;
+                HIP_TRY(hipMemcpyAsync(dd.base + r1, sdd.base + k1, nb1, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                HIP_TRY(hipMemcpyAsync(dd.est + r1, sdd.est + k1, nb1 * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                memcpy(hh.base + r1, sh.base + k1, nb1); memcpy(hh.est + r1, sh.est + k1, nb1 * 4);
+                if (b->runs_valid == 2) {
+                    HIP_TRY(hipMemcpyAsync(dd.shape + r1, sdd.shape + k1, nb1 * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                    HIP_TRY(hipMemcpyAsync(dd.scale + r1, sdd.scale + k1, nb1 * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                    HIP_TRY(hipMemcpyAsync(dd.dwell + r1, sdd.dwell + k1, nb1 * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                    memcpy(hh.shape + r1, sh.shape + k1, nb1 * 4); memcpy(hh.scale + r1, sh.scale + k1, nb1 * 4); memcpy(hh.dwell + r1, sh.dwell + k1, nb1 * 4);
+                }
+                hh.nrun[r] = sh.nrun[k]; hh.fail[r] = sh.fail[k]; hh.len[r] = sh.len[k];
+            }
             memcpy(b->h_bases + r1, sd->h_bases + (size_t)k * L, nb1);
             memcpy(b->h_quals + r1, sd->h_quals + (size_t)k * L, nb1);
             b->h_lens[r] = sd->h_lens[k];
@@ -1924,7 +2020,7 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
         return FFHIP_OK;
     }
     // one copy: [sat | abort] and, when the batch was decoded, [lens | score | bases | quals] behind them (the block of ffhip_batch_create)
-    if (!b->res_copied) HIP_TRY(hipMemcpyAsync(b->res_host, b->res_dev, (b->last_flags & FFHIP_RUN_NO_DECODE) ? b->res_head : b->res_bytes, hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
+    if (!b->res_copied) HIP_TRY(hipMemcpyAsync(b->res_host, b->res_dev, res_copy_bytes(b, b->last_flags), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
     b->res_copied = 0;
     HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
     if (rehearsal_rate() > 0) {                              // (test hook above: the emulated GPU finishes this batch at rehearsal_done_at)
@@ -1980,6 +2076,29 @@ extern "C" const char *ffhip_batch_quality(const ffhip_batch *b, int read) {
 extern "C" float ffhip_batch_score(const ffhip_batch *b, int read) {
     if (!results_ok(b, read) || (b->last_flags & FFHIP_RUN_NO_DECODE)) return NAN;
     return b->h_score[read];
+}
+
+extern "C" int ffhip_batch_set_run_scale(ffhip_batch *b, const double factor[4]) {
+    if (!b || !factor) return set_err(FFHIP_EINVAL, "null argument");
+    for (int i = 0; i < 4; i++) if (!(factor[i] > 0.0) || !std::isfinite(factor[i])) return set_err(FFHIP_EINVAL, "run-length scale factors must be positive");
+    for (int i = 0; i < 4; i++) b->run_scale.f[i] = factor[i];
+    return FFHIP_OK;
+}
+extern "C" int ffhip_batch_rle_runs(const ffhip_batch *b, int read, ffhip_rle_runs *out) {
+    if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
+    if (b->mdl->kind != FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "run records: not a run-length model");
+    if (!b->runs_valid) return set_err(FFHIP_EINVAL, "run records were not made in this run (FFHIP_RUN_RLE_RUNS)");
+    const RleRunOut &h = b->runs_host;
+    const size_t r1 = read_row1(b, read);
+    out->nrun = (size_t)h.nrun[read];
+    out->length = h.len[read];
+    out->failed = h.fail[read];
+    out->base = h.base + r1;
+    out->est = h.est + r1;
+    out->shape = b->runs_valid == 2 ? h.shape + r1 : nullptr;
+    out->scale = b->runs_valid == 2 ? h.scale + r1 : nullptr;
+    out->dwell = b->runs_valid == 2 ? h.dwell + r1 : nullptr;
+    return FFHIP_OK;
 }
 
 static int d2h(ffhip_batch *b, void *dst, const void *src, size_t bytes) {

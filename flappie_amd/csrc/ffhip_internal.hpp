@@ -209,6 +209,12 @@ void launch_rle_partition(hipStream_t s, const float *param, double *logz, int n
 void launch_rle_transpost(hipStream_t s, const float *param, float *post, float *fwd, int nread, int Tb, int nbase, int Ps, const int *tbs = nullptr);
 void launch_rle_viterbi(hipStream_t s, const float *param, uint8_t *tb, int *path, float *qpath, float *score, int nread, int Tb, int nbase, int Ps, const int *tbs = nullptr,
                         ReadMap map = ReadMap());      // map: a packed batch's reads (nbase 4, stride 40)
+// run records + run-length estimates of a decoded run-length batch (k_rle_runs, nbase 4): per read nrun / fail / len (expanded length); per run, at the read's
+// row of the (Tb + 1)-entry buffers, base and est, and shape / scale / dwell when those pointers are not null
+struct RleRunScale { double f[4]; };
+struct RleRunOut { uint8_t *base; int *est; float *shape, *scale; int *dwell; int *nrun, *fail; unsigned long long *len; };
+void launch_rle_runs(hipStream_t s, const float *param, const int *path, int nread, int Tb, int nbase, int Ps, const int *tbs, ReadMap map,
+                     const RleRunScale &sc, const RleRunOut &o);
 // first-generation run-length decoders (decode.c:552-892) on one matrix of 4 nbase rows; tb: 8 bytes a block, fwd / bwd: 8 floats a block (+1)
 void launch_rl1_viterbi(hipStream_t s, const float *param, uint8_t *tb, int *path, float *score, int nblk, int nbase, int Ps);
 void launch_rl1_posterior(hipStream_t s, const float *param, float *post, float *fwd, float *bwd, int nblk, int nbase, int Ps);

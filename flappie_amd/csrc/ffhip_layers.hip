@@ -580,6 +580,44 @@ extern "C" int ffhip_runlength_viterbi(ffhip_engine *eng, ffhip_mat param, int *
     return FFHIP_OK;
 }
 
+// run records and run-length estimates of one matrix and its path (k_rle_runs; include/ffhip.h)
+extern "C" int ffhip_op_rle_runs(ffhip_engine *eng, ffhip_mat param, const int *path, const double *factor, size_t *nrun, uint8_t *base, int32_t *est,
+                                 float *shape, float *scale, int32_t *dwell, int *failed, unsigned long long *length) {
+    OP_ENTER(eng);
+    int nbase;
+    if (!view_ok(param) || !path || !nrun || !base || !est || !flipflop_dims(param.nr, param.stride, &nbase) || nbase != 4 || param.nc > (size_t)1 << 30)
+        return set_err(FFHIP_EINVAL, "bad run record arguments");
+    const size_t nblock = param.nc, L = nblock + 1;
+    for (size_t b = 0; b < nblock; b++) if (path[b] < 0 || path[b] >= 2 * nbase) return set_err(FFHIP_EINVAL, "run records: a path entry is not a state");
+    RleRunScale sc{ { 1.02, 1.04, 1.04, 1.02 } };
+    if (factor) for (int i = 0; i < 4; i++) sc.f[i] = factor[i];
+    const bool rec = shape || scale || dwell;
+    float *d_p = upload_img(tmp, param, s);
+    int *d_path = (int *)tmp.get(L * 4), *d_info = (int *)tmp.get(16);
+    RleRunOut o{};
+    o.base = (uint8_t *)tmp.get(L); o.est = (int *)tmp.get(L * 4);
+    if (rec) { o.shape = (float *)tmp.get(L * 4); o.scale = (float *)tmp.get(L * 4); o.dwell = (int *)tmp.get(L * 4); }
+    if (!d_p || !d_path || !d_info || !o.base || !o.est || (rec && (!o.shape || !o.scale || !o.dwell))) OP_NOMEM();
+    o.nrun = d_info; o.fail = d_info + 1; o.len = (unsigned long long *)(d_info + 2);
+    HIP_TRY(hipMemcpyAsync(d_path, path, nblock * 4, hipMemcpyHostToDevice, s), FFHIP_EHIP);
+    launch_rle_runs(s, d_p, d_path, 1, (int)nblock, nbase, (int)param.stride, nullptr, ReadMap(), sc, o);
+    int info[4];
+    HIP_TRY(hipMemcpyAsync(info, d_info, 16, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    const size_t n = (size_t)info[0];
+    if (n > nblock) return set_err(FFHIP_EHIP, "run records: %zu runs from %zu blocks", n, nblock);
+    HIP_TRY(hipMemcpyAsync(base, o.base, n, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipMemcpyAsync(est, o.est, n * 4, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    if (shape) HIP_TRY(hipMemcpyAsync(shape, o.shape, n * 4, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    if (scale) HIP_TRY(hipMemcpyAsync(scale, o.scale, n * 4, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    if (dwell) HIP_TRY(hipMemcpyAsync(dwell, o.dwell, n * 4, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    *nrun = n;
+    if (failed) *failed = info[1];
+    if (length) { unsigned long long len; memcpy(&len, info + 2, 8); *length = len; }
+    return FFHIP_OK;
+}
+
 // ---- decoders of the first run-length head (decode.c:552-892): param is [4 nbase x nblock]
 static bool rl1_dims(const ffhip_mat &param, int *nbase) {
     if (!view_ok(param) || param.nr % 4 != 0 || param.nr / 4 < 1 || param.nr / 4 > 8) return false;

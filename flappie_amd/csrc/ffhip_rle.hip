@@ -608,7 +608,70 @@ k_rl1_mean(const float *__restrict__ param, const int *__restrict__ path, int *_
     if ((threadIdx.x & 63) == 0 && tot) atomicAdd(seqlen, tot);
 }
 
+// Run records of runnie.c:282-313 and decode_runnie.py's run-length estimate, one wave per read (as k_assemble): a run starts at every block p with
+// path[p] < nbase; its base is path[p], its shape / scale rows base and nbase + base of block p, its dwell the next run's start - p (the last run's:
+// Tb - p).  The estimate is the script's run_estimate_modes on the PRINTED scale: %f rounds to six decimals half-to-even (rint of scale * 1e6, exact
+// in double: 24 + 14 significant bits), Python's float() of that text is k / 1e6 correctly rounded, then max(1, floor(s6 * factor[base])).  A read
+// with a non-finite scale or an estimate >= 2^31 is flagged failed (the script's integer cast is undefined there).  Runs are compacted by ballot
+// into the read's row of the (Tb + 1)-entry buffers; shape / scale / dwell only when their pointers are given.
+__global__ void __launch_bounds__(64)
+k_rle_runs(const float *__restrict__ param, const int *__restrict__ path, int TbS, int nbase, int Ps, const int *__restrict__ tbs, ReadMap map,
+           RleRunScale sc, RleRunOut o) {
+    const int lane = threadIdx.x, r = blockIdx.x;
+    const int Tb = tbs ? tbs[r] : TbS;
+    if (Tb <= 0) {                                       // an empty slot: no runs
+        if (lane == 0) { o.nrun[r] = 0; o.fail[r] = 0; o.len[r] = 0; }
+        return;
+    }
+    const size_t r1 = map.row1(r, TbS);
+    const int *pth = path + r1;
+    const float *M = param + map.row0(r, TbS) * (size_t)Ps;
+    int count = 0, pend = -1;                            // runs so far; start of the last one (its dwell is written when the next one is found)
+    unsigned long long sum = 0;
+    bool bad = false;
+    for (int p0 = 0; p0 < Tb; p0 += 64) {
+        const int p = p0 + lane;
+        const int st = (p < Tb) ? pth[p] : nbase;
+        const bool start = (unsigned)st < (unsigned)nbase;
+        const unsigned long long mask = __ballot(start);
+        if (start) {
+            const int idx = count + __popcll(mask & ((1ull << lane) - 1ull));
+            const float shape = M[(size_t)p * Ps + st], scale = M[(size_t)p * Ps + nbase + st];
+            const double s6 = rint((double)scale * 1e6) / 1e6;
+            const double f = (st == 0) ? sc.f[0] : (st == 1) ? sc.f[1] : (st == 2) ? sc.f[2] : sc.f[3];      // (nbase 4: launch_rle_runs' callers check)
+            const double e = floor(s6 * f);
+            int est = 0;
+            if (!isfinite(scale) || !(e < 2147483648.0)) bad = true;
+            else est = (e < 1.0) ? 1 : (int)e;
+            sum += (unsigned long long)est;
+            o.base[r1 + idx] = (uint8_t)st;
+            o.est[r1 + idx] = est;
+            if (o.shape) { o.shape[r1 + idx] = shape; o.scale[r1 + idx] = scale; }
+            if (o.dwell) {
+                const unsigned long long above = mask & ~((2ull << lane) - 1ull);     // (lane 63: 2ull << 63 == 0, nothing above)
+                if (above) o.dwell[r1 + idx] = p0 + __ffsll((long long)above) - 1 - p;
+            }
+        }
+        if (mask) {
+            if (o.dwell && pend >= 0 && lane == 0) o.dwell[r1 + count - 1] = p0 + __ffsll((long long)mask) - 1 - pend;
+            pend = p0 + 63 - __clzll((long long)mask);
+        }
+        count += __popcll(mask);
+    }
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+    const bool failed = __ballot(bad) != 0ull;
+    if (lane == 0) {
+        if (o.dwell && pend >= 0) o.dwell[r1 + count - 1] = Tb - pend;
+        o.nrun[r] = count; o.fail[r] = failed ? 1 : 0; o.len[r] = sum;
+    }
+}
+
 }  // namespace
+
+void launch_rle_runs(hipStream_t s, const float *param, const int *path, int nread, int Tb, int nbase, int Ps, const int *tbs, ReadMap map,
+                     const RleRunScale &sc, const RleRunOut &o) {
+    if (nread > 0) hipLaunchKernelGGL(k_rle_runs, dim3(nread), dim3(64), 0, s, param, path, Tb, nbase, Ps, tbs, map, sc, o);
+}
 
 // the activation goes row-wise over the nrow rows (elementwise: a packed batch's gap blocks are computed and never read), the partition function and the subtraction per read
 void launch_rle_head_finish(hipStream_t s, float *param, double *logz, int nrow, int Tb, int nbase, int Ps, float temperature, const int *tbs,

@@ -73,6 +73,11 @@ static struct argp_option options[] = {
     {"shard", 18, "g/n", 0, "Call only files g, g+n, g+2n, ... of the sorted input list (one process per GPU: tools/flappie_multi_gpu.sh)"},
     {"readers", 17, "n", 0, "fast5 reader processes feeding the GPU (default 4: one keeps up with ~50 Msamples/s of files that need libhdf5 and > 200 of those host/fast5_raw.c reads; more only cost CPU; 0 reads in this process)"},
     {"shard-by-size", 19, 0, 0, "With --shard: deal the files to the n shards by size (largest first, each to the lightest shard) instead of by index"},
+#ifdef BUILD_RUNNIE
+    {"fasta", 20, 0, 0, "Write FASTA basecalls instead of run records: what the run records through misc/decode_runnie.py give, with runs and run lengths made on the GPU"},
+    {"rlc", 21, 0, 0, "With --fasta: the run-length compressed sequence (one base a run, as decode_runnie.py --rlc)"},
+    {"run-scale", 22, "A,C,G,T", 0, "With --fasta: per-base factors of the scale parameter (default 1.02,1.04,1.04,1.02, as decode_runnie.py --scale)"},
+#endif
     {0}
 };
 
@@ -104,7 +109,10 @@ static struct {
     int readers;
     int shard, nshard;
     bool shard_by_size;
-} args = { 1, 200, 0.0f, NULL, FLAPPIE_OUTFORMAT_FASTQ, 0, DEFAULT_MODEL, NULL, "", false, 1.0f, 200, 10, 100, 0.0f, false, NULL, true, 0, 4, 0, 0 };      /* batch 0: by model (below); nshard 0: --shard not given */
+    bool fasta, rlc, run_scale_set;     /* runnie: --fasta, --rlc, --run-scale given */
+    double run_scale[4];
+} args = { 1, 200, 0.0f, NULL, FLAPPIE_OUTFORMAT_FASTQ, 0, DEFAULT_MODEL, NULL, "", false, 1.0f, 200, 10, 100, 0.0f, false, NULL, true, 0, 4, 0, 0, false, false, false, false,
+           { 1.02, 1.04, 1.04, 1.02 } };      /* batch 0: by model (below); nshard 0: --shard not given */
 
 static void print_models(FILE *fh) {
     for (int mdl = 0; mdl < (int)flappie_nmodel; mdl++)
@@ -195,6 +203,22 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
             errx(EXIT_FAILURE, "--shard takes g/n with 0 <= g < n");
         break;
     case 19: args.shard_by_size = true; break;
+#ifdef BUILD_RUNNIE
+    case 20: args.fasta = true; break;
+    case 21: args.rlc = true; break;
+    case 22: {
+        char *p = arg;
+        for (int k = 0; k < 4; k++) {
+            char *end;
+            args.run_scale[k] = strtod(p, &end);
+            if (end == p || !(args.run_scale[k] > 0.0) || !isfinite(args.run_scale[k]) || *end != (k < 3 ? ',' : 0))
+                errx(EXIT_FAILURE, "--run-scale takes four positive factors A,C,G,T");
+            p = end + 1;
+        }
+        args.run_scale_set = true;
+        break;
+    }
+#endif
     case ARGP_KEY_NO_ARGS: argp_usage(state); break;
     case ARGP_KEY_ARG:
         args.files = &state->argv[state->next - 1];
@@ -328,7 +352,8 @@ typedef struct {
     char *filename;                     /* owned */
     struct _raw_basecall_info res;      /* rt filled by read_raw, start/end by the preparation; basecall == NULL until called */
     int prepared;                       /* index into the chunk's ffhip_prep, or -1 */
-    char *rle_text;                     /* runnie: the read's records, formatted (runnie.c:282-313) */
+    char *rle_text;                     /* runnie: the read's records, formatted (runnie.c:282-313); --fasta: its sequence, wrapped */
+    int rle_nocall;                     /* runnie --fasta: no runs, or a failed run-length estimate (decode_runnie.py: "No basecall returned") */
 } item;
 
 /* Batch objects own gigabytes of workspace; creating one per group costs more than running it.  Full-size groups
@@ -388,7 +413,17 @@ static size_t pack_row_cap(size_t want) {
  * later (flappie.c:264-316 after normalisation) -- so the host side of the next group overlaps the GPU side of this one. */
 struct chunk_ctx;
 typedef struct { ffhip_batch *b; int cached, n, *idx; item **its; const ffhip_prep *prep; struct chunk_ctx *owner; int packed; } pending_batch;
+#ifdef BUILD_RUNNIE
+/* --fasta: the runs and their run-length estimates come from the device (FFHIP_RUN_RLE_RUNS) with the batch's scale factors */
+static unsigned run_flags(void) { return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.fasta ? FFHIP_RUN_RLE_RUNS : 0u); }
+static int batch_run(ffhip_batch *b, unsigned flags) {
+    if (args.fasta) { const int rc = ffhip_batch_set_run_scale(b, args.run_scale); if (rc) return rc; }
+    return ffhip_batch_run(b, args.temperature, flags);
+}
+#else
 static unsigned run_flags(void) { return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE); }
+static int batch_run(ffhip_batch *b, unsigned flags) { return ffhip_batch_run(b, args.temperature, flags); }
+#endif
 
 /* n reads in the rows of one packed batch: slot_of / off_of from ffhip_pack_plan, `cap` the row capacity it was made for */
 static pending_batch submit_packed(struct ffhip_engine *eng, const struct ffhip_model *mdl, const ffhip_prep *prep, item **its, int n, const int *slot_of, const int *off_of,
@@ -430,7 +465,7 @@ static pending_batch submit_packed(struct ffhip_engine *eng, const struct ffhip_
     int rc_sub = (NULL == pb.b) ? -1 : ffhip_batch_set_prepared_packed(pb.b, prep, n, pb.idx, slot_of, off_of);
     t_phase[6] += now_s() - t0;
     const double t1 = now_s();
-    if (0 == rc_sub) rc_sub = ffhip_batch_run(pb.b, args.temperature, flags);
+    if (0 == rc_sub) rc_sub = batch_run(pb.b, flags);
     t_phase[7] += now_s() - t1;
     if (0 != rc_sub) { warnx("%s", ffhip_last_error()); pb.b = NULL; }
     t_phase[3] += now_s() - t0;
@@ -464,7 +499,7 @@ static pending_batch submit_batch(struct ffhip_engine *eng, const struct ffhip_m
     int rc_sub = (NULL == pb.b) ? -1 : ffhip_batch_set_prepared(pb.b, prep, pb.idx);
     t_phase[6] += now_s() - t0;
     const double t1 = now_s();
-    if (0 == rc_sub) rc_sub = ffhip_batch_run(pb.b, args.temperature, flags);
+    if (0 == rc_sub) rc_sub = batch_run(pb.b, flags);
     t_phase[7] += now_s() - t1;
     if (0 != rc_sub) {
         warnx("%s", ffhip_last_error());
@@ -494,7 +529,7 @@ static void call_one_read_a_row(const struct ffhip_model *mdl, const pending_bat
             for (int k = 0; k < g; k++) one.idx[k] = its[i + k]->prepared;
             one.b = ffhip_batch_create(flappie_hip_engine(), mdl, g, longest);
             int rc = (NULL == one.b) ? -1 : ffhip_batch_set_prepared(one.b, failed->prep, one.idx);
-            if (0 == rc) rc = ffhip_batch_run(one.b, args.temperature, run_flags());
+            if (0 == rc) rc = batch_run(one.b, run_flags());
             if (0 != rc) { warnx("%s", ffhip_last_error()); if (one.b) ffhip_batch_destroy(one.b); one.b = NULL; }
         }
         collect_batch(mdl, &one);                      /* (a failure there counts the group's reads as not called) */
@@ -520,7 +555,48 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
     const size_t nblock_cap = ffhip_batch_nblock(b), nstate = 2 * ffhip_model_nbase(mdl);
     (void)nblock_cap; (void)nstate;
 #ifdef BUILD_RUNNIE
-    {   /* runnie.c:262-313: path from decode_crf_runlength, then one line per emitted base with the discrete-Weibull
+    if (args.fasta) {   /* the reads' runs and run-length estimates came down with the batch (k_rle_runs); each run's base expanded `est` times, 60 a line */
+        for (int i = 0; i < n; i++) {
+            ffhip_rle_runs rr;
+            if (0 != ffhip_batch_rle_runs(b, i, &rr)) { warnx("%s", ffhip_last_error()); continue; }
+            char *text = NULL;
+            if (args.rlc || (rr.nrun > 0 && !rr.failed)) {
+                const size_t len = args.rlc ? rr.nrun : (size_t)rr.length;
+                char *seq = malloc(len + 1);
+                text = malloc(len + len / 60 + 2);
+                if (NULL == seq || NULL == text) { free(seq); free(text); warnx("out of memory for a sequence of %zu bases", len); continue; }
+                size_t o = 0;
+                for (size_t k = 0; k < rr.nrun; k++) {
+                    const size_t cnt = args.rlc ? 1 : (size_t)rr.est[k];
+                    memset(seq + o, basechar(rr.base[k]), cnt);
+                    o += cnt;
+                }
+                size_t t = 0;
+                for (size_t st = 0; st < len; st += 60) {
+                    const size_t w = (len - st < 60) ? len - st : 60;
+                    if (st) text[t++] = '\n';
+                    memcpy(text + t, seq + st, w);
+                    t += w;
+                }
+                text[t++] = '\n';
+                text[t] = 0;
+                free(seq);
+            }
+            its[i]->rle_text = text;
+            its[i]->rle_nocall = (NULL == text);
+            n_called_reads++;
+            n_called_samples += its[i]->res.rt.end - its[i]->res.rt.start;
+            n_raw_samples += its[i]->res.rt.n;
+            its[i]->res.score = ffhip_batch_score(b, i);
+            its[i]->res.nblock = ffhip_batch_read_nblock(b, i);
+        }
+        t_phase[4] += now_s() - t0; t0 = now_s();
+        if (!cached) ffhip_batch_destroy(b);
+        t_phase[2] += now_s() - t0;
+        free(pb->idx); free(pb->its);
+        pb->b = NULL;
+        return;
+    } else {   /* runnie.c:262-313: path from decode_crf_runlength, then one line per emitted base with the discrete-Weibull
          * shape and scale of the block that emitted it and the dwell in blocks */
         const size_t nbase = ffhip_model_nbase(mdl), P = ffhip_model_nparam(mdl);
         int *path = malloc((nblock_cap + 1) * sizeof(int));
@@ -706,13 +782,20 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
     for (int i = 0; i < c->n; i++) {
         item *it = &c->items[i];
 #ifdef BUILD_RUNNIE
-        if (NULL != it->rle_text) {
+        if (args.fasta && it->rle_nocall) {
+            fprintf(stderr, "No basecall returned for %s\n", it->res.rt.uuid ? it->res.rt.uuid : "");      /* (decode_runnie.py's words, its read name) */
+        } else if (NULL != it->rle_text && args.fasta) {
+            fprintf(args.output, ">%s\n%s", it->res.rt.uuid ? it->res.rt.uuid : "", it->rle_text);
+            free(it->rle_text);
+            it->rle_text = NULL;
+        } else if (NULL != it->rle_text) {
             fprintf(args.output, "# %s\n%s", it->res.rt.uuid ? it->res.rt.uuid : "", it->rle_text);      /* runnie.c:280 */
             free(it->rle_text);
             it->rle_text = NULL;
         } else {
             warnx("No basecall returned for %s", it->filename);
         }
+        it->rle_nocall = 0;
         free_raw_basecall_info(&it->res);
         free(it->filename);
         continue;
@@ -1326,6 +1409,9 @@ static void segv_trace(int sig) {
 int main(int argc, char *argv[]) {
     t_program_start = now_s();
     argp_parse(&argp, argc, argv, 0, 0, NULL);
+#ifdef BUILD_RUNNIE
+    if ((args.rlc || args.run_scale_set) && !args.fasta) errx(EXIT_FAILURE, "--rlc and --run-scale go with --fasta");
+#endif
     if (cli_dbg("segv_trace")) { signal(SIGSEGV, segv_trace); signal(SIGABRT, segv_trace); signal(SIGBUS, segv_trace); }
     if (NULL == args.output) args.output = stdout;
     const double t_start = now_s();

@@ -83,6 +83,10 @@ typedef struct {
 #define FFHIP_RUN_FAST_GATES2  256u   /* the same with the exponent of v_exp_f32 carried in two words and a Newton step behind v_rcp_f32: exp and the
                                        * reciprocal to ~1 ulp at every argument (the reference's cephes replay is no closer to the true functions); the default */
 #define FFHIP_RUN_EXACT_GATES  512u   /* the reference's exp_ps polynomial and its division replayed bit for bit (the default of rounds 1-5) */
+/* run records of the run-length model (FFHIP_NET_LSTM5_RLE, nbase 4; ffhip_batch_rle_runs below): made on the device behind the Viterbi and brought down in
+ * ffhip_batch_finish's one copy of the result block */
+#define FFHIP_RUN_RLE_RUNS    1024u   /* every run's base and run-length estimate, and per read the run count, expanded length and failure flag */
+#define FFHIP_RUN_RLE_RECORDS 2048u   /* ... and every run's shape, scale and dwell as well (the whole .run record; 12 more bytes a block) */
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -310,6 +314,29 @@ int ffhip_op_runlength_partition_function(ffhip_engine *eng, ffhip_mat S, double
 int ffhip_op_globalnorm_runlength_v1(ffhip_engine *eng, ffhip_mat X, ffhip_mat W, ffhip_mat b, float temperature, ffhip_mat C);
 int ffhip_op_runlength_partition_function_v1(ffhip_engine *eng, ffhip_mat S, double *logZ);
 int ffhip_runlength_transpost(ffhip_engine *eng, ffhip_mat param, ffhip_mat post);
+/* Run records (runnie.c:282-313) and run-length estimates (decode_runnie.py's run_estimate_modes), made on the device by k_rle_runs:
+ *   a run starts at every block p with path[p] < nbase: base = path[p]; shape, scale = rows base, nbase + base of block p of the posterior (under --viterbi
+ *   the transitions, the matrix runnie's .run writer reads); dwell = the next run's start - p, the last run's nblock - p; blocks before the first run count
+ *   for nothing.  est = max(1, floor(s6 * factor[base])) in double, s6 = rint(scale * 1e6) / 1e6: the value Python reads back from the %f text of the scale.
+ *   A read with a non-finite scale or an estimate >= 2^31 is `failed` (its estimates are not meaningful).  factor defaults to A, C, G, T = 1.02, 1.04, 1.04, 1.02.
+ * ffhip_batch_set_run_scale: the four factors of a batch's later runs (a batch never set uses the defaults).
+ * ffhip_batch_rle_runs: after ffhip_batch_finish of a run with FFHIP_RUN_RLE_RUNS (or _RECORDS); the arrays hold nrun entries, bases as 0 .. 3, and stay owned
+ *   by the batch; shape / scale / dwell are NULL unless the run had FFHIP_RUN_RLE_RECORDS.  A flip-flop model's batch, or a run without the flag: FFHIP_EINVAL.
+ * ffhip_op_rle_runs: the same on one [nparam x nblock] matrix (nbase 4) and its path (nblock entries, each 0 .. 2 nbase - 1); factor NULL: the defaults; the
+ *   outputs are caller-owned arrays of nblock entries (shape, scale, dwell may be NULL). */
+typedef struct {
+    size_t nrun;                      /* runs of the read */
+    unsigned long long length;        /* sum of est: the length of the expanded sequence */
+    int failed;                       /* 1: a scale was not finite or an estimate reached 2^31 */
+    const uint8_t *base;
+    const int32_t *est;
+    const float *shape, *scale;
+    const int32_t *dwell;
+} ffhip_rle_runs;
+int ffhip_batch_set_run_scale(ffhip_batch *b, const double factor[4]);
+int ffhip_batch_rle_runs(const ffhip_batch *b, int read, ffhip_rle_runs *out);
+int ffhip_op_rle_runs(ffhip_engine *eng, ffhip_mat param, const int *path, const double *factor, size_t *nrun, uint8_t *base, int32_t *est,
+                      float *shape, float *scale, int32_t *dwell, int *failed, unsigned long long *length);
 int ffhip_runlength_viterbi(ffhip_engine *eng, ffhip_mat param, int *path /* nblock */, float *score);
 /* decoders of the first-generation head on [4 nbase x nblock] matrices: decode_runlength (decode.c:694-767), posterior_runlength
  * (decode.c:793-892; post is [4 nbase x nblock + 1]), runlengths_mean (decode.c:576-603) */

@@ -10,8 +10,8 @@ each through `flappie --readers R` at --limit N/2 and N; the rate is MARGINAL (l
 packed run -- up to 90 GB each at 384 hidden units -- are allocated once, in the first chunks), the
 padding efficiency is the binary's own account (FLAPPIE_CLI_TIMING: samples / (slots x longest read) by batch and by 16-read tile).
 --runnie: the same two directories through `runnie` with a synthetic run-length model (runlength5_r941native.h), each twice: packed batches and one read a row
-(FLAPPIE_DEBUG=no_pack).
-Run on the GPU box.   usage: tools/length_mix.py [--runnie] [hidden=384] [nfiles=65536] [readers=4] [env NAME=VALUE ...: extra environment for the mixed runs]"""
+(FLAPPIE_DEBUG=no_pack).  --runnie --fasta: packed batches twice, the .run records and `runnie --fasta` (run records and estimates made on the device).
+Run on the GPU box.   usage: tools/length_mix.py [--runnie [--fasta]] [hidden=384] [nfiles=65536] [readers=4] [env NAME=VALUE ...: extra environment for the mixed runs]"""
 import os
 import shutil
 import subprocess
@@ -24,7 +24,10 @@ sys.path.insert(0, ROOT)
 from flappie_amd import model as M  # noqa: E402
 
 runnie = "--runnie" in sys.argv[1:]
-argv = [a for a in sys.argv if a != "--runnie"]
+fasta = "--fasta" in sys.argv[1:]
+if fasta and not runnie:
+    raise SystemExit("--fasta is a leg of --runnie (the run-length model's FASTA mode); flappie has no such option")
+argv = [a for a in sys.argv if a not in ("--runnie", "--fasta")]
 hidden = int(argv[1]) if len(argv) > 1 else 384
 nfiles = int(argv[2]) if len(argv) > 2 else 65536
 readers = argv[3] if len(argv) > 3 else "4"
@@ -34,6 +37,8 @@ d = tempfile.mkdtemp(prefix="ffhip_lenmix_", dir=base)
 exe, tool = os.path.join(ROOT, "flappie_amd", "runnie" if runnie else "flappie"), os.path.join(ROOT, "flappie_amd", "fast5_tool")
 # runs: (label, environment) -- runnie: packed batches, then one read a row
 modes = [("packed", {}), ("no_pack", {"FLAPPIE_DEBUG": "no_pack"})] if runnie else [("", {})]
+if fasta:
+    modes = [("packed", {}), ("packed --fasta", {})]
 try:
     if runnie:
         M.write_mdl(os.path.join(d, "runlength5_r941native.h"), M.synthetic_model(M.NET_LSTM5_RLE, hidden, seed=1, ident="r941native"))
@@ -57,11 +62,12 @@ try:
         res = {}
         # (a first short run is thrown away: what the allocation of the 2 x 100 GB packed batch objects costs depends on what the box's memory has been through -- 0 .. 5 s,
         # the first process to touch it pays most --; the timed runs then all start from the same state)
-        subprocess.run([exe, "--readers", readers, "--limit", str(n // 2), "-o", os.path.join(d, "out.fq"), os.path.join(d, name)], env=env, capture_output=True, text=True)
+        opts = ["--fasta"] if mode.endswith("--fasta") else []
+        subprocess.run([exe] + opts + ["--readers", readers, "--limit", str(n // 2), "-o", os.path.join(d, "out.fq"), os.path.join(d, name)], env=env, capture_output=True, text=True)
         for rep in range(2):
             for lim in (n // 2, n):
                 t0 = time.perf_counter()
-                r = subprocess.run([exe, "--readers", readers, "--limit", str(lim), "-o", os.path.join(d, "out.fq"), os.path.join(d, name)], env=env, capture_output=True, text=True)
+                r = subprocess.run([exe] + opts + ["--readers", readers, "--limit", str(lim), "-o", os.path.join(d, "out.fq"), os.path.join(d, name)], env=env, capture_output=True, text=True)
                 dt = time.perf_counter() - t0
                 called = [ln for ln in r.stderr.splitlines() if ln.startswith("basecalled:")]
                 pad = [ln for ln in r.stderr.splitlines() if ln.startswith("batches:")]
