@@ -29,6 +29,7 @@ RUN_EXACT_GATES = 512
 RUN_RLE_RUNS = 1024       # run-length model: run bases + run-length estimates made on the device (Batch.rle_runs)
 RUN_RLE_RECORDS = 2048    # ... and every run's shape, scale and dwell
 RLE_SCALE_DEFAULT = (1.02, 1.04, 1.04, 1.02)      # decode_runnie.py's default --scale (A, C, G, T)
+RUN_MOD_PROBS = 4096      # 5-base model: 5mC probabilities (SAM ML bytes) of the called bases made on the device (Batch.mod_probs)
 # ffhip_debug_gate_math forms (include/ffhip.h)
 GATE_FORMS = ("logistic_ref", "tanh_ref", "logistic_ref4_lean", "logistic_ref2_lean", "logistic_ref_lean", "tanh_ref_lean",
               "swish_act4", "tanh_act4", "logistic_hw1", "tanh_hw1", "logistic_hw2", "tanh_hw2")
@@ -172,6 +173,8 @@ def lib():
     L.ffhip_op_rle_runs.argtypes = [vp, CFMat, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8),
                                     C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int),
                                     C.POINTER(C.c_ulonglong)]
+    L.ffhip_batch_mod_probs.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
+    L.ffhip_op_mod_probs.argtypes = [vp, CFMat, C.POINTER(C.c_int), C.POINTER(C.c_uint8), C.POINTER(C.c_size_t)]
     _LIB = L
     return L
 
@@ -441,6 +444,12 @@ class Batch:
         _check(lib().ffhip_batch_rle_runs(self.h, read, C.byref(r)))
         return _runs_dict(r.nrun, r.base, r.est, r.shape, r.scale, r.dwell, r.failed, r.length)
 
+    def mod_probs(self, read: int) -> np.ndarray:
+        """5mC probabilities of a run with RUN_MOD_PROBS (ffhip_batch_mod_probs): one uint8 a called base, aligned with basecall(read); 0 for A, G, T"""
+        p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+        _check(lib().ffhip_batch_mod_probs(self.h, read, C.byref(p), C.byref(n)))
+        return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint8)
+
     def transitions(self, read: int) -> np.ndarray:
         out = np.zeros((self.read_nblock(read), self.P), dtype=np.float32)
         _check(lib().ffhip_batch_get_transitions(self.h, read, _fptr(out)))
@@ -560,6 +569,19 @@ def rle_runs_op(engine: Engine, param: np.ndarray, path: np.ndarray, factors=Non
     k = nrun.value
     return dict(base=base[:k].copy(), est=est[:k].copy(), shape=None if shape is None else shape[:k].copy(), scale=None if scale is None else scale[:k].copy(),
                 dwell=None if dwell is None else dwell[:k].copy(), failed=bool(failed.value), length=int(length.value))
+
+
+def mod_probs_op(engine: Engine, logpost: np.ndarray, path: np.ndarray) -> np.ndarray:
+    """ffhip_op_mod_probs: 5mC probabilities of ONE log posterior [nblock][60] (the layout Batch.posterior returns) and its path (the first nblock entries
+    are used, states 0 .. 9): one uint8 a called base"""
+    logpost = np.ascontiguousarray(logpost, dtype=np.float32)
+    nblock, nparam = logpost.shape
+    path = np.ascontiguousarray(path[:nblock], dtype=np.int32)
+    assert path.shape == (nblock,)
+    ml, n = np.zeros(max(nblock, 1), np.uint8), C.c_size_t()
+    _check(lib().ffhip_op_mod_probs(engine.h, CFMat(_fptr(logpost), nparam, nblock, nparam), path.ctypes.data_as(C.POINTER(C.c_int)),
+                                    ml.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(n)))
+    return ml[:n.value].copy()
 
 
 def basecall_reads(dmodel: DeviceModel, signals: np.ndarray, temperature: float = 1.0, flags: int = 0):

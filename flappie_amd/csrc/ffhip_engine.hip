@@ -755,6 +755,12 @@ struct ffhip_batch {
     RleRunOut runs_dev{}, runs_host{};
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
     int runs_valid = 0;                 // the last run made run records: 1 base and est, 2 with shape / scale / dwell
+    // 5mC probabilities of a 5-base flip-flop batch (FFHIP_RUN_MOD_PROBS, k_mod_probs): one byte a called base, a section behind [.. | quals] of the same block
+    // (where a run-length batch has its run section), added on the first run that asks for it
+    size_t res_ml_end = 0;
+    uint8_t *ml_dev = nullptr, *ml_host = nullptr;
+    bool mod_block = false;             // the block holds the section
+    int mod_valid = 0;                  // the last run made them
     std::vector<void *> owned;
     unsigned last_flags = 0;
     float last_temperature = 1.0f;
@@ -782,8 +788,9 @@ struct ffhip_batch {
 };
 
 // The result block's layout, in one place: [sat | abort | lens | score | bases | quals] (what every decoded run brings down), then the run section of a run-length
-// batch, [nrun | fail | len | base | est] and [shape | scale | dwell] (present once a run asked for it: ensure_run_block).  Offsets in bytes, each part 256-aligned.
-struct ResLayout { size_t sat, abort, lens, score, bases, quals, end, nrun, fail, len, base, est, runs_end, shape, scale, dwell, rec_end; };
+// batch, [nrun | fail | len | base | est] and [shape | scale | dwell] (present once a run asked for it: ensure_run_block), or in the same place the [ml] section of
+// a 5-base flip-flop batch (ensure_mod_block; a batch has one model, so never both).  Offsets in bytes, each part 256-aligned.
+struct ResLayout { size_t sat, abort, lens, score, bases, quals, end, nrun, fail, len, base, est, runs_end, shape, scale, dwell, rec_end, ml, ml_end; };
 static ResLayout res_layout(const ffhip_batch *b) {
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t nres = (size_t)b->cap_reads, n1 = (size_t)b->nread * ((size_t)b->Tb + 1);
@@ -793,6 +800,7 @@ static ResLayout res_layout(const ffhip_batch *b) {
     o.nrun = o.end; o.fail = o.nrun + up(nres * 4); o.len = o.fail + up(nres * 4); o.base = o.len + up(nres * 8); o.est = o.base + up(n1);
     o.runs_end = o.est + up(n1 * 4);
     o.shape = o.runs_end; o.scale = o.shape + up(n1 * 4); o.dwell = o.scale + up(n1 * 4); o.rec_end = o.dwell + up(n1 * 4);
+    o.ml = o.end; o.ml_end = o.ml + up(n1);
     return o;
 }
 // every pointer into the result block, device and pinned host side, from res_dev / res_host and the layout (the run section's when the block holds it; shape,
@@ -814,6 +822,9 @@ static void res_point(ffhip_batch *b, bool records) {
     };
     set(d, b->runs_dev);
     set(h, b->runs_host);
+    const bool mod = b->mod_block && b->res_cap >= o.ml_end;
+    b->ml_dev = mod ? d + o.ml : nullptr;
+    b->ml_host = mod ? h + o.ml : nullptr;
 }
 
 static void *dalloc(ffhip_batch *b, size_t bytes, bool zero) {
@@ -940,7 +951,7 @@ static ffhip_batch *batch_create_impl(ffhip_engine *eng, const ffhip_model *m, i
         const ResLayout o = res_layout(b);
         b->res_head = o.lens;
         b->res_bytes = o.end;
-        b->res_runs_end = o.runs_end; b->res_rec_end = o.rec_end;
+        b->res_runs_end = o.runs_end; b->res_rec_end = o.rec_end; b->res_ml_end = o.ml_end;
         b->res_cap = b->res_bytes;
         if (!(b->res_dev = (unsigned char *)dalloc(b, b->res_bytes, true))) BFAIL();
         if (hipHostMalloc((void **)&b->res_host, b->res_bytes) != hipSuccess) { set_err(FFHIP_ENOMEM, "pinned host allocation failed"); BFAIL(); }
@@ -971,11 +982,9 @@ extern "C" ffhip_batch *ffhip_batch_create_packed(ffhip_engine *eng, const ffhip
 }
 static inline int batch_nreads(const ffhip_batch *b) { return b->packed ? b->nvirt : b->nread; }
 
-// The result block's run section (ffhip_batch::res_runs_end): grown on the first run that asks for it, the block's contents kept (a packed batch's set-up writes
-// into it before the run); pointers into the block are set again.  Returns 0 or an FFHIP_E* code.
-static int ensure_run_block(ffhip_batch *b, bool records) {
-    const ResLayout o = res_layout(b);
-    const size_t need = records ? o.rec_end : o.runs_end;
+// The result block grown to `need` bytes, the block's contents kept (a packed batch's set-up writes into it before the run); the caller sets the pointers into it
+// again (res_point).  Returns 0 or an FFHIP_E* code.
+static int grow_res_block(ffhip_batch *b, size_t need) {
     if (b->res_cap < need) {
         HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
         unsigned char *d = nullptr, *h = nullptr;
@@ -992,7 +1001,19 @@ static int ensure_run_block(ffhip_batch *b, bool records) {
         b->dev_bytes += need - b->res_cap;
         b->res_dev = d; b->res_host = h; b->res_cap = need;
     }
+    return FFHIP_OK;
+}
+// The result block's run section (ffhip_batch::res_runs_end) or 5mC section (res_ml_end): grown on the first run that asks for it
+static int ensure_run_block(ffhip_batch *b, bool records) {
+    const ResLayout o = res_layout(b);
+    if (int rc = grow_res_block(b, records ? o.rec_end : o.runs_end)) return rc;
     res_point(b, records);
+    return FFHIP_OK;
+}
+static int ensure_mod_block(ffhip_batch *b) {
+    if (int rc = grow_res_block(b, res_layout(b).ml_end)) return rc;
+    b->mod_block = true;
+    res_point(b, false);
     return FFHIP_OK;
 }
 // bytes of the result block a finished run brings down: [sat | abort] alone without a decode, the run section when the run made one
@@ -1000,6 +1021,7 @@ static size_t res_copy_bytes(const ffhip_batch *b, unsigned flags) {
     if (flags & FFHIP_RUN_NO_DECODE) return b->res_head;
     if (flags & FFHIP_RUN_RLE_RECORDS) return b->res_rec_end;
     if (flags & FFHIP_RUN_RLE_RUNS) return b->res_runs_end;
+    if (flags & FFHIP_RUN_MOD_PROBS) return b->res_ml_end;
     return b->res_bytes;
 }
 extern "C" int ffhip_batch_nreads(const ffhip_batch *b) { return b ? batch_nreads(b) : 0; }
@@ -1512,6 +1534,13 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
             return set_err(FFHIP_EINVAL, "run records: a decoded run of the run-length model (nbase 4) only");
         if (int rc = ensure_run_block(b, (flags & FFHIP_RUN_RLE_RECORDS) != 0)) return rc;
     }
+    b->mod_valid = 0;
+    if (flags & FFHIP_RUN_MOD_PROBS) {
+        if (m->kind == FFHIP_NET_LSTM5_RLE || m->nbase != 5)
+            return set_err(FFHIP_EINVAL, "5mC probabilities: a flip-flop model with a modified base (nbase 5) only");
+        if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "5mC probabilities need a decoded run (FFHIP_RUN_NO_DECODE is set)");
+        if (int rc = ensure_mod_block(b)) return rc;
+    }
     if (b->packed && !p.packable)
         return set_err(FFHIP_EINVAL, "packed batches take the default path and the launch-per-step kernels only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / unfused flags, ordinary temperature)");
     // A packed batch's launch-per-step run keeps its two fp32 activations in the memory of the two split buffers its default run has (the same size at two
@@ -1767,7 +1796,7 @@ static int run_back(ffhip_batch *b) {
                                    : launch_head(s, b->fa[cur], b->trans, m->FFp, m->FFb, Tb, B16, b->nread, m->P, m->Ps, Hp / 16, temperature / 5.0f);
         if (b->packed) { HIP_TRY(hipEventRecord(eng->head_done, s), FFHIP_EHIP); eng->head_done_rec = 1; }      // (the next packed batch's set-up and convolutions start behind it: apply_packed)
         if (p.post_done) {
-            const bool want_post = !(flags & FFHIP_RUN_NO_DECODE) && !(flags & FFHIP_RUN_VITERBI_ONLY);
+            const bool want_post = !(flags & FFHIP_RUN_NO_DECODE) && (!(flags & FFHIP_RUN_VITERBI_ONLY) || (flags & FFHIP_RUN_MOD_PROBS));      // (--viterbi: 5mC probabilities still come from the posterior)
             if (!p.head_e) launch_crf_exp(s, b->trans, b->crf_e, b->nread, Tb, m->nbase, m->Ps, tbs, nullptr, 0.0f);
             mark(b, 4);       // the profile's "posterior" slot times the chain launch: partition function + normalisation + posterior together
             launch_crf_fb(s, m->nbase, b->crf_e, b->trans, b->post, (double *)b->fwd, nR, Tb, b->crf_logz, tbr, want_post ? 3 : 1, nullptr, rmap);
@@ -1782,11 +1811,11 @@ static int run_back(ffhip_batch *b) {
     b->last_flags = flags;
     if (!(flags & FFHIP_RUN_NO_DECODE)) {
         const float *scores = b->trans;
-        if (!(flags & FFHIP_RUN_VITERBI_ONLY)) {
+        if (!(flags & FFHIP_RUN_VITERBI_ONLY) || (flags & FFHIP_RUN_MOD_PROBS)) {
             if (p.rle_post8) launch_rle_post8(s, b->trans, b->post, b->crf_e, (double *)b->fwd, b->nread, Tb, tbs, nR, tbr, rmap, gblk);      // fp64 linear-space chains (ffhip_decode.hip)
             else if (rle) launch_rle_transpost(s, b->trans, b->post, b->fwd, b->nread, Tb, m->nbase, m->Ps, tbs);       // decode.c:1037-1159
             else if (!p.post_done) launch_transpost(s, b->trans, b->post, b->fwd, b->nread, Tb, m->nbase, m->Ps, tbs);
-            scores = b->post;
+            if (!(flags & FFHIP_RUN_VITERBI_ONLY)) scores = b->post;      // (--viterbi with FFHIP_RUN_MOD_PROBS: path, scores and trace still from the transitions)
             b->launches[4]++;
         }
         mark(b, 5);
@@ -1807,6 +1836,11 @@ static int run_back(ffhip_batch *b) {
             launch_viterbi(s, scores, b->tb, b->path, b->qpath, b->score, nR, Tb, m->nbase, m->Ps, tbr, rmap);
             launch_assemble(s, b->path, b->qpath, b->bases, b->quals, b->lens, nR, Tb, m->nbase, tbr, rmap);
             b->launches[5] += 2;
+            if (flags & FFHIP_RUN_MOD_PROBS) {          // from the posterior whatever decoded the path (run_front checked the model)
+                launch_mod_probs(s, b->post, b->path, b->ml_dev, nR, Tb, m->Ps, tbr, rmap);
+                b->mod_valid = 1;
+                b->launches[5]++;
+            }
             if (!(flags & FFHIP_RUN_NO_TRACE)) {
                 launch_trace(s, scores, b->trace, nR, Tb, m->nbase, m->Ps, 1, tbr, rmap);
                 b->launches[5]++;
@@ -1860,7 +1894,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
         const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
         b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
         b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-        b->ran = 1; b->finished = 0; b->paired_last = 0; b->runs_valid = 0;
+        b->ran = 1; b->finished = 0; b->paired_last = 0; b->runs_valid = 0; b->mod_valid = 0;
         return FFHIP_OK;
     }
     HIP_TRY(hipMemsetAsync(b->bases, 0, n * L, s), FFHIP_EHIP);
@@ -1876,7 +1910,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
     const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
     b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
     b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-    b->ran = 1; b->finished = 0; b->paired_last = 0; b->runs_valid = 0;
+    b->ran = 1; b->finished = 0; b->paired_last = 0; b->runs_valid = 0; b->mod_valid = 0;
     return FFHIP_OK;
 }
 
@@ -1973,7 +2007,7 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
             const size_t r = (size_t)reads[k0 + k], r0 = read_row0(b, (int)r), r1 = read_row1(b, (int)r), nb = (size_t)b->hTb[r], nb1 = nb + 1;
             HIP_TRY(hipMemcpyAsync(b->trans + r0 * Ps, sd->trans + (size_t)k * Tb * Ps, nb * Ps * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
             if (fl & FFHIP_RUN_NO_DECODE) continue;
-            if (!(fl & FFHIP_RUN_VITERBI_ONLY)) HIP_TRY(hipMemcpyAsync(b->post + r0 * Ps, sd->post + (size_t)k * Tb * Ps, nb * Ps * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+            if (!(fl & FFHIP_RUN_VITERBI_ONLY) || (fl & FFHIP_RUN_MOD_PROBS)) HIP_TRY(hipMemcpyAsync(b->post + r0 * Ps, sd->post + (size_t)k * Tb * Ps, nb * Ps * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
             HIP_TRY(hipMemcpyAsync(b->path + r1, sd->path + (size_t)k * L, nb1 * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
             HIP_TRY(hipMemcpyAsync(b->qpath + r1, sd->qpath + (size_t)k * L, nb1 * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
             HIP_TRY(hipMemcpyAsync(b->score + r, sd->score + k, 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
@@ -1995,6 +2029,10 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
                     memcpy(hh.shape + r1, sh.shape + k1, nb1 * 4); memcpy(hh.scale + r1, sh.scale + k1, nb1 * 4); memcpy(hh.dwell + r1, sh.dwell + k1, nb1 * 4);
                 }
                 hh.nrun[r] = sh.nrun[k]; hh.fail[r] = sh.fail[k]; hh.len[r] = sh.len[k];
+            }
+            if (b->mod_valid && sd->mod_valid) {        // the 5mC bytes of the f32 run (down in its result block, as its strings)
+                HIP_TRY(hipMemcpyAsync(b->ml_dev + r1, sd->ml_dev + (size_t)k * L, nb1, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                memcpy(b->ml_host + r1, sd->ml_host + (size_t)k * L, nb1);
             }
             memcpy(b->h_bases + r1, sd->h_bases + (size_t)k * L, nb1);
             memcpy(b->h_quals + r1, sd->h_quals + (size_t)k * L, nb1);
@@ -2101,6 +2139,14 @@ extern "C" int ffhip_batch_rle_runs(const ffhip_batch *b, int read, ffhip_rle_ru
     return FFHIP_OK;
 }
 
+extern "C" int ffhip_batch_mod_probs(const ffhip_batch *b, int read, const uint8_t **ml, size_t *length) {
+    if (!results_ok(b, read) || !ml) return FFHIP_EINVAL;
+    if (!b->mod_valid || !b->ml_host) return set_err(FFHIP_EINVAL, "5mC probabilities were not made in this run (FFHIP_RUN_MOD_PROBS)");
+    *ml = b->ml_host + read_row1(b, read);
+    if (length) *length = (size_t)b->h_lens[read];
+    return FFHIP_OK;
+}
+
 static int d2h(ffhip_batch *b, void *dst, const void *src, size_t bytes) {
     hipSetDevice(b->eng->device);
     HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
@@ -2141,7 +2187,8 @@ extern "C" int ffhip_batch_transitions_to(ffhip_batch *b, int read, ffhip_mat ou
     return FFHIP_OK;
 }
 extern "C" int ffhip_batch_get_posterior(ffhip_batch *b, int read, float *out) {
-    if (b && (b->last_flags & (FFHIP_RUN_VITERBI_ONLY | FFHIP_RUN_NO_DECODE))) return set_err(FFHIP_EINVAL, "posterior was not computed in this run");
+    if (b && ((b->last_flags & FFHIP_RUN_NO_DECODE) || ((b->last_flags & FFHIP_RUN_VITERBI_ONLY) && !(b->last_flags & FFHIP_RUN_MOD_PROBS))))
+        return set_err(FFHIP_EINVAL, "posterior was not computed in this run");
     return b ? get_scores(b, b->post, read, out) : FFHIP_EINVAL;
 }
 extern "C" int ffhip_batch_get_trace(ffhip_batch *b, int read, int32_t *out) {

@@ -198,6 +198,8 @@ void launch_viterbi(hipStream_t s, const float *score_mat, uint8_t *tb, int *pat
 // change positions -> base / quality strings
 void launch_assemble(hipStream_t s, const int *path, const float *qpath, char *bases, char *quals, int *lens,
                      int nread, int Tb, int nbase, const int *tbs = nullptr, ReadMap map = ReadMap());
+// 5mC probabilities of the called C / Z bases of a 5-base model (k_mod_probs): one byte a called base at the read's row of the (Tb + 1)-entry buffers
+void launch_mod_probs(hipStream_t s, const float *post, const int *path, uint8_t *ml, int nread, int Tb, int Ps, const int *tbs = nullptr, ReadMap map = ReadMap());
 // exp + trace_from_posterior
 void launch_trace(hipStream_t s, const float *post, int32_t *trace, int nread, int Tb, int nbase, int Ps, int is_log, const int *tbs = nullptr, ReadMap map = ReadMap());
 void launch_exp_inplace(hipStream_t s, float *x, size_t n);

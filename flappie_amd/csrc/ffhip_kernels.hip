@@ -2294,6 +2294,62 @@ void launch_assemble(hipStream_t s, const int *path, const float *qpath, char *b
     hipLaunchKernelGGL(k_assemble, dim3(nread), dim3(64), 0, s, path, qpath, bases, quals, lens, Tb, nbase, tbs, map);
 }
 
+// ---- 5mC probabilities of the called bases (FFHIP_RUN_MOD_PROBS; 5-base alphabet A C G T Z, 10 states, P = Ps = 60) ---------
+// k_assemble's change positions again, one wave per read: the called base at position pos gets, when it is a C (state % 5 == 1) or a Z (4),
+//   occ(j) = sum_f<10 x[10 j + f] + x[50 + j] + x[55 + j],   x = exp(log posterior of block pos - 1)
+// -- k_trace's column pos before its 255-scaling: the same cephes exp, the same sums in the same order -- and
+//   p = occ(4) / (occ(1) + occ(4)) (0 where the denominator is 0 or not finite),   ml = min(255, floor(256 p))   (SAMv1 1.7: N stands for [N/256, (N+1)/256)).
+// Every other called base gets 0.  ml holds one byte a called base at the read's row of the (Tb + 1)-entry buffers, aligned with k_assemble's string.
+// The C / Z lanes of a step load their 24 values each; the rest of the wave waits (profiles/r07_modbase_cost.txt: well under the batch's decode).
+__global__ void __launch_bounds__(64)
+k_mod_probs(const float *__restrict__ post, const int *__restrict__ path, uint8_t *__restrict__ ml, int TbS, int Ps, const int *__restrict__ tbs, ReadMap map) {
+    FFHIP_DECODE_PRIO_SET();
+    constexpr int nbase = 5, ns = 10, off = nbase * ns;
+    const int lane = threadIdx.x;
+    const int Tb = tbs ? tbs[blockIdx.x] : TbS;          // this read's blocks; TbS is the batch's stride
+    if (Tb <= 0) return;                                 // an empty slot
+    const size_t r1 = map.row1(blockIdx.x, TbS);
+    const int *pth = path + r1;
+    const float *Pp = post + map.row0(blockIdx.x, TbS) * Ps;
+    uint8_t *out = ml + r1;
+    int count = 0;
+    for (int p0 = 1; p0 < Tb; p0 += 64) {
+        const int pos = p0 + lane;
+        bool change = false;
+        int st = 0;
+        if (pos < Tb) { st = pth[pos]; change = (st != pth[pos - 1]); }
+        const unsigned long long mask = __ballot(change);
+        if (change) {
+            const int idx = count + __popcll(mask & ((1ull << lane) - 1ull));
+            const int base = st % nbase;
+            uint8_t v = 0;
+            if (base == 1 || base == 4) {
+                const float *x = Pp + (size_t)(pos - 1) * Ps;
+                float occ[2];
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    const int j = k ? 4 : 1;
+                    float flip = exp_cephes(x[j * ns]);
+                    for (int f = 1; f < ns; f++) flip += exp_cephes(x[j * ns + f]);
+                    const float flop = exp_cephes(x[off + j]) + exp_cephes(x[off + nbase + j]);
+                    occ[k] = flip + flop;
+                }
+                const float den = occ[0] + occ[1];
+                if (den > 0.0f && isfinite(den)) {
+                    const float q = floorf(256.0f * (occ[1] / den));
+                    v = (uint8_t)(q < 255.0f ? (q > 0.0f ? q : 0.0f) : 255.0f);
+                }
+            }
+            out[idx] = v;
+        }
+        count += __popcll(mask);
+    }
+}
+
+void launch_mod_probs(hipStream_t s, const float *post, const int *path, uint8_t *ml, int nread, int Tb, int Ps, const int *tbs, ReadMap map) {
+    if (nread > 0) hipLaunchKernelGGL(k_mod_probs, dim3(nread), dim3(64), 0, s, post, path, ml, Tb, Ps, tbs, map);
+}
+
 // ---- trace --------------------------------------------------------------------------------------
 // exp_activation_inplace (layers.c:56-66, cephes exp) followed by trace_from_posterior
 // (decode.c:499-543): column 0 sums block 0 by from-state, column blk+1 sums block blk by to-state.

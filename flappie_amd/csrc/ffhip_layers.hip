@@ -618,6 +618,30 @@ extern "C" int ffhip_op_rle_runs(ffhip_engine *eng, ffhip_mat param, const int *
     return FFHIP_OK;
 }
 
+// 5mC probabilities of one log posterior and its path (k_mod_probs; include/ffhip.h)
+extern "C" int ffhip_op_mod_probs(ffhip_engine *eng, ffhip_mat logpost, const int *path, uint8_t *ml, size_t *ncalled) {
+    OP_ENTER(eng);
+    int nbase;
+    if (!view_ok(logpost) || !path || !ml || !ncalled || !flipflop_dims(logpost.nr, logpost.stride, &nbase) || nbase != 5 || logpost.nc > (size_t)1 << 30)
+        return set_err(FFHIP_EINVAL, "bad 5mC probability arguments (a 5-base flip-flop posterior of 60 rows, a path, an output)");
+    const size_t nblock = logpost.nc, L = nblock + 1;
+    size_t n = 0;
+    for (size_t b = 0; b < nblock; b++) {
+        if (path[b] < 0 || path[b] >= 2 * nbase) return set_err(FFHIP_EINVAL, "5mC probabilities: a path entry is not a state");
+        if (b > 0 && path[b] != path[b - 1]) n++;      // a called base (k_assemble's change positions)
+    }
+    float *d_p = upload_img(tmp, logpost, s);
+    int *d_path = (int *)tmp.get(L * 4);
+    uint8_t *d_ml = (uint8_t *)tmp.get(L);
+    if (!d_p || !d_path || !d_ml) OP_NOMEM();
+    HIP_TRY(hipMemcpyAsync(d_path, path, nblock * 4, hipMemcpyHostToDevice, s), FFHIP_EHIP);
+    launch_mod_probs(s, d_p, d_path, d_ml, 1, (int)nblock, (int)logpost.stride, nullptr, ReadMap());
+    HIP_TRY(hipMemcpyAsync(ml, d_ml, n, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    *ncalled = n;
+    return FFHIP_OK;
+}
+
 // ---- decoders of the first run-length head (decode.c:552-892): param is [4 nbase x nblock]
 static bool rl1_dims(const ffhip_mat &param, int *nbase) {
     if (!view_ok(param) || param.nr % 4 != 0 || param.nr / 4 < 1 || param.nr / 4 > 8) return false;

@@ -37,6 +37,7 @@
 #include "../../include/ffhip.h"
 #include "../../include/flappie_common.h"
 #include "../../include/flappie_output.h"
+#include "../../include/flappie_modbase.h"
 #include "../../include/networks.h"
 
 const char *argp_program_version = "flappie (MI355X/HIP) 0.1, interface of flappie 2.1.3";
@@ -77,6 +78,8 @@ static struct argp_option options[] = {
     {"fasta", 20, 0, 0, "Write FASTA basecalls instead of run records: what the run records through misc/decode_runnie.py give, with runs and run lengths made on the GPU"},
     {"rlc", 21, 0, 0, "With --fasta: the run-length compressed sequence (one base a run, as decode_runnie.py --rlc)"},
     {"run-scale", 22, "A,C,G,T", 0, "With --fasta: per-base factors of the scale parameter (default 1.02,1.04,1.04,1.02, as decode_runnie.py --scale)"},
+#else
+    {"modbase-tags", 23, 0, 0, "Report modified bases as SAM MM/ML tags (5mC probabilities made on the GPU): Z is written as C and every C gets a probability (models with a modified base only, e.g. r941_5mC)"},
 #endif
     {0}
 };
@@ -111,6 +114,7 @@ static struct {
     bool shard_by_size;
     bool fasta, rlc, run_scale_set;     /* runnie: --fasta, --rlc, --run-scale given */
     double run_scale[4];
+    bool modbase_tags;                  /* flappie: --modbase-tags given */
 } args = { 1, 200, 0.0f, NULL, FLAPPIE_OUTFORMAT_FASTQ, 0, DEFAULT_MODEL, NULL, "", false, 1.0f, 200, 10, 100, 0.0f, false, NULL, true, 0, 4, 0, 0, false, false, false, false,
            { 1.02, 1.04, 1.04, 1.02 } };      /* batch 0: by model (below); nshard 0: --shard not given */
 
@@ -218,6 +222,8 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
         args.run_scale_set = true;
         break;
     }
+#else
+    case 23: args.modbase_tags = true; break;
 #endif
     case ARGP_KEY_NO_ARGS: argp_usage(state); break;
     case ARGP_KEY_ARG:
@@ -353,6 +359,7 @@ typedef struct {
     struct _raw_basecall_info res;      /* rt filled by read_raw, start/end by the preparation; basecall == NULL until called */
     int prepared;                       /* index into the chunk's ffhip_prep, or -1 */
     char *rle_text;                     /* runnie: the read's records, formatted (runnie.c:282-313); --fasta: its sequence, wrapped */
+    uint8_t *ml;                        /* --modbase-tags: the 5mC byte of every called base, aligned with res.basecall (owned) */
     int rle_nocall;                     /* runnie --fasta: no runs, or a failed run-length estimate (decode_runnie.py: "No basecall returned") */
 } item;
 
@@ -421,7 +428,10 @@ static int batch_run(ffhip_batch *b, unsigned flags) {
     return ffhip_batch_run(b, args.temperature, flags);
 }
 #else
-static unsigned run_flags(void) { return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE); }
+/* --modbase-tags: the 5mC bytes of the called bases come from the device (FFHIP_RUN_MOD_PROBS) */
+static unsigned run_flags(void) {
+    return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u);
+}
 static int batch_run(ffhip_batch *b, unsigned flags) { return ffhip_batch_run(b, args.temperature, flags); }
 #endif
 
@@ -660,9 +670,16 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
         r->score = ffhip_batch_score(b, i);
         r->nblock = nblock;
         r->pos = calloc(nblock + 1, sizeof(int));
+        if (args.modbase_tags) {
+            const uint8_t *ml = NULL;
+            size_t mlen = 0;
+            if (0 != ffhip_batch_mod_probs(b, i, &ml, &mlen) || mlen != blen) warnx("%s", ffhip_last_error());
+            else if (NULL != (its[i]->ml = malloc(blen ? blen : 1))) memcpy(its[i]->ml, ml, blen);
+        }
         if (args.reverse) {                                    /* flappie.c:294-297 */
             reverse_char_array(r->basecall, blen);
             reverse_char_array(r->quality, blen);
+            for (size_t k = 0; its[i]->ml && k < blen / 2; k++) { const uint8_t t = its[i]->ml[k]; its[i]->ml[k] = its[i]->ml[blen - 1 - k]; its[i]->ml[blen - 1 - k] = t; }
         }
         if (args.trace) {
             int32_t *tmp = malloc((nblock + 1) * nstate * sizeof(int32_t));
@@ -806,7 +823,13 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
             char *fn = strdup(it->filename);
             const char *base = basename(fn);
             const char *uuid = it->res.rt.uuid ? it->res.rt.uuid : "";
-            fprintf_format(args.outformat, args.output, uuid, base, args.uuid, args.prefix, it->res);
+            /* --modbase-tags: Z is written as C here, in the record only -- the trace file below keeps the call as it is */
+            if (args.modbase_tags) {
+                if (it->ml) fprintf_modbase_record(args.outformat, args.output, uuid, base, args.uuid, args.prefix, it->res, it->ml);
+                else warnx("No base-modification probabilities for %s", it->filename);
+            } else {
+                fprintf_format(args.outformat, args.output, uuid, base, args.uuid, args.prefix, it->res);
+            }
             if (hdf5out >= 0) {
                 pthread_mutex_lock(&hdf5_lock);
                 if (packs && packs[i]) summary_pack_write(hdf5out, args.uuid ? uuid : base, packs[i]);
@@ -816,6 +839,8 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
             }
             free(fn);
         }
+        free(it->ml);
+        it->ml = NULL;
         free_raw_basecall_info(&it->res);
         free(it->filename);
     }
@@ -1411,6 +1436,9 @@ int main(int argc, char *argv[]) {
     argp_parse(&argp, argc, argv, 0, 0, NULL);
 #ifdef BUILD_RUNNIE
     if ((args.rlc || args.run_scale_set) && !args.fasta) errx(EXIT_FAILURE, "--rlc and --run-scale go with --fasta");
+#else
+    if (args.modbase_tags && !flappie_model_has_modbase(args.model))      /* (the registry knows: before any file or the GPU is touched) */
+        errx(EXIT_FAILURE, "--modbase-tags needs a model with a modified base (r941_5mC); \"%s\" has none", flappie_model_string(args.model));
 #endif
     if (cli_dbg("segv_trace")) { signal(SIGSEGV, segv_trace); signal(SIGABRT, segv_trace); signal(SIGBUS, segv_trace); }
     if (NULL == args.output) args.output = stdout;

@@ -1,11 +1,13 @@
 /*  flappie_output.c -- record formatting (include/flappie_output.h), byte-compatible with
  *  /root/reference/src/flappie_output.c:16-132 (including the SAM record's repeated sequence/quality
- *  line, which the reference emits).
+ *  line, which the reference emits); and the records with SAMv1 1.7 base-modification tags
+ *  (include/flappie_modbase.h).
  */
 #include <err.h>
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/flappie_output.h"
+#include "../../include/flappie_modbase.h"
 
 enum flappie_outformat_type get_outformat(const char *formatstr) {
     if (NULL == formatstr) return FLAPPIE_OUTFORMAT_INVALID;
@@ -32,17 +34,17 @@ static void put_string(FILE *fp, const char *str, bool newline) {
     if (newline) fputc('\n', fp);
 }
 
-/* flappie_output.c:95-100,112-117: the JSON-ish header shared by FASTA and FASTQ */
+/* flappie_output.c:95-100,112-117: the JSON-ish header shared by FASTA and FASTQ; `tail` goes in front of its newline ("" for the reference's records) */
 static void put_header(FILE *fp, char lead, const char *uuid, const char *readname, bool uuid_primary, const char *prefix,
-                       const struct _raw_basecall_info *res) {
-    fprintf(fp, "%c%s%s  { \"filename\" : \"%s\", \"uuid\" : \"%s\", \"normalised_score\" : %f,  \"nblock\" : %zu,  \"sequence_length\" : %zu,  \"blocks_per_base\" : %f, \"nsample\" : %zu, \"trim\" : [ %zu, %zu ] }\n",
+                       const struct _raw_basecall_info *res, const char *tail) {
+    fprintf(fp, "%c%s%s  { \"filename\" : \"%s\", \"uuid\" : \"%s\", \"normalised_score\" : %f,  \"nblock\" : %zu,  \"sequence_length\" : %zu,  \"blocks_per_base\" : %f, \"nsample\" : %zu, \"trim\" : [ %zu, %zu ] }%s\n",
             lead, prefix, uuid_primary ? uuid : readname, readname, uuid, -res->score / res->nblock, res->nblock,
-            res->basecall_length, (float)res->nblock / (float)res->basecall_length, res->rt.n, res->rt.start, res->rt.end);
+            res->basecall_length, (float)res->nblock / (float)res->basecall_length, res->rt.n, res->rt.start, res->rt.end, tail);
 }
 
 void fprintf_fasta(FILE *fp, const char *uuid, const char *readname, bool uuid_primary, const char *prefix,
                    const struct _raw_basecall_info res) {
-    put_header(fp, '>', uuid, readname, uuid_primary, prefix, &res);
+    put_header(fp, '>', uuid, readname, uuid_primary, prefix, &res, "");
     put_string(fp, res.basecall, true);
     fflush(fp);
 }
@@ -53,7 +55,7 @@ void fprintf_fastq(FILE *fp, const char *uuid, const char *readname, bool uuid_p
         warnx("Can't output fastq for reads without quality values");
         return;
     }
-    put_header(fp, '@', uuid, readname, uuid_primary, prefix, &res);
+    put_header(fp, '@', uuid, readname, uuid_primary, prefix, &res, "");
     put_string(fp, res.basecall, true);
     fputs("+\n", fp);
     put_string(fp, res.quality, true);
@@ -84,4 +86,75 @@ void fprintf_format(enum flappie_outformat_type outformat, FILE *fp, const char 
 void printf_format(enum flappie_outformat_type outformat, const char *uuid, const char *readname, bool uuid_primary,
                    const char *prefix, const struct _raw_basecall_info res) {
     fprintf_format(outformat, stdout, uuid, readname, uuid_primary, prefix, res);
+}
+
+/* ---- records with base-modification tags (include/flappie_modbase.h) ---- */
+int flappie_modbase_tags(const char *seq, const uint8_t *ml, char **mm_tag, char **ml_tag) {
+    if (NULL == seq || NULL == mm_tag || NULL == ml_tag) return -1;
+    *mm_tag = *ml_tag = NULL;
+    size_t nc = 0;
+    for (const char *c = seq; *c; c++) nc += ('C' == *c);
+    if (nc > 0 && NULL == ml) return -1;
+    char *mm = malloc(11 + 2 * nc + 1), *mv = malloc(7 + 4 * nc + 1);      /* "MM:Z:C+m?" ",0"... ";"  and  "ML:B:C" ",255"... */
+    if (NULL == mm || NULL == mv) { free(mm); free(mv); return -1; }
+    size_t a = 0, b = 0;
+    memcpy(mm, "MM:Z:C+m?", 9); a = 9;
+    memcpy(mv, "ML:B:C", 6); b = 6;
+    for (size_t i = 0; seq[i]; i++) {      /* (digits by hand: a read has hundreds of Cs, and sprintf of each was most of the writer's time) */
+        if ('C' != seq[i]) continue;
+        mm[a++] = ','; mm[a++] = '0';
+        const unsigned v = ml[i];
+        mv[b++] = ',';
+        if (v >= 100) mv[b++] = (char)('0' + v / 100);
+        if (v >= 10) mv[b++] = (char)('0' + v / 10 % 10);
+        mv[b++] = (char)('0' + v % 10);
+    }
+    mm[a++] = ';';
+    mm[a] = 0;
+    mv[b] = 0;
+    *mm_tag = mm;
+    *ml_tag = mv;
+    return 0;
+}
+
+/* SEQ of a tagged record: the call with every Z written as C; and its two tags */
+static char *modbase_seq(const struct _raw_basecall_info *res, const uint8_t *ml, char **mm, char **mv) {
+    const char *call = res->basecall ? res->basecall : "";
+    char *seq = strdup(call);
+    if (NULL == seq) return NULL;
+    for (char *c = seq; *c; c++) if ('Z' == *c) *c = 'C';
+    if (0 != flappie_modbase_tags(seq, ml, mm, mv)) { free(seq); return NULL; }
+    return seq;
+}
+
+void fprintf_modbase_record(enum flappie_outformat_type outformat, FILE *fp, const char *uuid, const char *readname, bool uuid_primary,
+                            const char *prefix, const struct _raw_basecall_info res, const uint8_t *ml) {
+    if (FLAPPIE_OUTFORMAT_FASTQ == outformat && NULL == res.quality) {
+        warnx("Can't output fastq for reads without quality values");
+        return;
+    }
+    char *mm = NULL, *mv = NULL, *seq = modbase_seq(&res, ml, &mm, &mv);
+    if (NULL == seq) errx(EXIT_FAILURE, "out of memory for the base-modification tags of %s", uuid_primary ? uuid : readname);
+    char *tail = malloc(strlen(mm) + strlen(mv) + 3);
+    if (NULL == tail) errx(EXIT_FAILURE, "out of memory for the base-modification tags of %s", uuid_primary ? uuid : readname);
+    sprintf(tail, "\t%s\t%s", mm, mv);
+    switch (outformat) {
+    case FLAPPIE_OUTFORMAT_FASTA:
+        put_header(fp, '>', uuid, readname, uuid_primary, prefix, &res, tail);
+        put_string(fp, seq, true);
+        break;
+    case FLAPPIE_OUTFORMAT_FASTQ:
+        put_header(fp, '@', uuid, readname, uuid_primary, prefix, &res, tail);
+        put_string(fp, seq, true);
+        fputs("+\n", fp);
+        put_string(fp, res.quality, true);
+        break;
+    case FLAPPIE_OUTFORMAT_SAM:      /* one line: the 11 mandatory fields, then the tags */
+        fprintf(fp, "%s%s\t4\t*\t0\t0\t*\t*\t0\t0\t%s\t%s%s\n", prefix, uuid_primary ? uuid : readname, seq, res.quality ? res.quality : "", tail);
+        break;
+    case FLAPPIE_OUTFORMAT_INVALID: errx(EXIT_FAILURE, "Invalid flappie output %s:%d", __FILE__, __LINE__);
+    default: errx(EXIT_FAILURE, "Flappie enum failure -- report bug\n");
+    }
+    fflush(fp);
+    free(tail); free(seq); free(mm); free(mv);
 }

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/networks.h"
+#include "../../include/flappie_modbase.h"
 #include "../../include/ffhip.h"
 #include "mdl_loader.h"
 
@@ -71,6 +72,9 @@ const char *flappie_model_description(const enum model_type model) {
     errx(EXIT_FAILURE, "Flappie enum failure -- report as bug. %s:%d \n", __FILE__, __LINE__);
     return NULL;
 }
+
+/* include/flappie_modbase.h: the models whose alphabet has the modified base Z */
+int flappie_model_has_modbase(enum model_type model) { return valid_model((int)model) && FFHIP_NET_GRUMOD5 == registry[model].kind; }
 
 /* networks.c:86-105 */
 transition_function_ptr get_transition_function(const enum model_type model) {

@@ -87,6 +87,11 @@ typedef struct {
  * ffhip_batch_finish's one copy of the result block */
 #define FFHIP_RUN_RLE_RUNS    1024u   /* every run's base and run-length estimate, and per read the run count, expanded length and failure flag */
 #define FFHIP_RUN_RLE_RECORDS 2048u   /* ... and every run's shape, scale and dwell as well (the whole .run record; 12 more bytes a block) */
+/* 5mC probabilities of a flip-flop model with a modified base (nbase 5: A C G T Z, e.g. r941_5mC; ffhip_batch_mod_probs below): one byte a called base, made
+ * on the device from the posterior behind the Viterbi and brought down in ffhip_batch_finish's one copy of the result block.  Path, scores, strings and trace are
+ * those of the same run without the flag; under FFHIP_RUN_VITERBI_ONLY the forward-backward pass runs as well (for the probabilities only), and
+ * ffhip_batch_get_posterior returns its posterior.  Another model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
+#define FFHIP_RUN_MOD_PROBS   4096u
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -337,6 +342,17 @@ int ffhip_batch_set_run_scale(ffhip_batch *b, const double factor[4]);
 int ffhip_batch_rle_runs(const ffhip_batch *b, int read, ffhip_rle_runs *out);
 int ffhip_op_rle_runs(ffhip_engine *eng, ffhip_mat param, const int *path, const double *factor, size_t *nrun, uint8_t *base, int32_t *est,
                       float *shape, float *scale, int32_t *dwell, int *failed, unsigned long long *length);
+/* 5mC probabilities (SAMv1 1.7 ML values), made on the device by k_mod_probs.  A called base is a change position pos (1 <= pos < nblock,
+ * path[pos] != path[pos - 1]) -- the bases of ffhip_batch_basecall --; one whose state % 5 is 1 (C) or 4 (Z) gets, with x = exp(log posterior of block pos - 1),
+ *   occ(j) = sum_{f < 10} x[10 j + f] + x[50 + j] + x[55 + j]      (flip j + flop j: column pos of the trace before its 255-scaling)
+ *   p = occ(4) / (occ(1) + occ(4))  (0 if the denominator is 0 or not finite),   ml = min(255, floor(256 p));
+ * every other called base gets 0.
+ * ffhip_batch_mod_probs: after ffhip_batch_finish of a run with FFHIP_RUN_MOD_PROBS; *ml points at `length` bytes (the basecall's length), aligned with
+ *   ffhip_batch_basecall's string and owned by the batch.  A run without the flag: FFHIP_EINVAL.
+ * ffhip_op_mod_probs: the same on one [60 x nblock] log posterior (nbase 5) and its path (nblock entries, each 0 .. 9); ml: caller-owned, nblock bytes at
+ *   least; *ncalled: the called bases (bytes written). */
+int ffhip_batch_mod_probs(const ffhip_batch *b, int read, const uint8_t **ml, size_t *length);
+int ffhip_op_mod_probs(ffhip_engine *eng, ffhip_mat logpost, const int *path, uint8_t *ml, size_t *ncalled);
 int ffhip_runlength_viterbi(ffhip_engine *eng, ffhip_mat param, int *path /* nblock */, float *score);
 /* decoders of the first-generation head on [4 nbase x nblock] matrices: decode_runlength (decode.c:694-767), posterior_runlength
  * (decode.c:793-892; post is [4 nbase x nblock + 1]), runlengths_mean (decode.c:576-603) */
