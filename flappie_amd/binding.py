@@ -30,6 +30,7 @@ RUN_RLE_RUNS = 1024       # run-length model: run bases + run-length estimates m
 RUN_RLE_RECORDS = 2048    # ... and every run's shape, scale and dwell
 RLE_SCALE_DEFAULT = (1.02, 1.04, 1.04, 1.02)      # decode_runnie.py's default --scale (A, C, G, T)
 RUN_MOD_PROBS = 4096      # 5-base model: 5mC probabilities (SAM ML bytes) of the called bases made on the device (Batch.mod_probs)
+RUN_MOVES = 8192          # flip-flop model: the move table (one byte a block, 1 where a base is emitted) made on the device (Batch.moves)
 # ffhip_debug_gate_math forms (include/ffhip.h)
 GATE_FORMS = ("logistic_ref", "tanh_ref", "logistic_ref4_lean", "logistic_ref2_lean", "logistic_ref_lean", "tanh_ref_lean",
               "swish_act4", "tanh_act4", "logistic_hw1", "tanh_hw1", "logistic_hw2", "tanh_hw2")
@@ -175,6 +176,10 @@ def lib():
                                     C.POINTER(C.c_ulonglong)]
     L.ffhip_batch_mod_probs.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.ffhip_op_mod_probs.argtypes = [vp, CFMat, C.POINTER(C.c_int), C.POINTER(C.c_uint8), C.POINTER(C.c_size_t)]
+    L.ffhip_batch_moves.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
+    L.ffhip_op_moves.argtypes = [vp, C.POINTER(C.c_int), C.c_size_t, C.POINTER(C.c_uint8)]
+    L.ffhip_model_stride.restype = C.c_size_t
+    L.ffhip_model_stride.argtypes = [vp]
     _LIB = L
     return L
 
@@ -264,6 +269,11 @@ class DeviceModel:
     def launch_reads(self) -> int:
         """reads per batch that keep every layer launch of this model full on this device (ffhip_model_launch_reads)"""
         return int(lib().ffhip_model_launch_reads(self.h))
+
+    @property
+    def stride(self) -> int:
+        """samples a block: the product of the convolution strides (ffhip_model_stride)"""
+        return int(lib().ffhip_model_stride(self.h))
 
     def close(self):
         if self.h:
@@ -450,6 +460,12 @@ class Batch:
         _check(lib().ffhip_batch_mod_probs(self.h, read, C.byref(p), C.byref(n)))
         return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint8)
 
+    def moves(self, read: int) -> np.ndarray:
+        """move table of a run with RUN_MOVES (ffhip_batch_moves): one uint8 a block, 1 where the block's transition emits a base of basecall(read)"""
+        p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+        _check(lib().ffhip_batch_moves(self.h, read, C.byref(p), C.byref(n)))
+        return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint8)
+
     def transitions(self, read: int) -> np.ndarray:
         out = np.zeros((self.read_nblock(read), self.P), dtype=np.float32)
         _check(lib().ffhip_batch_get_transitions(self.h, read, _fptr(out)))
@@ -582,6 +598,15 @@ def mod_probs_op(engine: Engine, logpost: np.ndarray, path: np.ndarray) -> np.nd
     _check(lib().ffhip_op_mod_probs(engine.h, CFMat(_fptr(logpost), nparam, nblock, nparam), path.ctypes.data_as(C.POINTER(C.c_int)),
                                     ml.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(n)))
     return ml[:n.value].copy()
+
+
+def moves_op(engine: Engine, path: np.ndarray) -> np.ndarray:
+    """ffhip_op_moves: the move table of ONE path of nblock + 1 entries: nblock uint8"""
+    path = np.ascontiguousarray(path, dtype=np.int32)
+    assert path.ndim == 1 and path.size >= 2
+    mv = np.zeros(path.size - 1, np.uint8)
+    _check(lib().ffhip_op_moves(engine.h, path.ctypes.data_as(C.POINTER(C.c_int)), path.size - 1, mv.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return mv
 
 
 def basecall_reads(dmodel: DeviceModel, signals: np.ndarray, temperature: float = 1.0, flags: int = 0):

@@ -595,6 +595,7 @@ extern "C" ffhip_model *ffhip_model_upload(ffhip_engine *eng, const ffhip_model_
 extern "C" size_t ffhip_model_hidden(const ffhip_model *m) { return m ? (size_t)m->H : 0; }
 extern "C" size_t ffhip_model_nparam(const ffhip_model *m) { return m ? (size_t)m->P : 0; }
 extern "C" size_t ffhip_model_nbase(const ffhip_model *m) { return m ? (size_t)m->nbase : 0; }
+extern "C" size_t ffhip_model_stride(const ffhip_model *m) { size_t st = m ? 1 : 0; for (int l = 0; m && l < m->nconv; l++) st *= (size_t)m->conv[l].stride; return st; }
 // reads one FULL layer launch of this model takes on this device (the batch size that keeps every launch full): 1024 at 256 hidden units (the
 // packed forms), 512 at 384, else 256 -- on 256 CUs (ffhip_rnn_split.hip, split_next_launch_tiles)
 // (a device with fewer than 32 CUs -- none exists in this family -- still gets a unit of 1: the layer loop must advance)
@@ -761,6 +762,11 @@ struct ffhip_batch {
     uint8_t *ml_dev = nullptr, *ml_host = nullptr;
     bool mod_block = false;             // the block holds the section
     int mod_valid = 0;                  // the last run made them
+    // move table of a flip-flop batch (FFHIP_RUN_MOVES, k_moves): one byte a block, a section of its own behind the 5mC section where the block holds one and
+    // behind [.. | quals] where it does not, added on the first run that asks for it
+    uint8_t *mv_dev = nullptr, *mv_host = nullptr;
+    bool mv_block = false;              // the block holds the section
+    int mv_valid = 0;                   // the last run made them
     std::vector<void *> owned;
     unsigned last_flags = 0;
     float last_temperature = 1.0f;
@@ -789,8 +795,11 @@ struct ffhip_batch {
 
 // The result block's layout, in one place: [sat | abort | lens | score | bases | quals] (what every decoded run brings down), then the run section of a run-length
 // batch, [nrun | fail | len | base | est] and [shape | scale | dwell] (present once a run asked for it: ensure_run_block), or in the same place the [ml] section of
-// a 5-base flip-flop batch (ensure_mod_block; a batch has one model, so never both).  Offsets in bytes, each part 256-aligned.
-struct ResLayout { size_t sat, abort, lens, score, bases, quals, end, nrun, fail, len, base, est, runs_end, shape, scale, dwell, rec_end, ml, ml_end; };
+// a 5-base flip-flop batch (ensure_mod_block; a batch has one model, so never both), and the [mv] section of a flip-flop batch (ensure_moves_block) behind the
+// sections the block holds: [.. | quals | mv] or [.. | quals | ml | mv].  A finished run brings a PREFIX of the block down (res_copy_bytes), and a batch that
+// never asked for 5mC bytes has no ml section, so a run with moves alone copies no unused section; only a batch that has made both kinds and then runs with
+// moves alone copies the ml section's bytes unused.  Offsets in bytes, each part 256-aligned.
+struct ResLayout { size_t sat, abort, lens, score, bases, quals, end, nrun, fail, len, base, est, runs_end, shape, scale, dwell, rec_end, ml, ml_end, mv, mv_end; };
 static ResLayout res_layout(const ffhip_batch *b) {
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t nres = (size_t)b->cap_reads, n1 = (size_t)b->nread * ((size_t)b->Tb + 1);
@@ -801,6 +810,7 @@ static ResLayout res_layout(const ffhip_batch *b) {
     o.runs_end = o.est + up(n1 * 4);
     o.shape = o.runs_end; o.scale = o.shape + up(n1 * 4); o.dwell = o.scale + up(n1 * 4); o.rec_end = o.dwell + up(n1 * 4);
     o.ml = o.end; o.ml_end = o.ml + up(n1);
+    o.mv = b->mod_block ? o.ml_end : o.end; o.mv_end = o.mv + up(n1);
     return o;
 }
 // every pointer into the result block, device and pinned host side, from res_dev / res_host and the layout (the run section's when the block holds it; shape,
@@ -825,6 +835,9 @@ static void res_point(ffhip_batch *b, bool records) {
     const bool mod = b->mod_block && b->res_cap >= o.ml_end;
     b->ml_dev = mod ? d + o.ml : nullptr;
     b->ml_host = mod ? h + o.ml : nullptr;
+    const bool mv = b->mv_block && b->res_cap >= o.mv_end;
+    b->mv_dev = mv ? d + o.mv : nullptr;
+    b->mv_host = mv ? h + o.mv : nullptr;
 }
 
 static void *dalloc(ffhip_batch *b, size_t bytes, bool zero) {
@@ -1011,8 +1024,18 @@ static int ensure_run_block(ffhip_batch *b, bool records) {
     return FFHIP_OK;
 }
 static int ensure_mod_block(ffhip_batch *b) {
-    if (int rc = grow_res_block(b, res_layout(b).ml_end)) return rc;
-    b->mod_block = true;
+    if (b->mod_block) return FFHIP_OK;
+    b->mod_block = true;                // (the moves section, when the block holds one, now lies behind this one: res_layout)
+    const ResLayout o = res_layout(b);
+    if (int rc = grow_res_block(b, b->mv_block ? o.mv_end : o.ml_end)) { b->mod_block = false; return rc; }
+    res_point(b, false);
+    return FFHIP_OK;
+}
+// ... or its moves section
+static int ensure_moves_block(ffhip_batch *b) {
+    if (b->mv_block) return FFHIP_OK;
+    if (int rc = grow_res_block(b, res_layout(b).mv_end)) return rc;
+    b->mv_block = true;
     res_point(b, false);
     return FFHIP_OK;
 }
@@ -1021,6 +1044,7 @@ static size_t res_copy_bytes(const ffhip_batch *b, unsigned flags) {
     if (flags & FFHIP_RUN_NO_DECODE) return b->res_head;
     if (flags & FFHIP_RUN_RLE_RECORDS) return b->res_rec_end;
     if (flags & FFHIP_RUN_RLE_RUNS) return b->res_runs_end;
+    if (flags & FFHIP_RUN_MOVES) return res_layout(b).mv_end;
     if (flags & FFHIP_RUN_MOD_PROBS) return b->res_ml_end;
     return b->res_bytes;
 }
@@ -1541,6 +1565,12 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
         if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "5mC probabilities need a decoded run (FFHIP_RUN_NO_DECODE is set)");
         if (int rc = ensure_mod_block(b)) return rc;
     }
+    b->mv_valid = 0;
+    if (flags & FFHIP_RUN_MOVES) {
+        if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "move table: a flip-flop model only (the run-length model's run records carry dwells)");
+        if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "the move table needs a decoded run (FFHIP_RUN_NO_DECODE is set)");
+        if (int rc = ensure_moves_block(b)) return rc;
+    }
     if (b->packed && !p.packable)
         return set_err(FFHIP_EINVAL, "packed batches take the default path and the launch-per-step kernels only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / unfused flags, ordinary temperature)");
     // A packed batch's launch-per-step run keeps its two fp32 activations in the memory of the two split buffers its default run has (the same size at two
@@ -1841,6 +1871,11 @@ static int run_back(ffhip_batch *b) {
                 b->mod_valid = 1;
                 b->launches[5]++;
             }
+            if (flags & FFHIP_RUN_MOVES) {
+                launch_moves(s, b->path, b->mv_dev, nR, Tb, tbr, rmap);
+                b->mv_valid = 1;
+                b->launches[5]++;
+            }
             if (!(flags & FFHIP_RUN_NO_TRACE)) {
                 launch_trace(s, scores, b->trace, nR, Tb, m->nbase, m->Ps, 1, tbr, rmap);
                 b->launches[5]++;
@@ -1894,7 +1929,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
         const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
         b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
         b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-        b->ran = 1; b->finished = 0; b->paired_last = 0; b->runs_valid = 0; b->mod_valid = 0;
+        b->ran = 1; b->finished = 0; b->paired_last = 0; b->runs_valid = 0; b->mod_valid = 0; b->mv_valid = 0;
         return FFHIP_OK;
     }
     HIP_TRY(hipMemsetAsync(b->bases, 0, n * L, s), FFHIP_EHIP);
@@ -1910,7 +1945,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
     const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
     b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
     b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-    b->ran = 1; b->finished = 0; b->paired_last = 0; b->runs_valid = 0; b->mod_valid = 0;
+    b->ran = 1; b->finished = 0; b->paired_last = 0; b->runs_valid = 0; b->mod_valid = 0; b->mv_valid = 0;
     return FFHIP_OK;
 }
 
@@ -2034,6 +2069,10 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
                 HIP_TRY(hipMemcpyAsync(b->ml_dev + r1, sd->ml_dev + (size_t)k * L, nb1, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
                 memcpy(b->ml_host + r1, sd->ml_host + (size_t)k * L, nb1);
             }
+            if (b->mv_valid && sd->mv_valid) {          // and its move table
+                HIP_TRY(hipMemcpyAsync(b->mv_dev + r1, sd->mv_dev + (size_t)k * L, nb, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                memcpy(b->mv_host + r1, sd->mv_host + (size_t)k * L, nb);
+            }
             memcpy(b->h_bases + r1, sd->h_bases + (size_t)k * L, nb1);
             memcpy(b->h_quals + r1, sd->h_quals + (size_t)k * L, nb1);
             b->h_lens[r] = sd->h_lens[k];
@@ -2144,6 +2183,14 @@ extern "C" int ffhip_batch_mod_probs(const ffhip_batch *b, int read, const uint8
     if (!b->mod_valid || !b->ml_host) return set_err(FFHIP_EINVAL, "5mC probabilities were not made in this run (FFHIP_RUN_MOD_PROBS)");
     *ml = b->ml_host + read_row1(b, read);
     if (length) *length = (size_t)b->h_lens[read];
+    return FFHIP_OK;
+}
+
+extern "C" int ffhip_batch_moves(const ffhip_batch *b, int read, const uint8_t **moves, size_t *nblock) {
+    if (!results_ok(b, read) || !moves) return FFHIP_EINVAL;
+    if (!b->mv_valid || !b->mv_host) return set_err(FFHIP_EINVAL, "the move table was not made in this run (FFHIP_RUN_MOVES)");
+    *moves = b->mv_host + read_row1(b, read);
+    if (nblock) *nblock = (size_t)b->hTb[read];
     return FFHIP_OK;
 }
 

@@ -200,6 +200,8 @@ void launch_assemble(hipStream_t s, const int *path, const float *qpath, char *b
                      int nread, int Tb, int nbase, const int *tbs = nullptr, ReadMap map = ReadMap());
 // 5mC probabilities of the called C / Z bases of a 5-base model (k_mod_probs): one byte a called base at the read's row of the (Tb + 1)-entry buffers
 void launch_mod_probs(hipStream_t s, const float *post, const int *path, uint8_t *ml, int nread, int Tb, int Ps, const int *tbs = nullptr, ReadMap map = ReadMap());
+// move table of the called bases (k_moves): one byte a block at the read's row of the (Tb + 1)-entry buffers, 1 where the block's transition emits a base
+void launch_moves(hipStream_t s, const int *path, uint8_t *moves, int nread, int Tb, const int *tbs = nullptr, ReadMap map = ReadMap());
 // exp + trace_from_posterior
 void launch_trace(hipStream_t s, const float *post, int32_t *trace, int nread, int Tb, int nbase, int Ps, int is_log, const int *tbs = nullptr, ReadMap map = ReadMap());
 void launch_exp_inplace(hipStream_t s, float *x, size_t n);

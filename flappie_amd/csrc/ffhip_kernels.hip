@@ -2350,6 +2350,51 @@ void launch_mod_probs(hipStream_t s, const float *post, const int *path, uint8_t
     if (nread > 0) hipLaunchKernelGGL(k_mod_probs, dim3(nread), dim3(64), 0, s, post, path, ml, Tb, Ps, tbs, map);
 }
 
+// ---- move table of the called bases (FFHIP_RUN_MOVES) ------------------------------------------------------------------------
+// moves[b] = 1 iff b + 1 is one of k_assemble's change positions: 0 <= b <= Tb - 2 and path[b + 1] != path[b]; moves[Tb - 1] = 0 (path[Tb] is never emitted).
+// Element-wise on the path: a lane takes the four blocks of one aligned word of the read's Tb bytes (at the read's row of the (Tb + 1)-entry buffers), reads
+// their four path entries as one 16-byte load and the fifth beside it, and stores the word.  A row does not start on a word in general (rows of Tb + 1
+// entries, packed reads at any block offset), and the word at either end of a read is shared with its neighbour's bytes: the blocks of those two words
+// are written byte by byte by the lanes that hold them.  The path buffer and the byte buffer are both 16-byte aligned, so a word-aligned byte offset is a
+// 16-byte aligned path offset; the load falls back to four scalar ones where a caller's buffers are not.
+constexpr int kMovesThreads = 256;
+__global__ void __launch_bounds__(kMovesThreads)
+k_moves(const int *__restrict__ path, uint8_t *__restrict__ moves, int TbS, const int *__restrict__ tbs, ReadMap map) {
+    FFHIP_DECODE_PRIO_SET();
+    const int Tb = tbs ? tbs[blockIdx.x] : TbS;          // this read's blocks; TbS is the batch's stride
+    if (Tb <= 0) return;                                 // an empty slot writes nothing
+    const size_t r1 = map.row1(blockIdx.x, TbS);
+    const int *pth = path + r1;                          // entries 0 .. Tb
+    uint8_t *out = moves + r1;                           // bytes 0 .. Tb - 1
+    const int lead = (int)((uintptr_t)out & 3);          // bytes of the row's first word that are not this read's
+    for (int b0 = 4 * (int)threadIdx.x - lead; b0 < Tb; b0 += 4 * kMovesThreads) {
+        if (b0 >= 0 && b0 + 4 <= Tb) {                   // a whole word of this read: entries b0 .. b0 + 4 are its own
+            int p[5];
+            if ((((uintptr_t)(pth + b0)) & 15) == 0) {
+                const int4 v = *reinterpret_cast<const int4 *>(pth + b0);
+                p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++) p[i] = pth[b0 + i];
+            }
+            p[4] = pth[b0 + 4];
+            unsigned w = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) w |= (unsigned)(b0 + i < Tb - 1 && p[i + 1] != p[i]) << (8 * i);
+            *reinterpret_cast<unsigned *>(out + b0) = w;
+        } else {
+            for (int i = 0; i < 4; i++) {
+                const int b = b0 + i;
+                if (b >= 0 && b < Tb) out[b] = (uint8_t)(b < Tb - 1 && pth[b + 1] != pth[b]);
+            }
+        }
+    }
+}
+
+void launch_moves(hipStream_t s, const int *path, uint8_t *moves, int nread, int Tb, const int *tbs, ReadMap map) {
+    if (nread > 0) hipLaunchKernelGGL(k_moves, dim3(nread), dim3(kMovesThreads), 0, s, path, moves, Tb, tbs, map);
+}
+
 // ---- trace --------------------------------------------------------------------------------------
 // exp_activation_inplace (layers.c:56-66, cephes exp) followed by trace_from_posterior
 // (decode.c:499-543): column 0 sums block 0 by from-state, column blk+1 sums block blk by to-state.

@@ -642,6 +642,19 @@ extern "C" int ffhip_op_mod_probs(ffhip_engine *eng, ffhip_mat logpost, const in
     return FFHIP_OK;
 }
 
+// move table of one path (k_moves; include/ffhip.h)
+extern "C" int ffhip_op_moves(ffhip_engine *eng, const int *path, size_t nblock, uint8_t *moves) {
+    OP_ENTER(eng);
+    if (!path || !moves || nblock < 1 || nblock > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "bad move table arguments (a path of nblock + 1 entries, nblock >= 1, an output of nblock bytes)");
+    int *d_path = (int *)tmp.upload(path, (nblock + 1) * 4, s);
+    uint8_t *d_mv = (uint8_t *)tmp.get(nblock);
+    if (!d_path || !d_mv) OP_NOMEM();
+    launch_moves(s, d_path, d_mv, 1, (int)nblock, nullptr, ReadMap());
+    HIP_TRY(hipMemcpyAsync(moves, d_mv, nblock, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+
 // ---- decoders of the first run-length head (decode.c:552-892): param is [4 nbase x nblock]
 static bool rl1_dims(const ffhip_mat &param, int *nbase) {
     if (!view_ok(param) || param.nr % 4 != 0 || param.nr / 4 < 1 || param.nr / 4 > 8) return false;

@@ -38,6 +38,7 @@
 #include "../../include/flappie_common.h"
 #include "../../include/flappie_output.h"
 #include "../../include/flappie_modbase.h"
+#include "../../include/flappie_moves.h"
 #include "../../include/networks.h"
 
 const char *argp_program_version = "flappie (MI355X/HIP) 0.1, interface of flappie 2.1.3";
@@ -80,6 +81,7 @@ static struct argp_option options[] = {
     {"run-scale", 22, "A,C,G,T", 0, "With --fasta: per-base factors of the scale parameter (default 1.02,1.04,1.04,1.02, as decode_runnie.py --scale)"},
 #else
     {"modbase-tags", 23, 0, 0, "Report modified bases as SAM MM/ML tags (5mC probabilities made on the GPU): Z is written as C and every C gets a probability (models with a modified base only, e.g. r941_5mC)"},
+    {"emit-moves", 24, 0, 0, "Report where in the signal each base sits: the move table and signal tags of guppy --moves_out / dorado --emit-moves (qs, ns, ts, sm, sd, sv, mv), with the moves made on the GPU. mv is always in signal order: with --reverse SEQ, QUAL and ML are reversed and mv is not"},
 #endif
     {0}
 };
@@ -115,6 +117,7 @@ static struct {
     bool fasta, rlc, run_scale_set;     /* runnie: --fasta, --rlc, --run-scale given */
     double run_scale[4];
     bool modbase_tags;                  /* flappie: --modbase-tags given */
+    bool emit_moves;                    /* flappie: --emit-moves given */
 } args = { 1, 200, 0.0f, NULL, FLAPPIE_OUTFORMAT_FASTQ, 0, DEFAULT_MODEL, NULL, "", false, 1.0f, 200, 10, 100, 0.0f, false, NULL, true, 0, 4, 0, 0, false, false, false, false,
            { 1.02, 1.04, 1.04, 1.02 } };      /* batch 0: by model (below); nshard 0: --shard not given */
 
@@ -224,6 +227,7 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
     }
 #else
     case 23: args.modbase_tags = true; break;
+    case 24: args.emit_moves = true; break;
 #endif
     case ARGP_KEY_NO_ARGS: argp_usage(state); break;
     case ARGP_KEY_ARG:
@@ -360,6 +364,9 @@ typedef struct {
     int prepared;                       /* index into the chunk's ffhip_prep, or -1 */
     char *rle_text;                     /* runnie: the read's records, formatted (runnie.c:282-313); --fasta: its sequence, wrapped */
     uint8_t *ml;                        /* --modbase-tags: the 5mC byte of every called base, aligned with res.basecall (owned) */
+    uint8_t *mv;                        /* --emit-moves: the move byte of every block, in signal order (owned); res.pos holds the block of every base */
+    int mv_stride;                      /* ... the samples a block */
+    float sm, sd;                       /* ... the median and MAD the read was normalised with */
     int rle_nocall;                     /* runnie --fasta: no runs, or a failed run-length estimate (decode_runnie.py: "No basecall returned") */
 } item;
 
@@ -428,9 +435,10 @@ static int batch_run(ffhip_batch *b, unsigned flags) {
     return ffhip_batch_run(b, args.temperature, flags);
 }
 #else
-/* --modbase-tags: the 5mC bytes of the called bases come from the device (FFHIP_RUN_MOD_PROBS) */
+/* --modbase-tags: the 5mC bytes of the called bases come from the device (FFHIP_RUN_MOD_PROBS); --emit-moves: the move table does (FFHIP_RUN_MOVES) */
 static unsigned run_flags(void) {
-    return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u);
+    return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u) |
+           (args.emit_moves ? FFHIP_RUN_MOVES : 0u);
 }
 static int batch_run(ffhip_batch *b, unsigned flags) { return ffhip_batch_run(b, args.temperature, flags); }
 #endif
@@ -676,6 +684,19 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
             if (0 != ffhip_batch_mod_probs(b, i, &ml, &mlen) || mlen != blen) warnx("%s", ffhip_last_error());
             else if (NULL != (its[i]->ml = malloc(blen ? blen : 1))) memcpy(its[i]->ml, ml, blen);
         }
+        if (args.emit_moves) {                                 /* the move table stays in signal order whatever --reverse does to the strings */
+            const uint8_t *mv = NULL;
+            size_t nmv = 0;
+            if (0 != ffhip_batch_moves(b, i, &mv, &nmv) || nmv != nblock) warnx("%s", ffhip_last_error());
+            else if (NULL != (its[i]->mv = malloc(nblock ? nblock : 1))) {
+                memcpy(its[i]->mv, mv, nblock);
+                size_t k = 0;
+                for (size_t blk = 0; r->pos && blk < nblock && k < blen; blk++) if (mv[blk]) r->pos[k++] = (int)blk;      /* the block of base k */
+                its[i]->mv_stride = (int)ffhip_model_stride(mdl);
+                its[i]->sm = its[i]->sd = 0.0f;
+                if (args.delta == 0.0f && 0 != ffhip_prep_stats(prep, idx[i], &its[i]->sm, &its[i]->sd)) warnx("%s", ffhip_last_error());
+            }
+        }
         if (args.reverse) {                                    /* flappie.c:294-297 */
             reverse_char_array(r->basecall, blen);
             reverse_char_array(r->quality, blen);
@@ -824,7 +845,12 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
             const char *base = basename(fn);
             const char *uuid = it->res.rt.uuid ? it->res.rt.uuid : "";
             /* --modbase-tags: Z is written as C here, in the record only -- the trace file below keeps the call as it is */
-            if (args.modbase_tags) {
+            if (args.emit_moves) {
+                if (NULL == it->mv) warnx("No move table for %s", it->filename);
+                else if (args.modbase_tags && NULL == it->ml) warnx("No base-modification probabilities for %s", it->filename);
+                else fprintf_moves_record(args.outformat, args.output, uuid, base, args.uuid, args.prefix, it->res, args.modbase_tags ? it->ml : NULL, it->mv,
+                                          it->mv_stride, it->sm, it->sd, args.delta != 0.0f);
+            } else if (args.modbase_tags) {
                 if (it->ml) fprintf_modbase_record(args.outformat, args.output, uuid, base, args.uuid, args.prefix, it->res, it->ml);
                 else warnx("No base-modification probabilities for %s", it->filename);
             } else {
@@ -841,6 +867,8 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
         }
         free(it->ml);
         it->ml = NULL;
+        free(it->mv);
+        it->mv = NULL;
         free_raw_basecall_info(&it->res);
         free(it->filename);
     }
@@ -1454,6 +1482,12 @@ int main(int argc, char *argv[]) {
     start_reader_procs(&fl, cli_dbg("no_reader_thread") ? 0 : args.readers);      /* before the HIP runtime and libhdf5 are touched here */
     const struct ffhip_model *mdl = flappie_hip_model(args.model);
     if (NULL == mdl) { stop_reader_procs(); errx(EXIT_FAILURE, "model \"%s\" is not available (set FLAPPIE_MODEL_DIR)", flappie_model_string(args.model)); }
+#ifndef BUILD_RUNNIE
+    if (args.emit_moves && ffhip_model_stride(mdl) > 127) {      /* (mv:B:c carries the stride as an int8; no model of the registry has such a stride) */
+        stop_reader_procs();
+        errx(EXIT_FAILURE, "--emit-moves: the stride of model \"%s\" (%zu samples a block) does not fit the mv tag's int8", flappie_model_string(args.model), ffhip_model_stride(mdl));
+    }
+#endif
     struct ffhip_engine *eng = flappie_hip_engine();
     hid_t hdf5out = open_or_create_hdf5(args.trace);
     reader_state rs;

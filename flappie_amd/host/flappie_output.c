@@ -1,13 +1,15 @@
 /*  flappie_output.c -- record formatting (include/flappie_output.h), byte-compatible with
  *  /root/reference/src/flappie_output.c:16-132 (including the SAM record's repeated sequence/quality
- *  line, which the reference emits); and the records with SAMv1 1.7 base-modification tags
- *  (include/flappie_modbase.h).
+ *  line, which the reference emits); the records with SAMv1 1.7 base-modification tags
+ *  (include/flappie_modbase.h); and the records with the move table and signal tags (include/flappie_moves.h).
  */
 #include <err.h>
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/flappie_output.h"
 #include "../../include/flappie_modbase.h"
+#include "../../include/flappie_moves.h"
 
 enum flappie_outformat_type get_outformat(const char *formatstr) {
     if (NULL == formatstr) return FLAPPIE_OUTFORMAT_INVALID;
@@ -127,6 +129,29 @@ static char *modbase_seq(const struct _raw_basecall_info *res, const uint8_t *ml
     return seq;
 }
 
+/* a tagged record: SEQ and `tail` ("\t" + tags) in place of the call and of nothing -- FASTA / FASTQ with the tail in front of the header's newline, SAM as one line */
+static void put_tagged_record(enum flappie_outformat_type outformat, FILE *fp, const char *uuid, const char *readname, bool uuid_primary, const char *prefix,
+                              const struct _raw_basecall_info *res, const char *seq, const char *tail) {
+    switch (outformat) {
+    case FLAPPIE_OUTFORMAT_FASTA:
+        put_header(fp, '>', uuid, readname, uuid_primary, prefix, res, tail);
+        put_string(fp, seq, true);
+        break;
+    case FLAPPIE_OUTFORMAT_FASTQ:
+        put_header(fp, '@', uuid, readname, uuid_primary, prefix, res, tail);
+        put_string(fp, seq, true);
+        fputs("+\n", fp);
+        put_string(fp, res->quality, true);
+        break;
+    case FLAPPIE_OUTFORMAT_SAM:      /* one line: the 11 mandatory fields, then the tags */
+        fprintf(fp, "%s%s\t4\t*\t0\t0\t*\t*\t0\t0\t%s\t%s%s\n", prefix, uuid_primary ? uuid : readname, seq, res->quality ? res->quality : "", tail);
+        break;
+    case FLAPPIE_OUTFORMAT_INVALID: errx(EXIT_FAILURE, "Invalid flappie output %s:%d", __FILE__, __LINE__);
+    default: errx(EXIT_FAILURE, "Flappie enum failure -- report bug\n");
+    }
+    fflush(fp);
+}
+
 void fprintf_modbase_record(enum flappie_outformat_type outformat, FILE *fp, const char *uuid, const char *readname, bool uuid_primary,
                             const char *prefix, const struct _raw_basecall_info res, const uint8_t *ml) {
     if (FLAPPIE_OUTFORMAT_FASTQ == outformat && NULL == res.quality) {
@@ -138,23 +163,67 @@ void fprintf_modbase_record(enum flappie_outformat_type outformat, FILE *fp, con
     char *tail = malloc(strlen(mm) + strlen(mv) + 3);
     if (NULL == tail) errx(EXIT_FAILURE, "out of memory for the base-modification tags of %s", uuid_primary ? uuid : readname);
     sprintf(tail, "\t%s\t%s", mm, mv);
-    switch (outformat) {
-    case FLAPPIE_OUTFORMAT_FASTA:
-        put_header(fp, '>', uuid, readname, uuid_primary, prefix, &res, tail);
-        put_string(fp, seq, true);
-        break;
-    case FLAPPIE_OUTFORMAT_FASTQ:
-        put_header(fp, '@', uuid, readname, uuid_primary, prefix, &res, tail);
-        put_string(fp, seq, true);
-        fputs("+\n", fp);
-        put_string(fp, res.quality, true);
-        break;
-    case FLAPPIE_OUTFORMAT_SAM:      /* one line: the 11 mandatory fields, then the tags */
-        fprintf(fp, "%s%s\t4\t*\t0\t0\t*\t*\t0\t0\t%s\t%s%s\n", prefix, uuid_primary ? uuid : readname, seq, res.quality ? res.quality : "", tail);
-        break;
-    case FLAPPIE_OUTFORMAT_INVALID: errx(EXIT_FAILURE, "Invalid flappie output %s:%d", __FILE__, __LINE__);
-    default: errx(EXIT_FAILURE, "Flappie enum failure -- report bug\n");
-    }
-    fflush(fp);
+    put_tagged_record(outformat, fp, uuid, readname, uuid_primary, prefix, &res, seq, tail);
     free(tail); free(seq); free(mm); free(mv);
+}
+
+/* ---- records with the move table and signal tags (include/flappie_moves.h) ---- */
+double flappie_mean_quality(const char *quality) {
+    if (NULL == quality || 0 == quality[0]) return 0.0;
+    double perr[256], sum = 0.0;         /* 10^(-(Q - 33) / 10) of every character that occurs, computed once */
+    bool have[256] = { false };
+    size_t n = 0;
+    for (const unsigned char *c = (const unsigned char *)quality; *c; c++, n++) {
+        if (!have[*c]) { perr[*c] = pow(10.0, -((double)*c - 33.0) / 10.0); have[*c] = true; }
+        sum += perr[*c];
+    }
+    return -10.0 * log10(sum / (double)n) + 0.0;      /* (+ 0.0: all '!' gives 0, not -0) */
+}
+
+static size_t put_uint(char *dst, size_t v) {
+    char tmp[24];
+    size_t k = 0, n;
+    do { tmp[k++] = (char)('0' + v % 10); v /= 10; } while (v);
+    for (n = 0; n < k; n++) dst[n] = tmp[k - 1 - n];
+    return k;
+}
+
+char *flappie_moves_tags(const uint8_t *moves, size_t nblock, int stride, const raw_table *rt, const char *quality, float median, float mad, bool delta) {
+    if (NULL == rt || stride < 1 || stride > 127 || (nblock > 0 && NULL == moves)) return NULL;
+    size_t b0 = 0;
+    while (b0 < nblock && 0 == moves[b0]) b0++;         /* the first block with a move; nblock: an empty call */
+    char *out = malloc(256 + 2 * (nblock - b0));
+    if (NULL == out) return NULL;
+    size_t a = 0;
+    if (NULL != quality && 0 != quality[0]) a += (size_t)sprintf(out + a, "qs:f:%.3f\t", flappie_mean_quality(quality));
+    memcpy(out + a, "ns:i:", 5); a += 5; a += put_uint(out + a, rt->n);
+    memcpy(out + a, "\tts:i:", 6); a += 6; a += put_uint(out + a, rt->start + (size_t)stride * (b0 < nblock ? b0 : 0));
+    if (!delta) a += (size_t)sprintf(out + a, "\tsm:f:%.9g\tsd:f:%.9g\tsv:Z:med_mad", (double)median, (double)mad);
+    memcpy(out + a, "\tmv:B:c,", 8); a += 8; a += put_uint(out + a, (size_t)stride);
+    for (size_t b = b0; b < nblock; b++) {              /* (digits by hand: a read has thousands of blocks) */
+        out[a++] = ',';
+        out[a++] = moves[b] ? '1' : '0';
+    }
+    out[a] = 0;
+    return out;
+}
+
+void fprintf_moves_record(enum flappie_outformat_type outformat, FILE *fp, const char *uuid, const char *readname, bool uuid_primary, const char *prefix,
+                          const struct _raw_basecall_info res, const uint8_t *ml, const uint8_t *moves, int stride, float median, float mad, bool delta) {
+    if (FLAPPIE_OUTFORMAT_FASTQ == outformat && NULL == res.quality) {
+        warnx("Can't output fastq for reads without quality values");
+        return;
+    }
+    const char *name = uuid_primary ? uuid : readname;
+    char *mm = NULL, *mv = NULL, *seq = NULL;
+    if (NULL != ml) seq = modbase_seq(&res, ml, &mm, &mv);
+    else seq = strdup(res.basecall ? res.basecall : "");
+    char *tags = flappie_moves_tags(moves, res.nblock, stride, &res.rt, res.quality, median, mad, delta);
+    if (NULL == seq || NULL == tags) errx(EXIT_FAILURE, "no move table tags for %s (out of memory, or a stride that does not fit int8)", name);
+    char *tail = malloc((mm ? strlen(mm) + strlen(mv) + 2 : 0) + strlen(tags) + 2);
+    if (NULL == tail) errx(EXIT_FAILURE, "out of memory for the move table tags of %s", name);
+    if (mm) sprintf(tail, "\t%s\t%s\t%s", mm, mv, tags);
+    else sprintf(tail, "\t%s", tags);
+    put_tagged_record(outformat, fp, uuid, readname, uuid_primary, prefix, &res, seq, tail);
+    free(tail); free(tags); free(seq); free(mm); free(mv);
 }

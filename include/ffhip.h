@@ -92,6 +92,10 @@ typedef struct {
  * those of the same run without the flag; under FFHIP_RUN_VITERBI_ONLY the forward-backward pass runs as well (for the probabilities only), and
  * ffhip_batch_get_posterior returns its posterior.  Another model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
 #define FFHIP_RUN_MOD_PROBS   4096u
+/* Move table of a flip-flop model (ffhip_batch_moves below): one byte a block, 1 where the block's transition emits a base of ffhip_batch_basecall, made on the
+ * device from the Viterbi path (k_moves) and brought down in ffhip_batch_finish's one copy of the result block.  Everything else the run returns is that of the same
+ * run without the flag.  The run-length model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
+#define FFHIP_RUN_MOVES       8192u
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -111,6 +115,7 @@ void ffhip_model_free(ffhip_model *mdl);
 size_t ffhip_model_hidden(const ffhip_model *mdl);
 size_t ffhip_model_nparam(const ffhip_model *mdl);       /* nstate * (nbase + 1), rows of `trans` */
 size_t ffhip_model_nbase(const ffhip_model *mdl);
+size_t ffhip_model_stride(const ffhip_model *mdl);       /* samples a block: the product of the convolution strides (5 for the LSTM models, 2 for r941_5mC) */
 size_t ffhip_model_launch_reads(const ffhip_model *mdl);  /* reads per batch that keep every layer launch of this model full on this device (MI355X: 1024 at 256 hidden units, 512 at 384, else 256) */
 size_t ffhip_model_nblock(const ffhip_model *mdl, size_t nsample);   /* iceil chain, layers.c:204 */
 
@@ -353,6 +358,19 @@ int ffhip_op_rle_runs(ffhip_engine *eng, ffhip_mat param, const int *path, const
  *   least; *ncalled: the called bases (bytes written). */
 int ffhip_batch_mod_probs(const ffhip_batch *b, int read, const uint8_t **ml, size_t *length);
 int ffhip_op_mod_probs(ffhip_engine *eng, ffhip_mat logpost, const int *path, uint8_t *ml, size_t *ncalled);
+/* Move table: where in the signal each called base sits (the mv tag of guppy --moves_out / dorado --emit-moves).  For a read of nblock blocks with the path
+ * path[0 .. nblock]:
+ *   move[b] = 1  iff  0 <= b <= nblock - 2 and path[b + 1] != path[b]   (b + 1 is a change position, decode.c:66-79);   move[nblock - 1] = 0 always
+ *   (path[nblock] is never emitted).  Block b is the block whose transition enters the new state -- the block ffhip_op_mod_probs reads (pos - 1), column pos of
+ *   the trace.  The ones number ffhip_batch_basecall's length, and the k-th one in signal order is the k-th character of the call.
+ *   Block b stands for the samples [start + b * stride, start + (b + 1) * stride) of the raw signal, start the first sample the read was called from and
+ *   stride = ffhip_model_stride (the product of the convolution strides: 5 for the LSTM models, 2 for r941_5mC), clipped to the read's end; no centring on
+ *   the convolution window.
+ * ffhip_batch_moves: after ffhip_batch_finish of a run with FFHIP_RUN_MOVES; *moves points at *nblock bytes (0 / 1) owned by the batch.  A run without the
+ *   flag: FFHIP_EINVAL.
+ * ffhip_op_moves: the kernel on one host path of nblock + 1 entries (nblock >= 1); moves: caller-owned, nblock bytes. */
+int ffhip_batch_moves(const ffhip_batch *b, int read, const uint8_t **moves, size_t *nblock);
+int ffhip_op_moves(ffhip_engine *eng, const int *path, size_t nblock, uint8_t *moves);
 int ffhip_runlength_viterbi(ffhip_engine *eng, ffhip_mat param, int *path /* nblock */, float *score);
 /* decoders of the first-generation head on [4 nbase x nblock] matrices: decode_runlength (decode.c:694-767), posterior_runlength
  * (decode.c:793-892; post is [4 nbase x nblock + 1]), runlengths_mean (decode.c:576-603) */

@@ -26,7 +26,7 @@ struct _raw_basecall_info {
     char *basecall, *quality;   /* NUL-terminated, basecall_length characters each       */
     size_t basecall_length;
     flappie_imatrix trace;      /* [nstate x nblock+1] or NULL                           */
-    int *pos;                   /* change positions (unused by the batched driver)       */
+    int *pos;                   /* flappie --emit-moves: the block of every base, signal order (else zeros) */
     size_t nblock;
 };
 
