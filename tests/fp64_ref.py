@@ -1,7 +1,8 @@
-"""Plain float64 restatements of the operations on either side of the recurrent stack: the convolutions with their
-activations, the flip-flop and run-length CRF heads with their global normalisation, and the flip-flop forward-backward
-posterior.  The GPU tests (tests/test_front_head_fp64_gpu.py) hold each kernel to these on the kernel's OWN input, so a
-check does not depend on how the rounding upstream went; tests/test_fp64_ref.py holds these to the oracle and to autograd.
+"""Plain float64 restatements of the network's operations: the convolutions with their activations, one step of the recurrent
+layers (LSTM and GRUmod) from given x(t) and h(t-1), the flip-flop and run-length CRF heads with their global normalisation, and
+the flip-flop forward-backward posterior.  The GPU tests (tests/test_front_head_fp64_gpu.py, tests/test_layers_fp64_gpu.py) hold
+each kernel to these on the kernel's OWN input, so a check does not depend on how the rounding upstream went; tests/test_fp64_ref.py
+and tests/test_layer_step_ref.py hold these to the oracle, to torch and to autograd.
 TEST INFRASTRUCTURE: no code of the product imports this."""
 import numpy as np
 
@@ -196,3 +197,118 @@ def runlength_head(h, W, b, temperature, nbase):
     logz = crf_logz(tr, runlength_map(nbase))
     out[:, 2 * nbase:] = tr - logz / z.shape[0]
     return out, z, cond, logz
+
+
+# ---- recurrent layers, one step at a time ("teacher forced": every step starts from the h(t-1) the code under test wrote) ---
+LOGISTIC_CLAMP = 88.3762626647949      # the reference's exp_ps clamps its argument here: logistic(x <= -clamp) = 4.156e-39, and a NaN goes the same way
+
+
+def logistic64(z):
+    with np.errstate(invalid="ignore"):
+        zc = np.where(np.isnan(z), -LOGISTIC_CLAMP, np.clip(z, -LOGISTIC_CLAMP, LOGISTIC_CLAMP))
+    return 1.0 / (1.0 + np.exp(-zc))
+
+
+def layer_backward(l):
+    """layers 0, 2, 4 of both networks run from the read's end (networks.c:450-489, 539-586)"""
+    return l % 2 == 0
+
+
+def previous_state(h, backward):
+    """h [..., T, H] -> the state every step starts from: h(t-1) (h(t+1) in a backward layer), zero at the read's first step"""
+    hp = np.zeros_like(h)
+    if backward:
+        hp[..., :-1, :] = h[..., 1:, :]
+    else:
+        hp[..., 1:, :] = h[..., :-1, :]
+    return hp
+
+
+def layer_terms(x, hp, iW, sW, b):
+    """x, hp [..., T, H]; iW, sW [G H, H] ([out][in]); b [G H] -> float64 (iW x + b, |iW||x| + |b|, sW h, |sW||h|)"""
+    x64, h64, i64, s64, b64 = (np.asarray(a, dtype=np.float64) for a in (x, hp, iW, sW, b))
+    with np.errstate(invalid="ignore", over="ignore"):
+        zx = x64 @ i64.T + b64
+        cx = np.abs(x64) @ np.abs(i64).T + np.abs(b64)
+        zh = h64 @ s64.T
+        ch = np.abs(h64) @ np.abs(s64).T
+    return zx, cx, zh, ch
+
+
+def _budget(cond, floor):
+    """one unit of pre-activation error: cond 2^-24 (0 where the pre-activation is not finite: its gate is a constant there) + the format's floor"""
+    return np.where(np.isfinite(cond), cond, 0.0) * F32_EPS + floor
+
+
+def _dlogistic(s):
+    return s * (1.0 - s)
+
+
+def grumod_step_ref(x, h, iW, sW, b, backward, floor_x=0.0, floor_h=0.0):
+    """grumod_step (layers.c:664-715) in float64, every step from the given h(t-1): gate order z, r, candidate;
+    hbar = tanh(r (sW h)_c + (iW x)_c + b_c); h' = z h + (1 - z) hbar.  floor_x / floor_h: absolute error floor of the operand
+    format of x / h (0 for fp32 operands).  Returns (expected h, allowance for ONE unit of pre-activation error + the roundings
+    of the gate phase)."""
+    H = sW.shape[1]
+    hp = previous_state(np.asarray(h, dtype=np.float64), backward)
+    zx, cx, zh, ch = layer_terms(x, hp, iW, sW, b)
+    fx = floor_x * np.abs(np.asarray(iW, dtype=np.float64)).sum(axis=1)
+    fh = floor_h * np.abs(np.asarray(sW, dtype=np.float64)).sum(axis=1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        bud = _budget(cx + ch, fx + fh)
+        Z, Rg = logistic64((zx + zh)[..., :H]), logistic64((zx + zh)[..., H:2 * H])
+        dZ = _dlogistic(Z) * bud[..., :H] + 4 * ulp32(Z)
+        dR = _dlogistic(Rg) * bud[..., H:2 * H] + 4 * ulp32(Rg)
+        u, xc = zh[..., 2 * H:], zx[..., 2 * H:]
+        du, dxc = _budget(ch[..., 2 * H:], fh[2 * H:]), _budget(cx[..., 2 * H:], fx[2 * H:])
+        a = Rg * u + xc
+        afin = np.isfinite(a)
+        a0 = np.where(afin, a, 0.0)
+        da = np.abs(u) * dR + Rg * du + dxc + ulp32(np.where(afin, Rg * u, 0.0)) + ulp32(a0)
+        hbar = tanh64(a)
+        dhbar = np.where(afin, dtanh64(a0) * np.where(afin, da, 0.0), 0.0) + act_rounding(hbar, False)
+        want = Z * hp + (1.0 - Z) * hbar
+        allow = np.abs(hp - hbar) * dZ + (1.0 - Z) * dhbar + ulp32(Z * hp) + ulp32((1.0 - Z) * hbar) + ulp32(1.0 - Z) * np.abs(hbar) + ulp32(want)
+    return want, allow
+
+
+def lstm_step_ref(x, h, iW, sW, b, backward, floor_x=0.0, floor_h=0.0):
+    """lstm_step (layers.c:979-1026) in float64, gate order i, f, g, o, the gates of every step from the given h(t-1).  The cell state is
+    not part of the layer's output, so it is carried here, c64(t) = f c64(t-1) + i g, and beside it a first-order running bound e_c(t) on
+    |c - c64| of an evaluation whose pre-activations are off by one unit (cond 2^-24 + floor) and whose gate phase rounds in fp32:
+        e_c(t) = f e_c(t-1) + |c64(t-1)| d_f + |g| d_i + |i| d_g + ulp(f c) + ulp(i g) + ulp(c),   d_gate = |gate'(z)| unit + the gate's own rounding.
+    Returns (expected h = o tanh(c64), its allowance |tanh c| d_o + o tanh'(c) e_c + roundings, c64, e_c)."""
+    H = sW.shape[1]
+    hp = previous_state(np.asarray(h, dtype=np.float64), backward)
+    zx, cx, zh, ch = layer_terms(x, hp, iW, sW, b)
+    fl = floor_x * np.abs(np.asarray(iW, dtype=np.float64)).sum(axis=1) + floor_h * np.abs(np.asarray(sW, dtype=np.float64)).sum(axis=1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        z = zx + zh
+        bud = _budget(cx + ch, fl)
+        gi, gf, go = logistic64(z[..., :H]), logistic64(z[..., H:2 * H]), logistic64(z[..., 3 * H:])
+        zg = z[..., 2 * H:3 * H]
+        gg = tanh64(zg)
+        d_i = _dlogistic(gi) * bud[..., :H] + 4 * ulp32(gi)
+        d_f = _dlogistic(gf) * bud[..., H:2 * H] + 4 * ulp32(gf)
+        d_o = _dlogistic(go) * bud[..., 3 * H:] + 4 * ulp32(go)
+        d_g = np.where(np.isfinite(zg), dtanh64(np.where(np.isfinite(zg), zg, 0.0)), 0.0) * bud[..., 2 * H:3 * H] + act_rounding(gg, False)
+    T = z.shape[-2]
+    c64, e_c = np.zeros_like(gi), np.zeros_like(gi)
+    c, e = np.zeros(gi.shape[:-2] + (H,)), np.zeros(gi.shape[:-2] + (H,))
+    for t in (range(T - 1, -1, -1) if backward else range(T)):
+        f, i, g = gf[..., t, :], gi[..., t, :], gg[..., t, :]
+        cn = f * c + i * g
+        e = f * e + np.abs(c) * d_f[..., t, :] + np.abs(g) * d_i[..., t, :] + np.abs(i) * d_g[..., t, :] + ulp32(f * c) + ulp32(i * g) + ulp32(cn)
+        c = cn
+        c64[..., t, :], e_c[..., t, :] = c, e
+    tc = np.tanh(c64)
+    want = go * tc
+    allow = np.abs(tc) * d_o + go * (1.0 - tc * tc) * e_c + go * act_rounding(tc, False) + ulp32(want)
+    return want, allow, c64, e_c
+
+
+def layer_step_ref(lstm, x, h, iW, sW, b, backward, floor_x=0.0, floor_h=0.0):
+    """(expected h, allowance) of either cell"""
+    if lstm:
+        return lstm_step_ref(x, h, iW, sW, b, backward, floor_x, floor_h)[:2]
+    return grumod_step_ref(x, h, iW, sW, b, backward, floor_x, floor_h)

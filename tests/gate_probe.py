@@ -21,6 +21,47 @@ PROBE_VALUES = np.array([0.0, -0.0, 0.1, -0.1, 0.5, -0.5, 1.0, -1.0, 2.0, -2.0, 
                          1e30, -1e30, np.inf, -np.inf, np.nan], dtype=np.float32)
 
 
+# the layer kernels a run can take, by rnn_path() and run flags (tests/test_gate_levels_gpu.py with probe models, tests/test_layers_fp64_gpu.py with real weights)
+# (kind, H, run flags, reads, rnn path, whether the kernel follows the gate level)
+PATHS = {
+    "split_lstm128": (M.NET_LSTM5, 128, 0, 256, 3, True),
+    "split_lstm256": (M.NET_LSTM5, 256, 0, 520, 3, True),
+    "split_lstm384": (M.NET_LSTM5, 384, 0, 512, 3, True),        # the dense pair form at a full launch
+    "split_lstm512": (M.NET_LSTM5, 512, 0, 256, 3, True),        # k_lstm_split<0, 4, 2>
+    "split_grumod128": (M.NET_GRUMOD5, 128, 0, 256, 3, True),
+    "split_grumod256": (M.NET_GRUMOD5, 256, 0, 520, 3, True),
+    "unfused_lstm256": (M.NET_LSTM5, 256, "UNFUSED", 256, 4, False),       # k_inproj_split + k_rnn_split
+    "unfused_grumod128": (M.NET_GRUMOD5, 128, "UNFUSED", 256, 1, False),   # (no recurrence-only split kernel for GRUmod: k_rnn_persist)
+    "f32_lstm128": (M.NET_LSTM5, 128, "F32", 256, 2, False),               # k_lstm_fused
+    "f32_lstm384": (M.NET_LSTM5, 384, "F32", 256, 2, False),
+    "f32_grumod256": (M.NET_GRUMOD5, 256, "F32", 256, 2, False),
+    "f32_unfused_lstm128": (M.NET_LSTM5, 128, "F32|UNFUSED", 256, 1, False),   # k_rnn_persist
+    "stepwise_lstm128": (M.NET_LSTM5, 128, "STEPWISE", 256, 0, False),
+    "stepwise_grumod128": (M.NET_GRUMOD5, 128, "STEPWISE", 256, 0, False),
+    "small_lstm64": (M.NET_LSTM5, 64, 0, 256, 2, False),                   # the small-H default: k_lstm_fused
+    "small_lstm96": (M.NET_LSTM5, 96, 0, 256, 2, False),
+    "small_lstm36": (M.NET_LSTM5, 36, 0, 256, 2, False),                   # padded to 48 units
+    "small_grumod64": (M.NET_GRUMOD5, 64, 0, 256, 2, False),
+}
+
+
+def run_flags(B, spec):
+    if not spec:
+        return 0
+    names = {"UNFUSED": B.RUN_UNFUSED_RNN, "F32": B.RUN_F32_RNN, "STEPWISE": B.RUN_STEPWISE_RNN, "EXACT": B.RUN_EXACT_GATES,
+             "FAST": B.RUN_FAST_GATES, "FAST2": B.RUN_FAST_GATES2}
+    f = 0
+    for n in spec.split("|"):
+        f |= names[n]
+    return f
+
+
+def read_lengths(kind, nread):
+    """four distinct lengths (samples), ragged over the batch"""
+    base = (1500, 1237, 905, 1496) if kind == M.NET_LSTM5 else (800, 655, 421, 797)
+    return [base[(r * 7) % 4] for r in range(nread)]
+
+
 def probe_model(kind: int, hidden: int, seed: int = 5):
     """synthetic_model(kind, hidden) with zero recurrent-layer weights and biases drawn per unit and gate from PROBE_VALUES"""
     mdl = M.synthetic_model(kind, hidden, seed=seed)

@@ -36,27 +36,7 @@ def engine(B):
     e.close()
 
 
-# (kind, H, run flags, reads, rnn path, whether the kernel follows the gate level)
-PATHS = {
-    "split_lstm128": (M.NET_LSTM5, 128, 0, 256, 3, True),
-    "split_lstm256": (M.NET_LSTM5, 256, 0, 520, 3, True),
-    "split_lstm384": (M.NET_LSTM5, 384, 0, 512, 3, True),        # the dense pair form at a full launch
-    "split_lstm512": (M.NET_LSTM5, 512, 0, 256, 3, True),        # k_lstm_split<0, 4, 2>
-    "split_grumod128": (M.NET_GRUMOD5, 128, 0, 256, 3, True),
-    "split_grumod256": (M.NET_GRUMOD5, 256, 0, 520, 3, True),
-    "unfused_lstm256": (M.NET_LSTM5, 256, "UNFUSED", 256, 4, False),       # k_inproj_split + k_rnn_split
-    "unfused_grumod128": (M.NET_GRUMOD5, 128, "UNFUSED", 256, 1, False),   # (no recurrence-only split kernel for GRUmod: k_rnn_persist)
-    "f32_lstm128": (M.NET_LSTM5, 128, "F32", 256, 2, False),               # k_lstm_fused
-    "f32_lstm384": (M.NET_LSTM5, 384, "F32", 256, 2, False),
-    "f32_grumod256": (M.NET_GRUMOD5, 256, "F32", 256, 2, False),
-    "f32_unfused_lstm128": (M.NET_LSTM5, 128, "F32|UNFUSED", 256, 1, False),   # k_rnn_persist
-    "stepwise_lstm128": (M.NET_LSTM5, 128, "STEPWISE", 256, 0, False),
-    "stepwise_grumod128": (M.NET_GRUMOD5, 128, "STEPWISE", 256, 0, False),
-    "small_lstm64": (M.NET_LSTM5, 64, 0, 256, 2, False),                   # the small-H default: k_lstm_fused
-    "small_lstm96": (M.NET_LSTM5, 96, 0, 256, 2, False),
-    "small_lstm36": (M.NET_LSTM5, 36, 0, 256, 2, False),                   # padded to 48 units
-    "small_grumod64": (M.NET_GRUMOD5, 64, 0, 256, 2, False),
-}
+PATHS = GP.PATHS          # (kind, H, run flags, reads, rnn path, whether the kernel follows the gate level): shared with tests/test_layers_fp64_gpu.py
 
 # (run flags, FFHIP_FAST_GATES, the level that must result)
 SWITCHES = {
@@ -74,21 +54,8 @@ SWITCHES = {
 FULL_MATRIX = ("split_lstm128", "split_grumod128", "f32_lstm128", "small_lstm64")
 
 
-def _flags(B, spec):
-    if not spec:
-        return 0
-    names = {"UNFUSED": B.RUN_UNFUSED_RNN, "F32": B.RUN_F32_RNN, "STEPWISE": B.RUN_STEPWISE_RNN, "EXACT": B.RUN_EXACT_GATES,
-             "FAST": B.RUN_FAST_GATES, "FAST2": B.RUN_FAST_GATES2}
-    f = 0
-    for n in spec.split("|"):
-        f |= names[n]
-    return f
-
-
-def _lengths(kind, nread):
-    """four distinct lengths (samples), ragged over the batch"""
-    base = (1500, 1237, 905, 1496) if kind == M.NET_LSTM5 else (800, 655, 421, 797)
-    return [base[(r * 7) % 4] for r in range(nread)]
+_flags = GP.run_flags
+_lengths = GP.read_lengths
 
 
 _CACHE = {}
