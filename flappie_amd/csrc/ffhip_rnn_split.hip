@@ -187,8 +187,9 @@ __device__ __forceinline__ void wait_vmcnt_upto(int n) {
 // DN ("dense", TS = 2 only): the PAIR form in 128 registers and 77 KiB of LDS, so that TWO such workgroups -- of one launch or of the
 // launches of two batches in flight -- share a CU: four independent 16-read recurrences per CU.  The sweep of h(t-1) lands in
 // LDS (as in the one-tile form at N = 3) one tile after the other through ONE set of accumulators, the recurrent partials are
-// written over the landing zone they came from, the projection partials are single-buffered behind a per-(K quarter, tile)
-// "consumed" flag, and the x waves load x(t+1) (it is L2-warm) in pieces of one (tile, chunk) through two register buffers, the first
+// written over the landing zone they came from, the projection partials are single-buffered -- the x waves keep the partials of step i + 1 in
+// registers across barrier 1 of step i and write them behind it, when every h wave is done with those of step i (round 9; the packed forms
+// still write in front of it, behind a per-(K quarter, tile) "consumed" flag) --, and the x waves load x(t+1) (it is L2-warm) in pieces of one (tile, chunk) through two register buffers, the first
 // piece of the next step in flight across the gate phase (LSTM at N = 3, round 7; the N = 2 dense forms: a whole tile just in time).
 // PACK (GRUmod, H = 256, dense): the cell has three gates, and a unit tile of 4 units x 4 rows carries an empty row per unit -- a quarter of the
 // MFMAs of both products.  Here a member owns 16 units (groups of 16) as THREE gate-major row tiles (z, r, candidate; no empty rows); inside a
@@ -216,7 +217,7 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
     // have its partials in LDS -- a gate chain is twice as long as half a recurrent pass, the h waves then wait at the barrier for it: +11 %.)
     __shared__ v4f px[DN ? 1 : 2][4][TS][NRT][64];     // projection partials, double-buffered (DN: single): [step parity][K quarter][tile of the group][unit tile][lane]
     __shared__ v4f ph_[DN ? 1 : 4][DN ? 1 : TS][DN ? 1 : N][64];        // gate pre-activations by K quarter: projection partial + recurrent partial (DN: in the landing zone)
-    __shared__ int pxc[4][2];               // DN: step (+1) whose projection partial of (K quarter, tile) the h wave has consumed
+    __shared__ int pxc[4][2];               // PACK: step (+1) whose projection partial of (K quarter, tile) the h wave has consumed (the other dense forms write px behind barrier 1: PXB below)
     __shared__ v4f sbias[MT][4];             // bias of my rows: [unit tile][unit in tile] x 4 gates
     __shared__ unsigned short gsl[8][NS][16][4];   // per gate wave: bf16 slices of its tile's h(t), [slice][read][unit]
     __shared__ float gf32[8][16][4];        // per gate wave: fp32 h(t), [read][unit] (last layer's copy for the CRF head)
@@ -228,6 +229,7 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
     // HL: the sweep of h(t-1) LANDS IN LDS (buffer_load ... lds: no destination registers) and feeds the MFMAs through ds_read_b128.
     // The one-tile kernel at N = 3 then fits 128 registers: TWO workgroups -- two independent recurrences -- share a CU.
     constexpr bool HL = (TS == 1 && N == 3) || DN;
+    constexpr bool PXB = DN && !PACK;           // the x waves write px(i + 1) behind barrier 1 of step i; no "consumed" words (see the x waves' dense loop)
     __shared__ v4u hland[HL ? 4 : 1][HL ? TS : 1][HL ? N : 1][NS][64];      // per h wave: its K slice of h(t-1), [tile][chunk][slice][lane]
     // partials of K quarter w for gate tile (ts, j): 64 x 16 B
     auto ph_at = [&](int w, int ts, int j) -> v4f * {
@@ -276,7 +278,7 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
     const bool store_wave = gate_wave || sg_back;            // publishes a tile's h(t)
     const int my_gts = g6 / MT, my_gj = g6 % MT;             // (PACK: my_gj = the component = unit tile of the member)
     if (threadIdx.x < 2) cxflag[threadIdx.x] = 0;
-    if (threadIdx.x < 8) pxc[threadIdx.x >> 1][threadIdx.x & 1] = 0;
+    if constexpr (!PXB) { if (threadIdx.x < 8) pxc[threadIdx.x >> 1][threadIdx.x & 1] = 0; }
     // where quarter-wave q of a gate wave stores slice q of its 4 units x 16 reads: 8 bytes at k = 4*ut .. 4*ut+3
     auto out_off = [&](int gj) { const int ut = ut0 + gj; return (unsigned)((((ut >> 3) * NS + q) * 64 + ((ut & 7) >> 1) * 16 + rl) * 16 + (ut & 1) * 8); };
     auto out_tile = [&](int t, int gts) { return a.hout + ((size_t)t * a.B16 + (rtA + gts)) * tileB; };
@@ -358,14 +360,14 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
     // a per-wave word in LDS (one ds_add_u32 of lane 0, nobody waits for it) and the sums leave the kernel once, at its end -- 256 bytes of LDS, no
     // global traffic in the loop, both workgroups of a CU still resident.  Phase k = the stretch that ENDS at TL(k): 0 loop turn-around, 1 the h waves'
     // hand-off poll, 2 the wave's matrix work (x: loads + projection + flag wait + px; h: sweep + MFMAs + partials), 3 waiting at barrier 1, 4 the gate
-    // phase, 5 waiting at barrier 2.
+    // phase, 5 waiting at barrier 2.  Round 9, x waves of the dense forms: 6 ends behind the last projection MFMA (2 is then the rest up to barrier 1), 7 is the px write behind barrier 1.
     __shared__ unsigned tl_acc[8][8];
     if (threadIdx.x < 64) tl_acc[threadIdx.x >> 3][threadIdx.x & 7] = 0u;
     unsigned tl_prev = (unsigned)__builtin_readcyclecounter();
 #define TL(k) do { const unsigned now_ = (unsigned)__builtin_readcyclecounter(); if (lane == 0) __hip_atomic_fetch_add(&tl_acc[wave][(k)], now_ - tl_prev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); tl_prev = now_; } while (0)
 #elif FFHIP_FORCE_SKEW
     // The test build that shakes the step's interleavings (tools/test_hooks/libffhip_skew.so, tests/test_resweep_gpu.py; round 6): at every phase boundary of every
-    // role's loop -- top of the step, behind the h waves' poll, before / behind barrier 1, behind the gate phase, behind barrier 2 -- one wave in thirteen, rotating
+    // role's loop -- top of the step, behind the h waves' poll, before / behind barrier 1 (behind it: in front of the dense forms' px write), behind that write, behind the gate phase, behind barrier 2 -- one wave in thirteen, rotating
     // with the step, the site, the wave and the group member, sits out ~3000 cycles (a third of a step).  Every flag protocol of the kernel (hand-off sentinels,
     // "consumed" words, the split gate tiles' c(t) flag, LDS landing zones against partial sums) must give the release library's bits with any wave late anywhere.
 #define TL(k) do { if ((((unsigned)i * 5u + (unsigned)(k) * 3u + (unsigned)wave + (unsigned)m) % 13u) == 0u) __builtin_amdgcn_s_sleep(48); } while (0)
@@ -580,7 +582,7 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
     // role's live ranges alone.
     if (xw && DN) {
         // ---- x waves, dense form: per step and tile -- load x(step i+1) of my K quarter (an L2 hit: the group touched these lines three
-        // steps ago), project, wait until h wave kw has taken the previous partial of that tile (it always has), write the new one.
+        // steps ago), project, and write the new partials behind barrier 1 (PACK: in front of it, once h wave kw has taken the previous ones).
         // x comes a whole tile at a time (24 registers) in the N = 2 forms; in pieces (XP below) in the packed forms and at N = 3.
         if constexpr (DN) {
         v4u xb[N][NS];
@@ -593,8 +595,8 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
                 if (cc + 1 < N) __builtin_amdgcn_s_sleep(1);
             }
         };
-        // Both tiles' partials are computed BEFORE the wait for the h wave's "consumed" flags -- those are raised at the end of its
-        // recurrent pass, and a projection of the second tile started only then would stand between the h waves and the barrier.
+        // Both tiles' partials are computed BEFORE anything waits for the h waves (barrier 1; PACK: their "consumed" flags, raised at the end of the
+        // recurrent pass) -- a projection of the second tile started only then would stand between the h waves and the barrier.
         // pieces of the NEXT step that leave behind the last MFMAs of this one, in flight across the gate phase: both where the registers
         // are there (GRUmod: 124), the first one otherwise (the LSTM form spills 9 registers with both)
         constexpr int XPRE = KIND == 1 ? 2 : 1;
@@ -610,8 +612,7 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
 #pragma unroll
             for (int s = 0; s < NS; s++) dst[s] = __builtin_amdgcn_raw_buffer_load_b128(rx, lane_off, ((chunk[cc] * NS + s) * 64) * 16, 0);
         };
-        auto project_step = [&](int i, int want) {           // x(step i) of both tiles -> px[0][kw][*]; want = the step (+1) whose partials must have been consumed (0: none)
-            v4f acc[TS][NRT];
+        auto project_mm = [&](int i, v4f (&acc)[TS][NRT]) {      // x(step i) of both tiles times my input weights -> acc (registers)
             if constexpr (XP) {
                 // x(t) of the four (tile, chunk) pieces through TWO 8-register buffers, the load of piece k + 2 issued behind the MFMAs of piece k: two exposed L2
                 // round trips a step instead of four (the x waves closed every step of this form: the h waves waited 2960 of 11 640 cycles for them,
@@ -653,11 +654,15 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
                 for (int cc = 0; cc < N; cc++) mm6<NRT, N>(wf, cc, xb[cc], acc[ts]);
                 }
             }
+        };
+        auto write_px = [&](const v4f (&acc)[TS][NRT], int want) {      // acc -> px[0][kw][*]; PACK: want = the step (+1) whose partials must have been consumed (0: none)
 #pragma unroll
             for (int ts = 0; ts < TS; ts++) {
                 if (ts >= ntl) continue;
-                if (want > 0)
-                    for (unsigned spin = 0; LDSV(pxc[kw][ts]) != want && 0 == LDSV(lds_abort) && spin < 40000000u; spin++) __builtin_amdgcn_s_sleep(1);
+                if constexpr (PACK) {
+                    if (want > 0)
+                        for (unsigned spin = 0; LDSV(pxc[kw][ts]) != want && 0 == LDSV(lds_abort) && spin < 40000000u; spin++) __builtin_amdgcn_s_sleep(1);
+                }
 #pragma unroll
                 for (int j = 0; j < NRT; j++) px[0][kw][ts][j][lane] = acc[ts][j];
             }
@@ -675,15 +680,67 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
             touched = t;
         };
         if constexpr (XP) { if constexpr (XPRE >= 1) ldq(0, 0, xq[0]); if constexpr (XPRE >= 2) ldq(0, 1, xq[1]); }
-        project_step(0, 0);
+        {
+            v4f acc0[TS][NRT];
+            project_mm(0, acc0);
+            write_px(acc0, 0);
+        }
         touch_x(1);
         sink ^= touched;
         touch_x(2);
         raw_barrier();                                       // px(0) is in LDS before any h wave starts from it
+        if constexpr (PXB) {
+        // px(i + 1) is WRITTEN BEHIND BARRIER 1 (round 9).  px is single-buffered here, and until round 9 the x wave ended its projection with a wait for a
+        // "consumed" word that its h wave raised at the end of its whole recurrent pass (a re-sweep reads px again): the x waves reached barrier 1 a flag round
+        // trip, a poll interval and six ds_write_b128 + lgkmcnt(0) behind the h waves, every step.  Nothing needs px(i + 1) at barrier 1:
+        //   * every h wave finishes its pass over px(i), re-sweeps included, before it ARRIVES at barrier 1 (its reads of px feed the MFMAs it has waited
+        //     for; at step 0 raw_barrier's lgkmcnt(0) stands between the reads and the barrier): px(i) is dead when an x wave is past that barrier;
+        //   * the x wave's raw_barrier() in front of barrier 2 waits lgkmcnt(0): px(i + 1) is in LDS before any h wave starts step i + 1;
+        //   * px is no landing zone of the LDS-DMA path: the DS-path / DMA-path hazard of DESIGN.md section 5.4.1 does not arise.
+        // The accumulators stay in registers across the barrier (as they did while the wave polled) and are dead before the gate arithmetic; the stores go out
+        // at the gate work's priority -- they stand in front of tiles 4 and 5, which are on the step's chain.  No flag words, no store to them in the h waves,
+        // no spin on an LDS word next to the h wave.  An abort is seen by both roles behind barrier 1 of the same step, as before.
         for (int i = 0; i < Tb; i++) {
             TL(0);
             const unsigned lw = live_word(i);
-            if (i + 1 < Tb) project_step(i + 1, i + 1);
+            const bool more = i + 1 < Tb;                    // (the last step does not project)
+            v4f acc[TS][NRT];
+            if (more) project_mm(i + 1, acc);
+            else {                                           // (said, so that no accumulator is carried around the loop -- through the gate phase -- as a maybe-defined value)
+#pragma unroll
+                for (int ts = 0; ts < TS; ts++)
+#pragma unroll
+                    for (int j = 0; j < NRT; j++) acc[ts][j] = (v4f){ 0.f, 0.f, 0.f, 0.f };
+            }
+            TL(6);                                           // (FFHIP_PHASES: the x wave's matrix phase up to here is loads + MFMAs ...
+            sink ^= touched;
+            touch_x(i + WARM);
+            TL(2);                                           // ... and from here to barrier 1 the touch alone)
+            raw_barrier();
+            TL(3);                                           // (FFHIP_FORCE_SKEW: a late x wave between barrier 1 and its px write ...
+            __builtin_amdgcn_s_setprio(3);
+            if (more) write_px(acc, 0);
+            __builtin_amdgcn_sched_barrier(0);               // (the accumulators are dead before the first gate temporary lives: 128 registers)
+            TL(7);                                           // ... and one behind the write, in front of its gate work)
+            const int aborted = LDSV(lds_abort);      // (looked at behind the gate math: see the h waves' loop)
+            if (sg_front) gate_front(i, my_gts, my_gj, c, tb_of(lw));
+            else if (sg_back) gate_back(i, my_gts, my_gj, tb_of(lw));      // (the back half publishes the tile's h(t): as much on the step's chain as the front half; -1.3 % launch time at c2)
+            else if (gate_wave) gate_tile(i, my_gts, my_gj, c, tb_of(lw));
+            __builtin_amdgcn_s_setprio(0);
+            if (aborted) return;
+            TL(4);
+            raw_barrier();                                   // closes the gate phase: px(i + 1) is in LDS behind it
+            TL(5);
+        }
+        } else
+        for (int i = 0; i < Tb; i++) {
+            TL(0);
+            const unsigned lw = live_word(i);
+            if (i + 1 < Tb) {
+                v4f acc[TS][NRT];
+                project_mm(i + 1, acc);
+                write_px(acc, i + 1);
+            }
             sink ^= touched;
             touch_x(i + WARM);
             TL(2);
@@ -1034,9 +1091,12 @@ __device__ __forceinline__ void lstm_split_body(const SplitArgs &a, const int bl
                     }
                     }
                 }
-                // the projection partials of this step are consumed: the x wave of my K quarter may write the next ones
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                if (!PG && lane < 2) LDSV(pxc[kw][lane]) = i + 1;      // (the packed GRUmod form: released at the top of the step)
+                if constexpr (PACK) {
+                    // the projection partials of this step are consumed: the x wave of my K quarter may write the next ones
+                    // (the other dense forms have no such word: their x waves write px behind barrier 1, which this wave reaches with its pass over px done)
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    if (!PG && lane < 2) LDSV(pxc[kw][lane]) = i + 1;      // (the packed GRUmod form: released at the top of the step)
+                }
             } else {
 #pragma unroll
                 for (int ts = 0; ts < TS; ts++) {

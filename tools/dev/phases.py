@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Where a step of the layer kernel goes, per wave role, in the kernel AS IT RUNS IN PRODUCTION (round 5): the -DFFHIP_PHASES variant of libffhip.so
 (tools/dev/build_variants.sh phases="-DFFHIP_PHASES", copied over the tree's library by the caller) adds the time between its stamps to per-wave words
-in LDS and hands the sums out at the end of each launch.  usage: tools/dev/phases.py [config=c2|h256|c4|h512] [pairs=6] [serial]   (serial: one batch at a time, run + finish -- a launch alone on the chip)"""
+in LDS and hands the sums out at the end of each launch.  Round 9: the x waves of the dense forms stamp twice more -- "x:mm" ends behind their last projection
+MFMA (loads + MFMAs; "matrix" is then what lies between that stamp and their arrival at barrier 1), "x:px" is their write of px behind barrier 1.  usage: tools/dev/phases.py [config=c2|h256|c4|h512] [pairs=6] [serial]   (serial: one batch at a time, run + finish -- a launch alone on the chip)"""
 import ctypes as C
 import os
 import sys
@@ -44,12 +45,12 @@ for rnd in range(rounds + 1):
 L.ffhip_debug_phases(buf, 0)
 v = np.array(list(buf), dtype=np.float64)
 cyc, steps = v[:64].reshape(8, 8), v[64:72]
-names = ["turn", "poll", "matrix", "bar1", "gates", "bar2"]
+names = ["turn", "poll", "matrix", "bar1", "gates", "bar2", "x:mm", "x:px"]
 print("config %s: cycles per step by wave (mean over workgroups and steps; counter ticks)  -- waves 0-3 x, 4-7 h" % cfg)
 print("wave  " + "".join("%9s" % n for n in names) + "    total")
 for w in range(8):
     if steps[w] > 0:
-        per = cyc[w, :6] / steps[w]
+        per = cyc[w, :8] / steps[w]
         print("%4d  " % w + "".join("%9.0f" % x for x in per) + "%9.0f" % per.sum())
 for b in bs:
     b.close()
