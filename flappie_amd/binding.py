@@ -184,6 +184,21 @@ def lib():
     return L
 
 
+SPLIT_FORMS = ("one_tile", "pair_tiles", "dense3", "dense256", "pack", "none")
+
+
+def split_plan(kind: int, hidden: int, remaining: int, ncu: int, beside: int) -> dict:
+    """ffhip_debug_split_plan: the layer launch the split-operand kernels take for `remaining` read tiles of a batch (no device, no engine; reads FFHIP_DEBUG)"""
+    out = (C.c_int * 6)()
+    _check(lib().ffhip_debug_split_plan(C.c_int(kind), C.c_int(hidden), C.c_int(remaining), C.c_int(ncu), C.c_int(beside), out))
+    return {"form": SPLIT_FORMS[out[0]], "nrt": out[1], "ts": out[2], "workgroups": out[3], "per_cu": out[4], "fills_chip": out[5]}
+
+
+def split_pair_ok(kind: int, hidden: int, nrt: int, ncu: int) -> int:
+    """ffhip_debug_split_pair_ok: two batches of nrt read tiles each may share paired layer launches (no device, no engine; reads FFHIP_DEBUG)"""
+    return int(lib().ffhip_debug_split_pair_ok(C.c_int(kind), C.c_int(hidden), C.c_int(nrt), C.c_int(ncu)))
+
+
 def _check(rc: int):
     if rc != 0:
         raise FFHipError("ffhip error %d: %s" % (rc, lib().ffhip_last_error().decode()))

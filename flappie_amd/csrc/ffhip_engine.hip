@@ -597,12 +597,12 @@ extern "C" size_t ffhip_model_nparam(const ffhip_model *m) { return m ? (size_t)
 extern "C" size_t ffhip_model_nbase(const ffhip_model *m) { return m ? (size_t)m->nbase : 0; }
 extern "C" size_t ffhip_model_stride(const ffhip_model *m) { size_t st = m ? 1 : 0; for (int l = 0; m && l < m->nconv; l++) st *= (size_t)m->conv[l].stride; return st; }
 // reads one FULL layer launch of this model takes on this device (the batch size that keeps every launch full): 1024 at 256 hidden units (the
-// packed forms), 512 at 384, else 256 -- on 256 CUs (ffhip_rnn_split.hip, split_next_launch_tiles)
+// packed forms), 512 at 384, else 256 -- on 256 CUs (ffhip_rnn_split.hip, split_plan)
 // (a device with fewer than 32 CUs -- none exists in this family -- still gets a unit of 1: the layer loop must advance)
 extern "C" size_t ffhip_model_launch_reads(const ffhip_model *m) {
     if (!m) return 0;
     const int ncu = m->eng->prop.multiProcessorCount;
-    if (m->H == m->Hp && split_supported(m->cell, m->Hp) && m->rnn[0].Wsplit != nullptr) return (size_t)16 * split_next_launch_tiles(m->cell, m->Hp, 1 << 20, ncu);
+    if (m->H == m->Hp && split_supported(m->cell, m->Hp) && m->rnn[0].Wsplit != nullptr) return (size_t)16 * split_plan(m->cell, m->Hp, 1 << 20, ncu, 0).nrt;
     return (size_t)16 * 2 * std::max(1, ncu / 32);
 }
 extern "C" size_t ffhip_model_nblock(const ffhip_model *m, size_t nsample) {
@@ -1527,6 +1527,22 @@ static int layer_launched(ffhip_engine *e, hipStream_t s, bool chain) {
     return FFHIP_OK;
 }
 
+// another batch is between run and finish: its layer launches are on the chip
+static int other_in_flight(const ffhip_batch *b) { return b->eng->in_flight - (b->counted ? 1 : 0) > 0 ? 1 : 0; }
+
+// What layer l of batch b brings to a launch of its read tiles rt0 .. rt0 + nrt - 1 on the split-operand kernels, with the launch's epoch (the check-in words carry it:
+// no fill between launches); cur: which of actS[] / fa[] holds the layer's input.  The output doubles as the hand-off flag; the kernel arms it itself a few steps
+// ahead of its stores -- no fill.  The fp32 copy of a layer's output is needed by the f32 CRF head (last layer) and by FFHIP_RUN_KEEP_ACTS.
+// (One helper for run_layers and ffhip_batch_run_pair: a paired run is a split run without kept activations -- ModelPath::pairable -- whose fa[] is act[].)
+static SplitLaunch layer_split_launch(ffhip_batch *b, int l, int cur, int rt0, int nrt) {
+    const RnnDev &r = b->mdl->rnn[l];
+    const RunPath &p = b->run_path;
+    b->split_epoch = (b->split_epoch % 0x3FFFFFFu) + 1u;
+    return SplitLaunch{ r.Wsplit, r.bias, b->actS[cur], b->actS[cur ^ 1], ((l == 4 && !p.split_head) || p.keep) ? b->fa[cur ^ 1] : nullptr, b->pflags, b->pabort,
+                        b->Tb, b->B16, rt0, nrt, (l % 2 == 0) ? 1 : 0, p.persist_mode, r.split_S, p.gates,
+                        b->ragged ? b->d_tbs : nullptr, b->ragged ? b->d_tbt : nullptr, b->split_epoch, b->packed ? b->d_live : nullptr };
+}
+
 // FFHIP_RUN_KEEP_ACTS: the fp32 activations after the convolutions (slot 0) and after every layer
 static int keep_copy(ffhip_batch *b, int slot, const float *src) {
     if (!b->run_path.keep) return FFHIP_OK;
@@ -1596,12 +1612,8 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
     // launches of whatever else is in flight do too, the convolution only ever shares the chip with other batches' convolutions and
     // decodes, and the fat shape is the faster one there (in pairs at H = 384: 0.98 -> 0.6 ms per batch)
     bool full_chip = paired || p.split2;
-    if (p.split && !full_chip) {
-        const int beside_ = (eng->in_flight - (b->counted ? 1 : 0) > 0) ? 1 : 0;
-        const int nrt_ = split_next_launch_tiles(m->cell, Hp, B16, ncu);
-        full_chip = 2 * split_launch_workgroups(m->cell, Hp, nrt_, ncu, beside_) > ncu * split_workgroups_per_cu(m->cell, Hp, nrt_, ncu, beside_);
-    }
-    const int lean_conv = !full_chip && eng->in_flight - (b->counted ? 1 : 0) > 0;
+    if (p.split && !full_chip) full_chip = split_plan(m->cell, Hp, B16, ncu, other_in_flight(b)).fills_chip;
+    const int lean_conv = !full_chip && other_in_flight(b);
     // Whole batches one after the other when this batch's layer launches fill the chip and it is not half of a pair: its convolutions
     // would otherwise run beside the other batch's layer launches, whose workgroups then wait for slots (h256 with two 768-read batches
     // in flight: 160 against 179 Msamples/s one at a time; c4: 65.5 against 75).  The host side still overlaps: this only orders the GPU.
@@ -1702,7 +1714,7 @@ static int run_layers(ffhip_batch *b) {
             launch_inproj_split(s, b->actS[cur], b->xa, r.Wsplit, r.bias, Tb * B16, Hp, r.split_S);
             b->launches[1]++;
             if (prof) hipEventRecord(b->lev[l][1], s);
-            const int maxt = split_max_tiles(ncu);
+            const int maxt = rnn_split_max_tiles(ncu);
             float *out_f32 = (l == 4 || p.keep) ? out : nullptr;
             for (int rt0 = 0; rt0 < B16; rt0 += maxt) {
                 const int nrt = (B16 - rt0 < maxt) ? B16 - rt0 : maxt;
@@ -1716,25 +1728,17 @@ static int run_layers(ffhip_batch *b) {
                 b->launches[2]++;
             }
         } else if (p.split) {
-            void *outS = b->actS[cur ^ 1];
-            // (the output doubles as the hand-off flag; the kernel arms it itself a few steps ahead of its stores -- no fill)
-            // the fp32 copy of a layer's output is needed by the CRF head (last layer) and by FFHIP_RUN_KEEP_ACTS
-            float *out_f32 = ((l == 4 && !p.split_head) || p.keep) ? out : nullptr;
-            for (int rt0 = 0, nrt = 0; rt0 < B16; rt0 += nrt) {
-                nrt = split_next_launch_tiles(m->cell, Hp, B16 - rt0, ncu);
-                // (the check-in words carry the launch's epoch: no fill between launches)
-                b->split_epoch = (b->split_epoch % 0x3FFFFFFu) + 1u;
+            for (int rt0 = 0; rt0 < B16;) {
                 // another batch is between run and finish: at H = 384 this batch's launches take the dense form, which fits beside that batch's;
-                // two such launches run beside each other only if ALL their workgroups fit on the chip together
-                const int beside = (eng->in_flight - (b->counted ? 1 : 0) > 0) ? 1 : 0;
-                const bool chain = 2 * split_launch_workgroups(m->cell, Hp, nrt, ncu, beside) > ncu * split_workgroups_per_cu(m->cell, Hp, nrt, ncu, beside);
-                if (int rc = layer_wait(eng, s, chain)) return rc;
+                // two such launches run beside each other only if ALL their workgroups fit on the chip together (SplitPlan::fills_chip)
+                const SplitPlan sp = split_plan(m->cell, Hp, B16 - rt0, ncu, other_in_flight(b));
+                const SplitLaunch sl = layer_split_launch(b, l, cur, rt0, sp.nrt);
+                if (int rc = layer_wait(eng, s, sp.fills_chip)) return rc;
                 if (prof && rt0 == 0) hipEventRecord(b->lev[l][1], s);      // behind the wait: the layer's time is its kernels', not the other batch's
-                if (!launch_lstm_split(s, m->cell, r.Wsplit, r.bias, b->actS[cur], outS, out_f32, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt,
-                                       backward, p.persist_mode, r.split_S, p.gates, tbs, tbt, ncu, b->split_epoch, beside, live))
-                    return set_err(FFHIP_EINVAL, "split recurrent kernel: unsupported shape");
-                if (int rc = layer_launched(eng, s, chain)) return rc;
+                if (!launch_lstm_split(s, m->cell, Hp, sl, sp)) return set_err(FFHIP_EINVAL, "split recurrent kernel: unsupported shape");
+                if (int rc = layer_launched(eng, s, sp.fills_chip)) return rc;
                 b->launches[2]++;
+                rt0 += sp.nrt;
             }
         } else if (p.persist) {
             const bool fuse = p.fused;
@@ -1974,19 +1978,9 @@ extern "C" int ffhip_batch_run_pair(ffhip_batch *b0, ffhip_batch *b1, float temp
     HIP_TRY(hipEventRecord(b1->pair_ev, b1->stream), FFHIP_EHIP);
     HIP_TRY(hipStreamWaitEvent(s, b1->pair_ev, 0), FFHIP_EHIP);              // the second batch's convolutions are done before the first paired layer
     const bool prof = eng->profiling != 0;
-    const RunPath &p = b0->run_path;                                              // (b1's is the same: same model, flags and temperature)
-    ffhip_batch *bb[2] = { b0, b1 };
+    ffhip_batch *bb[2] = { b0, b1 };                                               // (their run paths are the same: same model, flags and temperature)
     for (int l = 0; l < 5; l++) {
-        const RnnDev &r = m->rnn[l];
-        SplitLaunch sl[2];
-        for (int k = 0; k < 2; k++) {
-            ffhip_batch *b = bb[k];
-            const int cur = b->run_cur;
-            b->split_epoch = (b->split_epoch % 0x3FFFFFFu) + 1u;
-            sl[k] = SplitLaunch{ r.Wsplit, r.bias, b->actS[cur], b->actS[cur ^ 1], (l == 4 && !p.split_head) ? b->act[cur ^ 1] : nullptr, b->pflags, b->pabort,
-                                 b->Tb, b->B16, 0, b->B16, (l % 2 == 0) ? 1 : 0, p.persist_mode, r.split_S, p.gates,
-                                 b->ragged ? b->d_tbs : nullptr, b->ragged ? b->d_tbt : nullptr, b->split_epoch, b->packed ? b->d_live : nullptr };
-        }
+        const SplitLaunch sl[2] = { layer_split_launch(b0, l, b0->run_cur, 0, b0->B16), layer_split_launch(b1, l, b1->run_cur, 0, b1->B16) };
         if (prof) hipEventRecord(b0->lev[l][1], s);
         if (int rc = layer_wait(eng, s, true)) return rc;      // a paired launch fills the chip: after any other layer launch
         if (!launch_lstm_split_pair(s, m->cell, m->Hp, eng->prop.multiProcessorCount, sl[0], sl[1]))
@@ -2323,6 +2317,14 @@ extern "C" int ffhip_debug_batch_head_input(ffhip_batch *b, int row, float *out)
 
 extern "C" int ffhip_debug_fallback_count(const ffhip_engine *eng) { return eng ? eng->fallbacks : -1; }
 extern "C" size_t ffhip_debug_batch_device_bytes(const ffhip_batch *b) { return b ? b->dev_bytes : 0; }
+extern "C" int ffhip_debug_split_plan(int kind, int hidden, int remaining, int ncu, int beside, int out[6]) {
+    if (!out) return set_err(FFHIP_EINVAL, "ffhip_debug_split_plan: out is NULL");
+    const SplitPlan p = split_plan(kind, hidden, remaining, ncu, beside);
+    const int v[6] = { (int)p.form, p.nrt, p.ts, p.workgroups, p.per_cu, p.fills_chip ? 1 : 0 };
+    memcpy(out, v, sizeof(v));
+    return FFHIP_OK;
+}
+extern "C" int ffhip_debug_split_pair_ok(int kind, int hidden, int nrt, int ncu) { return split_pair_ok(kind, hidden, nrt, ncu) ? 1 : 0; }
 
 // development counter next to the abort word (e.g. re-sweeps of the split layer kernel in builds that count them)
 extern "C" unsigned ffhip_debug_batch_counter(ffhip_batch *b) {

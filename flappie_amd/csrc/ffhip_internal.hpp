@@ -110,32 +110,40 @@ bool launch_lstm_fused(hipStream_t s, int kind, const float4 *sWp, const float4 
                        const int *tbs = nullptr, const int *tbt = nullptr);
 int persist_blocks_per_cu(int kind, int H);
 
-// persistent LSTM layer on bf16 MFMAs over three-way split operands (ffhip_rnn_split.hip): fp32-exact products at 2.7x
-// the f32 MFMA rate.  Activations in the SPLIT layout A[t][rt][k/32][slice 0..2][lane][8 bf16] (6 bytes per value).
+// persistent recurrent layer on 16-bit MFMAs over split operands (ffhip_rnn_split.hip, format in ffhip_split.hpp): two fp16 slices a value, three products
+// kept -- the accuracy of fp32 arithmetic at three matrix instructions a multiply-add block.  Activations in the SPLIT layout
+// A[t][rt][k/32][slice][lane][8 x 16 bit]: 4 bytes a value (-DFFHIP_SPLIT_BF16X3, the cross-check build: three bf16 slices, six products, 6 bytes).
 void launch_gather_rows(hipStream_t s, const float *const *src, const int *lens, float *dst, size_t row_stride, int nrow, const long long *dst_off = nullptr);
 // packed batches: the strided convolution's window table / the layer kernels' live mask from per-read records (ffhip_kernels.hip)
 void launch_pack_conv_table(hipStream_t s, const int4 *reads, int nread, int maxcols, int winlen, int stride, int Tmax, int *x0a, int *x0b, unsigned *overflow);
 void launch_pack_live(hipStream_t s, const int4 *reads, int nread, int maxblocks, int B16, unsigned *live);
 bool split_supported(int kind, int H);
-int split_launch_workgroups(int kind, int H, int nrt, int ncu, int beside);      // workgroups of one launch of nrt read tiles ...
-int split_workgroups_per_cu(int kind, int H, int nrt, int ncu, int beside);      // ... and how many of them share a CU
-int split_next_launch_tiles(int kind, int H, int remaining, int ncu);          // read tiles the next layer launch of a batch takes
-int split_max_tiles(int ncu, int H = 512);                // read tiles (of 16) per launch: 32 workgroups per PAIR of tiles, one per CU (two at H <= 256)
+// One layer launch of the split-operand kernels, decided in one place (split_plan): the kernel form, the read tiles it takes of the `remaining` ones of a
+// batch, its grid, and whether it fills the chip.  `beside`: another batch is between run and finish.
+enum SplitForm { kSplitOneTile, kSplitPairTiles, kSplitDense3, kSplitDense256, kSplitPack, kSplitNone };
+// kSplitNone: no layer kernel for (kind, H).  For a kind 0 / 1 and an H of 128 .. 512 without one (GRUmod at 512) the other fields are still filled, with what a pair-form
+// launch there would be -- the rules split_plan replaced answered for those shapes too, and tests/golden/split_plan_table.json holds their answers; all zero otherwise.
+struct SplitPlan {
+    SplitForm form;
+    int nrt;                          // read tiles (of 16) this launch takes
+    int ts, workgroups, per_cu;       // tiles a group, grid size, workgroups of this kernel that share a CU
+    bool fills_chip;                  // 2 * workgroups > ncu * per_cu: a second such launch is not co-resident with this one
+};
+SplitPlan split_plan(int kind, int H, int remaining, int ncu, int beside);
 size_t split_flag_words(int nrt);
 size_t split_pack_offset(int H);           // 16-byte pieces in front of the gate-major weight pack of the packed GRUmod form
 inline size_t split_bytes(size_t ntile, int H) { return ntile * (size_t)H * 32 * kSplitNS; }      // 16 reads x H x 2 B x slices
-struct SplitLaunch {          // one batch's share of a paired layer launch
+struct SplitLaunch {          // one batch's buffers and counts of a layer launch (scale_exp: the exponent S both products carry)
     const void *Wp; const float *bias; const void *xin; void *hout; float *hout_f32; unsigned *flags, *abort_word;
     int Tb, B16, rt0, nrt, backward, mode, scale_exp, fast_gates; const int *tbs, *tbt; unsigned epoch;
     const unsigned *live = nullptr;      // packed batch: bit r of word [t][read tile] = slot r holds a block of a read at step t (ffhip_rnn_split.hip SplitArgs)
 };
 bool split_pair_ok(int kind, int H, int nrt, int ncu);      // two batches of nrt read tiles each can share a layer launch: what launch_lstm_split_pair takes
 bool launch_lstm_split_pair(hipStream_t s, int kind, int H, int ncu, const SplitLaunch &p0, const SplitLaunch &p1);
-bool launch_lstm_split(hipStream_t s, int kind, const void *Wp, const float *bias, const void *xin, void *hout, float *hout_f32,
-                       unsigned *flags, unsigned *abort_word, int Tb, int B16, int H, int rt0, int nrt, int backward, int mode,
-                       int scale_exp, int fast_gates, const int *tbs, const int *tbt, int ncu, unsigned epoch, int beside, const unsigned *live = nullptr);      // scale_exp: the exponent S both products carry; live: packed batch (SplitLaunch)
+bool launch_lstm_split(hipStream_t s, int kind, int H, const SplitLaunch &l, const SplitPlan &p);      // l.nrt == p.nrt; false: kSplitNone
 // recurrence-only layer kernel on split operands behind launch_inproj_split (LSTM, H = 256 / 512): xa as from launch_inproj_split
 bool rnn_split_supported(int kind, int H);
+int rnn_split_max_tiles(int ncu);      // read tiles (of 16) a launch takes: 32 workgroups per PAIR of tiles, one per CU
 bool launch_rnn_split(hipStream_t s, const void *Wsplit, const float *xa, void *hout, float *hout_f32, unsigned *flags, unsigned *abort_word,
                       int Tb, int B16, int H, int rt0, int nrt, int backward, int mode, int scale_exp, const int *tbs = nullptr, const int *tbt = nullptr);
 // input projection GEMM on split operands: in_split = activations in the split layout, Wp = the split weight pack (its first

@@ -53,6 +53,7 @@
 #include "ffhip_math.hpp"
 #include "ffhip_split.hpp"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace ffhip {
 
@@ -1377,6 +1378,7 @@ k_rnn_split(RnnSplitArgs a) {
 }
 
 bool rnn_split_supported(int kind, int H) { return kind == 0 && (H == 256 || H == 512); }
+int rnn_split_max_tiles(int ncu) { return 2 * (ncu / 32); }
 bool launch_rnn_split(hipStream_t s, const void *Wsplit, const float *xa, void *hout, float *hout_f32, unsigned *flags, unsigned *abort_word,
                       int Tb, int B16, int H, int rt0, int nrt, int backward, int mode, int scale_exp, const int *tbs, const int *tbt) {
     RnnSplitArgs a;
@@ -1604,77 +1606,75 @@ void launch_gate_math(hipStream_t s, int form, const float *x, float *out, size_
 // ---- host side ---------------------------------------------------------------------------------
 // largest H / 128 whose two weight matrices fit one CU's registers: 16N rows x 256N k x 2 B x slices per CU
 // (three bf16 slices: 221 KiB at N = 3; two fp16 slices: 147 KiB at N = 3, 256 KiB at N = 4; the file holds 512 KiB)
-#ifdef FFHIP_SPLIT_BF16X3
-constexpr int kSplitMaxN = 3;
-#else
-constexpr int kSplitMaxN = 4;
-#endif
+constexpr int kSplitMaxN = kSplitF16 ? 4 : 3;
 // tiles per group by [kind][H / 128 - 1] (measured on MI355X)
 // 256 reads x 4000 samples, MI355X, Msamples/s TS = 2 -> 1: LSTM H = 256 97.4 -> 106.6, GRUmod H = 256 39.4 -> 44.3; at N = 3 the
 // one-tile form needs 161 registers (33 spilled at 128: 77.6 -> 67.5), at N = 4 it is hopeless (102 spilled)
 constexpr int kSplitTS[2][4] = { { 1, 1, 1, 2 }, { 1, 1, 2, 2 } };
-int split_tiles_per_group(int kind, int H);
 bool split_supported(int kind, int H) { return (kind == 0 || kind == 1) && H % 128 == 0 && H >= 128 && H <= 128 * (kind == 0 ? kSplitMaxN : 3); }      // GRUmod at N = 4 spills 169 registers; no GRUmod model is that wide
-// read tiles (of 16) one launch takes: 32 workgroups per group; one workgroup per CU and a pair of tiles per group, or two
-// workgroups per CU and one tile per group -- 2 * (ncu / 32) tiles either way
-// At H <= 256 the pair form also fits two workgroups per CU (<= 128 VGPRs, 53 KiB LDS): a launch then takes 4 * (ncu / 32) tiles --
-// 512 reads on 256 CUs, four independent 16-read recurrences per CU.  The step of this kernel is a latency chain (hand-off through
-// L2, sweep, gate math), so the reads in flight per launch are what sets its throughput.
-// H = 384 (LSTM): the dense pair form k_lstm_split<0, 3, 2, true> -- 128 registers, 77 KiB of LDS, two workgroups per CU: a launch takes
-// 512 reads, and the launches of two 256-read batches in flight run BESIDE each other instead of one after the other
-// (FFHIP_DEBUG=no_dense: no launch takes a dense form, paired launches included)
-static bool split_dense3(int kind, int H) { return kind == 0 && H == 384 && kSplitF16 && !dbg("no_dense"); }
-// H = 256 (LSTM and GRUmod): the dense pair form needs 79 registers and 53 KiB there -- THREE workgroups per CU, six 16-read recurrences,
-// 768 reads per launch
-static bool split_dense256(int H) { return H == 256 && kSplitF16 && !dbg("no_dense"); }
-// H = 256: the packed forms (lstm_split_body's PACK; k_grumod_pack, k_lstm_pack) -- 16 members a group, 128 registers, two workgroups a CU: a
-// FULL launch takes 8 * (ncu / 32) tiles, 1024 reads on 256 CUs; their weights are the second half of the layer's pack (FFHIP_NO_PACK: never)
-static bool split_pack256(int kind, int H) { return (kind == 0 || kind == 1) && split_dense256(H) && !dbg("no_pack"); }
-static bool split_launch_pack(int kind, int H, int nrt, int ncu) { return split_pack256(kind, H) && nrt == 8 * (ncu / 32); }
-int split_max_tiles(int ncu, int H) {
-    if (split_dense256(H)) return 6 * (ncu / 32);
-    return ((H <= 256 || split_dense3(0, H)) && !dbg("no_dense") ? 4 : 2) * (ncu / 32);
+
+// The forms a layer launch can take, and what split_plan and split_pair_ok below decide from (kind, H, ncu) and FFHIP_DEBUG:
+//  one-tile, pair   k_lstm_split<KIND, N, TS>: 32 workgroups a group of TS read tiles; one workgroup per CU and a pair of tiles per group, or two workgroups per CU and
+//                   one tile per group -- 2 * (ncu / 32) tiles a launch either way.  At H <= 256 the pair form also fits two workgroups per CU (<= 128 VGPRs, 53 KiB
+//                   LDS): a launch then takes 4 * (ncu / 32) tiles -- 512 reads on 256 CUs, four independent 16-read recurrences per CU.  The step of this kernel is a
+//                   latency chain (hand-off through L2, sweep, gate math), so the reads in flight per launch are what sets its throughput.
+//  dense, H = 384   (LSTM) k_lstm_split<0, 3, 2, true> -- 128 registers, 77 KiB of LDS, two workgroups per CU: a launch takes 512 reads, and the launches of two 256-read
+//                   batches in flight run BESIDE each other instead of one after the other
+//  dense, H = 256   (LSTM and GRUmod) the dense pair form needs 79 registers and 53 KiB there -- THREE workgroups per CU, six 16-read recurrences, 768 reads per launch
+//  packed, H = 256  (lstm_split_body's PACK; k_grumod_pack, k_lstm_pack) 16 members a group, 128 registers, two workgroups a CU: a FULL launch takes 8 * (ncu / 32)
+//                   tiles, 1024 reads on 256 CUs; their weights are the second half of the layer's pack
+//  paired           k_lstm_split_pair, the dense form at H = 384 with the tiles of two batches in one grid (split_pair_ok)
+// FFHIP_DEBUG=no_dense: no launch takes a dense or packed form, paired launches included; no_pack: none a packed form; no_pair: no paired launches.
+// The three-slice build (kSplitF16 false) has the one-tile and pair forms up to H = 384 only.
+static bool split_dense3(int kind, int H, bool no_dense) { return kSplitF16 && !no_dense && kind == 0 && H == 384; }
+struct SplitRules {
+    bool wide, dense3, dense256, pack;      // launches of four tiles a unit exist; the dense form at H = 384 / at H = 256 / the packed forms do
+    SplitRules(int kind, int H) {
+        const bool no_dense = dbg("no_dense") != nullptr, dense = kSplitF16 && !no_dense;
+        dense3 = split_dense3(kind, H, no_dense);
+        dense256 = dense && H == 256;
+        pack = dense256 && (kind == 0 || kind == 1) && !dbg("no_pack");
+        wide = !no_dense && (H <= 256 || (kSplitF16 && H == 384));      // (H = 384: either kind -- GRUmod's four tiles a unit go as pair groups, one workgroup a CU, half of them at a time)
+    }
+};
+
+SplitPlan split_plan(int kind, int H, int remaining, int ncu, int beside) {
+    SplitPlan p = { kSplitNone, 0, 0, 0, 0, false };
+    if ((kind != 0 && kind != 1) || H % 128 != 0 || H < 128 || H > 512) return p;
+    const SplitRules r(kind, H);
+    // tiles this launch takes of `remaining`: the dense and packed forms are for FULL launches only (a partly filled one has a group count that is no multiple
+    // of the 8 XCDs and loses the one-L2 hand-off)
+    const int cu32 = ncu / 32, unit = cu32 > 0 ? cu32 : 1;       // (unit is never 0: the engine's layer loop advances by it, the binary sizes its batches by it)
+    if (r.pack && remaining >= 8 * unit) p.nrt = 8 * unit;
+    else if (r.dense256 && remaining >= 6 * unit) p.nrt = 6 * unit;
+    else if (r.wide && remaining >= 4 * unit) p.nrt = 4 * unit;
+    else p.nrt = remaining < 2 * unit ? remaining : 2 * unit;
+    // the form: the dense forms (two or three workgroups per CU, a pair of tiles each) take launches with more tiles than the one-tile form can -- FULL launches in
+    // practice -- and at H = 384 also every launch that runs beside another batch's; a launch with more tiles than one workgroup a CU takes goes in pairs at
+    // H <= 256; everything else as measured (kSplitTS)
+    const bool over2 = p.nrt > 2 * cu32, pairs256 = H <= 256 && over2;
+    if (r.dense3 && (over2 || beside)) p.form = kSplitDense3;
+    else if (r.pack && p.nrt == 8 * cu32) p.form = kSplitPack;
+    else if (r.dense256 && p.nrt > 4 * cu32) p.form = kSplitDense256;
+    else p.form = (pairs256 || kSplitTS[kind][H / 128 - 1] == 2) ? kSplitPairTiles : kSplitOneTile;
+    // its grid, and how many workgroups of its kernel share a CU: two launches (of two batches in flight) are co-resident -- every workgroup of both must be,
+    // they wait for their peers -- iff together they fit
+    p.ts = p.form == kSplitOneTile ? 1 : 2;
+    p.workgroups = p.form == kSplitPack ? p.nrt / 2 * 16 : (p.nrt + p.ts - 1) / p.ts * 32;
+    p.per_cu = p.form == kSplitDense256 ? 3 : ((p.form == kSplitPairTiles && H > 256) ? 1 : 2);
+    p.fills_chip = 2 * p.workgroups > ncu * p.per_cu;
+    if (!split_supported(kind, H)) p.form = kSplitNone;      // (GRUmod at H = 512, LSTM at H = 512 in the three-slice build: no kernel)
+    return p;
 }
-// tiles the next launch of a batch takes when `remaining` are left: the dense forms are for FULL launches only (a partly filled
-// one has a group count that is no multiple of the 8 XCDs and loses the one-L2 hand-off)
-int split_next_launch_tiles(int kind, int H, int remaining, int ncu) {
-    const int unit = ncu / 32 > 0 ? ncu / 32 : 1;       // (never 0: the engine's layer loop advances by this, the binary sizes its batches by it)
-    if (split_pack256(kind, H) && remaining >= 8 * unit) return 8 * unit;
-    if (split_dense256(H) && remaining >= 6 * unit) return 6 * unit;
-    if ((H <= 256 || split_dense3(0, H)) && !dbg("no_dense") && remaining >= 4 * unit) return 4 * unit;
-    return remaining < 2 * unit ? remaining : 2 * unit;
-}
-// tiles per group of a launch of nrt read tiles
-// `beside`: another batch is between run and finish -- its layer launches are on the chip; the dense form runs BESIDE them
-static bool split_launch_dense256(int H, int nrt, int ncu) { return split_dense256(H) && nrt > 4 * (ncu / 32); }
-static bool split_launch_dense3(int kind, int H, int nrt, int ncu, int beside) {
-    return split_dense3(kind, H) && (nrt > 2 * (ncu / 32) || beside);
-}
-static int split_launch_ts(int kind, int H, int nrt, int ncu, int beside) {
-    // the dense forms (two workgroups per CU, a pair of tiles each) take launches with more tiles than the one-tile form can:
-    // FULL launches of 4 * (ncu / 32) tiles in practice (the engine's layer loop cuts a batch that way)
-    if (H <= 256 && nrt > 2 * (ncu / 32)) return 2;
-    if (split_launch_dense3(kind, H, nrt, ncu, beside)) return 2;
-    return split_tiles_per_group(kind, H);
-}
-// workgroups of such a launch, and how many workgroups of its kernel share a CU: two launches (of two batches in flight) are
-// co-resident -- every workgroup of both must be, they wait for their peers -- iff together they fit
-int split_launch_workgroups(int kind, int H, int nrt, int ncu, int beside) {
-    if (split_launch_pack(kind, H, nrt, ncu)) return nrt / 2 * 16;
-    const int ts = split_launch_ts(kind, H, nrt, ncu, beside);
-    return (nrt + ts - 1) / ts * 32;
-}
-int split_workgroups_per_cu(int kind, int H, int nrt, int ncu, int beside) {
-    const int ts = split_launch_ts(kind, H, nrt, ncu, beside);
-    if (split_launch_pack(kind, H, nrt, ncu)) return 2;
-    if (split_launch_dense256(H, nrt, ncu)) return 3;
-    return (ts == 1 || H <= 256 || split_launch_dense3(kind, H, nrt, ncu, beside)) ? 2 : 1;
+// paired launches (k_lstm_split_pair, the dense form at H = 384 only) of two batches of nrt read tiles each: the second batch's block indices
+// start at a multiple of the 8 XCDs
+bool split_pair_ok(int kind, int H, int nrt, int ncu) {
+    return split_dense3(kind, H, dbg("no_dense") != nullptr) && !dbg("no_pair") && nrt >= 1 && nrt <= 2 * (ncu / 32) && (((nrt + 1) / 2) & 7) == 0;
 }
 size_t split_flag_words(int nrt) { return (size_t)nrt * 32; }
 // 16-byte pieces of a layer's classic pack [2 matrices][H / 4 unit tiles][H / 32 chunks][slices][64 lanes]: the gate-major pack of the packed
 // GRUmod form ([2][3 H / 16 row tiles][H / 32][slices][64]) follows it
 size_t split_pack_offset(int H) { return (size_t)2 * (H / 4) * (H / 32) * NS * 64; }
-int split_tiles_per_group(int kind, int H) { return kSplitTS[kind & 1][H / 128 - 1]; }
 
 unsigned long long *g_split_dbg = nullptr;
 #ifdef FFHIP_PHASES
@@ -1692,103 +1692,85 @@ extern "C" int ffhip_debug_phases(unsigned long long *out, int reset) {
 namespace ffhip {
 #endif
 
-// paired launches (k_lstm_split_pair, the dense form at H = 384 only) of two batches of nrt read tiles each: the second batch's block indices
-// start at a multiple of the 8 XCDs
-bool split_pair_ok(int kind, int H, int nrt, int ncu) {
-#ifdef FFHIP_SPLIT_BF16X3
+static SplitArgs split_args(const SplitLaunch &l, int H) {
+    SplitArgs a;
+    a.epoch = l.epoch; a.acc_scale = split_pow2(l.scale_exp); a.scale_exp = l.scale_exp; a.fast_gates = l.fast_gates;
+    a.split_gate = 1;
+    a.Wp = (const v4u *)l.Wp; a.bias = l.bias; a.xin = (const unsigned char *)l.xin; a.hout = (unsigned char *)l.hout; a.hout_f32 = l.hout_f32;
+    a.flags = l.flags; a.abort_word = l.abort_word;
+    a.Tb = l.Tb; a.B16 = l.B16; a.H = H; a.rt0 = l.rt0; a.nrt = l.nrt; a.backward = l.backward; a.mode = l.mode;
+    a.tbs = l.tbs; a.tbt = l.tbt; a.live = l.live; a.dbg = g_split_dbg;
+    return a;
+}
+
+// The one launch site of the layer kernels.  kernel_of(LIVE, GL) names a kernel family's instantiation: a packed batch (a.live) takes the LIVE one, the gate level
+// picks the GL one.  BUILT false: a form this build has no kernels for (dense, packed and H = 512 with three slices) -- kernel_of is never instantiated then.
+template <bool BUILT, class KernelOf, class... Other>
+static bool split_go(hipStream_t s, int workgroups, const SplitArgs &a, KernelOf kernel_of, const Other &... other) {
+    if constexpr (BUILT) {
+        auto go = [&](auto live, auto gl) {
+            const auto kernel = kernel_of(live, gl);
+            hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(512), 0, s, a, other...);
+        };
+        using GL0 = std::integral_constant<int, 0>;
+        using GL2 = std::integral_constant<int, 2>;
+        if (a.live) { if (a.fast_gates) go(std::true_type(), GL2()); else go(std::true_type(), GL0()); }
+        else { if (a.fast_gates) go(std::false_type(), GL2()); else go(std::false_type(), GL0()); }
+    }
+    return BUILT;
+}
+template <int KIND, int N, int TS, bool DN = false>
+static bool split_go_tiles(hipStream_t s, const SplitArgs &a, const SplitPlan &p) {
+    return split_go<kSplitF16 || (!DN && N <= 3)>(s, p.workgroups, a, [](auto live, auto gl) { return k_lstm_split<KIND, N, TS, DN, decltype(live)::value, decltype(gl)::value>; });
+}
+// the one-tile or the pair form of one (kind, N)
+template <int KIND, int N>
+static bool split_go_measured(hipStream_t s, const SplitArgs &a, const SplitPlan &p) {
+    return p.ts == 1 ? split_go_tiles<KIND, N, 1>(s, a, p) : split_go_tiles<KIND, N, 2>(s, a, p);
+}
+
+bool launch_lstm_split(hipStream_t s, int kind, int H, const SplitLaunch &l, const SplitPlan &p) {
+    // (a plan made for another launch or another model is refused, not launched)
+    if (l.nrt != p.nrt || (kind != 0 && kind != 1)) return false;
+    if (p.form == kSplitDense3 ? (kind != 0 || H != 384) : ((p.form == kSplitDense256 || p.form == kSplitPack) && H != 256)) return false;
+    SplitArgs a = split_args(l, H);
+    switch (p.form) {
+    case kSplitDense3: return split_go_tiles<0, 3, 2, true>(s, a, p);
+    case kSplitDense256: return kind == 0 ? split_go_tiles<0, 2, 2, true>(s, a, p) : split_go_tiles<1, 2, 2, true>(s, a, p);
+    case kSplitPack:
+        a.Wp += split_pack_offset(H);
+        if (kind == 0) return split_go<kSplitF16>(s, p.workgroups, a, [](auto live, auto gl) { return k_lstm_pack<decltype(live)::value, decltype(gl)::value>; });
+        return split_go<kSplitF16>(s, p.workgroups, a, [](auto live, auto gl) { return k_grumod_pack<decltype(live)::value, decltype(gl)::value>; });
+    case kSplitOneTile:
+    case kSplitPairTiles:
+        switch (kind * 8 + H / 128) {
+        case 1: return split_go_measured<0, 1>(s, a, p);
+        case 2: return split_go_measured<0, 2>(s, a, p);
+        case 3: return split_go_measured<0, 3>(s, a, p);
+        case 4: return split_go_tiles<0, 4, 2>(s, a, p);      // (H = 512: the pair form only -- one tile per group would need 122 registers more than a second workgroup leaves)
+        case 9: return split_go_measured<1, 1>(s, a, p);
+        case 10: return split_go_measured<1, 2>(s, a, p);
+        case 11: return split_go_measured<1, 3>(s, a, p);
+        }
+        break;
+    case kSplitNone: break;
+    }
     return false;
-#else
-    return split_dense3(kind, H) && !dbg("no_pair") && nrt >= 1 && nrt <= 2 * (ncu / 32) && (((nrt + 1) / 2) & 7) == 0;
-#endif
 }
 
 // one launch for the layers of two batches; false: shapes split_pair_ok refuses -- launch them one by one
 bool launch_lstm_split_pair(hipStream_t s, int kind, int H, int ncu, const SplitLaunch &p0, const SplitLaunch &p1) {
-#ifdef FFHIP_SPLIT_BF16X3
-    return false;
-#else
     if (!split_pair_ok(kind, H, p0.nrt, ncu)) return false;
-    auto mk = [&](const SplitLaunch &p) {
-        SplitArgs a;
-        a.epoch = p.epoch; a.acc_scale = split_pow2(p.scale_exp); a.scale_exp = p.scale_exp; a.fast_gates = p.fast_gates;
-        a.split_gate = 1;
-        a.Wp = (const v4u *)p.Wp; a.bias = p.bias; a.xin = (const unsigned char *)p.xin; a.hout = (unsigned char *)p.hout; a.hout_f32 = p.hout_f32;
-        a.flags = p.flags; a.abort_word = p.abort_word;
-        a.Tb = p.Tb; a.B16 = p.B16; a.H = H; a.rt0 = p.rt0; a.nrt = p.nrt; a.backward = p.backward; a.mode = p.mode;
-        a.tbs = p.tbs; a.tbt = p.tbt; a.live = p.live; a.dbg = g_split_dbg;
-        return a;
-    };
-    const int g0 = (p0.nrt + 1) / 2, g1 = (p1.nrt + 1) / 2;
     // the two batches share everything but their buffers: same model (weights, exponents), same capacity and tile count
     if (p0.Wp != p1.Wp || p0.bias != p1.bias || p0.Tb != p1.Tb || p0.B16 != p1.B16 || p0.rt0 != p1.rt0 || p0.nrt != p1.nrt || p0.backward != p1.backward ||
         p0.mode != p1.mode || p0.scale_exp != p1.scale_exp || p0.fast_gates != p1.fast_gates || (p0.hout_f32 == nullptr) != (p1.hout_f32 == nullptr) ||
         (p0.tbs == nullptr) != (p1.tbs == nullptr) || (p0.live == nullptr) != (p1.live == nullptr)) return false;
-    const SplitArgs a1 = mk(p1);
+    const int g0 = (p0.nrt + 1) / 2, g1 = (p1.nrt + 1) / 2;
+    const SplitArgs a1 = split_args(p1, H);
     SplitArgsOther o;
     o.xin = a1.xin; o.hout = a1.hout; o.hout_f32 = a1.hout_f32; o.flags = a1.flags; o.abort_word = a1.abort_word; o.tbs = a1.tbs; o.tbt = a1.tbt; o.live = a1.live; o.epoch = a1.epoch;
     o.nwg0 = g0 * 32;
-    const dim3 grid((g0 + g1) * 32);
-    if (p0.live) { if (p0.fast_gates) hipLaunchKernelGGL((k_lstm_split_pair<0, 3, 2, true, true, 2>), grid, dim3(512), 0, s, mk(p0), o); else hipLaunchKernelGGL((k_lstm_split_pair<0, 3, 2, true, true, 0>), grid, dim3(512), 0, s, mk(p0), o); }
-    else { if (p0.fast_gates) hipLaunchKernelGGL((k_lstm_split_pair<0, 3, 2, true, false, 2>), grid, dim3(512), 0, s, mk(p0), o); else hipLaunchKernelGGL((k_lstm_split_pair<0, 3, 2, true, false, 0>), grid, dim3(512), 0, s, mk(p0), o); }
-    return true;
-#endif
-}
-
-bool launch_lstm_split(hipStream_t s, int kind, const void *Wp, const float *bias, const void *xin, void *hout, float *hout_f32,
-                       unsigned *flags, unsigned *abort_word, int Tb, int B16, int H, int rt0, int nrt, int backward, int mode,
-                       int scale_exp, int fast_gates, const int *tbs, const int *tbt, int ncu, unsigned epoch, int beside, const unsigned *live) {
-    SplitArgs a;
-    a.epoch = epoch;
-    a.acc_scale = split_pow2(scale_exp);
-    a.scale_exp = scale_exp;
-    a.fast_gates = fast_gates;
-    a.split_gate = 1;
-    a.Wp = (const v4u *)Wp; a.bias = bias; a.xin = (const unsigned char *)xin; a.hout = (unsigned char *)hout; a.hout_f32 = hout_f32;
-    a.flags = flags; a.abort_word = abort_word;
-    a.Tb = Tb; a.B16 = B16; a.H = H; a.rt0 = rt0; a.nrt = nrt; a.backward = backward; a.mode = mode;
-    a.tbs = tbs; a.tbt = tbt; a.live = live; a.dbg = g_split_dbg;
-    // tiles per group: 1 (two workgroups per CU, one read tile each) where that is faster, else 2 (kSplitTS)
-    // ... and 2 with two workgroups per CU when the launch carries more tiles than the one-tile form can take (H <= 256)
-    const int ts = split_launch_ts(kind, H, nrt, ncu, beside);
-    const int ngroup_l = (nrt + ts - 1) / ts;
-#ifndef FFHIP_SPLIT_BF16X3
-    // (a packed batch -- a.live -- takes the LIVE instantiation of the same form; the gate level picks the GL one)
-#define SPLIT_GO(KF, GRID) do { if (a.live) { if (a.fast_gates) hipLaunchKernelGGL((KF(true, 2)), dim3(GRID), dim3(512), 0, s, a); else hipLaunchKernelGGL((KF(true, 0)), dim3(GRID), dim3(512), 0, s, a); } \
-                                else { if (a.fast_gates) hipLaunchKernelGGL((KF(false, 2)), dim3(GRID), dim3(512), 0, s, a); else hipLaunchKernelGGL((KF(false, 0)), dim3(GRID), dim3(512), 0, s, a); } } while (0)
-#define K_DENSE3(L, G) k_lstm_split<0, 3, 2, true, L, G>
-#define K_GPACK(L, G) k_grumod_pack<L, G>
-#define K_LPACK(L, G) k_lstm_pack<L, G>
-#define K_D256L(L, G) k_lstm_split<0, 2, 2, true, L, G>
-#define K_D256G(L, G) k_lstm_split<1, 2, 2, true, L, G>
-    if (split_launch_dense3(kind, H, nrt, ncu, beside)) { SPLIT_GO(K_DENSE3, ngroup_l * 32); return true; }
-    if (split_launch_pack(kind, H, nrt, ncu)) {
-        a.Wp += split_pack_offset(H);
-        if (kind == 1) SPLIT_GO(K_GPACK, nrt / 2 * 16);
-        else SPLIT_GO(K_LPACK, nrt / 2 * 16);
-        return true;
-    }
-    if (split_launch_dense256(H, nrt, ncu)) {
-        if (kind == 0) SPLIT_GO(K_D256L, ngroup_l * 32);
-        else SPLIT_GO(K_D256G, ngroup_l * 32);
-        return true;
-    }
-#endif
-#define K_GEN(KK, NN, TT) [&]() { if (a.live) { if (a.fast_gates) hipLaunchKernelGGL((k_lstm_split<KK, NN, TT, false, true, 2>), dim3(ngroup_l * 32), dim3(512), 0, s, a); else hipLaunchKernelGGL((k_lstm_split<KK, NN, TT, false, true, 0>), dim3(ngroup_l * 32), dim3(512), 0, s, a); } \
-                                  else { if (a.fast_gates) hipLaunchKernelGGL((k_lstm_split<KK, NN, TT, false, false, 2>), dim3(ngroup_l * 32), dim3(512), 0, s, a); else hipLaunchKernelGGL((k_lstm_split<KK, NN, TT, false, false, 0>), dim3(ngroup_l * 32), dim3(512), 0, s, a); } }()
-#define SPLIT_LAUNCH(K, NN) do { if (ts == 1) K_GEN(K, NN, 1); else K_GEN(K, NN, 2); return true; } while (0)
-#ifdef FFHIP_SPLIT_BF16X3
-    if (kind == 0) switch (H / 128) { case 1: SPLIT_LAUNCH(0, 1); case 2: SPLIT_LAUNCH(0, 2); case 3: SPLIT_LAUNCH(0, 3); }
-    if (kind == 1) switch (H / 128) { case 1: SPLIT_LAUNCH(1, 1); case 2: SPLIT_LAUNCH(1, 2); case 3: SPLIT_LAUNCH(1, 3); }
-#else
-    if (kind == 0) switch (H / 128) { case 1: SPLIT_LAUNCH(0, 1); case 2: SPLIT_LAUNCH(0, 2); case 3: SPLIT_LAUNCH(0, 3);
-                                      case 4: { const dim3 g4((nrt + 1) / 2 * 32);      // (H = 512: the pair form only -- one tile per group would need 122 registers more than a second workgroup leaves)
-                                              if (a.live) { if (a.fast_gates) hipLaunchKernelGGL((k_lstm_split<0, 4, 2, false, true, 2>), g4, dim3(512), 0, s, a); else hipLaunchKernelGGL((k_lstm_split<0, 4, 2, false, true, 0>), g4, dim3(512), 0, s, a); }
-                                              else { if (a.fast_gates) hipLaunchKernelGGL((k_lstm_split<0, 4, 2, false, false, 2>), g4, dim3(512), 0, s, a); else hipLaunchKernelGGL((k_lstm_split<0, 4, 2, false, false, 0>), g4, dim3(512), 0, s, a); }
-                                              return true; } }
-    if (kind == 1) switch (H / 128) { case 1: SPLIT_LAUNCH(1, 1); case 2: SPLIT_LAUNCH(1, 2); case 3: SPLIT_LAUNCH(1, 3); }
-#endif
-#undef SPLIT_LAUNCH
-    return false;
+    return split_go<kSplitF16>(s, (g0 + g1) * 32, split_args(p0, H), [](auto live, auto gl) { return k_lstm_split_pair<0, 3, 2, true, decltype(live)::value, decltype(gl)::value>; }, o);
 }
 
 }  // namespace ffhip

@@ -449,6 +449,14 @@ int ffhip_batch_profile(const ffhip_batch *b, float ms[FFHIP_NGROUP], int launch
  * its peer workgroups (another tenant on the GPU); each occurrence also warns on stderr once per process and sends the next 64 runs
  * to those kernels directly */
 int ffhip_debug_fallback_count(const ffhip_engine *eng);
+/* the rule that picks a layer launch of the split-operand kernels (needs no engine, touches no device): for a model of `kind` (0 LSTM, 1 GRUmod) and `hidden`
+ * units with `remaining` read tiles (of 16 reads) of a batch still to launch on `ncu` compute units, `beside` != 0 when another batch is in flight,
+ * out = { form (0 one tile a group, 1 a pair, 2 dense at 384, 3 dense at 256, 4 packed, 5 no kernel), read tiles the launch takes, tiles a group, workgroups,
+ * workgroups of that kernel sharing a compute unit, 1 if the launch fills the chip (the next layer launch waits for it) }.  Reads FFHIP_DEBUG (no_dense, no_pack).
+ * Returns FFHIP_OK, or FFHIP_EINVAL without `out` */
+int ffhip_debug_split_plan(int kind, int hidden, int remaining, int ncu, int beside, int out[6]);
+/* 1 if two batches of `nrt` read tiles each may share paired layer launches (ffhip_batch_run_pair), else 0; reads FFHIP_DEBUG (no_dense, no_pair); no engine, no device */
+int ffhip_debug_split_pair_ok(int kind, int hidden, int nrt, int ncu);
 /* device memory the batch holds (its buffers, grown on first use by the paths its runs took): a packed batch's launch-per-step run adds less than one
  * activation buffer to what its default run holds -- the in-projection is computed a window of steps at a time */
 size_t ffhip_debug_batch_device_bytes(const ffhip_batch *b);

@@ -24,12 +24,14 @@ int main(int argc, char **argv) {
     const int mode = argc > 3 ? atoi(argv[3]) : 0;
     const int nrep = argc > 4 ? atoi(argv[4]) : 40;      // enough launches for the clocks to settle: the first ones run ~40 % slower
     const int kind = argc > 5 ? atoi(argv[5]) : 0;          // 1: GRUmod (H = 256 and B16 = 64: the packed form)
+    const SplitPlan plan = split_plan(kind, H, B16, 256, 0);      // B16 = 32 at H = 384: the dense form, two workgroups per CU
+    if (plan.nrt < B16) printf("one launch takes %d of the %d read tiles\n", plan.nrt, B16);
     for (int rep = 0; rep < nrep; rep++) {
         hipMemsetD32((hipDeviceptr_t)hout, 0xFFFFFFFF, abytes / 4);
         hipMemset(flags, 0, 4096 * 4);
         hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
         hipEventRecord(e0, 0);
-        launch_lstm_split(0, kind, Wp, bias, xin, hout, nullptr, flags, ab, Tb, B16, H, 0, B16, 1, mode, 0, 0, nullptr, nullptr, 256, (unsigned)(rep + 1), 0);   // B16 = 32 at H = 384: the dense form, two workgroups per CU
+        launch_lstm_split(0, kind, H, SplitLaunch{ Wp, bias, xin, hout, nullptr, flags, ab, Tb, B16, 0, plan.nrt, 1, mode, 0, 0, nullptr, nullptr, (unsigned)(rep + 1) }, plan);
         hipEventRecord(e1, 0); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1);
         if (rep < 2 || rep >= nrep - 2) printf("rep %d: layer %.3f ms = %.3f us/step = %.0f cycles/step\n", rep, ms, ms * 1e3 / Tb, ms * 1e3 / Tb * 2400);
