@@ -169,6 +169,7 @@ def lib():
     L.ffhip_debug_batch_forms.argtypes = [vp, C.POINTER(C.c_int)]
     L.ffhip_debug_batch_device_bytes.restype = C.c_size_t
     L.ffhip_debug_batch_device_bytes.argtypes = [vp]
+    L.ffhip_debug_result_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_size_t), C.c_int]
     L.ffhip_batch_set_run_scale.argtypes = [vp, C.POINTER(C.c_double)]
     L.ffhip_batch_rle_runs.argtypes = [vp, C.c_int, C.POINTER(CRleRuns)]
     L.ffhip_op_rle_runs.argtypes = [vp, CFMat, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8),
@@ -192,6 +193,19 @@ def split_plan(kind: int, hidden: int, remaining: int, ncu: int, beside: int) ->
     out = (C.c_int * 6)()
     _check(lib().ffhip_debug_split_plan(C.c_int(kind), C.c_int(hidden), C.c_int(remaining), C.c_int(ncu), C.c_int(beside), out))
     return {"form": SPLIT_FORMS[out[0]], "nrt": out[1], "ts": out[2], "workgroups": out[3], "per_cu": out[4], "fills_chip": out[5]}
+
+
+RESULT_FIELDS = ("sat", "abort", "lens", "score", "bases", "quals", "nrun", "fail", "len", "base", "est", "shape", "scale", "dwell", "ml", "mv")
+RESULT_SECTIONS = ("head", "core", "runs", "records", "mod", "moves")
+
+
+def result_layout(nread: int, cap_reads: int, Tb: int, sections=()) -> dict:
+    """ffhip_debug_result_layout: byte offset of every field and end of every section of a batch's result block that holds `sections` (names of RESULT_SECTIONS; no device, no engine)"""
+    n = len(RESULT_FIELDS) + len(RESULT_SECTIONS)
+    out = (C.c_size_t * n)()
+    mask = sum(1 << RESULT_SECTIONS.index(s) for s in sections)
+    _check(lib().ffhip_debug_result_layout(nread, cap_reads, Tb, mask, out, n))
+    return {"field": dict(zip(RESULT_FIELDS, out[:len(RESULT_FIELDS)])), "end": dict(zip(RESULT_SECTIONS, out[len(RESULT_FIELDS):]))}
 
 
 def split_pair_ok(kind: int, hidden: int, nrt: int, ncu: int) -> int:

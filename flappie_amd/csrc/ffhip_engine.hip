@@ -21,6 +21,7 @@
 #include "../../include/ffhip.h"
 #include "ffhip_internal.hpp"
 #include "ffhip_host.hpp"
+#include "ffhip_results.hpp"
 
 using namespace ffhip;
 
@@ -723,50 +724,39 @@ struct ffhip_batch {
     float *fa[2] = { nullptr, nullptr };       // the fp32 activations of the run in progress: act[], or -- a packed batch's launch-per-step run -- the memory of actS[]
     float *xa_win = nullptr;            // the launch-per-step run's in-projection, kStepWindow steps of it (run_layers); allocated on first use
     void *split_win = nullptr;          // ... and its input in the split layout
-    size_t dev_bytes = 0;               // what dalloc holds for the batch (ffhip_debug_batch_device_bytes)
+    size_t dev_bytes = 0;               // what dalloc holds for the batch (ffhip_debug_batch_device_bytes: this and the result block)
     float *trans = nullptr, *post = nullptr, *fwd = nullptr;
     double *crf_logz = nullptr;         // fp64 partition function per read
     double *crf_e = nullptr;            // exp(score - block max), workspace of the linear-space partition function
     uint8_t *tb = nullptr;
-    int *path = nullptr; float *qpath = nullptr; float *score = nullptr;
-    char *bases = nullptr, *quals = nullptr; int *lens = nullptr;
+    int *path = nullptr; float *qpath = nullptr;
     int32_t *trace = nullptr;
     unsigned split_epoch = 0;           // launch counter of the split layer kernel (its check-in words are never cleared)
     int counted = 0;                    // this batch is in the engine's in_flight count (between run and finish)
     const float **d_gsrc = nullptr; int *d_glen = nullptr;              // ffhip_batch_set_prepared: source rows of the gather
-    unsigned *pflags = nullptr, *pabort = nullptr, *h_abort = nullptr;   // persistent-kernel XCC ids / abort word
+    unsigned *pflags = nullptr;         // persistent-kernel XCC ids (the abort word: pabort() below)
     // reads with a value beyond the split format's range (ffhip_split.hpp: the swish convolutions' outputs are clamped at +-4094 there, the
     // reference's are unbounded, layers.c:24-33): one word per read, set by the producers of that format, looked at by ffhip_batch_finish,
     // which runs such reads again on the f32 path (`side`) and puts their results in place
-    unsigned *sat = nullptr, *h_sat = nullptr;
     double rehearsal_done_at = 0.0;     // FFHIP_DEBUG_HOST_REHEARSAL_MSPS: when the emulated GPU is done with this batch
     ffhip_batch *side = nullptr;        // 16 slots of this batch's capacity, created when the first read needs it
     bool is_side = false;
     int reruns = 0;                     // reads of the last run that took that way
     int persist_concurrent_ok = 0;      // two such batches fit on the chip at once
     float *scratch = nullptr;           // dense [Tb][H] for debug taps
-    // pinned host mirrors of the small results
-    char *h_bases = nullptr, *h_quals = nullptr; int *h_lens = nullptr; float *h_score = nullptr;
-    // what ffhip_batch_finish brings down is ONE block on the device and one pinned block on the host, [sat | abort | lens | score | bases | quals]: one copy
-    // instead of six (round 5; a batch that was not decoded takes the first two parts only)
-    unsigned char *res_dev = nullptr, *res_host = nullptr; size_t res_bytes = 0, res_head = 0;
-    // Run records of a run-length batch (FFHIP_RUN_RLE_RUNS / _RECORDS, k_rle_runs): a section behind [.. | quals] of the same block, added on the first run that asks
-    // for it -- [nrun | fail | len | base | est] (5 bytes a block), [shape | scale | dwell] (12 more) for the records; res_cap: what the block holds now
-    size_t res_cap = 0, res_runs_end = 0, res_rec_end = 0;
-    RleRunOut runs_dev{}, runs_host{};
+    // The small results, brought to the host by ffhip_batch_finish in one copy: the result block (ffhip_results.hpp), and thin views of its head and core fields
+    ResultBlock res;
+    unsigned *sat() const { return res.on_dev<unsigned>(RF_SAT); }
+    unsigned *pabort() const { return res.on_dev<unsigned>(RF_ABORT); }
+    int *lens() const { return res.on_dev<int>(RF_LENS); }
+    float *score() const { return res.on_dev<float>(RF_SCORE); }
+    char *bases() const { return res.on_dev<char>(RF_BASES); }
+    char *quals() const { return res.on_dev<char>(RF_QUALS); }
+    unsigned *h_sat() const { return res.on_host<unsigned>(RF_SAT); }
+    unsigned *h_abort() const { return res.on_host<unsigned>(RF_ABORT); }
+    int *h_lens() const { return res.on_host<int>(RF_LENS); }
+    unsigned res_made = 0;              // sections of the block the last run filled (res_bit)
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
-    int runs_valid = 0;                 // the last run made run records: 1 base and est, 2 with shape / scale / dwell
-    // 5mC probabilities of a 5-base flip-flop batch (FFHIP_RUN_MOD_PROBS, k_mod_probs): one byte a called base, a section behind [.. | quals] of the same block
-    // (where a run-length batch has its run section), added on the first run that asks for it
-    size_t res_ml_end = 0;
-    uint8_t *ml_dev = nullptr, *ml_host = nullptr;
-    bool mod_block = false;             // the block holds the section
-    int mod_valid = 0;                  // the last run made them
-    // move table of a flip-flop batch (FFHIP_RUN_MOVES, k_moves): one byte a block, a section of its own behind the 5mC section where the block holds one and
-    // behind [.. | quals] where it does not, added on the first run that asks for it
-    uint8_t *mv_dev = nullptr, *mv_host = nullptr;
-    bool mv_block = false;              // the block holds the section
-    int mv_valid = 0;                   // the last run made them
     std::vector<void *> owned;
     unsigned last_flags = 0;
     float last_temperature = 1.0f;
@@ -793,51 +783,13 @@ struct ffhip_batch {
     int forms[4] = { -1, -1, -1, -1 };  // kernel forms of the last run's convolution launches and its head launch (KernelForm)
 };
 
-// The result block's layout, in one place: [sat | abort | lens | score | bases | quals] (what every decoded run brings down), then the run section of a run-length
-// batch, [nrun | fail | len | base | est] and [shape | scale | dwell] (present once a run asked for it: ensure_run_block), or in the same place the [ml] section of
-// a 5-base flip-flop batch (ensure_mod_block; a batch has one model, so never both), and the [mv] section of a flip-flop batch (ensure_moves_block) behind the
-// sections the block holds: [.. | quals | mv] or [.. | quals | ml | mv].  A finished run brings a PREFIX of the block down (res_copy_bytes), and a batch that
-// never asked for 5mC bytes has no ml section, so a run with moves alone copies no unused section; only a batch that has made both kinds and then runs with
-// moves alone copies the ml section's bytes unused.  Offsets in bytes, each part 256-aligned.
-struct ResLayout { size_t sat, abort, lens, score, bases, quals, end, nrun, fail, len, base, est, runs_end, shape, scale, dwell, rec_end, ml, ml_end, mv, mv_end; };
-static ResLayout res_layout(const ffhip_batch *b) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t nres = (size_t)b->cap_reads, n1 = (size_t)b->nread * ((size_t)b->Tb + 1);
-    ResLayout o;
-    o.sat = 0; o.abort = up((size_t)b->Bp * 4); o.lens = o.abort + 256; o.score = o.lens + up(nres * 4);
-    o.bases = o.score + up(nres * 4); o.quals = o.bases + up(n1); o.end = o.quals + up(n1);
-    o.nrun = o.end; o.fail = o.nrun + up(nres * 4); o.len = o.fail + up(nres * 4); o.base = o.len + up(nres * 8); o.est = o.base + up(n1);
-    o.runs_end = o.est + up(n1 * 4);
-    o.shape = o.runs_end; o.scale = o.shape + up(n1 * 4); o.dwell = o.scale + up(n1 * 4); o.rec_end = o.dwell + up(n1 * 4);
-    o.ml = o.end; o.ml_end = o.ml + up(n1);
-    o.mv = b->mod_block ? o.ml_end : o.end; o.mv_end = o.mv + up(n1);
+// the run records' fields as the kernel's argument (shape, scale and dwell for a run that makes the whole record), or the same in the host half
+static RleRunOut rle_run_out(const ResultBlock &r, bool host, bool records) {
+    auto p = [&](ResField f) { return (host ? r.host : r.dev) + r.at.field[f]; };
+    RleRunOut o{};
+    o.nrun = (int *)p(RF_NRUN); o.fail = (int *)p(RF_FAIL); o.len = (unsigned long long *)p(RF_LEN); o.base = p(RF_BASE); o.est = (int *)p(RF_EST);
+    if (records) { o.shape = (float *)p(RF_SHAPE); o.scale = (float *)p(RF_SCALE); o.dwell = (int *)p(RF_DWELL); }
     return o;
-}
-// every pointer into the result block, device and pinned host side, from res_dev / res_host and the layout (the run section's when the block holds it; shape,
-// scale and dwell when it holds them and `records`)
-static void res_point(ffhip_batch *b, bool records) {
-    const ResLayout o = res_layout(b);
-    unsigned char *d = b->res_dev, *h = b->res_host;
-    b->sat = (unsigned *)(d + o.sat); b->pabort = (unsigned *)(d + o.abort); b->lens = (int *)(d + o.lens);
-    b->score = (float *)(d + o.score); b->bases = (char *)(d + o.bases); b->quals = (char *)(d + o.quals);
-    b->h_sat = (unsigned *)(h + o.sat); b->h_abort = (unsigned *)(h + o.abort); b->h_lens = (int *)(h + o.lens);
-    b->h_score = (float *)(h + o.score); b->h_bases = (char *)(h + o.bases); b->h_quals = (char *)(h + o.quals);
-    const bool runs = b->res_cap >= o.runs_end, rec = records && b->res_cap >= o.rec_end;
-    auto set = [&](unsigned char *base, RleRunOut &r) {
-        r = RleRunOut{};
-        if (!runs) return;
-        r.nrun = (int *)(base + o.nrun); r.fail = (int *)(base + o.fail); r.len = (unsigned long long *)(base + o.len);
-        r.base = base + o.base; r.est = (int *)(base + o.est);
-        if (rec) { r.shape = (float *)(base + o.shape); r.scale = (float *)(base + o.scale); r.dwell = (int *)(base + o.dwell); }
-    };
-    set(d, b->runs_dev);
-    set(h, b->runs_host);
-    const bool mod = b->mod_block && b->res_cap >= o.ml_end;
-    b->ml_dev = mod ? d + o.ml : nullptr;
-    b->ml_host = mod ? h + o.ml : nullptr;
-    const bool mv = b->mv_block && b->res_cap >= o.mv_end;
-    b->mv_dev = mv ? d + o.mv : nullptr;
-    b->mv_host = mv ? h + o.mv : nullptr;
 }
 
 static void *dalloc(ffhip_batch *b, size_t bytes, bool zero) {
@@ -898,7 +850,7 @@ extern "C" void ffhip_batch_destroy(ffhip_batch *b) {
     hipStreamSynchronize(b->stream);
     if (b->counted) { b->counted = 0; b->eng->in_flight--; }
     for (void *p : b->owned) hipFree(p);
-    if (b->res_host) hipHostFree(b->res_host);      // (h_sat, h_abort, h_lens, h_score, h_bases, h_quals point into it)
+    b->res.release();
     if (b->side) ffhip_batch_destroy(b->side);
     prof_unlink(b);
     if (b->have_ev) {
@@ -960,20 +912,9 @@ static ffhip_batch *batch_create_impl(ffhip_engine *eng, const ffhip_model *m, i
     if (!(b->tb = (uint8_t *)dalloc(b, (size_t)nread * Tb * kMaxState, false))) BFAIL();
     if (!(b->path = (int *)dalloc(b, (size_t)nread * (Tb + 1) * 4, true))) BFAIL();
     if (!(b->qpath = (float *)dalloc(b, (size_t)nread * (Tb + 1) * 4, true))) BFAIL();
-    {
-        const ResLayout o = res_layout(b);
-        b->res_head = o.lens;
-        b->res_bytes = o.end;
-        b->res_runs_end = o.runs_end; b->res_rec_end = o.rec_end; b->res_ml_end = o.ml_end;
-        b->res_cap = b->res_bytes;
-        if (!(b->res_dev = (unsigned char *)dalloc(b, b->res_bytes, true))) BFAIL();
-        if (hipHostMalloc((void **)&b->res_host, b->res_bytes) != hipSuccess) { set_err(FFHIP_ENOMEM, "pinned host allocation failed"); BFAIL(); }
-        memset(b->res_host, 0, b->res_bytes);
-        res_point(b, false);
-    }
+    if (b->res.create(b->Bp, b->cap_reads, nread, b->Tb, b->stream)) BFAIL();
     if (!(b->trace = (int32_t *)dalloc(b, (size_t)nread * (Tb + 1) * ns * 4, true))) BFAIL();
     if (!(b->pflags = (unsigned *)dalloc(b, persist_flag_words((int)Hp, b->B16) * sizeof(unsigned), true))) BFAIL();
-    // (pabort -- [0] abort word, [1] development counter -- and sat live in the result block above)
     if (persist_supported(m->cell, (int)Hp, eng->prop.multiProcessorCount)) {
         const int maxt = persist_max_tiles(m->cell, (int)Hp, eng->prop.multiProcessorCount, fused_supported(m->cell, (int)Hp));
         b->persist_concurrent_ok = 2 * b->B16 <= maxt;      // two such launches fit on the chip together
@@ -995,59 +936,6 @@ extern "C" ffhip_batch *ffhip_batch_create_packed(ffhip_engine *eng, const ffhip
 }
 static inline int batch_nreads(const ffhip_batch *b) { return b->packed ? b->nvirt : b->nread; }
 
-// The result block grown to `need` bytes, the block's contents kept (a packed batch's set-up writes into it before the run); the caller sets the pointers into it
-// again (res_point).  Returns 0 or an FFHIP_E* code.
-static int grow_res_block(ffhip_batch *b, size_t need) {
-    if (b->res_cap < need) {
-        HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
-        unsigned char *d = nullptr, *h = nullptr;
-        if (hipMalloc((void **)&d, need) != hipSuccess) return set_err(FFHIP_ENOMEM, "hipMalloc of %zu bytes failed", need);
-        if (hipHostMalloc((void **)&h, need) != hipSuccess) { hipFree(d); return set_err(FFHIP_ENOMEM, "pinned host allocation failed"); }
-        memset(h + b->res_cap, 0, need - b->res_cap);
-        memcpy(h, b->res_host, b->res_cap);
-        if (hipMemsetAsync(d + b->res_cap, 0, need - b->res_cap, b->stream) != hipSuccess ||
-            hipMemcpyAsync(d, b->res_dev, b->res_cap, hipMemcpyDeviceToDevice, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess) {
-            hipFree(d); hipHostFree(h); return set_err(FFHIP_EHIP, "copy of the result block failed");
-        }
-        for (void *&p : b->owned) if (p == b->res_dev) { hipFree(p); p = d; }
-        hipHostFree(b->res_host);
-        b->dev_bytes += need - b->res_cap;
-        b->res_dev = d; b->res_host = h; b->res_cap = need;
-    }
-    return FFHIP_OK;
-}
-// The result block's run section (ffhip_batch::res_runs_end) or 5mC section (res_ml_end): grown on the first run that asks for it
-static int ensure_run_block(ffhip_batch *b, bool records) {
-    const ResLayout o = res_layout(b);
-    if (int rc = grow_res_block(b, records ? o.rec_end : o.runs_end)) return rc;
-    res_point(b, records);
-    return FFHIP_OK;
-}
-static int ensure_mod_block(ffhip_batch *b) {
-    if (b->mod_block) return FFHIP_OK;
-    b->mod_block = true;                // (the moves section, when the block holds one, now lies behind this one: res_layout)
-    const ResLayout o = res_layout(b);
-    if (int rc = grow_res_block(b, b->mv_block ? o.mv_end : o.ml_end)) { b->mod_block = false; return rc; }
-    res_point(b, false);
-    return FFHIP_OK;
-}
-// ... or its moves section
-static int ensure_moves_block(ffhip_batch *b) {
-    if (b->mv_block) return FFHIP_OK;
-    if (int rc = grow_res_block(b, res_layout(b).mv_end)) return rc;
-    b->mv_block = true;
-    res_point(b, false);
-    return FFHIP_OK;
-}
-// bytes of the result block a finished run brings down: [sat | abort] alone without a decode, the run section when the run made one
-static size_t res_copy_bytes(const ffhip_batch *b, unsigned flags) {
-    if (flags & FFHIP_RUN_NO_DECODE) return b->res_head;
-    if (flags & FFHIP_RUN_RLE_RECORDS) return b->res_rec_end;
-    if (flags & FFHIP_RUN_RLE_RUNS) return b->res_runs_end;
-    if (flags & FFHIP_RUN_MOVES) return res_layout(b).mv_end;
-    if (flags & FFHIP_RUN_MOD_PROBS) return b->res_ml_end;
-    return b->res_bytes;
-}
 extern "C" int ffhip_batch_nreads(const ffhip_batch *b) { return b ? batch_nreads(b) : 0; }
 // first row of a read in the buffers of Tb / Tb + 1 rows a slot
 static inline size_t read_row0(const ffhip_batch *b, int read) { return b->packed ? (size_t)b->v_slot[read] * b->Tb + b->v_off[read] : (size_t)read * b->Tb; }
@@ -1300,10 +1188,10 @@ static int apply_packed(ffhip_batch *b, int nv, const std::vector<int> &lens, co
         }
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b->rag_x0a[l], kZeroCol, n, b->stream), FFHIP_EHIP);
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b->rag_x0b[l], kZeroCol, n, b->stream), FFHIP_EHIP);
-        HIP_TRY(hipMemsetAsync(b->pabort + 2, 0, sizeof(unsigned), b->stream), FFHIP_EHIP);
+        HIP_TRY(hipMemsetAsync(b->pabort() + 2, 0, sizeof(unsigned), b->stream), FFHIP_EHIP);
         if (nv > 0) {
             HIP_TRY(hipMemcpyAsync(b->d_prd, prd, (size_t)nv * sizeof(int4), hipMemcpyHostToDevice, b->stream), FFHIP_EHIP);
-            launch_pack_conv_table(b->stream, b->d_prd, nv, maxcols, winlen, st, Tmax, b->rag_x0a[l], b->rag_x0b[l], b->pabort + 2);
+            launch_pack_conv_table(b->stream, b->d_prd, nv, maxcols, winlen, st, Tmax, b->rag_x0a[l], b->rag_x0b[l], b->pabort() + 2);
         }
     }
     for (int v = 0; v < nv; v++) if (cur[v] != vtb[v]) return set_err(FFHIP_EINVAL, "internal error: block count of packed read %d", v);
@@ -1459,6 +1347,7 @@ extern "C" int ffhip_batch_set_prepared(ffhip_batch *b, const ffhip_prep *prep, 
 // ---- packed batches: reads of any lengths, several to a row (ffhip.h "packed batches")
 extern "C" int ffhip_batch_set_signals_packed(ffhip_batch *b, int nread, const float *const *signals, const size_t *nsample, const int *slot, const int *block_off) {
     if (!b || nread < 0 || (nread > 0 && (!signals || !nsample || !slot || !block_off))) return set_err(FFHIP_EINVAL, "bad packed-signal arguments");
+    if (rehearsal_rate() > 0) return set_err(FFHIP_EINVAL, "packed batches are not part of the host-load rehearsal");
     hipSetDevice(b->eng->device);
     std::vector<int> lens(nread);
     for (int v = 0; v < nread; v++) {
@@ -1538,7 +1427,7 @@ static SplitLaunch layer_split_launch(ffhip_batch *b, int l, int cur, int rt0, i
     const RnnDev &r = b->mdl->rnn[l];
     const RunPath &p = b->run_path;
     b->split_epoch = (b->split_epoch % 0x3FFFFFFu) + 1u;
-    return SplitLaunch{ r.Wsplit, r.bias, b->actS[cur], b->actS[cur ^ 1], ((l == 4 && !p.split_head) || p.keep) ? b->fa[cur ^ 1] : nullptr, b->pflags, b->pabort,
+    return SplitLaunch{ r.Wsplit, r.bias, b->actS[cur], b->actS[cur ^ 1], ((l == 4 && !p.split_head) || p.keep) ? b->fa[cur ^ 1] : nullptr, b->pflags, b->pabort(),
                         b->Tb, b->B16, rt0, nrt, (l % 2 == 0) ? 1 : 0, p.persist_mode, r.split_S, p.gates,
                         b->ragged ? b->d_tbs : nullptr, b->ragged ? b->d_tbt : nullptr, b->split_epoch, b->packed ? b->d_live : nullptr };
 }
@@ -1568,24 +1457,13 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
     memset(b->launches, 0, sizeof(b->launches));
     b->run_path = plan_run(m, flags, temperature, ncu);
     const RunPath &p = b->run_path;
-    b->runs_valid = 0;
-    if (flags & (FFHIP_RUN_RLE_RUNS | FFHIP_RUN_RLE_RECORDS)) {
-        if (m->kind != FFHIP_NET_LSTM5_RLE || m->nbase != 4 || (flags & FFHIP_RUN_NO_DECODE))
-            return set_err(FFHIP_EINVAL, "run records: a decoded run of the run-length model (nbase 4) only");
-        if (int rc = ensure_run_block(b, (flags & FFHIP_RUN_RLE_RECORDS) != 0)) return rc;
-    }
-    b->mod_valid = 0;
-    if (flags & FFHIP_RUN_MOD_PROBS) {
-        if (m->kind == FFHIP_NET_LSTM5_RLE || m->nbase != 5)
-            return set_err(FFHIP_EINVAL, "5mC probabilities: a flip-flop model with a modified base (nbase 5) only");
-        if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "5mC probabilities need a decoded run (FFHIP_RUN_NO_DECODE is set)");
-        if (int rc = ensure_mod_block(b)) return rc;
-    }
-    b->mv_valid = 0;
-    if (flags & FFHIP_RUN_MOVES) {
-        if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "move table: a flip-flop model only (the run-length model's run records carry dwells)");
-        if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "the move table needs a decoded run (FFHIP_RUN_NO_DECODE is set)");
-        if (int rc = ensure_moves_block(b)) return rc;
+    b->res_made = 0;
+    for (int i = 0; i < RS_COUNT; i++) {       // the sections this run asks for: may this model ask, is the run decoded, does the block hold them
+        const ResSectionRow &sec = kResSections[i];
+        if (!(flags & sec.flags)) continue;
+        if ((m->kind == FFHIP_NET_LSTM5_RLE) != sec.rle || (sec.nbase && m->nbase != sec.nbase)) return set_err(FFHIP_EINVAL, "%s", sec.model_text);
+        if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "%s", sec.undecoded_text);
+        if (int rc = b->res.ensure((ResSec)i, b->stream)) return rc;
     }
     if (b->packed && !p.packable)
         return set_err(FFHIP_EINVAL, "packed batches take the default path and the launch-per-step kernels only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / unfused flags, ordinary temperature)");
@@ -1626,20 +1504,20 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
     if (full_chip && by_layers && eng->persist_chained) HIP_TRY(hipStreamWaitEvent(s, eng->persist_done, 0), FFHIP_EHIP);
     else if (full_chip && !by_layers && fo[0] == 'b' && !paired && eng->batch_done_rec) HIP_TRY(hipStreamWaitEvent(s, eng->batch_done, 0), FFHIP_EHIP);
     mark(b, 0);                                        // (behind the wait: the convolution group's time is its kernels')
-    HIP_TRY(hipMemsetAsync(b->sat, 0, (size_t)Bp * sizeof(unsigned), s), FFHIP_EHIP);
+    HIP_TRY(hipMemsetAsync(b->sat(), 0, (size_t)Bp * sizeof(unsigned), s), FFHIP_EHIP);
     for (int i = 0; i < 4; i++) b->forms[i] = kFormNone;
     for (int l = 0; l < m->nconv; l++) {
         const ConvDev &c = m->conv[l];
         const int *x0a = b->ragged ? b->rag_x0a[l] : b->plan[l].x0a, *x0b = b->ragged ? b->rag_x0b[l] : b->plan[l].x0b, ldp = b->ragged ? b->plan[l].Tout : 0;
         if (l < m->nconv - 1)
             b->forms[l] = launch_conv_small(s, b->sbuf[l], b->sbuf[l + 1], c.taps, c.bias, x0a, x0b, Bp, b->plan[l].Tout, c.winlen, m->act, ldp, (b->ragged && !b->packed) ? b->rag_tin[l] : nullptr,
-                              (p.conv_f16 && l == m->nconv - 2) ? kSplitExpX : -100000, b->sat, (b->packed && m->conv[l].stride == 1) ? b->rag_seg[l] : nullptr);
+                              (p.conv_f16 && l == m->nconv - 2) ? kSplitExpX : -100000, b->sat(), (b->packed && m->conv[l].stride == 1) ? b->rag_seg[l] : nullptr);
         else if (p.conv_f16)
             b->forms[l] = launch_conv_split(s, b->sbuf[l], b->fa[0], c.Wsplit, c.bias, x0a, x0b, B16, Tb, c.Mpad, c.winlen, m->act, ldp, p.conv_split ? b->actS[0] : nullptr,
-                              kSplitExpX, c.split_S, lean_conv, b->sat);
+                              kSplitExpX, c.split_S, lean_conv, b->sat());
         else
             b->forms[l] = launch_conv_mfma(s, b->sbuf[l], b->fa[0], c.Wp, c.bias, x0a, x0b, B16, Tb, c.Mpad, c.K16, m->act, ldp, p.conv_split ? b->actS[0] : nullptr,
-                             m->act == ACT_SWISH ? kSplitExpX : kSplitExpH, b->sat, c.winlen * c.Fin);
+                             m->act == ACT_SWISH ? kSplitExpX : kSplitExpH, b->sat(), c.winlen * c.Fin);
         b->launches[0]++;
     }
     if (int rc = keep_copy(b, 0, b->fa[0])) return rc;
@@ -1653,9 +1531,9 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
         b->front_kept = 1;
     }
     mark(b, 1);
-    HIP_TRY(hipMemsetAsync(b->pabort, (p.persist && dbg("force_abort")) ? 1 : 0, sizeof(unsigned), s), FFHIP_EHIP);      // (debug: pretend a wait timed out)
+    HIP_TRY(hipMemsetAsync(b->pabort(), (p.persist && dbg("force_abort")) ? 1 : 0, sizeof(unsigned), s), FFHIP_EHIP);      // (debug: pretend a wait timed out)
     if ((p.split || p.split2) && !p.conv_split) {
-        launch_split_from_f32(s, b->fa[0], b->actS[0], (size_t)Tb * B16, Hp, m->act == ACT_SWISH ? kSplitExpX : kSplitExpH, b->sat, B16);
+        launch_split_from_f32(s, b->fa[0], b->actS[0], (size_t)Tb * B16, Hp, m->act == ACT_SWISH ? kSplitExpX : kSplitExpH, b->sat(), B16);
         b->launches[0]++;
     }
     b->run_cur = 0;
@@ -1678,7 +1556,7 @@ static int project(ffhip_batch *b, int l, const float *in, int n, float *xa, voi
     if (r.Wsplit && b->run_path.proj_split) {
         if (!*split && !(*split = dalloc(b, split_bytes((size_t)n * B16, Hp), false))) return FFHIP_ENOMEM;
         // (sat: the flag is the read tile's, tile % B16 -- a range of whole steps keeps it)
-        launch_split_from_f32(s, in, *split, (size_t)n * B16, Hp, (l == 0 && m->act == ACT_SWISH) ? kSplitExpX : kSplitExpH, b->sat, B16);
+        launch_split_from_f32(s, in, *split, (size_t)n * B16, Hp, (l == 0 && m->act == ACT_SWISH) ? kSplitExpX : kSplitExpH, b->sat(), B16);
         launch_inproj_split(s, *split, xa, r.Wsplit, r.bias, n * B16, Hp, r.split_S);
         b->launches[1] += 2;
     } else {
@@ -1721,7 +1599,7 @@ static int run_layers(ffhip_batch *b) {
                 HIP_TRY(hipMemsetAsync(b->pflags, 0, split_flag_words(nrt) * sizeof(unsigned), s), FFHIP_EHIP);
                 const bool chain = 2 * ((B16 + 1) / 2) * 32 > ncu;
                 if (int rc = layer_wait(eng, s, chain)) return rc;
-                if (!launch_rnn_split(s, r.Wsplit, b->xa, b->actS[cur ^ 1], out_f32, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt,
+                if (!launch_rnn_split(s, r.Wsplit, b->xa, b->actS[cur ^ 1], out_f32, b->pflags, b->pabort(), Tb, B16, Hp, rt0, nrt,
                                       backward, p.persist_mode, r.split_S, tbs, tbt))
                     return set_err(FFHIP_EINVAL, "split recurrent kernel: unsupported shape");
                 if (int rc = layer_launched(eng, s, chain)) return rc;
@@ -1757,8 +1635,8 @@ static int run_layers(ffhip_batch *b) {
                 const bool chain = !b->persist_concurrent_ok;
                 if (int rc = layer_wait(eng, s, chain)) return rc;
                 const bool okl = fuse
-                    ? launch_lstm_fused(s, m->cell, r.sWp, r.iWp, r.bias, in, out, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt, backward, p.persist_mode, tbs, tbt)
-                    : launch_rnn_persist(s, m->cell, r.sWp, b->xa, out, b->pflags, b->pabort, Tb, B16, Hp, rt0, nrt, backward, p.persist_mode, tbs, tbt);
+                    ? launch_lstm_fused(s, m->cell, r.sWp, r.iWp, r.bias, in, out, b->pflags, b->pabort(), Tb, B16, Hp, rt0, nrt, backward, p.persist_mode, tbs, tbt)
+                    : launch_rnn_persist(s, m->cell, r.sWp, b->xa, out, b->pflags, b->pabort(), Tb, B16, Hp, rt0, nrt, backward, p.persist_mode, tbs, tbt);
                 if (!okl) return set_err(FFHIP_EINVAL, "persistent recurrent kernel: unsupported shape");
                 if (int rc = layer_launched(eng, s, chain)) return rc;
                 b->launches[2]++;
@@ -1843,6 +1721,7 @@ static int run_back(ffhip_batch *b) {
     }
     if (!p.post_done) mark(b, 4);
     b->last_flags = flags;
+    b->res_made = res_sections_of(flags, b->res.held);      // (run_front checked the flags against the model and grew the block)
     if (!(flags & FFHIP_RUN_NO_DECODE)) {
         const float *scores = b->trans;
         if (!(flags & FFHIP_RUN_VITERBI_ONLY) || (flags & FFHIP_RUN_MOD_PROBS)) {
@@ -1856,28 +1735,25 @@ static int run_back(ffhip_batch *b) {
         if (rle) {
             // decode_crf_runlength (decode.c:927-1013); the run records are formed from the path by the caller
             // (runnie.c:282-313), there are no base/quality strings or trace for this model
-            launch_rle_viterbi(s, scores, b->tb, b->path, b->qpath, b->score, nR, Tb, m->nbase, m->Ps, tbr, rmap);
+            launch_rle_viterbi(s, scores, b->tb, b->path, b->qpath, b->score(), nR, Tb, m->nbase, m->Ps, tbr, rmap);
             if (flags & (FFHIP_RUN_RLE_RUNS | FFHIP_RUN_RLE_RECORDS)) {      // run records from the path and the matrix the host loop reads (runnie.c:282-313)
-                launch_rle_runs(s, scores, b->path, nR, Tb, m->nbase, m->Ps, tbr, rmap, b->run_scale, b->runs_dev);
-                b->runs_valid = (flags & FFHIP_RUN_RLE_RECORDS) ? 2 : 1;
+                launch_rle_runs(s, scores, b->path, nR, Tb, m->nbase, m->Ps, tbr, rmap, b->run_scale, rle_run_out(b->res, false, (flags & FFHIP_RUN_RLE_RECORDS) != 0));
                 b->launches[5]++;
             }
-            HIP_TRY(hipMemsetAsync(b->lens, 0, (size_t)nR * 4, s), FFHIP_EHIP);
-            HIP_TRY(hipMemsetAsync(b->bases, 0, (size_t)b->nread * (Tb + 1), s), FFHIP_EHIP);
-            HIP_TRY(hipMemsetAsync(b->quals, 0, (size_t)b->nread * (Tb + 1), s), FFHIP_EHIP);
+            HIP_TRY(hipMemsetAsync(b->lens(), 0, (size_t)nR * 4, s), FFHIP_EHIP);
+            HIP_TRY(hipMemsetAsync(b->bases(), 0, (size_t)b->nread * (Tb + 1), s), FFHIP_EHIP);
+            HIP_TRY(hipMemsetAsync(b->quals(), 0, (size_t)b->nread * (Tb + 1), s), FFHIP_EHIP);
             b->launches[5]++;
         } else {
-            launch_viterbi(s, scores, b->tb, b->path, b->qpath, b->score, nR, Tb, m->nbase, m->Ps, tbr, rmap);
-            launch_assemble(s, b->path, b->qpath, b->bases, b->quals, b->lens, nR, Tb, m->nbase, tbr, rmap);
+            launch_viterbi(s, scores, b->tb, b->path, b->qpath, b->score(), nR, Tb, m->nbase, m->Ps, tbr, rmap);
+            launch_assemble(s, b->path, b->qpath, b->bases(), b->quals(), b->lens(), nR, Tb, m->nbase, tbr, rmap);
             b->launches[5] += 2;
             if (flags & FFHIP_RUN_MOD_PROBS) {          // from the posterior whatever decoded the path (run_front checked the model)
-                launch_mod_probs(s, b->post, b->path, b->ml_dev, nR, Tb, m->Ps, tbr, rmap);
-                b->mod_valid = 1;
+                launch_mod_probs(s, b->post, b->path, b->res.on_dev<uint8_t>(RF_ML), nR, Tb, m->Ps, tbr, rmap);
                 b->launches[5]++;
             }
             if (flags & FFHIP_RUN_MOVES) {
-                launch_moves(s, b->path, b->mv_dev, nR, Tb, tbr, rmap);
-                b->mv_valid = 1;
+                launch_moves(s, b->path, b->res.on_dev<uint8_t>(RF_MV), nR, Tb, tbr, rmap);
                 b->launches[5]++;
             }
             if (!(flags & FFHIP_RUN_NO_TRACE)) {
@@ -1894,7 +1770,7 @@ static int run_back(ffhip_batch *b) {
     // and in front of the events the next batch's layer launches wait for.
     b->res_copied = 0;
     if (b->packed) {
-        HIP_TRY(hipMemcpyAsync(b->res_host, b->res_dev, res_copy_bytes(b, flags), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+        HIP_TRY(hipMemcpyAsync(b->res.host, b->res.dev, b->res.copy_bytes(flags), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
         b->res_copied = 1;
     }
     HIP_TRY(hipEventRecord(eng->batch_done, s), FFHIP_EHIP); eng->batch_done_rec = 1;
@@ -1916,6 +1792,7 @@ static int batch_run_impl(ffhip_batch *b, float temperature, unsigned flags) {
 // ---- host-load rehearsal: the run side (see rehearsal_rate() at the top of this file)
 static double now_seconds() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
+    if (b->packed) return set_err(FFHIP_EINVAL, "packed batches are not part of the host-load rehearsal");      // (hT / hTb hold a packed batch's READS, not its rows)
     hipSetDevice(b->eng->device);
     hipStream_t s = b->stream;
     const size_t n = (size_t)b->nread, L = (size_t)b->Tb + 1;
@@ -1927,30 +1804,31 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
     w = w * 2 / 5;                                        // placeholder calls: 0.4 'A' per block of the batch's shortest read, NUL-terminated rows
     for (size_t r = 0; r < n; r++) { lens[r] = b->hTb[r] > 0 ? w : 0; samples += b->hT[r]; }
     if (rehearsal_nogpu()) {                              // the host mirrors ffhip_batch_finish would have filled
-        memset(b->h_bases, 0, n * L); memset(b->h_quals, 0, n * L);
-        for (size_t r = 0; r < n; r++) { memset(b->h_bases + r * L, 'A', (size_t)lens[r]); memset(b->h_quals + r * L, '5', (size_t)lens[r]); b->h_lens[r] = lens[r]; b->h_score[r] = 0.0f; }
-        *b->h_abort = 0; memset(b->h_sat, 0, (size_t)b->Bp * sizeof(unsigned));
-        const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
-        b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
-        b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-        b->ran = 1; b->finished = 0; b->paired_last = 0; b->runs_valid = 0; b->mod_valid = 0; b->mv_valid = 0;
-        return FFHIP_OK;
+        char *hb = (char *)memset(b->res.on_host<char>(RF_BASES), 0, n * L), *hq = (char *)memset(b->res.on_host<char>(RF_QUALS), 0, n * L);
+        for (size_t r = 0; r < n; r++) { memset(hb + r * L, 'A', (size_t)lens[r]); memset(hq + r * L, '5', (size_t)lens[r]); b->h_lens()[r] = lens[r]; b->res.on_host<float>(RF_SCORE)[r] = 0.0f; }
+        b->h_abort()[0] = 0; memset(b->h_sat(), 0, (size_t)b->Bp * sizeof(unsigned));
+    } else {
+        HIP_TRY(hipMemsetAsync(b->bases(), 0, n * L, s), FFHIP_EHIP);
+        HIP_TRY(hipMemsetAsync(b->quals(), 0, n * L, s), FFHIP_EHIP);
+        if (w > 0) {
+            HIP_TRY(hipMemset2DAsync(b->bases(), L, 'A', (size_t)w, n, s), FFHIP_EHIP);
+            HIP_TRY(hipMemset2DAsync(b->quals(), L, '5', (size_t)w, n, s), FFHIP_EHIP);
+        }
+        HIP_TRY(hipMemsetAsync(b->score(), 0, n * 4, s), FFHIP_EHIP);
+        HIP_TRY(hipMemsetAsync(b->pabort(), 0, sizeof(unsigned), s), FFHIP_EHIP);
+        HIP_TRY(hipMemsetAsync(b->sat(), 0, (size_t)b->Bp * sizeof(unsigned), s), FFHIP_EHIP);
+        HIP_TRY(hipMemcpyAsync(b->lens(), lens, n * 4, hipMemcpyHostToDevice, s), FFHIP_EHIP);
     }
-    HIP_TRY(hipMemsetAsync(b->bases, 0, n * L, s), FFHIP_EHIP);
-    HIP_TRY(hipMemsetAsync(b->quals, 0, n * L, s), FFHIP_EHIP);
-    if (w > 0) {
-        HIP_TRY(hipMemset2DAsync(b->bases, L, 'A', (size_t)w, n, s), FFHIP_EHIP);
-        HIP_TRY(hipMemset2DAsync(b->quals, L, '5', (size_t)w, n, s), FFHIP_EHIP);
-    }
-    HIP_TRY(hipMemsetAsync(b->score, 0, n * 4, s), FFHIP_EHIP);
-    HIP_TRY(hipMemsetAsync(b->pabort, 0, sizeof(unsigned), s), FFHIP_EHIP);
-    HIP_TRY(hipMemsetAsync(b->sat, 0, (size_t)b->Bp * sizeof(unsigned), s), FFHIP_EHIP);
-    HIP_TRY(hipMemcpyAsync(b->lens, lens, n * 4, hipMemcpyHostToDevice, s), FFHIP_EHIP);
     const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
     b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
     b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-    b->ran = 1; b->finished = 0; b->paired_last = 0; b->runs_valid = 0; b->mod_valid = 0; b->mv_valid = 0;
+    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0;
     return FFHIP_OK;
+}
+
+static void rehearsal_wait(const ffhip_batch *b) {
+    const double left = b->rehearsal_done_at - now_seconds();
+    if (left > 0) { struct timespec ts = { (time_t)left, (long)((left - (double)(time_t)left) * 1e9) }; nanosleep(&ts, nullptr); }
 }
 
 extern "C" int ffhip_batch_run(ffhip_batch *b, float temperature, unsigned flags) {
@@ -2000,7 +1878,7 @@ extern "C" int ffhip_batch_run_pair(ffhip_batch *b0, ffhip_batch *b1, float temp
 
 extern "C" int ffhip_batch_paired(const ffhip_batch *b) { return (b && b->paired_last) ? 1 : 0; }
 
-// Reads of a finished batch that left the split format's range (b->h_sat) again, 16 at a time, through the all-f32 kernels, which
+// Reads of a finished batch that left the split format's range (b->h_sat()) again, 16 at a time, through the all-f32 kernels, which
 // have no bound (the reference has none: layers.c:24-33); their results replace the clamped ones in the batch's buffers.  Rare by
 // construction -- a normalised sample in the hundreds -- so this path is written for clarity: a side batch of 16 slots with the
 // same capacity (hence the same strides: a read's results are contiguous device-to-device copies), created on first use.
@@ -2039,38 +1917,17 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
             if (!(fl & FFHIP_RUN_VITERBI_ONLY) || (fl & FFHIP_RUN_MOD_PROBS)) HIP_TRY(hipMemcpyAsync(b->post + r0 * Ps, sd->post + (size_t)k * Tb * Ps, nb * Ps * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
             HIP_TRY(hipMemcpyAsync(b->path + r1, sd->path + (size_t)k * L, nb1 * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
             HIP_TRY(hipMemcpyAsync(b->qpath + r1, sd->qpath + (size_t)k * L, nb1 * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-            HIP_TRY(hipMemcpyAsync(b->score + r, sd->score + k, 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-            HIP_TRY(hipMemcpyAsync(b->bases + r1, sd->bases + (size_t)k * L, nb1, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-            HIP_TRY(hipMemcpyAsync(b->quals + r1, sd->quals + (size_t)k * L, nb1, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-            HIP_TRY(hipMemcpyAsync(b->lens + r, sd->lens + k, 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
             if (!(fl & FFHIP_RUN_NO_TRACE) && m->kind != FFHIP_NET_LSTM5_RLE)
                 HIP_TRY(hipMemcpyAsync(b->trace + r1 * ns, sd->trace + (size_t)k * L * ns, nb1 * ns * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-            if (b->runs_valid && sd->runs_valid) {      // the run records of the f32 run (its own copy came down in its result block)
-                const size_t k1 = (size_t)k * L;
-                const RleRunOut &dd = b->runs_dev, &sdd = sd->runs_dev, &hh = b->runs_host, &sh = sd->runs_host;
-                HIP_TRY(hipMemcpyAsync(dd.base + r1, sdd.base + k1, nb1, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                HIP_TRY(hipMemcpyAsync(dd.est + r1, sdd.est + k1, nb1 * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                memcpy(hh.base + r1, sh.base + k1, nb1); memcpy(hh.est + r1, sh.est + k1, nb1 * 4);
-                if (b->runs_valid == 2) {
-                    HIP_TRY(hipMemcpyAsync(dd.shape + r1, sdd.shape + k1, nb1 * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                    HIP_TRY(hipMemcpyAsync(dd.scale + r1, sdd.scale + k1, nb1 * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                    HIP_TRY(hipMemcpyAsync(dd.dwell + r1, sdd.dwell + k1, nb1 * 4, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                    memcpy(hh.shape + r1, sh.shape + k1, nb1 * 4); memcpy(hh.scale + r1, sh.scale + k1, nb1 * 4); memcpy(hh.dwell + r1, sh.dwell + k1, nb1 * 4);
-                }
-                hh.nrun[r] = sh.nrun[k]; hh.fail[r] = sh.fail[k]; hh.len[r] = sh.len[k];
+            // the result block: every patched field of the sections both runs filled, device half and host half (the f32 run's own copy came down in its block)
+            for (int f = 0; f < RF_COUNT; f++) {
+                const ResFieldRow &fr = kResFields[f];
+                if (fr.patch == PATCH_NONE || !(b->res_made & sd->res_made & res_bit(fr.sec))) continue;
+                const bool one = fr.ext == PER_READ;
+                const size_t to = (one ? r : r1) * fr.elem, from = (one ? (size_t)k : (size_t)k * L) * fr.elem, bytes = (one ? 1 : fr.patch == PATCH_BLOCKS ? nb : nb1) * fr.elem;
+                HIP_TRY(hipMemcpyAsync(b->res.on_dev<char>((ResField)f) + to, sd->res.on_dev<char>((ResField)f) + from, bytes, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                memcpy(b->res.on_host<char>((ResField)f) + to, sd->res.on_host<char>((ResField)f) + from, bytes);
             }
-            if (b->mod_valid && sd->mod_valid) {        // the 5mC bytes of the f32 run (down in its result block, as its strings)
-                HIP_TRY(hipMemcpyAsync(b->ml_dev + r1, sd->ml_dev + (size_t)k * L, nb1, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                memcpy(b->ml_host + r1, sd->ml_host + (size_t)k * L, nb1);
-            }
-            if (b->mv_valid && sd->mv_valid) {          // and its move table
-                HIP_TRY(hipMemcpyAsync(b->mv_dev + r1, sd->mv_dev + (size_t)k * L, nb, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                memcpy(b->mv_host + r1, sd->mv_host + (size_t)k * L, nb);
-            }
-            memcpy(b->h_bases + r1, sd->h_bases + (size_t)k * L, nb1);
-            memcpy(b->h_quals + r1, sd->h_quals + (size_t)k * L, nb1);
-            b->h_lens[r] = sd->h_lens[k];
-            b->h_score[r] = sd->h_score[k];
         }
         HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
     }
@@ -2084,23 +1941,19 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
     if (!b->ran) return set_err(FFHIP_EINVAL, "ffhip_batch_run has not been called");
     hipSetDevice(b->eng->device);
     if (rehearsal_nogpu()) {                                 // test hook (top of this file): the results are on the host already
-        const double left = b->rehearsal_done_at - now_seconds();
-        if (left > 0) { struct timespec ts = { (time_t)left, (long)((left - (double)(time_t)left) * 1e9) }; nanosleep(&ts, nullptr); }
+        rehearsal_wait(b);
         if (b->counted) { b->counted = 0; b->eng->in_flight--; }
         b->finished = 1; b->reruns = 0;
         return FFHIP_OK;
     }
     // one copy: [sat | abort] and, when the batch was decoded, [lens | score | bases | quals] behind them (the block of ffhip_batch_create)
-    if (!b->res_copied) HIP_TRY(hipMemcpyAsync(b->res_host, b->res_dev, res_copy_bytes(b, b->last_flags), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
+    if (!b->res_copied) HIP_TRY(hipMemcpyAsync(b->res.host, b->res.dev, b->res.copy_bytes(b->last_flags), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
     b->res_copied = 0;
     HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
-    if (rehearsal_rate() > 0) {                              // (test hook above: the emulated GPU finishes this batch at rehearsal_done_at)
-        const double left = b->rehearsal_done_at - now_seconds();
-        if (left > 0) { struct timespec ts = { (time_t)left, (long)((left - (double)(time_t)left) * 1e9) }; nanosleep(&ts, nullptr); }
-    }
+    if (rehearsal_rate() > 0) rehearsal_wait(b);          // (test hook above: the emulated GPU finishes this batch at rehearsal_done_at)
     if (b->counted) { b->counted = 0; b->eng->in_flight--; }
     HIP_TRY(hipGetLastError(), FFHIP_EHIP);
-    if (*b->h_abort != 0) {
+    if (b->h_abort()[0] != 0) {
         if ((b->last_flags & FFHIP_RUN_STEPWISE_RNN) || getenv("FFHIP_NO_FALLBACK"))
             return set_err(FFHIP_ETIMEOUT, "persistent recurrent kernel: an inter-workgroup wait timed out; results are invalid");
         // Not every workgroup of a persistent layer launch became resident -- something else holds part of the GPU.  The
@@ -2114,13 +1967,13 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
         if (rc != FFHIP_OK) return rc;
         return ffhip_batch_finish(b);
     }
-    if (b->packed && b->h_abort[2] != 0) return set_err(FFHIP_EINVAL, "packed batch: a read's convolution columns take more than two windows (not a shape of the reference's models)");
+    if (b->packed && b->h_abort()[2] != 0) return set_err(FFHIP_EINVAL, "packed batch: a read's convolution columns take more than two windows (not a shape of the reference's models)");
     b->finished = 1;
     b->reruns = 0;
     if (!b->is_side) {
         std::vector<int> over;
-        if (b->packed) { for (int v = 0; v < b->nvirt; v++) if (b->h_sat[b->v_slot[v]]) over.push_back(v); }      // (the flag is the row's: every read of it goes again)
-        else for (int r = 0; r < b->nread; r++) if (b->h_sat[r] && b->hT[r] > 0) over.push_back(r);
+        if (b->packed) { for (int v = 0; v < b->nvirt; v++) if (b->h_sat()[b->v_slot[v]]) over.push_back(v); }      // (the flag is the row's: every read of it goes again)
+        else for (int r = 0; r < b->nread; r++) if (b->h_sat()[r] && b->hT[r] > 0) over.push_back(r);
         if (!over.empty()) if (int rc = rerun_on_f32_path(b, over)) { b->finished = 0; return rc; }
     }
     return FFHIP_OK;
@@ -2137,16 +1990,16 @@ static bool results_ok(const ffhip_batch *b, int read) {
 
 extern "C" const char *ffhip_batch_basecall(const ffhip_batch *b, int read, size_t *length) {
     if (!results_ok(b, read) || (b->last_flags & FFHIP_RUN_NO_DECODE)) return nullptr;
-    if (length) *length = (size_t)b->h_lens[read];
-    return b->h_bases + read_row1(b, read);
+    if (length) *length = (size_t)b->h_lens()[read];
+    return b->res.on_host<char>(RF_BASES) + read_row1(b, read);
 }
 extern "C" const char *ffhip_batch_quality(const ffhip_batch *b, int read) {
     if (!results_ok(b, read) || (b->last_flags & FFHIP_RUN_NO_DECODE)) return nullptr;
-    return b->h_quals + read_row1(b, read);
+    return b->res.on_host<char>(RF_QUALS) + read_row1(b, read);
 }
 extern "C" float ffhip_batch_score(const ffhip_batch *b, int read) {
     if (!results_ok(b, read) || (b->last_flags & FFHIP_RUN_NO_DECODE)) return NAN;
-    return b->h_score[read];
+    return b->res.on_host<float>(RF_SCORE)[read];
 }
 
 extern "C" int ffhip_batch_set_run_scale(ffhip_batch *b, const double factor[4]) {
@@ -2158,32 +2011,32 @@ extern "C" int ffhip_batch_set_run_scale(ffhip_batch *b, const double factor[4])
 extern "C" int ffhip_batch_rle_runs(const ffhip_batch *b, int read, ffhip_rle_runs *out) {
     if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
     if (b->mdl->kind != FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "run records: not a run-length model");
-    if (!b->runs_valid) return set_err(FFHIP_EINVAL, "run records were not made in this run (FFHIP_RUN_RLE_RUNS)");
-    const RleRunOut &h = b->runs_host;
+    if (!(b->res_made & res_bit(RS_RUNS))) return set_err(FFHIP_EINVAL, "run records were not made in this run (FFHIP_RUN_RLE_RUNS)");
+    const RleRunOut h = rle_run_out(b->res, true, (b->res_made & res_bit(RS_RECORDS)) != 0);      // (shape, scale, dwell: null without the records)
     const size_t r1 = read_row1(b, read);
     out->nrun = (size_t)h.nrun[read];
     out->length = h.len[read];
     out->failed = h.fail[read];
     out->base = h.base + r1;
     out->est = h.est + r1;
-    out->shape = b->runs_valid == 2 ? h.shape + r1 : nullptr;
-    out->scale = b->runs_valid == 2 ? h.scale + r1 : nullptr;
-    out->dwell = b->runs_valid == 2 ? h.dwell + r1 : nullptr;
+    out->shape = h.shape ? h.shape + r1 : nullptr;
+    out->scale = h.scale ? h.scale + r1 : nullptr;
+    out->dwell = h.dwell ? h.dwell + r1 : nullptr;
     return FFHIP_OK;
 }
 
 extern "C" int ffhip_batch_mod_probs(const ffhip_batch *b, int read, const uint8_t **ml, size_t *length) {
     if (!results_ok(b, read) || !ml) return FFHIP_EINVAL;
-    if (!b->mod_valid || !b->ml_host) return set_err(FFHIP_EINVAL, "5mC probabilities were not made in this run (FFHIP_RUN_MOD_PROBS)");
-    *ml = b->ml_host + read_row1(b, read);
-    if (length) *length = (size_t)b->h_lens[read];
+    if (!(b->res_made & res_bit(RS_MOD))) return set_err(FFHIP_EINVAL, "5mC probabilities were not made in this run (FFHIP_RUN_MOD_PROBS)");
+    *ml = b->res.on_host<uint8_t>(RF_ML) + read_row1(b, read);
+    if (length) *length = (size_t)b->h_lens()[read];
     return FFHIP_OK;
 }
 
 extern "C" int ffhip_batch_moves(const ffhip_batch *b, int read, const uint8_t **moves, size_t *nblock) {
     if (!results_ok(b, read) || !moves) return FFHIP_EINVAL;
-    if (!b->mv_valid || !b->mv_host) return set_err(FFHIP_EINVAL, "the move table was not made in this run (FFHIP_RUN_MOVES)");
-    *moves = b->mv_host + read_row1(b, read);
+    if (!(b->res_made & res_bit(RS_MOVES))) return set_err(FFHIP_EINVAL, "the move table was not made in this run (FFHIP_RUN_MOVES)");
+    *moves = b->res.on_host<uint8_t>(RF_MV) + read_row1(b, read);
     if (nblock) *nblock = (size_t)b->hTb[read];
     return FFHIP_OK;
 }
@@ -2316,7 +2169,7 @@ extern "C" int ffhip_debug_batch_head_input(ffhip_batch *b, int row, float *out)
 }
 
 extern "C" int ffhip_debug_fallback_count(const ffhip_engine *eng) { return eng ? eng->fallbacks : -1; }
-extern "C" size_t ffhip_debug_batch_device_bytes(const ffhip_batch *b) { return b ? b->dev_bytes : 0; }
+extern "C" size_t ffhip_debug_batch_device_bytes(const ffhip_batch *b) { return b ? b->dev_bytes + b->res.cap : 0; }
 extern "C" int ffhip_debug_split_plan(int kind, int hidden, int remaining, int ncu, int beside, int out[6]) {
     if (!out) return set_err(FFHIP_EINVAL, "ffhip_debug_split_plan: out is NULL");
     const SplitPlan p = split_plan(kind, hidden, remaining, ncu, beside);
@@ -2324,12 +2177,18 @@ extern "C" int ffhip_debug_split_plan(int kind, int hidden, int remaining, int n
     memcpy(out, v, sizeof(v));
     return FFHIP_OK;
 }
+extern "C" int ffhip_debug_result_layout(int nread, int cap_reads, int Tb, unsigned sections, size_t *out, int nout) {
+    if (!out || nout < RF_COUNT + RS_COUNT || nread <= 0 || Tb <= 0) return set_err(FFHIP_EINVAL, "ffhip_debug_result_layout: bad arguments (out takes %d values)", RF_COUNT + RS_COUNT);
+    const ResLayout o = result_layout((nread + 15) / 16 * 16, std::max(cap_reads, nread), nread, Tb, sections | kResAlways);
+    memcpy(out, o.field, sizeof(o.field)); memcpy(out + RF_COUNT, o.end, sizeof(o.end));
+    return FFHIP_OK;
+}
 extern "C" int ffhip_debug_split_pair_ok(int kind, int hidden, int nrt, int ncu) { return split_pair_ok(kind, hidden, nrt, ncu) ? 1 : 0; }
 
 // development counter next to the abort word (e.g. re-sweeps of the split layer kernel in builds that count them)
 extern "C" unsigned ffhip_debug_batch_counter(ffhip_batch *b) {
     unsigned v = 0;
-    if (b) { hipSetDevice(b->eng->device); hipMemcpy(&v, b->pabort + 1, 4, hipMemcpyDeviceToHost); }
+    if (b) { hipSetDevice(b->eng->device); hipMemcpy(&v, b->pabort() + 1, 4, hipMemcpyDeviceToHost); }
     return v;
 }
 

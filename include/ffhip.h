@@ -457,6 +457,12 @@ int ffhip_debug_fallback_count(const ffhip_engine *eng);
 int ffhip_debug_split_plan(int kind, int hidden, int remaining, int ncu, int beside, int out[6]);
 /* 1 if two batches of `nrt` read tiles each may share paired layer launches (ffhip_batch_run_pair), else 0; reads FFHIP_DEBUG (no_dense, no_pair); no engine, no device */
 int ffhip_debug_split_pair_ok(int kind, int hidden, int nrt, int ncu);
+/* where the fields of a batch's result block lie (the block ffhip_batch_finish brings down in one copy; needs no engine, touches no device): for a batch of `nread`
+ * rows taking `cap_reads` reads (at least nread) of `Tb` blocks a row whose block holds `sections` (bit 2 run records' base and estimate, 3 their shape / scale /
+ * dwell, 4 5mC bytes, 5 move table; head and core always), out = { byte offsets of sat, abort, lens, score, bases, quals, nrun, fail, len, base, est, shape, scale,
+ * dwell, ml, mv; ends of the sections head, core, runs, records, mod, moves } -- 22 values, a section the block lacks where it would be added.
+ * Returns FFHIP_OK, or FFHIP_EINVAL (no `out`, nout < 22, nread or Tb < 1) */
+int ffhip_debug_result_layout(int nread, int cap_reads, int Tb, unsigned sections, size_t *out, int nout);
 /* device memory the batch holds (its buffers, grown on first use by the paths its runs took): a packed batch's launch-per-step run adds less than one
  * activation buffer to what its default run holds -- the in-projection is computed a window of steps at a time */
 size_t ffhip_debug_batch_device_bytes(const ffhip_batch *b);

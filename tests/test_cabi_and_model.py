@@ -4,6 +4,7 @@ package never touches the oracle."""
 import ctypes as C
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -193,3 +194,43 @@ def test_synthetic_models_are_input_driven(kind, hidden, seed):
             stays = int(np.sum(a["path"][1:] == a["path"][:-1]))
             assert 0 < stays < a["nblock"]                       # stays and moves both occur
             assert float(np.abs(other - a["trans"]).max()) < 5e-5
+
+
+_REHEARSAL_PACKED = """
+import numpy as np
+from flappie_amd import binding as B, model as M
+eng = B.Engine(0)
+dm = B.DeviceModel(eng, M.synthetic_model(M.NET_LSTM5, 128, seed=1))
+sigs = [np.random.default_rng(k).standard_normal(n).astype(np.float32) for k, n in enumerate((900, 400, 700))]
+pb = B.Batch(dm, 16, 2000, max_reads=3)
+slot, off = pb.pack_plan([x.size for x in sigs])
+try:
+    pb.set_signals_packed(sigs, slot, off)
+    raise SystemExit("a packed batch was accepted under the rehearsal")
+except B.FFHipError as e:
+    assert "packed batches are not part of the host-load rehearsal" in str(e), e
+b = B.Batch(dm, 3, 2000)                 # one read a row: the rehearsal's placeholder calls, 0.4 'A' a block of the shortest read
+b.set_signals_ragged(sigs)
+b.run(1.0, B.RUN_MOVES)
+b.finish()
+w = min(b.read_nblock(r) for r in range(3)) * 2 // 5
+assert w > 0 and all(b.basecall(r) == "A" * w and b.quality(r) == "5" * w for r in range(3))
+try:
+    b.moves(0)
+    raise SystemExit("the rehearsal made no move table")
+except B.FFHipError:
+    pass
+print("rehearsal ok")
+"""
+
+
+@pytest.mark.gpu
+def test_rehearsal_rejects_packed_batches():
+    """the hooks build under FFHIP_DEBUG_HOST_REHEARSAL_MSPS: a packed batch's set call is FFHIP_EINVAL (its per-read lengths are not what the rehearsal's
+    per-row placeholder results index), a batch of one read a row gets the placeholder calls"""
+    import subprocess
+    hooks = os.path.join(ROOT, "tools", "test_hooks", "libffhip.so")
+    assert os.path.exists(hooks), "tools/test_hooks/libffhip.so is missing: `make -C flappie_amd/csrc hooks`"
+    env = dict(os.environ, FFHIP_BINDING_LIBRARY=hooks, FFHIP_DEBUG_HOST_REHEARSAL_MSPS="1000", PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, "-c", _REHEARSAL_PACKED], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "rehearsal ok" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
