@@ -79,6 +79,11 @@ class CRawTable(C.Structure):
                 ("raw", C.POINTER(C.c_float))]
 
 
+class CDacRead(C.Structure):
+    """`ffhip_dac_read` of include/ffhip.h"""
+    _fields_ = [("dac", C.POINTER(C.c_int16)), ("n", C.c_size_t), ("offset", C.c_float), ("raw_unit", C.c_float)]
+
+
 def library_path() -> str:
     # FFHIP_BINDING_LIBRARY: another build of the same C-ABI (tests only: tools/test_hooks/libffhip_resweep.so, the library whose layer kernels re-sweep on purpose)
     return os.environ.get("FFHIP_BINDING_LIBRARY") or os.path.join(_HERE, "libffhip.so")
@@ -127,6 +132,10 @@ def lib():
     L.ffhip_prep_create.argtypes = [vp, C.POINTER(CRawTable), C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_int, C.c_float]
     L.ffhip_prep_begin.restype = vp
     L.ffhip_prep_begin.argtypes = L.ffhip_prep_create.argtypes
+    L.ffhip_prep_create_dac.restype = vp
+    L.ffhip_prep_create_dac.argtypes = [vp, C.POINTER(CDacRead)] + L.ffhip_prep_create.argtypes[2:]
+    L.ffhip_prep_begin_dac.restype = vp
+    L.ffhip_prep_begin_dac.argtypes = L.ffhip_prep_create_dac.argtypes
     L.ffhip_prep_finish.argtypes = [vp]
     L.ffhip_prep_destroy.argtypes = [vp]
     L.ffhip_prep_range.argtypes = [vp, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
@@ -317,10 +326,25 @@ class Prepared:
     """Raw reads trimmed and normalised on the device (ffhip_prep): trim_and_segment_raw + medmad_normalise_array."""
 
     def __init__(self, engine: "Engine", raws: List[np.ndarray], trim_start: int = 200, trim_end: int = 10,
-                 varseg_chunk: int = 100, varseg_thresh: float = 0.0, mode: int = PREP_MEDMAD, delta: float = 0.0, begin_only: bool = False):
-        """begin_only: ffhip_prep_begin (the work is enqueued, the call returns); `finish()` then waits -- ranges, statistics and signals are there after it"""
+                 varseg_chunk: int = 100, varseg_thresh: float = 0.0, mode: int = PREP_MEDMAD, delta: float = 0.0, begin_only: bool = False,
+                 calibrations=None):
+        """begin_only: ffhip_prep_begin (the work is enqueued, the call returns); `finish()` then waits -- ranges, statistics and signals are there after it.
+        calibrations: one (offset, raw_unit) per read -- `raws` are then int16 DAC values, scaled to picoamperes on the device (ffhip_prep_create_dac /
+        ffhip_prep_begin_dac).  varseg_chunk = 0 (either kind of input): no trimming at all, every read whole"""
         self.engine = engine
         self.n = len(raws)
+        if calibrations is not None:
+            if len(calibrations) != self.n:
+                raise ValueError("one (offset, raw_unit) per read")
+            darr = (CDacRead * self.n)()
+            keep = [np.ascontiguousarray(r, dtype=np.int16) for r in raws]
+            for i, r in enumerate(keep):
+                darr[i] = CDacRead(r.ctypes.data_as(C.POINTER(C.c_int16)), r.size, float(calibrations[i][0]), float(calibrations[i][1]))
+            fn = lib().ffhip_prep_begin_dac if begin_only else lib().ffhip_prep_create_dac
+            self.h = fn(engine.h, darr, self.n, trim_start, trim_end, varseg_chunk, varseg_thresh, mode, delta)
+            if not self.h:
+                raise FFHipError(lib().ffhip_last_error().decode())
+            return
         arr = (CRawTable * self.n)()
         keep = [np.ascontiguousarray(r, dtype=np.float32) for r in raws]
         for i, r in enumerate(keep):

@@ -307,7 +307,7 @@ extern "C" void ffhip_engine_destroy(ffhip_engine *e) {
     for (int i = 0; i < 4; i++) if (e->streams[i]) hipStreamDestroy(e->streams[i]);
     if (e->prep_stream) hipStreamDestroy(e->prep_stream);
     if (e->prep_pin) hipHostFree(e->prep_pin);
-    for (int i = 0; i < 4; i++) if (e->prep_scratch[i]) hipFree(e->prep_scratch[i]);
+    for (int i = 0; i < 5; i++) if (e->prep_scratch[i]) hipFree(e->prep_scratch[i]);
     for (auto &b : e->prep_pool) hipFree(b.first);
     if (e->persist_done) hipEventDestroy(e->persist_done);
     if (e->head_done) hipEventDestroy(e->head_done);

@@ -40,8 +40,9 @@ struct ffhip_engine {
     hipStream_t prep_stream = nullptr;
     void *prep_pin = nullptr;
     size_t prep_pin_cap = 0;
-    void *prep_scratch[4] = { nullptr, nullptr, nullptr, nullptr };
-    size_t prep_scratch_cap[4] = { 0, 0, 0, 0 };
+    void *prep_scratch[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };      // raw floats, chunk MADs, tables, statistics + calibrations, DAC values
+    size_t prep_scratch_cap[5] = { 0, 0, 0, 0, 0 };
+    ffhip_prep *prep_pending = nullptr;             // the one preparation begun and not finished (these buffers are its)
     std::vector<std::pair<void *, size_t>> prep_pool;       // free output buffers (pointer, bytes)
     double rehearsal_busy_until = 0.0;                      // FFHIP_DEBUG_HOST_REHEARSAL_MSPS (ffhip_engine.hip): when the emulated GPU is free again
 };

@@ -223,6 +223,42 @@ __global__ void __launch_bounds__(256) k_prep(PrepArgs a) {
     }
 }
 
+// ---- DAC values -> picoamperes, in front of k_prep (ffhip_prep_create_dac / _begin_dac) -------------------------------------
+// The reads stand back to back at offsets that are multiples of 4 elements, in `dac` as in `x`: the grid runs over the quads of the whole array -- a tile of
+// kDacTile samples a workgroup, so a read of any length is as many tiles as it holds and a chunk of short reads shares them -- and a thread finds its quad's
+// read in the offset table (a binary search once, then forwards).  A whole quad is one 8-byte load and one 16-byte store; the last quad of a read whose length
+// is no multiple of 4 goes element by element, and the padding behind it is neither read nor written.
+// (float)int16 is exact; the add and the multiply are rounded one by one, as the host loop (fast5_interface.c) rounds them.
+constexpr int kDacTile = 4096;
+__global__ void __launch_bounds__(256) k_dac_to_pa(const int16_t *__restrict__ dac, float *__restrict__ x, const size_t *__restrict__ off, const size_t *__restrict__ n,
+                                                   const float2 *__restrict__ cal, int nread, size_t nquad) {
+    size_t q = (size_t)blockIdx.x * (kDacTile / 4) + threadIdx.x;
+    if (q >= nquad) return;
+    int lo = 0, hi = nread - 1;                                            // the last read whose offset is <= 4 q
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= 4 * q) lo = mid; else hi = mid - 1;
+    }
+    int r = lo;
+    for (int k = 0; k < kDacTile / 4 / 256 && q < nquad; k++, q += 256) {
+        const size_t i = 4 * q;
+        while (r + 1 < nread && off[r + 1] <= i) r++;
+        const size_t last = off[r] + n[r];                                 // one past the read's last sample
+        const float2 c = cal[r];
+        if (i + 4 <= last) {
+            const short4 d = *reinterpret_cast<const short4 *>(dac + i);
+            float4 v;
+            v.x = __fmul_rn(__fadd_rn((float)d.x, c.x), c.y);
+            v.y = __fmul_rn(__fadd_rn((float)d.y, c.x), c.y);
+            v.z = __fmul_rn(__fadd_rn((float)d.z, c.x), c.y);
+            v.w = __fmul_rn(__fadd_rn((float)d.w, c.x), c.y);
+            *reinterpret_cast<float4 *>(x + i) = v;
+        } else {
+            for (size_t j = i; j < last; j++) x[j] = __fmul_rn(__fadd_rn((float)dac[j], c.x), c.y);
+        }
+    }
+}
+
 // quantiles of one array (quantilef, util.c:100-139)
 __global__ void __launch_bounds__(256) k_quantiles(const float *x, size_t n, float *p, int np) {
     __shared__ unsigned hist[256];
@@ -259,6 +295,7 @@ struct ffhip_prep {
     // ffhip_prep_begin: enqueued and not yet waited for (the tables the uploads read live here until then; `start` / `end` / `stats` are being written)
     bool pending = false;
     std::vector<size_t> n_in, s_in, e_in;
+    std::vector<float> cal;              // DAC entries: {offset, raw_unit} of every read
     // pinned landing place of the ranges and statistics, in the engine's staging buffer (a copy into pageable memory is not asynchronous: the call would wait for the kernel)
     void *h_res = nullptr;
 };
@@ -313,6 +350,7 @@ void ffhip::prep_mark_used(const ffhip_prep *p, hipStream_t s) {
 extern "C" void ffhip_prep_destroy(ffhip_prep *p) {
     if (!p) return;
     if (p->pending) { hipStreamSynchronize(p->eng->prep_stream); p->pending = false; }
+    if (p->eng && p->eng->prep_pending == p) p->eng->prep_pending = nullptr;
     if (p->used) { hipEventSynchronize(p->used); hipEventDestroy(p->used); }
     if (p->d_out) {
         // back to the engine's pool (at most four buffers wait there; the smallest goes when a fifth arrives)
@@ -328,9 +366,12 @@ extern "C" void ffhip_prep_destroy(ffhip_prep *p) {
     delete p;
 }
 
+// reads: float samples (raw_table) -- or dac: 16-bit DAC values with their calibration, scaled to picoamperes on the device in front of k_prep
 static ffhip_prep *prep_run(ffhip_engine *eng, const raw_table *reads, int nread, size_t trim_start, size_t trim_end,
-                            size_t chunk, float perc, int mode, float delta, int do_trim, float shift = 0.0f, bool wait = true) {
-    if (!eng || !reads || nread <= 0) { set_err(FFHIP_EINVAL, "bad signal-preparation arguments"); return nullptr; }
+                            size_t chunk, float perc, int mode, float delta, int do_trim, float shift = 0.0f, bool wait = true, const ffhip_dac_read *dac = nullptr) {
+    if (!eng || (!reads && !dac) || nread <= 0) { set_err(FFHIP_EINVAL, "bad signal-preparation arguments"); return nullptr; }
+    // one preparation at a time may be begun and not finished: the staging buffers, the scratch and the pinned landing place of its results are the engine's
+    if (eng->prep_pending) { set_err(FFHIP_EINVAL, "a signal preparation is pending on this engine: finish (or destroy) it before the next is started"); return nullptr; }
     if (mode < FFHIP_PREP_MEDMAD || mode > FFHIP_PREP_SHIFT_SCALE) { set_err(FFHIP_EINVAL, "unknown preparation mode %d", mode); return nullptr; }
     if (do_trim && (chunk < 2 || chunk > (size_t)kMaxChunk || !(perc >= 0.0f && perc <= 1.0f))) {
         set_err(FFHIP_EINVAL, "segmentation chunk must be 2..%d samples and the quantile within [0,1] (flappie_common.c:48-49)", kMaxChunk);
@@ -346,9 +387,12 @@ static ffhip_prep *prep_run(ffhip_engine *eng, const raw_table *reads, int nread
     std::vector<size_t> &n_in = p->n_in, &s_in = p->s_in, &e_in = p->e_in;
     n_in.resize(nread); s_in.resize(nread); e_in.resize(nread);
     size_t total = 0;
+    if (dac) p->cal.resize((size_t)2 * nread);
     for (int r = 0; r < nread; r++) {
-        const raw_table &rt = reads[r];
-        if (!rt.raw || rt.n == 0 || rt.end > rt.n || rt.start > rt.end) {
+        raw_table rt;
+        if (dac) { rt.uuid = nullptr; rt.n = dac[r].n; rt.start = 0; rt.end = dac[r].n; rt.raw = nullptr; p->cal[2 * (size_t)r] = dac[r].offset; p->cal[2 * (size_t)r + 1] = dac[r].raw_unit; }
+        else rt = reads[r];
+        if ((dac ? !dac[r].dac : !rt.raw) || rt.n == 0 || rt.end > rt.n || rt.start > rt.end) {
             set_err(FFHIP_EINVAL, "read %d: empty signal or start/end outside [0, n]", r);
             ffhip_prep_destroy(p);
             return nullptr;
@@ -358,15 +402,19 @@ static ffhip_prep *prep_run(ffhip_engine *eng, const raw_table *reads, int nread
     }
     float *d_raw = (float *)prep_scratch(eng, 0, total * 4), *d_mad = (float *)prep_scratch(eng, 1, total * 4);
     size_t *d_sz = (size_t *)prep_scratch(eng, 2, (size_t)6 * nread * sizeof(size_t));
-    float *d_stats = (float *)prep_scratch(eng, 3, (size_t)2 * nread * 4);
+    float *d_stats = (float *)prep_scratch(eng, 3, (size_t)4 * nread * 4), *d_cal = d_stats ? d_stats + (size_t)2 * nread : nullptr;      // statistics, then the DAC entries' calibrations
+    // DAC entries stage and upload 2 bytes a sample (same offsets in elements); the float array k_prep reads is written on the device
+    const size_t esize = dac ? 2 : 4;
+    int16_t *d_dac = dac ? (int16_t *)prep_scratch(eng, 4, total * 2) : nullptr;
     // (behind the raw samples: the landing place of ffhip_prep_begin's results -- ranges [2 nread] size_t, statistics [2 nread] float -- in the same pinned buffer)
-    const size_t res_off = (total * 4 + 63) & ~(size_t)63, res_bytes = (size_t)2 * nread * sizeof(size_t) + (size_t)2 * nread * 4;
+    const size_t res_off = (total * esize + 63) & ~(size_t)63, res_bytes = (size_t)2 * nread * sizeof(size_t) + (size_t)2 * nread * 4;
     float *pin = (float *)prep_pinned(eng, res_off + res_bytes);
 #define PFAIL(code, msg) do { set_err(code, msg); ffhip_prep_destroy(p); return nullptr; } while (0)
-    if (!d_raw || !d_mad || !d_sz || !d_stats || !pin || !(p->d_out = prep_pool_take(eng, total * 4, &p->d_out_cap))) PFAIL(FFHIP_ENOMEM, "device allocation failed");
+    if (!d_raw || !d_mad || !d_sz || !d_stats || !pin || (dac && !d_dac) || !(p->d_out = prep_pool_take(eng, total * 4, &p->d_out_cap))) PFAIL(FFHIP_ENOMEM, "device allocation failed");
     // one packed upload for the chunk: the reads are gathered in pinned memory first (a copy per read from pageable memory costs
     // 10-20 us of launch and staging each -- 30 ms for 2048 reads, during which nothing else was submitted)
-    for (int r = 0; r < nread; r++) memcpy(pin + p->off[r], reads[r].raw, reads[r].n * 4);
+    if (dac) for (int r = 0; r < nread; r++) memcpy((int16_t *)pin + p->off[r], dac[r].dac, dac[r].n * 2);
+    else for (int r = 0; r < nread; r++) memcpy(pin + p->off[r], reads[r].raw, reads[r].n * 4);
     if (rehearsal_nogpu()) {             // test hook (ffhip_engine.hip, "host-load rehearsal"): the host's share is done; fixed trims stand for the segmentation
         for (int r = 0; r < nread; r++) {
             p->start[r] = std::min(e_in[r], s_in[r] + trim_start);
@@ -375,12 +423,13 @@ static ffhip_prep *prep_run(ffhip_engine *eng, const raw_table *reads, int nread
         }
         return p;
     }
-    if (hipMemcpyAsync(d_raw, pin, total * 4, hipMemcpyHostToDevice, s) != hipSuccess) PFAIL(FFHIP_EHIP, "upload of raw signal failed");
+    if (hipMemcpyAsync(dac ? (void *)d_dac : (void *)d_raw, pin, total * esize, hipMemcpyHostToDevice, s) != hipSuccess) PFAIL(FFHIP_EHIP, "upload of raw signal failed");
     size_t *d_off = d_sz, *d_n = d_sz + nread, *d_s = d_sz + 2 * (size_t)nread, *d_e = d_sz + 3 * (size_t)nread, *d_so = d_sz + 4 * (size_t)nread, *d_eo = d_sz + 5 * (size_t)nread;
     bool ok = hipMemcpyAsync(d_off, p->off.data(), nread * sizeof(size_t), hipMemcpyHostToDevice, s) == hipSuccess;
     ok = ok && hipMemcpyAsync(d_n, n_in.data(), nread * sizeof(size_t), hipMemcpyHostToDevice, s) == hipSuccess;
     ok = ok && hipMemcpyAsync(d_s, s_in.data(), nread * sizeof(size_t), hipMemcpyHostToDevice, s) == hipSuccess;
     ok = ok && hipMemcpyAsync(d_e, e_in.data(), nread * sizeof(size_t), hipMemcpyHostToDevice, s) == hipSuccess;
+    if (dac) ok = ok && hipMemcpyAsync(d_cal, p->cal.data(), (size_t)2 * nread * 4, hipMemcpyHostToDevice, s) == hipSuccess;
     if (eng->persist_chained && total >= ((size_t)48 << 20)) hipStreamWaitEvent(s, eng->persist_done, 0);      // (see below: the fill and the kernel of a LARGE chunk)
     ok = ok && hipMemsetAsync(p->d_out, 0, total * 4, s) == hipSuccess;
     if (!ok) PFAIL(FFHIP_EHIP, "upload of read table failed");
@@ -389,6 +438,10 @@ static ffhip_prep *prep_run(ffhip_engine *eng, const raw_table *reads, int nread
     // beside a resident layer launch of the batch in flight, which it slows down as much (kernel trace, tools/dev/mixed_trace.sh): such a chunk is prepared behind
     // the engine's last layer launch (the wait stands in front of the output's fill above; the uploads before it are not held up: copies do not wait for compute).
     // The usual chunks (a millisecond or two) stay where they were.
+    if (dac) {                             // (behind the wait above, as k_prep is: a large chunk's 6 bytes a sample stay off the batch in flight too)
+        const size_t nquad = total / 4;
+        hipLaunchKernelGGL(k_dac_to_pa, dim3((unsigned)((nquad + kDacTile / 4 - 1) / (kDacTile / 4))), dim3(256), 0, s, d_dac, d_raw, d_off, d_n, (const float2 *)d_cal, nread, nquad);
+    }
     hipLaunchKernelGGL(k_prep, dim3(nread), dim3(256), 0, s, a);
     if (!wait) {
         // ffhip_prep_begin: the results land in pinned memory (ffhip_prep_finish waits and takes them from there); d_so and d_eo stand one behind the other
@@ -398,6 +451,7 @@ static ffhip_prep *prep_run(ffhip_engine *eng, const raw_table *reads, int nread
         ok = ok && hipMemcpyAsync((char *)p->h_res + nb, d_stats, (size_t)2 * nread * 4, hipMemcpyDeviceToHost, s) == hipSuccess;
         if (!ok) PFAIL(FFHIP_EHIP, "signal-preparation kernel failed");
         p->pending = true;
+        eng->prep_pending = p;
         return p;
     }
     ok = hipMemcpyAsync(p->start.data(), d_so, nread * sizeof(size_t), hipMemcpyDeviceToHost, s) == hipSuccess;
@@ -412,16 +466,17 @@ static ffhip_prep *prep_run(ffhip_engine *eng, const raw_table *reads, int nread
 // The two halves of ffhip_prep_create (round 6): begin enqueues the uploads, the kernel and the copies of the ranges on the engine's preparation stream and returns;
 // finish waits for them.  A caller with a pipeline of chunks begins chunk k + 1 before it submits chunk k's batches: the preparation -- one workgroup a read, as long as
 // its longest read's selection passes -- then runs BESIDE those batches' convolutions instead of in front of the next ones' (profiles/r06_pack_trace.txt).
-// ONE preparation may be pending at a time (the engine's staging buffers are shared); ranges, statistics and signals are there after finish.
+// ONE preparation may be pending at a time (the engine's staging buffers are shared; a second prep_run meanwhile fails with FFHIP_EINVAL); ranges, statistics and signals are there after finish.
 extern "C" ffhip_prep *ffhip_prep_begin(ffhip_engine *eng, const raw_table *reads, int nread, size_t trim_start, size_t trim_end,
                                         size_t varseg_chunk, float varseg_thresh, int mode, float delta) {
-    return prep_run(eng, reads, nread, trim_start, trim_end, varseg_chunk, varseg_thresh, mode, delta, 1, 0.0f, false);
+    return prep_run(eng, reads, nread, trim_start, trim_end, varseg_chunk, varseg_thresh, mode, delta, varseg_chunk != 0, 0.0f, false);
 }
 extern "C" int ffhip_prep_finish(ffhip_prep *p) {
     if (!p) return set_err(FFHIP_EINVAL, "no preparation");
     if (!p->pending) return FFHIP_OK;
     hipSetDevice(p->eng->device);
     p->pending = false;
+    if (p->eng->prep_pending == p) p->eng->prep_pending = nullptr;
     if (hipStreamSynchronize(p->eng->prep_stream) != hipSuccess || hipGetLastError() != hipSuccess) return set_err(FFHIP_EHIP, "signal-preparation kernel failed");
     if (p->h_res) {
         const size_t *r = (const size_t *)p->h_res;
@@ -435,7 +490,18 @@ extern "C" int ffhip_prep_finish(ffhip_prep *p) {
 
 extern "C" ffhip_prep *ffhip_prep_create(ffhip_engine *eng, const raw_table *reads, int nread, size_t trim_start, size_t trim_end,
                                          size_t varseg_chunk, float varseg_thresh, int mode, float delta) {
-    return prep_run(eng, reads, nread, trim_start, trim_end, varseg_chunk, varseg_thresh, mode, delta, 1);
+    return prep_run(eng, reads, nread, trim_start, trim_end, varseg_chunk, varseg_thresh, mode, delta, varseg_chunk != 0);      // (varseg_chunk == 0: the reads whole, as ffhip.h says)
+}
+
+extern "C" ffhip_prep *ffhip_prep_create_dac(ffhip_engine *eng, const ffhip_dac_read *reads, int nread, size_t trim_start, size_t trim_end,
+                                             size_t varseg_chunk, float varseg_thresh, int mode, float delta) {
+    if (!reads) { set_err(FFHIP_EINVAL, "bad signal-preparation arguments"); return nullptr; }
+    return prep_run(eng, nullptr, nread, trim_start, trim_end, varseg_chunk, varseg_thresh, mode, delta, varseg_chunk != 0, 0.0f, true, reads);
+}
+extern "C" ffhip_prep *ffhip_prep_begin_dac(ffhip_engine *eng, const ffhip_dac_read *reads, int nread, size_t trim_start, size_t trim_end,
+                                            size_t varseg_chunk, float varseg_thresh, int mode, float delta) {
+    if (!reads) { set_err(FFHIP_EINVAL, "bad signal-preparation arguments"); return nullptr; }
+    return prep_run(eng, nullptr, nread, trim_start, trim_end, varseg_chunk, varseg_thresh, mode, delta, varseg_chunk != 0, 0.0f, false, reads);
 }
 
 extern "C" int ffhip_prep_range(const ffhip_prep *p, int read, size_t *start, size_t *end) {

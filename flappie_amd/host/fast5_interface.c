@@ -1,4 +1,4 @@
-/*  fast5_interface.c -- single-read fast5 reader and trace writer (include/fast5_interface.h).
+/*  fast5_interface.c -- fast5 readers (single-read files; the cursor over a multi-read file) and trace writer (include/fast5_interface.h).
  *  Behaviour of /root/reference/src/fast5_interface.c:59-143,209-349.
  */
 #include <err.h>
@@ -70,6 +70,13 @@ static hid_t read_fapl(void) {
     return fapl;
 }
 
+/* libhdf5's own error stack stays off stderr for the readers of this file, as the reference's read_raw has it (fast5_interface.c:236): failures are reported
+ * here, in a line each.  Set once, by the first reader call that reaches libhdf5. */
+static void quiet_hdf5(void) {
+    static int done = 0;
+    if (!done) { H5Eset_auto2(H5E_DEFAULT, NULL, NULL); done = 1; }
+}
+
 raw_table read_raw(const char *filename, bool scale_to_pA) {
     if (NULL == filename) return (raw_table){ NULL, 0, 0, 0, NULL };
     {   /* round 6: the files this repo's own reader knows never reach libhdf5 (fast5_raw.c: one read(2), the structures walked in memory: ~105 -> ~10 us
@@ -85,11 +92,28 @@ raw_table read_raw(const char *filename, bool scale_to_pA) {
     return read_raw_hdf5(filename, scale_to_pA);
 }
 
+/* what a reader of any fast5 file calls per file: read_raw for a single-read file -- *multi stays NULL, the table is read_raw's --, or the cursor over a
+ * multi-read file (*multi set, an empty table).  A single-read file the walker knows costs what read_raw costs: the cursor is only asked where that refused. */
+raw_table read_raw_or_multi(const char *filename, bool scale_to_pA, fast5_multi **multi) {
+    *multi = NULL;
+    if (NULL == filename) return (raw_table){ NULL, 0, 0, 0, NULL };
+    const char *dbg = getenv("FLAPPIE_DEBUG");
+    const int use_fast = !(NULL != dbg && (NULL != strstr(dbg, "hdf5_read") || NULL != strstr(dbg, "plain_h5open")));
+    fast5_raw_read fr;
+    /* (a single-read file is 15 ... 400 KB and is read whole; a file beyond 8 MiB is asked first whether it is a multi-read one, which maps it) */
+    struct stat st;
+    const int large = use_fast && 0 == stat(filename, &st) && st.st_size > ((off_t)8 << 20);
+    if (use_fast && !large && fast5_read_raw_fast(filename, scale_to_pA, &fr)) return (raw_table){ fr.uuid, fr.n, 0, fr.n, fr.raw };
+    if (NULL != (*multi = fast5_multi_open(filename))) return (raw_table){ NULL, 0, 0, 0, NULL };
+    /* neither: the walker had its turn at a small file (it is not asked twice), a large single-read file has not been tried yet */
+    return large ? read_raw(filename, scale_to_pA) : read_raw_hdf5(filename, scale_to_pA);
+}
+
 /* read_raw through libhdf5 (fast5_interface.c:231-318) */
 raw_table read_raw_hdf5(const char *filename, bool scale_to_pA) {
     raw_table rawtbl = { NULL, 0, 0, 0, NULL };
     if (NULL == filename) return rawtbl;
-    H5Eset_auto2(H5E_DEFAULT, NULL, NULL);
+    quiet_hdf5();
     hid_t file = H5Fopen(filename, H5F_ACC_RDONLY, read_fapl());
     if (file < 0) { warnx("Failed to open %s for reading.", filename); return rawtbl; }
     /* the one read group under /Raw/Reads, opened by index (one traversal; the reference asks for its name, builds the path and walks it again for the
@@ -140,6 +164,157 @@ raw_table read_raw_hdf5(const char *filename, bool scale_to_pA) {
     H5Oclose(rgroup);
     H5Fclose(file);
     return rawtbl;
+}
+
+/* ---- multi-read files: the cursor (include/fast5_interface.h) ----------------------------------------------------------------- */
+struct fast5_multi {
+    char *filename;
+    int path;                  /* 0: the walker first, libhdf5 for what it refuses; 1: the walker only; 2: libhdf5 only */
+    fast5_walk *w;             /* the mapped file (NULL: libhdf5 reads everything) */
+    hid_t file;                /* opened when libhdf5 is first needed */
+    char **names;              /* libhdf5 path: the read groups, sorted (with a walker the names are its) */
+    size_t n, next;
+};
+
+static int by_name(const void *a, const void *b) { return strcmp(*(char *const *)a, *(char *const *)b); }
+
+typedef struct { char **v; size_t n, cap; int has_raw, failed; } name_list;
+static herr_t collect_name(hid_t g, const char *name, const H5L_info_t *info, void *arg) {
+    name_list *l = arg;
+    if (0 == strcmp(name, "Raw")) l->has_raw = 1;
+    if (0 != strncmp(name, "read_", 5)) return 0;
+    if (l->n == l->cap) {
+        const size_t cap = l->cap ? 2 * l->cap : 64;
+        char **v = realloc(l->v, cap * sizeof(char *));
+        if (NULL == v) { l->failed = 1; return -1; }
+        l->v = v; l->cap = cap;
+    }
+    if (NULL == (l->v[l->n] = strdup(name))) { l->failed = 1; return -1; }
+    l->n++;
+    return 0;
+}
+
+static hid_t multi_h5file(fast5_multi *m) {
+    if (m->file < 0) {
+        quiet_hdf5();
+        m->file = H5Fopen(m->filename, H5F_ACC_RDONLY, H5P_DEFAULT);      /* (the default driver: such a file is not read whole) */
+    }
+    return m->file;
+}
+
+fast5_multi *fast5_multi_open(const char *filename) {
+    const char *dbg = getenv("FLAPPIE_DEBUG");
+    return fast5_multi_open_path(filename, (NULL != dbg && (NULL != strstr(dbg, "hdf5_read") || NULL != strstr(dbg, "plain_h5open"))) ? 2 : 0);
+}
+
+fast5_multi *fast5_multi_open_path(const char *filename, int path) {
+    if (NULL == filename) return NULL;
+    fast5_multi *m = calloc(1, sizeof(*m));
+    if (NULL == m || NULL == (m->filename = strdup(filename))) { free(m); return NULL; }
+    m->path = path; m->file = -1;
+    int rc = -1;
+    if (2 != path) rc = fast5_walk_open(filename, &m->w);
+    if (1 == rc) { m->n = fast5_walk_count(m->w); return m; }
+    if (0 == rc || 1 == path) goto no;
+    {   /* libhdf5: the root group's links by name */
+        name_list l; memset(&l, 0, sizeof(l));
+        hsize_t idx = 0;
+        if (multi_h5file(m) < 0 || H5Literate(m->file, H5_INDEX_NAME, H5_ITER_INC, &idx, collect_name, &l) < 0 || l.failed || l.has_raw || 0 == l.n) {
+            for (size_t i = 0; i < l.n; i++) free(l.v[i]);
+            free(l.v);
+            goto no;
+        }
+        qsort(l.v, l.n, sizeof(char *), by_name);
+        m->names = l.v; m->n = l.n;
+        return m;
+    }
+no:
+    fast5_multi_close(m);
+    return NULL;
+}
+
+size_t fast5_multi_count(const fast5_multi *m) { return NULL != m ? m->n : 0; }
+const char *fast5_multi_next_name(const fast5_multi *m) {
+    if (NULL == m || m->next >= m->n) return NULL;
+    return NULL != m->w ? fast5_walk_name(m->w, m->next) : m->names[m->next];
+}
+
+/* one read through libhdf5: 1 = out filled, 0 = reported */
+static int multi_read_hdf5(fast5_multi *m, const char *name, fast5_dac_read *out) {
+    const hid_t file = multi_h5file(m);
+    if (file < 0) { warnx("Failed to open %s for reading.", m->filename); return 0; }
+    int ok = 0;
+    char *uuid = NULL;
+    short *dac = NULL;
+    hid_t rg = H5Gopen(file, name, H5P_DEFAULT), raw = -1, dset = -1, ch = -1, space = -1, dcpl = -1;
+    if (rg < 0 || (raw = H5Gopen(rg, "Raw", H5P_DEFAULT)) < 0) { warnx("%s: read %s has no Raw group.", m->filename, name); goto out; }
+    if (H5Aexists(raw, "read_id") > 0) uuid = string_attr(raw, "read_id");
+    else uuid = strdup(name + 5);
+    if (NULL == uuid) { warnx("%s: read %s has no readable read_id.", m->filename, name); goto out; }
+    if ((dset = H5Dopen(raw, "Signal", H5P_DEFAULT)) < 0) { warnx("%s: failed to open dataset %s/Raw/Signal.", m->filename, name); goto out; }
+    hsize_t nsample = 0;
+    if ((space = H5Dget_space(dset)) < 0 || 1 != H5Sget_simple_extent_ndims(space) || H5Sget_simple_extent_dims(space, &nsample, NULL) < 0 || 0 == nsample) {
+        warnx("%s: %s/Raw/Signal is not a one-dimensional dataset with samples.", m->filename, name);
+        goto out;
+    }
+    /* a filter this libhdf5 cannot apply (VBZ, 32020, without its plugin in HDF5_PLUGIN_PATH): said by number, and the run goes on */
+    if ((dcpl = H5Dget_create_plist(dset)) >= 0) {
+        const int nf = H5Pget_nfilters(dcpl);
+        for (int k = 0; k < nf; k++) {
+            unsigned flags = 0, cfg = 0; size_t ncd = 0; char fname[64] = "";
+            const H5Z_filter_t id = H5Pget_filter2(dcpl, (unsigned)k, &flags, &ncd, NULL, sizeof(fname), fname, &cfg);
+            if (id >= 0 && H5Zfilter_avail(id) <= 0) {
+                warnx("%s: read %s: Signal is stored with HDF5 filter %d%s%s%s, for which no plugin was found (HDF5_PLUGIN_PATH); the read is skipped.", m->filename, uuid, (int)id,
+                      fname[0] ? " (" : "", fname, fname[0] ? ")" : "");
+                goto out;
+            }
+        }
+    }
+    if (NULL == (dac = malloc(nsample * sizeof(short))) || H5Dread(dset, H5T_NATIVE_SHORT, H5S_ALL, H5S_ALL, H5P_DEFAULT, dac) < 0) {
+        warnx("%s: failed to read raw data from dataset %s/Raw/Signal.", m->filename, name);
+        goto out;
+    }
+    if ((ch = H5Gopen(rg, "channel_id", H5P_DEFAULT)) < 0) { warnx("%s: read %s has no channel_id group.", m->filename, name); goto out; }
+    {   const float digitisation = float_attr(ch, "digitisation"), offset = float_attr(ch, "offset"), range = float_attr(ch, "range");
+        out->offset = offset;
+        out->raw_unit = range / digitisation;
+    }
+    out->uuid = uuid; uuid = NULL;
+    out->dac = dac; dac = NULL;
+    out->n = nsample;
+    ok = 1;
+out:
+    free(uuid); free(dac);
+    if (dcpl >= 0) H5Pclose(dcpl);
+    if (space >= 0) H5Sclose(space);
+    if (ch >= 0) H5Gclose(ch);
+    if (dset >= 0) H5Dclose(dset);
+    if (raw >= 0) H5Gclose(raw);
+    if (rg >= 0) H5Gclose(rg);
+    return ok;
+}
+
+int fast5_multi_next(fast5_multi *m, fast5_dac_read *out) {
+    if (NULL == out) return 0;
+    memset(out, 0, sizeof(*out));
+    if (NULL == m || m->next >= m->n) return 0;
+    const size_t i = m->next++;
+    if (NULL != m->w) {
+        if (fast5_walk_read(m->w, i, out)) return 1;
+        if (1 == m->path) return -1;
+        return multi_read_hdf5(m, fast5_walk_name(m->w, i), out) ? 1 : -1;
+    }
+    return multi_read_hdf5(m, m->names[i], out) ? 1 : -1;
+}
+
+void fast5_multi_close(fast5_multi *m) {
+    if (NULL == m) return;
+    if (m->file >= 0) H5Fclose(m->file);
+    fast5_walk_close(m->w);
+    for (size_t i = 0; m->names && i < m->n; i++) free(m->names[i]);
+    free(m->names);
+    free(m->filename);
+    free(m);
 }
 
 hid_t open_or_create_hdf5(const char *filename) {

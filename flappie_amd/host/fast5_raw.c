@@ -1,4 +1,5 @@
-/*  fast5_raw.c -- the read side of a single-read fast5 file WITHOUT libhdf5 (round 6).
+/*  fast5_raw.c -- the read side of a fast5 file WITHOUT libhdf5: single-read files (round 6) and, at the end of this file, the
+ *  read groups of a multi-read file (mapped, not copied; the cursor of fast5_interface.c drives it).
  *
  *  What read_raw (/root/reference/src/fast5_interface.c:231-318) takes from a file is four things: the first entry of /Raw/Reads in
  *  name order, its `read_id` attribute, its `Signal` dataset, and three numeric attributes of /UniqueGlobalKey/channel_id.  Through
@@ -21,6 +22,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
 #include <zlib.h>
@@ -99,6 +101,7 @@ static int read_object(const h5file *f, uint64_t addr, h5obj *o) {
         if (NULL == q) return 0;
         const uint64_t c0 = le(q + off, szb);
         off += (size_t)szb;
+        if (c0 > f->n) return 0;                                                 /* (before the addition: an 8-byte size field near 2^64 would wrap it) */
         const unsigned char *blk = at(f, addr + off, c0 + 4);                    /* + checksum */
         if (NULL == blk) return 0;
         return parse_block(f, o, blk, (size_t)c0, 1, (fl & 4) != 0, 0);
@@ -117,10 +120,29 @@ static const h5msg *find_msg(const h5obj *o, unsigned type) {
 
 /* ---- groups ------------------------------------------------------------------------------------------------------------------- */
 /* visit(name, address) for every link of a group; want == NULL: keep the smallest name in strcmp order (index 0 of H5_INDEX_NAME, increasing) */
-typedef struct { const char *want; char best[256]; uint64_t addr; int found; } pick;
+typedef struct { char *name; uint64_t addr; } h5link;
+typedef struct { h5link *v; size_t n, cap; } h5links;
+typedef struct { const char *want; char best[256]; uint64_t addr; int found; h5links *all; /* all != NULL: every link is kept there */ } pick;
+#define MAX_LINKS ((size_t)1 << 20)
 
 static int offer(pick *pk, const char *name, size_t len, uint64_t addr) {
     if (len >= sizeof(pk->best)) return 0;                                       /* a name this long: not compared here */
+    if (NULL != pk->all) {
+        h5links *l = pk->all;
+        if (memchr(name, 0, len) || l->n >= MAX_LINKS) return 0;
+        if (l->n == l->cap) {
+            const size_t cap = l->cap ? 2 * l->cap : 64;
+            h5link *v = realloc(l->v, cap * sizeof(h5link));
+            if (NULL == v) return 0;
+            l->v = v; l->cap = cap;
+        }
+        char *nm = malloc(len + 1);
+        if (NULL == nm) return 0;
+        memcpy(nm, name, len); nm[len] = 0;
+        l->v[l->n++] = (h5link){ nm, addr };
+        pk->found = 1;
+        return 1;
+    }
     if (NULL != pk->want) {
         if (strlen(pk->want) == len && 0 == memcmp(pk->want, name, len)) { pk->addr = addr; pk->found = 1; }
         return 1;
@@ -418,7 +440,9 @@ static int walk_chunk_btree(const h5file *f, uint64_t addr, int ndim, const h5fi
         const uint64_t csize = le(k, 4), off0 = le(k + 8, 8), caddr = le(k + ksz, 8);
         const unsigned mask = (unsigned)le(k + 4, 4);
         if (level > 0) { if (!walk_chunk_btree(f, caddr, ndim, fl, chunk_elems, n, dst, cbuf, tmp, covered, depth + 1)) return 0; continue; }
-        if (off0 >= n || 0 != off0 % chunk_elems) return 0;
+        /* the leaves of a chunk B-tree stand in order of their offsets: every chunk must begin where the one before it ended -- a chunk met twice
+         * (or one missing: its elements would be the fill value) is not read here, so `covered == n` means every element was written once */
+        if (off0 >= n || off0 != *covered) return 0;
         const unsigned char *c = at(f, caddr, csize);
         if (NULL == c) return 0;
         if (!unfilter(fl, mask, c, (size_t)csize, cbuf, (size_t)chunk_elems * 2, 2, tmp)) return 0;
@@ -573,5 +597,109 @@ int fast5_read_raw_fast(const char *filename, int scale_to_pA, fast5_raw_read *o
     ok = 1;
 out:
     free(o); free(sig); free(uuid); free(buf);
+    return ok;
+}
+
+/* ---- multi-read files ----------------------------------------------------------------------------------------------------------
+ * One file, thousands of reads, each a root group read_<x> { Raw { Signal, read_id }, channel_id { digitisation, offset, range } }.  Such a file runs to a
+ * gigabyte: it is MAPPED, not copied, and the walker touches the pages of the structures and of the signals it is asked for.  The same rules as above: what
+ * is not known is refused -- the whole file (fast5_walk_open = -1) or one read (fast5_walk_read = 0) -- and fast5_interface.c asks libhdf5. */
+struct fast5_walk { unsigned char *map; size_t len; h5file f; h5links reads; };
+
+static int by_link_name(const void *a, const void *b) { return strcmp(((const h5link *)a)->name, ((const h5link *)b)->name); }
+static void free_links(h5links *l) {
+    for (size_t i = 0; i < l->n; i++) free(l->v[i].name);
+    free(l->v);
+    memset(l, 0, sizeof(*l));
+}
+
+int fast5_walk_open(const char *filename, fast5_walk **out) {
+    *out = NULL;
+    const int fd = open(filename, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return -1;
+    struct stat st;
+    void *map = MAP_FAILED;
+    if (0 == fstat(fd, &st) && S_ISREG(st.st_mode) && st.st_size >= 64) map = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    close(fd);
+    if (MAP_FAILED == map) return -1;
+    fast5_walk *w = calloc(1, sizeof(*w));
+    int rc = -1;
+    uint64_t root;
+    if (NULL == w) goto out;
+    w->map = map; w->len = (size_t)st.st_size;
+    w->f = (h5file){ w->map, w->len, 0 };
+    pick pk; memset(&pk, 0, sizeof(pk)); pk.all = &w->reads;
+    if (!root_address(&w->f, &root) || !group_lookup(&w->f, root, &pk)) goto out;
+    {   /* multi-read: no `Raw` child and at least one read_<x>; the root attribute file_type is not asked for (older files have none) */
+        size_t kept = 0;
+        int has_raw = 0;
+        for (size_t i = 0; i < w->reads.n; i++) {
+            h5link l = w->reads.v[i];
+            if (0 == strcmp(l.name, "Raw")) has_raw = 1;
+            if (0 == strncmp(l.name, "read_", 5)) w->reads.v[kept++] = l; else free(l.name);
+        }
+        w->reads.n = kept;
+        if (has_raw || 0 == kept) { rc = 0; goto out; }
+        qsort(w->reads.v, kept, sizeof(h5link), by_link_name);               /* H5_INDEX_NAME, H5_ITER_INC */
+    }
+    *out = w;
+    return 1;
+out:
+    if (NULL != w) { free_links(&w->reads); free(w); }
+    munmap(map, (size_t)st.st_size);
+    return rc;
+}
+
+size_t fast5_walk_count(const fast5_walk *w) { return w->reads.n; }
+const char *fast5_walk_name(const fast5_walk *w, size_t i) { return i < w->reads.n ? w->reads.v[i].name : NULL; }
+
+void fast5_walk_close(fast5_walk *w) {
+    if (NULL == w) return;
+    free_links(&w->reads);
+    munmap(w->map, w->len);
+    free(w);
+}
+
+/* dense attribute storage (attribute info message with a fractal heap): an attribute not found among the messages may live there */
+static int has_dense_attrs(const h5obj *o) {
+    const h5msg *ai = find_msg(o, 0x15);
+    if (NULL == ai) return 0;
+    if (ai->size < 2) return 1;
+    const size_t off = 2 + ((ai->data[1] & 1) ? 2 : 0);
+    if (ai->size < off + 8) return 1;
+    return UNDEF_ADDR != le(ai->data + off, 8);
+}
+
+int fast5_walk_read(const fast5_walk *w, size_t i, fast5_dac_read *out) {
+    memset(out, 0, sizeof(*out));
+    if (i >= w->reads.n) return 0;
+    const h5file *f = &w->f;
+    const uint64_t rd = w->reads.v[i].addr;
+    uint64_t rawg, ds, ch;
+    int16_t *sig = NULL; uint64_t n = 0;
+    char *uuid = NULL;
+    int ok = 0;
+    h5obj *o = malloc(sizeof(h5obj));
+    if (NULL == o) return 0;
+    if (!child(f, rd, "Raw", &rawg) || !read_object(f, rawg, o)) goto out;
+    uuid = attr_string(f, o, "read_id");
+    if (NULL == uuid) {                                                          /* no read_id on Raw: the group's name behind "read_" */
+        h5attr a;
+        if (find_attr(o, "read_id", &a) || has_dense_attrs(o)) goto out;         /* (it is there, in a form not read here) */
+        uuid = strdup(w->reads.v[i].name + 5);
+        if (NULL == uuid) goto out;
+    }
+    if (!child(f, rd, "channel_id", &ch) || !read_object(f, ch, o)) goto out;
+    float digitisation = 0.0f, offset = 0.0f, range = 0.0f;
+    if (!attr_float(o, "digitisation", &digitisation) || !attr_float(o, "offset", &offset) || !attr_float(o, "range", &range)) goto out;
+    if (!child(f, rawg, "Signal", &ds) || !read_signal(f, ds, &sig, &n)) goto out;
+    out->uuid = uuid; uuid = NULL;
+    out->dac = sig; sig = NULL;
+    out->n = (size_t)n;
+    out->offset = offset;
+    out->raw_unit = range / digitisation;                                        /* fast5_interface.c: in float, as read_raw computes it */
+    ok = 1;
+out:
+    free(o); free(sig); free(uuid);
     return ok;
 }

@@ -6,6 +6,9 @@
  *                      its index only, so several processes can fill one directory (bench.py's host-fed leg, tools/cli_throughput.py)
  *    fast5_tool synthln DIR COUNT MEDIAN SIGMA MINLEN MAXLEN SEED [FIRST [STEP]]   the same with LOG-NORMAL lengths: exp(ln MEDIAN + SIGMA z), z ~ N(0, 1),
  *                      clipped to [MINLEN, MAXLEN] -- a nanopore-like length mix (tools/length_mix.py)
+ *    fast5_tool writem out.fast5 FLAGS CHUNK LIST    a MULTI-read file: one root group read_<NAME> per line "NAME READ_ID digitisation offset range samples.i16 [filter]"
+ *                      of the text file LIST, each with Raw/Signal (int16), read_id on Raw, and channel_id {digitisation, offset, range, sampling_rate}
+ *                      (flags below, beside write_multi)
  *    fast5_tool dump   trace.hdf5 GROUP          (prints "signal N" + values, "trace R C" + values)
  *  Layout written: /Raw/Reads/Read_1/Signal (int16) with attribute read_id (fixed string) and
  *  /UniqueGlobalKey/channel_id {digitisation, offset, range, sampling_rate} (doubles), i.e. what
@@ -28,6 +31,8 @@ static int write_read_x(const char *path, const char *read_id, double digitisati
 static int write_read(const char *path, const char *read_id, double digitisation, double offset, double range, double rate, const short *raw, hsize_t n) {
     return write_read_x(path, read_id, digitisation, offset, range, rate, raw, n, 0, 0);
 }
+
+static int write_multi(const char *path, unsigned flags, hsize_t chunk, const char *list);
 
 static unsigned long long rng_next(unsigned long long *s) {      /* splitmix64 */
     unsigned long long z = (*s += 0x9E3779B97F4A7C15ull);
@@ -91,6 +96,7 @@ int main(int argc, char **argv) {
         free(raw);
         return rc;
     }
+    if (argc >= 6 && 0 == strcmp(argv[1], "writem")) return write_multi(argv[2], (unsigned)strtoul(argv[3], NULL, 0), (hsize_t)atol(argv[4]), argv[5]);
     if (argc >= 4 && 0 == strcmp(argv[1], "dump")) {
         hid_t f = H5Fopen(argv[2], H5F_ACC_RDONLY, H5P_DEFAULT);
         if (f < 0) return 2;
@@ -192,5 +198,97 @@ static int write_read_x(const char *path, const char *read_id, double digitisati
     dattr(u2, "sampling_rate", rate);
     H5Gclose(u2); H5Gclose(u1); H5Gclose(g3); H5Gclose(g2); H5Gclose(g1); H5Fclose(f);
     if (fapl != H5P_DEFAULT) H5Pclose(fapl);
+    return 0;
+}
+
+/* FLAGS of `writem` (the layouts a multi-read file can come in; tests/test_fast5_multi.py): 1 chunked Signal (CHUNK elements), 2 deflate, 4 shuffle (as writex),
+ * 32 the latest file format (with more than eight reads: dense link storage in the root group), 1024 no root attribute file_type, 2048 no read_id on Raw,
+ * 4096 the groups are created in another order than the list's (its odd entries first, then the even ones).
+ * A line that ends in a seventh field "filter" stores its Signal behind filter 32020 -- the number of VBZ, here a PLACEHOLDER that only flips bits (no VBZ coder
+ * exists in this repository): a reader without a plugin of that number cannot read the read, which is what the tests need of it. */
+#define PLACEHOLDER_FILTER 32020
+static size_t placeholder_filter(unsigned flags, size_t ncd, const unsigned cd[], size_t nbytes, size_t *buf_size, void **buf) {
+    unsigned char *p = *buf;
+    for (size_t i = 0; i < nbytes; i++) p[i] ^= 0x5a;
+    return nbytes;
+}
+
+static int write_multi(const char *path, unsigned flags, hsize_t chunk, const char *list) {
+    typedef struct { char name[128], id[128], file[4096]; double dig, off, rng; int filter; } entry;
+    FILE *fh = fopen(list, "r");
+    if (!fh) return 2;
+    entry *e = NULL;
+    size_t n = 0, cap = 0;
+    char line[8192];
+    while (fgets(line, sizeof(line), fh)) {
+        if (n == cap) { cap = cap ? 2 * cap : 16; e = realloc(e, cap * sizeof(entry)); }
+        char extra[32] = "";
+        const int got = sscanf(line, "%127s %127s %lf %lf %lf %4095s %31s", e[n].name, e[n].id, &e[n].dig, &e[n].off, &e[n].rng, e[n].file, extra);
+        if (got < 6) continue;
+        e[n].filter = (0 == strcmp(extra, "filter"));
+        n++;
+    }
+    fclose(fh);
+    hid_t fapl = H5P_DEFAULT;
+    if (flags & 32) { fapl = H5Pcreate(H5P_FILE_ACCESS); H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST); }
+    hid_t f = H5Fcreate(path, H5F_ACC_TRUNC, H5P_DEFAULT, fapl);
+    if (f < 0) return 2;
+    hid_t ss = H5Screate(H5S_SCALAR);
+    if (!(flags & 1024)) {
+        static const char ft[] = "multi-read";
+        hid_t st = H5Tcopy(H5T_C_S1); H5Tset_size(st, sizeof(ft));
+        hid_t a = H5Acreate(f, "file_type", st, ss, H5P_DEFAULT, H5P_DEFAULT);
+        H5Awrite(a, st, ft);
+        H5Aclose(a); H5Tclose(st);
+    }
+    for (size_t k = 0; k < n; k++) {
+        size_t i = k;
+        if (flags & 4096) { const size_t h = n / 2; i = k < h ? 2 * k + 1 : 2 * (k - h); }      /* 1, 3, 5 ... then 0, 2, 4 ... */
+        FILE *sf = fopen(e[i].file, "rb");
+        if (!sf) return 2;
+        fseek(sf, 0, SEEK_END); const long bytes = ftell(sf); fseek(sf, 0, SEEK_SET);
+        hsize_t ns = (hsize_t)(bytes / 2);
+        short *raw = malloc(bytes > 0 ? (size_t)bytes : 2);
+        if (fread(raw, 2, ns, sf) != ns) return 2;
+        fclose(sf);
+        char gname[160];
+        snprintf(gname, sizeof(gname), "/read_%s", e[i].name);
+        hid_t g = H5Gcreate(f, gname, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
+        hid_t gr = H5Gcreate(g, "Raw", H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
+        if (g < 0 || gr < 0) return 3;
+        if (!(flags & 2048)) {
+            hid_t st = H5Tcopy(H5T_C_S1); H5Tset_size(st, strlen(e[i].id) + 1);
+            hid_t a = H5Acreate(gr, "read_id", st, ss, H5P_DEFAULT, H5P_DEFAULT);
+            H5Awrite(a, st, e[i].id);
+            H5Aclose(a); H5Tclose(st);
+        }
+        hid_t sp = H5Screate_simple(1, &ns, NULL);
+        hid_t dcpl = H5P_DEFAULT;
+        if ((flags & 7) || e[i].filter) {
+            dcpl = H5Pcreate(H5P_DATASET_CREATE);
+            hsize_t ch = (chunk > 0 && chunk < ns) ? chunk : (ns > 0 ? ns : 1);
+            H5Pset_chunk(dcpl, 1, &ch);
+            if (flags & 4) H5Pset_shuffle(dcpl);
+            if (flags & 2) H5Pset_deflate(dcpl, 1);
+            if (e[i].filter) {
+                const H5Z_class2_t cls = { H5Z_CLASS_T_VERS, PLACEHOLDER_FILTER, 1, 1, "vbz (placeholder of fast5_tool)", NULL, NULL, placeholder_filter };
+                if (H5Zfilter_avail(PLACEHOLDER_FILTER) <= 0) H5Zregister(&cls);
+                H5Pset_filter(dcpl, PLACEHOLDER_FILTER, H5Z_FLAG_MANDATORY, 0, NULL);
+            }
+        }
+        hid_t d = H5Dcreate(gr, "Signal", H5T_STD_I16LE, sp, H5P_DEFAULT, dcpl, H5P_DEFAULT);
+        if (d < 0) return 3;
+        if (H5Dwrite(d, H5T_NATIVE_SHORT, H5S_ALL, H5S_ALL, H5P_DEFAULT, raw) < 0) return 3;
+        H5Dclose(d); H5Sclose(sp);
+        if (dcpl != H5P_DEFAULT) H5Pclose(dcpl);
+        hid_t c = H5Gcreate(g, "channel_id", H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
+        dattr(c, "digitisation", e[i].dig); dattr(c, "offset", e[i].off); dattr(c, "range", e[i].rng); dattr(c, "sampling_rate", 4000.0);
+        H5Gclose(c); H5Gclose(gr); H5Gclose(g);
+        free(raw);
+    }
+    H5Sclose(ss);
+    H5Fclose(f);
+    if (fapl != H5P_DEFAULT) H5Pclose(fapl);
+    free(e);
     return 0;
 }

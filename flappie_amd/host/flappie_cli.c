@@ -368,7 +368,13 @@ typedef struct {
     int mv_stride;                      /* ... the samples a block */
     float sm, sd;                       /* ... the median and MAD the read was normalised with */
     int rle_nocall;                     /* runnie --fasta: no runs, or a failed run-length estimate (decode_runnie.py: "No basecall returned") */
+    /* a read of a MULTI-READ file: its samples as the file holds them (owned; res.rt.raw stays NULL, res.rt.n counts them) and its calibration -- the
+     * preparation scales them on the device (ffhip_prep_begin_dac) */
+    int from_multi;
+    int16_t *dac;
+    float dac_offset, dac_unit;
 } item;
+static int item_has_signal(const item *it) { return NULL != it->res.rt.raw || NULL != it->dac; }
 
 /* Batch objects own gigabytes of workspace; creating one per group costs more than running it.  Full-size groups
  * (--batch reads) share one cached object whose capacity grows when a longer read turns up. */
@@ -712,7 +718,8 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
             }
             free(tmp);
             /* write_summary stores the signal the network saw (fast5_interface.c:332-335) */
-            if (0 != ffhip_prep_get_signal(prep, idx[i], r->rt.raw + r->rt.start)) warnx("%s", ffhip_last_error());
+            if (NULL == r->rt.raw) r->rt.raw = calloc(r->rt.n ? r->rt.n : 1, sizeof(float));      /* (a read that came as DAC values has no float array yet) */
+            if (NULL == r->rt.raw || 0 != ffhip_prep_get_signal(prep, idx[i], r->rt.raw + r->rt.start)) warnx("%s", NULL == r->rt.raw ? "out of memory" : ffhip_last_error());
         }
     }
     t_phase[4] += now_s() - t0; t0 = now_s();
@@ -731,6 +738,7 @@ typedef struct chunk_ctx {
     int n, buf;                  /* buf: which of the reader's buffers holds the items (released when the chunk is written) */
     ffhip_prep *prep;
     raw_table *rts;
+    ffhip_dac_read *dacs;        /* a chunk of DAC reads (read_chunk cuts a chunk where the kind changes: it holds one kind) */
     item **group;
     int m2, submitted, collected, all_submitted, live;
 } chunk_ctx;
@@ -750,14 +758,20 @@ static void chunk_begin(struct ffhip_engine *eng, chunk_ctx *c, item *items, int
     c->items = items; c->n = n; c->buf = buf; c->live = 1;
     c->group = calloc(n > 0 ? n : 1, sizeof(item *));
     c->rts = calloc(n > 0 ? n : 1, sizeof(raw_table));
-    int m = 0;
+    c->dacs = calloc(n > 0 ? n : 1, sizeof(ffhip_dac_read));
+    int m = 0, ndac = 0;
     for (int i = 0; i < n; i++) {
         items[i].prepared = -1;
-        if (NULL != items[i].res.rt.raw) { c->rts[m] = items[i].res.rt; items[i].prepared = m++; }
+        if (!item_has_signal(&items[i])) continue;
+        if (NULL != items[i].dac) { c->dacs[m] = (ffhip_dac_read){ items[i].dac, items[i].res.rt.n, items[i].dac_offset, items[i].dac_unit }; ndac++; }
+        else c->rts[m] = items[i].res.rt;
+        items[i].prepared = m++;
     }
+    if (ndac > 0 && ndac < m) errx(EXIT_FAILURE, "internal error: a chunk holds DAC reads and float reads");
     double tp0 = now_s();
-    c->prep = (m > 0) ? (wait ? ffhip_prep_create : ffhip_prep_begin)(eng, c->rts, m, args.trim_start, args.trim_end, args.varseg_chunk, args.varseg_thresh,
-                                                                         (args.delta == 0.0f) ? FFHIP_PREP_MEDMAD : FFHIP_PREP_DELTA, args.delta) : NULL;
+    const int pmode = (args.delta == 0.0f) ? FFHIP_PREP_MEDMAD : FFHIP_PREP_DELTA;
+    if (m > 0 && ndac > 0) c->prep = (wait ? ffhip_prep_create_dac : ffhip_prep_begin_dac)(eng, c->dacs, m, args.trim_start, args.trim_end, args.varseg_chunk, args.varseg_thresh, pmode, args.delta);
+    else c->prep = (m > 0) ? (wait ? ffhip_prep_create : ffhip_prep_begin)(eng, c->rts, m, args.trim_start, args.trim_end, args.varseg_chunk, args.varseg_thresh, pmode, args.delta) : NULL;
     t_phase[1] += now_s() - tp0;
     if (m > 0 && NULL == c->prep) warnx("%s", ffhip_last_error());
 }
@@ -835,6 +849,8 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
         }
         it->rle_nocall = 0;
         free_raw_basecall_info(&it->res);
+        free(it->dac);
+        it->dac = NULL;
         free(it->filename);
         continue;
 #endif
@@ -844,6 +860,8 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
             char *fn = strdup(it->filename);
             const char *base = basename(fn);
             const char *uuid = it->res.rt.uuid ? it->res.rt.uuid : "";
+            char *multi_name = NULL;              /* --no-uuid, a read of a multi-read file: <file>:<read id> (the file's name alone would stand for thousands of reads) */
+            if (it->from_multi && NULL != (multi_name = malloc(strlen(base) + strlen(uuid) + 2))) { sprintf(multi_name, "%s:%s", base, uuid); base = multi_name; }
             /* --modbase-tags: Z is written as C here, in the record only -- the trace file below keeps the call as it is */
             if (args.emit_moves) {
                 if (NULL == it->mv) warnx("No move table for %s", it->filename);
@@ -864,7 +882,10 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
                 if (packs) { summary_pack_free(packs[i]); packs[i] = NULL; }
             }
             free(fn);
+            free(multi_name);
         }
+        free(it->dac);
+        it->dac = NULL;
         free(it->ml);
         it->ml = NULL;
         free(it->mv);
@@ -875,6 +896,7 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
     if (packs) { for (int i = 0; i < c->n; i++) summary_pack_free(packs[i]); free(packs); }
     t_phase[5] += now_s() - to0;
     free(c->rts);
+    free(c->dacs);
     free(c->group);
     __atomic_store_n(&c->live, 0, __ATOMIC_RELEASE);
 }
@@ -1245,10 +1267,9 @@ static void list_files(file_list *fl) {
 }
 
 typedef struct {
-    const file_list *fl;
     int chunk_cap;
     item *items[NCHUNKBUF];              /* one more than the chunks that can be unfinished at a time (one per batch in flight) */
-    int nitem[NCHUNKBUF];
+    int nitem[NCHUNKBUF], last[NCHUNKBUF];      /* last: no read follows this chunk */
     sem_t filled[NCHUNKBUF], empty[NCHUNKBUF];
 } reader_state;
 
@@ -1283,17 +1304,40 @@ static int read_all(int fd, void *buf, size_t n) {
     return 0;
 }
 
+/* A record of a reader's pipe: this header, the uuid, the samples.  REC_FLOAT: a single-read file, its samples as picoampere floats (one record a file, as ever);
+ * REC_DAC: a read of a multi-read file, int16 DAC values as the file holds them and the calibration in the header (half the bytes down the pipe, into pinned memory
+ * and up to the device); REC_SKIP: a read of a multi-read file that could not be read (the child said why); REC_EOF: behind the last read of a multi-read file. */
+enum { REC_FLOAT = 0, REC_DAC = 1, REC_EOF = 2, REC_SKIP = 3 };
+typedef struct { uint64_t nsample, uuid_len; uint32_t kind; float offset, raw_unit; uint32_t pad; } rec_hdr;
+
 static void reader_child(const file_list *fl, int k, int R, int fd) {
     signal(SIGPIPE, SIG_IGN);            /* a parent that went away is a failed write, not a signal (the PARENT keeps the default: `flappie ... | head` ends) */
-    long kill_k = -1, kill_f = -1;       /* tests: FLAPPIE_DEBUG=kill_reader=k:f -- child k dies (SIGKILL) when it reaches file index f */
+    long kill_k = -1, kill_f = -1, kill_r = 0;      /* tests: FLAPPIE_DEBUG=kill_reader=k:f[:r] -- child k dies (SIGKILL) when it reaches file index f (read r of it, a multi-read file) */
     const char *kill_env = cli_dbg("kill_reader");
-    if (kill_env && 2 != sscanf(kill_env, "%ld:%ld", &kill_k, &kill_f)) kill_k = -1;
+    if (kill_env && sscanf(kill_env, "%ld:%ld:%ld", &kill_k, &kill_f, &kill_r) < 2) kill_k = -1;
     for (size_t f = (size_t)k; f < fl->n; f += (size_t)R) {
-        if (kill_k == k && (long)f >= kill_f) raise(SIGKILL);
-        raw_table rt = read_raw(fl->path[f], true);
-        uint64_t hdr[2] = { (NULL != rt.raw) ? (uint64_t)rt.n : 0, (NULL != rt.uuid && NULL != rt.raw) ? (uint64_t)strlen(rt.uuid) : 0 };
-        if (0 != write_all(fd, hdr, sizeof(hdr)) || (hdr[1] && 0 != write_all(fd, rt.uuid, hdr[1])) ||
-            (hdr[0] && 0 != write_all(fd, rt.raw, hdr[0] * sizeof(float)))) _exit(1);      /* the parent went away */
+        if (kill_k == k && (long)f >= kill_f && (0 == kill_r || (long)f > kill_f)) raise(SIGKILL);
+        fast5_multi *multi = NULL;
+        raw_table rt = read_raw_or_multi(fl->path[f], true, &multi);
+        if (NULL != multi) {
+            fast5_dac_read dr;
+            int rc;
+            for (long r = 0; 0 != (rc = fast5_multi_next(multi, &dr)); r++) {
+                if (kill_k == k && (long)f == kill_f && r >= kill_r) raise(SIGKILL);
+                rec_hdr h = { rc > 0 ? (uint64_t)dr.n : 0, (rc > 0 && NULL != dr.uuid) ? (uint64_t)strlen(dr.uuid) : 0, rc > 0 ? REC_DAC : REC_SKIP, dr.offset, dr.raw_unit, 0 };
+                if (0 != write_all(fd, &h, sizeof(h)) || (h.uuid_len && 0 != write_all(fd, dr.uuid, h.uuid_len)) ||
+                    (h.nsample && 0 != write_all(fd, dr.dac, h.nsample * sizeof(int16_t)))) _exit(1);
+                free(dr.dac);
+                free(dr.uuid);
+            }
+            fast5_multi_close(multi);
+            rec_hdr h = { 0, 0, REC_EOF, 0.0f, 0.0f, 0 };
+            if (0 != write_all(fd, &h, sizeof(h))) _exit(1);
+            continue;
+        }
+        rec_hdr h = { (NULL != rt.raw) ? (uint64_t)rt.n : 0, (NULL != rt.uuid && NULL != rt.raw) ? (uint64_t)strlen(rt.uuid) : 0, REC_FLOAT, 0.0f, 0.0f, 0 };
+        if (0 != write_all(fd, &h, sizeof(h)) || (h.uuid_len && 0 != write_all(fd, rt.uuid, h.uuid_len)) ||
+            (h.nsample && 0 != write_all(fd, rt.raw, h.nsample * sizeof(float)))) _exit(1);      /* the parent went away */
         free(rt.raw);
         free(rt.uuid);
     }
@@ -1325,37 +1369,113 @@ static void start_reader_procs(const file_list *fl, int R) {
     }
 }
 
-/* A reader child that dies (libhdf5 crashing on a corrupt file, an OOM kill) takes its stripe with it: the file it died on is
- * reported unreadable, every LATER file of the stripe is read in this process instead (as with --readers 0), and the exit status
- * of the run says that a reader failed.  A stream cut in the middle of a record is out of sync and handled the same way. */
-static raw_table reader_lost(size_t f, const char *path) {
-    raw_table rt = { NULL, 0, 0, 0, NULL };
+/* ---- the stream of reads: file after file, a multi-read file read after read (in increasing strcmp order of its group names: the cursor's order).
+ * next_item fills one item per read; a file -- or a read of a multi-read file -- that could not be read is an item without a signal ("No basecall returned").
+ *
+ * A reader child that dies (libhdf5 crashing on a corrupt file, an OOM kill) takes its stripe with it: the file it died on is reported unreadable -- of a
+ * multi-read file the reads not yet delivered are lost --, every LATER file of the stripe is read in this process instead (as with --readers 0), and the exit
+ * status of the run says that a reader failed.  A stream cut in the middle of a record is out of sync and handled the same way. */
+static struct {
+    const file_list *fl;
+    size_t f;                    /* the file the next read comes from */
+    fast5_multi *cur;            /* in-process: the cursor over file f */
+    int in_multi;                /* from a reader process: file f is a multi-read file and its end-of-file record has not come yet */
+    long nitems;                 /* --limit counts reads */
+    item held; int have_held;    /* read_chunk looked one read ahead */
+} in;
+
+static void reader_lost(size_t f, const char *path) {
     reader_proc *rp = &rprocs[f % (size_t)nrproc];
-    if (!rp->dead) {
-        rp->dead = 1;
-        reader_failures++;
-        warnx("reader process %zu ended early at %s; the rest of its files are read in-process", f % (size_t)nrproc, path);
-        return rt;                                                         /* this file: whatever killed the child stays unread */
-    }
-    pthread_mutex_lock(&hdf5_lock);
-    rt = read_raw(path, true);
-    pthread_mutex_unlock(&hdf5_lock);
-    return rt;
+    rp->dead = 1;
+    reader_failures++;
+    warnx("reader process %zu ended early at %s; the rest of its files are read in-process", f % (size_t)nrproc, path);
 }
 
-static raw_table read_from_proc(size_t f, const char *path) {
-    raw_table rt = { NULL, 0, 0, 0, NULL };
-    if (rprocs[f % (size_t)nrproc].dead) return reader_lost(f, path);
-    const int fd = rprocs[f % (size_t)nrproc].fd;
-    uint64_t hdr[2];
-    if (0 != read_all(fd, hdr, sizeof(hdr))) return reader_lost(f, path);
-    char *uuid = hdr[1] ? calloc(hdr[1] + 1, 1) : NULL;
-    if (hdr[1] && (NULL == uuid || 0 != read_all(fd, uuid, hdr[1]))) { free(uuid); return reader_lost(f, path); }
-    if (0 == hdr[0]) { free(uuid); return rt; }                        /* the child could not read the file (it said why) */
-    float *raw = malloc(hdr[0] * sizeof(float));
-    if (NULL == raw || 0 != read_all(fd, raw, hdr[0] * sizeof(float))) { free(raw); free(uuid); return reader_lost(f, path); }
-    rt = (raw_table){ uuid, hdr[0], 0, hdr[0], raw };
-    return rt;
+static void item_init(item *it, const char *path) {
+    memset(it, 0, sizeof(*it));
+    it->filename = strdup(path);
+}
+static void item_from_dac(item *it, const char *path, const fast5_dac_read *dr) {
+    item_init(it, path);
+    it->from_multi = 1;
+    if (NULL == dr) return;
+    it->res.rt = (raw_table){ dr->uuid, dr->n, 0, dr->n, NULL };
+    it->dac = dr->dac; it->dac_offset = dr->offset; it->dac_unit = dr->raw_unit;
+}
+
+/* no call of next_item can give another read (known without reading anything) */
+static int input_exhausted(void) {
+    if (args.limit > 0 && in.nitems >= args.limit) return 1;
+    return NULL == in.cur && !in.in_multi && in.f >= in.fl->n;
+}
+
+/* 1: *it is the next read; 0: the input has ended (or --limit reads were given out) */
+static int next_item(item *it) {
+    for (;;) {
+        if (args.limit > 0 && in.nitems >= args.limit) return 0;
+        if (NULL != in.cur) {                                               /* in-process, inside a multi-read file */
+            fast5_dac_read dr;
+            pthread_mutex_lock(&hdf5_lock);
+            const int rc = fast5_multi_next(in.cur, &dr);
+            if (0 == rc) { fast5_multi_close(in.cur); in.cur = NULL; }
+            pthread_mutex_unlock(&hdf5_lock);
+            if (0 == rc) { in.f++; continue; }
+            item_from_dac(it, in.fl->path[in.f], rc > 0 ? &dr : NULL);
+            in.nitems++;
+            return 1;
+        }
+        if (in.f >= in.fl->n) return 0;
+        const char *path = in.fl->path[in.f];
+        if (nrproc > 0 && !rprocs[in.f % (size_t)nrproc].dead) {
+            const int fd = rprocs[in.f % (size_t)nrproc].fd;
+            rec_hdr h;
+            char *uuid = NULL;
+            void *samples = NULL;
+            int lost = 0 != read_all(fd, &h, sizeof(h)) || h.kind > REC_SKIP || h.uuid_len > (1u << 16) || h.nsample > ((uint64_t)1 << 36);
+            if (!lost && h.uuid_len) { uuid = calloc(h.uuid_len + 1, 1); lost = NULL == uuid || 0 != read_all(fd, uuid, h.uuid_len); }
+            if (!lost && h.nsample) {
+                const size_t bytes = h.nsample * (REC_DAC == h.kind ? sizeof(int16_t) : sizeof(float));
+                samples = malloc(bytes);
+                lost = NULL == samples || 0 != read_all(fd, samples, bytes);
+            }
+            if (lost) {
+                free(uuid); free(samples);
+                reader_lost(in.f, path);
+                const int was_inside = in.in_multi;
+                in.in_multi = 0;
+                in.f++;
+                if (was_inside) continue;                                   /* the reads delivered so far stand; the file's others are lost */
+                item_init(it, path);                                        /* this file: whatever killed the child stays unread */
+                in.nitems++;
+                return 1;
+            }
+            if (REC_EOF == h.kind) { free(uuid); free(samples); in.in_multi = 0; in.f++; continue; }
+            if (REC_FLOAT == h.kind) {
+                item_init(it, path);
+                if (h.nsample) it->res.rt = (raw_table){ uuid, h.nsample, 0, h.nsample, samples };
+                else free(uuid);                                            /* the child could not read the file (it said why) */
+                in.f++;
+            } else {
+                in.in_multi = 1;
+                fast5_dac_read dr = { uuid, samples, h.nsample, h.offset, h.raw_unit };
+                item_from_dac(it, path, (REC_DAC == h.kind && h.nsample) ? &dr : NULL);
+                if (NULL == it->dac) { free(uuid); free(samples); }
+            }
+            in.nitems++;
+            return 1;
+        }
+        /* in-process: --readers 0, or the stripe of a reader that died */
+        pthread_mutex_lock(&hdf5_lock);
+        fast5_multi *multi = NULL;
+        const raw_table rt = read_raw_or_multi(path, true, &multi);         /* flappie.c:248 */
+        pthread_mutex_unlock(&hdf5_lock);
+        if (NULL != multi) { in.cur = multi; continue; }
+        item_init(it, path);
+        it->res.rt = rt;
+        in.f++;
+        in.nitems++;
+        return 1;
+    }
 }
 
 static void stop_reader_procs(void) {
@@ -1380,28 +1500,27 @@ static void stop_reader_procs(void) {
 #define PACK_WINDOW_MAX ((size_t)224 << 20)
 #define PACK_WINDOW_READS 4
 static int g_pack_window = 0;                /* set once the model is known: pack_allowed() */
-static void read_chunk(const file_list *fl, size_t first, int chunk_cap, item *items, int *nitem) {
+static void read_chunk(int chunk_cap, item *items, int *nitem, int *last) {
     /* a chunk is up to chunk_cap reads (CHUNK_BATCHES batches of the usual 4-8 k-sample reads) -- or, with long reads, what holds about as
      * many SAMPLES but at least one batch: records leave when their chunk is done, and a 1024-read chunk of 100 000-sample reads
-     * would be four seconds of GPU work with nothing written (and nothing for the writer thread to overlap) */
+     * would be four seconds of GPU work with nothing written (and nothing for the writer thread to overlap).
+     * A chunk holds ONE kind of read -- DAC values (multi-read files) or floats (single-read files): its preparation is one call of one entry, so the chunk is
+     * cut where the kind changes (the read that changes it is held for the next chunk; nothing is converted on the host to avoid the cut). */
     size_t sample_budget = (size_t)chunk_cap * 8192, longest = 0;
     size_t nsamp = 0;
-    int n = 0, read_cap = chunk_cap;
-    for (size_t f = first; f < fl->n && n < read_cap && !(n >= args.batch && nsamp >= sample_budget); f++, n++) {
+    int n = 0, read_cap = chunk_cap, kind = -1;
+    const double tr0 = now_s();
+    for (; n < read_cap && !(n >= args.batch && nsamp >= sample_budget); n++) {
         item *it = &items[n];
-        memset(it, 0, sizeof(*it));
-        it->filename = fl->path[f];                                   /* ownership moves to the item */
-        const double tr0 = now_s();
-        if (nrproc > 0) {
-            it->res.rt = read_from_proc(f, it->filename);
-        } else {
-            pthread_mutex_lock(&hdf5_lock);
-            it->res.rt = read_raw(it->filename, true);                /* flappie.c:248 */
-            pthread_mutex_unlock(&hdf5_lock);
+        if (in.have_held) { *it = in.held; in.have_held = 0; }
+        else if (!next_item(it)) break;
+        if (item_has_signal(it)) {
+            const int k = NULL != it->dac;
+            if (kind >= 0 && k != kind) { in.held = *it; in.have_held = 1; break; }
+            kind = k;
+            nsamp += it->res.rt.n;
         }
-        t_phase[0] += now_s() - tr0;
-        if (NULL != it->res.rt.raw) nsamp += it->res.rt.n;
-        if (g_pack_window && NULL != it->res.rt.raw && it->res.rt.n > longest) {
+        if (g_pack_window && item_has_signal(it) && it->res.rt.n > longest) {
             longest = it->res.rt.n;
             /* (... and a twentieth more: these are RAW samples, the rows hold trimmed ones, and rows that average a little MORE than the longest read let the planner --
              * every read into the emptiest row -- end with all rows alike; at exactly --batch x longest the trimming left the rows 2.7 % under a row that holds the
@@ -1411,6 +1530,11 @@ static void read_chunk(const file_list *fl, size_t first, int chunk_cap, item *i
             if (want > sample_budget) { sample_budget = want; read_cap = PACK_WINDOW_READS * chunk_cap; }
         }
     }
+    t_phase[0] += now_s() - tr0;
+    /* No read is taken ahead to learn whether a chunk follows (the first, small chunk goes to the GPU as soon as it is full): the input says when it is exhausted.
+     * Behind the last read of a multi-read file it cannot know yet -- the cursor, or the reader's end-of-file record, says so at the next call -- so a chunk that
+     * such a file's last read fills exactly is followed by an empty last one, which the main loop passes over. */
+    *last = 0 == n || (!in.have_held && input_exhausted());      /* (no read at all: next_item said that the input has ended) */
     *nitem = n;
 }
 
@@ -1418,12 +1542,13 @@ static void release_buffer(int buf, void *arg) { sem_post(&((reader_state *)arg)
 
 static void *reader_main(void *arg) {
     reader_state *rs = arg;
-    size_t first = 0;
-    for (int k = 0; first < rs->fl->n; k = (k + 1) % NCHUNKBUF) {
+    int first = 1, last = 0;
+    for (int k = 0; !last; k = (k + 1) % NCHUNKBUF) {
         sem_wait(&rs->empty[k]);
-        /* the first chunk is one batch only, so that the GPU starts after --batch files instead of CHUNK_BATCHES times as many */
-        read_chunk(rs->fl, first, first == 0 ? rs->chunk_cap / CHUNK_BATCHES : rs->chunk_cap, rs->items[k], &rs->nitem[k]);
-        first += rs->nitem[k];
+        /* the first chunk is one batch only, so that the GPU starts after --batch reads instead of CHUNK_BATCHES times as many */
+        read_chunk(first ? rs->chunk_cap / CHUNK_BATCHES : rs->chunk_cap, rs->items[k], &rs->nitem[k], &rs->last[k]);
+        first = 0;
+        last = rs->last[k];
         sem_post(&rs->filled[k]);
     }
     return NULL;
@@ -1438,9 +1563,10 @@ static int look_ahead_reader(item **items, int *n, int *buf) {
         return 0;
     }
     la.taken = 1;
+    if (0 == la.rs->nitem[la.kn]) return 0;      /* (the empty last chunk behind a multi-read file whose last read filled a chunk: nothing to prepare) */
     if (cli_dbg("pack_log")) fprintf(stderr, "look-ahead at %.3f s: buffer %d is there (%d reads)\n", now_s() - t_program_start, la.kn, la.rs->nitem[la.kn]);
     unsigned long long raw = 0;
-    for (int i = 0; i < la.rs->nitem[la.kn]; i++) if (NULL != la.rs->items[la.kn][i].res.rt.raw) raw += la.rs->items[la.kn][i].res.rt.n;
+    for (int i = 0; i < la.rs->nitem[la.kn]; i++) if (item_has_signal(&la.rs->items[la.kn][i])) raw += la.rs->items[la.kn][i].res.rt.n;
     unsigned long long least = 48ull << 20;      /* the usual chunks: their device pass is a millisecond beside the batch in flight as it is */
     const char *lm = cli_dbg("prep_ahead_min");  /* tests: FLAPPIE_DEBUG=prep_ahead_min=0 takes this path with chunks of any size */
     if (NULL != lm) least = strtoull(lm, NULL, 10);
@@ -1492,7 +1618,7 @@ int main(int argc, char *argv[]) {
     hid_t hdf5out = open_or_create_hdf5(args.trace);
     reader_state rs;
     memset(&rs, 0, sizeof(rs));
-    rs.fl = &fl;
+    in.fl = &fl;                 /* (before the reader thread starts: next_item reads the list through it) */
     /* reads per batch = what one layer launch takes (ffhip_rnn_split.hip): 1024 at H = 256 (the packed forms), 512 at H <= 384 (the dense
      * form), else 256 */
     if (0 == args.batch) args.batch = (int)ffhip_model_launch_reads(mdl);
@@ -1507,28 +1633,30 @@ int main(int argc, char *argv[]) {
     }
     const int threaded = !cli_dbg("no_reader_thread");
     pthread_t reader;
-    if (threaded && 0 != pthread_create(&reader, NULL, reader_main, &rs)) errx(EXIT_FAILURE, "could not start the reader thread");
-    size_t done = 0;
+    if (threaded && fl.n > 0 && 0 != pthread_create(&reader, NULL, reader_main, &rs)) errx(EXIT_FAILURE, "could not start the reader thread");
+    int first_chunk = 1, last_chunk = (0 == fl.n);
     double t_wait = 0.0;
     if (threaded) { pipe_state.released = release_buffer; pipe_state.released_arg = &rs; }
     /* A LARGE chunk that follows (the window of a directory of long reads: 48 M raw samples and more, what ffhip_prep_create holds behind the engine's last layer launch) has its
      * device pass begun before this chunk's batches are submitted, if the reader has it ready by then (FLAPPIE_DEBUG=no_prep_ahead: never) */
     la.rs = &rs; la.on = threaded && !cli_dbg("no_prep_ahead"); la.taken = 0;
-    for (int k = 0; done < fl.n; k = (k + 1) % NCHUNKBUF) {
+    for (int k = 0; !last_chunk; k = (k + 1) % NCHUNKBUF) {
         const double tw0 = now_s();
         /* buffer k was released when the chunk three back was written: at most two chunks are unfinished at a time (three with a chunk prepared ahead) */
         if (threaded) { if (!la.taken) sem_wait(&rs.filled[k]); }
-        else { pipe_wait_slot_written(); read_chunk(&fl, done, done == 0 ? rs.chunk_cap / CHUNK_BATCHES : rs.chunk_cap, rs.items[k], &rs.nitem[k]); }
+        else { pipe_wait_slot_written(); read_chunk(first_chunk ? rs.chunk_cap / CHUNK_BATCHES : rs.chunk_cap, rs.items[k], &rs.nitem[k], &rs.last[k]); }
+        first_chunk = 0;
         t_wait += now_s() - tw0;
         const int nk = rs.nitem[k];              /* (the reader may refill the buffer as soon as the chunk is written) */
-        la.taken = 0; la.kn = (k + 1) % NCHUNKBUF; la.more = done + (size_t)nk < fl.n;
-        pipe_chunk(eng, mdl, rs.items[k], nk, k, hdf5out, look_ahead_reader);
-        done += nk;
+        last_chunk = rs.last[k];
+        la.taken = 0; la.kn = (k + 1) % NCHUNKBUF; la.more = !last_chunk;
+        if (nk > 0) pipe_chunk(eng, mdl, rs.items[k], nk, k, hdf5out, look_ahead_reader);      /* (no read: the empty last chunk read_chunk describes, or files whose readers died before their first) */
     }
     pipe_drain(mdl, hdf5out);
-    if (threaded) pthread_join(reader, NULL);
+    if (threaded && fl.n > 0) pthread_join(reader, NULL);
     stop_reader_procs();
     for (int k = 0; k < NCHUNKBUF; k++) free(rs.items[k]);
+    for (size_t f = 0; f < fl.n; f++) free(fl.path[f]);      /* (an item holds a copy of its file's name: a file may give thousands of items) */
     free(fl.path);
     if (hdf5out >= 0) { pthread_mutex_lock(&hdf5_lock); H5Fclose(hdf5out); pthread_mutex_unlock(&hdf5_lock); }
     if (stdout != args.output) fclose(args.output);

@@ -382,7 +382,8 @@ int ffhip_runlength_v1_mean(ffhip_engine *eng, ffhip_mat param, const int *path,
  * trim_and_segment_raw (flappie_common.c:13-81) followed by medmad_normalise_array (util.c:198-212) or the
  * --delta transform (flappie.c:259-262) for a set of raw reads of any lengths, one workgroup per read; every
  * order statistic is an exact selection, so ranges and signals equal the reference's qsort-based ones.
- * The prepared signals stay in HBM; ffhip_batch_set_prepared feeds equal-length ones to a batch. */
+ * The prepared signals stay in HBM; ffhip_batch_set_prepared feeds equal-length ones to a batch.
+ * varseg_chunk == 0 (all four entries below): no trimming at all -- every read whole, trim_start / trim_end ignored --, then the mode's transform. */
 typedef struct ffhip_prep ffhip_prep;
 #define FFHIP_PREP_MEDMAD 0   /* medmad_normalise_array                                  */
 #define FFHIP_PREP_DELTA  1   /* difference_array + shift_scale_array(0, delta)          */
@@ -395,6 +396,15 @@ ffhip_prep *ffhip_prep_create(ffhip_engine *eng, const raw_table *reads, int nre
  * batches, and the preparation runs beside their convolutions.  One preparation may be pending at a time; ranges, statistics and signals are valid after finish. */
 ffhip_prep *ffhip_prep_begin(ffhip_engine *eng, const raw_table *reads, int nread, size_t trim_start, size_t trim_end,
                              size_t varseg_chunk, float varseg_thresh, int mode, float delta);
+/* The same two entries for reads that are still what the file holds: 16-bit DAC values and the read's calibration (a multi-read fast5 file's reads,
+ * fast5_interface.h's fast5_dac_read).  Half the bytes are staged and uploaded; a kernel in front of the preparation writes the picoampere floats
+ * (dac + offset) * raw_unit -- an add and a multiply, each rounded, as read_raw's loop does them -- and everything behind it is the float entries' bit for bit. */
+typedef struct { const int16_t *dac; size_t n; float offset, raw_unit; } ffhip_dac_read;
+ffhip_prep *ffhip_prep_create_dac(ffhip_engine *eng, const ffhip_dac_read *reads, int nread, size_t trim_start, size_t trim_end,
+                                  size_t varseg_chunk, float varseg_thresh, int mode, float delta);
+ffhip_prep *ffhip_prep_begin_dac(ffhip_engine *eng, const ffhip_dac_read *reads, int nread, size_t trim_start, size_t trim_end,
+                                 size_t varseg_chunk, float varseg_thresh, int mode, float delta);
+/* (a second preparation of either kind while one is begun and not finished fails with FFHIP_EINVAL: the engine's staging buffers are the pending one's) */
 int ffhip_prep_finish(ffhip_prep *p);
 void ffhip_prep_destroy(ffhip_prep *p);      /* waits for the copies ffhip_batch_set_prepared enqueued from it, not for the batches */
 /* start >= end: the read was rejected (trim_and_segment_raw would have returned a NULL table) */
