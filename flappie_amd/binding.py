@@ -31,6 +31,7 @@ RUN_RLE_RECORDS = 2048    # ... and every run's shape, scale and dwell
 RLE_SCALE_DEFAULT = (1.02, 1.04, 1.04, 1.02)      # decode_runnie.py's default --scale (A, C, G, T)
 RUN_MOD_PROBS = 4096      # 5-base model: 5mC probabilities (SAM ML bytes) of the called bases made on the device (Batch.mod_probs)
 RUN_MOVES = 8192          # flip-flop model: the move table (one byte a block, 1 where a base is emitted) made on the device (Batch.moves)
+RUN_BARCODES = 16384      # flip-flop model: one barcode record a read made on the device against the kit of Batch.set_barcodes (Batch.barcode)
 # ffhip_debug_gate_math forms (include/ffhip.h)
 GATE_FORMS = ("logistic_ref", "tanh_ref", "logistic_ref4_lean", "logistic_ref2_lean", "logistic_ref_lean", "tanh_ref_lean",
               "swish_act4", "tanh_act4", "logistic_hw1", "tanh_hw1", "logistic_hw2", "tanh_hw2")
@@ -71,6 +72,12 @@ class CRleRuns(C.Structure):
     _fields_ = [("nrun", C.c_size_t), ("length", C.c_ulonglong), ("failed", C.c_int),
                 ("base", C.POINTER(C.c_uint8)), ("est", C.POINTER(C.c_int32)),
                 ("shape", C.POINTER(C.c_float)), ("scale", C.POINTER(C.c_float)), ("dwell", C.POINTER(C.c_int32))]
+
+
+class CBarcodeCall(C.Structure):
+    """ffhip_barcode_call (include/ffhip.h): 16 bytes"""
+    _fields_ = [("best", C.c_int16), ("best_dist", C.c_uint8), ("second_dist", C.c_uint8), ("front_dist", C.c_uint8), ("rear_dist", C.c_uint8),
+                ("ends", C.c_uint8), ("pad", C.c_uint8), ("front_end", C.c_int16), ("rear_end", C.c_int16), ("reserved", C.c_int32)]
 
 
 class CRawTable(C.Structure):
@@ -190,6 +197,13 @@ def lib():
     L.ffhip_op_moves.argtypes = [vp, C.POINTER(C.c_int), C.c_size_t, C.POINTER(C.c_uint8)]
     L.ffhip_model_stride.restype = C.c_size_t
     L.ffhip_model_stride.argtypes = [vp]
+    L.ffhip_barcodes_upload.restype = vp
+    L.ffhip_barcodes_upload.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.c_int]
+    L.ffhip_barcodes_free.restype = None
+    L.ffhip_barcodes_free.argtypes = [vp]
+    L.ffhip_batch_set_barcodes.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
+    L.ffhip_batch_barcode.argtypes = [vp, C.c_int, C.POINTER(CBarcodeCall)]
+    L.ffhip_op_barcode_scores.argtypes = [vp, vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     _LIB = L
     return L
 
@@ -379,6 +393,27 @@ class Prepared:
             self.h = None
 
 
+class Barcodes:
+    """A barcode kit on the device (ffhip_barcodes): `seqs` are 1 .. 128 patterns over ACGT of 1 .. 128 bases, `window` the bases searched at each end of a call."""
+
+    def __init__(self, engine: Engine, seqs, window: int = 150):
+        self.engine = engine
+        self.seqs = [x if isinstance(x, bytes) else str(x).encode() for x in seqs]
+        self.n, self.window = len(self.seqs), int(window)
+        arr = (C.c_char_p * max(1, self.n))(*self.seqs)
+        self.h = lib().ffhip_barcodes_upload(engine.h, self.n, arr, self.window)
+        if not self.h:
+            raise FFHipError(lib().ffhip_last_error().decode())
+
+    def close(self):
+        if self.h:
+            lib().ffhip_barcodes_free(self.h)
+            self.h = None
+
+
+BARCODE_FIELDS = ("best", "best_dist", "second_dist", "front_dist", "rear_dist", "ends", "front_end", "rear_end")
+
+
 class Batch:
     """`nread` reads of `nsample` samples (ffhip_batch)."""
 
@@ -518,6 +553,16 @@ class Batch:
         p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
         _check(lib().ffhip_batch_moves(self.h, read, C.byref(p), C.byref(n)))
         return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint8)
+
+    def set_barcodes(self, kit, max_dist: int = -1, min_sep: int = -1, both_ends: bool = False):
+        """the kit and parameters of later runs with RUN_BARCODES (ffhip_batch_set_barcodes); max_dist < 0: floor(Lmin / 4), min_sep < 0: 3; kit None detaches"""
+        _check(lib().ffhip_batch_set_barcodes(self.h, kit.h if kit is not None else None, int(max_dist), int(min_sep), int(bool(both_ends))))
+
+    def barcode(self, read: int) -> dict:
+        """barcode record of a run with RUN_BARCODES (ffhip_batch_barcode): the fields of BARCODE_FIELDS as ints"""
+        c = CBarcodeCall()
+        _check(lib().ffhip_batch_barcode(self.h, read, C.byref(c)))
+        return {f: int(getattr(c, f)) for f in BARCODE_FIELDS}
 
     def transitions(self, read: int) -> np.ndarray:
         out = np.zeros((self.read_nblock(read), self.P), dtype=np.float32)
@@ -660,6 +705,14 @@ def moves_op(engine: Engine, path: np.ndarray) -> np.ndarray:
     mv = np.zeros(path.size - 1, np.uint8)
     _check(lib().ffhip_op_moves(engine.h, path.ctypes.data_as(C.POINTER(C.c_int)), path.size - 1, mv.ctypes.data_as(C.POINTER(C.c_uint8))))
     return mv
+
+
+def op_barcode_scores(engine: Engine, kit: Barcodes, bases) -> tuple:
+    """ffhip_op_barcode_scores: (dist, end), each int32 [2][n] (front, rear), of every pattern of the kit at both ends of ONE call (a str over ACGTZ, may be empty)"""
+    b = bases if isinstance(bases, bytes) else str(bases).encode()
+    dist, end = np.zeros((2, kit.n), np.int32), np.zeros((2, kit.n), np.int32)
+    _check(lib().ffhip_op_barcode_scores(engine.h, kit.h, b, len(b), dist.ctypes.data_as(C.POINTER(C.c_int32)), end.ctypes.data_as(C.POINTER(C.c_int32))))
+    return dist, end
 
 
 def basecall_reads(dmodel: DeviceModel, signals: np.ndarray, temperature: float = 1.0, flags: int = 0):

@@ -756,6 +756,12 @@ struct ffhip_batch {
     unsigned *h_abort() const { return res.on_host<unsigned>(RF_ABORT); }
     int *h_lens() const { return res.on_host<int>(RF_LENS); }
     unsigned res_made = 0;              // sections of the block the last run filled (res_bit)
+    // Barcode records (FFHIP_RUN_BARCODES, k_barcodes): 16 bytes a read, NOT a section of the result block -- a device buffer and a pinned host buffer of their own,
+    // cap_reads records each, created by the first run that asks, and one copy of their own beside the block's
+    const ffhip_barcodes *bc_kit = nullptr;
+    int bc_max_dist = 0, bc_min_sep = 3, bc_both = 0;
+    ffhip_barcode_call *bc_dev = nullptr, *bc_host = nullptr;
+    int bc_valid = 0;                   // the last run made them
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
     std::vector<void *> owned;
     unsigned last_flags = 0;
@@ -851,6 +857,7 @@ extern "C" void ffhip_batch_destroy(ffhip_batch *b) {
     if (b->counted) { b->counted = 0; b->eng->in_flight--; }
     for (void *p : b->owned) hipFree(p);
     b->res.release();
+    if (b->bc_host) hipHostFree(b->bc_host);
     if (b->side) ffhip_batch_destroy(b->side);
     prof_unlink(b);
     if (b->have_ev) {
@@ -1442,6 +1449,17 @@ static int keep_copy(ffhip_batch *b, int slot, const float *src) {
 }
 
 // One run of a batch is enqueued in three phases -- front (convolutions), the recurrent stack, back (head, CRF, decode) -- so that
+static_assert(sizeof(ffhip_barcode_call) == 16, "k_barcodes writes a record as one 16-byte store");
+static int ensure_barcode_buffers(ffhip_batch *b) {
+    const size_t bytes = (size_t)b->cap_reads * sizeof(ffhip_barcode_call);
+    if (!b->bc_dev && !(b->bc_dev = (ffhip_barcode_call *)dalloc(b, bytes, true))) return FFHIP_ENOMEM;
+    if (!b->bc_host) {
+        if (hipHostMalloc((void **)&b->bc_host, bytes, hipHostMallocDefault) != hipSuccess) { b->bc_host = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation failed"); }
+        memset(b->bc_host, 0, bytes);
+    }
+    return FFHIP_OK;
+}
+
 // ffhip_batch_run_pair can put the layer launches of TWO batches into one grid between their fronts and backs (`paired`).  The front
 // decides the run's path (b->run_path); the layers and the back follow it.
 static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool paired) {
@@ -1464,6 +1482,13 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
         if ((m->kind == FFHIP_NET_LSTM5_RLE) != sec.rle || (sec.nbase && m->nbase != sec.nbase)) return set_err(FFHIP_EINVAL, "%s", sec.model_text);
         if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "%s", sec.undecoded_text);
         if (int rc = b->res.ensure((ResSec)i, b->stream)) return rc;
+    }
+    b->bc_valid = 0;
+    if (flags & FFHIP_RUN_BARCODES) {      // (not a section of the result block: a buffer and a copy of their own)
+        if (!b->bc_kit) return set_err(FFHIP_EINVAL, "barcodes: no kit is attached to the batch (ffhip_batch_set_barcodes)");
+        if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "barcodes: a flip-flop model only (the run-length model has no base strings)");
+        if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "barcodes need a decoded run (FFHIP_RUN_NO_DECODE is set)");
+        if (int rc = ensure_barcode_buffers(b)) return rc;
     }
     if (b->packed && !p.packable)
         return set_err(FFHIP_EINVAL, "packed batches take the default path and the launch-per-step kernels only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / unfused flags, ordinary temperature)");
@@ -1748,6 +1773,11 @@ static int run_back(ffhip_batch *b) {
             launch_viterbi(s, scores, b->tb, b->path, b->qpath, b->score(), nR, Tb, m->nbase, m->Ps, tbr, rmap);
             launch_assemble(s, b->path, b->qpath, b->bases(), b->quals(), b->lens(), nR, Tb, m->nbase, tbr, rmap);
             b->launches[5] += 2;
+            if (flags & FFHIP_RUN_BARCODES) {           // from the strings and lengths k_assemble has just written (run_front checked the kit and the model)
+                launch_barcodes(s, b->bc_kit->kit, b->bases(), b->lens(), b->bc_dev, nR, Tb, tbr, rmap, b->bc_max_dist, b->bc_min_sep, b->bc_both);
+                b->bc_valid = 1;
+                b->launches[5]++;
+            }
             if (flags & FFHIP_RUN_MOD_PROBS) {          // from the posterior whatever decoded the path (run_front checked the model)
                 launch_mod_probs(s, b->post, b->path, b->res.on_dev<uint8_t>(RF_ML), nR, Tb, m->Ps, tbr, rmap);
                 b->launches[5]++;
@@ -1771,6 +1801,7 @@ static int run_back(ffhip_batch *b) {
     b->res_copied = 0;
     if (b->packed) {
         HIP_TRY(hipMemcpyAsync(b->res.host, b->res.dev, b->res.copy_bytes(flags), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+        if (b->bc_valid) HIP_TRY(hipMemcpyAsync(b->bc_host, b->bc_dev, (size_t)nR * sizeof(ffhip_barcode_call), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the barcode records' one copy
         b->res_copied = 1;
     }
     HIP_TRY(hipEventRecord(eng->batch_done, s), FFHIP_EHIP); eng->batch_done_rec = 1;
@@ -1822,7 +1853,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
     const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
     b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
     b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0;
+    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0;
     return FFHIP_OK;
 }
 
@@ -1906,6 +1937,7 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
         }
         sd->ran = sd->finished = 0;
         sd->run_scale = b->run_scale;
+        sd->bc_kit = b->bc_kit; sd->bc_max_dist = b->bc_max_dist; sd->bc_min_sep = b->bc_min_sep; sd->bc_both = b->bc_both;      // (last_flags asks the side batch for the records too)
         if (int rc = ffhip_batch_run(sd, b->last_temperature, (fl & ~(unsigned)FFHIP_RUN_KEEP_ACTS) | FFHIP_RUN_F32_RNN)) return rc;
         if (int rc = ffhip_batch_finish(sd)) return rc;
         hipStream_t s = b->stream;
@@ -1928,6 +1960,10 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
                 HIP_TRY(hipMemcpyAsync(b->res.on_dev<char>((ResField)f) + to, sd->res.on_dev<char>((ResField)f) + from, bytes, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
                 memcpy(b->res.on_host<char>((ResField)f) + to, sd->res.on_host<char>((ResField)f) + from, bytes);
             }
+            if (b->bc_valid && sd->bc_valid) {          // and the read's barcode record, both halves
+                HIP_TRY(hipMemcpyAsync(b->bc_dev + r, sd->bc_dev + k, sizeof(ffhip_barcode_call), hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                b->bc_host[r] = sd->bc_host[k];
+            }
         }
         HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
     }
@@ -1947,7 +1983,11 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
         return FFHIP_OK;
     }
     // one copy: [sat | abort] and, when the batch was decoded, [lens | score | bases | quals] behind them (the block of ffhip_batch_create)
-    if (!b->res_copied) HIP_TRY(hipMemcpyAsync(b->res.host, b->res.dev, b->res.copy_bytes(b->last_flags), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
+    if (!b->res_copied) {
+        HIP_TRY(hipMemcpyAsync(b->res.host, b->res.dev, b->res.copy_bytes(b->last_flags), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
+        if (b->bc_valid)                                     // the barcode records' one copy (a packed batch: enqueued in run_back, as the block's)
+            HIP_TRY(hipMemcpyAsync(b->bc_host, b->bc_dev, (size_t)batch_nreads(b) * sizeof(ffhip_barcode_call), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
+    }
     b->res_copied = 0;
     HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
     if (rehearsal_rate() > 0) rehearsal_wait(b);          // (test hook above: the emulated GPU finishes this batch at rehearsal_done_at)
@@ -2038,6 +2078,62 @@ extern "C" int ffhip_batch_moves(const ffhip_batch *b, int read, const uint8_t *
     if (!(b->res_made & res_bit(RS_MOVES))) return set_err(FFHIP_EINVAL, "the move table was not made in this run (FFHIP_RUN_MOVES)");
     *moves = b->res.on_host<uint8_t>(RF_MV) + read_row1(b, read);
     if (nblock) *nblock = (size_t)b->hTb[read];
+    return FFHIP_OK;
+}
+
+// ---- barcodes (include/ffhip.h "barcodes"; the kernel: ffhip_barcodes.hip)
+extern "C" ffhip_barcodes *ffhip_barcodes_upload(ffhip_engine *eng, int n, const char *const *seq, int window) {
+    if (!eng || !seq) { set_err(FFHIP_EINVAL, "null engine or kit"); return nullptr; }
+    if (n < 1 || n > kBarcodeMaxKit) { set_err(FFHIP_EINVAL, "a barcode kit holds 1 .. %d patterns, not %d", kBarcodeMaxKit, n); return nullptr; }
+    if (window < 1 || window > kBarcodeMaxWindow) { set_err(FFHIP_EINVAL, "the barcode window is 1 .. %d bases, not %d", kBarcodeMaxWindow, window); return nullptr; }
+    std::vector<unsigned long long> peq((size_t)n * 8, 0ull);
+    std::vector<int> len(n, 0);
+    int lmin = kBarcodeMaxLen, lmax = 0;
+    for (int k = 0; k < n; k++) {
+        const size_t L = seq[k] ? strnlen(seq[k], kBarcodeMaxLen + 1) : 0;
+        if (L < 1 || L > (size_t)kBarcodeMaxLen) { set_err(FFHIP_EINVAL, "barcode %d: a pattern has 1 .. %d bases", k, kBarcodeMaxLen); return nullptr; }
+        for (size_t i = 0; i < L; i++) {
+            const char *at = strchr("ACGT", seq[k][i]);
+            if (!at) { set_err(FFHIP_EINVAL, "barcode %d: character %zu is not one of ACGT", k, i); return nullptr; }
+            peq[((size_t)k * 4 + (size_t)(at - "ACGT")) * 2 + i / 64] |= 1ull << (i % 64);
+        }
+        len[k] = (int)L;
+        lmin = std::min(lmin, (int)L); lmax = std::max(lmax, (int)L);
+    }
+    hipSetDevice(eng->device);
+    ffhip_barcodes *kit = new ffhip_barcodes();
+    kit->eng = eng; kit->lmin = lmin;
+    if (hipMalloc(&kit->d_peq, peq.size() * 8) != hipSuccess || hipMalloc(&kit->d_len, len.size() * 4) != hipSuccess) {
+        set_err(FFHIP_ENOMEM, "device allocation failed"); ffhip_barcodes_free(kit); return nullptr;
+    }
+    if (hipMemcpy(kit->d_peq, peq.data(), peq.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(kit->d_len, len.data(), len.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        set_err(FFHIP_EHIP, "upload of the barcode kit failed"); ffhip_barcodes_free(kit); return nullptr;
+    }
+    kit->kit = BarcodeKit{ (const unsigned long long *)kit->d_peq, (const int *)kit->d_len, n, window, lmax > 64 ? 2 : 1 };
+    return kit;
+}
+extern "C" void ffhip_barcodes_free(ffhip_barcodes *kit) {
+    if (!kit) return;
+    hipSetDevice(kit->eng->device);
+    if (kit->d_peq) hipFree(kit->d_peq);
+    if (kit->d_len) hipFree(kit->d_len);
+    delete kit;
+}
+extern "C" int ffhip_batch_set_barcodes(ffhip_batch *b, const ffhip_barcodes *kit, int max_dist, int min_sep, int both_ends) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (!kit) { b->bc_kit = nullptr; return FFHIP_OK; }
+    if (kit->eng != b->eng) return set_err(FFHIP_EINVAL, "the barcode kit belongs to another engine");
+    if (max_dist > 255 || min_sep > 255) return set_err(FFHIP_EINVAL, "barcodes: max_dist and min_sep are at most 255");
+    b->bc_kit = kit;
+    b->bc_max_dist = max_dist < 0 ? kit->lmin / 4 : max_dist;
+    b->bc_min_sep = min_sep < 0 ? 3 : min_sep;
+    b->bc_both = both_ends ? 1 : 0;
+    return FFHIP_OK;
+}
+extern "C" int ffhip_batch_barcode(const ffhip_batch *b, int read, ffhip_barcode_call *out) {
+    if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
+    if (!b->bc_valid || !b->bc_host) return set_err(FFHIP_EINVAL, "barcode records were not made in this run (FFHIP_RUN_BARCODES)");
+    *out = b->bc_host[read];
     return FFHIP_OK;
 }
 

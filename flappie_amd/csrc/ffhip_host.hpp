@@ -49,6 +49,14 @@ struct ffhip_engine {
 
 struct ffhip_prep;
 
+// a barcode kit on the device (ffhip_barcodes_upload; the kernel's view of it is BarcodeKit)
+struct ffhip_barcodes {
+    ffhip_engine *eng = nullptr;
+    ffhip::BarcodeKit kit{};
+    int lmin = 0;                       // the shortest pattern: the default max_dist is lmin / 4
+    void *d_peq = nullptr, *d_len = nullptr;
+};
+
 namespace ffhip {
 
 int set_err(int code, const char *fmt, ...);        // records the thread's last error text, returns `code`

@@ -210,6 +210,16 @@ void launch_assemble(hipStream_t s, const int *path, const float *qpath, char *b
 void launch_mod_probs(hipStream_t s, const float *post, const int *path, uint8_t *ml, int nread, int Tb, int Ps, const int *tbs = nullptr, ReadMap map = ReadMap());
 // move table of the called bases (k_moves): one byte a block at the read's row of the (Tb + 1)-entry buffers, 1 where the block's transition emits a base
 void launch_moves(hipStream_t s, const int *path, uint8_t *moves, int nread, int Tb, const int *tbs = nullptr, ReadMap map = ReadMap());
+// barcode classification of the called reads (k_barcodes, ffhip_barcodes.hip): one 16-byte record a read (the layout of include/ffhip.h's ffhip_barcode_call) from the
+// base strings and their lengths; dist_out / end_out, when given, take the whole [2][n] matrices of distances and end positions of read 0 (a launch of one read)
+constexpr int kBarcodeMaxKit = 128, kBarcodeMaxLen = 128, kBarcodeMaxWindow = 256;
+struct BarcodeKit {
+    const unsigned long long *peq;      // [n][4][2]: bit i of word w of peq[k][c] = pattern k has base c (A C G T) at position 64 w + i
+    const int *len;                     // [n]
+    int n, window, words;               // patterns, bases of a window, 64-bit words the longest pattern takes (1 or 2)
+};
+void launch_barcodes(hipStream_t s, BarcodeKit kit, const char *bases, const int *lens, void *records, int nread, int Tb, const int *tbs, ReadMap map,
+                     int max_dist, int min_sep, int both_ends, int *dist_out = nullptr, int *end_out = nullptr);
 // exp + trace_from_posterior
 void launch_trace(hipStream_t s, const float *post, int32_t *trace, int nread, int Tb, int nbase, int Ps, int is_log, const int *tbs = nullptr, ReadMap map = ReadMap());
 void launch_exp_inplace(hipStream_t s, float *x, size_t n);

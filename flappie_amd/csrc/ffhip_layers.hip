@@ -655,6 +655,24 @@ extern "C" int ffhip_op_moves(ffhip_engine *eng, const int *path, size_t nblock,
     return FFHIP_OK;
 }
 
+// distances and end positions of every pattern of a kit at both ends of one call (k_barcodes; include/ffhip.h "barcodes")
+extern "C" int ffhip_op_barcode_scores(ffhip_engine *eng, const ffhip_barcodes *kit, const char *bases, size_t len, int32_t *dist, int32_t *end) {
+    OP_ENTER(eng);
+    if (!kit || kit->eng != eng || (!bases && len) || !dist || !end || len > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "bad barcode score arguments (a kit of this engine, a call of len characters, two outputs of 2 n entries)");
+    for (size_t i = 0; i < len; i++) if (!bases[i] || !strchr("ACGTZ", bases[i])) return set_err(FFHIP_EINVAL, "barcode scores: character %zu of the call is not one of ACGTZ", i);
+    const int n = kit->kit.n, ilen = (int)len;
+    char *d_bases = (char *)(len ? tmp.upload(bases, len, s) : tmp.get(4));
+    int *d_len = (int *)tmp.upload(&ilen, 4, s);
+    int *d_out = (int *)tmp.get((size_t)4 * n * 4);
+    void *d_rec = tmp.get(16);
+    if (!d_bases || !d_len || !d_out || !d_rec) OP_NOMEM();
+    launch_barcodes(s, kit->kit, d_bases, d_len, d_rec, 1, ilen > 0 ? ilen : 1, nullptr, ReadMap(), kit->lmin / 4, 3, 0, d_out, d_out + 2 * n);
+    HIP_TRY(hipMemcpyAsync(dist, d_out, (size_t)2 * n * 4, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipMemcpyAsync(end, d_out + 2 * n, (size_t)2 * n * 4, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+
 // ---- decoders of the first run-length head (decode.c:552-892): param is [4 nbase x nblock]
 static bool rl1_dims(const ffhip_mat &param, int *nbase) {
     if (!view_ok(param) || param.nr % 4 != 0 || param.nr / 4 < 1 || param.nr / 4 > 8) return false;

@@ -39,6 +39,7 @@
 #include "../../include/flappie_output.h"
 #include "../../include/flappie_modbase.h"
 #include "../../include/flappie_moves.h"
+#include "../../include/flappie_barcodes.h"
 #include "../../include/networks.h"
 
 const char *argp_program_version = "flappie (MI355X/HIP) 0.1, interface of flappie 2.1.3";
@@ -56,7 +57,11 @@ static struct argp_option options[] = {
     {"model", 'm', "name", 0, "Model to use (\"help\" to list)"},
     {"output", 'o', "filename", 0, "Write to file rather than stdout"},
     {"prefix", 'p', "string", 0, "Prefix to append to name of each read"},
+#ifdef BUILD_RUNNIE
     {"reverse", 'r', 0, 0, "Reverse output base calls"},
+#else
+    {"reverse", 'r', 0, 0, "Reverse output base calls (the mv tag of --emit-moves and the barcode tags of --barcodes keep describing the call in signal order)"},
+#endif
     {"no-reverse", 6, 0, OPTION_ALIAS, "Don't reverse output base calls"},
     {"temperature", 7, "factor", 0, "Temperature for weights"},
     {"trim", 't', "start:end", 0, "Number of samples to trim, as start:end"},
@@ -82,6 +87,15 @@ static struct argp_option options[] = {
 #else
     {"modbase-tags", 23, 0, 0, "Report modified bases as SAM MM/ML tags (5mC probabilities made on the GPU): Z is written as C and every C gets a probability (models with a modified base only, e.g. r941_5mC)"},
     {"emit-moves", 24, 0, 0, "Report where in the signal each base sits: the move table and signal tags of guppy --moves_out / dorado --emit-moves (qs, ns, ts, sm, sd, sv, mv), with the moves made on the GPU. mv is always in signal order: with --reverse SEQ, QUAL and ML are reversed and mv is not"},
+    {"barcodes", 25, "kit.fa", 0, "Demultiplex: classify every read against the barcodes of a FASTA file (1-128 records, the record's name is the barcode's, patterns of 1-128 bases over ACGT), scored on the GPU at both ends of the call. Every record gains BC:Z:<name> (or unclassified), bd:i: (best distance), bn:i: (runner-up's distance) and bp:B:s,<front_end>,<rear_end>, behind MM / ML and the move tags; a summary of reads per barcode goes to stderr. The tags describe the call in signal order, with --reverse too"},
+    {"barcode-window", 26, "bases", 0, "With --barcodes: bases searched at each end of a call (1-256, default 150)"},
+    {"barcode-max-dist", 27, "edits", 0, "With --barcodes: largest edit distance of an accepted barcode (default: a quarter of the kit's shortest pattern, rounded down)"},
+    {"barcode-min-sep", 28, "edits", 0, "With --barcodes: least distance between the best barcode and the runner-up (default 3)"},
+    {"barcode-both-ends", 29, 0, 0, "With --barcodes: a barcode must be found at both ends (its score is the larger of its two distances)"},
+    {"trim-barcodes", 30, 0, 0, "With --barcodes: cut the barcode and what precedes it from SEQ and QUAL of classified reads, at each end where it was found (not with --emit-moves, --modbase-tags or --trace)"},
+#endif
+#ifdef BUILD_RUNNIE
+    {"barcodes", 25, "kit.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
 #endif
     {0}
 };
@@ -118,8 +132,11 @@ static struct {
     double run_scale[4];
     bool modbase_tags;                  /* flappie: --modbase-tags given */
     bool emit_moves;                    /* flappie: --emit-moves given */
+    char *barcodes;                     /* flappie: --barcodes kit file; window, max_dist, min_sep (-1: the defaults), both ends, trim */
+    int bc_window, bc_max_dist, bc_min_sep;
+    bool bc_both, bc_trim, bc_opts;     /* bc_opts: one of the other barcode options was given */
 } args = { 1, 200, 0.0f, NULL, FLAPPIE_OUTFORMAT_FASTQ, 0, DEFAULT_MODEL, NULL, "", false, 1.0f, 200, 10, 100, 0.0f, false, NULL, true, 0, 4, 0, 0, false, false, false, false,
-           { 1.02, 1.04, 1.04, 1.02 } };      /* batch 0: by model (below); nshard 0: --shard not given */
+           { 1.02, 1.04, 1.04, 1.02 }, false, false, NULL, 150, -1, -1, false, false, false };      /* batch 0: by model (below); nshard 0: --shard not given */
 
 static void print_models(FILE *fh) {
     for (int mdl = 0; mdl < (int)flappie_nmodel; mdl++)
@@ -228,6 +245,23 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
 #else
     case 23: args.modbase_tags = true; break;
     case 24: args.emit_moves = true; break;
+#endif
+    case 25: args.barcodes = arg; break;
+#ifndef BUILD_RUNNIE
+    case 26:
+        args.bc_window = atoi(arg); args.bc_opts = true;
+        if (args.bc_window < 1 || args.bc_window > 256) errx(EXIT_FAILURE, "--barcode-window must be between 1 and 256");
+        break;
+    case 27:
+        args.bc_max_dist = atoi(arg); args.bc_opts = true;
+        if (args.bc_max_dist < 0 || args.bc_max_dist > 255) errx(EXIT_FAILURE, "--barcode-max-dist must be between 0 and 255");
+        break;
+    case 28:
+        args.bc_min_sep = atoi(arg); args.bc_opts = true;
+        if (args.bc_min_sep < 0 || args.bc_min_sep > 255) errx(EXIT_FAILURE, "--barcode-min-sep must be between 0 and 255");
+        break;
+    case 29: args.bc_both = true; args.bc_opts = true; break;
+    case 30: args.bc_trim = true; args.bc_opts = true; break;
 #endif
     case ARGP_KEY_NO_ARGS: argp_usage(state); break;
     case ARGP_KEY_ARG:
@@ -367,6 +401,8 @@ typedef struct {
     uint8_t *mv;                        /* --emit-moves: the move byte of every block, in signal order (owned); res.pos holds the block of every base */
     int mv_stride;                      /* ... the samples a block */
     float sm, sd;                       /* ... the median and MAD the read was normalised with */
+    ffhip_barcode_call bc;              /* --barcodes: the read's record */
+    int have_bc;
     int rle_nocall;                     /* runnie --fasta: no runs, or a failed run-length estimate (decode_runnie.py: "No basecall returned") */
     /* a read of a MULTI-READ file: its samples as the file holds them (owned; res.rt.raw stays NULL, res.rt.n counts them) and its calibration -- the
      * preparation scales them on the device (ffhip_prep_begin_dac) */
@@ -433,6 +469,10 @@ static size_t pack_row_cap(size_t want) {
  * later (flappie.c:264-316 after normalisation) -- so the host side of the next group overlaps the GPU side of this one. */
 struct chunk_ctx;
 typedef struct { ffhip_batch *b; int cached, n, *idx; item **its; const ffhip_prep *prep; struct chunk_ctx *owner; int packed; } pending_batch;
+/* flappie --barcodes: the kit as the file gave it and on the device; reads per barcode, the last entry the unclassified ones */
+static flappie_barcode_kit *bc_kit = NULL;
+static ffhip_barcodes *bc_dev = NULL;
+static unsigned long long bc_count[FLAPPIE_BARCODE_MAX_KIT + 1];
 #ifdef BUILD_RUNNIE
 /* --fasta: the runs and their run-length estimates come from the device (FFHIP_RUN_RLE_RUNS) with the batch's scale factors */
 static unsigned run_flags(void) { return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.fasta ? FFHIP_RUN_RLE_RUNS : 0u); }
@@ -441,12 +481,16 @@ static int batch_run(ffhip_batch *b, unsigned flags) {
     return ffhip_batch_run(b, args.temperature, flags);
 }
 #else
-/* --modbase-tags: the 5mC bytes of the called bases come from the device (FFHIP_RUN_MOD_PROBS); --emit-moves: the move table does (FFHIP_RUN_MOVES) */
+/* --modbase-tags: the 5mC bytes of the called bases come from the device (FFHIP_RUN_MOD_PROBS); --emit-moves: the move table does (FFHIP_RUN_MOVES);
+ * --barcodes: the reads' barcode records do (FFHIP_RUN_BARCODES) */
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u) |
-           (args.emit_moves ? FFHIP_RUN_MOVES : 0u);
+           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u);
 }
-static int batch_run(ffhip_batch *b, unsigned flags) { return ffhip_batch_run(b, args.temperature, flags); }
+static int batch_run(ffhip_batch *b, unsigned flags) {
+    if (bc_dev) { const int rc = ffhip_batch_set_barcodes(b, bc_dev, args.bc_max_dist, args.bc_min_sep, args.bc_both); if (rc) return rc; }
+    return ffhip_batch_run(b, args.temperature, flags);
+}
 #endif
 
 /* n reads in the rows of one packed batch: slot_of / off_of from ffhip_pack_plan, `cap` the row capacity it was made for */
@@ -703,6 +747,10 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
                 if (args.delta == 0.0f && 0 != ffhip_prep_stats(prep, idx[i], &its[i]->sm, &its[i]->sd)) warnx("%s", ffhip_last_error());
             }
         }
+        if (bc_dev) {                                          /* the record describes the call in signal order whatever --reverse does to the strings */
+            if (0 != ffhip_batch_barcode(b, i, &its[i]->bc) || its[i]->bc.best >= bc_kit->n) warnx("%s", ffhip_last_error());
+            else { its[i]->have_bc = 1; bc_count[its[i]->bc.best >= 0 ? its[i]->bc.best : bc_kit->n]++; }
+        }
         if (args.reverse) {                                    /* flappie.c:294-297 */
             reverse_char_array(r->basecall, blen);
             reverse_char_array(r->quality, blen);
@@ -863,7 +911,13 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
             char *multi_name = NULL;              /* --no-uuid, a read of a multi-read file: <file>:<read id> (the file's name alone would stand for thousands of reads) */
             if (it->from_multi && NULL != (multi_name = malloc(strlen(base) + strlen(uuid) + 2))) { sprintf(multi_name, "%s:%s", base, uuid); base = multi_name; }
             /* --modbase-tags: Z is written as C here, in the record only -- the trace file below keeps the call as it is */
-            if (args.emit_moves) {
+            if (NULL != bc_kit) {
+                if (!it->have_bc) warnx("No barcode record for %s", it->filename);
+                else if (args.emit_moves && NULL == it->mv) warnx("No move table for %s", it->filename);
+                else if (args.modbase_tags && NULL == it->ml) warnx("No base-modification probabilities for %s", it->filename);
+                else fprintf_barcode_record(args.outformat, args.output, uuid, base, args.uuid, args.prefix, it->res, args.modbase_tags ? it->ml : NULL,
+                                            args.emit_moves ? it->mv : NULL, it->mv_stride, it->sm, it->sd, args.delta != 0.0f, &it->bc, bc_kit, args.bc_trim, args.reverse);
+            } else if (args.emit_moves) {
                 if (NULL == it->mv) warnx("No move table for %s", it->filename);
                 else if (args.modbase_tags && NULL == it->ml) warnx("No base-modification probabilities for %s", it->filename);
                 else fprintf_moves_record(args.outformat, args.output, uuid, base, args.uuid, args.prefix, it->res, args.modbase_tags ? it->ml : NULL, it->mv,
@@ -890,6 +944,7 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
         it->ml = NULL;
         free(it->mv);
         it->mv = NULL;
+        it->have_bc = 0;
         free_raw_basecall_info(&it->res);
         free(it->filename);
     }
@@ -1590,7 +1645,17 @@ int main(int argc, char *argv[]) {
     argp_parse(&argp, argc, argv, 0, 0, NULL);
 #ifdef BUILD_RUNNIE
     if ((args.rlc || args.run_scale_set) && !args.fasta) errx(EXIT_FAILURE, "--rlc and --run-scale go with --fasta");
+    if (args.barcodes) errx(EXIT_FAILURE, "--barcodes is flappie's: the run-length model's records carry no base strings to search");
 #else
+    /* --barcodes: every refusal before any file or the GPU is touched */
+    if (args.bc_opts && NULL == args.barcodes) errx(EXIT_FAILURE, "--barcode-window, --barcode-max-dist, --barcode-min-sep, --barcode-both-ends and --trim-barcodes go with --barcodes");
+    if (args.bc_trim && (args.emit_moves || args.modbase_tags || NULL != args.trace))
+        errx(EXIT_FAILURE, "--trim-barcodes does not go with --emit-moves, --modbase-tags or --trace: their positions and probabilities are the untrimmed call's");
+    if (args.barcodes) {
+        char why[256];
+        bc_kit = flappie_barcode_kit_read(args.barcodes, why, sizeof why);
+        if (NULL == bc_kit) errx(EXIT_FAILURE, "--barcodes %s: %s", args.barcodes, why);
+    }
     if (args.modbase_tags && !flappie_model_has_modbase(args.model))      /* (the registry knows: before any file or the GPU is touched) */
         errx(EXIT_FAILURE, "--modbase-tags needs a model with a modified base (r941_5mC); \"%s\" has none", flappie_model_string(args.model));
 #endif
@@ -1615,6 +1680,12 @@ int main(int argc, char *argv[]) {
     }
 #endif
     struct ffhip_engine *eng = flappie_hip_engine();
+#ifndef BUILD_RUNNIE
+    if (bc_kit && NULL == (bc_dev = ffhip_barcodes_upload(eng, bc_kit->n, (const char *const *)bc_kit->seq, args.bc_window))) {
+        stop_reader_procs();
+        errx(EXIT_FAILURE, "--barcodes: %s", ffhip_last_error());
+    }
+#endif
     hid_t hdf5out = open_or_create_hdf5(args.trace);
     reader_state rs;
     memset(&rs, 0, sizeof(rs));
@@ -1675,6 +1746,14 @@ int main(int argc, char *argv[]) {
      * clamped, the engine ran them again on its f32 kernels (include/ffhip.h, ffhip_engine_f32_reruns) */
     if (ffhip_engine_f32_reruns(eng) > 0)
         warnx("%llu read(s) held samples beyond the range of the default kernels' operand format and were evaluated on the f32 kernels", ffhip_engine_f32_reruns(eng));
+#ifndef BUILD_RUNNIE
+    if (bc_kit) {                      /* reads per barcode, then the unclassified ones */
+        for (int k = 0; k < bc_kit->n; k++) fprintf(stderr, "barcode\t%s\t%llu\n", bc_kit->name[k], bc_count[k]);
+        fprintf(stderr, "barcode\tunclassified\t%llu\n", bc_count[bc_kit->n]);
+        ffhip_barcodes_free(bc_dev);
+        flappie_barcode_kit_free(bc_kit);
+    }
+#endif
     flappie_hip_shutdown();
     if (reader_failures) { warnx("%d reader process(es) failed; see the warnings above", reader_failures); return EXIT_FAILURE; }
     if (n_lost_reads > 0) { warnx("%llu read(s) were not called: their batches failed (see the warnings above)", n_lost_reads); return EXIT_FAILURE; }

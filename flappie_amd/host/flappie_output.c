@@ -1,7 +1,8 @@
 /*  flappie_output.c -- record formatting (include/flappie_output.h), byte-compatible with
  *  /root/reference/src/flappie_output.c:16-132 (including the SAM record's repeated sequence/quality
  *  line, which the reference emits); the records with SAMv1 1.7 base-modification tags
- *  (include/flappie_modbase.h); and the records with the move table and signal tags (include/flappie_moves.h).
+ *  (include/flappie_modbase.h); the records with the move table and signal tags (include/flappie_moves.h); and the records with
+ *  the barcode tags behind any of those (include/flappie_barcodes.h).
  */
 #include <err.h>
 #include <math.h>
@@ -10,6 +11,7 @@
 #include "../../include/flappie_output.h"
 #include "../../include/flappie_modbase.h"
 #include "../../include/flappie_moves.h"
+#include "../../include/flappie_barcodes.h"
 
 enum flappie_outformat_type get_outformat(const char *formatstr) {
     if (NULL == formatstr) return FLAPPIE_OUTFORMAT_INVALID;
@@ -226,4 +228,40 @@ void fprintf_moves_record(enum flappie_outformat_type outformat, FILE *fp, const
     else sprintf(tail, "\t%s", tags);
     put_tagged_record(outformat, fp, uuid, readname, uuid_primary, prefix, &res, seq, tail);
     free(tail); free(tags); free(seq); free(mm); free(mv);
+}
+
+/* ---- records with the barcode tags (include/flappie_barcodes.h): behind MM / ML and the move tags when the record carries those ---- */
+void fprintf_barcode_record(enum flappie_outformat_type outformat, FILE *fp, const char *uuid, const char *readname, bool uuid_primary, const char *prefix,
+                            const struct _raw_basecall_info res, const uint8_t *ml, const uint8_t *moves, int stride, float median, float mad, bool delta,
+                            const ffhip_barcode_call *bc, const flappie_barcode_kit *kit, bool trim, bool reversed) {
+    if (FLAPPIE_OUTFORMAT_FASTQ == outformat && NULL == res.quality) {
+        warnx("Can't output fastq for reads without quality values");
+        return;
+    }
+    const char *name = uuid_primary ? uuid : readname;
+    if (trim && (NULL != ml || NULL != moves)) errx(EXIT_FAILURE, "barcodes are not trimmed from a record with base-modification or move tags (%s)", name);
+    char *mm = NULL, *mv = NULL, *seq = NULL, *mtags = NULL, *qual = NULL;
+    if (NULL != ml) seq = modbase_seq(&res, ml, &mm, &mv);
+    else seq = strdup(res.basecall ? res.basecall : "");
+    if (NULL != moves) mtags = flappie_moves_tags(moves, res.nblock, stride, &res.rt, res.quality, median, mad, delta);
+    char *btags = flappie_barcode_tags(bc, kit);
+    if (NULL == seq || NULL == btags || (NULL != moves && NULL == mtags)) errx(EXIT_FAILURE, "no barcode tags for %s (out of memory, or a record that does not belong to the kit)", name);
+    struct _raw_basecall_info out = res;
+    if (trim) {      /* the cuts are the call's in signal order; a reversed SEQ loses them at its other ends */
+        const size_t len = strlen(seq);
+        size_t from = 0, to = len;
+        if (flappie_barcode_trim(bc, len, &from, &to)) warnx("%s: the barcode cuts at the two ends meet or cross; the record is written empty", name);
+        else if (reversed) { const size_t f = len - to; to = len - from; from = f; }
+        memmove(seq, seq + from, to - from);
+        seq[to - from] = 0;
+        if (NULL != res.quality && strlen(res.quality) == len && NULL != (qual = strndup(res.quality + from, to - from))) out.quality = qual;
+    }
+    char *tail = malloc((mm ? strlen(mm) + strlen(mv) + 2 : 0) + (mtags ? strlen(mtags) + 1 : 0) + strlen(btags) + 2);
+    if (NULL == tail) errx(EXIT_FAILURE, "out of memory for the barcode tags of %s", name);
+    size_t a = 0;
+    if (mm) a += (size_t)sprintf(tail + a, "\t%s\t%s", mm, mv);
+    if (mtags) a += (size_t)sprintf(tail + a, "\t%s", mtags);
+    sprintf(tail + a, "\t%s", btags);
+    put_tagged_record(outformat, fp, uuid, readname, uuid_primary, prefix, &out, seq, tail);
+    free(tail); free(btags); free(mtags); free(seq); free(mm); free(mv); free(qual);
 }

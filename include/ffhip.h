@@ -96,6 +96,11 @@ typedef struct {
  * device from the Viterbi path (k_moves) and brought down in ffhip_batch_finish's one copy of the result block.  Everything else the run returns is that of the same
  * run without the flag.  The run-length model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
 #define FFHIP_RUN_MOVES       8192u
+/* Barcode classification of a flip-flop model's calls (ffhip_batch_barcode below, "barcodes"): one 16-byte record a read, made on the device from the base strings
+ * (k_barcodes) against the kit attached with ffhip_batch_set_barcodes.  The records are NOT part of the result block: they live in a small buffer of their own
+ * (reads x 16 bytes) and come down in ONE extra copy, enqueued where the result block's copy is.  Everything else the run returns is that of the same run without the
+ * flag.  No kit attached, the run-length model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
+#define FFHIP_RUN_BARCODES   16384u
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -371,6 +376,29 @@ int ffhip_op_mod_probs(ffhip_engine *eng, ffhip_mat logpost, const int *path, ui
  * ffhip_op_moves: the kernel on one host path of nblock + 1 entries (nblock >= 1); moves: caller-owned, nblock bytes. */
 int ffhip_batch_moves(const ffhip_batch *b, int read, const uint8_t **moves, size_t *nblock);
 int ffhip_op_moves(ffhip_engine *eng, const int *path, size_t nblock, uint8_t *moves);
+/* Barcodes: which sample a read belongs to.
+ *   Kit: n patterns, 1 <= n <= 128, each a string over ACGT (upper case) of 1 .. 128 bases; anything else is refused.
+ *   Windows of a call s of `len` bases (Z read as C) at window size W, 1 <= W <= 256: front = s[0 : min(W, len)], rear = revcomp(s)[0 : min(W, len)] -- both ends are
+ *     the same search of the same patterns.
+ *   Infix edit distance of a pattern p (L bases) in a window x (m bases), edlib's HW mode: D[0][j] = 0, D[i][0] = i,
+ *     D[i][j] = min(D[i-1][j-1] + (p[i] != x[j]), D[i-1][j] + 1, D[i][j-1] + 1); dist = min_j D[L][j] over j = 0 .. m, end = the SMALLEST j that attains it
+ *     (an empty window: dist = L, end = 0).
+ *   Classification with max_dist, min_sep, both_ends: s_k = min(dist_front_k, dist_rear_k) (both_ends: their max); b = the smallest k of the minimal s_k;
+ *     second = min over k != b of s_k (a kit of one pattern: 255); the read is classified to b iff s_b <= max_dist and second - s_b >= min_sep.
+ *   The record: best = b or -1; and in every case best_dist = s_b, second_dist, front_dist / front_end / rear_dist / rear_end of pattern b, ends = bit 0 if
+ *     front_dist <= max_dist, bit 1 if rear_dist <= max_dist.  An empty slot of a batch: best -1, all four distances 255.
+ * ffhip_barcodes_upload: the kit's tables on the engine's device (NULL with a text on a bad kit); the kit must outlive the batches it is attached to.
+ * ffhip_batch_set_barcodes: the kit and the parameters of the batch's later runs with FFHIP_RUN_BARCODES; max_dist < 0: floor(Lmin / 4), Lmin the kit's shortest
+ *   pattern; min_sep < 0: 3; both at most 255.  kit == NULL detaches.
+ * ffhip_batch_barcode: after ffhip_batch_finish of a run with the flag.  A run without it: FFHIP_EINVAL.
+ * ffhip_op_barcode_scores: the kernel on one call of `len` characters of ACGTZ (len may be 0): the whole matrices dist[2][n], end[2][n], front first. */
+typedef struct ffhip_barcodes ffhip_barcodes;
+typedef struct { int16_t best; uint8_t best_dist, second_dist, front_dist, rear_dist, ends, pad; int16_t front_end, rear_end; int32_t reserved; } ffhip_barcode_call; /* 16 bytes */
+ffhip_barcodes *ffhip_barcodes_upload(ffhip_engine *eng, int n, const char *const *seq, int window);
+void ffhip_barcodes_free(ffhip_barcodes *kit);
+int ffhip_batch_set_barcodes(ffhip_batch *b, const ffhip_barcodes *kit, int max_dist, int min_sep, int both_ends);
+int ffhip_batch_barcode(const ffhip_batch *b, int read, ffhip_barcode_call *out);
+int ffhip_op_barcode_scores(ffhip_engine *eng, const ffhip_barcodes *kit, const char *bases, size_t len, int32_t *dist /*[2][n]*/, int32_t *end /*[2][n]*/);
 int ffhip_runlength_viterbi(ffhip_engine *eng, ffhip_mat param, int *path /* nblock */, float *score);
 /* decoders of the first-generation head on [4 nbase x nblock] matrices: decode_runlength (decode.c:694-767), posterior_runlength
  * (decode.c:793-892; post is [4 nbase x nblock + 1]), runlengths_mean (decode.c:576-603) */
