@@ -32,6 +32,7 @@ RLE_SCALE_DEFAULT = (1.02, 1.04, 1.04, 1.02)      # decode_runnie.py's default -
 RUN_MOD_PROBS = 4096      # 5-base model: 5mC probabilities (SAM ML bytes) of the called bases made on the device (Batch.mod_probs)
 RUN_MOVES = 8192          # flip-flop model: the move table (one byte a block, 1 where a base is emitted) made on the device (Batch.moves)
 RUN_BARCODES = 16384      # flip-flop model: one barcode record a read made on the device against the kit of Batch.set_barcodes (Batch.barcode)
+RUN_REMAP = 32768         # flip-flop model: each read's signal mapped to the sequence of Batch.set_remap on the device (Batch.remap)
 # ffhip_debug_gate_math forms (include/ffhip.h)
 GATE_FORMS = ("logistic_ref", "tanh_ref", "logistic_ref4_lean", "logistic_ref2_lean", "logistic_ref_lean", "tanh_ref_lean",
               "swish_act4", "tanh_act4", "logistic_hw1", "tanh_hw1", "logistic_hw2", "tanh_hw2")
@@ -78,6 +79,11 @@ class CBarcodeCall(C.Structure):
     """ffhip_barcode_call (include/ffhip.h): 16 bytes"""
     _fields_ = [("best", C.c_int16), ("best_dist", C.c_uint8), ("second_dist", C.c_uint8), ("front_dist", C.c_uint8), ("rear_dist", C.c_uint8),
                 ("ends", C.c_uint8), ("pad", C.c_uint8), ("front_end", C.c_int16), ("rear_end", C.c_int16), ("reserved", C.c_int32)]
+
+
+class CRemapCall(C.Structure):
+    """ffhip_remap_call (include/ffhip.h)"""
+    _fields_ = [("status", C.c_int), ("L", C.c_size_t), ("score", C.c_float), ("rm", C.POINTER(C.c_uint8)), ("nblock", C.c_size_t)]
 
 
 class CRawTable(C.Structure):
@@ -204,6 +210,10 @@ def lib():
     L.ffhip_batch_set_barcodes.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.ffhip_batch_barcode.argtypes = [vp, C.c_int, C.POINTER(CBarcodeCall)]
     L.ffhip_op_barcode_scores.argtypes = [vp, vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.ffhip_batch_set_remap.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t), C.c_int]
+    L.ffhip_batch_remap.argtypes = [vp, C.c_int, C.POINTER(CRemapCall)]
+    L.ffhip_op_remap.argtypes = [vp, CFMat, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_float)]
+    L.ffhip_debug_remap_form.argtypes = [C.c_size_t, C.c_int]
     _LIB = L
     return L
 
@@ -564,6 +574,29 @@ class Batch:
         _check(lib().ffhip_batch_barcode(self.h, read, C.byref(c)))
         return {f: int(getattr(c, f)) for f in BARCODE_FIELDS}
 
+    def set_remap(self, seqs, band: int = 2048):
+        """the sequences and band of later runs with RUN_REMAP (ffhip_batch_set_remap): one entry a read, None (no sequence) or codes 0 .. nbase - 1 in signal order; seqs None detaches"""
+        if seqs is None:
+            _check(lib().ffhip_batch_set_remap(self.h, 0, None, None, int(band)))
+            return
+        n = len(seqs)
+        arrs = [None if q is None else np.ascontiguousarray(q, dtype=np.uint8) for q in seqs]
+        ptrs = (C.POINTER(C.c_uint8) * max(1, n))()
+        lens = (C.c_size_t * max(1, n))()
+        dummy = np.zeros(1, np.uint8)
+        for r, a in enumerate(arrs):
+            if a is not None:
+                ptrs[r] = (a if a.size else dummy).ctypes.data_as(C.POINTER(C.c_uint8))
+                lens[r] = a.size
+        _check(lib().ffhip_batch_set_remap(self.h, n, ptrs, lens, int(band)))
+
+    def remap(self, read: int) -> dict:
+        """remap record of a run with RUN_REMAP (ffhip_batch_remap): status, L, score (float32), rm (uint8 [nblock], None unless status is 1), nblock"""
+        c = CRemapCall()
+        _check(lib().ffhip_batch_remap(self.h, read, C.byref(c)))
+        rm = np.ctypeslib.as_array(c.rm, shape=(c.nblock,)).copy() if c.status == 1 and c.nblock else None
+        return {"status": int(c.status), "L": int(c.L), "score": np.float32(c.score), "rm": rm, "nblock": int(c.nblock)}
+
     def transitions(self, read: int) -> np.ndarray:
         out = np.zeros((self.read_nblock(read), self.P), dtype=np.float32)
         _check(lib().ffhip_batch_get_transitions(self.h, read, _fptr(out)))
@@ -713,6 +746,16 @@ def op_barcode_scores(engine: Engine, kit: Barcodes, bases) -> tuple:
     dist, end = np.zeros((2, kit.n), np.int32), np.zeros((2, kit.n), np.int32)
     _check(lib().ffhip_op_barcode_scores(engine.h, kit.h, b, len(b), dist.ctypes.data_as(C.POINTER(C.c_int32)), end.ctypes.data_as(C.POINTER(C.c_int32))))
     return dist, end
+
+
+def op_remap(engine: Engine, trans: np.ndarray, nbase: int, codes, band: int = 2048) -> tuple:
+    """ffhip_op_remap: (rm uint8 [nblock], score float32) of ONE read's transition scores `trans` [nblock][nstate (nbase + 1)] mapped to `codes` (0 .. nbase - 1, signal order)"""
+    t = np.ascontiguousarray(trans, dtype=np.float32)
+    q = np.ascontiguousarray(codes, dtype=np.uint8)
+    rm, score = np.zeros(t.shape[0], np.uint8), C.c_float(0.0)
+    _check(lib().ffhip_op_remap(engine.h, CFMat(_fptr(t), t.shape[1], t.shape[0], t.shape[1]), int(nbase), (q if q.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), q.size, int(band),
+                                rm.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(score)))
+    return rm, np.float32(score.value)
 
 
 def basecall_reads(dmodel: DeviceModel, signals: np.ndarray, temperature: float = 1.0, flags: int = 0):

@@ -14,11 +14,6 @@
 // (lowest index first) and the runner-up by two butterfly reductions and writes the read's 16-byte record: nothing else leaves the kernel.
 #include "ffhip_internal.hpp"
 
-#ifndef FFHIP_DECODE_PRIO
-#define FFHIP_DECODE_PRIO 2
-#endif
-#define FFHIP_DECODE_PRIO_SET() __builtin_amdgcn_s_setprio(FFHIP_DECODE_PRIO)
-
 namespace ffhip {
 
 constexpr int kBcThreads = 2 * kBarcodeMaxKit;

@@ -36,10 +36,6 @@
 #define FFHIP_CHAIN_PRIO 3
 #endif
 #define FFHIP_CHAIN_PRIO_SET() __builtin_amdgcn_s_setprio(FFHIP_CHAIN_PRIO)
-#ifndef FFHIP_DECODE_PRIO
-#define FFHIP_DECODE_PRIO 2
-#endif
-#define FFHIP_DECODE_PRIO_SET() __builtin_amdgcn_s_setprio(FFHIP_DECODE_PRIO)
 #ifndef FFHIP_FB_CHUNK8
 #define FFHIP_FB_CHUNK8 32
 #endif

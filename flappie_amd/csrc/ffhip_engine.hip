@@ -762,6 +762,18 @@ struct ffhip_batch {
     int bc_max_dist = 0, bc_min_sep = 3, bc_both = 0;
     ffhip_barcode_call *bc_dev = nullptr, *bc_host = nullptr;
     int bc_valid = 0;                   // the last run made them
+    // Remap (FFHIP_RUN_REMAP, k_remap): the coded sequences of ffhip_batch_set_remap on the host and (rmp_dseq) on the device; ONE buffer of cap_reads 16-byte records and,
+    // behind them, a byte a block in the layout of the (Tb + 1)-entry buffers (rmp_dev, its pinned mirror rmp_host), with one copy of its own beside the block's; the
+    // reads' list (pinned, and on the device) and the traceback workspace, both written by the front of every run that asks, the workspace grown when a run needs more
+    std::vector<std::vector<unsigned short>> rmp_seq;      // per read: stay | move << 8 of every position (remap_code)
+    std::vector<signed char> rmp_state;                     // per read: 0 no sequence, 1 a sequence, 2 refused at the call (L = 0)
+    int rmp_set = 0, rmp_band = 0, rmp_valid = 0;
+    unsigned short *rmp_dseq = nullptr; size_t rmp_dseq_cap = 0;
+    unsigned long long *rmp_ws = nullptr; size_t rmp_ws_cap = 0;
+    RemapRead *rmp_dlist = nullptr, *rmp_hlist = nullptr;
+    uint8_t *rmp_dev = nullptr, *rmp_host = nullptr;
+    int rmp_count[kRemapForms] = { 0, 0, 0, 0 };
+    size_t rmp_bytes() const { return (size_t)cap_reads * 16 + (size_t)nread * ((size_t)Tb + 1); }
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
     std::vector<void *> owned;
     unsigned last_flags = 0;
@@ -858,6 +870,8 @@ extern "C" void ffhip_batch_destroy(ffhip_batch *b) {
     for (void *p : b->owned) hipFree(p);
     b->res.release();
     if (b->bc_host) hipHostFree(b->bc_host);
+    if (b->rmp_host) hipHostFree(b->rmp_host);
+    if (b->rmp_hlist) hipHostFree(b->rmp_hlist);
     if (b->side) ffhip_batch_destroy(b->side);
     prof_unlink(b);
     if (b->have_ev) {
@@ -1460,6 +1474,75 @@ static int ensure_barcode_buffers(ffhip_batch *b) {
     return FFHIP_OK;
 }
 
+// a device buffer of the batch that grows: the old one is given back first, once the batch's stream has drained (a run that was never finished may still read it)
+static int dgrow(ffhip_batch *b, void **p, size_t *cap, size_t need, const char *what) {
+    if (*p && need <= *cap) return FFHIP_OK;
+    if (*p) {
+        HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
+        b->owned.erase(std::remove(b->owned.begin(), b->owned.end(), *p), b->owned.end());
+        hipFree(*p);
+        b->dev_bytes -= *cap;
+        *p = nullptr; *cap = 0;
+    }
+    if (!(*p = dalloc(b, need, false))) return set_err(FFHIP_ENOMEM, "remap: the %s takes %zu bytes of device memory, which could not be had", what, need);
+    *cap = need;
+    return FFHIP_OK;
+}
+
+// Remap, the front's share: buffers on first use, every read's status, kernel form and place in the workspace, the lists a form each, their upload.
+static_assert(sizeof(RemapRead) == 24, "the reads' list is copied as it stands");
+static int remap_prepare(ffhip_batch *b) {
+    const int nR = b->packed ? b->nvirt : b->nread;
+    if (!b->rmp_set) return set_err(FFHIP_EINVAL, "remap: no sequences are set for the batch (ffhip_batch_set_remap)");
+    if ((int)b->rmp_seq.size() != nR) return set_err(FFHIP_EINVAL, "remap: sequences were set for %zu reads, the batch holds %d", b->rmp_seq.size(), nR);
+    const size_t bytes = b->rmp_bytes();
+    if (!b->rmp_dev && !(b->rmp_dev = (uint8_t *)dalloc(b, bytes, true))) return FFHIP_ENOMEM;
+    if (!b->rmp_dlist && !(b->rmp_dlist = (RemapRead *)dalloc(b, (size_t)b->cap_reads * sizeof(RemapRead), false))) return FFHIP_ENOMEM;
+    if (!b->rmp_host) {
+        if (hipHostMalloc((void **)&b->rmp_host, bytes, hipHostMallocDefault) != hipSuccess) { b->rmp_host = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation failed"); }
+        memset(b->rmp_host, 0, bytes);
+    }
+    if (!b->rmp_hlist && hipHostMalloc((void **)&b->rmp_hlist, (size_t)b->cap_reads * sizeof(RemapRead), hipHostMallocDefault) != hipSuccess) {
+        b->rmp_hlist = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation failed");
+    }
+    std::vector<RemapRead> per[kRemapForms];
+    size_t ws = 0, seq = 0;
+    for (int r = 0; r < nR; r++) {
+        const int N = b->hTb[r], L = (int)b->rmp_seq[r].size();
+        RemapRead rr{ ws, (unsigned)seq, L, b->rmp_state[r], r };
+        int form = 0;
+        if (rr.status == 1 && (N < 1 || L < 1 || L > N + 1)) rr.status = 2;
+        if (rr.status == 1) {
+            form = remap_form(L, b->rmp_band);
+            if (form < 0) return set_err(FFHIP_EINVAL, "remap: read %d's window of min(2 band + 1, L) cells is more than %d", r, remap_max_window());
+            ws += remap_ws_words(form, N);
+        }
+        seq += (size_t)L;
+        per[form].push_back(rr);
+    }
+    if (int rc = dgrow(b, (void **)&b->rmp_ws, &b->rmp_ws_cap, ws * 8, "traceback workspace")) return rc;
+    int at = 0;
+    for (int f = 0; f < kRemapForms; f++) {
+        b->rmp_count[f] = (int)per[f].size();
+        if (!per[f].empty()) memcpy(b->rmp_hlist + at, per[f].data(), per[f].size() * sizeof(RemapRead));
+        at += (int)per[f].size();
+    }
+    if (nR > 0) HIP_TRY(hipMemcpyAsync(b->rmp_dlist, b->rmp_hlist, (size_t)nR * sizeof(RemapRead), hipMemcpyHostToDevice, b->stream), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+static void remap_launch(ffhip_batch *b, int nR, const int *tbr, ReadMap rmap) {
+    int at = 0;
+    for (int f = 0; f < kRemapForms; f++) {
+        if (b->rmp_count[f] > 0) {
+            launch_remap(b->stream, f, b->rmp_dlist + at, b->rmp_count[f], b->rmp_dseq, b->trans, b->mdl->Ps, b->rmp_band, b->rmp_ws, b->rmp_dev,
+                         b->rmp_dev + (size_t)b->cap_reads * 16, b->Tb, tbr, rmap);
+            b->launches[5]++;
+        }
+        at += b->rmp_count[f];
+    }
+    b->rmp_valid = 1;
+}
+
 // ffhip_batch_run_pair can put the layer launches of TWO batches into one grid between their fronts and backs (`paired`).  The front
 // decides the run's path (b->run_path); the layers and the back follow it.
 static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool paired) {
@@ -1489,6 +1572,12 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
         if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "barcodes: a flip-flop model only (the run-length model has no base strings)");
         if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "barcodes need a decoded run (FFHIP_RUN_NO_DECODE is set)");
         if (int rc = ensure_barcode_buffers(b)) return rc;
+    }
+    b->rmp_valid = 0;
+    if (flags & FFHIP_RUN_REMAP) {         // (not a section of the result block either)
+        if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "remap: a flip-flop model only (the run-length model's scores are not transitions between bases)");
+        if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "remap needs a decoded run (FFHIP_RUN_NO_DECODE is set)");
+        if (int rc = remap_prepare(b)) return rc;
     }
     if (b->packed && !p.packable)
         return set_err(FFHIP_EINVAL, "packed batches take the default path and the launch-per-step kernels only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / unfused flags, ordinary temperature)");
@@ -1778,6 +1867,7 @@ static int run_back(ffhip_batch *b) {
                 b->bc_valid = 1;
                 b->launches[5]++;
             }
+            if (flags & FFHIP_RUN_REMAP) remap_launch(b, nR, tbr, rmap);      // from the transitions, whatever the path was decoded from (run_front made the lists)
             if (flags & FFHIP_RUN_MOD_PROBS) {          // from the posterior whatever decoded the path (run_front checked the model)
                 launch_mod_probs(s, b->post, b->path, b->res.on_dev<uint8_t>(RF_ML), nR, Tb, m->Ps, tbr, rmap);
                 b->launches[5]++;
@@ -1802,6 +1892,7 @@ static int run_back(ffhip_batch *b) {
     if (b->packed) {
         HIP_TRY(hipMemcpyAsync(b->res.host, b->res.dev, b->res.copy_bytes(flags), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
         if (b->bc_valid) HIP_TRY(hipMemcpyAsync(b->bc_host, b->bc_dev, (size_t)nR * sizeof(ffhip_barcode_call), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the barcode records' one copy
+        if (b->rmp_valid) HIP_TRY(hipMemcpyAsync(b->rmp_host, b->rmp_dev, b->rmp_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the remap records' and moves' one copy
         b->res_copied = 1;
     }
     HIP_TRY(hipEventRecord(eng->batch_done, s), FFHIP_EHIP); eng->batch_done_rec = 1;
@@ -1853,7 +1944,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
     const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
     b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
     b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0;
+    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0; b->rmp_valid = 0;
     return FFHIP_OK;
 }
 
@@ -1913,6 +2004,7 @@ extern "C" int ffhip_batch_paired(const ffhip_batch *b) { return (b && b->paired
 // have no bound (the reference has none: layers.c:24-33); their results replace the clamped ones in the batch's buffers.  Rare by
 // construction -- a normalised sample in the hundreds -- so this path is written for clarity: a side batch of 16 slots with the
 // same capacity (hence the same strides: a read's results are contiguous device-to-device copies), created on first use.
+static int remap_adopt(ffhip_batch *b, std::vector<std::vector<unsigned short>> &&seq, std::vector<signed char> &&state, int band);
 static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
     const ffhip_model *m = b->mdl;
     if (!b->side) {
@@ -1938,6 +2030,12 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
         sd->ran = sd->finished = 0;
         sd->run_scale = b->run_scale;
         sd->bc_kit = b->bc_kit; sd->bc_max_dist = b->bc_max_dist; sd->bc_min_sep = b->bc_min_sep; sd->bc_both = b->bc_both;      // (last_flags asks the side batch for the records too)
+        if (fl & FFHIP_RUN_REMAP) {                       // ... and for these reads' sequences
+            std::vector<std::vector<unsigned short>> sq(16);
+            std::vector<signed char> st(16, 0);
+            for (int k = 0; k < n; k++) { sq[k] = b->rmp_seq[reads[k0 + k]]; st[k] = b->rmp_state[reads[k0 + k]]; }
+            if (int rc = remap_adopt(sd, std::move(sq), std::move(st), b->rmp_band)) return rc;
+        }
         if (int rc = ffhip_batch_run(sd, b->last_temperature, (fl & ~(unsigned)FFHIP_RUN_KEEP_ACTS) | FFHIP_RUN_F32_RNN)) return rc;
         if (int rc = ffhip_batch_finish(sd)) return rc;
         hipStream_t s = b->stream;
@@ -1964,6 +2062,13 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
                 HIP_TRY(hipMemcpyAsync(b->bc_dev + r, sd->bc_dev + k, sizeof(ffhip_barcode_call), hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
                 b->bc_host[r] = sd->bc_host[k];
             }
+            if (b->rmp_valid && sd->rmp_valid) {        // and its remap record and moves, both halves
+                const size_t mv = (size_t)b->cap_reads * 16 + r1, smv = (size_t)sd->cap_reads * 16 + (size_t)k * L;
+                HIP_TRY(hipMemcpyAsync(b->rmp_dev + r * 16, sd->rmp_dev + (size_t)k * 16, 16, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                HIP_TRY(hipMemcpyAsync(b->rmp_dev + mv, sd->rmp_dev + smv, nb, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                memcpy(b->rmp_host + r * 16, sd->rmp_host + (size_t)k * 16, 16);
+                memcpy(b->rmp_host + mv, sd->rmp_host + smv, nb);
+            }
         }
         HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
     }
@@ -1987,6 +2092,8 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
         HIP_TRY(hipMemcpyAsync(b->res.host, b->res.dev, b->res.copy_bytes(b->last_flags), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
         if (b->bc_valid)                                     // the barcode records' one copy (a packed batch: enqueued in run_back, as the block's)
             HIP_TRY(hipMemcpyAsync(b->bc_host, b->bc_dev, (size_t)batch_nreads(b) * sizeof(ffhip_barcode_call), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
+        if (b->rmp_valid)                                    // the remap records' and moves' one copy (likewise)
+            HIP_TRY(hipMemcpyAsync(b->rmp_host, b->rmp_dev, b->rmp_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
     }
     b->res_copied = 0;
     HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
@@ -2137,6 +2244,54 @@ extern "C" int ffhip_batch_barcode(const ffhip_batch *b, int read, ffhip_barcode
     return FFHIP_OK;
 }
 
+// ---- remap (include/ffhip.h "remap"; the kernel: ffhip_remap.hip)
+static int remap_adopt(ffhip_batch *b, std::vector<std::vector<unsigned short>> &&seq, std::vector<signed char> &&state, int band) {
+    size_t total = 0;
+    for (const auto &q : seq) total += q.size();
+    hipSetDevice(b->eng->device);
+    HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
+    if (int rc = dgrow(b, (void **)&b->rmp_dseq, &b->rmp_dseq_cap, (total ? total : 1) * sizeof(unsigned short), "sequences")) return rc;
+    std::vector<unsigned short> flat;
+    flat.reserve(total);
+    for (const auto &q : seq) flat.insert(flat.end(), q.begin(), q.end());
+    if (total) HIP_TRY(hipMemcpy(b->rmp_dseq, flat.data(), total * sizeof(unsigned short), hipMemcpyHostToDevice), FFHIP_EHIP);
+    b->rmp_seq = std::move(seq); b->rmp_state = std::move(state);
+    b->rmp_band = band; b->rmp_set = 1;
+    return FFHIP_OK;
+}
+extern "C" int ffhip_batch_set_remap(ffhip_batch *b, int nread, const uint8_t *const *codes, const size_t *len, int band) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (!codes) { b->rmp_set = 0; b->rmp_seq.clear(); b->rmp_state.clear(); return FFHIP_OK; }
+    const ffhip_model *m = b->mdl;
+    if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "remap: a flip-flop model only (the run-length model's scores are not transitions between bases)");
+    if (!len || nread != batch_nreads(b)) return set_err(FFHIP_EINVAL, "remap: sequences for %d reads, the batch holds %d", nread, batch_nreads(b));
+    if (band < 0) return set_err(FFHIP_EINVAL, "remap: the band half-width is %d (>= 0)", band);
+    std::vector<std::vector<unsigned short>> seq((size_t)nread);
+    std::vector<signed char> state((size_t)nread, 0);
+    for (int r = 0; r < nread; r++) {
+        if (!codes[r]) continue;
+        if (len[r] > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "remap: read %d's sequence has %zu bases", r, len[r]);
+        state[r] = len[r] ? 1 : 2;
+        for (size_t i = 0; i < len[r]; i++) if (codes[r][i] >= m->nbase) return set_err(FFHIP_EINVAL, "remap: read %d, position %zu: code %d is not a base of the model (0 .. %d)", r, i, (int)codes[r][i], m->nbase - 1);
+        if (remap_form((int)len[r], band) < 0 && len[r]) return set_err(FFHIP_EINVAL, "remap: read %d's window of min(2 band + 1, L) cells is more than %d", r, remap_max_window());
+        seq[r].resize(len[r]);
+        remap_code(codes[r], len[r], m->nbase, seq[r].data());
+    }
+    return remap_adopt(b, std::move(seq), std::move(state), band);
+}
+extern "C" int ffhip_batch_remap(const ffhip_batch *b, int read, ffhip_remap_call *out) {
+    if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
+    if (!b->rmp_valid || !b->rmp_host) return set_err(FFHIP_EINVAL, "remap records were not made in this run (FFHIP_RUN_REMAP)");
+    int rec[4];
+    memcpy(rec, b->rmp_host + (size_t)read * 16, 16);
+    out->status = rec[0]; out->L = (size_t)rec[1];
+    memcpy(&out->score, &rec[2], 4);
+    out->nblock = (size_t)b->hTb[read];
+    out->rm = rec[0] == 1 ? b->rmp_host + (size_t)b->cap_reads * 16 + read_row1(b, read) : nullptr;
+    if (rec[0] == 1 && rec[3] != 0) return set_err(FFHIP_EHIP, "remap: read %d's traceback ended at position %d, not 0", read, rec[3]);
+    return FFHIP_OK;
+}
+
 static int d2h(ffhip_batch *b, void *dst, const void *src, size_t bytes) {
     hipSetDevice(b->eng->device);
     HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
@@ -2265,6 +2420,7 @@ extern "C" int ffhip_debug_batch_head_input(ffhip_batch *b, int row, float *out)
 }
 
 extern "C" int ffhip_debug_fallback_count(const ffhip_engine *eng) { return eng ? eng->fallbacks : -1; }
+extern "C" int ffhip_debug_remap_form(size_t L, int band) { return (L < 1 || L > ((size_t)1 << 30) || band < 0) ? -1 : remap_form((int)L, band); }
 extern "C" size_t ffhip_debug_batch_device_bytes(const ffhip_batch *b) { return b ? b->dev_bytes + b->res.cap : 0; }
 extern "C" int ffhip_debug_split_plan(int kind, int hidden, int remaining, int ncu, int beside, int out[6]) {
     if (!out) return set_err(FFHIP_EINVAL, "ffhip_debug_split_plan: out is NULL");

@@ -6,6 +6,13 @@
 #include <stddef.h>
 #include <stdint.h>
 
+// Head and decode kernels (remap and barcodes among them) run beside the NEXT batch's convolutions (run_front in ffhip_engine.hip, FFHIP_DEBUG=front_order=...) and the
+// next layer launches wait for them: their waves go first on a shared SIMD (the convolutions stay at priority 0)
+#ifndef FFHIP_DECODE_PRIO
+#define FFHIP_DECODE_PRIO 2
+#endif
+#define FFHIP_DECODE_PRIO_SET() __builtin_amdgcn_s_setprio(FFHIP_DECODE_PRIO)
+
 namespace ffhip {
 
 // Development switches live in ONE environment variable: FFHIP_DEBUG=token[,token=value ...] (INTEGRATION.md section 6 lists them).
@@ -220,6 +227,22 @@ struct BarcodeKit {
 };
 void launch_barcodes(hipStream_t s, BarcodeKit kit, const char *bases, const int *lens, void *records, int nread, int Tb, const int *tbs, ReadMap map,
                      int max_dist, int min_sep, int both_ends, int *dist_out = nullptr, int *end_out = nullptr);
+// signal-to-sequence mapping (k_remap, ffhip_remap.hip; include/ffhip.h "remap"): per listed read one 16-byte record { status, L, score bits, end } at rec[read] and,
+// for a mapped one, N bytes of 0 / 1 at the read's row of the (Tb + 1)-entry byte buffer `rm`.  A form is one instantiation of the kernel (0, 1: one wave; 2, 3: a
+// workgroup): remap_form gives the smallest that holds a window of min(2 band + 1, L) cells, -1 when none does; a launch takes the reads of ONE form.
+struct RemapRead {
+    unsigned long long ws;              // the read's first 64-bit word in the traceback workspace (remap_ws_words(form, N) of them)
+    unsigned seq;                       // its first entry in the coded sequences
+    int L, status, read;                // bases; 0 no sequence, 1 to be mapped, 2 refused; the read's index in the batch
+};
+constexpr int kRemapForms = 4;
+int remap_form(int L, int band);
+int remap_max_window();
+size_t remap_ws_words(int form, int nblock);
+// the entries of a block's score row that position i of a sequence of codes 0 .. nbase - 1 reads: stay | move << 8 (host; the flip-flop coding of include/ffhip.h)
+void remap_code(const uint8_t *codes, size_t L, int nbase, unsigned short *out);
+void launch_remap(hipStream_t s, int form, const RemapRead *list, int count, const unsigned short *seq, const float *trans, int Ps, int band,
+                  unsigned long long *ws, void *records, uint8_t *rm, int Tb, const int *tbs, ReadMap map);
 // exp + trace_from_posterior
 void launch_trace(hipStream_t s, const float *post, int32_t *trace, int nread, int Tb, int nbase, int Ps, int is_log, const int *tbs = nullptr, ReadMap map = ReadMap());
 void launch_exp_inplace(hipStream_t s, float *x, size_t n);

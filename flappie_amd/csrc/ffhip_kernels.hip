@@ -19,13 +19,6 @@
 #include "ffhip_math.hpp"
 #include <stdlib.h>
 
-// Head and decode kernels run beside the NEXT batch's convolutions (run_front in ffhip_engine.hip, FFHIP_DEBUG=front_order=...) and the next layer launches wait for them:
-// their waves go first on a shared SIMD (the convolutions stay at priority 0)
-#ifndef FFHIP_DECODE_PRIO
-#define FFHIP_DECODE_PRIO 2
-#endif
-#define FFHIP_DECODE_PRIO_SET() __builtin_amdgcn_s_setprio(FFHIP_DECODE_PRIO)
-
 namespace ffhip {
 
 typedef float v4f __attribute__((ext_vector_type(4)));

@@ -673,6 +673,40 @@ extern "C" int ffhip_op_barcode_scores(ffhip_engine *eng, const ffhip_barcodes *
     return FFHIP_OK;
 }
 
+// one matrix of transition scores mapped to one sequence (k_remap; include/ffhip.h "remap")
+extern "C" int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, int band, uint8_t *rm, float *score) {
+    OP_ENTER(eng);
+    if (!view_ok(trans) || !codes || !rm || !score || nbase < 1 || 2 * nbase > kMaxState || trans.nr != (size_t)(2 * nbase * (nbase + 1)) || trans.stride % 4 != 0 || trans.stride > 2048 ||
+        trans.nc > (size_t)1 << 30)
+        return set_err(FFHIP_EINVAL, "bad remap arguments (scores of 2 nbase (nbase + 1) rows, a sequence, outputs of nblock bytes and one float)");
+    const size_t N = trans.nc;
+    if (band < 0) return set_err(FFHIP_EINVAL, "remap: the band half-width is %d (>= 0)", band);
+    if (L < 1 || L > N + 1) return set_err(FFHIP_EINVAL, "remap: a sequence of %zu bases has no path through %zu blocks (1 <= L <= nblock + 1)", L, N);
+    for (size_t i = 0; i < L; i++) if (codes[i] >= nbase) return set_err(FFHIP_EINVAL, "remap: position %zu: code %d is not a base (0 .. %d)", i, (int)codes[i], nbase - 1);
+    const int form = remap_form((int)L, band);
+    if (form < 0) return set_err(FFHIP_EINVAL, "remap: the window of min(2 band + 1, L) cells is more than %d", remap_max_window());
+    std::vector<unsigned short> coded(L);
+    remap_code(codes, L, nbase, coded.data());
+    const RemapRead rr{ 0ull, 0u, (int)L, 1, 0 };
+    float *d_t = upload_img(tmp, trans, s);
+    unsigned short *d_seq = (unsigned short *)tmp.upload(coded.data(), L * sizeof(unsigned short), s);
+    RemapRead *d_list = (RemapRead *)tmp.upload(&rr, sizeof rr, s);
+    const size_t ws_bytes = remap_ws_words(form, (int)N) * 8;
+    unsigned long long *d_ws = (unsigned long long *)tmp.get(ws_bytes);
+    uint8_t *d_rm = (uint8_t *)tmp.get(N + 1);
+    void *d_rec = tmp.get(16);
+    if (!d_ws) return set_err(FFHIP_ENOMEM, "remap: the traceback workspace takes %zu bytes of device memory, which could not be had", ws_bytes);
+    if (!d_t || !d_seq || !d_list || !d_rm || !d_rec) OP_NOMEM();
+    launch_remap(s, form, d_list, 1, d_seq, d_t, (int)trans.stride, band, d_ws, d_rec, d_rm, (int)N, nullptr, ReadMap());
+    int rec[4];
+    HIP_TRY(hipMemcpyAsync(rec, d_rec, 16, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipMemcpyAsync(rm, d_rm, N, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    if (rec[0] != 1 || rec[3] != 0) return set_err(FFHIP_EHIP, "remap: status %d, traceback ended at position %d", rec[0], rec[3]);
+    memcpy(score, &rec[2], 4);
+    return FFHIP_OK;
+}
+
 // ---- decoders of the first run-length head (decode.c:552-892): param is [4 nbase x nblock]
 static bool rl1_dims(const ffhip_mat &param, int *nbase) {
     if (!view_ok(param) || param.nr % 4 != 0 || param.nr / 4 < 1 || param.nr / 4 > 8) return false;

@@ -40,6 +40,7 @@
 #include "../../include/flappie_modbase.h"
 #include "../../include/flappie_moves.h"
 #include "../../include/flappie_barcodes.h"
+#include "../../include/flappie_remap.h"
 #include "../../include/networks.h"
 
 const char *argp_program_version = "flappie (MI355X/HIP) 0.1, interface of flappie 2.1.3";
@@ -93,9 +94,13 @@ static struct argp_option options[] = {
     {"barcode-min-sep", 28, "edits", 0, "With --barcodes: least distance between the best barcode and the runner-up (default 3)"},
     {"barcode-both-ends", 29, 0, 0, "With --barcodes: a barcode must be found at both ends (its score is the larger of its two distances)"},
     {"trim-barcodes", 30, 0, 0, "With --barcodes: cut the barcode and what precedes it from SEQ and QUAL of classified reads, at each end where it was found (not with --emit-moves, --modbase-tags or --trace)"},
+    {"remap", 31, "refs.fa", 0, "Map each read's signal to a sequence you already know: the records of a FASTA file, found by read id, then by the file's base name, in SIGNAL order (reverse them yourself for --reverse and RNA). The best path of the read's transition scores through its sequence is made on the GPU and written to --remap-out; stdout does not change"},
+    {"remap-out", 256, "map.tsv", 0, "With --remap: one line per read that had a record: name, status (1 mapped, 2 not: a letter outside the model's alphabet, or more bases than blocks + 1), nblock, stride, trim_start, L, band, maxdev, score and the block every base starts at"},
+    {"remap-band", 257, "W", 0, "With --remap: the band's half-width in sequence positions around the straight line from (0, 0) to (nblock, L - 1) (0-2303, default 2048: the GPU holds a window of at most 2 W + 1 <= 4608 positions; maxdev = W in map.tsv says the band was touched)"},
 #endif
 #ifdef BUILD_RUNNIE
     {"barcodes", 25, "kit.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"remap", 31, "refs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
 #endif
     {0}
 };
@@ -135,8 +140,11 @@ static struct {
     char *barcodes;                     /* flappie: --barcodes kit file; window, max_dist, min_sep (-1: the defaults), both ends, trim */
     int bc_window, bc_max_dist, bc_min_sep;
     bool bc_both, bc_trim, bc_opts;     /* bc_opts: one of the other barcode options was given */
+    char *remap, *remap_out;            /* flappie: --remap refs file, --remap-out table; the band's half-width */
+    int remap_band;
+    bool remap_band_set;
 } args = { 1, 200, 0.0f, NULL, FLAPPIE_OUTFORMAT_FASTQ, 0, DEFAULT_MODEL, NULL, "", false, 1.0f, 200, 10, 100, 0.0f, false, NULL, true, 0, 4, 0, 0, false, false, false, false,
-           { 1.02, 1.04, 1.04, 1.02 }, false, false, NULL, 150, -1, -1, false, false, false };      /* batch 0: by model (below); nshard 0: --shard not given */
+           { 1.02, 1.04, 1.04, 1.02 }, false, false, NULL, 150, -1, -1, false, false, false, NULL, NULL, 2048, false };      /* batch 0: by model (below); nshard 0: --shard not given */
 
 static void print_models(FILE *fh) {
     for (int mdl = 0; mdl < (int)flappie_nmodel; mdl++)
@@ -247,6 +255,17 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
     case 24: args.emit_moves = true; break;
 #endif
     case 25: args.barcodes = arg; break;
+    case 31: args.remap = arg; break;
+#ifndef BUILD_RUNNIE
+    case 256: args.remap_out = arg; break;      /* (keys above UCHAR_MAX: argp makes a short option of a printable one) */
+    case 257: {
+        char *end = NULL;
+        const long w = strtol(arg, &end, 10);
+        if (end == arg || *end != '\0' || w < 0 || w > FLAPPIE_REMAP_BAND_MAX) errx(EXIT_FAILURE, "--remap-band must be a whole number from 0 to %d", FLAPPIE_REMAP_BAND_MAX);
+        args.remap_band = (int)w; args.remap_band_set = true;
+        break;
+    }
+#endif
 #ifndef BUILD_RUNNIE
     case 26:
         args.bc_window = atoi(arg); args.bc_opts = true;
@@ -403,6 +422,11 @@ typedef struct {
     float sm, sd;                       /* ... the median and MAD the read was normalised with */
     ffhip_barcode_call bc;              /* --barcodes: the read's record */
     int have_bc;
+    int rm_ref;                         /* --remap: the read's record of the sequences (-1: none), and what the batch returned for it */
+    int have_rm, rm_status;
+    size_t rm_L, rm_nblock;
+    float rm_score;
+    uint8_t *rm;                        /* ... its moves (owned; NULL unless mapped) */
     int rle_nocall;                     /* runnie --fasta: no runs, or a failed run-length estimate (decode_runnie.py: "No basecall returned") */
     /* a read of a MULTI-READ file: its samples as the file holds them (owned; res.rt.raw stays NULL, res.rt.n counts them) and its calibration -- the
      * preparation scales them on the device (ffhip_prep_begin_dac) */
@@ -473,10 +497,14 @@ typedef struct { ffhip_batch *b; int cached, n, *idx; item **its; const ffhip_pr
 static flappie_barcode_kit *bc_kit = NULL;
 static ffhip_barcodes *bc_dev = NULL;
 static unsigned long long bc_count[FLAPPIE_BARCODE_MAX_KIT + 1];
+/* flappie --remap: the sequences, the table, and the summary's counts: mapped, no record, refused, mapped with maxdev = band */
+static flappie_remap_refs *rm_refs = NULL;
+static FILE *rm_out = NULL;
+static unsigned long long rm_count[4];
 #ifdef BUILD_RUNNIE
 /* --fasta: the runs and their run-length estimates come from the device (FFHIP_RUN_RLE_RUNS) with the batch's scale factors */
 static unsigned run_flags(void) { return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.fasta ? FFHIP_RUN_RLE_RUNS : 0u); }
-static int batch_run(ffhip_batch *b, unsigned flags) {
+static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
     if (args.fasta) { const int rc = ffhip_batch_set_run_scale(b, args.run_scale); if (rc) return rc; }
     return ffhip_batch_run(b, args.temperature, flags);
 }
@@ -485,10 +513,30 @@ static int batch_run(ffhip_batch *b, unsigned flags) {
  * --barcodes: the reads' barcode records do (FFHIP_RUN_BARCODES) */
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u) |
-           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u);
+           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u);
 }
-static int batch_run(ffhip_batch *b, unsigned flags) {
+/* --remap: every read's record, by its read id, then by its file's base name; a bad record goes as a sequence of no bases (status 2) */
+static int batch_set_remap(ffhip_batch *b, item **its, int n) {
+    const int nb = ffhip_batch_nreads(b);
+    const uint8_t **codes = calloc(nb > 0 ? nb : 1, sizeof(uint8_t *));
+    size_t *len = calloc(nb > 0 ? nb : 1, sizeof(size_t));
+    static const uint8_t none = 0;
+    int rc = (codes && len) ? 0 : -1;
+    for (int i = 0; 0 == rc && i < n && i < nb; i++) {
+        const int k = its[i]->rm_ref = flappie_remap_refs_find(rm_refs, its[i]->res.rt.uuid, its[i]->filename);
+        if (k < 0) continue;
+        const int bad = rm_refs->bad[k] || 0 == rm_refs->len[k];
+        codes[i] = bad ? &none : rm_refs->codes[k];
+        len[i] = bad ? 0 : rm_refs->len[k];
+    }
+    if (0 == rc) rc = ffhip_batch_set_remap(b, nb, codes, len, args.remap_band);
+    free(codes);
+    free(len);
+    return rc;
+}
+static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
     if (bc_dev) { const int rc = ffhip_batch_set_barcodes(b, bc_dev, args.bc_max_dist, args.bc_min_sep, args.bc_both); if (rc) return rc; }
+    if (rm_refs) { const int rc = batch_set_remap(b, its, n); if (rc) return rc; }
     return ffhip_batch_run(b, args.temperature, flags);
 }
 #endif
@@ -533,7 +581,7 @@ static pending_batch submit_packed(struct ffhip_engine *eng, const struct ffhip_
     int rc_sub = (NULL == pb.b) ? -1 : ffhip_batch_set_prepared_packed(pb.b, prep, n, pb.idx, slot_of, off_of);
     t_phase[6] += now_s() - t0;
     const double t1 = now_s();
-    if (0 == rc_sub) rc_sub = batch_run(pb.b, flags);
+    if (0 == rc_sub) rc_sub = batch_run(pb.b, flags, pb.its, n);
     t_phase[7] += now_s() - t1;
     if (0 != rc_sub) { warnx("%s", ffhip_last_error()); pb.b = NULL; }
     t_phase[3] += now_s() - t0;
@@ -567,7 +615,7 @@ static pending_batch submit_batch(struct ffhip_engine *eng, const struct ffhip_m
     int rc_sub = (NULL == pb.b) ? -1 : ffhip_batch_set_prepared(pb.b, prep, pb.idx);
     t_phase[6] += now_s() - t0;
     const double t1 = now_s();
-    if (0 == rc_sub) rc_sub = batch_run(pb.b, flags);
+    if (0 == rc_sub) rc_sub = batch_run(pb.b, flags, pb.its, n);
     t_phase[7] += now_s() - t1;
     if (0 != rc_sub) {
         warnx("%s", ffhip_last_error());
@@ -597,7 +645,7 @@ static void call_one_read_a_row(const struct ffhip_model *mdl, const pending_bat
             for (int k = 0; k < g; k++) one.idx[k] = its[i + k]->prepared;
             one.b = ffhip_batch_create(flappie_hip_engine(), mdl, g, longest);
             int rc = (NULL == one.b) ? -1 : ffhip_batch_set_prepared(one.b, failed->prep, one.idx);
-            if (0 == rc) rc = batch_run(one.b, run_flags());
+            if (0 == rc) rc = batch_run(one.b, run_flags(), one.its, g);
             if (0 != rc) { warnx("%s", ffhip_last_error()); if (one.b) ffhip_batch_destroy(one.b); one.b = NULL; }
         }
         collect_batch(mdl, &one);                      /* (a failure there counts the group's reads as not called) */
@@ -750,6 +798,15 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
         if (bc_dev) {                                          /* the record describes the call in signal order whatever --reverse does to the strings */
             if (0 != ffhip_batch_barcode(b, i, &its[i]->bc) || its[i]->bc.best >= bc_kit->n) warnx("%s", ffhip_last_error());
             else { its[i]->have_bc = 1; bc_count[its[i]->bc.best >= 0 ? its[i]->bc.best : bc_kit->n]++; }
+        }
+        if (rm_refs && its[i]->rm_ref >= 0) {                  /* the read's mapping to its sequence: the table's line is written with the read's record */
+            ffhip_remap_call rc;
+            if (0 != ffhip_batch_remap(b, i, &rc)) warnx("%s", ffhip_last_error());
+            else {
+                its[i]->have_rm = 1; its[i]->rm_status = rc.status; its[i]->rm_L = rc.L; its[i]->rm_nblock = rc.nblock; its[i]->rm_score = rc.score;
+                if (1 == rc.status && NULL != (its[i]->rm = malloc(rc.nblock ? rc.nblock : 1))) memcpy(its[i]->rm, rc.rm, rc.nblock);
+                its[i]->mv_stride = (int)ffhip_model_stride(mdl);
+            }
         }
         if (args.reverse) {                                    /* flappie.c:294-297 */
             reverse_char_array(r->basecall, blen);
@@ -928,6 +985,17 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
             } else {
                 fprintf_format(args.outformat, args.output, uuid, base, args.uuid, args.prefix, it->res);
             }
+            if (rm_refs) {                                     /* stdout above is what it is without --remap; the table gets the read's line */
+                if (it->rm_ref < 0) rm_count[1]++;
+                else if (!it->have_rm) warnx("No mapping returned for %s", it->filename);
+                else {
+                    const size_t L = rm_refs->bad[it->rm_ref] ? 0 : rm_refs->len[it->rm_ref];
+                    const long dev = flappie_remap_write_line(rm_out, rm_refs->name[it->rm_ref], it->rm_status, it->rm_nblock, it->mv_stride, it->res.rt.start, L,
+                                                              args.remap_band, it->rm, it->rm_score);
+                    if (dev < 0) warnx("The moves of %s do not fit its sequence", it->filename);
+                    if (1 == it->rm_status) { rm_count[0]++; if (dev == (long)args.remap_band) rm_count[3]++; } else rm_count[2]++;
+                }
+            }
             if (hdf5out >= 0) {
                 pthread_mutex_lock(&hdf5_lock);
                 if (packs && packs[i]) summary_pack_write(hdf5out, args.uuid ? uuid : base, packs[i]);
@@ -945,6 +1013,10 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
         free(it->mv);
         it->mv = NULL;
         it->have_bc = 0;
+        free(it->rm);
+        it->rm = NULL;
+        it->have_rm = 0;
+        it->rm_ref = -1;
         free_raw_basecall_info(&it->res);
         free(it->filename);
     }
@@ -1449,6 +1521,7 @@ static void reader_lost(size_t f, const char *path) {
 static void item_init(item *it, const char *path) {
     memset(it, 0, sizeof(*it));
     it->filename = strdup(path);
+    it->rm_ref = -1;
 }
 static void item_from_dac(item *it, const char *path, const fast5_dac_read *dr) {
     item_init(it, path);
@@ -1646,6 +1719,7 @@ int main(int argc, char *argv[]) {
 #ifdef BUILD_RUNNIE
     if ((args.rlc || args.run_scale_set) && !args.fasta) errx(EXIT_FAILURE, "--rlc and --run-scale go with --fasta");
     if (args.barcodes) errx(EXIT_FAILURE, "--barcodes is flappie's: the run-length model's records carry no base strings to search");
+    if (args.remap) errx(EXIT_FAILURE, "--remap is flappie's: the run-length model's scores are not transitions between the bases of a sequence");
 #else
     /* --barcodes: every refusal before any file or the GPU is touched */
     if (args.bc_opts && NULL == args.barcodes) errx(EXIT_FAILURE, "--barcode-window, --barcode-max-dist, --barcode-min-sep, --barcode-both-ends and --trim-barcodes go with --barcodes");
@@ -1655,6 +1729,17 @@ int main(int argc, char *argv[]) {
         char why[256];
         bc_kit = flappie_barcode_kit_read(args.barcodes, why, sizeof why);
         if (NULL == bc_kit) errx(EXIT_FAILURE, "--barcodes %s: %s", args.barcodes, why);
+    }
+    /* --remap: likewise */
+    if ((NULL == args.remap) != (NULL == args.remap_out)) errx(EXIT_FAILURE, "--remap and --remap-out go together");
+    if (args.remap_band_set && NULL == args.remap) errx(EXIT_FAILURE, "--remap-band goes with --remap");
+    if (args.remap) {
+        char why[256];
+        rm_refs = flappie_remap_refs_read(args.remap, flappie_model_has_modbase(args.model) ? "ACGTZ" : "ACGT", why, sizeof why);
+        if (NULL == rm_refs) errx(EXIT_FAILURE, "--remap %s: %s", args.remap, why);
+        for (int k = 0; k < rm_refs->n; k++)
+            if (rm_refs->bad[k]) warnx("--remap: record %s holds a letter outside the model's alphabet: its read is not mapped (status 2)", rm_refs->name[k]);
+        if (NULL == (rm_out = fopen(args.remap_out, "w"))) errx(EXIT_FAILURE, "--remap-out %s: cannot be written", args.remap_out);
     }
     if (args.modbase_tags && !flappie_model_has_modbase(args.model))      /* (the registry knows: before any file or the GPU is touched) */
         errx(EXIT_FAILURE, "--modbase-tags needs a model with a modified base (r941_5mC); \"%s\" has none", flappie_model_string(args.model));
@@ -1752,6 +1837,11 @@ int main(int argc, char *argv[]) {
         fprintf(stderr, "barcode\tunclassified\t%llu\n", bc_count[bc_kit->n]);
         ffhip_barcodes_free(bc_dev);
         flappie_barcode_kit_free(bc_kit);
+    }
+    if (rm_refs) {                     /* mapped, no record, refused, and the mapped reads whose path touched the band */
+        fprintf(stderr, "remap\tmapped\t%llu\nremap\tno_record\t%llu\nremap\trefused\t%llu\nremap\tband_touched\t%llu\n", rm_count[0], rm_count[1], rm_count[2], rm_count[3]);
+        if (0 != fclose(rm_out)) warnx("--remap-out %s: write failed", args.remap_out);
+        flappie_remap_refs_free(rm_refs);
     }
 #endif
     flappie_hip_shutdown();

@@ -101,6 +101,11 @@ typedef struct {
  * (reads x 16 bytes) and come down in ONE extra copy, enqueued where the result block's copy is.  Everything else the run returns is that of the same run without the
  * flag.  No kit attached, the run-length model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
 #define FFHIP_RUN_BARCODES   16384u
+/* Signal-to-sequence mapping of a flip-flop model's reads (ffhip_batch_remap below, "remap"): the best path of each read's transition scores through a sequence the
+ * caller gave with ffhip_batch_set_remap, made on the device (k_remap) in the launch sequence of the decode.  Records and moves are NOT part of the result block:
+ * they live in ONE buffer of their own (reads x 16 bytes, then a byte a block) and come down in ONE extra copy, enqueued where the result block's copy is.
+ * Everything else the run returns is that of the same run without the flag.  No sequences set, the run-length model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
+#define FFHIP_RUN_REMAP      32768u
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -399,6 +404,36 @@ void ffhip_barcodes_free(ffhip_barcodes *kit);
 int ffhip_batch_set_barcodes(ffhip_batch *b, const ffhip_barcodes *kit, int max_dist, int min_sep, int both_ends);
 int ffhip_batch_barcode(const ffhip_batch *b, int read, ffhip_barcode_call *out);
 int ffhip_op_barcode_scores(ffhip_engine *eng, const ffhip_barcodes *kit, const char *bases, size_t len, int32_t *dist /*[2][n]*/, int32_t *end /*[2][n]*/);
+/* Remap: the signal of a read mapped to a sequence the caller knows.
+ *   Read: N >= 1 blocks with transition scores T[b][.], b = 0 .. N - 1, nparam = nstate (nbase + 1) floats a block -- exactly what ffhip_batch_get_transitions
+ *     returns for that run.  Sequence: s of L bases as codes 0 .. nbase - 1 (the model's alphabet, ACGT or ACGTZ), in SIGNAL order (--reverse, RNA: the caller's business).
+ *   Flip-flop coding: q_0 = s_0; q_i = s_i if s_i != s_{i-1}; otherwise q_i = s_i + nbase if q_{i-1} < nbase, else s_i.
+ *   Path: p_0 .. p_N with p_0 = 0, p_N = L - 1, p_{b+1} - p_b in {0, 1}; it needs 1 <= L <= N + 1.  Its score is
+ *     sum_b T[b][trans_lookup(q_{p_b}, q_{p_{b+1}}, nbase)] (decode.c:104-114: to < nbase ? to nstate + from : nbase nstate + from); a stay is from = to.
+ *   Band: c(b) = floor(b (L - 1) / N) in 64-bit integers, b = 0 .. N; cell (b, i) is allowed iff 0 <= i <= L - 1 and |i - c(b)| <= W, W >= 0 the band half-width.
+ *     The centre line is itself a path, so every W has a solution; W >= L - 1 excludes nothing.
+ *   Recursion, in float32: V_0[0] = 0, V_0[i > 0] = -inf.  For an allowed cell (b + 1, i): stay = V_b[i] + T[b][idx(q_i, q_i)], move = V_b[i-1] + T[b][idx(q_{i-1}, q_i)],
+ *     a term being -inf where its source cell is not allowed or i = 0; V_{b+1}[i] = move if move > stay STRICTLY, else stay, and the cell's bit records which won.
+ *     Each sum is one rounded add: no fused multiply-add, no re-association, no other arithmetic.  score = V_N[L - 1]; the traceback from (N, L - 1) follows the bits.
+ *   Output per read: the score; rm[b] = p_{b+1} - p_b, b = 0 .. N - 1 (N bytes of 0 / 1 whose sum is L - 1); status 0 no sequence given, 1 mapped,
+ *     2 not mapped (L > N + 1 or L = 0).
+ *   What a caller derives: base i starts at block start[0] = 0, start[i] = 1 + (index of the i-th one); maxdev = max_b |p_b - c(b)| says whether the band was
+ *     touched; block b stands for samples [trim_start + b stride, ...) as for ffhip_batch_moves.
+ * ffhip_batch_set_remap: the sequences (copied, and coded, at the call) and the band of the batch's later runs with FFHIP_RUN_REMAP; nread = the batch's reads
+ *   (ffhip_batch_nreads, so after the reads of a ragged or packed batch are set); codes[r] == NULL: read r has no sequence (status 0); len[r] == 0: status 2.  A code
+ *   >= nbase, band < 0, the run-length model, or a read whose window min(2 band + 1, L) is more than 4608 cells (what the widest kernel form holds): FFHIP_EINVAL.
+ *   codes == NULL detaches.  Not between a run and its finish.
+ * ffhip_batch_remap: after ffhip_batch_finish of a run with the flag; rm points into the batch (nblock bytes, valid until the next run), NULL unless status is 1.
+ * ffhip_op_remap: the kernel on ONE matrix of scores (nstate (nbase + 1) rows, a column a block) and one sequence; rm: caller-owned, nblock bytes.  L = 0 or
+ *   L > nblock + 1, a code >= nbase, band < 0: FFHIP_EINVAL.
+ * The traceback workspace (a bit a cell of the window and block, in 64-bit words) is grown by the first run that needs it, sized from the batch's reads and the band,
+ * freed with the batch and counted by ffhip_debug_batch_device_bytes; when it cannot be had: FFHIP_ENOMEM with the bytes in the text. */
+typedef struct { int status; size_t L; float score; const uint8_t *rm; size_t nblock; } ffhip_remap_call;
+int ffhip_batch_set_remap(ffhip_batch *b, int nread, const uint8_t *const *codes, const size_t *len, int band);
+int ffhip_batch_remap(const ffhip_batch *b, int read, ffhip_remap_call *out);
+int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, int band, uint8_t *rm /* nblock */, float *score);
+/* the kernel form a sequence of L bases takes at this band: 0, 1 one wave (windows up to 64, 256 cells), 2, 3 a workgroup (up to 1024, 4608 cells); -1: none */
+int ffhip_debug_remap_form(size_t L, int band);
 int ffhip_runlength_viterbi(ffhip_engine *eng, ffhip_mat param, int *path /* nblock */, float *score);
 /* decoders of the first-generation head on [4 nbase x nblock] matrices: decode_runlength (decode.c:694-767), posterior_runlength
  * (decode.c:793-892; post is [4 nbase x nblock + 1]), runlengths_mean (decode.c:576-603) */
