@@ -33,6 +33,9 @@ RUN_MOD_PROBS = 4096      # 5-base model: 5mC probabilities (SAM ML bytes) of th
 RUN_MOVES = 8192          # flip-flop model: the move table (one byte a block, 1 where a base is emitted) made on the device (Batch.moves)
 RUN_BARCODES = 16384      # flip-flop model: one barcode record a read made on the device against the kit of Batch.set_barcodes (Batch.barcode)
 RUN_REMAP = 32768         # flip-flop model: each read's signal mapped to the sequence of Batch.set_remap on the device (Batch.remap)
+RUN_TRUTH = 65536         # flip-flop model: each read's call aligned to the truth of Batch.set_truth on the device (Batch.truth)
+TRUTH_BAND_MAX = 1279     # the widest kernel form holds a window of 2 W + 1 <= 2560 cells
+TRUTH_FIELDS = ("status", "n", "m", "dist", "n_match", "n_mismatch", "n_ins", "n_del", "maxdev")
 # ffhip_debug_gate_math forms (include/ffhip.h)
 GATE_FORMS = ("logistic_ref", "tanh_ref", "logistic_ref4_lean", "logistic_ref2_lean", "logistic_ref_lean", "tanh_ref_lean",
               "swish_act4", "tanh_act4", "logistic_hw1", "tanh_hw1", "logistic_hw2", "tanh_hw2")
@@ -84,6 +87,12 @@ class CBarcodeCall(C.Structure):
 class CRemapCall(C.Structure):
     """ffhip_remap_call (include/ffhip.h)"""
     _fields_ = [("status", C.c_int), ("L", C.c_size_t), ("score", C.c_float), ("rm", C.POINTER(C.c_uint8)), ("nblock", C.c_size_t)]
+
+
+class CTruthCall(C.Structure):
+    """ffhip_truth_call (include/ffhip.h)"""
+    _fields_ = [("status", C.c_int), ("n", C.c_size_t), ("m", C.c_size_t), ("dist", C.c_int), ("n_match", C.c_int), ("n_mismatch", C.c_int), ("n_ins", C.c_int),
+                ("n_del", C.c_int), ("maxdev", C.c_int), ("nops", C.c_size_t), ("ops", C.POINTER(C.c_uint8))]
 
 
 class CRawTable(C.Structure):
@@ -214,6 +223,10 @@ def lib():
     L.ffhip_batch_remap.argtypes = [vp, C.c_int, C.POINTER(CRemapCall)]
     L.ffhip_op_remap.argtypes = [vp, CFMat, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_float)]
     L.ffhip_debug_remap_form.argtypes = [C.c_size_t, C.c_int]
+    L.ffhip_batch_set_truth.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t), C.c_int]
+    L.ffhip_batch_truth.argtypes = [vp, C.c_int, C.POINTER(CTruthCall)]
+    L.ffhip_op_truth.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.POINTER(CTruthCall), C.POINTER(C.c_uint8)]
+    L.ffhip_debug_truth_form.argtypes = [C.c_size_t]
     _LIB = L
     return L
 
@@ -597,6 +610,28 @@ class Batch:
         rm = np.ctypeslib.as_array(c.rm, shape=(c.nblock,)).copy() if c.status == 1 and c.nblock else None
         return {"status": int(c.status), "L": int(c.L), "score": np.float32(c.score), "rm": rm, "nblock": int(c.nblock)}
 
+    def set_truth(self, seqs, band: int = 512):
+        """the truths and band of later runs with RUN_TRUTH (ffhip_batch_set_truth): one entry a read, None (no truth) or codes 0 .. nbase - 1 in signal order; seqs None detaches"""
+        if seqs is None:
+            _check(lib().ffhip_batch_set_truth(self.h, 0, None, None, int(band)))
+            return
+        n = len(seqs)
+        arrs = [None if q is None else np.ascontiguousarray(q, dtype=np.uint8) for q in seqs]
+        ptrs = (C.POINTER(C.c_uint8) * max(1, n))()
+        lens = (C.c_size_t * max(1, n))()
+        dummy = np.zeros(1, np.uint8)
+        for r, a in enumerate(arrs):
+            if a is not None:
+                ptrs[r] = (a if a.size else dummy).ctypes.data_as(C.POINTER(C.c_uint8))
+                lens[r] = a.size
+        _check(lib().ffhip_batch_set_truth(self.h, n, ptrs, lens, int(band)))
+
+    def truth(self, read: int) -> dict:
+        """truth record of a run with RUN_TRUTH (ffhip_batch_truth): TRUTH_FIELDS as ints and ops (uint8 [dist + n_match] in path order, None unless status is 1)"""
+        c = CTruthCall()
+        _check(lib().ffhip_batch_truth(self.h, read, C.byref(c)))
+        return _truth_dict(c, np.ctypeslib.as_array(c.ops, shape=(c.nops,)).copy() if c.status == 1 and c.nops else None)
+
     def transitions(self, read: int) -> np.ndarray:
         out = np.zeros((self.read_nblock(read), self.P), dtype=np.float32)
         _check(lib().ffhip_batch_get_transitions(self.h, read, _fptr(out)))
@@ -756,6 +791,27 @@ def op_remap(engine: Engine, trans: np.ndarray, nbase: int, codes, band: int = 2
     _check(lib().ffhip_op_remap(engine.h, CFMat(_fptr(t), t.shape[1], t.shape[0], t.shape[1]), int(nbase), (q if q.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), q.size, int(band),
                                 rm.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(score)))
     return rm, np.float32(score.value)
+
+
+def _truth_dict(c, ops) -> dict:
+    out = {f: int(getattr(c, f)) for f in TRUTH_FIELDS}
+    out["ops"] = (np.zeros(0, np.uint8) if ops is None else ops) if c.status == 1 else None
+    return out
+
+
+def op_truth(engine: Engine, call, codes, band: int = 512) -> dict:
+    """ffhip_op_truth: the record (TRUTH_FIELDS, ops) of ONE call (letters A C G T Z, str or bytes) aligned to `codes` (0 .. 4, signal order)"""
+    s = call.encode() if isinstance(call, str) else bytes(call)
+    q = np.ascontiguousarray(codes, dtype=np.uint8)
+    ops, c = np.zeros(max(1, len(s) + q.size), np.uint8), CTruthCall()
+    _check(lib().ffhip_op_truth(engine.h, s, len(s), (q if q.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), q.size, int(band), C.byref(c),
+                                ops.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return _truth_dict(c, ops[:c.nops].copy())
+
+
+def truth_form(window: int) -> int:
+    """ffhip_debug_truth_form: the kernel form a window of that many cells takes (-1: none)"""
+    return int(lib().ffhip_debug_truth_form(int(window)))
 
 
 def basecall_reads(dmodel: DeviceModel, signals: np.ndarray, temperature: float = 1.0, flags: int = 0):

@@ -774,6 +774,20 @@ struct ffhip_batch {
     uint8_t *rmp_dev = nullptr, *rmp_host = nullptr;
     int rmp_count[kRemapForms] = { 0, 0, 0, 0 };
     size_t rmp_bytes() const { return (size_t)cap_reads * 16 + (size_t)nread * ((size_t)Tb + 1); }
+    // Truth (FFHIP_RUN_TRUTH, k_truth): the truths of ffhip_batch_set_truth on the host and (tru_dseq) on the device; ONE buffer of cap_reads 48-byte records and,
+    // behind them, m + blocks + 1 bytes of ops a read with a truth (tru_dev, its pinned mirror tru_host: both grow with the truths), with one copy of its own beside
+    // the block's; the reads' list and the traceback workspace as for remap
+    std::vector<std::vector<uint8_t>> tru_seq;              // per read: codes 0 .. nbase - 1
+    std::vector<signed char> tru_state;                     // per read: 0 no truth, 1 a truth, 2 an empty one
+    std::vector<size_t> tru_ops;                            // per read: its first byte of ops behind the records, and (one more entry) the end
+    int tru_set = 0, tru_band = 0, tru_valid = 0;
+    uint8_t *tru_dseq = nullptr; size_t tru_dseq_cap = 0;
+    unsigned long long *tru_ws = nullptr; size_t tru_ws_cap = 0;
+    TruthRead *tru_dlist = nullptr, *tru_hlist = nullptr;
+    uint8_t *tru_dev = nullptr, *tru_host = nullptr; size_t tru_dev_cap = 0, tru_host_cap = 0;
+    int tru_count[kTruthForms] = { 0, 0, 0, 0 };
+    size_t tru_rec_bytes() const { return (size_t)cap_reads * kTruthRecInts * 4; }
+    size_t tru_bytes() const { return tru_rec_bytes() + (tru_ops.empty() ? 0 : tru_ops.back()); }
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
     std::vector<void *> owned;
     unsigned last_flags = 0;
@@ -872,6 +886,8 @@ extern "C" void ffhip_batch_destroy(ffhip_batch *b) {
     if (b->bc_host) hipHostFree(b->bc_host);
     if (b->rmp_host) hipHostFree(b->rmp_host);
     if (b->rmp_hlist) hipHostFree(b->rmp_hlist);
+    if (b->tru_host) hipHostFree(b->tru_host);
+    if (b->tru_hlist) hipHostFree(b->tru_hlist);
     if (b->side) ffhip_batch_destroy(b->side);
     prof_unlink(b);
     if (b->have_ev) {
@@ -1484,7 +1500,7 @@ static int dgrow(ffhip_batch *b, void **p, size_t *cap, size_t need, const char 
         b->dev_bytes -= *cap;
         *p = nullptr; *cap = 0;
     }
-    if (!(*p = dalloc(b, need, false))) return set_err(FFHIP_ENOMEM, "remap: the %s takes %zu bytes of device memory, which could not be had", what, need);
+    if (!(*p = dalloc(b, need, false))) return set_err(FFHIP_ENOMEM, "%s takes %zu bytes of device memory, which could not be had", what, need);
     *cap = need;
     return FFHIP_OK;
 }
@@ -1520,7 +1536,7 @@ static int remap_prepare(ffhip_batch *b) {
         seq += (size_t)L;
         per[form].push_back(rr);
     }
-    if (int rc = dgrow(b, (void **)&b->rmp_ws, &b->rmp_ws_cap, ws * 8, "traceback workspace")) return rc;
+    if (int rc = dgrow(b, (void **)&b->rmp_ws, &b->rmp_ws_cap, ws * 8, "remap: the traceback workspace")) return rc;
     int at = 0;
     for (int f = 0; f < kRemapForms; f++) {
         b->rmp_count[f] = (int)per[f].size();
@@ -1541,6 +1557,66 @@ static void remap_launch(ffhip_batch *b, int nR, const int *tbr, ReadMap rmap) {
         at += b->rmp_count[f];
     }
     b->rmp_valid = 1;
+}
+
+// Truth, the front's share: as remap's.  The ops' bytes follow from the truths and the reads' blocks, so records and ops grow here too (device and pinned host).
+static_assert(sizeof(TruthRead) == 40, "the reads' list is copied as it stands");
+static int truth_prepare(ffhip_batch *b) {
+    const int nR = b->packed ? b->nvirt : b->nread;
+    if (!b->tru_set) return set_err(FFHIP_EINVAL, "truth: no truths are set for the batch (ffhip_batch_set_truth)");
+    if ((int)b->tru_seq.size() != nR) return set_err(FFHIP_EINVAL, "truth: truths were set for %zu reads, the batch holds %d", b->tru_seq.size(), nR);
+    if (!b->tru_dlist && !(b->tru_dlist = (TruthRead *)dalloc(b, (size_t)b->cap_reads * sizeof(TruthRead), false))) return FFHIP_ENOMEM;
+    if (!b->tru_hlist && hipHostMalloc((void **)&b->tru_hlist, (size_t)b->cap_reads * sizeof(TruthRead), hipHostMallocDefault) != hipSuccess) {
+        b->tru_hlist = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation failed");
+    }
+    std::vector<TruthRead> per[kTruthForms];
+    std::vector<size_t> off((size_t)nR + 1, 0);
+    size_t ws = 0, seq = 0, ops = 0;
+    for (int r = 0; r < nR; r++) {
+        const int N = b->hTb[r], m = (int)b->tru_seq[r].size();
+        const int cap = b->tru_state[r] == 1 && N > 0 ? m + N + 1 : 0;
+        TruthRead tr{ ws, ops, (unsigned)seq, m, N > 0 ? b->tru_state[r] : 0, r, cap, 0 };
+        int form = 0;
+        if (tr.status == 1) {
+            form = truth_form(std::min<long long>(2ll * b->tru_band + 1, (long long)N + 2));
+            if (form < 0) return set_err(FFHIP_EINVAL, "truth: read %d's window of min(2 band + 1, blocks + 2) cells is more than %d", r, truth_max_window());
+            ws += truth_ws_words(form, m);
+        }
+        off[r] = ops;
+        seq += (size_t)m; ops += (size_t)cap;
+        per[form].push_back(tr);
+    }
+    off[nR] = ops;
+    const size_t bytes = b->tru_rec_bytes() + ops;
+    if (int rc = dgrow(b, (void **)&b->tru_ws, &b->tru_ws_cap, ws * 8, "truth: the traceback workspace")) return rc;
+    if (int rc = dgrow(b, (void **)&b->tru_dev, &b->tru_dev_cap, bytes, "truth: the records and ops")) return rc;
+    if (!b->tru_host || bytes > b->tru_host_cap) {
+        if (b->tru_host) { HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP); hipHostFree(b->tru_host); b->tru_host = nullptr; b->tru_host_cap = 0; }
+        if (hipHostMalloc((void **)&b->tru_host, bytes, hipHostMallocDefault) != hipSuccess) { b->tru_host = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation failed"); }
+        b->tru_host_cap = bytes;
+        memset(b->tru_host, 0, bytes);
+    }
+    b->tru_ops = std::move(off);
+    int at = 0;
+    for (int f = 0; f < kTruthForms; f++) {
+        b->tru_count[f] = (int)per[f].size();
+        if (!per[f].empty()) memcpy(b->tru_hlist + at, per[f].data(), per[f].size() * sizeof(TruthRead));
+        at += (int)per[f].size();
+    }
+    if (nR > 0) HIP_TRY(hipMemcpyAsync(b->tru_dlist, b->tru_hlist, (size_t)nR * sizeof(TruthRead), hipMemcpyHostToDevice, b->stream), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+static void truth_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {
+    int at = 0;
+    for (int f = 0; f < kTruthForms; f++) {
+        if (b->tru_count[f] > 0) {
+            launch_truth(b->stream, f, b->tru_dlist + at, b->tru_count[f], b->tru_dseq, b->bases(), b->lens(), b->tru_band, b->tru_ws, (int *)b->tru_dev,
+                         b->tru_dev + b->tru_rec_bytes(), b->Tb, tbr, rmap);
+            b->launches[5]++;
+        }
+        at += b->tru_count[f];
+    }
+    b->tru_valid = 1;
 }
 
 // ffhip_batch_run_pair can put the layer launches of TWO batches into one grid between their fronts and backs (`paired`).  The front
@@ -1578,6 +1654,12 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
         if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "remap: a flip-flop model only (the run-length model's scores are not transitions between bases)");
         if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "remap needs a decoded run (FFHIP_RUN_NO_DECODE is set)");
         if (int rc = remap_prepare(b)) return rc;
+    }
+    b->tru_valid = 0;
+    if (flags & FFHIP_RUN_TRUTH) {         // (nor this)
+        if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "truth: a flip-flop model only (the run-length model's call is a list of runs)");
+        if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "truth needs a decoded run (FFHIP_RUN_NO_DECODE is set)");
+        if (int rc = truth_prepare(b)) return rc;
     }
     if (b->packed && !p.packable)
         return set_err(FFHIP_EINVAL, "packed batches take the default path and the launch-per-step kernels only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / unfused flags, ordinary temperature)");
@@ -1867,6 +1949,7 @@ static int run_back(ffhip_batch *b) {
                 b->bc_valid = 1;
                 b->launches[5]++;
             }
+            if (flags & FFHIP_RUN_TRUTH) truth_launch(b, tbr, rmap);          // from the strings and lengths too (run_front made the lists)
             if (flags & FFHIP_RUN_REMAP) remap_launch(b, nR, tbr, rmap);      // from the transitions, whatever the path was decoded from (run_front made the lists)
             if (flags & FFHIP_RUN_MOD_PROBS) {          // from the posterior whatever decoded the path (run_front checked the model)
                 launch_mod_probs(s, b->post, b->path, b->res.on_dev<uint8_t>(RF_ML), nR, Tb, m->Ps, tbr, rmap);
@@ -1893,6 +1976,7 @@ static int run_back(ffhip_batch *b) {
         HIP_TRY(hipMemcpyAsync(b->res.host, b->res.dev, b->res.copy_bytes(flags), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
         if (b->bc_valid) HIP_TRY(hipMemcpyAsync(b->bc_host, b->bc_dev, (size_t)nR * sizeof(ffhip_barcode_call), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the barcode records' one copy
         if (b->rmp_valid) HIP_TRY(hipMemcpyAsync(b->rmp_host, b->rmp_dev, b->rmp_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the remap records' and moves' one copy
+        if (b->tru_valid) HIP_TRY(hipMemcpyAsync(b->tru_host, b->tru_dev, b->tru_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the truth records' and ops' one copy
         b->res_copied = 1;
     }
     HIP_TRY(hipEventRecord(eng->batch_done, s), FFHIP_EHIP); eng->batch_done_rec = 1;
@@ -1944,7 +2028,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
     const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
     b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
     b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0; b->rmp_valid = 0;
+    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0; b->rmp_valid = 0; b->tru_valid = 0;
     return FFHIP_OK;
 }
 
@@ -2005,6 +2089,7 @@ extern "C" int ffhip_batch_paired(const ffhip_batch *b) { return (b && b->paired
 // construction -- a normalised sample in the hundreds -- so this path is written for clarity: a side batch of 16 slots with the
 // same capacity (hence the same strides: a read's results are contiguous device-to-device copies), created on first use.
 static int remap_adopt(ffhip_batch *b, std::vector<std::vector<unsigned short>> &&seq, std::vector<signed char> &&state, int band);
+static int truth_adopt(ffhip_batch *b, std::vector<std::vector<uint8_t>> &&seq, std::vector<signed char> &&state, int band);
 static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
     const ffhip_model *m = b->mdl;
     if (!b->side) {
@@ -2035,6 +2120,12 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
             std::vector<signed char> st(16, 0);
             for (int k = 0; k < n; k++) { sq[k] = b->rmp_seq[reads[k0 + k]]; st[k] = b->rmp_state[reads[k0 + k]]; }
             if (int rc = remap_adopt(sd, std::move(sq), std::move(st), b->rmp_band)) return rc;
+        }
+        if (fl & FFHIP_RUN_TRUTH) {                       // ... and truths
+            std::vector<std::vector<uint8_t>> sq(16);
+            std::vector<signed char> st(16, 0);
+            for (int k = 0; k < n; k++) { sq[k] = b->tru_seq[reads[k0 + k]]; st[k] = b->tru_state[reads[k0 + k]]; }
+            if (int rc = truth_adopt(sd, std::move(sq), std::move(st), b->tru_band)) return rc;
         }
         if (int rc = ffhip_batch_run(sd, b->last_temperature, (fl & ~(unsigned)FFHIP_RUN_KEEP_ACTS) | FFHIP_RUN_F32_RNN)) return rc;
         if (int rc = ffhip_batch_finish(sd)) return rc;
@@ -2069,6 +2160,16 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
                 memcpy(b->rmp_host + r * 16, sd->rmp_host + (size_t)k * 16, 16);
                 memcpy(b->rmp_host + mv, sd->rmp_host + smv, nb);
             }
+            if (b->tru_valid && sd->tru_valid) {        // and its truth record and ops (the same blocks and truth: the same bytes of ops), both halves
+                const size_t rb = (size_t)kTruthRecInts * 4, to = b->tru_rec_bytes() + b->tru_ops[r], from = sd->tru_rec_bytes() + sd->tru_ops[k];
+                const size_t ob = std::min(b->tru_ops[r + 1] - b->tru_ops[r], sd->tru_ops[k + 1] - sd->tru_ops[k]);
+                HIP_TRY(hipMemcpyAsync(b->tru_dev + r * rb, sd->tru_dev + (size_t)k * rb, rb, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                memcpy(b->tru_host + r * rb, sd->tru_host + (size_t)k * rb, rb);
+                if (ob) {
+                    HIP_TRY(hipMemcpyAsync(b->tru_dev + to, sd->tru_dev + from, ob, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                    memcpy(b->tru_host + to, sd->tru_host + from, ob);
+                }
+            }
         }
         HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
     }
@@ -2094,6 +2195,8 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
             HIP_TRY(hipMemcpyAsync(b->bc_host, b->bc_dev, (size_t)batch_nreads(b) * sizeof(ffhip_barcode_call), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
         if (b->rmp_valid)                                    // the remap records' and moves' one copy (likewise)
             HIP_TRY(hipMemcpyAsync(b->rmp_host, b->rmp_dev, b->rmp_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
+        if (b->tru_valid)                                    // the truth records' and ops' one copy (likewise)
+            HIP_TRY(hipMemcpyAsync(b->tru_host, b->tru_dev, b->tru_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
     }
     b->res_copied = 0;
     HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
@@ -2250,7 +2353,7 @@ static int remap_adopt(ffhip_batch *b, std::vector<std::vector<unsigned short>> 
     for (const auto &q : seq) total += q.size();
     hipSetDevice(b->eng->device);
     HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
-    if (int rc = dgrow(b, (void **)&b->rmp_dseq, &b->rmp_dseq_cap, (total ? total : 1) * sizeof(unsigned short), "sequences")) return rc;
+    if (int rc = dgrow(b, (void **)&b->rmp_dseq, &b->rmp_dseq_cap, (total ? total : 1) * sizeof(unsigned short), "remap: the sequences")) return rc;
     std::vector<unsigned short> flat;
     flat.reserve(total);
     for (const auto &q : seq) flat.insert(flat.end(), q.begin(), q.end());
@@ -2289,6 +2392,58 @@ extern "C" int ffhip_batch_remap(const ffhip_batch *b, int read, ffhip_remap_cal
     out->nblock = (size_t)b->hTb[read];
     out->rm = rec[0] == 1 ? b->rmp_host + (size_t)b->cap_reads * 16 + read_row1(b, read) : nullptr;
     if (rec[0] == 1 && rec[3] != 0) return set_err(FFHIP_EHIP, "remap: read %d's traceback ended at position %d, not 0", read, rec[3]);
+    return FFHIP_OK;
+}
+
+// ---- truth (include/ffhip.h "truth"; the kernel: ffhip_truth.hip)
+static int truth_adopt(ffhip_batch *b, std::vector<std::vector<uint8_t>> &&seq, std::vector<signed char> &&state, int band) {
+    size_t total = 0;
+    for (const auto &q : seq) total += q.size();
+    hipSetDevice(b->eng->device);
+    HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
+    if (int rc = dgrow(b, (void **)&b->tru_dseq, &b->tru_dseq_cap, total ? total : 1, "truth: the truths")) return rc;
+    std::vector<uint8_t> flat;
+    flat.reserve(total);
+    for (const auto &q : seq) flat.insert(flat.end(), q.begin(), q.end());
+    if (total) HIP_TRY(hipMemcpy(b->tru_dseq, flat.data(), total, hipMemcpyHostToDevice), FFHIP_EHIP);
+    b->tru_seq = std::move(seq); b->tru_state = std::move(state);
+    b->tru_band = band; b->tru_set = 1;
+    return FFHIP_OK;
+}
+extern "C" int ffhip_batch_set_truth(ffhip_batch *b, int nread, const uint8_t *const *codes, const size_t *len, int band) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "truth: the batch is between a run and its finish");
+    if (!codes) { b->tru_set = 0; b->tru_seq.clear(); b->tru_state.clear(); return FFHIP_OK; }
+    const ffhip_model *m = b->mdl;
+    if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "truth: a flip-flop model only (the run-length model's call is a list of runs)");
+    if (!len || nread != batch_nreads(b)) return set_err(FFHIP_EINVAL, "truth: truths for %d reads, the batch holds %d", nread, batch_nreads(b));
+    if (band < 0 || band > truth_max_band())
+        return set_err(FFHIP_EINVAL, "truth: the band half-width is %d (0 .. %d: the widest kernel form holds a window of %d cells)", band, truth_max_band(), truth_max_window());
+    std::vector<std::vector<uint8_t>> seq((size_t)nread);
+    std::vector<signed char> state((size_t)nread, 0);
+    for (int r = 0; r < nread; r++) {
+        if (!codes[r]) continue;
+        if (len[r] > (size_t)kTruthMaxLen) return set_err(FFHIP_EINVAL, "truth: read %d's truth has %zu bases (at most %d)", r, len[r], kTruthMaxLen);
+        state[r] = len[r] ? 1 : 2;
+        for (size_t i = 0; i < len[r]; i++) if (codes[r][i] >= m->nbase) return set_err(FFHIP_EINVAL, "truth: read %d, position %zu: code %d is not a base of the model (0 .. %d)", r, i, (int)codes[r][i], m->nbase - 1);
+        seq[r].assign(codes[r], codes[r] + len[r]);
+    }
+    return truth_adopt(b, std::move(seq), std::move(state), band);
+}
+extern "C" int ffhip_batch_truth(const ffhip_batch *b, int read, ffhip_truth_call *out) {
+    if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
+    if (!b->tru_valid || !b->tru_host) return set_err(FFHIP_EINVAL, "truth records were not made in this run (FFHIP_RUN_TRUTH)");
+    int rec[kTruthRecInts];
+    memcpy(rec, b->tru_host + (size_t)read * sizeof rec, sizeof rec);
+    out->status = rec[0]; out->n = (size_t)rec[1]; out->m = (size_t)rec[2]; out->dist = rec[3];
+    out->n_match = rec[4]; out->n_mismatch = rec[5]; out->n_ins = rec[6]; out->n_del = rec[7];
+    out->maxdev = rec[8]; out->nops = (size_t)rec[9];
+    out->ops = nullptr;
+    if (rec[0] == 1) {
+        const size_t cap = b->tru_ops[read + 1] - b->tru_ops[read];
+        if (rec[10] != 0 || out->nops > cap) return set_err(FFHIP_EHIP, "truth: read %d's traceback ended %d cells from (0, 0)", read, rec[10]);
+        out->ops = b->tru_host + b->tru_rec_bytes() + b->tru_ops[read + 1] - out->nops;
+    }
     return FFHIP_OK;
 }
 
@@ -2421,6 +2576,7 @@ extern "C" int ffhip_debug_batch_head_input(ffhip_batch *b, int row, float *out)
 
 extern "C" int ffhip_debug_fallback_count(const ffhip_engine *eng) { return eng ? eng->fallbacks : -1; }
 extern "C" int ffhip_debug_remap_form(size_t L, int band) { return (L < 1 || L > ((size_t)1 << 30) || band < 0) ? -1 : remap_form((int)L, band); }
+extern "C" int ffhip_debug_truth_form(size_t window) { return (window < 1 || window > ((size_t)1 << 30)) ? -1 : truth_form((long long)window); }
 extern "C" size_t ffhip_debug_batch_device_bytes(const ffhip_batch *b) { return b ? b->dev_bytes + b->res.cap : 0; }
 extern "C" int ffhip_debug_split_plan(int kind, int hidden, int remaining, int ncu, int beside, int out[6]) {
     if (!out) return set_err(FFHIP_EINVAL, "ffhip_debug_split_plan: out is NULL");

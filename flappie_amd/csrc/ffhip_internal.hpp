@@ -243,6 +243,24 @@ size_t remap_ws_words(int form, int nblock);
 void remap_code(const uint8_t *codes, size_t L, int nbase, unsigned short *out);
 void launch_remap(hipStream_t s, int form, const RemapRead *list, int count, const unsigned short *seq, const float *trans, int Ps, int band,
                   unsigned long long *ws, void *records, uint8_t *rm, int Tb, const int *tbs, ReadMap map);
+// the call scored against a known sequence (k_truth, ffhip_truth.hip; include/ffhip.h "truth"): per listed read one record of kTruthRecInts int32
+// { status, n, m, dist, matches, mismatches, insertions, deletions, maxdev, K, end, 0 } at rec[read] and, for an aligned one, its K op bytes RIGHT-aligned in the read's
+// `cap` bytes of `ops` (the path's last op at [ops + cap - 1]; cap >= n + m).  A form is one instantiation of the kernel (0, 1: one wave; 2, 3: a workgroup):
+// truth_form gives the smallest that holds a window of that many cells, -1 when none does; a launch takes the reads of ONE form.
+struct TruthRead {
+    unsigned long long ws;              // the read's first 64-bit word in the traceback workspace (truth_ws_words(form, m) of them)
+    unsigned long long ops;             // its first byte in the ops buffer
+    unsigned seq;                       // its first code in the truths
+    int m, status, read, cap, pad;      // bases; 0 no truth, 1 to be aligned, 2 refused; the read's index in the batch; its bytes of ops
+};
+constexpr int kTruthForms = 4, kTruthRecInts = 12;
+constexpr int kTruthMaxLen = 1 << 24;   // call and truth: the recursion's integers stay far below its +inf (1 << 29)
+int truth_form(long long window);
+int truth_max_window();
+int truth_max_band();
+size_t truth_ws_words(int form, int m);
+void launch_truth(hipStream_t s, int form, const TruthRead *list, int count, const uint8_t *seq, const char *bases, const int *lens, int band,
+                  unsigned long long *ws, int *records, uint8_t *ops, int Tb, const int *tbs, ReadMap map);
 // exp + trace_from_posterior
 void launch_trace(hipStream_t s, const float *post, int32_t *trace, int nread, int Tb, int nbase, int Ps, int is_log, const int *tbs = nullptr, ReadMap map = ReadMap());
 void launch_exp_inplace(hipStream_t s, float *x, size_t n);

@@ -707,6 +707,46 @@ extern "C" int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, con
     return FFHIP_OK;
 }
 
+// one call aligned to one truth (k_truth; include/ffhip.h "truth")
+extern "C" int ffhip_op_truth(ffhip_engine *eng, const char *call, size_t n, const uint8_t *truth, size_t m, int band, ffhip_truth_call *out, uint8_t *ops) {
+    OP_ENTER(eng);
+    if (!out || (n && !call) || (m && !truth) || ((n + m) && !ops)) return set_err(FFHIP_EINVAL, "bad truth arguments (a call, a truth, a record and n + m bytes of ops)");
+    if (n > (size_t)kTruthMaxLen || m > (size_t)kTruthMaxLen) return set_err(FFHIP_EINVAL, "truth: a call of %zu and a truth of %zu bases (at most %d each)", n, m, kTruthMaxLen);
+    if (band < 0 || band > truth_max_band())
+        return set_err(FFHIP_EINVAL, "truth: the band half-width is %d (0 .. %d: the widest kernel form holds a window of %d cells)", band, truth_max_band(), truth_max_window());
+    for (size_t i = 0; i < n; i++) if (!call[i] || !strchr("ACGTZ", call[i])) return set_err(FFHIP_EINVAL, "truth: position %zu of the call: '%c' is not one of A C G T Z", i, call[i]);
+    for (size_t i = 0; i < m; i++) if (truth[i] > 4) return set_err(FFHIP_EINVAL, "truth: position %zu of the truth: code %d is not a base (0 .. 4)", i, (int)truth[i]);
+    const int form = truth_form(std::min<long long>(2ll * band + 1, (long long)n + 1));
+    const int ni = (int)n, cap = (int)(n + m);
+    const TruthRead tr{ 0ull, 0ull, 0u, (int)m, m ? 1 : 2, 0, cap, 0 };
+    char *d_call = (char *)tmp.upload(n ? call : "", n ? n : 1, s);
+    uint8_t *d_seq = (uint8_t *)tmp.upload(m ? truth : (const uint8_t *)"", m ? m : 1, s);
+    int *d_len = (int *)tmp.upload(&ni, 4, s);
+    TruthRead *d_list = (TruthRead *)tmp.upload(&tr, sizeof tr, s);
+    const size_t ws_bytes = truth_ws_words(form, (int)m) * 8;
+    unsigned long long *d_ws = (unsigned long long *)tmp.get(ws_bytes ? ws_bytes : 8);
+    uint8_t *d_ops = (uint8_t *)tmp.get(cap ? cap : 1);
+    int *d_rec = (int *)tmp.get(kTruthRecInts * 4);
+    if (!d_ws) return set_err(FFHIP_ENOMEM, "truth: the traceback workspace takes %zu bytes of device memory, which could not be had", ws_bytes);
+    if (!d_call || !d_seq || !d_len || !d_list || !d_ops || !d_rec) OP_NOMEM();
+    // (Tb = max(n, 1): a read of no blocks is an empty slot to the kernel, which then reads no length)
+    launch_truth(s, form, d_list, 1, d_seq, d_call, d_len, band, d_ws, d_rec, d_ops, ni > 0 ? ni : 1, nullptr, ReadMap());
+    int rec[kTruthRecInts];
+    std::vector<uint8_t> got((size_t)cap);
+    HIP_TRY(hipMemcpyAsync(rec, d_rec, sizeof rec, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    if (cap) HIP_TRY(hipMemcpyAsync(got.data(), d_ops, (size_t)cap, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    HIP_TRY(hipGetLastError(), FFHIP_EHIP);
+    out->status = rec[0]; out->n = (size_t)rec[1]; out->m = (size_t)rec[2]; out->dist = rec[3];
+    out->n_match = rec[4]; out->n_mismatch = rec[5]; out->n_ins = rec[6]; out->n_del = rec[7];
+    out->maxdev = rec[8]; out->nops = (size_t)rec[9]; out->ops = nullptr;
+    if (rec[0] == 1) {
+        if (rec[10] != 0 || rec[9] < 0 || rec[9] > cap) return set_err(FFHIP_EHIP, "truth: the traceback ended %d cells from (0, 0)", rec[10]);
+        memcpy(ops, got.data() + cap - rec[9], (size_t)rec[9]);
+    }
+    return FFHIP_OK;
+}
+
 // ---- decoders of the first run-length head (decode.c:552-892): param is [4 nbase x nblock]
 static bool rl1_dims(const ffhip_mat &param, int *nbase) {
     if (!view_ok(param) || param.nr % 4 != 0 || param.nr / 4 < 1 || param.nr / 4 > 8) return false;

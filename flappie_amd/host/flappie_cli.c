@@ -41,6 +41,7 @@
 #include "../../include/flappie_moves.h"
 #include "../../include/flappie_barcodes.h"
 #include "../../include/flappie_remap.h"
+#include "../../include/flappie_truth.h"
 #include "../../include/networks.h"
 
 const char *argp_program_version = "flappie (MI355X/HIP) 0.1, interface of flappie 2.1.3";
@@ -97,10 +98,14 @@ static struct argp_option options[] = {
     {"remap", 31, "refs.fa", 0, "Map each read's signal to a sequence you already know: the records of a FASTA file, found by read id, then by the file's base name, in SIGNAL order (reverse them yourself for --reverse and RNA). The best path of the read's transition scores through its sequence is made on the GPU and written to --remap-out; stdout does not change"},
     {"remap-out", 256, "map.tsv", 0, "With --remap: one line per read that had a record: name, status (1 mapped, 2 not: a letter outside the model's alphabet, or more bases than blocks + 1), nblock, stride, trim_start, L, band, maxdev, score and the block every base starts at"},
     {"remap-band", 257, "W", 0, "With --remap: the band's half-width in sequence positions around the straight line from (0, 0) to (nblock, L - 1) (0-2303, default 2048: the GPU holds a window of at most 2 W + 1 <= 4608 positions; maxdev = W in map.tsv says the band was touched)"},
+    {"truth", 258, "refs.fa", 0, "Score each read's call against the sequence it should have been: the records of a FASTA file, found as for --remap (the same file may serve both), in SIGNAL order. The whole call is aligned to its record on the GPU (banded global edit distance) and the result written to --truth-out; stdout does not change. The alignment is always of the whole call in signal order: --reverse and --trim-barcodes do not alter it"},
+    {"truth-out", 259, "acc.tsv", 0, "With --truth (required): one line per read that had a record: name, status (1 aligned, 2 not: an empty record, a letter outside the model's alphabet, or a band that leaves no path), n, m, band, maxdev, dist, matches, mismatches, insertions, deletions, identity and the extended CIGAR (=XID)"},
+    {"truth-band", 260, "W", 0, "With --truth: the band's half-width in called bases around the straight line from (0, 0) to (m, n) (0-1279, default 512: the GPU holds a window of at most 2 W + 1 <= 2560 cells; maxdev = W in acc.tsv says the band was touched)"},
 #endif
 #ifdef BUILD_RUNNIE
     {"barcodes", 25, "kit.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"remap", 31, "refs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"truth", 258, "refs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
 #endif
     {0}
 };
@@ -143,8 +148,11 @@ static struct {
     char *remap, *remap_out;            /* flappie: --remap refs file, --remap-out table; the band's half-width */
     int remap_band;
     bool remap_band_set;
+    char *truth, *truth_out;            /* flappie: --truth refs file, --truth-out table; the band's half-width */
+    int truth_band;
+    bool truth_band_set;
 } args = { 1, 200, 0.0f, NULL, FLAPPIE_OUTFORMAT_FASTQ, 0, DEFAULT_MODEL, NULL, "", false, 1.0f, 200, 10, 100, 0.0f, false, NULL, true, 0, 4, 0, 0, false, false, false, false,
-           { 1.02, 1.04, 1.04, 1.02 }, false, false, NULL, 150, -1, -1, false, false, false, NULL, NULL, 2048, false };      /* batch 0: by model (below); nshard 0: --shard not given */
+           { 1.02, 1.04, 1.04, 1.02 }, false, false, NULL, 150, -1, -1, false, false, false, NULL, NULL, 2048, false, NULL, NULL, FLAPPIE_TRUTH_BAND_DEFAULT, false };      /* batch 0: by model (below); nshard 0: --shard not given */
 
 static void print_models(FILE *fh) {
     for (int mdl = 0; mdl < (int)flappie_nmodel; mdl++)
@@ -256,6 +264,7 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
 #endif
     case 25: args.barcodes = arg; break;
     case 31: args.remap = arg; break;
+    case 258: args.truth = arg; break;
 #ifndef BUILD_RUNNIE
     case 256: args.remap_out = arg; break;      /* (keys above UCHAR_MAX: argp makes a short option of a printable one) */
     case 257: {
@@ -263,6 +272,14 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
         const long w = strtol(arg, &end, 10);
         if (end == arg || *end != '\0' || w < 0 || w > FLAPPIE_REMAP_BAND_MAX) errx(EXIT_FAILURE, "--remap-band must be a whole number from 0 to %d", FLAPPIE_REMAP_BAND_MAX);
         args.remap_band = (int)w; args.remap_band_set = true;
+        break;
+    }
+    case 259: args.truth_out = arg; break;
+    case 260: {
+        char *end = NULL;
+        const long w = strtol(arg, &end, 10);
+        if (end == arg || *end != '\0' || w < 0 || w > FLAPPIE_TRUTH_BAND_MAX) errx(EXIT_FAILURE, "--truth-band must be a whole number from 0 to %d", FLAPPIE_TRUTH_BAND_MAX);
+        args.truth_band = (int)w; args.truth_band_set = true;
         break;
     }
 #endif
@@ -427,6 +444,10 @@ typedef struct {
     size_t rm_L, rm_nblock;
     float rm_score;
     uint8_t *rm;                        /* ... its moves (owned; NULL unless mapped) */
+    int tr_ref, have_tr;                /* --truth: the read's record of the truths (-1: none), and what the batch returned for it */
+    flappie_truth_rec tr;
+    uint8_t *tr_ops;                    /* ... its ops (owned; NULL unless aligned) */
+    size_t tr_nops;
     int rle_nocall;                     /* runnie --fasta: no runs, or a failed run-length estimate (decode_runnie.py: "No basecall returned") */
     /* a read of a MULTI-READ file: its samples as the file holds them (owned; res.rt.raw stays NULL, res.rt.n counts them) and its calibration -- the
      * preparation scales them on the device (ffhip_prep_begin_dac) */
@@ -501,6 +522,10 @@ static unsigned long long bc_count[FLAPPIE_BARCODE_MAX_KIT + 1];
 static flappie_remap_refs *rm_refs = NULL;
 static FILE *rm_out = NULL;
 static unsigned long long rm_count[4];
+/* flappie --truth: the truths, the table, and the summary */
+static flappie_remap_refs *tr_refs = NULL;
+static FILE *tr_out = NULL;
+static flappie_truth_summary tr_sum;
 #ifdef BUILD_RUNNIE
 /* --fasta: the runs and their run-length estimates come from the device (FFHIP_RUN_RLE_RUNS) with the batch's scale factors */
 static unsigned run_flags(void) { return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.fasta ? FFHIP_RUN_RLE_RUNS : 0u); }
@@ -513,7 +538,7 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
  * --barcodes: the reads' barcode records do (FFHIP_RUN_BARCODES) */
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u) |
-           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u);
+           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | (tr_refs ? FFHIP_RUN_TRUTH : 0u);
 }
 /* --remap: every read's record, by its read id, then by its file's base name; a bad record goes as a sequence of no bases (status 2) */
 static int batch_set_remap(ffhip_batch *b, item **its, int n) {
@@ -534,9 +559,29 @@ static int batch_set_remap(ffhip_batch *b, item **its, int n) {
     free(len);
     return rc;
 }
+/* --truth: likewise */
+static int batch_set_truth(ffhip_batch *b, item **its, int n) {
+    const int nb = ffhip_batch_nreads(b);
+    const uint8_t **codes = calloc(nb > 0 ? nb : 1, sizeof(uint8_t *));
+    size_t *len = calloc(nb > 0 ? nb : 1, sizeof(size_t));
+    static const uint8_t none = 0;
+    int rc = (codes && len) ? 0 : -1;
+    for (int i = 0; 0 == rc && i < n && i < nb; i++) {
+        const int k = its[i]->tr_ref = flappie_remap_refs_find(tr_refs, its[i]->res.rt.uuid, its[i]->filename);
+        if (k < 0) continue;
+        const int bad = tr_refs->bad[k] || 0 == tr_refs->len[k];
+        codes[i] = bad ? &none : tr_refs->codes[k];
+        len[i] = bad ? 0 : tr_refs->len[k];
+    }
+    if (0 == rc) rc = ffhip_batch_set_truth(b, nb, codes, len, args.truth_band);
+    free(codes);
+    free(len);
+    return rc;
+}
 static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
     if (bc_dev) { const int rc = ffhip_batch_set_barcodes(b, bc_dev, args.bc_max_dist, args.bc_min_sep, args.bc_both); if (rc) return rc; }
     if (rm_refs) { const int rc = batch_set_remap(b, its, n); if (rc) return rc; }
+    if (tr_refs) { const int rc = batch_set_truth(b, its, n); if (rc) return rc; }
     return ffhip_batch_run(b, args.temperature, flags);
 }
 #endif
@@ -808,6 +853,16 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
                 its[i]->mv_stride = (int)ffhip_model_stride(mdl);
             }
         }
+        if (tr_refs && its[i]->tr_ref >= 0) {                  /* the call against its truth, in signal order whatever --reverse does below */
+            ffhip_truth_call tc;
+            if (0 != ffhip_batch_truth(b, i, &tc)) warnx("%s", ffhip_last_error());
+            else {
+                its[i]->have_tr = 1;
+                its[i]->tr = (flappie_truth_rec){ tc.status, tc.n, tc.m, args.truth_band, tc.maxdev, tc.dist, tc.n_match, tc.n_mismatch, tc.n_ins, tc.n_del };
+                its[i]->tr_nops = 0;
+                if (1 == tc.status && NULL != (its[i]->tr_ops = malloc(tc.nops ? tc.nops : 1))) { memcpy(its[i]->tr_ops, tc.ops, tc.nops); its[i]->tr_nops = tc.nops; }
+            }
+        }
         if (args.reverse) {                                    /* flappie.c:294-297 */
             reverse_char_array(r->basecall, blen);
             reverse_char_array(r->quality, blen);
@@ -996,6 +1051,14 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
                     if (1 == it->rm_status) { rm_count[0]++; if (dev == (long)args.remap_band) rm_count[3]++; } else rm_count[2]++;
                 }
             }
+            if (tr_refs) {                                     /* likewise for --truth */
+                if (it->tr_ref < 0) flappie_truth_summary_add(&tr_sum, NULL);
+                else if (!it->have_tr) warnx("No alignment returned for %s", it->filename);
+                else {
+                    if (0 != flappie_truth_write_line(tr_out, tr_refs->name[it->tr_ref], &it->tr, it->tr_ops, it->tr_nops)) warnx("The ops of %s do not fit its record", it->filename);
+                    if (0 != flappie_truth_summary_add(&tr_sum, &it->tr)) warnx("--truth: out of memory for the summary");
+                }
+            }
             if (hdf5out >= 0) {
                 pthread_mutex_lock(&hdf5_lock);
                 if (packs && packs[i]) summary_pack_write(hdf5out, args.uuid ? uuid : base, packs[i]);
@@ -1017,6 +1080,10 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
         it->rm = NULL;
         it->have_rm = 0;
         it->rm_ref = -1;
+        free(it->tr_ops);
+        it->tr_ops = NULL;
+        it->have_tr = 0;
+        it->tr_ref = -1;
         free_raw_basecall_info(&it->res);
         free(it->filename);
     }
@@ -1522,6 +1589,7 @@ static void item_init(item *it, const char *path) {
     memset(it, 0, sizeof(*it));
     it->filename = strdup(path);
     it->rm_ref = -1;
+    it->tr_ref = -1;
 }
 static void item_from_dac(item *it, const char *path, const fast5_dac_read *dr) {
     item_init(it, path);
@@ -1720,6 +1788,7 @@ int main(int argc, char *argv[]) {
     if ((args.rlc || args.run_scale_set) && !args.fasta) errx(EXIT_FAILURE, "--rlc and --run-scale go with --fasta");
     if (args.barcodes) errx(EXIT_FAILURE, "--barcodes is flappie's: the run-length model's records carry no base strings to search");
     if (args.remap) errx(EXIT_FAILURE, "--remap is flappie's: the run-length model's scores are not transitions between the bases of a sequence");
+    if (args.truth) errx(EXIT_FAILURE, "--truth is flappie's: the run-length model's call is a list of runs");
 #else
     /* --barcodes: every refusal before any file or the GPU is touched */
     if (args.bc_opts && NULL == args.barcodes) errx(EXIT_FAILURE, "--barcode-window, --barcode-max-dist, --barcode-min-sep, --barcode-both-ends and --trim-barcodes go with --barcodes");
@@ -1740,6 +1809,17 @@ int main(int argc, char *argv[]) {
         for (int k = 0; k < rm_refs->n; k++)
             if (rm_refs->bad[k]) warnx("--remap: record %s holds a letter outside the model's alphabet: its read is not mapped (status 2)", rm_refs->name[k]);
         if (NULL == (rm_out = fopen(args.remap_out, "w"))) errx(EXIT_FAILURE, "--remap-out %s: cannot be written", args.remap_out);
+    }
+    /* --truth: likewise */
+    if ((NULL == args.truth) != (NULL == args.truth_out)) errx(EXIT_FAILURE, "--truth and --truth-out go together");
+    if (args.truth_band_set && NULL == args.truth) errx(EXIT_FAILURE, "--truth-band goes with --truth");
+    if (args.truth) {
+        char why[256];
+        tr_refs = flappie_remap_refs_read(args.truth, flappie_model_has_modbase(args.model) ? "ACGTZ" : "ACGT", why, sizeof why);
+        if (NULL == tr_refs) errx(EXIT_FAILURE, "--truth %s: %s", args.truth, why);
+        for (int k = 0; k < tr_refs->n; k++)
+            if (tr_refs->bad[k]) warnx("--truth: record %s holds a letter outside the model's alphabet: its read is not aligned (status 2)", tr_refs->name[k]);
+        if (NULL == (tr_out = fopen(args.truth_out, "w"))) errx(EXIT_FAILURE, "--truth-out %s: cannot be written", args.truth_out);
     }
     if (args.modbase_tags && !flappie_model_has_modbase(args.model))      /* (the registry knows: before any file or the GPU is touched) */
         errx(EXIT_FAILURE, "--modbase-tags needs a model with a modified base (r941_5mC); \"%s\" has none", flappie_model_string(args.model));
@@ -1842,6 +1922,12 @@ int main(int argc, char *argv[]) {
         fprintf(stderr, "remap\tmapped\t%llu\nremap\tno_record\t%llu\nremap\trefused\t%llu\nremap\tband_touched\t%llu\n", rm_count[0], rm_count[1], rm_count[2], rm_count[3]);
         if (0 != fclose(rm_out)) warnx("--remap-out %s: write failed", args.remap_out);
         flappie_remap_refs_free(rm_refs);
+    }
+    if (tr_refs) {                     /* reads aligned, not aligned, without a record, the pooled and the median identity */
+        flappie_truth_summary_print(stderr, &tr_sum);
+        flappie_truth_summary_free(&tr_sum);
+        if (0 != fclose(tr_out)) warnx("--truth-out %s: write failed", args.truth_out);
+        flappie_remap_refs_free(tr_refs);
     }
 #endif
     flappie_hip_shutdown();

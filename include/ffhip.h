@@ -106,6 +106,11 @@ typedef struct {
  * they live in ONE buffer of their own (reads x 16 bytes, then a byte a block) and come down in ONE extra copy, enqueued where the result block's copy is.
  * Everything else the run returns is that of the same run without the flag.  No sequences set, the run-length model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
 #define FFHIP_RUN_REMAP      32768u
+/* The call scored against a sequence the caller knows (ffhip_batch_truth below, "truth"): a banded global edit-distance alignment of each read's called letters to
+ * the truth given with ffhip_batch_set_truth, with traceback, made on the device (k_truth) behind the call's assembly.  Records and ops are NOT part of the result
+ * block: they live in ONE buffer of their own (reads x 48 bytes, then the ops) and come down in ONE extra copy, enqueued where the result block's copy is.
+ * Everything else the run returns is that of the same run without the flag.  No truths set, the run-length model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
+#define FFHIP_RUN_TRUTH      65536u
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -434,6 +439,44 @@ int ffhip_batch_remap(const ffhip_batch *b, int read, ffhip_remap_call *out);
 int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, int band, uint8_t *rm /* nblock */, float *score);
 /* the kernel form a sequence of L bases takes at this band: 0, 1 one wave (windows up to 64, 256 cells), 2, 3 a workgroup (up to 1024, 4608 cells); -1: none */
 int ffhip_debug_remap_form(size_t L, int band);
+/* Truth: how close a call is to the sequence it should have been.
+ *   Inputs: the call s of n >= 0 bases -- the batch's called letters in signal order, Z read as C (as the barcode search reads it); the truth t of m bases as codes
+ *     0 .. nbase - 1, code 4 (Z) folded to 1 (C) for the comparison; the band half-width W >= 0.
+ *   Cells: (j, i), j = 0 .. m truth bases and i = 0 .. n call bases consumed.  c(j) = floor(j n / m) in 64-bit integers; a cell is allowed iff |i - c(j)| <= W.
+ *   Recursion, in integers over allowed cells only, a cell that is not allowed counting as +inf: D[0][0] = 0,
+ *     D[j][i] = min(D[j-1][i-1] + (t_j != s_i), D[j-1][i] + 1, D[j][i-1] + 1); dist = D[m][n].
+ *   Status: 0 no truth given; 1 aligned; 2 not aligned: m = 0, or D[m][n] is infinite (the band leaves no path).  n = 0 with m >= 1 is status 1: m deletions.
+ *     (An empty slot of a batch -- a read of no blocks -- has no call at all, not a call of no bases: its truth is set aside, its record says status 0, and
+ *     ffhip_batch_truth refuses the slot as every other result call does.)
+ *   Traceback, defined on D alone so that no evaluation order can change it: from (m, n), at cell (j, i)
+ *     1. the diagonal if j, i > 0, (j-1, i-1) is allowed and D[j-1][i-1] + (t_j != s_i) == D[j][i]: op '=' (0) or 'X' (1);
+ *     2. else the deletion if j > 0, (j-1, i) is allowed and D[j-1][i] + 1 == D[j][i]: op 'D' (3);
+ *     3. else the insertion: op 'I' (2).
+ *   Output per read: status, n, m, dist; the four op counts (n_match + n_mismatch + n_ins = n, n_match + n_mismatch + n_del = m); maxdev = max |i - c(j)| over
+ *     the path's cells (maxdev == W: widen the band); the ops in path order from (0, 0), one byte each, nops = dist + n_match of them.
+ *   The band runs along the truth, so that the host, which knows m but not n, can size everything: the traceback workspace is two bits a cell of row and window
+ *     (m rows of the chosen kernel form's cells), the window min(2 W + 1, nblock + 2) cells since n <= nblock + 1.  The kernel forms hold windows of 64, 256, 1280
+ *     and 2560 cells, so W runs from 0 to 1279.  Call and truth: at most 2^24 bases each.
+ * ffhip_batch_set_truth: the truths (copied at the call) and the band of the batch's later runs with FFHIP_RUN_TRUTH; nread = the batch's reads (ffhip_batch_nreads);
+ *   codes[r] == NULL: read r has no truth (status 0); len[r] == 0: status 2.  A code >= nbase, band < 0 or > 1279 (a band the widest form cannot hold), the
+ *   run-length model, or a call between a run and its finish: FFHIP_EINVAL, and the batch is as it was.  codes == NULL detaches.
+ * ffhip_batch_truth: after ffhip_batch_finish of a run with the flag; ops points into the batch (nops bytes, valid until the next run), NULL unless status is 1.
+ * ffhip_op_truth: the kernel on ONE pair; call: n letters of A C G T Z; ops: caller-owned, n + m bytes, of which the first out->nops are written; out->ops is NULL.
+ *   A letter outside A C G T Z, a code > 4, a band outside 0 .. 1279: FFHIP_EINVAL.  m = 0 is status 2.
+ * The traceback workspace and the buffer of records and ops are grown by the first run that needs them, sized from the truths' lengths, the reads' blocks and the
+ * band, freed with the batch and counted by ffhip_debug_batch_device_bytes; when one cannot be had: FFHIP_ENOMEM with the bytes in the text. */
+typedef struct {
+    int status;
+    size_t n, m;
+    int dist, n_match, n_mismatch, n_ins, n_del, maxdev;
+    size_t nops;
+    const uint8_t *ops;
+} ffhip_truth_call;
+int ffhip_batch_set_truth(ffhip_batch *b, int nread, const uint8_t *const *codes, const size_t *len, int band);
+int ffhip_batch_truth(const ffhip_batch *b, int read, ffhip_truth_call *out);
+int ffhip_op_truth(ffhip_engine *eng, const char *call, size_t n, const uint8_t *truth, size_t m, int band, ffhip_truth_call *out, uint8_t *ops /* n + m */);
+/* the kernel form a window of that many cells takes: 0, 1 one wave (up to 64, 256 cells), 2, 3 a workgroup (up to 1280, 2560 cells); -1: none */
+int ffhip_debug_truth_form(size_t window);
 int ffhip_runlength_viterbi(ffhip_engine *eng, ffhip_mat param, int *path /* nblock */, float *score);
 /* decoders of the first-generation head on [4 nbase x nblock] matrices: decode_runlength (decode.c:694-767), posterior_runlength
  * (decode.c:793-892; post is [4 nbase x nblock + 1]), runlengths_mean (decode.c:576-603) */
