@@ -34,6 +34,8 @@ RUN_MOVES = 8192          # flip-flop model: the move table (one byte a block, 1
 RUN_BARCODES = 16384      # flip-flop model: one barcode record a read made on the device against the kit of Batch.set_barcodes (Batch.barcode)
 RUN_REMAP = 32768         # flip-flop model: each read's signal mapped to the sequence of Batch.set_remap on the device (Batch.remap)
 RUN_TRUTH = 65536         # flip-flop model: each read's call aligned to the truth of Batch.set_truth on the device (Batch.truth)
+RUN_EVENTS = 131072       # with RUN_REMAP: first sample, count, mean and sd of every base of every mapped read, made on the device (Batch.events)
+EVENT_DTYPE = np.dtype([("first", np.int32), ("count", np.int32), ("mean", np.float32), ("sd", np.float32)])      # ffhip_event (include/ffhip.h)
 TRUTH_BAND_MAX = 1279     # the widest kernel form holds a window of 2 W + 1 <= 2560 cells
 TRUTH_FIELDS = ("status", "n", "m", "dist", "n_match", "n_mismatch", "n_ins", "n_del", "maxdev")
 # ffhip_debug_gate_math forms (include/ffhip.h)
@@ -223,6 +225,8 @@ def lib():
     L.ffhip_batch_remap.argtypes = [vp, C.c_int, C.POINTER(CRemapCall)]
     L.ffhip_op_remap.argtypes = [vp, CFMat, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_float)]
     L.ffhip_debug_remap_form.argtypes = [C.c_size_t, C.c_int]
+    L.ffhip_batch_events.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ffhip_op_events.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_size_t, vp]
     L.ffhip_batch_set_truth.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t), C.c_int]
     L.ffhip_batch_truth.argtypes = [vp, C.c_int, C.POINTER(CTruthCall)]
     L.ffhip_op_truth.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.POINTER(CTruthCall), C.POINTER(C.c_uint8)]
@@ -610,6 +614,14 @@ class Batch:
         rm = np.ctypeslib.as_array(c.rm, shape=(c.nblock,)).copy() if c.status == 1 and c.nblock else None
         return {"status": int(c.status), "L": int(c.L), "score": np.float32(c.score), "rm": rm, "nblock": int(c.nblock)}
 
+    def events(self, read: int):
+        """events of a run with RUN_REMAP | RUN_EVENTS (ffhip_batch_events): a structured array (EVENT_DTYPE) of L entries, base after base; None unless the read's remap status is 1"""
+        ev, n = C.c_void_p(), C.c_size_t()
+        _check(lib().ffhip_batch_events(self.h, read, C.byref(ev), C.byref(n)))
+        if not ev.value:
+            return None
+        return np.frombuffer(C.string_at(ev.value, n.value * EVENT_DTYPE.itemsize), dtype=EVENT_DTYPE).copy()
+
     def set_truth(self, seqs, band: int = 512):
         """the truths and band of later runs with RUN_TRUTH (ffhip_batch_set_truth): one entry a read, None (no truth) or codes 0 .. nbase - 1 in signal order; seqs None detaches"""
         if seqs is None:
@@ -791,6 +803,16 @@ def op_remap(engine: Engine, trans: np.ndarray, nbase: int, codes, band: int = 2
     _check(lib().ffhip_op_remap(engine.h, CFMat(_fptr(t), t.shape[1], t.shape[0], t.shape[1]), int(nbase), (q if q.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), q.size, int(band),
                                 rm.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(score)))
     return rm, np.float32(score.value)
+
+
+def op_events(engine: Engine, signal, stride: int, rm, L: int) -> np.ndarray:
+    """ffhip_op_events: the events (EVENT_DTYPE, L entries) of ONE read from its prepared signal (float32), the model's stride and its remap path rm (uint8, a byte a block)"""
+    x = np.ascontiguousarray(signal, dtype=np.float32)
+    m = np.ascontiguousarray(rm, dtype=np.uint8)
+    out = np.zeros(max(1, int(L)), EVENT_DTYPE)
+    _check(lib().ffhip_op_events(engine.h, (x if x.size else np.zeros(1, np.float32)).ctypes.data_as(C.POINTER(C.c_float)), x.size, int(stride),
+                                 (m if m.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), m.size, int(L), out.ctypes.data_as(C.c_void_p)))
+    return out[:int(L)]
 
 
 def _truth_dict(c, ops) -> dict:

@@ -788,6 +788,13 @@ struct ffhip_batch {
     int tru_count[kTruthForms] = { 0, 0, 0, 0 };
     size_t tru_rec_bytes() const { return (size_t)cap_reads * kTruthRecInts * 4; }
     size_t tru_bytes() const { return tru_rec_bytes() + (tru_ops.empty() ? 0 : tru_ops.back()); }
+    // Events (FFHIP_RUN_EVENTS with FFHIP_RUN_REMAP, k_events): ONE buffer of 16 bytes a base of every read with a sequence that can be mapped, one read behind the
+    // other (evt_dev, its pinned mirror evt_host: both grow with the sequences), with one copy of its own beside the remap buffer's; the reads' list as for remap
+    std::vector<size_t> evt_off;                            // per read: its first event, and (one more entry) the end
+    EventRead *evt_dlist = nullptr, *evt_hlist = nullptr;
+    uint8_t *evt_dev = nullptr, *evt_host = nullptr; size_t evt_dev_cap = 0, evt_host_cap = 0;
+    int evt_valid = 0, evt_count = 0;
+    size_t evt_bytes() const { return (evt_off.empty() ? 0 : evt_off.back()) * sizeof(ffhip_event); }
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
     std::vector<void *> owned;
     unsigned last_flags = 0;
@@ -888,6 +895,8 @@ extern "C" void ffhip_batch_destroy(ffhip_batch *b) {
     if (b->rmp_hlist) hipHostFree(b->rmp_hlist);
     if (b->tru_host) hipHostFree(b->tru_host);
     if (b->tru_hlist) hipHostFree(b->tru_hlist);
+    if (b->evt_host) hipHostFree(b->evt_host);
+    if (b->evt_hlist) hipHostFree(b->evt_hlist);
     if (b->side) ffhip_batch_destroy(b->side);
     prof_unlink(b);
     if (b->have_ev) {
@@ -1559,6 +1568,54 @@ static void remap_launch(ffhip_batch *b, int nR, const int *tbr, ReadMap rmap) {
     b->rmp_valid = 1;
 }
 
+// Events, the front's share, behind remap's: every read's place in the one buffer, from the L of its sequence, and where its samples stand (the addresses
+// rerun_on_f32_path reads them at); the buffer and its mirror grow here.  A read remap_prepare refuses has no room and no entry.
+static_assert(sizeof(EventRead) == 32 && sizeof(ffhip_event) == 16, "the reads' list is copied as it stands; k_events writes an event as one 16-byte store");
+static int events_prepare(ffhip_batch *b) {
+    const int nR = b->packed ? b->nvirt : b->nread, st = total_stride(b->mdl);
+    if (!b->evt_dlist && !(b->evt_dlist = (EventRead *)dalloc(b, (size_t)b->cap_reads * sizeof(EventRead), false))) return FFHIP_ENOMEM;
+    if (!b->evt_hlist && hipHostMalloc((void **)&b->evt_hlist, (size_t)b->cap_reads * sizeof(EventRead), hipHostMallocDefault) != hipSuccess) {
+        b->evt_hlist = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation failed");
+    }
+    std::vector<size_t> off((size_t)nR + 1, 0);
+    std::vector<EventRead> list;
+    size_t at = 0;
+    for (int r = 0; r < nR; r++) {
+        const int N = b->hTb[r], L = (int)b->rmp_seq[r].size();
+        off[r] = at;
+        if (b->rmp_state[r] != 1 || N < 1 || L < 1 || L > N + 1) continue;
+        const size_t sig = (b->packed ? (size_t)b->v_slot[r] * b->sbuf[0].rs + (size_t)b->v_off[r] * st : (size_t)r * b->sbuf[0].rs) + kSamplePad;
+        list.push_back(EventRead{ sig, at, b->hT[r], L, r, 0 });
+        at += (size_t)L;
+    }
+    off[nR] = at;
+    const size_t bytes = std::max<size_t>(at, 1) * sizeof(ffhip_event);
+    if (int rc = dgrow(b, (void **)&b->evt_dev, &b->evt_dev_cap, bytes, "events: the reads' events")) return rc;
+    if (!b->evt_host || bytes > b->evt_host_cap) {
+        if (b->evt_host) { HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP); hipHostFree(b->evt_host); b->evt_host = nullptr; b->evt_host_cap = 0; }
+        if (hipHostMalloc((void **)&b->evt_host, bytes, hipHostMallocDefault) != hipSuccess) {
+            b->evt_host = nullptr; return set_err(FFHIP_ENOMEM, "events: the reads' events take %zu bytes of pinned host memory, which could not be had", bytes);
+        }
+        b->evt_host_cap = bytes;
+        memset(b->evt_host, 0, bytes);
+    }
+    b->evt_off = std::move(off);
+    b->evt_count = (int)list.size();
+    if (!list.empty()) {
+        memcpy(b->evt_hlist, list.data(), list.size() * sizeof(EventRead));
+        HIP_TRY(hipMemcpyAsync(b->evt_dlist, b->evt_hlist, list.size() * sizeof(EventRead), hipMemcpyHostToDevice, b->stream), FFHIP_EHIP);
+    }
+    return FFHIP_OK;
+}
+static void events_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {
+    if (b->evt_count > 0) {
+        launch_events(b->stream, b->evt_dlist, b->evt_count, b->sbuf[0].p, total_stride(b->mdl), b->rmp_dev, b->rmp_dev + (size_t)b->cap_reads * 16, b->evt_dev,
+                      b->Tb, tbr, rmap);
+        b->launches[5]++;
+    }
+    b->evt_valid = 1;
+}
+
 // Truth, the front's share: as remap's.  The ops' bytes follow from the truths and the reads' blocks, so records and ops grow here too (device and pinned host).
 static_assert(sizeof(TruthRead) == 40, "the reads' list is copied as it stands");
 static int truth_prepare(ffhip_batch *b) {
@@ -1654,6 +1711,11 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
         if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "remap: a flip-flop model only (the run-length model's scores are not transitions between bases)");
         if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "remap needs a decoded run (FFHIP_RUN_NO_DECODE is set)");
         if (int rc = remap_prepare(b)) return rc;
+    }
+    b->evt_valid = 0;
+    if (flags & FFHIP_RUN_EVENTS) {        // (remap's checks have passed)
+        if (!(flags & FFHIP_RUN_REMAP)) return set_err(FFHIP_EINVAL, "events: the signal of a mapped read's bases needs the mapping (FFHIP_RUN_EVENTS goes with FFHIP_RUN_REMAP)");
+        if (int rc = events_prepare(b)) return rc;
     }
     b->tru_valid = 0;
     if (flags & FFHIP_RUN_TRUTH) {         // (nor this)
@@ -1951,6 +2013,7 @@ static int run_back(ffhip_batch *b) {
             }
             if (flags & FFHIP_RUN_TRUTH) truth_launch(b, tbr, rmap);          // from the strings and lengths too (run_front made the lists)
             if (flags & FFHIP_RUN_REMAP) remap_launch(b, nR, tbr, rmap);      // from the transitions, whatever the path was decoded from (run_front made the lists)
+            if (flags & FFHIP_RUN_EVENTS) events_launch(b, tbr, rmap);        // from the path k_remap has just written and the signal the convolutions read
             if (flags & FFHIP_RUN_MOD_PROBS) {          // from the posterior whatever decoded the path (run_front checked the model)
                 launch_mod_probs(s, b->post, b->path, b->res.on_dev<uint8_t>(RF_ML), nR, Tb, m->Ps, tbr, rmap);
                 b->launches[5]++;
@@ -1976,6 +2039,7 @@ static int run_back(ffhip_batch *b) {
         HIP_TRY(hipMemcpyAsync(b->res.host, b->res.dev, b->res.copy_bytes(flags), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
         if (b->bc_valid) HIP_TRY(hipMemcpyAsync(b->bc_host, b->bc_dev, (size_t)nR * sizeof(ffhip_barcode_call), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the barcode records' one copy
         if (b->rmp_valid) HIP_TRY(hipMemcpyAsync(b->rmp_host, b->rmp_dev, b->rmp_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the remap records' and moves' one copy
+        if (b->evt_valid && b->evt_bytes()) HIP_TRY(hipMemcpyAsync(b->evt_host, b->evt_dev, b->evt_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the events' one copy
         if (b->tru_valid) HIP_TRY(hipMemcpyAsync(b->tru_host, b->tru_dev, b->tru_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the truth records' and ops' one copy
         b->res_copied = 1;
     }
@@ -2028,7 +2092,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
     const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
     b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
     b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0; b->rmp_valid = 0; b->tru_valid = 0;
+    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0; b->rmp_valid = 0; b->tru_valid = 0; b->evt_valid = 0;
     return FFHIP_OK;
 }
 
@@ -2160,6 +2224,14 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
                 memcpy(b->rmp_host + r * 16, sd->rmp_host + (size_t)k * 16, 16);
                 memcpy(b->rmp_host + mv, sd->rmp_host + smv, nb);
             }
+            if (b->evt_valid && sd->evt_valid) {        // and its events (the same sequence and blocks: the same room), both halves
+                const size_t ne = std::min(b->evt_off[r + 1] - b->evt_off[r], sd->evt_off[k + 1] - sd->evt_off[k]) * sizeof(ffhip_event);
+                const size_t to = b->evt_off[r] * sizeof(ffhip_event), from = sd->evt_off[k] * sizeof(ffhip_event);
+                if (ne) {
+                    HIP_TRY(hipMemcpyAsync(b->evt_dev + to, sd->evt_dev + from, ne, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                    memcpy(b->evt_host + to, sd->evt_host + from, ne);
+                }
+            }
             if (b->tru_valid && sd->tru_valid) {        // and its truth record and ops (the same blocks and truth: the same bytes of ops), both halves
                 const size_t rb = (size_t)kTruthRecInts * 4, to = b->tru_rec_bytes() + b->tru_ops[r], from = sd->tru_rec_bytes() + sd->tru_ops[k];
                 const size_t ob = std::min(b->tru_ops[r + 1] - b->tru_ops[r], sd->tru_ops[k + 1] - sd->tru_ops[k]);
@@ -2195,6 +2267,8 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
             HIP_TRY(hipMemcpyAsync(b->bc_host, b->bc_dev, (size_t)batch_nreads(b) * sizeof(ffhip_barcode_call), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
         if (b->rmp_valid)                                    // the remap records' and moves' one copy (likewise)
             HIP_TRY(hipMemcpyAsync(b->rmp_host, b->rmp_dev, b->rmp_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
+        if (b->evt_valid && b->evt_bytes())                  // the events' one copy (likewise)
+            HIP_TRY(hipMemcpyAsync(b->evt_host, b->evt_dev, b->evt_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
         if (b->tru_valid)                                    // the truth records' and ops' one copy (likewise)
             HIP_TRY(hipMemcpyAsync(b->tru_host, b->tru_dev, b->tru_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
     }
@@ -2392,6 +2466,21 @@ extern "C" int ffhip_batch_remap(const ffhip_batch *b, int read, ffhip_remap_cal
     out->nblock = (size_t)b->hTb[read];
     out->rm = rec[0] == 1 ? b->rmp_host + (size_t)b->cap_reads * 16 + read_row1(b, read) : nullptr;
     if (rec[0] == 1 && rec[3] != 0) return set_err(FFHIP_EHIP, "remap: read %d's traceback ended at position %d, not 0", read, rec[3]);
+    return FFHIP_OK;
+}
+
+// ---- events (include/ffhip.h "events"; the kernel: ffhip_events.hip)
+extern "C" int ffhip_batch_events(const ffhip_batch *b, int read, const ffhip_event **ev, size_t *L) {
+    if (!results_ok(b, read) || !ev || !L) return FFHIP_EINVAL;
+    if (!b->evt_valid || !b->rmp_valid || !b->evt_host) return set_err(FFHIP_EINVAL, "events were not made in this run (FFHIP_RUN_REMAP | FFHIP_RUN_EVENTS)");
+    int rec[4];
+    memcpy(rec, b->rmp_host + (size_t)read * 16, 16);
+    *ev = nullptr; *L = 0;
+    if (rec[0] != 1) return FFHIP_OK;
+    if (rec[3] != 0) return set_err(FFHIP_EHIP, "remap: read %d's traceback ended at position %d, not 0", read, rec[3]);
+    if ((size_t)rec[1] != b->evt_off[read + 1] - b->evt_off[read]) return set_err(FFHIP_EHIP, "events: read %d was mapped to %d bases, its events hold %zu", read, rec[1], b->evt_off[read + 1] - b->evt_off[read]);
+    *ev = (const ffhip_event *)b->evt_host + b->evt_off[read];
+    *L = (size_t)rec[1];
     return FFHIP_OK;
 }
 

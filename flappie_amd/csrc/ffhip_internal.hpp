@@ -261,6 +261,16 @@ int truth_max_band();
 size_t truth_ws_words(int form, int m);
 void launch_truth(hipStream_t s, int form, const TruthRead *list, int count, const uint8_t *seq, const char *bases, const int *lens, int band,
                   unsigned long long *ws, int *records, uint8_t *ops, int Tb, const int *tbs, ReadMap map);
+// the signal of every base of a mapped read (k_events, ffhip_events.hip; include/ffhip.h "events"): per listed read whose remap record at records[read] says
+// { status 1, end 0 }, L events of 16 bytes { int32 first, count; float mean, sd } at events[out ..], from the read's samples sig[sig .. sig + n) and its bytes at the
+// read's row of the (Tb + 1)-entry byte buffer `rm`; any other read writes nothing.  One form; the launch comes behind launch_remap on the same stream.
+struct EventRead {
+    unsigned long long sig;             // the read's first sample, in floats from `sig`
+    unsigned long long out;             // its first event
+    int n, L, read, pad;                // samples; the bases it has room for (a record with more writes nothing); the read's index in the batch
+};
+void launch_events(hipStream_t s, const EventRead *list, int count, const float *sig, int stride, const void *records, const uint8_t *rm, void *events,
+                   int Tb, const int *tbs, ReadMap map);
 // exp + trace_from_posterior
 void launch_trace(hipStream_t s, const float *post, int32_t *trace, int nread, int Tb, int nbase, int Ps, int is_log, const int *tbs = nullptr, ReadMap map = ReadMap());
 void launch_exp_inplace(hipStream_t s, float *x, size_t n);

@@ -707,6 +707,35 @@ extern "C" int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, con
     return FFHIP_OK;
 }
 
+// the events of one read from its signal and its path (k_events; include/ffhip.h "events")
+extern "C" int ffhip_op_events(ffhip_engine *eng, const float *signal, size_t nsample, int stride, const uint8_t *rm, size_t nblock, size_t L, ffhip_event *out) {
+    OP_ENTER(eng);
+    if (!rm || !out || (nsample && !signal)) return set_err(FFHIP_EINVAL, "bad events arguments (a signal, a path of nblock bytes and L events of output)");
+    if (stride < 1 || nblock < 1 || L < 1 || nblock > (size_t)1 << 30 || nsample > (size_t)1 << 30)
+        return set_err(FFHIP_EINVAL, "events: stride %d, %zu blocks, %zu samples and %zu bases (a stride >= 1, 1 .. 2^30 blocks, at most 2^30 samples, L >= 1)", stride, nblock, nsample, L);
+    size_t ones = 0;
+    for (size_t i = 0; i < nblock; i++) {
+        if (rm[i] > 1) return set_err(FFHIP_EINVAL, "events: block %zu of the path is %d (0 or 1)", i, (int)rm[i]);
+        ones += rm[i];
+    }
+    if (ones != L - 1) return set_err(FFHIP_EINVAL, "events: the path moves %zu times, a sequence of %zu bases takes %zu", ones, L, L - 1);
+    const EventRead er{ 0ull, 0ull, (int)nsample, (int)L, 0, 0 };
+    const unsigned rec[4] = { 1u, (unsigned)L, 0u, 0u };
+    const float none = 0.0f;
+    float *d_x = (float *)tmp.upload(nsample ? signal : &none, (nsample ? nsample : 1) * sizeof(float), s);
+    uint8_t *d_rm = (uint8_t *)tmp.upload(rm, nblock, s);
+    EventRead *d_list = (EventRead *)tmp.upload(&er, sizeof er, s);
+    void *d_rec = tmp.upload(rec, sizeof rec, s);
+    void *d_ev = tmp.get(L * sizeof(ffhip_event));
+    if (!d_ev) return set_err(FFHIP_ENOMEM, "events: the events take %zu bytes of device memory, which could not be had", L * sizeof(ffhip_event));
+    if (!d_x || !d_rm || !d_list || !d_rec) OP_NOMEM();
+    launch_events(s, d_list, 1, d_x, stride, d_rec, d_rm, d_ev, (int)nblock, nullptr, ReadMap());
+    HIP_TRY(hipMemcpyAsync(out, d_ev, L * sizeof(ffhip_event), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    HIP_TRY(hipGetLastError(), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+
 // one call aligned to one truth (k_truth; include/ffhip.h "truth")
 extern "C" int ffhip_op_truth(ffhip_engine *eng, const char *call, size_t n, const uint8_t *truth, size_t m, int band, ffhip_truth_call *out, uint8_t *ops) {
     OP_ENTER(eng);

@@ -98,6 +98,7 @@ static struct argp_option options[] = {
     {"remap", 31, "refs.fa", 0, "Map each read's signal to a sequence you already know: the records of a FASTA file, found by read id, then by the file's base name, in SIGNAL order (reverse them yourself for --reverse and RNA). The best path of the read's transition scores through its sequence is made on the GPU and written to --remap-out; stdout does not change"},
     {"remap-out", 256, "map.tsv", 0, "With --remap: one line per read that had a record: name, status (1 mapped, 2 not: a letter outside the model's alphabet, or more bases than blocks + 1), nblock, stride, trim_start, L, band, maxdev, score and the block every base starts at"},
     {"remap-band", 257, "W", 0, "With --remap: the band's half-width in sequence positions around the straight line from (0, 0) to (nblock, L - 1) (0-2303, default 2048: the GPU holds a window of at most 2 W + 1 <= 4608 positions; maxdev = W in map.tsv says the band was touched)"},
+    {"remap-events", 261, "events.tsv", 0, "With --remap: the signal under every base of every mapped read, made on the GPU from the mapping and the read's normalised signal: one line per base, reads in output order and bases in signal order, no header: name, base index, base letter, first raw sample, samples, mean and standard deviation (population form; a base without samples has 0 for both)"},
     {"truth", 258, "refs.fa", 0, "Score each read's call against the sequence it should have been: the records of a FASTA file, found as for --remap (the same file may serve both), in SIGNAL order. The whole call is aligned to its record on the GPU (banded global edit distance) and the result written to --truth-out; stdout does not change. The alignment is always of the whole call in signal order: --reverse and --trim-barcodes do not alter it"},
     {"truth-out", 259, "acc.tsv", 0, "With --truth (required): one line per read that had a record: name, status (1 aligned, 2 not: an empty record, a letter outside the model's alphabet, or a band that leaves no path), n, m, band, maxdev, dist, matches, mismatches, insertions, deletions, identity and the extended CIGAR (=XID)"},
     {"truth-band", 260, "W", 0, "With --truth: the band's half-width in called bases around the straight line from (0, 0) to (m, n) (0-1279, default 512: the GPU holds a window of at most 2 W + 1 <= 2560 cells; maxdev = W in acc.tsv says the band was touched)"},
@@ -106,6 +107,7 @@ static struct argp_option options[] = {
     {"barcodes", 25, "kit.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"remap", 31, "refs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"truth", 258, "refs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"remap-events", 261, "events.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
 #endif
     {0}
 };
@@ -146,13 +148,14 @@ static struct {
     int bc_window, bc_max_dist, bc_min_sep;
     bool bc_both, bc_trim, bc_opts;     /* bc_opts: one of the other barcode options was given */
     char *remap, *remap_out;            /* flappie: --remap refs file, --remap-out table; the band's half-width */
+    char *remap_events;                 /* ... and --remap-events table */
     int remap_band;
     bool remap_band_set;
     char *truth, *truth_out;            /* flappie: --truth refs file, --truth-out table; the band's half-width */
     int truth_band;
     bool truth_band_set;
 } args = { 1, 200, 0.0f, NULL, FLAPPIE_OUTFORMAT_FASTQ, 0, DEFAULT_MODEL, NULL, "", false, 1.0f, 200, 10, 100, 0.0f, false, NULL, true, 0, 4, 0, 0, false, false, false, false,
-           { 1.02, 1.04, 1.04, 1.02 }, false, false, NULL, 150, -1, -1, false, false, false, NULL, NULL, 2048, false, NULL, NULL, FLAPPIE_TRUTH_BAND_DEFAULT, false };      /* batch 0: by model (below); nshard 0: --shard not given */
+           { 1.02, 1.04, 1.04, 1.02 }, false, false, NULL, 150, -1, -1, false, false, false, NULL, NULL, NULL, 2048, false, NULL, NULL, FLAPPIE_TRUTH_BAND_DEFAULT, false };      /* batch 0: by model (below); nshard 0: --shard not given */
 
 static void print_models(FILE *fh) {
     for (int mdl = 0; mdl < (int)flappie_nmodel; mdl++)
@@ -265,6 +268,7 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
     case 25: args.barcodes = arg; break;
     case 31: args.remap = arg; break;
     case 258: args.truth = arg; break;
+    case 261: args.remap_events = arg; break;
 #ifndef BUILD_RUNNIE
     case 256: args.remap_out = arg; break;      /* (keys above UCHAR_MAX: argp makes a short option of a printable one) */
     case 257: {
@@ -444,6 +448,7 @@ typedef struct {
     size_t rm_L, rm_nblock;
     float rm_score;
     uint8_t *rm;                        /* ... its moves (owned; NULL unless mapped) */
+    ffhip_event *ev;                    /* --remap-events: its rm_L events (owned; NULL unless mapped) */
     int tr_ref, have_tr;                /* --truth: the read's record of the truths (-1: none), and what the batch returned for it */
     flappie_truth_rec tr;
     uint8_t *tr_ops;                    /* ... its ops (owned; NULL unless aligned) */
@@ -522,6 +527,14 @@ static unsigned long long bc_count[FLAPPIE_BARCODE_MAX_KIT + 1];
 static flappie_remap_refs *rm_refs = NULL;
 static FILE *rm_out = NULL;
 static unsigned long long rm_count[4];
+/* flappie --remap-events: the table, and the summary's counts: reads and bases written */
+static FILE *ev_out = NULL;
+static unsigned long long ev_count[2];
+/* --remap-events: a mapped read's lines of events.tsv: name, base index, base letter, first raw sample, samples, mean, sd */
+static void write_events(FILE *out, const char *name, const uint8_t *codes, const char *alphabet, size_t trim_start, const ffhip_event *ev, size_t L) {
+    for (size_t i = 0; i < L; i++)
+        fprintf(out, "%s\t%zu\t%c\t%zu\t%d\t%.9g\t%.9g\n", name, i, alphabet[codes[i]], trim_start + (size_t)ev[i].first, (int)ev[i].count, (double)ev[i].mean, (double)ev[i].sd);
+}
 /* flappie --truth: the truths, the table, and the summary */
 static flappie_remap_refs *tr_refs = NULL;
 static FILE *tr_out = NULL;
@@ -538,7 +551,8 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
  * --barcodes: the reads' barcode records do (FFHIP_RUN_BARCODES) */
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u) |
-           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | (tr_refs ? FFHIP_RUN_TRUTH : 0u);
+           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | (tr_refs ? FFHIP_RUN_TRUTH : 0u) |
+           (ev_out ? FFHIP_RUN_EVENTS : 0u);
 }
 /* --remap: every read's record, by its read id, then by its file's base name; a bad record goes as a sequence of no bases (status 2) */
 static int batch_set_remap(ffhip_batch *b, item **its, int n) {
@@ -851,6 +865,12 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
                 its[i]->have_rm = 1; its[i]->rm_status = rc.status; its[i]->rm_L = rc.L; its[i]->rm_nblock = rc.nblock; its[i]->rm_score = rc.score;
                 if (1 == rc.status && NULL != (its[i]->rm = malloc(rc.nblock ? rc.nblock : 1))) memcpy(its[i]->rm, rc.rm, rc.nblock);
                 its[i]->mv_stride = (int)ffhip_model_stride(mdl);
+                if (ev_out && 1 == rc.status) {                /* ... and the signal under its bases */
+                    const ffhip_event *ev = NULL;
+                    size_t nev = 0;
+                    if (0 != ffhip_batch_events(b, i, &ev, &nev) || NULL == ev || nev != rc.L) warnx("No events returned for %s: %s", its[i]->filename, ffhip_last_error());
+                    else if (NULL != (its[i]->ev = malloc(nev * sizeof(ffhip_event)))) memcpy(its[i]->ev, ev, nev * sizeof(ffhip_event));
+                }
             }
         }
         if (tr_refs && its[i]->tr_ref >= 0) {                  /* the call against its truth, in signal order whatever --reverse does below */
@@ -1049,6 +1069,13 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
                                                               args.remap_band, it->rm, it->rm_score);
                     if (dev < 0) warnx("The moves of %s do not fit its sequence", it->filename);
                     if (1 == it->rm_status) { rm_count[0]++; if (dev == (long)args.remap_band) rm_count[3]++; } else rm_count[2]++;
+                    if (ev_out && 1 == it->rm_status) {
+                        if (NULL == it->ev || it->rm_L != L) warnx("No events for %s", it->filename);
+                        else {
+                            write_events(ev_out, rm_refs->name[it->rm_ref], rm_refs->codes[it->rm_ref], "ACGTZ", it->res.rt.start, it->ev, L);
+                            ev_count[0]++; ev_count[1] += L;
+                        }
+                    }
                 }
             }
             if (tr_refs) {                                     /* likewise for --truth */
@@ -1078,6 +1105,8 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
         it->have_bc = 0;
         free(it->rm);
         it->rm = NULL;
+        free(it->ev);
+        it->ev = NULL;
         it->have_rm = 0;
         it->rm_ref = -1;
         free(it->tr_ops);
@@ -1789,6 +1818,7 @@ int main(int argc, char *argv[]) {
     if (args.barcodes) errx(EXIT_FAILURE, "--barcodes is flappie's: the run-length model's records carry no base strings to search");
     if (args.remap) errx(EXIT_FAILURE, "--remap is flappie's: the run-length model's scores are not transitions between the bases of a sequence");
     if (args.truth) errx(EXIT_FAILURE, "--truth is flappie's: the run-length model's call is a list of runs");
+    if (args.remap_events) errx(EXIT_FAILURE, "--remap-events is flappie's: it goes with --remap, which the run-length model does not have");
 #else
     /* --barcodes: every refusal before any file or the GPU is touched */
     if (args.bc_opts && NULL == args.barcodes) errx(EXIT_FAILURE, "--barcode-window, --barcode-max-dist, --barcode-min-sep, --barcode-both-ends and --trim-barcodes go with --barcodes");
@@ -1802,6 +1832,7 @@ int main(int argc, char *argv[]) {
     /* --remap: likewise */
     if ((NULL == args.remap) != (NULL == args.remap_out)) errx(EXIT_FAILURE, "--remap and --remap-out go together");
     if (args.remap_band_set && NULL == args.remap) errx(EXIT_FAILURE, "--remap-band goes with --remap");
+    if (args.remap_events && NULL == args.remap) errx(EXIT_FAILURE, "--remap-events goes with --remap");
     if (args.remap) {
         char why[256];
         rm_refs = flappie_remap_refs_read(args.remap, flappie_model_has_modbase(args.model) ? "ACGTZ" : "ACGT", why, sizeof why);
@@ -1809,6 +1840,7 @@ int main(int argc, char *argv[]) {
         for (int k = 0; k < rm_refs->n; k++)
             if (rm_refs->bad[k]) warnx("--remap: record %s holds a letter outside the model's alphabet: its read is not mapped (status 2)", rm_refs->name[k]);
         if (NULL == (rm_out = fopen(args.remap_out, "w"))) errx(EXIT_FAILURE, "--remap-out %s: cannot be written", args.remap_out);
+        if (args.remap_events && NULL == (ev_out = fopen(args.remap_events, "w"))) errx(EXIT_FAILURE, "--remap-events %s: cannot be written", args.remap_events);
     }
     /* --truth: likewise */
     if ((NULL == args.truth) != (NULL == args.truth_out)) errx(EXIT_FAILURE, "--truth and --truth-out go together");
@@ -1921,6 +1953,10 @@ int main(int argc, char *argv[]) {
     if (rm_refs) {                     /* mapped, no record, refused, and the mapped reads whose path touched the band */
         fprintf(stderr, "remap\tmapped\t%llu\nremap\tno_record\t%llu\nremap\trefused\t%llu\nremap\tband_touched\t%llu\n", rm_count[0], rm_count[1], rm_count[2], rm_count[3]);
         if (0 != fclose(rm_out)) warnx("--remap-out %s: write failed", args.remap_out);
+        if (ev_out) {                  /* mapped reads written, and their bases */
+            fprintf(stderr, "events\treads\t%llu\nevents\tbases\t%llu\n", ev_count[0], ev_count[1]);
+            if (0 != fclose(ev_out)) warnx("--remap-events %s: write failed", args.remap_events);
+        }
         flappie_remap_refs_free(rm_refs);
     }
     if (tr_refs) {                     /* reads aligned, not aligned, without a record, the pooled and the median identity */

@@ -111,6 +111,12 @@ typedef struct {
  * block: they live in ONE buffer of their own (reads x 48 bytes, then the ops) and come down in ONE extra copy, enqueued where the result block's copy is.
  * Everything else the run returns is that of the same run without the flag.  No truths set, the run-length model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
 #define FFHIP_RUN_TRUTH      65536u
+/* With FFHIP_RUN_REMAP: the signal of every base of every mapped read (ffhip_batch_events below, "events"): first sample, sample count, mean and standard deviation,
+ * made on the device (k_events) behind k_remap from the path it has just written and the signal the batch was given.  The events are NOT part of the result
+ * block: they live in ONE buffer of their own (16 bytes a base, one read behind the other) and come down in ONE extra copy, enqueued where the remap buffer's copy
+ * is.  Everything else the run returns is that of the same run without the flag.  Without FFHIP_RUN_REMAP: FFHIP_EINVAL; the run-length model and
+ * FFHIP_RUN_NO_DECODE are refused as for remap. */
+#define FFHIP_RUN_EVENTS     131072u
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -439,6 +445,26 @@ int ffhip_batch_remap(const ffhip_batch *b, int read, ffhip_remap_call *out);
 int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, int band, uint8_t *rm /* nblock */, float *score);
 /* the kernel form a sequence of L bases takes at this band: 0, 1 one wave (windows up to 64, 256 cells), 2, 3 a workgroup (up to 1024, 4608 cells); -1: none */
 int ffhip_debug_remap_form(size_t L, int band);
+/* Events: the signal under every base of a mapped read -- what resquiggle tables, eventalign and comparisons of two samples' levels start from.
+ *   Inputs: the read's prepared signal x[0 .. n - 1], float32 -- exactly what the batch was given with any ffhip_batch_set_* call, i.e. what the first convolution
+ *     reads; the model's stride (samples a block); the read's N blocks and its remap path rm[0 .. N - 1] with its L, remap status 1.
+ *   Spans: start[0] = 0, start[i] = 1 + (index of the i-th one in rm) as above, start[L] = N.  Base i covers the samples [s_i, e_i),
+ *     s_i = min(start[i] stride, n), e_i = min(start[i + 1] stride, n), count_i = e_i - s_i.  count_i may be 0: with L = N + 1 the last base has no block, and the
+ *     last block may lie past n where the chain of ceilings that gives N rounds up.
+ *   Event of base i: the 16 bytes { int32 first = s_i; int32 count = count_i; float mean; float sd; }.  count = 0: mean = sd = 0.  Otherwise, in fp64 and in two
+ *     passes, mean = (sum x_k) / count and sd = sqrt((sum (x_k - mean)^2) / count) over the span -- the population form -- each rounded to float32 once at the end.
+ *     The order of the sums is the kernel's, and a function of the span's sample count only: a read's events are the same bytes in a one-read-a-row, ragged, packed,
+ *     paired, launch-per-step or f32-rerun batch and from one run to the next.  No floating-point atomics, and no one-pass form with a sum of squares: a span of one
+ *     repeated value has mean = that value and sd = 0.0 exactly.  first counts from the prepared signal's first sample (add the read's trim_start for raw samples).
+ * ffhip_batch_events: after ffhip_batch_finish of a run with FFHIP_RUN_REMAP | FFHIP_RUN_EVENTS; *ev points into the batch (*L events, base after base, valid until
+ *   the next run); *ev = NULL and *L = 0 unless the read's remap status is 1.
+ * ffhip_op_events: the kernel on ONE read from host arrays: nsample samples (0 is allowed), nblock bytes of 0 / 1 and L; out: caller-owned, L events.
+ *   sum rm != L - 1, a byte > 1, L = 0, stride < 1, nblock = 0 or more than 2^30 of either: FFHIP_EINVAL.
+ * The events' buffer and its pinned mirror are sized at the front of every run with the flag from the L of ffhip_batch_set_remap, grown when a run needs more, freed
+ * with the batch and counted by ffhip_debug_batch_device_bytes; when one cannot be had: FFHIP_ENOMEM with the bytes in the text. */
+typedef struct { int32_t first, count; float mean, sd; } ffhip_event;      /* 16 bytes */
+int ffhip_batch_events(const ffhip_batch *b, int read, const ffhip_event **ev, size_t *L);
+int ffhip_op_events(ffhip_engine *eng, const float *signal, size_t nsample, int stride, const uint8_t *rm, size_t nblock, size_t L, ffhip_event *out /* L */);
 /* Truth: how close a call is to the sequence it should have been.
  *   Inputs: the call s of n >= 0 bases -- the batch's called letters in signal order, Z read as C (as the barcode search reads it); the truth t of m bases as codes
  *     0 .. nbase - 1, code 4 (Z) folded to 1 (C) for the comparison; the band half-width W >= 0.
