@@ -36,6 +36,8 @@ RUN_REMAP = 32768         # flip-flop model: each read's signal mapped to the se
 RUN_TRUTH = 65536         # flip-flop model: each read's call aligned to the truth of Batch.set_truth on the device (Batch.truth)
 RUN_EVENTS = 131072       # with RUN_REMAP: first sample, count, mean and sd of every base of every mapped read, made on the device (Batch.events)
 EVENT_DTYPE = np.dtype([("first", np.int32), ("count", np.int32), ("mean", np.float32), ("sd", np.float32)])      # ffhip_event (include/ffhip.h)
+RUN_REMAP_MODS = 262144   # with RUN_REMAP, a model of the alphabet ACGTZ: the log scores with C and with Z at every C / Z of every mapped sequence, made on the device (Batch.site_mods)
+SITE_MOD_DTYPE = np.dtype([("pos", np.int32), ("nblock", np.int32), ("can", np.float32), ("mod", np.float32)])      # ffhip_site_mod (include/ffhip.h)
 TRUTH_BAND_MAX = 1279     # the widest kernel form holds a window of 2 W + 1 <= 2560 cells
 TRUTH_FIELDS = ("status", "n", "m", "dist", "n_match", "n_mismatch", "n_ins", "n_del", "maxdev")
 # ffhip_debug_gate_math forms (include/ffhip.h)
@@ -227,6 +229,9 @@ def lib():
     L.ffhip_debug_remap_form.argtypes = [C.c_size_t, C.c_int]
     L.ffhip_batch_events.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.ffhip_op_events.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_size_t, vp]
+    L.ffhip_batch_set_remap_mods.argtypes = [vp, C.c_int, C.c_int]
+    L.ffhip_batch_site_mods.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ffhip_op_site_mods.argtypes = [vp, CFMat, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.c_int, vp, C.POINTER(C.c_size_t)]
     L.ffhip_batch_set_truth.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t), C.c_int]
     L.ffhip_batch_truth.argtypes = [vp, C.c_int, C.POINTER(CTruthCall)]
     L.ffhip_op_truth.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.POINTER(CTruthCall), C.POINTER(C.c_uint8)]
@@ -622,6 +627,18 @@ class Batch:
             return None
         return np.frombuffer(C.string_at(ev.value, n.value * EVENT_DTYPE.itemsize), dtype=EVENT_DTYPE).copy()
 
+    def set_remap_mods(self, context: int = 15, all_paths: bool = False):
+        """the context (0 .. 31 positions either side of a site) and the mode (best path, or all paths in fp64) of later runs with RUN_REMAP_MODS (ffhip_batch_set_remap_mods)"""
+        _check(lib().ffhip_batch_set_remap_mods(self.h, int(context), 1 if all_paths else 0))
+
+    def site_mods(self, read: int):
+        """site mods of a run with RUN_REMAP | RUN_REMAP_MODS (ffhip_batch_site_mods): a structured array (SITE_MOD_DTYPE), one entry a C / Z of the read's sequence in increasing pos; None unless the read's remap status is 1"""
+        sm, n = C.c_void_p(), C.c_size_t()
+        _check(lib().ffhip_batch_site_mods(self.h, read, C.byref(sm), C.byref(n)))
+        if not sm.value:
+            return None
+        return np.frombuffer(C.string_at(sm.value, n.value * SITE_MOD_DTYPE.itemsize), dtype=SITE_MOD_DTYPE).copy()
+
     def set_truth(self, seqs, band: int = 512):
         """the truths and band of later runs with RUN_TRUTH (ffhip_batch_set_truth): one entry a read, None (no truth) or codes 0 .. nbase - 1 in signal order; seqs None detaches"""
         if seqs is None:
@@ -813,6 +830,25 @@ def op_events(engine: Engine, signal, stride: int, rm, L: int) -> np.ndarray:
     _check(lib().ffhip_op_events(engine.h, (x if x.size else np.zeros(1, np.float32)).ctypes.data_as(C.POINTER(C.c_float)), x.size, int(stride),
                                  (m if m.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), m.size, int(L), out.ctypes.data_as(C.c_void_p)))
     return out[:int(L)]
+
+
+def op_site_mods(engine: Engine, trans: np.ndarray, nbase: int, codes, rm, context: int = 15, all_paths: bool = False, stride: int = 0) -> np.ndarray:
+    """ffhip_op_site_mods: the site mods (SITE_MOD_DTYPE, one entry a C / Z of `codes`) of ONE read from its transition scores `trans` [nblock][nstate (nbase + 1)],
+    its sequence and its remap path rm (uint8, a byte a block); stride > trans.shape[1]: the matrix is handed over with that many floats a block"""
+    t = np.ascontiguousarray(trans, dtype=np.float32)
+    nparam = t.shape[1] if t.ndim == 2 else 0
+    if stride > nparam and t.ndim == 2:
+        wide = np.full((t.shape[0], int(stride)), np.float32(np.nan))      # (the padding is never read)
+        wide[:, :nparam] = t
+        t = wide
+    q = np.ascontiguousarray(codes, dtype=np.uint8)
+    m = np.ascontiguousarray(rm, dtype=np.uint8)
+    out, n = np.zeros(max(1, q.size), SITE_MOD_DTYPE), C.c_size_t(0)
+    _check(lib().ffhip_op_site_mods(engine.h, CFMat(_fptr(t), nparam, t.shape[0], t.shape[1] if t.ndim == 2 else 0), int(nbase),
+                                    (q if q.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), q.size,
+                                    (m if m.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), m.size, int(context), 1 if all_paths else 0,
+                                    out.ctypes.data_as(C.c_void_p), C.byref(n)))
+    return out[:n.value]
 
 
 def _truth_dict(c, ops) -> dict:

@@ -795,6 +795,16 @@ struct ffhip_batch {
     uint8_t *evt_dev = nullptr, *evt_host = nullptr; size_t evt_dev_cap = 0, evt_host_cap = 0;
     int evt_valid = 0, evt_count = 0;
     size_t evt_bytes() const { return (evt_off.empty() ? 0 : evt_off.back()) * sizeof(ffhip_event); }
+    // Site mods (FFHIP_RUN_REMAP_MODS with FFHIP_RUN_REMAP, k_site_mods): ONE buffer of 16 bytes a C / Z of every read with a sequence that can be mapped, one read
+    // behind the other (smd_dev, its pinned mirror smd_host), with one copy of its own beside the remap buffer's; the workspace of starts (L + 1 int32 a listed
+    // read) and the lists (the reads, then the sites: one pinned image, one upload) grow with the sequences too
+    std::vector<size_t> smd_off;                            // per read: its first site, and (one more entry) the end
+    uint8_t *smd_dlist = nullptr, *smd_hlist = nullptr; size_t smd_dlist_cap = 0, smd_hlist_cap = 0;
+    int *smd_start = nullptr; size_t smd_start_cap = 0;
+    uint8_t *smd_dev = nullptr, *smd_host = nullptr; size_t smd_dev_cap = 0, smd_host_cap = 0;
+    int smd_valid = 0, smd_reads = 0, smd_context = 15, smd_all = 0;
+    size_t smd_nsite() const { return smd_off.empty() ? 0 : smd_off.back(); }
+    size_t smd_bytes() const { return smd_nsite() * sizeof(ffhip_site_mod); }
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
     std::vector<void *> owned;
     unsigned last_flags = 0;
@@ -897,6 +907,8 @@ extern "C" void ffhip_batch_destroy(ffhip_batch *b) {
     if (b->tru_hlist) hipHostFree(b->tru_hlist);
     if (b->evt_host) hipHostFree(b->evt_host);
     if (b->evt_hlist) hipHostFree(b->evt_hlist);
+    if (b->smd_host) hipHostFree(b->smd_host);
+    if (b->smd_hlist) hipHostFree(b->smd_hlist);
     if (b->side) ffhip_batch_destroy(b->side);
     prof_unlink(b);
     if (b->have_ev) {
@@ -1616,6 +1628,62 @@ static void events_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {
     b->evt_valid = 1;
 }
 
+// Site mods, the front's share, behind remap's: the reads that have a C or Z and can be mapped, their sites one read behind the other (a site's place in the list is
+// its record's place in the buffer), every read's L + 1 words of starts; the buffers and their mirrors grow here.  A read remap_prepare refuses has no entry.
+static_assert(sizeof(SiteRead) == 24 && sizeof(SiteMod) == 8 && sizeof(ffhip_site_mod) == 16, "the lists are copied as they stand; k_site_mods writes a record as one 16-byte store");
+static int pinned_grow(ffhip_batch *b, uint8_t **p, size_t *cap, size_t need, const char *what) {
+    if (*p && need <= *cap) return FFHIP_OK;
+    if (*p) { HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP); hipHostFree(*p); *p = nullptr; *cap = 0; }
+    if (hipHostMalloc((void **)p, need, hipHostMallocDefault) != hipSuccess) {
+        *p = nullptr; return set_err(FFHIP_ENOMEM, "%s take %zu bytes of pinned host memory, which could not be had", what, need);
+    }
+    *cap = need;
+    memset(*p, 0, need);
+    return FFHIP_OK;
+}
+static int sitemods_prepare(ffhip_batch *b) {
+    const int nR = b->packed ? b->nvirt : b->nread;
+    std::vector<size_t> off((size_t)nR + 1, 0);
+    std::vector<SiteRead> list;
+    std::vector<SiteMod> sites;
+    size_t words = 0, seq = 0;
+    for (int r = 0; r < nR; r++) {
+        const int N = b->hTb[r], L = (int)b->rmp_seq[r].size();
+        off[r] = sites.size();
+        if (b->rmp_state[r] == 1 && N >= 1 && L >= 1 && L <= N + 1 && sitemods_sites(b->rmp_seq[r].data(), (size_t)L, (int)list.size(), &sites)) {
+            list.push_back(SiteRead{ words, (unsigned)seq, L, r, 0 });
+            words += (size_t)L + 1;
+        }
+        seq += (size_t)L;
+    }
+    off[nR] = sites.size();
+    if (sites.size() > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "site mods: %zu sites in one batch", sites.size());
+    const size_t bytes = std::max<size_t>(sites.size(), 1) * sizeof(ffhip_site_mod);
+    const size_t lb = list.size() * sizeof(SiteRead), lbytes = std::max<size_t>(lb + sites.size() * sizeof(SiteMod), 8);
+    if (int rc = dgrow(b, (void **)&b->smd_dev, &b->smd_dev_cap, bytes, "site mods: the sites' records")) return rc;
+    if (int rc = dgrow(b, (void **)&b->smd_start, &b->smd_start_cap, std::max<size_t>(words, 1) * 4, "site mods: the workspace of starts")) return rc;
+    if (int rc = dgrow(b, (void **)&b->smd_dlist, &b->smd_dlist_cap, lbytes, "site mods: the lists of reads and sites")) return rc;
+    if (int rc = pinned_grow(b, &b->smd_host, &b->smd_host_cap, bytes, "site mods: the sites' records")) return rc;
+    if (int rc = pinned_grow(b, &b->smd_hlist, &b->smd_hlist_cap, lbytes, "site mods: the lists of reads and sites")) return rc;
+    b->smd_off = std::move(off);
+    b->smd_reads = (int)list.size();
+    if (!sites.empty()) {
+        memcpy(b->smd_hlist, list.data(), lb);
+        memcpy(b->smd_hlist + lb, sites.data(), sites.size() * sizeof(SiteMod));
+        HIP_TRY(hipMemcpyAsync(b->smd_dlist, b->smd_hlist, lb + sites.size() * sizeof(SiteMod), hipMemcpyHostToDevice, b->stream), FFHIP_EHIP);
+    }
+    return FFHIP_OK;
+}
+static void sitemods_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {
+    if (b->smd_nsite() > 0) {
+        launch_site_mods(b->stream, (const SiteRead *)b->smd_dlist, b->smd_reads, (const SiteMod *)(b->smd_dlist + (size_t)b->smd_reads * sizeof(SiteRead)), (int)b->smd_nsite(),
+                         b->rmp_dseq, b->trans, b->mdl->Ps, b->smd_context, b->smd_all, b->rmp_dev, b->rmp_dev + (size_t)b->cap_reads * 16, b->smd_start, b->smd_dev,
+                         b->Tb, tbr, rmap);
+        b->launches[5] += 2;
+    }
+    b->smd_valid = 1;
+}
+
 // Truth, the front's share: as remap's.  The ops' bytes follow from the truths and the reads' blocks, so records and ops grow here too (device and pinned host).
 static_assert(sizeof(TruthRead) == 40, "the reads' list is copied as it stands");
 static int truth_prepare(ffhip_batch *b) {
@@ -1716,6 +1784,12 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
     if (flags & FFHIP_RUN_EVENTS) {        // (remap's checks have passed)
         if (!(flags & FFHIP_RUN_REMAP)) return set_err(FFHIP_EINVAL, "events: the signal of a mapped read's bases needs the mapping (FFHIP_RUN_EVENTS goes with FFHIP_RUN_REMAP)");
         if (int rc = events_prepare(b)) return rc;
+    }
+    b->smd_valid = 0;
+    if (flags & FFHIP_RUN_REMAP_MODS) {    // (likewise)
+        if (!(flags & FFHIP_RUN_REMAP)) return set_err(FFHIP_EINVAL, "site mods: the scores of a mapped sequence's C positions need the mapping (FFHIP_RUN_REMAP_MODS goes with FFHIP_RUN_REMAP)");
+        if (m->nbase != 5) return set_err(FFHIP_EINVAL, "site mods: the model has no modified base (FFHIP_RUN_REMAP_MODS takes a model of the alphabet ACGTZ)");
+        if (int rc = sitemods_prepare(b)) return rc;
     }
     b->tru_valid = 0;
     if (flags & FFHIP_RUN_TRUTH) {         // (nor this)
@@ -2014,6 +2088,7 @@ static int run_back(ffhip_batch *b) {
             if (flags & FFHIP_RUN_TRUTH) truth_launch(b, tbr, rmap);          // from the strings and lengths too (run_front made the lists)
             if (flags & FFHIP_RUN_REMAP) remap_launch(b, nR, tbr, rmap);      // from the transitions, whatever the path was decoded from (run_front made the lists)
             if (flags & FFHIP_RUN_EVENTS) events_launch(b, tbr, rmap);        // from the path k_remap has just written and the signal the convolutions read
+            if (flags & FFHIP_RUN_REMAP_MODS) sitemods_launch(b, tbr, rmap);  // from that path, the transitions and the coded sequences
             if (flags & FFHIP_RUN_MOD_PROBS) {          // from the posterior whatever decoded the path (run_front checked the model)
                 launch_mod_probs(s, b->post, b->path, b->res.on_dev<uint8_t>(RF_ML), nR, Tb, m->Ps, tbr, rmap);
                 b->launches[5]++;
@@ -2040,6 +2115,7 @@ static int run_back(ffhip_batch *b) {
         if (b->bc_valid) HIP_TRY(hipMemcpyAsync(b->bc_host, b->bc_dev, (size_t)nR * sizeof(ffhip_barcode_call), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the barcode records' one copy
         if (b->rmp_valid) HIP_TRY(hipMemcpyAsync(b->rmp_host, b->rmp_dev, b->rmp_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the remap records' and moves' one copy
         if (b->evt_valid && b->evt_bytes()) HIP_TRY(hipMemcpyAsync(b->evt_host, b->evt_dev, b->evt_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the events' one copy
+        if (b->smd_valid && b->smd_bytes()) HIP_TRY(hipMemcpyAsync(b->smd_host, b->smd_dev, b->smd_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the site mods' one copy
         if (b->tru_valid) HIP_TRY(hipMemcpyAsync(b->tru_host, b->tru_dev, b->tru_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the truth records' and ops' one copy
         b->res_copied = 1;
     }
@@ -2092,7 +2168,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
     const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
     b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
     b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0; b->rmp_valid = 0; b->tru_valid = 0; b->evt_valid = 0;
+    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0; b->rmp_valid = 0; b->tru_valid = 0; b->evt_valid = 0; b->smd_valid = 0;
     return FFHIP_OK;
 }
 
@@ -2184,6 +2260,7 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
             std::vector<signed char> st(16, 0);
             for (int k = 0; k < n; k++) { sq[k] = b->rmp_seq[reads[k0 + k]]; st[k] = b->rmp_state[reads[k0 + k]]; }
             if (int rc = remap_adopt(sd, std::move(sq), std::move(st), b->rmp_band)) return rc;
+            sd->smd_context = b->smd_context; sd->smd_all = b->smd_all;
         }
         if (fl & FFHIP_RUN_TRUTH) {                       // ... and truths
             std::vector<std::vector<uint8_t>> sq(16);
@@ -2232,6 +2309,14 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
                     memcpy(b->evt_host + to, sd->evt_host + from, ne);
                 }
             }
+            if (b->smd_valid && sd->smd_valid) {        // and its site mods (the same sequence: the same sites), both halves
+                const size_t ne = std::min(b->smd_off[r + 1] - b->smd_off[r], sd->smd_off[k + 1] - sd->smd_off[k]) * sizeof(ffhip_site_mod);
+                const size_t to = b->smd_off[r] * sizeof(ffhip_site_mod), from = sd->smd_off[k] * sizeof(ffhip_site_mod);
+                if (ne) {
+                    HIP_TRY(hipMemcpyAsync(b->smd_dev + to, sd->smd_dev + from, ne, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                    memcpy(b->smd_host + to, sd->smd_host + from, ne);
+                }
+            }
             if (b->tru_valid && sd->tru_valid) {        // and its truth record and ops (the same blocks and truth: the same bytes of ops), both halves
                 const size_t rb = (size_t)kTruthRecInts * 4, to = b->tru_rec_bytes() + b->tru_ops[r], from = sd->tru_rec_bytes() + sd->tru_ops[k];
                 const size_t ob = std::min(b->tru_ops[r + 1] - b->tru_ops[r], sd->tru_ops[k + 1] - sd->tru_ops[k]);
@@ -2269,6 +2354,8 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
             HIP_TRY(hipMemcpyAsync(b->rmp_host, b->rmp_dev, b->rmp_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
         if (b->evt_valid && b->evt_bytes())                  // the events' one copy (likewise)
             HIP_TRY(hipMemcpyAsync(b->evt_host, b->evt_dev, b->evt_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
+        if (b->smd_valid && b->smd_bytes())                  // the site mods' one copy (likewise)
+            HIP_TRY(hipMemcpyAsync(b->smd_host, b->smd_dev, b->smd_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
         if (b->tru_valid)                                    // the truth records' and ops' one copy (likewise)
             HIP_TRY(hipMemcpyAsync(b->tru_host, b->tru_dev, b->tru_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
     }
@@ -2481,6 +2568,27 @@ extern "C" int ffhip_batch_events(const ffhip_batch *b, int read, const ffhip_ev
     if ((size_t)rec[1] != b->evt_off[read + 1] - b->evt_off[read]) return set_err(FFHIP_EHIP, "events: read %d was mapped to %d bases, its events hold %zu", read, rec[1], b->evt_off[read + 1] - b->evt_off[read]);
     *ev = (const ffhip_event *)b->evt_host + b->evt_off[read];
     *L = (size_t)rec[1];
+    return FFHIP_OK;
+}
+
+// ---- site mods (include/ffhip.h "site mods"; the kernels: ffhip_sitemods.hip)
+extern "C" int ffhip_batch_set_remap_mods(ffhip_batch *b, int context, int all_paths) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "site mods: the batch is running (ffhip_batch_finish first)");
+    if (context < 0 || context > kSiteModsMaxContext) return set_err(FFHIP_EINVAL, "site mods: the context is %d (0 .. %d)", context, kSiteModsMaxContext);
+    b->smd_context = context; b->smd_all = all_paths ? 1 : 0;
+    return FFHIP_OK;
+}
+extern "C" int ffhip_batch_site_mods(const ffhip_batch *b, int read, const ffhip_site_mod **sm, size_t *nsite) {
+    if (!results_ok(b, read) || !sm || !nsite) return FFHIP_EINVAL;
+    if (!b->smd_valid || !b->rmp_valid || !b->smd_host) return set_err(FFHIP_EINVAL, "site mods were not made in this run (FFHIP_RUN_REMAP | FFHIP_RUN_REMAP_MODS)");
+    int rec[4];
+    memcpy(rec, b->rmp_host + (size_t)read * 16, 16);
+    *sm = nullptr; *nsite = 0;
+    if (rec[0] != 1) return FFHIP_OK;
+    if (rec[3] != 0) return set_err(FFHIP_EHIP, "remap: read %d's traceback ended at position %d, not 0", read, rec[3]);
+    *sm = (const ffhip_site_mod *)b->smd_host + b->smd_off[read];
+    *nsite = b->smd_off[read + 1] - b->smd_off[read];
     return FFHIP_OK;
 }
 

@@ -271,6 +271,21 @@ struct EventRead {
 };
 void launch_events(hipStream_t s, const EventRead *list, int count, const float *sig, int stride, const void *records, const uint8_t *rm, void *events,
                    int Tb, const int *tbs, ReadMap map);
+// 5mC at every C / Z of a mapped sequence (k_site_starts + k_site_mods, ffhip_sitemods.hip; include/ffhip.h "site mods"), a model of nbase 5 only: per listed site
+// whose read's remap record at records[read] says { status 1, end 0, L }, the 16 bytes { int32 pos, nblock; float can, mod } at out[site's index in `sites`], from
+// the read's score rows, its coded sequence (remap_code) and its bytes at the read's row of the (Tb + 1)-entry byte buffer `rm`; any other read writes nothing.
+// `starts` is the workspace of L + 1 int32 a listed read.  Two launches behind launch_remap on the same stream; all_paths picks the fp64 instantiation.
+struct SiteRead {
+    unsigned long long start;           // the read's first word in the workspace of starts
+    unsigned seq;                       // its first entry in the coded sequences
+    int L, read, pad;                   // the bases of its sequence; the read's index in the batch
+};
+struct SiteMod { int k, pos; };         // the site's read, as an index into the list of SiteRead; its position in the sequence
+constexpr int kSiteModsMaxContext = 31; // a window of 2 c + 1 <= 63 positions: a lane a position
+// the sites of one coded sequence, in increasing position (appended to *out with read index k when out is given); the count
+size_t sitemods_sites(const unsigned short *coded, size_t L, int k, std::vector<SiteMod> *out);
+void launch_site_mods(hipStream_t s, const SiteRead *list, int nread, const SiteMod *sites, int nsite, const unsigned short *seq, const float *trans, int Ps,
+                      int context, int all_paths, const void *records, const uint8_t *rm, int *starts, void *out, int Tb, const int *tbs, ReadMap map);
 // exp + trace_from_posterior
 void launch_trace(hipStream_t s, const float *post, int32_t *trace, int nread, int Tb, int nbase, int Ps, int is_log, const int *tbs = nullptr, ReadMap map = ReadMap());
 void launch_exp_inplace(hipStream_t s, float *x, size_t n);

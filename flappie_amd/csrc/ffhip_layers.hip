@@ -736,6 +736,47 @@ extern "C" int ffhip_op_events(ffhip_engine *eng, const float *signal, size_t ns
     return FFHIP_OK;
 }
 
+// the site mods of one read from its scores, its sequence and its path (k_site_starts + k_site_mods; include/ffhip.h "site mods")
+extern "C" int ffhip_op_site_mods(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, const uint8_t *rm, size_t nblock, int context, int all_paths,
+                                  ffhip_site_mod *out, size_t *nsite) {
+    OP_ENTER(eng);
+    if (nbase != 5) return set_err(FFHIP_EINVAL, "site mods: nbase is %d (a model of the alphabet ACGTZ: 5)", nbase);
+    if (!view_ok(trans) || !codes || !rm || !out || !nsite || trans.nr != (size_t)(2 * nbase * (nbase + 1)) || trans.stride % 4 != 0 || trans.stride > 2048)
+        return set_err(FFHIP_EINVAL, "bad site mods arguments (scores of 2 nbase (nbase + 1) rows, a sequence, a path of nblock bytes, records and their count)");
+    if (context < 0 || context > kSiteModsMaxContext) return set_err(FFHIP_EINVAL, "site mods: the context is %d (0 .. %d)", context, kSiteModsMaxContext);
+    if (nblock < 1 || nblock != trans.nc || L < 1 || nblock > (size_t)1 << 30)
+        return set_err(FFHIP_EINVAL, "site mods: %zu blocks of path, %zu of scores and %zu bases (the same 1 .. 2^30 blocks, L >= 1)", nblock, trans.nc, L);
+    size_t ones = 0;
+    for (size_t i = 0; i < nblock; i++) {
+        if (rm[i] > 1) return set_err(FFHIP_EINVAL, "site mods: block %zu of the path is %d (0 or 1)", i, (int)rm[i]);
+        ones += rm[i];
+    }
+    if (ones != L - 1) return set_err(FFHIP_EINVAL, "site mods: the path moves %zu times, a sequence of %zu bases takes %zu", ones, L, L - 1);
+    for (size_t i = 0; i < L; i++) if (codes[i] >= nbase) return set_err(FFHIP_EINVAL, "site mods: position %zu: code %d is not a base (0 .. %d)", i, (int)codes[i], nbase - 1);
+    std::vector<unsigned short> coded(L);
+    remap_code(codes, L, nbase, coded.data());
+    std::vector<SiteMod> sites;
+    *nsite = sitemods_sites(coded.data(), L, 0, &sites);
+    if (sites.empty()) return FFHIP_OK;
+    const SiteRead sr{ 0ull, 0u, (int)L, 0, 0 };
+    const unsigned rec[4] = { 1u, (unsigned)L, 0u, 0u };
+    float *d_t = upload_img(tmp, trans, s);
+    unsigned short *d_seq = (unsigned short *)tmp.upload(coded.data(), L * sizeof(unsigned short), s);
+    uint8_t *d_rm = (uint8_t *)tmp.upload(rm, nblock, s);
+    SiteRead *d_list = (SiteRead *)tmp.upload(&sr, sizeof sr, s);
+    SiteMod *d_sites = (SiteMod *)tmp.upload(sites.data(), sites.size() * sizeof(SiteMod), s);
+    void *d_rec = tmp.upload(rec, sizeof rec, s);
+    int *d_start = (int *)tmp.get((L + 1) * 4);
+    void *d_out = tmp.get(sites.size() * sizeof(ffhip_site_mod));
+    if (!d_start || !d_out) return set_err(FFHIP_ENOMEM, "site mods: the records and starts take %zu bytes of device memory, which could not be had", sites.size() * sizeof(ffhip_site_mod) + (L + 1) * 4);
+    if (!d_t || !d_seq || !d_rm || !d_list || !d_sites || !d_rec) OP_NOMEM();
+    launch_site_mods(s, d_list, 1, d_sites, (int)sites.size(), d_seq, d_t, (int)trans.stride, context, all_paths ? 1 : 0, d_rec, d_rm, d_start, d_out, (int)nblock, nullptr, ReadMap());
+    HIP_TRY(hipMemcpyAsync(out, d_out, sites.size() * sizeof(ffhip_site_mod), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    HIP_TRY(hipGetLastError(), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+
 // one call aligned to one truth (k_truth; include/ffhip.h "truth")
 extern "C" int ffhip_op_truth(ffhip_engine *eng, const char *call, size_t n, const uint8_t *truth, size_t m, int band, ffhip_truth_call *out, uint8_t *ops) {
     OP_ENTER(eng);

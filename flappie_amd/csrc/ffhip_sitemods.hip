@@ -1,0 +1,170 @@
+// ffhip_sitemods.hip -- 5mC at every C of a mapped sequence (FFHIP_RUN_REMAP_MODS, include/ffhip.h "site mods"): around every position i of the sequence that holds C
+// or Z, the blocks the mapping gave to the bases i - c .. i + c are scored twice through the transition scores, once with C and once with Z at i, every path of the
+// window's blocks through the window's bases allowed.  A few hundred small, independent dynamic programmes a read: wide parallel work on data that is resident when
+// k_remap is done (the scores, the coded sequences, the path's bytes).
+//
+// k_site_starts: one workgroup a listed read; start[0 .. L] (the block every base starts at, start[L] = N) from a prefix count of the path's bytes -- a ballot and a
+//   population count in a wave, four wave totals through LDS -- into the read's L + 1 words of the workspace.  A read whose remap record is not { status 1, end 0 }
+//   writes nothing.
+// k_site_mods<ALL>: one wave a site, kSmWaves sites a workgroup, no barrier and no LDS.  Lane j owns position lo + j of the window (P <= 63 positions) and carries the
+//   value of BOTH hypotheses in registers.  The hypothesis' flip-flop states come from the coding of s that the batch holds: positions before i keep theirs, position
+//   i takes the letter with the flip or flop that q_{i-1} leaves it, and the positions behind it are recoded one after the other, in a loop that is uniform in the
+//   wave and ends where the coding meets that of s again (the end of the run of equal letters).  A lane then knows the (at most) four entries of a block's score row
+//   it reads: stay and move of either hypothesis.  A step is, per hypothesis, one cross-lane move (the value of the lane below), two adds and one compare (best
+//   path, float32) or one log1p(exp()) (all paths, fp64); the two hypotheses are independent chains and fill each other's latency.  The rows are read through the
+//   cache, kSmChunk blocks ahead of the chain in registers: no step waits for memory.  What bounds a step is the chain cross-lane move -> add -> compare.
+//   The order of operations depends on the window alone: the same read gives the same bytes wherever it stands in a batch.  No atomics, no scratch.
+#include "ffhip_internal.hpp"
+#include <math.h>
+#include <type_traits>
+
+namespace ffhip {
+
+constexpr int kSmNT = 256;              // threads of either kernel's workgroup
+constexpr int kSmWaves = kSmNT / 64;    // sites a workgroup
+constexpr int kSmChunk = 8;             // blocks whose entries a lane holds ahead of the chain
+constexpr int kSmNbase = 5, kSmNs = 2 * kSmNbase, kSmOff = kSmNbase * kSmNs;      // the model with a modified base: ACGTZ
+
+// the flip-flop state of a coded position (remap_code's low byte is trans_lookup(q, q))
+__host__ __device__ __forceinline__ int sm_state(unsigned short e) { const int st = e & 255; return st < kSmOff ? st / (kSmNs + 1) : st - kSmOff; }
+__device__ __forceinline__ int sm_lookup(int from, int to) { return to < kSmNbase ? to * kSmNs + from : kSmOff + from; }
+// the state a letter takes behind state `prev` (prev < 0: the sequence's first position)
+__device__ __forceinline__ int sm_next(int prev, int letter) { return (prev >= 0 && prev % kSmNbase == letter && prev < kSmNbase) ? letter + kSmNbase : letter; }
+
+size_t sitemods_sites(const unsigned short *coded, size_t L, int k, std::vector<SiteMod> *out) {
+    size_t n = 0;
+    for (size_t i = 0; i < L; i++) {
+        const int letter = sm_state(coded[i]) % kSmNbase;
+        if (letter != 1 && letter != 4) continue;
+        if (out) out->push_back(SiteMod{ k, (int)i });
+        n++;
+    }
+    return n;
+}
+
+__global__ void __launch_bounds__(kSmNT)
+k_site_starts(const SiteRead *__restrict__ list, const uint4 *__restrict__ rec, const uint8_t *__restrict__ rm, int *__restrict__ starts, int TbS,
+              const int *__restrict__ tbs, ReadMap map) {
+    FFHIP_DECODE_PRIO_SET();
+    __shared__ int wsum[2][kSmWaves];
+    const SiteRead sr = list[blockIdx.x];
+    const int read = sr.read, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint4 rc = rec[read];
+    const int N = tbs ? tbs[read] : TbS, L = sr.L;
+    if (rc.x != 1u || rc.w != 0u || (int)rc.y != L || L < 1 || N < 1) return;      // not mapped: nothing is written
+    const uint8_t *m = rm + map.row1(read, TbS);
+    int *st = starts + sr.start;
+    if (tid == 0) { st[0] = 0; st[L] = N; }
+    int ones = 0;                                                               // ones in front of this round
+    for (int b0 = 0, par = 0; b0 < N; b0 += kSmNT, par ^= 1) {
+        const int b = b0 + tid;
+        const bool one = b < N && m[b] != 0;
+        const unsigned long long bal = __ballot(one);
+        if (lane == 0) wsum[par][wv] = __popcll(bal);
+        __syncthreads();                                                        // (two sets of totals: one barrier a round)
+        int before = ones, total = 0;
+#pragma unroll
+        for (int w = 0; w < kSmWaves; w++) { const int c = wsum[par][w]; before += w < wv ? c : 0; total += c; }
+        const int k = before + __popcll(bal & ((1ull << lane) - 1ull)) + 1;
+        if (one && k < L) st[k] = b + 1;
+        ones += total;
+    }
+}
+
+template <bool ALL>
+__global__ void __launch_bounds__(kSmNT)
+k_site_mods(const SiteRead *__restrict__ list, const SiteMod *__restrict__ sites, int nsite, const unsigned short *__restrict__ seq, const float *__restrict__ trans,
+            int Ps, int ctx, const uint4 *__restrict__ rec, const int *__restrict__ starts, int4 *__restrict__ out, int TbS, const int *__restrict__ tbs, ReadMap map) {
+    FFHIP_DECODE_PRIO_SET();
+    using real = typename std::conditional<ALL, double, float>::type;
+    const int lane = threadIdx.x & 63, site = blockIdx.x * kSmWaves + (threadIdx.x >> 6);
+    if (site >= nsite) return;                                                  // (a whole wave: the kernel has no barrier)
+    const SiteMod sm = sites[site];
+    const SiteRead sr = list[sm.k];
+    const int read = sr.read, L = sr.L, i = sm.pos;
+    const uint4 rc = rec[read];
+    const int N = tbs ? tbs[read] : TbS;
+    if (rc.x != 1u || rc.w != 0u || (int)rc.y != L || L < 1 || N < 1 || i < 0 || i >= L) return;
+    const int lo = max(0, i - ctx), hi = min(L - 1, i + ctx), P = hi - lo + 1;  // (ctx <= 31: P <= 63)
+    const int *st = starts + sr.start;
+    const int t0 = min(max(st[lo], 0), N);
+    const int t1 = min(max(hi < L - 1 ? st[hi + 1] - 1 : N, t0), N);           // (a path's starts give t0 <= t1 <= N; anything else reads no row outside the read)
+    const unsigned short *sq = seq + sr.seq;
+    const float *T = trans + map.row0(read, TbS) * (size_t)Ps;
+
+    // ---- the states of both hypotheses at this lane's position
+    const int pos = lo + lane;
+    const int q0 = lane < P ? sm_state(sq[pos]) : 0;                            // the coding of s itself
+    const int qb = i > 0 ? sm_state(sq[i - 1]) : -1;
+    int q[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        int prev = sm_next(qb, h ? 4 : 1);
+        int mine = pos == i ? prev : q0;
+        for (int p = i + 1; p <= hi; p++) {                                     // (uniform in the wave)
+            const int orig = __shfl(q0, p - lo, 64);
+            const int now = sm_next(prev, orig % kSmNbase);
+            if (now == orig) break;                                             // the coding of s from here on
+            mine = pos == p ? now : mine;
+            prev = now;
+        }
+        q[h] = mine;
+    }
+    int is[2], im[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const int below = __shfl_up(q[h], 1, 64);
+        is[h] = sm_lookup(q[h], q[h]);
+        im[h] = lane > 0 ? sm_lookup(below, q[h]) : 0;
+    }
+
+    // ---- the recursion
+    const real NEG = (real)-INFINITY;
+    real X[2] = { lane == 0 ? (real)0 : NEG, lane == 0 ? (real)0 : NEG };
+    auto load = [&](int t, float (&a)[kSmChunk][4]) {                           // (t < t1; a block past the window's last reads the last again, unused)
+#pragma unroll
+        for (int u = 0; u < kSmChunk; u++) {
+            const float *row = T + (size_t)min(t + u, t1 - 1) * Ps;
+            a[u][0] = row[is[0]]; a[u][1] = row[im[0]]; a[u][2] = row[is[1]]; a[u][3] = row[im[1]];
+        }
+    };
+    float cur[kSmChunk][4], nxt[kSmChunk][4];
+    if (t0 < t1) load(t0, cur);
+    for (int t = t0; t < t1; t += kSmChunk) {
+        const bool more = t + kSmChunk < t1;
+        if (more) load(t + kSmChunk, nxt);
+#pragma unroll
+        for (int u = 0; u < kSmChunk; u++) {
+            if (t + u < t1) {                                                   // (uniform)
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const real up = __shfl_up(X[h], 1, 64);
+                    const real stay = X[h] + (real)cur[u][2 * h];
+                    const real move = lane == 0 ? NEG : up + (real)cur[u][2 * h + 1];
+                    const real m = move > stay ? move : stay;
+                    if constexpr (ALL) X[h] = m == NEG ? NEG : m + log1p(exp(-fabs(stay - move)));
+                    else X[h] = m;
+                }
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int u = 0; u < kSmChunk; u++)
+#pragma unroll
+                for (int k = 0; k < 4; k++) cur[u][k] = nxt[u][k];
+        }
+    }
+    if (lane == P - 1) out[site] = make_int4(i, t1 - t0, __float_as_int((float)X[0]), __float_as_int((float)X[1]));
+}
+
+void launch_site_mods(hipStream_t s, const SiteRead *list, int nread, const SiteMod *sites, int nsite, const unsigned short *seq, const float *trans, int Ps,
+                      int context, int all_paths, const void *records, const uint8_t *rm, int *starts, void *out, int Tb, const int *tbs, ReadMap map) {
+    if (nread <= 0 || nsite <= 0) return;
+    const uint4 *rec = (const uint4 *)records;
+    hipLaunchKernelGGL(k_site_starts, dim3(nread), dim3(kSmNT), 0, s, list, rec, rm, starts, Tb, tbs, map);
+    const dim3 grid((nsite + kSmWaves - 1) / kSmWaves);
+    if (all_paths) hipLaunchKernelGGL((k_site_mods<true>), grid, dim3(kSmNT), 0, s, list, sites, nsite, seq, trans, Ps, context, rec, starts, (int4 *)out, Tb, tbs, map);
+    else hipLaunchKernelGGL((k_site_mods<false>), grid, dim3(kSmNT), 0, s, list, sites, nsite, seq, trans, Ps, context, rec, starts, (int4 *)out, Tb, tbs, map);
+}
+
+}  // namespace ffhip

@@ -38,6 +38,7 @@
 #include "../../include/flappie_common.h"
 #include "../../include/flappie_output.h"
 #include "../../include/flappie_modbase.h"
+#include "../../include/flappie_sitemods.h"
 #include "../../include/flappie_moves.h"
 #include "../../include/flappie_barcodes.h"
 #include "../../include/flappie_remap.h"
@@ -99,6 +100,9 @@ static struct argp_option options[] = {
     {"remap-out", 256, "map.tsv", 0, "With --remap: one line per read that had a record: name, status (1 mapped, 2 not: a letter outside the model's alphabet, or more bases than blocks + 1), nblock, stride, trim_start, L, band, maxdev, score and the block every base starts at"},
     {"remap-band", 257, "W", 0, "With --remap: the band's half-width in sequence positions around the straight line from (0, 0) to (nblock, L - 1) (0-2303, default 2048: the GPU holds a window of at most 2 W + 1 <= 4608 positions; maxdev = W in map.tsv says the band was touched)"},
     {"remap-events", 261, "events.tsv", 0, "With --remap: the signal under every base of every mapped read, made on the GPU from the mapping and the read's normalised signal: one line per base, reads in output order and bases in signal order, no header: name, base index, base letter, first raw sample, samples, mean and standard deviation (population form; a base without samples has 0 for both)"},
+    {"remap-mods", 262, "mods.tsv", 0, "With --remap, a model with a modified base (r941_5mC): at every C or Z of every mapped read's sequence, the log scores of the signal around it with C and with 5mC at that position, made on the GPU from the mapping and the read's transition scores: one line per site, reads in output order and sites in signal order, no header: name, position, the given letter, blocks of the window, score with C, score with 5mC, and their difference (the log-likelihood ratio; p(5mC) = 1 / (1 + exp(ratio)))"},
+    {"remap-mods-context", 263, "N", 0, "With --remap-mods: the bases either side of a site whose signal is scored (0-31, default 15)"},
+    {"remap-mods-all-paths", 264, 0, 0, "With --remap-mods: sum over all paths of the window in double precision instead of taking the best path"},
     {"truth", 258, "refs.fa", 0, "Score each read's call against the sequence it should have been: the records of a FASTA file, found as for --remap (the same file may serve both), in SIGNAL order. The whole call is aligned to its record on the GPU (banded global edit distance) and the result written to --truth-out; stdout does not change. The alignment is always of the whole call in signal order: --reverse and --trim-barcodes do not alter it"},
     {"truth-out", 259, "acc.tsv", 0, "With --truth (required): one line per read that had a record: name, status (1 aligned, 2 not: an empty record, a letter outside the model's alphabet, or a band that leaves no path), n, m, band, maxdev, dist, matches, mismatches, insertions, deletions, identity and the extended CIGAR (=XID)"},
     {"truth-band", 260, "W", 0, "With --truth: the band's half-width in called bases around the straight line from (0, 0) to (m, n) (0-1279, default 512: the GPU holds a window of at most 2 W + 1 <= 2560 cells; maxdev = W in acc.tsv says the band was touched)"},
@@ -108,6 +112,7 @@ static struct argp_option options[] = {
     {"remap", 31, "refs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"truth", 258, "refs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"remap-events", 261, "events.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"remap-mods", 262, "mods.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
 #endif
     {0}
 };
@@ -156,6 +161,13 @@ static struct {
     bool truth_band_set;
 } args = { 1, 200, 0.0f, NULL, FLAPPIE_OUTFORMAT_FASTQ, 0, DEFAULT_MODEL, NULL, "", false, 1.0f, 200, 10, 100, 0.0f, false, NULL, true, 0, 4, 0, 0, false, false, false, false,
            { 1.02, 1.04, 1.04, 1.02 }, false, false, NULL, 150, -1, -1, false, false, false, NULL, NULL, NULL, 2048, false, NULL, NULL, FLAPPIE_TRUTH_BAND_DEFAULT, false };      /* batch 0: by model (below); nshard 0: --shard not given */
+
+/* flappie: --remap-mods table, --remap-mods-context, --remap-mods-all-paths */
+static char *mods_path = NULL;
+#ifndef BUILD_RUNNIE
+static int mods_context = 15;
+static bool mods_context_set = false, mods_all_paths = false;
+#endif
 
 static void print_models(FILE *fh) {
     for (int mdl = 0; mdl < (int)flappie_nmodel; mdl++)
@@ -269,7 +281,16 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
     case 31: args.remap = arg; break;
     case 258: args.truth = arg; break;
     case 261: args.remap_events = arg; break;
+    case 262: mods_path = arg; break;
 #ifndef BUILD_RUNNIE
+    case 263: {
+        char *end = NULL;
+        const long c = strtol(arg, &end, 10);
+        if (end == arg || *end != '\0' || c < 0 || c > 31) errx(EXIT_FAILURE, "--remap-mods-context must be a whole number from 0 to 31");
+        mods_context = (int)c; mods_context_set = true;
+        break;
+    }
+    case 264: mods_all_paths = true; break;
     case 256: args.remap_out = arg; break;      /* (keys above UCHAR_MAX: argp makes a short option of a printable one) */
     case 257: {
         char *end = NULL;
@@ -449,6 +470,8 @@ typedef struct {
     float rm_score;
     uint8_t *rm;                        /* ... its moves (owned; NULL unless mapped) */
     ffhip_event *ev;                    /* --remap-events: its rm_L events (owned; NULL unless mapped) */
+    ffhip_site_mod *smods;               /* --remap-mods: its nsm site records (owned; NULL unless mapped) */
+    size_t nsmods;
     int tr_ref, have_tr;                /* --truth: the read's record of the truths (-1: none), and what the batch returned for it */
     flappie_truth_rec tr;
     uint8_t *tr_ops;                    /* ... its ops (owned; NULL unless aligned) */
@@ -535,6 +558,9 @@ static void write_events(FILE *out, const char *name, const uint8_t *codes, cons
     for (size_t i = 0; i < L; i++)
         fprintf(out, "%s\t%zu\t%c\t%zu\t%d\t%.9g\t%.9g\n", name, i, alphabet[codes[i]], trim_start + (size_t)ev[i].first, (int)ev[i].count, (double)ev[i].mean, (double)ev[i].sd);
 }
+/* flappie --remap-mods: the table, and the summary's counts: reads and sites written */
+static FILE *md_out = NULL;
+static unsigned long long md_count[2];
 /* flappie --truth: the truths, the table, and the summary */
 static flappie_remap_refs *tr_refs = NULL;
 static FILE *tr_out = NULL;
@@ -552,7 +578,7 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u) |
            (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | (tr_refs ? FFHIP_RUN_TRUTH : 0u) |
-           (ev_out ? FFHIP_RUN_EVENTS : 0u);
+           (ev_out ? FFHIP_RUN_EVENTS : 0u) | (md_out ? FFHIP_RUN_REMAP_MODS : 0u);
 }
 /* --remap: every read's record, by its read id, then by its file's base name; a bad record goes as a sequence of no bases (status 2) */
 static int batch_set_remap(ffhip_batch *b, item **its, int n) {
@@ -569,6 +595,7 @@ static int batch_set_remap(ffhip_batch *b, item **its, int n) {
         len[i] = bad ? 0 : rm_refs->len[k];
     }
     if (0 == rc) rc = ffhip_batch_set_remap(b, nb, codes, len, args.remap_band);
+    if (0 == rc && md_out) rc = ffhip_batch_set_remap_mods(b, mods_context, mods_all_paths ? 1 : 0);
     free(codes);
     free(len);
     return rc;
@@ -871,6 +898,12 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
                     if (0 != ffhip_batch_events(b, i, &ev, &nev) || NULL == ev || nev != rc.L) warnx("No events returned for %s: %s", its[i]->filename, ffhip_last_error());
                     else if (NULL != (its[i]->ev = malloc(nev * sizeof(ffhip_event)))) memcpy(its[i]->ev, ev, nev * sizeof(ffhip_event));
                 }
+                if (md_out && 1 == rc.status) {                /* ... and the scores at its C positions */
+                    const ffhip_site_mod *sm = NULL;
+                    size_t nsm = 0;
+                    if (0 != ffhip_batch_site_mods(b, i, &sm, &nsm) || NULL == sm) warnx("No site mods returned for %s: %s", its[i]->filename, ffhip_last_error());
+                    else if (NULL != (its[i]->smods = malloc((nsm ? nsm : 1) * sizeof(ffhip_site_mod)))) { memcpy(its[i]->smods, sm, nsm * sizeof(ffhip_site_mod)); its[i]->nsmods = nsm; }
+                }
             }
         }
         if (tr_refs && its[i]->tr_ref >= 0) {                  /* the call against its truth, in signal order whatever --reverse does below */
@@ -1076,6 +1109,12 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
                             ev_count[0]++; ev_count[1] += L;
                         }
                     }
+                    if (md_out && 1 == it->rm_status) {
+                        if (NULL == it->smods || it->rm_L != L) warnx("No site mods for %s", it->filename);
+                        else if (0 != flappie_sitemods_write(md_out, rm_refs->name[it->rm_ref], rm_refs->codes[it->rm_ref], L, "ACGTZ", it->smods, it->nsmods))
+                            warnx("The site mods of %s do not fit its sequence", it->filename);
+                        else { md_count[0]++; md_count[1] += it->nsmods; }
+                    }
                 }
             }
             if (tr_refs) {                                     /* likewise for --truth */
@@ -1107,6 +1146,9 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
         it->rm = NULL;
         free(it->ev);
         it->ev = NULL;
+        free(it->smods);
+        it->smods = NULL;
+        it->nsmods = 0;
         it->have_rm = 0;
         it->rm_ref = -1;
         free(it->tr_ops);
@@ -1819,6 +1861,7 @@ int main(int argc, char *argv[]) {
     if (args.remap) errx(EXIT_FAILURE, "--remap is flappie's: the run-length model's scores are not transitions between the bases of a sequence");
     if (args.truth) errx(EXIT_FAILURE, "--truth is flappie's: the run-length model's call is a list of runs");
     if (args.remap_events) errx(EXIT_FAILURE, "--remap-events is flappie's: it goes with --remap, which the run-length model does not have");
+    if (mods_path) errx(EXIT_FAILURE, "--remap-mods is flappie's: it goes with --remap, which the run-length model does not have");
 #else
     /* --barcodes: every refusal before any file or the GPU is touched */
     if (args.bc_opts && NULL == args.barcodes) errx(EXIT_FAILURE, "--barcode-window, --barcode-max-dist, --barcode-min-sep, --barcode-both-ends and --trim-barcodes go with --barcodes");
@@ -1833,6 +1876,10 @@ int main(int argc, char *argv[]) {
     if ((NULL == args.remap) != (NULL == args.remap_out)) errx(EXIT_FAILURE, "--remap and --remap-out go together");
     if (args.remap_band_set && NULL == args.remap) errx(EXIT_FAILURE, "--remap-band goes with --remap");
     if (args.remap_events && NULL == args.remap) errx(EXIT_FAILURE, "--remap-events goes with --remap");
+    if (mods_path && NULL == args.remap) errx(EXIT_FAILURE, "--remap-mods goes with --remap");
+    if ((mods_context_set || mods_all_paths) && NULL == mods_path) errx(EXIT_FAILURE, "--remap-mods-context and --remap-mods-all-paths go with --remap-mods");
+    if (mods_path && !flappie_model_has_modbase(args.model))      /* (the registry knows: before any file or the GPU is touched) */
+        errx(EXIT_FAILURE, "--remap-mods needs a model with a modified base (r941_5mC); \"%s\" has none", flappie_model_string(args.model));
     if (args.remap) {
         char why[256];
         rm_refs = flappie_remap_refs_read(args.remap, flappie_model_has_modbase(args.model) ? "ACGTZ" : "ACGT", why, sizeof why);
@@ -1841,6 +1888,7 @@ int main(int argc, char *argv[]) {
             if (rm_refs->bad[k]) warnx("--remap: record %s holds a letter outside the model's alphabet: its read is not mapped (status 2)", rm_refs->name[k]);
         if (NULL == (rm_out = fopen(args.remap_out, "w"))) errx(EXIT_FAILURE, "--remap-out %s: cannot be written", args.remap_out);
         if (args.remap_events && NULL == (ev_out = fopen(args.remap_events, "w"))) errx(EXIT_FAILURE, "--remap-events %s: cannot be written", args.remap_events);
+        if (mods_path && NULL == (md_out = fopen(mods_path, "w"))) errx(EXIT_FAILURE, "--remap-mods %s: cannot be written", mods_path);
     }
     /* --truth: likewise */
     if ((NULL == args.truth) != (NULL == args.truth_out)) errx(EXIT_FAILURE, "--truth and --truth-out go together");
@@ -1956,6 +2004,10 @@ int main(int argc, char *argv[]) {
         if (ev_out) {                  /* mapped reads written, and their bases */
             fprintf(stderr, "events\treads\t%llu\nevents\tbases\t%llu\n", ev_count[0], ev_count[1]);
             if (0 != fclose(ev_out)) warnx("--remap-events %s: write failed", args.remap_events);
+        }
+        if (md_out) {                  /* mapped reads written, and their sites */
+            fprintf(stderr, "mods\treads\t%llu\nmods\tsites\t%llu\n", md_count[0], md_count[1]);
+            if (0 != fclose(md_out)) warnx("--remap-mods %s: write failed", mods_path);
         }
         flappie_remap_refs_free(rm_refs);
     }

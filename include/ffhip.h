@@ -117,6 +117,12 @@ typedef struct {
  * is.  Everything else the run returns is that of the same run without the flag.  Without FFHIP_RUN_REMAP: FFHIP_EINVAL; the run-length model and
  * FFHIP_RUN_NO_DECODE are refused as for remap. */
 #define FFHIP_RUN_EVENTS     131072u
+/* With FFHIP_RUN_REMAP, a model of the alphabet ACGTZ: at every C or Z of every mapped read's sequence, the log scores of the signal around it with C and with Z
+ * at that position (ffhip_batch_site_mods below, "site mods"), made on the device (k_site_mods) behind k_remap from the transition scores, the coded sequences and
+ * the path it has just written.  The records are NOT part of the result block: they live in ONE buffer of their own (16 bytes a site, one read behind the other)
+ * and come down in ONE extra copy, enqueued where the remap buffer's copy is.  Everything else the run returns is that of the same run without the flag.  Without
+ * FFHIP_RUN_REMAP, or on a model whose nbase is not 5: FFHIP_EINVAL; the run-length model and FFHIP_RUN_NO_DECODE are refused as for remap. */
+#define FFHIP_RUN_REMAP_MODS 262144u
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -465,6 +471,41 @@ int ffhip_debug_remap_form(size_t L, int band);
 typedef struct { int32_t first, count; float mean, sd; } ffhip_event;      /* 16 bytes */
 int ffhip_batch_events(const ffhip_batch *b, int read, const ffhip_event **ev, size_t *L);
 int ffhip_op_events(ffhip_engine *eng, const float *signal, size_t nsample, int stride, const uint8_t *rm, size_t nblock, size_t L, ffhip_event *out /* L */);
+/* Site mods: at this C of my sequence, is this read methylated?  Per-read modified-base scoring against a reference: the mapping is kept, and around every C the
+ * signal is scored twice through the model's transition scores, once with C and once with Z there.
+ *   Inputs: a read of N >= 1 blocks with transition scores T[b][.] (what ffhip_batch_get_transitions returns); a model of nbase = 5 (codes A 0, C 1, G 2, T 3, Z 4);
+ *     the sequence s of L codes of ffhip_batch_set_remap; the read's remap result with status 1, rm[0 .. N - 1], and from it start[0] = 0, start[i] = 1 + (index of
+ *     the i-th one), start[L] = N as under "remap"; the context c, 0 <= c <= 31, and the mode, best-path or all-paths.
+ *   Sites: every i with s_i in {1, 4}, in increasing i.  The given letter may be C or Z: both hypotheses are scored either way.
+ *   Window of site i: lo = max(0, i - c), hi = min(L - 1, i + c), P = hi - lo + 1 (at most 63) positions; time runs from t0 = start[lo] to t1 = start[hi + 1] - 1
+ *     if hi < L - 1 (block start[hi + 1] - 1 is the move out of hi: not part of the window), else t1 = N; n = t1 - t0.  The remap path itself passes from (t0, lo) to
+ *     (t1, hi), so n >= P - 1 always; n may be 0 (P = 1).
+ *   Hypotheses: s^can is s with s_i := 1, s^mod is s with s_i := 4; q^h is the flip-flop coding (the rule under "remap") of the WHOLE hypothesis sequence: the
+ *     positions before i code as in s itself, those after i may change between flip and flop until the run of equal letters ends (CCC codes C c C, CZC codes C Z C).
+ *   Recursion over all cells j = lo .. hi, no band, for t = t0 .. t1 - 1: X_t0[lo] = 0, X_t0[j > lo] = -inf; stay = X_t[j] + T[t][idx(q_j, q_j)],
+ *     move = X_t[j-1] + T[t][idx(q_{j-1}, q_j)] (-inf for j = lo), idx = remap's trans_lookup.
+ *     Best-path mode, in float32, each term ONE rounded add: X_{t+1}[j] = max(stay, move); the score X_t1[hi] is reproducible to the bit.
+ *     All-paths mode, in fp64 (T converted exactly): X_{t+1}[j] = m + log1p(exp(-|stay - move|)), m = max(stay, move); m = -inf gives -inf, never a NaN; the
+ *     score X_t1[hi] is rounded to float32 once.
+ *   Output per site: the 16 bytes { int32 pos = i; int32 nblock = n; float can; float mod; }.  The log-likelihood ratio is can - mod and
+ *     p(5mC) = 1 / (1 + exp(can - mod)): both are left to the reader.
+ *   The order of operations depends on the window alone: a read's records are the same bytes in a one-read-a-row, ragged, packed, paired, launch-per-step or
+ *     f32-rerun batch (there from the re-run's own transitions and path, as remap's record is) and from one run to the next, in both modes.
+ * ffhip_batch_set_remap_mods: the context (0 .. 31; anything else FFHIP_EINVAL) and the mode of the batch's later runs with the flag; never called: 15 and
+ *   best-path.  Not between a run and its finish.
+ * ffhip_batch_site_mods: after ffhip_batch_finish of a run with FFHIP_RUN_REMAP | FFHIP_RUN_REMAP_MODS; *sm points into the batch (*nsite records in increasing
+ *   pos, valid until the next run; a mapped sequence without C or Z: 0 records); *sm = NULL and *nsite = 0 unless the read's remap status is 1.
+ * ffhip_op_site_mods: the kernel on ONE read from host arrays: the scores (60 rows, a column a block), L codes, nblock = trans.nc bytes of 0 / 1; out:
+ *   caller-owned, room for every C and Z of codes (at most L records); *nsite: the records written.  nbase != 5, a code >= nbase, sum rm != L - 1, a byte > 1,
+ *   L = 0, nblock = 0 or != trans.nc or more than 2^30, a context outside 0 .. 31: FFHIP_EINVAL.
+ * The records' buffer and its pinned mirror, the workspace of starts (L + 1 int32 a read) and the lists of reads and sites are sized at the front of every run with
+ * the flag from the sequences of ffhip_batch_set_remap, grown when a run needs more, freed with the batch and counted by ffhip_debug_batch_device_bytes; when one
+ * cannot be had: FFHIP_ENOMEM with the bytes in the text. */
+typedef struct { int32_t pos, nblock; float can, mod; } ffhip_site_mod;      /* 16 bytes */
+int ffhip_batch_set_remap_mods(ffhip_batch *b, int context, int all_paths);
+int ffhip_batch_site_mods(const ffhip_batch *b, int read, const ffhip_site_mod **sm, size_t *nsite);
+int ffhip_op_site_mods(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, const uint8_t *rm, size_t nblock, int context, int all_paths,
+                       ffhip_site_mod *out, size_t *nsite);
 /* Truth: how close a call is to the sequence it should have been.
  *   Inputs: the call s of n >= 0 bases -- the batch's called letters in signal order, Z read as C (as the barcode search reads it); the truth t of m bases as codes
  *     0 .. nbase - 1, code 4 (Z) folded to 1 (C) for the comparison; the band half-width W >= 0.
