@@ -38,6 +38,9 @@ RUN_EVENTS = 131072       # with RUN_REMAP: first sample, count, mean and sd of 
 EVENT_DTYPE = np.dtype([("first", np.int32), ("count", np.int32), ("mean", np.float32), ("sd", np.float32)])      # ffhip_event (include/ffhip.h)
 RUN_REMAP_MODS = 262144   # with RUN_REMAP, a model of the alphabet ACGTZ: the log scores with C and with Z at every C / Z of every mapped sequence, made on the device (Batch.site_mods)
 SITE_MOD_DTYPE = np.dtype([("pos", np.int32), ("nblock", np.int32), ("can", np.float32), ("mod", np.float32)])      # ffhip_site_mod (include/ffhip.h)
+RUN_REMAP_VARIANTS = 524288   # with RUN_REMAP: the log scores of every variant of Batch.set_remap_variants under the sequence as given and as edited, made on the device (Batch.variant_calls)
+VARIANT_DTYPE = np.dtype([("pos", np.int32), ("nref", np.uint8), ("nalt", np.uint8), ("alt", np.uint8, (16,)), ("pad", np.uint8, (2,))])      # ffhip_variant (include/ffhip.h)
+VARIANT_CALL_DTYPE = np.dtype([("index", np.int32), ("nblock", np.int32), ("ref", np.float32), ("alt", np.float32)])      # ffhip_variant_call (include/ffhip.h)
 TRUTH_BAND_MAX = 1279     # the widest kernel form holds a window of 2 W + 1 <= 2560 cells
 TRUTH_FIELDS = ("status", "n", "m", "dist", "n_match", "n_mismatch", "n_ins", "n_del", "maxdev")
 # ffhip_debug_gate_math forms (include/ffhip.h)
@@ -232,6 +235,9 @@ def lib():
     L.ffhip_batch_set_remap_mods.argtypes = [vp, C.c_int, C.c_int]
     L.ffhip_batch_site_mods.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.ffhip_op_site_mods.argtypes = [vp, CFMat, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.c_int, vp, C.POINTER(C.c_size_t)]
+    L.ffhip_batch_set_remap_variants.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.c_int]
+    L.ffhip_batch_variant_calls.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ffhip_op_variants.argtypes = [vp, CFMat, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, vp]
     L.ffhip_batch_set_truth.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t), C.c_int]
     L.ffhip_batch_truth.argtypes = [vp, C.c_int, C.POINTER(CTruthCall)]
     L.ffhip_op_truth.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.POINTER(CTruthCall), C.POINTER(C.c_uint8)]
@@ -639,6 +645,27 @@ class Batch:
             return None
         return np.frombuffer(C.string_at(sm.value, n.value * SITE_MOD_DTYPE.itemsize), dtype=SITE_MOD_DTYPE).copy()
 
+    def set_remap_variants(self, variants, context: int = 10, all_paths: bool = False):
+        """the variants, the context (1 .. 23 positions either side of an edit) and the mode (best path, or all paths in fp64) of later runs with RUN_REMAP_VARIANTS
+        (ffhip_batch_set_remap_variants; after set_remap): one entry a read, None or an array of VARIANT_DTYPE (make_variants); variants None detaches"""
+        if variants is None:
+            _check(lib().ffhip_batch_set_remap_variants(self.h, 0, None, None, int(context), 1 if all_paths else 0))
+            return
+        keep = [None if v is None else np.ascontiguousarray(v, dtype=VARIANT_DTYPE) for v in variants]
+        n = len(keep)
+        ptrs = (C.c_void_p * max(1, n))(*[None if v is None or v.size == 0 else v.ctypes.data for v in keep])
+        lens = (C.c_size_t * max(1, n))(*[0 if v is None else v.size for v in keep])
+        _check(lib().ffhip_batch_set_remap_variants(self.h, n, ptrs, lens, int(context), 1 if all_paths else 0))
+
+    def variant_calls(self, read: int):
+        """the records of a run with RUN_REMAP | RUN_REMAP_VARIANTS (ffhip_batch_variant_calls): a structured array (VARIANT_CALL_DTYPE), one entry a variant of the
+        read's list in list order; None unless the read's remap status is 1"""
+        vc, n = C.c_void_p(), C.c_size_t()
+        _check(lib().ffhip_batch_variant_calls(self.h, read, C.byref(vc), C.byref(n)))
+        if not vc.value:
+            return None
+        return np.frombuffer(C.string_at(vc.value, n.value * VARIANT_CALL_DTYPE.itemsize), dtype=VARIANT_CALL_DTYPE).copy()
+
     def set_truth(self, seqs, band: int = 512):
         """the truths and band of later runs with RUN_TRUTH (ffhip_batch_set_truth): one entry a read, None (no truth) or codes 0 .. nbase - 1 in signal order; seqs None detaches"""
         if seqs is None:
@@ -849,6 +876,37 @@ def op_site_mods(engine: Engine, trans: np.ndarray, nbase: int, codes, rm, conte
                                     (m if m.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), m.size, int(context), 1 if all_paths else 0,
                                     out.ctypes.data_as(C.c_void_p), C.byref(n)))
     return out[:n.value]
+
+
+def make_variants(variants) -> np.ndarray:
+    """an array of VARIANT_DTYPE from (pos, nref, alt codes) triples"""
+    out = np.zeros(len(variants), VARIANT_DTYPE)
+    for i, (pos, nref, alt) in enumerate(variants):
+        alt = np.asarray(alt, np.uint8).reshape(-1)
+        out[i]["pos"], out[i]["nref"], out[i]["nalt"] = int(pos), int(nref), min(alt.size, 255)
+        out[i]["alt"][:min(alt.size, 16)] = alt[:16]
+    return out
+
+
+def op_variants(engine: Engine, trans: np.ndarray, nbase: int, codes, rm, variants, context: int = 10, all_paths: bool = False, stride: int = 0) -> np.ndarray:
+    """ffhip_op_variants: the records (VARIANT_CALL_DTYPE, one entry a variant) of ONE read from its transition scores `trans` [nblock][nstate (nbase + 1)], its
+    sequence, its remap path rm (uint8, a byte a block) and its variants (VARIANT_DTYPE); stride > trans.shape[1]: the matrix is handed over with that many floats a block"""
+    t = np.ascontiguousarray(trans, dtype=np.float32)
+    nparam = t.shape[1] if t.ndim == 2 else 0
+    if stride > nparam and t.ndim == 2:
+        wide = np.full((t.shape[0], int(stride)), np.float32(np.nan))      # (the padding is never read)
+        wide[:, :nparam] = t
+        t = wide
+    q = np.ascontiguousarray(codes, dtype=np.uint8)
+    m = np.ascontiguousarray(rm, dtype=np.uint8)
+    v = np.ascontiguousarray(variants, dtype=VARIANT_DTYPE)
+    out = np.zeros(max(1, v.size), VARIANT_CALL_DTYPE)
+    _check(lib().ffhip_op_variants(engine.h, CFMat(_fptr(t), nparam, t.shape[0], t.shape[1] if t.ndim == 2 else 0), int(nbase),
+                                   (q if q.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), q.size,
+                                   (m if m.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), m.size,
+                                   (v if v.size else np.zeros(1, VARIANT_DTYPE)).ctypes.data_as(C.c_void_p), v.size, int(context), 1 if all_paths else 0,
+                                   out.ctypes.data_as(C.c_void_p)))
+    return out[:v.size]
 
 
 def _truth_dict(c, ops) -> dict:

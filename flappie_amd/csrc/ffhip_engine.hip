@@ -805,6 +805,18 @@ struct ffhip_batch {
     int smd_valid = 0, smd_reads = 0, smd_context = 15, smd_all = 0;
     size_t smd_nsite() const { return smd_off.empty() ? 0 : smd_off.back(); }
     size_t smd_bytes() const { return smd_nsite() * sizeof(ffhip_site_mod); }
+    // Variants (FFHIP_RUN_REMAP_VARIANTS with FFHIP_RUN_REMAP, k_variants): the lists of ffhip_batch_set_remap_variants (copied), and, as for site mods, ONE buffer
+    // of 16 bytes a variant of every read with a sequence that can be mapped, one read behind the other (var_dev, its pinned mirror var_host), with one copy of
+    // its own beside the remap buffer's; its own workspace of starts (L + 1 int32 a listed read) and its own list (the variants, then the reads: one pinned
+    // image, one upload)
+    std::vector<std::vector<ffhip_variant>> var_set;        // per read: its variants (empty: the feature is detached)
+    std::vector<size_t> var_off;                            // per read: its first record, and (one more entry) the end
+    uint8_t *var_dlist = nullptr, *var_hlist = nullptr; size_t var_dlist_cap = 0, var_hlist_cap = 0;
+    int *var_start = nullptr; size_t var_start_cap = 0;
+    uint8_t *var_dev = nullptr, *var_host = nullptr; size_t var_dev_cap = 0, var_host_cap = 0;
+    int var_valid = 0, var_reads = 0, var_context = 10, var_all = 0;
+    size_t var_count() const { return var_off.empty() ? 0 : var_off.back(); }
+    size_t var_bytes() const { return var_count() * sizeof(ffhip_variant_call); }
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
     std::vector<void *> owned;
     unsigned last_flags = 0;
@@ -909,6 +921,8 @@ extern "C" void ffhip_batch_destroy(ffhip_batch *b) {
     if (b->evt_hlist) hipHostFree(b->evt_hlist);
     if (b->smd_host) hipHostFree(b->smd_host);
     if (b->smd_hlist) hipHostFree(b->smd_hlist);
+    if (b->var_host) hipHostFree(b->var_host);
+    if (b->var_hlist) hipHostFree(b->var_hlist);
     if (b->side) ffhip_batch_destroy(b->side);
     prof_unlink(b);
     if (b->have_ev) {
@@ -1684,6 +1698,60 @@ static void sitemods_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {
     b->smd_valid = 1;
 }
 
+// Variants, the front's share, behind remap's: as site mods', over this feature's own list of reads (those that can be mapped and have a variant), with its own
+// workspace of starts.  A variant's place in the list is its record's place in the buffer; the variants stand in front of the reads (an entry is read as 16-byte words).
+static_assert(sizeof(VarEntry) == 32 && sizeof(Variant) == sizeof(ffhip_variant) && sizeof(ffhip_variant) == 24 && sizeof(ffhip_variant_call) == 16,
+              "the lists are copied as they stand; k_variants writes a record as one 16-byte store");
+static int variants_prepare(ffhip_batch *b) {
+    const int nR = b->packed ? b->nvirt : b->nread;
+    if (b->var_set.empty()) return set_err(FFHIP_EINVAL, "variants: none are set for the batch (ffhip_batch_set_remap_variants)");
+    if ((int)b->var_set.size() != nR) return set_err(FFHIP_EINVAL, "variants: lists were set for %zu reads, the batch holds %d", b->var_set.size(), nR);
+    std::vector<size_t> off((size_t)nR + 1, 0);
+    std::vector<SiteRead> list;
+    std::vector<VarEntry> vars;
+    size_t words = 0, seq = 0;
+    for (int r = 0; r < nR; r++) {
+        const int N = b->hTb[r], L = (int)b->rmp_seq[r].size();
+        off[r] = vars.size();
+        if (b->rmp_state[r] == 1 && N >= 1 && L >= 1 && L <= N + 1 && !b->var_set[r].empty()) {
+            for (size_t i = 0; i < b->var_set[r].size(); i++) {
+                VarEntry e{ (int)list.size(), (int)i, {} };
+                memcpy(&e.v, &b->var_set[r][i], sizeof e.v);
+                vars.push_back(e);
+            }
+            list.push_back(SiteRead{ words, (unsigned)seq, L, r, 0 });
+            words += (size_t)L + 1;
+        }
+        seq += (size_t)L;
+    }
+    off[nR] = vars.size();
+    if (vars.size() > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "variants: %zu variants in one batch", vars.size());
+    const size_t bytes = std::max<size_t>(vars.size(), 1) * sizeof(ffhip_variant_call);
+    const size_t vb = vars.size() * sizeof(VarEntry), lbytes = std::max<size_t>(vb + list.size() * sizeof(SiteRead), 8);
+    if (int rc = dgrow(b, (void **)&b->var_dev, &b->var_dev_cap, bytes, "variants: the variants' records")) return rc;
+    if (int rc = dgrow(b, (void **)&b->var_start, &b->var_start_cap, std::max<size_t>(words, 1) * 4, "variants: the workspace of starts")) return rc;
+    if (int rc = dgrow(b, (void **)&b->var_dlist, &b->var_dlist_cap, lbytes, "variants: the list of variants and reads")) return rc;
+    if (int rc = pinned_grow(b, &b->var_host, &b->var_host_cap, bytes, "variants: the variants' records")) return rc;
+    if (int rc = pinned_grow(b, &b->var_hlist, &b->var_hlist_cap, lbytes, "variants: the list of variants and reads")) return rc;
+    b->var_off = std::move(off);
+    b->var_reads = (int)list.size();
+    if (!vars.empty()) {
+        memcpy(b->var_hlist, vars.data(), vb);
+        memcpy(b->var_hlist + vb, list.data(), list.size() * sizeof(SiteRead));
+        HIP_TRY(hipMemcpyAsync(b->var_dlist, b->var_hlist, vb + list.size() * sizeof(SiteRead), hipMemcpyHostToDevice, b->stream), FFHIP_EHIP);
+    }
+    return FFHIP_OK;
+}
+static void variants_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {
+    if (b->var_count() > 0) {
+        launch_variants(b->stream, (const SiteRead *)(b->var_dlist + b->var_count() * sizeof(VarEntry)), b->var_reads, (const VarEntry *)b->var_dlist, (int)b->var_count(),
+                        b->rmp_dseq, b->trans, b->mdl->Ps, b->mdl->nbase, b->var_context, b->var_all, b->rmp_dev, b->rmp_dev + (size_t)b->cap_reads * 16, b->var_start,
+                        b->var_dev, b->Tb, tbr, rmap);
+        b->launches[5] += 2;
+    }
+    b->var_valid = 1;
+}
+
 // Truth, the front's share: as remap's.  The ops' bytes follow from the truths and the reads' blocks, so records and ops grow here too (device and pinned host).
 static_assert(sizeof(TruthRead) == 40, "the reads' list is copied as it stands");
 static int truth_prepare(ffhip_batch *b) {
@@ -1790,6 +1858,11 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
         if (!(flags & FFHIP_RUN_REMAP)) return set_err(FFHIP_EINVAL, "site mods: the scores of a mapped sequence's C positions need the mapping (FFHIP_RUN_REMAP_MODS goes with FFHIP_RUN_REMAP)");
         if (m->nbase != 5) return set_err(FFHIP_EINVAL, "site mods: the model has no modified base (FFHIP_RUN_REMAP_MODS takes a model of the alphabet ACGTZ)");
         if (int rc = sitemods_prepare(b)) return rc;
+    }
+    b->var_valid = 0;
+    if (flags & FFHIP_RUN_REMAP_VARIANTS) {      // (likewise)
+        if (!(flags & FFHIP_RUN_REMAP)) return set_err(FFHIP_EINVAL, "variants: the scores of a mapped sequence's alleles need the mapping (FFHIP_RUN_REMAP_VARIANTS goes with FFHIP_RUN_REMAP)");
+        if (int rc = variants_prepare(b)) return rc;
     }
     b->tru_valid = 0;
     if (flags & FFHIP_RUN_TRUTH) {         // (nor this)
@@ -2089,6 +2162,7 @@ static int run_back(ffhip_batch *b) {
             if (flags & FFHIP_RUN_REMAP) remap_launch(b, nR, tbr, rmap);      // from the transitions, whatever the path was decoded from (run_front made the lists)
             if (flags & FFHIP_RUN_EVENTS) events_launch(b, tbr, rmap);        // from the path k_remap has just written and the signal the convolutions read
             if (flags & FFHIP_RUN_REMAP_MODS) sitemods_launch(b, tbr, rmap);  // from that path, the transitions and the coded sequences
+            if (flags & FFHIP_RUN_REMAP_VARIANTS) variants_launch(b, tbr, rmap);      // (likewise)
             if (flags & FFHIP_RUN_MOD_PROBS) {          // from the posterior whatever decoded the path (run_front checked the model)
                 launch_mod_probs(s, b->post, b->path, b->res.on_dev<uint8_t>(RF_ML), nR, Tb, m->Ps, tbr, rmap);
                 b->launches[5]++;
@@ -2116,6 +2190,7 @@ static int run_back(ffhip_batch *b) {
         if (b->rmp_valid) HIP_TRY(hipMemcpyAsync(b->rmp_host, b->rmp_dev, b->rmp_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the remap records' and moves' one copy
         if (b->evt_valid && b->evt_bytes()) HIP_TRY(hipMemcpyAsync(b->evt_host, b->evt_dev, b->evt_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the events' one copy
         if (b->smd_valid && b->smd_bytes()) HIP_TRY(hipMemcpyAsync(b->smd_host, b->smd_dev, b->smd_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the site mods' one copy
+        if (b->var_valid && b->var_bytes()) HIP_TRY(hipMemcpyAsync(b->var_host, b->var_dev, b->var_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the variants' one copy
         if (b->tru_valid) HIP_TRY(hipMemcpyAsync(b->tru_host, b->tru_dev, b->tru_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the truth records' and ops' one copy
         b->res_copied = 1;
     }
@@ -2168,7 +2243,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
     const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
     b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
     b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0; b->rmp_valid = 0; b->tru_valid = 0; b->evt_valid = 0; b->smd_valid = 0;
+    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0; b->rmp_valid = 0; b->tru_valid = 0; b->evt_valid = 0; b->smd_valid = 0; b->var_valid = 0;
     return FFHIP_OK;
 }
 
@@ -2261,6 +2336,11 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
             for (int k = 0; k < n; k++) { sq[k] = b->rmp_seq[reads[k0 + k]]; st[k] = b->rmp_state[reads[k0 + k]]; }
             if (int rc = remap_adopt(sd, std::move(sq), std::move(st), b->rmp_band)) return rc;
             sd->smd_context = b->smd_context; sd->smd_all = b->smd_all;
+            if (fl & FFHIP_RUN_REMAP_VARIANTS) {          // ... and their variants (remap_adopt has detached the side batch's)
+                sd->var_set.assign(16, std::vector<ffhip_variant>());
+                for (int k = 0; k < n; k++) sd->var_set[k] = b->var_set[reads[k0 + k]];
+                sd->var_context = b->var_context; sd->var_all = b->var_all;
+            }
         }
         if (fl & FFHIP_RUN_TRUTH) {                       // ... and truths
             std::vector<std::vector<uint8_t>> sq(16);
@@ -2317,6 +2397,14 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
                     memcpy(b->smd_host + to, sd->smd_host + from, ne);
                 }
             }
+            if (b->var_valid && sd->var_valid) {        // and its variants' records (the same list: the same room), both halves
+                const size_t ne = std::min(b->var_off[r + 1] - b->var_off[r], sd->var_off[k + 1] - sd->var_off[k]) * sizeof(ffhip_variant_call);
+                const size_t to = b->var_off[r] * sizeof(ffhip_variant_call), from = sd->var_off[k] * sizeof(ffhip_variant_call);
+                if (ne) {
+                    HIP_TRY(hipMemcpyAsync(b->var_dev + to, sd->var_dev + from, ne, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                    memcpy(b->var_host + to, sd->var_host + from, ne);
+                }
+            }
             if (b->tru_valid && sd->tru_valid) {        // and its truth record and ops (the same blocks and truth: the same bytes of ops), both halves
                 const size_t rb = (size_t)kTruthRecInts * 4, to = b->tru_rec_bytes() + b->tru_ops[r], from = sd->tru_rec_bytes() + sd->tru_ops[k];
                 const size_t ob = std::min(b->tru_ops[r + 1] - b->tru_ops[r], sd->tru_ops[k + 1] - sd->tru_ops[k]);
@@ -2356,6 +2444,8 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
             HIP_TRY(hipMemcpyAsync(b->evt_host, b->evt_dev, b->evt_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
         if (b->smd_valid && b->smd_bytes())                  // the site mods' one copy (likewise)
             HIP_TRY(hipMemcpyAsync(b->smd_host, b->smd_dev, b->smd_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
+        if (b->var_valid && b->var_bytes())                  // the variants' one copy (likewise)
+            HIP_TRY(hipMemcpyAsync(b->var_host, b->var_dev, b->var_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
         if (b->tru_valid)                                    // the truth records' and ops' one copy (likewise)
             HIP_TRY(hipMemcpyAsync(b->tru_host, b->tru_dev, b->tru_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
     }
@@ -2521,11 +2611,12 @@ static int remap_adopt(ffhip_batch *b, std::vector<std::vector<unsigned short>> 
     if (total) HIP_TRY(hipMemcpy(b->rmp_dseq, flat.data(), total * sizeof(unsigned short), hipMemcpyHostToDevice), FFHIP_EHIP);
     b->rmp_seq = std::move(seq); b->rmp_state = std::move(state);
     b->rmp_band = band; b->rmp_set = 1;
+    b->var_set.clear();                                     // (variants are validated against the sequences: new sequences detach them)
     return FFHIP_OK;
 }
 extern "C" int ffhip_batch_set_remap(ffhip_batch *b, int nread, const uint8_t *const *codes, const size_t *len, int band) {
     if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (!codes) { b->rmp_set = 0; b->rmp_seq.clear(); b->rmp_state.clear(); return FFHIP_OK; }
+    if (!codes) { b->rmp_set = 0; b->rmp_seq.clear(); b->rmp_state.clear(); b->var_set.clear(); return FFHIP_OK; }
     const ffhip_model *m = b->mdl;
     if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "remap: a flip-flop model only (the run-length model's scores are not transitions between bases)");
     if (!len || nread != batch_nreads(b)) return set_err(FFHIP_EINVAL, "remap: sequences for %d reads, the batch holds %d", nread, batch_nreads(b));
@@ -2589,6 +2680,45 @@ extern "C" int ffhip_batch_site_mods(const ffhip_batch *b, int read, const ffhip
     if (rec[3] != 0) return set_err(FFHIP_EHIP, "remap: read %d's traceback ended at position %d, not 0", read, rec[3]);
     *sm = (const ffhip_site_mod *)b->smd_host + b->smd_off[read];
     *nsite = b->smd_off[read + 1] - b->smd_off[read];
+    return FFHIP_OK;
+}
+
+// ---- variants (include/ffhip.h "variants"; the kernel: ffhip_variants.hip)
+extern "C" int ffhip_batch_set_remap_variants(ffhip_batch *b, int nread, const ffhip_variant *const *vars, const size_t *nvar, int context, int all_paths) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "variants: the batch is running (ffhip_batch_finish first)");
+    if (!vars) { b->var_set.clear(); return FFHIP_OK; }
+    if (!b->rmp_set) return set_err(FFHIP_EINVAL, "variants: no sequences are set for the batch (ffhip_batch_set_remap comes first)");
+    if (!nvar || nread != batch_nreads(b) || (size_t)nread != b->rmp_seq.size()) return set_err(FFHIP_EINVAL, "variants: lists for %d reads, the batch holds %d", nread, batch_nreads(b));
+    if (context < kVariantsMinContext || context > kVariantsMaxContext) return set_err(FFHIP_EINVAL, "variants: the context is %d (%d .. %d)", context, kVariantsMinContext, kVariantsMaxContext);
+    std::vector<std::vector<ffhip_variant>> set((size_t)nread);
+    for (int r = 0; r < nread; r++) {
+        if (!nvar[r]) continue;
+        if (!vars[r]) return set_err(FFHIP_EINVAL, "variants: read %d has %zu variants and no list", r, nvar[r]);
+        if (nvar[r] > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "variants: read %d has %zu variants", r, nvar[r]);
+        if (b->rmp_state[r] != 1) return set_err(FFHIP_EINVAL, "variants: read %d, index 0: the read has no sequence", r);
+        for (size_t i = 0; i < nvar[r]; i++) {
+            Variant v;
+            memcpy(&v, &vars[r][i], sizeof v);
+            if (const char *why = variant_invalid(v, b->rmp_seq[r].size(), b->mdl->nbase))
+                return set_err(FFHIP_EINVAL, "variants: read %d, index %zu: %s (pos %d, nref %d, nalt %d, a sequence of %zu codes)", r, i, why, (int)v.pos, (int)v.nref, (int)v.nalt, b->rmp_seq[r].size());
+        }
+        set[r].assign(vars[r], vars[r] + nvar[r]);
+    }
+    b->var_set = std::move(set);
+    b->var_context = context; b->var_all = all_paths ? 1 : 0;
+    return FFHIP_OK;
+}
+extern "C" int ffhip_batch_variant_calls(const ffhip_batch *b, int read, const ffhip_variant_call **vc, size_t *nvar) {
+    if (!results_ok(b, read) || !vc || !nvar) return FFHIP_EINVAL;
+    if (!b->var_valid || !b->rmp_valid || !b->var_host) return set_err(FFHIP_EINVAL, "variants were not scored in this run (FFHIP_RUN_REMAP | FFHIP_RUN_REMAP_VARIANTS)");
+    int rec[4];
+    memcpy(rec, b->rmp_host + (size_t)read * 16, 16);
+    *vc = nullptr; *nvar = 0;
+    if (rec[0] != 1) return FFHIP_OK;
+    if (rec[3] != 0) return set_err(FFHIP_EHIP, "remap: read %d's traceback ended at position %d, not 0", read, rec[3]);
+    *vc = (const ffhip_variant_call *)b->var_host + b->var_off[read];
+    *nvar = b->var_off[read + 1] - b->var_off[read];
     return FFHIP_OK;
 }
 

@@ -286,6 +286,19 @@ constexpr int kSiteModsMaxContext = 31; // a window of 2 c + 1 <= 63 positions: 
 size_t sitemods_sites(const unsigned short *coded, size_t L, int k, std::vector<SiteMod> *out);
 void launch_site_mods(hipStream_t s, const SiteRead *list, int nread, const SiteMod *sites, int nsite, const unsigned short *seq, const float *trans, int Ps,
                       int context, int all_paths, const void *records, const uint8_t *rm, int *starts, void *out, int Tb, const int *tbs, ReadMap map);
+// k_site_starts alone, for another list of reads and another workspace (ffhip_variants.hip launches it over its own): one launch, nread workgroups
+void launch_site_starts(hipStream_t s, const SiteRead *list, int nread, const void *records, const uint8_t *rm, int *starts, int Tb, const int *tbs, ReadMap map);
+// Ref against alt alleles of a mapped sequence (k_variants, ffhip_variants.hip; include/ffhip.h "variants"), nbase 4 or 5: per listed variant whose read's remap
+// record at records[read] says { status 1, end 0, L }, the 16 bytes { int32 index, nblock; float ref, alt } at out[variant's place in `vars`], from the read's
+// score rows, its coded sequence (remap_code), its starts (k_site_starts over `list`, launched here first) and the variant's 24 bytes; any other read writes
+// nothing.  The reads' list has SiteRead's form.  Two launches behind launch_remap on the same stream; all_paths picks the fp64 instantiation.
+struct Variant { int pos; uint8_t nref, nalt, alt[16], pad[2]; };      // include/ffhip.h's ffhip_variant, byte for byte
+struct VarEntry { int k, index; Variant v; };           // the variant's read, as an index into the list of SiteRead; its place in the read's own list; the variant
+constexpr int kVariantsMinContext = 1, kVariantsMaxContext = 23, kVariantsMaxAllele = 16;      // windows of 2 c + max(r, k) <= 62 positions: a lane a position
+// nullptr when the variant keeps every limit of include/ffhip.h "variants" for a sequence of L codes, else the limit it breaks (a text for the error message)
+const char *variant_invalid(const Variant &v, size_t L, int nbase);
+void launch_variants(hipStream_t s, const SiteRead *list, int nread, const VarEntry *vars, int nvar, const unsigned short *seq, const float *trans, int Ps, int nbase,
+                     int context, int all_paths, const void *records, const uint8_t *rm, int *starts, void *out, int Tb, const int *tbs, ReadMap map);
 // exp + trace_from_posterior
 void launch_trace(hipStream_t s, const float *post, int32_t *trace, int nread, int Tb, int nbase, int Ps, int is_log, const int *tbs = nullptr, ReadMap map = ReadMap());
 void launch_exp_inplace(hipStream_t s, float *x, size_t n);

@@ -777,6 +777,53 @@ extern "C" int ffhip_op_site_mods(ffhip_engine *eng, ffhip_mat trans, int nbase,
     return FFHIP_OK;
 }
 
+// the variants of one read from its scores, its sequence and its path (k_site_starts + k_variants; include/ffhip.h "variants")
+extern "C" int ffhip_op_variants(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, const uint8_t *rm, size_t nblock,
+                                 const ffhip_variant *vars, size_t nvar, int context, int all_paths, ffhip_variant_call *out) {
+    OP_ENTER(eng);
+    static_assert(sizeof(Variant) == sizeof(ffhip_variant) && sizeof(VarEntry) == 32 && sizeof(ffhip_variant_call) == 16, "the list is copied as it stands");
+    if (nbase != 4 && nbase != 5) return set_err(FFHIP_EINVAL, "variants: nbase is %d (4 or 5)", nbase);
+    if (!view_ok(trans) || !codes || !rm || (nvar && (!vars || !out)) || trans.nr != (size_t)(2 * nbase * (nbase + 1)) || trans.stride % 4 != 0 || trans.stride > 2048)
+        return set_err(FFHIP_EINVAL, "bad variants arguments (scores of 2 nbase (nbase + 1) rows, a sequence, a path of nblock bytes, variants and room for their records)");
+    if (context < kVariantsMinContext || context > kVariantsMaxContext) return set_err(FFHIP_EINVAL, "variants: the context is %d (%d .. %d)", context, kVariantsMinContext, kVariantsMaxContext);
+    if (nblock < 1 || nblock != trans.nc || L < 1 || nblock > (size_t)1 << 30 || nvar > (size_t)1 << 30)
+        return set_err(FFHIP_EINVAL, "variants: %zu blocks of path, %zu of scores, %zu bases and %zu variants (the same 1 .. 2^30 blocks, L >= 1)", nblock, trans.nc, L, nvar);
+    size_t ones = 0;
+    for (size_t i = 0; i < nblock; i++) {
+        if (rm[i] > 1) return set_err(FFHIP_EINVAL, "variants: block %zu of the path is %d (0 or 1)", i, (int)rm[i]);
+        ones += rm[i];
+    }
+    if (ones != L - 1) return set_err(FFHIP_EINVAL, "variants: the path moves %zu times, a sequence of %zu bases takes %zu", ones, L, L - 1);
+    for (size_t i = 0; i < L; i++) if (codes[i] >= nbase) return set_err(FFHIP_EINVAL, "variants: position %zu: code %d is not a base (0 .. %d)", i, (int)codes[i], nbase - 1);
+    std::vector<VarEntry> list(nvar);
+    for (size_t i = 0; i < nvar; i++) {
+        list[i].k = 0; list[i].index = (int)i;
+        memcpy(&list[i].v, &vars[i], sizeof(Variant));
+        if (const char *why = variant_invalid(list[i].v, L, nbase))
+            return set_err(FFHIP_EINVAL, "variants: read 0, index %zu: %s (pos %d, nref %d, nalt %d, a sequence of %zu codes)", i, why, (int)vars[i].pos, (int)vars[i].nref, (int)vars[i].nalt, L);
+    }
+    if (!nvar) return FFHIP_OK;
+    std::vector<unsigned short> coded(L);
+    remap_code(codes, L, nbase, coded.data());
+    const SiteRead sr{ 0ull, 0u, (int)L, 0, 0 };
+    const unsigned rec[4] = { 1u, (unsigned)L, 0u, 0u };
+    float *d_t = upload_img(tmp, trans, s);
+    unsigned short *d_seq = (unsigned short *)tmp.upload(coded.data(), L * sizeof(unsigned short), s);
+    uint8_t *d_rm = (uint8_t *)tmp.upload(rm, nblock, s);
+    SiteRead *d_list = (SiteRead *)tmp.upload(&sr, sizeof sr, s);
+    VarEntry *d_vars = (VarEntry *)tmp.upload(list.data(), nvar * sizeof(VarEntry), s);
+    void *d_rec = tmp.upload(rec, sizeof rec, s);
+    int *d_start = (int *)tmp.get((L + 1) * 4);
+    void *d_out = tmp.get(nvar * sizeof(ffhip_variant_call));
+    if (!d_start || !d_out) return set_err(FFHIP_ENOMEM, "variants: the records and starts take %zu bytes of device memory, which could not be had", nvar * sizeof(ffhip_variant_call) + (L + 1) * 4);
+    if (!d_t || !d_seq || !d_rm || !d_list || !d_vars || !d_rec) OP_NOMEM();
+    launch_variants(s, d_list, 1, d_vars, (int)nvar, d_seq, d_t, (int)trans.stride, nbase, context, all_paths ? 1 : 0, d_rec, d_rm, d_start, d_out, (int)nblock, nullptr, ReadMap());
+    HIP_TRY(hipMemcpyAsync(out, d_out, nvar * sizeof(ffhip_variant_call), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    HIP_TRY(hipGetLastError(), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+
 // one call aligned to one truth (k_truth; include/ffhip.h "truth")
 extern "C" int ffhip_op_truth(ffhip_engine *eng, const char *call, size_t n, const uint8_t *truth, size_t m, int band, ffhip_truth_call *out, uint8_t *ops) {
     OP_ENTER(eng);

@@ -157,6 +157,11 @@ k_site_mods(const SiteRead *__restrict__ list, const SiteMod *__restrict__ sites
     if (lane == P - 1) out[site] = make_int4(i, t1 - t0, __float_as_int((float)X[0]), __float_as_int((float)X[1]));
 }
 
+void launch_site_starts(hipStream_t s, const SiteRead *list, int nread, const void *records, const uint8_t *rm, int *starts, int Tb, const int *tbs, ReadMap map) {
+    if (nread <= 0) return;
+    hipLaunchKernelGGL(k_site_starts, dim3(nread), dim3(kSmNT), 0, s, list, (const uint4 *)records, rm, starts, Tb, tbs, map);
+}
+
 void launch_site_mods(hipStream_t s, const SiteRead *list, int nread, const SiteMod *sites, int nsite, const unsigned short *seq, const float *trans, int Ps,
                       int context, int all_paths, const void *records, const uint8_t *rm, int *starts, void *out, int Tb, const int *tbs, ReadMap map) {
     if (nread <= 0 || nsite <= 0) return;

@@ -39,6 +39,7 @@
 #include "../../include/flappie_output.h"
 #include "../../include/flappie_modbase.h"
 #include "../../include/flappie_sitemods.h"
+#include "../../include/flappie_variants.h"
 #include "../../include/flappie_moves.h"
 #include "../../include/flappie_barcodes.h"
 #include "../../include/flappie_remap.h"
@@ -103,6 +104,10 @@ static struct argp_option options[] = {
     {"remap-mods", 262, "mods.tsv", 0, "With --remap, a model with a modified base (r941_5mC): at every C or Z of every mapped read's sequence, the log scores of the signal around it with C and with 5mC at that position, made on the GPU from the mapping and the read's transition scores: one line per site, reads in output order and sites in signal order, no header: name, position, the given letter, blocks of the window, score with C, score with 5mC, and their difference (the log-likelihood ratio; p(5mC) = 1 / (1 + exp(ratio)))"},
     {"remap-mods-context", 263, "N", 0, "With --remap-mods: the bases either side of a site whose signal is scored (0-31, default 15)"},
     {"remap-mods-all-paths", 264, 0, 0, "With --remap-mods: sum over all paths of the window in double precision instead of taking the best path"},
+    {"remap-variants", 265, "vars.tsv", 0, "With --remap: for every variant of a tab-separated file (name, pos, ref, alt: the record's name as --remap finds it, the 0-based position in the record in signal order, the record's letters there and the letters to put in their place, at most 16 each, - for none), the log scores of the signal around it under the record as given and as edited, made on the GPU from the mapping and the read's transition scores, written to --remap-variants-out; a line that cannot be used is skipped and counted"},
+    {"remap-variants-out", 266, "calls.tsv", 0, "With --remap-variants (required): one line per variant of every mapped read, reads in output order and variants in file order, no header: name, pos, ref, alt, blocks of the window, score of ref, score of alt, and their difference (the log-likelihood ratio)"},
+    {"remap-variants-context", 267, "N", 0, "With --remap-variants: the bases either side of an edit whose signal is scored (1-23, default 10)"},
+    {"remap-variants-all-paths", 268, 0, 0, "With --remap-variants: sum over all paths of the window in double precision instead of taking the best path"},
     {"truth", 258, "refs.fa", 0, "Score each read's call against the sequence it should have been: the records of a FASTA file, found as for --remap (the same file may serve both), in SIGNAL order. The whole call is aligned to its record on the GPU (banded global edit distance) and the result written to --truth-out; stdout does not change. The alignment is always of the whole call in signal order: --reverse and --trim-barcodes do not alter it"},
     {"truth-out", 259, "acc.tsv", 0, "With --truth (required): one line per read that had a record: name, status (1 aligned, 2 not: an empty record, a letter outside the model's alphabet, or a band that leaves no path), n, m, band, maxdev, dist, matches, mismatches, insertions, deletions, identity and the extended CIGAR (=XID)"},
     {"truth-band", 260, "W", 0, "With --truth: the band's half-width in called bases around the straight line from (0, 0) to (m, n) (0-1279, default 512: the GPU holds a window of at most 2 W + 1 <= 2560 cells; maxdev = W in acc.tsv says the band was touched)"},
@@ -113,6 +118,10 @@ static struct argp_option options[] = {
     {"truth", 258, "refs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"remap-events", 261, "events.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"remap-mods", 262, "mods.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"remap-variants", 265, "vars.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"remap-variants-out", 266, "calls.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"remap-variants-context", 267, "N", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"remap-variants-all-paths", 268, 0, OPTION_HIDDEN, "(flappie's option: refused here)"},
 #endif
     {0}
 };
@@ -167,6 +176,14 @@ static char *mods_path = NULL;
 #ifndef BUILD_RUNNIE
 static int mods_context = 15;
 static bool mods_context_set = false, mods_all_paths = false;
+#endif
+
+/* flappie: --remap-variants file and table, --remap-variants-context, --remap-variants-all-paths (runnie: seen, to be refused) */
+static char *vars_path = NULL, *vars_out_path = NULL;
+static bool vars_opts = false;
+#ifndef BUILD_RUNNIE
+static int vars_context = 10;
+static bool vars_all_paths = false;
 #endif
 
 static void print_models(FILE *fh) {
@@ -282,7 +299,19 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
     case 258: args.truth = arg; break;
     case 261: args.remap_events = arg; break;
     case 262: mods_path = arg; break;
-#ifndef BUILD_RUNNIE
+    case 265: vars_path = arg; break;
+    case 266: vars_out_path = arg; break;
+#ifdef BUILD_RUNNIE
+    case 267: case 268: vars_opts = true; break;
+#else
+    case 267: {
+        char *end = NULL;
+        const long c = strtol(arg, &end, 10);
+        if (end == arg || *end != '\0' || c < 1 || c > 23) errx(EXIT_FAILURE, "--remap-variants-context must be a whole number from 1 to 23");
+        vars_context = (int)c; vars_opts = true;
+        break;
+    }
+    case 268: vars_all_paths = true; vars_opts = true; break;
     case 263: {
         char *end = NULL;
         const long c = strtol(arg, &end, 10);
@@ -472,6 +501,8 @@ typedef struct {
     ffhip_event *ev;                    /* --remap-events: its rm_L events (owned; NULL unless mapped) */
     ffhip_site_mod *smods;               /* --remap-mods: its nsm site records (owned; NULL unless mapped) */
     size_t nsmods;
+    ffhip_variant_call *vcalls;          /* --remap-variants: its nvcalls records (owned; NULL unless mapped and with variants) */
+    size_t nvcalls;
     int tr_ref, have_tr;                /* --truth: the read's record of the truths (-1: none), and what the batch returned for it */
     flappie_truth_rec tr;
     uint8_t *tr_ops;                    /* ... its ops (owned; NULL unless aligned) */
@@ -561,6 +592,11 @@ static void write_events(FILE *out, const char *name, const uint8_t *codes, cons
 /* flappie --remap-mods: the table, and the summary's counts: reads and sites written */
 static FILE *md_out = NULL;
 static unsigned long long md_count[2];
+/* flappie --remap-variants: the variants, the table, the records whose variants were written, and the summary's counts: reads and variants written */
+static flappie_variants *vr_vars = NULL;
+static FILE *vr_out = NULL;
+static unsigned char *vr_done = NULL;
+static unsigned long long vr_count[2];
 /* flappie --truth: the truths, the table, and the summary */
 static flappie_remap_refs *tr_refs = NULL;
 static FILE *tr_out = NULL;
@@ -578,7 +614,7 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u) |
            (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | (tr_refs ? FFHIP_RUN_TRUTH : 0u) |
-           (ev_out ? FFHIP_RUN_EVENTS : 0u) | (md_out ? FFHIP_RUN_REMAP_MODS : 0u);
+           (ev_out ? FFHIP_RUN_EVENTS : 0u) | (md_out ? FFHIP_RUN_REMAP_MODS : 0u) | (vr_out ? FFHIP_RUN_REMAP_VARIANTS : 0u);
 }
 /* --remap: every read's record, by its read id, then by its file's base name; a bad record goes as a sequence of no bases (status 2) */
 static int batch_set_remap(ffhip_batch *b, item **its, int n) {
@@ -596,6 +632,23 @@ static int batch_set_remap(ffhip_batch *b, item **its, int n) {
     }
     if (0 == rc) rc = ffhip_batch_set_remap(b, nb, codes, len, args.remap_band);
     if (0 == rc && md_out) rc = ffhip_batch_set_remap_mods(b, mods_context, mods_all_paths ? 1 : 0);
+    if (0 == rc && vr_out) {           /* every read's variants: those of its record, in file order (a record that cannot be used has none) */
+        size_t total = 0, at = 0;
+        for (int i = 0; i < n && i < nb; i++) if (its[i]->rm_ref >= 0 && len[i]) total += flappie_variants_of(vr_vars, its[i]->rm_ref, NULL);
+        ffhip_variant *all = malloc((total ? total : 1) * sizeof *all);
+        const ffhip_variant **lists = calloc(nb > 0 ? nb : 1, sizeof *lists);
+        size_t *nvar = calloc(nb > 0 ? nb : 1, sizeof *nvar);
+        if (NULL == all || NULL == lists || NULL == nvar) rc = -1;
+        for (int i = 0; 0 == rc && i < n && i < nb; i++) {
+            if (its[i]->rm_ref < 0 || 0 == len[i]) continue;
+            lists[i] = all + at;
+            at += nvar[i] = flappie_variants_of(vr_vars, its[i]->rm_ref, all + at);
+        }
+        if (0 == rc) rc = ffhip_batch_set_remap_variants(b, nb, lists, nvar, vars_context, vars_all_paths ? 1 : 0);
+        free(all);
+        free(lists);
+        free(nvar);
+    }
     free(codes);
     free(len);
     return rc;
@@ -904,6 +957,12 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
                     if (0 != ffhip_batch_site_mods(b, i, &sm, &nsm) || NULL == sm) warnx("No site mods returned for %s: %s", its[i]->filename, ffhip_last_error());
                     else if (NULL != (its[i]->smods = malloc((nsm ? nsm : 1) * sizeof(ffhip_site_mod)))) { memcpy(its[i]->smods, sm, nsm * sizeof(ffhip_site_mod)); its[i]->nsmods = nsm; }
                 }
+                if (vr_out && 1 == rc.status) {                /* ... and the scores of its variants */
+                    const ffhip_variant_call *vc = NULL;
+                    size_t nvc = 0;
+                    if (0 != ffhip_batch_variant_calls(b, i, &vc, &nvc) || NULL == vc) warnx("No variant calls returned for %s: %s", its[i]->filename, ffhip_last_error());
+                    else if (NULL != (its[i]->vcalls = malloc((nvc ? nvc : 1) * sizeof(ffhip_variant_call)))) { memcpy(its[i]->vcalls, vc, nvc * sizeof(ffhip_variant_call)); its[i]->nvcalls = nvc; }
+                }
             }
         }
         if (tr_refs && its[i]->tr_ref >= 0) {                  /* the call against its truth, in signal order whatever --reverse does below */
@@ -1115,6 +1174,16 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
                             warnx("The site mods of %s do not fit its sequence", it->filename);
                         else { md_count[0]++; md_count[1] += it->nsmods; }
                     }
+                    if (vr_out && 1 == it->rm_status) {
+                        const size_t nv = flappie_variants_of(vr_vars, it->rm_ref, NULL);
+                        ffhip_variant *var = malloc((nv ? nv : 1) * sizeof *var);
+                        if (NULL == it->vcalls || it->nvcalls != nv || it->rm_L != L || NULL == var) warnx("No variant calls for %s", it->filename);
+                        else if (flappie_variants_of(vr_vars, it->rm_ref, var), 0 != flappie_variants_write(vr_out, rm_refs->name[it->rm_ref], rm_refs->codes[it->rm_ref], L,
+                                                                                                              "ACGTZ", var, it->vcalls, nv))
+                            warnx("The variant calls of %s do not fit its sequence", it->filename);
+                        else if (nv) { vr_count[0]++; vr_count[1] += nv; vr_done[it->rm_ref] = 1; }
+                        free(var);
+                    }
                 }
             }
             if (tr_refs) {                                     /* likewise for --truth */
@@ -1149,6 +1218,9 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
         free(it->smods);
         it->smods = NULL;
         it->nsmods = 0;
+        free(it->vcalls);
+        it->vcalls = NULL;
+        it->nvcalls = 0;
         it->have_rm = 0;
         it->rm_ref = -1;
         free(it->tr_ops);
@@ -1862,6 +1934,7 @@ int main(int argc, char *argv[]) {
     if (args.truth) errx(EXIT_FAILURE, "--truth is flappie's: the run-length model's call is a list of runs");
     if (args.remap_events) errx(EXIT_FAILURE, "--remap-events is flappie's: it goes with --remap, which the run-length model does not have");
     if (mods_path) errx(EXIT_FAILURE, "--remap-mods is flappie's: it goes with --remap, which the run-length model does not have");
+    if (vars_path || vars_out_path || vars_opts) errx(EXIT_FAILURE, "--remap-variants is flappie's: it goes with --remap, which the run-length model does not have");
 #else
     /* --barcodes: every refusal before any file or the GPU is touched */
     if (args.bc_opts && NULL == args.barcodes) errx(EXIT_FAILURE, "--barcode-window, --barcode-max-dist, --barcode-min-sep, --barcode-both-ends and --trim-barcodes go with --barcodes");
@@ -1880,6 +1953,9 @@ int main(int argc, char *argv[]) {
     if ((mods_context_set || mods_all_paths) && NULL == mods_path) errx(EXIT_FAILURE, "--remap-mods-context and --remap-mods-all-paths go with --remap-mods");
     if (mods_path && !flappie_model_has_modbase(args.model))      /* (the registry knows: before any file or the GPU is touched) */
         errx(EXIT_FAILURE, "--remap-mods needs a model with a modified base (r941_5mC); \"%s\" has none", flappie_model_string(args.model));
+    if (vars_path && NULL == args.remap) errx(EXIT_FAILURE, "--remap-variants goes with --remap");
+    if ((vars_opts || vars_out_path) && NULL == vars_path) errx(EXIT_FAILURE, "--remap-variants-out, --remap-variants-context and --remap-variants-all-paths go with --remap-variants");
+    if (vars_path && NULL == vars_out_path) errx(EXIT_FAILURE, "--remap-variants and --remap-variants-out go together");
     if (args.remap) {
         char why[256];
         rm_refs = flappie_remap_refs_read(args.remap, flappie_model_has_modbase(args.model) ? "ACGTZ" : "ACGT", why, sizeof why);
@@ -1889,6 +1965,15 @@ int main(int argc, char *argv[]) {
         if (NULL == (rm_out = fopen(args.remap_out, "w"))) errx(EXIT_FAILURE, "--remap-out %s: cannot be written", args.remap_out);
         if (args.remap_events && NULL == (ev_out = fopen(args.remap_events, "w"))) errx(EXIT_FAILURE, "--remap-events %s: cannot be written", args.remap_events);
         if (mods_path && NULL == (md_out = fopen(mods_path, "w"))) errx(EXIT_FAILURE, "--remap-mods %s: cannot be written", mods_path);
+        if (vars_path) {
+            vr_vars = flappie_variants_read(vars_path, rm_refs, flappie_model_has_modbase(args.model) ? "ACGTZ" : "ACGT", why, sizeof why);
+            if (NULL == vr_vars) errx(EXIT_FAILURE, "--remap-variants %s: %s", vars_path, why);
+            for (int k = 0; k < FLAPPIE_VARIANTS_KINDS; k++)
+                if (vr_vars->skipped[k]) warnx("--remap-variants: line %zu %s: it is skipped, and %llu like it (%s)", vr_vars->skipped_line[k], flappie_variants_kind(k),
+                                               vr_vars->skipped[k] - 1, vr_vars->skipped_text[k]);
+            if (NULL == (vr_done = calloc(rm_refs->n > 0 ? rm_refs->n : 1, 1))) errx(EXIT_FAILURE, "--remap-variants %s: out of memory", vars_path);
+            if (NULL == (vr_out = fopen(vars_out_path, "w"))) errx(EXIT_FAILURE, "--remap-variants-out %s: cannot be written", vars_out_path);
+        }
     }
     /* --truth: likewise */
     if ((NULL == args.truth) != (NULL == args.truth_out)) errx(EXIT_FAILURE, "--truth and --truth-out go together");
@@ -2008,6 +2093,15 @@ int main(int argc, char *argv[]) {
         if (md_out) {                  /* mapped reads written, and their sites */
             fprintf(stderr, "mods\treads\t%llu\nmods\tsites\t%llu\n", md_count[0], md_count[1]);
             if (0 != fclose(md_out)) warnx("--remap-mods %s: write failed", mods_path);
+        }
+        if (vr_out) {                  /* mapped reads written, their variants, the file's lines that were skipped, and the variants of records no mapped read had */
+            unsigned long long skipped = 0, unmapped = 0;
+            for (int k = 0; k < FLAPPIE_VARIANTS_KINDS; k++) skipped += vr_vars->skipped[k];
+            for (int k = 0; k < rm_refs->n; k++) if (!vr_done[k]) unmapped += flappie_variants_of(vr_vars, k, NULL);
+            fprintf(stderr, "variants\treads\t%llu\nvariants\tscored\t%llu\nvariants\tskipped\t%llu\nvariants\tunmapped\t%llu\n", vr_count[0], vr_count[1], skipped, unmapped);
+            if (0 != fclose(vr_out)) warnx("--remap-variants-out %s: write failed", vars_out_path);
+            flappie_variants_free(vr_vars);
+            free(vr_done);
         }
         flappie_remap_refs_free(rm_refs);
     }

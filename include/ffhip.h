@@ -123,6 +123,13 @@ typedef struct {
  * and come down in ONE extra copy, enqueued where the remap buffer's copy is.  Everything else the run returns is that of the same run without the flag.  Without
  * FFHIP_RUN_REMAP, or on a model whose nbase is not 5: FFHIP_EINVAL; the run-length model and FFHIP_RUN_NO_DECODE are refused as for remap. */
 #define FFHIP_RUN_REMAP_MODS 262144u
+/* With FFHIP_RUN_REMAP, any flip-flop model (nbase 4 or 5): for every variant of ffhip_batch_set_remap_variants -- a short edit of a mapped read's sequence: a
+ * substitution, an insertion or a deletion -- the log scores of the signal around it under the sequence as given (ref) and under the edited one (alt)
+ * (ffhip_batch_variant_calls below, "variants"), made on the device (k_variants) behind k_remap from the transition scores, the coded sequences and the path it has
+ * just written.  The records are NOT part of the result block: they live in ONE buffer of their own (16 bytes a variant, one read behind the other) and come down
+ * in ONE extra copy, enqueued where the remap buffer's copy is.  Everything else the run returns -- events and site mods included -- is that of the same run
+ * without the flag.  Without FFHIP_RUN_REMAP, or with no variants set: FFHIP_EINVAL; the run-length model and FFHIP_RUN_NO_DECODE are refused as for remap. */
+#define FFHIP_RUN_REMAP_VARIANTS 524288u
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -506,6 +513,48 @@ int ffhip_batch_set_remap_mods(ffhip_batch *b, int context, int all_paths);
 int ffhip_batch_site_mods(const ffhip_batch *b, int read, const ffhip_site_mod **sm, size_t *nsite);
 int ffhip_op_site_mods(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, const uint8_t *rm, size_t nblock, int context, int all_paths,
                        ffhip_site_mod *out, size_t *nsite);
+/* Variants: does this read support the reference allele or the alternative one?  The other half of per-read scoring against a reference: the computation of
+ * "site mods" with two generalisations -- the two hypotheses may be any short edit of the sequence, not only C <-> Z, and they may differ in length.
+ *   Inputs: a read of N >= 1 blocks with transition scores T[b][.]; nbase 4 or 5; the sequence s of L codes of ffhip_batch_set_remap; the read's remap result
+ *     with status 1, its path rm and start[0 .. L], exactly as under "site mods"; a context c, 1 <= c <= 23; the mode, best-path or all-paths.
+ *   A variant is { pos p, nref r, nalt k, alt[0 .. k - 1] }: 0 <= r <= 16, 0 <= k <= 16, r + k >= 1; 0 <= p, p + r <= L; every alt code < nbase;
+ *     L - r + k >= 1.  The ref hypothesis is s itself; the alt hypothesis is s^alt = s[0:p] + alt + s[p+r:], of L - r + k codes.  r = 0 is a pure insertion in
+ *     front of position p (p = L: behind the last base), k = 0 a pure deletion.  ref = alt letter for letter is allowed and gives two equal scores.
+ *   Window: lo = max(0, p - c), hi = min(L - 1, p + r + c - 1); P_ref = hi - lo + 1 positions of s, P_alt = P_ref - r + k positions of s^alt; under the limits
+ *     above both are between 1 and 62.  Blocks: t0 = start[lo]; t1 = start[hi + 1] - 1 if hi < L - 1 (block start[hi + 1] - 1 is the move out of hi), else N;
+ *     n = t1 - t0.  BOTH hypotheses are scored over the same blocks t0 .. t1 - 1, each from its first window position at t0 to its last window position at t1:
+ *     the ref hypothesis over positions lo .. hi of s, the alt hypothesis over positions lo .. lo + P_alt - 1 of s^alt.
+ *   Coding: q^ref is remap's coding of s.  q^alt is the flip-flop coding (the rule under "remap") of the WHOLE s^alt: equal to q before p; behind the edit it may
+ *     differ between flip and flop until a run of equal letters ends, and so may still differ at the window's last position.
+ *   Recursion: that of "site mods", over each hypothesis's own P positions j = 0 .. P - 1: X_t0[0] = 0, X_t0[j > 0] = -inf; for t = t0 .. t1 - 1:
+ *     stay = X_t[j] + T[t][idx(q_j, q_j)], move = X_t[j-1] + T[t][idx(q_{j-1}, q_j)] (-inf for j = 0), idx = remap's trans_lookup.
+ *     Best-path mode, in float32, each term ONE rounded add: X_{t+1}[j] = move if move > stay (a strict compare) else stay; reproducible to the bit.
+ *     All-paths mode, in fp64 (T converted exactly): X_{t+1}[j] = m + log1p(exp(-|stay - move|)), m = max(stay, move); m = -inf gives -inf, never a NaN; the
+ *     score is rounded to float32 once.
+ *     The score is X_t1[P - 1].  A hypothesis with n < P - 1 has no path: its score is -inf, which comes out of the recursion and is no special case (the ref
+ *     hypothesis always has one: the remap path itself).
+ *   Output per variant: the 16 bytes { int32 index; int32 nblock = n; float ref; float alt; }; index is the variant's place in the read's list, and the records
+ *     stand in list order.  The log-likelihood ratio ref - alt and any probability are left to the reader.
+ *   The order of operations depends on the window and the variant alone: a read's records are the same bytes in a one-read-a-row, ragged, packed, paired,
+ *     launch-per-step or f32-rerun batch (there from the re-run's own transitions and path, as remap's record is) and from one run to the next, in both modes.
+ * ffhip_batch_set_remap_variants: one list a read (vars[r]: nvar[r] variants; nvar[r] = 0: none, vars[r] may be NULL), the context and the mode of the batch's
+ *   later runs with the flag.  Called AFTER ffhip_batch_set_remap, because it validates against those L; the lists are copied.  vars = NULL detaches, and so does
+ *   a later ffhip_batch_set_remap.  Not between a run and its finish.  FFHIP_EINVAL, with a text that names the read and the index: any limit above violated, a
+ *   variant for a read without a sequence; also a context outside 1 .. 23, nread not the batch's, and a call with no sequences set.
+ * ffhip_batch_variant_calls: after ffhip_batch_finish of a run with FFHIP_RUN_REMAP | FFHIP_RUN_REMAP_VARIANTS; *vc points into the batch (*nvar records in list
+ *   order, valid until the next run); *vc = NULL and *nvar = 0 unless the read's remap status is 1.
+ * ffhip_op_variants: the kernels on ONE read from host arrays: the scores (2 nbase (nbase + 1) rows, a column a block), L codes, nblock = trans.nc bytes of
+ *   0 / 1, nvar variants; out: caller-owned, nvar records.  What ffhip_op_site_mods refuses (a code >= nbase, sum rm != L - 1, a byte > 1, L = 0, nblock = 0 or
+ *   != trans.nc or more than 2^30), nbase other than 4 or 5, a context outside 1 .. 23 and every invalid variant: FFHIP_EINVAL.
+ * The records' buffer and its pinned mirror, the workspace of starts (L + 1 int32 a read with variants) and the list of reads and variants are sized at the front
+ * of every run with the flag, grown when a run needs more, freed with the batch and counted by ffhip_debug_batch_device_bytes; when one cannot be had:
+ * FFHIP_ENOMEM with the bytes in the text. */
+typedef struct { int32_t pos; uint8_t nref, nalt; uint8_t alt[16]; uint8_t pad[2]; } ffhip_variant;      /* 24 bytes */
+typedef struct { int32_t index, nblock; float ref, alt; } ffhip_variant_call;                              /* 16 bytes */
+int ffhip_batch_set_remap_variants(ffhip_batch *b, int nread, const ffhip_variant *const *vars, const size_t *nvar, int context, int all_paths);
+int ffhip_batch_variant_calls(const ffhip_batch *b, int read, const ffhip_variant_call **vc, size_t *nvar);
+int ffhip_op_variants(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, const uint8_t *rm, size_t nblock,
+                      const ffhip_variant *vars, size_t nvar, int context, int all_paths, ffhip_variant_call *out /* nvar */);
 /* Truth: how close a call is to the sequence it should have been.
  *   Inputs: the call s of n >= 0 bases -- the batch's called letters in signal order, Z read as C (as the barcode search reads it); the truth t of m bases as codes
  *     0 .. nbase - 1, code 4 (Z) folded to 1 (C) for the comparison; the band half-width W >= 0.
