@@ -31,6 +31,9 @@ RUN_RLE_RECORDS = 2048    # ... and every run's shape, scale and dwell
 RLE_SCALE_DEFAULT = (1.02, 1.04, 1.04, 1.02)      # decode_runnie.py's default --scale (A, C, G, T)
 RUN_MOD_PROBS = 4096      # 5-base model: 5mC probabilities (SAM ML bytes) of the called bases made on the device (Batch.mod_probs)
 RUN_MOVES = 8192          # flip-flop model: the move table (one byte a block, 1 where a base is emitted) made on the device (Batch.moves)
+RUN_ADAPTERS = 1048576   # flip-flop model: one adapter record a read (a header and up to 15 hits) made on the device against the kit of Batch.set_adapters (Batch.adapters)
+ADAPTER_SEGMENT = 512    # FFHIP_ADAPTER_SEGMENT (include/ffhip.h "adapters"): the columns one wave of k_adapters owns; checked against the library at load
+ADAPTER_MAX_HITS = 15
 RUN_BARCODES = 16384      # flip-flop model: one barcode record a read made on the device against the kit of Batch.set_barcodes (Batch.barcode)
 RUN_REMAP = 32768         # flip-flop model: each read's signal mapped to the sequence of Batch.set_remap on the device (Batch.remap)
 RUN_TRUTH = 65536         # flip-flop model: each read's call aligned to the truth of Batch.set_truth on the device (Batch.truth)
@@ -89,6 +92,16 @@ class CBarcodeCall(C.Structure):
     """ffhip_barcode_call (include/ffhip.h): 16 bytes"""
     _fields_ = [("best", C.c_int16), ("best_dist", C.c_uint8), ("second_dist", C.c_uint8), ("front_dist", C.c_uint8), ("rear_dist", C.c_uint8),
                 ("ends", C.c_uint8), ("pad", C.c_uint8), ("front_end", C.c_int16), ("rear_end", C.c_int16), ("reserved", C.c_int32)]
+
+
+class CAdapterHeader(C.Structure):
+    """ffhip_adapter_header (include/ffhip.h): 16 bytes"""
+    _fields_ = [("nhit", C.c_int32), ("len", C.c_int32), ("kept", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CAdapterHit(C.Structure):
+    """ffhip_adapter_hit (include/ffhip.h): 16 bytes"""
+    _fields_ = [("start", C.c_int32), ("end", C.c_int32), ("pattern", C.c_int16), ("orientation", C.c_uint8), ("dist", C.c_uint8), ("reserved", C.c_int32)]
 
 
 class CRemapCall(C.Structure):
@@ -226,6 +239,17 @@ def lib():
     L.ffhip_batch_set_barcodes.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.ffhip_batch_barcode.argtypes = [vp, C.c_int, C.POINTER(CBarcodeCall)]
     L.ffhip_op_barcode_scores.argtypes = [vp, vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.ffhip_adapters_upload.restype = vp
+    L.ffhip_adapters_upload.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p)]
+    L.ffhip_adapters_free.restype = None
+    L.ffhip_adapters_free.argtypes = [vp]
+    L.ffhip_batch_set_adapters.argtypes = [vp, vp, C.c_int]
+    L.ffhip_batch_adapters.argtypes = [vp, C.c_int, C.POINTER(CAdapterHeader), C.POINTER(C.POINTER(CAdapterHit))]
+    L.ffhip_op_adapter_scores.argtypes = [vp, vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8)]
+    L.ffhip_op_adapter_hits.argtypes = [vp, vp, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(CAdapterHeader), C.POINTER(CAdapterHit)]
+    L.ffhip_adapter_segment.restype = C.c_int
+    L.ffhip_adapter_segment.argtypes = []
+    assert L.ffhip_adapter_segment() == ADAPTER_SEGMENT, "binding.py and libffhip.so disagree on FFHIP_ADAPTER_SEGMENT"
     L.ffhip_batch_set_remap.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t), C.c_int]
     L.ffhip_batch_remap.argtypes = [vp, C.c_int, C.POINTER(CRemapCall)]
     L.ffhip_op_remap.argtypes = [vp, CFMat, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_float)]
@@ -449,6 +473,31 @@ class Barcodes:
             self.h = None
 
 
+class Adapters:
+    """An adapter kit on the device (ffhip_adapters): `seqs` are 1 .. 32 patterns over ACGT of 1 .. 64 bases, each searched as given and as its reverse complement."""
+
+    def __init__(self, engine: Engine, seqs):
+        self.engine = engine
+        self.seqs = [x if isinstance(x, bytes) else str(x).encode() for x in seqs]
+        self.n = len(self.seqs)
+        arr = (C.c_char_p * max(1, self.n))(*self.seqs)
+        self.h = lib().ffhip_adapters_upload(engine.h, self.n, arr)
+        if not self.h:
+            raise FFHipError(lib().ffhip_last_error().decode())
+
+    def close(self):
+        if self.h:
+            lib().ffhip_adapters_free(self.h)
+            self.h = None
+
+
+def _adapter_record(header, hits) -> dict:
+    """a header and its hit slots as a dict: nhit, len, kept, hits = kept tuples (start, end, pattern, orientation, dist)"""
+    kept = int(header.kept)
+    return {"nhit": int(header.nhit), "len": int(header.len), "kept": kept,
+            "hits": [(int(hits[i].start), int(hits[i].end), int(hits[i].pattern), int(hits[i].orientation), int(hits[i].dist)) for i in range(kept)]}
+
+
 BARCODE_FIELDS = ("best", "best_dist", "second_dist", "front_dist", "rear_dist", "ends", "front_end", "rear_end")
 
 
@@ -595,6 +644,16 @@ class Batch:
     def set_barcodes(self, kit, max_dist: int = -1, min_sep: int = -1, both_ends: bool = False):
         """the kit and parameters of later runs with RUN_BARCODES (ffhip_batch_set_barcodes); max_dist < 0: floor(Lmin / 4), min_sep < 0: 3; kit None detaches"""
         _check(lib().ffhip_batch_set_barcodes(self.h, kit.h if kit is not None else None, int(max_dist), int(min_sep), int(bool(both_ends))))
+
+    def set_adapters(self, kit, max_dist: int = -1):
+        """the kit and bound of later runs with RUN_ADAPTERS (ffhip_batch_set_adapters); max_dist < 0: floor(L / 4) of each pattern; kit None detaches"""
+        _check(lib().ffhip_batch_set_adapters(self.h, kit.h if kit is not None else None, int(max_dist)))
+
+    def adapters(self, read: int) -> dict:
+        """adapter record of a run with RUN_ADAPTERS (ffhip_batch_adapters): nhit, len, kept, hits = kept tuples (start, end, pattern, orientation, dist) by (end, q)"""
+        h, hits = CAdapterHeader(), C.POINTER(CAdapterHit)()
+        _check(lib().ffhip_batch_adapters(self.h, read, C.byref(h), C.byref(hits)))
+        return _adapter_record(h, hits)
 
     def barcode(self, read: int) -> dict:
         """barcode record of a run with RUN_BARCODES (ffhip_batch_barcode): the fields of BARCODE_FIELDS as ints"""
@@ -837,6 +896,24 @@ def op_barcode_scores(engine: Engine, kit: Barcodes, bases) -> tuple:
     dist, end = np.zeros((2, kit.n), np.int32), np.zeros((2, kit.n), np.int32)
     _check(lib().ffhip_op_barcode_scores(engine.h, kit.h, b, len(b), dist.ctypes.data_as(C.POINTER(C.c_int32)), end.ctypes.data_as(C.POINTER(C.c_int32))))
     return dist, end
+
+
+def op_adapter_scores(engine: Engine, kit: Adapters, bases) -> np.ndarray:
+    """ffhip_op_adapter_scores: the whole score rows uint8 [2 n][len + 1], row q = 2 k + orientation, of ONE call (a str over ACGTZ, may be empty)"""
+    b = bases if isinstance(bases, bytes) else str(bases).encode()
+    d = np.zeros((2 * kit.n, len(b) + 1), np.uint8)
+    _check(lib().ffhip_op_adapter_scores(engine.h, kit.h, b, len(b), d.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return d
+
+
+def op_adapter_hits(engine: Engine, kit: Adapters, bases, max_dist: int = -1) -> dict:
+    """ffhip_op_adapter_hits: the record of ONE call, as Batch.adapters gives it; "raw": the 15 hit slots as 60 int32 (the slots no hit took are zero)"""
+    b = bases if isinstance(bases, bytes) else str(bases).encode()
+    h, hits = CAdapterHeader(), (CAdapterHit * ADAPTER_MAX_HITS)()
+    _check(lib().ffhip_op_adapter_hits(engine.h, kit.h, int(max_dist), b, len(b), C.byref(h), hits))
+    rec = _adapter_record(h, hits)
+    rec["raw"] = np.frombuffer(bytes(hits), np.int32).copy()
+    return rec
 
 
 def op_remap(engine: Engine, trans: np.ndarray, nbase: int, codes, band: int = 2048) -> tuple:

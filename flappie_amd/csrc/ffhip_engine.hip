@@ -762,6 +762,12 @@ struct ffhip_batch {
     int bc_max_dist = 0, bc_min_sep = 3, bc_both = 0;
     ffhip_barcode_call *bc_dev = nullptr, *bc_host = nullptr;
     int bc_valid = 0;                   // the last run made them
+    // Adapter records (FFHIP_RUN_ADAPTERS, k_adapters): 256 bytes a read, likewise a device buffer and a pinned host buffer of their own, cap_reads records each,
+    // created by the first run that asks, and one copy of their own beside the block's
+    const ffhip_adapters *ad_kit = nullptr;
+    int ad_max_dist = -1;
+    uint8_t *ad_dev = nullptr, *ad_host = nullptr;
+    int ad_valid = 0;                   // the last run made them
     // Remap (FFHIP_RUN_REMAP, k_remap): the coded sequences of ffhip_batch_set_remap on the host and (rmp_dseq) on the device; ONE buffer of cap_reads 16-byte records and,
     // behind them, a byte a block in the layout of the (Tb + 1)-entry buffers (rmp_dev, its pinned mirror rmp_host), with one copy of its own beside the block's; the
     // reads' list (pinned, and on the device) and the traceback workspace, both written by the front of every run that asks, the workspace grown when a run needs more
@@ -913,6 +919,7 @@ extern "C" void ffhip_batch_destroy(ffhip_batch *b) {
     for (void *p : b->owned) hipFree(p);
     b->res.release();
     if (b->bc_host) hipHostFree(b->bc_host);
+    if (b->ad_host) hipHostFree(b->ad_host);
     if (b->rmp_host) hipHostFree(b->rmp_host);
     if (b->rmp_hlist) hipHostFree(b->rmp_hlist);
     if (b->tru_host) hipHostFree(b->tru_host);
@@ -1525,6 +1532,18 @@ static int ensure_barcode_buffers(ffhip_batch *b) {
     return FFHIP_OK;
 }
 
+static_assert(sizeof(ffhip_adapter_header) == 16 && sizeof(ffhip_adapter_hit) == 16 && FFHIP_ADAPTER_SEGMENT == kAdSeg && FFHIP_ADAPTER_MAX_HITS == kAdapterMaxHits,
+              "k_adapters writes a header and a hit as one 16-byte store each");
+static int ensure_adapter_buffers(ffhip_batch *b) {
+    const size_t bytes = (size_t)b->cap_reads * kAdapterRecBytes;
+    if (!b->ad_dev && !(b->ad_dev = (uint8_t *)dalloc(b, bytes, true))) return FFHIP_ENOMEM;
+    if (!b->ad_host) {
+        if (hipHostMalloc((void **)&b->ad_host, bytes, hipHostMallocDefault) != hipSuccess) { b->ad_host = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation of %zu bytes failed", bytes); }
+        memset(b->ad_host, 0, bytes);
+    }
+    return FFHIP_OK;
+}
+
 // a device buffer of the batch that grows: the old one is given back first, once the batch's stream has drained (a run that was never finished may still read it)
 static int dgrow(ffhip_batch *b, void **p, size_t *cap, size_t need, const char *what) {
     if (*p && need <= *cap) return FFHIP_OK;
@@ -1842,6 +1861,13 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
         if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "barcodes need a decoded run (FFHIP_RUN_NO_DECODE is set)");
         if (int rc = ensure_barcode_buffers(b)) return rc;
     }
+    b->ad_valid = 0;
+    if (flags & FFHIP_RUN_ADAPTERS) {      // (likewise)
+        if (!b->ad_kit) return set_err(FFHIP_EINVAL, "adapters: no kit is attached to the batch (ffhip_batch_set_adapters)");
+        if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "adapters: a flip-flop model only (the run-length model has no base strings)");
+        if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "adapters need a decoded run (FFHIP_RUN_NO_DECODE is set)");
+        if (int rc = ensure_adapter_buffers(b)) return rc;
+    }
     b->rmp_valid = 0;
     if (flags & FFHIP_RUN_REMAP) {         // (not a section of the result block either)
         if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "remap: a flip-flop model only (the run-length model's scores are not transitions between bases)");
@@ -2158,6 +2184,11 @@ static int run_back(ffhip_batch *b) {
                 b->bc_valid = 1;
                 b->launches[5]++;
             }
+            if (flags & FFHIP_RUN_ADAPTERS) {           // likewise (run_front checked the kit and the model)
+                launch_adapters(s, b->ad_kit->kit, b->bases(), b->lens(), b->ad_dev, nR, Tb, tbr, rmap, b->ad_max_dist);
+                b->ad_valid = 1;
+                b->launches[5]++;
+            }
             if (flags & FFHIP_RUN_TRUTH) truth_launch(b, tbr, rmap);          // from the strings and lengths too (run_front made the lists)
             if (flags & FFHIP_RUN_REMAP) remap_launch(b, nR, tbr, rmap);      // from the transitions, whatever the path was decoded from (run_front made the lists)
             if (flags & FFHIP_RUN_EVENTS) events_launch(b, tbr, rmap);        // from the path k_remap has just written and the signal the convolutions read
@@ -2187,6 +2218,7 @@ static int run_back(ffhip_batch *b) {
     if (b->packed) {
         HIP_TRY(hipMemcpyAsync(b->res.host, b->res.dev, b->res.copy_bytes(flags), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
         if (b->bc_valid) HIP_TRY(hipMemcpyAsync(b->bc_host, b->bc_dev, (size_t)nR * sizeof(ffhip_barcode_call), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the barcode records' one copy
+        if (b->ad_valid) HIP_TRY(hipMemcpyAsync(b->ad_host, b->ad_dev, (size_t)nR * kAdapterRecBytes, hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the adapter records' one copy
         if (b->rmp_valid) HIP_TRY(hipMemcpyAsync(b->rmp_host, b->rmp_dev, b->rmp_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the remap records' and moves' one copy
         if (b->evt_valid && b->evt_bytes()) HIP_TRY(hipMemcpyAsync(b->evt_host, b->evt_dev, b->evt_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the events' one copy
         if (b->smd_valid && b->smd_bytes()) HIP_TRY(hipMemcpyAsync(b->smd_host, b->smd_dev, b->smd_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the site mods' one copy
@@ -2243,7 +2275,7 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
     const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
     b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
     b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0; b->rmp_valid = 0; b->tru_valid = 0; b->evt_valid = 0; b->smd_valid = 0; b->var_valid = 0;
+    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0; b->ad_valid = 0; b->rmp_valid = 0; b->tru_valid = 0; b->evt_valid = 0; b->smd_valid = 0; b->var_valid = 0;
     return FFHIP_OK;
 }
 
@@ -2330,6 +2362,7 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
         sd->ran = sd->finished = 0;
         sd->run_scale = b->run_scale;
         sd->bc_kit = b->bc_kit; sd->bc_max_dist = b->bc_max_dist; sd->bc_min_sep = b->bc_min_sep; sd->bc_both = b->bc_both;      // (last_flags asks the side batch for the records too)
+        sd->ad_kit = b->ad_kit; sd->ad_max_dist = b->ad_max_dist;
         if (fl & FFHIP_RUN_REMAP) {                       // ... and for these reads' sequences
             std::vector<std::vector<unsigned short>> sq(16);
             std::vector<signed char> st(16, 0);
@@ -2373,6 +2406,10 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
             if (b->bc_valid && sd->bc_valid) {          // and the read's barcode record, both halves
                 HIP_TRY(hipMemcpyAsync(b->bc_dev + r, sd->bc_dev + k, sizeof(ffhip_barcode_call), hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
                 b->bc_host[r] = sd->bc_host[k];
+            }
+            if (b->ad_valid && sd->ad_valid) {          // and its adapter record, both halves
+                HIP_TRY(hipMemcpyAsync(b->ad_dev + r * kAdapterRecBytes, sd->ad_dev + (size_t)k * kAdapterRecBytes, kAdapterRecBytes, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                memcpy(b->ad_host + r * kAdapterRecBytes, sd->ad_host + (size_t)k * kAdapterRecBytes, kAdapterRecBytes);
             }
             if (b->rmp_valid && sd->rmp_valid) {        // and its remap record and moves, both halves
                 const size_t mv = (size_t)b->cap_reads * 16 + r1, smv = (size_t)sd->cap_reads * 16 + (size_t)k * L;
@@ -2438,6 +2475,8 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
         HIP_TRY(hipMemcpyAsync(b->res.host, b->res.dev, b->res.copy_bytes(b->last_flags), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
         if (b->bc_valid)                                     // the barcode records' one copy (a packed batch: enqueued in run_back, as the block's)
             HIP_TRY(hipMemcpyAsync(b->bc_host, b->bc_dev, (size_t)batch_nreads(b) * sizeof(ffhip_barcode_call), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
+        if (b->ad_valid)                                     // the adapter records' one copy (likewise)
+            HIP_TRY(hipMemcpyAsync(b->ad_host, b->ad_dev, (size_t)batch_nreads(b) * kAdapterRecBytes, hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
         if (b->rmp_valid)                                    // the remap records' and moves' one copy (likewise)
             HIP_TRY(hipMemcpyAsync(b->rmp_host, b->rmp_dev, b->rmp_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
         if (b->evt_valid && b->evt_bytes())                  // the events' one copy (likewise)
@@ -2595,6 +2634,61 @@ extern "C" int ffhip_batch_barcode(const ffhip_batch *b, int read, ffhip_barcode
     if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
     if (!b->bc_valid || !b->bc_host) return set_err(FFHIP_EINVAL, "barcode records were not made in this run (FFHIP_RUN_BARCODES)");
     *out = b->bc_host[read];
+    return FFHIP_OK;
+}
+
+// ---- adapters (include/ffhip.h "adapters"; the kernel: ffhip_adapters.hip)
+extern "C" int ffhip_adapter_segment(void) { return kAdSeg; }
+extern "C" ffhip_adapters *ffhip_adapters_upload(ffhip_engine *eng, int n, const char *const *seq) {
+    if (!eng || !seq) { set_err(FFHIP_EINVAL, "null engine or kit"); return nullptr; }
+    if (n < 1 || n > kAdapterMaxKit) { set_err(FFHIP_EINVAL, "an adapter kit holds 1 .. %d patterns, not %d", kAdapterMaxKit, n); return nullptr; }
+    std::vector<unsigned long long> peq((size_t)n * 8, 0ull);       // [2 n][4]: as given, then the reverse complement
+    std::vector<int> len(n, 0);
+    for (int k = 0; k < n; k++) {
+        const size_t L = seq[k] ? strnlen(seq[k], kAdapterMaxLen + 1) : 0;
+        if (L < 1 || L > (size_t)kAdapterMaxLen) { set_err(FFHIP_EINVAL, "adapter %d: a pattern has 1 .. %d bases", k, kAdapterMaxLen); return nullptr; }
+        for (size_t i = 0; i < L; i++) {
+            const char *at = strchr("ACGT", seq[k][i]);
+            if (!at) { set_err(FFHIP_EINVAL, "adapter %d: character %zu is not one of ACGT", k, i); return nullptr; }
+            const size_t c = (size_t)(at - "ACGT");
+            peq[((size_t)2 * k) * 4 + c] |= 1ull << i;
+            peq[((size_t)2 * k + 1) * 4 + (3 - c)] |= 1ull << (L - 1 - i);
+        }
+        len[k] = (int)L;
+    }
+    hipSetDevice(eng->device);
+    ffhip_adapters *kit = new ffhip_adapters();
+    kit->eng = eng;
+    if (hipMalloc(&kit->d_peq, peq.size() * 8) != hipSuccess || hipMalloc(&kit->d_len, len.size() * 4) != hipSuccess) {
+        set_err(FFHIP_ENOMEM, "device allocation failed"); ffhip_adapters_free(kit); return nullptr;
+    }
+    if (hipMemcpy(kit->d_peq, peq.data(), peq.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(kit->d_len, len.data(), len.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        set_err(FFHIP_EHIP, "upload of the adapter kit failed"); ffhip_adapters_free(kit); return nullptr;
+    }
+    kit->kit = AdapterKit{ (const unsigned long long *)kit->d_peq, (const int *)kit->d_len, n };
+    return kit;
+}
+extern "C" void ffhip_adapters_free(ffhip_adapters *kit) {
+    if (!kit) return;
+    hipSetDevice(kit->eng->device);
+    if (kit->d_peq) hipFree(kit->d_peq);
+    if (kit->d_len) hipFree(kit->d_len);
+    delete kit;
+}
+extern "C" int ffhip_batch_set_adapters(ffhip_batch *b, const ffhip_adapters *kit, int max_dist) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (!kit) { b->ad_kit = nullptr; return FFHIP_OK; }
+    if (kit->eng != b->eng) return set_err(FFHIP_EINVAL, "the adapter kit belongs to another engine");
+    b->ad_kit = kit;
+    b->ad_max_dist = max_dist < 0 ? -1 : std::min(max_dist, kAdapterMaxLen - 1);
+    return FFHIP_OK;
+}
+extern "C" int ffhip_batch_adapters(const ffhip_batch *b, int read, ffhip_adapter_header *header, const ffhip_adapter_hit **hits) {
+    if (!results_ok(b, read) || !header || !hits) return FFHIP_EINVAL;
+    if (!b->ad_valid || !b->ad_host) return set_err(FFHIP_EINVAL, "adapter records were not made in this run (FFHIP_RUN_ADAPTERS)");
+    const uint8_t *rec = b->ad_host + (size_t)read * kAdapterRecBytes;
+    memcpy(header, rec, sizeof *header);
+    *hits = (const ffhip_adapter_hit *)(rec + sizeof *header);
     return FFHIP_OK;
 }
 

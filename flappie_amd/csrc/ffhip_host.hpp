@@ -57,6 +57,13 @@ struct ffhip_barcodes {
     void *d_peq = nullptr, *d_len = nullptr;
 };
 
+// an adapter kit on the device (ffhip_adapters_upload; the kernel's view of it is AdapterKit)
+struct ffhip_adapters {
+    ffhip_engine *eng = nullptr;
+    ffhip::AdapterKit kit{};
+    void *d_peq = nullptr, *d_len = nullptr;
+};
+
 namespace ffhip {
 
 int set_err(int code, const char *fmt, ...);        // records the thread's last error text, returns `code`

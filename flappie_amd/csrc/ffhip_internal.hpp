@@ -227,6 +227,18 @@ struct BarcodeKit {
 };
 void launch_barcodes(hipStream_t s, BarcodeKit kit, const char *bases, const int *lens, void *records, int nread, int Tb, const int *tbs, ReadMap map,
                      int max_dist, int min_sep, int both_ends, int *dist_out = nullptr, int *end_out = nullptr);
+// adapters anywhere in the called reads (k_adapters, ffhip_adapters.hip; include/ffhip.h "adapters"): one 256-byte record a read -- a 16-byte header and up to 15
+// hits of 16 bytes (ffhip_adapter_header, ffhip_adapter_hit) -- from the base strings and their lengths; d_out, when given, takes the whole score rows
+// [2 n][len + 1] of read 0 (a launch of one read)
+constexpr int kAdapterMaxKit = 32, kAdapterMaxLen = 64, kAdapterMaxHits = 15, kAdReach = 64, kAdSeg = 512;
+constexpr size_t kAdapterRecBytes = 16 * (size_t)(kAdapterMaxHits + 1);
+struct AdapterKit {
+    const unsigned long long *peq;      // [2 n][4]: bit i of peq[q][c] = the oriented pattern of search q = 2 k + o has base c (A C G T) at position i
+    const int *len;                     // [n]
+    int n;
+};
+void launch_adapters(hipStream_t s, AdapterKit kit, const char *bases, const int *lens, void *records, int nread, int Tb, const int *tbs, ReadMap map,
+                     int max_dist, uint8_t *d_out = nullptr);
 // signal-to-sequence mapping (k_remap, ffhip_remap.hip; include/ffhip.h "remap"): per listed read one 16-byte record { status, L, score bits, end } at rec[read] and,
 // for a mapped one, N bytes of 0 / 1 at the read's row of the (Tb + 1)-entry byte buffer `rm`.  A form is one instantiation of the kernel (0, 1: one wave; 2, 3: a
 // workgroup): remap_form gives the smallest that holds a window of min(2 band + 1, L) cells, -1 when none does; a launch takes the reads of ONE form.

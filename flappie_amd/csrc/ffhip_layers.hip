@@ -673,6 +673,34 @@ extern "C" int ffhip_op_barcode_scores(ffhip_engine *eng, const ffhip_barcodes *
     return FFHIP_OK;
 }
 
+// the kernel of the adapter search on one call (k_adapters; include/ffhip.h "adapters"): the whole score rows, or the call's record
+static int op_adapters(ffhip_engine *eng, const ffhip_adapters *kit, int max_dist, const char *bases, size_t len, uint8_t *d, ffhip_adapter_header *header, ffhip_adapter_hit *hits) {
+    OP_ENTER(eng);
+    if (!kit || kit->eng != eng || (!bases && len) || len > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "bad adapter arguments (a kit of this engine, a call of len characters, the outputs)");
+    for (size_t i = 0; i < len; i++) if (!bases[i] || !strchr("ACGTZ", bases[i])) return set_err(FFHIP_EINVAL, "adapters: character %zu of the call is not one of ACGTZ", i);
+    const int n = kit->kit.n, ilen = (int)len;
+    const size_t dbytes = d ? (size_t)2 * n * (len + 1) : 0;
+    char *d_bases = (char *)(len ? tmp.upload(bases, len, s) : tmp.get(4));
+    int *d_len = (int *)tmp.upload(&ilen, 4, s);
+    uint8_t *d_d = d ? (uint8_t *)tmp.get(dbytes) : nullptr;
+    uint8_t *d_rec = (uint8_t *)tmp.get(kAdapterRecBytes);
+    if (!d_bases || !d_len || (d && !d_d) || !d_rec) OP_NOMEM();
+    launch_adapters(s, kit->kit, d_bases, d_len, d_rec, 1, ilen > 0 ? ilen : 1, nullptr, ReadMap(), max_dist, d_d);
+    if (d) HIP_TRY(hipMemcpyAsync(d, d_d, dbytes, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    if (header) HIP_TRY(hipMemcpyAsync(header, d_rec, 16, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    if (hits) HIP_TRY(hipMemcpyAsync(hits, d_rec + 16, kAdapterRecBytes - 16, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+extern "C" int ffhip_op_adapter_scores(ffhip_engine *eng, const ffhip_adapters *kit, const char *bases, size_t len, uint8_t *d) {
+    if (!d) return set_err(FFHIP_EINVAL, "adapter scores: an output of 2 n (len + 1) bytes");
+    return op_adapters(eng, kit, -1, bases, len, d, nullptr, nullptr);
+}
+extern "C" int ffhip_op_adapter_hits(ffhip_engine *eng, const ffhip_adapters *kit, int max_dist, const char *bases, size_t len, ffhip_adapter_header *header, ffhip_adapter_hit *hits) {
+    if (!header || !hits) return set_err(FFHIP_EINVAL, "adapter hits: a header and room for 15 hits");
+    return op_adapters(eng, kit, max_dist < 0 ? -1 : (max_dist > kAdapterMaxLen - 1 ? kAdapterMaxLen - 1 : max_dist), bases, len, nullptr, header, hits);
+}
+
 // one matrix of transition scores mapped to one sequence (k_remap; include/ffhip.h "remap")
 extern "C" int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, int band, uint8_t *rm, float *score) {
     OP_ENTER(eng);

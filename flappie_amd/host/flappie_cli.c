@@ -42,6 +42,7 @@
 #include "../../include/flappie_variants.h"
 #include "../../include/flappie_moves.h"
 #include "../../include/flappie_barcodes.h"
+#include "../../include/flappie_adapters.h"
 #include "../../include/flappie_remap.h"
 #include "../../include/flappie_truth.h"
 #include "../../include/networks.h"
@@ -97,6 +98,12 @@ static struct argp_option options[] = {
     {"barcode-min-sep", 28, "edits", 0, "With --barcodes: least distance between the best barcode and the runner-up (default 3)"},
     {"barcode-both-ends", 29, 0, 0, "With --barcodes: a barcode must be found at both ends (its score is the larger of its two distances)"},
     {"trim-barcodes", 30, 0, 0, "With --barcodes: cut the barcode and what precedes it from SEQ and QUAL of classified reads, at each end where it was found (not with --emit-moves, --modbase-tags or --trace)"},
+    {"adapters", 269, "kit.fa", 0, "Find sequencing adapters and primers anywhere in every call: the records of a FASTA file (1-32 records, the record's name is the adapter's, patterns of 1-64 bases over ACGT), every occurrence in both orientations with exact start and end, searched on the GPU. Every record gains an:i:<hits> and ah:Z:<name>,<+|->,<start>,<end>,<dist>;... (at most 15 hits, ordered by end), behind the barcode tags; a summary of hits per adapter goes to stderr. The tags describe the call in signal order, with --reverse too"},
+    {"adapter-max-dist", 270, "edits", 0, "With --adapters: largest edit distance of a hit (default: a quarter of each pattern's length, rounded down)"},
+    {"trim-adapters", 271, 0, 0, "With --adapters: cut SEQ and QUAL behind the last hit that ends within --adapter-window bases of the front, and in front of the first hit that starts within as many bases of the rear; with --trim-barcodes the larger cut at each end wins (not with --emit-moves, --modbase-tags or --trace)"},
+    {"adapter-window", 272, "bases", 0, "With --trim-adapters or --split-reads: how far from an end of the call a hit is an end's adapter (default 150)"},
+    {"split-reads", 273, 0, 0, "With --adapters: a read with a hit in its interior is two molecules called as one: write every stretch of the call that no hit covers as a record of its own, named <name>:<k> in signal order, with pi:Z:<name> and sp:B:i,<start>,<end>; a read without an interior hit is written whole, trimmed at its ends; a read with more than 15 hits is written unsplit (not with --emit-moves, --modbase-tags, --trace, --remap or --truth)"},
+    {"split-min-length", 274, "bases", 0, "With --split-reads: pieces shorter than this are dropped and counted (default 200)"},
     {"remap", 31, "refs.fa", 0, "Map each read's signal to a sequence you already know: the records of a FASTA file, found by read id, then by the file's base name, in SIGNAL order (reverse them yourself for --reverse and RNA). The best path of the read's transition scores through its sequence is made on the GPU and written to --remap-out; stdout does not change"},
     {"remap-out", 256, "map.tsv", 0, "With --remap: one line per read that had a record: name, status (1 mapped, 2 not: a letter outside the model's alphabet, or more bases than blocks + 1), nblock, stride, trim_start, L, band, maxdev, score and the block every base starts at"},
     {"remap-band", 257, "W", 0, "With --remap: the band's half-width in sequence positions around the straight line from (0, 0) to (nblock, L - 1) (0-2303, default 2048: the GPU holds a window of at most 2 W + 1 <= 4608 positions; maxdev = W in map.tsv says the band was touched)"},
@@ -114,6 +121,12 @@ static struct argp_option options[] = {
 #endif
 #ifdef BUILD_RUNNIE
     {"barcodes", 25, "kit.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"adapters", 269, "kit.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"adapter-max-dist", 270, "edits", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"trim-adapters", 271, 0, OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"adapter-window", 272, "bases", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"split-reads", 273, 0, OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"split-min-length", 274, "bases", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"remap", 31, "refs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"truth", 258, "refs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"remap-events", 261, "events.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
@@ -176,6 +189,18 @@ static char *mods_path = NULL;
 #ifndef BUILD_RUNNIE
 static int mods_context = 15;
 static bool mods_context_set = false, mods_all_paths = false;
+#endif
+
+/* flappie: --adapters kit file, --adapter-max-dist (-1: the default), --trim-adapters, --adapter-window, --split-reads, --split-min-length (runnie: seen, to be
+ * refused); ad_opts: one of the options that go with --adapters was given */
+static char *ad_path = NULL;
+static bool ad_opts = false;
+static int ad_window = 150;
+static long ad_min_length = 200;
+static bool ad_trim = false, ad_split = false;
+#ifndef BUILD_RUNNIE
+static int ad_max_dist = -1;
+static bool ad_window_set = false, ad_min_length_set = false;
 #endif
 
 /* flappie: --remap-variants file and table, --remap-variants-context, --remap-variants-all-paths (runnie: seen, to be refused) */
@@ -300,6 +325,34 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
     case 261: args.remap_events = arg; break;
     case 262: mods_path = arg; break;
     case 265: vars_path = arg; break;
+    case 269: ad_path = arg; break;
+#ifdef BUILD_RUNNIE
+    case 270: case 271: case 272: case 273: case 274: ad_opts = true; break;
+#else
+    case 270: {
+        char *end = NULL;
+        const long v = strtol(arg, &end, 10);
+        if (end == arg || *end != '\0' || v < 0 || v > 63) errx(EXIT_FAILURE, "--adapter-max-dist must be a whole number from 0 to 63");
+        ad_max_dist = (int)v; ad_opts = true;
+        break;
+    }
+    case 271: ad_trim = true; ad_opts = true; break;
+    case 272: {
+        char *end = NULL;
+        const long v = strtol(arg, &end, 10);
+        if (end == arg || *end != '\0' || v < 0 || v > 1000000) errx(EXIT_FAILURE, "--adapter-window must be a whole number from 0 to 1000000");
+        ad_window = (int)v; ad_window_set = true; ad_opts = true;
+        break;
+    }
+    case 273: ad_split = true; ad_opts = true; break;
+    case 274: {
+        char *end = NULL;
+        const long v = strtol(arg, &end, 10);
+        if (end == arg || *end != '\0' || v < 0 || v > 1000000000) errx(EXIT_FAILURE, "--split-min-length must be a whole number from 0 to 1000000000");
+        ad_min_length = v; ad_min_length_set = true; ad_opts = true;
+        break;
+    }
+#endif
     case 266: vars_out_path = arg; break;
 #ifdef BUILD_RUNNIE
     case 267: case 268: vars_opts = true; break;
@@ -493,6 +546,9 @@ typedef struct {
     float sm, sd;                       /* ... the median and MAD the read was normalised with */
     ffhip_barcode_call bc;              /* --barcodes: the read's record */
     int have_bc;
+    ffhip_adapter_header ad_head;       /* --adapters: the read's record */
+    ffhip_adapter_hit ad_hits[FFHIP_ADAPTER_MAX_HITS];
+    int have_ad;
     int rm_ref;                         /* --remap: the read's record of the sequences (-1: none), and what the batch returned for it */
     int have_rm, rm_status;
     size_t rm_L, rm_nblock;
@@ -577,6 +633,11 @@ typedef struct { ffhip_batch *b; int cached, n, *idx; item **its; const ffhip_pr
 static flappie_barcode_kit *bc_kit = NULL;
 static ffhip_barcodes *bc_dev = NULL;
 static unsigned long long bc_count[FLAPPIE_BARCODE_MAX_KIT + 1];
+/* flappie --adapters: likewise; kept hits per adapter, reads with a hit, and what --split-reads did (reads split, pieces written, pieces dropped, reads with more
+ * than 15 hits) */
+static flappie_adapter_kit *ad_kit = NULL;
+static ffhip_adapters *ad_dev = NULL;
+static unsigned long long ad_count[FLAPPIE_ADAPTER_MAX_KIT], ad_reads_with_hit, ad_stats[4];
 /* flappie --remap: the sequences, the table, and the summary's counts: mapped, no record, refused, mapped with maxdev = band */
 static flappie_remap_refs *rm_refs = NULL;
 static FILE *rm_out = NULL;
@@ -610,10 +671,10 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
 }
 #else
 /* --modbase-tags: the 5mC bytes of the called bases come from the device (FFHIP_RUN_MOD_PROBS); --emit-moves: the move table does (FFHIP_RUN_MOVES);
- * --barcodes: the reads' barcode records do (FFHIP_RUN_BARCODES) */
+ * --barcodes: the reads' barcode records do (FFHIP_RUN_BARCODES); --adapters: their adapter records (FFHIP_RUN_ADAPTERS) */
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u) |
-           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | (tr_refs ? FFHIP_RUN_TRUTH : 0u) |
+           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | (tr_refs ? FFHIP_RUN_TRUTH : 0u) |
            (ev_out ? FFHIP_RUN_EVENTS : 0u) | (md_out ? FFHIP_RUN_REMAP_MODS : 0u) | (vr_out ? FFHIP_RUN_REMAP_VARIANTS : 0u);
 }
 /* --remap: every read's record, by its read id, then by its file's base name; a bad record goes as a sequence of no bases (status 2) */
@@ -674,6 +735,7 @@ static int batch_set_truth(ffhip_batch *b, item **its, int n) {
 }
 static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
     if (bc_dev) { const int rc = ffhip_batch_set_barcodes(b, bc_dev, args.bc_max_dist, args.bc_min_sep, args.bc_both); if (rc) return rc; }
+    if (ad_dev) { const int rc = ffhip_batch_set_adapters(b, ad_dev, ad_max_dist); if (rc) return rc; }
     if (rm_refs) { const int rc = batch_set_remap(b, its, n); if (rc) return rc; }
     if (tr_refs) { const int rc = batch_set_truth(b, its, n); if (rc) return rc; }
     return ffhip_batch_run(b, args.temperature, flags);
@@ -938,6 +1000,20 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
             if (0 != ffhip_batch_barcode(b, i, &its[i]->bc) || its[i]->bc.best >= bc_kit->n) warnx("%s", ffhip_last_error());
             else { its[i]->have_bc = 1; bc_count[its[i]->bc.best >= 0 ? its[i]->bc.best : bc_kit->n]++; }
         }
+        if (ad_dev) {                                          /* likewise */
+            const ffhip_adapter_hit *hits = NULL;
+            if (0 != ffhip_batch_adapters(b, i, &its[i]->ad_head, &hits)) warnx("%s", ffhip_last_error());
+            else if (its[i]->ad_head.kept < 0 || its[i]->ad_head.kept > FFHIP_ADAPTER_MAX_HITS) warnx("A bad adapter record for %s", its[i]->filename);
+            else {
+                memcpy(its[i]->ad_hits, hits, sizeof its[i]->ad_hits);
+                its[i]->have_ad = 1;
+                for (int h = 0; h < its[i]->ad_head.kept; h++) {
+                    if (hits[h].pattern < 0 || hits[h].pattern >= ad_kit->n) { its[i]->have_ad = 0; break; }
+                    ad_count[hits[h].pattern]++;
+                }
+                if (its[i]->have_ad && its[i]->ad_head.nhit > 0) ad_reads_with_hit++;
+            }
+        }
         if (rm_refs && its[i]->rm_ref >= 0) {                  /* the read's mapping to its sequence: the table's line is written with the read's record */
             ffhip_remap_call rc;
             if (0 != ffhip_batch_remap(b, i, &rc)) warnx("%s", ffhip_last_error());
@@ -1135,7 +1211,16 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
             char *multi_name = NULL;              /* --no-uuid, a read of a multi-read file: <file>:<read id> (the file's name alone would stand for thousands of reads) */
             if (it->from_multi && NULL != (multi_name = malloc(strlen(base) + strlen(uuid) + 2))) { sprintf(multi_name, "%s:%s", base, uuid); base = multi_name; }
             /* --modbase-tags: Z is written as C here, in the record only -- the trace file below keeps the call as it is */
-            if (NULL != bc_kit) {
+            if (NULL != ad_kit) {
+                const flappie_adapter_out ad = { &it->ad_head, it->ad_hits, ad_kit, ad_trim, ad_split, ad_window, (size_t)ad_min_length };
+                if (!it->have_ad) warnx("No adapter record for %s", it->filename);
+                else if (NULL != bc_kit && !it->have_bc) warnx("No barcode record for %s", it->filename);
+                else if (args.emit_moves && NULL == it->mv) warnx("No move table for %s", it->filename);
+                else if (args.modbase_tags && NULL == it->ml) warnx("No base-modification probabilities for %s", it->filename);
+                else fprintf_adapter_record(args.outformat, args.output, uuid, base, args.uuid, args.prefix, it->res, args.modbase_tags ? it->ml : NULL,
+                                            args.emit_moves ? it->mv : NULL, it->mv_stride, it->sm, it->sd, args.delta != 0.0f, bc_kit ? &it->bc : NULL, bc_kit,
+                                            args.bc_trim, &ad, args.reverse, ad_stats);
+            } else if (NULL != bc_kit) {
                 if (!it->have_bc) warnx("No barcode record for %s", it->filename);
                 else if (args.emit_moves && NULL == it->mv) warnx("No move table for %s", it->filename);
                 else if (args.modbase_tags && NULL == it->ml) warnx("No base-modification probabilities for %s", it->filename);
@@ -1211,6 +1296,7 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
         free(it->mv);
         it->mv = NULL;
         it->have_bc = 0;
+        it->have_ad = 0;
         free(it->rm);
         it->rm = NULL;
         free(it->ev);
@@ -1930,6 +2016,7 @@ int main(int argc, char *argv[]) {
 #ifdef BUILD_RUNNIE
     if ((args.rlc || args.run_scale_set) && !args.fasta) errx(EXIT_FAILURE, "--rlc and --run-scale go with --fasta");
     if (args.barcodes) errx(EXIT_FAILURE, "--barcodes is flappie's: the run-length model's records carry no base strings to search");
+    if (ad_path || ad_opts) errx(EXIT_FAILURE, "--adapters is flappie's: the run-length model's records carry no base strings to search");
     if (args.remap) errx(EXIT_FAILURE, "--remap is flappie's: the run-length model's scores are not transitions between the bases of a sequence");
     if (args.truth) errx(EXIT_FAILURE, "--truth is flappie's: the run-length model's call is a list of runs");
     if (args.remap_events) errx(EXIT_FAILURE, "--remap-events is flappie's: it goes with --remap, which the run-length model does not have");
@@ -1944,6 +2031,19 @@ int main(int argc, char *argv[]) {
         char why[256];
         bc_kit = flappie_barcode_kit_read(args.barcodes, why, sizeof why);
         if (NULL == bc_kit) errx(EXIT_FAILURE, "--barcodes %s: %s", args.barcodes, why);
+    }
+    /* --adapters: likewise */
+    if (ad_opts && NULL == ad_path) errx(EXIT_FAILURE, "--adapter-max-dist, --trim-adapters, --adapter-window, --split-reads and --split-min-length go with --adapters");
+    if (ad_window_set && !ad_trim && !ad_split) errx(EXIT_FAILURE, "--adapter-window goes with --trim-adapters or --split-reads");
+    if (ad_min_length_set && !ad_split) errx(EXIT_FAILURE, "--split-min-length goes with --split-reads");
+    if (ad_trim && (args.emit_moves || args.modbase_tags || NULL != args.trace))
+        errx(EXIT_FAILURE, "--trim-adapters does not go with --emit-moves, --modbase-tags or --trace: their positions and probabilities are the untrimmed call's");
+    if (ad_split && (args.emit_moves || args.modbase_tags || NULL != args.trace || NULL != args.remap || NULL != args.truth))
+        errx(EXIT_FAILURE, "--split-reads does not go with --emit-moves, --modbase-tags, --trace, --remap or --truth: they describe the read as one molecule");
+    if (ad_path) {
+        char why[256];
+        ad_kit = flappie_adapter_kit_read(ad_path, why, sizeof why);
+        if (NULL == ad_kit) errx(EXIT_FAILURE, "--adapters %s: %s", ad_path, why);
     }
     /* --remap: likewise */
     if ((NULL == args.remap) != (NULL == args.remap_out)) errx(EXIT_FAILURE, "--remap and --remap-out go together");
@@ -2015,6 +2115,10 @@ int main(int argc, char *argv[]) {
         stop_reader_procs();
         errx(EXIT_FAILURE, "--barcodes: %s", ffhip_last_error());
     }
+    if (ad_kit && NULL == (ad_dev = ffhip_adapters_upload(eng, ad_kit->n, (const char *const *)ad_kit->seq))) {
+        stop_reader_procs();
+        errx(EXIT_FAILURE, "--adapters: %s", ffhip_last_error());
+    }
 #endif
     hid_t hdf5out = open_or_create_hdf5(args.trace);
     reader_state rs;
@@ -2082,6 +2186,13 @@ int main(int argc, char *argv[]) {
         fprintf(stderr, "barcode\tunclassified\t%llu\n", bc_count[bc_kit->n]);
         ffhip_barcodes_free(bc_dev);
         flappie_barcode_kit_free(bc_kit);
+    }
+    if (ad_kit) {                      /* kept hits per adapter, reads with a hit, and what --split-reads did */
+        for (int k = 0; k < ad_kit->n; k++) fprintf(stderr, "adapter\t%s\t%llu\n", ad_kit->name[k], ad_count[k]);
+        fprintf(stderr, "adapters\treads_with_hit\t%llu\nadapters\tsplit_reads\t%llu\nadapters\tpieces\t%llu\nadapters\tdropped_pieces\t%llu\nadapters\toverflow\t%llu\n",
+                ad_reads_with_hit, ad_stats[0], ad_stats[1], ad_stats[2], ad_stats[3]);
+        ffhip_adapters_free(ad_dev);
+        flappie_adapter_kit_free(ad_kit);
     }
     if (rm_refs) {                     /* mapped, no record, refused, and the mapped reads whose path touched the band */
         fprintf(stderr, "remap\tmapped\t%llu\nremap\tno_record\t%llu\nremap\trefused\t%llu\nremap\tband_touched\t%llu\n", rm_count[0], rm_count[1], rm_count[2], rm_count[3]);

@@ -130,6 +130,11 @@ typedef struct {
  * in ONE extra copy, enqueued where the remap buffer's copy is.  Everything else the run returns -- events and site mods included -- is that of the same run
  * without the flag.  Without FFHIP_RUN_REMAP, or with no variants set: FFHIP_EINVAL; the run-length model and FFHIP_RUN_NO_DECODE are refused as for remap. */
 #define FFHIP_RUN_REMAP_VARIANTS 524288u
+/* Adapters and primers anywhere in a flip-flop model's calls (ffhip_batch_adapters below, "adapters"): one 256-byte record a read -- a header and up to 15 hits with
+ * exact start and end -- made on the device from the base strings (k_adapters) against the kit attached with ffhip_batch_set_adapters.  The records are NOT part of
+ * the result block: they live in a buffer of their own (reads x 256 bytes) and come down in ONE extra copy, enqueued where the result block's copy is.  Everything
+ * else the run returns is that of the same run without the flag.  No kit attached, the run-length model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
+#define FFHIP_RUN_ADAPTERS   1048576u
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -428,6 +433,41 @@ void ffhip_barcodes_free(ffhip_barcodes *kit);
 int ffhip_batch_set_barcodes(ffhip_batch *b, const ffhip_barcodes *kit, int max_dist, int min_sep, int both_ends);
 int ffhip_batch_barcode(const ffhip_batch *b, int read, ffhip_barcode_call *out);
 int ffhip_op_barcode_scores(ffhip_engine *eng, const ffhip_barcodes *kit, const char *bases, size_t len, int32_t *dist /*[2][n]*/, int32_t *end /*[2][n]*/);
+/* Adapters: every occurrence of a sequencing adapter or primer in a call, in both orientations, with exact start and end -- what trimming and read splitting need.
+ *   Kit: n patterns, 1 <= n <= 32, each a string over ACGT (upper case) of 1 .. 64 bases; anything else is refused with a text.
+ *   Searches: every pattern k is searched as given (orientation 0) and as its reverse complement (orientation 1), both on the call x of `len` bases in SIGNAL order,
+ *     Z read as C.  The search index is q = 2 k + orientation: at most 64 searches.
+ *   Score row of search q with (oriented) pattern p of L bases: the infix edit distance ending at column j, edlib's HW mode, exactly as for barcodes above:
+ *     D[0][j] = 0, D[i][0] = i, D[i][j] = min(D[i-1][j-1] + (p[i] != x[j]), D[i-1][j] + 1, D[i][j-1] + 1); d_q[j] = D[L][j], j = 0 .. len.
+ *   Hit: with R = 64 and md_k the pattern's bound, column j is a hit end of search q iff d_q[j] <= md_k, and d_q[j] < d_q[j'] for every j' in [j - R, j) within
+ *     [0, len], and d_q[j] <= d_q[j'] for every j' in (j, j + R] within [0, len]: the leftmost minimum within R columns either way, so a homopolymer run gives
+ *     one hit, not one a column.  md_k = floor(L_k / 4) when max_dist < 0, else min(max_dist, L_k - 1).
+ *   Start of a hit (q, j, d): the largest i with ed(p, x[i:j]) = d.  Equivalently: the reversed pattern against x[j-1], x[j-2], ... with an anchored start
+ *     (D[0][c] = c), the first column c with D[L][c] = d; start = j - c, and c <= L + d <= 127.  The hit covers x[start : end], end = j.
+ *   Record of a read, 256 bytes: the header { nhit, len, kept, reserved } and up to 15 hits { start, end, pattern, orientation, dist, reserved }, ordered by (end, q).
+ *     nhit counts ALL hits of the read; kept = min(nhit, 15), and the first `kept` hits in that order are stored (the other slots are zero).  An empty slot of a
+ *     batch: nhit = 0, len = 0.
+ *   Locality (what the segmented kernel rests on): d_q[j] <= L, and an optimal match spans at most L + d <= 128 columns, so a search started fresh at column a
+ *     (D[i][a] = i) has the exact d_q[j] for every j >= a + 128; and the hit rule looks 64 columns either way.  k_adapters cuts a call into segments of
+ *     FFHIP_ADAPTER_SEGMENT columns -- segment g owns the hit ends in (g S, (g + 1) S] -- each worked by one wave from a fresh search 192 columns before it.
+ * ffhip_adapters_upload: the kit's tables on the engine's device (NULL with a text on a bad kit); the kit must outlive the batches it is attached to.
+ * ffhip_batch_set_adapters: the kit and the bound of the batch's later runs with FFHIP_RUN_ADAPTERS.  kit == NULL detaches.
+ * ffhip_batch_adapters: after ffhip_batch_finish of a run with the flag: the read's header, and its hits in the batch's host buffer (valid until the batch's next
+ *   run).  A run without the flag: FFHIP_EINVAL.
+ * ffhip_op_adapter_scores: the kernel on one call of `len` characters of ACGTZ (len may be 0): the whole score rows d[2 n][len + 1], row q = 2 k + orientation.
+ * ffhip_op_adapter_hits: likewise, the call's record: the header and all 15 hit slots. */
+#define FFHIP_ADAPTER_SEGMENT 512
+#define FFHIP_ADAPTER_MAX_HITS 15
+typedef struct ffhip_adapters ffhip_adapters;
+typedef struct { int32_t nhit, len, kept, reserved; } ffhip_adapter_header;                                            /* 16 bytes */
+typedef struct { int32_t start, end; int16_t pattern; uint8_t orientation, dist; int32_t reserved; } ffhip_adapter_hit; /* 16 bytes */
+int ffhip_adapter_segment(void);                /* FFHIP_ADAPTER_SEGMENT of the library as built */
+ffhip_adapters *ffhip_adapters_upload(ffhip_engine *eng, int n, const char *const *seq);
+void ffhip_adapters_free(ffhip_adapters *kit);
+int ffhip_batch_set_adapters(ffhip_batch *b, const ffhip_adapters *kit, int max_dist);
+int ffhip_batch_adapters(const ffhip_batch *b, int read, ffhip_adapter_header *header, const ffhip_adapter_hit **hits);
+int ffhip_op_adapter_scores(ffhip_engine *eng, const ffhip_adapters *kit, const char *bases, size_t len, uint8_t *d /*[2 n][len + 1]*/);
+int ffhip_op_adapter_hits(ffhip_engine *eng, const ffhip_adapters *kit, int max_dist, const char *bases, size_t len, ffhip_adapter_header *header, ffhip_adapter_hit *hits /*[15]*/);
 /* Remap: the signal of a read mapped to a sequence the caller knows.
  *   Read: N >= 1 blocks with transition scores T[b][.], b = 0 .. N - 1, nparam = nstate (nbase + 1) floats a block -- exactly what ffhip_batch_get_transitions
  *     returns for that run.  Sequence: s of L bases as codes 0 .. nbase - 1 (the model's alphabet, ACGT or ACGTZ), in SIGNAL order (--reverse, RNA: the caller's business).
