@@ -22,6 +22,7 @@
 #include "ffhip_internal.hpp"
 #include "ffhip_host.hpp"
 #include "ffhip_results.hpp"
+#include "ffhip_annot.hpp"
 
 using namespace ffhip;
 
@@ -756,73 +757,48 @@ struct ffhip_batch {
     unsigned *h_abort() const { return res.on_host<unsigned>(RF_ABORT); }
     int *h_lens() const { return res.on_host<int>(RF_LENS); }
     unsigned res_made = 0;              // sections of the block the last run filled (res_bit)
-    // Barcode records (FFHIP_RUN_BARCODES, k_barcodes): 16 bytes a read, NOT a section of the result block -- a device buffer and a pinned host buffer of their own,
-    // cap_reads records each, created by the first run that asks, and one copy of their own beside the block's
-    const ffhip_barcodes *bc_kit = nullptr;
-    int bc_max_dist = 0, bc_min_sep = 3, bc_both = 0;
-    ffhip_barcode_call *bc_dev = nullptr, *bc_host = nullptr;
-    int bc_valid = 0;                   // the last run made them
-    // Adapter records (FFHIP_RUN_ADAPTERS, k_adapters): 256 bytes a read, likewise a device buffer and a pinned host buffer of their own, cap_reads records each,
-    // created by the first run that asks, and one copy of their own beside the block's
-    const ffhip_adapters *ad_kit = nullptr;
-    int ad_max_dist = -1;
-    uint8_t *ad_dev = nullptr, *ad_host = nullptr;
-    int ad_valid = 0;                   // the last run made them
-    // Remap (FFHIP_RUN_REMAP, k_remap): the coded sequences of ffhip_batch_set_remap on the host and (rmp_dseq) on the device; ONE buffer of cap_reads 16-byte records and,
-    // behind them, a byte a block in the layout of the (Tb + 1)-entry buffers (rmp_dev, its pinned mirror rmp_host), with one copy of its own beside the block's; the
-    // reads' list (pinned, and on the device) and the traceback workspace, both written by the front of every run that asks, the workspace grown when a run needs more
-    std::vector<std::vector<unsigned short>> rmp_seq;      // per read: stay | move << 8 of every position (remap_code)
-    std::vector<signed char> rmp_state;                     // per read: 0 no sequence, 1 a sequence, 2 refused at the call (L = 0)
-    int rmp_set = 0, rmp_band = 0, rmp_valid = 0;
-    unsigned short *rmp_dseq = nullptr; size_t rmp_dseq_cap = 0;
-    unsigned long long *rmp_ws = nullptr; size_t rmp_ws_cap = 0;
-    RemapRead *rmp_dlist = nullptr, *rmp_hlist = nullptr;
-    uint8_t *rmp_dev = nullptr, *rmp_host = nullptr;
-    int rmp_count[kRemapForms] = { 0, 0, 0, 0 };
-    size_t rmp_bytes() const { return (size_t)cap_reads * 16 + (size_t)nread * ((size_t)Tb + 1); }
-    // Truth (FFHIP_RUN_TRUTH, k_truth): the truths of ffhip_batch_set_truth on the host and (tru_dseq) on the device; ONE buffer of cap_reads 48-byte records and,
-    // behind them, m + blocks + 1 bytes of ops a read with a truth (tru_dev, its pinned mirror tru_host: both grow with the truths), with one copy of its own beside
-    // the block's; the reads' list and the traceback workspace as for remap
-    std::vector<std::vector<uint8_t>> tru_seq;              // per read: codes 0 .. nbase - 1
-    std::vector<signed char> tru_state;                     // per read: 0 no truth, 1 a truth, 2 an empty one
-    std::vector<size_t> tru_ops;                            // per read: its first byte of ops behind the records, and (one more entry) the end
-    int tru_set = 0, tru_band = 0, tru_valid = 0;
-    uint8_t *tru_dseq = nullptr; size_t tru_dseq_cap = 0;
-    unsigned long long *tru_ws = nullptr; size_t tru_ws_cap = 0;
-    TruthRead *tru_dlist = nullptr, *tru_hlist = nullptr;
-    uint8_t *tru_dev = nullptr, *tru_host = nullptr; size_t tru_dev_cap = 0, tru_host_cap = 0;
-    int tru_count[kTruthForms] = { 0, 0, 0, 0 };
-    size_t tru_rec_bytes() const { return (size_t)cap_reads * kTruthRecInts * 4; }
-    size_t tru_bytes() const { return tru_rec_bytes() + (tru_ops.empty() ? 0 : tru_ops.back()); }
-    // Events (FFHIP_RUN_EVENTS with FFHIP_RUN_REMAP, k_events): ONE buffer of 16 bytes a base of every read with a sequence that can be mapped, one read behind the
-    // other (evt_dev, its pinned mirror evt_host: both grow with the sequences), with one copy of its own beside the remap buffer's; the reads' list as for remap
-    std::vector<size_t> evt_off;                            // per read: its first event, and (one more entry) the end
-    EventRead *evt_dlist = nullptr, *evt_hlist = nullptr;
-    uint8_t *evt_dev = nullptr, *evt_host = nullptr; size_t evt_dev_cap = 0, evt_host_cap = 0;
-    int evt_valid = 0, evt_count = 0;
-    size_t evt_bytes() const { return (evt_off.empty() ? 0 : evt_off.back()) * sizeof(ffhip_event); }
-    // Site mods (FFHIP_RUN_REMAP_MODS with FFHIP_RUN_REMAP, k_site_mods): ONE buffer of 16 bytes a C / Z of every read with a sequence that can be mapped, one read
-    // behind the other (smd_dev, its pinned mirror smd_host), with one copy of its own beside the remap buffer's; the workspace of starts (L + 1 int32 a listed
-    // read) and the lists (the reads, then the sites: one pinned image, one upload) grow with the sequences too
-    std::vector<size_t> smd_off;                            // per read: its first site, and (one more entry) the end
-    uint8_t *smd_dlist = nullptr, *smd_hlist = nullptr; size_t smd_dlist_cap = 0, smd_hlist_cap = 0;
-    int *smd_start = nullptr; size_t smd_start_cap = 0;
-    uint8_t *smd_dev = nullptr, *smd_host = nullptr; size_t smd_dev_cap = 0, smd_host_cap = 0;
-    int smd_valid = 0, smd_reads = 0, smd_context = 15, smd_all = 0;
-    size_t smd_nsite() const { return smd_off.empty() ? 0 : smd_off.back(); }
-    size_t smd_bytes() const { return smd_nsite() * sizeof(ffhip_site_mod); }
-    // Variants (FFHIP_RUN_REMAP_VARIANTS with FFHIP_RUN_REMAP, k_variants): the lists of ffhip_batch_set_remap_variants (copied), and, as for site mods, ONE buffer
-    // of 16 bytes a variant of every read with a sequence that can be mapped, one read behind the other (var_dev, its pinned mirror var_host), with one copy of
-    // its own beside the remap buffer's; its own workspace of starts (L + 1 int32 a listed read) and its own list (the variants, then the reads: one pinned
-    // image, one upload)
-    std::vector<std::vector<ffhip_variant>> var_set;        // per read: its variants (empty: the feature is detached)
-    std::vector<size_t> var_off;                            // per read: its first record, and (one more entry) the end
-    uint8_t *var_dlist = nullptr, *var_hlist = nullptr; size_t var_dlist_cap = 0, var_hlist_cap = 0;
-    int *var_start = nullptr; size_t var_start_cap = 0;
-    uint8_t *var_dev = nullptr, *var_host = nullptr; size_t var_dev_cap = 0, var_host_cap = 0;
-    int var_valid = 0, var_reads = 0, var_context = 10, var_all = 0;
-    size_t var_count() const { return var_off.empty() ? 0 : var_off.back(); }
-    size_t var_bytes() const { return var_count() * sizeof(ffhip_variant_call); }
+    // The per-read products OUTSIDE the result block (ffhip_annot.hpp): each a struct of its own that starts with its records (`rec`: a device buffer and its pinned
+    // mirror, created or grown by the front of the first run that asks, one copy of their own beside the block's), its uploaded list if it has one, and `valid`
+    // (the last run made them).  annot(i) is feature i of kAnnots.
+    // Barcode records (FFHIP_RUN_BARCODES, k_barcodes): 16 bytes a read, cap_reads of them
+    struct Barcodes : Annot { const ffhip_barcodes *kit = nullptr; int max_dist = 0, min_sep = 3, both = 0; } bc;
+    // Adapter records (FFHIP_RUN_ADAPTERS, k_adapters): 256 bytes a read, cap_reads of them
+    struct Adapters : Annot { const ffhip_adapters *kit = nullptr; int max_dist = -1; } ad;
+    // Remap (FFHIP_RUN_REMAP, k_remap): the coded sequences of ffhip_batch_set_remap on the host and (dseq) on the device; cap_reads 16-byte records and, behind them,
+    // a byte a block in the layout of the (Tb + 1)-entry buffers; the reads' list and the traceback workspace, both written by the front of every run that asks
+    struct Remap : Annot {
+        std::vector<std::vector<unsigned short>> seq;       // per read: stay | move << 8 of every position (remap_code)
+        std::vector<signed char> state;                      // per read: 0 no sequence, 1 a sequence, 2 refused at the call (L = 0)
+        int set = 0, band = 0;
+        unsigned short *dseq = nullptr; size_t dseq_cap = 0;
+        unsigned long long *ws = nullptr; size_t ws_cap = 0;
+        int count[kRemapForms] = { 0, 0, 0, 0 };
+    } rmp;
+    // Truth (FFHIP_RUN_TRUTH, k_truth): the truths of ffhip_batch_set_truth on the host and (dseq) on the device; cap_reads 48-byte records and, behind them,
+    // m + blocks + 1 bytes of ops a read with a truth; the reads' list and the traceback workspace as for remap
+    struct Truth : Annot {
+        std::vector<std::vector<uint8_t>> seq;               // per read: codes 0 .. nbase - 1
+        std::vector<signed char> state;                      // per read: 0 no truth, 1 a truth, 2 an empty one
+        std::vector<size_t> off;                             // per read: its first byte of ops behind the records, and (one more entry) the end
+        int set = 0, band = 0;
+        uint8_t *dseq = nullptr; size_t dseq_cap = 0;
+        unsigned long long *ws = nullptr; size_t ws_cap = 0;
+        int count[kTruthForms] = { 0, 0, 0, 0 };
+    } tru;
+    // Events (FFHIP_RUN_EVENTS with FFHIP_RUN_REMAP, k_events): 16 bytes a base of every read with a sequence that can be mapped, one read behind the other
+    // Site mods (FFHIP_RUN_REMAP_MODS with FFHIP_RUN_REMAP, k_site_mods): 16 bytes a C / Z of every such read; the workspace of starts (L + 1 int32 a listed read);
+    // the lists are the reads, then the sites
+    // Variants (FFHIP_RUN_REMAP_VARIANTS with FFHIP_RUN_REMAP, k_variants): 16 bytes a variant of every such read; a workspace of starts of its own; the lists are
+    // the variants, then the reads; `set`: the lists of ffhip_batch_set_remap_variants (copied; empty: the feature is detached)
+    struct PerBase : Annot {                                 // records of 16 bytes, a read's one behind the other
+        std::vector<size_t> off;                             // per read: its first record, and (one more entry) the end
+        int reads = 0;                                       // the reads in the list
+        size_t total() const { return off.empty() ? 0 : off.back(); }
+    } evt;
+    struct Sites : PerBase { int *start = nullptr; size_t start_cap = 0; int context, all = 0; explicit Sites(int c) : context(c) {} } smd{ 15 };
+    struct Variants : Sites { std::vector<std::vector<ffhip_variant>> set; Variants() : Sites(10) {} } var;
+    enum { AN_COUNT = 7 };
+    Annot &annot(int i) { Annot *const a[AN_COUNT] = { &bc, &ad, &tru, &rmp, &evt, &smd, &var }; return *a[i]; }       // (the order of kAnnots: launch order)
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
     std::vector<void *> owned;
     unsigned last_flags = 0;
@@ -859,7 +835,7 @@ static RleRunOut rle_run_out(const ResultBlock &r, bool host, bool records) {
     return o;
 }
 
-static void *dalloc(ffhip_batch *b, size_t bytes, bool zero) {
+void *ffhip::dalloc(ffhip_batch *b, size_t bytes, bool zero) {
     void *d = nullptr;
     if (hipMalloc(&d, bytes ? bytes : 4) != hipSuccess) { set_err(FFHIP_ENOMEM, "hipMalloc of %zu bytes failed", bytes); return nullptr; }
     // zero on the BATCH's stream: everything that touches the buffer afterwards is enqueued there.  (A hipMemset on the null stream
@@ -918,18 +894,7 @@ extern "C" void ffhip_batch_destroy(ffhip_batch *b) {
     if (b->counted) { b->counted = 0; b->eng->in_flight--; }
     for (void *p : b->owned) hipFree(p);
     b->res.release();
-    if (b->bc_host) hipHostFree(b->bc_host);
-    if (b->ad_host) hipHostFree(b->ad_host);
-    if (b->rmp_host) hipHostFree(b->rmp_host);
-    if (b->rmp_hlist) hipHostFree(b->rmp_hlist);
-    if (b->tru_host) hipHostFree(b->tru_host);
-    if (b->tru_hlist) hipHostFree(b->tru_hlist);
-    if (b->evt_host) hipHostFree(b->evt_host);
-    if (b->evt_hlist) hipHostFree(b->evt_hlist);
-    if (b->smd_host) hipHostFree(b->smd_host);
-    if (b->smd_hlist) hipHostFree(b->smd_hlist);
-    if (b->var_host) hipHostFree(b->var_host);
-    if (b->var_hlist) hipHostFree(b->var_hlist);
+    for (int i = 0; i < ffhip_batch::AN_COUNT; i++) { b->annot(i).rec.release(); b->annot(i).list.release(); }
     if (b->side) ffhip_batch_destroy(b->side);
     prof_unlink(b);
     if (b->have_ev) {
@@ -1014,6 +979,9 @@ extern "C" ffhip_batch *ffhip_batch_create_packed(ffhip_engine *eng, const ffhip
     return batch_create_impl(eng, m, nslot, nsample, max_reads);
 }
 static inline int batch_nreads(const ffhip_batch *b) { return b->packed ? b->nvirt : b->nread; }
+// behind the cap_reads records of remap's and truth's buffers: where the moves and the ops start
+static inline size_t remap_moves_at(const ffhip_batch *b) { return (size_t)b->cap_reads * 16; }
+static inline size_t truth_ops_at(const ffhip_batch *b) { return (size_t)b->cap_reads * kTruthRecInts * 4; }
 
 extern "C" int ffhip_batch_nreads(const ffhip_batch *b) { return b ? batch_nreads(b) : 0; }
 // first row of a read in the buffers of Tb / Tb + 1 rows a slot
@@ -1520,32 +1488,8 @@ static int keep_copy(ffhip_batch *b, int slot, const float *src) {
     return FFHIP_OK;
 }
 
-// One run of a batch is enqueued in three phases -- front (convolutions), the recurrent stack, back (head, CRF, decode) -- so that
-static_assert(sizeof(ffhip_barcode_call) == 16, "k_barcodes writes a record as one 16-byte store");
-static int ensure_barcode_buffers(ffhip_batch *b) {
-    const size_t bytes = (size_t)b->cap_reads * sizeof(ffhip_barcode_call);
-    if (!b->bc_dev && !(b->bc_dev = (ffhip_barcode_call *)dalloc(b, bytes, true))) return FFHIP_ENOMEM;
-    if (!b->bc_host) {
-        if (hipHostMalloc((void **)&b->bc_host, bytes, hipHostMallocDefault) != hipSuccess) { b->bc_host = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation failed"); }
-        memset(b->bc_host, 0, bytes);
-    }
-    return FFHIP_OK;
-}
-
-static_assert(sizeof(ffhip_adapter_header) == 16 && sizeof(ffhip_adapter_hit) == 16 && FFHIP_ADAPTER_SEGMENT == kAdSeg && FFHIP_ADAPTER_MAX_HITS == kAdapterMaxHits,
-              "k_adapters writes a header and a hit as one 16-byte store each");
-static int ensure_adapter_buffers(ffhip_batch *b) {
-    const size_t bytes = (size_t)b->cap_reads * kAdapterRecBytes;
-    if (!b->ad_dev && !(b->ad_dev = (uint8_t *)dalloc(b, bytes, true))) return FFHIP_ENOMEM;
-    if (!b->ad_host) {
-        if (hipHostMalloc((void **)&b->ad_host, bytes, hipHostMallocDefault) != hipSuccess) { b->ad_host = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation of %zu bytes failed", bytes); }
-        memset(b->ad_host, 0, bytes);
-    }
-    return FFHIP_OK;
-}
-
 // a device buffer of the batch that grows: the old one is given back first, once the batch's stream has drained (a run that was never finished may still read it)
-static int dgrow(ffhip_batch *b, void **p, size_t *cap, size_t need, const char *what) {
+int ffhip::dgrow(ffhip_batch *b, void **p, size_t *cap, size_t need, const char *what) {
     if (*p && need <= *cap) return FFHIP_OK;
     if (*p) {
         HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
@@ -1559,238 +1503,118 @@ static int dgrow(ffhip_batch *b, void **p, size_t *cap, size_t need, const char 
     return FFHIP_OK;
 }
 
+// ---- the per-read products outside the result block (ffhip_annot.hpp).  Per feature: its share of the front (prepare: checks of its own, lists, workspaces, room
+// for the records), its share of the back (launch), what a finished run brings down (bytes) and where a read's record lies (spans); kAnnots, the table, at the end.
+static void span1(AnnotSpan out[2], size_t at, size_t bytes) { out[0] = AnnotSpan{ at, bytes }; out[1] = AnnotSpan{}; }
+
+static_assert(sizeof(ffhip_barcode_call) == 16, "k_barcodes writes a record as one 16-byte store");
+static int barcodes_prepare(ffhip_batch *b) {
+    if (!b->bc.kit) return set_err(FFHIP_EINVAL, "barcodes: no kit is attached to the batch (ffhip_batch_set_barcodes)");
+    return b->bc.rec.fixed(b, (size_t)b->cap_reads * sizeof(ffhip_barcode_call), "barcodes: the reads' records");
+}
+static void barcodes_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {        // from the strings and lengths k_assemble has just written
+    launch_barcodes(b->stream, b->bc.kit->kit, b->bases(), b->lens(), b->bc.rec.dev, batch_nreads(b), b->Tb, tbr, rmap, b->bc.max_dist, b->bc.min_sep, b->bc.both);
+    b->launches[5]++;
+    b->bc.valid = 1;
+}
+static size_t barcodes_bytes(const ffhip_batch *b) { return (size_t)batch_nreads(b) * sizeof(ffhip_barcode_call); }
+static void barcodes_spans(const ffhip_batch *, int r, AnnotSpan out[2]) { span1(out, (size_t)r * sizeof(ffhip_barcode_call), sizeof(ffhip_barcode_call)); }
+
+static_assert(sizeof(ffhip_adapter_header) == 16 && sizeof(ffhip_adapter_hit) == 16 && FFHIP_ADAPTER_SEGMENT == kAdSeg && FFHIP_ADAPTER_MAX_HITS == kAdapterMaxHits,
+              "k_adapters writes a header and a hit as one 16-byte store each");
+static int adapters_prepare(ffhip_batch *b) {
+    if (!b->ad.kit) return set_err(FFHIP_EINVAL, "adapters: no kit is attached to the batch (ffhip_batch_set_adapters)");
+    return b->ad.rec.fixed(b, (size_t)b->cap_reads * kAdapterRecBytes, "adapters: the reads' records");
+}
+static void adapters_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {        // likewise
+    launch_adapters(b->stream, b->ad.kit->kit, b->bases(), b->lens(), b->ad.rec.dev, batch_nreads(b), b->Tb, tbr, rmap, b->ad.max_dist);
+    b->launches[5]++;
+    b->ad.valid = 1;
+}
+static size_t adapters_bytes(const ffhip_batch *b) { return (size_t)batch_nreads(b) * kAdapterRecBytes; }
+static void adapters_spans(const ffhip_batch *, int r, AnnotSpan out[2]) { span1(out, (size_t)r * kAdapterRecBytes, kAdapterRecBytes); }
+
+// Remap and truth list their reads a kernel form each, one form behind the other: the pinned image and its upload, and the walk over the forms, a launch each
+static_assert(kRemapForms == kTruthForms, "one packing for both");
+template <class Read> static int forms_upload(ffhip_batch *b, Annot &f, const std::vector<Read> (&per)[kRemapForms], int (&count)[kRemapForms], int nR) {
+    size_t at = 0;
+    for (int k = 0; k < kRemapForms; k++) {
+        count[k] = (int)per[k].size();
+        if (!per[k].empty()) memcpy((Read *)f.list.host + at, per[k].data(), per[k].size() * sizeof(Read));
+        at += per[k].size();
+    }
+    return nR > 0 ? f.list.copy_up((size_t)nR * sizeof(Read), b->stream) : FFHIP_OK;
+}
+template <class Launch> static void forms_launch(ffhip_batch *b, Annot &f, const int (&count)[kRemapForms], Launch launch) {
+    size_t at = 0;
+    for (int k = 0; k < kRemapForms; k++) {
+        if (count[k] > 0) { launch(k, at, count[k]); b->launches[5]++; }
+        at += (size_t)count[k];
+    }
+    f.valid = 1;
+}
+
 // Remap, the front's share: buffers on first use, every read's status, kernel form and place in the workspace, the lists a form each, their upload.
 static_assert(sizeof(RemapRead) == 24, "the reads' list is copied as it stands");
+static bool remap_mappable(const ffhip_batch *b, int r) {      // this read's sequence can be mapped
+    const int N = b->hTb[r], L = (int)b->rmp.seq[r].size();
+    return b->rmp.state[r] == 1 && N >= 1 && L >= 1 && L <= N + 1;
+}
+static size_t remap_bytes(const ffhip_batch *b) { return remap_moves_at(b) + (size_t)b->nread * ((size_t)b->Tb + 1); }
 static int remap_prepare(ffhip_batch *b) {
-    const int nR = b->packed ? b->nvirt : b->nread;
-    if (!b->rmp_set) return set_err(FFHIP_EINVAL, "remap: no sequences are set for the batch (ffhip_batch_set_remap)");
-    if ((int)b->rmp_seq.size() != nR) return set_err(FFHIP_EINVAL, "remap: sequences were set for %zu reads, the batch holds %d", b->rmp_seq.size(), nR);
-    const size_t bytes = b->rmp_bytes();
-    if (!b->rmp_dev && !(b->rmp_dev = (uint8_t *)dalloc(b, bytes, true))) return FFHIP_ENOMEM;
-    if (!b->rmp_dlist && !(b->rmp_dlist = (RemapRead *)dalloc(b, (size_t)b->cap_reads * sizeof(RemapRead), false))) return FFHIP_ENOMEM;
-    if (!b->rmp_host) {
-        if (hipHostMalloc((void **)&b->rmp_host, bytes, hipHostMallocDefault) != hipSuccess) { b->rmp_host = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation failed"); }
-        memset(b->rmp_host, 0, bytes);
-    }
-    if (!b->rmp_hlist && hipHostMalloc((void **)&b->rmp_hlist, (size_t)b->cap_reads * sizeof(RemapRead), hipHostMallocDefault) != hipSuccess) {
-        b->rmp_hlist = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation failed");
-    }
+    ffhip_batch::Remap &f = b->rmp;
+    const int nR = batch_nreads(b);
+    if (!f.set) return set_err(FFHIP_EINVAL, "remap: no sequences are set for the batch (ffhip_batch_set_remap)");
+    if ((int)f.seq.size() != nR) return set_err(FFHIP_EINVAL, "remap: sequences were set for %zu reads, the batch holds %d", f.seq.size(), nR);
+    if (int rc = f.rec.fixed(b, remap_bytes(b), "remap: the records and moves")) return rc;
+    if (int rc = f.list.grow(b, b->stream, (size_t)b->cap_reads * sizeof(RemapRead), "remap: the reads' list")) return rc;
     std::vector<RemapRead> per[kRemapForms];
     size_t ws = 0, seq = 0;
     for (int r = 0; r < nR; r++) {
-        const int N = b->hTb[r], L = (int)b->rmp_seq[r].size();
-        RemapRead rr{ ws, (unsigned)seq, L, b->rmp_state[r], r };
+        const int L = (int)f.seq[r].size();
+        RemapRead rr{ ws, (unsigned)seq, L, f.state[r], r };
         int form = 0;
-        if (rr.status == 1 && (N < 1 || L < 1 || L > N + 1)) rr.status = 2;
+        if (rr.status == 1 && !remap_mappable(b, r)) rr.status = 2;
         if (rr.status == 1) {
-            form = remap_form(L, b->rmp_band);
+            form = remap_form(L, f.band);
             if (form < 0) return set_err(FFHIP_EINVAL, "remap: read %d's window of min(2 band + 1, L) cells is more than %d", r, remap_max_window());
-            ws += remap_ws_words(form, N);
+            ws += remap_ws_words(form, b->hTb[r]);
         }
         seq += (size_t)L;
         per[form].push_back(rr);
     }
-    if (int rc = dgrow(b, (void **)&b->rmp_ws, &b->rmp_ws_cap, ws * 8, "remap: the traceback workspace")) return rc;
-    int at = 0;
-    for (int f = 0; f < kRemapForms; f++) {
-        b->rmp_count[f] = (int)per[f].size();
-        if (!per[f].empty()) memcpy(b->rmp_hlist + at, per[f].data(), per[f].size() * sizeof(RemapRead));
-        at += (int)per[f].size();
-    }
-    if (nR > 0) HIP_TRY(hipMemcpyAsync(b->rmp_dlist, b->rmp_hlist, (size_t)nR * sizeof(RemapRead), hipMemcpyHostToDevice, b->stream), FFHIP_EHIP);
-    return FFHIP_OK;
+    if (int rc = dgrow(b, (void **)&f.ws, &f.ws_cap, ws * 8, "remap: the traceback workspace")) return rc;
+    return forms_upload(b, f, per, f.count, nR);
 }
-static void remap_launch(ffhip_batch *b, int nR, const int *tbr, ReadMap rmap) {
-    int at = 0;
-    for (int f = 0; f < kRemapForms; f++) {
-        if (b->rmp_count[f] > 0) {
-            launch_remap(b->stream, f, b->rmp_dlist + at, b->rmp_count[f], b->rmp_dseq, b->trans, b->mdl->Ps, b->rmp_band, b->rmp_ws, b->rmp_dev,
-                         b->rmp_dev + (size_t)b->cap_reads * 16, b->Tb, tbr, rmap);
-            b->launches[5]++;
-        }
-        at += b->rmp_count[f];
-    }
-    b->rmp_valid = 1;
+static void remap_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {           // from the transitions, whatever the path was decoded from
+    ffhip_batch::Remap &f = b->rmp;
+    forms_launch(b, f, f.count, [&](int form, size_t at, int n) {
+        launch_remap(b->stream, form, (const RemapRead *)f.list.dev + at, n, f.dseq, b->trans, b->mdl->Ps, f.band, f.ws, f.rec.dev, f.rec.dev + remap_moves_at(b), b->Tb, tbr, rmap);
+    });
+}
+static void remap_spans(const ffhip_batch *b, int r, AnnotSpan out[2]) {           // the record, and the moves of the read's blocks (not the entry behind them)
+    out[0] = AnnotSpan{ (size_t)r * 16, 16 };
+    out[1] = AnnotSpan{ remap_moves_at(b) + read_row1(b, r), (size_t)b->hTb[r] };
 }
 
-// Events, the front's share, behind remap's: every read's place in the one buffer, from the L of its sequence, and where its samples stand (the addresses
-// rerun_on_f32_path reads them at); the buffer and its mirror grow here.  A read remap_prepare refuses has no room and no entry.
-static_assert(sizeof(EventRead) == 32 && sizeof(ffhip_event) == 16, "the reads' list is copied as it stands; k_events writes an event as one 16-byte store");
-static int events_prepare(ffhip_batch *b) {
-    const int nR = b->packed ? b->nvirt : b->nread, st = total_stride(b->mdl);
-    if (!b->evt_dlist && !(b->evt_dlist = (EventRead *)dalloc(b, (size_t)b->cap_reads * sizeof(EventRead), false))) return FFHIP_ENOMEM;
-    if (!b->evt_hlist && hipHostMalloc((void **)&b->evt_hlist, (size_t)b->cap_reads * sizeof(EventRead), hipHostMallocDefault) != hipSuccess) {
-        b->evt_hlist = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation failed");
-    }
-    std::vector<size_t> off((size_t)nR + 1, 0);
-    std::vector<EventRead> list;
-    size_t at = 0;
-    for (int r = 0; r < nR; r++) {
-        const int N = b->hTb[r], L = (int)b->rmp_seq[r].size();
-        off[r] = at;
-        if (b->rmp_state[r] != 1 || N < 1 || L < 1 || L > N + 1) continue;
-        const size_t sig = (b->packed ? (size_t)b->v_slot[r] * b->sbuf[0].rs + (size_t)b->v_off[r] * st : (size_t)r * b->sbuf[0].rs) + kSamplePad;
-        list.push_back(EventRead{ sig, at, b->hT[r], L, r, 0 });
-        at += (size_t)L;
-    }
-    off[nR] = at;
-    const size_t bytes = std::max<size_t>(at, 1) * sizeof(ffhip_event);
-    if (int rc = dgrow(b, (void **)&b->evt_dev, &b->evt_dev_cap, bytes, "events: the reads' events")) return rc;
-    if (!b->evt_host || bytes > b->evt_host_cap) {
-        if (b->evt_host) { HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP); hipHostFree(b->evt_host); b->evt_host = nullptr; b->evt_host_cap = 0; }
-        if (hipHostMalloc((void **)&b->evt_host, bytes, hipHostMallocDefault) != hipSuccess) {
-            b->evt_host = nullptr; return set_err(FFHIP_ENOMEM, "events: the reads' events take %zu bytes of pinned host memory, which could not be had", bytes);
-        }
-        b->evt_host_cap = bytes;
-        memset(b->evt_host, 0, bytes);
-    }
-    b->evt_off = std::move(off);
-    b->evt_count = (int)list.size();
-    if (!list.empty()) {
-        memcpy(b->evt_hlist, list.data(), list.size() * sizeof(EventRead));
-        HIP_TRY(hipMemcpyAsync(b->evt_dlist, b->evt_hlist, list.size() * sizeof(EventRead), hipMemcpyHostToDevice, b->stream), FFHIP_EHIP);
-    }
-    return FFHIP_OK;
-}
-static void events_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {
-    if (b->evt_count > 0) {
-        launch_events(b->stream, b->evt_dlist, b->evt_count, b->sbuf[0].p, total_stride(b->mdl), b->rmp_dev, b->rmp_dev + (size_t)b->cap_reads * 16, b->evt_dev,
-                      b->Tb, tbr, rmap);
-        b->launches[5]++;
-    }
-    b->evt_valid = 1;
-}
-
-// Site mods, the front's share, behind remap's: the reads that have a C or Z and can be mapped, their sites one read behind the other (a site's place in the list is
-// its record's place in the buffer), every read's L + 1 words of starts; the buffers and their mirrors grow here.  A read remap_prepare refuses has no entry.
-static_assert(sizeof(SiteRead) == 24 && sizeof(SiteMod) == 8 && sizeof(ffhip_site_mod) == 16, "the lists are copied as they stand; k_site_mods writes a record as one 16-byte store");
-static int pinned_grow(ffhip_batch *b, uint8_t **p, size_t *cap, size_t need, const char *what) {
-    if (*p && need <= *cap) return FFHIP_OK;
-    if (*p) { HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP); hipHostFree(*p); *p = nullptr; *cap = 0; }
-    if (hipHostMalloc((void **)p, need, hipHostMallocDefault) != hipSuccess) {
-        *p = nullptr; return set_err(FFHIP_ENOMEM, "%s take %zu bytes of pinned host memory, which could not be had", what, need);
-    }
-    *cap = need;
-    memset(*p, 0, need);
-    return FFHIP_OK;
-}
-static int sitemods_prepare(ffhip_batch *b) {
-    const int nR = b->packed ? b->nvirt : b->nread;
-    std::vector<size_t> off((size_t)nR + 1, 0);
-    std::vector<SiteRead> list;
-    std::vector<SiteMod> sites;
-    size_t words = 0, seq = 0;
-    for (int r = 0; r < nR; r++) {
-        const int N = b->hTb[r], L = (int)b->rmp_seq[r].size();
-        off[r] = sites.size();
-        if (b->rmp_state[r] == 1 && N >= 1 && L >= 1 && L <= N + 1 && sitemods_sites(b->rmp_seq[r].data(), (size_t)L, (int)list.size(), &sites)) {
-            list.push_back(SiteRead{ words, (unsigned)seq, L, r, 0 });
-            words += (size_t)L + 1;
-        }
-        seq += (size_t)L;
-    }
-    off[nR] = sites.size();
-    if (sites.size() > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "site mods: %zu sites in one batch", sites.size());
-    const size_t bytes = std::max<size_t>(sites.size(), 1) * sizeof(ffhip_site_mod);
-    const size_t lb = list.size() * sizeof(SiteRead), lbytes = std::max<size_t>(lb + sites.size() * sizeof(SiteMod), 8);
-    if (int rc = dgrow(b, (void **)&b->smd_dev, &b->smd_dev_cap, bytes, "site mods: the sites' records")) return rc;
-    if (int rc = dgrow(b, (void **)&b->smd_start, &b->smd_start_cap, std::max<size_t>(words, 1) * 4, "site mods: the workspace of starts")) return rc;
-    if (int rc = dgrow(b, (void **)&b->smd_dlist, &b->smd_dlist_cap, lbytes, "site mods: the lists of reads and sites")) return rc;
-    if (int rc = pinned_grow(b, &b->smd_host, &b->smd_host_cap, bytes, "site mods: the sites' records")) return rc;
-    if (int rc = pinned_grow(b, &b->smd_hlist, &b->smd_hlist_cap, lbytes, "site mods: the lists of reads and sites")) return rc;
-    b->smd_off = std::move(off);
-    b->smd_reads = (int)list.size();
-    if (!sites.empty()) {
-        memcpy(b->smd_hlist, list.data(), lb);
-        memcpy(b->smd_hlist + lb, sites.data(), sites.size() * sizeof(SiteMod));
-        HIP_TRY(hipMemcpyAsync(b->smd_dlist, b->smd_hlist, lb + sites.size() * sizeof(SiteMod), hipMemcpyHostToDevice, b->stream), FFHIP_EHIP);
-    }
-    return FFHIP_OK;
-}
-static void sitemods_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {
-    if (b->smd_nsite() > 0) {
-        launch_site_mods(b->stream, (const SiteRead *)b->smd_dlist, b->smd_reads, (const SiteMod *)(b->smd_dlist + (size_t)b->smd_reads * sizeof(SiteRead)), (int)b->smd_nsite(),
-                         b->rmp_dseq, b->trans, b->mdl->Ps, b->smd_context, b->smd_all, b->rmp_dev, b->rmp_dev + (size_t)b->cap_reads * 16, b->smd_start, b->smd_dev,
-                         b->Tb, tbr, rmap);
-        b->launches[5] += 2;
-    }
-    b->smd_valid = 1;
-}
-
-// Variants, the front's share, behind remap's: as site mods', over this feature's own list of reads (those that can be mapped and have a variant), with its own
-// workspace of starts.  A variant's place in the list is its record's place in the buffer; the variants stand in front of the reads (an entry is read as 16-byte words).
-static_assert(sizeof(VarEntry) == 32 && sizeof(Variant) == sizeof(ffhip_variant) && sizeof(ffhip_variant) == 24 && sizeof(ffhip_variant_call) == 16,
-              "the lists are copied as they stand; k_variants writes a record as one 16-byte store");
-static int variants_prepare(ffhip_batch *b) {
-    const int nR = b->packed ? b->nvirt : b->nread;
-    if (b->var_set.empty()) return set_err(FFHIP_EINVAL, "variants: none are set for the batch (ffhip_batch_set_remap_variants)");
-    if ((int)b->var_set.size() != nR) return set_err(FFHIP_EINVAL, "variants: lists were set for %zu reads, the batch holds %d", b->var_set.size(), nR);
-    std::vector<size_t> off((size_t)nR + 1, 0);
-    std::vector<SiteRead> list;
-    std::vector<VarEntry> vars;
-    size_t words = 0, seq = 0;
-    for (int r = 0; r < nR; r++) {
-        const int N = b->hTb[r], L = (int)b->rmp_seq[r].size();
-        off[r] = vars.size();
-        if (b->rmp_state[r] == 1 && N >= 1 && L >= 1 && L <= N + 1 && !b->var_set[r].empty()) {
-            for (size_t i = 0; i < b->var_set[r].size(); i++) {
-                VarEntry e{ (int)list.size(), (int)i, {} };
-                memcpy(&e.v, &b->var_set[r][i], sizeof e.v);
-                vars.push_back(e);
-            }
-            list.push_back(SiteRead{ words, (unsigned)seq, L, r, 0 });
-            words += (size_t)L + 1;
-        }
-        seq += (size_t)L;
-    }
-    off[nR] = vars.size();
-    if (vars.size() > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "variants: %zu variants in one batch", vars.size());
-    const size_t bytes = std::max<size_t>(vars.size(), 1) * sizeof(ffhip_variant_call);
-    const size_t vb = vars.size() * sizeof(VarEntry), lbytes = std::max<size_t>(vb + list.size() * sizeof(SiteRead), 8);
-    if (int rc = dgrow(b, (void **)&b->var_dev, &b->var_dev_cap, bytes, "variants: the variants' records")) return rc;
-    if (int rc = dgrow(b, (void **)&b->var_start, &b->var_start_cap, std::max<size_t>(words, 1) * 4, "variants: the workspace of starts")) return rc;
-    if (int rc = dgrow(b, (void **)&b->var_dlist, &b->var_dlist_cap, lbytes, "variants: the list of variants and reads")) return rc;
-    if (int rc = pinned_grow(b, &b->var_host, &b->var_host_cap, bytes, "variants: the variants' records")) return rc;
-    if (int rc = pinned_grow(b, &b->var_hlist, &b->var_hlist_cap, lbytes, "variants: the list of variants and reads")) return rc;
-    b->var_off = std::move(off);
-    b->var_reads = (int)list.size();
-    if (!vars.empty()) {
-        memcpy(b->var_hlist, vars.data(), vb);
-        memcpy(b->var_hlist + vb, list.data(), list.size() * sizeof(SiteRead));
-        HIP_TRY(hipMemcpyAsync(b->var_dlist, b->var_hlist, vb + list.size() * sizeof(SiteRead), hipMemcpyHostToDevice, b->stream), FFHIP_EHIP);
-    }
-    return FFHIP_OK;
-}
-static void variants_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {
-    if (b->var_count() > 0) {
-        launch_variants(b->stream, (const SiteRead *)(b->var_dlist + b->var_count() * sizeof(VarEntry)), b->var_reads, (const VarEntry *)b->var_dlist, (int)b->var_count(),
-                        b->rmp_dseq, b->trans, b->mdl->Ps, b->mdl->nbase, b->var_context, b->var_all, b->rmp_dev, b->rmp_dev + (size_t)b->cap_reads * 16, b->var_start,
-                        b->var_dev, b->Tb, tbr, rmap);
-        b->launches[5] += 2;
-    }
-    b->var_valid = 1;
-}
-
-// Truth, the front's share: as remap's.  The ops' bytes follow from the truths and the reads' blocks, so records and ops grow here too (device and pinned host).
+// Truth, the front's share: as remap's.  The ops' bytes follow from the truths and the reads' blocks, so records and ops grow here.
 static_assert(sizeof(TruthRead) == 40, "the reads' list is copied as it stands");
 static int truth_prepare(ffhip_batch *b) {
-    const int nR = b->packed ? b->nvirt : b->nread;
-    if (!b->tru_set) return set_err(FFHIP_EINVAL, "truth: no truths are set for the batch (ffhip_batch_set_truth)");
-    if ((int)b->tru_seq.size() != nR) return set_err(FFHIP_EINVAL, "truth: truths were set for %zu reads, the batch holds %d", b->tru_seq.size(), nR);
-    if (!b->tru_dlist && !(b->tru_dlist = (TruthRead *)dalloc(b, (size_t)b->cap_reads * sizeof(TruthRead), false))) return FFHIP_ENOMEM;
-    if (!b->tru_hlist && hipHostMalloc((void **)&b->tru_hlist, (size_t)b->cap_reads * sizeof(TruthRead), hipHostMallocDefault) != hipSuccess) {
-        b->tru_hlist = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation failed");
-    }
+    ffhip_batch::Truth &f = b->tru;
+    const int nR = batch_nreads(b);
+    if (!f.set) return set_err(FFHIP_EINVAL, "truth: no truths are set for the batch (ffhip_batch_set_truth)");
+    if ((int)f.seq.size() != nR) return set_err(FFHIP_EINVAL, "truth: truths were set for %zu reads, the batch holds %d", f.seq.size(), nR);
+    if (int rc = f.list.grow(b, b->stream, (size_t)b->cap_reads * sizeof(TruthRead), "truth: the reads' list")) return rc;
     std::vector<TruthRead> per[kTruthForms];
     std::vector<size_t> off((size_t)nR + 1, 0);
     size_t ws = 0, seq = 0, ops = 0;
     for (int r = 0; r < nR; r++) {
-        const int N = b->hTb[r], m = (int)b->tru_seq[r].size();
-        const int cap = b->tru_state[r] == 1 && N > 0 ? m + N + 1 : 0;
-        TruthRead tr{ ws, ops, (unsigned)seq, m, N > 0 ? b->tru_state[r] : 0, r, cap, 0 };
+        const int N = b->hTb[r], m = (int)f.seq[r].size();
+        const int cap = f.state[r] == 1 && N > 0 ? m + N + 1 : 0;
+        TruthRead tr{ ws, ops, (unsigned)seq, m, N > 0 ? f.state[r] : 0, r, cap, 0 };
         int form = 0;
         if (tr.status == 1) {
-            form = truth_form(std::min<long long>(2ll * b->tru_band + 1, (long long)N + 2));
+            form = truth_form(std::min<long long>(2ll * f.band + 1, (long long)N + 2));
             if (form < 0) return set_err(FFHIP_EINVAL, "truth: read %d's window of min(2 band + 1, blocks + 2) cells is more than %d", r, truth_max_window());
             ws += truth_ws_words(form, m);
         }
@@ -1799,38 +1623,185 @@ static int truth_prepare(ffhip_batch *b) {
         per[form].push_back(tr);
     }
     off[nR] = ops;
-    const size_t bytes = b->tru_rec_bytes() + ops;
-    if (int rc = dgrow(b, (void **)&b->tru_ws, &b->tru_ws_cap, ws * 8, "truth: the traceback workspace")) return rc;
-    if (int rc = dgrow(b, (void **)&b->tru_dev, &b->tru_dev_cap, bytes, "truth: the records and ops")) return rc;
-    if (!b->tru_host || bytes > b->tru_host_cap) {
-        if (b->tru_host) { HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP); hipHostFree(b->tru_host); b->tru_host = nullptr; b->tru_host_cap = 0; }
-        if (hipHostMalloc((void **)&b->tru_host, bytes, hipHostMallocDefault) != hipSuccess) { b->tru_host = nullptr; return set_err(FFHIP_ENOMEM, "pinned host allocation failed"); }
-        b->tru_host_cap = bytes;
-        memset(b->tru_host, 0, bytes);
-    }
-    b->tru_ops = std::move(off);
-    int at = 0;
-    for (int f = 0; f < kTruthForms; f++) {
-        b->tru_count[f] = (int)per[f].size();
-        if (!per[f].empty()) memcpy(b->tru_hlist + at, per[f].data(), per[f].size() * sizeof(TruthRead));
-        at += (int)per[f].size();
-    }
-    if (nR > 0) HIP_TRY(hipMemcpyAsync(b->tru_dlist, b->tru_hlist, (size_t)nR * sizeof(TruthRead), hipMemcpyHostToDevice, b->stream), FFHIP_EHIP);
-    return FFHIP_OK;
+    if (int rc = dgrow(b, (void **)&f.ws, &f.ws_cap, ws * 8, "truth: the traceback workspace")) return rc;
+    if (int rc = f.rec.grow(b, b->stream, truth_ops_at(b) + ops, "truth: the records and ops")) return rc;
+    f.off = std::move(off);
+    return forms_upload(b, f, per, f.count, nR);
 }
-static void truth_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {
-    int at = 0;
-    for (int f = 0; f < kTruthForms; f++) {
-        if (b->tru_count[f] > 0) {
-            launch_truth(b->stream, f, b->tru_dlist + at, b->tru_count[f], b->tru_dseq, b->bases(), b->lens(), b->tru_band, b->tru_ws, (int *)b->tru_dev,
-                         b->tru_dev + b->tru_rec_bytes(), b->Tb, tbr, rmap);
-            b->launches[5]++;
-        }
-        at += b->tru_count[f];
-    }
-    b->tru_valid = 1;
+static void truth_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {           // from the strings and lengths k_assemble has just written
+    ffhip_batch::Truth &f = b->tru;
+    forms_launch(b, f, f.count, [&](int form, size_t at, int n) {
+        launch_truth(b->stream, form, (const TruthRead *)f.list.dev + at, n, f.dseq, b->bases(), b->lens(), f.band, f.ws, (int *)f.rec.dev, f.rec.dev + truth_ops_at(b), b->Tb, tbr, rmap);
+    });
+}
+static size_t truth_bytes(const ffhip_batch *b) { return truth_ops_at(b) + (b->tru.off.empty() ? 0 : b->tru.off.back()); }
+static void truth_spans(const ffhip_batch *b, int r, AnnotSpan out[2]) {
+    out[0] = AnnotSpan{ (size_t)r * kTruthRecInts * 4, (size_t)kTruthRecInts * 4 };
+    out[1] = AnnotSpan{ truth_ops_at(b) + b->tru.off[r], b->tru.off[r + 1] - b->tru.off[r] };
 }
 
+// Events, site mods and variants: 16-byte records, a read's one behind the other from its offset
+static_assert(sizeof(ffhip_event) == 16 && sizeof(ffhip_site_mod) == 16 && sizeof(ffhip_variant_call) == 16, "their kernels write a record as one 16-byte store");
+static size_t perbase_bytes(const ffhip_batch::PerBase &f) { return f.total() * 16; }
+static void perbase_spans(const ffhip_batch::PerBase &f, int r, AnnotSpan out[2]) { span1(out, f.off[r] * 16, (f.off[r + 1] - f.off[r]) * 16); }
+
+// Events, the front's share, behind remap's: every read's place in the one buffer, from the L of its sequence, and where its samples stand (the addresses
+// rerun_on_f32_path reads them at); the buffer and its mirror grow here.  A read remap_prepare refuses has no room and no entry.
+static_assert(sizeof(EventRead) == 32, "the reads' list is copied as it stands");
+static int events_prepare(ffhip_batch *b) {
+    ffhip_batch::PerBase &f = b->evt;
+    const int nR = batch_nreads(b), st = total_stride(b->mdl);
+    if (int rc = f.list.grow(b, b->stream, (size_t)b->cap_reads * sizeof(EventRead), "events: the reads' list")) return rc;
+    std::vector<size_t> off((size_t)nR + 1, 0);
+    std::vector<EventRead> list;
+    size_t at = 0;
+    for (int r = 0; r < nR; r++) {
+        const int L = (int)b->rmp.seq[r].size();
+        off[r] = at;
+        if (!remap_mappable(b, r)) continue;
+        const size_t sig = (b->packed ? (size_t)b->v_slot[r] * b->sbuf[0].rs + (size_t)b->v_off[r] * st : (size_t)r * b->sbuf[0].rs) + kSamplePad;
+        list.push_back(EventRead{ sig, at, b->hT[r], L, r, 0 });
+        at += (size_t)L;
+    }
+    off[nR] = at;
+    if (int rc = f.rec.grow(b, b->stream, std::max<size_t>(at, 1) * sizeof(ffhip_event), "events: the reads' events")) return rc;
+    f.off = std::move(off);
+    f.reads = (int)list.size();
+    if (list.empty()) return FFHIP_OK;
+    memcpy(f.list.host, list.data(), list.size() * sizeof(EventRead));
+    return f.list.copy_up(list.size() * sizeof(EventRead), b->stream);
+}
+static void events_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {          // from the path k_remap has just written and the signal the convolutions read
+    if (b->evt.reads > 0) {
+        launch_events(b->stream, (const EventRead *)b->evt.list.dev, b->evt.reads, b->sbuf[0].p, total_stride(b->mdl), b->rmp.rec.dev, b->rmp.rec.dev + remap_moves_at(b),
+                      b->evt.rec.dev, b->Tb, tbr, rmap);
+        b->launches[5]++;
+    }
+    b->evt.valid = 1;
+}
+static size_t events_bytes(const ffhip_batch *b) { return perbase_bytes(b->evt); }
+static void events_spans(const ffhip_batch *b, int r, AnnotSpan out[2]) { perbase_spans(b->evt, r, out); }
+
+// Site mods and variants, the front's share, behind remap's: the reads that can be mapped and have an entry (a C or Z; a variant), their entries one read behind the
+// other (an entry's place in its list is its record's place in the buffer), every listed read's L + 1 words of starts; buffers, mirrors and workspace grow here.
+// entries_of(r, k, &ent) appends read r's entries as those of listed read k and says whether there are any.  The two lists are one pinned image and one upload:
+// the entries in front of the reads (entries_first) or behind them.  A read remap_prepare refuses has no entry.
+struct SitesText { const char *name, *noun, *records, *starts, *lists; };
+template <class Entry, class EntriesOf> static int sites_prepare(ffhip_batch *b, ffhip_batch::Sites &f, bool entries_first, const SitesText &t, EntriesOf entries_of) {
+    const int nR = batch_nreads(b);
+    std::vector<size_t> off((size_t)nR + 1, 0);
+    std::vector<SiteRead> list;
+    std::vector<Entry> ent;
+    size_t words = 0, seq = 0;
+    for (int r = 0; r < nR; r++) {
+        const int L = (int)b->rmp.seq[r].size();
+        off[r] = ent.size();
+        if (remap_mappable(b, r) && entries_of(r, (int)list.size(), &ent)) {
+            list.push_back(SiteRead{ words, (unsigned)seq, L, r, 0 });
+            words += (size_t)L + 1;
+        }
+        seq += (size_t)L;
+    }
+    off[nR] = ent.size();
+    if (ent.size() > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "%s: %zu %s in one batch", t.name, ent.size(), t.noun);
+    const size_t lb = list.size() * sizeof(SiteRead), eb = ent.size() * sizeof(Entry);
+    if (int rc = f.rec.grow(b, b->stream, std::max<size_t>(ent.size(), 1) * 16, t.records)) return rc;
+    if (int rc = dgrow(b, (void **)&f.start, &f.start_cap, std::max<size_t>(words, 1) * 4, t.starts)) return rc;
+    if (int rc = f.list.grow(b, b->stream, std::max<size_t>(lb + eb, 8), t.lists)) return rc;
+    f.off = std::move(off);
+    f.reads = (int)list.size();
+    if (ent.empty()) return FFHIP_OK;
+    memcpy(f.list.host + (entries_first ? eb : 0), list.data(), lb);
+    memcpy(f.list.host + (entries_first ? 0 : lb), ent.data(), eb);
+    return f.list.copy_up(lb + eb, b->stream);
+}
+
+static_assert(sizeof(SiteRead) == 24 && sizeof(SiteMod) == 8, "the lists are copied as they stand");
+static int sitemods_prepare(ffhip_batch *b) {
+    static const SitesText t{ "site mods", "sites", "site mods: the sites' records", "site mods: the workspace of starts", "site mods: the lists of reads and sites" };
+    return sites_prepare<SiteMod>(b, b->smd, false, t, [&](int r, int k, std::vector<SiteMod> *out) { return sitemods_sites(b->rmp.seq[r].data(), b->rmp.seq[r].size(), k, out) > 0; });
+}
+static void sitemods_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {        // from that path, the transitions and the coded sequences
+    ffhip_batch::Sites &f = b->smd;
+    if (f.total() > 0) {
+        launch_site_mods(b->stream, (const SiteRead *)f.list.dev, f.reads, (const SiteMod *)(f.list.dev + (size_t)f.reads * sizeof(SiteRead)), (int)f.total(), b->rmp.dseq, b->trans,
+                         b->mdl->Ps, f.context, f.all, b->rmp.rec.dev, b->rmp.rec.dev + remap_moves_at(b), f.start, f.rec.dev, b->Tb, tbr, rmap);
+        b->launches[5] += 2;
+    }
+    f.valid = 1;
+}
+static size_t sitemods_bytes(const ffhip_batch *b) { return perbase_bytes(b->smd); }
+static void sitemods_spans(const ffhip_batch *b, int r, AnnotSpan out[2]) { perbase_spans(b->smd, r, out); }
+
+// (the variants stand in front of the reads: an entry is read as 16-byte words)
+static_assert(sizeof(VarEntry) == 32 && sizeof(Variant) == sizeof(ffhip_variant) && sizeof(ffhip_variant) == 24, "the lists are copied as they stand");
+static int variants_prepare(ffhip_batch *b) {
+    static const SitesText t{ "variants", "variants", "variants: the variants' records", "variants: the workspace of starts", "variants: the list of variants and reads" };
+    const int nR = batch_nreads(b);
+    if (b->var.set.empty()) return set_err(FFHIP_EINVAL, "variants: none are set for the batch (ffhip_batch_set_remap_variants)");
+    if ((int)b->var.set.size() != nR) return set_err(FFHIP_EINVAL, "variants: lists were set for %zu reads, the batch holds %d", b->var.set.size(), nR);
+    return sites_prepare<VarEntry>(b, b->var, true, t, [&](int r, int k, std::vector<VarEntry> *out) {
+        for (size_t i = 0; i < b->var.set[r].size(); i++) {
+            VarEntry e{ k, (int)i, {} };
+            memcpy(&e.v, &b->var.set[r][i], sizeof e.v);
+            out->push_back(e);
+        }
+        return !b->var.set[r].empty();
+    });
+}
+static void variants_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {        // (likewise)
+    ffhip_batch::Variants &f = b->var;
+    if (f.total() > 0) {
+        launch_variants(b->stream, (const SiteRead *)(f.list.dev + f.total() * sizeof(VarEntry)), f.reads, (const VarEntry *)f.list.dev, (int)f.total(), b->rmp.dseq, b->trans,
+                        b->mdl->Ps, b->mdl->nbase, f.context, f.all, b->rmp.rec.dev, b->rmp.rec.dev + remap_moves_at(b), f.start, f.rec.dev, b->Tb, tbr, rmap);
+        b->launches[5] += 2;
+    }
+    f.valid = 1;
+}
+static size_t variants_bytes(const ffhip_batch *b) { return perbase_bytes(b->var); }
+static void variants_spans(const ffhip_batch *b, int r, AnnotSpan out[2]) { perbase_spans(b->var, r, out); }
+
+// The table, in launch order (ffhip_batch::annot has the same): truth reads the strings as barcodes and adapters do; events, site mods and variants read what
+// k_remap has just written
+constexpr AnnotRow kAnnots[ffhip_batch::AN_COUNT] = {
+    { FFHIP_RUN_BARCODES, nullptr, 0, "barcodes: a flip-flop model only (the run-length model has no base strings)", "barcodes need a decoded run (FFHIP_RUN_NO_DECODE is set)",
+      barcodes_prepare, barcodes_launch, barcodes_bytes, barcodes_spans },
+    { FFHIP_RUN_ADAPTERS, nullptr, 0, "adapters: a flip-flop model only (the run-length model has no base strings)", "adapters need a decoded run (FFHIP_RUN_NO_DECODE is set)",
+      adapters_prepare, adapters_launch, adapters_bytes, adapters_spans },
+    { FFHIP_RUN_TRUTH, nullptr, 0, "truth: a flip-flop model only (the run-length model's call is a list of runs)", "truth needs a decoded run (FFHIP_RUN_NO_DECODE is set)",
+      truth_prepare, truth_launch, truth_bytes, truth_spans },
+    { FFHIP_RUN_REMAP, nullptr, 0, "remap: a flip-flop model only (the run-length model's scores are not transitions between bases)", "remap needs a decoded run (FFHIP_RUN_NO_DECODE is set)",
+      remap_prepare, remap_launch, remap_bytes, remap_spans },
+    { FFHIP_RUN_EVENTS, "events: the signal of a mapped read's bases needs the mapping (FFHIP_RUN_EVENTS goes with FFHIP_RUN_REMAP)", 0, nullptr, nullptr,
+      events_prepare, events_launch, events_bytes, events_spans },
+    { FFHIP_RUN_REMAP_MODS, "site mods: the scores of a mapped sequence's C positions need the mapping (FFHIP_RUN_REMAP_MODS goes with FFHIP_RUN_REMAP)", 5,
+      "site mods: the model has no modified base (FFHIP_RUN_REMAP_MODS takes a model of the alphabet ACGTZ)", nullptr, sitemods_prepare, sitemods_launch, sitemods_bytes, sitemods_spans },
+    { FFHIP_RUN_REMAP_VARIANTS, "variants: the scores of a mapped sequence's alleles need the mapping (FFHIP_RUN_REMAP_VARIANTS goes with FFHIP_RUN_REMAP)", 0, nullptr, nullptr,
+      variants_prepare, variants_launch, variants_bytes, variants_spans },
+};
+// the front's share of them all: may this run ask, then the feature's own preparations
+static int annots_prepare(ffhip_batch *b, unsigned flags) {
+    const ffhip_model *m = b->mdl;
+    for (int i = 0; i < ffhip_batch::AN_COUNT; i++) {
+        const AnnotRow &row = kAnnots[i];
+        b->annot(i).valid = 0;
+        if (!(flags & row.flag)) continue;
+        if (row.remap_text && !(flags & FFHIP_RUN_REMAP)) return set_err(FFHIP_EINVAL, "%s", row.remap_text);
+        if (row.model_text && (m->kind == FFHIP_NET_LSTM5_RLE || (row.nbase && m->nbase != row.nbase))) return set_err(FFHIP_EINVAL, "%s", row.model_text);
+        if (row.undecoded_text && (flags & FFHIP_RUN_NO_DECODE)) return set_err(FFHIP_EINVAL, "%s", row.undecoded_text);
+        if (int rc = row.prepare(b)) return rc;
+    }
+    return FFHIP_OK;
+}
+// the copies of a finished run beside the block's: one a feature the run made, if it has a byte to bring
+static int annots_copy_down(ffhip_batch *b) {
+    for (int i = 0; i < ffhip_batch::AN_COUNT; i++)
+        if (const size_t n = b->annot(i).valid ? kAnnots[i].bytes(b) : 0)
+            if (int rc = b->annot(i).rec.copy_down(n, b->stream)) return rc;
+    return FFHIP_OK;
+}
+
+// One run of a batch is enqueued in three phases -- front (convolutions), the recurrent stack, back (head, CRF, decode) -- so that
 // ffhip_batch_run_pair can put the layer launches of TWO batches into one grid between their fronts and backs (`paired`).  The front
 // decides the run's path (b->run_path); the layers and the back follow it.
 static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool paired) {
@@ -1854,48 +1825,7 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
         if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "%s", sec.undecoded_text);
         if (int rc = b->res.ensure((ResSec)i, b->stream)) return rc;
     }
-    b->bc_valid = 0;
-    if (flags & FFHIP_RUN_BARCODES) {      // (not a section of the result block: a buffer and a copy of their own)
-        if (!b->bc_kit) return set_err(FFHIP_EINVAL, "barcodes: no kit is attached to the batch (ffhip_batch_set_barcodes)");
-        if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "barcodes: a flip-flop model only (the run-length model has no base strings)");
-        if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "barcodes need a decoded run (FFHIP_RUN_NO_DECODE is set)");
-        if (int rc = ensure_barcode_buffers(b)) return rc;
-    }
-    b->ad_valid = 0;
-    if (flags & FFHIP_RUN_ADAPTERS) {      // (likewise)
-        if (!b->ad_kit) return set_err(FFHIP_EINVAL, "adapters: no kit is attached to the batch (ffhip_batch_set_adapters)");
-        if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "adapters: a flip-flop model only (the run-length model has no base strings)");
-        if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "adapters need a decoded run (FFHIP_RUN_NO_DECODE is set)");
-        if (int rc = ensure_adapter_buffers(b)) return rc;
-    }
-    b->rmp_valid = 0;
-    if (flags & FFHIP_RUN_REMAP) {         // (not a section of the result block either)
-        if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "remap: a flip-flop model only (the run-length model's scores are not transitions between bases)");
-        if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "remap needs a decoded run (FFHIP_RUN_NO_DECODE is set)");
-        if (int rc = remap_prepare(b)) return rc;
-    }
-    b->evt_valid = 0;
-    if (flags & FFHIP_RUN_EVENTS) {        // (remap's checks have passed)
-        if (!(flags & FFHIP_RUN_REMAP)) return set_err(FFHIP_EINVAL, "events: the signal of a mapped read's bases needs the mapping (FFHIP_RUN_EVENTS goes with FFHIP_RUN_REMAP)");
-        if (int rc = events_prepare(b)) return rc;
-    }
-    b->smd_valid = 0;
-    if (flags & FFHIP_RUN_REMAP_MODS) {    // (likewise)
-        if (!(flags & FFHIP_RUN_REMAP)) return set_err(FFHIP_EINVAL, "site mods: the scores of a mapped sequence's C positions need the mapping (FFHIP_RUN_REMAP_MODS goes with FFHIP_RUN_REMAP)");
-        if (m->nbase != 5) return set_err(FFHIP_EINVAL, "site mods: the model has no modified base (FFHIP_RUN_REMAP_MODS takes a model of the alphabet ACGTZ)");
-        if (int rc = sitemods_prepare(b)) return rc;
-    }
-    b->var_valid = 0;
-    if (flags & FFHIP_RUN_REMAP_VARIANTS) {      // (likewise)
-        if (!(flags & FFHIP_RUN_REMAP)) return set_err(FFHIP_EINVAL, "variants: the scores of a mapped sequence's alleles need the mapping (FFHIP_RUN_REMAP_VARIANTS goes with FFHIP_RUN_REMAP)");
-        if (int rc = variants_prepare(b)) return rc;
-    }
-    b->tru_valid = 0;
-    if (flags & FFHIP_RUN_TRUTH) {         // (nor this)
-        if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "truth: a flip-flop model only (the run-length model's call is a list of runs)");
-        if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "truth needs a decoded run (FFHIP_RUN_NO_DECODE is set)");
-        if (int rc = truth_prepare(b)) return rc;
-    }
+    if (int rc = annots_prepare(b, flags)) return rc;      // the products outside the block (kAnnots): may this run ask; their lists, workspaces and room
     if (b->packed && !p.packable)
         return set_err(FFHIP_EINVAL, "packed batches take the default path and the launch-per-step kernels only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / unfused flags, ordinary temperature)");
     // A packed batch's launch-per-step run keeps its two fp32 activations in the memory of the two split buffers its default run has (the same size at two
@@ -2179,21 +2109,8 @@ static int run_back(ffhip_batch *b) {
             launch_viterbi(s, scores, b->tb, b->path, b->qpath, b->score(), nR, Tb, m->nbase, m->Ps, tbr, rmap);
             launch_assemble(s, b->path, b->qpath, b->bases(), b->quals(), b->lens(), nR, Tb, m->nbase, tbr, rmap);
             b->launches[5] += 2;
-            if (flags & FFHIP_RUN_BARCODES) {           // from the strings and lengths k_assemble has just written (run_front checked the kit and the model)
-                launch_barcodes(s, b->bc_kit->kit, b->bases(), b->lens(), b->bc_dev, nR, Tb, tbr, rmap, b->bc_max_dist, b->bc_min_sep, b->bc_both);
-                b->bc_valid = 1;
-                b->launches[5]++;
-            }
-            if (flags & FFHIP_RUN_ADAPTERS) {           // likewise (run_front checked the kit and the model)
-                launch_adapters(s, b->ad_kit->kit, b->bases(), b->lens(), b->ad_dev, nR, Tb, tbr, rmap, b->ad_max_dist);
-                b->ad_valid = 1;
-                b->launches[5]++;
-            }
-            if (flags & FFHIP_RUN_TRUTH) truth_launch(b, tbr, rmap);          // from the strings and lengths too (run_front made the lists)
-            if (flags & FFHIP_RUN_REMAP) remap_launch(b, nR, tbr, rmap);      // from the transitions, whatever the path was decoded from (run_front made the lists)
-            if (flags & FFHIP_RUN_EVENTS) events_launch(b, tbr, rmap);        // from the path k_remap has just written and the signal the convolutions read
-            if (flags & FFHIP_RUN_REMAP_MODS) sitemods_launch(b, tbr, rmap);  // from that path, the transitions and the coded sequences
-            if (flags & FFHIP_RUN_REMAP_VARIANTS) variants_launch(b, tbr, rmap);      // (likewise)
+            for (int i = 0; i < ffhip_batch::AN_COUNT; i++)      // the products outside the block, in the table's order (run_front checked the flags and made the lists)
+                if (flags & kAnnots[i].flag) kAnnots[i].launch(b, tbr, rmap);
             if (flags & FFHIP_RUN_MOD_PROBS) {          // from the posterior whatever decoded the path (run_front checked the model)
                 launch_mod_probs(s, b->post, b->path, b->res.on_dev<uint8_t>(RF_ML), nR, Tb, m->Ps, tbr, rmap);
                 b->launches[5]++;
@@ -2217,13 +2134,7 @@ static int run_back(ffhip_batch *b) {
     b->res_copied = 0;
     if (b->packed) {
         HIP_TRY(hipMemcpyAsync(b->res.host, b->res.dev, b->res.copy_bytes(flags), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-        if (b->bc_valid) HIP_TRY(hipMemcpyAsync(b->bc_host, b->bc_dev, (size_t)nR * sizeof(ffhip_barcode_call), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the barcode records' one copy
-        if (b->ad_valid) HIP_TRY(hipMemcpyAsync(b->ad_host, b->ad_dev, (size_t)nR * kAdapterRecBytes, hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the adapter records' one copy
-        if (b->rmp_valid) HIP_TRY(hipMemcpyAsync(b->rmp_host, b->rmp_dev, b->rmp_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the remap records' and moves' one copy
-        if (b->evt_valid && b->evt_bytes()) HIP_TRY(hipMemcpyAsync(b->evt_host, b->evt_dev, b->evt_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the events' one copy
-        if (b->smd_valid && b->smd_bytes()) HIP_TRY(hipMemcpyAsync(b->smd_host, b->smd_dev, b->smd_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the site mods' one copy
-        if (b->var_valid && b->var_bytes()) HIP_TRY(hipMemcpyAsync(b->var_host, b->var_dev, b->var_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the variants' one copy
-        if (b->tru_valid) HIP_TRY(hipMemcpyAsync(b->tru_host, b->tru_dev, b->tru_bytes(), hipMemcpyDeviceToHost, s), FFHIP_EHIP);      // the truth records' and ops' one copy
+        if (int rc = annots_copy_down(b)) return rc;
         b->res_copied = 1;
     }
     HIP_TRY(hipEventRecord(eng->batch_done, s), FFHIP_EHIP); eng->batch_done_rec = 1;
@@ -2275,7 +2186,8 @@ static int rehearsal_run(ffhip_batch *b, float temperature, unsigned flags) {
     const double t = now_seconds(), start = t > b->eng->rehearsal_busy_until ? t : b->eng->rehearsal_busy_until;
     b->eng->rehearsal_busy_until = b->rehearsal_done_at = start + samples / (rehearsal_rate() * 1e6);
     b->last_flags = b->run_flags = flags; b->last_temperature = temperature;
-    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0; b->bc_valid = 0; b->ad_valid = 0; b->rmp_valid = 0; b->tru_valid = 0; b->evt_valid = 0; b->smd_valid = 0; b->var_valid = 0;
+    b->ran = 1; b->finished = 0; b->paired_last = 0; b->res_made = 0;
+    for (int i = 0; i < ffhip_batch::AN_COUNT; i++) b->annot(i).valid = 0;
     return FFHIP_OK;
 }
 
@@ -2361,25 +2273,25 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
         }
         sd->ran = sd->finished = 0;
         sd->run_scale = b->run_scale;
-        sd->bc_kit = b->bc_kit; sd->bc_max_dist = b->bc_max_dist; sd->bc_min_sep = b->bc_min_sep; sd->bc_both = b->bc_both;      // (last_flags asks the side batch for the records too)
-        sd->ad_kit = b->ad_kit; sd->ad_max_dist = b->ad_max_dist;
+        sd->bc.kit = b->bc.kit; sd->bc.max_dist = b->bc.max_dist; sd->bc.min_sep = b->bc.min_sep; sd->bc.both = b->bc.both;      // (last_flags asks the side batch for the records too)
+        sd->ad.kit = b->ad.kit; sd->ad.max_dist = b->ad.max_dist;
         if (fl & FFHIP_RUN_REMAP) {                       // ... and for these reads' sequences
             std::vector<std::vector<unsigned short>> sq(16);
             std::vector<signed char> st(16, 0);
-            for (int k = 0; k < n; k++) { sq[k] = b->rmp_seq[reads[k0 + k]]; st[k] = b->rmp_state[reads[k0 + k]]; }
-            if (int rc = remap_adopt(sd, std::move(sq), std::move(st), b->rmp_band)) return rc;
-            sd->smd_context = b->smd_context; sd->smd_all = b->smd_all;
+            for (int k = 0; k < n; k++) { sq[k] = b->rmp.seq[reads[k0 + k]]; st[k] = b->rmp.state[reads[k0 + k]]; }
+            if (int rc = remap_adopt(sd, std::move(sq), std::move(st), b->rmp.band)) return rc;
+            sd->smd.context = b->smd.context; sd->smd.all = b->smd.all;
             if (fl & FFHIP_RUN_REMAP_VARIANTS) {          // ... and their variants (remap_adopt has detached the side batch's)
-                sd->var_set.assign(16, std::vector<ffhip_variant>());
-                for (int k = 0; k < n; k++) sd->var_set[k] = b->var_set[reads[k0 + k]];
-                sd->var_context = b->var_context; sd->var_all = b->var_all;
+                sd->var.set.assign(16, std::vector<ffhip_variant>());
+                for (int k = 0; k < n; k++) sd->var.set[k] = b->var.set[reads[k0 + k]];
+                sd->var.context = b->var.context; sd->var.all = b->var.all;
             }
         }
         if (fl & FFHIP_RUN_TRUTH) {                       // ... and truths
             std::vector<std::vector<uint8_t>> sq(16);
             std::vector<signed char> st(16, 0);
-            for (int k = 0; k < n; k++) { sq[k] = b->tru_seq[reads[k0 + k]]; st[k] = b->tru_state[reads[k0 + k]]; }
-            if (int rc = truth_adopt(sd, std::move(sq), std::move(st), b->tru_band)) return rc;
+            for (int k = 0; k < n; k++) { sq[k] = b->tru.seq[reads[k0 + k]]; st[k] = b->tru.state[reads[k0 + k]]; }
+            if (int rc = truth_adopt(sd, std::move(sq), std::move(st), b->tru.band)) return rc;
         }
         if (int rc = ffhip_batch_run(sd, b->last_temperature, (fl & ~(unsigned)FFHIP_RUN_KEEP_ACTS) | FFHIP_RUN_F32_RNN)) return rc;
         if (int rc = ffhip_batch_finish(sd)) return rc;
@@ -2403,53 +2315,19 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
                 HIP_TRY(hipMemcpyAsync(b->res.on_dev<char>((ResField)f) + to, sd->res.on_dev<char>((ResField)f) + from, bytes, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
                 memcpy(b->res.on_host<char>((ResField)f) + to, sd->res.on_host<char>((ResField)f) + from, bytes);
             }
-            if (b->bc_valid && sd->bc_valid) {          // and the read's barcode record, both halves
-                HIP_TRY(hipMemcpyAsync(b->bc_dev + r, sd->bc_dev + k, sizeof(ffhip_barcode_call), hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                b->bc_host[r] = sd->bc_host[k];
-            }
-            if (b->ad_valid && sd->ad_valid) {          // and its adapter record, both halves
-                HIP_TRY(hipMemcpyAsync(b->ad_dev + r * kAdapterRecBytes, sd->ad_dev + (size_t)k * kAdapterRecBytes, kAdapterRecBytes, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                memcpy(b->ad_host + r * kAdapterRecBytes, sd->ad_host + (size_t)k * kAdapterRecBytes, kAdapterRecBytes);
-            }
-            if (b->rmp_valid && sd->rmp_valid) {        // and its remap record and moves, both halves
-                const size_t mv = (size_t)b->cap_reads * 16 + r1, smv = (size_t)sd->cap_reads * 16 + (size_t)k * L;
-                HIP_TRY(hipMemcpyAsync(b->rmp_dev + r * 16, sd->rmp_dev + (size_t)k * 16, 16, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                HIP_TRY(hipMemcpyAsync(b->rmp_dev + mv, sd->rmp_dev + smv, nb, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                memcpy(b->rmp_host + r * 16, sd->rmp_host + (size_t)k * 16, 16);
-                memcpy(b->rmp_host + mv, sd->rmp_host + smv, nb);
-            }
-            if (b->evt_valid && sd->evt_valid) {        // and its events (the same sequence and blocks: the same room), both halves
-                const size_t ne = std::min(b->evt_off[r + 1] - b->evt_off[r], sd->evt_off[k + 1] - sd->evt_off[k]) * sizeof(ffhip_event);
-                const size_t to = b->evt_off[r] * sizeof(ffhip_event), from = sd->evt_off[k] * sizeof(ffhip_event);
-                if (ne) {
-                    HIP_TRY(hipMemcpyAsync(b->evt_dev + to, sd->evt_dev + from, ne, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                    memcpy(b->evt_host + to, sd->evt_host + from, ne);
-                }
-            }
-            if (b->smd_valid && sd->smd_valid) {        // and its site mods (the same sequence: the same sites), both halves
-                const size_t ne = std::min(b->smd_off[r + 1] - b->smd_off[r], sd->smd_off[k + 1] - sd->smd_off[k]) * sizeof(ffhip_site_mod);
-                const size_t to = b->smd_off[r] * sizeof(ffhip_site_mod), from = sd->smd_off[k] * sizeof(ffhip_site_mod);
-                if (ne) {
-                    HIP_TRY(hipMemcpyAsync(b->smd_dev + to, sd->smd_dev + from, ne, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                    memcpy(b->smd_host + to, sd->smd_host + from, ne);
-                }
-            }
-            if (b->var_valid && sd->var_valid) {        // and its variants' records (the same list: the same room), both halves
-                const size_t ne = std::min(b->var_off[r + 1] - b->var_off[r], sd->var_off[k + 1] - sd->var_off[k]) * sizeof(ffhip_variant_call);
-                const size_t to = b->var_off[r] * sizeof(ffhip_variant_call), from = sd->var_off[k] * sizeof(ffhip_variant_call);
-                if (ne) {
-                    HIP_TRY(hipMemcpyAsync(b->var_dev + to, sd->var_dev + from, ne, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                    memcpy(b->var_host + to, sd->var_host + from, ne);
-                }
-            }
-            if (b->tru_valid && sd->tru_valid) {        // and its truth record and ops (the same blocks and truth: the same bytes of ops), both halves
-                const size_t rb = (size_t)kTruthRecInts * 4, to = b->tru_rec_bytes() + b->tru_ops[r], from = sd->tru_rec_bytes() + sd->tru_ops[k];
-                const size_t ob = std::min(b->tru_ops[r + 1] - b->tru_ops[r], sd->tru_ops[k + 1] - sd->tru_ops[k]);
-                HIP_TRY(hipMemcpyAsync(b->tru_dev + r * rb, sd->tru_dev + (size_t)k * rb, rb, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                memcpy(b->tru_host + r * rb, sd->tru_host + (size_t)k * rb, rb);
-                if (ob) {
-                    HIP_TRY(hipMemcpyAsync(b->tru_dev + to, sd->tru_dev + from, ob, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
-                    memcpy(b->tru_host + to, sd->tru_host + from, ob);
+            // and the products outside the block: the pieces of the read's record in every feature both runs made, both halves (the same sequence, truth,
+            // variants and blocks: the same room; remap's moves are the read's nb bytes)
+            for (int i = 0; i < ffhip_batch::AN_COUNT; i++) {
+                Annot &to = b->annot(i), &from = sd->annot(i);
+                if (!to.valid || !from.valid) continue;
+                AnnotSpan here[2], there[2];
+                kAnnots[i].spans(b, (int)r, here);
+                kAnnots[i].spans(sd, k, there);
+                for (int j = 0; j < 2; j++) {
+                    const size_t bytes = std::min(here[j].bytes, there[j].bytes);
+                    if (!bytes) continue;
+                    HIP_TRY(hipMemcpyAsync(to.rec.dev + here[j].at, from.rec.dev + there[j].at, bytes, hipMemcpyDeviceToDevice, s), FFHIP_EHIP);
+                    memcpy(to.rec.host + here[j].at, from.rec.host + there[j].at, bytes);
                 }
             }
         }
@@ -2473,20 +2351,7 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
     // one copy: [sat | abort] and, when the batch was decoded, [lens | score | bases | quals] behind them (the block of ffhip_batch_create)
     if (!b->res_copied) {
         HIP_TRY(hipMemcpyAsync(b->res.host, b->res.dev, b->res.copy_bytes(b->last_flags), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
-        if (b->bc_valid)                                     // the barcode records' one copy (a packed batch: enqueued in run_back, as the block's)
-            HIP_TRY(hipMemcpyAsync(b->bc_host, b->bc_dev, (size_t)batch_nreads(b) * sizeof(ffhip_barcode_call), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
-        if (b->ad_valid)                                     // the adapter records' one copy (likewise)
-            HIP_TRY(hipMemcpyAsync(b->ad_host, b->ad_dev, (size_t)batch_nreads(b) * kAdapterRecBytes, hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
-        if (b->rmp_valid)                                    // the remap records' and moves' one copy (likewise)
-            HIP_TRY(hipMemcpyAsync(b->rmp_host, b->rmp_dev, b->rmp_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
-        if (b->evt_valid && b->evt_bytes())                  // the events' one copy (likewise)
-            HIP_TRY(hipMemcpyAsync(b->evt_host, b->evt_dev, b->evt_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
-        if (b->smd_valid && b->smd_bytes())                  // the site mods' one copy (likewise)
-            HIP_TRY(hipMemcpyAsync(b->smd_host, b->smd_dev, b->smd_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
-        if (b->var_valid && b->var_bytes())                  // the variants' one copy (likewise)
-            HIP_TRY(hipMemcpyAsync(b->var_host, b->var_dev, b->var_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
-        if (b->tru_valid)                                    // the truth records' and ops' one copy (likewise)
-            HIP_TRY(hipMemcpyAsync(b->tru_host, b->tru_dev, b->tru_bytes(), hipMemcpyDeviceToHost, b->stream), FFHIP_EHIP);
+        if (int rc = annots_copy_down(b)) return rc;      // (a packed batch: enqueued in run_back, as the block's)
     }
     b->res_copied = 0;
     HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
@@ -2621,19 +2486,19 @@ extern "C" void ffhip_barcodes_free(ffhip_barcodes *kit) {
 }
 extern "C" int ffhip_batch_set_barcodes(ffhip_batch *b, const ffhip_barcodes *kit, int max_dist, int min_sep, int both_ends) {
     if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (!kit) { b->bc_kit = nullptr; return FFHIP_OK; }
+    if (!kit) { b->bc.kit = nullptr; return FFHIP_OK; }
     if (kit->eng != b->eng) return set_err(FFHIP_EINVAL, "the barcode kit belongs to another engine");
     if (max_dist > 255 || min_sep > 255) return set_err(FFHIP_EINVAL, "barcodes: max_dist and min_sep are at most 255");
-    b->bc_kit = kit;
-    b->bc_max_dist = max_dist < 0 ? kit->lmin / 4 : max_dist;
-    b->bc_min_sep = min_sep < 0 ? 3 : min_sep;
-    b->bc_both = both_ends ? 1 : 0;
+    b->bc.kit = kit;
+    b->bc.max_dist = max_dist < 0 ? kit->lmin / 4 : max_dist;
+    b->bc.min_sep = min_sep < 0 ? 3 : min_sep;
+    b->bc.both = both_ends ? 1 : 0;
     return FFHIP_OK;
 }
 extern "C" int ffhip_batch_barcode(const ffhip_batch *b, int read, ffhip_barcode_call *out) {
     if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
-    if (!b->bc_valid || !b->bc_host) return set_err(FFHIP_EINVAL, "barcode records were not made in this run (FFHIP_RUN_BARCODES)");
-    *out = b->bc_host[read];
+    if (!b->bc.valid || !b->bc.rec.host) return set_err(FFHIP_EINVAL, "barcode records were not made in this run (FFHIP_RUN_BARCODES)");
+    memcpy(out, b->bc.rec.host + (size_t)read * sizeof *out, sizeof *out);
     return FFHIP_OK;
 }
 
@@ -2677,40 +2542,45 @@ extern "C" void ffhip_adapters_free(ffhip_adapters *kit) {
 }
 extern "C" int ffhip_batch_set_adapters(ffhip_batch *b, const ffhip_adapters *kit, int max_dist) {
     if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (!kit) { b->ad_kit = nullptr; return FFHIP_OK; }
+    if (!kit) { b->ad.kit = nullptr; return FFHIP_OK; }
     if (kit->eng != b->eng) return set_err(FFHIP_EINVAL, "the adapter kit belongs to another engine");
-    b->ad_kit = kit;
-    b->ad_max_dist = max_dist < 0 ? -1 : std::min(max_dist, kAdapterMaxLen - 1);
+    b->ad.kit = kit;
+    b->ad.max_dist = max_dist < 0 ? -1 : std::min(max_dist, kAdapterMaxLen - 1);
     return FFHIP_OK;
 }
 extern "C" int ffhip_batch_adapters(const ffhip_batch *b, int read, ffhip_adapter_header *header, const ffhip_adapter_hit **hits) {
     if (!results_ok(b, read) || !header || !hits) return FFHIP_EINVAL;
-    if (!b->ad_valid || !b->ad_host) return set_err(FFHIP_EINVAL, "adapter records were not made in this run (FFHIP_RUN_ADAPTERS)");
-    const uint8_t *rec = b->ad_host + (size_t)read * kAdapterRecBytes;
+    if (!b->ad.valid || !b->ad.rec.host) return set_err(FFHIP_EINVAL, "adapter records were not made in this run (FFHIP_RUN_ADAPTERS)");
+    const uint8_t *rec = b->ad.rec.host + (size_t)read * kAdapterRecBytes;
     memcpy(header, rec, sizeof *header);
     *hits = (const ffhip_adapter_hit *)(rec + sizeof *header);
     return FFHIP_OK;
 }
 
 // ---- remap (include/ffhip.h "remap"; the kernel: ffhip_remap.hip)
-static int remap_adopt(ffhip_batch *b, std::vector<std::vector<unsigned short>> &&seq, std::vector<signed char> &&state, int band) {
+// new sequences of a batch (remap's coded ones, the truths): flattened, the device buffer grown to them, uploaded
+template <class T> static int seq_adopt(ffhip_batch *b, const std::vector<std::vector<T>> &seq, T **dseq, size_t *cap, const char *what) {
     size_t total = 0;
     for (const auto &q : seq) total += q.size();
     hipSetDevice(b->eng->device);
     HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
-    if (int rc = dgrow(b, (void **)&b->rmp_dseq, &b->rmp_dseq_cap, (total ? total : 1) * sizeof(unsigned short), "remap: the sequences")) return rc;
-    std::vector<unsigned short> flat;
+    if (int rc = dgrow(b, (void **)dseq, cap, (total ? total : 1) * sizeof(T), what)) return rc;
+    std::vector<T> flat;
     flat.reserve(total);
     for (const auto &q : seq) flat.insert(flat.end(), q.begin(), q.end());
-    if (total) HIP_TRY(hipMemcpy(b->rmp_dseq, flat.data(), total * sizeof(unsigned short), hipMemcpyHostToDevice), FFHIP_EHIP);
-    b->rmp_seq = std::move(seq); b->rmp_state = std::move(state);
-    b->rmp_band = band; b->rmp_set = 1;
-    b->var_set.clear();                                     // (variants are validated against the sequences: new sequences detach them)
+    if (total) HIP_TRY(hipMemcpy(*dseq, flat.data(), total * sizeof(T), hipMemcpyHostToDevice), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+static int remap_adopt(ffhip_batch *b, std::vector<std::vector<unsigned short>> &&seq, std::vector<signed char> &&state, int band) {
+    if (int rc = seq_adopt(b, seq, &b->rmp.dseq, &b->rmp.dseq_cap, "remap: the sequences")) return rc;
+    b->rmp.seq = std::move(seq); b->rmp.state = std::move(state);
+    b->rmp.band = band; b->rmp.set = 1;
+    b->var.set.clear();                                     // (variants are validated against the sequences: new sequences detach them)
     return FFHIP_OK;
 }
 extern "C" int ffhip_batch_set_remap(ffhip_batch *b, int nread, const uint8_t *const *codes, const size_t *len, int band) {
     if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (!codes) { b->rmp_set = 0; b->rmp_seq.clear(); b->rmp_state.clear(); b->var_set.clear(); return FFHIP_OK; }
+    if (!codes) { b->rmp.set = 0; b->rmp.seq.clear(); b->rmp.state.clear(); b->var.set.clear(); return FFHIP_OK; }
     const ffhip_model *m = b->mdl;
     if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "remap: a flip-flop model only (the run-length model's scores are not transitions between bases)");
     if (!len || nread != batch_nreads(b)) return set_err(FFHIP_EINVAL, "remap: sequences for %d reads, the batch holds %d", nread, batch_nreads(b));
@@ -2728,30 +2598,37 @@ extern "C" int ffhip_batch_set_remap(ffhip_batch *b, int nread, const uint8_t *c
     }
     return remap_adopt(b, std::move(seq), std::move(state), band);
 }
+// A mapped read's traceback ends at position 0; and what the accessors of everything made from the mapping ask first: the read's remap record, their outputs saying
+// "nothing", which is the answer for a status other than 1
+static int remap_end_check(int read, const int rec[4]) {
+    return rec[0] == 1 && rec[3] != 0 ? set_err(FFHIP_EHIP, "remap: read %d's traceback ended at position %d, not 0", read, rec[3]) : FFHIP_OK;
+}
+template <class T> static int remap_record(const ffhip_batch *b, int read, int rec[4], const T **out, size_t *n) {
+    memcpy(rec, b->rmp.rec.host + (size_t)read * 16, 16);
+    *out = nullptr; *n = 0;
+    return remap_end_check(read, rec);
+}
 extern "C" int ffhip_batch_remap(const ffhip_batch *b, int read, ffhip_remap_call *out) {
     if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
-    if (!b->rmp_valid || !b->rmp_host) return set_err(FFHIP_EINVAL, "remap records were not made in this run (FFHIP_RUN_REMAP)");
+    if (!b->rmp.valid || !b->rmp.rec.host) return set_err(FFHIP_EINVAL, "remap records were not made in this run (FFHIP_RUN_REMAP)");
     int rec[4];
-    memcpy(rec, b->rmp_host + (size_t)read * 16, 16);
+    memcpy(rec, b->rmp.rec.host + (size_t)read * 16, 16);
     out->status = rec[0]; out->L = (size_t)rec[1];
     memcpy(&out->score, &rec[2], 4);
     out->nblock = (size_t)b->hTb[read];
-    out->rm = rec[0] == 1 ? b->rmp_host + (size_t)b->cap_reads * 16 + read_row1(b, read) : nullptr;
-    if (rec[0] == 1 && rec[3] != 0) return set_err(FFHIP_EHIP, "remap: read %d's traceback ended at position %d, not 0", read, rec[3]);
-    return FFHIP_OK;
+    out->rm = rec[0] == 1 ? b->rmp.rec.host + remap_moves_at(b) + read_row1(b, read) : nullptr;
+    return remap_end_check(read, rec);
 }
 
 // ---- events (include/ffhip.h "events"; the kernel: ffhip_events.hip)
 extern "C" int ffhip_batch_events(const ffhip_batch *b, int read, const ffhip_event **ev, size_t *L) {
     if (!results_ok(b, read) || !ev || !L) return FFHIP_EINVAL;
-    if (!b->evt_valid || !b->rmp_valid || !b->evt_host) return set_err(FFHIP_EINVAL, "events were not made in this run (FFHIP_RUN_REMAP | FFHIP_RUN_EVENTS)");
+    if (!b->evt.valid || !b->rmp.valid || !b->evt.rec.host) return set_err(FFHIP_EINVAL, "events were not made in this run (FFHIP_RUN_REMAP | FFHIP_RUN_EVENTS)");
     int rec[4];
-    memcpy(rec, b->rmp_host + (size_t)read * 16, 16);
-    *ev = nullptr; *L = 0;
+    if (int rc = remap_record(b, read, rec, ev, L)) return rc;
     if (rec[0] != 1) return FFHIP_OK;
-    if (rec[3] != 0) return set_err(FFHIP_EHIP, "remap: read %d's traceback ended at position %d, not 0", read, rec[3]);
-    if ((size_t)rec[1] != b->evt_off[read + 1] - b->evt_off[read]) return set_err(FFHIP_EHIP, "events: read %d was mapped to %d bases, its events hold %zu", read, rec[1], b->evt_off[read + 1] - b->evt_off[read]);
-    *ev = (const ffhip_event *)b->evt_host + b->evt_off[read];
+    if ((size_t)rec[1] != b->evt.off[read + 1] - b->evt.off[read]) return set_err(FFHIP_EHIP, "events: read %d was mapped to %d bases, its events hold %zu", read, rec[1], b->evt.off[read + 1] - b->evt.off[read]);
+    *ev = (const ffhip_event *)b->evt.rec.host + b->evt.off[read];
     *L = (size_t)rec[1];
     return FFHIP_OK;
 }
@@ -2761,19 +2638,17 @@ extern "C" int ffhip_batch_set_remap_mods(ffhip_batch *b, int context, int all_p
     if (!b) return set_err(FFHIP_EINVAL, "null batch");
     if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "site mods: the batch is running (ffhip_batch_finish first)");
     if (context < 0 || context > kSiteModsMaxContext) return set_err(FFHIP_EINVAL, "site mods: the context is %d (0 .. %d)", context, kSiteModsMaxContext);
-    b->smd_context = context; b->smd_all = all_paths ? 1 : 0;
+    b->smd.context = context; b->smd.all = all_paths ? 1 : 0;
     return FFHIP_OK;
 }
 extern "C" int ffhip_batch_site_mods(const ffhip_batch *b, int read, const ffhip_site_mod **sm, size_t *nsite) {
     if (!results_ok(b, read) || !sm || !nsite) return FFHIP_EINVAL;
-    if (!b->smd_valid || !b->rmp_valid || !b->smd_host) return set_err(FFHIP_EINVAL, "site mods were not made in this run (FFHIP_RUN_REMAP | FFHIP_RUN_REMAP_MODS)");
+    if (!b->smd.valid || !b->rmp.valid || !b->smd.rec.host) return set_err(FFHIP_EINVAL, "site mods were not made in this run (FFHIP_RUN_REMAP | FFHIP_RUN_REMAP_MODS)");
     int rec[4];
-    memcpy(rec, b->rmp_host + (size_t)read * 16, 16);
-    *sm = nullptr; *nsite = 0;
+    if (int rc = remap_record(b, read, rec, sm, nsite)) return rc;
     if (rec[0] != 1) return FFHIP_OK;
-    if (rec[3] != 0) return set_err(FFHIP_EHIP, "remap: read %d's traceback ended at position %d, not 0", read, rec[3]);
-    *sm = (const ffhip_site_mod *)b->smd_host + b->smd_off[read];
-    *nsite = b->smd_off[read + 1] - b->smd_off[read];
+    *sm = (const ffhip_site_mod *)b->smd.rec.host + b->smd.off[read];
+    *nsite = b->smd.off[read + 1] - b->smd.off[read];
     return FFHIP_OK;
 }
 
@@ -2781,60 +2656,50 @@ extern "C" int ffhip_batch_site_mods(const ffhip_batch *b, int read, const ffhip
 extern "C" int ffhip_batch_set_remap_variants(ffhip_batch *b, int nread, const ffhip_variant *const *vars, const size_t *nvar, int context, int all_paths) {
     if (!b) return set_err(FFHIP_EINVAL, "null batch");
     if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "variants: the batch is running (ffhip_batch_finish first)");
-    if (!vars) { b->var_set.clear(); return FFHIP_OK; }
-    if (!b->rmp_set) return set_err(FFHIP_EINVAL, "variants: no sequences are set for the batch (ffhip_batch_set_remap comes first)");
-    if (!nvar || nread != batch_nreads(b) || (size_t)nread != b->rmp_seq.size()) return set_err(FFHIP_EINVAL, "variants: lists for %d reads, the batch holds %d", nread, batch_nreads(b));
+    if (!vars) { b->var.set.clear(); return FFHIP_OK; }
+    if (!b->rmp.set) return set_err(FFHIP_EINVAL, "variants: no sequences are set for the batch (ffhip_batch_set_remap comes first)");
+    if (!nvar || nread != batch_nreads(b) || (size_t)nread != b->rmp.seq.size()) return set_err(FFHIP_EINVAL, "variants: lists for %d reads, the batch holds %d", nread, batch_nreads(b));
     if (context < kVariantsMinContext || context > kVariantsMaxContext) return set_err(FFHIP_EINVAL, "variants: the context is %d (%d .. %d)", context, kVariantsMinContext, kVariantsMaxContext);
     std::vector<std::vector<ffhip_variant>> set((size_t)nread);
     for (int r = 0; r < nread; r++) {
         if (!nvar[r]) continue;
         if (!vars[r]) return set_err(FFHIP_EINVAL, "variants: read %d has %zu variants and no list", r, nvar[r]);
         if (nvar[r] > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "variants: read %d has %zu variants", r, nvar[r]);
-        if (b->rmp_state[r] != 1) return set_err(FFHIP_EINVAL, "variants: read %d, index 0: the read has no sequence", r);
+        if (b->rmp.state[r] != 1) return set_err(FFHIP_EINVAL, "variants: read %d, index 0: the read has no sequence", r);
         for (size_t i = 0; i < nvar[r]; i++) {
             Variant v;
             memcpy(&v, &vars[r][i], sizeof v);
-            if (const char *why = variant_invalid(v, b->rmp_seq[r].size(), b->mdl->nbase))
-                return set_err(FFHIP_EINVAL, "variants: read %d, index %zu: %s (pos %d, nref %d, nalt %d, a sequence of %zu codes)", r, i, why, (int)v.pos, (int)v.nref, (int)v.nalt, b->rmp_seq[r].size());
+            if (const char *why = variant_invalid(v, b->rmp.seq[r].size(), b->mdl->nbase))
+                return set_err(FFHIP_EINVAL, "variants: read %d, index %zu: %s (pos %d, nref %d, nalt %d, a sequence of %zu codes)", r, i, why, (int)v.pos, (int)v.nref, (int)v.nalt, b->rmp.seq[r].size());
         }
         set[r].assign(vars[r], vars[r] + nvar[r]);
     }
-    b->var_set = std::move(set);
-    b->var_context = context; b->var_all = all_paths ? 1 : 0;
+    b->var.set = std::move(set);
+    b->var.context = context; b->var.all = all_paths ? 1 : 0;
     return FFHIP_OK;
 }
 extern "C" int ffhip_batch_variant_calls(const ffhip_batch *b, int read, const ffhip_variant_call **vc, size_t *nvar) {
     if (!results_ok(b, read) || !vc || !nvar) return FFHIP_EINVAL;
-    if (!b->var_valid || !b->rmp_valid || !b->var_host) return set_err(FFHIP_EINVAL, "variants were not scored in this run (FFHIP_RUN_REMAP | FFHIP_RUN_REMAP_VARIANTS)");
+    if (!b->var.valid || !b->rmp.valid || !b->var.rec.host) return set_err(FFHIP_EINVAL, "variants were not scored in this run (FFHIP_RUN_REMAP | FFHIP_RUN_REMAP_VARIANTS)");
     int rec[4];
-    memcpy(rec, b->rmp_host + (size_t)read * 16, 16);
-    *vc = nullptr; *nvar = 0;
+    if (int rc = remap_record(b, read, rec, vc, nvar)) return rc;
     if (rec[0] != 1) return FFHIP_OK;
-    if (rec[3] != 0) return set_err(FFHIP_EHIP, "remap: read %d's traceback ended at position %d, not 0", read, rec[3]);
-    *vc = (const ffhip_variant_call *)b->var_host + b->var_off[read];
-    *nvar = b->var_off[read + 1] - b->var_off[read];
+    *vc = (const ffhip_variant_call *)b->var.rec.host + b->var.off[read];
+    *nvar = b->var.off[read + 1] - b->var.off[read];
     return FFHIP_OK;
 }
 
 // ---- truth (include/ffhip.h "truth"; the kernel: ffhip_truth.hip)
 static int truth_adopt(ffhip_batch *b, std::vector<std::vector<uint8_t>> &&seq, std::vector<signed char> &&state, int band) {
-    size_t total = 0;
-    for (const auto &q : seq) total += q.size();
-    hipSetDevice(b->eng->device);
-    HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
-    if (int rc = dgrow(b, (void **)&b->tru_dseq, &b->tru_dseq_cap, total ? total : 1, "truth: the truths")) return rc;
-    std::vector<uint8_t> flat;
-    flat.reserve(total);
-    for (const auto &q : seq) flat.insert(flat.end(), q.begin(), q.end());
-    if (total) HIP_TRY(hipMemcpy(b->tru_dseq, flat.data(), total, hipMemcpyHostToDevice), FFHIP_EHIP);
-    b->tru_seq = std::move(seq); b->tru_state = std::move(state);
-    b->tru_band = band; b->tru_set = 1;
+    if (int rc = seq_adopt(b, seq, &b->tru.dseq, &b->tru.dseq_cap, "truth: the truths")) return rc;
+    b->tru.seq = std::move(seq); b->tru.state = std::move(state);
+    b->tru.band = band; b->tru.set = 1;
     return FFHIP_OK;
 }
 extern "C" int ffhip_batch_set_truth(ffhip_batch *b, int nread, const uint8_t *const *codes, const size_t *len, int band) {
     if (!b) return set_err(FFHIP_EINVAL, "null batch");
     if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "truth: the batch is between a run and its finish");
-    if (!codes) { b->tru_set = 0; b->tru_seq.clear(); b->tru_state.clear(); return FFHIP_OK; }
+    if (!codes) { b->tru.set = 0; b->tru.seq.clear(); b->tru.state.clear(); return FFHIP_OK; }
     const ffhip_model *m = b->mdl;
     if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "truth: a flip-flop model only (the run-length model's call is a list of runs)");
     if (!len || nread != batch_nreads(b)) return set_err(FFHIP_EINVAL, "truth: truths for %d reads, the batch holds %d", nread, batch_nreads(b));
@@ -2853,17 +2718,17 @@ extern "C" int ffhip_batch_set_truth(ffhip_batch *b, int nread, const uint8_t *c
 }
 extern "C" int ffhip_batch_truth(const ffhip_batch *b, int read, ffhip_truth_call *out) {
     if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
-    if (!b->tru_valid || !b->tru_host) return set_err(FFHIP_EINVAL, "truth records were not made in this run (FFHIP_RUN_TRUTH)");
+    if (!b->tru.valid || !b->tru.rec.host) return set_err(FFHIP_EINVAL, "truth records were not made in this run (FFHIP_RUN_TRUTH)");
     int rec[kTruthRecInts];
-    memcpy(rec, b->tru_host + (size_t)read * sizeof rec, sizeof rec);
+    memcpy(rec, b->tru.rec.host + (size_t)read * sizeof rec, sizeof rec);
     out->status = rec[0]; out->n = (size_t)rec[1]; out->m = (size_t)rec[2]; out->dist = rec[3];
     out->n_match = rec[4]; out->n_mismatch = rec[5]; out->n_ins = rec[6]; out->n_del = rec[7];
     out->maxdev = rec[8]; out->nops = (size_t)rec[9];
     out->ops = nullptr;
     if (rec[0] == 1) {
-        const size_t cap = b->tru_ops[read + 1] - b->tru_ops[read];
+        const size_t cap = b->tru.off[read + 1] - b->tru.off[read];
         if (rec[10] != 0 || out->nops > cap) return set_err(FFHIP_EHIP, "truth: read %d's traceback ended %d cells from (0, 0)", read, rec[10]);
-        out->ops = b->tru_host + b->tru_rec_bytes() + b->tru_ops[read + 1] - out->nops;
+        out->ops = b->tru.rec.host + truth_ops_at(b) + b->tru.off[read + 1] - out->nops;
     }
     return FFHIP_OK;
 }
