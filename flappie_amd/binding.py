@@ -34,6 +34,10 @@ RUN_MOVES = 8192          # flip-flop model: the move table (one byte a block, 1
 RUN_ADAPTERS = 1048576   # flip-flop model: one adapter record a read (a header and up to 15 hits) made on the device against the kit of Batch.set_adapters (Batch.adapters)
 ADAPTER_SEGMENT = 512    # FFHIP_ADAPTER_SEGMENT (include/ffhip.h "adapters"): the columns one wave of k_adapters owns; checked against the library at load
 ADAPTER_MAX_HITS = 15
+RUN_POLYTAIL = 2097152    # flip-flop model: one poly tail record a read made on the device from the Viterbi path and the signal with the parameters of Batch.set_polytail (Batch.polytail)
+POLYTAIL_DTYPE = np.dtype([("status", np.int32), ("first", np.int32), ("count", np.int32), ("flat", np.int32), ("calls", np.int32),
+                           ("level", np.float32), ("rate", np.float32), ("bases", np.float32)])      # ffhip_polytail (include/ffhip.h)
+POLYTAIL_DEFAULTS = dict(base=0, from_end=0, window=8, min_calls=4, gap=2, min_windows=5, search=500, min_bases=20, max_sd=0.3)      # flappie --poly-tail's, at stride 5
 RUN_BARCODES = 16384      # flip-flop model: one barcode record a read made on the device against the kit of Batch.set_barcodes (Batch.barcode)
 RUN_REMAP = 32768         # flip-flop model: each read's signal mapped to the sequence of Batch.set_remap on the device (Batch.remap)
 RUN_TRUTH = 65536         # flip-flop model: each read's call aligned to the truth of Batch.set_truth on the device (Batch.truth)
@@ -92,6 +96,24 @@ class CBarcodeCall(C.Structure):
     """ffhip_barcode_call (include/ffhip.h): 16 bytes"""
     _fields_ = [("best", C.c_int16), ("best_dist", C.c_uint8), ("second_dist", C.c_uint8), ("front_dist", C.c_uint8), ("rear_dist", C.c_uint8),
                 ("ends", C.c_uint8), ("pad", C.c_uint8), ("front_end", C.c_int16), ("rear_end", C.c_int16), ("reserved", C.c_int32)]
+
+
+class CPolyTailParams(C.Structure):
+    """ffhip_polytail_params (include/ffhip.h): 36 bytes"""
+    _fields_ = [("base", C.c_int32), ("from_end", C.c_int32), ("window", C.c_int32), ("min_calls", C.c_int32), ("gap", C.c_int32), ("min_windows", C.c_int32),
+                ("search", C.c_int32), ("min_bases", C.c_int32), ("max_sd", C.c_float)]
+
+
+def _polytail_params(params: dict) -> CPolyTailParams:
+    """POLYTAIL_DEFAULTS with `params` over them; min_calls follows a window given without it (half the window, rounded up)"""
+    unknown = set(params) - set(POLYTAIL_DEFAULTS)
+    if unknown:
+        raise TypeError("no such poly tail parameter: " + ", ".join(sorted(unknown)))
+    p = dict(POLYTAIL_DEFAULTS)
+    if "window" in params and "min_calls" not in params:
+        p["min_calls"] = (int(params["window"]) + 1) // 2
+    p.update(params)
+    return CPolyTailParams(*[int(p[k]) for k in list(POLYTAIL_DEFAULTS)[:8]], float(p["max_sd"]))
 
 
 class CAdapterHeader(C.Structure):
@@ -250,6 +272,11 @@ def lib():
     L.ffhip_adapter_segment.restype = C.c_int
     L.ffhip_adapter_segment.argtypes = []
     assert L.ffhip_adapter_segment() == ADAPTER_SEGMENT, "binding.py and libffhip.so disagree on FFHIP_ADAPTER_SEGMENT"
+    L.ffhip_batch_set_polytail.argtypes = [vp, C.POINTER(CPolyTailParams)]
+    L.ffhip_batch_polytail.argtypes = [vp, C.c_int, vp]
+    L.ffhip_op_polytail.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_int), C.c_size_t, C.c_int, C.POINTER(CPolyTailParams), vp]
+    L.ffhip_op_polytail_windows.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_int), C.c_size_t, C.c_int, C.POINTER(CPolyTailParams),
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
     L.ffhip_batch_set_remap.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t), C.c_int]
     L.ffhip_batch_remap.argtypes = [vp, C.c_int, C.POINTER(CRemapCall)]
     L.ffhip_op_remap.argtypes = [vp, CFMat, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_float)]
@@ -655,6 +682,21 @@ class Batch:
         _check(lib().ffhip_batch_adapters(self.h, read, C.byref(h), C.byref(hits)))
         return _adapter_record(h, hits)
 
+    def set_polytail(self, **params):
+        """the parameters of later runs with RUN_POLYTAIL (ffhip_batch_set_polytail): the fields of POLYTAIL_DEFAULTS by name, the others at their defaults;
+        set_polytail(detach=True) detaches"""
+        if params.pop("detach", False):
+            _check(lib().ffhip_batch_set_polytail(self.h, None))
+            return
+        p = _polytail_params(params)
+        _check(lib().ffhip_batch_set_polytail(self.h, C.byref(p)))
+
+    def polytail(self, read: int):
+        """poly tail record of a run with RUN_POLYTAIL (ffhip_batch_polytail): a numpy record of POLYTAIL_DTYPE"""
+        out = np.zeros((), POLYTAIL_DTYPE)
+        _check(lib().ffhip_batch_polytail(self.h, read, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def barcode(self, read: int) -> dict:
         """barcode record of a run with RUN_BARCODES (ffhip_batch_barcode): the fields of BARCODE_FIELDS as ints"""
         c = CBarcodeCall()
@@ -924,6 +966,32 @@ def op_remap(engine: Engine, trans: np.ndarray, nbase: int, codes, band: int = 2
     _check(lib().ffhip_op_remap(engine.h, CFMat(_fptr(t), t.shape[1], t.shape[0], t.shape[1]), int(nbase), (q if q.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), q.size, int(band),
                                 rm.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(score)))
     return rm, np.float32(score.value)
+
+
+def _polytail_inputs(signal, path):
+    x = np.ascontiguousarray(signal, dtype=np.float32)
+    pth = np.ascontiguousarray(path, dtype=np.int32)
+    return x, pth, (x if x.size else np.zeros(1, np.float32)).ctypes.data_as(C.POINTER(C.c_float)), (pth if pth.size else np.zeros(1, np.int32)).ctypes.data_as(C.POINTER(C.c_int))
+
+
+def op_polytail(engine: Engine, signal, stride: int, path, nbase: int, **params):
+    """ffhip_op_polytail: the poly tail record (POLYTAIL_DTYPE) of ONE read from its prepared signal (float32), the model's stride and its Viterbi path (nblock + 1 states)"""
+    x, pth, xp, pp = _polytail_inputs(signal, path)
+    p, out = _polytail_params(params), np.zeros((), POLYTAIL_DTYPE)
+    _check(lib().ffhip_op_polytail(engine.h, xp, x.size, int(stride), pp, max(pth.size, 1) - 1, int(nbase), C.byref(p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def op_polytail_windows(engine: Engine, signal, stride: int, path, nbase: int, **params) -> tuple:
+    """ffhip_op_polytail_windows: (mu float64, q float64, flag uint8) of the NW windows of ONE read, inputs as for op_polytail"""
+    x, pth, xp, pp = _polytail_inputs(signal, path)
+    p = _polytail_params(params)
+    nblock = max(pth.size, 1) - 1
+    nw = min(nblock, x.size // max(int(stride), 1)) // max(int(p.window), 1)
+    mu, q, flag = np.zeros(max(nw, 1)), np.zeros(max(nw, 1)), np.zeros(max(nw, 1), np.uint8)
+    _check(lib().ffhip_op_polytail_windows(engine.h, xp, x.size, int(stride), pp, nblock, int(nbase), C.byref(p), mu.ctypes.data_as(C.POINTER(C.c_double)),
+                                           q.ctypes.data_as(C.POINTER(C.c_double)), flag.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return mu[:nw], q[:nw], flag[:nw]
 
 
 def op_events(engine: Engine, signal, stride: int, rm, L: int) -> np.ndarray:

@@ -764,6 +764,9 @@ struct ffhip_batch {
     struct Barcodes : Annot { const ffhip_barcodes *kit = nullptr; int max_dist = 0, min_sep = 3, both = 0; } bc;
     // Adapter records (FFHIP_RUN_ADAPTERS, k_adapters): 256 bytes a read, cap_reads of them
     struct Adapters : Annot { const ffhip_adapters *kit = nullptr; int max_dist = -1; } ad;
+    // Poly tail records (FFHIP_RUN_POLYTAIL, k_polytail): 32 bytes a read, cap_reads of them; the reads' list, written by the front of every run that asks; the
+    // windows' workspace (a double and a byte a window of every read, `windows` of them in this run), grown when a run needs more
+    struct PolyTail : Annot { ffhip_polytail_params p{}; bool set = false; uint8_t *ws = nullptr; size_t ws_cap = 0, windows = 0; } pt;
     // Remap (FFHIP_RUN_REMAP, k_remap): the coded sequences of ffhip_batch_set_remap on the host and (dseq) on the device; cap_reads 16-byte records and, behind them,
     // a byte a block in the layout of the (Tb + 1)-entry buffers; the reads' list and the traceback workspace, both written by the front of every run that asks
     struct Remap : Annot {
@@ -797,8 +800,8 @@ struct ffhip_batch {
     } evt;
     struct Sites : PerBase { int *start = nullptr; size_t start_cap = 0; int context, all = 0; explicit Sites(int c) : context(c) {} } smd{ 15 };
     struct Variants : Sites { std::vector<std::vector<ffhip_variant>> set; Variants() : Sites(10) {} } var;
-    enum { AN_COUNT = 7 };
-    Annot &annot(int i) { Annot *const a[AN_COUNT] = { &bc, &ad, &tru, &rmp, &evt, &smd, &var }; return *a[i]; }       // (the order of kAnnots: launch order)
+    enum { AN_COUNT = 8 };
+    Annot &annot(int i) { Annot *const a[AN_COUNT] = { &bc, &ad, &pt, &tru, &rmp, &evt, &smd, &var }; return *a[i]; }       // (the order of kAnnots: launch order)
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
     std::vector<void *> owned;
     unsigned last_flags = 0;
@@ -1534,6 +1537,38 @@ static void adapters_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {     
 static size_t adapters_bytes(const ffhip_batch *b) { return (size_t)batch_nreads(b) * kAdapterRecBytes; }
 static void adapters_spans(const ffhip_batch *, int r, AnnotSpan out[2]) { span1(out, (size_t)r * kAdapterRecBytes, kAdapterRecBytes); }
 
+// Poly tail, the front's share: every read's samples (the addresses events_prepare gives) and its first window in the workspace, which grows here
+static_assert(sizeof(ffhip_polytail) == kPolyTailRecBytes && sizeof(ffhip_polytail_params) == sizeof(PolyTailParams) && sizeof(PolyRead) == 24,
+              "k_polytail writes a record as two 16-byte stores; the parameters and the reads' list are copied as they stand");
+static int polytail_prepare(ffhip_batch *b) {
+    ffhip_batch::PolyTail &f = b->pt;
+    if (!f.set) return set_err(FFHIP_EINVAL, "poly tail: no parameters are set for the batch (ffhip_batch_set_polytail)");
+    const int nR = batch_nreads(b), st = total_stride(b->mdl);
+    if (int rc = f.rec.fixed(b, (size_t)b->cap_reads * kPolyTailRecBytes, "poly tail: the reads' records")) return rc;
+    if (int rc = f.list.grow(b, b->stream, (size_t)b->cap_reads * sizeof(PolyRead), "poly tail: the reads' list")) return rc;
+    PolyRead *list = (PolyRead *)f.list.host;
+    size_t at = 0;
+    for (int r = 0; r < nR; r++) {
+        const size_t sig = (b->packed ? (size_t)b->v_slot[r] * b->sbuf[0].rs + (size_t)b->v_off[r] * st : (size_t)r * b->sbuf[0].rs) + kSamplePad;
+        list[r] = PolyRead{ sig, at, b->hT[r], r };
+        at += (size_t)(std::min(b->hTb[r], b->hT[r] / st) / f.p.window);
+    }
+    if (int rc = dgrow(b, (void **)&f.ws, &f.ws_cap, std::max<size_t>(at, 1) * 9, "poly tail: the windows' workspace")) return rc;
+    f.windows = at;
+    return nR > 0 ? f.list.copy_up((size_t)nR * sizeof(PolyRead), b->stream) : FFHIP_OK;
+}
+static void polytail_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {        // from the path the decode has just written and the signal the convolutions read
+    ffhip_batch::PolyTail &f = b->pt;
+    PolyTailParams p;
+    memcpy(&p, &f.p, sizeof p);
+    launch_polytail(b->stream, (const PolyRead *)f.list.dev, batch_nreads(b), b->sbuf[0].p, total_stride(b->mdl), b->path, b->mdl->nbase, p, f.rec.dev,
+                    (double *)f.ws, f.ws + 8 * f.windows, nullptr, b->Tb, tbr, rmap);
+    b->launches[5]++;
+    f.valid = 1;
+}
+static size_t polytail_bytes(const ffhip_batch *b) { return (size_t)batch_nreads(b) * kPolyTailRecBytes; }
+static void polytail_spans(const ffhip_batch *, int r, AnnotSpan out[2]) { span1(out, (size_t)r * kPolyTailRecBytes, kPolyTailRecBytes); }
+
 // Remap and truth list their reads a kernel form each, one form behind the other: the pinned image and its upload, and the walk over the forms, a launch each
 static_assert(kRemapForms == kTruthForms, "one packing for both");
 template <class Read> static int forms_upload(ffhip_batch *b, Annot &f, const std::vector<Read> (&per)[kRemapForms], int (&count)[kRemapForms], int nR) {
@@ -1761,13 +1796,15 @@ static void variants_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {     
 static size_t variants_bytes(const ffhip_batch *b) { return perbase_bytes(b->var); }
 static void variants_spans(const ffhip_batch *b, int r, AnnotSpan out[2]) { perbase_spans(b->var, r, out); }
 
-// The table, in launch order (ffhip_batch::annot has the same): truth reads the strings as barcodes and adapters do; events, site mods and variants read what
+// The table, in launch order (ffhip_batch::annot has the same): truth reads the strings as barcodes and adapters do; the poly tail reads the path and the signal; events, site mods and variants read what
 // k_remap has just written
 constexpr AnnotRow kAnnots[ffhip_batch::AN_COUNT] = {
     { FFHIP_RUN_BARCODES, nullptr, 0, "barcodes: a flip-flop model only (the run-length model has no base strings)", "barcodes need a decoded run (FFHIP_RUN_NO_DECODE is set)",
       barcodes_prepare, barcodes_launch, barcodes_bytes, barcodes_spans },
     { FFHIP_RUN_ADAPTERS, nullptr, 0, "adapters: a flip-flop model only (the run-length model has no base strings)", "adapters need a decoded run (FFHIP_RUN_NO_DECODE is set)",
       adapters_prepare, adapters_launch, adapters_bytes, adapters_spans },
+    { FFHIP_RUN_POLYTAIL, nullptr, 0, "poly tail: a flip-flop model only (the run-length model's path is not one of bases)", "poly tail needs a decoded run (FFHIP_RUN_NO_DECODE is set)",
+      polytail_prepare, polytail_launch, polytail_bytes, polytail_spans },
     { FFHIP_RUN_TRUTH, nullptr, 0, "truth: a flip-flop model only (the run-length model's call is a list of runs)", "truth needs a decoded run (FFHIP_RUN_NO_DECODE is set)",
       truth_prepare, truth_launch, truth_bytes, truth_spans },
     { FFHIP_RUN_REMAP, nullptr, 0, "remap: a flip-flop model only (the run-length model's scores are not transitions between bases)", "remap needs a decoded run (FFHIP_RUN_NO_DECODE is set)",
@@ -2275,6 +2312,7 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
         sd->run_scale = b->run_scale;
         sd->bc.kit = b->bc.kit; sd->bc.max_dist = b->bc.max_dist; sd->bc.min_sep = b->bc.min_sep; sd->bc.both = b->bc.both;      // (last_flags asks the side batch for the records too)
         sd->ad.kit = b->ad.kit; sd->ad.max_dist = b->ad.max_dist;
+        sd->pt.p = b->pt.p; sd->pt.set = b->pt.set;
         if (fl & FFHIP_RUN_REMAP) {                       // ... and for these reads' sequences
             std::vector<std::vector<unsigned short>> sq(16);
             std::vector<signed char> st(16, 0);
@@ -2554,6 +2592,26 @@ extern "C" int ffhip_batch_adapters(const ffhip_batch *b, int read, ffhip_adapte
     const uint8_t *rec = b->ad.rec.host + (size_t)read * kAdapterRecBytes;
     memcpy(header, rec, sizeof *header);
     *hits = (const ffhip_adapter_hit *)(rec + sizeof *header);
+    return FFHIP_OK;
+}
+
+// ---- poly tail (include/ffhip.h "poly tail"; the kernel: ffhip_polytail.hip)
+extern "C" int ffhip_batch_set_polytail(ffhip_batch *b, const ffhip_polytail_params *params) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "poly tail: the batch is between a run and its finish");
+    if (!params) { b->pt.set = false; return FFHIP_OK; }
+    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "poly tail: a flip-flop model only (the run-length model's path is not one of bases)");
+    PolyTailParams p;
+    memcpy(&p, params, sizeof p);
+    if (const char *why = polytail_invalid(p)) return set_err(FFHIP_EINVAL, "poly tail: %s", why);
+    b->pt.p = *params;
+    b->pt.set = true;
+    return FFHIP_OK;
+}
+extern "C" int ffhip_batch_polytail(const ffhip_batch *b, int read, ffhip_polytail *out) {
+    if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
+    if (!b->pt.valid || !b->pt.rec.host) return set_err(FFHIP_EINVAL, "poly tail records were not made in this run (FFHIP_RUN_POLYTAIL)");
+    memcpy(out, b->pt.rec.host + (size_t)read * kPolyTailRecBytes, sizeof *out);
     return FFHIP_OK;
 }
 

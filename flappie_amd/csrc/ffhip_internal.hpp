@@ -283,6 +283,22 @@ struct EventRead {
 };
 void launch_events(hipStream_t s, const EventRead *list, int count, const float *sig, int stride, const void *records, const uint8_t *rm, void *events,
                    int Tb, const int *tbs, ReadMap map);
+// the poly(A) tail of a read (k_polytail, ffhip_polytail.hip; include/ffhip.h "poly tail"): per listed read the 32 bytes { int32 status, first, count, flat, calls;
+// float level, rate, bases } at records[read], from the read's samples sig[sig .. sig + n) and its entries at the read's row of the (Tb + 1)-entry `path`; a read
+// without blocks gets zeros.  wmu / wfl are the windows' workspace (a double and a byte a window, the read's first at `ws`; bit 0 of the byte is the flag); wq, when
+// given, takes every window's q.  One form, one launch, behind the decode on the same stream.
+struct PolyTailParams { int base, from_end, window, min_calls, gap, min_windows, search, min_bases; float max_sd; };      // include/ffhip.h's ffhip_polytail_params, byte for byte
+struct PolyRead {
+    unsigned long long sig;             // the read's first sample, in floats from `sig`
+    unsigned long long ws;              // its first window in the workspace
+    int n, read;                        // samples; the read's index in the batch
+};
+constexpr int kPolyTailMaxWindow = 64, kPolyTailMaxGap = 16;
+constexpr size_t kPolyTailRecBytes = 32;
+// nullptr when every parameter is in its range, else the range it leaves (a text for the error message)
+const char *polytail_invalid(const PolyTailParams &p);
+void launch_polytail(hipStream_t s, const PolyRead *list, int count, const float *sig, int stride, const int *path, int nbase, const PolyTailParams &p, void *records,
+                     double *wmu, uint8_t *wfl, double *wq, int Tb, const int *tbs, ReadMap map);
 // 5mC at every C / Z of a mapped sequence (k_site_starts + k_site_mods, ffhip_sitemods.hip; include/ffhip.h "site mods"), a model of nbase 5 only: per listed site
 // whose read's remap record at records[read] says { status 1, end 0, L }, the 16 bytes { int32 pos, nblock; float can, mod } at out[site's index in `sites`], from
 // the read's score rows, its coded sequence (remap_code) and its bytes at the read's row of the (Tb + 1)-entry byte buffer `rm`; any other read writes nothing.

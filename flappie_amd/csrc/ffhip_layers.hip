@@ -735,6 +735,48 @@ extern "C" int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, con
     return FFHIP_OK;
 }
 
+// the poly tail of one read from its signal and its Viterbi path (k_polytail; include/ffhip.h "poly tail"): the record, or the windows' values
+static int op_polytail(ffhip_engine *eng, const float *signal, size_t nsample, int stride, const int *path, size_t nblock, int nbase, const ffhip_polytail_params *params,
+                       ffhip_polytail *out, double *mu, double *q, uint8_t *flag) {
+    OP_ENTER(eng);
+    if (!path || !params || (nsample && !signal)) return set_err(FFHIP_EINVAL, "bad poly tail arguments (a signal, a path of nblock + 1 states, the parameters, the outputs)");
+    if (stride < 1 || nblock < 1 || nblock > (size_t)1 << 30 || nsample > (size_t)1 << 30 || (nbase != 4 && nbase != 5))
+        return set_err(FFHIP_EINVAL, "poly tail: stride %d, %zu blocks, %zu samples, nbase %d (a stride >= 1, 1 .. 2^30 blocks, at most 2^30 samples, nbase 4 or 5)", stride, nblock, nsample, nbase);
+    PolyTailParams p;
+    memcpy(&p, params, sizeof p);
+    if (const char *why = polytail_invalid(p)) return set_err(FFHIP_EINVAL, "poly tail: %s", why);
+    for (size_t i = 0; i <= nblock; i++) if (path[i] < 0 || path[i] >= 2 * nbase) return set_err(FFHIP_EINVAL, "poly tail: entry %zu of the path is %d (a state, 0 .. %d)", i, path[i], 2 * nbase - 1);
+    const size_t NW = std::min(nblock, nsample / (size_t)stride) / (size_t)p.window, room = NW ? NW : 1;
+    const PolyRead pr{ 0ull, 0ull, (int)nsample, 0 };
+    const float none = 0.0f;
+    float *d_x = (float *)tmp.upload(nsample ? signal : &none, (nsample ? nsample : 1) * sizeof(float), s);
+    int *d_path = (int *)tmp.upload(path, (nblock + 1) * 4, s);
+    PolyRead *d_list = (PolyRead *)tmp.upload(&pr, sizeof pr, s);
+    double *d_mu = (double *)tmp.get(room * 8), *d_q = (double *)tmp.get(room * 8);
+    uint8_t *d_fl = (uint8_t *)tmp.get(room), *d_rec = (uint8_t *)tmp.get(kPolyTailRecBytes);
+    if (!d_x || !d_path || !d_list || !d_mu || !d_q || !d_fl || !d_rec) OP_NOMEM();
+    launch_polytail(s, d_list, 1, d_x, stride, d_path, nbase, p, d_rec, d_mu, d_fl, d_q, (int)nblock, nullptr, ReadMap());
+    if (out) HIP_TRY(hipMemcpyAsync(out, d_rec, kPolyTailRecBytes, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    if (mu && NW) {
+        HIP_TRY(hipMemcpyAsync(mu, d_mu, NW * 8, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+        HIP_TRY(hipMemcpyAsync(q, d_q, NW * 8, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+        HIP_TRY(hipMemcpyAsync(flag, d_fl, NW, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    }
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    if (mu) for (size_t w = 0; w < NW; w++) flag[w] &= 1;       // (bit 1 is the scan's: the window ends a candidate)
+    return FFHIP_OK;
+}
+extern "C" int ffhip_op_polytail(ffhip_engine *eng, const float *signal, size_t nsample, int stride, const int *path, size_t nblock, int nbase,
+                                 const ffhip_polytail_params *params, ffhip_polytail *out) {
+    if (!out) return set_err(FFHIP_EINVAL, "poly tail: an output record");
+    return op_polytail(eng, signal, nsample, stride, path, nblock, nbase, params, out, nullptr, nullptr, nullptr);
+}
+extern "C" int ffhip_op_polytail_windows(ffhip_engine *eng, const float *signal, size_t nsample, int stride, const int *path, size_t nblock, int nbase,
+                                         const ffhip_polytail_params *params, double *mu, double *q, uint8_t *flag) {
+    if (!mu || !q || !flag) return set_err(FFHIP_EINVAL, "poly tail windows: three outputs of NW entries");
+    return op_polytail(eng, signal, nsample, stride, path, nblock, nbase, params, nullptr, mu, q, flag);
+}
+
 // the events of one read from its signal and its path (k_events; include/ffhip.h "events")
 extern "C" int ffhip_op_events(ffhip_engine *eng, const float *signal, size_t nsample, int stride, const uint8_t *rm, size_t nblock, size_t L, ffhip_event *out) {
     OP_ENTER(eng);

@@ -43,6 +43,7 @@
 #include "../../include/flappie_moves.h"
 #include "../../include/flappie_barcodes.h"
 #include "../../include/flappie_adapters.h"
+#include "../../include/flappie_polytail.h"
 #include "../../include/flappie_remap.h"
 #include "../../include/flappie_truth.h"
 #include "../../include/networks.h"
@@ -104,6 +105,16 @@ static struct argp_option options[] = {
     {"adapter-window", 272, "bases", 0, "With --trim-adapters or --split-reads: how far from an end of the call a hit is an end's adapter (default 150)"},
     {"split-reads", 273, 0, 0, "With --adapters: a read with a hit in its interior is two molecules called as one: write every stretch of the call that no hit covers as a record of its own, named <name>:<k> in signal order, with pi:Z:<name> and sp:B:i,<start>,<end>; a read without an interior hit is written whole, trimmed at its ends; a read with more than 15 hits is written unsplit (not with --emit-moves, --modbase-tags, --trace, --remap or --truth)"},
     {"split-min-length", 274, "bases", 0, "With --split-reads: pieces shorter than this are dropped and counted (default 200)"},
+    {"poly-tail", 275, 0, 0, "Measure every read's poly(A) tail on the GPU: the stretch of signal that stays flat while the model says the tail's base, divided by the samples a base of the rest of the read. Every record gains pt:i:<bases>, pa:B:i,<start>,<end> (raw samples) and pr:f:<samples a base>, or pt:i:-1 where no tail or no rate was found, behind every other tag; a summary goes to stderr (not with --split-reads)"},
+    {"poly-tail-base", 276, "letter", 0, "With --poly-tail: the tail's base, one of ACGT (default A)"},
+    {"poly-tail-end", 277, 0, 0, "With --poly-tail: search from the signal's end, for cDNA reads whose tail is there"},
+    {"poly-tail-window", 278, "blocks", 0, "With --poly-tail: blocks a window (1-64, default 8)"},
+    {"poly-tail-min-calls", 279, "blocks", 0, "With --poly-tail: blocks of the tail's base a window needs (0 to the window; default half the window, rounded up)"},
+    {"poly-tail-max-sd", 280, "sd", 0, "With --poly-tail: largest standard deviation of a flat window's samples, in the units of the normalised signal (default 0.3)"},
+    {"poly-tail-gap", 281, "windows", 0, "With --poly-tail: windows that are not flat a tail may bridge (0-16, default 2)"},
+    {"poly-tail-min-windows", 282, "windows", 0, "With --poly-tail: shortest tail kept (default 5)"},
+    {"poly-tail-search", 283, "samples", 0, "With --poly-tail: how far from the chosen end of the signal a tail may begin (default 20000)"},
+    {"poly-tail-min-bases", 284, "bases", 0, "With --poly-tail: called bases beside the tail that the rate needs (default 20)"},
     {"remap", 31, "refs.fa", 0, "Map each read's signal to a sequence you already know: the records of a FASTA file, found by read id, then by the file's base name, in SIGNAL order (reverse them yourself for --reverse and RNA). The best path of the read's transition scores through its sequence is made on the GPU and written to --remap-out; stdout does not change"},
     {"remap-out", 256, "map.tsv", 0, "With --remap: one line per read that had a record: name, status (1 mapped, 2 not: a letter outside the model's alphabet, or more bases than blocks + 1), nblock, stride, trim_start, L, band, maxdev, score and the block every base starts at"},
     {"remap-band", 257, "W", 0, "With --remap: the band's half-width in sequence positions around the straight line from (0, 0) to (nblock, L - 1) (0-2303, default 2048: the GPU holds a window of at most 2 W + 1 <= 4608 positions; maxdev = W in map.tsv says the band was touched)"},
@@ -127,6 +138,16 @@ static struct argp_option options[] = {
     {"adapter-window", 272, "bases", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"split-reads", 273, 0, OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"split-min-length", 274, "bases", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"poly-tail", 275, 0, OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"poly-tail-base", 276, "letter", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"poly-tail-end", 277, 0, OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"poly-tail-window", 278, "blocks", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"poly-tail-min-calls", 279, "blocks", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"poly-tail-max-sd", 280, "sd", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"poly-tail-gap", 281, "windows", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"poly-tail-min-windows", 282, "windows", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"poly-tail-search", 283, "samples", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"poly-tail-min-bases", 284, "bases", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"remap", 31, "refs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"truth", 258, "refs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"remap-events", 261, "events.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
@@ -201,6 +222,16 @@ static bool ad_trim = false, ad_split = false;
 #ifndef BUILD_RUNNIE
 static int ad_max_dist = -1;
 static bool ad_window_set = false, ad_min_length_set = false;
+#endif
+
+/* flappie: --poly-tail and its options (runnie: seen, to be refused); pt_opts: one of the options that go with --poly-tail was given; pt_err: the first
+ * refusal of a value, reported once every option is read (the options' order on the command line does not matter) */
+static bool pt_on = false, pt_opts = false;
+static flappie_polytail_summary pt_sum;
+#ifndef BUILD_RUNNIE
+static ffhip_polytail_params pt_params;
+static flappie_polytail_opts pt_o = { 0, 0, 8, -1, 2, 5, 20000, 20, 0.3f };
+static char pt_err[256];
 #endif
 
 /* flappie: --remap-variants file and table, --remap-variants-context, --remap-variants-all-paths (runnie: seen, to be refused) */
@@ -326,6 +357,19 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
     case 262: mods_path = arg; break;
     case 265: vars_path = arg; break;
     case 269: ad_path = arg; break;
+    case 275: pt_on = true; break;
+#ifdef BUILD_RUNNIE
+    case 276: case 277: case 278: case 279: case 280: case 281: case 282: case 283: case 284: pt_opts = true; break;
+#else
+    case 277: pt_o.from_end = 1; pt_opts = true; break;
+    case 276: case 278: case 279: case 280: case 281: case 282: case 283: case 284: {
+        static const char *const names[] = { "base", NULL, "window", "min-calls", "max-sd", "gap", "min-windows", "search", "min-bases" };
+        char why[256];
+        pt_opts = true;
+        if (0 != flappie_polytail_set(&pt_o, names[key - 276], arg, why, sizeof why) && 0 == pt_err[0]) snprintf(pt_err, sizeof pt_err, "%s", why);
+        break;
+    }
+#endif
 #ifdef BUILD_RUNNIE
     case 270: case 271: case 272: case 273: case 274: ad_opts = true; break;
 #else
@@ -549,6 +593,8 @@ typedef struct {
     ffhip_adapter_header ad_head;       /* --adapters: the read's record */
     ffhip_adapter_hit ad_hits[FFHIP_ADAPTER_MAX_HITS];
     int have_ad;
+    ffhip_polytail pt;                  /* --poly-tail: the read's record */
+    int have_pt;
     int rm_ref;                         /* --remap: the read's record of the sequences (-1: none), and what the batch returned for it */
     int have_rm, rm_status;
     size_t rm_L, rm_nblock;
@@ -671,10 +717,11 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
 }
 #else
 /* --modbase-tags: the 5mC bytes of the called bases come from the device (FFHIP_RUN_MOD_PROBS); --emit-moves: the move table does (FFHIP_RUN_MOVES);
- * --barcodes: the reads' barcode records do (FFHIP_RUN_BARCODES); --adapters: their adapter records (FFHIP_RUN_ADAPTERS) */
+ * --barcodes: the reads' barcode records do (FFHIP_RUN_BARCODES); --adapters: their adapter records (FFHIP_RUN_ADAPTERS); --poly-tail: their poly tail
+ * records (FFHIP_RUN_POLYTAIL) */
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u) |
-           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | (tr_refs ? FFHIP_RUN_TRUTH : 0u) |
+           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | (tr_refs ? FFHIP_RUN_TRUTH : 0u) |
            (ev_out ? FFHIP_RUN_EVENTS : 0u) | (md_out ? FFHIP_RUN_REMAP_MODS : 0u) | (vr_out ? FFHIP_RUN_REMAP_VARIANTS : 0u);
 }
 /* --remap: every read's record, by its read id, then by its file's base name; a bad record goes as a sequence of no bases (status 2) */
@@ -736,6 +783,7 @@ static int batch_set_truth(ffhip_batch *b, item **its, int n) {
 static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
     if (bc_dev) { const int rc = ffhip_batch_set_barcodes(b, bc_dev, args.bc_max_dist, args.bc_min_sep, args.bc_both); if (rc) return rc; }
     if (ad_dev) { const int rc = ffhip_batch_set_adapters(b, ad_dev, ad_max_dist); if (rc) return rc; }
+    if (pt_on) { const int rc = ffhip_batch_set_polytail(b, &pt_params); if (rc) return rc; }
     if (rm_refs) { const int rc = batch_set_remap(b, its, n); if (rc) return rc; }
     if (tr_refs) { const int rc = batch_set_truth(b, its, n); if (rc) return rc; }
     return ffhip_batch_run(b, args.temperature, flags);
@@ -1014,6 +1062,10 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
                 if (its[i]->have_ad && its[i]->ad_head.nhit > 0) ad_reads_with_hit++;
             }
         }
+        if (pt_on) {                                           /* likewise */
+            if (0 != ffhip_batch_polytail(b, i, &its[i]->pt)) warnx("%s", ffhip_last_error());
+            else { its[i]->have_pt = 1; if (0 != flappie_polytail_count(&pt_sum, &its[i]->pt)) warnx("out of memory for the poly tail summary"); }
+        }
         if (rm_refs && its[i]->rm_ref >= 0) {                  /* the read's mapping to its sequence: the table's line is written with the read's record */
             ffhip_remap_call rc;
             if (0 != ffhip_batch_remap(b, i, &rc)) warnx("%s", ffhip_last_error());
@@ -1211,7 +1263,17 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
             char *multi_name = NULL;              /* --no-uuid, a read of a multi-read file: <file>:<read id> (the file's name alone would stand for thousands of reads) */
             if (it->from_multi && NULL != (multi_name = malloc(strlen(base) + strlen(uuid) + 2))) { sprintf(multi_name, "%s:%s", base, uuid); base = multi_name; }
             /* --modbase-tags: Z is written as C here, in the record only -- the trace file below keeps the call as it is */
-            if (NULL != ad_kit) {
+            if (pt_on) {                             /* every tag the other options bring, and the poly tail tags behind them */
+                const flappie_adapter_out ad = { &it->ad_head, it->ad_hits, ad_kit, ad_trim, ad_split, ad_window, (size_t)ad_min_length };
+                if (!it->have_pt) warnx("No poly tail record for %s", it->filename);
+                else if (NULL != ad_kit && !it->have_ad) warnx("No adapter record for %s", it->filename);
+                else if (NULL != bc_kit && !it->have_bc) warnx("No barcode record for %s", it->filename);
+                else if (args.emit_moves && NULL == it->mv) warnx("No move table for %s", it->filename);
+                else if (args.modbase_tags && NULL == it->ml) warnx("No base-modification probabilities for %s", it->filename);
+                else fprintf_polytail_record(args.outformat, args.output, uuid, base, args.uuid, args.prefix, it->res, args.modbase_tags ? it->ml : NULL,
+                                             args.emit_moves ? it->mv : NULL, it->mv_stride, it->sm, it->sd, args.delta != 0.0f, bc_kit ? &it->bc : NULL, bc_kit,
+                                             args.bc_trim, ad_kit ? &ad : NULL, args.reverse, ad_stats, &it->pt);
+            } else if (NULL != ad_kit) {
                 const flappie_adapter_out ad = { &it->ad_head, it->ad_hits, ad_kit, ad_trim, ad_split, ad_window, (size_t)ad_min_length };
                 if (!it->have_ad) warnx("No adapter record for %s", it->filename);
                 else if (NULL != bc_kit && !it->have_bc) warnx("No barcode record for %s", it->filename);
@@ -1297,6 +1359,7 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
         it->mv = NULL;
         it->have_bc = 0;
         it->have_ad = 0;
+        it->have_pt = 0;
         free(it->rm);
         it->rm = NULL;
         free(it->ev);
@@ -2017,6 +2080,7 @@ int main(int argc, char *argv[]) {
     if ((args.rlc || args.run_scale_set) && !args.fasta) errx(EXIT_FAILURE, "--rlc and --run-scale go with --fasta");
     if (args.barcodes) errx(EXIT_FAILURE, "--barcodes is flappie's: the run-length model's records carry no base strings to search");
     if (ad_path || ad_opts) errx(EXIT_FAILURE, "--adapters is flappie's: the run-length model's records carry no base strings to search");
+    if (pt_on || pt_opts) errx(EXIT_FAILURE, "--poly-tail is flappie's: the run-length model's path is not one of bases");
     if (args.remap) errx(EXIT_FAILURE, "--remap is flappie's: the run-length model's scores are not transitions between the bases of a sequence");
     if (args.truth) errx(EXIT_FAILURE, "--truth is flappie's: the run-length model's call is a list of runs");
     if (args.remap_events) errx(EXIT_FAILURE, "--remap-events is flappie's: it goes with --remap, which the run-length model does not have");
@@ -2031,6 +2095,14 @@ int main(int argc, char *argv[]) {
         char why[256];
         bc_kit = flappie_barcode_kit_read(args.barcodes, why, sizeof why);
         if (NULL == bc_kit) errx(EXIT_FAILURE, "--barcodes %s: %s", args.barcodes, why);
+    }
+    /* --poly-tail: the options' values and what it does not go with */
+    if (pt_opts && !pt_on) errx(EXIT_FAILURE, "--poly-tail-base, --poly-tail-end, --poly-tail-window, --poly-tail-min-calls, --poly-tail-max-sd, --poly-tail-gap, --poly-tail-min-windows, --poly-tail-search and --poly-tail-min-bases go with --poly-tail");
+    if (pt_err[0]) errx(EXIT_FAILURE, "%s", pt_err);
+    if (pt_on) {
+        char why[256];
+        if (0 != flappie_polytail_params(&pt_o, 1, &pt_params, why, sizeof why)) errx(EXIT_FAILURE, "%s", why);
+        if (ad_split) errx(EXIT_FAILURE, "--poly-tail does not go with --split-reads: the pieces of a split read have no tail of their own");
     }
     /* --adapters: likewise */
     if (ad_opts && NULL == ad_path) errx(EXIT_FAILURE, "--adapter-max-dist, --trim-adapters, --adapter-window, --split-reads and --split-min-length go with --adapters");
@@ -2111,6 +2183,10 @@ int main(int argc, char *argv[]) {
 #endif
     struct ffhip_engine *eng = flappie_hip_engine();
 #ifndef BUILD_RUNNIE
+    if (pt_on) {                       /* the windows searched, from the samples asked for, at this model's stride */
+        char why[256];
+        if (0 != flappie_polytail_params(&pt_o, (int)ffhip_model_stride(mdl), &pt_params, why, sizeof why)) { stop_reader_procs(); errx(EXIT_FAILURE, "%s", why); }
+    }
     if (bc_kit && NULL == (bc_dev = ffhip_barcodes_upload(eng, bc_kit->n, (const char *const *)bc_kit->seq, args.bc_window))) {
         stop_reader_procs();
         errx(EXIT_FAILURE, "--barcodes: %s", ffhip_last_error());
@@ -2193,6 +2269,10 @@ int main(int argc, char *argv[]) {
                 ad_reads_with_hit, ad_stats[0], ad_stats[1], ad_stats[2], ad_stats[3]);
         ffhip_adapters_free(ad_dev);
         flappie_adapter_kit_free(ad_kit);
+    }
+    if (pt_on) {                       /* reads with a record, with a tail and a rate, with a tail alone; the median tail */
+        flappie_polytail_summary_print(stderr, &pt_sum);
+        flappie_polytail_summary_free(&pt_sum);
     }
     if (rm_refs) {                     /* mapped, no record, refused, and the mapped reads whose path touched the band */
         fprintf(stderr, "remap\tmapped\t%llu\nremap\tno_record\t%llu\nremap\trefused\t%llu\nremap\tband_touched\t%llu\n", rm_count[0], rm_count[1], rm_count[2], rm_count[3]);

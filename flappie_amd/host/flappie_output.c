@@ -3,7 +3,7 @@
  *  line, which the reference emits); the records with SAMv1 1.7 base-modification tags
  *  (include/flappie_modbase.h); the records with the move table and signal tags (include/flappie_moves.h); and the records with
  *  the barcode tags behind any of those (include/flappie_barcodes.h); and the records with the adapter tags behind all of them, trimmed or split
- *  (include/flappie_adapters.h).
+ *  (include/flappie_adapters.h); and the records with the poly tail tags behind everything (include/flappie_polytail.h).
  */
 #include <err.h>
 #include <math.h>
@@ -14,6 +14,7 @@
 #include "../../include/flappie_moves.h"
 #include "../../include/flappie_barcodes.h"
 #include "../../include/flappie_adapters.h"
+#include "../../include/flappie_polytail.h"
 
 enum flappie_outformat_type get_outformat(const char *formatstr) {
     if (NULL == formatstr) return FLAPPIE_OUTFORMAT_INVALID;
@@ -268,26 +269,27 @@ void fprintf_barcode_record(enum flappie_outformat_type outformat, FILE *fp, con
     free(tail); free(btags); free(mtags); free(seq); free(mm); free(mv); free(qual);
 }
 
-/* ---- records with the adapter tags (include/flappie_adapters.h): behind MM / ML, the move tags and the barcode tags when the record carries those ---- */
-void fprintf_adapter_record(enum flappie_outformat_type outformat, FILE *fp, const char *uuid, const char *readname, bool uuid_primary, const char *prefix,
-                            const struct _raw_basecall_info res, const uint8_t *ml, const uint8_t *moves, int stride, float median, float mad, bool delta,
-                            const ffhip_barcode_call *bc, const flappie_barcode_kit *bkit, bool bc_trim, const flappie_adapter_out *ad, bool reversed,
-                            unsigned long long stats[4]) {
+/* ---- records with the adapter tags (include/flappie_adapters.h): behind MM / ML, the move tags and the barcode tags when the record carries those; and with
+ * `extra` (tags, no tab in front) behind them.  ad == NULL: no adapter tags, no adapter trim, no split ---- */
+static void put_cut_record(enum flappie_outformat_type outformat, FILE *fp, const char *uuid, const char *readname, bool uuid_primary, const char *prefix,
+                           const struct _raw_basecall_info res, const uint8_t *ml, const uint8_t *moves, int stride, float median, float mad, bool delta,
+                           const ffhip_barcode_call *bc, const flappie_barcode_kit *bkit, bool bc_trim, const flappie_adapter_out *ad, bool reversed,
+                           unsigned long long stats[4], const char *extra) {
     if (FLAPPIE_OUTFORMAT_FASTQ == outformat && NULL == res.quality) {
         warnx("Can't output fastq for reads without quality values");
         return;
     }
     const char *name = uuid_primary ? uuid : readname;
-    if (NULL == ad) errx(EXIT_FAILURE, "no adapter record for %s", name);
-    const bool cuts = bc_trim || ad->trim || ad->split;
+    const bool ad_trim = NULL != ad && ad->trim, ad_split = NULL != ad && ad->split;
+    const bool cuts = bc_trim || ad_trim || ad_split;
     if (cuts && (NULL != ml || NULL != moves)) errx(EXIT_FAILURE, "adapters are not trimmed from a record with base-modification or move tags, nor is it split (%s)", name);
     char *mm = NULL, *mv = NULL, *seq = NULL, *mtags = NULL, *btags = NULL;
     if (NULL != ml) seq = modbase_seq(&res, ml, &mm, &mv);
     else seq = strdup(res.basecall ? res.basecall : "");
     if (NULL != moves) mtags = flappie_moves_tags(moves, res.nblock, stride, &res.rt, res.quality, median, mad, delta);
     if (NULL != bc) btags = flappie_barcode_tags(bc, bkit);
-    char *atags = flappie_adapter_tags(ad->head, ad->hits, ad->kit);
-    if (NULL == seq || NULL == atags || (NULL != bc && NULL == btags) || (NULL != moves && NULL == mtags))
+    char *atags = ad ? flappie_adapter_tags(ad->head, ad->hits, ad->kit) : NULL;
+    if (NULL == seq || (NULL != ad && NULL == atags) || (NULL != bc && NULL == btags) || (NULL != moves && NULL == mtags))
         errx(EXIT_FAILURE, "no adapter tags for %s (out of memory, or a record that does not belong to the kit)", name);
     const size_t len = strlen(seq);
     /* the pieces to write, in signal order: the whole call, what the trims leave of it, or the pieces of a split read */
@@ -296,7 +298,7 @@ void fprintf_adapter_record(enum flappie_outformat_type outformat, FILE *fp, con
     size_t bfrom = 0, bto = len;
     int crossed = 0;
     if (bc_trim && NULL != bc) crossed = flappie_barcode_trim(bc, len, &bfrom, &bto);
-    if (ad->split && !crossed) {
+    if (ad_split && !crossed) {
         int ndropped = 0;
         mode = flappie_adapter_split(ad->head, ad->hits, len, ad->window, ad->min_length, bfrom, bto, pieces, &npiece, &ndropped);
         if (FLAPPIE_SPLIT_OVERFLOW == mode) {
@@ -305,10 +307,10 @@ void fprintf_adapter_record(enum flappie_outformat_type outformat, FILE *fp, con
         } else if (FLAPPIE_SPLIT_SPLIT == mode && stats) { stats[0]++; stats[1] += (unsigned long long)npiece; stats[2] += (unsigned long long)ndropped; }
         else if (FLAPPIE_SPLIT_WHOLE == mode && 0 == pieces[0].to && len > 0) crossed = 1;
     }
-    if (!ad->split || FLAPPIE_SPLIT_OVERFLOW == mode) {      /* one record: the larger cut at each end wins */
+    if (!ad_split || FLAPPIE_SPLIT_OVERFLOW == mode) {      /* one record: the larger cut at each end wins */
         size_t from = 0, to = len;
         npiece = 1;
-        if (ad->trim && !crossed) crossed = flappie_adapter_trim(ad->head, ad->hits, len, ad->window, &from, &to);
+        if (ad_trim && !crossed) crossed = flappie_adapter_trim(ad->head, ad->hits, len, ad->window, &from, &to);
         if (!crossed) {
             if (bfrom > from) from = bfrom;
             if (bto < to) to = bto;
@@ -322,7 +324,7 @@ void fprintf_adapter_record(enum flappie_outformat_type outformat, FILE *fp, con
         pieces[0].from = pieces[0].to = 0;
         npiece = 1;
     }
-    const size_t fixed = (mm ? strlen(mm) + strlen(mv) + 2 : 0) + (mtags ? strlen(mtags) + 1 : 0) + (btags ? strlen(btags) + 1 : 0) + strlen(atags) + 2;
+    const size_t fixed = (mm ? strlen(mm) + strlen(mv) + 2 : 0) + (mtags ? strlen(mtags) + 1 : 0) + (btags ? strlen(btags) + 1 : 0) + (atags ? strlen(atags) + 1 : 0) + (extra ? strlen(extra) + 1 : 0) + 2;
     const bool named = FLAPPIE_SPLIT_SPLIT == mode;
     for (int k = 0; k < npiece; k++) {
         const size_t from = reversed ? len - pieces[k].to : pieces[k].from, to = reversed ? len - pieces[k].from : pieces[k].to;      /* a reversed SEQ holds the piece at its other end */
@@ -335,7 +337,9 @@ void fprintf_adapter_record(enum flappie_outformat_type outformat, FILE *fp, con
         if (mm) a += (size_t)sprintf(tail + a, "\t%s\t%s", mm, mv);
         if (mtags) a += (size_t)sprintf(tail + a, "\t%s", mtags);
         if (btags) a += (size_t)sprintf(tail + a, "\t%s", btags);
-        a += (size_t)sprintf(tail + a, "\t%s", atags);
+        tail[a] = 0;
+        if (atags) a += (size_t)sprintf(tail + a, "\t%s", atags);
+        if (extra) a += (size_t)sprintf(tail + a, "\t%s", extra);
         if (named) {
             sprintf(tail + a, "\tpi:Z:%s\tsp:B:i,%zu,%zu", name, pieces[k].from, pieces[k].to);
             if (NULL == (pname = malloc(strlen(name) + 16))) errx(EXIT_FAILURE, "out of memory for the adapter tags of %s", name);
@@ -345,4 +349,23 @@ void fprintf_adapter_record(enum flappie_outformat_type outformat, FILE *fp, con
         free(tail); free(pseq); free(qual); free(pname);
     }
     free(atags); free(btags); free(mtags); free(seq); free(mm); free(mv);
+}
+
+void fprintf_adapter_record(enum flappie_outformat_type outformat, FILE *fp, const char *uuid, const char *readname, bool uuid_primary, const char *prefix,
+                            const struct _raw_basecall_info res, const uint8_t *ml, const uint8_t *moves, int stride, float median, float mad, bool delta,
+                            const ffhip_barcode_call *bc, const flappie_barcode_kit *bkit, bool bc_trim, const flappie_adapter_out *ad, bool reversed,
+                            unsigned long long stats[4]) {
+    if (NULL == ad) errx(EXIT_FAILURE, "no adapter record for %s", uuid_primary ? uuid : readname);
+    put_cut_record(outformat, fp, uuid, readname, uuid_primary, prefix, res, ml, moves, stride, median, mad, delta, bc, bkit, bc_trim, ad, reversed, stats, NULL);
+}
+
+/* ---- records with the poly tail tags (include/flappie_polytail.h): behind every other tag ---- */
+void fprintf_polytail_record(enum flappie_outformat_type outformat, FILE *fp, const char *uuid, const char *readname, bool uuid_primary, const char *prefix,
+                             const struct _raw_basecall_info res, const uint8_t *ml, const uint8_t *moves, int stride, float median, float mad, bool delta,
+                             const ffhip_barcode_call *bc, const flappie_barcode_kit *bkit, bool bc_trim, const flappie_adapter_out *ad, bool reversed,
+                             unsigned long long stats[4], const ffhip_polytail *pt) {
+    char *tags = flappie_polytail_tags(pt, res.rt.start);
+    if (NULL == tags) errx(EXIT_FAILURE, "no poly tail tags for %s (out of memory, or no record)", uuid_primary ? uuid : readname);
+    put_cut_record(outformat, fp, uuid, readname, uuid_primary, prefix, res, ml, moves, stride, median, mad, delta, bc, bkit, bc_trim, ad, reversed, stats, tags);
+    free(tags);
 }

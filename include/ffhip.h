@@ -135,6 +135,12 @@ typedef struct {
  * the result block: they live in a buffer of their own (reads x 256 bytes) and come down in ONE extra copy, enqueued where the result block's copy is.  Everything
  * else the run returns is that of the same run without the flag.  No kit attached, the run-length model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
 #define FFHIP_RUN_ADAPTERS   1048576u
+/* The poly(A) tail of a flip-flop model's reads (ffhip_batch_polytail below, "poly tail"): one 32-byte record a read -- where the signal stays flat while the path
+ * says the tail's base, and how many bases that is at the read's own speed -- made on the device (k_polytail) behind the decode from the Viterbi path and the signal
+ * the batch was given, with the parameters of ffhip_batch_set_polytail.  It needs no FFHIP_RUN_REMAP.  The records are NOT part of the result block: they live in a
+ * buffer of their own (reads x 32 bytes) and come down in ONE extra copy, enqueued where the result block's copy is.  Everything else the run returns is that of the
+ * same run without the flag.  No parameters set, the run-length model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
+#define FFHIP_RUN_POLYTAIL   2097152u
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -595,6 +601,52 @@ int ffhip_batch_set_remap_variants(ffhip_batch *b, int nread, const ffhip_varian
 int ffhip_batch_variant_calls(const ffhip_batch *b, int read, const ffhip_variant_call **vc, size_t *nvar);
 int ffhip_op_variants(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, const uint8_t *rm, size_t nblock,
                       const ffhip_variant *vars, size_t nvar, int context, int all_paths, ffhip_variant_call *out /* nvar */);
+/* Poly tail: how long a read's poly(A) tail is (pt:i of dorado, polya of nanopolish and tailfindr).  Over a homopolymer the signal is flat and the model sits in
+ * one state for hundreds of blocks, so the call holds a handful of As; the length is in the signal: how long it stays flat while the path says the tail's base,
+ * divided by how fast the rest of the read moves.
+ *   Inputs for one read: the prepared signal x[0 .. n), float32 -- exactly what the first convolution reads; the model's stride S; the read's N >= 1 blocks; its
+ *     Viterbi path path[0 .. N], states of the flip-flop model, and nbase.
+ *   Parameters (ffhip_polytail_params, all int32 but the last): base t, 0 .. 3; from_end 0 (the tail is searched from the signal's start) or 1 (from its end);
+ *     window K, 1 .. 64 blocks a window; min_calls, 0 .. K blocks of t a window needs; gap G, 0 .. 16 unflagged windows a tail may bridge; min_windows Wmin >= 1,
+ *     the shortest interval kept; search R >= 1, the windows searched from the chosen end; min_bases >= 1, the called bases the rate needs; max_sd >= 0, float32,
+ *     the flatness bound.
+ *   1. Block base and moves: base_b = path[b + 1] % nbase, 4 (Z) read as 1 (C); mv[b] exactly as "Move table" above has it.
+ *   2. Windows: NW = floor(min(N, floor(n / S)) / K); window w covers the samples [w K S, (w + 1) K S) and the blocks [w K, (w + 1) K).  A trailing partial
+ *     window belongs to nothing.
+ *   3. Window statistics, in fp64, two passes, each sum sequential in sample order, no fused multiply-add: a = sum x_k, mu = a / (K S), q = sum (x_k - mu)^2;
+ *     flag_w = (q <= ((double)max_sd * (double)max_sd) * (double)(K S)) and #{b in w : base_b == t} >= min_calls.  No sqrt is taken.
+ *   4. Candidates: flagged windows are merged across runs of at most G unflagged windows that lie between two flagged ones; a candidate [ws, we) is a maximal
+ *     merged run, and starts and ends on a flagged window.
+ *   5. The tail: of the candidates with we - ws >= Wmin that are in reach -- ws < R, or we > NW - R when from_end -- the longest; ties go to the smallest ws, or
+ *     the largest we when from_end.  None: status 2.
+ *   6. The record, with bs = ws K and be = we K: first = bs S; count = (be - bs) S; flat = the flagged windows in [ws, we);
+ *     calls = #{b in [bs, be) : mv[b] == 1 and base_b == t}; level = the mean of mu_w over the interval's flagged windows, in fp64 in the kernel's own order,
+ *     rounded to float32 once.
+ *   7. Rate, from the far side of the tail (the transcript).  from_end 0: c = sum of mv[b] over b >= be, so = min(N S, n) - be S; from_end 1: c = sum of mv[b]
+ *     over b < bs, so = bs S.  c < min_bases or so <= 0: status 3, the record keeps what step 6 gave and rate = bases = 0.  Otherwise status 1 with
+ *     rate = (float)((double)so / (double)c) and bases = (float)(((double)count * (double)c) / (double)so): integers in, one rounded product, one rounded
+ *     quotient, one rounding to float32.
+ *   The record, 32 bytes: { int32 status, first, count, flat, calls; float level, rate, bases }.  An empty slot of a batch is all zero (status 0); status 2 is
+ *     { 2, 0, ... }.  Every field except level is a function of the inputs alone: the same read gives the same bytes in a one-read-a-row, ragged, packed, paired,
+ *     launch-per-step or f32-rerun batch and from one run to the next.  first counts from the prepared signal's first sample (add the read's trim_start for raw
+ *     samples).
+ * ffhip_batch_set_polytail: the parameters (copied) of the batch's later runs with FFHIP_RUN_POLYTAIL; NULL detaches.  A parameter out of range, the run-length
+ *   model, or a call between a run and its finish: FFHIP_EINVAL with a text, and the batch is as it was.
+ * ffhip_batch_polytail: after ffhip_batch_finish of a run with the flag.  A run without it: FFHIP_EINVAL.
+ * ffhip_op_polytail: the kernel on ONE read from host arrays: nsample samples (0 is allowed), a path of nblock + 1 states; out: one record.
+ * ffhip_op_polytail_windows: likewise, the NW windows' mu, q and flag (0 / 1), each caller-owned with room for NW entries: what holds the order of the sums to
+ *   the bit.  Both: nblock = 0, stride < 1, nbase other than 4 or 5, a state >= 2 nbase, a parameter out of range, more than 2^30 of anything: FFHIP_EINVAL.
+ * The records' buffer (fixed), the list of reads and the windows' workspace (9 bytes a window: mu and the flag bits) are made at the front of the first run with
+ * the flag, the workspace grown when a run needs more, freed with the batch and counted by ffhip_debug_batch_device_bytes; when one cannot be had: FFHIP_ENOMEM
+ * with the bytes in the text. */
+typedef struct { int32_t base, from_end, window, min_calls, gap, min_windows, search, min_bases; float max_sd; } ffhip_polytail_params;      /* 36 bytes */
+typedef struct { int32_t status, first, count, flat, calls; float level, rate, bases; } ffhip_polytail;                                      /* 32 bytes */
+int ffhip_batch_set_polytail(ffhip_batch *b, const ffhip_polytail_params *params);
+int ffhip_batch_polytail(const ffhip_batch *b, int read, ffhip_polytail *out);
+int ffhip_op_polytail(ffhip_engine *eng, const float *signal, size_t nsample, int stride, const int *path /* nblock + 1 */, size_t nblock, int nbase,
+                      const ffhip_polytail_params *params, ffhip_polytail *out);
+int ffhip_op_polytail_windows(ffhip_engine *eng, const float *signal, size_t nsample, int stride, const int *path /* nblock + 1 */, size_t nblock, int nbase,
+                              const ffhip_polytail_params *params, double *mu /* NW */, double *q /* NW */, uint8_t *flag /* NW */);
 /* Truth: how close a call is to the sequence it should have been.
  *   Inputs: the call s of n >= 0 bases -- the batch's called letters in signal order, Z read as C (as the barcode search reads it); the truth t of m bases as codes
  *     0 .. nbase - 1, code 4 (Z) folded to 1 (C) for the comparison; the band half-width W >= 0.
