@@ -11,6 +11,14 @@
 // One workgroup per read, one lane per state, log-space chains in the reference's order of operations (libm
 // expf/log1pf/tanhf are ocml here, <= 1-2 ulp apart).  These are Tb-step dependent chains; forward and backward
 // posteriors run on two concurrent waves.
+//
+// Which of these still run: the product shape (nbase = 4, stride 40) takes the 8-state forms of ffhip_decode.hip --
+// k_rle_partition8x, k_crf_fb<8, 1> + k_rle_post8, k_viterbi8x<1> -- so of the chains here
+//   * k_rle_partition and k_rle_viterbi run for every other shape only (nbase 1, 2, 3, 5, or another stride);
+//   * k_rle_transpost runs for every other shape, ALWAYS for the C function transpost_crf_runlength (launch_rle_transpost
+//     has no 8-state form), and for a batch's posterior when 10 / temperature > kFbRange (the linear-space chains' range);
+//   * k_rle_activate, k_rle_sub and k_rle_runs run for every shape.
+// tests/test_runlength_decode_gpu.py holds both families to the oracle and to fp64.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -258,17 +266,18 @@ k_rle_transpost(const float *__restrict__ param, float *__restrict__ post, float
                 float v = 0.0f;
                 if (lane < ns) {
                     // source state (b1, stay = lane >= nbase): chain over its moves to b2 != b1 in ascending b2, then its stay exit
-                    // (decode.c:1085-1100; the first step, lse(-inf, x) = x exactly, is a copy)
+                    // (decode.c:1085-1100; the first step, lse(-inf, x), is a copy: it is x exactly for every x but -inf, where the
+                    // reference's (-inf) - (-inf) gives NaN -- a caller's matrix with a -inf score; the forward chain's `inner` is never -inf)
                     const int b1 = lane < nbase ? lane : lane - nbase, st1 = lane < nbase ? 0 : 1;
                     bool first = true;
                     for (int b2 = 0; b2 < nbase; b2++) {
                         if (b1 == b2) continue;
                         const float c = prev[b2] + S[rle_idx(b1, st1, b2, nbase)];
-                        v = first ? c : logsumexpf_ref(v, c);
+                        v = first ? (c == -HUGE_VALF ? NAN : c) : logsumexpf_ref(v, c);
                         first = false;
                     }
                     const float cs = prev[b1 + nbase] + S[rle_idx(b1, st1, b1, nbase)];
-                    v = first ? cs : logsumexpf_ref(v, cs);
+                    v = first ? (cs == -HUGE_VALF ? NAN : cs) : logsumexpf_ref(v, cs);
                 }
                 if (lane < ns) bs[cur ^ 1][lane] = v;
                 RLE_WAVE_SYNC();
@@ -689,6 +698,8 @@ void launch_rle_partition(hipStream_t s, const float *param, double *logz, int n
     else hipLaunchKernelGGL(k_rle_partition, dim3(nread), dim3(64), 0, s, param, Tb, nbase, Ps, logz, tbs);
 }
 
+// always the generic log-space kernel, nbase 4 included: the C function transpost_crf_runlength and a batch beyond kFbRange come here; a batch within it
+// goes to launch_rle_post8 (ffhip_decode.hip) from the engine and never reaches this
 void launch_rle_transpost(hipStream_t s, const float *param, float *post, float *fwd, int nread, int Tb, int nbase, int Ps, const int *tbs) {
     const int P = 2 * nbase * (nbase + 1);
     hipLaunchKernelGGL(k_rle_transpost, dim3(nread), dim3(256), 0, s, param, post, fwd, fwd + (size_t)nread * (Tb + 1) * kMaxState, Tb, nbase, P, Ps, tbs);

@@ -166,6 +166,42 @@ def crf_posterior(S, cmap):
     return np.exp(alpha[:T][:, src] + S + beta[1:][:, dst] - logz), logz
 
 
+def runlength_transpost64(S, nbase):
+    """transpost_crf_runlength's transition columns in float64, as decode.c:1102-1126 writes them: alpha[t][src] + S[t] + beta[t+1][dst], not
+    normalised, no - logZ (S [T, 2 nbase^2]: the transition columns alone).  Returns (post [T, P], alpha [T + 1, ns], beta [T + 1, ns])."""
+    src, dst, ns = runlength_map(nbase)
+    S = np.asarray(S, dtype=np.float64)
+    T = S.shape[0]
+    alpha = np.zeros((T + 1, ns))
+    for t in range(T):
+        alpha[t + 1] = _lse_into(alpha[t][src] + S[t], dst, ns)
+    beta = np.zeros((T + 1, ns))
+    for t in range(T, 0, -1):
+        beta[t - 1] = _lse_into(S[t - 1] + beta[t][dst], src, ns)
+    return alpha[:T][:, src] + S + beta[1:][:, dst], alpha, beta
+
+
+def runlength_best_path(S, nbase):
+    """plain float64 Viterbi over the run-length states, every state starting at 0 (decode_crf_runlength, decode.c:927-1013): (score, path [T]).
+    np.argmax takes the first maximum, which is NOT the reference's order among equal scores: for scores without ties only."""
+    src, dst, ns = runlength_map(nbase)
+    S = np.asarray(S, dtype=np.float64)
+    T = S.shape[0]
+    v = np.zeros(ns)
+    back = np.zeros((T, ns), dtype=np.int64)
+    for t in range(T):
+        cand = np.full((ns, ns), -np.inf)                     # [dst][src]
+        cand[dst, src] = v[src] + S[t]
+        back[t] = cand.argmax(axis=1)
+        v = cand.max(axis=1)
+    path = np.zeros(T, dtype=np.int64)
+    last = int(v.argmax())
+    for t in range(T - 1, -1, -1):
+        path[t] = last
+        last = back[t, last]
+    return float(v.max()), path
+
+
 # ---- heads ---------------------------------------------------------------------------------------------------------------
 def head_terms(h, W, b):
     """h [T, H]; W [P, H]; b [P] -> (z, cond): float64 W h + b and sum |W h| + |b|"""

@@ -94,3 +94,48 @@ def test_posterior_matches_autograd_and_oracle(nbase, T):
     np.testing.assert_allclose(post.sum(axis=1), 1.0, rtol=0, atol=1e-12)
     got = ffo.take(ffo.lib().fo_transpost(omat(s).ptr, 0))           # the oracle's fp32 log-space chains
     np.testing.assert_allclose(got, post, rtol=0, atol=1e-4)
+
+
+def _enumerate_runlength(param, nbase):
+    """tests/test_runlength.py's enumeration over every state path (free start state, cost 0), kept per transition: the log-sum of exp(path score)
+    over the paths that take transition p in block t -- what alpha[t][src] + S[t] + beta[t+1][dst] is"""
+    import itertools
+    from test_runlength import allowed, rle_idx
+    T, ns = param.shape[0], 2 * nbase
+    S = param[:, ns:].astype(np.float64)
+    post = np.full(S.shape, -np.inf)
+    for start in range(ns):
+        for path in itertools.product(range(ns), repeat=T):
+            prev, sc, used = start, 0.0, []
+            for t, cur in enumerate(path):
+                if not allowed(prev, cur, nbase):
+                    break
+                p = rle_idx(prev % nbase, prev >= nbase, cur % nbase, nbase)
+                sc += S[t, p]
+                used.append(p)
+                prev = cur
+            else:
+                for t, p in enumerate(used):
+                    post[t, p] = np.logaddexp(post[t, p], sc)
+    return post
+
+
+@pytest.mark.parametrize("nbase,T", [(2, 1), (2, 2), (2, 5), (3, 1), (3, 3), (3, 5)])
+def test_runlength_helpers_against_enumeration(nbase, T):
+    """runlength_transpost64, runlength_best_path and crf_logz(., runlength_map) against the enumeration over all state paths: 1e-12 relative"""
+    from test_runlength import brute_force, random_param
+    param = random_param(np.random.default_rng(10 * nbase + T), T, nbase, scale=2.0)
+    S = param[:, 2 * nbase:].astype(np.float64)
+    logz, best, best_path = brute_force(param, nbase)
+
+    def close(got, want):
+        return np.all(np.abs(got - want) <= 1e-12 * np.maximum(1.0, np.abs(want)))
+    assert close(R.crf_logz(S, R.runlength_map(nbase)), logz)
+    post, alpha, beta = R.runlength_transpost64(S, nbase)
+    assert post.shape == S.shape and alpha.shape == beta.shape == (T + 1, 2 * nbase)
+    assert close(post, _enumerate_runlength(param, nbase))
+    # the chains' ends: every state starts and ends at log 1; alpha's last and beta's first vector both sum to Z
+    assert not alpha[0].any() and not beta[T].any()
+    assert close(np.logaddexp.reduce(alpha[T]), logz) and close(np.logaddexp.reduce(beta[0]), logz)
+    score, path = R.runlength_best_path(S, nbase)
+    assert close(score, best) and tuple(path) == best_path
