@@ -34,6 +34,10 @@ RUN_MOVES = 8192          # flip-flop model: the move table (one byte a block, 1
 RUN_ADAPTERS = 1048576   # flip-flop model: one adapter record a read (a header and up to 15 hits) made on the device against the kit of Batch.set_adapters (Batch.adapters)
 ADAPTER_SEGMENT = 512    # FFHIP_ADAPTER_SEGMENT (include/ffhip.h "adapters"): the columns one wave of k_adapters owns; checked against the library at load
 ADAPTER_MAX_HITS = 15
+RUN_MAP = 4194304        # flip-flop model: one map record a read (status, strand and record, span, either anchor's place) made on the device against the reference of Batch.set_map (Batch.map)
+MAP_SEGMENT = 2048       # FFHIP_MAP_SEGMENT (include/ffhip.h "map"): the columns one task of k_map_scan owns; checked against the library at load
+MAP_MAX_TOTAL = 1 << 20
+MAP_MAX_ANCHOR = 4096
 RUN_POLYTAIL = 2097152    # flip-flop model: one poly tail record a read made on the device from the Viterbi path and the signal with the parameters of Batch.set_polytail (Batch.polytail)
 POLYTAIL_DTYPE = np.dtype([("status", np.int32), ("first", np.int32), ("count", np.int32), ("flat", np.int32), ("calls", np.int32),
                            ("level", np.float32), ("rate", np.float32), ("bases", np.float32)])      # ffhip_polytail (include/ffhip.h)
@@ -114,6 +118,24 @@ def _polytail_params(params: dict) -> CPolyTailParams:
         p["min_calls"] = (int(params["window"]) + 1) // 2
     p.update(params)
     return CPolyTailParams(*[int(p[k]) for k in list(POLYTAIL_DEFAULTS)[:8]], float(p["max_sd"]))
+
+
+class CMapCall(C.Structure):
+    """ffhip_map_call (include/ffhip.h): 64 bytes, sixteen int32"""
+    _fields_ = [("v", C.c_int32 * 16)]
+
+
+MAP_FIELDS = ("status", "n", "nanchor", "q", "tstart", "tend")
+MAP_ANCHOR_FIELDS = ("q", "start", "end", "dist", "second")
+
+
+def _map_record(rec) -> dict:
+    """a map record as a dict: MAP_FIELDS, "anchors": two dicts of MAP_ANCHOR_FIELDS, "raw": the sixteen int32"""
+    v = [int(x) for x in rec.v]
+    out = dict(zip(MAP_FIELDS, v[:6]))
+    out["anchors"] = [dict(zip(MAP_ANCHOR_FIELDS, v[6 + 5 * a:11 + 5 * a])) for a in range(2)]
+    out["raw"] = np.array(v, np.int32)
+    return out
 
 
 class CAdapterHeader(C.Structure):
@@ -272,6 +294,17 @@ def lib():
     L.ffhip_adapter_segment.restype = C.c_int
     L.ffhip_adapter_segment.argtypes = []
     assert L.ffhip_adapter_segment() == ADAPTER_SEGMENT, "binding.py and libffhip.so disagree on FFHIP_ADAPTER_SEGMENT"
+    L.ffhip_map_ref_upload.restype = vp
+    L.ffhip_map_ref_upload.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p)]
+    L.ffhip_map_ref_free.restype = None
+    L.ffhip_map_ref_free.argtypes = [vp]
+    L.ffhip_batch_set_map.argtypes = [vp, vp, C.c_int, C.c_int]
+    L.ffhip_batch_map.argtypes = [vp, C.c_int, C.POINTER(CMapCall)]
+    L.ffhip_op_map_scores.argtypes = [vp, vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
+    L.ffhip_op_map.argtypes = [vp, vp, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(CMapCall)]
+    L.ffhip_map_segment.restype = C.c_int
+    L.ffhip_map_segment.argtypes = []
+    assert L.ffhip_map_segment() == MAP_SEGMENT, "binding.py and libffhip.so disagree on FFHIP_MAP_SEGMENT"
     L.ffhip_batch_set_polytail.argtypes = [vp, C.POINTER(CPolyTailParams)]
     L.ffhip_batch_polytail.argtypes = [vp, C.c_int, vp]
     L.ffhip_op_polytail.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_int), C.c_size_t, C.c_int, C.POINTER(CPolyTailParams), vp]
@@ -518,6 +551,25 @@ class Adapters:
             self.h = None
 
 
+class MapRef:
+    """A reference on the device (ffhip_map_ref): `seqs` are 1 .. 1024 records over ACGT of 1 or more bases, at most 2^20 together, each searched on both strands."""
+
+    def __init__(self, engine: Engine, seqs):
+        self.engine = engine
+        self.seqs = [x if isinstance(x, bytes) else str(x).encode() for x in seqs]
+        self.n = len(self.seqs)
+        self.lens = [len(x) for x in self.seqs]
+        arr = (C.c_char_p * max(1, self.n))(*self.seqs)
+        self.h = lib().ffhip_map_ref_upload(engine.h, self.n, arr)
+        if not self.h:
+            raise FFHipError(lib().ffhip_last_error().decode())
+
+    def close(self):
+        if self.h:
+            lib().ffhip_map_ref_free(self.h)
+            self.h = None
+
+
 def _adapter_record(header, hits) -> dict:
     """a header and its hit slots as a dict: nhit, len, kept, hits = kept tuples (start, end, pattern, orientation, dist)"""
     kept = int(header.kept)
@@ -675,6 +727,16 @@ class Batch:
     def set_adapters(self, kit, max_dist: int = -1):
         """the kit and bound of later runs with RUN_ADAPTERS (ffhip_batch_set_adapters); max_dist < 0: floor(L / 4) of each pattern; kit None detaches"""
         _check(lib().ffhip_batch_set_adapters(self.h, kit.h if kit is not None else None, int(max_dist)))
+
+    def set_map(self, ref, window: int = -1, max_error: int = -1):
+        """the reference, window and bound (per mille) of later runs with RUN_MAP (ffhip_batch_set_map); negative: the defaults 4096 and 250; ref None detaches"""
+        _check(lib().ffhip_batch_set_map(self.h, ref.h if ref is not None else None, int(window), int(max_error)))
+
+    def map(self, read: int) -> dict:
+        """map record of a run with RUN_MAP (ffhip_batch_map): status, n, nanchor, q, tstart, tend, anchors = two dicts (q, start, end, dist, second), raw"""
+        rec = CMapCall()
+        _check(lib().ffhip_batch_map(self.h, read, C.byref(rec)))
+        return _map_record(rec)
 
     def adapters(self, read: int) -> dict:
         """adapter record of a run with RUN_ADAPTERS (ffhip_batch_adapters): nhit, len, kept, hits = kept tuples (start, end, pattern, orientation, dist) by (end, q)"""
@@ -956,6 +1018,27 @@ def op_adapter_hits(engine: Engine, kit: Adapters, bases, max_dist: int = -1) ->
     rec = _adapter_record(h, hits)
     rec["raw"] = np.frombuffer(bytes(hits), np.int32).copy()
     return rec
+
+
+def op_map_scores(engine: Engine, ref: MapRef, pattern) -> list:
+    """ffhip_op_map_scores: the whole score rows of ONE anchor (a str over ACGTZ of 1 .. 4096 letters): a list of 2 K int32 arrays, row q = 2 k + strand of m_k + 1 entries"""
+    b = pattern if isinstance(pattern, bytes) else str(pattern).encode()
+    d = np.zeros(2 * sum(m + 1 for m in ref.lens), np.int32)
+    _check(lib().ffhip_op_map_scores(engine.h, ref.h, b, len(b), d.ctypes.data_as(C.POINTER(C.c_int32))))
+    rows, at = [], 0
+    for m in ref.lens:
+        for _ in range(2):
+            rows.append(d[at:at + m + 1])
+            at += m + 1
+    return rows
+
+
+def op_map(engine: Engine, ref: MapRef, bases, window: int = -1, max_error: int = -1) -> dict:
+    """ffhip_op_map: the record of ONE call (a str over ACGTZ, may be empty), as Batch.map gives it"""
+    b = bases if isinstance(bases, bytes) else str(bases).encode()
+    rec = CMapCall()
+    _check(lib().ffhip_op_map(engine.h, ref.h, int(window), int(max_error), b, len(b), C.byref(rec)))
+    return _map_record(rec)
 
 
 def op_remap(engine: Engine, trans: np.ndarray, nbase: int, codes, band: int = 2048) -> tuple:

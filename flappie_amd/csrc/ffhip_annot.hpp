@@ -1,5 +1,5 @@
 // ffhip_annot.hpp -- the per-read products of a batch that live OUTSIDE its result block, described once (host only, no kernels; included by ffhip_engine.hip).
-// Barcodes, adapters, truth, remap, events, site mods and variants each bring their records to the host in a buffer and a copy of their own.  Such a buffer is a
+// Barcodes, adapters, the map, the poly tail, truth, remap, events, site mods and variants each bring their records to the host in a buffer and a copy of their own.  Such a buffer is a
 // Mirrored (below), a feature is a struct of its own in ffhip_batch that starts as an Annot, and kAnnots (ffhip_engine.hip, behind the features' functions) has one
 // row a feature, in launch order.  To add a per-read product outside the block one writes
 //   its struct        struct Thing : Annot { <parameters, lists, workspaces, per-read offsets> } thing;      (ffhip_batch, and its place in ffhip_batch::annot)

@@ -764,6 +764,9 @@ struct ffhip_batch {
     struct Barcodes : Annot { const ffhip_barcodes *kit = nullptr; int max_dist = 0, min_sep = 3, both = 0; } bc;
     // Adapter records (FFHIP_RUN_ADAPTERS, k_adapters): 256 bytes a read, cap_reads of them
     struct Adapters : Annot { const ffhip_adapters *kit = nullptr; int max_dist = -1; } ad;
+    // Map records (FFHIP_RUN_MAP, k_map_scan and k_map_finish): 64 bytes a read, cap_reads of them; the tasks' slots (8 bytes a task of either anchor of every read),
+    // taken by the front of the first run that asks
+    struct Map : Annot { const ffhip_map_ref *ref = nullptr; int window = kMapMaxAnchor, max_error = 250; void *ws = nullptr; size_t ws_cap = 0; } map;
     // Poly tail records (FFHIP_RUN_POLYTAIL, k_polytail): 32 bytes a read, cap_reads of them; the reads' list, written by the front of every run that asks; the
     // windows' workspace (a double and a byte a window of every read, `windows` of them in this run), grown when a run needs more
     struct PolyTail : Annot { ffhip_polytail_params p{}; bool set = false; uint8_t *ws = nullptr; size_t ws_cap = 0, windows = 0; } pt;
@@ -800,8 +803,8 @@ struct ffhip_batch {
     } evt;
     struct Sites : PerBase { int *start = nullptr; size_t start_cap = 0; int context, all = 0; explicit Sites(int c) : context(c) {} } smd{ 15 };
     struct Variants : Sites { std::vector<std::vector<ffhip_variant>> set; Variants() : Sites(10) {} } var;
-    enum { AN_COUNT = 8 };
-    Annot &annot(int i) { Annot *const a[AN_COUNT] = { &bc, &ad, &pt, &tru, &rmp, &evt, &smd, &var }; return *a[i]; }       // (the order of kAnnots: launch order)
+    enum { AN_COUNT = 9 };
+    Annot &annot(int i) { Annot *const a[AN_COUNT] = { &bc, &ad, &map, &pt, &tru, &rmp, &evt, &smd, &var }; return *a[i]; }       // (the order of kAnnots: launch order)
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
     std::vector<void *> owned;
     unsigned last_flags = 0;
@@ -1537,6 +1540,23 @@ static void adapters_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {     
 static size_t adapters_bytes(const ffhip_batch *b) { return (size_t)batch_nreads(b) * kAdapterRecBytes; }
 static void adapters_spans(const ffhip_batch *, int r, AnnotSpan out[2]) { span1(out, (size_t)r * kAdapterRecBytes, kAdapterRecBytes); }
 
+static_assert(sizeof(ffhip_map_call) == kMapRecBytes && FFHIP_MAP_SEGMENT == kMapSeg && FFHIP_MAP_MAX_TOTAL == kMapMaxTotal && FFHIP_MAP_MAX_ANCHOR == kMapMaxAnchor,
+              "k_map_finish writes a record as four 16-byte stores");
+static int map_prepare(ffhip_batch *b) {
+    ffhip_batch::Map &f = b->map;
+    if (!f.ref) return set_err(FFHIP_EINVAL, "map: no reference is attached to the batch (ffhip_batch_set_map)");
+    if (int rc = f.rec.fixed(b, (size_t)b->cap_reads * kMapRecBytes, "map: the reads' records")) return rc;
+    return dgrow(b, &f.ws, &f.ws_cap, (size_t)b->cap_reads * 2 * (size_t)f.ref->view.ntask * 8, "map: the tasks' slots");
+}
+static void map_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {        // from the strings and lengths, as barcodes and adapters
+    ffhip_batch::Map &f = b->map;
+    launch_map(b->stream, f.ref->view, b->bases(), b->lens(), f.rec.dev, batch_nreads(b), b->Tb, tbr, rmap, f.window, f.max_error, f.ws);
+    b->launches[5] += 2;
+    f.valid = 1;
+}
+static size_t map_bytes(const ffhip_batch *b) { return (size_t)batch_nreads(b) * kMapRecBytes; }
+static void map_spans(const ffhip_batch *, int r, AnnotSpan out[2]) { span1(out, (size_t)r * kMapRecBytes, kMapRecBytes); }
+
 // Poly tail, the front's share: every read's samples (the addresses events_prepare gives) and its first window in the workspace, which grows here
 static_assert(sizeof(ffhip_polytail) == kPolyTailRecBytes && sizeof(ffhip_polytail_params) == sizeof(PolyTailParams) && sizeof(PolyRead) == 24,
               "k_polytail writes a record as two 16-byte stores; the parameters and the reads' list are copied as they stand");
@@ -1803,6 +1823,8 @@ constexpr AnnotRow kAnnots[ffhip_batch::AN_COUNT] = {
       barcodes_prepare, barcodes_launch, barcodes_bytes, barcodes_spans },
     { FFHIP_RUN_ADAPTERS, nullptr, 0, "adapters: a flip-flop model only (the run-length model has no base strings)", "adapters need a decoded run (FFHIP_RUN_NO_DECODE is set)",
       adapters_prepare, adapters_launch, adapters_bytes, adapters_spans },
+    { FFHIP_RUN_MAP, nullptr, 0, "map: a flip-flop model only (the run-length model has no base strings)", "map needs a decoded run (FFHIP_RUN_NO_DECODE is set)",
+      map_prepare, map_launch, map_bytes, map_spans },
     { FFHIP_RUN_POLYTAIL, nullptr, 0, "poly tail: a flip-flop model only (the run-length model's path is not one of bases)", "poly tail needs a decoded run (FFHIP_RUN_NO_DECODE is set)",
       polytail_prepare, polytail_launch, polytail_bytes, polytail_spans },
     { FFHIP_RUN_TRUTH, nullptr, 0, "truth: a flip-flop model only (the run-length model's call is a list of runs)", "truth needs a decoded run (FFHIP_RUN_NO_DECODE is set)",
@@ -2312,6 +2334,7 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
         sd->run_scale = b->run_scale;
         sd->bc.kit = b->bc.kit; sd->bc.max_dist = b->bc.max_dist; sd->bc.min_sep = b->bc.min_sep; sd->bc.both = b->bc.both;      // (last_flags asks the side batch for the records too)
         sd->ad.kit = b->ad.kit; sd->ad.max_dist = b->ad.max_dist;
+        sd->map.ref = b->map.ref; sd->map.window = b->map.window; sd->map.max_error = b->map.max_error;
         sd->pt.p = b->pt.p; sd->pt.set = b->pt.set;
         if (fl & FFHIP_RUN_REMAP) {                       // ... and for these reads' sequences
             std::vector<std::vector<unsigned short>> sq(16);
@@ -2592,6 +2615,74 @@ extern "C" int ffhip_batch_adapters(const ffhip_batch *b, int read, ffhip_adapte
     const uint8_t *rec = b->ad.rec.host + (size_t)read * kAdapterRecBytes;
     memcpy(header, rec, sizeof *header);
     *hits = (const ffhip_adapter_hit *)(rec + sizeof *header);
+    return FFHIP_OK;
+}
+
+// ---- map (include/ffhip.h "map"; the kernels: ffhip_map.hip)
+extern "C" int ffhip_map_segment(void) { return kMapSeg; }
+extern "C" ffhip_map_ref *ffhip_map_ref_upload(ffhip_engine *eng, int n, const char *const *seq) {
+    if (!eng || !seq) { set_err(FFHIP_EINVAL, "null engine or reference"); return nullptr; }
+    if (n < 1 || n > kMapMaxRecords) { set_err(FFHIP_EINVAL, "a reference holds 1 .. %d records, not %d", kMapMaxRecords, n); return nullptr; }
+    std::vector<int2> recs(n);
+    std::vector<int> rowoff((size_t)2 * n);
+    std::vector<MapTask> tasks;
+    size_t total = 0, entries = 0;
+    for (int k = 0; k < n; k++) {
+        const size_t m = seq[k] ? strnlen(seq[k], (size_t)kMapMaxTotal + 1) : 0;
+        if (m < 1) { set_err(FFHIP_EINVAL, "reference record %d: position 0: a record has 1 or more bases", k); return nullptr; }
+        if (total + m > (size_t)kMapMaxTotal) {
+            set_err(FFHIP_EINVAL, "reference record %d: position %zu: the records hold at most %d bases together", k, (size_t)kMapMaxTotal - total, kMapMaxTotal);
+            return nullptr;
+        }
+        recs[k] = make_int2((int)total, (int)m);
+        total += m;
+        for (int o = 0; o < 2; o++) {
+            rowoff[2 * k + o] = (int)entries;
+            entries += m + 1;
+            for (size_t s = 0; s < m; s += kMapSeg) tasks.push_back(MapTask{ 2 * k + o, (int)s, (int)std::min(m, s + kMapSeg), 0 });
+        }
+    }
+    std::vector<unsigned> words((total + 2 * kMapPad + 15) / 16 + 2, 0u);
+    for (int k = 0; k < n; k++)
+        for (int i = 0; i < recs[k].y; i++) {
+            const char *at = strchr("ACGT", seq[k][i]);
+            if (!at) { set_err(FFHIP_EINVAL, "reference record %d: position %d: the character is not one of ACGT", k, i); return nullptr; }
+            const size_t g = (size_t)kMapPad + recs[k].x + i;
+            words[g >> 4] |= (unsigned)(at - "ACGT") << (2 * (g & 15));
+        }
+    hipSetDevice(eng->device);
+    ffhip_map_ref *ref = new ffhip_map_ref();
+    ref->eng = eng;
+    ref->score_entries = entries;
+    const struct { void **dev; const void *host; size_t bytes; } up[4] = { { &ref->d_words, words.data(), words.size() * 4 }, { &ref->d_tasks, tasks.data(), tasks.size() * sizeof(MapTask) },
+                                                                          { &ref->d_recs, recs.data(), recs.size() * sizeof(int2) }, { &ref->d_rowoff, rowoff.data(), rowoff.size() * 4 } };
+    for (const auto &u : up) {
+        if (hipMalloc(u.dev, u.bytes) != hipSuccess) { *u.dev = nullptr; set_err(FFHIP_ENOMEM, "device allocation failed"); ffhip_map_ref_free(ref); return nullptr; }
+        if (hipMemcpy(*u.dev, u.host, u.bytes, hipMemcpyHostToDevice) != hipSuccess) { set_err(FFHIP_EHIP, "upload of the reference failed"); ffhip_map_ref_free(ref); return nullptr; }
+    }
+    ref->view = MapRefView{ (const unsigned *)ref->d_words, (const MapTask *)ref->d_tasks, (const int2 *)ref->d_recs, (const int *)ref->d_rowoff, (int)tasks.size(), n };
+    return ref;
+}
+extern "C" void ffhip_map_ref_free(ffhip_map_ref *ref) {
+    if (!ref) return;
+    hipSetDevice(ref->eng->device);
+    for (void *p : { ref->d_words, ref->d_tasks, ref->d_recs, ref->d_rowoff }) if (p) hipFree(p);
+    delete ref;
+}
+extern "C" int ffhip_batch_set_map(ffhip_batch *b, const ffhip_map_ref *ref, int window, int max_error) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (!ref) { b->map.ref = nullptr; return FFHIP_OK; }
+    if (ref->eng != b->eng) return set_err(FFHIP_EINVAL, "the reference belongs to another engine");
+    if (const char *why = map_invalid(window, max_error)) return set_err(FFHIP_EINVAL, "map: %s", why);
+    b->map.ref = ref;
+    b->map.window = window < 0 ? kMapMaxAnchor : window;
+    b->map.max_error = max_error < 0 ? 250 : max_error;
+    return FFHIP_OK;
+}
+extern "C" int ffhip_batch_map(const ffhip_batch *b, int read, ffhip_map_call *out) {
+    if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
+    if (!b->map.valid || !b->map.rec.host) return set_err(FFHIP_EINVAL, "map records were not made in this run (FFHIP_RUN_MAP)");
+    memcpy(out, b->map.rec.host + (size_t)read * kMapRecBytes, sizeof *out);
     return FFHIP_OK;
 }
 

@@ -64,6 +64,14 @@ struct ffhip_adapters {
     void *d_peq = nullptr, *d_len = nullptr;
 };
 
+// a reference on the device (ffhip_map_ref_upload; the kernels' view of it is MapRefView): the coded letters, the records' table, the task list, the score rows' starts
+struct ffhip_map_ref {
+    ffhip_engine *eng = nullptr;
+    ffhip::MapRefView view{};
+    void *d_words = nullptr, *d_tasks = nullptr, *d_recs = nullptr, *d_rowoff = nullptr;
+    size_t score_entries = 0;           // of all 2 K score rows together: the sum of m_k + 1, twice
+};
+
 namespace ffhip {
 
 int set_err(int code, const char *fmt, ...);        // records the thread's last error text, returns `code`

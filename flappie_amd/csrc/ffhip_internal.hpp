@@ -239,6 +239,22 @@ struct AdapterKit {
 };
 void launch_adapters(hipStream_t s, AdapterKit kit, const char *bases, const int *lens, void *records, int nread, int Tb, const int *tbs, ReadMap map,
                      int max_dist, uint8_t *d_out = nullptr);
+// every call placed on a small reference (k_map_scan, k_map_finish, ffhip_map.hip; include/ffhip.h "map"): one 64-byte record a read (ffhip_map_call) from the base
+// strings and their lengths.  `slots`: 2 nread ntask pairs of int32, the tasks' best (d, j); d_out, when given, takes the whole score rows of read 0's front anchor
+// (a launch of one read)
+constexpr int kMapMaxRecords = 1024, kMapMaxTotal = 1 << 20, kMapMaxAnchor = 4096, kMapSeg = 2048, kMapPad = 16, kMapWavesY = 128;
+constexpr size_t kMapRecBytes = 64;
+struct MapTask { int q, s, e, pad; };   // search q = 2 k + o, the ends (s, e] of record k's strand o (and 0, if s = 0)
+struct MapRefView {
+    const unsigned *words;              // the records' letters one behind the other, 2 bits a letter, 16 a word, kMapPad letters of padding before and behind
+    const MapTask *tasks;               // [ntask], by (q, s)
+    const int2 *recs;                   // [nrec]: { the record's first letter, its letters }
+    const int *rowoff;                  // [2 nrec]: where search q's score row starts in d_out
+    int ntask, nrec;
+};
+const char *map_invalid(int window, int max_error);      // nullptr, or what is wrong with the parameters (negative: the default)
+void launch_map(hipStream_t s, const MapRefView &ref, const char *bases, const int *lens, void *records, int nread, int Tb, const int *tbs, ReadMap map, int window,
+                int max_error, void *slots, int *d_out = nullptr);
 // signal-to-sequence mapping (k_remap, ffhip_remap.hip; include/ffhip.h "remap"): per listed read one 16-byte record { status, L, score bits, end } at rec[read] and,
 // for a mapped one, N bytes of 0 / 1 at the read's row of the (Tb + 1)-entry byte buffer `rm`.  A form is one instantiation of the kernel (0, 1: one wave; 2, 3: a
 // workgroup): remap_form gives the smallest that holds a window of min(2 band + 1, L) cells, -1 when none does; a launch takes the reads of ONE form.

@@ -701,6 +701,36 @@ extern "C" int ffhip_op_adapter_hits(ffhip_engine *eng, const ffhip_adapters *ki
     return op_adapters(eng, kit, max_dist < 0 ? -1 : (max_dist > kAdapterMaxLen - 1 ? kAdapterMaxLen - 1 : max_dist), bases, len, nullptr, header, hits);
 }
 
+// the kernels of the map on one call (k_map_scan, k_map_finish; include/ffhip.h "map"): the whole score rows of its front anchor, or the call's record
+static int op_map(ffhip_engine *eng, const ffhip_map_ref *ref, int window, int max_error, const char *bases, size_t len, int32_t *d, ffhip_map_call *out) {
+    OP_ENTER(eng);
+    if (!ref || ref->eng != eng || (!bases && len) || len > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "bad map arguments (a reference of this engine, a call of len characters, the output)");
+    if (const char *why = map_invalid(window, max_error)) return set_err(FFHIP_EINVAL, "map: %s", why);
+    for (size_t i = 0; i < len; i++) if (!bases[i] || !strchr("ACGTZ", bases[i])) return set_err(FFHIP_EINVAL, "map: character %zu of the call is not one of ACGTZ", i);
+    const int ilen = (int)len;
+    const size_t dbytes = d ? ref->score_entries * 4 : 0;
+    char *d_bases = (char *)(len ? tmp.upload(bases, len, s) : tmp.get(4));
+    int *d_len = (int *)tmp.upload(&ilen, 4, s);
+    int *d_d = d ? (int *)tmp.get(dbytes) : nullptr;
+    void *d_slots = tmp.get((size_t)2 * ref->view.ntask * 8);
+    uint8_t *d_rec = (uint8_t *)tmp.get(kMapRecBytes);
+    if (!d_bases || !d_len || (d && !d_d) || !d_slots || !d_rec) OP_NOMEM();
+    launch_map(s, ref->view, d_bases, d_len, d_rec, 1, ilen > 0 ? ilen : 1, nullptr, ReadMap(), window < 0 ? kMapMaxAnchor : window, max_error < 0 ? 250 : max_error, d_slots, d_d);
+    if (d) HIP_TRY(hipMemcpyAsync(d, d_d, dbytes, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    if (out) HIP_TRY(hipMemcpyAsync(out, d_rec, kMapRecBytes, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+extern "C" int ffhip_op_map_scores(ffhip_engine *eng, const ffhip_map_ref *ref, const char *pattern, size_t len, int32_t *d) {
+    if (!d) return set_err(FFHIP_EINVAL, "map scores: an output of twice the sum of m_k + 1 entries");
+    if (len < 1 || len > (size_t)kMapMaxAnchor) return set_err(FFHIP_EINVAL, "map scores: an anchor has 1 .. %d letters, not %zu", kMapMaxAnchor, len);
+    return op_map(eng, ref, kMapMaxAnchor, -1, pattern, len, d, nullptr);
+}
+extern "C" int ffhip_op_map(ffhip_engine *eng, const ffhip_map_ref *ref, int window, int max_error, const char *bases, size_t len, ffhip_map_call *out) {
+    if (!out) return set_err(FFHIP_EINVAL, "map: a record to fill");
+    return op_map(eng, ref, window, max_error, bases, len, nullptr, out);
+}
+
 // one matrix of transition scores mapped to one sequence (k_remap; include/ffhip.h "remap")
 extern "C" int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, int band, uint8_t *rm, float *score) {
     OP_ENTER(eng);

@@ -43,6 +43,7 @@
 #include "../../include/flappie_moves.h"
 #include "../../include/flappie_barcodes.h"
 #include "../../include/flappie_adapters.h"
+#include "../../include/flappie_map.h"
 #include "../../include/flappie_polytail.h"
 #include "../../include/flappie_remap.h"
 #include "../../include/flappie_truth.h"
@@ -129,8 +130,18 @@ static struct argp_option options[] = {
     {"truth", 258, "refs.fa", 0, "Score each read's call against the sequence it should have been: the records of a FASTA file, found as for --remap (the same file may serve both), in SIGNAL order. The whole call is aligned to its record on the GPU (banded global edit distance) and the result written to --truth-out; stdout does not change. The alignment is always of the whole call in signal order: --reverse and --trim-barcodes do not alter it"},
     {"truth-out", 259, "acc.tsv", 0, "With --truth (required): one line per read that had a record: name, status (1 aligned, 2 not: an empty record, a letter outside the model's alphabet, or a band that leaves no path), n, m, band, maxdev, dist, matches, mismatches, insertions, deletions, identity and the extended CIGAR (=XID)"},
     {"truth-band", 260, "W", 0, "With --truth: the band's half-width in called bases around the straight line from (0, 0) to (m, n) (0-1279, default 512: the GPU holds a window of at most 2 W + 1 <= 2560 cells; maxdev = W in acc.tsv says the band was touched)"},
+    {"map", 285, "ref.fa", 0, "Place every read's call on a small reference (the lambda control, a plasmid, a mitochondrion, a virus, an amplicon panel): the records of a FASTA file (1-1024 records over ACGT, at most 1048576 bases together; lower case is upper-cased, N and IUPAC letters are refused). The first and the last --map-window bases of the call are searched on both strands of every record on the GPU (infix edit distance) and the result written to --map-out; stdout does not change. The whole call is mapped in signal order: --reverse, --trim-barcodes, --trim-adapters and --split-reads do not alter it"},
+    {"map-out", 286, "hits.tsv", 0, "With --map (required): one line per read, no header: name, status (0 no call, 1 mapped, 2 unmapped, 3 discordant), n, anchors, record, strand, tstart, tend (forward strand), the record's length, and distance and runner-up of the front and the rear anchor; for status 2 and 3 record, strand, start and end of either anchor behind them"},
+    {"map-window", 287, "W", 0, "With --map: bases of an anchor (64-4096, default 4096); a call of more has two, its first and its last W bases"},
+    {"map-max-error", 288, "permille", 0, "With --map: largest edit distance of an anchor, and largest difference between the span on the reference and the call's length, in thousandths of their lengths (0-500, default 250)"},
+    {"map-records", 289, "recs.fa", 0, "With --map: for every mapped read a FASTA record of its own stretch of the reference in signal order (reverse-complemented for the - strand): the file --truth and --remap take in a second run"},
 #endif
 #ifdef BUILD_RUNNIE
+    {"map", 285, "ref.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-out", 286, "hits.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-window", 287, "W", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-max-error", 288, "permille", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-records", 289, "recs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"barcodes", 25, "kit.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"adapters", 269, "kit.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"adapter-max-dist", 270, "edits", OPTION_HIDDEN, "(flappie's option: refused here)"},
@@ -210,6 +221,15 @@ static char *mods_path = NULL;
 #ifndef BUILD_RUNNIE
 static int mods_context = 15;
 static bool mods_context_set = false, mods_all_paths = false;
+#endif
+
+/* flappie: --map reference file, --map-out table, --map-records file, --map-window and --map-max-error (-1: the defaults) (runnie: seen, to be refused);
+ * map_opts: one of the options that go with --map was given */
+static char *map_path = NULL, *map_out_path = NULL, *map_recs_path = NULL;
+static bool map_opts = false;
+static int map_window = -1;
+#ifndef BUILD_RUNNIE
+static int map_max_error = -1;
 #endif
 
 /* flappie: --adapters kit file, --adapter-max-dist (-1: the default), --trim-adapters, --adapter-window, --split-reads, --split-min-length (runnie: seen, to be
@@ -370,9 +390,27 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
         break;
     }
 #endif
+    case 285: map_path = arg; break;
+    case 286: map_out_path = arg; map_opts = true; break;
+    case 289: map_recs_path = arg; map_opts = true; break;
 #ifdef BUILD_RUNNIE
+    case 287: case 288: map_opts = true; break;
     case 270: case 271: case 272: case 273: case 274: ad_opts = true; break;
 #else
+    case 287: {
+        char *end = NULL;
+        const long v = strtol(arg, &end, 10);
+        if (end == arg || *end != '\0' || v < 64 || v > FFHIP_MAP_MAX_ANCHOR) errx(EXIT_FAILURE, "--map-window must be a whole number from 64 to %d", FFHIP_MAP_MAX_ANCHOR);
+        map_window = (int)v; map_opts = true;
+        break;
+    }
+    case 288: {
+        char *end = NULL;
+        const long v = strtol(arg, &end, 10);
+        if (end == arg || *end != '\0' || v < 0 || v > 500) errx(EXIT_FAILURE, "--map-max-error must be a whole number from 0 to 500");
+        map_max_error = (int)v; map_opts = true;
+        break;
+    }
     case 270: {
         char *end = NULL;
         const long v = strtol(arg, &end, 10);
@@ -593,6 +631,8 @@ typedef struct {
     ffhip_adapter_header ad_head;       /* --adapters: the read's record */
     ffhip_adapter_hit ad_hits[FFHIP_ADAPTER_MAX_HITS];
     int have_ad;
+    ffhip_map_call mp;                  /* --map: the read's record */
+    int have_mp;
     ffhip_polytail pt;                  /* --poly-tail: the read's record */
     int have_pt;
     int rm_ref;                         /* --remap: the read's record of the sequences (-1: none), and what the batch returned for it */
@@ -684,6 +724,11 @@ static unsigned long long bc_count[FLAPPIE_BARCODE_MAX_KIT + 1];
 static flappie_adapter_kit *ad_kit = NULL;
 static ffhip_adapters *ad_dev = NULL;
 static unsigned long long ad_count[FLAPPIE_ADAPTER_MAX_KIT], ad_reads_with_hit, ad_stats[4];
+/* flappie --map: the reference as the file gave it and on the device, the table, the records' file, and the summary */
+static flappie_map_ref *mp_ref = NULL;
+static ffhip_map_ref *mp_dev = NULL;
+static FILE *mp_out = NULL, *mp_recs = NULL;
+static flappie_map_summary mp_sum;
 /* flappie --remap: the sequences, the table, and the summary's counts: mapped, no record, refused, mapped with maxdev = band */
 static flappie_remap_refs *rm_refs = NULL;
 static FILE *rm_out = NULL;
@@ -721,7 +766,7 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
  * records (FFHIP_RUN_POLYTAIL) */
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u) |
-           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | (tr_refs ? FFHIP_RUN_TRUTH : 0u) |
+           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (mp_dev ? FFHIP_RUN_MAP : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | (tr_refs ? FFHIP_RUN_TRUTH : 0u) |
            (ev_out ? FFHIP_RUN_EVENTS : 0u) | (md_out ? FFHIP_RUN_REMAP_MODS : 0u) | (vr_out ? FFHIP_RUN_REMAP_VARIANTS : 0u);
 }
 /* --remap: every read's record, by its read id, then by its file's base name; a bad record goes as a sequence of no bases (status 2) */
@@ -783,6 +828,7 @@ static int batch_set_truth(ffhip_batch *b, item **its, int n) {
 static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
     if (bc_dev) { const int rc = ffhip_batch_set_barcodes(b, bc_dev, args.bc_max_dist, args.bc_min_sep, args.bc_both); if (rc) return rc; }
     if (ad_dev) { const int rc = ffhip_batch_set_adapters(b, ad_dev, ad_max_dist); if (rc) return rc; }
+    if (mp_dev) { const int rc = ffhip_batch_set_map(b, mp_dev, map_window, map_max_error); if (rc) return rc; }
     if (pt_on) { const int rc = ffhip_batch_set_polytail(b, &pt_params); if (rc) return rc; }
     if (rm_refs) { const int rc = batch_set_remap(b, its, n); if (rc) return rc; }
     if (tr_refs) { const int rc = batch_set_truth(b, its, n); if (rc) return rc; }
@@ -1062,6 +1108,10 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
                 if (its[i]->have_ad && its[i]->ad_head.nhit > 0) ad_reads_with_hit++;
             }
         }
+        if (mp_dev) {                                          /* likewise: the whole call in signal order */
+            if (0 != ffhip_batch_map(b, i, &its[i]->mp)) warnx("%s", ffhip_last_error());
+            else its[i]->have_mp = 1;
+        }
         if (pt_on) {                                           /* likewise */
             if (0 != ffhip_batch_polytail(b, i, &its[i]->pt)) warnx("%s", ffhip_last_error());
             else { its[i]->have_pt = 1; if (0 != flappie_polytail_count(&pt_sum, &its[i]->pt)) warnx("out of memory for the poly tail summary"); }
@@ -1333,6 +1383,15 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
                     }
                 }
             }
+            if (mp_ref) {                                      /* likewise for --map: a line a read, and the mapped read's own stretch */
+                const char *name = *uuid ? uuid : base;       /* (what --truth and --remap find a record by) */
+                if (!it->have_mp) warnx("No map record returned for %s", it->filename);
+                else if (0 != flappie_map_write_line(mp_out, name, &it->mp, mp_ref)) warnx("The map record of %s does not fit the reference", it->filename);
+                else {
+                    flappie_map_summary_add(&mp_sum, &it->mp, map_window);
+                    if (mp_recs && flappie_map_write_record(mp_recs, name, &it->mp, mp_ref) < 0) warnx("The span of %s does not fit the reference", it->filename);
+                }
+            }
             if (tr_refs) {                                     /* likewise for --truth */
                 if (it->tr_ref < 0) flappie_truth_summary_add(&tr_sum, NULL);
                 else if (!it->have_tr) warnx("No alignment returned for %s", it->filename);
@@ -1360,6 +1419,7 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
         it->have_bc = 0;
         it->have_ad = 0;
         it->have_pt = 0;
+        it->have_mp = 0;
         free(it->rm);
         it->rm = NULL;
         free(it->ev);
@@ -2080,6 +2140,7 @@ int main(int argc, char *argv[]) {
     if ((args.rlc || args.run_scale_set) && !args.fasta) errx(EXIT_FAILURE, "--rlc and --run-scale go with --fasta");
     if (args.barcodes) errx(EXIT_FAILURE, "--barcodes is flappie's: the run-length model's records carry no base strings to search");
     if (ad_path || ad_opts) errx(EXIT_FAILURE, "--adapters is flappie's: the run-length model's records carry no base strings to search");
+    if (map_path || map_opts) errx(EXIT_FAILURE, "--map is flappie's: the run-length model's records carry no base strings to place");
     if (pt_on || pt_opts) errx(EXIT_FAILURE, "--poly-tail is flappie's: the run-length model's path is not one of bases");
     if (args.remap) errx(EXIT_FAILURE, "--remap is flappie's: the run-length model's scores are not transitions between the bases of a sequence");
     if (args.truth) errx(EXIT_FAILURE, "--truth is flappie's: the run-length model's call is a list of runs");
@@ -2116,6 +2177,16 @@ int main(int argc, char *argv[]) {
         char why[256];
         ad_kit = flappie_adapter_kit_read(ad_path, why, sizeof why);
         if (NULL == ad_kit) errx(EXIT_FAILURE, "--adapters %s: %s", ad_path, why);
+    }
+    /* --map: likewise */
+    if (map_opts && NULL == map_path) errx(EXIT_FAILURE, "--map-out, --map-window, --map-max-error and --map-records go with --map");
+    if (map_path && NULL == map_out_path) errx(EXIT_FAILURE, "--map and --map-out go together");
+    if (map_path) {
+        char why[256];
+        mp_ref = flappie_map_ref_read(map_path, why, sizeof why);
+        if (NULL == mp_ref) errx(EXIT_FAILURE, "--map %s: %s", map_path, why);
+        if (NULL == (mp_out = fopen(map_out_path, "w"))) errx(EXIT_FAILURE, "--map-out %s: cannot be written", map_out_path);
+        if (map_recs_path && NULL == (mp_recs = fopen(map_recs_path, "w"))) errx(EXIT_FAILURE, "--map-records %s: cannot be written", map_recs_path);
     }
     /* --remap: likewise */
     if ((NULL == args.remap) != (NULL == args.remap_out)) errx(EXIT_FAILURE, "--remap and --remap-out go together");
@@ -2195,6 +2266,10 @@ int main(int argc, char *argv[]) {
         stop_reader_procs();
         errx(EXIT_FAILURE, "--adapters: %s", ffhip_last_error());
     }
+    if (mp_ref && NULL == (mp_dev = ffhip_map_ref_upload(eng, mp_ref->n, (const char *const *)mp_ref->seq))) {
+        stop_reader_procs();
+        errx(EXIT_FAILURE, "--map: %s", ffhip_last_error());
+    }
 #endif
     hid_t hdf5out = open_or_create_hdf5(args.trace);
     reader_state rs;
@@ -2270,7 +2345,14 @@ int main(int argc, char *argv[]) {
         ffhip_adapters_free(ad_dev);
         flappie_adapter_kit_free(ad_kit);
     }
-    if (pt_on) {                       /* reads with a record, with a tail and a rate, with a tail alone; the median tail */
+    if (mp_ref) {                      /* reads, mapped, unmapped, discordant; the mapped reads' anchor distances over their anchor bases */
+        flappie_map_summary_print(stderr, &mp_sum);
+        if (0 != fclose(mp_out)) warnx("--map-out %s: write failed", map_out_path);
+        if (mp_recs && 0 != fclose(mp_recs)) warnx("--map-records %s: write failed", map_recs_path);
+        ffhip_map_ref_free(mp_dev);
+        flappie_map_ref_free(mp_ref);
+    }
+    if (pt_on) {                      /* reads with a record, with a tail and a rate, with a tail alone; the median tail */
         flappie_polytail_summary_print(stderr, &pt_sum);
         flappie_polytail_summary_free(&pt_sum);
     }

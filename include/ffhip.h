@@ -141,6 +141,12 @@ typedef struct {
  * buffer of their own (reads x 32 bytes) and come down in ONE extra copy, enqueued where the result block's copy is.  Everything else the run returns is that of the
  * same run without the flag.  No parameters set, the run-length model, or FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
 #define FFHIP_RUN_POLYTAIL   2097152u
+/* Every call of a flip-flop model placed on a small reference (ffhip_batch_map below, "map"): one 64-byte record a read -- status, strand and record, the span, and
+ * either anchor's own place, distance and runner-up -- made on the device from the base strings (k_map_scan, k_map_finish) against the reference attached with
+ * ffhip_batch_set_map.  The records are NOT part of the result block: they live in a buffer of their own (reads x 64 bytes) and come down in ONE extra copy, enqueued
+ * where the result block's copy is.  Everything else the run returns is that of the same run without the flag.  No reference attached, the run-length model, or
+ * FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
+#define FFHIP_RUN_MAP        4194304u
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -474,6 +480,52 @@ int ffhip_batch_set_adapters(ffhip_batch *b, const ffhip_adapters *kit, int max_
 int ffhip_batch_adapters(const ffhip_batch *b, int read, ffhip_adapter_header *header, const ffhip_adapter_hit **hits);
 int ffhip_op_adapter_scores(ffhip_engine *eng, const ffhip_adapters *kit, const char *bases, size_t len, uint8_t *d /*[2 n][len + 1]*/);
 int ffhip_op_adapter_hits(ffhip_engine *eng, const ffhip_adapters *kit, int max_dist, const char *bases, size_t len, ffhip_adapter_header *header, ffhip_adapter_hit *hits /*[15]*/);
+/* Map: where on a small reference (the lambda control, a plasmid, a mitochondrion, a virus, an amplicon panel) a call lies, on either strand: the step from "a genome"
+ * to "this read's own stretch of it, in signal order", which truth and remap take.  The call is the pattern here and the reference the text.
+ *   Reference: K records, 1 <= K <= 1024, each a string over ACGT (upper case) of 1 or more bases, at most FFHIP_MAP_MAX_TOTAL = 2^20 bases together; anything else
+ *     is refused with a text that names the record and the position.
+ *   Searches: q = 2 k + o; the text y_q of m_k columns is record k as given (o = 0) or its reverse complement (o = 1).  A search never runs across records.
+ *   Anchors of a call x of n bases (SIGNAL order, Z read as C) with window W, 64 <= W <= 4096 (default 4096): na = 1 if n <= W, else 2; the front anchor
+ *     p_0 = x[0 : min(n, W)], the rear anchor p_1 = x[n - min(n, W) : n].  With na = 1 the rear anchor is the front one and one search is made.  An anchor has L
+ *     bases, 1 <= L <= FFHIP_MAP_MAX_ANCHOR = 4096: at most 64 words of 64 rows.
+ *   Score row of anchor a in search q: the infix edit distance exactly as for barcodes and adapters above: D[0][j] = 0, D[i][0] = i, unit costs;
+ *     d_{a,q}[j] = D[L][j], j = 0 .. m_k.
+ *   Best place of an anchor: the lexicographically smallest (d, q, j) over all searches and columns -- the distance minimal, among equals the smallest q, then
+ *     the leftmost end j.  second = the minimum of d over all (q', j) with q' != q of the best place (with K = 1: the other strand).
+ *   Start, as for adapters: the largest i with ed(p, y[i:j]) = d.  Equivalently: the reversed anchor against y[j-1], y[j-2], ... with an anchored start
+ *     (D[0][c] = c), the first column c with D[L][c] = d; start = j - c, and c <= L + d <= 2 L.  The place covers y_q[start : end], end = j.
+ *   Bound: md_a = floor(L_a e / 1000), e the maximal error in per mille, 0 <= e <= 500 (default 250); 64-bit integer arithmetic.
+ *   Status: 0 no call (an empty slot of the batch, or n = 0); 1 mapped; 2 unmapped: some anchor's dist > md_a; 3 discordant: two anchors, both within their
+ *     bounds, but their q differ, or start_0 >= end_1, or |(end_1 - start_0) - n| > floor(n e / 1000).
+ *   Span, for status 1: tstart = start_0, tend = end_{na-1}, in the coordinates of y_q.  The forward-strand coordinates are the host's to make: [tstart, tend) for
+ *     o = 0, [m_k - tend, m_k - tstart) for o = 1.
+ *   Record (ffhip_map_call, 64 bytes, sixteen int32): status, n, nanchor, q, tstart, tend, then for each of two anchors { q, start, end, dist, second }.  With
+ *     nanchor = 1 the rear slot repeats the front one.  Status 0 is all zeros apart from the status (which is 0 too); for status 2 and 3 the record's own q,
+ *     tstart and tend are zero and the anchors' slots say why.
+ *   Locality (what the segmented kernel rests on): d <= L, and an optimal match spans at most L + d <= 2 L columns, so a search started fresh at column a
+ *     (D[i][a] = i) has the exact d at every column j >= a + 2 L.  k_map_scan cuts every search into segments of
+ *     FFHIP_MAP_SEGMENT columns -- segment g owns the ends in (g S, (g + 1) S], the first one column 0 too -- each worked from a fresh search 2 L columns before
+ *     it, or from the record's start if that is nearer.
+ * ffhip_map_ref_upload: the reference as 2-bit codes and its task list on the engine's device (NULL with a text on a bad reference); it must outlive the batches
+ *   it is attached to.
+ * ffhip_batch_set_map: the reference, window and bound of the batch's later runs with FFHIP_RUN_MAP.  Negative values mean the defaults; ref == NULL detaches.
+ * ffhip_batch_map: after ffhip_batch_finish of a run with the flag.  A run without the flag: FFHIP_EINVAL.
+ * ffhip_op_map_scores: the scan kernel on ONE anchor of 1 .. 4096 letters of ACGTZ: the whole score rows, those of q = 0 .. 2 K - 1 one after another, m_k + 1
+ *   entries each (twice the sum of m_k + 1 in all).
+ * ffhip_op_map: likewise, the record of one call of any len >= 0. */
+#define FFHIP_MAP_SEGMENT 2048
+#define FFHIP_MAP_MAX_TOTAL 1048576
+#define FFHIP_MAP_MAX_ANCHOR 4096
+typedef struct ffhip_map_ref ffhip_map_ref;
+typedef struct { int32_t q, start, end, dist, second; } ffhip_map_anchor;                                               /* 20 bytes */
+typedef struct { int32_t status, n, nanchor, q, tstart, tend; ffhip_map_anchor anchor[2]; } ffhip_map_call;             /* 64 bytes */
+int ffhip_map_segment(void);                    /* FFHIP_MAP_SEGMENT of the library as built */
+ffhip_map_ref *ffhip_map_ref_upload(ffhip_engine *eng, int n, const char *const *seq);
+void ffhip_map_ref_free(ffhip_map_ref *ref);
+int ffhip_batch_set_map(ffhip_batch *b, const ffhip_map_ref *ref, int window, int max_error);
+int ffhip_batch_map(const ffhip_batch *b, int read, ffhip_map_call *out);
+int ffhip_op_map_scores(ffhip_engine *eng, const ffhip_map_ref *ref, const char *pattern, size_t len, int32_t *d /* 2 sum (m_k + 1) */);
+int ffhip_op_map(ffhip_engine *eng, const ffhip_map_ref *ref, int window, int max_error, const char *bases, size_t len, ffhip_map_call *out);
 /* Remap: the signal of a read mapped to a sequence the caller knows.
  *   Read: N >= 1 blocks with transition scores T[b][.], b = 0 .. N - 1, nparam = nstate (nbase + 1) floats a block -- exactly what ffhip_batch_get_transitions
  *     returns for that run.  Sequence: s of L bases as codes 0 .. nbase - 1 (the model's alphabet, ACGT or ACGTZ), in SIGNAL order (--reverse, RNA: the caller's business).
