@@ -326,6 +326,10 @@ def lib():
     L.ffhip_batch_truth.argtypes = [vp, C.c_int, C.POINTER(CTruthCall)]
     L.ffhip_op_truth.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.POINTER(CTruthCall), C.POINTER(C.c_uint8)]
     L.ffhip_debug_truth_form.argtypes = [C.c_size_t]
+    L.ffhip_batch_set_truth_from_map.argtypes = [vp, C.c_int, C.c_int]
+    L.ffhip_op_map_stretch.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
+    L.ffhip_debug_map_truth_bound.restype = C.c_longlong
+    L.ffhip_debug_map_truth_bound.argtypes = [C.c_int, C.c_int]
     _LIB = L
     return L
 
@@ -845,6 +849,10 @@ class Batch:
                 lens[r] = a.size
         _check(lib().ffhip_batch_set_truth(self.h, n, ptrs, lens, int(band)))
 
+    def set_truth_from_map(self, on: bool = True, band: int = 512):
+        """later runs with RUN_MAP | RUN_TRUTH take each read's truth from its map record (ffhip_batch_set_truth_from_map); it and set_truth replace each other"""
+        _check(lib().ffhip_batch_set_truth_from_map(self.h, 1 if on else 0, int(band)))
+
     def truth(self, read: int) -> dict:
         """truth record of a run with RUN_TRUTH (ffhip_batch_truth): TRUTH_FIELDS as ints and ops (uint8 [dist + n_match] in path order, None unless status is 1)"""
         c = CTruthCall()
@@ -1039,6 +1047,18 @@ def op_map(engine: Engine, ref: MapRef, bases, window: int = -1, max_error: int 
     rec = CMapCall()
     _check(lib().ffhip_op_map(engine.h, ref.h, int(window), int(max_error), b, len(b), C.byref(rec)))
     return _map_record(rec)
+
+
+def op_map_stretch(engine: Engine, ref: MapRef, q: int, start: int, end: int) -> np.ndarray:
+    """ffhip_op_map_stretch: y_q[start : end] of the reference as codes 0 .. 3 (uint8 [end - start]), gathered by the kernel of truth from map"""
+    out = np.zeros(max(1, int(end) - int(start)), np.uint8)
+    _check(lib().ffhip_op_map_stretch(engine.h, ref.h, int(q), int(start), int(end), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return out[:int(end) - int(start)]
+
+
+def map_truth_bound(nblock: int, max_error: int) -> int:
+    """ffhip_debug_map_truth_bound: the most bases a mapped call's stretch can have for a read of `nblock` blocks (-1: bad arguments)"""
+    return int(lib().ffhip_debug_map_truth_bound(int(nblock), int(max_error)))
 
 
 def op_remap(engine: Engine, trans: np.ndarray, nbase: int, codes, band: int = 2048) -> tuple:

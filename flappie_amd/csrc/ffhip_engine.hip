@@ -781,12 +781,13 @@ struct ffhip_batch {
         int count[kRemapForms] = { 0, 0, 0, 0 };
     } rmp;
     // Truth (FFHIP_RUN_TRUTH, k_truth): the truths of ffhip_batch_set_truth on the host and (dseq) on the device; cap_reads 48-byte records and, behind them,
-    // m + blocks + 1 bytes of ops a read with a truth; the reads' list and the traceback workspace as for remap
+    // m + blocks + 1 bytes of ops a read with a truth; the reads' list and the traceback workspace as for remap.  from_map (ffhip_batch_set_truth_from_map): no
+    // truths on the host -- k_map_stretch writes each mapped read's into dseq and patches the list, and everything is sized from the bound (map_truth_bound)
     struct Truth : Annot {
         std::vector<std::vector<uint8_t>> seq;               // per read: codes 0 .. nbase - 1
         std::vector<signed char> state;                      // per read: 0 no truth, 1 a truth, 2 an empty one
         std::vector<size_t> off;                             // per read: its first byte of ops behind the records, and (one more entry) the end
-        int set = 0, band = 0;
+        int set = 0, band = 0, from_map = 0;
         uint8_t *dseq = nullptr; size_t dseq_cap = 0;
         unsigned long long *ws = nullptr; size_t ws_cap = 0;
         int count[kTruthForms] = { 0, 0, 0, 0 };
@@ -1652,11 +1653,50 @@ static void remap_spans(const ffhip_batch *b, int r, AnnotSpan out[2]) {        
     out[1] = AnnotSpan{ remap_moves_at(b) + read_row1(b, r), (size_t)b->hTb[r] };
 }
 
+// Truth from map: the most bases a stretch of a call of a read of N blocks can have, with max_error e per mille (include/ffhip.h "truth from map")
+static long long map_truth_bound(long long N, long long e) { return (N + 1) + (N + 1) * e / 1000; }
+// ... and the front's share in that mode: no truth's length is known here, so every read of N > 0 blocks is listed with m = 0 and status 1 for k_map_stretch to
+// patch, and its share of the truths, its workspace and its ops are those of bound(N, e)
+static int truth_prepare_from_map(ffhip_batch *b) {
+    ffhip_batch::Truth &f = b->tru;
+    const int nR = batch_nreads(b);
+    if (!(b->run_flags & FFHIP_RUN_MAP)) return set_err(FFHIP_EINVAL, "truth from map: the run does not make the map records (FFHIP_RUN_TRUTH goes with FFHIP_RUN_MAP in this mode)");
+    if (!b->map.ref) return set_err(FFHIP_EINVAL, "truth from map: no reference is attached to the batch (ffhip_batch_set_map)");
+    if (int rc = f.list.grow(b, b->stream, (size_t)b->cap_reads * sizeof(TruthRead), "truth: the reads' list")) return rc;
+    std::vector<TruthRead> per[kTruthForms];
+    std::vector<size_t> off((size_t)nR + 1, 0);
+    size_t ws = 0, seq = 0, ops = 0;
+    for (int r = 0; r < nR; r++) {
+        const int N = b->hTb[r];
+        const long long bound = N > 0 ? map_truth_bound(N, b->map.max_error) : 0;
+        if (bound > kTruthMaxLen) return set_err(FFHIP_EINVAL, "truth from map: read %d's stretch may have %lld bases (at most %d)", r, bound, kTruthMaxLen);
+        if (seq + (size_t)bound > (size_t)0xffffffffu)
+            return set_err(FFHIP_EINVAL, "truth from map: the reads' bounds come to more than 2^32 - 1 bases together (read %d: %lld), which the list's 32-bit offsets cannot hold", r, bound);
+        const int cap = N > 0 ? (int)bound + N + 1 : 0;
+        TruthRead tr{ ws, ops, (unsigned)seq, 0, N > 0 ? 1 : 0, r, cap, (int)bound };
+        int form = 0;
+        if (tr.status == 1) {
+            form = truth_form(std::min<long long>(2ll * f.band + 1, (long long)N + 2));
+            if (form < 0) return set_err(FFHIP_EINVAL, "truth: read %d's window of min(2 band + 1, blocks + 2) cells is more than %d", r, truth_max_window());
+            ws += truth_ws_words(form, (int)bound);
+        }
+        off[r] = ops;
+        seq += (size_t)bound; ops += (size_t)cap;
+        per[form].push_back(tr);
+    }
+    off[nR] = ops;
+    if (int rc = dgrow(b, (void **)&f.dseq, &f.dseq_cap, seq ? seq : 1, "truth from map: the truths")) return rc;
+    if (int rc = dgrow(b, (void **)&f.ws, &f.ws_cap, ws * 8, "truth: the traceback workspace")) return rc;
+    if (int rc = f.rec.grow(b, b->stream, truth_ops_at(b) + ops, "truth: the records and ops")) return rc;
+    f.off = std::move(off);
+    return forms_upload(b, f, per, f.count, nR);
+}
 // Truth, the front's share: as remap's.  The ops' bytes follow from the truths and the reads' blocks, so records and ops grow here.
 static_assert(sizeof(TruthRead) == 40, "the reads' list is copied as it stands");
 static int truth_prepare(ffhip_batch *b) {
     ffhip_batch::Truth &f = b->tru;
     const int nR = batch_nreads(b);
+    if (f.from_map) return truth_prepare_from_map(b);
     if (!f.set) return set_err(FFHIP_EINVAL, "truth: no truths are set for the batch (ffhip_batch_set_truth)");
     if ((int)f.seq.size() != nR) return set_err(FFHIP_EINVAL, "truth: truths were set for %zu reads, the batch holds %d", f.seq.size(), nR);
     if (int rc = f.list.grow(b, b->stream, (size_t)b->cap_reads * sizeof(TruthRead), "truth: the reads' list")) return rc;
@@ -1685,6 +1725,10 @@ static int truth_prepare(ffhip_batch *b) {
 }
 static void truth_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {           // from the strings and lengths k_assemble has just written
     ffhip_batch::Truth &f = b->tru;
+    if (f.from_map) {                                       // every form's entries in one launch, behind k_map_finish (map's row stands ahead of truth's in kAnnots)
+        launch_map_stretch(b->stream, b->map.ref->view, b->map.rec.dev, (TruthRead *)f.list.dev, batch_nreads(b), f.dseq);
+        b->launches[5]++;
+    }
     forms_launch(b, f, f.count, [&](int form, size_t at, int n) {
         launch_truth(b->stream, form, (const TruthRead *)f.list.dev + at, n, f.dseq, b->bases(), b->lens(), f.band, f.ws, (int *)f.rec.dev, f.rec.dev + truth_ops_at(b), b->Tb, tbr, rmap);
     });
@@ -1816,7 +1860,7 @@ static void variants_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {     
 static size_t variants_bytes(const ffhip_batch *b) { return perbase_bytes(b->var); }
 static void variants_spans(const ffhip_batch *b, int r, AnnotSpan out[2]) { perbase_spans(b->var, r, out); }
 
-// The table, in launch order (ffhip_batch::annot has the same): truth reads the strings as barcodes and adapters do; the poly tail reads the path and the signal; events, site mods and variants read what
+// The table, in launch order (ffhip_batch::annot has the same): the map stands ahead of truth, which in its from-map mode reads the records k_map_finish has just written; truth reads the strings as barcodes and adapters do; the poly tail reads the path and the signal; events, site mods and variants read what
 // k_remap has just written
 constexpr AnnotRow kAnnots[ffhip_batch::AN_COUNT] = {
     { FFHIP_RUN_BARCODES, nullptr, 0, "barcodes: a flip-flop model only (the run-length model has no base strings)", "barcodes need a decoded run (FFHIP_RUN_NO_DECODE is set)",
@@ -2348,7 +2392,11 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
                 sd->var.context = b->var.context; sd->var.all = b->var.all;
             }
         }
-        if (fl & FFHIP_RUN_TRUTH) {                       // ... and truths
+        if ((fl & FFHIP_RUN_TRUTH) && b->tru.from_map) {  // ... and truth's mode: the side batch maps these reads itself and takes their truths from its own records
+            sd->tru.seq.clear(); sd->tru.state.clear();   //     (the same N and max_error: the same room for a read in both batches)
+            sd->tru.set = 0; sd->tru.from_map = 1; sd->tru.band = b->tru.band;
+        } else if (fl & FFHIP_RUN_TRUTH) {                // ... or the truths
+            sd->tru.from_map = 0;
             std::vector<std::vector<uint8_t>> sq(16);
             std::vector<signed char> st(16, 0);
             for (int k = 0; k < n; k++) { sq[k] = b->tru.seq[reads[k0 + k]]; st[k] = b->tru.state[reads[k0 + k]]; }
@@ -2654,6 +2702,7 @@ extern "C" ffhip_map_ref *ffhip_map_ref_upload(ffhip_engine *eng, int n, const c
     ffhip_map_ref *ref = new ffhip_map_ref();
     ref->eng = eng;
     ref->score_entries = entries;
+    for (int k = 0; k < n; k++) ref->rec_len.push_back(recs[k].y);
     const struct { void **dev; const void *host; size_t bytes; } up[4] = { { &ref->d_words, words.data(), words.size() * 4 }, { &ref->d_tasks, tasks.data(), tasks.size() * sizeof(MapTask) },
                                                                           { &ref->d_recs, recs.data(), recs.size() * sizeof(int2) }, { &ref->d_rowoff, rowoff.data(), rowoff.size() * 4 } };
     for (const auto &u : up) {
@@ -2842,13 +2891,13 @@ extern "C" int ffhip_batch_variant_calls(const ffhip_batch *b, int read, const f
 static int truth_adopt(ffhip_batch *b, std::vector<std::vector<uint8_t>> &&seq, std::vector<signed char> &&state, int band) {
     if (int rc = seq_adopt(b, seq, &b->tru.dseq, &b->tru.dseq_cap, "truth: the truths")) return rc;
     b->tru.seq = std::move(seq); b->tru.state = std::move(state);
-    b->tru.band = band; b->tru.set = 1;
+    b->tru.band = band; b->tru.set = 1; b->tru.from_map = 0;
     return FFHIP_OK;
 }
 extern "C" int ffhip_batch_set_truth(ffhip_batch *b, int nread, const uint8_t *const *codes, const size_t *len, int band) {
     if (!b) return set_err(FFHIP_EINVAL, "null batch");
     if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "truth: the batch is between a run and its finish");
-    if (!codes) { b->tru.set = 0; b->tru.seq.clear(); b->tru.state.clear(); return FFHIP_OK; }
+    if (!codes) { b->tru.set = 0; b->tru.from_map = 0; b->tru.seq.clear(); b->tru.state.clear(); return FFHIP_OK; }
     const ffhip_model *m = b->mdl;
     if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "truth: a flip-flop model only (the run-length model's call is a list of runs)");
     if (!len || nread != batch_nreads(b)) return set_err(FFHIP_EINVAL, "truth: truths for %d reads, the batch holds %d", nread, batch_nreads(b));
@@ -2864,6 +2913,21 @@ extern "C" int ffhip_batch_set_truth(ffhip_batch *b, int nread, const uint8_t *c
         seq[r].assign(codes[r], codes[r] + len[r]);
     }
     return truth_adopt(b, std::move(seq), std::move(state), band);
+}
+// truth from map (include/ffhip.h "truth from map"; the kernel: k_map_stretch, ffhip_map.hip)
+extern "C" int ffhip_batch_set_truth_from_map(ffhip_batch *b, int on, int band) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "truth from map: the batch is between a run and its finish");
+    if (!on) { b->tru.from_map = 0; return FFHIP_OK; }
+    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "truth from map: a flip-flop model only (the run-length model's call is a list of runs)");
+    if (band < 0 || band > truth_max_band())
+        return set_err(FFHIP_EINVAL, "truth from map: the band half-width is %d (0 .. %d: the widest kernel form holds a window of %d cells)", band, truth_max_band(), truth_max_window());
+    b->tru.seq.clear(); b->tru.state.clear();               // (the two ways of giving truths replace each other)
+    b->tru.set = 0; b->tru.from_map = 1; b->tru.band = band;
+    return FFHIP_OK;
+}
+extern "C" long long ffhip_debug_map_truth_bound(int nblock, int max_error) {
+    return (nblock < 0 || max_error < 0 || max_error > 500) ? -1 : map_truth_bound(nblock, max_error);
 }
 extern "C" int ffhip_batch_truth(const ffhip_batch *b, int read, ffhip_truth_call *out) {
     if (!results_ok(b, read) || !out) return FFHIP_EINVAL;

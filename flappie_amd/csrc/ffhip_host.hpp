@@ -70,6 +70,7 @@ struct ffhip_map_ref {
     ffhip::MapRefView view{};
     void *d_words = nullptr, *d_tasks = nullptr, *d_recs = nullptr, *d_rowoff = nullptr;
     size_t score_entries = 0;           // of all 2 K score rows together: the sum of m_k + 1, twice
+    std::vector<int> rec_len;           // [nrec]: the records' letters, on the host (ffhip_op_map_stretch checks its span against them)
 };
 
 namespace ffhip {

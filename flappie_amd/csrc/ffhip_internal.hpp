@@ -279,8 +279,8 @@ struct TruthRead {
     unsigned long long ws;              // the read's first 64-bit word in the traceback workspace (truth_ws_words(form, m) of them)
     unsigned long long ops;             // its first byte in the ops buffer
     unsigned seq;                       // its first code in the truths
-    int m, status, read, cap, pad;      // bases; 0 no truth, 1 to be aligned, 2 refused; the read's index in the batch; its bytes of ops
-};
+    int m, status, read, cap, room;     // bases; 0 no truth, 1 to be aligned, 2 refused; the read's index in the batch; its bytes of ops; truth from map: its share of
+};                                      // the truths (the bound), which k_map_stretch fills -- it patches m and status; else 0
 constexpr int kTruthForms = 4, kTruthRecInts = 12;
 constexpr int kTruthMaxLen = 1 << 24;   // call and truth: the recursion's integers stay far below its +inf (1 << 29)
 int truth_form(long long window);
@@ -289,6 +289,9 @@ int truth_max_band();
 size_t truth_ws_words(int form, int m);
 void launch_truth(hipStream_t s, int form, const TruthRead *list, int count, const uint8_t *seq, const char *bases, const int *lens, int band,
                   unsigned long long *ws, int *records, uint8_t *ops, int Tb, const int *tbs, ReadMap map);
+// truth from map (k_map_stretch, ffhip_map.hip; include/ffhip.h "truth from map"): for each of `count` entries of truth's list with status 1, from the map record at
+// records[entry.read]: the stretch y_q[tstart : tend] as codes 0 .. 3 at seq + entry.seq, and entry.m and entry.status patched by the header's rule
+void launch_map_stretch(hipStream_t s, const MapRefView &ref, const void *records, TruthRead *list, int count, uint8_t *seq);
 // the signal of every base of a mapped read (k_events, ffhip_events.hip; include/ffhip.h "events"): per listed read whose remap record at records[read] says
 // { status 1, end 0 }, L events of 16 bytes { int32 first, count; float mean, sd } at events[out ..], from the read's samples sig[sig .. sig + n) and its bytes at the
 // read's row of the (Tb + 1)-entry byte buffer `rm`; any other read writes nothing.  One form; the launch comes behind launch_remap on the same stream.

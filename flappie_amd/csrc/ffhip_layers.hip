@@ -731,6 +731,32 @@ extern "C" int ffhip_op_map(ffhip_engine *eng, const ffhip_map_ref *ref, int win
     return op_map(eng, ref, window, max_error, bases, len, nullptr, out);
 }
 
+// the gather of truth from map on one span from host arguments (k_map_stretch; include/ffhip.h "truth from map"): a record and a list entry made here
+extern "C" int ffhip_op_map_stretch(ffhip_engine *eng, const ffhip_map_ref *ref, int q, int start, int end, uint8_t *codes) {
+    OP_ENTER(eng);
+    if (!ref || ref->eng != eng || !codes) return set_err(FFHIP_EINVAL, "bad map stretch arguments (a reference of this engine, an output of end - start bytes)");
+    if (q < 0 || q >= 2 * ref->view.nrec) return set_err(FFHIP_EINVAL, "map stretch: search %d is not one of 0 .. %d", q, 2 * ref->view.nrec - 1);
+    const int mk = ref->rec_len[(size_t)q >> 1];
+    if (start < 0 || end > mk || start >= end) return set_err(FFHIP_EINVAL, "map stretch: [%d, %d) is not a span of 1 or more of the record's %d bases", start, end, mk);
+    const int m = end - start;
+    ffhip_map_call rec;
+    memset(&rec, 0, sizeof rec);
+    rec.status = 1; rec.nanchor = 1; rec.q = q; rec.tstart = start; rec.tend = end;
+    const TruthRead tr{ 0ull, 0ull, 0u, 0, 1, 0, 0, m };
+    void *d_rec = tmp.upload(&rec, sizeof rec, s);
+    TruthRead *d_list = (TruthRead *)tmp.upload(&tr, sizeof tr, s);
+    uint8_t *d_seq = (uint8_t *)tmp.get((size_t)m);
+    if (!d_rec || !d_list || !d_seq) OP_NOMEM();
+    launch_map_stretch(s, ref->view, d_rec, d_list, 1, d_seq);
+    TruthRead got;
+    HIP_TRY(hipMemcpyAsync(&got, d_list, sizeof got, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipMemcpyAsync(codes, d_seq, (size_t)m, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    HIP_TRY(hipGetLastError(), FFHIP_EHIP);
+    if (got.status != 1 || got.m != m) return set_err(FFHIP_EHIP, "map stretch: the kernel left status %d and %d bases for a span of %d", got.status, got.m, m);
+    return FFHIP_OK;
+}
+
 // one matrix of transition scores mapped to one sequence (k_remap; include/ffhip.h "remap")
 extern "C" int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, int band, uint8_t *rm, float *score) {
     OP_ENTER(eng);

@@ -18,6 +18,8 @@
 //   wave minimum of d over the tasks of the other searches.  The start: the reversed anchor against y[j-1], y[j-2], ... with an anchored start (+1 enters word 0
 //   at every column), the same lane pipeline with one group of 64 lanes, until D[L][c] = d; c <= 2 L.  Then the bound, the pairing rule, and the record as four
 //   16-byte stores.
+// k_map_stretch (include/ffhip.h "truth from map"): one wave an entry of truth's read list, behind k_map_finish: the mapped read's stretch of the reference as codes
+//   where k_truth reads its truth, and the entry's length and status patched.  Its own comment stands in front of it.
 #include "ffhip_internal.hpp"
 
 namespace ffhip {
@@ -217,6 +219,49 @@ k_map_finish(MapRefView ref, const char *__restrict__ bases, const int *__restri
     else if (lane == 1) out[1] = make_uint4(ok ? (unsigned)as[0] : 0u, ok ? (unsigned)ae[1] : 0u, (unsigned)aq[0], (unsigned)as[0]);
     else if (lane == 2) out[2] = make_uint4((unsigned)ae[0], (unsigned)ad[0], (unsigned)a2[0], (unsigned)aq[1]);
     else if (lane == 3) out[3] = make_uint4((unsigned)as[1], (unsigned)ae[1], (unsigned)ad[1], (unsigned)a2[1]);
+}
+
+// k_map_stretch (include/ffhip.h "truth from map"): one wave an entry of truth's read list, all forms' entries in one launch, behind k_map_finish and ahead of the
+// k_truth launches.  A read whose map record says status 1 gets its stretch y_q[tstart : tend] as codes 0 .. 3 at seq + entry.seq, m = tend - tstart of them, read
+// with map_chunk in the orientation of q as the scan reads it; a lane takes one letter of 64 a pass, so a pass is one store of 64 bytes in a row.  Lane 0 then
+// patches the entry's m and status in the list, which k_truth reads.  entry.room is the read's share of `seq` (the bound): m > room, or a record that does not lie
+// in its reference record, is status 2 and writes no code.  An entry of status 0 (an empty slot) is left as it is.  Integers only, no atomics.
+__global__ void __launch_bounds__(64)
+k_map_stretch(MapRefView ref, const uint4 *__restrict__ rec, TruthRead *__restrict__ list, uint8_t *__restrict__ seq) {
+    FFHIP_DECODE_PRIO_SET();
+    const int lane = threadIdx.x;
+    TruthRead *e = list + blockIdx.x;
+    const TruthRead tr = *e;                             // (read whole before lane 0 patches it)
+    if (tr.status != 1) return;                          // an empty slot
+    const uint4 *r = rec + (size_t)tr.read * 4;
+    const uint4 r0 = r[0], r1 = r[1];
+    const int mstatus = (int)r0.x, q = (int)r0.w, ts = (int)r1.x, te = (int)r1.y, room = tr.room;
+    int status = 0, m = 0;
+    if (mstatus == 1) {
+        status = 2;
+        if (q >= 0 && q < 2 * ref.nrec) {
+            const int2 rc = ref.recs[q >> 1];                // { first letter, letters }
+            if (ts >= 0 && ts < te && te <= rc.y) {
+                m = te - ts;
+                if (m <= room) {
+                    status = 1;
+                    const int o = q & 1, dir = o ? -1 : 1;
+                    const long long g0 = o ? (long long)rc.x + rc.y - 1 - ts : (long long)rc.x + ts;      // the reference letter of y_q[tstart]
+                    uint8_t *out = seq + tr.seq;
+                    for (int i = lane; i < m; i += 64) {
+                        const unsigned v = map_chunk(ref.words, g0 + (long long)dir * (i & ~15), dir, o);
+                        out[i] = (uint8_t)((v >> (2 * (i & 15))) & 3u);
+                    }
+                }
+            }
+        }
+    }
+    if (lane == 0) { e->m = m; e->status = status; }
+}
+
+void launch_map_stretch(hipStream_t s, const MapRefView &ref, const void *records, TruthRead *list, int count, uint8_t *seq) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_map_stretch, dim3(count), dim3(64), 0, s, ref, (const uint4 *)records, list, seq);
 }
 
 const char *map_invalid(int window, int max_error) {

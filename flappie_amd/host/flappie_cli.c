@@ -47,6 +47,7 @@
 #include "../../include/flappie_polytail.h"
 #include "../../include/flappie_remap.h"
 #include "../../include/flappie_truth.h"
+#include "../../include/flappie_align.h"
 #include "../../include/networks.h"
 
 const char *argp_program_version = "flappie (MI355X/HIP) 0.1, interface of flappie 2.1.3";
@@ -134,7 +135,9 @@ static struct argp_option options[] = {
     {"map-out", 286, "hits.tsv", 0, "With --map (required): one line per read, no header: name, status (0 no call, 1 mapped, 2 unmapped, 3 discordant), n, anchors, record, strand, tstart, tend (forward strand), the record's length, and distance and runner-up of the front and the rear anchor; for status 2 and 3 record, strand, start and end of either anchor behind them"},
     {"map-window", 287, "W", 0, "With --map: bases of an anchor (64-4096, default 4096); a call of more has two, its first and its last W bases"},
     {"map-max-error", 288, "permille", 0, "With --map: largest edit distance of an anchor, and largest difference between the span on the reference and the call's length, in thousandths of their lengths (0-500, default 250)"},
-    {"map-records", 289, "recs.fa", 0, "With --map: for every mapped read a FASTA record of its own stretch of the reference in signal order (reverse-complemented for the - strand): the file --truth and --remap take in a second run"},
+    {"map-records", 289, "recs.fa", 0, "With --map: for every mapped read a FASTA record of its own stretch of the reference in signal order (reverse-complemented for the - strand): the file --remap takes in a second run (--truth too, which --truth-from-map spares)"},
+    {"truth-from-map", 290, 0, 0, "With --map and --truth-out: align every mapped read's call to its own stretch of the reference in the same run, on the GPU, as --truth would in a second run with the file of --map-records. acc.tsv gets one line per mapped read: the thirteen columns of --truth-out with the read's name as in hits.tsv, then record, strand, tstart and tend as in hits.tsv; the CIGAR stays in signal order. --truth-band applies; not with --truth. stdout, hits.tsv and recs.fa do not change"},
+    {"map-sam", 291, "aln.sam", 0, "With --truth-from-map: the alignments as a SAM file with @SQ lines: one line per read with a call, in output order; a read that is mapped and aligned with FLAG 0 or 16, POS, the CIGAR (=XID) in forward-strand order, SEQ (Z written as C) and QUAL turned to the forward strand and NM:i; every other read unmapped (FLAG 4). SEQ is always the whole call: --reverse, --trim-barcodes, --trim-adapters and --split-reads do not alter it"},
 #endif
 #ifdef BUILD_RUNNIE
     {"map", 285, "ref.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
@@ -142,6 +145,8 @@ static struct argp_option options[] = {
     {"map-window", 287, "W", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-max-error", 288, "permille", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-records", 289, "recs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"truth-from-map", 290, 0, OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-sam", 291, "aln.sam", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"barcodes", 25, "kit.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"adapters", 269, "kit.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"adapter-max-dist", 270, "edits", OPTION_HIDDEN, "(flappie's option: refused here)"},
@@ -227,6 +232,9 @@ static bool mods_context_set = false, mods_all_paths = false;
  * map_opts: one of the options that go with --map was given */
 static char *map_path = NULL, *map_out_path = NULL, *map_recs_path = NULL;
 static bool map_opts = false;
+/* flappie: --truth-from-map and the file of --map-sam (runnie: seen, to be refused) */
+static bool tfm_on = false;
+static char *tfm_sam_path = NULL;
 static int map_window = -1;
 #ifndef BUILD_RUNNIE
 static int map_max_error = -1;
@@ -393,6 +401,8 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
     case 285: map_path = arg; break;
     case 286: map_out_path = arg; map_opts = true; break;
     case 289: map_recs_path = arg; map_opts = true; break;
+    case 290: tfm_on = true; break;
+    case 291: tfm_sam_path = arg; break;
 #ifdef BUILD_RUNNIE
     case 287: case 288: map_opts = true; break;
     case 270: case 271: case 272: case 273: case 274: ad_opts = true; break;
@@ -753,6 +763,8 @@ static unsigned long long vr_count[2];
 static flappie_remap_refs *tr_refs = NULL;
 static FILE *tr_out = NULL;
 static flappie_truth_summary tr_sum;
+/* flappie --truth-from-map: the truths are the mapped stretches (tr_refs stays NULL; tr_out and tr_sum serve); the file of --map-sam */
+static FILE *tfm_sam = NULL;
 #ifdef BUILD_RUNNIE
 /* --fasta: the runs and their run-length estimates come from the device (FFHIP_RUN_RLE_RUNS) with the batch's scale factors */
 static unsigned run_flags(void) { return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.fasta ? FFHIP_RUN_RLE_RUNS : 0u); }
@@ -766,7 +778,7 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
  * records (FFHIP_RUN_POLYTAIL) */
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u) |
-           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (mp_dev ? FFHIP_RUN_MAP : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | (tr_refs ? FFHIP_RUN_TRUTH : 0u) |
+           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (mp_dev ? FFHIP_RUN_MAP : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | ((tr_refs || tfm_on) ? FFHIP_RUN_TRUTH : 0u) |
            (ev_out ? FFHIP_RUN_EVENTS : 0u) | (md_out ? FFHIP_RUN_REMAP_MODS : 0u) | (vr_out ? FFHIP_RUN_REMAP_VARIANTS : 0u);
 }
 /* --remap: every read's record, by its read id, then by its file's base name; a bad record goes as a sequence of no bases (status 2) */
@@ -832,6 +844,7 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
     if (pt_on) { const int rc = ffhip_batch_set_polytail(b, &pt_params); if (rc) return rc; }
     if (rm_refs) { const int rc = batch_set_remap(b, its, n); if (rc) return rc; }
     if (tr_refs) { const int rc = batch_set_truth(b, its, n); if (rc) return rc; }
+    if (tfm_on) { const int rc = ffhip_batch_set_truth_from_map(b, 1, args.truth_band); if (rc) return rc; }
     return ffhip_batch_run(b, args.temperature, flags);
 }
 #endif
@@ -1143,7 +1156,7 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
                 }
             }
         }
-        if (tr_refs && its[i]->tr_ref >= 0) {                  /* the call against its truth, in signal order whatever --reverse does below */
+        if ((tr_refs && its[i]->tr_ref >= 0) || tfm_on) {      /* the call against its truth, in signal order whatever --reverse does below */
             ffhip_truth_call tc;
             if (0 != ffhip_batch_truth(b, i, &tc)) warnx("%s", ffhip_last_error());
             else {
@@ -1398,6 +1411,28 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
                 else {
                     if (0 != flappie_truth_write_line(tr_out, tr_refs->name[it->tr_ref], &it->tr, it->tr_ops, it->tr_nops)) warnx("The ops of %s do not fit its record", it->filename);
                     if (0 != flappie_truth_summary_add(&tr_sum, &it->tr)) warnx("--truth: out of memory for the summary");
+                }
+            }
+            if (tfm_on) {                                      /* --truth-from-map: a line a mapped read, with its place behind the alignment; the SAM file */
+                const char *name = *uuid ? uuid : base;       /* (hits.tsv's name) */
+                const int mapped = it->have_mp && 1 == it->mp.status;
+                if (!it->have_mp || !it->have_tr) warnx("No %s returned for %s", it->have_mp ? "alignment" : "map record", it->filename);
+                if (!mapped || !it->have_tr) flappie_truth_summary_add(&tr_sum, NULL);
+                else {
+                    if (0 != flappie_align_write_acc_line(tr_out, name, &it->tr, it->tr_ops, it->tr_nops, &it->mp, mp_ref)) warnx("The ops of %s do not fit its record", it->filename);
+                    if (0 != flappie_truth_summary_add(&tr_sum, &it->tr)) warnx("--truth-from-map: out of memory for the summary");
+                }
+                if (tfm_sam) {                                 /* the whole call in signal order, whatever --reverse did to the strings */
+                    const size_t n = strlen(it->res.basecall);
+                    char *sq = strdup(it->res.basecall), *ql = it->res.quality ? strdup(it->res.quality) : NULL;
+                    if (NULL == sq || NULL == ql || strlen(ql) != n) warnx("--map-sam: no call and quality of one length for %s", it->filename);
+                    else {
+                        if (args.reverse) { reverse_char_array(sq, n); reverse_char_array(ql, n); }
+                        if (flappie_align_write_sam_line(tfm_sam, name, sq, ql, n, (mapped && it->have_tr) ? &it->tr : NULL, it->tr_ops, it->tr_nops, &it->mp, mp_ref) < 0)
+                            warnx("The alignment of %s does not fit the reference", it->filename);
+                    }
+                    free(sq);
+                    free(ql);
                 }
             }
             if (hdf5out >= 0) {
@@ -2144,6 +2179,7 @@ int main(int argc, char *argv[]) {
     if (pt_on || pt_opts) errx(EXIT_FAILURE, "--poly-tail is flappie's: the run-length model's path is not one of bases");
     if (args.remap) errx(EXIT_FAILURE, "--remap is flappie's: the run-length model's scores are not transitions between the bases of a sequence");
     if (args.truth) errx(EXIT_FAILURE, "--truth is flappie's: the run-length model's call is a list of runs");
+    if (tfm_on || tfm_sam_path) errx(EXIT_FAILURE, "--truth-from-map and --map-sam are flappie's: the run-length model's call is a list of runs");
     if (args.remap_events) errx(EXIT_FAILURE, "--remap-events is flappie's: it goes with --remap, which the run-length model does not have");
     if (mods_path) errx(EXIT_FAILURE, "--remap-mods is flappie's: it goes with --remap, which the run-length model does not have");
     if (vars_path || vars_out_path || vars_opts) errx(EXIT_FAILURE, "--remap-variants is flappie's: it goes with --remap, which the run-length model does not have");
@@ -2181,6 +2217,11 @@ int main(int argc, char *argv[]) {
     /* --map: likewise */
     if (map_opts && NULL == map_path) errx(EXIT_FAILURE, "--map-out, --map-window, --map-max-error and --map-records go with --map");
     if (map_path && NULL == map_out_path) errx(EXIT_FAILURE, "--map and --map-out go together");
+    /* ... and --truth-from-map, which stands on it */
+    if (tfm_on && NULL == map_path) errx(EXIT_FAILURE, "--truth-from-map goes with --map: it aligns a call to the stretch --map placed it on");
+    if (tfm_on && NULL != args.truth) errx(EXIT_FAILURE, "--truth-from-map does not go with --truth: a call is aligned to one truth, the file's record or the mapped stretch");
+    if (tfm_on && NULL == args.truth_out) errx(EXIT_FAILURE, "--truth-from-map and --truth-out go together");
+    if (tfm_sam_path && !tfm_on) errx(EXIT_FAILURE, "--map-sam goes with --truth-from-map");
     if (map_path) {
         char why[256];
         mp_ref = flappie_map_ref_read(map_path, why, sizeof why);
@@ -2219,8 +2260,15 @@ int main(int argc, char *argv[]) {
         }
     }
     /* --truth: likewise */
-    if ((NULL == args.truth) != (NULL == args.truth_out)) errx(EXIT_FAILURE, "--truth and --truth-out go together");
-    if (args.truth_band_set && NULL == args.truth) errx(EXIT_FAILURE, "--truth-band goes with --truth");
+    if (!tfm_on && (NULL == args.truth) != (NULL == args.truth_out)) errx(EXIT_FAILURE, "--truth and --truth-out go together");
+    if (args.truth_band_set && NULL == args.truth && !tfm_on) errx(EXIT_FAILURE, "--truth-band goes with --truth or --truth-from-map");
+    if (tfm_on) {
+        if (NULL == (tr_out = fopen(args.truth_out, "w"))) errx(EXIT_FAILURE, "--truth-out %s: cannot be written", args.truth_out);
+        if (tfm_sam_path) {
+            if (NULL == (tfm_sam = fopen(tfm_sam_path, "w"))) errx(EXIT_FAILURE, "--map-sam %s: cannot be written", tfm_sam_path);
+            flappie_align_write_sam_header(tfm_sam, mp_ref);
+        }
+    }
     if (args.truth) {
         char why[256];
         tr_refs = flappie_remap_refs_read(args.truth, flappie_model_has_modbase(args.model) ? "ACGTZ" : "ACGT", why, sizeof why);
@@ -2383,6 +2431,12 @@ int main(int argc, char *argv[]) {
         flappie_truth_summary_free(&tr_sum);
         if (0 != fclose(tr_out)) warnx("--truth-out %s: write failed", args.truth_out);
         flappie_remap_refs_free(tr_refs);
+    }
+    if (tfm_on) {                      /* the same lines: the reads that were not mapped count as no_record */
+        flappie_truth_summary_print(stderr, &tr_sum);
+        flappie_truth_summary_free(&tr_sum);
+        if (0 != fclose(tr_out)) warnx("--truth-out %s: write failed", args.truth_out);
+        if (tfm_sam && 0 != fclose(tfm_sam)) warnx("--map-sam %s: write failed", tfm_sam_path);
     }
 #endif
     flappie_hip_shutdown();

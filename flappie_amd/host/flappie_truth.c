@@ -24,9 +24,9 @@ long flappie_truth_write_cigar(FILE *out, const uint8_t *ops, size_t nops) {
     return wrote;
 }
 
-int flappie_truth_write_line(FILE *out, const char *name, const flappie_truth_rec *rec, const uint8_t *ops, size_t nops) {
+int flappie_truth_write_fields(FILE *out, const char *name, const flappie_truth_rec *rec, const uint8_t *ops, size_t nops) {
     if (1 != rec->status) {
-        fprintf(out, "%s\t%d\t%zu\t%zu\t%d\t*\t*\t*\t*\t*\t*\t*\t*\n", name, rec->status, rec->n, rec->m, rec->band);
+        fprintf(out, "%s\t%d\t%zu\t%zu\t%d\t*\t*\t*\t*\t*\t*\t*\t*", name, rec->status, rec->n, rec->m, rec->band);
         return 0;
     }
     size_t cnt[4] = { 0, 0, 0, 0 };
@@ -37,6 +37,11 @@ int flappie_truth_write_line(FILE *out, const char *name, const flappie_truth_re
     fprintf(out, "%s\t%d\t%zu\t%zu\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.6f\t", name, rec->status, rec->n, rec->m, rec->band, rec->maxdev, rec->dist, rec->n_match, rec->n_mismatch,
             rec->n_ins, rec->n_del, flappie_truth_identity(rec));
     flappie_truth_write_cigar(out, ops, nops);
+    return 0;
+}
+
+int flappie_truth_write_line(FILE *out, const char *name, const flappie_truth_rec *rec, const uint8_t *ops, size_t nops) {
+    if (0 != flappie_truth_write_fields(out, name, rec, ops, nops)) return -1;
     fputc('\n', out);
     return 0;
 }

@@ -737,6 +737,33 @@ int ffhip_batch_truth(const ffhip_batch *b, int read, ffhip_truth_call *out);
 int ffhip_op_truth(ffhip_engine *eng, const char *call, size_t n, const uint8_t *truth, size_t m, int band, ffhip_truth_call *out, uint8_t *ops /* n + m */);
 /* the kernel form a window of that many cells takes: 0, 1 one wave (up to 64, 256 cells), 2, 3 a workgroup (up to 1280, 2560 cells); -1: none */
 int ffhip_debug_truth_form(size_t window);
+/* Truth from map: each call aligned to the stretch of the reference it was mapped to, in ONE run -- the map record is on the device when k_map_finish is done, the
+ * reference is resident as 2-bit codes and the call's letters are where k_truth reads them, so nothing goes through the host (tests/maptruth_ref.py restates this).
+ *   Stretch of a map record with status 1, search q = 2 k + o and span [tstart, tend): y_q[tstart : tend], y_q record k as given (o = 0) or its reverse complement
+ *     (o = 1), as codes 0 .. 3 (A C G T): m = tend - tstart bases.
+ *   The truth of a read in this mode: map status 1 and 1 <= m <= bound: the stretch, and the truth status is what the recursion under "truth" gives (1 or 2).  Any
+ *     other map status (0, 2, 3): no truth, truth status 0 -- a read without a truth under ffhip_batch_set_truth.  1 <= m with m > bound cannot occur (below); the
+ *     kernel guards against it all the same and reports truth status 2.
+ *   The bound: a mapped call of n bases has m <= n + floor(n e / 1000), e the batch's max_error.  One anchor: its place spans c <= L + d <= n + md columns.  Two
+ *     anchors: the concordance rule itself.  n <= nblock + 1, so bound(N, e) = (N + 1) + floor((N + 1) e / 1000) for a read of N blocks, in 64-bit integers.  The host
+ *     knows N and e and not n: a read's share of the truths is bound bases, its traceback workspace that of bound rows of its kernel form (the form follows from
+ *     min(2 band + 1, N + 2) cells as under "truth") and its ops bound + N + 1 bytes.
+ *   The price: the workspace is sized for bound rows and not for m.  At about 0.4 called bases a block, m is about 0.4 N and bound 1.25 N at the default e: roughly
+ *     three to four times what exact sizing takes.  ffhip_debug_batch_device_bytes counts it; when it cannot be had: FFHIP_ENOMEM with the bytes in the text, as under
+ *     "truth".  The bounds of a batch's reads together must fit 32 bits (the list's offsets), and one bound 2^24: otherwise FFHIP_EINVAL with a text.
+ *   Everything else -- band, recursion, traceback rule, record, ops, the folding of Z -- is that of "truth" with t the stretch: a read's truth record and ops are the
+ *     same bytes as those of a second run given the stretch through ffhip_batch_set_truth.  That equality defines the feature.
+ * ffhip_batch_set_truth_from_map: on = 1: the batch's later runs with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH take each read's truth from its map record (k_map_stretch, one
+ *   launch behind k_map_finish and ahead of k_truth, no copy and no wait); band as for ffhip_batch_set_truth (0 .. 1279, otherwise FFHIP_EINVAL).  on = 0 leaves the
+ *   mode.  It and ffhip_batch_set_truth replace each other: the later call wins.  The run-length model, or a call between a run and its finish: FFHIP_EINVAL.  A run in
+ *   this mode with FFHIP_RUN_TRUTH but without FFHIP_RUN_MAP, or with no reference attached: FFHIP_EINVAL with a text that says which.  ffhip_batch_truth is
+ *   unchanged: m comes from the record.
+ * ffhip_op_map_stretch: the gather kernel on ONE span from host arguments: y_q[start : end] as end - start codes.  q outside 0 .. 2 K - 1, start < 0, end > m_k or
+ *   start >= end: FFHIP_EINVAL.
+ * ffhip_debug_map_truth_bound: bound(nblock, max_error) as the library sizes by it (-1: nblock < 0 or max_error outside 0 .. 500); no engine, no device. */
+int ffhip_batch_set_truth_from_map(ffhip_batch *b, int on, int band);
+int ffhip_op_map_stretch(ffhip_engine *eng, const ffhip_map_ref *ref, int q, int start, int end, uint8_t *codes /* end - start */);
+long long ffhip_debug_map_truth_bound(int nblock, int max_error);
 int ffhip_runlength_viterbi(ffhip_engine *eng, ffhip_mat param, int *path /* nblock */, float *score);
 /* decoders of the first-generation head on [4 nbase x nblock] matrices: decode_runlength (decode.c:694-767), posterior_runlength
  * (decode.c:793-892; post is [4 nbase x nblock + 1]), runlengths_mean (decode.c:576-603) */

@@ -13,7 +13,8 @@
  *  half open) and the record's length are * unless status is 1.  For status 2 and 3 eight further columns say where each anchor went on its own:
  *    front_record  front_strand  front_start  front_end  rear_record  rear_strand  rear_start  rear_end      (forward strand)
  *  --map-records recs.fa: for every mapped read ">name" and y_q[tstart : tend] -- the read's own stretch of the reference in SIGNAL order, reverse-complemented for
- *  the - strand: the file --truth and --remap take (in a second run: their sequences are set before a batch runs).
+ *  the - strand: the file --remap takes (in a second run: its sequences are set before a batch runs), and --truth too, which --truth-from-map spares
+ *  (include/flappie_align.h).
  *  A search's coordinates [start, end) in y_q are [start, end) on the forward strand for strand + and [m - end, m - start) for strand -.
  */
 #ifndef FFHIP_FLAPPIE_MAP_H

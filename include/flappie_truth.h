@@ -41,6 +41,8 @@ double flappie_truth_identity(const flappie_truth_rec *rec);
 long flappie_truth_write_cigar(FILE *out, const uint8_t *ops, size_t nops);
 /* one line of acc.tsv; ops may be NULL unless status is 1.  Returns 0, -1 for ops that do not fit the record's counts (nothing is written then) */
 int flappie_truth_write_line(FILE *out, const char *name, const flappie_truth_rec *rec, const uint8_t *ops, size_t nops);
+/* the same thirteen columns without the end of the line, for a table that puts columns of its own behind them (include/flappie_align.h) */
+int flappie_truth_write_fields(FILE *out, const char *name, const flappie_truth_rec *rec, const uint8_t *ops, size_t nops);
 /* the summary: a read with a record (rec != NULL) or without one; 0, -1 when memory runs out */
 int flappie_truth_summary_add(flappie_truth_summary *sum, const flappie_truth_rec *rec);
 double flappie_truth_summary_pooled(const flappie_truth_summary *sum);
