@@ -467,15 +467,18 @@ class Prepared:
 
     def __init__(self, engine: "Engine", raws: List[np.ndarray], trim_start: int = 200, trim_end: int = 10,
                  varseg_chunk: int = 100, varseg_thresh: float = 0.0, mode: int = PREP_MEDMAD, delta: float = 0.0, begin_only: bool = False,
-                 calibrations=None):
+                 calibrations=None, ranges=None):
         """begin_only: ffhip_prep_begin (the work is enqueued, the call returns); `finish()` then waits -- ranges, statistics and signals are there after it.
         calibrations: one (offset, raw_unit) per read -- `raws` are then int16 DAC values, scaled to picoamperes on the device (ffhip_prep_create_dac /
-        ffhip_prep_begin_dac).  varseg_chunk = 0 (either kind of input): no trimming at all, every read whole"""
+        ffhip_prep_begin_dac).  varseg_chunk = 0 (either kind of input): no trimming at all, every read whole.
+        ranges: one (start, end) per read of float samples -- raw_table's `start` and `end`, the stretch the preparation starts from (default: 0 and the read's length)"""
         self.engine = engine
         self.n = len(raws)
         if calibrations is not None:
             if len(calibrations) != self.n:
                 raise ValueError("one (offset, raw_unit) per read")
+            if ranges is not None:
+                raise ValueError("DAC reads are prepared whole: no ranges")
             darr = (CDacRead * self.n)()
             keep = [np.ascontiguousarray(r, dtype=np.int16) for r in raws]
             for i, r in enumerate(keep):
@@ -487,8 +490,11 @@ class Prepared:
             return
         arr = (CRawTable * self.n)()
         keep = [np.ascontiguousarray(r, dtype=np.float32) for r in raws]
+        if ranges is not None and len(ranges) != self.n:
+            raise ValueError("one (start, end) per read")
         for i, r in enumerate(keep):
-            arr[i] = CRawTable(None, r.size, 0, r.size, _fptr(r))
+            start, end = (0, r.size) if ranges is None else ranges[i]
+            arr[i] = CRawTable(None, r.size, start, end, _fptr(r))
         fn = lib().ffhip_prep_begin if begin_only else lib().ffhip_prep_create
         self.h = fn(engine.h, arr, self.n, trim_start, trim_end, varseg_chunk, varseg_thresh, mode, delta)
         if not self.h:

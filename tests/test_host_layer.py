@@ -54,6 +54,14 @@ def host():
     L.medianf.restype = C.c_float
     L.medianf.argtypes = [C.POINTER(C.c_float), C.c_size_t]
     L.medmad_normalise_array.argtypes = [C.POINTER(C.c_float), C.c_size_t]
+    L.quantilef.restype = None
+    L.quantilef.argtypes = [C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t]
+    L.madf.restype = C.c_float
+    L.madf.argtypes = [C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float)]
+    L.shift_scale_array.restype = None
+    L.shift_scale_array.argtypes = [C.POINTER(C.c_float), C.c_size_t, C.c_float, C.c_float]
+    L.difference_array.restype = None
+    L.difference_array.argtypes = [C.POINTER(C.c_float), C.c_size_t]
     L.trim_and_segment_raw.restype = RawTable
     L.trim_and_segment_raw.argtypes = [RawTable, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float]
     L.trim_raw_by_mad.restype = RawTable
@@ -157,6 +165,68 @@ def test_signal_prep_matches_reference_fixtures_and_oracle(host):
     assert np.array_equal(x, y)
     a = np.array([0, 1, 2, 3, 4], dtype=np.float32)
     assert host.medianf(_f(a), 5) == 2.0 and abs(host.medianf(_f(a), 4) - 1.5) <= 1e-5   # test_util.c:32-42
+
+
+@pytest.mark.gpu
+def test_reference_named_prep_functions_on_hostile_arrays(host):
+    """quantilef, medianf, madf, medmad_normalise_array, shift_scale_array and difference_array by their reference names, against the sort-based numpy statement
+    (tests/prep_ref.py, held to the oracle in tests/test_prep_ref.py): every value family of tests/test_prep_selection_gpu.py at an odd short length and one past a
+    workgroup's width."""
+    import prep_ref as R
+    for name, n, x in R.single_arrays():
+        if n not in (5, 257):
+            continue
+        got = R.QUANTILES.copy()
+        host.quantilef(_f(x), n, _f(got), got.size)
+        assert R.same(got, R.quantilef(x, R.QUANTILES)), (name, n, got)
+        assert R.same(np.float32(host.medianf(_f(x), n)), R.medianf(x)), (name, n)
+        assert R.same(np.float32(host.madf(_f(x), n, None)), R.madf(x)), (name, n)
+        med = C.c_float(R.GIVEN_MEDIAN)
+        assert R.same(np.float32(host.madf(_f(x), n, C.byref(med))), R.madf(x, R.GIVEN_MEDIAN)), (name, n)
+        y = x.copy()
+        host.medmad_normalise_array(_f(y), n)
+        assert R.same(y, R.medmad_normalise_array(x)[0]), (name, n)
+    for n in (1, 2, 257):
+        x = R.element_values(n, np.random.default_rng([18, n]))
+        y = x.copy()
+        host.difference_array(_f(y), n)
+        assert R.same(y, R.difference_array(x)), n
+        y = x.copy()
+        host.shift_scale_array(_f(y), n, -3.25, 2.5)
+        assert R.same(y, R.shift_scale_array(x, -3.25, 2.5)), n
+
+
+@pytest.mark.gpu
+def test_reference_named_trims_with_stretches_and_thresholds(host):
+    """trim_raw_by_mad and trim_and_segment_raw by their reference names with raw_table.start != 0, end != n and a non-zero threshold quantile, against
+    tests/prep_ref.py.  trim_and_segment_raw frees the samples of a read it rejects (flappie_common.c:22-25): its reads are handed over in malloc'ed memory."""
+    import prep_ref as R
+    libc = C.CDLL(None)
+    libc.malloc.restype = C.c_void_p
+    libc.malloc.argtypes = [C.c_size_t]
+    libc.free.argtypes = [C.c_void_p]
+    kept = rejected = 0
+    for chunk in (3, 65):
+        for label, raw, start, end in R.trim_reads(chunk):
+            if label.split()[0] not in ("dac", "round") or int(label.split()[2]) not in (1, 4, 9):
+                continue
+            buf = raw.copy()
+            out = host.trim_raw_by_mad(RawTable(None, buf.size, start, end, _f(buf)), chunk, 0.5)
+            assert (out.start, out.end) == R.trim_raw_by_mad(raw, start, end, chunk, 0.5), (chunk, label)
+            assert out.n == raw.size and np.array_equal(buf, raw)
+            for perc, trim_start, trim_end in ((0.5, 0, 0), (0.9, 1, 1)):
+                want = R.trim_and_segment_raw(raw, start, end, trim_start, trim_end, chunk, perc)
+                mem = libc.malloc(raw.nbytes)
+                C.memmove(mem, raw.ctypes.data, raw.nbytes)
+                out = host.trim_and_segment_raw(RawTable(None, raw.size, start, end, C.cast(mem, C.POINTER(C.c_float))), trim_start, trim_end, chunk, perc)
+                if want is None:
+                    rejected += 1
+                    assert not out.raw and (out.n, out.start, out.end) == (0, 0, 0), (chunk, label, perc)      # (the samples are freed)
+                    continue
+                kept += 1
+                assert out.raw and (out.n, out.start, out.end) == (raw.size,) + want, (chunk, label, perc)
+                libc.free(mem)
+    assert kept >= 8 and rejected >= 1, (kept, rejected)
 
 
 @pytest.mark.parametrize("name", ["r941_native", "r941_5mC"])
