@@ -35,6 +35,8 @@ RUN_ADAPTERS = 1048576   # flip-flop model: one adapter record a read (a header 
 ADAPTER_SEGMENT = 512    # FFHIP_ADAPTER_SEGMENT (include/ffhip.h "adapters"): the columns one wave of k_adapters owns; checked against the library at load
 ADAPTER_MAX_HITS = 15
 RUN_MAP = 4194304        # flip-flop model: one map record a read (status, strand and record, span, either anchor's place) made on the device against the reference of Batch.set_map (Batch.map)
+RUN_PILEUP = 8388608     # with RUN_MAP | RUN_TRUTH in the mode of Batch.set_truth_from_map: every aligned read's per-position counts added into the Pileup of Batch.set_pileup
+PILEUP_TOTALS = ("reads", "skipped", "match", "mismatch", "del", "ins", "edge_ins", "reserved")      # ffhip_pileup_totals, eight uint64
 MAP_SEGMENT = 2048       # FFHIP_MAP_SEGMENT (include/ffhip.h "map"): the columns one task of k_map_scan owns; checked against the library at load
 MAP_MAX_TOTAL = 1 << 20
 MAP_MAX_ANCHOR = 4096
@@ -328,6 +330,16 @@ def lib():
     L.ffhip_debug_truth_form.argtypes = [C.c_size_t]
     L.ffhip_batch_set_truth_from_map.argtypes = [vp, C.c_int, C.c_int]
     L.ffhip_op_map_stretch.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
+    L.ffhip_pileup_create.restype = vp
+    L.ffhip_pileup_create.argtypes = [vp, vp, C.c_int]
+    L.ffhip_pileup_free.restype = None
+    L.ffhip_pileup_free.argtypes = [vp]
+    L.ffhip_pileup_reset.argtypes = [vp]
+    L.ffhip_pileup_positions.restype = C.c_size_t
+    L.ffhip_pileup_positions.argtypes = [vp]
+    L.ffhip_pileup_download.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.ffhip_batch_set_pileup.argtypes = [vp, vp]
+    L.ffhip_op_pileup.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t]
     L.ffhip_debug_map_truth_bound.restype = C.c_longlong
     L.ffhip_debug_map_truth_bound.argtypes = [C.c_int, C.c_int]
     _LIB = L
@@ -577,6 +589,34 @@ class MapRef:
     def close(self):
         if self.h:
             lib().ffhip_map_ref_free(self.h)
+            self.h = None
+
+
+class Pileup:
+    """Per-position counts over all the reads of all the batches it is attached to (ffhip_pileup, include/ffhip.h "pileup"): 12 planes [strand][A C G T del ins]
+    of P uint32 and eight uint64 totals on the device.  `min_identity` in per mille (0 .. 1000) is fixed here.  `ref` must outlive it, and it every batch it is attached to."""
+
+    def __init__(self, engine: Engine, ref: MapRef, min_identity: int = 0):
+        self.engine = engine
+        self.ref = ref
+        self.h = lib().ffhip_pileup_create(engine.h, ref.h, int(min_identity))
+        if not self.h:
+            raise FFHipError(lib().ffhip_last_error().decode())
+        self.positions = int(lib().ffhip_pileup_positions(self.h))
+
+    def download(self):
+        """(counts uint32 [2][6][P], totals dict of PILEUP_TOTALS) once every accumulation enqueued by any batch is done (ffhip_pileup_download)"""
+        counts = np.zeros((2, 6, self.positions), dtype=np.uint32)
+        tot = np.zeros(len(PILEUP_TOTALS), dtype=np.uint64)
+        _check(lib().ffhip_pileup_download(self.h, counts.ctypes.data_as(C.POINTER(C.c_uint32)), tot.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return counts, {k: int(v) for k, v in zip(PILEUP_TOTALS, tot)}
+
+    def reset(self):
+        _check(lib().ffhip_pileup_reset(self.h))
+
+    def close(self):
+        if self.h:
+            lib().ffhip_pileup_free(self.h)
             self.h = None
 
 
@@ -859,6 +899,10 @@ class Batch:
         """later runs with RUN_MAP | RUN_TRUTH take each read's truth from its map record (ffhip_batch_set_truth_from_map); it and set_truth replace each other"""
         _check(lib().ffhip_batch_set_truth_from_map(self.h, 1 if on else 0, int(band)))
 
+    def set_pileup(self, pileup):
+        """the Pileup that later runs with RUN_MAP | RUN_TRUTH | RUN_PILEUP add to when they are finished (ffhip_batch_set_pileup); None detaches"""
+        _check(lib().ffhip_batch_set_pileup(self.h, pileup.h if pileup is not None else None))
+
     def truth(self, read: int) -> dict:
         """truth record of a run with RUN_TRUTH (ffhip_batch_truth): TRUTH_FIELDS as ints and ops (uint8 [dist + n_match] in path order, None unless status is 1)"""
         c = CTruthCall()
@@ -1053,6 +1097,13 @@ def op_map(engine: Engine, ref: MapRef, bases, window: int = -1, max_error: int 
     rec = CMapCall()
     _check(lib().ffhip_op_map(engine.h, ref.h, int(window), int(max_error), b, len(b), C.byref(rec)))
     return _map_record(rec)
+
+
+def op_pileup(engine: Engine, pileup: Pileup, q: int, tstart: int, tend: int, call, ops):
+    """ffhip_op_pileup: ONE alignment -- search q, span [tstart, tend), the call's letters (A C G T Z, signal order) and its ops (0 .. 3, path order) -- added into `pileup`"""
+    s = call if isinstance(call, bytes) else str(call).encode()
+    o = np.ascontiguousarray(ops, dtype=np.uint8)
+    _check(lib().ffhip_op_pileup(engine.h, pileup.h, int(q), int(tstart), int(tend), s, len(s), (o if o.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), o.size))
 
 
 def op_map_stretch(engine: Engine, ref: MapRef, q: int, start: int, end: int) -> np.ndarray:

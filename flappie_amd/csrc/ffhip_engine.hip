@@ -804,6 +804,8 @@ struct ffhip_batch {
     } evt;
     struct Sites : PerBase { int *start = nullptr; size_t start_cap = 0; int context, all = 0; explicit Sites(int c) : context(c) {} } smd{ 15 };
     struct Variants : Sites { std::vector<std::vector<ffhip_variant>> set; Variants() : Sites(10) {} } var;
+    // Pileup (FFHIP_RUN_PILEUP, k_pileup): the engine-level object the batch's finished runs add to; nothing of it is the batch's
+    ffhip_pileup *pile = nullptr;
     enum { AN_COUNT = 9 };
     Annot &annot(int i) { Annot *const a[AN_COUNT] = { &bc, &ad, &map, &pt, &tru, &rmp, &evt, &smd, &var }; return *a[i]; }       // (the order of kAnnots: launch order)
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
@@ -1896,6 +1898,24 @@ static int annots_prepare(ffhip_batch *b, unsigned flags) {
     }
     return FFHIP_OK;
 }
+// Pileup (include/ffhip.h "pileup"): no record, no buffer of the batch's, so no row above.  The front's share: may this run ask
+static int pileup_check(const ffhip_batch *b, unsigned flags) {
+    if (!(flags & FFHIP_RUN_PILEUP)) return FFHIP_OK;
+    if (!(flags & FFHIP_RUN_TRUTH)) return set_err(FFHIP_EINVAL, "pileup: the run does not make the truth records (FFHIP_RUN_PILEUP goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH)");
+    if (!(flags & FFHIP_RUN_MAP)) return set_err(FFHIP_EINVAL, "pileup: the run does not make the map records (FFHIP_RUN_PILEUP goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH)");
+    if (!b->tru.from_map) return set_err(FFHIP_EINVAL, "pileup: the batch is not in the mode of truth from map (ffhip_batch_set_truth_from_map)");
+    if (!b->pile) return set_err(FFHIP_EINVAL, "pileup: no pileup is attached to the batch (ffhip_batch_set_pileup)");
+    if (b->pile->ref != b->map.ref) return set_err(FFHIP_EINVAL, "pileup: the attached pileup belongs to another reference than the batch's map reference");
+    return FFHIP_OK;
+}
+// ... and the finish's: the records, ops and letters are final (ffhip_batch_finish), so every listed read is counted once, on the batch's stream, unwaited for
+static void pileup_launch(ffhip_batch *b) {
+    ffhip_pileup *p = b->pile;
+    const ReadMap rmap = b->packed ? ReadMap{ b->d_vb0, b->d_vb1, b->nread } : ReadMap();
+    launch_pileup(b->stream, p->ref->view, (const TruthRead *)b->tru.list.dev, batch_nreads(b), b->map.rec.dev, (const int *)b->tru.rec.dev,
+                  b->tru.rec.dev + truth_ops_at(b), b->bases(), b->Tb, rmap, p->view);
+    for (int i = 0; i < b->eng->nstreams; i++) if (b->eng->streams[i] == b->stream) p->used[i] = true;
+}
 // the copies of a finished run beside the block's: one a feature the run made, if it has a byte to bring
 static int annots_copy_down(ffhip_batch *b) {
     for (int i = 0; i < ffhip_batch::AN_COUNT; i++)
@@ -1928,6 +1948,7 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
         if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "%s", sec.undecoded_text);
         if (int rc = b->res.ensure((ResSec)i, b->stream)) return rc;
     }
+    if (int rc = pileup_check(b, flags)) return rc;        // (ahead of truth's own refusal of a run without the map: the text names the flag that asked)
     if (int rc = annots_prepare(b, flags)) return rc;      // the products outside the block (kAnnots): may this run ask; their lists, workspaces and room
     if (b->packed && !p.packable)
         return set_err(FFHIP_EINVAL, "packed batches take the default path and the launch-per-step kernels only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / unfused flags, ordinary temperature)");
@@ -2402,7 +2423,7 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
             for (int k = 0; k < n; k++) { sq[k] = b->tru.seq[reads[k0 + k]]; st[k] = b->tru.state[reads[k0 + k]]; }
             if (int rc = truth_adopt(sd, std::move(sq), std::move(st), b->tru.band)) return rc;
         }
-        if (int rc = ffhip_batch_run(sd, b->last_temperature, (fl & ~(unsigned)FFHIP_RUN_KEEP_ACTS) | FFHIP_RUN_F32_RNN)) return rc;
+        if (int rc = ffhip_batch_run(sd, b->last_temperature, (fl & ~(unsigned)(FFHIP_RUN_KEEP_ACTS | FFHIP_RUN_PILEUP)) | FFHIP_RUN_F32_RNN)) return rc;      // (a side batch never counts: this batch does, below, from the patched records)
         if (int rc = ffhip_batch_finish(sd)) return rc;
         hipStream_t s = b->stream;
         for (int k = 0; k < n; k++) {
@@ -2489,6 +2510,9 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
         if (b->packed) { for (int v = 0; v < b->nvirt; v++) if (b->h_sat()[b->v_slot[v]]) over.push_back(v); }      // (the flag is the row's: every read of it goes again)
         else for (int r = 0; r < b->nread; r++) if (b->h_sat()[r] && b->hT[r] > 0) over.push_back(r);
         if (!over.empty()) if (int rc = rerun_on_f32_path(b, over)) { b->finished = 0; return rc; }
+        // the pileup: last, behind the patches of the re-runs, and here only -- the finish of a batch that went again on the launch-per-step kernels returned above
+        // with this inner finish's result -- so every read counts once, from the records the caller reads
+        if ((b->last_flags & FFHIP_RUN_PILEUP) && b->pile && b->map.valid && b->tru.valid) pileup_launch(b);
     }
     return FFHIP_OK;
 }
@@ -2924,6 +2948,68 @@ extern "C" int ffhip_batch_set_truth_from_map(ffhip_batch *b, int on, int band) 
         return set_err(FFHIP_EINVAL, "truth from map: the band half-width is %d (0 .. %d: the widest kernel form holds a window of %d cells)", band, truth_max_band(), truth_max_window());
     b->tru.seq.clear(); b->tru.state.clear();               // (the two ways of giving truths replace each other)
     b->tru.set = 0; b->tru.from_map = 1; b->tru.band = band;
+    return FFHIP_OK;
+}
+// ---- pileup (include/ffhip.h "pileup"; the kernel: ffhip_pileup.hip)
+static int pileup_wait(ffhip_pileup *p) {                // every accumulation enqueued against it, by any batch, is done
+    hipSetDevice(p->eng->device);
+    for (int i = 0; i < p->eng->nstreams; i++)
+        if (p->used[i]) { HIP_TRY(hipStreamSynchronize(p->eng->streams[i]), FFHIP_EHIP); p->used[i] = false; }
+    return FFHIP_OK;
+}
+static int pileup_zero(ffhip_pileup *p) {
+    hipStream_t s = p->eng->streams[0];
+    HIP_TRY(hipMemsetAsync(p->view.counts, 0, (size_t)kPileupPlanes * p->view.P * 4, s), FFHIP_EHIP);
+    HIP_TRY(hipMemsetAsync(p->view.totals, 0, (size_t)kPileupTotals * 8, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+extern "C" ffhip_pileup *ffhip_pileup_create(ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity) {
+    if (!eng || !ref || ref->eng != eng) { set_err(FFHIP_EINVAL, "pileup: a reference of this engine"); return nullptr; }
+    if (min_identity > 1000) { set_err(FFHIP_EINVAL, "pileup: min_identity is %d per mille (0 .. 1000)", min_identity); return nullptr; }
+    hipSetDevice(eng->device);
+    ffhip_pileup *p = new ffhip_pileup();
+    p->eng = eng; p->ref = ref;
+    size_t P = 0;
+    for (int m : ref->rec_len) P += (size_t)m;
+    p->view.P = P; p->view.min_identity = min_identity < 0 ? 0 : min_identity;
+    const size_t bytes = (size_t)kPileupPlanes * P * 4;
+    if (hipMalloc((void **)&p->view.counts, bytes) != hipSuccess || hipMalloc((void **)&p->view.totals, (size_t)kPileupTotals * 8) != hipSuccess) {
+        set_err(FFHIP_ENOMEM, "pileup: the counters take %zu bytes of device memory, which could not be had", bytes + (size_t)kPileupTotals * 8);
+        if (p->view.counts) hipFree(p->view.counts);
+        delete p;
+        return nullptr;
+    }
+    if (pileup_zero(p) != FFHIP_OK) { hipFree(p->view.counts); hipFree(p->view.totals); delete p; return nullptr; }
+    return p;
+}
+extern "C" void ffhip_pileup_free(ffhip_pileup *p) {
+    if (!p) return;
+    pileup_wait(p);
+    hipFree(p->view.counts); hipFree(p->view.totals);
+    delete p;
+}
+extern "C" int ffhip_pileup_reset(ffhip_pileup *p) {
+    if (!p) return set_err(FFHIP_EINVAL, "null pileup");
+    if (int rc = pileup_wait(p)) return rc;
+    return pileup_zero(p);
+}
+extern "C" size_t ffhip_pileup_positions(const ffhip_pileup *p) { return p ? p->view.P : 0; }
+extern "C" int ffhip_pileup_download(ffhip_pileup *p, uint32_t *counts, ffhip_pileup_totals *totals) {
+    if (!p) return set_err(FFHIP_EINVAL, "null pileup");
+    static_assert(sizeof(ffhip_pileup_totals) == kPileupTotals * 8, "the totals come down as they stand");
+    if (int rc = pileup_wait(p)) return rc;
+    if (counts) HIP_TRY(hipMemcpy(counts, p->view.counts, (size_t)kPileupPlanes * p->view.P * 4, hipMemcpyDeviceToHost), FFHIP_EHIP);
+    if (totals) HIP_TRY(hipMemcpy(totals, p->view.totals, sizeof *totals, hipMemcpyDeviceToHost), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+extern "C" int ffhip_batch_set_pileup(ffhip_batch *b, ffhip_pileup *p) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "pileup: the batch is between a run and its finish");
+    if (!p) { b->pile = nullptr; return FFHIP_OK; }
+    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "pileup: a flip-flop model only (the run-length model's call is a list of runs)");
+    if (p->eng != b->eng) return set_err(FFHIP_EINVAL, "pileup: the pileup belongs to another engine");
+    b->pile = p;
     return FFHIP_OK;
 }
 extern "C" long long ffhip_debug_map_truth_bound(int nblock, int max_error) {

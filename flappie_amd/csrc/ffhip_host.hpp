@@ -73,6 +73,15 @@ struct ffhip_map_ref {
     std::vector<int> rec_len;           // [nrec]: the records' letters, on the host (ffhip_op_map_stretch checks its span against them)
 };
 
+// a pileup on the device (ffhip_pileup_create; the kernel's view of it is PileupView): 12 planes of P uint32 and eight uint64 totals, which the batches it is
+// attached to add to on their own streams -- `used` says which of the engine's streams hold such work that nothing has waited for yet
+struct ffhip_pileup {
+    ffhip_engine *eng = nullptr;
+    const ffhip_map_ref *ref = nullptr;
+    ffhip::PileupView view{};
+    bool used[4] = { false, false, false, false };
+};
+
 namespace ffhip {
 
 int set_err(int code, const char *fmt, ...);        // records the thread's last error text, returns `code`

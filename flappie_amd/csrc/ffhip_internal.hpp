@@ -292,6 +292,14 @@ void launch_truth(hipStream_t s, int form, const TruthRead *list, int count, con
 // truth from map (k_map_stretch, ffhip_map.hip; include/ffhip.h "truth from map"): for each of `count` entries of truth's list with status 1, from the map record at
 // records[entry.read]: the stretch y_q[tstart : tend] as codes 0 .. 3 at seq + entry.seq, and entry.m and entry.status patched by the header's rule
 void launch_map_stretch(hipStream_t s, const MapRefView &ref, const void *records, TruthRead *list, int count, uint8_t *seq);
+// pileup (k_pileup, ffhip_pileup.hip; include/ffhip.h "pileup"): for each of `count` entries of truth's list, from the map record at map_records[entry.read], the
+// truth record at truth_records[entry.read], the K op bytes right-aligned in the entry's cap bytes of `ops` and the call's letters, the read's counts added into the
+// 12 planes of P uint32 [strand][column][position] and the eight uint64 totals { reads, skipped, match, mismatch, del, ins, edge_ins, 0 }.  The entry's m and
+// status are not read.  One launch, a workgroup an entry, atomics only.
+struct PileupView { unsigned *counts; unsigned long long *totals; size_t P; int min_identity; };
+constexpr int kPileupPlanes = 12, kPileupTotals = 8;
+void launch_pileup(hipStream_t s, const MapRefView &ref, const TruthRead *list, int count, const void *map_records, const int *truth_records, const uint8_t *ops,
+                   const char *bases, int Tb, ReadMap map, const PileupView &pv);
 // the signal of every base of a mapped read (k_events, ffhip_events.hip; include/ffhip.h "events"): per listed read whose remap record at records[read] says
 // { status 1, end 0 }, L events of 16 bytes { int32 first, count; float mean, sd } at events[out ..], from the read's samples sig[sig .. sig + n) and its bytes at the
 // read's row of the (Tb + 1)-entry byte buffer `rm`; any other read writes nothing.  One form; the launch comes behind launch_remap on the same stream.

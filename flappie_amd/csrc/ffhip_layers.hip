@@ -757,6 +757,41 @@ extern "C" int ffhip_op_map_stretch(ffhip_engine *eng, const ffhip_map_ref *ref,
     return FFHIP_OK;
 }
 
+// one alignment from host arguments added into a pileup (k_pileup; include/ffhip.h "pileup"): a map record, a truth record and a list entry made here
+extern "C" int ffhip_op_pileup(ffhip_engine *eng, ffhip_pileup *p, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops) {
+    OP_ENTER(eng);
+    if (!p || p->eng != eng || (n && !call) || !ops) return set_err(FFHIP_EINVAL, "bad pileup arguments (a pileup of this engine, a call of n letters, nops ops)");
+    const ffhip_map_ref *ref = p->ref;
+    if (q < 0 || q >= 2 * ref->view.nrec) return set_err(FFHIP_EINVAL, "pileup: search %d is not one of 0 .. %d", q, 2 * ref->view.nrec - 1);
+    const int mk = ref->rec_len[(size_t)q >> 1];
+    if (tstart < 0 || tend > mk || tstart >= tend) return set_err(FFHIP_EINVAL, "pileup: [%d, %d) is not a span of 1 or more of the record's %d bases", tstart, tend, mk);
+    if (n > (size_t)kTruthMaxLen || nops > (size_t)2 * kTruthMaxLen) return set_err(FFHIP_EINVAL, "pileup: a call of %zu bases and %zu ops (at most %d bases)", n, nops, kTruthMaxLen);
+    for (size_t i = 0; i < n; i++) if (!call[i] || !strchr("ACGTZ", call[i])) return set_err(FFHIP_EINVAL, "pileup: position %zu of the call: '%c' is not one of A C G T Z", i, call[i]);
+    const size_t m = (size_t)(tend - tstart);
+    size_t cnt[4] = { 0, 0, 0, 0 };
+    for (size_t k = 0; k < nops; k++) {
+        if (ops[k] > 3) return set_err(FFHIP_EINVAL, "pileup: op %zu: code %d is not one of 0 .. 3", k, (int)ops[k]);
+        cnt[ops[k]]++;
+    }
+    if (cnt[0] + cnt[1] + cnt[3] != m || cnt[0] + cnt[1] + cnt[2] != n)
+        return set_err(FFHIP_EINVAL, "pileup: the ops consume %zu truth and %zu call bases, the span has %zu and the call %zu", cnt[0] + cnt[1] + cnt[3], cnt[0] + cnt[1] + cnt[2], m, n);
+    ffhip_map_call mrec;
+    memset(&mrec, 0, sizeof mrec);
+    mrec.status = 1; mrec.n = (int)n; mrec.nanchor = 1; mrec.q = q; mrec.tstart = tstart; mrec.tend = tend;
+    const int trec[kTruthRecInts] = { 1, (int)n, (int)m, (int)(cnt[1] + cnt[2] + cnt[3]), (int)cnt[0], (int)cnt[1], (int)cnt[2], (int)cnt[3], 0, (int)nops, 0, 0 };
+    const TruthRead tr{ 0ull, 0ull, 0u, (int)m, 1, 0, (int)nops, 0 };
+    void *d_mrec = tmp.upload(&mrec, sizeof mrec, s);
+    int *d_trec = (int *)tmp.upload(trec, sizeof trec, s);
+    TruthRead *d_list = (TruthRead *)tmp.upload(&tr, sizeof tr, s);
+    uint8_t *d_ops = (uint8_t *)tmp.upload(ops, nops, s);
+    char *d_call = (char *)tmp.upload(n ? call : "", n ? n : 1, s);
+    if (!d_mrec || !d_trec || !d_list || !d_ops || !d_call) OP_NOMEM();
+    launch_pileup(s, ref->view, d_list, 1, d_mrec, d_trec, d_ops, d_call, n > 0 ? (int)n : 1, ReadMap(), p->view);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    HIP_TRY(hipGetLastError(), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+
 // one matrix of transition scores mapped to one sequence (k_remap; include/ffhip.h "remap")
 extern "C" int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, int band, uint8_t *rm, float *score) {
     OP_ENTER(eng);

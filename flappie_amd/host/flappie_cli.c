@@ -48,6 +48,7 @@
 #include "../../include/flappie_remap.h"
 #include "../../include/flappie_truth.h"
 #include "../../include/flappie_align.h"
+#include "../../include/flappie_pileup.h"
 #include "../../include/networks.h"
 
 const char *argp_program_version = "flappie (MI355X/HIP) 0.1, interface of flappie 2.1.3";
@@ -138,8 +139,12 @@ static struct argp_option options[] = {
     {"map-records", 289, "recs.fa", 0, "With --map: for every mapped read a FASTA record of its own stretch of the reference in signal order (reverse-complemented for the - strand): the file --remap takes in a second run (--truth too, which --truth-from-map spares)"},
     {"truth-from-map", 290, 0, 0, "With --map and --truth-out: align every mapped read's call to its own stretch of the reference in the same run, on the GPU, as --truth would in a second run with the file of --map-records. acc.tsv gets one line per mapped read: the thirteen columns of --truth-out with the read's name as in hits.tsv, then record, strand, tstart and tend as in hits.tsv; the CIGAR stays in signal order. --truth-band applies; not with --truth. stdout, hits.tsv and recs.fa do not change"},
     {"map-sam", 291, "aln.sam", 0, "With --truth-from-map: the alignments as a SAM file with @SQ lines: one line per read with a call, in output order; a read that is mapped and aligned with FLAG 0 or 16, POS, the CIGAR (=XID) in forward-strand order, SEQ (Z written as C) and QUAL turned to the forward strand and NM:i; every other read unmapped (FLAG 4). SEQ is always the whole call: --reverse, --trim-barcodes, --trim-adapters and --split-reads do not alter it"},
+    {"map-pileup", 292, "pileup.tsv", 0, "With --truth-from-map: per position of the reference, the aligned calls' counts, added up on the GPU over the whole run and written at its end: one line for every position of every record in reference order, no header: record, 0-based position, reference letter, depth (A, C, G, T and del of both strands), then A, C, G, T, del, ins of the + strand and of the - strand. An insertion stands at the position to its left on the forward strand; insertions before the first or behind the last aligned base are counted on stderr only (edge_ins). Inserted letters are not kept. The whole call counts: --reverse, --trim-barcodes, --trim-adapters and --split-reads do not alter it. stdout, hits.tsv, acc.tsv and aln.sam do not change"},
+    {"map-pileup-min-identity", 293, "permille", 0, "With --map-pileup: count only reads whose alignment's identity, matches over matches + mismatches + insertions + deletions, is at least this many thousandths (0-1000, default 0); the others are counted as skipped"},
 #endif
 #ifdef BUILD_RUNNIE
+    {"map-pileup", 292, "pileup.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-pileup-min-identity", 293, "permille", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map", 285, "ref.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-out", 286, "hits.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-window", 287, "W", OPTION_HIDDEN, "(flappie's option: refused here)"},
@@ -235,6 +240,9 @@ static bool map_opts = false;
 /* flappie: --truth-from-map and the file of --map-sam (runnie: seen, to be refused) */
 static bool tfm_on = false;
 static char *tfm_sam_path = NULL;
+/* flappie: the file of --map-pileup and --map-pileup-min-identity (-1: not given) (runnie: seen, to be refused) */
+static char *pu_path = NULL;
+static int pu_min_identity = -1;
 static int map_window = -1;
 #ifndef BUILD_RUNNIE
 static int map_max_error = -1;
@@ -403,6 +411,14 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
     case 289: map_recs_path = arg; map_opts = true; break;
     case 290: tfm_on = true; break;
     case 291: tfm_sam_path = arg; break;
+    case 292: pu_path = arg; break;
+    case 293: {
+        char *end = NULL;
+        const long v = strtol(arg, &end, 10);
+        if (end == arg || *end != '\0' || v < 0 || v > 1000) errx(EXIT_FAILURE, "--map-pileup-min-identity must be a whole number from 0 to 1000");
+        pu_min_identity = (int)v;
+        break;
+    }
 #ifdef BUILD_RUNNIE
     case 287: case 288: map_opts = true; break;
     case 270: case 271: case 272: case 273: case 274: ad_opts = true; break;
@@ -773,12 +789,15 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
     return ffhip_batch_run(b, args.temperature, flags);
 }
 #else
+/* flappie --map-pileup: the one pileup of the run, attached to every batch object and downloaded once at the end; its table */
+static ffhip_pileup *pu_dev = NULL;
+static FILE *pu_out = NULL;
 /* --modbase-tags: the 5mC bytes of the called bases come from the device (FFHIP_RUN_MOD_PROBS); --emit-moves: the move table does (FFHIP_RUN_MOVES);
  * --barcodes: the reads' barcode records do (FFHIP_RUN_BARCODES); --adapters: their adapter records (FFHIP_RUN_ADAPTERS); --poly-tail: their poly tail
  * records (FFHIP_RUN_POLYTAIL) */
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u) |
-           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (mp_dev ? FFHIP_RUN_MAP : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | ((tr_refs || tfm_on) ? FFHIP_RUN_TRUTH : 0u) |
+           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (mp_dev ? FFHIP_RUN_MAP : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | ((tr_refs || tfm_on) ? FFHIP_RUN_TRUTH : 0u) | (pu_dev ? FFHIP_RUN_PILEUP : 0u) |
            (ev_out ? FFHIP_RUN_EVENTS : 0u) | (md_out ? FFHIP_RUN_REMAP_MODS : 0u) | (vr_out ? FFHIP_RUN_REMAP_VARIANTS : 0u);
 }
 /* --remap: every read's record, by its read id, then by its file's base name; a bad record goes as a sequence of no bases (status 2) */
@@ -845,6 +864,7 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
     if (rm_refs) { const int rc = batch_set_remap(b, its, n); if (rc) return rc; }
     if (tr_refs) { const int rc = batch_set_truth(b, its, n); if (rc) return rc; }
     if (tfm_on) { const int rc = ffhip_batch_set_truth_from_map(b, 1, args.truth_band); if (rc) return rc; }
+    if (pu_dev) { const int rc = ffhip_batch_set_pileup(b, pu_dev); if (rc) return rc; }
     return ffhip_batch_run(b, args.temperature, flags);
 }
 #endif
@@ -2180,6 +2200,7 @@ int main(int argc, char *argv[]) {
     if (args.remap) errx(EXIT_FAILURE, "--remap is flappie's: the run-length model's scores are not transitions between the bases of a sequence");
     if (args.truth) errx(EXIT_FAILURE, "--truth is flappie's: the run-length model's call is a list of runs");
     if (tfm_on || tfm_sam_path) errx(EXIT_FAILURE, "--truth-from-map and --map-sam are flappie's: the run-length model's call is a list of runs");
+    if (pu_path || pu_min_identity >= 0) errx(EXIT_FAILURE, "--map-pileup and --map-pileup-min-identity are flappie's: the run-length model's call is a list of runs");
     if (args.remap_events) errx(EXIT_FAILURE, "--remap-events is flappie's: it goes with --remap, which the run-length model does not have");
     if (mods_path) errx(EXIT_FAILURE, "--remap-mods is flappie's: it goes with --remap, which the run-length model does not have");
     if (vars_path || vars_out_path || vars_opts) errx(EXIT_FAILURE, "--remap-variants is flappie's: it goes with --remap, which the run-length model does not have");
@@ -2222,6 +2243,8 @@ int main(int argc, char *argv[]) {
     if (tfm_on && NULL != args.truth) errx(EXIT_FAILURE, "--truth-from-map does not go with --truth: a call is aligned to one truth, the file's record or the mapped stretch");
     if (tfm_on && NULL == args.truth_out) errx(EXIT_FAILURE, "--truth-from-map and --truth-out go together");
     if (tfm_sam_path && !tfm_on) errx(EXIT_FAILURE, "--map-sam goes with --truth-from-map");
+    if (pu_path && !tfm_on) errx(EXIT_FAILURE, "--map-pileup goes with --truth-from-map: it counts what the alignments say");
+    if (pu_min_identity >= 0 && NULL == pu_path) errx(EXIT_FAILURE, "--map-pileup-min-identity goes with --map-pileup");
     if (map_path) {
         char why[256];
         mp_ref = flappie_map_ref_read(map_path, why, sizeof why);
@@ -2268,6 +2291,7 @@ int main(int argc, char *argv[]) {
             if (NULL == (tfm_sam = fopen(tfm_sam_path, "w"))) errx(EXIT_FAILURE, "--map-sam %s: cannot be written", tfm_sam_path);
             flappie_align_write_sam_header(tfm_sam, mp_ref);
         }
+        if (pu_path && NULL == (pu_out = fopen(pu_path, "w"))) errx(EXIT_FAILURE, "--map-pileup %s: cannot be written", pu_path);
     }
     if (args.truth) {
         char why[256];
@@ -2317,6 +2341,10 @@ int main(int argc, char *argv[]) {
     if (mp_ref && NULL == (mp_dev = ffhip_map_ref_upload(eng, mp_ref->n, (const char *const *)mp_ref->seq))) {
         stop_reader_procs();
         errx(EXIT_FAILURE, "--map: %s", ffhip_last_error());
+    }
+    if (pu_out && NULL == (pu_dev = ffhip_pileup_create(eng, mp_dev, pu_min_identity))) {
+        stop_reader_procs();
+        errx(EXIT_FAILURE, "--map-pileup: %s", ffhip_last_error());
     }
 #endif
     hid_t hdf5out = open_or_create_hdf5(args.trace);
@@ -2392,6 +2420,20 @@ int main(int argc, char *argv[]) {
                 ad_reads_with_hit, ad_stats[0], ad_stats[1], ad_stats[2], ad_stats[3]);
         ffhip_adapters_free(ad_dev);
         flappie_adapter_kit_free(ad_kit);
+    }
+    if (pu_dev) {                      /* the table, once: every batch object is gone, so every accumulation is done; reads counted and skipped, positions, those covered, the ops */
+        const size_t P = ffhip_pileup_positions(pu_dev);
+        uint32_t *counts = malloc((P ? P : 1) * FFHIP_PILEUP_PLANES * sizeof *counts);
+        ffhip_pileup_totals tot;
+        unsigned long long covered = 0;
+        if (NULL == counts || 0 != ffhip_pileup_download(pu_dev, counts, &tot)) warnx("--map-pileup: %s", counts ? ffhip_last_error() : "out of memory for the table");
+        else {
+            flappie_pileup_write(pu_out, mp_ref, counts, &covered);
+            flappie_pileup_summary_print(stderr, &tot, (unsigned long long)P, covered);
+        }
+        free(counts);
+        if (0 != fclose(pu_out)) warnx("--map-pileup %s: write failed", pu_path);
+        ffhip_pileup_free(pu_dev);
     }
     if (mp_ref) {                      /* reads, mapped, unmapped, discordant; the mapped reads' anchor distances over their anchor bases */
         flappie_map_summary_print(stderr, &mp_sum);

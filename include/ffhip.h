@@ -147,6 +147,12 @@ typedef struct {
  * where the result block's copy is.  Everything else the run returns is that of the same run without the flag.  No reference attached, the run-length model, or
  * FFHIP_RUN_NO_DECODE with it: FFHIP_EINVAL. */
 #define FFHIP_RUN_MAP        4194304u
+/* With FFHIP_RUN_MAP | FFHIP_RUN_TRUTH in the mode of ffhip_batch_set_truth_from_map: every aligned read's counts added, per reference position, into the pileup
+ * attached with ffhip_batch_set_pileup ("pileup" below) -- on the device (k_pileup), as the last step of ffhip_batch_finish, from the records the caller reads.
+ * Nothing comes down per read and the batch holds nothing new: the counters are the pileup's (ffhip_debug_batch_device_bytes does not change).  Everything the run
+ * returns is that of the same run without the flag.  Without FFHIP_RUN_TRUTH, without FFHIP_RUN_MAP, outside the mode, with no pileup attached or with a pileup of
+ * another reference than the batch's: FFHIP_EINVAL with a text that says which. */
+#define FFHIP_RUN_PILEUP     8388608u
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -764,6 +770,48 @@ int ffhip_debug_truth_form(size_t window);
 int ffhip_batch_set_truth_from_map(ffhip_batch *b, int on, int band);
 int ffhip_op_map_stretch(ffhip_engine *eng, const ffhip_map_ref *ref, int q, int start, int end, uint8_t *codes /* end - start */);
 long long ffhip_debug_map_truth_bound(int nblock, int max_error);
+/* Pileup: per reference position, how many aligned calls cover it and what they say there, added up over all the reads of all the batches it is attached to
+ * (tests/pileup_ref.py restates this).  The first product here that is not a per-read record: integer adds commute, so the counters are the same bytes whatever
+ * the batch size, packing, pairing or read order.
+ *   A pileup belongs to one ffhip_map_ref of K records of M_k bases.  off_k = the sum of the lengths before record k, P = the sum of all (at most 2^20).
+ *   Counters: 12 planes of P uint32, [strand o][column c][position]: o = 0 (+) or 1 (-); c = 0 .. 3 the base A C G T, 4 del, 5 ins.  Eight uint64 totals:
+ *     reads, skipped, match, mismatch, del, ins, edge_ins, and one reserved word that stays 0.
+ *   Which reads count: a read of a finished batch whose map record has status 1, whose truth record has status 1 and for which, in 64-bit integers,
+ *     1000 n_match >= min_identity (n_match + n_mismatch + n_ins + n_del); min_identity in per mille, 0 .. 1000, fixed at creation.  A read with both statuses 1
+ *     that fails the test adds 1 to `skipped` and nothing else; any other read adds nothing.
+ *   What a counted read adds: q = 2 k + o and the span [tstart, tend) of its map record, m = tend - tstart; its call s of n letters in signal order (Z read as C,
+ *     codes A 0, C 1, G 2, T 3); the K ops of its truth record.  reads += 1; then the ops from (0, 0), j the truth and i the call bases consumed so far:
+ *       '=' (0) or 'X' (1): f = o ? M_k - 1 - (tstart + j) : tstart + j; base = o ? 3 - code(s_i) : code(s_i); count[o][base][off_k + f] += 1; match or mismatch
+ *         += 1; j++, i++.
+ *       'D' (3): f as above; count[o][4][off_k + f] += 1; del += 1; j++.
+ *       'I' (2): 1 <= j <= m - 1: the inserted base lies between two aligned positions and is counted at the one to its LEFT on the forward strand:
+ *         p = o ? M_k - 1 - tstart - j : tstart + j - 1; count[o][5][off_k + p] += 1; ins += 1.  j = 0 or j = m: an edge insertion, a clip in spirit:
+ *         edge_ins += 1 and no plane changes.  Both: i++.
+ *     An op's contribution depends on the op, j and i alone, so the kernel takes an op a thread with j and i from prefix counts.
+ *   Counters wrap at 2^32 (the totals at 2^64); there is no guard.  Inserted letters are not kept.
+ *   When: as the last step of a successful ffhip_batch_finish of a run with FFHIP_RUN_PILEUP -- behind the f32 re-runs of saturated reads, which patch the records,
+ *     and in the innermost finish when the batch went again on the launch-per-step kernels -- so every read counts once, from the records ffhip_batch_map,
+ *     ffhip_batch_truth and ffhip_batch_basecall return.  The kernel is enqueued on the batch's stream and nothing waits for it; the batch's next run is ordered
+ *     behind it.  A batch's internal side batch never counts.
+ * ffhip_pileup_create: zeroed counters on the engine's device; min_identity < 0 means 0, > 1000: NULL with a text.  The reference must outlive the pileup, and the
+ *   pileup every batch it is attached to.
+ * ffhip_pileup_free / _reset / _download wait for every accumulation enqueued against the pileup by any batch; download then makes one copy for the planes
+ *   (counts: [12][P], may be NULL) and one for the totals (may be NULL).  ffhip_pileup_positions: P.
+ * ffhip_batch_set_pileup: the pileup of the batch's later runs with FFHIP_RUN_PILEUP; NULL detaches.  A pileup of another engine, the run-length model, or a call
+ *   between a run and its finish: FFHIP_EINVAL.
+ * ffhip_op_pileup: the kernel on ONE alignment from host arguments, added into p.  q, tstart or tend outside the record (the rule of ffhip_op_map_stretch), a
+ *   letter outside A C G T Z, an op above 3, or ops that do not consume exactly tend - tstart truth bases and n call bases: FFHIP_EINVAL, and nothing is added.
+ *   The identity test applies: an alignment below min_identity adds 1 to `skipped`. */
+typedef struct ffhip_pileup ffhip_pileup;
+typedef struct { uint64_t reads, skipped, match, mismatch, del, ins, edge_ins, reserved; } ffhip_pileup_totals;      /* 64 bytes */
+#define FFHIP_PILEUP_PLANES 12
+ffhip_pileup *ffhip_pileup_create(ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity);
+void ffhip_pileup_free(ffhip_pileup *p);
+int ffhip_pileup_reset(ffhip_pileup *p);
+size_t ffhip_pileup_positions(const ffhip_pileup *p);
+int ffhip_pileup_download(ffhip_pileup *p, uint32_t *counts /* [12][P] */, ffhip_pileup_totals *totals);
+int ffhip_batch_set_pileup(ffhip_batch *b, ffhip_pileup *p);
+int ffhip_op_pileup(ffhip_engine *eng, ffhip_pileup *p, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops);
 int ffhip_runlength_viterbi(ffhip_engine *eng, ffhip_mat param, int *path /* nblock */, float *score);
 /* decoders of the first-generation head on [4 nbase x nblock] matrices: decode_runlength (decode.c:694-767), posterior_runlength
  * (decode.c:793-892; post is [4 nbase x nblock + 1]), runlengths_mean (decode.c:576-603) */
