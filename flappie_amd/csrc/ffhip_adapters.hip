@@ -6,7 +6,7 @@
 // leftmost minimum of d_q within 64 columns either way; the hit's start is the largest i with ed(p, x[i:j]) = d_q[j].  All of it is integer arithmetic: exact.
 //
 // k_adapters: one workgroup a read, four waves, ONE SEARCH A LANE.  A lane holds its search's column as vertical differences in one 64-bit word (Myers' recurrence
-// in Hyyro's form, as k_barcodes) and the four match masks of its oriented pattern in registers, and follows d at bit L - 1.  A call of 50 000 bases must not be
+// in Hyyro's form: myers_step, ffhip_seq.hpp) and the four match masks of its oriented pattern in registers, and follows d at bit L - 1.  A call of 50 000 bases must not be
 // one wave's chain, so the text is cut into SEGMENTS of kAdSeg = FFHIP_ADAPTER_SEGMENT columns: segment g owns the hit ends j in (g S, (g + 1) S].  The waves take
 // the segments in turn, four a ROUND.  The wave of a segment starts a fresh search (D[i][a] = i) 192 columns before it: d_q[j] <= L and an optimal match spans at
 // most L + d <= 128 columns, so the fresh search is exact from column a + 128 on, which leaves 64 exact columns before the segment for the hit rule; it runs on
@@ -24,6 +24,7 @@
 //         over the round's four counts and the read's running total, and 60 threads store the hits that fall into the record's 15 slots: one 16-byte store a hit,
 //         one for the header.  No atomics.
 #include "ffhip_internal.hpp"
+#include "ffhip_seq.hpp"
 
 namespace ffhip {
 
@@ -34,14 +35,6 @@ constexpr int kAdText = kAdWaves * kAdSeg + kAdWarm + kAdReach;  // characters s
 static_assert(kAdSeg % kAdTile == 0 && kAdWarm % kAdTile == 0 && kAdReach == kAdTile && kAdWarm >= 128 + kAdReach, "whole tiles; exact d 64 columns before a segment");
 static_assert(kAdReach == 64, "the differences of 64 columns a word: one word pair behind the tested column, one before it");
 static_assert(kAdText % 16 == 0 && kAdapterMaxKit * 2 == 64 && kAdapterMaxLen == 64 && kAdapterMaxHits == 15, "a search a lane, a pattern a word, a record of 16 stores");
-
-__device__ __forceinline__ unsigned ad_code(char c) { return c == 'A' ? 0u : c == 'G' ? 2u : c == 'T' ? 3u : 1u; }      // C and Z: 1 (the call holds A C G T Z only)
-
-__device__ __forceinline__ int ad_wave_min(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(v, d, 64); v = o < v ? o : v; }
-    return v;
-}
 
 // the hit rule at column j with d[j] = v0: (bp, bm) hold the differences d[j - i] - d[j - i - 1] at bit i (the columns before), (ap, am) the differences
 // d[j + 64 - i] - d[j + 63 - i] at bit i (the columns behind): strictly below the 64 columns before, not above the 64 behind, within [0, len]
@@ -69,13 +62,7 @@ __device__ __forceinline__ int ad_start(const unsigned long long peq[4], int L, 
     while (score != d && c < j && c < 2 * kAdapterMaxLen) {
         const int idx = j - 1 - c - t0;
         const unsigned ch = (text[idx >> 4] >> (2 * (idx & 15))) & 3u;
-        const unsigned long long Eq = ch == 0 ? rp[0] : ch == 1 ? rp[1] : ch == 2 ? rp[2] : rp[3];
-        const unsigned long long Xv = Eq | mv, Xh = (((Eq & pv) + pv) ^ pv) | Eq;
-        unsigned long long Ph = mv | ~(Xh | pv), Mh = pv & Xh;
-        score += (int)((Ph >> (L - 1)) & 1ull) - (int)((Mh >> (L - 1)) & 1ull);
-        Ph = (Ph << 1) | 1ull; Mh <<= 1;                 // D[0][c] = c: +1 enters at bit 0
-        pv = Mh | ~(Xv | Ph);
-        mv = Ph & Xv;
+        score += myers_diff(myers_step(pv, mv, myers_eq(rp, ch), 1), L - 1);      // D[0][c] = c: +1 enters at bit 0
         c++;
     }
     return j - c;
@@ -116,7 +103,7 @@ k_adapters(AdapterKit kit, const char *__restrict__ bases, const int *__restrict
 #pragma unroll
             for (int e = 0; e < 16; e++) {
                 const int i = t0 + 16 * w + e;
-                if (i >= 0 && i < len) v |= ad_code(bs[i]) << (2 * e);
+                if (i >= 0 && i < len) v |= seq_code(bs[i]) << (2 * e);
             }
             text[w] = v;
         }
@@ -138,14 +125,9 @@ k_adapters(AdapterKit kit, const char *__restrict__ bases, const int *__restrict
 #pragma unroll
                     for (int i = 0; i < 16; i++) {
                         const unsigned c = (chars >> (2 * i)) & 3u;
-                        const unsigned long long Eq = c == 0 ? peq[0] : c == 1 ? peq[1] : c == 2 ? peq[2] : peq[3];
-                        const unsigned long long Xv = Eq | mv, Xh = (((Eq & pv) + pv) ^ pv) | Eq;
-                        unsigned long long Ph = mv | ~(Xh | pv), Mh = pv & Xh;
-                        const unsigned long long up = (Ph >> topb) & 1ull, dn = (Mh >> topb) & 1ull;
+                        const MyersH h = myers_step(pv, mv, myers_eq(peq, c), 0);      // D[0][j] = 0: nothing enters at bit 0
+                        const unsigned long long up = (h.Ph >> topb) & 1ull, dn = (h.Mh >> topb) & 1ull;
                         score += (int)up - (int)dn;
-                        Ph <<= 1; Mh <<= 1;              // D[0][j] = 0: nothing enters at bit 0
-                        pv = Mh | ~(Xv | Ph);
-                        mv = Ph & Xv;
                         hp1 = (hp1 << 1) | (hp0 >> 63); hm1 = (hm1 << 1) | (hm0 >> 63);
                         hp0 = (hp0 << 1) | up; hm0 = (hm0 << 1) | dn;
                         lag += (int)(hp1 & 1ull) - (int)(hm1 & 1ull);      // d[t - 64], t = c0 + 16 g + i + 1 this column
@@ -155,7 +137,7 @@ k_adapters(AdapterKit kit, const char *__restrict__ bases, const int *__restrict
                     }
                 }
                 for (;;) {                               // the hit columns of the tile before in ascending order, the lanes of a column in theirs: (end, q)
-                    const int cm = ad_wave_min(hitj);
+                    const int cm = wave_min(hitj);
                     if (cm == 0x7fffffff) break;
                     const bool mine = hitj == cm;
                     const unsigned long long bal = __ballot(mine);

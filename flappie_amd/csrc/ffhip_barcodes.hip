@@ -4,8 +4,8 @@
 // its reverse complement.  Every pattern is searched in both by the infix edit distance (edlib's HW mode): D[0][j] = 0, D[i][0] = i, unit costs,
 // dist = min_j D[L][j], end = the smallest j that attains it.  All of it is integer arithmetic: the results are exact.
 //
-// k_barcodes: one workgroup a read, 256 threads = 2 ends x 128 patterns, ONE PATTERN A LANE.  Myers' bit-vector recurrence (J. ACM 46:395, in Hyyro's form with
-// a horizontal carry between words, as edlib's calculateBlock) holds a column of the matrix as vertical differences in one 64-bit word a lane, two when the
+// k_barcodes: one workgroup a read, 256 threads = 2 ends x 128 patterns, ONE PATTERN A LANE.  Myers' bit-vector recurrence (in Hyyro's form with
+// a horizontal carry between words: myers_step, ffhip_seq.hpp) holds a column of the matrix as vertical differences in one 64-bit word a lane, two when the
 // kit has a pattern longer than 64 (the carry out of bit 63 of the first enters the second).  The pattern's match masks Peq[4] stay in registers.  The window's
 // characters are staged once in LDS as codes 0 .. 3, the rear window read from the call's end and complemented; the two waves of an end read the same
 // character at every step (a broadcast), so lanes differ only in the bit that is their pattern's last row.  Bits above that row hold garbage that never
@@ -13,20 +13,13 @@
 // differences at its top bit and keeps the first minimum.  The two distances of every pattern go through LDS to the first wave, which finds the minimum
 // (lowest index first) and the runner-up by two butterfly reductions and writes the read's 16-byte record: nothing else leaves the kernel.
 #include "ffhip_internal.hpp"
+#include "ffhip_seq.hpp"
 
 namespace ffhip {
 
 constexpr int kBcThreads = 2 * kBarcodeMaxKit;
 constexpr int kBcNone = 1000;                   // beyond every distance (<= 128): a lane without a pattern
 static_assert(kBarcodeMaxKit == 128 && kBarcodeMaxLen == 128 && kBarcodeMaxWindow % 4 == 0, "two words a pattern, four waves a read, windows staged as whole words");
-
-__device__ __forceinline__ unsigned bc_code(char c) { return c == 'A' ? 0u : c == 'G' ? 2u : c == 'T' ? 3u : 1u; }      // C and Z: 1 (the call holds A C G T Z only)
-
-__device__ __forceinline__ int bc_wave_min(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(v, d, 64); v = o < v ? o : v; }
-    return v;
-}
 
 template <int NW>
 __global__ void __launch_bounds__(kBcThreads)
@@ -45,17 +38,17 @@ k_barcodes(BarcodeKit kit, const char *__restrict__ bases, const int *__restrict
     const int m = len < kit.window ? len : kit.window;
     const char *bs = bases + map.row1(read, TbS);
     for (int j = tid; j < 2 * m; j += kBcThreads)        // front: s[j]; rear: the complement of s[len - 1 - j]
-        if (j < m) win[0][j] = (uint8_t)bc_code(bs[j]);
-        else win[1][j - m] = (uint8_t)(3u - bc_code(bs[len - 1 - (j - m)]));
+        if (j < m) win[0][j] = (uint8_t)seq_code(bs[j]);
+        else win[1][j - m] = (uint8_t)(3u - seq_code(bs[len - 1 - (j - m)]));
     __syncthreads();
     const int end = tid / kBarcodeMaxKit, k = tid % kBarcodeMaxKit;      // waves 0, 1: the front; 2, 3: the rear
     const bool live = k < kit.n;
-    unsigned long long peq[4][NW], pv[NW], mv[NW];
+    unsigned long long peq[NW][4], pv[NW], mv[NW];
     const int L = live ? kit.len[k] : 1;
 #pragma unroll
     for (int c = 0; c < 4; c++)
 #pragma unroll
-        for (int w = 0; w < NW; w++) peq[c][w] = live ? kit.peq[((size_t)k * 4 + c) * 2 + w] : 0ull;
+        for (int w = 0; w < NW; w++) peq[w][c] = live ? kit.peq[((size_t)k * 4 + c) * 2 + w] : 0ull;
 #pragma unroll
     for (int w = 0; w < NW; w++) { pv[w] = ~0ull; mv[w] = 0ull; }
     const int topw = (L - 1) >> 6, topb = (L - 1) & 63;
@@ -70,17 +63,9 @@ k_barcodes(BarcodeKit kit, const char *__restrict__ bases, const int *__restrict
             int hin = 0, delta = 0;
 #pragma unroll
             for (int w = 0; w < NW; w++) {
-                unsigned long long Eq = c == 0 ? peq[0][w] : c == 1 ? peq[1][w] : c == 2 ? peq[2][w] : peq[3][w];
-                const unsigned long long Pv = pv[w], Mv = mv[w], Xv = Eq | Mv, neg = hin < 0 ? 1ull : 0ull, pos = hin > 0 ? 1ull : 0ull;
-                Eq |= neg;
-                const unsigned long long Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-                unsigned long long Ph = Mv | ~(Xh | Pv), Mh = Pv & Xh;
-                if (w == topw) delta = (int)((Ph >> topb) & 1ull) - (int)((Mh >> topb) & 1ull);
-                hin = (int)(Ph >> 63) - (int)(Mh >> 63);
-                Ph = (Ph << 1) | pos;
-                Mh = (Mh << 1) | neg;
-                pv[w] = Mh | ~(Xv | Ph);
-                mv[w] = Ph & Xv;
+                const MyersH h = myers_step(pv[w], mv[w], myers_eq(peq[w], c), hin);
+                if (w == topw) delta = myers_diff(h, topb);
+                hin = (int)(h.Ph >> 63) - (int)(h.Mh >> 63);
             }
             score += delta;
             if (score < best) { best = score; bend = j0 + i + 1; }      // the FIRST column of the minimum
@@ -100,12 +85,12 @@ k_barcodes(BarcodeKit kit, const char *__restrict__ bases, const int *__restrict
         const int kh = (s[h] << 8) | kk;
         key = kh < key ? kh : key;
     }
-    key = bc_wave_min(key);
+    key = wave_min(key);
     const int bi = key & 255, sb = key >> 8;
     int sec = kBcNone;
 #pragma unroll
     for (int h = 0; h < 2; h++) if (tid + 64 * h != bi && s[h] < sec) sec = s[h];
-    sec = bc_wave_min(sec);
+    sec = wave_min(sec);
     if (sec >= kBcNone) sec = 255;
     if (tid == 0) {
         const int df = sdist[0][bi], dr = sdist[1][bi], ef = send[0][bi], er = send[1][bi];

@@ -12,18 +12,13 @@
 //   Both passes are fp64 -- the mean, then the squared distances from it -- and each result is rounded to float32 once.  The order of every sum is a function of the
 //   span's sample count alone: the same read gives the same bytes wherever it stands in a batch.  No atomics; a span of one repeated value has sd 0.0 exactly.
 #include "ffhip_internal.hpp"
+#include "ffhip_seq.hpp"
 #include <math.h>
 
 namespace ffhip {
 
 constexpr int kEvNT = 256;              // threads of a workgroup: blocks a round of the scan, bases a round of the events
 constexpr int kEvLane = 32;             // samples a thread reduces alone; a longer span is its wave's
-
-__device__ __forceinline__ double ev_wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = v + __shfl_xor(v, d, 64);
-    return v;
-}
 
 __global__ void __launch_bounds__(kEvNT)
 k_events(const EventRead *__restrict__ list, const float *__restrict__ sig, int stride, const uint4 *__restrict__ rec, const uint8_t *__restrict__ rm,
@@ -88,9 +83,9 @@ k_events(const EventRead *__restrict__ list, const float *__restrict__ sig, int 
             const float *p = x + sj;
             double a = 0.0, q = 0.0;
             for (int k = lane; k < cj; k += 64) a = a + (double)p[k];
-            const double mu = ev_wave_sum(a) / (double)cj;
+            const double mu = wave_sum(a) / (double)cj;
             for (int k = lane; k < cj; k += 64) { const double d = (double)p[k] - mu; q = q + d * d; }
-            const double dev = sqrt(ev_wave_sum(q) / (double)cj);
+            const double dev = sqrt(wave_sum(q) / (double)cj);
             if (lane == j) { mean = mu; sd = dev; }
         }
         if (tid < nb) ev[i0 + tid] = make_int4(s, cnt, __float_as_int((float)mean), __float_as_int((float)sd));

@@ -5,7 +5,7 @@
 // min(n, W) letters of a call in signal order, Z read as C: L <= 4096 rows, so up to 64 words of 64 rows.  d_{a,q}[j] = D[L][j] of the infix edit distance
 // (D[0][j] = 0, D[i][0] = i, unit costs).  All of it is integer arithmetic: exact.
 //
-// k_map_scan: Myers' recurrence in Hyyro's block form, as k_adapters, over MANY words.  Word w of an anchor is worked by lane w of a LANE GROUP of G lanes, G the
+// k_map_scan: Myers' recurrence in Hyyro's block form (myers_step, ffhip_seq.hpp) over MANY words.  Word w of an anchor is worked by lane w of a LANE GROUP of G lanes, G the
 // next power of two >= ceil(L / 64): a wave holds 64 / G tasks.  Lane w is one column behind lane w - 1: at step t it works column t - w, and the horizontal
 // difference (-1, 0, +1) that left word w - 1 at that column a step ago enters it through a lane shuffle, the column's letter with it (two bits more of the same
 // word) -- only lane 0 of a group reads the reference, 16 letters a load, the next load under way while these are worked.  Nothing goes through LDS or memory.
@@ -21,12 +21,11 @@
 // k_map_stretch (include/ffhip.h "truth from map"): one wave an entry of truth's read list, behind k_map_finish: the mapped read's stretch of the reference as codes
 //   where k_truth reads its truth, and the entry's length and status patched.  Its own comment stands in front of it.
 #include "ffhip_internal.hpp"
+#include "ffhip_seq.hpp"
 
 namespace ffhip {
 
 static_assert(kMapMaxAnchor == 64 * 64 && (kMapSeg % 16) == 0 && kMapPad == 16, "an anchor is at most a wave of words; letters are read 16 a word");
-
-__device__ __forceinline__ unsigned map_code(char c) { return c == 'A' ? 0u : c == 'G' ? 2u : c == 'T' ? 3u : 1u; }      // C and Z: 1 (the call holds A C G T Z only)
 
 // 16 letters of a strand as 2-bit codes, the first in bits 0-1: those at g, g + 1, ... (dir > 0) or g, g - 1, ... (dir < 0) of the reference, complemented if comp.
 // g - 15 >= -kMapPad and g + 15 < total + kMapPad: the words hold a word of padding either side (map_ref_upload).
@@ -44,25 +43,10 @@ __device__ __forceinline__ void map_masks(const char *__restrict__ p, int L, int
     for (int i = 0; i < 64; i++) {
         const int r = 64 * w + i;
         if (r >= L) break;
-        const unsigned c = map_code(p[rev ? L - 1 - r : r]);
+        const unsigned c = seq_code(p[rev ? L - 1 - r : r]);
         const unsigned long long bit = 1ull << i;
         peq[0] |= c == 0 ? bit : 0ull; peq[1] |= c == 1 ? bit : 0ull; peq[2] |= c == 2 ? bit : 0ull; peq[3] |= c == 3 ? bit : 0ull;
     }
-}
-
-// one column of one word: the letter c, the difference hin (-1, 0, +1) entering at bit 0; returns the difference leaving at bit `top`
-__device__ __forceinline__ int map_step(unsigned long long &pv, unsigned long long &mv, const unsigned long long peq[4], unsigned c, int hin, int top) {
-    unsigned long long Eq = c == 0 ? peq[0] : c == 1 ? peq[1] : c == 2 ? peq[2] : peq[3];
-    const unsigned long long neg = hin < 0 ? 1ull : 0ull, pos = hin > 0 ? 1ull : 0ull;
-    const unsigned long long Xv = Eq | mv;
-    Eq |= neg;
-    const unsigned long long Xh = (((Eq & pv) + pv) ^ pv) | Eq;
-    unsigned long long Ph = mv | ~(Xh | pv), Mh = pv & Xh;
-    const int hout = (int)((Ph >> top) & 1ull) - (int)((Mh >> top) & 1ull);
-    Ph = (Ph << 1) | pos; Mh = (Mh << 1) | neg;
-    pv = Mh | ~(Xv | Ph);
-    mv = Ph & Xv;
-    return hout;
 }
 
 __device__ __forceinline__ int map_anchor_len(int n, int window) { return n < window ? n : window; }
@@ -111,7 +95,7 @@ k_map_scan(MapRefView ref, const char *__restrict__ bases, const int *__restrict
                 if (have && col >= 0 && col < ncol) {
                     const unsigned c = w == 0 ? (cur >> (2 * i)) & 3u : (unsigned)in >> 2;
                     const int hin = w == 0 ? 0 : (in & 3) - 1;
-                    const int hout = map_step(pv, mv, peq, c, hin, last ? top : 63);
+                    const int hout = myers_diff(myers_step(pv, mv, myers_eq(peq, c), hin), last ? top : 63);      // what leaves the word, or its last row
                     carry = (hout + 1) | (int)(c << 2);
                     if (last) {
                         score += hout;
@@ -127,16 +111,6 @@ k_map_scan(MapRefView ref, const char *__restrict__ bases, const int *__restrict
         }
         if (have && last) myslots[task] = make_int2(bd, bj);
     }
-}
-
-__device__ __forceinline__ unsigned long long map_wave_min64(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, d, 64), hi = __shfl_xor((unsigned)(v >> 32), d, 64);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        v = o < v ? o : v;
-    }
-    return v;
 }
 
 // start of the place (q, j, d) of the anchor p of L letters: the reversed anchor against y_q[j-1], y_q[j-2], ... from an anchored start, until D[L][c] = d; one
@@ -161,7 +135,7 @@ __device__ __forceinline__ int map_start(const MapRefView &ref, const char *__re
             if (!idle && col >= 0 && col < ncol) {
                 const unsigned c = w == 0 ? (cur >> (2 * i)) & 3u : (unsigned)in >> 2;
                 const int hin = w == 0 ? 1 : (in & 3) - 1;
-                const int hout = map_step(pv, mv, peq, c, hin, last ? top : 63);
+                const int hout = myers_diff(myers_step(pv, mv, myers_eq(peq, c), hin), last ? top : 63);      // what leaves the word, or its last row
                 carry = (hout + 1) | (int)(c << 2);
                 if (last) {
                     score += hout;
@@ -198,12 +172,12 @@ k_map_finish(MapRefView ref, const char *__restrict__ bases, const int *__restri
             const unsigned long long k = ((unsigned long long)(unsigned)sl[t].x << 32) | (unsigned)t;
             key = k < key ? k : key;
         }
-        key = map_wave_min64(key);
+        key = wave_min(key);
         const int bt = (int)(unsigned)key, d = (int)(key >> 32), q = ref.tasks[bt].q, j = sl[bt].y;
         unsigned long long k2 = ~0ull;
         for (int t = lane; t < ref.ntask; t += 64)
             if (ref.tasks[t].q != q) { const unsigned long long k = (unsigned long long)(unsigned)sl[t].x; k2 = k < k2 ? k : k2; }
-        k2 = map_wave_min64(k2);
+        k2 = wave_min(k2);
         aq[a] = q; ae[a] = j; ad[a] = d; a2[a] = (int)k2;
         as[a] = map_start(ref, x + (a ? n - L : 0), L, q, j, d, lane);
     }

@@ -9,13 +9,12 @@
 // [strand][column][position], so the lanes of a wave that hit one plane hit consecutive words.  The totals are ballot popcounts kept by every wave, summed through
 // LDS at the end and added with one 64-bit atomic each.  256 threads, under 100 bytes of LDS, no scratch: it runs beside the next pair's layer launch as the decode does.
 #include "ffhip_internal.hpp"
+#include "ffhip_seq.hpp"
 
 namespace ffhip {
 
 constexpr int kPileupNT = 256, kPileupNW = kPileupNT / 64;
 enum { PT_READS = 0, PT_SKIPPED, PT_MATCH, PT_MISMATCH, PT_DEL, PT_INS, PT_EDGE_INS, PT_RESERVED };
-
-__device__ __forceinline__ int pu_code(char c) { return c == 'A' ? 0 : c == 'G' ? 2 : c == 'T' ? 3 : 1; }      // C and Z: 1, as k_truth reads the call
 
 __global__ void __launch_bounds__(kPileupNT)
 k_pileup(const int2 *__restrict__ recs, int nrec, const TruthRead *__restrict__ list, const uint4 *__restrict__ maprec, const int *__restrict__ trec,
@@ -67,7 +66,7 @@ k_pileup(const int2 *__restrict__ recs, int nrec, const TruthRead *__restrict__ 
         int col = -1, f = 0;
         if (diag || del) {
             f = o ? Mk - 1 - (ts + j) : ts + j;
-            const int c = (diag && i < n) ? pu_code(bs[i]) : 0;
+            const int c = (diag && i < n) ? (int)seq_code(bs[i]) : 0;      // C and Z: 1, as k_truth reads the call
             col = del ? 4 : (i < n ? (o ? 3 - c : c) : -1);
         } else if (inner) {
             f = o ? Mk - 1 - ts - j : ts + j - 1;

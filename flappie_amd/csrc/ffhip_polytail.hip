@@ -17,6 +17,7 @@
 //      sums in order), the tail's moves, the moves on the far side.  Thread 0 writes the record as two 16-byte stores.
 //   Every integer field and rate and bases are functions of the read alone; level's order is a function of the winner's windows alone.  No atomics.
 #include "ffhip_internal.hpp"
+#include "ffhip_seq.hpp"
 
 namespace ffhip {
 
@@ -37,21 +38,6 @@ const char *polytail_invalid(const PolyTailParams &p) {
 }
 
 __device__ __forceinline__ int pt_base(int state, int nbase) { const int c = state % nbase; return c == 4 ? 1 : c; }
-__device__ __forceinline__ int pt_wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ double pt_wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = v + __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ long long pt_wave_max(long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const long long o = __shfl_xor(v, d, 64); v = o > v ? o : v; }
-    return v;
-}
 
 __global__ void __launch_bounds__(kPtNT)
 k_polytail(const PolyRead *__restrict__ list, const float *__restrict__ sig, int stride, const int *__restrict__ path, int nbase, PolyTailParams p,
@@ -179,7 +165,7 @@ k_polytail(const PolyRead *__restrict__ list, const float *__restrict__ sig, int
             cstart = slast;
         }
     }
-    best = pt_wave_max(best);
+    best = wave_max(best);
     if (lane == 0) wkey[wv] = best;
     __syncthreads();
 #pragma unroll
@@ -197,7 +183,7 @@ k_polytail(const PolyRead *__restrict__ list, const float *__restrict__ sig, int
     for (int w = ws + tid; w < we; w += kPtNT) if (fl[w] & 1) { flat++; lv = lv + mus[w]; }
     for (int b = bs + tid; b < be; b += kPtNT) calls += b < N - 1 && pth[b + 1] != pth[b] && pt_base(pth[b + 1], nbase) == t;
     for (int b = (p.from_end ? 0 : be) + tid; b < (p.from_end ? bs : N); b += kPtNT) c += b < N - 1 && pth[b + 1] != pth[b];
-    flat = pt_wave_sum(flat); calls = pt_wave_sum(calls); c = pt_wave_sum(c); lv = pt_wave_sum(lv);
+    flat = wave_sum(flat); calls = wave_sum(calls); c = wave_sum(c); lv = wave_sum(lv);
     if (lane == 0) { isum[0][wv] = flat; isum[1][wv] = calls; isum[2][wv] = c; dsum[wv] = lv; }
     __syncthreads();
     if (tid == 0) {

@@ -2,7 +2,7 @@
 // the signal belong to which base of a sequence the caller already knows.
 //
 // The sequence s of L bases is flip-flop coded (q_i: a repeated base alternates between its flip and its flop state), a path p_0 = 0 .. p_N = L - 1 steps by 0 or 1
-// a block, and its score is the sum of the entries trans_lookup(q_from, q_to) (decode.c:104-114) of the blocks' score rows.  Cell (b, i) is allowed iff
+// a block, and its score is the sum of the entries ff_lookup(q_from, q_to) (ffhip_seq.hpp) of the blocks' score rows.  Cell (b, i) is allowed iff
 // |i - c(b)| <= W, c(b) = floor(b (L - 1) / N).  V_{b+1}[i] = move if move > stay (strictly) else stay, each ONE float32 add; include/ffhip.h holds the whole
 // statement and tests/remap_ref.py restates it.  The host codes the sequence when it copies it (remap_code): what reaches the device is, per position, the two
 // entries a block's row is read at -- stay (q_i -> q_i) in the low byte, move (q_{i-1} -> q_i) in the high byte.
@@ -18,6 +18,7 @@
 // Traceback: the same workgroup, behind a fence, brings the words back in chunks of 256 / K blocks (the chunk before prefetched in registers); thread 0
 // follows the bits from cell L - 1 -- the bit of cell i is bit (i mod S) / K mod 64 of word [wave][(i mod S) mod K] -- and the chunk's bytes go out together.
 #include "ffhip_internal.hpp"
+#include "ffhip_seq.hpp"
 #include <math.h>
 #include <algorithm>
 
@@ -36,13 +37,11 @@ int remap_max_window() { return kRemapNT[kRemapForms - 1] * kRemapK[kRemapForms 
 size_t remap_ws_words(int form, int nblock) { return (size_t)nblock * (size_t)(kRemapNT[form] / 64 * kRemapK[form]); }
 
 void remap_code(const uint8_t *codes, size_t L, int nbase, unsigned short *out) {
-    const int ns = 2 * nbase, off = nbase * ns;
-    auto lookup = [&](int from, int to) { return to < nbase ? to * ns + from : off + from; };      // trans_lookup, decode.c:104-114
     int prev = 0;
     for (size_t i = 0; i < L; i++) {
         const int s = codes[i];
         const int q = (i > 0 && s == codes[i - 1] && prev < nbase) ? s + nbase : s;
-        out[i] = (unsigned short)(lookup(q, q) | ((i > 0 ? lookup(prev, q) : 0) << 8));
+        out[i] = (unsigned short)(ff_lookup(q, q, nbase) | ((i > 0 ? ff_lookup(prev, q, nbase) : 0) << 8));
         prev = q;
     }
 }

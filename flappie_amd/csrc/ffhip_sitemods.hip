@@ -10,31 +10,21 @@
 //   value of BOTH hypotheses in registers.  The hypothesis' flip-flop states come from the coding of s that the batch holds: positions before i keep theirs, position
 //   i takes the letter with the flip or flop that q_{i-1} leaves it, and the positions behind it are recoded one after the other, in a loop that is uniform in the
 //   wave and ends where the coding meets that of s again (the end of the run of equal letters).  A lane then knows the (at most) four entries of a block's score row
-//   it reads: stay and move of either hypothesis.  A step is, per hypothesis, one cross-lane move (the value of the lane below), two adds and one compare (best
-//   path, float32) or one log1p(exp()) (all paths, fp64); the two hypotheses are independent chains and fill each other's latency.  The rows are read through the
-//   cache, kSmChunk blocks ahead of the chain in registers: no step waits for memory.  What bounds a step is the chain cross-lane move -> add -> compare.
+//   it reads: stay and move of either hypothesis, and window_scores (ffhip_seq.hpp) runs both through the window's blocks: best path in float32, all paths in fp64.
 //   The order of operations depends on the window alone: the same read gives the same bytes wherever it stands in a batch.  No atomics, no scratch.
 #include "ffhip_internal.hpp"
-#include <math.h>
-#include <type_traits>
+#include "ffhip_seq.hpp"
 
 namespace ffhip {
 
 constexpr int kSmNT = 256;              // threads of either kernel's workgroup
 constexpr int kSmWaves = kSmNT / 64;    // sites a workgroup
-constexpr int kSmChunk = 8;             // blocks whose entries a lane holds ahead of the chain
-constexpr int kSmNbase = 5, kSmNs = 2 * kSmNbase, kSmOff = kSmNbase * kSmNs;      // the model with a modified base: ACGTZ
-
-// the flip-flop state of a coded position (remap_code's low byte is trans_lookup(q, q))
-__host__ __device__ __forceinline__ int sm_state(unsigned short e) { const int st = e & 255; return st < kSmOff ? st / (kSmNs + 1) : st - kSmOff; }
-__device__ __forceinline__ int sm_lookup(int from, int to) { return to < kSmNbase ? to * kSmNs + from : kSmOff + from; }
-// the state a letter takes behind state `prev` (prev < 0: the sequence's first position)
-__device__ __forceinline__ int sm_next(int prev, int letter) { return (prev >= 0 && prev % kSmNbase == letter && prev < kSmNbase) ? letter + kSmNbase : letter; }
+constexpr int kSmNbase = 5;             // the model with a modified base: ACGTZ
 
 size_t sitemods_sites(const unsigned short *coded, size_t L, int k, std::vector<SiteMod> *out) {
     size_t n = 0;
     for (size_t i = 0; i < L; i++) {
-        const int letter = sm_state(coded[i]) % kSmNbase;
+        const int letter = ff_state<kSmNbase>(coded[i]) % kSmNbase;
         if (letter != 1 && letter != 4) continue;
         if (out) out->push_back(SiteMod{ k, (int)i });
         n++;
@@ -76,7 +66,6 @@ __global__ void __launch_bounds__(kSmNT)
 k_site_mods(const SiteRead *__restrict__ list, const SiteMod *__restrict__ sites, int nsite, const unsigned short *__restrict__ seq, const float *__restrict__ trans,
             int Ps, int ctx, const uint4 *__restrict__ rec, const int *__restrict__ starts, int4 *__restrict__ out, int TbS, const int *__restrict__ tbs, ReadMap map) {
     FFHIP_DECODE_PRIO_SET();
-    using real = typename std::conditional<ALL, double, float>::type;
     const int lane = threadIdx.x & 63, site = blockIdx.x * kSmWaves + (threadIdx.x >> 6);
     if (site >= nsite) return;                                                  // (a whole wave: the kernel has no barrier)
     const SiteMod sm = sites[site];
@@ -94,16 +83,16 @@ k_site_mods(const SiteRead *__restrict__ list, const SiteMod *__restrict__ sites
 
     // ---- the states of both hypotheses at this lane's position
     const int pos = lo + lane;
-    const int q0 = lane < P ? sm_state(sq[pos]) : 0;                            // the coding of s itself
-    const int qb = i > 0 ? sm_state(sq[i - 1]) : -1;
+    const int q0 = lane < P ? ff_state<kSmNbase>(sq[pos]) : 0;                            // the coding of s itself
+    const int qb = i > 0 ? ff_state<kSmNbase>(sq[i - 1]) : -1;
     int q[2];
 #pragma unroll
     for (int h = 0; h < 2; h++) {
-        int prev = sm_next(qb, h ? 4 : 1);
+        int prev = ff_next<kSmNbase>(qb, h ? 4 : 1);
         int mine = pos == i ? prev : q0;
         for (int p = i + 1; p <= hi; p++) {                                     // (uniform in the wave)
             const int orig = __shfl(q0, p - lo, 64);
-            const int now = sm_next(prev, orig % kSmNbase);
+            const int now = ff_next<kSmNbase>(prev, orig % kSmNbase);
             if (now == orig) break;                                             // the coding of s from here on
             mine = pos == p ? now : mine;
             prev = now;
@@ -114,46 +103,12 @@ k_site_mods(const SiteRead *__restrict__ list, const SiteMod *__restrict__ sites
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         const int below = __shfl_up(q[h], 1, 64);
-        is[h] = sm_lookup(q[h], q[h]);
-        im[h] = lane > 0 ? sm_lookup(below, q[h]) : 0;
+        is[h] = ff_lookup(q[h], q[h], kSmNbase);
+        im[h] = lane > 0 ? ff_lookup(below, q[h], kSmNbase) : 0;
     }
 
-    // ---- the recursion
-    const real NEG = (real)-INFINITY;
-    real X[2] = { lane == 0 ? (real)0 : NEG, lane == 0 ? (real)0 : NEG };
-    auto load = [&](int t, float (&a)[kSmChunk][4]) {                           // (t < t1; a block past the window's last reads the last again, unused)
-#pragma unroll
-        for (int u = 0; u < kSmChunk; u++) {
-            const float *row = T + (size_t)min(t + u, t1 - 1) * Ps;
-            a[u][0] = row[is[0]]; a[u][1] = row[im[0]]; a[u][2] = row[is[1]]; a[u][3] = row[im[1]];
-        }
-    };
-    float cur[kSmChunk][4], nxt[kSmChunk][4];
-    if (t0 < t1) load(t0, cur);
-    for (int t = t0; t < t1; t += kSmChunk) {
-        const bool more = t + kSmChunk < t1;
-        if (more) load(t + kSmChunk, nxt);
-#pragma unroll
-        for (int u = 0; u < kSmChunk; u++) {
-            if (t + u < t1) {                                                   // (uniform)
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const real up = __shfl_up(X[h], 1, 64);
-                    const real stay = X[h] + (real)cur[u][2 * h];
-                    const real move = lane == 0 ? NEG : up + (real)cur[u][2 * h + 1];
-                    const real m = move > stay ? move : stay;
-                    if constexpr (ALL) X[h] = m == NEG ? NEG : m + log1p(exp(-fabs(stay - move)));
-                    else X[h] = m;
-                }
-            }
-        }
-        if (more) {
-#pragma unroll
-            for (int u = 0; u < kSmChunk; u++)
-#pragma unroll
-                for (int k = 0; k < 4; k++) cur[u][k] = nxt[u][k];
-        }
-    }
+    win_real<ALL> X[2];
+    window_scores<ALL>(T, Ps, t0, t1, is, im, lane, X);
     if (lane == P - 1) out[site] = make_int4(i, t1 - t0, __float_as_int((float)X[0]), __float_as_int((float)X[1]));
 }
 

@@ -18,6 +18,7 @@
 // the words back through LDS in chunks of rows; thread 0 follows them from (m, n) and writes the op bytes downwards from the end of the read's bytes, so that they
 // stand in path order and end at the last byte; the counts, maxdev and K go to the read's record.
 #include "ffhip_internal.hpp"
+#include "ffhip_seq.hpp"
 #include <algorithm>
 
 namespace ffhip {
@@ -34,8 +35,6 @@ int truth_form(long long window) {
 int truth_max_window() { return kTruthNT[kTruthForms - 1] * kTruthK[kTruthForms - 1]; }
 int truth_max_band() { return (truth_max_window() - 1) / 2; }
 size_t truth_ws_words(int form, int m) { return (size_t)m * (size_t)(kTruthNT[form] / 64 * kTruthK[form] * 2); }
-
-__device__ __forceinline__ int tr_code(char c) { return c == 'A' ? 0 : c == 'G' ? 2 : c == 'T' ? 3 : 1; }      // C and Z: 1 (the call holds A C G T Z only)
 
 // inclusive prefix minimum over the wave's 64 lanes: four shifts inside each row of 16 lanes, then lane 15 and lane 31 broadcast to the rows behind them
 __device__ __forceinline__ int tr_wave_scan_min(int v, int lane) {
@@ -102,7 +101,7 @@ k_truth(const TruthRead *__restrict__ list, const uint8_t *__restrict__ seq, con
     {
         int a, b;
         reach(1, &a, &b);
-        for (int i = a + tid; i < b; i += NT) ring[i & (R - 1)] = i > 0 ? (uint8_t)tr_code(bs[i - 1]) : (uint8_t)0;
+        for (int i = a + tid; i < b; i += NT) ring[i & (R - 1)] = i > 0 ? (uint8_t)seq_code(bs[i - 1]) : (uint8_t)0;
         have = b;
         if (tid < min(RC, m)) { const int t = tt[tid]; tq[0][tid] = (uint8_t)(t == 4 ? 1 : t); }
     }
@@ -118,7 +117,7 @@ k_truth(const TruthRead *__restrict__ list, const uint8_t *__restrict__ seq, con
         if (j1 <= m) { reach(j1, &na, &nb); na = max(na, have); }
         uint8_t pf[PF];
 #pragma unroll
-        for (int x = 0; x < PF; x++) { const int i = na + tid + x * NT; pf[x] = (i < nb && i > 0) ? (uint8_t)tr_code(bs[i - 1]) : (uint8_t)0; }
+        for (int x = 0; x < PF; x++) { const int i = na + tid + x * NT; pf[x] = (i < nb && i > 0) ? (uint8_t)seq_code(bs[i - 1]) : (uint8_t)0; }
         const int tnext = (j1 <= m && tid < min(RC, m + 1 - j1)) ? tt[j1 - 1 + tid] : 0;
 
         for (int j = j0; j < j1; j++) {

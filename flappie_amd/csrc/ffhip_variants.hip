@@ -1,8 +1,8 @@
 // ffhip_variants.hip -- ref against alt alleles of a mapped sequence (FFHIP_RUN_REMAP_VARIANTS, include/ffhip.h "variants"): around every variant -- a short edit
 // { pos p, nref r, nalt k, alt[] } of the sequence s a read was mapped to -- the blocks the mapping gave to the bases p - c .. p + r + c - 1 are scored twice through
 // the transition scores, once through those bases of s and once through the bases the edit puts in their place, every path of the window's blocks through a
-// hypothesis's bases allowed.  It is k_site_mods (ffhip_sitemods.hip) with two generalisations: the edit is any substitution, insertion or deletion of up to 16
-// letters, so the two hypotheses may differ in LENGTH, and the alphabet has 4 or 5 letters.  The starts come from k_site_starts, launched here over this
+// hypothesis's bases allowed.  The recursion is k_site_mods' (window_scores, ffhip_seq.hpp); the hypotheses are more general: the edit is any substitution,
+// insertion or deletion of up to 16 letters, so the two may differ in LENGTH, and the alphabet has 4 or 5 letters.  The starts come from k_site_starts, launched here over this
 // feature's own list of reads into its own workspace.
 //
 // k_variants<ALL>: one wave a variant, kVrWaves variants a workgroup, no barrier and no LDS.  Lane j owns window position j of EACH hypothesis -- position lo + j
@@ -10,31 +10,18 @@
 //   holds.  Lane j's alt letter is s[lo + j] in front of p, alt[lo + j - p] inside the edit (the variant's 24 bytes) and s[lo + j - k + r] behind it; the alt
 //   states are those of s in front of p, and from p on they are coded one after the other from the state of q[p - 1], in a loop that is uniform in the wave and
 //   ends, behind the edit, where the coding meets that of s again (the end of a run of equal letters) or at the window's last position.  A lane then knows the
-//   (at most) four entries of a block's score row it reads: stay and move of either hypothesis.  A step is, per hypothesis, one cross-lane move (the value of the
-//   lane below), two adds and one compare (best path, float32) or one log1p(exp()) (all paths, fp64); the two hypotheses are independent chains and fill each
-//   other's latency.  The rows are read through the cache, kVrChunk blocks ahead of the chain in registers: no step waits for memory.  What bounds a step is the
-//   chain cross-lane move -> add -> compare.  A hypothesis with fewer blocks than moves keeps -inf in its last lane: no special case.  The two results sit in
+//   (at most) four entries of a block's score row it reads: stay and move of either hypothesis, and window_scores (ffhip_seq.hpp) runs both through the window's
+//   blocks: best path in float32, all paths in fp64.  A hypothesis with fewer blocks than moves keeps -inf in its last lane: no special case.  The two results sit in
 //   lanes P_ref - 1 and P_alt - 1; the alt one is brought to lane P_ref - 1, which writes the record as one 16-byte store.
 //   The order of operations depends on the window and the variant alone: the same read gives the same bytes wherever it stands in a batch.  No atomics, no scratch.
 #include "ffhip_internal.hpp"
-#include <math.h>
-#include <type_traits>
+#include "ffhip_seq.hpp"
 
 namespace ffhip {
 
 constexpr int kVrNT = 256;              // threads of the workgroup
 constexpr int kVrWaves = kVrNT / 64;    // variants a workgroup
-constexpr int kVrChunk = 8;             // blocks whose entries a lane holds ahead of the chain
 static_assert(2 * kVariantsMaxContext + kVariantsMaxAllele <= 64, "a lane a window position");
-
-// the flip-flop state of a coded position (remap_code's low byte is trans_lookup(q, q)); NB: the letters of the alphabet
-template <int NB>
-__device__ __forceinline__ int vr_state(unsigned short e) { const int st = e & 255; return st < 2 * NB * NB ? st / (2 * NB + 1) : st - 2 * NB * NB; }
-template <int NB>
-__device__ __forceinline__ int vr_lookup(int from, int to) { return to < NB ? to * 2 * NB + from : 2 * NB * NB + from; }
-// the state a letter takes behind state `prev` (prev < 0: the sequence's first position)
-template <int NB>
-__device__ __forceinline__ int vr_next(int prev, int letter) { return (prev >= 0 && prev < NB && prev == letter) ? letter + NB : letter; }
 
 const char *variant_invalid(const Variant &v, size_t L, int nbase) {
     if (v.nref > kVariantsMaxAllele || v.nalt > kVariantsMaxAllele) return "an allele is longer than 16";
@@ -50,7 +37,6 @@ __global__ void __launch_bounds__(kVrNT)
 k_variants(const SiteRead *__restrict__ list, const VarEntry *__restrict__ vars, int nvar, const unsigned short *__restrict__ seq, const float *__restrict__ trans,
            int Ps, int ctx, const uint4 *__restrict__ rec, const int *__restrict__ starts, int4 *__restrict__ out, int TbS, const int *__restrict__ tbs, ReadMap map) {
     FFHIP_DECODE_PRIO_SET();
-    using real = typename std::conditional<ALL, double, float>::type;
     const int lane = threadIdx.x & 63, vi = blockIdx.x * kVrWaves + (threadIdx.x >> 6);
     if (vi >= nvar) return;                                                     // (a whole wave: the kernel has no barrier)
     const int4 head = *(const int4 *)(vars + vi);                               // { k, index, pos, nref | nalt << 8 | alt[0 .. 1] << 16 }
@@ -69,16 +55,16 @@ k_variants(const SiteRead *__restrict__ list, const VarEntry *__restrict__ vars,
 
     // ---- the states of both hypotheses at this lane's position
     const int a = lo + lane;                                                    // this lane's position, in s and in s^alt
-    const int q0 = lane < Pr ? vr_state<NB>(sq[a]) : 0;                         // the coding of s itself
+    const int q0 = lane < Pr ? ff_state<NB>(sq[a]) : 0;                         // the coding of s itself
     const int myalt = lane < k ? vars[vi].v.alt[lane] : 0;                      // the alt allele, a letter a lane
     const int inside = __shfl(myalt, (a - p) & 63, 64);
     const int behind = __shfl(q0, (lane - k + r) & 63, 64);                     // the state of s at the position that stands here behind the edit
     const int la = a < p ? q0 % NB : a < p + k ? inside : behind % NB;          // this lane's alt letter
     int qa = lane >= Pa ? 0 : a < p ? q0 : behind;
     {
-        int prev = p > 0 ? vr_state<NB>(sq[p - 1]) : -1;
+        int prev = p > 0 ? ff_state<NB>(sq[p - 1]) : -1;
         for (int x = p; x < lo + Pa; x++) {                                     // (uniform in the wave)
-            const int now = vr_next<NB>(prev, __shfl(la, x - lo, 64));
+            const int now = ff_next<NB>(prev, __shfl(la, x - lo, 64));
             if (x >= p + k && now == __shfl(q0, x - k + r - lo, 64)) break;     // the coding of s from here on
             qa = a == x ? now : qa;
             prev = now;
@@ -89,46 +75,12 @@ k_variants(const SiteRead *__restrict__ list, const VarEntry *__restrict__ vars,
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         const int below = __shfl_up(q[h], 1, 64);
-        is[h] = vr_lookup<NB>(q[h], q[h]);
-        im[h] = lane > 0 ? vr_lookup<NB>(below, q[h]) : 0;
+        is[h] = ff_lookup(q[h], q[h], NB);
+        im[h] = lane > 0 ? ff_lookup(below, q[h], NB) : 0;
     }
 
-    // ---- the recursion
-    const real NEG = (real)-INFINITY;
-    real X[2] = { lane == 0 ? (real)0 : NEG, lane == 0 ? (real)0 : NEG };
-    auto load = [&](int t, float (&v)[kVrChunk][4]) {                           // (t < t1; a block past the window's last reads the last again, unused)
-#pragma unroll
-        for (int u = 0; u < kVrChunk; u++) {
-            const float *row = T + (size_t)min(t + u, t1 - 1) * Ps;
-            v[u][0] = row[is[0]]; v[u][1] = row[im[0]]; v[u][2] = row[is[1]]; v[u][3] = row[im[1]];
-        }
-    };
-    float cur[kVrChunk][4], nxt[kVrChunk][4];
-    if (t0 < t1) load(t0, cur);
-    for (int t = t0; t < t1; t += kVrChunk) {
-        const bool more = t + kVrChunk < t1;
-        if (more) load(t + kVrChunk, nxt);
-#pragma unroll
-        for (int u = 0; u < kVrChunk; u++) {
-            if (t + u < t1) {                                                   // (uniform)
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const real up = __shfl_up(X[h], 1, 64);
-                    const real stay = X[h] + (real)cur[u][2 * h];
-                    const real move = lane == 0 ? NEG : up + (real)cur[u][2 * h + 1];
-                    const real m = move > stay ? move : stay;
-                    if constexpr (ALL) X[h] = m == NEG ? NEG : m + log1p(exp(-fabs(stay - move)));
-                    else X[h] = m;
-                }
-            }
-        }
-        if (more) {
-#pragma unroll
-            for (int u = 0; u < kVrChunk; u++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) cur[u][j] = nxt[u][j];
-        }
-    }
+    win_real<ALL> X[2];
+    window_scores<ALL>(T, Ps, t0, t1, is, im, lane, X);
     const float ref = (float)X[0], alt = __shfl((float)X[1], Pa - 1, 64);
     if (lane == Pr - 1) out[vi] = make_int4(head.y, t1 - t0, __float_as_int(ref), __float_as_int(alt));
 }
