@@ -1,13 +1,14 @@
-// ffhip_annot.hpp -- the per-read products of a batch that live OUTSIDE its result block, described once (host only, no kernels; included by ffhip_engine.hip).
+// ffhip_annot.hpp -- the per-read products of a batch that live OUTSIDE its result block, described once (host only, no kernels; included by ffhip_batch.hpp).
 // Barcodes, adapters, the map, the poly tail, truth, remap, events, site mods and variants each bring their records to the host in a buffer and a copy of their own.  Such a buffer is a
-// Mirrored (below), a feature is a struct of its own in ffhip_batch that starts as an Annot, and kAnnots (ffhip_engine.hip, behind the features' functions) has one
+// Mirrored (below), a feature is a struct of its own in ffhip_batch that starts as an Annot, and kAnnots (ffhip_features.hip, behind the features' functions) has one
 // row a feature, in launch order.  To add a per-read product outside the block one writes
-//   its struct        struct Thing : Annot { <parameters, lists, workspaces, per-read offsets> } thing;      (ffhip_batch, and its place in ffhip_batch::annot)
+//   its struct        struct Thing : Annot { <parameters, lists, workspaces, per-read offsets> } thing;      (ffhip_batch in ffhip_batch.hpp, and its place in ffhip_batch::annot)
+// and in ffhip_features.hip
 //   its two functions thing_prepare (run_front: lists, workspaces, room in `rec`), thing_launch (run_back: the kernel)
 //   its two layouts   thing_bytes (what a finished run brings down), thing_spans (where a read's record lies in `rec`: at most two pieces)
 //   its row           { FFHIP_RUN_THING, <the text without FFHIP_RUN_REMAP, or nullptr>, <nbase, the model's text>, <the undecoded text>, the four functions }
-//   its accessor      ffhip_batch_thing: b->thing.rec.host + ...
-// and nothing in the front's checks, the back's launches, the copies of a packed or an ordinary finish, the f32 re-run's patching, the rehearsal or the destroy.
+//   its setter, accessor and operator   ffhip_batch_set_thing, ffhip_batch_thing: b->thing.rec.host + ..., ffhip_op_thing; each check through its one helper ("each check once")
+// and nothing in ffhip_engine.hip, whose front, back, finish, f32 re-run, rehearsal and destroy reach the features through the declarations at the end of this file only.
 #pragma once
 #include <string.h>
 
@@ -80,5 +81,15 @@ struct AnnotRow {
     size_t (*bytes)(const ffhip_batch *);
     void (*spans)(const ffhip_batch *, int read, AnnotSpan out[2]);
 };
+
+// ---- what ffhip_engine.hip asks of ffhip_features.hip: the table (ffhip_batch::AN_COUNT rows), the front's and the finish's share of all features and of the
+// pileup, and rerun_on_f32_path's way of handing its side batch the re-run reads' sequences and truths
+FFHIP_LOCAL extern const AnnotRow kAnnots[];
+FFHIP_LOCAL int annots_prepare(ffhip_batch *b, unsigned flags);
+FFHIP_LOCAL int annots_copy_down(ffhip_batch *b);
+FFHIP_LOCAL int pileup_check(const ffhip_batch *b, unsigned flags);
+FFHIP_LOCAL void pileup_launch(ffhip_batch *b);
+FFHIP_LOCAL int remap_adopt(ffhip_batch *b, std::vector<std::vector<unsigned short>> &&seq, std::vector<signed char> &&state, int band);
+FFHIP_LOCAL int truth_adopt(ffhip_batch *b, std::vector<std::vector<uint8_t>> &&seq, std::vector<signed char> &&state, int band);
 
 }  // namespace ffhip

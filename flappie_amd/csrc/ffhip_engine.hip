@@ -18,11 +18,7 @@
 #include <mutex>
 #include <unordered_map>
 
-#include "../../include/ffhip.h"
-#include "ffhip_internal.hpp"
-#include "ffhip_host.hpp"
-#include "ffhip_results.hpp"
-#include "ffhip_annot.hpp"
+#include "ffhip_batch.hpp"
 
 using namespace ffhip;
 
@@ -337,39 +333,7 @@ extern "C" int ffhip_engine_set_profiling(ffhip_engine *e, int on) {
     return FFHIP_OK;
 }
 
-// ------------------------------------------------------------------------------------ model
-struct ConvDev {
-    int Fin = 0, Fout = 0, winlen = 0, stride = 1;
-    float *taps = nullptr;      // [Fout][winlen][Fin]   (VALU layers)
-    float *bias = nullptr;      // [Fout] or [Mpad] for the MFMA layer
-    float4 *Wp = nullptr;       // A-fragment order     (last layer)
-    int K16 = 0, Mpad = 0;
-    void *Wsplit = nullptr;     // last layer with 16 input features: fp16 slices in 16x16x32 A order for k_conv_split (ffhip_split.hpp)
-    int split_S = 0;            // exponent its accumulators carry: weight exponent + kSplitExpX
-};
-struct RnnDev {
-    float4 *iWp = nullptr, *sWp = nullptr;
-    float *bias = nullptr;      // [4*Hp] permuted rows
-    int Kin16 = 0;
-    void *Wsplit = nullptr;     // both matrices as 16-bit slices in MFMA 16x16x32 A order (ffhip_rnn_split.hip, ffhip_split.hpp), or nullptr
-    int split_S = 0;            // the power-of-two exponent both products of this layer carry: sw(Wi) + e(x) = sw(sW) + e(h)
-};
-
-struct ffhip_model {
-    ffhip_engine *eng = nullptr;
-    int kind = 0, cell = 0, nconv = 0, G = 4;
-    int H = 0, Hp = 0;          // hidden units, padded to a multiple of 16
-    int P = 0, Ps = 0, nbase = 0, nstate = 0;
-    int act = ACT_SWISH;
-    ConvDev conv[3];
-    RnnDev rnn[5];
-    float4 *FFp = nullptr;
-    float *FFb = nullptr;
-    void *FFsplit = nullptr;    // the head's weights as fp16 slices in 16x16x32 A order (k_head_split: reads the last layer's split output)
-    int FF_split_S = 0;         // exponent its accumulators carry: weight exponent + kSplitExpH
-    std::vector<void *> owned;
-};
-
+// ------------------------------------------------------------------------------------ model (ConvDev, RnnDev, ffhip_model: ffhip_batch.hpp)
 static void *dev_upload(ffhip_model *m, const void *host, size_t bytes) {
     void *d = nullptr;
     if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
@@ -633,18 +597,6 @@ static ModelPath model_path(const ffhip_model *m, unsigned flags, int ncu, int p
     p.pairable = lean && split_pair_ok(m->cell, m->Hp, pair_tiles, ncu);
     return p;
 }
-struct RunPath {
-    bool keep = false, persist = false, fused = false;           // FFHIP_RUN_KEEP_ACTS; one launch per layer (and chunk of read tiles); the f32 layer kernel with the projection inside
-    bool proj_split = false, split = false, split2 = false;      // projections on split operands; ModelPath::split; H = 512 (and FFHIP_RUN_UNFUSED_RNN at H = 256):
-                                                                 // projection GEMM + recurrence-only layer kernel, both on split operands
-    bool conv_split = false, conv_f16 = false;                   // the last convolution writes the split layout / runs on split operands (its predecessor writes fp16 slices)
-    bool split_head = false, packable = false;                   // the CRF head reads the last layer's split output (k_head_split: no fp32 copy of it); a packed batch may take the run
-    bool post_done = false, head_e = false, rle_post8 = false;   // 8- / 10-state flip-flop models, a block's scores spanning at most kFbRange: ONE pair of fp64 linear-space chains
-                                                                 // per read gives logZ, the normalised scores and the posterior (k_crf_fb); head_e: their input exp(S - block max)
-                                                                 // comes from the split head's epilogue; rle_post8: the run-length model's posterior from such chains (k_rle_post8)
-    int R = 0, gates = 2, persist_mode = 0, rnn_path = 0;       // rescaling interval of the linear-space CRF normalisation (0: log space); gate_level; hand-off of the persistent
-                                                                 // layer kernels (0: write-through where a group spans XCDs); ffhip_batch_rnn_path
-};
 static RunPath plan_run(const ffhip_model *m, unsigned flags, float temperature, int ncu) {
     const int Hp = m->Hp;
     const ModelPath mp = model_path(m, flags, ncu);
@@ -671,170 +623,7 @@ static RunPath plan_run(const ffhip_model *m, unsigned flags, float temperature,
     return p;
 }
 
-// ------------------------------------------------------------------------------------ batch
-struct ConvPlan { int Tin = 0, Tout = 0; int *x0a = nullptr, *x0b = nullptr; };
-
-struct ffhip_batch {
-    ffhip_engine *eng = nullptr;
-    const ffhip_model *mdl = nullptr;
-    hipStream_t stream = nullptr;
-    int nread = 0, B16 = 0, Bp = 0;
-    int T = 0, Tb = 0;                  // capacity: samples / blocks of the longest read the batch can take
-    ConvPlan plan[3];
-    // ragged batch (reads of different lengths, all <= T): per-read window tables, block counts and tile maxima
-    bool ragged = false;
-    std::vector<int> hT, hTb;           // samples / blocks of each read
-    // host images of the tables below: they stay alive here so that their uploads can be asynchronous on the batch's stream (a
-    // synchronous copy or a stream synchronisation in the set-up path waits for compute slots the other batch's layer launches hold)
-    // (pinned: an asynchronous copy from pageable memory is staged by the runtime and may block the caller)
-    struct Pinned {
-        void *p = nullptr; size_t cap = 0;
-        void *get(size_t bytes) {
-            if (cap >= bytes && p) return p;
-            if (p) hipHostFree(p);
-            p = nullptr; cap = 0;
-            if (hipHostMalloc(&p, bytes + bytes / 4 + 64, hipHostMallocDefault) != hipSuccess) return nullptr;
-            cap = bytes + bytes / 4 + 64;
-            return p;
-        }
-        ~Pinned() { if (p) hipHostFree(p); }
-    };
-    Pinned h_tin[3], h_ta[3], h_tq[3], h_tbs, h_tbt, h_glen, h_gsrc, h_rehearsal;
-    int *d_tbs = nullptr, *d_tbt = nullptr;
-    int *rag_x0a[3] = { nullptr, nullptr, nullptr }, *rag_x0b[3] = { nullptr, nullptr, nullptr };
-    int *rag_tin[3] = { nullptr, nullptr, nullptr };       // stride-1 thin layers: per-read input lengths replace the table
-    // Packed batch (ffhip_batch_set_*_packed): the `nread` rows of the buffers are SLOTS, each holding one or more reads one behind the other with a gap of
-    // ffhip_model_pack_gap() blocks; results are indexed by READ (0 .. nvirt - 1, the order of the set call).  hT / hTb hold the reads' lengths then.
-    int res_copied = 0;                 // the result block's copy to the host is already enqueued (a packed batch: behind its decode, in ffhip_batch_run)
-    int cap_reads = 0;                  // the per-read result arrays (lens, score, logZ) take this many reads (>= nread)
-    bool packed = false;
-    int nvirt = 0;
-    std::vector<int> v_slot, v_off;     // slot and first block of every read
-    int *d_vb0 = nullptr, *d_vb1 = nullptr, *d_vtb = nullptr;      // per read: first row in Tb-row / (Tb + 1)-row buffers, blocks
-    unsigned *d_live = nullptr;         // [Tb][B16]: bit r = slot 16 rt + r holds a block of a read at step t (the layer kernels' reset mask)
-    int *rag_seg[3] = { nullptr, nullptr, nullptr };       // stride-1 thin layers of a packed batch: read boundaries per row (k_conv_small `seg`)
-    size_t rag_seg_cap[3] = { 0, 0, 0 };
-    long long *d_goff = nullptr;        // destination of every read's signal (floats from sbuf[0].p + kSamplePad)
-    int4 *d_prd = nullptr;             // per read records for the device-side table / mask builders: [conv table | live mask] x cap_reads
-    Pinned h_vb0, h_vb1, h_vtb, h_prd, h_seg[3], h_goff;
-    SampleBuf sbuf[3];                  // sbuf[0] = signal, sbuf[l] = output of conv l-1
-    float *act[2] = { nullptr, nullptr };
-    void *actS[2] = { nullptr, nullptr };      // the same two buffers in the split-operand layout (ffhip_rnn_split.hip), allocated on first use
-    float *keep[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    float *xa = nullptr, *cstate = nullptr;
-    float *fa[2] = { nullptr, nullptr };       // the fp32 activations of the run in progress: act[], or -- a packed batch's launch-per-step run -- the memory of actS[]
-    float *xa_win = nullptr;            // the launch-per-step run's in-projection, kStepWindow steps of it (run_layers); allocated on first use
-    void *split_win = nullptr;          // ... and its input in the split layout
-    size_t dev_bytes = 0;               // what dalloc holds for the batch (ffhip_debug_batch_device_bytes: this and the result block)
-    float *trans = nullptr, *post = nullptr, *fwd = nullptr;
-    double *crf_logz = nullptr;         // fp64 partition function per read
-    double *crf_e = nullptr;            // exp(score - block max), workspace of the linear-space partition function
-    uint8_t *tb = nullptr;
-    int *path = nullptr; float *qpath = nullptr;
-    int32_t *trace = nullptr;
-    unsigned split_epoch = 0;           // launch counter of the split layer kernel (its check-in words are never cleared)
-    int counted = 0;                    // this batch is in the engine's in_flight count (between run and finish)
-    const float **d_gsrc = nullptr; int *d_glen = nullptr;              // ffhip_batch_set_prepared: source rows of the gather
-    unsigned *pflags = nullptr;         // persistent-kernel XCC ids (the abort word: pabort() below)
-    // reads with a value beyond the split format's range (ffhip_split.hpp: the swish convolutions' outputs are clamped at +-4094 there, the
-    // reference's are unbounded, layers.c:24-33): one word per read, set by the producers of that format, looked at by ffhip_batch_finish,
-    // which runs such reads again on the f32 path (`side`) and puts their results in place
-    double rehearsal_done_at = 0.0;     // FFHIP_DEBUG_HOST_REHEARSAL_MSPS: when the emulated GPU is done with this batch
-    ffhip_batch *side = nullptr;        // 16 slots of this batch's capacity, created when the first read needs it
-    bool is_side = false;
-    int reruns = 0;                     // reads of the last run that took that way
-    int persist_concurrent_ok = 0;      // two such batches fit on the chip at once
-    float *scratch = nullptr;           // dense [Tb][H] for debug taps
-    // The small results, brought to the host by ffhip_batch_finish in one copy: the result block (ffhip_results.hpp), and thin views of its head and core fields
-    ResultBlock res;
-    unsigned *sat() const { return res.on_dev<unsigned>(RF_SAT); }
-    unsigned *pabort() const { return res.on_dev<unsigned>(RF_ABORT); }
-    int *lens() const { return res.on_dev<int>(RF_LENS); }
-    float *score() const { return res.on_dev<float>(RF_SCORE); }
-    char *bases() const { return res.on_dev<char>(RF_BASES); }
-    char *quals() const { return res.on_dev<char>(RF_QUALS); }
-    unsigned *h_sat() const { return res.on_host<unsigned>(RF_SAT); }
-    unsigned *h_abort() const { return res.on_host<unsigned>(RF_ABORT); }
-    int *h_lens() const { return res.on_host<int>(RF_LENS); }
-    unsigned res_made = 0;              // sections of the block the last run filled (res_bit)
-    // The per-read products OUTSIDE the result block (ffhip_annot.hpp): each a struct of its own that starts with its records (`rec`: a device buffer and its pinned
-    // mirror, created or grown by the front of the first run that asks, one copy of their own beside the block's), its uploaded list if it has one, and `valid`
-    // (the last run made them).  annot(i) is feature i of kAnnots.
-    // Barcode records (FFHIP_RUN_BARCODES, k_barcodes): 16 bytes a read, cap_reads of them
-    struct Barcodes : Annot { const ffhip_barcodes *kit = nullptr; int max_dist = 0, min_sep = 3, both = 0; } bc;
-    // Adapter records (FFHIP_RUN_ADAPTERS, k_adapters): 256 bytes a read, cap_reads of them
-    struct Adapters : Annot { const ffhip_adapters *kit = nullptr; int max_dist = -1; } ad;
-    // Map records (FFHIP_RUN_MAP, k_map_scan and k_map_finish): 64 bytes a read, cap_reads of them; the tasks' slots (8 bytes a task of either anchor of every read),
-    // taken by the front of the first run that asks
-    struct Map : Annot { const ffhip_map_ref *ref = nullptr; int window = kMapMaxAnchor, max_error = 250; void *ws = nullptr; size_t ws_cap = 0; } map;
-    // Poly tail records (FFHIP_RUN_POLYTAIL, k_polytail): 32 bytes a read, cap_reads of them; the reads' list, written by the front of every run that asks; the
-    // windows' workspace (a double and a byte a window of every read, `windows` of them in this run), grown when a run needs more
-    struct PolyTail : Annot { ffhip_polytail_params p{}; bool set = false; uint8_t *ws = nullptr; size_t ws_cap = 0, windows = 0; } pt;
-    // Remap (FFHIP_RUN_REMAP, k_remap): the coded sequences of ffhip_batch_set_remap on the host and (dseq) on the device; cap_reads 16-byte records and, behind them,
-    // a byte a block in the layout of the (Tb + 1)-entry buffers; the reads' list and the traceback workspace, both written by the front of every run that asks
-    struct Remap : Annot {
-        std::vector<std::vector<unsigned short>> seq;       // per read: stay | move << 8 of every position (remap_code)
-        std::vector<signed char> state;                      // per read: 0 no sequence, 1 a sequence, 2 refused at the call (L = 0)
-        int set = 0, band = 0;
-        unsigned short *dseq = nullptr; size_t dseq_cap = 0;
-        unsigned long long *ws = nullptr; size_t ws_cap = 0;
-        int count[kRemapForms] = { 0, 0, 0, 0 };
-    } rmp;
-    // Truth (FFHIP_RUN_TRUTH, k_truth): the truths of ffhip_batch_set_truth on the host and (dseq) on the device; cap_reads 48-byte records and, behind them,
-    // m + blocks + 1 bytes of ops a read with a truth; the reads' list and the traceback workspace as for remap.  from_map (ffhip_batch_set_truth_from_map): no
-    // truths on the host -- k_map_stretch writes each mapped read's into dseq and patches the list, and everything is sized from the bound (map_truth_bound)
-    struct Truth : Annot {
-        std::vector<std::vector<uint8_t>> seq;               // per read: codes 0 .. nbase - 1
-        std::vector<signed char> state;                      // per read: 0 no truth, 1 a truth, 2 an empty one
-        std::vector<size_t> off;                             // per read: its first byte of ops behind the records, and (one more entry) the end
-        int set = 0, band = 0, from_map = 0;
-        uint8_t *dseq = nullptr; size_t dseq_cap = 0;
-        unsigned long long *ws = nullptr; size_t ws_cap = 0;
-        int count[kTruthForms] = { 0, 0, 0, 0 };
-    } tru;
-    // Events (FFHIP_RUN_EVENTS with FFHIP_RUN_REMAP, k_events): 16 bytes a base of every read with a sequence that can be mapped, one read behind the other
-    // Site mods (FFHIP_RUN_REMAP_MODS with FFHIP_RUN_REMAP, k_site_mods): 16 bytes a C / Z of every such read; the workspace of starts (L + 1 int32 a listed read);
-    // the lists are the reads, then the sites
-    // Variants (FFHIP_RUN_REMAP_VARIANTS with FFHIP_RUN_REMAP, k_variants): 16 bytes a variant of every such read; a workspace of starts of its own; the lists are
-    // the variants, then the reads; `set`: the lists of ffhip_batch_set_remap_variants (copied; empty: the feature is detached)
-    struct PerBase : Annot {                                 // records of 16 bytes, a read's one behind the other
-        std::vector<size_t> off;                             // per read: its first record, and (one more entry) the end
-        int reads = 0;                                       // the reads in the list
-        size_t total() const { return off.empty() ? 0 : off.back(); }
-    } evt;
-    struct Sites : PerBase { int *start = nullptr; size_t start_cap = 0; int context, all = 0; explicit Sites(int c) : context(c) {} } smd{ 15 };
-    struct Variants : Sites { std::vector<std::vector<ffhip_variant>> set; Variants() : Sites(10) {} } var;
-    // Pileup (FFHIP_RUN_PILEUP, k_pileup): the engine-level object the batch's finished runs add to; nothing of it is the batch's
-    ffhip_pileup *pile = nullptr;
-    enum { AN_COUNT = 9 };
-    Annot &annot(int i) { Annot *const a[AN_COUNT] = { &bc, &ad, &map, &pt, &tru, &rmp, &evt, &smd, &var }; return *a[i]; }       // (the order of kAnnots: launch order)
-    RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale
-    std::vector<void *> owned;
-    unsigned last_flags = 0;
-    float last_temperature = 1.0f;
-    int ran = 0, finished = 0;
-    int final_act = 0;                  // which act[] holds the last recurrent layer's output
-    RunPath run_path;                   // the run's path, decided at its front (plan_run)
-    int rnn_path = 0;                   // what the last run used: 0 launch per step, 1 persistent recurrence behind a projection GEMM, 2 fused f32 layer kernel, 3 split-operand layer kernel, 4 split-operand projection GEMM + recurrence-only layer kernel
-    hipEvent_t ev[FFHIP_NGROUP + 1];
-    int have_ev = 0;
-    int launches[FFHIP_NGROUP];
-    hipEvent_t lev[5][3];
-    hipEvent_t pair_ev = nullptr;       // ffhip_batch_run_pair: orders the two streams around the paired layer launches
-    int run_cur = 0;                    // which of act[] / actS[] holds the current activations between the phases of a run
-    unsigned run_flags = 0;
-    int paired_last = 0;                // the last run's layers were one launch with another batch's
-    ffhip_batch *prof_mate = nullptr;   // second batch of a profiled pair: the batch whose lev[][] events bracket the paired launches (two event records
-                                        // per launch instead of six: each is a packet between two layer launches, ~5 us of idle chip)
-    ffhip_batch *prof_ref = nullptr;    // ... and the first batch's way back, so that either can go first
-    int profiled = 0;
-    // debug read-outs (ffhip_debug_batch_keep_front / _front / _head_input / _forms): none of them changes what a run launches
-    bool keep_front = false;            // the next runs copy the last convolution's output to front_keep
-    void *front_keep = nullptr;         // [Tb][B16] tiles in the split layout (front_exp: values * 2^front_exp) or fp32 tile-interleaved (front_exp < -1000)
-    int front_kept = 0, front_exp = -100000, front_f16 = -1;       // the last run kept it; the thin layer whose output was fp16 slices (-1: none)
-    int forms[4] = { -1, -1, -1, -1 };  // kernel forms of the last run's convolution launches and its head launch (KernelForm)
-};
-
+// ------------------------------------------------------------------------------------ batch (ffhip_batch and its inline accessors: ffhip_batch.hpp)
 // the run records' fields as the kernel's argument (shape, scale and dwell for a run that makes the whole record), or the same in the host half
 static RleRunOut rle_run_out(const ResultBlock &r, bool host, bool records) {
     auto p = [&](ResField f) { return (host ? r.host : r.dev) + r.at.field[f]; };
@@ -987,16 +776,10 @@ extern "C" ffhip_batch *ffhip_batch_create(ffhip_engine *eng, const ffhip_model 
 extern "C" ffhip_batch *ffhip_batch_create_packed(ffhip_engine *eng, const ffhip_model *m, int nslot, size_t nsample, int max_reads) {
     return batch_create_impl(eng, m, nslot, nsample, max_reads);
 }
-static inline int batch_nreads(const ffhip_batch *b) { return b->packed ? b->nvirt : b->nread; }
-// behind the cap_reads records of remap's and truth's buffers: where the moves and the ops start
-static inline size_t remap_moves_at(const ffhip_batch *b) { return (size_t)b->cap_reads * 16; }
-static inline size_t truth_ops_at(const ffhip_batch *b) { return (size_t)b->cap_reads * kTruthRecInts * 4; }
 
 extern "C" int ffhip_batch_nreads(const ffhip_batch *b) { return b ? batch_nreads(b) : 0; }
 // first row of a read in the buffers of Tb / Tb + 1 rows a slot
 static inline size_t read_row0(const ffhip_batch *b, int read) { return b->packed ? (size_t)b->v_slot[read] * b->Tb + b->v_off[read] : (size_t)read * b->Tb; }
-static inline size_t read_row1(const ffhip_batch *b, int read) { return b->packed ? (size_t)b->v_slot[read] * (b->Tb + 1) + b->v_off[read] : (size_t)read * (b->Tb + 1); }
-static int total_stride(const ffhip_model *m) { int st = 1; for (int l = 0; l < m->nconv; l++) st *= m->conv[l].stride; return st; }
 // does this model's default path take packed batches?  (what a packed batch's run asks of the model: model_path)
 extern "C" int ffhip_model_packable(const ffhip_model *m) {
     if (!m) return 0;
@@ -1512,418 +1295,6 @@ int ffhip::dgrow(ffhip_batch *b, void **p, size_t *cap, size_t need, const char 
     return FFHIP_OK;
 }
 
-// ---- the per-read products outside the result block (ffhip_annot.hpp).  Per feature: its share of the front (prepare: checks of its own, lists, workspaces, room
-// for the records), its share of the back (launch), what a finished run brings down (bytes) and where a read's record lies (spans); kAnnots, the table, at the end.
-static void span1(AnnotSpan out[2], size_t at, size_t bytes) { out[0] = AnnotSpan{ at, bytes }; out[1] = AnnotSpan{}; }
-
-static_assert(sizeof(ffhip_barcode_call) == 16, "k_barcodes writes a record as one 16-byte store");
-static int barcodes_prepare(ffhip_batch *b) {
-    if (!b->bc.kit) return set_err(FFHIP_EINVAL, "barcodes: no kit is attached to the batch (ffhip_batch_set_barcodes)");
-    return b->bc.rec.fixed(b, (size_t)b->cap_reads * sizeof(ffhip_barcode_call), "barcodes: the reads' records");
-}
-static void barcodes_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {        // from the strings and lengths k_assemble has just written
-    launch_barcodes(b->stream, b->bc.kit->kit, b->bases(), b->lens(), b->bc.rec.dev, batch_nreads(b), b->Tb, tbr, rmap, b->bc.max_dist, b->bc.min_sep, b->bc.both);
-    b->launches[5]++;
-    b->bc.valid = 1;
-}
-static size_t barcodes_bytes(const ffhip_batch *b) { return (size_t)batch_nreads(b) * sizeof(ffhip_barcode_call); }
-static void barcodes_spans(const ffhip_batch *, int r, AnnotSpan out[2]) { span1(out, (size_t)r * sizeof(ffhip_barcode_call), sizeof(ffhip_barcode_call)); }
-
-static_assert(sizeof(ffhip_adapter_header) == 16 && sizeof(ffhip_adapter_hit) == 16 && FFHIP_ADAPTER_SEGMENT == kAdSeg && FFHIP_ADAPTER_MAX_HITS == kAdapterMaxHits,
-              "k_adapters writes a header and a hit as one 16-byte store each");
-static int adapters_prepare(ffhip_batch *b) {
-    if (!b->ad.kit) return set_err(FFHIP_EINVAL, "adapters: no kit is attached to the batch (ffhip_batch_set_adapters)");
-    return b->ad.rec.fixed(b, (size_t)b->cap_reads * kAdapterRecBytes, "adapters: the reads' records");
-}
-static void adapters_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {        // likewise
-    launch_adapters(b->stream, b->ad.kit->kit, b->bases(), b->lens(), b->ad.rec.dev, batch_nreads(b), b->Tb, tbr, rmap, b->ad.max_dist);
-    b->launches[5]++;
-    b->ad.valid = 1;
-}
-static size_t adapters_bytes(const ffhip_batch *b) { return (size_t)batch_nreads(b) * kAdapterRecBytes; }
-static void adapters_spans(const ffhip_batch *, int r, AnnotSpan out[2]) { span1(out, (size_t)r * kAdapterRecBytes, kAdapterRecBytes); }
-
-static_assert(sizeof(ffhip_map_call) == kMapRecBytes && FFHIP_MAP_SEGMENT == kMapSeg && FFHIP_MAP_MAX_TOTAL == kMapMaxTotal && FFHIP_MAP_MAX_ANCHOR == kMapMaxAnchor,
-              "k_map_finish writes a record as four 16-byte stores");
-static int map_prepare(ffhip_batch *b) {
-    ffhip_batch::Map &f = b->map;
-    if (!f.ref) return set_err(FFHIP_EINVAL, "map: no reference is attached to the batch (ffhip_batch_set_map)");
-    if (int rc = f.rec.fixed(b, (size_t)b->cap_reads * kMapRecBytes, "map: the reads' records")) return rc;
-    return dgrow(b, &f.ws, &f.ws_cap, (size_t)b->cap_reads * 2 * (size_t)f.ref->view.ntask * 8, "map: the tasks' slots");
-}
-static void map_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {        // from the strings and lengths, as barcodes and adapters
-    ffhip_batch::Map &f = b->map;
-    launch_map(b->stream, f.ref->view, b->bases(), b->lens(), f.rec.dev, batch_nreads(b), b->Tb, tbr, rmap, f.window, f.max_error, f.ws);
-    b->launches[5] += 2;
-    f.valid = 1;
-}
-static size_t map_bytes(const ffhip_batch *b) { return (size_t)batch_nreads(b) * kMapRecBytes; }
-static void map_spans(const ffhip_batch *, int r, AnnotSpan out[2]) { span1(out, (size_t)r * kMapRecBytes, kMapRecBytes); }
-
-// Poly tail, the front's share: every read's samples (the addresses events_prepare gives) and its first window in the workspace, which grows here
-static_assert(sizeof(ffhip_polytail) == kPolyTailRecBytes && sizeof(ffhip_polytail_params) == sizeof(PolyTailParams) && sizeof(PolyRead) == 24,
-              "k_polytail writes a record as two 16-byte stores; the parameters and the reads' list are copied as they stand");
-static int polytail_prepare(ffhip_batch *b) {
-    ffhip_batch::PolyTail &f = b->pt;
-    if (!f.set) return set_err(FFHIP_EINVAL, "poly tail: no parameters are set for the batch (ffhip_batch_set_polytail)");
-    const int nR = batch_nreads(b), st = total_stride(b->mdl);
-    if (int rc = f.rec.fixed(b, (size_t)b->cap_reads * kPolyTailRecBytes, "poly tail: the reads' records")) return rc;
-    if (int rc = f.list.grow(b, b->stream, (size_t)b->cap_reads * sizeof(PolyRead), "poly tail: the reads' list")) return rc;
-    PolyRead *list = (PolyRead *)f.list.host;
-    size_t at = 0;
-    for (int r = 0; r < nR; r++) {
-        const size_t sig = (b->packed ? (size_t)b->v_slot[r] * b->sbuf[0].rs + (size_t)b->v_off[r] * st : (size_t)r * b->sbuf[0].rs) + kSamplePad;
-        list[r] = PolyRead{ sig, at, b->hT[r], r };
-        at += (size_t)(std::min(b->hTb[r], b->hT[r] / st) / f.p.window);
-    }
-    if (int rc = dgrow(b, (void **)&f.ws, &f.ws_cap, std::max<size_t>(at, 1) * 9, "poly tail: the windows' workspace")) return rc;
-    f.windows = at;
-    return nR > 0 ? f.list.copy_up((size_t)nR * sizeof(PolyRead), b->stream) : FFHIP_OK;
-}
-static void polytail_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {        // from the path the decode has just written and the signal the convolutions read
-    ffhip_batch::PolyTail &f = b->pt;
-    PolyTailParams p;
-    memcpy(&p, &f.p, sizeof p);
-    launch_polytail(b->stream, (const PolyRead *)f.list.dev, batch_nreads(b), b->sbuf[0].p, total_stride(b->mdl), b->path, b->mdl->nbase, p, f.rec.dev,
-                    (double *)f.ws, f.ws + 8 * f.windows, nullptr, b->Tb, tbr, rmap);
-    b->launches[5]++;
-    f.valid = 1;
-}
-static size_t polytail_bytes(const ffhip_batch *b) { return (size_t)batch_nreads(b) * kPolyTailRecBytes; }
-static void polytail_spans(const ffhip_batch *, int r, AnnotSpan out[2]) { span1(out, (size_t)r * kPolyTailRecBytes, kPolyTailRecBytes); }
-
-// Remap and truth list their reads a kernel form each, one form behind the other: the pinned image and its upload, and the walk over the forms, a launch each
-static_assert(kRemapForms == kTruthForms, "one packing for both");
-template <class Read> static int forms_upload(ffhip_batch *b, Annot &f, const std::vector<Read> (&per)[kRemapForms], int (&count)[kRemapForms], int nR) {
-    size_t at = 0;
-    for (int k = 0; k < kRemapForms; k++) {
-        count[k] = (int)per[k].size();
-        if (!per[k].empty()) memcpy((Read *)f.list.host + at, per[k].data(), per[k].size() * sizeof(Read));
-        at += per[k].size();
-    }
-    return nR > 0 ? f.list.copy_up((size_t)nR * sizeof(Read), b->stream) : FFHIP_OK;
-}
-template <class Launch> static void forms_launch(ffhip_batch *b, Annot &f, const int (&count)[kRemapForms], Launch launch) {
-    size_t at = 0;
-    for (int k = 0; k < kRemapForms; k++) {
-        if (count[k] > 0) { launch(k, at, count[k]); b->launches[5]++; }
-        at += (size_t)count[k];
-    }
-    f.valid = 1;
-}
-
-// Remap, the front's share: buffers on first use, every read's status, kernel form and place in the workspace, the lists a form each, their upload.
-static_assert(sizeof(RemapRead) == 24, "the reads' list is copied as it stands");
-static bool remap_mappable(const ffhip_batch *b, int r) {      // this read's sequence can be mapped
-    const int N = b->hTb[r], L = (int)b->rmp.seq[r].size();
-    return b->rmp.state[r] == 1 && N >= 1 && L >= 1 && L <= N + 1;
-}
-static size_t remap_bytes(const ffhip_batch *b) { return remap_moves_at(b) + (size_t)b->nread * ((size_t)b->Tb + 1); }
-static int remap_prepare(ffhip_batch *b) {
-    ffhip_batch::Remap &f = b->rmp;
-    const int nR = batch_nreads(b);
-    if (!f.set) return set_err(FFHIP_EINVAL, "remap: no sequences are set for the batch (ffhip_batch_set_remap)");
-    if ((int)f.seq.size() != nR) return set_err(FFHIP_EINVAL, "remap: sequences were set for %zu reads, the batch holds %d", f.seq.size(), nR);
-    if (int rc = f.rec.fixed(b, remap_bytes(b), "remap: the records and moves")) return rc;
-    if (int rc = f.list.grow(b, b->stream, (size_t)b->cap_reads * sizeof(RemapRead), "remap: the reads' list")) return rc;
-    std::vector<RemapRead> per[kRemapForms];
-    size_t ws = 0, seq = 0;
-    for (int r = 0; r < nR; r++) {
-        const int L = (int)f.seq[r].size();
-        RemapRead rr{ ws, (unsigned)seq, L, f.state[r], r };
-        int form = 0;
-        if (rr.status == 1 && !remap_mappable(b, r)) rr.status = 2;
-        if (rr.status == 1) {
-            form = remap_form(L, f.band);
-            if (form < 0) return set_err(FFHIP_EINVAL, "remap: read %d's window of min(2 band + 1, L) cells is more than %d", r, remap_max_window());
-            ws += remap_ws_words(form, b->hTb[r]);
-        }
-        seq += (size_t)L;
-        per[form].push_back(rr);
-    }
-    if (int rc = dgrow(b, (void **)&f.ws, &f.ws_cap, ws * 8, "remap: the traceback workspace")) return rc;
-    return forms_upload(b, f, per, f.count, nR);
-}
-static void remap_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {           // from the transitions, whatever the path was decoded from
-    ffhip_batch::Remap &f = b->rmp;
-    forms_launch(b, f, f.count, [&](int form, size_t at, int n) {
-        launch_remap(b->stream, form, (const RemapRead *)f.list.dev + at, n, f.dseq, b->trans, b->mdl->Ps, f.band, f.ws, f.rec.dev, f.rec.dev + remap_moves_at(b), b->Tb, tbr, rmap);
-    });
-}
-static void remap_spans(const ffhip_batch *b, int r, AnnotSpan out[2]) {           // the record, and the moves of the read's blocks (not the entry behind them)
-    out[0] = AnnotSpan{ (size_t)r * 16, 16 };
-    out[1] = AnnotSpan{ remap_moves_at(b) + read_row1(b, r), (size_t)b->hTb[r] };
-}
-
-// Truth from map: the most bases a stretch of a call of a read of N blocks can have, with max_error e per mille (include/ffhip.h "truth from map")
-static long long map_truth_bound(long long N, long long e) { return (N + 1) + (N + 1) * e / 1000; }
-// ... and the front's share in that mode: no truth's length is known here, so every read of N > 0 blocks is listed with m = 0 and status 1 for k_map_stretch to
-// patch, and its share of the truths, its workspace and its ops are those of bound(N, e)
-static int truth_prepare_from_map(ffhip_batch *b) {
-    ffhip_batch::Truth &f = b->tru;
-    const int nR = batch_nreads(b);
-    if (!(b->run_flags & FFHIP_RUN_MAP)) return set_err(FFHIP_EINVAL, "truth from map: the run does not make the map records (FFHIP_RUN_TRUTH goes with FFHIP_RUN_MAP in this mode)");
-    if (!b->map.ref) return set_err(FFHIP_EINVAL, "truth from map: no reference is attached to the batch (ffhip_batch_set_map)");
-    if (int rc = f.list.grow(b, b->stream, (size_t)b->cap_reads * sizeof(TruthRead), "truth: the reads' list")) return rc;
-    std::vector<TruthRead> per[kTruthForms];
-    std::vector<size_t> off((size_t)nR + 1, 0);
-    size_t ws = 0, seq = 0, ops = 0;
-    for (int r = 0; r < nR; r++) {
-        const int N = b->hTb[r];
-        const long long bound = N > 0 ? map_truth_bound(N, b->map.max_error) : 0;
-        if (bound > kTruthMaxLen) return set_err(FFHIP_EINVAL, "truth from map: read %d's stretch may have %lld bases (at most %d)", r, bound, kTruthMaxLen);
-        if (seq + (size_t)bound > (size_t)0xffffffffu)
-            return set_err(FFHIP_EINVAL, "truth from map: the reads' bounds come to more than 2^32 - 1 bases together (read %d: %lld), which the list's 32-bit offsets cannot hold", r, bound);
-        const int cap = N > 0 ? (int)bound + N + 1 : 0;
-        TruthRead tr{ ws, ops, (unsigned)seq, 0, N > 0 ? 1 : 0, r, cap, (int)bound };
-        int form = 0;
-        if (tr.status == 1) {
-            form = truth_form(std::min<long long>(2ll * f.band + 1, (long long)N + 2));
-            if (form < 0) return set_err(FFHIP_EINVAL, "truth: read %d's window of min(2 band + 1, blocks + 2) cells is more than %d", r, truth_max_window());
-            ws += truth_ws_words(form, (int)bound);
-        }
-        off[r] = ops;
-        seq += (size_t)bound; ops += (size_t)cap;
-        per[form].push_back(tr);
-    }
-    off[nR] = ops;
-    if (int rc = dgrow(b, (void **)&f.dseq, &f.dseq_cap, seq ? seq : 1, "truth from map: the truths")) return rc;
-    if (int rc = dgrow(b, (void **)&f.ws, &f.ws_cap, ws * 8, "truth: the traceback workspace")) return rc;
-    if (int rc = f.rec.grow(b, b->stream, truth_ops_at(b) + ops, "truth: the records and ops")) return rc;
-    f.off = std::move(off);
-    return forms_upload(b, f, per, f.count, nR);
-}
-// Truth, the front's share: as remap's.  The ops' bytes follow from the truths and the reads' blocks, so records and ops grow here.
-static_assert(sizeof(TruthRead) == 40, "the reads' list is copied as it stands");
-static int truth_prepare(ffhip_batch *b) {
-    ffhip_batch::Truth &f = b->tru;
-    const int nR = batch_nreads(b);
-    if (f.from_map) return truth_prepare_from_map(b);
-    if (!f.set) return set_err(FFHIP_EINVAL, "truth: no truths are set for the batch (ffhip_batch_set_truth)");
-    if ((int)f.seq.size() != nR) return set_err(FFHIP_EINVAL, "truth: truths were set for %zu reads, the batch holds %d", f.seq.size(), nR);
-    if (int rc = f.list.grow(b, b->stream, (size_t)b->cap_reads * sizeof(TruthRead), "truth: the reads' list")) return rc;
-    std::vector<TruthRead> per[kTruthForms];
-    std::vector<size_t> off((size_t)nR + 1, 0);
-    size_t ws = 0, seq = 0, ops = 0;
-    for (int r = 0; r < nR; r++) {
-        const int N = b->hTb[r], m = (int)f.seq[r].size();
-        const int cap = f.state[r] == 1 && N > 0 ? m + N + 1 : 0;
-        TruthRead tr{ ws, ops, (unsigned)seq, m, N > 0 ? f.state[r] : 0, r, cap, 0 };
-        int form = 0;
-        if (tr.status == 1) {
-            form = truth_form(std::min<long long>(2ll * f.band + 1, (long long)N + 2));
-            if (form < 0) return set_err(FFHIP_EINVAL, "truth: read %d's window of min(2 band + 1, blocks + 2) cells is more than %d", r, truth_max_window());
-            ws += truth_ws_words(form, m);
-        }
-        off[r] = ops;
-        seq += (size_t)m; ops += (size_t)cap;
-        per[form].push_back(tr);
-    }
-    off[nR] = ops;
-    if (int rc = dgrow(b, (void **)&f.ws, &f.ws_cap, ws * 8, "truth: the traceback workspace")) return rc;
-    if (int rc = f.rec.grow(b, b->stream, truth_ops_at(b) + ops, "truth: the records and ops")) return rc;
-    f.off = std::move(off);
-    return forms_upload(b, f, per, f.count, nR);
-}
-static void truth_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {           // from the strings and lengths k_assemble has just written
-    ffhip_batch::Truth &f = b->tru;
-    if (f.from_map) {                                       // every form's entries in one launch, behind k_map_finish (map's row stands ahead of truth's in kAnnots)
-        launch_map_stretch(b->stream, b->map.ref->view, b->map.rec.dev, (TruthRead *)f.list.dev, batch_nreads(b), f.dseq);
-        b->launches[5]++;
-    }
-    forms_launch(b, f, f.count, [&](int form, size_t at, int n) {
-        launch_truth(b->stream, form, (const TruthRead *)f.list.dev + at, n, f.dseq, b->bases(), b->lens(), f.band, f.ws, (int *)f.rec.dev, f.rec.dev + truth_ops_at(b), b->Tb, tbr, rmap);
-    });
-}
-static size_t truth_bytes(const ffhip_batch *b) { return truth_ops_at(b) + (b->tru.off.empty() ? 0 : b->tru.off.back()); }
-static void truth_spans(const ffhip_batch *b, int r, AnnotSpan out[2]) {
-    out[0] = AnnotSpan{ (size_t)r * kTruthRecInts * 4, (size_t)kTruthRecInts * 4 };
-    out[1] = AnnotSpan{ truth_ops_at(b) + b->tru.off[r], b->tru.off[r + 1] - b->tru.off[r] };
-}
-
-// Events, site mods and variants: 16-byte records, a read's one behind the other from its offset
-static_assert(sizeof(ffhip_event) == 16 && sizeof(ffhip_site_mod) == 16 && sizeof(ffhip_variant_call) == 16, "their kernels write a record as one 16-byte store");
-static size_t perbase_bytes(const ffhip_batch::PerBase &f) { return f.total() * 16; }
-static void perbase_spans(const ffhip_batch::PerBase &f, int r, AnnotSpan out[2]) { span1(out, f.off[r] * 16, (f.off[r + 1] - f.off[r]) * 16); }
-
-// Events, the front's share, behind remap's: every read's place in the one buffer, from the L of its sequence, and where its samples stand (the addresses
-// rerun_on_f32_path reads them at); the buffer and its mirror grow here.  A read remap_prepare refuses has no room and no entry.
-static_assert(sizeof(EventRead) == 32, "the reads' list is copied as it stands");
-static int events_prepare(ffhip_batch *b) {
-    ffhip_batch::PerBase &f = b->evt;
-    const int nR = batch_nreads(b), st = total_stride(b->mdl);
-    if (int rc = f.list.grow(b, b->stream, (size_t)b->cap_reads * sizeof(EventRead), "events: the reads' list")) return rc;
-    std::vector<size_t> off((size_t)nR + 1, 0);
-    std::vector<EventRead> list;
-    size_t at = 0;
-    for (int r = 0; r < nR; r++) {
-        const int L = (int)b->rmp.seq[r].size();
-        off[r] = at;
-        if (!remap_mappable(b, r)) continue;
-        const size_t sig = (b->packed ? (size_t)b->v_slot[r] * b->sbuf[0].rs + (size_t)b->v_off[r] * st : (size_t)r * b->sbuf[0].rs) + kSamplePad;
-        list.push_back(EventRead{ sig, at, b->hT[r], L, r, 0 });
-        at += (size_t)L;
-    }
-    off[nR] = at;
-    if (int rc = f.rec.grow(b, b->stream, std::max<size_t>(at, 1) * sizeof(ffhip_event), "events: the reads' events")) return rc;
-    f.off = std::move(off);
-    f.reads = (int)list.size();
-    if (list.empty()) return FFHIP_OK;
-    memcpy(f.list.host, list.data(), list.size() * sizeof(EventRead));
-    return f.list.copy_up(list.size() * sizeof(EventRead), b->stream);
-}
-static void events_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {          // from the path k_remap has just written and the signal the convolutions read
-    if (b->evt.reads > 0) {
-        launch_events(b->stream, (const EventRead *)b->evt.list.dev, b->evt.reads, b->sbuf[0].p, total_stride(b->mdl), b->rmp.rec.dev, b->rmp.rec.dev + remap_moves_at(b),
-                      b->evt.rec.dev, b->Tb, tbr, rmap);
-        b->launches[5]++;
-    }
-    b->evt.valid = 1;
-}
-static size_t events_bytes(const ffhip_batch *b) { return perbase_bytes(b->evt); }
-static void events_spans(const ffhip_batch *b, int r, AnnotSpan out[2]) { perbase_spans(b->evt, r, out); }
-
-// Site mods and variants, the front's share, behind remap's: the reads that can be mapped and have an entry (a C or Z; a variant), their entries one read behind the
-// other (an entry's place in its list is its record's place in the buffer), every listed read's L + 1 words of starts; buffers, mirrors and workspace grow here.
-// entries_of(r, k, &ent) appends read r's entries as those of listed read k and says whether there are any.  The two lists are one pinned image and one upload:
-// the entries in front of the reads (entries_first) or behind them.  A read remap_prepare refuses has no entry.
-struct SitesText { const char *name, *noun, *records, *starts, *lists; };
-template <class Entry, class EntriesOf> static int sites_prepare(ffhip_batch *b, ffhip_batch::Sites &f, bool entries_first, const SitesText &t, EntriesOf entries_of) {
-    const int nR = batch_nreads(b);
-    std::vector<size_t> off((size_t)nR + 1, 0);
-    std::vector<SiteRead> list;
-    std::vector<Entry> ent;
-    size_t words = 0, seq = 0;
-    for (int r = 0; r < nR; r++) {
-        const int L = (int)b->rmp.seq[r].size();
-        off[r] = ent.size();
-        if (remap_mappable(b, r) && entries_of(r, (int)list.size(), &ent)) {
-            list.push_back(SiteRead{ words, (unsigned)seq, L, r, 0 });
-            words += (size_t)L + 1;
-        }
-        seq += (size_t)L;
-    }
-    off[nR] = ent.size();
-    if (ent.size() > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "%s: %zu %s in one batch", t.name, ent.size(), t.noun);
-    const size_t lb = list.size() * sizeof(SiteRead), eb = ent.size() * sizeof(Entry);
-    if (int rc = f.rec.grow(b, b->stream, std::max<size_t>(ent.size(), 1) * 16, t.records)) return rc;
-    if (int rc = dgrow(b, (void **)&f.start, &f.start_cap, std::max<size_t>(words, 1) * 4, t.starts)) return rc;
-    if (int rc = f.list.grow(b, b->stream, std::max<size_t>(lb + eb, 8), t.lists)) return rc;
-    f.off = std::move(off);
-    f.reads = (int)list.size();
-    if (ent.empty()) return FFHIP_OK;
-    memcpy(f.list.host + (entries_first ? eb : 0), list.data(), lb);
-    memcpy(f.list.host + (entries_first ? 0 : lb), ent.data(), eb);
-    return f.list.copy_up(lb + eb, b->stream);
-}
-
-static_assert(sizeof(SiteRead) == 24 && sizeof(SiteMod) == 8, "the lists are copied as they stand");
-static int sitemods_prepare(ffhip_batch *b) {
-    static const SitesText t{ "site mods", "sites", "site mods: the sites' records", "site mods: the workspace of starts", "site mods: the lists of reads and sites" };
-    return sites_prepare<SiteMod>(b, b->smd, false, t, [&](int r, int k, std::vector<SiteMod> *out) { return sitemods_sites(b->rmp.seq[r].data(), b->rmp.seq[r].size(), k, out) > 0; });
-}
-static void sitemods_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {        // from that path, the transitions and the coded sequences
-    ffhip_batch::Sites &f = b->smd;
-    if (f.total() > 0) {
-        launch_site_mods(b->stream, (const SiteRead *)f.list.dev, f.reads, (const SiteMod *)(f.list.dev + (size_t)f.reads * sizeof(SiteRead)), (int)f.total(), b->rmp.dseq, b->trans,
-                         b->mdl->Ps, f.context, f.all, b->rmp.rec.dev, b->rmp.rec.dev + remap_moves_at(b), f.start, f.rec.dev, b->Tb, tbr, rmap);
-        b->launches[5] += 2;
-    }
-    f.valid = 1;
-}
-static size_t sitemods_bytes(const ffhip_batch *b) { return perbase_bytes(b->smd); }
-static void sitemods_spans(const ffhip_batch *b, int r, AnnotSpan out[2]) { perbase_spans(b->smd, r, out); }
-
-// (the variants stand in front of the reads: an entry is read as 16-byte words)
-static_assert(sizeof(VarEntry) == 32 && sizeof(Variant) == sizeof(ffhip_variant) && sizeof(ffhip_variant) == 24, "the lists are copied as they stand");
-static int variants_prepare(ffhip_batch *b) {
-    static const SitesText t{ "variants", "variants", "variants: the variants' records", "variants: the workspace of starts", "variants: the list of variants and reads" };
-    const int nR = batch_nreads(b);
-    if (b->var.set.empty()) return set_err(FFHIP_EINVAL, "variants: none are set for the batch (ffhip_batch_set_remap_variants)");
-    if ((int)b->var.set.size() != nR) return set_err(FFHIP_EINVAL, "variants: lists were set for %zu reads, the batch holds %d", b->var.set.size(), nR);
-    return sites_prepare<VarEntry>(b, b->var, true, t, [&](int r, int k, std::vector<VarEntry> *out) {
-        for (size_t i = 0; i < b->var.set[r].size(); i++) {
-            VarEntry e{ k, (int)i, {} };
-            memcpy(&e.v, &b->var.set[r][i], sizeof e.v);
-            out->push_back(e);
-        }
-        return !b->var.set[r].empty();
-    });
-}
-static void variants_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {        // (likewise)
-    ffhip_batch::Variants &f = b->var;
-    if (f.total() > 0) {
-        launch_variants(b->stream, (const SiteRead *)(f.list.dev + f.total() * sizeof(VarEntry)), f.reads, (const VarEntry *)f.list.dev, (int)f.total(), b->rmp.dseq, b->trans,
-                        b->mdl->Ps, b->mdl->nbase, f.context, f.all, b->rmp.rec.dev, b->rmp.rec.dev + remap_moves_at(b), f.start, f.rec.dev, b->Tb, tbr, rmap);
-        b->launches[5] += 2;
-    }
-    f.valid = 1;
-}
-static size_t variants_bytes(const ffhip_batch *b) { return perbase_bytes(b->var); }
-static void variants_spans(const ffhip_batch *b, int r, AnnotSpan out[2]) { perbase_spans(b->var, r, out); }
-
-// The table, in launch order (ffhip_batch::annot has the same): the map stands ahead of truth, which in its from-map mode reads the records k_map_finish has just written; truth reads the strings as barcodes and adapters do; the poly tail reads the path and the signal; events, site mods and variants read what
-// k_remap has just written
-constexpr AnnotRow kAnnots[ffhip_batch::AN_COUNT] = {
-    { FFHIP_RUN_BARCODES, nullptr, 0, "barcodes: a flip-flop model only (the run-length model has no base strings)", "barcodes need a decoded run (FFHIP_RUN_NO_DECODE is set)",
-      barcodes_prepare, barcodes_launch, barcodes_bytes, barcodes_spans },
-    { FFHIP_RUN_ADAPTERS, nullptr, 0, "adapters: a flip-flop model only (the run-length model has no base strings)", "adapters need a decoded run (FFHIP_RUN_NO_DECODE is set)",
-      adapters_prepare, adapters_launch, adapters_bytes, adapters_spans },
-    { FFHIP_RUN_MAP, nullptr, 0, "map: a flip-flop model only (the run-length model has no base strings)", "map needs a decoded run (FFHIP_RUN_NO_DECODE is set)",
-      map_prepare, map_launch, map_bytes, map_spans },
-    { FFHIP_RUN_POLYTAIL, nullptr, 0, "poly tail: a flip-flop model only (the run-length model's path is not one of bases)", "poly tail needs a decoded run (FFHIP_RUN_NO_DECODE is set)",
-      polytail_prepare, polytail_launch, polytail_bytes, polytail_spans },
-    { FFHIP_RUN_TRUTH, nullptr, 0, "truth: a flip-flop model only (the run-length model's call is a list of runs)", "truth needs a decoded run (FFHIP_RUN_NO_DECODE is set)",
-      truth_prepare, truth_launch, truth_bytes, truth_spans },
-    { FFHIP_RUN_REMAP, nullptr, 0, "remap: a flip-flop model only (the run-length model's scores are not transitions between bases)", "remap needs a decoded run (FFHIP_RUN_NO_DECODE is set)",
-      remap_prepare, remap_launch, remap_bytes, remap_spans },
-    { FFHIP_RUN_EVENTS, "events: the signal of a mapped read's bases needs the mapping (FFHIP_RUN_EVENTS goes with FFHIP_RUN_REMAP)", 0, nullptr, nullptr,
-      events_prepare, events_launch, events_bytes, events_spans },
-    { FFHIP_RUN_REMAP_MODS, "site mods: the scores of a mapped sequence's C positions need the mapping (FFHIP_RUN_REMAP_MODS goes with FFHIP_RUN_REMAP)", 5,
-      "site mods: the model has no modified base (FFHIP_RUN_REMAP_MODS takes a model of the alphabet ACGTZ)", nullptr, sitemods_prepare, sitemods_launch, sitemods_bytes, sitemods_spans },
-    { FFHIP_RUN_REMAP_VARIANTS, "variants: the scores of a mapped sequence's alleles need the mapping (FFHIP_RUN_REMAP_VARIANTS goes with FFHIP_RUN_REMAP)", 0, nullptr, nullptr,
-      variants_prepare, variants_launch, variants_bytes, variants_spans },
-};
-// the front's share of them all: may this run ask, then the feature's own preparations
-static int annots_prepare(ffhip_batch *b, unsigned flags) {
-    const ffhip_model *m = b->mdl;
-    for (int i = 0; i < ffhip_batch::AN_COUNT; i++) {
-        const AnnotRow &row = kAnnots[i];
-        b->annot(i).valid = 0;
-        if (!(flags & row.flag)) continue;
-        if (row.remap_text && !(flags & FFHIP_RUN_REMAP)) return set_err(FFHIP_EINVAL, "%s", row.remap_text);
-        if (row.model_text && (m->kind == FFHIP_NET_LSTM5_RLE || (row.nbase && m->nbase != row.nbase))) return set_err(FFHIP_EINVAL, "%s", row.model_text);
-        if (row.undecoded_text && (flags & FFHIP_RUN_NO_DECODE)) return set_err(FFHIP_EINVAL, "%s", row.undecoded_text);
-        if (int rc = row.prepare(b)) return rc;
-    }
-    return FFHIP_OK;
-}
-// Pileup (include/ffhip.h "pileup"): no record, no buffer of the batch's, so no row above.  The front's share: may this run ask
-static int pileup_check(const ffhip_batch *b, unsigned flags) {
-    if (!(flags & FFHIP_RUN_PILEUP)) return FFHIP_OK;
-    if (!(flags & FFHIP_RUN_TRUTH)) return set_err(FFHIP_EINVAL, "pileup: the run does not make the truth records (FFHIP_RUN_PILEUP goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH)");
-    if (!(flags & FFHIP_RUN_MAP)) return set_err(FFHIP_EINVAL, "pileup: the run does not make the map records (FFHIP_RUN_PILEUP goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH)");
-    if (!b->tru.from_map) return set_err(FFHIP_EINVAL, "pileup: the batch is not in the mode of truth from map (ffhip_batch_set_truth_from_map)");
-    if (!b->pile) return set_err(FFHIP_EINVAL, "pileup: no pileup is attached to the batch (ffhip_batch_set_pileup)");
-    if (b->pile->ref != b->map.ref) return set_err(FFHIP_EINVAL, "pileup: the attached pileup belongs to another reference than the batch's map reference");
-    return FFHIP_OK;
-}
-// ... and the finish's: the records, ops and letters are final (ffhip_batch_finish), so every listed read is counted once, on the batch's stream, unwaited for
-static void pileup_launch(ffhip_batch *b) {
-    ffhip_pileup *p = b->pile;
-    const ReadMap rmap = b->packed ? ReadMap{ b->d_vb0, b->d_vb1, b->nread } : ReadMap();
-    launch_pileup(b->stream, p->ref->view, (const TruthRead *)b->tru.list.dev, batch_nreads(b), b->map.rec.dev, (const int *)b->tru.rec.dev,
-                  b->tru.rec.dev + truth_ops_at(b), b->bases(), b->Tb, rmap, p->view);
-    for (int i = 0; i < b->eng->nstreams; i++) if (b->eng->streams[i] == b->stream) p->used[i] = true;
-}
-// the copies of a finished run beside the block's: one a feature the run made, if it has a byte to bring
-static int annots_copy_down(ffhip_batch *b) {
-    for (int i = 0; i < ffhip_batch::AN_COUNT; i++)
-        if (const size_t n = b->annot(i).valid ? kAnnots[i].bytes(b) : 0)
-            if (int rc = b->annot(i).rec.copy_down(n, b->stream)) return rc;
-    return FFHIP_OK;
-}
-
 // One run of a batch is enqueued in three phases -- front (convolutions), the recurrent stack, back (head, CRF, decode) -- so that
 // ffhip_batch_run_pair can put the layer launches of TWO batches into one grid between their fronts and backs (`paired`).  The front
 // decides the run's path (b->run_path); the layers and the back follow it.
@@ -2371,8 +1742,6 @@ extern "C" int ffhip_batch_paired(const ffhip_batch *b) { return (b && b->paired
 // have no bound (the reference has none: layers.c:24-33); their results replace the clamped ones in the batch's buffers.  Rare by
 // construction -- a normalised sample in the hundreds -- so this path is written for clarity: a side batch of 16 slots with the
 // same capacity (hence the same strides: a read's results are contiguous device-to-device copies), created on first use.
-static int remap_adopt(ffhip_batch *b, std::vector<std::vector<unsigned short>> &&seq, std::vector<signed char> &&state, int band);
-static int truth_adopt(ffhip_batch *b, std::vector<std::vector<uint8_t>> &&seq, std::vector<signed char> &&state, int band);
 static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
     const ffhip_model *m = b->mdl;
     if (!b->side) {
@@ -2520,7 +1889,7 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
 extern "C" int ffhip_batch_f32_reruns(const ffhip_batch *b) { return b ? b->reruns : -1; }
 extern "C" unsigned long long ffhip_engine_f32_reruns(const ffhip_engine *eng) { return eng ? eng->f32_reruns : 0; }
 
-static bool results_ok(const ffhip_batch *b, int read) {
+bool results_ok(const ffhip_batch *b, int read) {
     if (!b || !b->finished || read < 0 || read >= batch_nreads(b)) { set_err(FFHIP_EINVAL, "results not available (finish the batch, check the read index)"); return false; }
     if (b->hTb[read] == 0) { set_err(FFHIP_EINVAL, "slot %d of the batch is empty", read); return false; }
     return true;
@@ -2576,459 +1945,6 @@ extern "C" int ffhip_batch_moves(const ffhip_batch *b, int read, const uint8_t *
     if (!(b->res_made & res_bit(RS_MOVES))) return set_err(FFHIP_EINVAL, "the move table was not made in this run (FFHIP_RUN_MOVES)");
     *moves = b->res.on_host<uint8_t>(RF_MV) + read_row1(b, read);
     if (nblock) *nblock = (size_t)b->hTb[read];
-    return FFHIP_OK;
-}
-
-// ---- barcodes (include/ffhip.h "barcodes"; the kernel: ffhip_barcodes.hip)
-extern "C" ffhip_barcodes *ffhip_barcodes_upload(ffhip_engine *eng, int n, const char *const *seq, int window) {
-    if (!eng || !seq) { set_err(FFHIP_EINVAL, "null engine or kit"); return nullptr; }
-    if (n < 1 || n > kBarcodeMaxKit) { set_err(FFHIP_EINVAL, "a barcode kit holds 1 .. %d patterns, not %d", kBarcodeMaxKit, n); return nullptr; }
-    if (window < 1 || window > kBarcodeMaxWindow) { set_err(FFHIP_EINVAL, "the barcode window is 1 .. %d bases, not %d", kBarcodeMaxWindow, window); return nullptr; }
-    std::vector<unsigned long long> peq((size_t)n * 8, 0ull);
-    std::vector<int> len(n, 0);
-    int lmin = kBarcodeMaxLen, lmax = 0;
-    for (int k = 0; k < n; k++) {
-        const size_t L = seq[k] ? strnlen(seq[k], kBarcodeMaxLen + 1) : 0;
-        if (L < 1 || L > (size_t)kBarcodeMaxLen) { set_err(FFHIP_EINVAL, "barcode %d: a pattern has 1 .. %d bases", k, kBarcodeMaxLen); return nullptr; }
-        for (size_t i = 0; i < L; i++) {
-            const char *at = strchr("ACGT", seq[k][i]);
-            if (!at) { set_err(FFHIP_EINVAL, "barcode %d: character %zu is not one of ACGT", k, i); return nullptr; }
-            peq[((size_t)k * 4 + (size_t)(at - "ACGT")) * 2 + i / 64] |= 1ull << (i % 64);
-        }
-        len[k] = (int)L;
-        lmin = std::min(lmin, (int)L); lmax = std::max(lmax, (int)L);
-    }
-    hipSetDevice(eng->device);
-    ffhip_barcodes *kit = new ffhip_barcodes();
-    kit->eng = eng; kit->lmin = lmin;
-    if (hipMalloc(&kit->d_peq, peq.size() * 8) != hipSuccess || hipMalloc(&kit->d_len, len.size() * 4) != hipSuccess) {
-        set_err(FFHIP_ENOMEM, "device allocation failed"); ffhip_barcodes_free(kit); return nullptr;
-    }
-    if (hipMemcpy(kit->d_peq, peq.data(), peq.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(kit->d_len, len.data(), len.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        set_err(FFHIP_EHIP, "upload of the barcode kit failed"); ffhip_barcodes_free(kit); return nullptr;
-    }
-    kit->kit = BarcodeKit{ (const unsigned long long *)kit->d_peq, (const int *)kit->d_len, n, window, lmax > 64 ? 2 : 1 };
-    return kit;
-}
-extern "C" void ffhip_barcodes_free(ffhip_barcodes *kit) {
-    if (!kit) return;
-    hipSetDevice(kit->eng->device);
-    if (kit->d_peq) hipFree(kit->d_peq);
-    if (kit->d_len) hipFree(kit->d_len);
-    delete kit;
-}
-extern "C" int ffhip_batch_set_barcodes(ffhip_batch *b, const ffhip_barcodes *kit, int max_dist, int min_sep, int both_ends) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (!kit) { b->bc.kit = nullptr; return FFHIP_OK; }
-    if (kit->eng != b->eng) return set_err(FFHIP_EINVAL, "the barcode kit belongs to another engine");
-    if (max_dist > 255 || min_sep > 255) return set_err(FFHIP_EINVAL, "barcodes: max_dist and min_sep are at most 255");
-    b->bc.kit = kit;
-    b->bc.max_dist = max_dist < 0 ? kit->lmin / 4 : max_dist;
-    b->bc.min_sep = min_sep < 0 ? 3 : min_sep;
-    b->bc.both = both_ends ? 1 : 0;
-    return FFHIP_OK;
-}
-extern "C" int ffhip_batch_barcode(const ffhip_batch *b, int read, ffhip_barcode_call *out) {
-    if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
-    if (!b->bc.valid || !b->bc.rec.host) return set_err(FFHIP_EINVAL, "barcode records were not made in this run (FFHIP_RUN_BARCODES)");
-    memcpy(out, b->bc.rec.host + (size_t)read * sizeof *out, sizeof *out);
-    return FFHIP_OK;
-}
-
-// ---- adapters (include/ffhip.h "adapters"; the kernel: ffhip_adapters.hip)
-extern "C" int ffhip_adapter_segment(void) { return kAdSeg; }
-extern "C" ffhip_adapters *ffhip_adapters_upload(ffhip_engine *eng, int n, const char *const *seq) {
-    if (!eng || !seq) { set_err(FFHIP_EINVAL, "null engine or kit"); return nullptr; }
-    if (n < 1 || n > kAdapterMaxKit) { set_err(FFHIP_EINVAL, "an adapter kit holds 1 .. %d patterns, not %d", kAdapterMaxKit, n); return nullptr; }
-    std::vector<unsigned long long> peq((size_t)n * 8, 0ull);       // [2 n][4]: as given, then the reverse complement
-    std::vector<int> len(n, 0);
-    for (int k = 0; k < n; k++) {
-        const size_t L = seq[k] ? strnlen(seq[k], kAdapterMaxLen + 1) : 0;
-        if (L < 1 || L > (size_t)kAdapterMaxLen) { set_err(FFHIP_EINVAL, "adapter %d: a pattern has 1 .. %d bases", k, kAdapterMaxLen); return nullptr; }
-        for (size_t i = 0; i < L; i++) {
-            const char *at = strchr("ACGT", seq[k][i]);
-            if (!at) { set_err(FFHIP_EINVAL, "adapter %d: character %zu is not one of ACGT", k, i); return nullptr; }
-            const size_t c = (size_t)(at - "ACGT");
-            peq[((size_t)2 * k) * 4 + c] |= 1ull << i;
-            peq[((size_t)2 * k + 1) * 4 + (3 - c)] |= 1ull << (L - 1 - i);
-        }
-        len[k] = (int)L;
-    }
-    hipSetDevice(eng->device);
-    ffhip_adapters *kit = new ffhip_adapters();
-    kit->eng = eng;
-    if (hipMalloc(&kit->d_peq, peq.size() * 8) != hipSuccess || hipMalloc(&kit->d_len, len.size() * 4) != hipSuccess) {
-        set_err(FFHIP_ENOMEM, "device allocation failed"); ffhip_adapters_free(kit); return nullptr;
-    }
-    if (hipMemcpy(kit->d_peq, peq.data(), peq.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(kit->d_len, len.data(), len.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        set_err(FFHIP_EHIP, "upload of the adapter kit failed"); ffhip_adapters_free(kit); return nullptr;
-    }
-    kit->kit = AdapterKit{ (const unsigned long long *)kit->d_peq, (const int *)kit->d_len, n };
-    return kit;
-}
-extern "C" void ffhip_adapters_free(ffhip_adapters *kit) {
-    if (!kit) return;
-    hipSetDevice(kit->eng->device);
-    if (kit->d_peq) hipFree(kit->d_peq);
-    if (kit->d_len) hipFree(kit->d_len);
-    delete kit;
-}
-extern "C" int ffhip_batch_set_adapters(ffhip_batch *b, const ffhip_adapters *kit, int max_dist) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (!kit) { b->ad.kit = nullptr; return FFHIP_OK; }
-    if (kit->eng != b->eng) return set_err(FFHIP_EINVAL, "the adapter kit belongs to another engine");
-    b->ad.kit = kit;
-    b->ad.max_dist = max_dist < 0 ? -1 : std::min(max_dist, kAdapterMaxLen - 1);
-    return FFHIP_OK;
-}
-extern "C" int ffhip_batch_adapters(const ffhip_batch *b, int read, ffhip_adapter_header *header, const ffhip_adapter_hit **hits) {
-    if (!results_ok(b, read) || !header || !hits) return FFHIP_EINVAL;
-    if (!b->ad.valid || !b->ad.rec.host) return set_err(FFHIP_EINVAL, "adapter records were not made in this run (FFHIP_RUN_ADAPTERS)");
-    const uint8_t *rec = b->ad.rec.host + (size_t)read * kAdapterRecBytes;
-    memcpy(header, rec, sizeof *header);
-    *hits = (const ffhip_adapter_hit *)(rec + sizeof *header);
-    return FFHIP_OK;
-}
-
-// ---- map (include/ffhip.h "map"; the kernels: ffhip_map.hip)
-extern "C" int ffhip_map_segment(void) { return kMapSeg; }
-extern "C" ffhip_map_ref *ffhip_map_ref_upload(ffhip_engine *eng, int n, const char *const *seq) {
-    if (!eng || !seq) { set_err(FFHIP_EINVAL, "null engine or reference"); return nullptr; }
-    if (n < 1 || n > kMapMaxRecords) { set_err(FFHIP_EINVAL, "a reference holds 1 .. %d records, not %d", kMapMaxRecords, n); return nullptr; }
-    std::vector<int2> recs(n);
-    std::vector<int> rowoff((size_t)2 * n);
-    std::vector<MapTask> tasks;
-    size_t total = 0, entries = 0;
-    for (int k = 0; k < n; k++) {
-        const size_t m = seq[k] ? strnlen(seq[k], (size_t)kMapMaxTotal + 1) : 0;
-        if (m < 1) { set_err(FFHIP_EINVAL, "reference record %d: position 0: a record has 1 or more bases", k); return nullptr; }
-        if (total + m > (size_t)kMapMaxTotal) {
-            set_err(FFHIP_EINVAL, "reference record %d: position %zu: the records hold at most %d bases together", k, (size_t)kMapMaxTotal - total, kMapMaxTotal);
-            return nullptr;
-        }
-        recs[k] = make_int2((int)total, (int)m);
-        total += m;
-        for (int o = 0; o < 2; o++) {
-            rowoff[2 * k + o] = (int)entries;
-            entries += m + 1;
-            for (size_t s = 0; s < m; s += kMapSeg) tasks.push_back(MapTask{ 2 * k + o, (int)s, (int)std::min(m, s + kMapSeg), 0 });
-        }
-    }
-    std::vector<unsigned> words((total + 2 * kMapPad + 15) / 16 + 2, 0u);
-    for (int k = 0; k < n; k++)
-        for (int i = 0; i < recs[k].y; i++) {
-            const char *at = strchr("ACGT", seq[k][i]);
-            if (!at) { set_err(FFHIP_EINVAL, "reference record %d: position %d: the character is not one of ACGT", k, i); return nullptr; }
-            const size_t g = (size_t)kMapPad + recs[k].x + i;
-            words[g >> 4] |= (unsigned)(at - "ACGT") << (2 * (g & 15));
-        }
-    hipSetDevice(eng->device);
-    ffhip_map_ref *ref = new ffhip_map_ref();
-    ref->eng = eng;
-    ref->score_entries = entries;
-    for (int k = 0; k < n; k++) ref->rec_len.push_back(recs[k].y);
-    const struct { void **dev; const void *host; size_t bytes; } up[4] = { { &ref->d_words, words.data(), words.size() * 4 }, { &ref->d_tasks, tasks.data(), tasks.size() * sizeof(MapTask) },
-                                                                          { &ref->d_recs, recs.data(), recs.size() * sizeof(int2) }, { &ref->d_rowoff, rowoff.data(), rowoff.size() * 4 } };
-    for (const auto &u : up) {
-        if (hipMalloc(u.dev, u.bytes) != hipSuccess) { *u.dev = nullptr; set_err(FFHIP_ENOMEM, "device allocation failed"); ffhip_map_ref_free(ref); return nullptr; }
-        if (hipMemcpy(*u.dev, u.host, u.bytes, hipMemcpyHostToDevice) != hipSuccess) { set_err(FFHIP_EHIP, "upload of the reference failed"); ffhip_map_ref_free(ref); return nullptr; }
-    }
-    ref->view = MapRefView{ (const unsigned *)ref->d_words, (const MapTask *)ref->d_tasks, (const int2 *)ref->d_recs, (const int *)ref->d_rowoff, (int)tasks.size(), n };
-    return ref;
-}
-extern "C" void ffhip_map_ref_free(ffhip_map_ref *ref) {
-    if (!ref) return;
-    hipSetDevice(ref->eng->device);
-    for (void *p : { ref->d_words, ref->d_tasks, ref->d_recs, ref->d_rowoff }) if (p) hipFree(p);
-    delete ref;
-}
-extern "C" int ffhip_batch_set_map(ffhip_batch *b, const ffhip_map_ref *ref, int window, int max_error) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (!ref) { b->map.ref = nullptr; return FFHIP_OK; }
-    if (ref->eng != b->eng) return set_err(FFHIP_EINVAL, "the reference belongs to another engine");
-    if (const char *why = map_invalid(window, max_error)) return set_err(FFHIP_EINVAL, "map: %s", why);
-    b->map.ref = ref;
-    b->map.window = window < 0 ? kMapMaxAnchor : window;
-    b->map.max_error = max_error < 0 ? 250 : max_error;
-    return FFHIP_OK;
-}
-extern "C" int ffhip_batch_map(const ffhip_batch *b, int read, ffhip_map_call *out) {
-    if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
-    if (!b->map.valid || !b->map.rec.host) return set_err(FFHIP_EINVAL, "map records were not made in this run (FFHIP_RUN_MAP)");
-    memcpy(out, b->map.rec.host + (size_t)read * kMapRecBytes, sizeof *out);
-    return FFHIP_OK;
-}
-
-// ---- poly tail (include/ffhip.h "poly tail"; the kernel: ffhip_polytail.hip)
-extern "C" int ffhip_batch_set_polytail(ffhip_batch *b, const ffhip_polytail_params *params) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "poly tail: the batch is between a run and its finish");
-    if (!params) { b->pt.set = false; return FFHIP_OK; }
-    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "poly tail: a flip-flop model only (the run-length model's path is not one of bases)");
-    PolyTailParams p;
-    memcpy(&p, params, sizeof p);
-    if (const char *why = polytail_invalid(p)) return set_err(FFHIP_EINVAL, "poly tail: %s", why);
-    b->pt.p = *params;
-    b->pt.set = true;
-    return FFHIP_OK;
-}
-extern "C" int ffhip_batch_polytail(const ffhip_batch *b, int read, ffhip_polytail *out) {
-    if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
-    if (!b->pt.valid || !b->pt.rec.host) return set_err(FFHIP_EINVAL, "poly tail records were not made in this run (FFHIP_RUN_POLYTAIL)");
-    memcpy(out, b->pt.rec.host + (size_t)read * kPolyTailRecBytes, sizeof *out);
-    return FFHIP_OK;
-}
-
-// ---- remap (include/ffhip.h "remap"; the kernel: ffhip_remap.hip)
-// new sequences of a batch (remap's coded ones, the truths): flattened, the device buffer grown to them, uploaded
-template <class T> static int seq_adopt(ffhip_batch *b, const std::vector<std::vector<T>> &seq, T **dseq, size_t *cap, const char *what) {
-    size_t total = 0;
-    for (const auto &q : seq) total += q.size();
-    hipSetDevice(b->eng->device);
-    HIP_TRY(hipStreamSynchronize(b->stream), FFHIP_EHIP);
-    if (int rc = dgrow(b, (void **)dseq, cap, (total ? total : 1) * sizeof(T), what)) return rc;
-    std::vector<T> flat;
-    flat.reserve(total);
-    for (const auto &q : seq) flat.insert(flat.end(), q.begin(), q.end());
-    if (total) HIP_TRY(hipMemcpy(*dseq, flat.data(), total * sizeof(T), hipMemcpyHostToDevice), FFHIP_EHIP);
-    return FFHIP_OK;
-}
-static int remap_adopt(ffhip_batch *b, std::vector<std::vector<unsigned short>> &&seq, std::vector<signed char> &&state, int band) {
-    if (int rc = seq_adopt(b, seq, &b->rmp.dseq, &b->rmp.dseq_cap, "remap: the sequences")) return rc;
-    b->rmp.seq = std::move(seq); b->rmp.state = std::move(state);
-    b->rmp.band = band; b->rmp.set = 1;
-    b->var.set.clear();                                     // (variants are validated against the sequences: new sequences detach them)
-    return FFHIP_OK;
-}
-extern "C" int ffhip_batch_set_remap(ffhip_batch *b, int nread, const uint8_t *const *codes, const size_t *len, int band) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (!codes) { b->rmp.set = 0; b->rmp.seq.clear(); b->rmp.state.clear(); b->var.set.clear(); return FFHIP_OK; }
-    const ffhip_model *m = b->mdl;
-    if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "remap: a flip-flop model only (the run-length model's scores are not transitions between bases)");
-    if (!len || nread != batch_nreads(b)) return set_err(FFHIP_EINVAL, "remap: sequences for %d reads, the batch holds %d", nread, batch_nreads(b));
-    if (band < 0) return set_err(FFHIP_EINVAL, "remap: the band half-width is %d (>= 0)", band);
-    std::vector<std::vector<unsigned short>> seq((size_t)nread);
-    std::vector<signed char> state((size_t)nread, 0);
-    for (int r = 0; r < nread; r++) {
-        if (!codes[r]) continue;
-        if (len[r] > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "remap: read %d's sequence has %zu bases", r, len[r]);
-        state[r] = len[r] ? 1 : 2;
-        for (size_t i = 0; i < len[r]; i++) if (codes[r][i] >= m->nbase) return set_err(FFHIP_EINVAL, "remap: read %d, position %zu: code %d is not a base of the model (0 .. %d)", r, i, (int)codes[r][i], m->nbase - 1);
-        if (remap_form((int)len[r], band) < 0 && len[r]) return set_err(FFHIP_EINVAL, "remap: read %d's window of min(2 band + 1, L) cells is more than %d", r, remap_max_window());
-        seq[r].resize(len[r]);
-        remap_code(codes[r], len[r], m->nbase, seq[r].data());
-    }
-    return remap_adopt(b, std::move(seq), std::move(state), band);
-}
-// A mapped read's traceback ends at position 0; and what the accessors of everything made from the mapping ask first: the read's remap record, their outputs saying
-// "nothing", which is the answer for a status other than 1
-static int remap_end_check(int read, const int rec[4]) {
-    return rec[0] == 1 && rec[3] != 0 ? set_err(FFHIP_EHIP, "remap: read %d's traceback ended at position %d, not 0", read, rec[3]) : FFHIP_OK;
-}
-template <class T> static int remap_record(const ffhip_batch *b, int read, int rec[4], const T **out, size_t *n) {
-    memcpy(rec, b->rmp.rec.host + (size_t)read * 16, 16);
-    *out = nullptr; *n = 0;
-    return remap_end_check(read, rec);
-}
-extern "C" int ffhip_batch_remap(const ffhip_batch *b, int read, ffhip_remap_call *out) {
-    if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
-    if (!b->rmp.valid || !b->rmp.rec.host) return set_err(FFHIP_EINVAL, "remap records were not made in this run (FFHIP_RUN_REMAP)");
-    int rec[4];
-    memcpy(rec, b->rmp.rec.host + (size_t)read * 16, 16);
-    out->status = rec[0]; out->L = (size_t)rec[1];
-    memcpy(&out->score, &rec[2], 4);
-    out->nblock = (size_t)b->hTb[read];
-    out->rm = rec[0] == 1 ? b->rmp.rec.host + remap_moves_at(b) + read_row1(b, read) : nullptr;
-    return remap_end_check(read, rec);
-}
-
-// ---- events (include/ffhip.h "events"; the kernel: ffhip_events.hip)
-extern "C" int ffhip_batch_events(const ffhip_batch *b, int read, const ffhip_event **ev, size_t *L) {
-    if (!results_ok(b, read) || !ev || !L) return FFHIP_EINVAL;
-    if (!b->evt.valid || !b->rmp.valid || !b->evt.rec.host) return set_err(FFHIP_EINVAL, "events were not made in this run (FFHIP_RUN_REMAP | FFHIP_RUN_EVENTS)");
-    int rec[4];
-    if (int rc = remap_record(b, read, rec, ev, L)) return rc;
-    if (rec[0] != 1) return FFHIP_OK;
-    if ((size_t)rec[1] != b->evt.off[read + 1] - b->evt.off[read]) return set_err(FFHIP_EHIP, "events: read %d was mapped to %d bases, its events hold %zu", read, rec[1], b->evt.off[read + 1] - b->evt.off[read]);
-    *ev = (const ffhip_event *)b->evt.rec.host + b->evt.off[read];
-    *L = (size_t)rec[1];
-    return FFHIP_OK;
-}
-
-// ---- site mods (include/ffhip.h "site mods"; the kernels: ffhip_sitemods.hip)
-extern "C" int ffhip_batch_set_remap_mods(ffhip_batch *b, int context, int all_paths) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "site mods: the batch is running (ffhip_batch_finish first)");
-    if (context < 0 || context > kSiteModsMaxContext) return set_err(FFHIP_EINVAL, "site mods: the context is %d (0 .. %d)", context, kSiteModsMaxContext);
-    b->smd.context = context; b->smd.all = all_paths ? 1 : 0;
-    return FFHIP_OK;
-}
-extern "C" int ffhip_batch_site_mods(const ffhip_batch *b, int read, const ffhip_site_mod **sm, size_t *nsite) {
-    if (!results_ok(b, read) || !sm || !nsite) return FFHIP_EINVAL;
-    if (!b->smd.valid || !b->rmp.valid || !b->smd.rec.host) return set_err(FFHIP_EINVAL, "site mods were not made in this run (FFHIP_RUN_REMAP | FFHIP_RUN_REMAP_MODS)");
-    int rec[4];
-    if (int rc = remap_record(b, read, rec, sm, nsite)) return rc;
-    if (rec[0] != 1) return FFHIP_OK;
-    *sm = (const ffhip_site_mod *)b->smd.rec.host + b->smd.off[read];
-    *nsite = b->smd.off[read + 1] - b->smd.off[read];
-    return FFHIP_OK;
-}
-
-// ---- variants (include/ffhip.h "variants"; the kernel: ffhip_variants.hip)
-extern "C" int ffhip_batch_set_remap_variants(ffhip_batch *b, int nread, const ffhip_variant *const *vars, const size_t *nvar, int context, int all_paths) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "variants: the batch is running (ffhip_batch_finish first)");
-    if (!vars) { b->var.set.clear(); return FFHIP_OK; }
-    if (!b->rmp.set) return set_err(FFHIP_EINVAL, "variants: no sequences are set for the batch (ffhip_batch_set_remap comes first)");
-    if (!nvar || nread != batch_nreads(b) || (size_t)nread != b->rmp.seq.size()) return set_err(FFHIP_EINVAL, "variants: lists for %d reads, the batch holds %d", nread, batch_nreads(b));
-    if (context < kVariantsMinContext || context > kVariantsMaxContext) return set_err(FFHIP_EINVAL, "variants: the context is %d (%d .. %d)", context, kVariantsMinContext, kVariantsMaxContext);
-    std::vector<std::vector<ffhip_variant>> set((size_t)nread);
-    for (int r = 0; r < nread; r++) {
-        if (!nvar[r]) continue;
-        if (!vars[r]) return set_err(FFHIP_EINVAL, "variants: read %d has %zu variants and no list", r, nvar[r]);
-        if (nvar[r] > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "variants: read %d has %zu variants", r, nvar[r]);
-        if (b->rmp.state[r] != 1) return set_err(FFHIP_EINVAL, "variants: read %d, index 0: the read has no sequence", r);
-        for (size_t i = 0; i < nvar[r]; i++) {
-            Variant v;
-            memcpy(&v, &vars[r][i], sizeof v);
-            if (const char *why = variant_invalid(v, b->rmp.seq[r].size(), b->mdl->nbase))
-                return set_err(FFHIP_EINVAL, "variants: read %d, index %zu: %s (pos %d, nref %d, nalt %d, a sequence of %zu codes)", r, i, why, (int)v.pos, (int)v.nref, (int)v.nalt, b->rmp.seq[r].size());
-        }
-        set[r].assign(vars[r], vars[r] + nvar[r]);
-    }
-    b->var.set = std::move(set);
-    b->var.context = context; b->var.all = all_paths ? 1 : 0;
-    return FFHIP_OK;
-}
-extern "C" int ffhip_batch_variant_calls(const ffhip_batch *b, int read, const ffhip_variant_call **vc, size_t *nvar) {
-    if (!results_ok(b, read) || !vc || !nvar) return FFHIP_EINVAL;
-    if (!b->var.valid || !b->rmp.valid || !b->var.rec.host) return set_err(FFHIP_EINVAL, "variants were not scored in this run (FFHIP_RUN_REMAP | FFHIP_RUN_REMAP_VARIANTS)");
-    int rec[4];
-    if (int rc = remap_record(b, read, rec, vc, nvar)) return rc;
-    if (rec[0] != 1) return FFHIP_OK;
-    *vc = (const ffhip_variant_call *)b->var.rec.host + b->var.off[read];
-    *nvar = b->var.off[read + 1] - b->var.off[read];
-    return FFHIP_OK;
-}
-
-// ---- truth (include/ffhip.h "truth"; the kernel: ffhip_truth.hip)
-static int truth_adopt(ffhip_batch *b, std::vector<std::vector<uint8_t>> &&seq, std::vector<signed char> &&state, int band) {
-    if (int rc = seq_adopt(b, seq, &b->tru.dseq, &b->tru.dseq_cap, "truth: the truths")) return rc;
-    b->tru.seq = std::move(seq); b->tru.state = std::move(state);
-    b->tru.band = band; b->tru.set = 1; b->tru.from_map = 0;
-    return FFHIP_OK;
-}
-extern "C" int ffhip_batch_set_truth(ffhip_batch *b, int nread, const uint8_t *const *codes, const size_t *len, int band) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "truth: the batch is between a run and its finish");
-    if (!codes) { b->tru.set = 0; b->tru.from_map = 0; b->tru.seq.clear(); b->tru.state.clear(); return FFHIP_OK; }
-    const ffhip_model *m = b->mdl;
-    if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "truth: a flip-flop model only (the run-length model's call is a list of runs)");
-    if (!len || nread != batch_nreads(b)) return set_err(FFHIP_EINVAL, "truth: truths for %d reads, the batch holds %d", nread, batch_nreads(b));
-    if (band < 0 || band > truth_max_band())
-        return set_err(FFHIP_EINVAL, "truth: the band half-width is %d (0 .. %d: the widest kernel form holds a window of %d cells)", band, truth_max_band(), truth_max_window());
-    std::vector<std::vector<uint8_t>> seq((size_t)nread);
-    std::vector<signed char> state((size_t)nread, 0);
-    for (int r = 0; r < nread; r++) {
-        if (!codes[r]) continue;
-        if (len[r] > (size_t)kTruthMaxLen) return set_err(FFHIP_EINVAL, "truth: read %d's truth has %zu bases (at most %d)", r, len[r], kTruthMaxLen);
-        state[r] = len[r] ? 1 : 2;
-        for (size_t i = 0; i < len[r]; i++) if (codes[r][i] >= m->nbase) return set_err(FFHIP_EINVAL, "truth: read %d, position %zu: code %d is not a base of the model (0 .. %d)", r, i, (int)codes[r][i], m->nbase - 1);
-        seq[r].assign(codes[r], codes[r] + len[r]);
-    }
-    return truth_adopt(b, std::move(seq), std::move(state), band);
-}
-// truth from map (include/ffhip.h "truth from map"; the kernel: k_map_stretch, ffhip_map.hip)
-extern "C" int ffhip_batch_set_truth_from_map(ffhip_batch *b, int on, int band) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "truth from map: the batch is between a run and its finish");
-    if (!on) { b->tru.from_map = 0; return FFHIP_OK; }
-    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "truth from map: a flip-flop model only (the run-length model's call is a list of runs)");
-    if (band < 0 || band > truth_max_band())
-        return set_err(FFHIP_EINVAL, "truth from map: the band half-width is %d (0 .. %d: the widest kernel form holds a window of %d cells)", band, truth_max_band(), truth_max_window());
-    b->tru.seq.clear(); b->tru.state.clear();               // (the two ways of giving truths replace each other)
-    b->tru.set = 0; b->tru.from_map = 1; b->tru.band = band;
-    return FFHIP_OK;
-}
-// ---- pileup (include/ffhip.h "pileup"; the kernel: ffhip_pileup.hip)
-static int pileup_wait(ffhip_pileup *p) {                // every accumulation enqueued against it, by any batch, is done
-    hipSetDevice(p->eng->device);
-    for (int i = 0; i < p->eng->nstreams; i++)
-        if (p->used[i]) { HIP_TRY(hipStreamSynchronize(p->eng->streams[i]), FFHIP_EHIP); p->used[i] = false; }
-    return FFHIP_OK;
-}
-static int pileup_zero(ffhip_pileup *p) {
-    hipStream_t s = p->eng->streams[0];
-    HIP_TRY(hipMemsetAsync(p->view.counts, 0, (size_t)kPileupPlanes * p->view.P * 4, s), FFHIP_EHIP);
-    HIP_TRY(hipMemsetAsync(p->view.totals, 0, (size_t)kPileupTotals * 8, s), FFHIP_EHIP);
-    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    return FFHIP_OK;
-}
-extern "C" ffhip_pileup *ffhip_pileup_create(ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity) {
-    if (!eng || !ref || ref->eng != eng) { set_err(FFHIP_EINVAL, "pileup: a reference of this engine"); return nullptr; }
-    if (min_identity > 1000) { set_err(FFHIP_EINVAL, "pileup: min_identity is %d per mille (0 .. 1000)", min_identity); return nullptr; }
-    hipSetDevice(eng->device);
-    ffhip_pileup *p = new ffhip_pileup();
-    p->eng = eng; p->ref = ref;
-    size_t P = 0;
-    for (int m : ref->rec_len) P += (size_t)m;
-    p->view.P = P; p->view.min_identity = min_identity < 0 ? 0 : min_identity;
-    const size_t bytes = (size_t)kPileupPlanes * P * 4;
-    if (hipMalloc((void **)&p->view.counts, bytes) != hipSuccess || hipMalloc((void **)&p->view.totals, (size_t)kPileupTotals * 8) != hipSuccess) {
-        set_err(FFHIP_ENOMEM, "pileup: the counters take %zu bytes of device memory, which could not be had", bytes + (size_t)kPileupTotals * 8);
-        if (p->view.counts) hipFree(p->view.counts);
-        delete p;
-        return nullptr;
-    }
-    if (pileup_zero(p) != FFHIP_OK) { hipFree(p->view.counts); hipFree(p->view.totals); delete p; return nullptr; }
-    return p;
-}
-extern "C" void ffhip_pileup_free(ffhip_pileup *p) {
-    if (!p) return;
-    pileup_wait(p);
-    hipFree(p->view.counts); hipFree(p->view.totals);
-    delete p;
-}
-extern "C" int ffhip_pileup_reset(ffhip_pileup *p) {
-    if (!p) return set_err(FFHIP_EINVAL, "null pileup");
-    if (int rc = pileup_wait(p)) return rc;
-    return pileup_zero(p);
-}
-extern "C" size_t ffhip_pileup_positions(const ffhip_pileup *p) { return p ? p->view.P : 0; }
-extern "C" int ffhip_pileup_download(ffhip_pileup *p, uint32_t *counts, ffhip_pileup_totals *totals) {
-    if (!p) return set_err(FFHIP_EINVAL, "null pileup");
-    static_assert(sizeof(ffhip_pileup_totals) == kPileupTotals * 8, "the totals come down as they stand");
-    if (int rc = pileup_wait(p)) return rc;
-    if (counts) HIP_TRY(hipMemcpy(counts, p->view.counts, (size_t)kPileupPlanes * p->view.P * 4, hipMemcpyDeviceToHost), FFHIP_EHIP);
-    if (totals) HIP_TRY(hipMemcpy(totals, p->view.totals, sizeof *totals, hipMemcpyDeviceToHost), FFHIP_EHIP);
-    return FFHIP_OK;
-}
-extern "C" int ffhip_batch_set_pileup(ffhip_batch *b, ffhip_pileup *p) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "pileup: the batch is between a run and its finish");
-    if (!p) { b->pile = nullptr; return FFHIP_OK; }
-    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "pileup: a flip-flop model only (the run-length model's call is a list of runs)");
-    if (p->eng != b->eng) return set_err(FFHIP_EINVAL, "pileup: the pileup belongs to another engine");
-    b->pile = p;
-    return FFHIP_OK;
-}
-extern "C" long long ffhip_debug_map_truth_bound(int nblock, int max_error) {
-    return (nblock < 0 || max_error < 0 || max_error > 500) ? -1 : map_truth_bound(nblock, max_error);
-}
-extern "C" int ffhip_batch_truth(const ffhip_batch *b, int read, ffhip_truth_call *out) {
-    if (!results_ok(b, read) || !out) return FFHIP_EINVAL;
-    if (!b->tru.valid || !b->tru.rec.host) return set_err(FFHIP_EINVAL, "truth records were not made in this run (FFHIP_RUN_TRUTH)");
-    int rec[kTruthRecInts];
-    memcpy(rec, b->tru.rec.host + (size_t)read * sizeof rec, sizeof rec);
-    out->status = rec[0]; out->n = (size_t)rec[1]; out->m = (size_t)rec[2]; out->dist = rec[3];
-    out->n_match = rec[4]; out->n_mismatch = rec[5]; out->n_ins = rec[6]; out->n_del = rec[7];
-    out->maxdev = rec[8]; out->nops = (size_t)rec[9];
-    out->ops = nullptr;
-    if (rec[0] == 1) {
-        const size_t cap = b->tru.off[read + 1] - b->tru.off[read];
-        if (rec[10] != 0 || out->nops > cap) return set_err(FFHIP_EHIP, "truth: read %d's traceback ended %d cells from (0, 0)", read, rec[10]);
-        out->ops = b->tru.rec.host + truth_ops_at(b) + b->tru.off[read + 1] - out->nops;
-    }
     return FFHIP_OK;
 }
 
@@ -3160,8 +2076,6 @@ extern "C" int ffhip_debug_batch_head_input(ffhip_batch *b, int row, float *out)
 }
 
 extern "C" int ffhip_debug_fallback_count(const ffhip_engine *eng) { return eng ? eng->fallbacks : -1; }
-extern "C" int ffhip_debug_remap_form(size_t L, int band) { return (L < 1 || L > ((size_t)1 << 30) || band < 0) ? -1 : remap_form((int)L, band); }
-extern "C" int ffhip_debug_truth_form(size_t window) { return (window < 1 || window > ((size_t)1 << 30)) ? -1 : truth_form((long long)window); }
 extern "C" size_t ffhip_debug_batch_device_bytes(const ffhip_batch *b) { return b ? b->dev_bytes + b->res.cap : 0; }
 extern "C" int ffhip_debug_split_plan(int kind, int hidden, int remaining, int ncu, int beside, int out[6]) {
     if (!out) return set_err(FFHIP_EINVAL, "ffhip_debug_split_plan: out is NULL");

@@ -1,4 +1,4 @@
-// ffhip_host.hpp -- host-side helpers shared by ffhip_engine.hip and ffhip_layers.hip (not public).
+// ffhip_host.hpp -- host-side helpers shared by ffhip_engine.hip, ffhip_features.hip and ffhip_layers.hip (not public).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -81,6 +81,9 @@ struct ffhip_pileup {
     ffhip::PileupView view{};
     bool used[4] = { false, false, false, false };
 };
+
+// a function or table one file of the library defines for another and the library does not export
+#define FFHIP_LOCAL __attribute__((visibility("hidden")))
 
 namespace ffhip {
 
@@ -182,6 +185,16 @@ static inline hipError_t mat_done(const ffhip_mat &m, float *d, bool lazy, hipSt
     if (m.dev && m.dev_state && *m.dev && d != (float *)*m.dev) { pool_put(*m.dev); *m.dev = nullptr; *m.dev_state = 0; }      // a reused output: its old device image is stale
     return hipMemcpyAsync(m.data, d, m.nc * m.stride * sizeof(float), hipMemcpyDeviceToHost, s);
 }
+
+// how every single-matrix and single-read operator starts, and what it says when its scratch could not be had
+#define OP_ENTER(eng_)                                                     \
+    if (!(eng_)) return set_err(FFHIP_EINVAL, "null engine");              \
+    hipSetDevice((eng_)->device);                                          \
+    hipStream_t s = (eng_)->streams[0];                                    \
+    TmpDev tmp
+#define OP_NOMEM() return set_err(FFHIP_ENOMEM, "device allocation failed")
+
+static inline bool view_ok(const ffhip_mat &m) { return m.data && m.nr > 0 && m.nc > 0 && m.stride >= m.nr; }
 
 static inline bool flipflop_dims(size_t nparam, size_t stride, int *nbase) {
     const int nb = (int)roundf((-1.0f + sqrtf(1.0f + 2.0f * (float)nparam)) / 2.0f);

@@ -168,8 +168,6 @@ __global__ void k_log_row_normalise(float *__restrict__ img, int nr, size_t stri
 
 inline unsigned nblk(size_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
-bool view_ok(const ffhip_mat &m) { return m.data && m.nr > 0 && m.nc > 0 && m.stride >= m.nr; }
-
 // image of a whole matrix, device side
 float *upload_img(TmpDev &t, const ffhip_mat &m, hipStream_t s) { return mat_in(t, m, s); }      // the matrix's device image if it has one, else an upload
 
@@ -191,13 +189,6 @@ std::vector<float> pack_recurrent(const ffhip_mat &sW, int H, int G, int Hp) {
 }
 
 }  // namespace
-
-#define OP_ENTER(eng_)                                                     \
-    if (!(eng_)) return set_err(FFHIP_EINVAL, "null engine");              \
-    hipSetDevice((eng_)->device);                                          \
-    hipStream_t s = (eng_)->streams[0];                                    \
-    TmpDev tmp
-#define OP_NOMEM() return set_err(FFHIP_ENOMEM, "device allocation failed")
 
 // ------------------------------------------------------------------------------------ element-wise ops
 extern "C" int ffhip_op_activation(ffhip_engine *eng, ffhip_mat C, int act, float p0, float p1) {
@@ -652,376 +643,6 @@ extern "C" int ffhip_op_moves(ffhip_engine *eng, const int *path, size_t nblock,
     launch_moves(s, d_path, d_mv, 1, (int)nblock, nullptr, ReadMap());
     HIP_TRY(hipMemcpyAsync(moves, d_mv, nblock, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
     HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    return FFHIP_OK;
-}
-
-// distances and end positions of every pattern of a kit at both ends of one call (k_barcodes; include/ffhip.h "barcodes")
-extern "C" int ffhip_op_barcode_scores(ffhip_engine *eng, const ffhip_barcodes *kit, const char *bases, size_t len, int32_t *dist, int32_t *end) {
-    OP_ENTER(eng);
-    if (!kit || kit->eng != eng || (!bases && len) || !dist || !end || len > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "bad barcode score arguments (a kit of this engine, a call of len characters, two outputs of 2 n entries)");
-    for (size_t i = 0; i < len; i++) if (!bases[i] || !strchr("ACGTZ", bases[i])) return set_err(FFHIP_EINVAL, "barcode scores: character %zu of the call is not one of ACGTZ", i);
-    const int n = kit->kit.n, ilen = (int)len;
-    char *d_bases = (char *)(len ? tmp.upload(bases, len, s) : tmp.get(4));
-    int *d_len = (int *)tmp.upload(&ilen, 4, s);
-    int *d_out = (int *)tmp.get((size_t)4 * n * 4);
-    void *d_rec = tmp.get(16);
-    if (!d_bases || !d_len || !d_out || !d_rec) OP_NOMEM();
-    launch_barcodes(s, kit->kit, d_bases, d_len, d_rec, 1, ilen > 0 ? ilen : 1, nullptr, ReadMap(), kit->lmin / 4, 3, 0, d_out, d_out + 2 * n);
-    HIP_TRY(hipMemcpyAsync(dist, d_out, (size_t)2 * n * 4, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    HIP_TRY(hipMemcpyAsync(end, d_out + 2 * n, (size_t)2 * n * 4, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    return FFHIP_OK;
-}
-
-// the kernel of the adapter search on one call (k_adapters; include/ffhip.h "adapters"): the whole score rows, or the call's record
-static int op_adapters(ffhip_engine *eng, const ffhip_adapters *kit, int max_dist, const char *bases, size_t len, uint8_t *d, ffhip_adapter_header *header, ffhip_adapter_hit *hits) {
-    OP_ENTER(eng);
-    if (!kit || kit->eng != eng || (!bases && len) || len > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "bad adapter arguments (a kit of this engine, a call of len characters, the outputs)");
-    for (size_t i = 0; i < len; i++) if (!bases[i] || !strchr("ACGTZ", bases[i])) return set_err(FFHIP_EINVAL, "adapters: character %zu of the call is not one of ACGTZ", i);
-    const int n = kit->kit.n, ilen = (int)len;
-    const size_t dbytes = d ? (size_t)2 * n * (len + 1) : 0;
-    char *d_bases = (char *)(len ? tmp.upload(bases, len, s) : tmp.get(4));
-    int *d_len = (int *)tmp.upload(&ilen, 4, s);
-    uint8_t *d_d = d ? (uint8_t *)tmp.get(dbytes) : nullptr;
-    uint8_t *d_rec = (uint8_t *)tmp.get(kAdapterRecBytes);
-    if (!d_bases || !d_len || (d && !d_d) || !d_rec) OP_NOMEM();
-    launch_adapters(s, kit->kit, d_bases, d_len, d_rec, 1, ilen > 0 ? ilen : 1, nullptr, ReadMap(), max_dist, d_d);
-    if (d) HIP_TRY(hipMemcpyAsync(d, d_d, dbytes, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    if (header) HIP_TRY(hipMemcpyAsync(header, d_rec, 16, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    if (hits) HIP_TRY(hipMemcpyAsync(hits, d_rec + 16, kAdapterRecBytes - 16, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    return FFHIP_OK;
-}
-extern "C" int ffhip_op_adapter_scores(ffhip_engine *eng, const ffhip_adapters *kit, const char *bases, size_t len, uint8_t *d) {
-    if (!d) return set_err(FFHIP_EINVAL, "adapter scores: an output of 2 n (len + 1) bytes");
-    return op_adapters(eng, kit, -1, bases, len, d, nullptr, nullptr);
-}
-extern "C" int ffhip_op_adapter_hits(ffhip_engine *eng, const ffhip_adapters *kit, int max_dist, const char *bases, size_t len, ffhip_adapter_header *header, ffhip_adapter_hit *hits) {
-    if (!header || !hits) return set_err(FFHIP_EINVAL, "adapter hits: a header and room for 15 hits");
-    return op_adapters(eng, kit, max_dist < 0 ? -1 : (max_dist > kAdapterMaxLen - 1 ? kAdapterMaxLen - 1 : max_dist), bases, len, nullptr, header, hits);
-}
-
-// the kernels of the map on one call (k_map_scan, k_map_finish; include/ffhip.h "map"): the whole score rows of its front anchor, or the call's record
-static int op_map(ffhip_engine *eng, const ffhip_map_ref *ref, int window, int max_error, const char *bases, size_t len, int32_t *d, ffhip_map_call *out) {
-    OP_ENTER(eng);
-    if (!ref || ref->eng != eng || (!bases && len) || len > (size_t)1 << 30) return set_err(FFHIP_EINVAL, "bad map arguments (a reference of this engine, a call of len characters, the output)");
-    if (const char *why = map_invalid(window, max_error)) return set_err(FFHIP_EINVAL, "map: %s", why);
-    for (size_t i = 0; i < len; i++) if (!bases[i] || !strchr("ACGTZ", bases[i])) return set_err(FFHIP_EINVAL, "map: character %zu of the call is not one of ACGTZ", i);
-    const int ilen = (int)len;
-    const size_t dbytes = d ? ref->score_entries * 4 : 0;
-    char *d_bases = (char *)(len ? tmp.upload(bases, len, s) : tmp.get(4));
-    int *d_len = (int *)tmp.upload(&ilen, 4, s);
-    int *d_d = d ? (int *)tmp.get(dbytes) : nullptr;
-    void *d_slots = tmp.get((size_t)2 * ref->view.ntask * 8);
-    uint8_t *d_rec = (uint8_t *)tmp.get(kMapRecBytes);
-    if (!d_bases || !d_len || (d && !d_d) || !d_slots || !d_rec) OP_NOMEM();
-    launch_map(s, ref->view, d_bases, d_len, d_rec, 1, ilen > 0 ? ilen : 1, nullptr, ReadMap(), window < 0 ? kMapMaxAnchor : window, max_error < 0 ? 250 : max_error, d_slots, d_d);
-    if (d) HIP_TRY(hipMemcpyAsync(d, d_d, dbytes, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    if (out) HIP_TRY(hipMemcpyAsync(out, d_rec, kMapRecBytes, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    return FFHIP_OK;
-}
-extern "C" int ffhip_op_map_scores(ffhip_engine *eng, const ffhip_map_ref *ref, const char *pattern, size_t len, int32_t *d) {
-    if (!d) return set_err(FFHIP_EINVAL, "map scores: an output of twice the sum of m_k + 1 entries");
-    if (len < 1 || len > (size_t)kMapMaxAnchor) return set_err(FFHIP_EINVAL, "map scores: an anchor has 1 .. %d letters, not %zu", kMapMaxAnchor, len);
-    return op_map(eng, ref, kMapMaxAnchor, -1, pattern, len, d, nullptr);
-}
-extern "C" int ffhip_op_map(ffhip_engine *eng, const ffhip_map_ref *ref, int window, int max_error, const char *bases, size_t len, ffhip_map_call *out) {
-    if (!out) return set_err(FFHIP_EINVAL, "map: a record to fill");
-    return op_map(eng, ref, window, max_error, bases, len, nullptr, out);
-}
-
-// the gather of truth from map on one span from host arguments (k_map_stretch; include/ffhip.h "truth from map"): a record and a list entry made here
-extern "C" int ffhip_op_map_stretch(ffhip_engine *eng, const ffhip_map_ref *ref, int q, int start, int end, uint8_t *codes) {
-    OP_ENTER(eng);
-    if (!ref || ref->eng != eng || !codes) return set_err(FFHIP_EINVAL, "bad map stretch arguments (a reference of this engine, an output of end - start bytes)");
-    if (q < 0 || q >= 2 * ref->view.nrec) return set_err(FFHIP_EINVAL, "map stretch: search %d is not one of 0 .. %d", q, 2 * ref->view.nrec - 1);
-    const int mk = ref->rec_len[(size_t)q >> 1];
-    if (start < 0 || end > mk || start >= end) return set_err(FFHIP_EINVAL, "map stretch: [%d, %d) is not a span of 1 or more of the record's %d bases", start, end, mk);
-    const int m = end - start;
-    ffhip_map_call rec;
-    memset(&rec, 0, sizeof rec);
-    rec.status = 1; rec.nanchor = 1; rec.q = q; rec.tstart = start; rec.tend = end;
-    const TruthRead tr{ 0ull, 0ull, 0u, 0, 1, 0, 0, m };
-    void *d_rec = tmp.upload(&rec, sizeof rec, s);
-    TruthRead *d_list = (TruthRead *)tmp.upload(&tr, sizeof tr, s);
-    uint8_t *d_seq = (uint8_t *)tmp.get((size_t)m);
-    if (!d_rec || !d_list || !d_seq) OP_NOMEM();
-    launch_map_stretch(s, ref->view, d_rec, d_list, 1, d_seq);
-    TruthRead got;
-    HIP_TRY(hipMemcpyAsync(&got, d_list, sizeof got, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    HIP_TRY(hipMemcpyAsync(codes, d_seq, (size_t)m, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    HIP_TRY(hipGetLastError(), FFHIP_EHIP);
-    if (got.status != 1 || got.m != m) return set_err(FFHIP_EHIP, "map stretch: the kernel left status %d and %d bases for a span of %d", got.status, got.m, m);
-    return FFHIP_OK;
-}
-
-// one alignment from host arguments added into a pileup (k_pileup; include/ffhip.h "pileup"): a map record, a truth record and a list entry made here
-extern "C" int ffhip_op_pileup(ffhip_engine *eng, ffhip_pileup *p, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops) {
-    OP_ENTER(eng);
-    if (!p || p->eng != eng || (n && !call) || !ops) return set_err(FFHIP_EINVAL, "bad pileup arguments (a pileup of this engine, a call of n letters, nops ops)");
-    const ffhip_map_ref *ref = p->ref;
-    if (q < 0 || q >= 2 * ref->view.nrec) return set_err(FFHIP_EINVAL, "pileup: search %d is not one of 0 .. %d", q, 2 * ref->view.nrec - 1);
-    const int mk = ref->rec_len[(size_t)q >> 1];
-    if (tstart < 0 || tend > mk || tstart >= tend) return set_err(FFHIP_EINVAL, "pileup: [%d, %d) is not a span of 1 or more of the record's %d bases", tstart, tend, mk);
-    if (n > (size_t)kTruthMaxLen || nops > (size_t)2 * kTruthMaxLen) return set_err(FFHIP_EINVAL, "pileup: a call of %zu bases and %zu ops (at most %d bases)", n, nops, kTruthMaxLen);
-    for (size_t i = 0; i < n; i++) if (!call[i] || !strchr("ACGTZ", call[i])) return set_err(FFHIP_EINVAL, "pileup: position %zu of the call: '%c' is not one of A C G T Z", i, call[i]);
-    const size_t m = (size_t)(tend - tstart);
-    size_t cnt[4] = { 0, 0, 0, 0 };
-    for (size_t k = 0; k < nops; k++) {
-        if (ops[k] > 3) return set_err(FFHIP_EINVAL, "pileup: op %zu: code %d is not one of 0 .. 3", k, (int)ops[k]);
-        cnt[ops[k]]++;
-    }
-    if (cnt[0] + cnt[1] + cnt[3] != m || cnt[0] + cnt[1] + cnt[2] != n)
-        return set_err(FFHIP_EINVAL, "pileup: the ops consume %zu truth and %zu call bases, the span has %zu and the call %zu", cnt[0] + cnt[1] + cnt[3], cnt[0] + cnt[1] + cnt[2], m, n);
-    ffhip_map_call mrec;
-    memset(&mrec, 0, sizeof mrec);
-    mrec.status = 1; mrec.n = (int)n; mrec.nanchor = 1; mrec.q = q; mrec.tstart = tstart; mrec.tend = tend;
-    const int trec[kTruthRecInts] = { 1, (int)n, (int)m, (int)(cnt[1] + cnt[2] + cnt[3]), (int)cnt[0], (int)cnt[1], (int)cnt[2], (int)cnt[3], 0, (int)nops, 0, 0 };
-    const TruthRead tr{ 0ull, 0ull, 0u, (int)m, 1, 0, (int)nops, 0 };
-    void *d_mrec = tmp.upload(&mrec, sizeof mrec, s);
-    int *d_trec = (int *)tmp.upload(trec, sizeof trec, s);
-    TruthRead *d_list = (TruthRead *)tmp.upload(&tr, sizeof tr, s);
-    uint8_t *d_ops = (uint8_t *)tmp.upload(ops, nops, s);
-    char *d_call = (char *)tmp.upload(n ? call : "", n ? n : 1, s);
-    if (!d_mrec || !d_trec || !d_list || !d_ops || !d_call) OP_NOMEM();
-    launch_pileup(s, ref->view, d_list, 1, d_mrec, d_trec, d_ops, d_call, n > 0 ? (int)n : 1, ReadMap(), p->view);
-    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    HIP_TRY(hipGetLastError(), FFHIP_EHIP);
-    return FFHIP_OK;
-}
-
-// one matrix of transition scores mapped to one sequence (k_remap; include/ffhip.h "remap")
-extern "C" int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, int band, uint8_t *rm, float *score) {
-    OP_ENTER(eng);
-    if (!view_ok(trans) || !codes || !rm || !score || nbase < 1 || 2 * nbase > kMaxState || trans.nr != (size_t)(2 * nbase * (nbase + 1)) || trans.stride % 4 != 0 || trans.stride > 2048 ||
-        trans.nc > (size_t)1 << 30)
-        return set_err(FFHIP_EINVAL, "bad remap arguments (scores of 2 nbase (nbase + 1) rows, a sequence, outputs of nblock bytes and one float)");
-    const size_t N = trans.nc;
-    if (band < 0) return set_err(FFHIP_EINVAL, "remap: the band half-width is %d (>= 0)", band);
-    if (L < 1 || L > N + 1) return set_err(FFHIP_EINVAL, "remap: a sequence of %zu bases has no path through %zu blocks (1 <= L <= nblock + 1)", L, N);
-    for (size_t i = 0; i < L; i++) if (codes[i] >= nbase) return set_err(FFHIP_EINVAL, "remap: position %zu: code %d is not a base (0 .. %d)", i, (int)codes[i], nbase - 1);
-    const int form = remap_form((int)L, band);
-    if (form < 0) return set_err(FFHIP_EINVAL, "remap: the window of min(2 band + 1, L) cells is more than %d", remap_max_window());
-    std::vector<unsigned short> coded(L);
-    remap_code(codes, L, nbase, coded.data());
-    const RemapRead rr{ 0ull, 0u, (int)L, 1, 0 };
-    float *d_t = upload_img(tmp, trans, s);
-    unsigned short *d_seq = (unsigned short *)tmp.upload(coded.data(), L * sizeof(unsigned short), s);
-    RemapRead *d_list = (RemapRead *)tmp.upload(&rr, sizeof rr, s);
-    const size_t ws_bytes = remap_ws_words(form, (int)N) * 8;
-    unsigned long long *d_ws = (unsigned long long *)tmp.get(ws_bytes);
-    uint8_t *d_rm = (uint8_t *)tmp.get(N + 1);
-    void *d_rec = tmp.get(16);
-    if (!d_ws) return set_err(FFHIP_ENOMEM, "remap: the traceback workspace takes %zu bytes of device memory, which could not be had", ws_bytes);
-    if (!d_t || !d_seq || !d_list || !d_rm || !d_rec) OP_NOMEM();
-    launch_remap(s, form, d_list, 1, d_seq, d_t, (int)trans.stride, band, d_ws, d_rec, d_rm, (int)N, nullptr, ReadMap());
-    int rec[4];
-    HIP_TRY(hipMemcpyAsync(rec, d_rec, 16, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    HIP_TRY(hipMemcpyAsync(rm, d_rm, N, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    if (rec[0] != 1 || rec[3] != 0) return set_err(FFHIP_EHIP, "remap: status %d, traceback ended at position %d", rec[0], rec[3]);
-    memcpy(score, &rec[2], 4);
-    return FFHIP_OK;
-}
-
-// the poly tail of one read from its signal and its Viterbi path (k_polytail; include/ffhip.h "poly tail"): the record, or the windows' values
-static int op_polytail(ffhip_engine *eng, const float *signal, size_t nsample, int stride, const int *path, size_t nblock, int nbase, const ffhip_polytail_params *params,
-                       ffhip_polytail *out, double *mu, double *q, uint8_t *flag) {
-    OP_ENTER(eng);
-    if (!path || !params || (nsample && !signal)) return set_err(FFHIP_EINVAL, "bad poly tail arguments (a signal, a path of nblock + 1 states, the parameters, the outputs)");
-    if (stride < 1 || nblock < 1 || nblock > (size_t)1 << 30 || nsample > (size_t)1 << 30 || (nbase != 4 && nbase != 5))
-        return set_err(FFHIP_EINVAL, "poly tail: stride %d, %zu blocks, %zu samples, nbase %d (a stride >= 1, 1 .. 2^30 blocks, at most 2^30 samples, nbase 4 or 5)", stride, nblock, nsample, nbase);
-    PolyTailParams p;
-    memcpy(&p, params, sizeof p);
-    if (const char *why = polytail_invalid(p)) return set_err(FFHIP_EINVAL, "poly tail: %s", why);
-    for (size_t i = 0; i <= nblock; i++) if (path[i] < 0 || path[i] >= 2 * nbase) return set_err(FFHIP_EINVAL, "poly tail: entry %zu of the path is %d (a state, 0 .. %d)", i, path[i], 2 * nbase - 1);
-    const size_t NW = std::min(nblock, nsample / (size_t)stride) / (size_t)p.window, room = NW ? NW : 1;
-    const PolyRead pr{ 0ull, 0ull, (int)nsample, 0 };
-    const float none = 0.0f;
-    float *d_x = (float *)tmp.upload(nsample ? signal : &none, (nsample ? nsample : 1) * sizeof(float), s);
-    int *d_path = (int *)tmp.upload(path, (nblock + 1) * 4, s);
-    PolyRead *d_list = (PolyRead *)tmp.upload(&pr, sizeof pr, s);
-    double *d_mu = (double *)tmp.get(room * 8), *d_q = (double *)tmp.get(room * 8);
-    uint8_t *d_fl = (uint8_t *)tmp.get(room), *d_rec = (uint8_t *)tmp.get(kPolyTailRecBytes);
-    if (!d_x || !d_path || !d_list || !d_mu || !d_q || !d_fl || !d_rec) OP_NOMEM();
-    launch_polytail(s, d_list, 1, d_x, stride, d_path, nbase, p, d_rec, d_mu, d_fl, d_q, (int)nblock, nullptr, ReadMap());
-    if (out) HIP_TRY(hipMemcpyAsync(out, d_rec, kPolyTailRecBytes, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    if (mu && NW) {
-        HIP_TRY(hipMemcpyAsync(mu, d_mu, NW * 8, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-        HIP_TRY(hipMemcpyAsync(q, d_q, NW * 8, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-        HIP_TRY(hipMemcpyAsync(flag, d_fl, NW, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    }
-    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    if (mu) for (size_t w = 0; w < NW; w++) flag[w] &= 1;       // (bit 1 is the scan's: the window ends a candidate)
-    return FFHIP_OK;
-}
-extern "C" int ffhip_op_polytail(ffhip_engine *eng, const float *signal, size_t nsample, int stride, const int *path, size_t nblock, int nbase,
-                                 const ffhip_polytail_params *params, ffhip_polytail *out) {
-    if (!out) return set_err(FFHIP_EINVAL, "poly tail: an output record");
-    return op_polytail(eng, signal, nsample, stride, path, nblock, nbase, params, out, nullptr, nullptr, nullptr);
-}
-extern "C" int ffhip_op_polytail_windows(ffhip_engine *eng, const float *signal, size_t nsample, int stride, const int *path, size_t nblock, int nbase,
-                                         const ffhip_polytail_params *params, double *mu, double *q, uint8_t *flag) {
-    if (!mu || !q || !flag) return set_err(FFHIP_EINVAL, "poly tail windows: three outputs of NW entries");
-    return op_polytail(eng, signal, nsample, stride, path, nblock, nbase, params, nullptr, mu, q, flag);
-}
-
-// the events of one read from its signal and its path (k_events; include/ffhip.h "events")
-extern "C" int ffhip_op_events(ffhip_engine *eng, const float *signal, size_t nsample, int stride, const uint8_t *rm, size_t nblock, size_t L, ffhip_event *out) {
-    OP_ENTER(eng);
-    if (!rm || !out || (nsample && !signal)) return set_err(FFHIP_EINVAL, "bad events arguments (a signal, a path of nblock bytes and L events of output)");
-    if (stride < 1 || nblock < 1 || L < 1 || nblock > (size_t)1 << 30 || nsample > (size_t)1 << 30)
-        return set_err(FFHIP_EINVAL, "events: stride %d, %zu blocks, %zu samples and %zu bases (a stride >= 1, 1 .. 2^30 blocks, at most 2^30 samples, L >= 1)", stride, nblock, nsample, L);
-    size_t ones = 0;
-    for (size_t i = 0; i < nblock; i++) {
-        if (rm[i] > 1) return set_err(FFHIP_EINVAL, "events: block %zu of the path is %d (0 or 1)", i, (int)rm[i]);
-        ones += rm[i];
-    }
-    if (ones != L - 1) return set_err(FFHIP_EINVAL, "events: the path moves %zu times, a sequence of %zu bases takes %zu", ones, L, L - 1);
-    const EventRead er{ 0ull, 0ull, (int)nsample, (int)L, 0, 0 };
-    const unsigned rec[4] = { 1u, (unsigned)L, 0u, 0u };
-    const float none = 0.0f;
-    float *d_x = (float *)tmp.upload(nsample ? signal : &none, (nsample ? nsample : 1) * sizeof(float), s);
-    uint8_t *d_rm = (uint8_t *)tmp.upload(rm, nblock, s);
-    EventRead *d_list = (EventRead *)tmp.upload(&er, sizeof er, s);
-    void *d_rec = tmp.upload(rec, sizeof rec, s);
-    void *d_ev = tmp.get(L * sizeof(ffhip_event));
-    if (!d_ev) return set_err(FFHIP_ENOMEM, "events: the events take %zu bytes of device memory, which could not be had", L * sizeof(ffhip_event));
-    if (!d_x || !d_rm || !d_list || !d_rec) OP_NOMEM();
-    launch_events(s, d_list, 1, d_x, stride, d_rec, d_rm, d_ev, (int)nblock, nullptr, ReadMap());
-    HIP_TRY(hipMemcpyAsync(out, d_ev, L * sizeof(ffhip_event), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    HIP_TRY(hipGetLastError(), FFHIP_EHIP);
-    return FFHIP_OK;
-}
-
-// the site mods of one read from its scores, its sequence and its path (k_site_starts + k_site_mods; include/ffhip.h "site mods")
-extern "C" int ffhip_op_site_mods(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, const uint8_t *rm, size_t nblock, int context, int all_paths,
-                                  ffhip_site_mod *out, size_t *nsite) {
-    OP_ENTER(eng);
-    if (nbase != 5) return set_err(FFHIP_EINVAL, "site mods: nbase is %d (a model of the alphabet ACGTZ: 5)", nbase);
-    if (!view_ok(trans) || !codes || !rm || !out || !nsite || trans.nr != (size_t)(2 * nbase * (nbase + 1)) || trans.stride % 4 != 0 || trans.stride > 2048)
-        return set_err(FFHIP_EINVAL, "bad site mods arguments (scores of 2 nbase (nbase + 1) rows, a sequence, a path of nblock bytes, records and their count)");
-    if (context < 0 || context > kSiteModsMaxContext) return set_err(FFHIP_EINVAL, "site mods: the context is %d (0 .. %d)", context, kSiteModsMaxContext);
-    if (nblock < 1 || nblock != trans.nc || L < 1 || nblock > (size_t)1 << 30)
-        return set_err(FFHIP_EINVAL, "site mods: %zu blocks of path, %zu of scores and %zu bases (the same 1 .. 2^30 blocks, L >= 1)", nblock, trans.nc, L);
-    size_t ones = 0;
-    for (size_t i = 0; i < nblock; i++) {
-        if (rm[i] > 1) return set_err(FFHIP_EINVAL, "site mods: block %zu of the path is %d (0 or 1)", i, (int)rm[i]);
-        ones += rm[i];
-    }
-    if (ones != L - 1) return set_err(FFHIP_EINVAL, "site mods: the path moves %zu times, a sequence of %zu bases takes %zu", ones, L, L - 1);
-    for (size_t i = 0; i < L; i++) if (codes[i] >= nbase) return set_err(FFHIP_EINVAL, "site mods: position %zu: code %d is not a base (0 .. %d)", i, (int)codes[i], nbase - 1);
-    std::vector<unsigned short> coded(L);
-    remap_code(codes, L, nbase, coded.data());
-    std::vector<SiteMod> sites;
-    *nsite = sitemods_sites(coded.data(), L, 0, &sites);
-    if (sites.empty()) return FFHIP_OK;
-    const SiteRead sr{ 0ull, 0u, (int)L, 0, 0 };
-    const unsigned rec[4] = { 1u, (unsigned)L, 0u, 0u };
-    float *d_t = upload_img(tmp, trans, s);
-    unsigned short *d_seq = (unsigned short *)tmp.upload(coded.data(), L * sizeof(unsigned short), s);
-    uint8_t *d_rm = (uint8_t *)tmp.upload(rm, nblock, s);
-    SiteRead *d_list = (SiteRead *)tmp.upload(&sr, sizeof sr, s);
-    SiteMod *d_sites = (SiteMod *)tmp.upload(sites.data(), sites.size() * sizeof(SiteMod), s);
-    void *d_rec = tmp.upload(rec, sizeof rec, s);
-    int *d_start = (int *)tmp.get((L + 1) * 4);
-    void *d_out = tmp.get(sites.size() * sizeof(ffhip_site_mod));
-    if (!d_start || !d_out) return set_err(FFHIP_ENOMEM, "site mods: the records and starts take %zu bytes of device memory, which could not be had", sites.size() * sizeof(ffhip_site_mod) + (L + 1) * 4);
-    if (!d_t || !d_seq || !d_rm || !d_list || !d_sites || !d_rec) OP_NOMEM();
-    launch_site_mods(s, d_list, 1, d_sites, (int)sites.size(), d_seq, d_t, (int)trans.stride, context, all_paths ? 1 : 0, d_rec, d_rm, d_start, d_out, (int)nblock, nullptr, ReadMap());
-    HIP_TRY(hipMemcpyAsync(out, d_out, sites.size() * sizeof(ffhip_site_mod), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    HIP_TRY(hipGetLastError(), FFHIP_EHIP);
-    return FFHIP_OK;
-}
-
-// the variants of one read from its scores, its sequence and its path (k_site_starts + k_variants; include/ffhip.h "variants")
-extern "C" int ffhip_op_variants(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, const uint8_t *rm, size_t nblock,
-                                 const ffhip_variant *vars, size_t nvar, int context, int all_paths, ffhip_variant_call *out) {
-    OP_ENTER(eng);
-    static_assert(sizeof(Variant) == sizeof(ffhip_variant) && sizeof(VarEntry) == 32 && sizeof(ffhip_variant_call) == 16, "the list is copied as it stands");
-    if (nbase != 4 && nbase != 5) return set_err(FFHIP_EINVAL, "variants: nbase is %d (4 or 5)", nbase);
-    if (!view_ok(trans) || !codes || !rm || (nvar && (!vars || !out)) || trans.nr != (size_t)(2 * nbase * (nbase + 1)) || trans.stride % 4 != 0 || trans.stride > 2048)
-        return set_err(FFHIP_EINVAL, "bad variants arguments (scores of 2 nbase (nbase + 1) rows, a sequence, a path of nblock bytes, variants and room for their records)");
-    if (context < kVariantsMinContext || context > kVariantsMaxContext) return set_err(FFHIP_EINVAL, "variants: the context is %d (%d .. %d)", context, kVariantsMinContext, kVariantsMaxContext);
-    if (nblock < 1 || nblock != trans.nc || L < 1 || nblock > (size_t)1 << 30 || nvar > (size_t)1 << 30)
-        return set_err(FFHIP_EINVAL, "variants: %zu blocks of path, %zu of scores, %zu bases and %zu variants (the same 1 .. 2^30 blocks, L >= 1)", nblock, trans.nc, L, nvar);
-    size_t ones = 0;
-    for (size_t i = 0; i < nblock; i++) {
-        if (rm[i] > 1) return set_err(FFHIP_EINVAL, "variants: block %zu of the path is %d (0 or 1)", i, (int)rm[i]);
-        ones += rm[i];
-    }
-    if (ones != L - 1) return set_err(FFHIP_EINVAL, "variants: the path moves %zu times, a sequence of %zu bases takes %zu", ones, L, L - 1);
-    for (size_t i = 0; i < L; i++) if (codes[i] >= nbase) return set_err(FFHIP_EINVAL, "variants: position %zu: code %d is not a base (0 .. %d)", i, (int)codes[i], nbase - 1);
-    std::vector<VarEntry> list(nvar);
-    for (size_t i = 0; i < nvar; i++) {
-        list[i].k = 0; list[i].index = (int)i;
-        memcpy(&list[i].v, &vars[i], sizeof(Variant));
-        if (const char *why = variant_invalid(list[i].v, L, nbase))
-            return set_err(FFHIP_EINVAL, "variants: read 0, index %zu: %s (pos %d, nref %d, nalt %d, a sequence of %zu codes)", i, why, (int)vars[i].pos, (int)vars[i].nref, (int)vars[i].nalt, L);
-    }
-    if (!nvar) return FFHIP_OK;
-    std::vector<unsigned short> coded(L);
-    remap_code(codes, L, nbase, coded.data());
-    const SiteRead sr{ 0ull, 0u, (int)L, 0, 0 };
-    const unsigned rec[4] = { 1u, (unsigned)L, 0u, 0u };
-    float *d_t = upload_img(tmp, trans, s);
-    unsigned short *d_seq = (unsigned short *)tmp.upload(coded.data(), L * sizeof(unsigned short), s);
-    uint8_t *d_rm = (uint8_t *)tmp.upload(rm, nblock, s);
-    SiteRead *d_list = (SiteRead *)tmp.upload(&sr, sizeof sr, s);
-    VarEntry *d_vars = (VarEntry *)tmp.upload(list.data(), nvar * sizeof(VarEntry), s);
-    void *d_rec = tmp.upload(rec, sizeof rec, s);
-    int *d_start = (int *)tmp.get((L + 1) * 4);
-    void *d_out = tmp.get(nvar * sizeof(ffhip_variant_call));
-    if (!d_start || !d_out) return set_err(FFHIP_ENOMEM, "variants: the records and starts take %zu bytes of device memory, which could not be had", nvar * sizeof(ffhip_variant_call) + (L + 1) * 4);
-    if (!d_t || !d_seq || !d_rm || !d_list || !d_vars || !d_rec) OP_NOMEM();
-    launch_variants(s, d_list, 1, d_vars, (int)nvar, d_seq, d_t, (int)trans.stride, nbase, context, all_paths ? 1 : 0, d_rec, d_rm, d_start, d_out, (int)nblock, nullptr, ReadMap());
-    HIP_TRY(hipMemcpyAsync(out, d_out, nvar * sizeof(ffhip_variant_call), hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    HIP_TRY(hipGetLastError(), FFHIP_EHIP);
-    return FFHIP_OK;
-}
-
-// one call aligned to one truth (k_truth; include/ffhip.h "truth")
-extern "C" int ffhip_op_truth(ffhip_engine *eng, const char *call, size_t n, const uint8_t *truth, size_t m, int band, ffhip_truth_call *out, uint8_t *ops) {
-    OP_ENTER(eng);
-    if (!out || (n && !call) || (m && !truth) || ((n + m) && !ops)) return set_err(FFHIP_EINVAL, "bad truth arguments (a call, a truth, a record and n + m bytes of ops)");
-    if (n > (size_t)kTruthMaxLen || m > (size_t)kTruthMaxLen) return set_err(FFHIP_EINVAL, "truth: a call of %zu and a truth of %zu bases (at most %d each)", n, m, kTruthMaxLen);
-    if (band < 0 || band > truth_max_band())
-        return set_err(FFHIP_EINVAL, "truth: the band half-width is %d (0 .. %d: the widest kernel form holds a window of %d cells)", band, truth_max_band(), truth_max_window());
-    for (size_t i = 0; i < n; i++) if (!call[i] || !strchr("ACGTZ", call[i])) return set_err(FFHIP_EINVAL, "truth: position %zu of the call: '%c' is not one of A C G T Z", i, call[i]);
-    for (size_t i = 0; i < m; i++) if (truth[i] > 4) return set_err(FFHIP_EINVAL, "truth: position %zu of the truth: code %d is not a base (0 .. 4)", i, (int)truth[i]);
-    const int form = truth_form(std::min<long long>(2ll * band + 1, (long long)n + 1));
-    const int ni = (int)n, cap = (int)(n + m);
-    const TruthRead tr{ 0ull, 0ull, 0u, (int)m, m ? 1 : 2, 0, cap, 0 };
-    char *d_call = (char *)tmp.upload(n ? call : "", n ? n : 1, s);
-    uint8_t *d_seq = (uint8_t *)tmp.upload(m ? truth : (const uint8_t *)"", m ? m : 1, s);
-    int *d_len = (int *)tmp.upload(&ni, 4, s);
-    TruthRead *d_list = (TruthRead *)tmp.upload(&tr, sizeof tr, s);
-    const size_t ws_bytes = truth_ws_words(form, (int)m) * 8;
-    unsigned long long *d_ws = (unsigned long long *)tmp.get(ws_bytes ? ws_bytes : 8);
-    uint8_t *d_ops = (uint8_t *)tmp.get(cap ? cap : 1);
-    int *d_rec = (int *)tmp.get(kTruthRecInts * 4);
-    if (!d_ws) return set_err(FFHIP_ENOMEM, "truth: the traceback workspace takes %zu bytes of device memory, which could not be had", ws_bytes);
-    if (!d_call || !d_seq || !d_len || !d_list || !d_ops || !d_rec) OP_NOMEM();
-    // (Tb = max(n, 1): a read of no blocks is an empty slot to the kernel, which then reads no length)
-    launch_truth(s, form, d_list, 1, d_seq, d_call, d_len, band, d_ws, d_rec, d_ops, ni > 0 ? ni : 1, nullptr, ReadMap());
-    int rec[kTruthRecInts];
-    std::vector<uint8_t> got((size_t)cap);
-    HIP_TRY(hipMemcpyAsync(rec, d_rec, sizeof rec, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    if (cap) HIP_TRY(hipMemcpyAsync(got.data(), d_ops, (size_t)cap, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
-    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    HIP_TRY(hipGetLastError(), FFHIP_EHIP);
-    out->status = rec[0]; out->n = (size_t)rec[1]; out->m = (size_t)rec[2]; out->dist = rec[3];
-    out->n_match = rec[4]; out->n_mismatch = rec[5]; out->n_ins = rec[6]; out->n_del = rec[7];
-    out->maxdev = rec[8]; out->nops = (size_t)rec[9]; out->ops = nullptr;
-    if (rec[0] == 1) {
-        if (rec[10] != 0 || rec[9] < 0 || rec[9] > cap) return set_err(FFHIP_EHIP, "truth: the traceback ended %d cells from (0, 0)", rec[10]);
-        memcpy(ops, got.data() + cap - rec[9], (size_t)rec[9]);
-    }
     return FFHIP_OK;
 }
 
