@@ -37,6 +37,9 @@ ADAPTER_MAX_HITS = 15
 RUN_MAP = 4194304        # flip-flop model: one map record a read (status, strand and record, span, either anchor's place) made on the device against the reference of Batch.set_map (Batch.map)
 RUN_PILEUP = 8388608     # with RUN_MAP | RUN_TRUTH in the mode of Batch.set_truth_from_map: every aligned read's per-position counts added into the Pileup of Batch.set_pileup
 PILEUP_TOTALS = ("reads", "skipped", "match", "mismatch", "del", "ins", "edge_ins", "reserved")      # ffhip_pileup_totals, eight uint64
+RUN_MOD_PILEUP = 16777216  # with RUN_MAP | RUN_TRUTH | RUN_MOD_PROBS in the same mode: every aligned read's 5mC bytes classed per reference C into the ModPileup of Batch.set_modpileup
+MODPILEUP_TOTALS = ("reads", "skipped", "sites", "mod", "canon", "fail", "diff", "del")      # ffhip_modpileup_totals, eight uint64
+MODPILEUP_COLUMNS = ("mod", "canon", "fail", "diff", "del")
 MAP_SEGMENT = 2048       # FFHIP_MAP_SEGMENT (include/ffhip.h "map"): the columns one task of k_map_scan owns; checked against the library at load
 MAP_MAX_TOTAL = 1 << 20
 MAP_MAX_ANCHOR = 4096
@@ -340,6 +343,16 @@ def lib():
     L.ffhip_pileup_download.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.ffhip_batch_set_pileup.argtypes = [vp, vp]
     L.ffhip_op_pileup.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t]
+    L.ffhip_modpileup_create.restype = vp
+    L.ffhip_modpileup_create.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
+    L.ffhip_modpileup_free.restype = None
+    L.ffhip_modpileup_free.argtypes = [vp]
+    L.ffhip_modpileup_reset.argtypes = [vp]
+    L.ffhip_modpileup_positions.restype = C.c_size_t
+    L.ffhip_modpileup_positions.argtypes = [vp]
+    L.ffhip_modpileup_download.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.ffhip_batch_set_modpileup.argtypes = [vp, vp]
+    L.ffhip_op_modpileup.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t]
     L.ffhip_debug_map_truth_bound.restype = C.c_longlong
     L.ffhip_debug_map_truth_bound.argtypes = [C.c_int, C.c_int]
     _LIB = L
@@ -617,6 +630,37 @@ class Pileup:
     def close(self):
         if self.h:
             lib().ffhip_pileup_free(self.h)
+            self.h = None
+
+
+class ModPileup:
+    """Per reference C (- strand: G), how the aligned calls of all the batches it is attached to class their 5mC bytes (ffhip_modpileup, include/ffhip.h "mod pileup"):
+    10 planes [strand][mod canon fail diff del] of P uint32, eight uint64 totals and a histogram of 256 uint64 on the device.  `min_identity` in per mille and the
+    byte thresholds 0 <= lo < hi <= 255 (mod: ml >= hi, canon: ml <= lo) are fixed here.  `ref` must outlive it, and it every batch it is attached to."""
+
+    def __init__(self, engine: Engine, ref: MapRef, min_identity: int = 0, lo: int = 50, hi: int = 205):
+        self.engine = engine
+        self.ref = ref
+        self.h = lib().ffhip_modpileup_create(engine.h, ref.h, int(min_identity), int(lo), int(hi))
+        if not self.h:
+            raise FFHipError(lib().ffhip_last_error().decode())
+        self.positions = int(lib().ffhip_modpileup_positions(self.h))
+
+    def download(self):
+        """(counts uint32 [10][P], totals dict of MODPILEUP_TOTALS, hist uint64 [256]) once every accumulation enqueued by any batch is done (ffhip_modpileup_download)"""
+        counts = np.zeros((10, self.positions), dtype=np.uint32)
+        tot = np.zeros(len(MODPILEUP_TOTALS), dtype=np.uint64)
+        hist = np.zeros(256, dtype=np.uint64)
+        u64 = C.POINTER(C.c_uint64)
+        _check(lib().ffhip_modpileup_download(self.h, counts.ctypes.data_as(C.POINTER(C.c_uint32)), tot.ctypes.data_as(u64), hist.ctypes.data_as(u64)))
+        return counts, {k: int(v) for k, v in zip(MODPILEUP_TOTALS, tot)}, hist
+
+    def reset(self):
+        _check(lib().ffhip_modpileup_reset(self.h))
+
+    def close(self):
+        if self.h:
+            lib().ffhip_modpileup_free(self.h)
             self.h = None
 
 
@@ -903,6 +947,10 @@ class Batch:
         """the Pileup that later runs with RUN_MAP | RUN_TRUTH | RUN_PILEUP add to when they are finished (ffhip_batch_set_pileup); None detaches"""
         _check(lib().ffhip_batch_set_pileup(self.h, pileup.h if pileup is not None else None))
 
+    def set_modpileup(self, modpileup):
+        """the ModPileup that later runs with RUN_MAP | RUN_TRUTH | RUN_MOD_PROBS | RUN_MOD_PILEUP add to when they are finished (ffhip_batch_set_modpileup); None detaches"""
+        _check(lib().ffhip_batch_set_modpileup(self.h, modpileup.h if modpileup is not None else None))
+
     def truth(self, read: int) -> dict:
         """truth record of a run with RUN_TRUTH (ffhip_batch_truth): TRUTH_FIELDS as ints and ops (uint8 [dist + n_match] in path order, None unless status is 1)"""
         c = CTruthCall()
@@ -1104,6 +1152,21 @@ def op_pileup(engine: Engine, pileup: Pileup, q: int, tstart: int, tend: int, ca
     s = call if isinstance(call, bytes) else str(call).encode()
     o = np.ascontiguousarray(ops, dtype=np.uint8)
     _check(lib().ffhip_op_pileup(engine.h, pileup.h, int(q), int(tstart), int(tend), s, len(s), (o if o.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), o.size))
+
+
+def op_modpileup(engine: Engine, modpileup: ModPileup, q: int, tstart: int, tend: int, call, ml, ops):
+    """ffhip_op_modpileup: ONE alignment -- search q, span [tstart, tend), the call's letters, its 5mC bytes (one a letter) and its ops (0 .. 3) -- added into `modpileup`"""
+    s = call if isinstance(call, bytes) else str(call).encode()
+    o = np.ascontiguousarray(ops, dtype=np.uint8)
+    u8 = C.POINTER(C.c_uint8)
+    if ml is None:
+        pm = None
+    else:
+        v = np.ascontiguousarray(ml, dtype=np.uint8)
+        if v.size != len(s):
+            raise ValueError("op_modpileup: %d 5mC bytes for a call of %d letters" % (v.size, len(s)))
+        pm = (v if v.size else np.zeros(1, np.uint8)).ctypes.data_as(u8)
+    _check(lib().ffhip_op_modpileup(engine.h, modpileup.h, int(q), int(tstart), int(tend), s, pm, len(s), (o if o.size else np.zeros(1, np.uint8)).ctypes.data_as(u8), o.size))
 
 
 def op_map_stretch(engine: Engine, ref: MapRef, q: int, start: int, end: int) -> np.ndarray:

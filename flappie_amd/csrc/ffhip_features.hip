@@ -1,4 +1,4 @@
-// ffhip_features.hip -- host side of the per-read features (barcodes, adapters, map, poly tail, remap, events, site mods, variants, truth, truth from map, pileup):
+// ffhip_features.hip -- host side of the per-read features (barcodes, adapters, map, poly tail, remap, events, site mods, variants, truth, truth from map, pileup, mod pileup):
 // each feature's share of a batch's run (ffhip_annot.hpp), its device objects, setters and accessors (include/ffhip.h), and its single-read operator ffhip_op_*.
 // No kernel lives here (theirs are ffhip_barcodes.hip ... ffhip_variants.hip) and none is launched from here but through their launch_* functions, so the Makefile
 // compiles this file as C++.  ffhip_engine.hip reaches it through ffhip_annot.hpp only.
@@ -424,6 +424,9 @@ int ffhip::annots_prepare(ffhip_batch *b, unsigned flags) {
     }
     return FFHIP_OK;
 }
+template <class Pile> static void pileup_mark(Pile *p, const ffhip_batch *b) {      // work against it was enqueued on the batch's stream (pileup_wait)
+    for (int i = 0; i < b->eng->nstreams; i++) if (b->eng->streams[i] == b->stream) p->used[i] = true;
+}
 // Pileup (include/ffhip.h "pileup"): no record, no buffer of the batch's, so no row above.  The front's share: may this run ask
 int ffhip::pileup_check(const ffhip_batch *b, unsigned flags) {
     if (!(flags & FFHIP_RUN_PILEUP)) return FFHIP_OK;
@@ -440,7 +443,26 @@ void ffhip::pileup_launch(ffhip_batch *b) {
     const ReadMap rmap = b->packed ? ReadMap{ b->d_vb0, b->d_vb1, b->nread } : ReadMap();
     launch_pileup(b->stream, p->ref->view, (const TruthRead *)b->tru.list.dev, batch_nreads(b), b->map.rec.dev, (const int *)b->tru.rec.dev,
                   b->tru.rec.dev + truth_ops_at(b), b->bases(), b->Tb, rmap, p->view);
-    for (int i = 0; i < b->eng->nstreams; i++) if (b->eng->streams[i] == b->stream) p->used[i] = true;
+    pileup_mark(p, b);
+}
+// Mod pileup (include/ffhip.h "mod pileup"): the pileup's twin over the calls' 5mC bytes, with the same two shares
+int ffhip::modpileup_check(const ffhip_batch *b, unsigned flags) {
+    if (!(flags & FFHIP_RUN_MOD_PILEUP)) return FFHIP_OK;
+    static const char goes[] = "(FFHIP_RUN_MOD_PILEUP goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH | FFHIP_RUN_MOD_PROBS)";
+    if (!(flags & FFHIP_RUN_MAP)) return set_err(FFHIP_EINVAL, "mod pileup: the run does not make the map records %s", goes);
+    if (!(flags & FFHIP_RUN_TRUTH)) return set_err(FFHIP_EINVAL, "mod pileup: the run does not make the truth records %s", goes);
+    if (!(flags & FFHIP_RUN_MOD_PROBS)) return set_err(FFHIP_EINVAL, "mod pileup: the run does not make the 5mC probabilities %s", goes);
+    if (!b->tru.from_map) return set_err(FFHIP_EINVAL, "mod pileup: the batch is not in the mode of truth from map (ffhip_batch_set_truth_from_map)");
+    if (!b->modpile) return set_err(FFHIP_EINVAL, "mod pileup: no mod pileup is attached to the batch (ffhip_batch_set_modpileup)");
+    if (b->modpile->ref != b->map.ref) return set_err(FFHIP_EINVAL, "mod pileup: the attached mod pileup belongs to another reference than the batch's map reference");
+    return FFHIP_OK;
+}
+void ffhip::modpileup_launch(ffhip_batch *b) {
+    ffhip_modpileup *p = b->modpile;
+    const ReadMap rmap = b->packed ? ReadMap{ b->d_vb0, b->d_vb1, b->nread } : ReadMap();
+    launch_modpileup(b->stream, p->ref->view, (const TruthRead *)b->tru.list.dev, batch_nreads(b), b->map.rec.dev, (const int *)b->tru.rec.dev,
+                     b->tru.rec.dev + truth_ops_at(b), b->bases(), b->res.on_dev<uint8_t>(RF_ML), b->Tb, rmap, p->view);
+    pileup_mark(p, b);
 }
 // the copies of a finished run beside the block's: one a feature the run made, if it has a byte to bring
 int ffhip::annots_copy_down(ffhip_batch *b) {
@@ -781,19 +803,20 @@ extern "C" int ffhip_batch_set_truth_from_map(ffhip_batch *b, int on, int band) 
     return FFHIP_OK;
 }
 // ---- pileup (include/ffhip.h "pileup"; the kernel: ffhip_pileup.hip)
-static int pileup_wait(ffhip_pileup *p) {                // every accumulation enqueued against it, by any batch, is done
+template <class Pile> static int pileup_wait(Pile *p) {  // every accumulation enqueued against it, by any batch, is done (the pileup and the mod pileup)
     hipSetDevice(p->eng->device);
     for (int i = 0; i < p->eng->nstreams; i++)
         if (p->used[i]) { HIP_TRY(hipStreamSynchronize(p->eng->streams[i]), FFHIP_EHIP); p->used[i] = false; }
     return FFHIP_OK;
 }
-static int pileup_zero(ffhip_pileup *p) {
+template <class Pile> static int pileup_zero(Pile *p, int planes, int words) {      // the planes and the `words` uint64 behind view.totals
     hipStream_t s = p->eng->streams[0];
-    HIP_TRY(hipMemsetAsync(p->view.counts, 0, (size_t)kPileupPlanes * p->view.P * 4, s), FFHIP_EHIP);
-    HIP_TRY(hipMemsetAsync(p->view.totals, 0, (size_t)kPileupTotals * 8, s), FFHIP_EHIP);
+    HIP_TRY(hipMemsetAsync(p->view.counts, 0, (size_t)planes * p->view.P * 4, s), FFHIP_EHIP);
+    HIP_TRY(hipMemsetAsync(p->view.totals, 0, (size_t)words * 8, s), FFHIP_EHIP);
     HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
     return FFHIP_OK;
 }
+static int pileup_zero(ffhip_pileup *p) { return pileup_zero(p, kPileupPlanes, kPileupTotals); }
 extern "C" ffhip_pileup *ffhip_pileup_create(ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity) {
     if (!eng || !ref || ref->eng != eng) { set_err(FFHIP_EINVAL, "pileup: a reference of this engine"); return nullptr; }
     if (min_identity > 1000) { set_err(FFHIP_EINVAL, "pileup: min_identity is %d per mille (0 .. 1000)", min_identity); return nullptr; }
@@ -839,6 +862,58 @@ extern "C" int ffhip_batch_set_pileup(ffhip_batch *b, ffhip_pileup *p) {
     if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "pileup: a flip-flop model only (the run-length model's call is a list of runs)");
     if (p->eng != b->eng) return set_err(FFHIP_EINVAL, "pileup: the pileup belongs to another engine");
     b->pile = p;
+    return FFHIP_OK;
+}
+// ---- mod pileup (include/ffhip.h "mod pileup"; the kernel: ffhip_modpileup.hip): the totals and the histogram are one allocation, view.hist behind view.totals
+static int modpileup_zero(ffhip_modpileup *p) { return pileup_zero(p, kModPileupPlanes, kModPileupTotals + kModPileupBins); }
+extern "C" ffhip_modpileup *ffhip_modpileup_create(ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity, int lo, int hi) {
+    if (!eng || !ref || ref->eng != eng) { set_err(FFHIP_EINVAL, "mod pileup: a reference of this engine"); return nullptr; }
+    if (min_identity > 1000) { set_err(FFHIP_EINVAL, "mod pileup: min_identity is %d per mille (0 .. 1000)", min_identity); return nullptr; }
+    if (lo < 0 || lo >= hi || hi > 255) { set_err(FFHIP_EINVAL, "mod pileup: the thresholds are lo %d and hi %d (0 <= lo < hi <= 255)", lo, hi); return nullptr; }
+    hipSetDevice(eng->device);
+    ffhip_modpileup *p = new ffhip_modpileup();
+    p->eng = eng; p->ref = ref;
+    size_t P = 0;
+    for (int m : ref->rec_len) P += (size_t)m;
+    p->view.P = P; p->view.min_identity = min_identity < 0 ? 0 : min_identity; p->view.lo = lo; p->view.hi = hi;
+    const size_t bytes = (size_t)kModPileupPlanes * P * 4, words = (size_t)(kModPileupTotals + kModPileupBins) * 8;
+    if (dev_fill("mod pileup", { { (void **)&p->view.counts, nullptr, bytes }, { (void **)&p->view.totals, nullptr, words } })) {
+        set_err(FFHIP_ENOMEM, "mod pileup: the counters take %zu bytes of device memory, which could not be had", bytes + words);
+        delete p;
+        return nullptr;
+    }
+    p->view.hist = p->view.totals + kModPileupTotals;
+    if (modpileup_zero(p) != FFHIP_OK) { ffhip_modpileup_free(p); return nullptr; }
+    return p;
+}
+extern "C" void ffhip_modpileup_free(ffhip_modpileup *p) {
+    if (!p) return;
+    pileup_wait(p);
+    dev_free({ (void **)&p->view.counts, (void **)&p->view.totals });
+    delete p;
+}
+extern "C" int ffhip_modpileup_reset(ffhip_modpileup *p) {
+    if (!p) return set_err(FFHIP_EINVAL, "null mod pileup");
+    if (int rc = pileup_wait(p)) return rc;
+    return modpileup_zero(p);
+}
+extern "C" size_t ffhip_modpileup_positions(const ffhip_modpileup *p) { return p ? p->view.P : 0; }
+extern "C" int ffhip_modpileup_download(ffhip_modpileup *p, uint32_t *counts, ffhip_modpileup_totals *totals, uint64_t *hist) {
+    if (!p) return set_err(FFHIP_EINVAL, "null mod pileup");
+    static_assert(sizeof(ffhip_modpileup_totals) == kModPileupTotals * 8 && FFHIP_MODPILEUP_PLANES == kModPileupPlanes, "the totals come down as they stand");
+    if (int rc = pileup_wait(p)) return rc;
+    if (counts) HIP_TRY(hipMemcpy(counts, p->view.counts, (size_t)kModPileupPlanes * p->view.P * 4, hipMemcpyDeviceToHost), FFHIP_EHIP);
+    if (totals) HIP_TRY(hipMemcpy(totals, p->view.totals, sizeof *totals, hipMemcpyDeviceToHost), FFHIP_EHIP);
+    if (hist) HIP_TRY(hipMemcpy(hist, p->view.hist, (size_t)kModPileupBins * 8, hipMemcpyDeviceToHost), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+extern "C" int ffhip_batch_set_modpileup(ffhip_batch *b, ffhip_modpileup *p) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "mod pileup: the batch is between a run and its finish");
+    if (!p) { b->modpile = nullptr; return FFHIP_OK; }
+    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE || b->mdl->nbase != 5) return set_err(FFHIP_EINVAL, "mod pileup: the model has no modified base (a model of the alphabet ACGTZ)");
+    if (p->eng != b->eng) return set_err(FFHIP_EINVAL, "mod pileup: the mod pileup belongs to another engine");
+    b->modpile = p;
     return FFHIP_OK;
 }
 extern "C" long long ffhip_debug_map_truth_bound(int nblock, int max_error) {
@@ -961,34 +1036,52 @@ extern "C" int ffhip_op_map_stretch(ffhip_engine *eng, const ffhip_map_ref *ref,
     return FFHIP_OK;
 }
 
-// one alignment from host arguments added into a pileup (k_pileup; include/ffhip.h "pileup"): a map record, a truth record and a list entry made here
-extern "C" int ffhip_op_pileup(ffhip_engine *eng, ffhip_pileup *p, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops) {
-    OP_ENTER(eng);
-    if (!p || p->eng != eng || (n && !call) || !ops) return set_err(FFHIP_EINVAL, "bad pileup arguments (a pileup of this engine, a call of n letters, nops ops)");
-    const ffhip_map_ref *ref = p->ref;
-    if (int rc = span_check("pileup", ref, q, tstart, tend)) return rc;
-    if (n > (size_t)kTruthMaxLen || nops > (size_t)2 * kTruthMaxLen) return set_err(FFHIP_EINVAL, "pileup: a call of %zu bases and %zu ops (at most %d bases)", n, nops, kTruthMaxLen);
-    if (const size_t i = bad_letter(call, n); i < n) return set_err(FFHIP_EINVAL, "pileup: position %zu of the call: '%c' is not one of A C G T Z", i, call[i]);
+// one alignment from host arguments added into a pileup or a mod pileup (k_pileup, k_modpileup): the checks of both, then a map record, a truth record and a list
+// entry made here, and the ops and the call on the device
+struct PileOp { void *mrec; int *trec; TruthRead *list; uint8_t *ops; char *call; };
+static int pile_op(const char *who, TmpDev &tmp, hipStream_t s, const ffhip_map_ref *ref, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops, PileOp *out) {
+    if (int rc = span_check(who, ref, q, tstart, tend)) return rc;
+    if (n > (size_t)kTruthMaxLen || nops > (size_t)2 * kTruthMaxLen) return set_err(FFHIP_EINVAL, "%s: a call of %zu bases and %zu ops (at most %d bases)", who, n, nops, kTruthMaxLen);
+    if (const size_t i = bad_letter(call, n); i < n) return set_err(FFHIP_EINVAL, "%s: position %zu of the call: '%c' is not one of A C G T Z", who, i, call[i]);
     const size_t m = (size_t)(tend - tstart);
     size_t cnt[4] = { 0, 0, 0, 0 };
     for (size_t k = 0; k < nops; k++) {
-        if (ops[k] > 3) return set_err(FFHIP_EINVAL, "pileup: op %zu: code %d is not one of 0 .. 3", k, (int)ops[k]);
+        if (ops[k] > 3) return set_err(FFHIP_EINVAL, "%s: op %zu: code %d is not one of 0 .. 3", who, k, (int)ops[k]);
         cnt[ops[k]]++;
     }
     if (cnt[0] + cnt[1] + cnt[3] != m || cnt[0] + cnt[1] + cnt[2] != n)
-        return set_err(FFHIP_EINVAL, "pileup: the ops consume %zu truth and %zu call bases, the span has %zu and the call %zu", cnt[0] + cnt[1] + cnt[3], cnt[0] + cnt[1] + cnt[2], m, n);
+        return set_err(FFHIP_EINVAL, "%s: the ops consume %zu truth and %zu call bases, the span has %zu and the call %zu", who, cnt[0] + cnt[1] + cnt[3], cnt[0] + cnt[1] + cnt[2], m, n);
     ffhip_map_call mrec;
     memset(&mrec, 0, sizeof mrec);
     mrec.status = 1; mrec.n = (int)n; mrec.nanchor = 1; mrec.q = q; mrec.tstart = tstart; mrec.tend = tend;
     const int trec[kTruthRecInts] = { 1, (int)n, (int)m, (int)(cnt[1] + cnt[2] + cnt[3]), (int)cnt[0], (int)cnt[1], (int)cnt[2], (int)cnt[3], 0, (int)nops, 0, 0 };
     const TruthRead tr{ 0ull, 0ull, 0u, (int)m, 1, 0, (int)nops, 0 };
-    void *d_mrec = tmp.upload(&mrec, sizeof mrec, s);
-    int *d_trec = (int *)tmp.upload(trec, sizeof trec, s);
-    TruthRead *d_list = (TruthRead *)tmp.upload(&tr, sizeof tr, s);
-    uint8_t *d_ops = (uint8_t *)tmp.upload(ops, nops, s);
-    char *d_call = (char *)tmp.upload(n ? call : "", n ? n : 1, s);
-    if (!d_mrec || !d_trec || !d_list || !d_ops || !d_call) OP_NOMEM();
-    launch_pileup(s, ref->view, d_list, 1, d_mrec, d_trec, d_ops, d_call, n > 0 ? (int)n : 1, ReadMap(), p->view);
+    out->mrec = tmp.upload(&mrec, sizeof mrec, s);
+    out->trec = (int *)tmp.upload(trec, sizeof trec, s);
+    out->list = (TruthRead *)tmp.upload(&tr, sizeof tr, s);
+    out->ops = (uint8_t *)tmp.upload(ops, nops, s);
+    out->call = (char *)tmp.upload(n ? call : "", n ? n : 1, s);
+    if (!out->mrec || !out->trec || !out->list || !out->ops || !out->call) OP_NOMEM();
+    return FFHIP_OK;
+}
+extern "C" int ffhip_op_pileup(ffhip_engine *eng, ffhip_pileup *p, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops) {
+    OP_ENTER(eng);
+    if (!p || p->eng != eng || (n && !call) || !ops) return set_err(FFHIP_EINVAL, "bad pileup arguments (a pileup of this engine, a call of n letters, nops ops)");
+    PileOp d;
+    if (int rc = pile_op("pileup", tmp, s, p->ref, q, tstart, tend, call, n, ops, nops, &d)) return rc;
+    launch_pileup(s, p->ref->view, d.list, 1, d.mrec, d.trec, d.ops, d.call, n > 0 ? (int)n : 1, ReadMap(), p->view);
+    return op_done(s);
+}
+extern "C" int ffhip_op_modpileup(ffhip_engine *eng, ffhip_modpileup *p, int q, int tstart, int tend, const char *call, const uint8_t *ml, size_t n, const uint8_t *ops, size_t nops) {
+    OP_ENTER(eng);
+    if (!p || p->eng != eng || (n && (!call || !ml)) || !ops)
+        return set_err(FFHIP_EINVAL, "bad mod pileup arguments (a mod pileup of this engine, a call of n letters with its n 5mC bytes, nops ops)");
+    PileOp d;
+    if (int rc = pile_op("mod pileup", tmp, s, p->ref, q, tstart, tend, call, n, ops, nops, &d)) return rc;
+    const uint8_t zero = 0;
+    const uint8_t *d_ml = (const uint8_t *)tmp.upload(n ? ml : &zero, n ? n : 1, s);
+    if (!d_ml) OP_NOMEM();
+    launch_modpileup(s, p->ref->view, d.list, 1, d.mrec, d.trec, d.ops, d.call, d_ml, n > 0 ? (int)n : 1, ReadMap(), p->view);
     return op_done(s);
 }
 

@@ -81,6 +81,14 @@ struct ffhip_pileup {
     ffhip::PileupView view{};
     bool used[4] = { false, false, false, false };
 };
+// a mod pileup on the device (ffhip_modpileup_create; the kernel's view of it is ModPileupView): 10 planes of P uint32, and eight uint64 totals with the 256 uint64
+// bins of the histogram behind them in one allocation; `used` as the pileup's
+struct ffhip_modpileup {
+    ffhip_engine *eng = nullptr;
+    const ffhip_map_ref *ref = nullptr;
+    ffhip::ModPileupView view{};
+    bool used[4] = { false, false, false, false };
+};
 
 // a function or table one file of the library defines for another and the library does not export
 #define FFHIP_LOCAL __attribute__((visibility("hidden")))

@@ -300,6 +300,14 @@ struct PileupView { unsigned *counts; unsigned long long *totals; size_t P; int 
 constexpr int kPileupPlanes = 12, kPileupTotals = 8;
 void launch_pileup(hipStream_t s, const MapRefView &ref, const TruthRead *list, int count, const void *map_records, const int *truth_records, const uint8_t *ops,
                    const char *bases, int Tb, ReadMap map, const PileupView &pv);
+// mod pileup (k_modpileup, ffhip_modpileup.hip; include/ffhip.h "mod pileup"): the same entries, records, ops and letters, and the calls' 5mC bytes `ml` (rows as the
+// letters'): the read's counts at the reference's C (- strand: G) positions added into the 10 planes of P uint32 [strand][mod canon fail diff del][position], the
+// eight uint64 totals { reads, skipped, sites, mod, canon, fail, diff, del } and the 256 uint64 bins of the histogram of the counted bytes.  The reference's letters
+// come from ref.words.  One launch, a workgroup an entry, atomics only.
+struct ModPileupView { unsigned *counts; unsigned long long *totals, *hist; size_t P; int min_identity, lo, hi; };
+constexpr int kModPileupColumns = 5, kModPileupPlanes = 2 * kModPileupColumns, kModPileupTotals = 8, kModPileupBins = 256;
+void launch_modpileup(hipStream_t s, const MapRefView &ref, const TruthRead *list, int count, const void *map_records, const int *truth_records, const uint8_t *ops,
+                      const char *bases, const uint8_t *ml, int Tb, ReadMap map, const ModPileupView &pv);
 // the signal of every base of a mapped read (k_events, ffhip_events.hip; include/ffhip.h "events"): per listed read whose remap record at records[read] says
 // { status 1, end 0 }, L events of 16 bytes { int32 first, count; float mean, sd } at events[out ..], from the read's samples sig[sig .. sig + n) and its bytes at the
 // read's row of the (Tb + 1)-entry byte buffer `rm`; any other read writes nothing.  One form; the launch comes behind launch_remap on the same stream.

@@ -49,6 +49,7 @@
 #include "../../include/flappie_truth.h"
 #include "../../include/flappie_align.h"
 #include "../../include/flappie_pileup.h"
+#include "../../include/flappie_modpileup.h"
 #include "../../include/networks.h"
 
 const char *argp_program_version = "flappie (MI355X/HIP) 0.1, interface of flappie 2.1.3";
@@ -141,10 +142,24 @@ static struct argp_option options[] = {
     {"map-sam", 291, "aln.sam", 0, "With --truth-from-map: the alignments as a SAM file with @SQ lines: one line per read with a call, in output order; a read that is mapped and aligned with FLAG 0 or 16, POS, the CIGAR (=XID) in forward-strand order, SEQ (Z written as C) and QUAL turned to the forward strand and NM:i; every other read unmapped (FLAG 4). SEQ is always the whole call: --reverse, --trim-barcodes, --trim-adapters and --split-reads do not alter it"},
     {"map-pileup", 292, "pileup.tsv", 0, "With --truth-from-map: per position of the reference, the aligned calls' counts, added up on the GPU over the whole run and written at its end: one line for every position of every record in reference order, no header: record, 0-based position, reference letter, depth (A, C, G, T and del of both strands), then A, C, G, T, del, ins of the + strand and of the - strand. An insertion stands at the position to its left on the forward strand; insertions before the first or behind the last aligned base are counted on stderr only (edge_ins). Inserted letters are not kept. The whole call counts: --reverse, --trim-barcodes, --trim-adapters and --split-reads do not alter it. stdout, hits.tsv, acc.tsv and aln.sam do not change"},
     {"map-pileup-min-identity", 293, "permille", 0, "With --map-pileup: count only reads whose alignment's identity, matches over matches + mismatches + insertions + deletions, is at least this many thousandths (0-1000, default 0); the others are counted as skipped"},
+    {"map-mods", 294, "mods.bed", 0, "With --truth-from-map and a model with a modified base (r941_5mC): per C of the reference, how methylated the aligned calls say it is, added up on the GPU over the whole run and written at its end as a bedMethyl table (the eighteen columns of modkit pileup, no header, modification code m): a row for every C of the + strand and every G of the - strand that passes --map-mods-motif and is covered. A C or Z call on such a site counts as modified when its 5mC byte (ML, floor(256 p)) is at least --map-mods-hi, as canonical when it is at most --map-mods-lo, and as failed between; another letter counts as Ndiff, a deletion as Ndelete. The 5mC bytes are made whether or not --modbase-tags is given. The whole call counts: --reverse, the trims and --split-reads do not alter it. stdout, hits.tsv, acc.tsv, aln.sam and pileup.tsv do not change"},
+    {"map-mods-hi", 295, "byte", 0, "With --map-mods: a 5mC byte of at least this is a modified call (0-255, above --map-mods-lo; default 205, p >= 0.8). The default comes from reasoning, not from reads: see --map-mods-hist"},
+    {"map-mods-lo", 296, "byte", 0, "With --map-mods: a 5mC byte of at most this is a canonical call (0-255, below --map-mods-hi; default 50, p < 0.2)"},
+    {"map-mods-min-identity", 297, "permille", 0, "With --map-mods: count only reads whose alignment's identity is at least this many thousandths (0-1000, default 0), as --map-pileup-min-identity"},
+    {"map-mods-motif", 298, "CG|C", 0, "With --map-mods: the sites written: CG (default: a C followed by a G, and on the - strand a G behind a C) or C (every C, every G on the - strand)"},
+    {"map-mods-combine-strands", 299, 0, 0, "With --map-mods and the motif CG: one row a CpG, the - strand's counts of its G added to the + strand's row of its C, strand '.'"},
+    {"map-mods-hist", 300, "hist.tsv", 0, "With --map-mods: 256 lines of byte and count: how many counted C or Z calls on a site had each 5mC byte -- the distribution to choose --map-mods-hi and --map-mods-lo from"},
 #endif
 #ifdef BUILD_RUNNIE
     {"map-pileup", 292, "pileup.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-pileup-min-identity", 293, "permille", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-mods", 294, "mods.bed", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-mods-hi", 295, "byte", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-mods-lo", 296, "byte", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-mods-min-identity", 297, "permille", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-mods-motif", 298, "CG|C", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-mods-combine-strands", 299, 0, OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-mods-hist", 300, "hist.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map", 285, "ref.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-out", 286, "hits.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-window", 287, "W", OPTION_HIDDEN, "(flappie's option: refused here)"},
@@ -243,6 +258,11 @@ static char *tfm_sam_path = NULL;
 /* flappie: the file of --map-pileup and --map-pileup-min-identity (-1: not given) (runnie: seen, to be refused) */
 static char *pu_path = NULL;
 static int pu_min_identity = -1;
+/* flappie: the file of --map-mods, its thresholds and min identity (-1: not given), its motif (NULL: not given), --map-mods-combine-strands and the file of
+ * --map-mods-hist (runnie: seen, to be refused) */
+static char *mm_path = NULL, *mm_hist_path = NULL, *mm_motif = NULL;
+static int mm_hi = -1, mm_lo = -1, mm_min_identity = -1;
+static bool mm_combine = false;
 static int map_window = -1;
 #ifndef BUILD_RUNNIE
 static int map_max_error = -1;
@@ -419,6 +439,21 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
         pu_min_identity = (int)v;
         break;
     }
+    case 294: mm_path = arg; break;
+    case 295: case 296: case 297: {
+        char *end = NULL;
+        const long v = strtol(arg, &end, 10), top = key == 297 ? 1000 : 255;
+        if (end == arg || *end != '\0' || v < 0 || v > top)
+            errx(EXIT_FAILURE, "--map-mods-%s must be a whole number from 0 to %ld", key == 295 ? "hi" : key == 296 ? "lo" : "min-identity", top);
+        *(key == 295 ? &mm_hi : key == 296 ? &mm_lo : &mm_min_identity) = (int)v;
+        break;
+    }
+    case 298:
+        if (0 != strcmp(arg, "CG") && 0 != strcmp(arg, "C")) errx(EXIT_FAILURE, "--map-mods-motif is CG or C, not \"%s\"", arg);
+        mm_motif = arg;
+        break;
+    case 299: mm_combine = true; break;
+    case 300: mm_hist_path = arg; break;
 #ifdef BUILD_RUNNIE
     case 287: case 288: map_opts = true; break;
     case 270: case 271: case 272: case 273: case 274: ad_opts = true; break;
@@ -792,11 +827,14 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
 /* flappie --map-pileup: the one pileup of the run, attached to every batch object and downloaded once at the end; its table */
 static ffhip_pileup *pu_dev = NULL;
 static FILE *pu_out = NULL;
+/* flappie --map-mods: likewise the one mod pileup of the run; its table and the histogram's file */
+static ffhip_modpileup *mm_dev = NULL;
+static FILE *mm_out = NULL, *mm_hist = NULL;
 /* --modbase-tags: the 5mC bytes of the called bases come from the device (FFHIP_RUN_MOD_PROBS); --emit-moves: the move table does (FFHIP_RUN_MOVES);
  * --barcodes: the reads' barcode records do (FFHIP_RUN_BARCODES); --adapters: their adapter records (FFHIP_RUN_ADAPTERS); --poly-tail: their poly tail
  * records (FFHIP_RUN_POLYTAIL) */
 static unsigned run_flags(void) {
-    return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | (args.modbase_tags ? FFHIP_RUN_MOD_PROBS : 0u) |
+    return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | ((args.modbase_tags || mm_dev) ? FFHIP_RUN_MOD_PROBS : 0u) | (mm_dev ? FFHIP_RUN_MOD_PILEUP : 0u) |
            (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (mp_dev ? FFHIP_RUN_MAP : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | ((tr_refs || tfm_on) ? FFHIP_RUN_TRUTH : 0u) | (pu_dev ? FFHIP_RUN_PILEUP : 0u) |
            (ev_out ? FFHIP_RUN_EVENTS : 0u) | (md_out ? FFHIP_RUN_REMAP_MODS : 0u) | (vr_out ? FFHIP_RUN_REMAP_VARIANTS : 0u);
 }
@@ -865,6 +903,7 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
     if (tr_refs) { const int rc = batch_set_truth(b, its, n); if (rc) return rc; }
     if (tfm_on) { const int rc = ffhip_batch_set_truth_from_map(b, 1, args.truth_band); if (rc) return rc; }
     if (pu_dev) { const int rc = ffhip_batch_set_pileup(b, pu_dev); if (rc) return rc; }
+    if (mm_dev) { const int rc = ffhip_batch_set_modpileup(b, mm_dev); if (rc) return rc; }
     return ffhip_batch_run(b, args.temperature, flags);
 }
 #endif
@@ -2201,6 +2240,8 @@ int main(int argc, char *argv[]) {
     if (args.truth) errx(EXIT_FAILURE, "--truth is flappie's: the run-length model's call is a list of runs");
     if (tfm_on || tfm_sam_path) errx(EXIT_FAILURE, "--truth-from-map and --map-sam are flappie's: the run-length model's call is a list of runs");
     if (pu_path || pu_min_identity >= 0) errx(EXIT_FAILURE, "--map-pileup and --map-pileup-min-identity are flappie's: the run-length model's call is a list of runs");
+    if (mm_path || mm_hi >= 0 || mm_lo >= 0 || mm_min_identity >= 0 || mm_motif || mm_combine || mm_hist_path)
+        errx(EXIT_FAILURE, "--map-mods and its --map-mods-* options are flappie's: the run-length model's call is a list of runs and it has no modified base");
     if (args.remap_events) errx(EXIT_FAILURE, "--remap-events is flappie's: it goes with --remap, which the run-length model does not have");
     if (mods_path) errx(EXIT_FAILURE, "--remap-mods is flappie's: it goes with --remap, which the run-length model does not have");
     if (vars_path || vars_out_path || vars_opts) errx(EXIT_FAILURE, "--remap-variants is flappie's: it goes with --remap, which the run-length model does not have");
@@ -2245,6 +2286,18 @@ int main(int argc, char *argv[]) {
     if (tfm_sam_path && !tfm_on) errx(EXIT_FAILURE, "--map-sam goes with --truth-from-map");
     if (pu_path && !tfm_on) errx(EXIT_FAILURE, "--map-pileup goes with --truth-from-map: it counts what the alignments say");
     if (pu_min_identity >= 0 && NULL == pu_path) errx(EXIT_FAILURE, "--map-pileup-min-identity goes with --map-pileup");
+    /* --map-mods: likewise; the thresholds' defaults read p >= 0.8 and p < 0.2 of ml = floor(256 p) */
+    if ((mm_hi >= 0 || mm_lo >= 0 || mm_min_identity >= 0 || mm_motif || mm_combine || mm_hist_path) && NULL == mm_path)
+        errx(EXIT_FAILURE, "--map-mods-hi, --map-mods-lo, --map-mods-min-identity, --map-mods-motif, --map-mods-combine-strands and --map-mods-hist go with --map-mods");
+    if (mm_path && !tfm_on) errx(EXIT_FAILURE, "--map-mods goes with --truth-from-map: it counts what the alignments say");
+    if (mm_path && !flappie_model_has_modbase(args.model))      /* (the registry knows: before any file or the GPU is touched) */
+        errx(EXIT_FAILURE, "--map-mods needs a model with a modified base (r941_5mC); \"%s\" has none", flappie_model_string(args.model));
+    if (mm_path) {
+        if (mm_hi < 0) mm_hi = 205;
+        if (mm_lo < 0) mm_lo = 50;
+        if (mm_lo >= mm_hi) errx(EXIT_FAILURE, "--map-mods-lo (%d) must be below --map-mods-hi (%d)", mm_lo, mm_hi);
+        if (mm_combine && mm_motif && 0 != strcmp(mm_motif, "CG")) errx(EXIT_FAILURE, "--map-mods-combine-strands goes with the motif CG: a lone C has no partner on the other strand");
+    }
     if (map_path) {
         char why[256];
         mp_ref = flappie_map_ref_read(map_path, why, sizeof why);
@@ -2292,6 +2345,8 @@ int main(int argc, char *argv[]) {
             flappie_align_write_sam_header(tfm_sam, mp_ref);
         }
         if (pu_path && NULL == (pu_out = fopen(pu_path, "w"))) errx(EXIT_FAILURE, "--map-pileup %s: cannot be written", pu_path);
+        if (mm_path && NULL == (mm_out = fopen(mm_path, "w"))) errx(EXIT_FAILURE, "--map-mods %s: cannot be written", mm_path);
+        if (mm_hist_path && NULL == (mm_hist = fopen(mm_hist_path, "w"))) errx(EXIT_FAILURE, "--map-mods-hist %s: cannot be written", mm_hist_path);
     }
     if (args.truth) {
         char why[256];
@@ -2345,6 +2400,10 @@ int main(int argc, char *argv[]) {
     if (pu_out && NULL == (pu_dev = ffhip_pileup_create(eng, mp_dev, pu_min_identity))) {
         stop_reader_procs();
         errx(EXIT_FAILURE, "--map-pileup: %s", ffhip_last_error());
+    }
+    if (mm_out && NULL == (mm_dev = ffhip_modpileup_create(eng, mp_dev, mm_min_identity, mm_lo, mm_hi))) {
+        stop_reader_procs();
+        errx(EXIT_FAILURE, "--map-mods: %s", ffhip_last_error());
     }
 #endif
     hid_t hdf5out = open_or_create_hdf5(args.trace);
@@ -2434,6 +2493,23 @@ int main(int argc, char *argv[]) {
         free(counts);
         if (0 != fclose(pu_out)) warnx("--map-pileup %s: write failed", pu_path);
         ffhip_pileup_free(pu_dev);
+    }
+    if (mm_dev) {                      /* the bedMethyl table and the histogram, once: every batch object is gone, so every accumulation is done */
+        const size_t P = ffhip_modpileup_positions(mm_dev);
+        uint32_t *counts = malloc((P ? P : 1) * FFHIP_MODPILEUP_PLANES * sizeof *counts);
+        ffhip_modpileup_totals tot;
+        uint64_t hist[256];
+        unsigned long long rows = 0;
+        if (NULL == counts || 0 != ffhip_modpileup_download(mm_dev, counts, &tot, hist)) warnx("--map-mods: %s", counts ? ffhip_last_error() : "out of memory for the table");
+        else {
+            flappie_modpileup_write(mm_out, mp_ref, counts, (mm_motif && 0 == strcmp(mm_motif, "C")) ? FLAPPIE_MODS_MOTIF_C : FLAPPIE_MODS_MOTIF_CG, mm_combine, &rows);
+            if (mm_hist) flappie_modpileup_hist_write(mm_hist, hist);
+            flappie_modpileup_summary_print(stderr, &tot, rows);
+        }
+        free(counts);
+        if (0 != fclose(mm_out)) warnx("--map-mods %s: write failed", mm_path);
+        if (mm_hist && 0 != fclose(mm_hist)) warnx("--map-mods-hist %s: write failed", mm_hist_path);
+        ffhip_modpileup_free(mm_dev);
     }
     if (mp_ref) {                      /* reads, mapped, unmapped, discordant; the mapped reads' anchor distances over their anchor bases */
         flappie_map_summary_print(stderr, &mp_sum);

@@ -153,6 +153,13 @@ typedef struct {
  * returns is that of the same run without the flag.  Without FFHIP_RUN_TRUTH, without FFHIP_RUN_MAP, outside the mode, with no pileup attached or with a pileup of
  * another reference than the batch's: FFHIP_EINVAL with a text that says which. */
 #define FFHIP_RUN_PILEUP     8388608u
+/* With FFHIP_RUN_MAP | FFHIP_RUN_TRUTH | FFHIP_RUN_MOD_PROBS in the mode of ffhip_batch_set_truth_from_map, a 5-base model: every aligned read's 5mC bytes classed and
+ * added, per reference C (- strand: G), into the mod pileup attached with ffhip_batch_set_modpileup ("mod pileup" below) -- on the device (k_modpileup), as the last
+ * step of ffhip_batch_finish, from the records, letters and bytes the caller reads.  Nothing comes down per read and the batch holds nothing new
+ * (ffhip_debug_batch_device_bytes does not change); everything the run returns is that of the same run without the flag.  Without FFHIP_RUN_MAP, FFHIP_RUN_TRUTH or
+ * FFHIP_RUN_MOD_PROBS, outside the mode, with no mod pileup attached or with one of another reference than the batch's: FFHIP_EINVAL with a text that says which.
+ * FFHIP_RUN_PILEUP is neither required nor excluded. */
+#define FFHIP_RUN_MOD_PILEUP (1u << 24)   /* 16777216: the bit behind FFHIP_RUN_PILEUP */
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -812,6 +819,42 @@ size_t ffhip_pileup_positions(const ffhip_pileup *p);
 int ffhip_pileup_download(ffhip_pileup *p, uint32_t *counts /* [12][P] */, ffhip_pileup_totals *totals);
 int ffhip_batch_set_pileup(ffhip_batch *b, ffhip_pileup *p);
 int ffhip_op_pileup(ffhip_engine *eng, ffhip_pileup *p, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops);
+/* Mod pileup: per reference C, how many aligned calls say "methylated", "not", or neither there, added up over all the reads of all the batches it is attached to
+ * (tests/modpileup_ref.py restates this).  The pileup's twin over the 5mC bytes of ffhip_batch_mod_probs: integer adds only, the same bytes whatever the batch
+ * size, packing, pairing or read order.
+ *   A mod pileup belongs to one ffhip_map_ref of K records of M_k bases; off_k and P as the pileup's.
+ *   Counters: 10 planes of P uint32, [strand o][column c][position]: c = 0 mod, 1 canon, 2 fail, 3 diff, 4 del.  Eight uint64 totals: reads, skipped, sites, mod,
+ *     canon, fail, diff, del.  A histogram of 256 uint64: how many counted C / Z calls on a reference C had each byte -- to see the distribution and choose thresholds.
+ *   Fixed at creation: min_identity in per mille by the pileup's rule (negative: 0; above 1000: refused), and two byte thresholds 0 <= lo < hi <= 255.
+ *   Which reads count: the pileup's rule -- map status 1, truth status 1 and 1000 n_match >= min_identity (n_match + n_mismatch + n_ins + n_del) in 64-bit integers.
+ *     A read with both statuses 1 that fails the test adds 1 to `skipped` and nothing else; any other read adds nothing.
+ *   What a counted read adds: q = 2 k + o and the span [tstart, tend) of its map record, m = tend - tstart; its call s of n letters; its n bytes ml, aligned with s
+ *     (ffhip_batch_mod_probs); the K ops of its truth record.  reads += 1; then the ops from (j, i) = (0, 0):
+ *       '=' (0) or 'X' (1): f = o ? M_k - 1 - (tstart + j) : tstart + j.  The op is ON A SITE when the forward letter of record k at f is C (o = 0) or G (o = 1).
+ *         On a site: sites += 1; s_i is C or Z: v = ml[i], hist[v] += 1, and the column is mod (v >= hi), canon (v <= lo) or fail (between); any other letter:
+ *         diff.  count[o][column][off_k + f] += 1 and the total of the same name += 1.  Then j++, i++.  The class follows the call's LETTER, not the op code.
+ *       'D' (3): f as above; on a site: sites += 1, column del.  j++.
+ *       'I' (2): i++, and nothing else.
+ *     An op's contribution depends on the op, j, i and the reference's letter alone, so the kernel takes an op a thread with j and i from prefix counts.
+ *   Counters wrap at 2^32 (the totals and the histogram at 2^64); there is no guard.
+ *   When: the last step of a successful ffhip_batch_finish of a run with FFHIP_RUN_MOD_PILEUP, where the pileup's stands: behind the f32 re-runs' patches (they patch
+ *     the letters and the bytes too) and in the innermost finish of the time-out fallback.  A side batch never counts.  Its order against k_pileup is free.
+ * ffhip_modpileup_create: zeroed counters; a bad min_identity or thresholds: NULL with a text.  The reference must outlive it, and it every batch it is attached to.
+ * ffhip_modpileup_free / _reset / _download wait for every accumulation enqueued against it; each output of download may be NULL.  _positions: P.
+ * ffhip_batch_set_modpileup: the mod pileup of the batch's later runs with the flag; NULL detaches.  One of another engine, a model whose alphabet is not ACGTZ, or a
+ *   call between a run and its finish: FFHIP_EINVAL.
+ * ffhip_op_modpileup: the kernel on ONE alignment from host arguments, added into p: ffhip_op_pileup's refusals, and ml NULL with n > 0; nothing is added by any.
+ *   The ops may disagree with the letters.  The identity test applies. */
+typedef struct ffhip_modpileup ffhip_modpileup;
+typedef struct { uint64_t reads, skipped, sites, mod, canon, fail, diff, del; } ffhip_modpileup_totals;      /* 64 bytes */
+#define FFHIP_MODPILEUP_PLANES 10
+ffhip_modpileup *ffhip_modpileup_create(ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity, int lo, int hi);
+void ffhip_modpileup_free(ffhip_modpileup *p);
+int ffhip_modpileup_reset(ffhip_modpileup *p);
+size_t ffhip_modpileup_positions(const ffhip_modpileup *p);
+int ffhip_modpileup_download(ffhip_modpileup *p, uint32_t *counts /* [10][P] */, ffhip_modpileup_totals *totals, uint64_t *hist /* [256] */);
+int ffhip_batch_set_modpileup(ffhip_batch *b, ffhip_modpileup *p);
+int ffhip_op_modpileup(ffhip_engine *eng, ffhip_modpileup *p, int q, int tstart, int tend, const char *call, const uint8_t *ml, size_t n, const uint8_t *ops, size_t nops);
 int ffhip_runlength_viterbi(ffhip_engine *eng, ffhip_mat param, int *path /* nblock */, float *score);
 /* decoders of the first-generation head on [4 nbase x nblock] matrices: decode_runlength (decode.c:694-767), posterior_runlength
  * (decode.c:793-892; post is [4 nbase x nblock + 1]), runlengths_mean (decode.c:576-603) */
