@@ -40,6 +40,12 @@ PILEUP_TOTALS = ("reads", "skipped", "match", "mismatch", "del", "ins", "edge_in
 RUN_MOD_PILEUP = 16777216  # with RUN_MAP | RUN_TRUTH | RUN_MOD_PROBS in the same mode: every aligned read's 5mC bytes classed per reference C into the ModPileup of Batch.set_modpileup
 MODPILEUP_TOTALS = ("reads", "skipped", "sites", "mod", "canon", "fail", "diff", "del")      # ffhip_modpileup_totals, eight uint64
 MODPILEUP_COLUMNS = ("mod", "canon", "fail", "diff", "del")
+RUN_CONSENSUS = 33554432   # with RUN_MAP | RUN_TRUTH in the same mode: every aligned read's forward letters, deletions and inserted letters added per position into the Consensus of Batch.set_consensus
+CONSENSUS_TOTALS = ("reads", "skipped", "bases", "del", "ins_bases", "long_ins", "edge_ins", "reserved")      # ffhip_consensus_totals, eight uint64
+CONSENSUS_PLANES = 37    # FFHIP_CONSENSUS_PLANES: A C G T del, then A C G T of each of the CONSENSUS_MINOR insertion columns behind the position
+CONSENSUS_MINOR = 8
+CONSENSUS_LOW, CONSENSUS_SAME, CONSENSUS_SUB, CONSENSUS_DEL, CONSENSUS_INS = 0, 1, 2, 3, 4      # a cell's `what`: one of the first four, CONSENSUS_INS a bit beside it
+CONSENSUS_CELL = np.dtype([("n", "u1"), ("what", "u1"), ("s", "S10"), ("depth", "<u4")])       # ffhip_consensus_cell, 16 bytes
 MAP_SEGMENT = 2048       # FFHIP_MAP_SEGMENT (include/ffhip.h "map"): the columns one task of k_map_scan owns; checked against the library at load
 MAP_MAX_TOTAL = 1 << 20
 MAP_MAX_ANCHOR = 4096
@@ -353,6 +359,17 @@ def lib():
     L.ffhip_modpileup_download.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.ffhip_batch_set_modpileup.argtypes = [vp, vp]
     L.ffhip_op_modpileup.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t]
+    L.ffhip_consensus_create.restype = vp
+    L.ffhip_consensus_create.argtypes = [vp, vp, C.c_int]
+    L.ffhip_consensus_free.restype = None
+    L.ffhip_consensus_free.argtypes = [vp]
+    L.ffhip_consensus_reset.argtypes = [vp]
+    L.ffhip_consensus_positions.restype = C.c_size_t
+    L.ffhip_consensus_positions.argtypes = [vp]
+    L.ffhip_consensus_download.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.ffhip_consensus_call.argtypes = [vp, C.c_int, vp]
+    L.ffhip_batch_set_consensus.argtypes = [vp, vp]
+    L.ffhip_op_consensus.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t]
     L.ffhip_debug_map_truth_bound.restype = C.c_longlong
     L.ffhip_debug_map_truth_bound.argtypes = [C.c_int, C.c_int]
     _LIB = L
@@ -664,6 +681,41 @@ class ModPileup:
             self.h = None
 
 
+class Consensus:
+    """Per reference position, the forward letters, deletions and inserted letters of the aligned calls of all the batches it is attached to (ffhip_consensus,
+    include/ffhip.h "consensus"): 37 planes of P uint32 -- A C G T del, then A C G T of each of 8 insertion columns -- and eight uint64 totals on the device, and the
+    consensus called from them there.  `min_identity` in per mille (0 .. 1000) is fixed here.  `ref` must outlive it, and it every batch it is attached to."""
+
+    def __init__(self, engine: Engine, ref: MapRef, min_identity: int = 0):
+        self.engine = engine
+        self.ref = ref
+        self.h = lib().ffhip_consensus_create(engine.h, ref.h, int(min_identity))
+        if not self.h:
+            raise FFHipError(lib().ffhip_last_error().decode())
+        self.positions = int(lib().ffhip_consensus_positions(self.h))
+
+    def download(self):
+        """(counts uint32 [37][P], totals dict of CONSENSUS_TOTALS) once every accumulation enqueued by any batch is done (ffhip_consensus_download)"""
+        counts = np.zeros((CONSENSUS_PLANES, self.positions), dtype=np.uint32)
+        tot = np.zeros(len(CONSENSUS_TOTALS), dtype=np.uint64)
+        _check(lib().ffhip_consensus_download(self.h, counts.ctypes.data_as(C.POINTER(C.c_uint32)), tot.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return counts, {k: int(v) for k, v in zip(CONSENSUS_TOTALS, tot)}
+
+    def call(self, min_depth: int = 3) -> np.ndarray:
+        """the consensus called on the device from the counters as they stand (ffhip_consensus_call): CONSENSUS_CELL [P], one 16-byte cell a position"""
+        cells = np.zeros(self.positions, dtype=CONSENSUS_CELL)
+        _check(lib().ffhip_consensus_call(self.h, int(min_depth), cells.ctypes.data_as(C.c_void_p)))
+        return cells
+
+    def reset(self):
+        _check(lib().ffhip_consensus_reset(self.h))
+
+    def close(self):
+        if self.h:
+            lib().ffhip_consensus_free(self.h)
+            self.h = None
+
+
 def _adapter_record(header, hits) -> dict:
     """a header and its hit slots as a dict: nhit, len, kept, hits = kept tuples (start, end, pattern, orientation, dist)"""
     kept = int(header.kept)
@@ -951,6 +1003,10 @@ class Batch:
         """the ModPileup that later runs with RUN_MAP | RUN_TRUTH | RUN_MOD_PROBS | RUN_MOD_PILEUP add to when they are finished (ffhip_batch_set_modpileup); None detaches"""
         _check(lib().ffhip_batch_set_modpileup(self.h, modpileup.h if modpileup is not None else None))
 
+    def set_consensus(self, consensus):
+        """the Consensus that later runs with RUN_MAP | RUN_TRUTH | RUN_CONSENSUS add to when they are finished (ffhip_batch_set_consensus); None detaches"""
+        _check(lib().ffhip_batch_set_consensus(self.h, consensus.h if consensus is not None else None))
+
     def truth(self, read: int) -> dict:
         """truth record of a run with RUN_TRUTH (ffhip_batch_truth): TRUTH_FIELDS as ints and ops (uint8 [dist + n_match] in path order, None unless status is 1)"""
         c = CTruthCall()
@@ -1152,6 +1208,13 @@ def op_pileup(engine: Engine, pileup: Pileup, q: int, tstart: int, tend: int, ca
     s = call if isinstance(call, bytes) else str(call).encode()
     o = np.ascontiguousarray(ops, dtype=np.uint8)
     _check(lib().ffhip_op_pileup(engine.h, pileup.h, int(q), int(tstart), int(tend), s, len(s), (o if o.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), o.size))
+
+
+def op_consensus(engine: Engine, consensus: Consensus, q: int, tstart: int, tend: int, call, ops):
+    """ffhip_op_consensus: ONE alignment -- search q, span [tstart, tend), the call's letters and its ops (0 .. 3) -- added into `consensus` by the kernel of the batches"""
+    s = call if isinstance(call, bytes) else str(call).encode()
+    o = np.ascontiguousarray(ops, dtype=np.uint8)
+    _check(lib().ffhip_op_consensus(engine.h, consensus.h, int(q), int(tstart), int(tend), s, len(s), (o if o.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), o.size))
 
 
 def op_modpileup(engine: Engine, modpileup: ModPileup, q: int, tstart: int, tend: int, call, ml, ops):

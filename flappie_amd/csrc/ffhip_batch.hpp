@@ -188,6 +188,7 @@ struct ffhip_batch {
     // Pileup (FFHIP_RUN_PILEUP, k_pileup): the engine-level object the batch's finished runs add to; nothing of it is the batch's
     ffhip_pileup *pile = nullptr;
     ffhip_modpileup *modpile = nullptr;                      // (FFHIP_RUN_MOD_PILEUP, k_modpileup: likewise)
+    ffhip_consensus *cons = nullptr;                         // (FFHIP_RUN_CONSENSUS, k_consensus: likewise)
     enum { AN_COUNT = 9 };
     Annot &annot(int i) { Annot *const a[AN_COUNT] = { &bc, &ad, &map, &pt, &tru, &rmp, &evt, &smd, &var }; return *a[i]; }       // (the order of kAnnots: launch order)
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale

@@ -1,4 +1,4 @@
-// ffhip_features.hip -- host side of the per-read features (barcodes, adapters, map, poly tail, remap, events, site mods, variants, truth, truth from map, pileup, mod pileup):
+// ffhip_features.hip -- host side of the per-read features (barcodes, adapters, map, poly tail, remap, events, site mods, variants, truth, truth from map, pileup, mod pileup, consensus):
 // each feature's share of a batch's run (ffhip_annot.hpp), its device objects, setters and accessors (include/ffhip.h), and its single-read operator ffhip_op_*.
 // No kernel lives here (theirs are ffhip_barcodes.hip ... ffhip_variants.hip) and none is launched from here but through their launch_* functions, so the Makefile
 // compiles this file as C++.  ffhip_engine.hip reaches it through ffhip_annot.hpp only.
@@ -464,6 +464,24 @@ void ffhip::modpileup_launch(ffhip_batch *b) {
                      b->tru.rec.dev + truth_ops_at(b), b->bases(), b->res.on_dev<uint8_t>(RF_ML), b->Tb, rmap, p->view);
     pileup_mark(p, b);
 }
+// Consensus (include/ffhip.h "consensus"): the pileup's second twin, which keeps the inserted letters, with the same two shares
+int ffhip::consensus_check(const ffhip_batch *b, unsigned flags) {
+    if (!(flags & FFHIP_RUN_CONSENSUS)) return FFHIP_OK;
+    static const char goes[] = "(FFHIP_RUN_CONSENSUS goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH)";
+    if (!(flags & FFHIP_RUN_TRUTH)) return set_err(FFHIP_EINVAL, "consensus: the run does not make the truth records %s", goes);
+    if (!(flags & FFHIP_RUN_MAP)) return set_err(FFHIP_EINVAL, "consensus: the run does not make the map records %s", goes);
+    if (!b->tru.from_map) return set_err(FFHIP_EINVAL, "consensus: the batch is not in the mode of truth from map (ffhip_batch_set_truth_from_map)");
+    if (!b->cons) return set_err(FFHIP_EINVAL, "consensus: no consensus is attached to the batch (ffhip_batch_set_consensus)");
+    if (b->cons->ref != b->map.ref) return set_err(FFHIP_EINVAL, "consensus: the attached consensus belongs to another reference than the batch's map reference");
+    return FFHIP_OK;
+}
+void ffhip::consensus_launch(ffhip_batch *b) {
+    ffhip_consensus *c = b->cons;
+    const ReadMap rmap = b->packed ? ReadMap{ b->d_vb0, b->d_vb1, b->nread } : ReadMap();
+    launch_consensus(b->stream, c->ref->view, (const TruthRead *)b->tru.list.dev, batch_nreads(b), b->map.rec.dev, (const int *)b->tru.rec.dev,
+                     b->tru.rec.dev + truth_ops_at(b), b->bases(), b->Tb, rmap, c->view);
+    pileup_mark(c, b);
+}
 // the copies of a finished run beside the block's: one a feature the run made, if it has a byte to bring
 int ffhip::annots_copy_down(ffhip_batch *b) {
     for (int i = 0; i < ffhip_batch::AN_COUNT; i++)
@@ -916,6 +934,77 @@ extern "C" int ffhip_batch_set_modpileup(ffhip_batch *b, ffhip_modpileup *p) {
     b->modpile = p;
     return FFHIP_OK;
 }
+// ---- consensus (include/ffhip.h "consensus"; the kernels: ffhip_consensus.hip)
+static int consensus_zero(ffhip_consensus *c) { return pileup_zero(c, kConsensusPlanes, kConsensusTotals); }
+extern "C" ffhip_consensus *ffhip_consensus_create(ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity) {
+    if (!eng || !ref || ref->eng != eng) { set_err(FFHIP_EINVAL, "consensus: a reference of this engine"); return nullptr; }
+    if (min_identity > 1000) { set_err(FFHIP_EINVAL, "consensus: min_identity is %d per mille (0 .. 1000)", min_identity); return nullptr; }
+    hipSetDevice(eng->device);
+    ffhip_consensus *c = new ffhip_consensus();
+    c->eng = eng; c->ref = ref;
+    size_t P = 0;
+    for (int m : ref->rec_len) P += (size_t)m;
+    c->view.P = P; c->view.min_identity = min_identity < 0 ? 0 : min_identity;
+    const size_t bytes = (size_t)kConsensusPlanes * P * 4;
+    if (dev_fill("consensus", { { (void **)&c->view.counts, nullptr, bytes }, { (void **)&c->view.totals, nullptr, (size_t)kConsensusTotals * 8 } })) {
+        set_err(FFHIP_ENOMEM, "consensus: the counters take %zu bytes of device memory, which could not be had", bytes + (size_t)kConsensusTotals * 8);
+        delete c;
+        return nullptr;
+    }
+    if (consensus_zero(c) != FFHIP_OK) { ffhip_consensus_free(c); return nullptr; }
+    return c;
+}
+extern "C" void ffhip_consensus_free(ffhip_consensus *c) {
+    if (!c) return;
+    pileup_wait(c);
+    dev_free({ (void **)&c->view.counts, (void **)&c->view.totals });
+    delete c;
+}
+extern "C" int ffhip_consensus_reset(ffhip_consensus *c) {
+    if (!c) return set_err(FFHIP_EINVAL, "null consensus");
+    if (int rc = pileup_wait(c)) return rc;
+    return consensus_zero(c);
+}
+extern "C" size_t ffhip_consensus_positions(const ffhip_consensus *c) { return c ? c->view.P : 0; }
+extern "C" int ffhip_consensus_download(ffhip_consensus *c, uint32_t *counts, ffhip_consensus_totals *totals) {
+    if (!c) return set_err(FFHIP_EINVAL, "null consensus");
+    static_assert(sizeof(ffhip_consensus_totals) == kConsensusTotals * 8 && FFHIP_CONSENSUS_PLANES == kConsensusPlanes && FFHIP_CONSENSUS_MINOR == kConsensusMinor,
+                  "the totals come down as they stand");
+    if (int rc = pileup_wait(c)) return rc;
+    if (counts) HIP_TRY(hipMemcpy(counts, c->view.counts, (size_t)kConsensusPlanes * c->view.P * 4, hipMemcpyDeviceToHost), FFHIP_EHIP);
+    if (totals) HIP_TRY(hipMemcpy(totals, c->view.totals, sizeof *totals, hipMemcpyDeviceToHost), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+// the call: one launch over the planes as they stand, the cells through a buffer that lives for the call
+extern "C" int ffhip_consensus_call(ffhip_consensus *c, int min_depth, ffhip_consensus_cell *cells) {
+    if (!c || !cells) return set_err(FFHIP_EINVAL, "null consensus or cells");
+    static_assert(sizeof(ffhip_consensus_cell) == 16, "a cell is one 16-byte store of k_consensus_call");
+    static_assert(FFHIP_CONSENSUS_LOW == kConsensusLow && FFHIP_CONSENSUS_SAME == kConsensusSame && FFHIP_CONSENSUS_SUB == kConsensusSub &&
+                  FFHIP_CONSENSUS_DEL == kConsensusDel && FFHIP_CONSENSUS_INS == kConsensusIns, "the kernel's codes are the header's");
+    if (min_depth < 1) return set_err(FFHIP_EINVAL, "consensus: min_depth is %d (1 or more: a position nobody covers has no winner)", min_depth);
+    if (int rc = pileup_wait(c)) return rc;
+    const size_t bytes = c->view.P * sizeof *cells;
+    void *d_cells = nullptr;
+    if (dev_fill("consensus cells", { { &d_cells, nullptr, bytes } })) return set_err(FFHIP_ENOMEM, "consensus: the cells take %zu bytes of device memory, which could not be had", bytes);
+    hipStream_t s = c->eng->streams[0];
+    launch_consensus_call(s, c->ref->view, c->view, (unsigned)min_depth, d_cells);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(cells, d_cells, bytes, hipMemcpyDeviceToHost, s);
+    const hipError_t e2 = hipStreamSynchronize(s);
+    dev_free({ &d_cells });
+    HIP_TRY(e, FFHIP_EHIP);
+    HIP_TRY(e2, FFHIP_EHIP);
+    return FFHIP_OK;
+}
+extern "C" int ffhip_batch_set_consensus(ffhip_batch *b, ffhip_consensus *c) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "consensus: the batch is between a run and its finish");
+    if (!c) { b->cons = nullptr; return FFHIP_OK; }
+    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "consensus: a flip-flop model only (the run-length model's call is a list of runs)");
+    if (c->eng != b->eng) return set_err(FFHIP_EINVAL, "consensus: the consensus belongs to another engine");
+    b->cons = c;
+    return FFHIP_OK;
+}
 extern "C" long long ffhip_debug_map_truth_bound(int nblock, int max_error) {
     return (nblock < 0 || max_error < 0 || max_error > 500) ? -1 : map_truth_bound(nblock, max_error);
 }
@@ -1070,6 +1159,14 @@ extern "C" int ffhip_op_pileup(ffhip_engine *eng, ffhip_pileup *p, int q, int ts
     PileOp d;
     if (int rc = pile_op("pileup", tmp, s, p->ref, q, tstart, tend, call, n, ops, nops, &d)) return rc;
     launch_pileup(s, p->ref->view, d.list, 1, d.mrec, d.trec, d.ops, d.call, n > 0 ? (int)n : 1, ReadMap(), p->view);
+    return op_done(s);
+}
+extern "C" int ffhip_op_consensus(ffhip_engine *eng, ffhip_consensus *c, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops) {
+    OP_ENTER(eng);
+    if (!c || c->eng != eng || (n && !call) || !ops) return set_err(FFHIP_EINVAL, "bad consensus arguments (a consensus of this engine, a call of n letters, nops ops)");
+    PileOp d;
+    if (int rc = pile_op("consensus", tmp, s, c->ref, q, tstart, tend, call, n, ops, nops, &d)) return rc;
+    launch_consensus(s, c->ref->view, d.list, 1, d.mrec, d.trec, d.ops, d.call, n > 0 ? (int)n : 1, ReadMap(), c->view);
     return op_done(s);
 }
 extern "C" int ffhip_op_modpileup(ffhip_engine *eng, ffhip_modpileup *p, int q, int tstart, int tend, const char *call, const uint8_t *ml, size_t n, const uint8_t *ops, size_t nops) {

@@ -89,6 +89,13 @@ struct ffhip_modpileup {
     ffhip::ModPileupView view{};
     bool used[4] = { false, false, false, false };
 };
+// a consensus on the device (ffhip_consensus_create; the kernels' view of it is ConsensusView): 37 planes of P uint32 and eight uint64 totals; `used` as the pileup's
+struct ffhip_consensus {
+    ffhip_engine *eng = nullptr;
+    const ffhip_map_ref *ref = nullptr;
+    ffhip::ConsensusView view{};
+    bool used[4] = { false, false, false, false };
+};
 
 // a function or table one file of the library defines for another and the library does not export
 #define FFHIP_LOCAL __attribute__((visibility("hidden")))

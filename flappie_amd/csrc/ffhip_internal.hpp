@@ -308,6 +308,16 @@ struct ModPileupView { unsigned *counts; unsigned long long *totals, *hist; size
 constexpr int kModPileupColumns = 5, kModPileupPlanes = 2 * kModPileupColumns, kModPileupTotals = 8, kModPileupBins = 256;
 void launch_modpileup(hipStream_t s, const MapRefView &ref, const TruthRead *list, int count, const void *map_records, const int *truth_records, const uint8_t *ops,
                       const char *bases, const uint8_t *ml, int Tb, ReadMap map, const ModPileupView &pv);
+// consensus (k_consensus and k_consensus_call, ffhip_consensus.hip; include/ffhip.h "consensus"): the same entries, records, ops and letters as the pileup's: the read's
+// forward letters, deletions and inserted letters added into the 37 planes of P uint32 [plane][position] -- A C G T del, then A C G T of each of the 8 minor columns
+// behind the position -- and the eight uint64 totals { reads, skipped, bases, del, ins_bases, long_ins, edge_ins, reserved }.  One launch, a workgroup an entry,
+// atomics only.  launch_consensus_call: a 16-byte ffhip_consensus_cell a position into `cells` (device memory), the reference's letters from ref.words.
+struct ConsensusView { unsigned *counts; unsigned long long *totals; size_t P; int min_identity; };
+constexpr int kConsensusMinor = 8, kConsensusPlanes = 5 + 4 * kConsensusMinor, kConsensusTotals = 8;
+enum { kConsensusLow = 0, kConsensusSame = 1, kConsensusSub = 2, kConsensusDel = 3, kConsensusIns = 4 };      // a cell's `what` (FFHIP_CONSENSUS_LOW ...: ffhip_consensus_call holds them equal)
+void launch_consensus(hipStream_t s, const MapRefView &ref, const TruthRead *list, int count, const void *map_records, const int *truth_records, const uint8_t *ops,
+                      const char *bases, int Tb, ReadMap map, const ConsensusView &cv);
+void launch_consensus_call(hipStream_t s, const MapRefView &ref, const ConsensusView &cv, unsigned min_depth, void *cells);
 // the signal of every base of a mapped read (k_events, ffhip_events.hip; include/ffhip.h "events"): per listed read whose remap record at records[read] says
 // { status 1, end 0 }, L events of 16 bytes { int32 first, count; float mean, sd } at events[out ..], from the read's samples sig[sig .. sig + n) and its bytes at the
 // read's row of the (Tb + 1)-entry byte buffer `rm`; any other read writes nothing.  One form; the launch comes behind launch_remap on the same stream.

@@ -50,6 +50,7 @@
 #include "../../include/flappie_align.h"
 #include "../../include/flappie_pileup.h"
 #include "../../include/flappie_modpileup.h"
+#include "../../include/flappie_consensus.h"
 #include "../../include/networks.h"
 
 const char *argp_program_version = "flappie (MI355X/HIP) 0.1, interface of flappie 2.1.3";
@@ -149,8 +150,16 @@ static struct argp_option options[] = {
     {"map-mods-motif", 298, "CG|C", 0, "With --map-mods: the sites written: CG (default: a C followed by a G, and on the - strand a G behind a C) or C (every C, every G on the - strand)"},
     {"map-mods-combine-strands", 299, 0, 0, "With --map-mods and the motif CG: one row a CpG, the - strand's counts of its G added to the + strand's row of its C, strand '.'"},
     {"map-mods-hist", 300, "hist.tsv", 0, "With --map-mods: 256 lines of byte and count: how many counted C or Z calls on a site had each 5mC byte -- the distribution to choose --map-mods-hi and --map-mods-lo from"},
+    {"map-consensus", 301, "cons.fa", 0, "With --truth-from-map: the sample's sequence per record of the reference, from the aligned calls' bases, deletions and inserted letters, counted on the GPU over the whole run and called there at its end: one FASTA record per record of the reference, in reference order, in lines of 70. Per position the most frequent of A, C, G, T and deletion is written (a tie goes to the reference's letter, else to the first in that order), then up to 8 inserted letters behind it, each while more than half of the position's depth has one. A position below --map-consensus-min-depth writes the reference's letter in lower case. Letters of an insertion beyond the eighth are counted on stderr only (long_ins), as are insertions before the first or behind the last aligned base (edge_ins). No polishing round, no qualities. The whole call counts: --reverse, the trims and --split-reads do not alter it. stdout, hits.tsv, acc.tsv, aln.sam, pileup.tsv and mods.bed do not change"},
+    {"map-consensus-changes", 302, "changes.tsv", 0, "With --map-consensus: where the consensus differs from the reference: one line for every position with a substitution, a deletion or inserted letters, no header: record, 0-based position, reference letter, the letters written there (- if none), depth, the winner's count, the first inserted letter's count (0 if none)"},
+    {"map-consensus-min-depth", 303, "N", 0, "With --map-consensus: a position covered by fewer aligned calls than this keeps the reference's letter, in lower case (1-65535, default 3). The default comes from reasoning, not from reads"},
+    {"map-consensus-min-identity", 304, "permille", 0, "With --map-consensus: count only reads whose alignment's identity is at least this many thousandths (0-1000, default 0), as --map-pileup-min-identity"},
 #endif
 #ifdef BUILD_RUNNIE
+    {"map-consensus", 301, "cons.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-consensus-changes", 302, "changes.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-consensus-min-depth", 303, "N", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"map-consensus-min-identity", 304, "permille", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-pileup", 292, "pileup.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-pileup-min-identity", 293, "permille", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-mods", 294, "mods.bed", OPTION_HIDDEN, "(flappie's option: refused here)"},
@@ -263,6 +272,9 @@ static int pu_min_identity = -1;
 static char *mm_path = NULL, *mm_hist_path = NULL, *mm_motif = NULL;
 static int mm_hi = -1, mm_lo = -1, mm_min_identity = -1;
 static bool mm_combine = false;
+/* flappie: the files of --map-consensus and --map-consensus-changes, --map-consensus-min-depth and -min-identity (-1: not given) (runnie: seen, to be refused) */
+static char *cs_path = NULL, *cs_changes_path = NULL;
+static int cs_min_depth = -1, cs_min_identity = -1;
 static int map_window = -1;
 #ifndef BUILD_RUNNIE
 static int map_max_error = -1;
@@ -454,6 +466,16 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
         break;
     case 299: mm_combine = true; break;
     case 300: mm_hist_path = arg; break;
+    case 301: cs_path = arg; break;
+    case 302: cs_changes_path = arg; break;
+    case 303: case 304: {
+        char *end = NULL;
+        const long v = strtol(arg, &end, 10), low = key == 303 ? 1 : 0, top = key == 303 ? 65535 : 1000;
+        if (end == arg || *end != '\0' || v < low || v > top)
+            errx(EXIT_FAILURE, "--map-consensus-%s must be a whole number from %ld to %ld", key == 303 ? "min-depth" : "min-identity", low, top);
+        *(key == 303 ? &cs_min_depth : &cs_min_identity) = (int)v;
+        break;
+    }
 #ifdef BUILD_RUNNIE
     case 287: case 288: map_opts = true; break;
     case 270: case 271: case 272: case 273: case 274: ad_opts = true; break;
@@ -830,12 +852,15 @@ static FILE *pu_out = NULL;
 /* flappie --map-mods: likewise the one mod pileup of the run; its table and the histogram's file */
 static ffhip_modpileup *mm_dev = NULL;
 static FILE *mm_out = NULL, *mm_hist = NULL;
+/* flappie --map-consensus: likewise the one consensus of the run; its FASTA file and the table of changes */
+static ffhip_consensus *cs_dev = NULL;
+static FILE *cs_out = NULL, *cs_changes = NULL;
 /* --modbase-tags: the 5mC bytes of the called bases come from the device (FFHIP_RUN_MOD_PROBS); --emit-moves: the move table does (FFHIP_RUN_MOVES);
  * --barcodes: the reads' barcode records do (FFHIP_RUN_BARCODES); --adapters: their adapter records (FFHIP_RUN_ADAPTERS); --poly-tail: their poly tail
  * records (FFHIP_RUN_POLYTAIL) */
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | ((args.modbase_tags || mm_dev) ? FFHIP_RUN_MOD_PROBS : 0u) | (mm_dev ? FFHIP_RUN_MOD_PILEUP : 0u) |
-           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (mp_dev ? FFHIP_RUN_MAP : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | ((tr_refs || tfm_on) ? FFHIP_RUN_TRUTH : 0u) | (pu_dev ? FFHIP_RUN_PILEUP : 0u) |
+           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (mp_dev ? FFHIP_RUN_MAP : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | ((tr_refs || tfm_on) ? FFHIP_RUN_TRUTH : 0u) | (pu_dev ? FFHIP_RUN_PILEUP : 0u) | (cs_dev ? FFHIP_RUN_CONSENSUS : 0u) |
            (ev_out ? FFHIP_RUN_EVENTS : 0u) | (md_out ? FFHIP_RUN_REMAP_MODS : 0u) | (vr_out ? FFHIP_RUN_REMAP_VARIANTS : 0u);
 }
 /* --remap: every read's record, by its read id, then by its file's base name; a bad record goes as a sequence of no bases (status 2) */
@@ -904,6 +929,7 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
     if (tfm_on) { const int rc = ffhip_batch_set_truth_from_map(b, 1, args.truth_band); if (rc) return rc; }
     if (pu_dev) { const int rc = ffhip_batch_set_pileup(b, pu_dev); if (rc) return rc; }
     if (mm_dev) { const int rc = ffhip_batch_set_modpileup(b, mm_dev); if (rc) return rc; }
+    if (cs_dev) { const int rc = ffhip_batch_set_consensus(b, cs_dev); if (rc) return rc; }
     return ffhip_batch_run(b, args.temperature, flags);
 }
 #endif
@@ -2242,6 +2268,8 @@ int main(int argc, char *argv[]) {
     if (pu_path || pu_min_identity >= 0) errx(EXIT_FAILURE, "--map-pileup and --map-pileup-min-identity are flappie's: the run-length model's call is a list of runs");
     if (mm_path || mm_hi >= 0 || mm_lo >= 0 || mm_min_identity >= 0 || mm_motif || mm_combine || mm_hist_path)
         errx(EXIT_FAILURE, "--map-mods and its --map-mods-* options are flappie's: the run-length model's call is a list of runs and it has no modified base");
+    if (cs_path || cs_changes_path || cs_min_depth >= 0 || cs_min_identity >= 0)
+        errx(EXIT_FAILURE, "--map-consensus and its --map-consensus-* options are flappie's: the run-length model's call is a list of runs");
     if (args.remap_events) errx(EXIT_FAILURE, "--remap-events is flappie's: it goes with --remap, which the run-length model does not have");
     if (mods_path) errx(EXIT_FAILURE, "--remap-mods is flappie's: it goes with --remap, which the run-length model does not have");
     if (vars_path || vars_out_path || vars_opts) errx(EXIT_FAILURE, "--remap-variants is flappie's: it goes with --remap, which the run-length model does not have");
@@ -2298,6 +2326,11 @@ int main(int argc, char *argv[]) {
         if (mm_lo >= mm_hi) errx(EXIT_FAILURE, "--map-mods-lo (%d) must be below --map-mods-hi (%d)", mm_lo, mm_hi);
         if (mm_combine && mm_motif && 0 != strcmp(mm_motif, "CG")) errx(EXIT_FAILURE, "--map-mods-combine-strands goes with the motif CG: a lone C has no partner on the other strand");
     }
+    /* --map-consensus: likewise; a depth of 3 is the least at which two agreeing calls outvote a third */
+    if ((cs_changes_path || cs_min_depth >= 0 || cs_min_identity >= 0) && NULL == cs_path)
+        errx(EXIT_FAILURE, "--map-consensus-changes, --map-consensus-min-depth and --map-consensus-min-identity go with --map-consensus");
+    if (cs_path && !tfm_on) errx(EXIT_FAILURE, "--map-consensus goes with --truth-from-map: it counts what the alignments say");
+    if (cs_path && cs_min_depth < 0) cs_min_depth = 3;
     if (map_path) {
         char why[256];
         mp_ref = flappie_map_ref_read(map_path, why, sizeof why);
@@ -2347,6 +2380,8 @@ int main(int argc, char *argv[]) {
         if (pu_path && NULL == (pu_out = fopen(pu_path, "w"))) errx(EXIT_FAILURE, "--map-pileup %s: cannot be written", pu_path);
         if (mm_path && NULL == (mm_out = fopen(mm_path, "w"))) errx(EXIT_FAILURE, "--map-mods %s: cannot be written", mm_path);
         if (mm_hist_path && NULL == (mm_hist = fopen(mm_hist_path, "w"))) errx(EXIT_FAILURE, "--map-mods-hist %s: cannot be written", mm_hist_path);
+        if (cs_path && NULL == (cs_out = fopen(cs_path, "w"))) errx(EXIT_FAILURE, "--map-consensus %s: cannot be written", cs_path);
+        if (cs_changes_path && NULL == (cs_changes = fopen(cs_changes_path, "w"))) errx(EXIT_FAILURE, "--map-consensus-changes %s: cannot be written", cs_changes_path);
     }
     if (args.truth) {
         char why[256];
@@ -2404,6 +2439,10 @@ int main(int argc, char *argv[]) {
     if (mm_out && NULL == (mm_dev = ffhip_modpileup_create(eng, mp_dev, mm_min_identity, mm_lo, mm_hi))) {
         stop_reader_procs();
         errx(EXIT_FAILURE, "--map-mods: %s", ffhip_last_error());
+    }
+    if (cs_out && NULL == (cs_dev = ffhip_consensus_create(eng, mp_dev, cs_min_identity))) {
+        stop_reader_procs();
+        errx(EXIT_FAILURE, "--map-consensus: %s", ffhip_last_error());
     }
 #endif
     hid_t hdf5out = open_or_create_hdf5(args.trace);
@@ -2510,6 +2549,25 @@ int main(int argc, char *argv[]) {
         if (0 != fclose(mm_out)) warnx("--map-mods %s: write failed", mm_path);
         if (mm_hist && 0 != fclose(mm_hist)) warnx("--map-mods-hist %s: write failed", mm_hist_path);
         ffhip_modpileup_free(mm_dev);
+    }
+    if (cs_dev) {                      /* the consensus, called once: every batch object is gone, so every accumulation is done; the planes come down for the changes only */
+        const size_t P = ffhip_consensus_positions(cs_dev);
+        ffhip_consensus_cell *cells = malloc((P ? P : 1) * sizeof *cells);
+        uint32_t *counts = cs_changes ? malloc((P ? P : 1) * FFHIP_CONSENSUS_PLANES * sizeof *counts) : NULL;
+        ffhip_consensus_totals tot;
+        flappie_consensus_stats st;
+        if (NULL == cells || (cs_changes && NULL == counts)) warnx("--map-consensus: out of memory for the cells");
+        else if (0 != ffhip_consensus_call(cs_dev, cs_min_depth, cells) || 0 != ffhip_consensus_download(cs_dev, counts, &tot)) warnx("--map-consensus: %s", ffhip_last_error());
+        else {
+            flappie_consensus_write(cs_out, mp_ref, cells, &st);
+            if (cs_changes) flappie_consensus_changes_write(cs_changes, mp_ref, cells, counts);
+            flappie_consensus_summary_print(stderr, &tot, &st);
+        }
+        free(counts);
+        free(cells);
+        if (0 != fclose(cs_out)) warnx("--map-consensus %s: write failed", cs_path);
+        if (cs_changes && 0 != fclose(cs_changes)) warnx("--map-consensus-changes %s: write failed", cs_changes_path);
+        ffhip_consensus_free(cs_dev);
     }
     if (mp_ref) {                      /* reads, mapped, unmapped, discordant; the mapped reads' anchor distances over their anchor bases */
         flappie_map_summary_print(stderr, &mp_sum);

@@ -160,6 +160,13 @@ typedef struct {
  * FFHIP_RUN_MOD_PROBS, outside the mode, with no mod pileup attached or with one of another reference than the batch's: FFHIP_EINVAL with a text that says which.
  * FFHIP_RUN_PILEUP is neither required nor excluded. */
 #define FFHIP_RUN_MOD_PILEUP (1u << 24)   /* 16777216: the bit behind FFHIP_RUN_PILEUP */
+/* With FFHIP_RUN_MAP | FFHIP_RUN_TRUTH in the mode of ffhip_batch_set_truth_from_map: every aligned read's forward letters, deletions and INSERTED letters added, per
+ * reference position, into the consensus attached with ffhip_batch_set_consensus ("consensus" below) -- on the device (k_consensus), as the last step of
+ * ffhip_batch_finish, from the records and letters the caller reads.  Nothing comes down per read and the batch holds nothing new (ffhip_debug_batch_device_bytes
+ * does not change); everything the run returns is that of the same run without the flag.  Without FFHIP_RUN_TRUTH, without FFHIP_RUN_MAP, outside the mode, with no
+ * consensus attached or with one of another reference than the batch's: FFHIP_EINVAL with a text that says which.  FFHIP_RUN_PILEUP and FFHIP_RUN_MOD_PILEUP are
+ * neither required nor excluded. */
+#define FFHIP_RUN_CONSENSUS  (1u << 25)   /* 33554432: the bit behind FFHIP_RUN_MOD_PILEUP */
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -855,6 +862,54 @@ size_t ffhip_modpileup_positions(const ffhip_modpileup *p);
 int ffhip_modpileup_download(ffhip_modpileup *p, uint32_t *counts /* [10][P] */, ffhip_modpileup_totals *totals, uint64_t *hist /* [256] */);
 int ffhip_batch_set_modpileup(ffhip_batch *b, ffhip_modpileup *p);
 int ffhip_op_modpileup(ffhip_engine *eng, ffhip_modpileup *p, int q, int tstart, int tend, const char *call, const uint8_t *ml, size_t n, const uint8_t *ops, size_t nops);
+/* Consensus: per reference position, the letters the aligned calls put there -- bases, deletions and what they INSERT behind it -- added up over all the reads of
+ * all the batches it is attached to, and a consensus called from the sums (tests/consensus_ref.py restates this).  The pileup's second twin: integer adds only, the
+ * same bytes whatever the batch size, packing, pairing or read order.  Strands are merged: everything is stored as forward-strand letters.
+ *   A consensus belongs to one ffhip_map_ref of K records of M_k bases; off_k and P as the pileup's.
+ *   Counters: FFHIP_CONSENSUS_PLANES = 37 planes of P uint32, [plane][position].  Planes 0 .. 4: A, C, G, T and del at the position.  Plane 5 + 4 d + base, d = 0 ..
+ *     FFHIP_CONSENSUS_MINOR - 1: inserted base `base` at forward offset d in the gap behind the position (the pileup's placement: the gap belongs to the position
+ *     to its left on the forward strand).  Eight uint64 totals: reads, skipped, bases, del, ins_bases, long_ins, edge_ins, reserved.
+ *   Fixed at creation: min_identity in per mille by the pileup's rule (negative: 0; above 1000: refused).
+ *   Which reads count: the pileup's rule -- map status 1, truth status 1 and 1000 n_match >= min_identity (n_match + n_mismatch + n_ins + n_del) in 64-bit integers.
+ *     A read with both statuses 1 that fails the test adds 1 to `skipped` and nothing else; any other read adds nothing.
+ *   What a counted read adds: q = 2 k + o and the span [tstart, tend) of its map record, m = tend - tstart; its call s of n letters (code: A 0, C and Z 1, G 2, T 3);
+ *     the ops of its truth record.  reads += 1; then the ops in signal order from (j, i) = (0, 0):
+ *       '=' (0) or 'X' (1): f = o ? M_k - 1 - (tstart + j) : tstart + j, base = o ? 3 - code(s_i) : code(s_i).  plane[base][off_k + f] += 1, bases += 1.  j++, i++.
+ *       'D' (3): f as above.  plane[4][off_k + f] += 1, del += 1.  j++.
+ *       a maximal run of l consecutive 'I' (2) at j: if j < 1 or j > m - 1 every letter of the run adds 1 to edge_ins and nothing else.  Otherwise the gap is
+ *         p = o ? M_k - 1 - tstart - j : tstart + j - 1; the run's r-th letter in signal order is s_(i + r), its forward offset d = o ? l - 1 - r : r, its base as
+ *         above.  d < 8: plane[5 + 4 d + base][off_k + p] += 1, ins_bases += 1; else long_ins += 1.  i += l.
+ *     A letter's contribution depends on its op, j, i and at most 8 neighbouring ops alone, so the kernel takes an op a thread with j and i from prefix counts.
+ *   Counters wrap at 2^32 (the totals at 2^64); there is no guard.
+ *   When: the last step of a successful ffhip_batch_finish of a run with FFHIP_RUN_CONSENSUS, where the pileup's stands: behind the f32 re-runs' patches and in the
+ *     innermost finish of the time-out fallback.  A side batch never counts.  Its order against k_pileup and k_modpileup is free.
+ *   The call (ffhip_consensus_call, k_consensus_call): one 16-byte cell a position.  depth = the sum of planes 0 .. 4 in 64 bits (saturated to 2^32 - 1 in the cell).
+ *     depth < min_depth: n = 1, s[0] the reference's letter in LOWER case, what = FFHIP_CONSENSUS_LOW, and no insertion is looked at.  Otherwise the winner is the
+ *     largest of the five counts; a tie goes to the reference's letter if it is among the tied, else to the first in the order A, C, G, T, del.  what =
+ *     FFHIP_CONSENSUS_SAME (the reference's letter), _SUB (another) or _DEL; a deletion writes no letter, the others the letter in upper case.  Then for d = 0, 1, ...
+ *     while d < 8: t_d = the sum of column d's four counts; stop unless 2 t_d > depth; append the letter of the column's largest count (a tie: the first in A, C, G,
+ *     T) and set the bit FFHIP_CONSENSUS_INS in `what`.  n = the letters written (0 .. 9); the bytes of s behind them are 0.  The consensus of a record is its cells'
+ *     letters concatenated.
+ * ffhip_consensus_create: zeroed counters; a bad min_identity: NULL with a text.  The reference must outlive it, and it every batch it is attached to.
+ * ffhip_consensus_free / _reset / _download / ffhip_consensus_call wait for every accumulation enqueued against it; each output of download may be NULL.
+ *   _positions: P.  ffhip_consensus_call: min_depth < 1 or cells NULL: FFHIP_EINVAL with a text.  It changes no counter and may be made again.
+ * ffhip_batch_set_consensus: the consensus of the batch's later runs with the flag; NULL detaches.  One of another engine, the run-length model, or a call between
+ *   a run and its finish: FFHIP_EINVAL.
+ * ffhip_op_consensus: the kernel on ONE alignment from host arguments, added into c: ffhip_op_pileup's refusals; nothing is added by any.  The identity test applies. */
+typedef struct ffhip_consensus ffhip_consensus;
+typedef struct { uint64_t reads, skipped, bases, del, ins_bases, long_ins, edge_ins, reserved; } ffhip_consensus_totals;      /* 64 bytes */
+typedef struct { uint8_t n, what; char s[10]; uint32_t depth; } ffhip_consensus_cell;      /* 16 bytes */
+#define FFHIP_CONSENSUS_PLANES 37
+#define FFHIP_CONSENSUS_MINOR 8
+enum { FFHIP_CONSENSUS_LOW = 0, FFHIP_CONSENSUS_SAME = 1, FFHIP_CONSENSUS_SUB = 2, FFHIP_CONSENSUS_DEL = 3, FFHIP_CONSENSUS_INS = 4 /* a bit beside the others */ };
+ffhip_consensus *ffhip_consensus_create(ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity);
+void ffhip_consensus_free(ffhip_consensus *c);
+int ffhip_consensus_reset(ffhip_consensus *c);
+size_t ffhip_consensus_positions(const ffhip_consensus *c);
+int ffhip_consensus_download(ffhip_consensus *c, uint32_t *counts /* [37][P] */, ffhip_consensus_totals *totals);
+int ffhip_consensus_call(ffhip_consensus *c, int min_depth, ffhip_consensus_cell *cells /* [P] */);
+int ffhip_batch_set_consensus(ffhip_batch *b, ffhip_consensus *c);
+int ffhip_op_consensus(ffhip_engine *eng, ffhip_consensus *c, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops);
 int ffhip_runlength_viterbi(ffhip_engine *eng, ffhip_mat param, int *path /* nblock */, float *score);
 /* decoders of the first-generation head on [4 nbase x nblock] matrices: decode_runlength (decode.c:694-767), posterior_runlength
  * (decode.c:793-892; post is [4 nbase x nblock + 1]), runlengths_mean (decode.c:576-603) */
