@@ -46,6 +46,12 @@ CONSENSUS_PLANES = 37    # FFHIP_CONSENSUS_PLANES: A C G T del, then A C G T of 
 CONSENSUS_MINOR = 8
 CONSENSUS_LOW, CONSENSUS_SAME, CONSENSUS_SUB, CONSENSUS_DEL, CONSENSUS_INS = 0, 1, 2, 3, 4      # a cell's `what`: one of the first four, CONSENSUS_INS a bit beside it
 CONSENSUS_CELL = np.dtype([("n", "u1"), ("what", "u1"), ("s", "S10"), ("depth", "<u4")])       # ffhip_consensus_cell, 16 bytes
+RUN_ERRPROFILE = 67108864  # with RUN_TRUTH in either truth mode (truth from map: RUN_MAP too): every aligned read's ops classed into the ErrProfile of Batch.set_errprofile
+ERRPROFILE_TOTALS = ("reads", "skipped", "match", "mismatch", "del", "ins", "edge_ins", "ctx_sites", "hp_runs", "hp_long", "hp_wide", "reserved")      # ffhip_errprofile_totals, twelve uint64
+ERRPROFILE_SECTIONS = (("sub", 0, (4, 5)), ("ins", 20, (4,)), ("qual", 24, (94, 3)), ("ctx", 306, (1024, 4)), ("hp", 4402, (4, 16, 33)))      # name, FFHIP_ERRPROFILE_<NAME>, shape
+ERRPROFILE_TABLE_WORDS = 6514   # FFHIP_ERRPROFILE_TABLE_WORDS: the sections together; the totals stand behind them
+ERRPROFILE_WORDS = 6526         # FFHIP_ERRPROFILE_WORDS, ffhip_errprofile_words()
+ERRPROFILE_HP_MAX_RUN, ERRPROFILE_HP_MAX_CALLED, ERRPROFILE_HP_MAX_OPS = 16, 32, 64
 MAP_SEGMENT = 2048       # FFHIP_MAP_SEGMENT (include/ffhip.h "map"): the columns one task of k_map_scan owns; checked against the library at load
 MAP_MAX_TOTAL = 1 << 20
 MAP_MAX_ANCHOR = 4096
@@ -370,6 +376,19 @@ def lib():
     L.ffhip_consensus_call.argtypes = [vp, C.c_int, vp]
     L.ffhip_batch_set_consensus.argtypes = [vp, vp]
     L.ffhip_op_consensus.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t]
+    L.ffhip_errprofile_create.restype = vp
+    L.ffhip_errprofile_create.argtypes = [vp, C.c_int]
+    L.ffhip_errprofile_free.restype = None
+    L.ffhip_errprofile_free.argtypes = [vp]
+    L.ffhip_errprofile_reset.argtypes = [vp]
+    L.ffhip_errprofile_words.restype = C.c_size_t
+    L.ffhip_errprofile_words.argtypes = []
+    L.ffhip_errprofile_download.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.ffhip_batch_set_errprofile.argtypes = [vp, vp]
+    L.ffhip_op_errprofile.argtypes = [vp, vp, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t]
+    L.ffhip_op_errprofile_mapped.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t]
+    L.ffhip_debug_errprofile_groups.argtypes = [vp, C.c_int]
+    L.ffhip_debug_batch_clear_stretches.argtypes = [vp]
     L.ffhip_debug_map_truth_bound.restype = C.c_longlong
     L.ffhip_debug_map_truth_bound.argtypes = [C.c_int, C.c_int]
     _LIB = L
@@ -716,6 +735,42 @@ class Consensus:
             self.h = None
 
 
+class ErrProfile:
+    """By class, what the aligned calls of all the batches it is attached to got right and wrong (ffhip_errprofile, include/ffhip.h "error profile"): the tables
+    sub[4][5], ins[4], qual[94][3], ctx[1024][4], hp[4][16][33] and twelve totals, all uint64 on the device.  `min_identity` in per mille (0 .. 1000) is fixed here.
+    It belongs to no reference, serves either truth mode, and must outlive every batch it is attached to."""
+
+    def __init__(self, engine: Engine, min_identity: int = 0):
+        self.engine = engine
+        self.h = lib().ffhip_errprofile_create(engine.h, int(min_identity))
+        if not self.h:
+            raise FFHipError(lib().ffhip_last_error().decode())
+
+    def download(self):
+        """(counts uint64 [ERRPROFILE_TABLE_WORDS], totals dict of ERRPROFILE_TOTALS) once every accumulation enqueued by any batch is done (ffhip_errprofile_download)"""
+        counts = np.zeros(ERRPROFILE_TABLE_WORDS, dtype=np.uint64)
+        tot = np.zeros(len(ERRPROFILE_TOTALS), dtype=np.uint64)
+        _check(lib().ffhip_errprofile_download(self.h, counts.ctypes.data_as(C.POINTER(C.c_uint64)), tot.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return counts, {k: int(v) for k, v in zip(ERRPROFILE_TOTALS, tot)}
+
+    @staticmethod
+    def sections(counts) -> dict:
+        """the flat counts as views by section: sub, ins, qual, ctx, hp (ERRPROFILE_SECTIONS)"""
+        return {name: counts[at:at + int(np.prod(shape))].reshape(shape) for name, at, shape in ERRPROFILE_SECTIONS}
+
+    def reset(self):
+        _check(lib().ffhip_errprofile_reset(self.h))
+
+    def debug_groups(self, groups: int):
+        """test hook (ffhip_debug_errprofile_groups): the most workgroups of the later launches; 0: the default"""
+        _check(lib().ffhip_debug_errprofile_groups(self.h, int(groups)))
+
+    def close(self):
+        if self.h:
+            lib().ffhip_errprofile_free(self.h)
+            self.h = None
+
+
 def _adapter_record(header, hits) -> dict:
     """a header and its hit slots as a dict: nhit, len, kept, hits = kept tuples (start, end, pattern, orientation, dist)"""
     kept = int(header.kept)
@@ -1007,6 +1062,14 @@ class Batch:
         """the Consensus that later runs with RUN_MAP | RUN_TRUTH | RUN_CONSENSUS add to when they are finished (ffhip_batch_set_consensus); None detaches"""
         _check(lib().ffhip_batch_set_consensus(self.h, consensus.h if consensus is not None else None))
 
+    def set_errprofile(self, errprofile):
+        """the ErrProfile that later runs with RUN_TRUTH | RUN_ERRPROFILE add to when they are finished (ffhip_batch_set_errprofile); None detaches"""
+        _check(lib().ffhip_batch_set_errprofile(self.h, errprofile.h if errprofile is not None else None))
+
+    def debug_clear_stretches(self):
+        """test hook (ffhip_debug_batch_clear_stretches): between a run in the mode of truth from map and its finish, zero the gathered stretches behind k_truth"""
+        _check(lib().ffhip_debug_batch_clear_stretches(self.h))
+
     def truth(self, read: int) -> dict:
         """truth record of a run with RUN_TRUTH (ffhip_batch_truth): TRUTH_FIELDS as ints and ops (uint8 [dist + n_match] in path order, None unless status is 1)"""
         c = CTruthCall()
@@ -1215,6 +1278,28 @@ def op_consensus(engine: Engine, consensus: Consensus, q: int, tstart: int, tend
     s = call if isinstance(call, bytes) else str(call).encode()
     o = np.ascontiguousarray(ops, dtype=np.uint8)
     _check(lib().ffhip_op_consensus(engine.h, consensus.h, int(q), int(tstart), int(tend), s, len(s), (o if o.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), o.size))
+
+
+def _errprofile_args(call, qual, ops):
+    s = call if isinstance(call, bytes) else str(call).encode()
+    qb = qual if isinstance(qual, bytes) else bytes(qual) if not isinstance(qual, str) else qual.encode("latin-1")
+    if len(qb) != len(s):
+        raise ValueError("a quality character a letter of the call")
+    o = np.ascontiguousarray(ops, dtype=np.uint8)
+    return s, qb, o, (o if o.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def op_errprofile(engine: Engine, errprofile: ErrProfile, call, qual, truth, ops):
+    """ffhip_op_errprofile: ONE alignment -- the call's letters, its quality characters (bytes), the truth's codes 0 .. 4 and its ops (0 .. 3) -- added into `errprofile`"""
+    s, qb, o, op = _errprofile_args(call, qual, ops)
+    t = np.ascontiguousarray(truth, dtype=np.uint8)
+    _check(lib().ffhip_op_errprofile(engine.h, errprofile.h, s, qb, len(s), (t if t.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), t.size, op, o.size))
+
+
+def op_errprofile_mapped(engine: Engine, errprofile: ErrProfile, ref: MapRef, q: int, tstart: int, tend: int, call, qual, ops):
+    """ffhip_op_errprofile_mapped: the same with the truth's letters from the span [tstart, tend) of search q of `ref`"""
+    s, qb, o, op = _errprofile_args(call, qual, ops)
+    _check(lib().ffhip_op_errprofile_mapped(engine.h, errprofile.h, ref.h, int(q), int(tstart), int(tend), s, qb, len(s), op, o.size))
 
 
 def op_modpileup(engine: Engine, modpileup: ModPileup, q: int, tstart: int, tend: int, call, ml, ops):

@@ -93,6 +93,8 @@ FFHIP_LOCAL int modpileup_check(const ffhip_batch *b, unsigned flags);
 FFHIP_LOCAL void modpileup_launch(ffhip_batch *b);
 FFHIP_LOCAL int consensus_check(const ffhip_batch *b, unsigned flags);
 FFHIP_LOCAL void consensus_launch(ffhip_batch *b);
+FFHIP_LOCAL int errprofile_check(const ffhip_batch *b, unsigned flags);
+FFHIP_LOCAL void errprofile_launch(ffhip_batch *b);
 FFHIP_LOCAL int remap_adopt(ffhip_batch *b, std::vector<std::vector<unsigned short>> &&seq, std::vector<signed char> &&state, int band);
 FFHIP_LOCAL int truth_adopt(ffhip_batch *b, std::vector<std::vector<uint8_t>> &&seq, std::vector<signed char> &&state, int band);
 

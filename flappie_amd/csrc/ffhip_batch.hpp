@@ -189,6 +189,7 @@ struct ffhip_batch {
     ffhip_pileup *pile = nullptr;
     ffhip_modpileup *modpile = nullptr;                      // (FFHIP_RUN_MOD_PILEUP, k_modpileup: likewise)
     ffhip_consensus *cons = nullptr;                         // (FFHIP_RUN_CONSENSUS, k_consensus: likewise)
+    ffhip_errprofile *errp = nullptr;                        // (FFHIP_RUN_ERRPROFILE, k_errprofile: likewise; it belongs to no reference)
     enum { AN_COUNT = 9 };
     Annot &annot(int i) { Annot *const a[AN_COUNT] = { &bc, &ad, &map, &pt, &tru, &rmp, &evt, &smd, &var }; return *a[i]; }       // (the order of kAnnots: launch order)
     RleRunScale run_scale{ { 1.02, 1.04, 1.04, 1.02 } };      // decode_runnie.py's default --scale

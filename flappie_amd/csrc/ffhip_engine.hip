@@ -1322,6 +1322,7 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
     if (int rc = pileup_check(b, flags)) return rc;        // (ahead of truth's own refusal of a run without the map: the text names the flag that asked)
     if (int rc = modpileup_check(b, flags)) return rc;     // (likewise)
     if (int rc = consensus_check(b, flags)) return rc;     // (likewise)
+    if (int rc = errprofile_check(b, flags)) return rc;    // (likewise)
     if (int rc = annots_prepare(b, flags)) return rc;      // the products outside the block (kAnnots): may this run ask; their lists, workspaces and room
     if (b->packed && !p.packable)
         return set_err(FFHIP_EINVAL, "packed batches take the default path and the launch-per-step kernels only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / unfused flags, ordinary temperature)");
@@ -1794,7 +1795,7 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
             for (int k = 0; k < n; k++) { sq[k] = b->tru.seq[reads[k0 + k]]; st[k] = b->tru.state[reads[k0 + k]]; }
             if (int rc = truth_adopt(sd, std::move(sq), std::move(st), b->tru.band)) return rc;
         }
-        if (int rc = ffhip_batch_run(sd, b->last_temperature, (fl & ~(unsigned)(FFHIP_RUN_KEEP_ACTS | FFHIP_RUN_PILEUP | FFHIP_RUN_MOD_PILEUP | FFHIP_RUN_CONSENSUS)) | FFHIP_RUN_F32_RNN)) return rc;      // (a side batch never counts: this batch does, below, from the patched records)
+        if (int rc = ffhip_batch_run(sd, b->last_temperature, (fl & ~(unsigned)(FFHIP_RUN_KEEP_ACTS | FFHIP_RUN_PILEUP | FFHIP_RUN_MOD_PILEUP | FFHIP_RUN_CONSENSUS | FFHIP_RUN_ERRPROFILE)) | FFHIP_RUN_F32_RNN)) return rc;      // (a side batch never counts: this batch does, below, from the patched records)
         if (int rc = ffhip_batch_finish(sd)) return rc;
         hipStream_t s = b->stream;
         for (int k = 0; k < n; k++) {
@@ -1886,6 +1887,7 @@ extern "C" int ffhip_batch_finish(ffhip_batch *b) {
         if ((b->last_flags & FFHIP_RUN_PILEUP) && b->pile && b->map.valid && b->tru.valid) pileup_launch(b);
         if ((b->last_flags & FFHIP_RUN_MOD_PILEUP) && b->modpile && b->map.valid && b->tru.valid && (b->res_made & res_bit(RS_MOD))) modpileup_launch(b);      // (the mod pileup: the same place)
         if ((b->last_flags & FFHIP_RUN_CONSENSUS) && b->cons && b->map.valid && b->tru.valid) consensus_launch(b);      // (the consensus: likewise)
+        if ((b->last_flags & FFHIP_RUN_ERRPROFILE) && b->errp && b->tru.valid && (!b->tru.from_map || b->map.valid)) errprofile_launch(b);      // (the error profile: likewise, in either truth mode)
     }
     return FFHIP_OK;
 }

@@ -482,6 +482,25 @@ void ffhip::consensus_launch(ffhip_batch *b) {
                      b->tru.rec.dev + truth_ops_at(b), b->bases(), b->Tb, rmap, c->view);
     pileup_mark(c, b);
 }
+// Error profile (include/ffhip.h "error profile"): their sibling by class, in either truth mode, with the same two shares.  It belongs to no reference: in the mode
+// of truth from map its launch takes the batch's own
+int ffhip::errprofile_check(const ffhip_batch *b, unsigned flags) {
+    if (!(flags & FFHIP_RUN_ERRPROFILE)) return FFHIP_OK;
+    if (!(flags & FFHIP_RUN_TRUTH)) return set_err(FFHIP_EINVAL, "error profile: the run does not make the truth records (FFHIP_RUN_ERRPROFILE goes with FFHIP_RUN_TRUTH)");
+    if (b->tru.from_map && !(flags & FFHIP_RUN_MAP))
+        return set_err(FFHIP_EINVAL, "error profile: the run does not make the map records (in the mode of truth from map FFHIP_RUN_ERRPROFILE goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH)");
+    if (!b->errp) return set_err(FFHIP_EINVAL, "error profile: no error profile is attached to the batch (ffhip_batch_set_errprofile)");
+    if (b->errp->eng != b->eng) return set_err(FFHIP_EINVAL, "error profile: the attached error profile belongs to another engine");
+    return FFHIP_OK;
+}
+void ffhip::errprofile_launch(ffhip_batch *b) {
+    ffhip_errprofile *p = b->errp;
+    const ReadMap rmap = b->packed ? ReadMap{ b->d_vb0, b->d_vb1, b->nread } : ReadMap();
+    const bool fm = b->tru.from_map != 0;
+    launch_errprofile(b->stream, fm ? &b->map.ref->view : nullptr, (const TruthRead *)b->tru.list.dev, batch_nreads(b), p->groups, fm ? b->map.rec.dev : nullptr,
+                      (const int *)b->tru.rec.dev, b->tru.rec.dev + truth_ops_at(b), b->bases(), b->quals(), b->tru.dseq, b->Tb, rmap, p->view);
+    pileup_mark(p, b);
+}
 // the copies of a finished run beside the block's: one a feature the run made, if it has a byte to bring
 int ffhip::annots_copy_down(ffhip_batch *b) {
     for (int i = 0; i < ffhip_batch::AN_COUNT; i++)
@@ -1005,6 +1024,76 @@ extern "C" int ffhip_batch_set_consensus(ffhip_batch *b, ffhip_consensus *c) {
     b->cons = c;
     return FFHIP_OK;
 }
+// ---- error profile (include/ffhip.h "error profile"; the kernel: ffhip_errprofile.hip)
+static int errprofile_zero(ffhip_errprofile *p) {
+    hipStream_t s = p->eng->streams[0];
+    HIP_TRY(hipMemsetAsync(p->view.counts, 0, (size_t)kErrWords * 8, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+extern "C" ffhip_errprofile *ffhip_errprofile_create(ffhip_engine *eng, int min_identity) {
+    if (!eng) { set_err(FFHIP_EINVAL, "error profile: an engine"); return nullptr; }
+    if (min_identity > 1000) { set_err(FFHIP_EINVAL, "error profile: min_identity is %d per mille (0 .. 1000)", min_identity); return nullptr; }
+    hipSetDevice(eng->device);
+    ffhip_errprofile *p = new ffhip_errprofile();
+    p->eng = eng;
+    p->view.min_identity = min_identity < 0 ? 0 : min_identity;
+    p->groups = std::max(1, eng->prop.multiProcessorCount);
+    if (dev_fill("error profile", { { (void **)&p->view.counts, nullptr, (size_t)kErrWords * 8 } })) {
+        set_err(FFHIP_ENOMEM, "error profile: the counters take %zu bytes of device memory, which could not be had", (size_t)kErrWords * 8);
+        delete p;
+        return nullptr;
+    }
+    if (errprofile_zero(p) != FFHIP_OK) { ffhip_errprofile_free(p); return nullptr; }
+    return p;
+}
+extern "C" void ffhip_errprofile_free(ffhip_errprofile *p) {
+    if (!p) return;
+    pileup_wait(p);
+    dev_free({ (void **)&p->view.counts });
+    delete p;
+}
+extern "C" int ffhip_errprofile_reset(ffhip_errprofile *p) {
+    if (!p) return set_err(FFHIP_EINVAL, "null error profile");
+    if (int rc = pileup_wait(p)) return rc;
+    return errprofile_zero(p);
+}
+extern "C" size_t ffhip_errprofile_words(void) { return (size_t)kErrWords; }
+extern "C" int ffhip_errprofile_download(ffhip_errprofile *p, uint64_t *counts, ffhip_errprofile_totals *totals) {
+    if (!p) return set_err(FFHIP_EINVAL, "null error profile");
+    static_assert(sizeof(ffhip_errprofile_totals) == kErrTotals * 8 && FFHIP_ERRPROFILE_WORDS == kErrWords && FFHIP_ERRPROFILE_TABLE_WORDS == kErrTableWords &&
+                  FFHIP_ERRPROFILE_SUB == kErrAtSub && FFHIP_ERRPROFILE_INS == kErrAtIns && FFHIP_ERRPROFILE_QUAL == kErrAtQual && FFHIP_ERRPROFILE_CTX == kErrAtCtx &&
+                  FFHIP_ERRPROFILE_HP == kErrAtHp && FFHIP_ERRPROFILE_HP_MAX_RUN == kErrHpMaxRun && FFHIP_ERRPROFILE_HP_MAX_CALLED == kErrHpMaxCalled &&
+                  FFHIP_ERRPROFILE_HP_MAX_OPS == kErrHpMaxOps, "the counters come down as they stand, in the header's sections");
+    if (int rc = pileup_wait(p)) return rc;
+    if (counts) HIP_TRY(hipMemcpy(counts, p->view.counts, (size_t)kErrTableWords * 8, hipMemcpyDeviceToHost), FFHIP_EHIP);
+    if (totals) HIP_TRY(hipMemcpy(totals, p->view.counts + kErrTableWords, sizeof *totals, hipMemcpyDeviceToHost), FFHIP_EHIP);
+    return FFHIP_OK;
+}
+extern "C" int ffhip_batch_set_errprofile(ffhip_batch *b, ffhip_errprofile *p) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "error profile: the batch is between a run and its finish");
+    if (!p) { b->errp = nullptr; return FFHIP_OK; }
+    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "error profile: a flip-flop model only (the run-length model's call is a list of runs)");
+    if (p->eng != b->eng) return set_err(FFHIP_EINVAL, "error profile: the error profile belongs to another engine");
+    b->errp = p;
+    return FFHIP_OK;
+}
+// test hook: the most workgroups of the object's later launches (0: the engine's compute units again), so that a workgroup's walk over several reads can be held
+// to one read a workgroup
+extern "C" int ffhip_debug_errprofile_groups(ffhip_errprofile *p, int groups) {
+    if (!p || groups < 0) return set_err(FFHIP_EINVAL, "error profile: an object and 0 or more workgroups");
+    p->groups = groups ? groups : std::max(1, p->eng->prop.multiProcessorCount);
+    return FFHIP_OK;
+}
+// test hook: between a run in the mode of truth from map and its finish, the stretches k_map_stretch gathered for k_truth are zeroed behind k_truth, on the batch's
+// stream -- what a re-run on the f32 path whose map record moved leaves stale.  Whatever the finish launches must not read them
+extern "C" int ffhip_debug_batch_clear_stretches(ffhip_batch *b) {
+    if (!b || !b->ran || b->finished || !b->tru.from_map || !b->tru.dseq) return set_err(FFHIP_EINVAL, "clear stretches: a batch in the mode of truth from map, between a run and its finish");
+    hipSetDevice(b->eng->device);
+    HIP_TRY(hipMemsetAsync(b->tru.dseq, 0, b->tru.dseq_cap, b->stream), FFHIP_EHIP);
+    return FFHIP_OK;
+}
 extern "C" long long ffhip_debug_map_truth_bound(int nblock, int max_error) {
     return (nblock < 0 || max_error < 0 || max_error > 500) ? -1 : map_truth_bound(nblock, max_error);
 }
@@ -1129,7 +1218,8 @@ extern "C" int ffhip_op_map_stretch(ffhip_engine *eng, const ffhip_map_ref *ref,
 // entry made here, and the ops and the call on the device
 struct PileOp { void *mrec; int *trec; TruthRead *list; uint8_t *ops; char *call; };
 static int pile_op(const char *who, TmpDev &tmp, hipStream_t s, const ffhip_map_ref *ref, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops, PileOp *out) {
-    if (int rc = span_check(who, ref, q, tstart, tend)) return rc;
+    if (ref) { if (int rc = span_check(who, ref, q, tstart, tend)) return rc; }      // (no reference: the error profile of a given truth, [0, m))
+    else if (tstart != 0 || tend < 1) return set_err(FFHIP_EINVAL, "%s: a truth of 1 or more bases", who);
     if (n > (size_t)kTruthMaxLen || nops > (size_t)2 * kTruthMaxLen) return set_err(FFHIP_EINVAL, "%s: a call of %zu bases and %zu ops (at most %d bases)", who, n, nops, kTruthMaxLen);
     if (const size_t i = bad_letter(call, n); i < n) return set_err(FFHIP_EINVAL, "%s: position %zu of the call: '%c' is not one of A C G T Z", who, i, call[i]);
     const size_t m = (size_t)(tend - tstart);
@@ -1168,6 +1258,31 @@ extern "C" int ffhip_op_consensus(ffhip_engine *eng, ffhip_consensus *c, int q, 
     if (int rc = pile_op("consensus", tmp, s, c->ref, q, tstart, tend, call, n, ops, nops, &d)) return rc;
     launch_consensus(s, c->ref->view, d.list, 1, d.mrec, d.trec, d.ops, d.call, n > 0 ? (int)n : 1, ReadMap(), c->view);
     return op_done(s);
+}
+// ... into an error profile (k_errprofile): with a reference the truth's letters are its span's, else the m codes given
+static int errprofile_op(ffhip_engine *eng, ffhip_errprofile *p, const ffhip_map_ref *ref, int q, int tstart, int tend, const char *call, const char *qual, size_t n,
+                         const uint8_t *truth, const uint8_t *ops, size_t nops) {
+    OP_ENTER(eng);
+    if (!p || p->eng != eng || (n && (!call || !qual)) || !ops || (ref ? ref->eng != eng : !truth))
+        return set_err(FFHIP_EINVAL, "bad error profile arguments (an error profile of this engine, a call of n letters with its n quality characters, a truth or a reference of this engine, nops ops)");
+    PileOp d;
+    if (int rc = pile_op("error profile", tmp, s, ref, q, tstart, tend, call, n, ops, nops, &d)) return rc;
+    const size_t m = (size_t)(tend - tstart);
+    if (!ref) if (const size_t j = bad_code(truth, m, 5); j < m) return set_err(FFHIP_EINVAL, "error profile: position %zu of the truth: code %d is not one of 0 .. 4", j, (int)truth[j]);
+    const char *d_qual = (const char *)tmp.upload(n ? qual : "", n ? n : 1, s);
+    const uint8_t *d_truth = ref ? nullptr : (const uint8_t *)tmp.upload(truth, m, s);
+    if (!d_qual || (!ref && !d_truth)) OP_NOMEM();
+    launch_errprofile(s, ref ? &ref->view : nullptr, d.list, 1, 1, d.mrec, d.trec, d.ops, d.call, d_qual, d_truth, n > 0 ? (int)n : 1, ReadMap(), p->view);
+    return op_done(s);
+}
+extern "C" int ffhip_op_errprofile(ffhip_engine *eng, ffhip_errprofile *p, const char *call, const char *qual, size_t n, const uint8_t *truth, size_t m, const uint8_t *ops, size_t nops) {
+    if (m > (size_t)kTruthMaxLen) return set_err(FFHIP_EINVAL, "error profile: a truth of %zu bases (at most %d)", m, kTruthMaxLen);
+    return errprofile_op(eng, p, nullptr, 0, 0, (int)m, call, qual, n, truth, ops, nops);
+}
+extern "C" int ffhip_op_errprofile_mapped(ffhip_engine *eng, ffhip_errprofile *p, const ffhip_map_ref *ref, int q, int tstart, int tend, const char *call, const char *qual, size_t n,
+                                          const uint8_t *ops, size_t nops) {
+    if (!ref) return set_err(FFHIP_EINVAL, "error profile: a reference of this engine");
+    return errprofile_op(eng, p, ref, q, tstart, tend, call, qual, n, nullptr, ops, nops);
 }
 extern "C" int ffhip_op_modpileup(ffhip_engine *eng, ffhip_modpileup *p, int q, int tstart, int tend, const char *call, const uint8_t *ml, size_t n, const uint8_t *ops, size_t nops) {
     OP_ENTER(eng);

@@ -96,6 +96,14 @@ struct ffhip_consensus {
     ffhip::ConsensusView view{};
     bool used[4] = { false, false, false, false };
 };
+// an error profile on the device (ffhip_errprofile_create; the kernel's view of it is ErrProfileView): kErrWords uint64, the tables and the twelve totals behind them;
+// `used` as the pileup's.  groups: the most workgroups of a launch (the engine's compute units; ffhip_debug_errprofile_groups sets another)
+struct ffhip_errprofile {
+    ffhip_engine *eng = nullptr;
+    ffhip::ErrProfileView view{};
+    int groups = 1;
+    bool used[4] = { false, false, false, false };
+};
 
 // a function or table one file of the library defines for another and the library does not export
 #define FFHIP_LOCAL __attribute__((visibility("hidden")))

@@ -318,6 +318,16 @@ enum { kConsensusLow = 0, kConsensusSame = 1, kConsensusSub = 2, kConsensusDel =
 void launch_consensus(hipStream_t s, const MapRefView &ref, const TruthRead *list, int count, const void *map_records, const int *truth_records, const uint8_t *ops,
                       const char *bases, int Tb, ReadMap map, const ConsensusView &cv);
 void launch_consensus_call(hipStream_t s, const MapRefView &ref, const ConsensusView &cv, unsigned min_depth, void *cells);
+// error profile (k_errprofile, ffhip_errprofile.hip; include/ffhip.h "error profile"): the same entries, truth records, ops and letters, the calls' quality characters
+// `quals` (rows as the letters') and the truths: the read's ops classed into kErrWords uint64 at ev.counts -- sub[4][5], ins[4], qual[94][3], ctx[1024][4],
+// hp[4][16][33], then the twelve totals { reads, skipped, match, mismatch, del, ins, edge_ins, ctx_sites, hp_runs, hp_long, hp_wide, reserved }.  `ref` given: the
+// mode of truth from map -- the map records are read and a truth letter comes from ref's words at the record's span; `seq` is not read.  `ref` null: a set truth --
+// a letter is seq[entry.seq + j] and no map record is read.  One launch of min(count, groups) workgroups, each taking every gridDim.x-th entry; atomics only.
+struct ErrProfileView { unsigned long long *counts; int min_identity; };
+constexpr int kErrHpMaxRun = 16, kErrHpMaxCalled = 32, kErrHpMaxOps = 64;
+constexpr int kErrAtSub = 0, kErrAtIns = 20, kErrAtQual = 24, kErrAtCtx = 306, kErrAtHp = 4402, kErrTableWords = 6514, kErrTotals = 12, kErrWords = kErrTableWords + kErrTotals;
+void launch_errprofile(hipStream_t s, const MapRefView *ref, const TruthRead *list, int count, int groups, const void *map_records, const int *truth_records,
+                       const uint8_t *ops, const char *bases, const char *quals, const uint8_t *seq, int Tb, ReadMap map, const ErrProfileView &ev);
 // the signal of every base of a mapped read (k_events, ffhip_events.hip; include/ffhip.h "events"): per listed read whose remap record at records[read] says
 // { status 1, end 0 }, L events of 16 bytes { int32 first, count; float mean, sd } at events[out ..], from the read's samples sig[sig .. sig + n) and its bytes at the
 // read's row of the (Tb + 1)-entry byte buffer `rm`; any other read writes nothing.  One form; the launch comes behind launch_remap on the same stream.

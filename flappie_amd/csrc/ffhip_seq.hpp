@@ -1,7 +1,7 @@
 // ffhip_seq.hpp -- what the sequence kernels share, each written once: the letters' 2-bit codes, one column of Myers' bit-vector recurrence, the 64-lane
 // butterfly reductions, the flip-flop state coding of a coded position, and the two-hypothesis window recursion over a read's score rows.  Device code, except the
 // state coding, which the host reads too.  Every result is an integer, or a float with a fixed order of operations: a kernel that calls these computes the same
-// bytes wherever it stands.  Included by ffhip_adapters, _barcodes, _map, _truth, _pileup, _modpileup, _consensus, _polytail, _events, _remap, _sitemods and _variants.hip.
+// bytes wherever it stands.  Included by ffhip_adapters, _barcodes, _map, _truth, _pileup, _modpileup, _consensus, _errprofile, _polytail, _events, _remap, _sitemods and _variants.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

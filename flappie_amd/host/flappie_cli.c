@@ -51,6 +51,7 @@
 #include "../../include/flappie_pileup.h"
 #include "../../include/flappie_modpileup.h"
 #include "../../include/flappie_consensus.h"
+#include "../../include/flappie_errprofile.h"
 #include "../../include/networks.h"
 
 const char *argp_program_version = "flappie (MI355X/HIP) 0.1, interface of flappie 2.1.3";
@@ -154,8 +155,12 @@ static struct argp_option options[] = {
     {"map-consensus-changes", 302, "changes.tsv", 0, "With --map-consensus: where the consensus differs from the reference: one line for every position with a substitution, a deletion or inserted letters, no header: record, 0-based position, reference letter, the letters written there (- if none), depth, the winner's count, the first inserted letter's count (0 if none)"},
     {"map-consensus-min-depth", 303, "N", 0, "With --map-consensus: a position covered by fewer aligned calls than this keeps the reference's letter, in lower case (1-65535, default 3). The default comes from reasoning, not from reads"},
     {"map-consensus-min-identity", 304, "permille", 0, "With --map-consensus: count only reads whose alignment's identity is at least this many thousandths (0-1000, default 0), as --map-pileup-min-identity"},
+    {"truth-errors", 305, "errors.tsv", 0, "With --truth and --truth-out, or with --truth-from-map: the run's error profile, counted on the GPU over all the aligned reads and written once at the end, no header, integers only: 20 lines 'sub', truth letter, called letter (- a deletion), count; 4 lines 'ins', inserted letter, count; 94 lines 'qual', quality, matches, mismatches, inserted letters with it; 'ctx', the truth's 5-mer, matches, mismatches and deletions at its centre and insertions behind it, for every 5-mer with a count; 'hp', letter, true length (1-16), called length (32: 32 or more), count, for every homopolymer run inside a truth. Runs longer than 16 and runs whose alignment takes more than 64 ops are counted on stderr only (hp_long, hp_wide), as are insertions before the first or behind the last truth base (edge_ins). The whole call counts: --reverse, the trims and --split-reads do not alter it. stdout, acc.tsv, hits.tsv and every other file do not change"},
+    {"truth-errors-min-identity", 306, "permille", 0, "With --truth-errors: count only reads whose alignment's identity is at least this many thousandths (0-1000, default 0), as --map-pileup-min-identity"},
 #endif
 #ifdef BUILD_RUNNIE
+    {"truth-errors", 305, "errors.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"truth-errors-min-identity", 306, "permille", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-consensus", 301, "cons.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-consensus-changes", 302, "changes.tsv", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-consensus-min-depth", 303, "N", OPTION_HIDDEN, "(flappie's option: refused here)"},
@@ -275,6 +280,9 @@ static bool mm_combine = false;
 /* flappie: the files of --map-consensus and --map-consensus-changes, --map-consensus-min-depth and -min-identity (-1: not given) (runnie: seen, to be refused) */
 static char *cs_path = NULL, *cs_changes_path = NULL;
 static int cs_min_depth = -1, cs_min_identity = -1;
+/* flappie: the file of --truth-errors and --truth-errors-min-identity (-1: not given) (runnie: seen, to be refused) */
+static char *ep_path = NULL;
+static int ep_min_identity = -1;
 static int map_window = -1;
 #ifndef BUILD_RUNNIE
 static int map_max_error = -1;
@@ -474,6 +482,14 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
         if (end == arg || *end != '\0' || v < low || v > top)
             errx(EXIT_FAILURE, "--map-consensus-%s must be a whole number from %ld to %ld", key == 303 ? "min-depth" : "min-identity", low, top);
         *(key == 303 ? &cs_min_depth : &cs_min_identity) = (int)v;
+        break;
+    }
+    case 305: ep_path = arg; break;
+    case 306: {
+        char *end = NULL;
+        const long v = strtol(arg, &end, 10);
+        if (end == arg || *end != '\0' || v < 0 || v > 1000) errx(EXIT_FAILURE, "--truth-errors-min-identity must be a whole number from 0 to 1000");
+        ep_min_identity = (int)v;
         break;
     }
 #ifdef BUILD_RUNNIE
@@ -855,12 +871,15 @@ static FILE *mm_out = NULL, *mm_hist = NULL;
 /* flappie --map-consensus: likewise the one consensus of the run; its FASTA file and the table of changes */
 static ffhip_consensus *cs_dev = NULL;
 static FILE *cs_out = NULL, *cs_changes = NULL;
+/* flappie --truth-errors: likewise the one error profile of the run, in either truth mode; its table */
+static ffhip_errprofile *ep_dev = NULL;
+static FILE *ep_out = NULL;
 /* --modbase-tags: the 5mC bytes of the called bases come from the device (FFHIP_RUN_MOD_PROBS); --emit-moves: the move table does (FFHIP_RUN_MOVES);
  * --barcodes: the reads' barcode records do (FFHIP_RUN_BARCODES); --adapters: their adapter records (FFHIP_RUN_ADAPTERS); --poly-tail: their poly tail
  * records (FFHIP_RUN_POLYTAIL) */
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | ((args.modbase_tags || mm_dev) ? FFHIP_RUN_MOD_PROBS : 0u) | (mm_dev ? FFHIP_RUN_MOD_PILEUP : 0u) |
-           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (mp_dev ? FFHIP_RUN_MAP : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | ((tr_refs || tfm_on) ? FFHIP_RUN_TRUTH : 0u) | (pu_dev ? FFHIP_RUN_PILEUP : 0u) | (cs_dev ? FFHIP_RUN_CONSENSUS : 0u) |
+           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (mp_dev ? FFHIP_RUN_MAP : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | ((tr_refs || tfm_on) ? FFHIP_RUN_TRUTH : 0u) | (pu_dev ? FFHIP_RUN_PILEUP : 0u) | (cs_dev ? FFHIP_RUN_CONSENSUS : 0u) | (ep_dev ? FFHIP_RUN_ERRPROFILE : 0u) |
            (ev_out ? FFHIP_RUN_EVENTS : 0u) | (md_out ? FFHIP_RUN_REMAP_MODS : 0u) | (vr_out ? FFHIP_RUN_REMAP_VARIANTS : 0u);
 }
 /* --remap: every read's record, by its read id, then by its file's base name; a bad record goes as a sequence of no bases (status 2) */
@@ -930,6 +949,7 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
     if (pu_dev) { const int rc = ffhip_batch_set_pileup(b, pu_dev); if (rc) return rc; }
     if (mm_dev) { const int rc = ffhip_batch_set_modpileup(b, mm_dev); if (rc) return rc; }
     if (cs_dev) { const int rc = ffhip_batch_set_consensus(b, cs_dev); if (rc) return rc; }
+    if (ep_dev) { const int rc = ffhip_batch_set_errprofile(b, ep_dev); if (rc) return rc; }
     return ffhip_batch_run(b, args.temperature, flags);
 }
 #endif
@@ -2270,6 +2290,7 @@ int main(int argc, char *argv[]) {
         errx(EXIT_FAILURE, "--map-mods and its --map-mods-* options are flappie's: the run-length model's call is a list of runs and it has no modified base");
     if (cs_path || cs_changes_path || cs_min_depth >= 0 || cs_min_identity >= 0)
         errx(EXIT_FAILURE, "--map-consensus and its --map-consensus-* options are flappie's: the run-length model's call is a list of runs");
+    if (ep_path || ep_min_identity >= 0) errx(EXIT_FAILURE, "--truth-errors and --truth-errors-min-identity are flappie's: the run-length model's call is a list of runs");
     if (args.remap_events) errx(EXIT_FAILURE, "--remap-events is flappie's: it goes with --remap, which the run-length model does not have");
     if (mods_path) errx(EXIT_FAILURE, "--remap-mods is flappie's: it goes with --remap, which the run-length model does not have");
     if (vars_path || vars_out_path || vars_opts) errx(EXIT_FAILURE, "--remap-variants is flappie's: it goes with --remap, which the run-length model does not have");
@@ -2331,6 +2352,9 @@ int main(int argc, char *argv[]) {
         errx(EXIT_FAILURE, "--map-consensus-changes, --map-consensus-min-depth and --map-consensus-min-identity go with --map-consensus");
     if (cs_path && !tfm_on) errx(EXIT_FAILURE, "--map-consensus goes with --truth-from-map: it counts what the alignments say");
     if (cs_path && cs_min_depth < 0) cs_min_depth = 3;
+    /* --truth-errors: the alignments of either truth mode, classed */
+    if (ep_min_identity >= 0 && NULL == ep_path) errx(EXIT_FAILURE, "--truth-errors-min-identity goes with --truth-errors");
+    if (ep_path && !tfm_on && NULL == args.truth) errx(EXIT_FAILURE, "--truth-errors goes with --truth or --truth-from-map: it counts what the alignments say");
     if (map_path) {
         char why[256];
         mp_ref = flappie_map_ref_read(map_path, why, sizeof why);
@@ -2391,6 +2415,7 @@ int main(int argc, char *argv[]) {
             if (tr_refs->bad[k]) warnx("--truth: record %s holds a letter outside the model's alphabet: its read is not aligned (status 2)", tr_refs->name[k]);
         if (NULL == (tr_out = fopen(args.truth_out, "w"))) errx(EXIT_FAILURE, "--truth-out %s: cannot be written", args.truth_out);
     }
+    if (ep_path && NULL == (ep_out = fopen(ep_path, "w"))) errx(EXIT_FAILURE, "--truth-errors %s: cannot be written", ep_path);
     if (args.modbase_tags && !flappie_model_has_modbase(args.model))      /* (the registry knows: before any file or the GPU is touched) */
         errx(EXIT_FAILURE, "--modbase-tags needs a model with a modified base (r941_5mC); \"%s\" has none", flappie_model_string(args.model));
 #endif
@@ -2443,6 +2468,10 @@ int main(int argc, char *argv[]) {
     if (cs_out && NULL == (cs_dev = ffhip_consensus_create(eng, mp_dev, cs_min_identity))) {
         stop_reader_procs();
         errx(EXIT_FAILURE, "--map-consensus: %s", ffhip_last_error());
+    }
+    if (ep_out && NULL == (ep_dev = ffhip_errprofile_create(eng, ep_min_identity))) {
+        stop_reader_procs();
+        errx(EXIT_FAILURE, "--truth-errors: %s", ffhip_last_error());
     }
 #endif
     hid_t hdf5out = open_or_create_hdf5(args.trace);
@@ -2568,6 +2597,19 @@ int main(int argc, char *argv[]) {
         if (0 != fclose(cs_out)) warnx("--map-consensus %s: write failed", cs_path);
         if (cs_changes && 0 != fclose(cs_changes)) warnx("--map-consensus-changes %s: write failed", cs_changes_path);
         ffhip_consensus_free(cs_dev);
+    }
+    if (ep_dev) {                      /* the error profile, once: every batch object is gone, so every accumulation is done */
+        uint64_t *counts = malloc(FFHIP_ERRPROFILE_TABLE_WORDS * sizeof *counts);
+        ffhip_errprofile_totals tot;
+        if (NULL == counts) warnx("--truth-errors: out of memory for the counters");
+        else if (0 != ffhip_errprofile_download(ep_dev, counts, &tot)) warnx("--truth-errors: %s", ffhip_last_error());
+        else {
+            flappie_errprofile_write(ep_out, counts);
+            flappie_errprofile_summary_print(stderr, &tot);
+        }
+        free(counts);
+        if (0 != fclose(ep_out)) warnx("--truth-errors %s: write failed", ep_path);
+        ffhip_errprofile_free(ep_dev);
     }
     if (mp_ref) {                      /* reads, mapped, unmapped, discordant; the mapped reads' anchor distances over their anchor bases */
         flappie_map_summary_print(stderr, &mp_sum);

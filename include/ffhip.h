@@ -167,6 +167,14 @@ typedef struct {
  * consensus attached or with one of another reference than the batch's: FFHIP_EINVAL with a text that says which.  FFHIP_RUN_PILEUP and FFHIP_RUN_MOD_PILEUP are
  * neither required nor excluded. */
 #define FFHIP_RUN_CONSENSUS  (1u << 25)   /* 33554432: the bit behind FFHIP_RUN_MOD_PILEUP */
+/* With FFHIP_RUN_TRUTH, in either truth mode (ffhip_batch_set_truth, or ffhip_batch_set_truth_from_map and then FFHIP_RUN_MAP as well): every aligned read's ops classed
+ * -- which truth base was called as which, the quality of every called base, the truth 5-mer under every op, every homopolymer run's called length -- into the error
+ * profile attached with ffhip_batch_set_errprofile ("error profile" below) -- on the device (k_errprofile), as the last step of ffhip_batch_finish, from the records,
+ * letters and qualities the caller reads.  Nothing comes down per read and the batch holds nothing new (ffhip_debug_batch_device_bytes does not change); everything the
+ * run returns is that of the same run without the flag.  Without FFHIP_RUN_TRUTH, in the mode of truth from map without FFHIP_RUN_MAP, with no error profile attached
+ * or with one of another engine: FFHIP_EINVAL with a text that says which.  The run-length model and FFHIP_RUN_NO_DECODE are refused as for FFHIP_RUN_TRUTH.
+ * FFHIP_RUN_PILEUP, FFHIP_RUN_MOD_PILEUP and FFHIP_RUN_CONSENSUS are neither required nor excluded. */
+#define FFHIP_RUN_ERRPROFILE (UINT32_C(1) << 26)   /* 67108864: the bit behind FFHIP_RUN_CONSENSUS */
 
 const char *ffhip_last_error(void);
 const char *ffhip_version(void);
@@ -910,6 +918,72 @@ int ffhip_consensus_download(ffhip_consensus *c, uint32_t *counts /* [37][P] */,
 int ffhip_consensus_call(ffhip_consensus *c, int min_depth, ffhip_consensus_cell *cells /* [P] */);
 int ffhip_batch_set_consensus(ffhip_batch *b, ffhip_consensus *c);
 int ffhip_op_consensus(ffhip_engine *eng, ffhip_consensus *c, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops);
+/* Error profile: by CLASS instead of by position, what the aligned calls of all the reads of all the batches it is attached to got right and wrong
+ * (tests/errprofile_ref.py restates this).  The pileup's sibling: integer adds only, the same bytes whatever the batch size, packing, pairing or read order.  It needs
+ * no reference coordinates, so it serves a set truth (ffhip_batch_set_truth) as well as truth from map, and belongs to no reference.
+ *   Inputs of one counted read: its call s of n letters in signal order (code: A 0, C and Z 1, G 2, T 3); its n quality characters Q, the bytes of ffhip_batch_basecall's
+ *     quality string taken as unsigned, qv_i = clamp(Q_i - 33, 0, 93); its truth t of m codes in signal order, code 4 read as 1 -- the codes of ffhip_batch_set_truth or,
+ *     in the mode of truth from map, y_q[tstart + j] of its MAP RECORD (read from the reference's letters, not from a kept copy of the stretch); the K ops of its truth
+ *     record (0 '=', 1 'X', 2 'I', 3 'D').  (j, i) is the number of truth and call bases consumed before an op.  An 'I' op is INTERIOR iff 1 <= j <= m - 1, else an EDGE
+ *     insertion.
+ *   Which reads count: the pileup's rule -- truth status 1; in the mode of truth from map also map status 1 and tend - tstart == m; and 1000 n_match >= min_identity
+ *     (n_match + n_mismatch + n_ins + n_del) in 64-bit integers.  A read with the statuses that fails the test adds 1 to `skipped` and nothing else; any other read adds
+ *     nothing.  A counted read adds 1 to `reads`.
+ *   Counters: FFHIP_ERRPROFILE_WORDS = 6526 uint64 in one flat array: the tables (FFHIP_ERRPROFILE_TABLE_WORDS = 6514) and the twelve totals behind them.
+ *     sub[4][5] at FFHIP_ERRPROFILE_SUB: '=' / 'X' adds to sub[t_j][code(s_i)], 'D' to sub[t_j][4].
+ *     ins[4] at FFHIP_ERRPROFILE_INS: an interior 'I' adds to ins[code(s_i)].
+ *     qual[94][3] at FFHIP_ERRPROFILE_QUAL: '=' adds to qual[qv_i][0], 'X' to qual[qv_i][1], an interior 'I' to qual[qv_i][2].
+ *     ctx[1024][4] at FFHIP_ERRPROFILE_CTX, with w(c) = sum over d = -2 .. 2 of 4^(2 - d) t_(c + d), defined for 2 <= c <= m - 3: an op that consumes t_j with such a j
+ *       adds to ctx[w(j)][0 | 1 | 2] for '=', 'X', 'D'.  An interior 'I' at (j, i) belongs to the centre j - 1: with 3 <= j <= m - 2 it adds to ctx[w(j - 1)][3].
+ *       Everything else adds nothing here.
+ *     hp[4][16][33] at FFHIP_ERRPROFILE_HP: the maximal runs of equal letters of t, run [a, a + r) of letter b.  Only INTERIOR runs count: a >= 1 and a + r <= m - 1 (a
+ *       run that touches an end of the truth has an unknown true length).  r > 16: hp_long += 1 and nothing else.  Otherwise let k_first and k_last be the ops that
+ *       consume t_a and t_(a + r - 1), F the maximal block of consecutive 'I' ops ending at k_first - 1 and B the one starting at k_last + 1 (both gaps are interior by
+ *       construction).  The run's ops are [k_first - |F|, k_last + |B|].  More than 64 of them: hp_wide += 1 and nothing else.  Otherwise c = the '=' ops in [k_first,
+ *       k_last] + the 'I' ops among the run's ops whose letter is b; hp[b][r - 1][min(c, 32)] += 1 and hp_runs += 1.  Neighbouring runs differ in letter, so no inserted
+ *       letter counts twice.
+ *       One bounded walk decides this, so "r > 16" is read off the run's first 17 letters: a run with a >= 1 whose letters t_a .. t_(a + 16) are equal and whose 17th is
+ *       not the truth's last (a + 17 <= m - 1) adds to hp_long, whether or not it goes on to the truth's end; a run that reaches the end within those 17 adds nothing.
+ *     Totals (ffhip_errprofile_totals): reads, skipped, match, mismatch, del, ins (interior), edge_ins, ctx_sites (the ops that added to ctx), hp_runs, hp_long, hp_wide
+ *       and one reserved word that stays 0.
+ *   Counters wrap at 2^64.  Fixed at creation: min_identity in per mille by the pileup's rule (negative: 0; above 1000: refused).
+ *   When: the last step of a successful ffhip_batch_finish of a run with FFHIP_RUN_ERRPROFILE, where the pileup's stands: behind the f32 re-runs' patches and in the
+ *     innermost finish of the time-out fallback.  A side batch never counts.  Its order against the pileup's kernels is free.
+ *   The limits 16, 64 and 32 come from reasoning about small references, whose longest homopolymers are about 10; no real read has been through them.
+ * ffhip_errprofile_create: zeroed counters; a bad min_identity: NULL with a text.  It must outlive every batch it is attached to.
+ * ffhip_errprofile_free / _reset / _download wait for every accumulation enqueued against it; each output of download may be NULL.  ffhip_errprofile_words: 6526.
+ * ffhip_batch_set_errprofile: the error profile of the batch's later runs with the flag; NULL detaches.  One of another engine, the run-length model, or a call between
+ *   a run and its finish: FFHIP_EINVAL.
+ * ffhip_op_errprofile: the kernel on ONE alignment from host arrays, added into p: the call and its n quality characters, the truth's m codes (0 .. 4) and the ops.
+ * ffhip_op_errprofile_mapped: the same with the truth's letters from the span [tstart, tend) of search q of `ref`.  Both refuse what ffhip_op_pileup refuses (a span
+ *   or a truth of no base, letters other than A C G T Z, codes out of range, ops that do not consume exactly the call and the truth) and add nothing then.  The
+ *   identity test applies.
+ * ffhip_debug_errprofile_groups: a test hook -- the most workgroups of the object's later launches (0: the default, the device's compute units). */
+typedef struct ffhip_errprofile ffhip_errprofile;
+typedef struct { uint64_t reads, skipped, match, mismatch, del, ins, edge_ins, ctx_sites, hp_runs, hp_long, hp_wide, reserved; } ffhip_errprofile_totals;      /* 96 bytes */
+#define FFHIP_ERRPROFILE_SUB 0
+#define FFHIP_ERRPROFILE_INS 20
+#define FFHIP_ERRPROFILE_QUAL 24
+#define FFHIP_ERRPROFILE_CTX 306
+#define FFHIP_ERRPROFILE_HP 4402
+#define FFHIP_ERRPROFILE_TABLE_WORDS 6514
+#define FFHIP_ERRPROFILE_WORDS 6526
+#define FFHIP_ERRPROFILE_HP_MAX_RUN 16
+#define FFHIP_ERRPROFILE_HP_MAX_CALLED 32
+#define FFHIP_ERRPROFILE_HP_MAX_OPS 64
+ffhip_errprofile *ffhip_errprofile_create(ffhip_engine *eng, int min_identity);
+void ffhip_errprofile_free(ffhip_errprofile *p);
+int ffhip_errprofile_reset(ffhip_errprofile *p);
+size_t ffhip_errprofile_words(void);
+int ffhip_errprofile_download(ffhip_errprofile *p, uint64_t *counts /* [6514] */, ffhip_errprofile_totals *totals);
+int ffhip_batch_set_errprofile(ffhip_batch *b, ffhip_errprofile *p);
+int ffhip_op_errprofile(ffhip_engine *eng, ffhip_errprofile *p, const char *call, const char *qual, size_t n, const uint8_t *truth, size_t m, const uint8_t *ops, size_t nops);
+int ffhip_op_errprofile_mapped(ffhip_engine *eng, ffhip_errprofile *p, const ffhip_map_ref *ref, int q, int tstart, int tend, const char *call, const char *qual, size_t n,
+                               const uint8_t *ops, size_t nops);
+int ffhip_debug_errprofile_groups(ffhip_errprofile *p, int groups);
+/* a test hook: between a run in the mode of truth from map and its finish, zero the stretches gathered for k_truth, behind k_truth on the batch's stream -- what a re-run
+ * on the f32 path whose map record moved leaves stale.  Nothing the finish launches may read them; every record the run returns is unchanged */
+int ffhip_debug_batch_clear_stretches(ffhip_batch *b);
 int ffhip_runlength_viterbi(ffhip_engine *eng, ffhip_mat param, int *path /* nblock */, float *score);
 /* decoders of the first-generation head on [4 nbase x nblock] matrices: decode_runlength (decode.c:694-767), posterior_runlength
  * (decode.c:793-892; post is [4 nbase x nblock + 1]), runlengths_mean (decode.c:576-603) */
