@@ -331,6 +331,9 @@ def lib():
     L.ffhip_batch_remap.argtypes = [vp, C.c_int, C.POINTER(CRemapCall)]
     L.ffhip_op_remap.argtypes = [vp, CFMat, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_float)]
     L.ffhip_debug_remap_form.argtypes = [C.c_size_t, C.c_int]
+    L.ffhip_batch_set_remap_from_map.argtypes = [vp, C.c_int, C.c_int]
+    L.ffhip_op_map_remap_code.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+    L.ffhip_debug_remap_from_map_form.argtypes = [C.c_int, C.c_int]
     L.ffhip_batch_events.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.ffhip_op_events.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_size_t, vp]
     L.ffhip_batch_set_remap_mods.argtypes = [vp, C.c_int, C.c_int]
@@ -1046,6 +1049,10 @@ class Batch:
                 lens[r] = a.size
         _check(lib().ffhip_batch_set_truth(self.h, n, ptrs, lens, int(band)))
 
+    def set_remap_from_map(self, on: bool = True, band: int = 2048):
+        """later runs with RUN_MAP | RUN_REMAP take each read's sequence from its map record (ffhip_batch_set_remap_from_map); it and set_remap replace each other"""
+        _check(lib().ffhip_batch_set_remap_from_map(self.h, 1 if on else 0, int(band)))
+
     def set_truth_from_map(self, on: bool = True, band: int = 512):
         """later runs with RUN_MAP | RUN_TRUTH take each read's truth from its map record (ffhip_batch_set_truth_from_map); it and set_truth replace each other"""
         _check(lib().ffhip_batch_set_truth_from_map(self.h, 1 if on else 0, int(band)))
@@ -1322,6 +1329,21 @@ def op_map_stretch(engine: Engine, ref: MapRef, q: int, start: int, end: int) ->
     out = np.zeros(max(1, int(end) - int(start)), np.uint8)
     _check(lib().ffhip_op_map_stretch(engine.h, ref.h, int(q), int(start), int(end), out.ctypes.data_as(C.POINTER(C.c_uint8))))
     return out[:int(end) - int(start)]
+
+
+def op_map_remap_code(engine: Engine, ref: MapRef, q: int, start: int, end: int, nbase: int, room: int, fill: int = 0xffff) -> tuple:
+    """ffhip_op_map_remap_code: (entries uint16 [end - start], status, L) of y_q[start : end] in remap's coding (stay | move << 8), made by the kernel of remap from
+    map for an entry of `room` positions; with status 2 the entries are `fill`, what the output held before the call"""
+    n = max(1, int(end) - int(start))
+    out = np.full(n, fill, np.uint16)
+    status, L = C.c_int(0), C.c_size_t(0)
+    _check(lib().ffhip_op_map_remap_code(engine.h, ref.h, int(q), int(start), int(end), int(nbase), int(room), out.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(status), C.byref(L)))
+    return out[:max(0, int(end) - int(start))], int(status.value), int(L.value)
+
+
+def remap_from_map_form(nblock: int, band: int) -> int:
+    """ffhip_debug_remap_from_map_form: the kernel form a read of `nblock` blocks takes in the mode of remap from map (-1: none)"""
+    return int(lib().ffhip_debug_remap_from_map_form(int(nblock), int(band)))
 
 
 def map_truth_bound(nblock: int, max_error: int) -> int:

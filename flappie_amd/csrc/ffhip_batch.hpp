@@ -152,11 +152,13 @@ struct ffhip_batch {
     // windows' workspace (a double and a byte a window of every read, `windows` of them in this run), grown when a run needs more
     struct PolyTail : Annot { ffhip_polytail_params p{}; bool set = false; uint8_t *ws = nullptr; size_t ws_cap = 0, windows = 0; } pt;
     // Remap (FFHIP_RUN_REMAP, k_remap): the coded sequences of ffhip_batch_set_remap on the host and (dseq) on the device; cap_reads 16-byte records and, behind them,
-    // a byte a block in the layout of the (Tb + 1)-entry buffers; the reads' list and the traceback workspace, both written by the front of every run that asks
+    // a byte a block in the layout of the (Tb + 1)-entry buffers; the reads' list and the traceback workspace, both written by the front of every run that asks.
+    // from_map (ffhip_batch_set_remap_from_map): no sequences on the host -- k_map_remap_seq codes each mapped read's stretch into dseq and patches the list, and
+    // everything is sized from the read's blocks N: N + 1 positions
     struct Remap : Annot {
         std::vector<std::vector<unsigned short>> seq;       // per read: stay | move << 8 of every position (remap_code)
         std::vector<signed char> state;                      // per read: 0 no sequence, 1 a sequence, 2 refused at the call (L = 0)
-        int set = 0, band = 0;
+        int set = 0, band = 0, from_map = 0;
         unsigned short *dseq = nullptr; size_t dseq_cap = 0;
         unsigned long long *ws = nullptr; size_t ws_cap = 0;
         int count[kRemapForms] = { 0, 0, 0, 0 };

@@ -1773,7 +1773,10 @@ static int rerun_on_f32_path(ffhip_batch *b, const std::vector<int> &reads) {
         sd->ad.kit = b->ad.kit; sd->ad.max_dist = b->ad.max_dist;
         sd->map.ref = b->map.ref; sd->map.window = b->map.window; sd->map.max_error = b->map.max_error;
         sd->pt.p = b->pt.p; sd->pt.set = b->pt.set;
-        if (fl & FFHIP_RUN_REMAP) {                       // ... and for these reads' sequences
+        if ((fl & FFHIP_RUN_REMAP) && b->rmp.from_map) {  // ... and remap's mode: the side batch maps these reads itself and codes their sequences from its own records
+            sd->rmp.seq.clear(); sd->rmp.state.clear(); sd->var.set.clear();      // (the same N: the same room for a read in both batches)
+            sd->rmp.set = 0; sd->rmp.from_map = 1; sd->rmp.band = b->rmp.band;
+        } else if (fl & FFHIP_RUN_REMAP) {                // ... or these reads' sequences
             std::vector<std::vector<unsigned short>> sq(16);
             std::vector<signed char> st(16, 0);
             for (int k = 0; k < n; k++) { sq[k] = b->rmp.seq[reads[k0 + k]]; st[k] = b->rmp.state[reads[k0 + k]]; }

@@ -170,23 +170,40 @@ template <class Launch> static void forms_launch(ffhip_batch *b, Annot &f, const
 
 // Remap, the front's share: buffers on first use, every read's status, kernel form and place in the workspace, the lists a form each, their upload.
 static_assert(sizeof(RemapRead) == 24, "the reads' list is copied as it stands");
-static bool remap_mappable(const ffhip_batch *b, int r) {      // this read's sequence can be mapped
-    const int N = b->hTb[r], L = (int)b->rmp.seq[r].size();
-    return b->rmp.state[r] == 1 && N >= 1 && L >= 1 && L <= N + 1;
+// the sequence's positions the host sizes read r by: its sequence's, or -- remap from map, where no length is known here -- the N + 1 a path of its N blocks can hold
+static int remap_room(const ffhip_batch *b, int r) { return b->rmp.from_map ? (b->hTb[r] >= 1 ? b->hTb[r] + 1 : 0) : (int)b->rmp.seq[r].size(); }
+static bool remap_mappable(const ffhip_batch *b, int r) {      // this read's sequence can be mapped (from the map: it may have one)
+    const int N = b->hTb[r], L = remap_room(b, r);
+    return (b->rmp.from_map || b->rmp.state[r] == 1) && N >= 1 && L >= 1 && L <= N + 1;
 }
 static size_t remap_bytes(const ffhip_batch *b) { return remap_moves_at(b) + (size_t)b->nread * ((size_t)b->Tb + 1); }
+// The two modes differ in where a read's length and status come from, as truth's do.  A set sequence has its own.  From the map every read of N >= 1 blocks is listed
+// with L = 0 and status 1 for k_map_remap_seq to patch; its share of the sequences (dseq grows here in this mode), its kernel form and its workspace are those of
+// N + 1 positions, the most a path of N blocks can hold.
 static int remap_prepare(ffhip_batch *b) {
     ffhip_batch::Remap &f = b->rmp;
     const int nR = batch_nreads(b);
-    if (!f.set) return set_err(FFHIP_EINVAL, "remap: no sequences are set for the batch (ffhip_batch_set_remap)");
-    if ((int)f.seq.size() != nR) return set_err(FFHIP_EINVAL, "remap: sequences were set for %zu reads, the batch holds %d", f.seq.size(), nR);
+    const bool fm = f.from_map != 0;
+    if (fm) {
+        if (!(b->run_flags & FFHIP_RUN_MAP)) return set_err(FFHIP_EINVAL, "remap from map: the run does not make the map records (FFHIP_RUN_REMAP goes with FFHIP_RUN_MAP in this mode)");
+        if (!b->map.ref) return set_err(FFHIP_EINVAL, "remap from map: no reference is attached to the batch (ffhip_batch_set_map)");
+        if (b->run_flags & FFHIP_RUN_REMAP_MODS)
+            return set_err(FFHIP_EINVAL, "remap from map: site mods are listed on the host from sequences it does not have in this mode (FFHIP_RUN_REMAP_MODS goes with ffhip_batch_set_remap)");
+        if (b->run_flags & FFHIP_RUN_REMAP_VARIANTS)
+            return set_err(FFHIP_EINVAL, "remap from map: variants are validated on the host against sequences it does not have in this mode (FFHIP_RUN_REMAP_VARIANTS goes with ffhip_batch_set_remap)");
+    } else {
+        if (!f.set) return set_err(FFHIP_EINVAL, "remap: no sequences are set for the batch (ffhip_batch_set_remap)");
+        if ((int)f.seq.size() != nR) return set_err(FFHIP_EINVAL, "remap: sequences were set for %zu reads, the batch holds %d", f.seq.size(), nR);
+    }
     if (int rc = f.rec.fixed(b, remap_bytes(b), "remap: the records and moves")) return rc;
     if (int rc = f.list.grow(b, b->stream, (size_t)b->cap_reads * sizeof(RemapRead), "remap: the reads' list")) return rc;
     std::vector<RemapRead> per[kRemapForms];
     size_t ws = 0, seq = 0;
     for (int r = 0; r < nR; r++) {
-        const int L = (int)f.seq[r].size();
-        RemapRead rr{ ws, (unsigned)seq, L, f.state[r], r };
+        const int L = remap_room(b, r);
+        if (fm && seq + (size_t)L > (size_t)0xffffffffu)
+            return set_err(FFHIP_EINVAL, "remap from map: the reads' rooms come to more than 2^32 - 1 positions together (read %d: %d), which the list's 32-bit offsets cannot hold", r, L);
+        RemapRead rr{ ws, (unsigned)seq, fm ? 0 : L, fm ? (L > 0 ? 1 : 0) : f.state[r], r };
         int form = 0;
         if (rr.status == 1 && !remap_mappable(b, r)) rr.status = 2;
         if (rr.status == 1) {
@@ -197,11 +214,16 @@ static int remap_prepare(ffhip_batch *b) {
         seq += (size_t)L;
         per[form].push_back(rr);
     }
+    if (fm) if (int rc = dgrow(b, (void **)&f.dseq, &f.dseq_cap, (seq ? seq : 1) * sizeof(unsigned short), "remap from map: the sequences")) return rc;
     if (int rc = dgrow(b, (void **)&f.ws, &f.ws_cap, ws * 8, "remap: the traceback workspace")) return rc;
     return forms_upload(b, f, per, f.count, nR);
 }
 static void remap_launch(ffhip_batch *b, const int *tbr, ReadMap rmap) {           // from the transitions, whatever the path was decoded from
     ffhip_batch::Remap &f = b->rmp;
+    if (f.from_map) {                                       // every form's entries in one launch, behind k_map_finish (map's row stands ahead of remap's in kAnnots)
+        launch_map_remap_seq(b->stream, b->map.ref->view, b->map.rec.dev, (RemapRead *)f.list.dev, batch_nreads(b), f.dseq, b->mdl->nbase, b->Tb, tbr);
+        b->launches[5]++;
+    }
     forms_launch(b, f, f.count, [&](int form, size_t at, int n) {
         launch_remap(b->stream, form, (const RemapRead *)f.list.dev + at, n, f.dseq, b->trans, b->mdl->Ps, f.band, f.ws, f.rec.dev, f.rec.dev + remap_moves_at(b), b->Tb, tbr, rmap);
     });
@@ -290,7 +312,7 @@ static int events_prepare(ffhip_batch *b) {
     std::vector<EventRead> list;
     size_t at = 0;
     for (int r = 0; r < nR; r++) {
-        const int L = (int)b->rmp.seq[r].size();
+        const int L = remap_room(b, r);                      // (remap from map: room for N + 1 events; k_events writes the L of remap's record and leaves the rest alone)
         off[r] = at;
         if (!remap_mappable(b, r)) continue;
         list.push_back(EventRead{ signal_at(b, r, st), at, b->hT[r], L, r, 0 });
@@ -695,13 +717,13 @@ template <class T> static int seq_adopt(ffhip_batch *b, const std::vector<std::v
 int ffhip::remap_adopt(ffhip_batch *b, std::vector<std::vector<unsigned short>> &&seq, std::vector<signed char> &&state, int band) {
     if (int rc = seq_adopt(b, seq, &b->rmp.dseq, &b->rmp.dseq_cap, "remap: the sequences")) return rc;
     b->rmp.seq = std::move(seq); b->rmp.state = std::move(state);
-    b->rmp.band = band; b->rmp.set = 1;
+    b->rmp.band = band; b->rmp.set = 1; b->rmp.from_map = 0;
     b->var.set.clear();                                     // (variants are validated against the sequences: new sequences detach them)
     return FFHIP_OK;
 }
 extern "C" int ffhip_batch_set_remap(ffhip_batch *b, int nread, const uint8_t *const *codes, const size_t *len, int band) {
     if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (!codes) { b->rmp.set = 0; b->rmp.seq.clear(); b->rmp.state.clear(); b->var.set.clear(); return FFHIP_OK; }
+    if (!codes) { b->rmp.set = 0; b->rmp.from_map = 0; b->rmp.seq.clear(); b->rmp.state.clear(); b->var.set.clear(); return FFHIP_OK; }
     const ffhip_model *m = b->mdl;
     if (m->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "remap: a flip-flop model only (the run-length model's scores are not transitions between bases)");
     if (!len || nread != batch_nreads(b)) return set_err(FFHIP_EINVAL, "remap: sequences for %d reads, the batch holds %d", nread, batch_nreads(b));
@@ -719,6 +741,18 @@ extern "C" int ffhip_batch_set_remap(ffhip_batch *b, int nread, const uint8_t *c
         remap_code(codes[r], len[r], m->nbase, seq[r].data());
     }
     return remap_adopt(b, std::move(seq), std::move(state), band);
+}
+// remap from map (include/ffhip.h "remap from map"; the kernel: k_map_remap_seq, ffhip_map.hip)
+extern "C" int ffhip_batch_set_remap_from_map(ffhip_batch *b, int on, int band) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "remap from map: the batch is between a run and its finish");
+    if (!on) { b->rmp.from_map = 0; return FFHIP_OK; }
+    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "remap from map: a flip-flop model only (the run-length model's scores are not transitions between bases)");
+    if (band < 0 || 2 * band + 1 > remap_max_window())
+        return set_err(FFHIP_EINVAL, "remap from map: the band half-width is %d (0 .. %d: the widest kernel form holds a window of %d cells)", band, (remap_max_window() - 1) / 2, remap_max_window());
+    b->rmp.seq.clear(); b->rmp.state.clear(); b->var.set.clear();      // (the two ways of giving sequences replace each other; variants are validated against set ones)
+    b->rmp.set = 0; b->rmp.from_map = 1; b->rmp.band = band;
+    return FFHIP_OK;
 }
 // A mapped read's traceback ends at position 0; and the accessor of everything made from the mapping (events, site mods, variants: feature f): made in this run,
 // then the read's remap record, and its records in f -- or "nothing", which is the answer for a status other than 1
@@ -751,6 +785,7 @@ extern "C" int ffhip_batch_remap(const ffhip_batch *b, int read, ffhip_remap_cal
 extern "C" int ffhip_batch_events(const ffhip_batch *b, int read, const ffhip_event **ev, size_t *L) {
     int rec[4];
     if (int rc = mapped_records(b, read, &ffhip_batch::evt, "events were not made in this run (FFHIP_RUN_REMAP | FFHIP_RUN_EVENTS)", rec, ev, L)) return rc;
+    if (rec[0] == 1 && b->rmp.from_map && rec[1] >= 1 && (size_t)rec[1] <= *L) *L = (size_t)rec[1];      // (remap from map: what is held is the room, and the record's L the events)
     if (rec[0] != 1 || (size_t)rec[1] == *L) return FFHIP_OK;
     const size_t held = *L;
     *ev = nullptr; *L = 0;
@@ -1112,6 +1147,9 @@ extern "C" int ffhip_batch_truth(const ffhip_batch *b, int read, ffhip_truth_cal
 }
 
 extern "C" int ffhip_debug_remap_form(size_t L, int band) { return (L < 1 || L > ((size_t)1 << 30) || band < 0) ? -1 : remap_form((int)L, band); }
+extern "C" int ffhip_debug_remap_from_map_form(int nblock, int band) {      // the form a read of nblock blocks takes in the mode of remap from map: that of its room
+    return (nblock < 1 || nblock >= (1 << 30) || band < 0) ? -1 : remap_form(nblock + 1, band);
+}
 extern "C" int ffhip_debug_truth_form(size_t window) { return (window < 1 || window > ((size_t)1 << 30)) ? -1 : truth_form((long long)window); }
 
 // distances and end positions of every pattern of a kit at both ends of one call (k_barcodes; include/ffhip.h "barcodes")
@@ -1211,6 +1249,37 @@ extern "C" int ffhip_op_map_stretch(ffhip_engine *eng, const ffhip_map_ref *ref,
     HIP_TRY(hipMemcpyAsync(codes, d_seq, (size_t)m, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
     if (int rc = op_done(s)) return rc;
     if (got.status != 1 || got.m != m) return set_err(FFHIP_EHIP, "map stretch: the kernel left status %d and %d bases for a span of %d", got.status, got.m, m);
+    return FFHIP_OK;
+}
+
+// the coding of remap from map on one span from host arguments (k_map_remap_seq; include/ffhip.h "remap from map"): a record and a list entry made here, the
+// entry's room given as the blocks of a batch of one read.  *status and *L are what the kernel patched; out holds L entries when *status is 1 and is untouched otherwise
+extern "C" int ffhip_op_map_remap_code(ffhip_engine *eng, const ffhip_map_ref *ref, int q, int start, int end, int nbase, int room, uint16_t *out, int *status, size_t *L) {
+    OP_ENTER(eng);
+    if (!ref || ref->eng != eng || !out || !status || !L) return set_err(FFHIP_EINVAL, "bad map remap code arguments (a reference of this engine, an output of end - start entries, a status and a length)");
+    if (nbase != 4 && nbase != 5) return set_err(FFHIP_EINVAL, "map remap code: an alphabet of 4 or 5 bases, not %d", nbase);
+    if (room < 0 || room > (1 << 30)) return set_err(FFHIP_EINVAL, "map remap code: a room of 0 .. 2^30 positions, not %d", room);
+    if (int rc = span_check("map remap code", ref, q, start, end)) return rc;
+    const int m = end - start;
+    ffhip_map_call rec;
+    memset(&rec, 0, sizeof rec);
+    rec.status = 1; rec.nanchor = 1; rec.q = q; rec.tstart = start; rec.tend = end;
+    const RemapRead rr{ 0ull, 0u, 0, 1, 0 };
+    void *d_rec = tmp.upload(&rec, sizeof rec, s);
+    RemapRead *d_list = (RemapRead *)tmp.upload(&rr, sizeof rr, s);
+    unsigned short *d_seq = (unsigned short *)tmp.get((size_t)std::max(room, 1) * 2);
+    if (!d_rec || !d_list || !d_seq) OP_NOMEM();
+    launch_map_remap_seq(s, ref->view, d_rec, d_list, 1, d_seq, nbase, room - 1, nullptr);
+    RemapRead got;
+    HIP_TRY(hipMemcpyAsync(&got, d_list, sizeof got, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    if (int rc = op_done(s)) return rc;
+    if (got.L != m || (got.status != 1 && got.status != 2) || (got.status == 1) != (m <= room))
+        return set_err(FFHIP_EHIP, "map remap code: the kernel left status %d and %d bases for a span of %d in a room of %d", got.status, got.L, m, room);
+    if (got.status == 1) {
+        HIP_TRY(hipMemcpyAsync(out, d_seq, (size_t)m * 2, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+        if (int rc = op_done(s)) return rc;
+    }
+    *status = got.status; *L = (size_t)got.L;
     return FFHIP_OK;
 }
 

@@ -292,6 +292,10 @@ void launch_truth(hipStream_t s, int form, const TruthRead *list, int count, con
 // truth from map (k_map_stretch, ffhip_map.hip; include/ffhip.h "truth from map"): for each of `count` entries of truth's list with status 1, from the map record at
 // records[entry.read]: the stretch y_q[tstart : tend] as codes 0 .. 3 at seq + entry.seq, and entry.m and entry.status patched by the header's rule
 void launch_map_stretch(hipStream_t s, const MapRefView &ref, const void *records, TruthRead *list, int count, uint8_t *seq);
+// remap from map (k_map_remap_seq, ffhip_map.hip; include/ffhip.h "remap from map"): for each of `count` entries of remap's list with status 1, from the map record at
+// records[entry.read]: the stretch y_q[tstart : tend] as remap_code's entries (stay | move << 8, alphabet of nbase) at seq + entry.seq, and entry.L and entry.status
+// patched by the header's rule; an entry's room is the read's blocks (tbs[read], or Tb) + 1
+void launch_map_remap_seq(hipStream_t s, const MapRefView &ref, const void *records, RemapRead *list, int count, unsigned short *seq, int nbase, int Tb, const int *tbs);
 // pileup (k_pileup, ffhip_pileup.hip; include/ffhip.h "pileup"): for each of `count` entries of truth's list, from the map record at map_records[entry.read], the
 // truth record at truth_records[entry.read], the K op bytes right-aligned in the entry's cap bytes of `ops` and the call's letters, the read's counts added into the
 // 12 planes of P uint32 [strand][column][position] and the eight uint64 totals { reads, skipped, match, mismatch, del, ins, edge_ins, 0 }.  The entry's m and

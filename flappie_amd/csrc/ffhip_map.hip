@@ -20,6 +20,7 @@
 //   16-byte stores.
 // k_map_stretch (include/ffhip.h "truth from map"): one wave an entry of truth's read list, behind k_map_finish: the mapped read's stretch of the reference as codes
 //   where k_truth reads its truth, and the entry's length and status patched.  Its own comment stands in front of it.
+// k_map_remap_seq (include/ffhip.h "remap from map"): the same for an entry of remap's read list, the stretch in remap's flip-flop coding where k_remap reads its sequence.
 #include "ffhip_internal.hpp"
 #include "ffhip_seq.hpp"
 
@@ -236,6 +237,72 @@ k_map_stretch(MapRefView ref, const uint4 *__restrict__ rec, TruthRead *__restri
 void launch_map_stretch(hipStream_t s, const MapRefView &ref, const void *records, TruthRead *list, int count, uint8_t *seq) {
     if (count <= 0) return;
     hipLaunchKernelGGL(k_map_stretch, dim3(count), dim3(64), 0, s, ref, (const uint4 *)records, list, seq);
+}
+
+// k_map_remap_seq (include/ffhip.h "remap from map"): k_map_stretch's twin for remap, one wave an entry of remap's read list, all forms' entries in one launch, behind
+// k_map_finish and ahead of the k_remap launches.  A read whose map record says status 1 gets its stretch y_q[tstart : tend] in remap's coding at seq + entry.seq, m =
+// tend - tstart entries of 16 bits: stay (q_i -> q_i) | move (q_{i-1} -> q_i) << 8, byte for byte what remap_code makes on the host.  q_i = s_i + nbase * ((i -
+// runstart_i) & 1).  A lane takes one letter of 64 a pass.  One ballot of s_i != s_{i-1} marks the pass's run starts, and the highest mark at or below a lane is its
+// own; with no mark there the run began in an earlier pass, and its start comes with the carry (the last run start, letter and q of the pass before: the same in every
+// lane).  q_{i-1} is one cross-lane move, or the carry for lane 0.  Lane 0 then patches the entry's L and status, which k_remap reads.  The room of an entry is the
+// N + 1 positions a path of the read's N blocks can hold: m > room is status 2 with L = m and no entry written, as is a record that does not lie in its reference
+// record (L = 0); a read the map did not place is status 0.  An entry of status 0 (an empty slot) is left as it is.  Integers only, no atomics, no LDS.
+__global__ void __launch_bounds__(64)
+k_map_remap_seq(MapRefView ref, const uint4 *__restrict__ rec, RemapRead *__restrict__ list, unsigned short *__restrict__ seq, int nbase, int TbS, const int *__restrict__ tbs) {
+    FFHIP_DECODE_PRIO_SET();
+    const int lane = threadIdx.x;
+    RemapRead *e = list + blockIdx.x;
+    const RemapRead rr = *e;                             // (read whole before lane 0 patches it)
+    if (rr.status != 1) return;                          // an empty slot
+    const uint4 *r = rec + (size_t)rr.read * 4;
+    const uint4 r0 = r[0], r1 = r[1];
+    const int mstatus = (int)r0.x, q = (int)r0.w, ts = (int)r1.x, te = (int)r1.y;
+    const int N = tbs ? tbs[rr.read] : TbS;
+    const long long room = (long long)N + 1;
+    int status = 0, m = 0;
+    if (mstatus == 1) {
+        status = 2;
+        if (q >= 0 && q < 2 * ref.nrec) {
+            const int2 rc = ref.recs[q >> 1];                // { first letter, letters }
+            if (ts >= 0 && ts < te && te <= rc.y) {
+                m = te - ts;
+                if (m <= room) {
+                    status = 1;
+                    const int o = q & 1, dir = o ? -1 : 1;
+                    const long long g0 = o ? (long long)rc.x + rc.y - 1 - ts : (long long)rc.x + ts;      // the reference letter of y_q[tstart]
+                    unsigned short *out = seq + rr.seq;
+                    int c_start = 0, c_s = -1, c_q = 0;      // the carry: nothing stands in front of position 0
+                    for (int i0 = 0; i0 < m; i0 += 64) {     // (uniform over the wave)
+                        const int i = i0 + lane;
+                        const bool have = i < m;
+                        int s = 0;
+                        if (have) {
+                            const unsigned v = map_chunk(ref.words, g0 + (long long)dir * (i & ~15), dir, o);
+                            s = (int)((v >> (2 * (i & 15))) & 3u);
+                        }
+                        const int below = __shfl_up(s, 1, 64);
+                        const int sp = lane == 0 ? c_s : below;
+                        const unsigned long long marks = __ballot(have && s != sp);
+                        const unsigned long long mine = marks & (~0ull >> (63 - lane));      // the marks at or below this lane
+                        const int start = mine ? i0 + 63 - __clzll((long long)mine) : c_start;
+                        const int qi = s + nbase * ((i - start) & 1);
+                        const int qb = __shfl_up(qi, 1, 64);
+                        const int qp = lane == 0 ? c_q : qb;
+                        if (have) out[i] = (unsigned short)(ff_lookup(qi, qi, nbase) | ((i > 0 ? ff_lookup(qp, qi, nbase) : 0) << 8));
+                        c_start = marks ? i0 + 63 - __clzll((long long)marks) : c_start;      // (a full pass, or the last one: lane 63's letter is real wherever it is read)
+                        c_s = __shfl(s, 63, 64);
+                        c_q = __shfl(qi, 63, 64);
+                    }
+                }
+            }
+        }
+    }
+    if (lane == 0) { e->L = m; e->status = status; }
+}
+
+void launch_map_remap_seq(hipStream_t s, const MapRefView &ref, const void *records, RemapRead *list, int count, unsigned short *seq, int nbase, int Tb, const int *tbs) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_map_remap_seq, dim3(count), dim3(64), 0, s, ref, (const uint4 *)records, list, seq, nbase, Tb, tbs);
 }
 
 const char *map_invalid(int window, int max_error) {

@@ -141,6 +141,7 @@ static struct argp_option options[] = {
     {"map-max-error", 288, "permille", 0, "With --map: largest edit distance of an anchor, and largest difference between the span on the reference and the call's length, in thousandths of their lengths (0-500, default 250)"},
     {"map-records", 289, "recs.fa", 0, "With --map: for every mapped read a FASTA record of its own stretch of the reference in signal order (reverse-complemented for the - strand): the file --remap takes in a second run (--truth too, which --truth-from-map spares)"},
     {"truth-from-map", 290, 0, 0, "With --map and --truth-out: align every mapped read's call to its own stretch of the reference in the same run, on the GPU, as --truth would in a second run with the file of --map-records. acc.tsv gets one line per mapped read: the thirteen columns of --truth-out with the read's name as in hits.tsv, then record, strand, tstart and tend as in hits.tsv; the CIGAR stays in signal order. --truth-band applies; not with --truth. stdout, hits.tsv and recs.fa do not change"},
+    {"remap-from-map", 307, 0, 0, "With --map and --remap-out: map every mapped read's signal to its own stretch of the reference in the same run, on the GPU, as --remap would in a second run with the file of --map-records. map.tsv gets one line per mapped read: the columns of --remap-out with the read's name as in hits.tsv, then record, strand, tstart and tend as in hits.tsv; the starts stay in signal order. --remap-band and --remap-events apply (a base's letter is the reference's, turned to the read's strand), and --truth-from-map goes in the same run; not with --remap, --remap-mods or --remap-variants. stdout, hits.tsv, acc.tsv and every other file do not change"},
     {"map-sam", 291, "aln.sam", 0, "With --truth-from-map: the alignments as a SAM file with @SQ lines: one line per read with a call, in output order; a read that is mapped and aligned with FLAG 0 or 16, POS, the CIGAR (=XID) in forward-strand order, SEQ (Z written as C) and QUAL turned to the forward strand and NM:i; every other read unmapped (FLAG 4). SEQ is always the whole call: --reverse, --trim-barcodes, --trim-adapters and --split-reads do not alter it"},
     {"map-pileup", 292, "pileup.tsv", 0, "With --truth-from-map: per position of the reference, the aligned calls' counts, added up on the GPU over the whole run and written at its end: one line for every position of every record in reference order, no header: record, 0-based position, reference letter, depth (A, C, G, T and del of both strands), then A, C, G, T, del, ins of the + strand and of the - strand. An insertion stands at the position to its left on the forward strand; insertions before the first or behind the last aligned base are counted on stderr only (edge_ins). Inserted letters are not kept. The whole call counts: --reverse, --trim-barcodes, --trim-adapters and --split-reads do not alter it. stdout, hits.tsv, acc.tsv and aln.sam do not change"},
     {"map-pileup-min-identity", 293, "permille", 0, "With --map-pileup: count only reads whose alignment's identity, matches over matches + mismatches + insertions + deletions, is at least this many thousandths (0-1000, default 0); the others are counted as skipped"},
@@ -181,6 +182,7 @@ static struct argp_option options[] = {
     {"map-records", 289, "recs.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"truth-from-map", 290, 0, OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"map-sam", 291, "aln.sam", OPTION_HIDDEN, "(flappie's option: refused here)"},
+    {"remap-from-map", 307, 0, OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"barcodes", 25, "kit.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"adapters", 269, "kit.fa", OPTION_HIDDEN, "(flappie's option: refused here)"},
     {"adapter-max-dist", 270, "edits", OPTION_HIDDEN, "(flappie's option: refused here)"},
@@ -268,6 +270,8 @@ static char *map_path = NULL, *map_out_path = NULL, *map_recs_path = NULL;
 static bool map_opts = false;
 /* flappie: --truth-from-map and the file of --map-sam (runnie: seen, to be refused) */
 static bool tfm_on = false;
+/* flappie: --remap-from-map (runnie: seen, to be refused) */
+static bool rfm_on = false;
 static char *tfm_sam_path = NULL;
 /* flappie: the file of --map-pileup and --map-pileup-min-identity (-1: not given) (runnie: seen, to be refused) */
 static char *pu_path = NULL;
@@ -450,6 +454,7 @@ static error_t parse_arg(int key, char *arg, struct argp_state *state) {
     case 286: map_out_path = arg; map_opts = true; break;
     case 289: map_recs_path = arg; map_opts = true; break;
     case 290: tfm_on = true; break;
+    case 307: rfm_on = true; break;
     case 291: tfm_sam_path = arg; break;
     case 292: pu_path = arg; break;
     case 293: {
@@ -879,7 +884,7 @@ static FILE *ep_out = NULL;
  * records (FFHIP_RUN_POLYTAIL) */
 static unsigned run_flags(void) {
     return (args.viterbi_only ? FFHIP_RUN_VITERBI_ONLY : 0u) | (args.trace ? 0u : FFHIP_RUN_NO_TRACE) | ((args.modbase_tags || mm_dev) ? FFHIP_RUN_MOD_PROBS : 0u) | (mm_dev ? FFHIP_RUN_MOD_PILEUP : 0u) |
-           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (mp_dev ? FFHIP_RUN_MAP : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | (rm_refs ? FFHIP_RUN_REMAP : 0u) | ((tr_refs || tfm_on) ? FFHIP_RUN_TRUTH : 0u) | (pu_dev ? FFHIP_RUN_PILEUP : 0u) | (cs_dev ? FFHIP_RUN_CONSENSUS : 0u) | (ep_dev ? FFHIP_RUN_ERRPROFILE : 0u) |
+           (args.emit_moves ? FFHIP_RUN_MOVES : 0u) | (bc_dev ? FFHIP_RUN_BARCODES : 0u) | (ad_dev ? FFHIP_RUN_ADAPTERS : 0u) | (mp_dev ? FFHIP_RUN_MAP : 0u) | (pt_on ? FFHIP_RUN_POLYTAIL : 0u) | ((rm_refs || rfm_on) ? FFHIP_RUN_REMAP : 0u) | ((tr_refs || tfm_on) ? FFHIP_RUN_TRUTH : 0u) | (pu_dev ? FFHIP_RUN_PILEUP : 0u) | (cs_dev ? FFHIP_RUN_CONSENSUS : 0u) | (ep_dev ? FFHIP_RUN_ERRPROFILE : 0u) |
            (ev_out ? FFHIP_RUN_EVENTS : 0u) | (md_out ? FFHIP_RUN_REMAP_MODS : 0u) | (vr_out ? FFHIP_RUN_REMAP_VARIANTS : 0u);
 }
 /* --remap: every read's record, by its read id, then by its file's base name; a bad record goes as a sequence of no bases (status 2) */
@@ -946,6 +951,7 @@ static int batch_run(ffhip_batch *b, unsigned flags, item **its, int n) {
     if (rm_refs) { const int rc = batch_set_remap(b, its, n); if (rc) return rc; }
     if (tr_refs) { const int rc = batch_set_truth(b, its, n); if (rc) return rc; }
     if (tfm_on) { const int rc = ffhip_batch_set_truth_from_map(b, 1, args.truth_band); if (rc) return rc; }
+    if (rfm_on) { const int rc = ffhip_batch_set_remap_from_map(b, 1, args.remap_band); if (rc) return rc; }
     if (pu_dev) { const int rc = ffhip_batch_set_pileup(b, pu_dev); if (rc) return rc; }
     if (mm_dev) { const int rc = ffhip_batch_set_modpileup(b, mm_dev); if (rc) return rc; }
     if (cs_dev) { const int rc = ffhip_batch_set_consensus(b, cs_dev); if (rc) return rc; }
@@ -1234,7 +1240,7 @@ static void collect_batch(const struct ffhip_model *mdl, pending_batch *pb) {
             if (0 != ffhip_batch_polytail(b, i, &its[i]->pt)) warnx("%s", ffhip_last_error());
             else { its[i]->have_pt = 1; if (0 != flappie_polytail_count(&pt_sum, &its[i]->pt)) warnx("out of memory for the poly tail summary"); }
         }
-        if (rm_refs && its[i]->rm_ref >= 0) {                  /* the read's mapping to its sequence: the table's line is written with the read's record */
+        if ((rm_refs && its[i]->rm_ref >= 0) || rfm_on) {      /* the read's mapping to its sequence: the table's line is written with the read's record */
             ffhip_remap_call rc;
             if (0 != ffhip_batch_remap(b, i, &rc)) warnx("%s", ffhip_last_error());
             else {
@@ -1498,6 +1504,34 @@ static void chunk_finish(chunk_ctx *c, hid_t hdf5out) {
                             warnx("The variant calls of %s do not fit its sequence", it->filename);
                         else if (nv) { vr_count[0]++; vr_count[1] += nv; vr_done[it->rm_ref] = 1; }
                         free(var);
+                    }
+                }
+            }
+            if (rfm_on) {                                      /* --remap-from-map: a line a mapped read, with its place behind the mapping; its events */
+                const char *name = *uuid ? uuid : base;       /* (hits.tsv's name) */
+                int k = 0;
+                char o = '+';
+                long a = 0, e = 0;
+                if (!it->have_mp || !it->have_rm) warnx("No %s returned for %s", it->have_mp ? "mapping" : "map record", it->filename);
+                if (!it->have_mp || 1 != it->mp.status || !it->have_rm) rm_count[1]++;
+                else if (0 != flappie_map_forward(mp_ref, it->mp.q, it->mp.tstart, it->mp.tend, &k, &o, &a, &e)) warnx("The map record of %s does not fit the reference", it->filename);
+                else {
+                    const size_t L = (size_t)(e - a);
+                    const long dev = (1 == it->rm_status && it->rm_L != L) ? -1 :
+                        flappie_remap_write_placed_line(rm_out, name, it->rm_status, it->rm_nblock, it->mv_stride, it->res.rt.start, L, args.remap_band, it->rm, it->rm_score,
+                                                        mp_ref->name[k], o, a, e);
+                    if (dev < 0) warnx("The moves of %s do not fit its stretch of the reference", it->filename);
+                    if (1 == it->rm_status) { rm_count[0]++; if (dev == (long)args.remap_band) rm_count[3]++; } else rm_count[2]++;
+                    if (ev_out && 1 == it->rm_status && dev >= 0) {
+                        uint8_t *codes = malloc(L ? L : 1);  /* the stretch in signal order, from the letters --map-records writes */
+                        if (NULL == it->ev || NULL == codes) warnx("No events for %s", it->filename);
+                        else {
+                            const char *sq = mp_ref->seq[k];
+                            for (size_t i = 0; i < L; i++) { const int c = (int)(strchr("ACGT", '+' == o ? sq[a + (long)i] : sq[e - 1 - (long)i]) - "ACGT"); codes[i] = (uint8_t)('+' == o ? c : 3 - c); }
+                            write_events(ev_out, name, codes, "ACGTZ", it->res.rt.start, it->ev, L);
+                            ev_count[0]++; ev_count[1] += L;
+                        }
+                        free(codes);
                     }
                 }
             }
@@ -2285,6 +2319,7 @@ int main(int argc, char *argv[]) {
     if (args.remap) errx(EXIT_FAILURE, "--remap is flappie's: the run-length model's scores are not transitions between the bases of a sequence");
     if (args.truth) errx(EXIT_FAILURE, "--truth is flappie's: the run-length model's call is a list of runs");
     if (tfm_on || tfm_sam_path) errx(EXIT_FAILURE, "--truth-from-map and --map-sam are flappie's: the run-length model's call is a list of runs");
+    if (rfm_on) errx(EXIT_FAILURE, "--remap-from-map is flappie's: the run-length model's scores are not transitions between the bases of a sequence");
     if (pu_path || pu_min_identity >= 0) errx(EXIT_FAILURE, "--map-pileup and --map-pileup-min-identity are flappie's: the run-length model's call is a list of runs");
     if (mm_path || mm_hi >= 0 || mm_lo >= 0 || mm_min_identity >= 0 || mm_motif || mm_combine || mm_hist_path)
         errx(EXIT_FAILURE, "--map-mods and its --map-mods-* options are flappie's: the run-length model's call is a list of runs and it has no modified base");
@@ -2333,6 +2368,14 @@ int main(int argc, char *argv[]) {
     if (tfm_on && NULL != args.truth) errx(EXIT_FAILURE, "--truth-from-map does not go with --truth: a call is aligned to one truth, the file's record or the mapped stretch");
     if (tfm_on && NULL == args.truth_out) errx(EXIT_FAILURE, "--truth-from-map and --truth-out go together");
     if (tfm_sam_path && !tfm_on) errx(EXIT_FAILURE, "--map-sam goes with --truth-from-map");
+    /* --remap-from-map, which stands on --map too: the sequences are the mapped stretches, which only the device has when the run is made */
+    if (rfm_on && NULL == map_path) errx(EXIT_FAILURE, "--remap-from-map goes with --map: it maps a read's signal to the stretch --map placed its call on");
+    if (rfm_on && NULL != args.remap) errx(EXIT_FAILURE, "--remap-from-map does not go with --remap: a read's signal is mapped to one sequence, the file's record or the mapped stretch");
+    if (rfm_on && mods_path) errx(EXIT_FAILURE, "--remap-from-map does not go with --remap-mods: the sites are listed from sequences the host has before the run, and the mapped stretches are not known then");
+    if (rfm_on && (vars_path || vars_out_path || vars_opts))
+        errx(EXIT_FAILURE, "--remap-from-map does not go with --remap-variants: variants are given in the coordinates of a sequence the host has before the run, and the mapped stretches are not known then");
+    if (rfm_on && NULL == args.remap_out) errx(EXIT_FAILURE, "--remap-from-map and --remap-out go together");
+    if (rfm_on && ad_split) errx(EXIT_FAILURE, "--split-reads does not go with --remap-from-map: it describes the read as one molecule");
     if (pu_path && !tfm_on) errx(EXIT_FAILURE, "--map-pileup goes with --truth-from-map: it counts what the alignments say");
     if (pu_min_identity >= 0 && NULL == pu_path) errx(EXIT_FAILURE, "--map-pileup-min-identity goes with --map-pileup");
     /* --map-mods: likewise; the thresholds' defaults read p >= 0.8 and p < 0.2 of ml = floor(256 p) */
@@ -2363,9 +2406,9 @@ int main(int argc, char *argv[]) {
         if (map_recs_path && NULL == (mp_recs = fopen(map_recs_path, "w"))) errx(EXIT_FAILURE, "--map-records %s: cannot be written", map_recs_path);
     }
     /* --remap: likewise */
-    if ((NULL == args.remap) != (NULL == args.remap_out)) errx(EXIT_FAILURE, "--remap and --remap-out go together");
-    if (args.remap_band_set && NULL == args.remap) errx(EXIT_FAILURE, "--remap-band goes with --remap");
-    if (args.remap_events && NULL == args.remap) errx(EXIT_FAILURE, "--remap-events goes with --remap");
+    if (!rfm_on && (NULL == args.remap) != (NULL == args.remap_out)) errx(EXIT_FAILURE, "--remap and --remap-out go together");
+    if (args.remap_band_set && NULL == args.remap && !rfm_on) errx(EXIT_FAILURE, "--remap-band goes with --remap");
+    if (args.remap_events && NULL == args.remap && !rfm_on) errx(EXIT_FAILURE, "--remap-events goes with --remap");
     if (mods_path && NULL == args.remap) errx(EXIT_FAILURE, "--remap-mods goes with --remap");
     if ((mods_context_set || mods_all_paths) && NULL == mods_path) errx(EXIT_FAILURE, "--remap-mods-context and --remap-mods-all-paths go with --remap-mods");
     if (mods_path && !flappie_model_has_modbase(args.model))      /* (the registry knows: before any file or the GPU is touched) */
@@ -2391,6 +2434,10 @@ int main(int argc, char *argv[]) {
             if (NULL == (vr_done = calloc(rm_refs->n > 0 ? rm_refs->n : 1, 1))) errx(EXIT_FAILURE, "--remap-variants %s: out of memory", vars_path);
             if (NULL == (vr_out = fopen(vars_out_path, "w"))) errx(EXIT_FAILURE, "--remap-variants-out %s: cannot be written", vars_out_path);
         }
+    }
+    if (rfm_on) {
+        if (NULL == (rm_out = fopen(args.remap_out, "w"))) errx(EXIT_FAILURE, "--remap-out %s: cannot be written", args.remap_out);
+        if (args.remap_events && NULL == (ev_out = fopen(args.remap_events, "w"))) errx(EXIT_FAILURE, "--remap-events %s: cannot be written", args.remap_events);
     }
     /* --truth: likewise */
     if (!tfm_on && (NULL == args.truth) != (NULL == args.truth_out)) errx(EXIT_FAILURE, "--truth and --truth-out go together");
@@ -2622,7 +2669,7 @@ int main(int argc, char *argv[]) {
         flappie_polytail_summary_print(stderr, &pt_sum);
         flappie_polytail_summary_free(&pt_sum);
     }
-    if (rm_refs) {                     /* mapped, no record, refused, and the mapped reads whose path touched the band */
+    if (rm_refs || rfm_on) {           /* mapped, no record (--remap-from-map: not placed by the map), refused, and the mapped reads whose path touched the band */
         fprintf(stderr, "remap\tmapped\t%llu\nremap\tno_record\t%llu\nremap\trefused\t%llu\nremap\tband_touched\t%llu\n", rm_count[0], rm_count[1], rm_count[2], rm_count[3]);
         if (0 != fclose(rm_out)) warnx("--remap-out %s: write failed", args.remap_out);
         if (ev_out) {                  /* mapped reads written, and their bases */

@@ -1,5 +1,5 @@
 /*  flappie_remap.c -- the host side of flappie --remap (include/flappie_remap.h): the reader of the sequences, start[] and maxdev of a read's moves, the
- *  line of map.tsv.  The mapping is the GPU's (k_remap, FFHIP_RUN_REMAP).
+ *  line of map.tsv, and that line with the read's place on the reference behind it (flappie --remap-from-map).  The mapping is the GPU's (k_remap, FFHIP_RUN_REMAP).
  */
 #include <ctype.h>
 #include <stdlib.h>
@@ -147,16 +147,30 @@ int flappie_remap_starts(const uint8_t *rm, size_t nblock, size_t L, size_t *sta
     return 0;
 }
 
-long flappie_remap_write_line(FILE *out, const char *name, int status, size_t nblock, int stride, size_t trim_start, size_t L, int band, const uint8_t *rm, float score) {
+/* the columns of a line of map.tsv, without its end */
+static long write_fields(FILE *out, const char *name, int status, size_t nblock, int stride, size_t trim_start, size_t L, int band, const uint8_t *rm, float score) {
     if (1 != status) {
-        fprintf(out, "%s\t%d\t%zu\t%d\t%zu\t%zu\t%d\t*\t*\t*\n", name, status, nblock, stride, trim_start, L, band);
+        fprintf(out, "%s\t%d\t%zu\t%d\t%zu\t%zu\t%d\t*\t*\t*", name, status, nblock, stride, trim_start, L, band);
         return 0;
     }
     size_t *start = malloc((L ? L : 1) * sizeof(size_t)), maxdev = 0;
     if (NULL == start || 0 != flappie_remap_starts(rm, nblock, L, start, &maxdev)) { free(start); return -1; }
     fprintf(out, "%s\t%d\t%zu\t%d\t%zu\t%zu\t%d\t%zu\t%.9g\t", name, status, nblock, stride, trim_start, L, band, maxdev, (double)score);
     for (size_t i = 0; i < L; i++) fprintf(out, i ? ",%zu" : "%zu", start[i]);
-    fputc('\n', out);
     free(start);
     return (long)maxdev;
+}
+
+long flappie_remap_write_line(FILE *out, const char *name, int status, size_t nblock, int stride, size_t trim_start, size_t L, int band, const uint8_t *rm, float score) {
+    const long dev = write_fields(out, name, status, nblock, stride, trim_start, L, band, rm, score);
+    if (dev >= 0) fputc('\n', out);
+    return dev;
+}
+
+long flappie_remap_write_placed_line(FILE *out, const char *name, int status, size_t nblock, int stride, size_t trim_start, size_t L, int band, const uint8_t *rm, float score,
+                                     const char *record, char strand, long tstart, long tend) {
+    if (NULL == out || NULL == name || NULL == record || ('+' != strand && '-' != strand) || tstart < 0 || tend < tstart) return -1;
+    const long dev = write_fields(out, name, status, nblock, stride, trim_start, L, band, rm, score);
+    if (dev >= 0) fprintf(out, "\t%s\t%c\t%ld\t%ld\n", record, strand, tstart, tend);
+    return dev;
 }

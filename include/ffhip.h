@@ -584,6 +584,34 @@ int ffhip_batch_remap(const ffhip_batch *b, int read, ffhip_remap_call *out);
 int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint8_t *codes, size_t L, int band, uint8_t *rm /* nblock */, float *score);
 /* the kernel form a sequence of L bases takes at this band: 0, 1 one wave (windows up to 64, 256 cells), 2, 3 a workgroup (up to 1024, 4608 cells); -1: none */
 int ffhip_debug_remap_form(size_t L, int band);
+/* Remap from map: each read's signal mapped to the stretch of the reference its call was mapped to, in ONE run -- the map record is on the device when k_map_finish
+ * is done, the reference is resident as 2-bit codes and the transitions are where k_remap reads them, so nothing goes through the host (tests/mapremap_ref.py
+ * restates this).  The stretch of a map record is that of "truth from map" below: y_q[tstart : tend] as codes 0 .. 3, m = tend - tstart bases, in the orientation of
+ * the search q, which is signal order.  It is coded on the device by the flip-flop coding above, written without the recurrence:
+ *     q_i = s_i + nbase ((i - runstart_i) & 1), runstart_i the first position of the run of equal letters that i lies in.
+ *   The rule, for a read of N >= 1 blocks, room = N + 1 (a path needs L <= N + 1):
+ *     map status 1, 1 <= m <= room, the record inside its reference record:  remap status 1, L = m: the recursion under "remap" on the stretch
+ *     map status 1, m > room:                                                 remap status 2, L = m, nothing coded
+ *     map status 0, 2 or 3:                                                    remap status 0, L = 0 -- a read without a sequence under ffhip_batch_set_remap
+ *     (map status 1 with a record that does not lie in its reference record cannot occur; the kernel guards against it all the same: status 2, L = 0)
+ *   Sizing: the host knows N and not m.  A read's share of the coded sequences is room entries, its kernel form that of room positions at the band
+ *     (ffhip_debug_remap_from_map_form) and its workspace that form's at N blocks; with FFHIP_RUN_EVENTS it has room for room events, of which the L of its record
+ *     are written and returned.  The form is therefore at least as large as the one the real L would take; the recursion is defined to the bit, so the bytes do not
+ *     depend on the form.  The rooms of a batch's reads together must fit 32 bits (the list's offsets): otherwise FFHIP_EINVAL with a text.
+ *   Everything else -- band, recursion, traceback, record, moves, events -- is that of "remap" and "events" with s the stretch: a read's remap record, moves and
+ *     events are the same bytes as those of a second run given the stretch through ffhip_batch_set_remap with the same band.  That equality defines the feature.
+ * ffhip_batch_set_remap_from_map: on = 1: the batch's later runs with FFHIP_RUN_MAP | FFHIP_RUN_REMAP take each read's sequence from its map record
+ *   (k_map_remap_seq, one launch behind k_map_finish and ahead of k_remap, no copy and no wait); band 0 .. 2303 (any window of 2 band + 1 cells fits the widest kernel
+ *   form), otherwise FFHIP_EINVAL.  on = 0 leaves the mode.  It and ffhip_batch_set_remap replace each other: the later call wins.  The run-length model, or a call
+ *   between a run and its finish: FFHIP_EINVAL.  A run in this mode with FFHIP_RUN_REMAP but without FFHIP_RUN_MAP, or with no reference attached: FFHIP_EINVAL with a
+ *   text that says which.  FFHIP_RUN_REMAP_MODS and FFHIP_RUN_REMAP_VARIANTS in this mode: FFHIP_EINVAL -- their site and variant lists are built on the host from
+ *   sequences it does not have here.  ffhip_batch_remap and ffhip_batch_events are unchanged: L comes from the record.
+ * ffhip_op_map_remap_code: the coding kernel on ONE span from host arguments, for an entry of `room` positions: *status and *L as the rule patches them, and with
+ *   status 1 the end - start entries stay | move << 8 in out (untouched otherwise).  It refuses what ffhip_op_map_stretch refuses, and an nbase other than 4 or 5.
+ * ffhip_debug_remap_from_map_form: the form a read of nblock blocks takes in this mode, ffhip_debug_remap_form(nblock + 1, band); no engine, no device. */
+int ffhip_batch_set_remap_from_map(ffhip_batch *b, int on, int band);
+int ffhip_op_map_remap_code(ffhip_engine *eng, const ffhip_map_ref *ref, int q, int start, int end, int nbase, int room, uint16_t *out /* end - start */, int *status, size_t *L);
+int ffhip_debug_remap_from_map_form(int nblock, int band);
 /* Events: the signal under every base of a mapped read -- what resquiggle tables, eventalign and comparisons of two samples' levels start from.
  *   Inputs: the read's prepared signal x[0 .. n - 1], float32 -- exactly what the batch was given with any ffhip_batch_set_* call, i.e. what the first convolution
  *     reads; the model's stride (samples a block); the read's N blocks and its remap path rm[0 .. N - 1] with its L, remap status 1.

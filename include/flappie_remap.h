@@ -7,6 +7,7 @@
  *  first, then by its file's base name (with or without the extension).  Sequences are in SIGNAL order.
  *  map.tsv, one line per read that had a record, tab-separated:
  *    name  status  nblock  stride  trim_start  L  band  maxdev  score(%.9g)  start[0],start[1],...     (maxdev, score and start[] are * for status 2)
+ *  With --remap-from-map (a line per read the map placed, the sequence its stretch of the reference) four columns follow: record  strand  tstart  tend, as in hits.tsv.
  *  Base i starts at block start[i] (start[0] = 0, start[i] = 1 + the index of the i-th one of the moves), block b stands for samples
  *  [trim_start + b stride, ...); maxdev = max_b |p_b - c(b)| says whether the band was touched (maxdev = band).
  */
@@ -44,6 +45,11 @@ int flappie_remap_refs_find(const flappie_remap_refs *refs, const char *read_id,
 int flappie_remap_starts(const uint8_t *rm, size_t nblock, size_t L, size_t *start, size_t *maxdev);
 /* one line of map.tsv; rm may be NULL unless status is 1.  Returns maxdev (0 for the other statuses), -1 on moves that do not fit L */
 long flappie_remap_write_line(FILE *out, const char *name, int status, size_t nblock, int stride, size_t trim_start, size_t L, int band, const uint8_t *rm, float score);
+/* flappie --remap-from-map: the same line with the read's place behind it, as hits.tsv and acc.tsv have it: the record's name, the strand (+ or -) and the span
+ * [tstart, tend) on the record's forward strand.  The sequence is the mapped stretch in signal order, L = tend - tstart.  Same return; -1 too (nothing written) for
+ * a NULL argument, another strand or a span that is none */
+long flappie_remap_write_placed_line(FILE *out, const char *name, int status, size_t nblock, int stride, size_t trim_start, size_t L, int band, const uint8_t *rm, float score,
+                                     const char *record, char strand, long tstart, long tend);
 
 #ifdef __cplusplus
 }
