@@ -644,17 +644,36 @@ class MapRef:
             self.h = None
 
 
-class Pileup:
-    """Per-position counts over all the reads of all the batches it is attached to (ffhip_pileup, include/ffhip.h "pileup"): 12 planes [strand][A C G T del ins]
-    of P uint32 and eight uint64 totals on the device.  `min_identity` in per mille (0 .. 1000) is fixed here.  `ref` must outlive it, and it every batch it is attached to."""
+class _Pile:
+    """What the run-wide accumulators share: an object of the library `_name` (ffhip_<_name>_create, _reset, _free and, for one that counts by a reference's
+    positions, _positions), made from the arguments of create or FFHipError."""
+    _name, _by_position = None, True
 
-    def __init__(self, engine: Engine, ref: MapRef, min_identity: int = 0):
+    def _create(self, engine: Engine, *args):
         self.engine = engine
-        self.ref = ref
-        self.h = lib().ffhip_pileup_create(engine.h, ref.h, int(min_identity))
+        self.h = getattr(lib(), "ffhip_%s_create" % self._name)(engine.h, *args)
         if not self.h:
             raise FFHipError(lib().ffhip_last_error().decode())
-        self.positions = int(lib().ffhip_pileup_positions(self.h))
+        if self._by_position:
+            self.positions = int(getattr(lib(), "ffhip_%s_positions" % self._name)(self.h))
+
+    def reset(self):
+        _check(getattr(lib(), "ffhip_%s_reset" % self._name)(self.h))
+
+    def close(self):
+        if self.h:
+            getattr(lib(), "ffhip_%s_free" % self._name)(self.h)
+            self.h = None
+
+
+class Pileup(_Pile):
+    """Per-position counts over all the reads of all the batches it is attached to (ffhip_pileup, include/ffhip.h "pileup"): 12 planes [strand][A C G T del ins]
+    of P uint32 and eight uint64 totals on the device.  `min_identity` in per mille (0 .. 1000) is fixed here.  `ref` must outlive it, and it every batch it is attached to."""
+    _name = "pileup"
+
+    def __init__(self, engine: Engine, ref: MapRef, min_identity: int = 0):
+        self.ref = ref
+        self._create(engine, ref.h, int(min_identity))
 
     def download(self):
         """(counts uint32 [2][6][P], totals dict of PILEUP_TOTALS) once every accumulation enqueued by any batch is done (ffhip_pileup_download)"""
@@ -663,27 +682,16 @@ class Pileup:
         _check(lib().ffhip_pileup_download(self.h, counts.ctypes.data_as(C.POINTER(C.c_uint32)), tot.ctypes.data_as(C.POINTER(C.c_uint64))))
         return counts, {k: int(v) for k, v in zip(PILEUP_TOTALS, tot)}
 
-    def reset(self):
-        _check(lib().ffhip_pileup_reset(self.h))
 
-    def close(self):
-        if self.h:
-            lib().ffhip_pileup_free(self.h)
-            self.h = None
-
-
-class ModPileup:
+class ModPileup(_Pile):
     """Per reference C (- strand: G), how the aligned calls of all the batches it is attached to class their 5mC bytes (ffhip_modpileup, include/ffhip.h "mod pileup"):
     10 planes [strand][mod canon fail diff del] of P uint32, eight uint64 totals and a histogram of 256 uint64 on the device.  `min_identity` in per mille and the
     byte thresholds 0 <= lo < hi <= 255 (mod: ml >= hi, canon: ml <= lo) are fixed here.  `ref` must outlive it, and it every batch it is attached to."""
+    _name = "modpileup"
 
     def __init__(self, engine: Engine, ref: MapRef, min_identity: int = 0, lo: int = 50, hi: int = 205):
-        self.engine = engine
         self.ref = ref
-        self.h = lib().ffhip_modpileup_create(engine.h, ref.h, int(min_identity), int(lo), int(hi))
-        if not self.h:
-            raise FFHipError(lib().ffhip_last_error().decode())
-        self.positions = int(lib().ffhip_modpileup_positions(self.h))
+        self._create(engine, ref.h, int(min_identity), int(lo), int(hi))
 
     def download(self):
         """(counts uint32 [10][P], totals dict of MODPILEUP_TOTALS, hist uint64 [256]) once every accumulation enqueued by any batch is done (ffhip_modpileup_download)"""
@@ -694,27 +702,16 @@ class ModPileup:
         _check(lib().ffhip_modpileup_download(self.h, counts.ctypes.data_as(C.POINTER(C.c_uint32)), tot.ctypes.data_as(u64), hist.ctypes.data_as(u64)))
         return counts, {k: int(v) for k, v in zip(MODPILEUP_TOTALS, tot)}, hist
 
-    def reset(self):
-        _check(lib().ffhip_modpileup_reset(self.h))
 
-    def close(self):
-        if self.h:
-            lib().ffhip_modpileup_free(self.h)
-            self.h = None
-
-
-class Consensus:
+class Consensus(_Pile):
     """Per reference position, the forward letters, deletions and inserted letters of the aligned calls of all the batches it is attached to (ffhip_consensus,
     include/ffhip.h "consensus"): 37 planes of P uint32 -- A C G T del, then A C G T of each of 8 insertion columns -- and eight uint64 totals on the device, and the
     consensus called from them there.  `min_identity` in per mille (0 .. 1000) is fixed here.  `ref` must outlive it, and it every batch it is attached to."""
+    _name = "consensus"
 
     def __init__(self, engine: Engine, ref: MapRef, min_identity: int = 0):
-        self.engine = engine
         self.ref = ref
-        self.h = lib().ffhip_consensus_create(engine.h, ref.h, int(min_identity))
-        if not self.h:
-            raise FFHipError(lib().ffhip_last_error().decode())
-        self.positions = int(lib().ffhip_consensus_positions(self.h))
+        self._create(engine, ref.h, int(min_identity))
 
     def download(self):
         """(counts uint32 [37][P], totals dict of CONSENSUS_TOTALS) once every accumulation enqueued by any batch is done (ffhip_consensus_download)"""
@@ -729,25 +726,15 @@ class Consensus:
         _check(lib().ffhip_consensus_call(self.h, int(min_depth), cells.ctypes.data_as(C.c_void_p)))
         return cells
 
-    def reset(self):
-        _check(lib().ffhip_consensus_reset(self.h))
 
-    def close(self):
-        if self.h:
-            lib().ffhip_consensus_free(self.h)
-            self.h = None
-
-
-class ErrProfile:
+class ErrProfile(_Pile):
     """By class, what the aligned calls of all the batches it is attached to got right and wrong (ffhip_errprofile, include/ffhip.h "error profile"): the tables
     sub[4][5], ins[4], qual[94][3], ctx[1024][4], hp[4][16][33] and twelve totals, all uint64 on the device.  `min_identity` in per mille (0 .. 1000) is fixed here.
     It belongs to no reference, serves either truth mode, and must outlive every batch it is attached to."""
+    _name, _by_position = "errprofile", False
 
     def __init__(self, engine: Engine, min_identity: int = 0):
-        self.engine = engine
-        self.h = lib().ffhip_errprofile_create(engine.h, int(min_identity))
-        if not self.h:
-            raise FFHipError(lib().ffhip_last_error().decode())
+        self._create(engine, int(min_identity))
 
     def download(self):
         """(counts uint64 [ERRPROFILE_TABLE_WORDS], totals dict of ERRPROFILE_TOTALS) once every accumulation enqueued by any batch is done (ffhip_errprofile_download)"""
@@ -761,17 +748,9 @@ class ErrProfile:
         """the flat counts as views by section: sub, ins, qual, ctx, hp (ERRPROFILE_SECTIONS)"""
         return {name: counts[at:at + int(np.prod(shape))].reshape(shape) for name, at, shape in ERRPROFILE_SECTIONS}
 
-    def reset(self):
-        _check(lib().ffhip_errprofile_reset(self.h))
-
     def debug_groups(self, groups: int):
         """test hook (ffhip_debug_errprofile_groups): the most workgroups of the later launches; 0: the default"""
         _check(lib().ffhip_debug_errprofile_groups(self.h, int(groups)))
-
-    def close(self):
-        if self.h:
-            lib().ffhip_errprofile_free(self.h)
-            self.h = None
 
 
 def _adapter_record(header, hits) -> dict:

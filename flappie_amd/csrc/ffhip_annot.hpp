@@ -83,17 +83,14 @@ struct AnnotRow {
 };
 
 // ---- what ffhip_engine.hip asks of ffhip_features.hip: the table (ffhip_batch::AN_COUNT rows), the front's and the finish's share of all features and of the
-// pileup, and rerun_on_f32_path's way of handing its side batch the re-run reads' sequences and truths
+// run-wide accumulators, and rerun_on_f32_path's way of handing its side batch the re-run reads' sequences and truths
 FFHIP_LOCAL extern const AnnotRow kAnnots[];
 FFHIP_LOCAL int annots_prepare(ffhip_batch *b, unsigned flags);
 FFHIP_LOCAL int annots_copy_down(ffhip_batch *b);
-FFHIP_LOCAL int pileup_check(const ffhip_batch *b, unsigned flags);
+FFHIP_LOCAL int piles_check(const ffhip_batch *b, unsigned flags);
 FFHIP_LOCAL void pileup_launch(ffhip_batch *b);
-FFHIP_LOCAL int modpileup_check(const ffhip_batch *b, unsigned flags);
 FFHIP_LOCAL void modpileup_launch(ffhip_batch *b);
-FFHIP_LOCAL int consensus_check(const ffhip_batch *b, unsigned flags);
 FFHIP_LOCAL void consensus_launch(ffhip_batch *b);
-FFHIP_LOCAL int errprofile_check(const ffhip_batch *b, unsigned flags);
 FFHIP_LOCAL void errprofile_launch(ffhip_batch *b);
 FFHIP_LOCAL int remap_adopt(ffhip_batch *b, std::vector<std::vector<unsigned short>> &&seq, std::vector<signed char> &&state, int band);
 FFHIP_LOCAL int truth_adopt(ffhip_batch *b, std::vector<std::vector<uint8_t>> &&seq, std::vector<signed char> &&state, int band);

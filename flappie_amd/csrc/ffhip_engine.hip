@@ -57,7 +57,7 @@ extern "C" ffhip_engine *ffhip_engine_create(int device) {
         delete e;
         return nullptr;
     }
-    if (const char *ns = dbg("streams")) e->nstreams = atoi(ns) < 2 ? 2 : (atoi(ns) > 4 ? 4 : atoi(ns));
+    if (const char *ns = dbg("streams")) e->nstreams = atoi(ns) < 2 ? 2 : (atoi(ns) > kEngineStreams ? kEngineStreams : atoi(ns));
     for (int i = 0; i < e->nstreams; i++) HIP_TRY(hipStreamCreateWithFlags(&e->streams[i], hipStreamNonBlocking), (delete e, nullptr));
     HIP_TRY(hipStreamCreateWithFlags(&e->prep_stream, hipStreamNonBlocking), (delete e, nullptr));
     HIP_TRY(hipEventCreateWithFlags(&e->persist_done, hipEventDisableTiming), (delete e, nullptr));
@@ -301,7 +301,7 @@ extern "C" void ffhip_engine_destroy(ffhip_engine *e) {
     hipSetDevice(e->device);
     hipDeviceSynchronize();
     if (ffhip::pool_engine_gone(e->device)) ffhip::pool_trim(e->device);
-    for (int i = 0; i < 4; i++) if (e->streams[i]) hipStreamDestroy(e->streams[i]);
+    for (int i = 0; i < kEngineStreams; i++) if (e->streams[i]) hipStreamDestroy(e->streams[i]);
     if (e->prep_stream) hipStreamDestroy(e->prep_stream);
     if (e->prep_pin) hipHostFree(e->prep_pin);
     for (int i = 0; i < 5; i++) if (e->prep_scratch[i]) hipFree(e->prep_scratch[i]);
@@ -1319,10 +1319,7 @@ static int run_front(ffhip_batch *b, float temperature, unsigned flags, bool pai
         if (flags & FFHIP_RUN_NO_DECODE) return set_err(FFHIP_EINVAL, "%s", sec.undecoded_text);
         if (int rc = b->res.ensure((ResSec)i, b->stream)) return rc;
     }
-    if (int rc = pileup_check(b, flags)) return rc;        // (ahead of truth's own refusal of a run without the map: the text names the flag that asked)
-    if (int rc = modpileup_check(b, flags)) return rc;     // (likewise)
-    if (int rc = consensus_check(b, flags)) return rc;     // (likewise)
-    if (int rc = errprofile_check(b, flags)) return rc;    // (likewise)
+    if (int rc = piles_check(b, flags)) return rc;         // (ahead of truth's own refusal of a run without the map: the text names the flag that asked)
     if (int rc = annots_prepare(b, flags)) return rc;      // the products outside the block (kAnnots): may this run ask; their lists, workspaces and room
     if (b->packed && !p.packable)
         return set_err(FFHIP_EINVAL, "packed batches take the default path and the launch-per-step kernels only (flip-flop or run-length model with 128 .. 512 hidden units, no kept activations, no f32 / unfused flags, ordinary temperature)");

@@ -446,82 +446,65 @@ int ffhip::annots_prepare(ffhip_batch *b, unsigned flags) {
     }
     return FFHIP_OK;
 }
-template <class Pile> static void pileup_mark(Pile *p, const ffhip_batch *b) {      // work against it was enqueued on the batch's stream (pileup_wait)
-    for (int i = 0; i < b->eng->nstreams; i++) if (b->eng->streams[i] == b->stream) p->used[i] = true;
-}
-// Pileup (include/ffhip.h "pileup"): no record, no buffer of the batch's, so no row above.  The front's share: may this run ask
-int ffhip::pileup_check(const ffhip_batch *b, unsigned flags) {
-    if (!(flags & FFHIP_RUN_PILEUP)) return FFHIP_OK;
-    if (!(flags & FFHIP_RUN_TRUTH)) return set_err(FFHIP_EINVAL, "pileup: the run does not make the truth records (FFHIP_RUN_PILEUP goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH)");
-    if (!(flags & FFHIP_RUN_MAP)) return set_err(FFHIP_EINVAL, "pileup: the run does not make the map records (FFHIP_RUN_PILEUP goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH)");
-    if (!b->tru.from_map) return set_err(FFHIP_EINVAL, "pileup: the batch is not in the mode of truth from map (ffhip_batch_set_truth_from_map)");
-    if (!b->pile) return set_err(FFHIP_EINVAL, "pileup: no pileup is attached to the batch (ffhip_batch_set_pileup)");
-    if (b->pile->ref != b->map.ref) return set_err(FFHIP_EINVAL, "pileup: the attached pileup belongs to another reference than the batch's map reference");
+// ---- the run-wide accumulators (include/ffhip.h "pileup", "mod pileup", "consensus", "error profile"): no record, no buffer of the batch's, so no row above.
+// One row an accumulator.  The front's share: may this run ask -- the flag's companions in the order their refusals are reported, then the mode of truth from map
+// and the reference (the error profile serves either mode and belongs to no reference: it asks for the map in that mode only, and for the batch's engine)
+struct PileRow {
+    unsigned flag;
+    const char *name, *goes, *setter;
+    struct { unsigned flag; const char *makes; } with[3];
+    bool by_position;
+    const ffhip_pile *(*attached)(const ffhip_batch *);
+};
+static const PileRow kPiles[] = {
+    { FFHIP_RUN_PILEUP, "pileup", "(FFHIP_RUN_PILEUP goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH)", "ffhip_batch_set_pileup",
+      { { FFHIP_RUN_TRUTH, "truth records" }, { FFHIP_RUN_MAP, "map records" } }, true, [](const ffhip_batch *b) -> const ffhip_pile * { return b->pile; } },
+    { FFHIP_RUN_MOD_PILEUP, "mod pileup", "(FFHIP_RUN_MOD_PILEUP goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH | FFHIP_RUN_MOD_PROBS)", "ffhip_batch_set_modpileup",
+      { { FFHIP_RUN_MAP, "map records" }, { FFHIP_RUN_TRUTH, "truth records" }, { FFHIP_RUN_MOD_PROBS, "5mC probabilities" } }, true,
+      [](const ffhip_batch *b) -> const ffhip_pile * { return b->modpile; } },
+    { FFHIP_RUN_CONSENSUS, "consensus", "(FFHIP_RUN_CONSENSUS goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH)", "ffhip_batch_set_consensus",
+      { { FFHIP_RUN_TRUTH, "truth records" }, { FFHIP_RUN_MAP, "map records" } }, true, [](const ffhip_batch *b) -> const ffhip_pile * { return b->cons; } },
+    { FFHIP_RUN_ERRPROFILE, "error profile", "(FFHIP_RUN_ERRPROFILE goes with FFHIP_RUN_TRUTH)", "ffhip_batch_set_errprofile",
+      { { FFHIP_RUN_TRUTH, "truth records" } }, false, [](const ffhip_batch *b) -> const ffhip_pile * { return b->errp; } },
+};
+int ffhip::piles_check(const ffhip_batch *b, unsigned flags) {
+    for (const PileRow &row : kPiles) {
+        if (!(flags & row.flag)) continue;
+        for (const auto &w : row.with)
+            if (w.flag && !(flags & w.flag)) return set_err(FFHIP_EINVAL, "%s: the run does not make the %s %s", row.name, w.makes, row.goes);
+        if (!row.by_position && b->tru.from_map && !(flags & FFHIP_RUN_MAP))
+            return set_err(FFHIP_EINVAL, "%s: the run does not make the map records (in the mode of truth from map FFHIP_RUN_ERRPROFILE goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH)", row.name);
+        if (row.by_position && !b->tru.from_map) return set_err(FFHIP_EINVAL, "%s: the batch is not in the mode of truth from map (ffhip_batch_set_truth_from_map)", row.name);
+        const ffhip_pile *p = row.attached(b);
+        if (!p) return set_err(FFHIP_EINVAL, "%s: no %s is attached to the batch (%s)", row.name, row.name, row.setter);
+        if (row.by_position && p->ref != b->map.ref) return set_err(FFHIP_EINVAL, "%s: the attached %s belongs to another reference than the batch's map reference", row.name, row.name);
+        if (!row.by_position && p->eng != b->eng) return set_err(FFHIP_EINVAL, "%s: the attached %s belongs to another engine", row.name, row.name);
+    }
     return FFHIP_OK;
 }
 // ... and the finish's: the records, ops and letters are final (ffhip_batch_finish), so every listed read is counted once, on the batch's stream, unwaited for
-void ffhip::pileup_launch(ffhip_batch *b) {
-    ffhip_pileup *p = b->pile;
-    const ReadMap rmap = b->packed ? ReadMap{ b->d_vb0, b->d_vb1, b->nread } : ReadMap();
-    launch_pileup(b->stream, p->ref->view, (const TruthRead *)b->tru.list.dev, batch_nreads(b), b->map.rec.dev, (const int *)b->tru.rec.dev,
-                  b->tru.rec.dev + truth_ops_at(b), b->bases(), b->Tb, rmap, p->view);
-    pileup_mark(p, b);
+static PileArgs pile_args(const ffhip_batch *b) {
+    return { (const TruthRead *)b->tru.list.dev, batch_nreads(b), b->map.rec.dev, (const int *)b->tru.rec.dev, b->tru.rec.dev + truth_ops_at(b), b->bases(), b->Tb,
+             b->packed ? ReadMap{ b->d_vb0, b->d_vb1, b->nread } : ReadMap() };
 }
-// Mod pileup (include/ffhip.h "mod pileup"): the pileup's twin over the calls' 5mC bytes, with the same two shares
-int ffhip::modpileup_check(const ffhip_batch *b, unsigned flags) {
-    if (!(flags & FFHIP_RUN_MOD_PILEUP)) return FFHIP_OK;
-    static const char goes[] = "(FFHIP_RUN_MOD_PILEUP goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH | FFHIP_RUN_MOD_PROBS)";
-    if (!(flags & FFHIP_RUN_MAP)) return set_err(FFHIP_EINVAL, "mod pileup: the run does not make the map records %s", goes);
-    if (!(flags & FFHIP_RUN_TRUTH)) return set_err(FFHIP_EINVAL, "mod pileup: the run does not make the truth records %s", goes);
-    if (!(flags & FFHIP_RUN_MOD_PROBS)) return set_err(FFHIP_EINVAL, "mod pileup: the run does not make the 5mC probabilities %s", goes);
-    if (!b->tru.from_map) return set_err(FFHIP_EINVAL, "mod pileup: the batch is not in the mode of truth from map (ffhip_batch_set_truth_from_map)");
-    if (!b->modpile) return set_err(FFHIP_EINVAL, "mod pileup: no mod pileup is attached to the batch (ffhip_batch_set_modpileup)");
-    if (b->modpile->ref != b->map.ref) return set_err(FFHIP_EINVAL, "mod pileup: the attached mod pileup belongs to another reference than the batch's map reference");
-    return FFHIP_OK;
+static void pile_mark(ffhip_pile *p, const ffhip_batch *b) {     // work against it was enqueued on the batch's stream (pile_wait)
+    for (int i = 0; i < b->eng->nstreams; i++) if (b->eng->streams[i] == b->stream) p->used[i] = true;
+}
+void ffhip::pileup_launch(ffhip_batch *b) {
+    launch_pileup(b->stream, b->pile->ref->view, pile_args(b), b->pile->view);
+    pile_mark(b->pile, b);
 }
 void ffhip::modpileup_launch(ffhip_batch *b) {
-    ffhip_modpileup *p = b->modpile;
-    const ReadMap rmap = b->packed ? ReadMap{ b->d_vb0, b->d_vb1, b->nread } : ReadMap();
-    launch_modpileup(b->stream, p->ref->view, (const TruthRead *)b->tru.list.dev, batch_nreads(b), b->map.rec.dev, (const int *)b->tru.rec.dev,
-                     b->tru.rec.dev + truth_ops_at(b), b->bases(), b->res.on_dev<uint8_t>(RF_ML), b->Tb, rmap, p->view);
-    pileup_mark(p, b);
-}
-// Consensus (include/ffhip.h "consensus"): the pileup's second twin, which keeps the inserted letters, with the same two shares
-int ffhip::consensus_check(const ffhip_batch *b, unsigned flags) {
-    if (!(flags & FFHIP_RUN_CONSENSUS)) return FFHIP_OK;
-    static const char goes[] = "(FFHIP_RUN_CONSENSUS goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH)";
-    if (!(flags & FFHIP_RUN_TRUTH)) return set_err(FFHIP_EINVAL, "consensus: the run does not make the truth records %s", goes);
-    if (!(flags & FFHIP_RUN_MAP)) return set_err(FFHIP_EINVAL, "consensus: the run does not make the map records %s", goes);
-    if (!b->tru.from_map) return set_err(FFHIP_EINVAL, "consensus: the batch is not in the mode of truth from map (ffhip_batch_set_truth_from_map)");
-    if (!b->cons) return set_err(FFHIP_EINVAL, "consensus: no consensus is attached to the batch (ffhip_batch_set_consensus)");
-    if (b->cons->ref != b->map.ref) return set_err(FFHIP_EINVAL, "consensus: the attached consensus belongs to another reference than the batch's map reference");
-    return FFHIP_OK;
+    launch_modpileup(b->stream, b->modpile->ref->view, pile_args(b), b->res.on_dev<uint8_t>(RF_ML), b->modpile->view);
+    pile_mark(b->modpile, b);
 }
 void ffhip::consensus_launch(ffhip_batch *b) {
-    ffhip_consensus *c = b->cons;
-    const ReadMap rmap = b->packed ? ReadMap{ b->d_vb0, b->d_vb1, b->nread } : ReadMap();
-    launch_consensus(b->stream, c->ref->view, (const TruthRead *)b->tru.list.dev, batch_nreads(b), b->map.rec.dev, (const int *)b->tru.rec.dev,
-                     b->tru.rec.dev + truth_ops_at(b), b->bases(), b->Tb, rmap, c->view);
-    pileup_mark(c, b);
+    launch_consensus(b->stream, b->cons->ref->view, pile_args(b), b->cons->view);
+    pile_mark(b->cons, b);
 }
-// Error profile (include/ffhip.h "error profile"): their sibling by class, in either truth mode, with the same two shares.  It belongs to no reference: in the mode
-// of truth from map its launch takes the batch's own
-int ffhip::errprofile_check(const ffhip_batch *b, unsigned flags) {
-    if (!(flags & FFHIP_RUN_ERRPROFILE)) return FFHIP_OK;
-    if (!(flags & FFHIP_RUN_TRUTH)) return set_err(FFHIP_EINVAL, "error profile: the run does not make the truth records (FFHIP_RUN_ERRPROFILE goes with FFHIP_RUN_TRUTH)");
-    if (b->tru.from_map && !(flags & FFHIP_RUN_MAP))
-        return set_err(FFHIP_EINVAL, "error profile: the run does not make the map records (in the mode of truth from map FFHIP_RUN_ERRPROFILE goes with FFHIP_RUN_MAP | FFHIP_RUN_TRUTH)");
-    if (!b->errp) return set_err(FFHIP_EINVAL, "error profile: no error profile is attached to the batch (ffhip_batch_set_errprofile)");
-    if (b->errp->eng != b->eng) return set_err(FFHIP_EINVAL, "error profile: the attached error profile belongs to another engine");
-    return FFHIP_OK;
-}
-void ffhip::errprofile_launch(ffhip_batch *b) {
-    ffhip_errprofile *p = b->errp;
-    const ReadMap rmap = b->packed ? ReadMap{ b->d_vb0, b->d_vb1, b->nread } : ReadMap();
-    const bool fm = b->tru.from_map != 0;
-    launch_errprofile(b->stream, fm ? &b->map.ref->view : nullptr, (const TruthRead *)b->tru.list.dev, batch_nreads(b), p->groups, fm ? b->map.rec.dev : nullptr,
-                      (const int *)b->tru.rec.dev, b->tru.rec.dev + truth_ops_at(b), b->bases(), b->quals(), b->tru.dseq, b->Tb, rmap, p->view);
-    pileup_mark(p, b);
+void ffhip::errprofile_launch(ffhip_batch *b) {                  // (in the mode of truth from map it takes the batch's own reference)
+    launch_errprofile(b->stream, b->tru.from_map ? &b->map.ref->view : nullptr, pile_args(b), b->errp->groups, b->quals(), b->tru.dseq, b->errp->view);
+    pile_mark(b->errp, b);
 }
 // the copies of a finished run beside the block's: one a feature the run made, if it has a byte to bring
 int ffhip::annots_copy_down(ffhip_batch *b) {
@@ -874,160 +857,120 @@ extern "C" int ffhip_batch_set_truth_from_map(ffhip_batch *b, int on, int band) 
     b->tru.set = 0; b->tru.from_map = 1; b->tru.band = band;
     return FFHIP_OK;
 }
-// ---- pileup (include/ffhip.h "pileup"; the kernel: ffhip_pileup.hip)
-template <class Pile> static int pileup_wait(Pile *p) {  // every accumulation enqueued against it, by any batch, is done (the pileup and the mod pileup)
+// ---- the run-wide accumulators' objects (the kernels: ffhip_pileup, _modpileup, _consensus and _errprofile.hip).  What every one of them does alike:
+static int pile_wait(ffhip_pile *p) {                            // every accumulation enqueued against it, by any batch, is done
     hipSetDevice(p->eng->device);
     for (int i = 0; i < p->eng->nstreams; i++)
         if (p->used[i]) { HIP_TRY(hipStreamSynchronize(p->eng->streams[i]), FFHIP_EHIP); p->used[i] = false; }
     return FFHIP_OK;
 }
-template <class Pile> static int pileup_zero(Pile *p, int planes, int words) {      // the planes and the `words` uint64 behind view.totals
+static int pile_zero(ffhip_pile *p, void *a, size_t abytes, void *b, size_t bbytes) {      // its two allocations (b may be none)
     hipStream_t s = p->eng->streams[0];
-    HIP_TRY(hipMemsetAsync(p->view.counts, 0, (size_t)planes * p->view.P * 4, s), FFHIP_EHIP);
-    HIP_TRY(hipMemsetAsync(p->view.totals, 0, (size_t)words * 8, s), FFHIP_EHIP);
+    HIP_TRY(hipMemsetAsync(a, 0, abytes, s), FFHIP_EHIP);
+    if (b) HIP_TRY(hipMemsetAsync(b, 0, bbytes, s), FFHIP_EHIP);
     HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
     return FFHIP_OK;
 }
-static int pileup_zero(ffhip_pileup *p) { return pileup_zero(p, kPileupPlanes, kPileupTotals); }
-extern "C" ffhip_pileup *ffhip_pileup_create(ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity) {
-    if (!eng || !ref || ref->eng != eng) { set_err(FFHIP_EINVAL, "pileup: a reference of this engine"); return nullptr; }
-    if (min_identity > 1000) { set_err(FFHIP_EINVAL, "pileup: min_identity is %d per mille (0 .. 1000)", min_identity); return nullptr; }
+template <class Obj> static void pile_free(Obj *p, std::initializer_list<void **> bufs) {
+    pile_wait(p);
+    dev_free(bufs);
+    delete p;
+}
+// attaching one to a batch: `slot` of the batch takes it (nullptr: none).  acgtz: a model with the modified base, else any flip-flop model
+template <class Obj> static int pile_attach(ffhip_batch *b, Obj *p, Obj *ffhip_batch::*slot, const char *name, bool acgtz) {
+    if (!b) return set_err(FFHIP_EINVAL, "null batch");
+    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "%s: the batch is between a run and its finish", name);
+    if (!p) { b->*slot = nullptr; return FFHIP_OK; }
+    if (acgtz && (b->mdl->kind == FFHIP_NET_LSTM5_RLE || b->mdl->nbase != 5)) return set_err(FFHIP_EINVAL, "%s: the model has no modified base (a model of the alphabet ACGTZ)", name);
+    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "%s: a flip-flop model only (the run-length model's call is a list of runs)", name);
+    if (p->eng != b->eng) return set_err(FFHIP_EINVAL, "%s: the %s belongs to another engine", name, name);
+    b->*slot = p;
+    return FFHIP_OK;
+}
+// ... and the three that count by a reference's positions: `planes` planes of P uint32 and `words` uint64 behind view.totals
+struct PileKind { const char *name; int planes, words; };
+static const PileKind kPileupKind = { "pileup", kPileupPlanes, kPileupTotals }, kModPileupKind = { "mod pileup", kModPileupPlanes, kModPileupTotals + kModPileupBins },
+                      kConsensusKind = { "consensus", kConsensusPlanes, kConsensusTotals };
+static int pile_zero(ffhip_pile *p, const PileView &v, const PileKind &k) { return pile_zero(p, v.counts, (size_t)k.planes * v.P * 4, v.totals, (size_t)k.words * 8); }
+template <class Obj> static Obj *pile_create(const PileKind &k, ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity) {
+    if (!eng || !ref || ref->eng != eng) { set_err(FFHIP_EINVAL, "%s: a reference of this engine", k.name); return nullptr; }
+    if (min_identity > 1000) { set_err(FFHIP_EINVAL, "%s: min_identity is %d per mille (0 .. 1000)", k.name, min_identity); return nullptr; }
     hipSetDevice(eng->device);
-    ffhip_pileup *p = new ffhip_pileup();
+    Obj *p = new Obj();
     p->eng = eng; p->ref = ref;
     size_t P = 0;
     for (int m : ref->rec_len) P += (size_t)m;
     p->view.P = P; p->view.min_identity = min_identity < 0 ? 0 : min_identity;
-    const size_t bytes = (size_t)kPileupPlanes * P * 4;
-    if (dev_fill("pileup", { { (void **)&p->view.counts, nullptr, bytes }, { (void **)&p->view.totals, nullptr, (size_t)kPileupTotals * 8 } })) {
-        set_err(FFHIP_ENOMEM, "pileup: the counters take %zu bytes of device memory, which could not be had", bytes + (size_t)kPileupTotals * 8);
+    const size_t bytes = (size_t)k.planes * P * 4, words = (size_t)k.words * 8;
+    if (dev_fill(k.name, { { (void **)&p->view.counts, nullptr, bytes }, { (void **)&p->view.totals, nullptr, words } })) {
+        set_err(FFHIP_ENOMEM, "%s: the counters take %zu bytes of device memory, which could not be had", k.name, bytes + words);
         delete p;
         return nullptr;
     }
-    if (pileup_zero(p) != FFHIP_OK) { ffhip_pileup_free(p); return nullptr; }
+    if (pile_zero(p, p->view, k) != FFHIP_OK) { pile_free(p, { (void **)&p->view.counts, (void **)&p->view.totals }); return nullptr; }
     return p;
 }
-extern "C" void ffhip_pileup_free(ffhip_pileup *p) {
-    if (!p) return;
-    pileup_wait(p);
-    dev_free({ (void **)&p->view.counts, (void **)&p->view.totals });
-    delete p;
+// the planes and the first uint64 behind view.totals, once every accumulation is done
+static int pile_download(ffhip_pile *p, const PileView &v, const PileKind &k, uint32_t *counts, void *totals, size_t totals_bytes) {
+    if (int rc = pile_wait(p)) return rc;
+    if (counts) HIP_TRY(hipMemcpy(counts, v.counts, (size_t)k.planes * v.P * 4, hipMemcpyDeviceToHost), FFHIP_EHIP);
+    if (totals) HIP_TRY(hipMemcpy(totals, v.totals, totals_bytes, hipMemcpyDeviceToHost), FFHIP_EHIP);
+    return FFHIP_OK;
 }
+// ---- pileup (include/ffhip.h "pileup"; the kernel: ffhip_pileup.hip)
+extern "C" ffhip_pileup *ffhip_pileup_create(ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity) { return pile_create<ffhip_pileup>(kPileupKind, eng, ref, min_identity); }
+extern "C" void ffhip_pileup_free(ffhip_pileup *p) { if (p) pile_free(p, { (void **)&p->view.counts, (void **)&p->view.totals }); }
 extern "C" int ffhip_pileup_reset(ffhip_pileup *p) {
     if (!p) return set_err(FFHIP_EINVAL, "null pileup");
-    if (int rc = pileup_wait(p)) return rc;
-    return pileup_zero(p);
+    if (int rc = pile_wait(p)) return rc;
+    return pile_zero(p, p->view, kPileupKind);
 }
 extern "C" size_t ffhip_pileup_positions(const ffhip_pileup *p) { return p ? p->view.P : 0; }
 extern "C" int ffhip_pileup_download(ffhip_pileup *p, uint32_t *counts, ffhip_pileup_totals *totals) {
     if (!p) return set_err(FFHIP_EINVAL, "null pileup");
     static_assert(sizeof(ffhip_pileup_totals) == kPileupTotals * 8, "the totals come down as they stand");
-    if (int rc = pileup_wait(p)) return rc;
-    if (counts) HIP_TRY(hipMemcpy(counts, p->view.counts, (size_t)kPileupPlanes * p->view.P * 4, hipMemcpyDeviceToHost), FFHIP_EHIP);
-    if (totals) HIP_TRY(hipMemcpy(totals, p->view.totals, sizeof *totals, hipMemcpyDeviceToHost), FFHIP_EHIP);
-    return FFHIP_OK;
+    return pile_download(p, p->view, kPileupKind, counts, totals, sizeof *totals);
 }
-extern "C" int ffhip_batch_set_pileup(ffhip_batch *b, ffhip_pileup *p) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "pileup: the batch is between a run and its finish");
-    if (!p) { b->pile = nullptr; return FFHIP_OK; }
-    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "pileup: a flip-flop model only (the run-length model's call is a list of runs)");
-    if (p->eng != b->eng) return set_err(FFHIP_EINVAL, "pileup: the pileup belongs to another engine");
-    b->pile = p;
-    return FFHIP_OK;
-}
+extern "C" int ffhip_batch_set_pileup(ffhip_batch *b, ffhip_pileup *p) { return pile_attach(b, p, &ffhip_batch::pile, "pileup", false); }
 // ---- mod pileup (include/ffhip.h "mod pileup"; the kernel: ffhip_modpileup.hip): the totals and the histogram are one allocation, view.hist behind view.totals
-static int modpileup_zero(ffhip_modpileup *p) { return pileup_zero(p, kModPileupPlanes, kModPileupTotals + kModPileupBins); }
 extern "C" ffhip_modpileup *ffhip_modpileup_create(ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity, int lo, int hi) {
-    if (!eng || !ref || ref->eng != eng) { set_err(FFHIP_EINVAL, "mod pileup: a reference of this engine"); return nullptr; }
-    if (min_identity > 1000) { set_err(FFHIP_EINVAL, "mod pileup: min_identity is %d per mille (0 .. 1000)", min_identity); return nullptr; }
-    if (lo < 0 || lo >= hi || hi > 255) { set_err(FFHIP_EINVAL, "mod pileup: the thresholds are lo %d and hi %d (0 <= lo < hi <= 255)", lo, hi); return nullptr; }
-    hipSetDevice(eng->device);
-    ffhip_modpileup *p = new ffhip_modpileup();
-    p->eng = eng; p->ref = ref;
-    size_t P = 0;
-    for (int m : ref->rec_len) P += (size_t)m;
-    p->view.P = P; p->view.min_identity = min_identity < 0 ? 0 : min_identity; p->view.lo = lo; p->view.hi = hi;
-    const size_t bytes = (size_t)kModPileupPlanes * P * 4, words = (size_t)(kModPileupTotals + kModPileupBins) * 8;
-    if (dev_fill("mod pileup", { { (void **)&p->view.counts, nullptr, bytes }, { (void **)&p->view.totals, nullptr, words } })) {
-        set_err(FFHIP_ENOMEM, "mod pileup: the counters take %zu bytes of device memory, which could not be had", bytes + words);
-        delete p;
+    if (eng && ref && ref->eng == eng && min_identity <= 1000 && (lo < 0 || lo >= hi || hi > 255)) {      // (behind the refusals that pile_create words)
+        set_err(FFHIP_EINVAL, "mod pileup: the thresholds are lo %d and hi %d (0 <= lo < hi <= 255)", lo, hi);
         return nullptr;
     }
-    p->view.hist = p->view.totals + kModPileupTotals;
-    if (modpileup_zero(p) != FFHIP_OK) { ffhip_modpileup_free(p); return nullptr; }
+    ffhip_modpileup *p = pile_create<ffhip_modpileup>(kModPileupKind, eng, ref, min_identity);
+    if (p) { p->view.lo = lo; p->view.hi = hi; p->view.hist = p->view.totals + kModPileupTotals; }
     return p;
 }
-extern "C" void ffhip_modpileup_free(ffhip_modpileup *p) {
-    if (!p) return;
-    pileup_wait(p);
-    dev_free({ (void **)&p->view.counts, (void **)&p->view.totals });
-    delete p;
-}
+extern "C" void ffhip_modpileup_free(ffhip_modpileup *p) { if (p) pile_free(p, { (void **)&p->view.counts, (void **)&p->view.totals }); }
 extern "C" int ffhip_modpileup_reset(ffhip_modpileup *p) {
     if (!p) return set_err(FFHIP_EINVAL, "null mod pileup");
-    if (int rc = pileup_wait(p)) return rc;
-    return modpileup_zero(p);
+    if (int rc = pile_wait(p)) return rc;
+    return pile_zero(p, p->view, kModPileupKind);
 }
 extern "C" size_t ffhip_modpileup_positions(const ffhip_modpileup *p) { return p ? p->view.P : 0; }
 extern "C" int ffhip_modpileup_download(ffhip_modpileup *p, uint32_t *counts, ffhip_modpileup_totals *totals, uint64_t *hist) {
     if (!p) return set_err(FFHIP_EINVAL, "null mod pileup");
     static_assert(sizeof(ffhip_modpileup_totals) == kModPileupTotals * 8 && FFHIP_MODPILEUP_PLANES == kModPileupPlanes, "the totals come down as they stand");
-    if (int rc = pileup_wait(p)) return rc;
-    if (counts) HIP_TRY(hipMemcpy(counts, p->view.counts, (size_t)kModPileupPlanes * p->view.P * 4, hipMemcpyDeviceToHost), FFHIP_EHIP);
-    if (totals) HIP_TRY(hipMemcpy(totals, p->view.totals, sizeof *totals, hipMemcpyDeviceToHost), FFHIP_EHIP);
+    if (int rc = pile_download(p, p->view, kModPileupKind, counts, totals, sizeof *totals)) return rc;
     if (hist) HIP_TRY(hipMemcpy(hist, p->view.hist, (size_t)kModPileupBins * 8, hipMemcpyDeviceToHost), FFHIP_EHIP);
     return FFHIP_OK;
 }
-extern "C" int ffhip_batch_set_modpileup(ffhip_batch *b, ffhip_modpileup *p) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "mod pileup: the batch is between a run and its finish");
-    if (!p) { b->modpile = nullptr; return FFHIP_OK; }
-    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE || b->mdl->nbase != 5) return set_err(FFHIP_EINVAL, "mod pileup: the model has no modified base (a model of the alphabet ACGTZ)");
-    if (p->eng != b->eng) return set_err(FFHIP_EINVAL, "mod pileup: the mod pileup belongs to another engine");
-    b->modpile = p;
-    return FFHIP_OK;
-}
+extern "C" int ffhip_batch_set_modpileup(ffhip_batch *b, ffhip_modpileup *p) { return pile_attach(b, p, &ffhip_batch::modpile, "mod pileup", true); }
 // ---- consensus (include/ffhip.h "consensus"; the kernels: ffhip_consensus.hip)
-static int consensus_zero(ffhip_consensus *c) { return pileup_zero(c, kConsensusPlanes, kConsensusTotals); }
-extern "C" ffhip_consensus *ffhip_consensus_create(ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity) {
-    if (!eng || !ref || ref->eng != eng) { set_err(FFHIP_EINVAL, "consensus: a reference of this engine"); return nullptr; }
-    if (min_identity > 1000) { set_err(FFHIP_EINVAL, "consensus: min_identity is %d per mille (0 .. 1000)", min_identity); return nullptr; }
-    hipSetDevice(eng->device);
-    ffhip_consensus *c = new ffhip_consensus();
-    c->eng = eng; c->ref = ref;
-    size_t P = 0;
-    for (int m : ref->rec_len) P += (size_t)m;
-    c->view.P = P; c->view.min_identity = min_identity < 0 ? 0 : min_identity;
-    const size_t bytes = (size_t)kConsensusPlanes * P * 4;
-    if (dev_fill("consensus", { { (void **)&c->view.counts, nullptr, bytes }, { (void **)&c->view.totals, nullptr, (size_t)kConsensusTotals * 8 } })) {
-        set_err(FFHIP_ENOMEM, "consensus: the counters take %zu bytes of device memory, which could not be had", bytes + (size_t)kConsensusTotals * 8);
-        delete c;
-        return nullptr;
-    }
-    if (consensus_zero(c) != FFHIP_OK) { ffhip_consensus_free(c); return nullptr; }
-    return c;
-}
-extern "C" void ffhip_consensus_free(ffhip_consensus *c) {
-    if (!c) return;
-    pileup_wait(c);
-    dev_free({ (void **)&c->view.counts, (void **)&c->view.totals });
-    delete c;
-}
+extern "C" ffhip_consensus *ffhip_consensus_create(ffhip_engine *eng, const ffhip_map_ref *ref, int min_identity) { return pile_create<ffhip_consensus>(kConsensusKind, eng, ref, min_identity); }
+extern "C" void ffhip_consensus_free(ffhip_consensus *c) { if (c) pile_free(c, { (void **)&c->view.counts, (void **)&c->view.totals }); }
 extern "C" int ffhip_consensus_reset(ffhip_consensus *c) {
     if (!c) return set_err(FFHIP_EINVAL, "null consensus");
-    if (int rc = pileup_wait(c)) return rc;
-    return consensus_zero(c);
+    if (int rc = pile_wait(c)) return rc;
+    return pile_zero(c, c->view, kConsensusKind);
 }
 extern "C" size_t ffhip_consensus_positions(const ffhip_consensus *c) { return c ? c->view.P : 0; }
 extern "C" int ffhip_consensus_download(ffhip_consensus *c, uint32_t *counts, ffhip_consensus_totals *totals) {
     if (!c) return set_err(FFHIP_EINVAL, "null consensus");
     static_assert(sizeof(ffhip_consensus_totals) == kConsensusTotals * 8 && FFHIP_CONSENSUS_PLANES == kConsensusPlanes && FFHIP_CONSENSUS_MINOR == kConsensusMinor,
                   "the totals come down as they stand");
-    if (int rc = pileup_wait(c)) return rc;
-    if (counts) HIP_TRY(hipMemcpy(counts, c->view.counts, (size_t)kConsensusPlanes * c->view.P * 4, hipMemcpyDeviceToHost), FFHIP_EHIP);
-    if (totals) HIP_TRY(hipMemcpy(totals, c->view.totals, sizeof *totals, hipMemcpyDeviceToHost), FFHIP_EHIP);
-    return FFHIP_OK;
+    return pile_download(c, c->view, kConsensusKind, counts, totals, sizeof *totals);
 }
 // the call: one launch over the planes as they stand, the cells through a buffer that lives for the call
 extern "C" int ffhip_consensus_call(ffhip_consensus *c, int min_depth, ffhip_consensus_cell *cells) {
@@ -1036,7 +979,7 @@ extern "C" int ffhip_consensus_call(ffhip_consensus *c, int min_depth, ffhip_con
     static_assert(FFHIP_CONSENSUS_LOW == kConsensusLow && FFHIP_CONSENSUS_SAME == kConsensusSame && FFHIP_CONSENSUS_SUB == kConsensusSub &&
                   FFHIP_CONSENSUS_DEL == kConsensusDel && FFHIP_CONSENSUS_INS == kConsensusIns, "the kernel's codes are the header's");
     if (min_depth < 1) return set_err(FFHIP_EINVAL, "consensus: min_depth is %d (1 or more: a position nobody covers has no winner)", min_depth);
-    if (int rc = pileup_wait(c)) return rc;
+    if (int rc = pile_wait(c)) return rc;
     const size_t bytes = c->view.P * sizeof *cells;
     void *d_cells = nullptr;
     if (dev_fill("consensus cells", { { &d_cells, nullptr, bytes } })) return set_err(FFHIP_ENOMEM, "consensus: the cells take %zu bytes of device memory, which could not be had", bytes);
@@ -1050,22 +993,8 @@ extern "C" int ffhip_consensus_call(ffhip_consensus *c, int min_depth, ffhip_con
     HIP_TRY(e2, FFHIP_EHIP);
     return FFHIP_OK;
 }
-extern "C" int ffhip_batch_set_consensus(ffhip_batch *b, ffhip_consensus *c) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "consensus: the batch is between a run and its finish");
-    if (!c) { b->cons = nullptr; return FFHIP_OK; }
-    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "consensus: a flip-flop model only (the run-length model's call is a list of runs)");
-    if (c->eng != b->eng) return set_err(FFHIP_EINVAL, "consensus: the consensus belongs to another engine");
-    b->cons = c;
-    return FFHIP_OK;
-}
-// ---- error profile (include/ffhip.h "error profile"; the kernel: ffhip_errprofile.hip)
-static int errprofile_zero(ffhip_errprofile *p) {
-    hipStream_t s = p->eng->streams[0];
-    HIP_TRY(hipMemsetAsync(p->view.counts, 0, (size_t)kErrWords * 8, s), FFHIP_EHIP);
-    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    return FFHIP_OK;
-}
+extern "C" int ffhip_batch_set_consensus(ffhip_batch *b, ffhip_consensus *c) { return pile_attach(b, c, &ffhip_batch::cons, "consensus", false); }
+// ---- error profile (include/ffhip.h "error profile"; the kernel: ffhip_errprofile.hip): one allocation, by class and of no reference
 extern "C" ffhip_errprofile *ffhip_errprofile_create(ffhip_engine *eng, int min_identity) {
     if (!eng) { set_err(FFHIP_EINVAL, "error profile: an engine"); return nullptr; }
     if (min_identity > 1000) { set_err(FFHIP_EINVAL, "error profile: min_identity is %d per mille (0 .. 1000)", min_identity); return nullptr; }
@@ -1079,19 +1008,14 @@ extern "C" ffhip_errprofile *ffhip_errprofile_create(ffhip_engine *eng, int min_
         delete p;
         return nullptr;
     }
-    if (errprofile_zero(p) != FFHIP_OK) { ffhip_errprofile_free(p); return nullptr; }
+    if (ffhip_errprofile_reset(p) != FFHIP_OK) { ffhip_errprofile_free(p); return nullptr; }
     return p;
 }
-extern "C" void ffhip_errprofile_free(ffhip_errprofile *p) {
-    if (!p) return;
-    pileup_wait(p);
-    dev_free({ (void **)&p->view.counts });
-    delete p;
-}
+extern "C" void ffhip_errprofile_free(ffhip_errprofile *p) { if (p) pile_free(p, { (void **)&p->view.counts }); }
 extern "C" int ffhip_errprofile_reset(ffhip_errprofile *p) {
     if (!p) return set_err(FFHIP_EINVAL, "null error profile");
-    if (int rc = pileup_wait(p)) return rc;
-    return errprofile_zero(p);
+    if (int rc = pile_wait(p)) return rc;
+    return pile_zero(p, p->view.counts, (size_t)kErrWords * 8, nullptr, 0);
 }
 extern "C" size_t ffhip_errprofile_words(void) { return (size_t)kErrWords; }
 extern "C" int ffhip_errprofile_download(ffhip_errprofile *p, uint64_t *counts, ffhip_errprofile_totals *totals) {
@@ -1100,20 +1024,12 @@ extern "C" int ffhip_errprofile_download(ffhip_errprofile *p, uint64_t *counts, 
                   FFHIP_ERRPROFILE_SUB == kErrAtSub && FFHIP_ERRPROFILE_INS == kErrAtIns && FFHIP_ERRPROFILE_QUAL == kErrAtQual && FFHIP_ERRPROFILE_CTX == kErrAtCtx &&
                   FFHIP_ERRPROFILE_HP == kErrAtHp && FFHIP_ERRPROFILE_HP_MAX_RUN == kErrHpMaxRun && FFHIP_ERRPROFILE_HP_MAX_CALLED == kErrHpMaxCalled &&
                   FFHIP_ERRPROFILE_HP_MAX_OPS == kErrHpMaxOps, "the counters come down as they stand, in the header's sections");
-    if (int rc = pileup_wait(p)) return rc;
+    if (int rc = pile_wait(p)) return rc;
     if (counts) HIP_TRY(hipMemcpy(counts, p->view.counts, (size_t)kErrTableWords * 8, hipMemcpyDeviceToHost), FFHIP_EHIP);
     if (totals) HIP_TRY(hipMemcpy(totals, p->view.counts + kErrTableWords, sizeof *totals, hipMemcpyDeviceToHost), FFHIP_EHIP);
     return FFHIP_OK;
 }
-extern "C" int ffhip_batch_set_errprofile(ffhip_batch *b, ffhip_errprofile *p) {
-    if (!b) return set_err(FFHIP_EINVAL, "null batch");
-    if (b->ran && !b->finished) return set_err(FFHIP_EINVAL, "error profile: the batch is between a run and its finish");
-    if (!p) { b->errp = nullptr; return FFHIP_OK; }
-    if (b->mdl->kind == FFHIP_NET_LSTM5_RLE) return set_err(FFHIP_EINVAL, "error profile: a flip-flop model only (the run-length model's call is a list of runs)");
-    if (p->eng != b->eng) return set_err(FFHIP_EINVAL, "error profile: the error profile belongs to another engine");
-    b->errp = p;
-    return FFHIP_OK;
-}
+extern "C" int ffhip_batch_set_errprofile(ffhip_batch *b, ffhip_errprofile *p) { return pile_attach(b, p, &ffhip_batch::errp, "error profile", false); }
 // test hook: the most workgroups of the object's later launches (0: the engine's compute units again), so that a workgroup's walk over several reads can be held
 // to one read a workgroup
 extern "C" int ffhip_debug_errprofile_groups(ffhip_errprofile *p, int groups) {
@@ -1283,10 +1199,9 @@ extern "C" int ffhip_op_map_remap_code(ffhip_engine *eng, const ffhip_map_ref *r
     return FFHIP_OK;
 }
 
-// one alignment from host arguments added into a pileup or a mod pileup (k_pileup, k_modpileup): the checks of both, then a map record, a truth record and a list
-// entry made here, and the ops and the call on the device
-struct PileOp { void *mrec; int *trec; TruthRead *list; uint8_t *ops; char *call; };
-static int pile_op(const char *who, TmpDev &tmp, hipStream_t s, const ffhip_map_ref *ref, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops, PileOp *out) {
+// one alignment from host arguments added into an accumulator: the checks of all four, then a map record, a truth record and a list entry made here, and the ops and
+// the call on the device -- what a launch takes (PileArgs)
+static int pile_op(const char *who, TmpDev &tmp, hipStream_t s, const ffhip_map_ref *ref, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops, PileArgs *out) {
     if (ref) { if (int rc = span_check(who, ref, q, tstart, tend)) return rc; }      // (no reference: the error profile of a given truth, [0, m))
     else if (tstart != 0 || tend < 1) return set_err(FFHIP_EINVAL, "%s: a truth of 1 or more bases", who);
     if (n > (size_t)kTruthMaxLen || nops > (size_t)2 * kTruthMaxLen) return set_err(FFHIP_EINVAL, "%s: a call of %zu bases and %zu ops (at most %d bases)", who, n, nops, kTruthMaxLen);
@@ -1304,28 +1219,25 @@ static int pile_op(const char *who, TmpDev &tmp, hipStream_t s, const ffhip_map_
     mrec.status = 1; mrec.n = (int)n; mrec.nanchor = 1; mrec.q = q; mrec.tstart = tstart; mrec.tend = tend;
     const int trec[kTruthRecInts] = { 1, (int)n, (int)m, (int)(cnt[1] + cnt[2] + cnt[3]), (int)cnt[0], (int)cnt[1], (int)cnt[2], (int)cnt[3], 0, (int)nops, 0, 0 };
     const TruthRead tr{ 0ull, 0ull, 0u, (int)m, 1, 0, (int)nops, 0 };
-    out->mrec = tmp.upload(&mrec, sizeof mrec, s);
-    out->trec = (int *)tmp.upload(trec, sizeof trec, s);
-    out->list = (TruthRead *)tmp.upload(&tr, sizeof tr, s);
-    out->ops = (uint8_t *)tmp.upload(ops, nops, s);
-    out->call = (char *)tmp.upload(n ? call : "", n ? n : 1, s);
-    if (!out->mrec || !out->trec || !out->list || !out->ops || !out->call) OP_NOMEM();
+    *out = { (const TruthRead *)tmp.upload(&tr, sizeof tr, s), 1, tmp.upload(&mrec, sizeof mrec, s), (const int *)tmp.upload(trec, sizeof trec, s),
+             (const uint8_t *)tmp.upload(ops, nops, s), (const char *)tmp.upload(n ? call : "", n ? n : 1, s), n > 0 ? (int)n : 1, ReadMap() };
+    if (!out->list || !out->map_records || !out->truth_records || !out->ops || !out->bases) OP_NOMEM();
     return FFHIP_OK;
 }
 extern "C" int ffhip_op_pileup(ffhip_engine *eng, ffhip_pileup *p, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops) {
     OP_ENTER(eng);
     if (!p || p->eng != eng || (n && !call) || !ops) return set_err(FFHIP_EINVAL, "bad pileup arguments (a pileup of this engine, a call of n letters, nops ops)");
-    PileOp d;
+    PileArgs d;
     if (int rc = pile_op("pileup", tmp, s, p->ref, q, tstart, tend, call, n, ops, nops, &d)) return rc;
-    launch_pileup(s, p->ref->view, d.list, 1, d.mrec, d.trec, d.ops, d.call, n > 0 ? (int)n : 1, ReadMap(), p->view);
+    launch_pileup(s, p->ref->view, d, p->view);
     return op_done(s);
 }
 extern "C" int ffhip_op_consensus(ffhip_engine *eng, ffhip_consensus *c, int q, int tstart, int tend, const char *call, size_t n, const uint8_t *ops, size_t nops) {
     OP_ENTER(eng);
     if (!c || c->eng != eng || (n && !call) || !ops) return set_err(FFHIP_EINVAL, "bad consensus arguments (a consensus of this engine, a call of n letters, nops ops)");
-    PileOp d;
+    PileArgs d;
     if (int rc = pile_op("consensus", tmp, s, c->ref, q, tstart, tend, call, n, ops, nops, &d)) return rc;
-    launch_consensus(s, c->ref->view, d.list, 1, d.mrec, d.trec, d.ops, d.call, n > 0 ? (int)n : 1, ReadMap(), c->view);
+    launch_consensus(s, c->ref->view, d, c->view);
     return op_done(s);
 }
 // ... into an error profile (k_errprofile): with a reference the truth's letters are its span's, else the m codes given
@@ -1334,14 +1246,14 @@ static int errprofile_op(ffhip_engine *eng, ffhip_errprofile *p, const ffhip_map
     OP_ENTER(eng);
     if (!p || p->eng != eng || (n && (!call || !qual)) || !ops || (ref ? ref->eng != eng : !truth))
         return set_err(FFHIP_EINVAL, "bad error profile arguments (an error profile of this engine, a call of n letters with its n quality characters, a truth or a reference of this engine, nops ops)");
-    PileOp d;
+    PileArgs d;
     if (int rc = pile_op("error profile", tmp, s, ref, q, tstart, tend, call, n, ops, nops, &d)) return rc;
     const size_t m = (size_t)(tend - tstart);
     if (!ref) if (const size_t j = bad_code(truth, m, 5); j < m) return set_err(FFHIP_EINVAL, "error profile: position %zu of the truth: code %d is not one of 0 .. 4", j, (int)truth[j]);
     const char *d_qual = (const char *)tmp.upload(n ? qual : "", n ? n : 1, s);
     const uint8_t *d_truth = ref ? nullptr : (const uint8_t *)tmp.upload(truth, m, s);
     if (!d_qual || (!ref && !d_truth)) OP_NOMEM();
-    launch_errprofile(s, ref ? &ref->view : nullptr, d.list, 1, 1, d.mrec, d.trec, d.ops, d.call, d_qual, d_truth, n > 0 ? (int)n : 1, ReadMap(), p->view);
+    launch_errprofile(s, ref ? &ref->view : nullptr, d, 1, d_qual, d_truth, p->view);
     return op_done(s);
 }
 extern "C" int ffhip_op_errprofile(ffhip_engine *eng, ffhip_errprofile *p, const char *call, const char *qual, size_t n, const uint8_t *truth, size_t m, const uint8_t *ops, size_t nops) {
@@ -1357,12 +1269,12 @@ extern "C" int ffhip_op_modpileup(ffhip_engine *eng, ffhip_modpileup *p, int q, 
     OP_ENTER(eng);
     if (!p || p->eng != eng || (n && (!call || !ml)) || !ops)
         return set_err(FFHIP_EINVAL, "bad mod pileup arguments (a mod pileup of this engine, a call of n letters with its n 5mC bytes, nops ops)");
-    PileOp d;
+    PileArgs d;
     if (int rc = pile_op("mod pileup", tmp, s, p->ref, q, tstart, tend, call, n, ops, nops, &d)) return rc;
     const uint8_t zero = 0;
     const uint8_t *d_ml = (const uint8_t *)tmp.upload(n ? ml : &zero, n ? n : 1, s);
     if (!d_ml) OP_NOMEM();
-    launch_modpileup(s, p->ref->view, d.list, 1, d.mrec, d.trec, d.ops, d.call, d_ml, n > 0 ? (int)n : 1, ReadMap(), p->view);
+    launch_modpileup(s, p->ref->view, d, d_ml, p->view);
     return op_done(s);
 }
 

@@ -8,11 +8,13 @@
 #include "../../include/ffhip.h"
 #include "ffhip_internal.hpp"
 
+constexpr int kEngineStreams = 4;
+
 struct ffhip_engine {
     int device = 0;
     hipDeviceProp_t prop;
-    hipStream_t streams[4] = { nullptr, nullptr, nullptr, nullptr };      // batches take them in turn (FFHIP_DEBUG=streams=2..4)
-    int nstreams = 4, next_stream = 0;
+    hipStream_t streams[kEngineStreams] = {};      // batches take them in turn (FFHIP_DEBUG=streams=2..4)
+    int nstreams = kEngineStreams, next_stream = 0;
     int profiling = 0;
     // Persistent recurrent kernels spin on their peers: every workgroup of a launch must be resident.
     // Two batches (streams) may run such kernels at the same time only if both fit; otherwise the
@@ -73,37 +75,23 @@ struct ffhip_map_ref {
     std::vector<int> rec_len;           // [nrec]: the records' letters, on the host (ffhip_op_map_stretch checks its span against them)
 };
 
-// a pileup on the device (ffhip_pileup_create; the kernel's view of it is PileupView): 12 planes of P uint32 and eight uint64 totals, which the batches it is
-// attached to add to on their own streams -- `used` says which of the engine's streams hold such work that nothing has waited for yet
-struct ffhip_pileup {
+// a run-wide accumulator on the device: counters which the batches it is attached to add to on their own streams -- `used` says which of the engine's streams hold
+// such work that nothing has waited for yet.  ref: the reference whose positions it counts by (the error profile: none)
+struct ffhip_pile {
     ffhip_engine *eng = nullptr;
     const ffhip_map_ref *ref = nullptr;
-    ffhip::PileupView view{};
-    bool used[4] = { false, false, false, false };
+    bool used[kEngineStreams] = {};
 };
-// a mod pileup on the device (ffhip_modpileup_create; the kernel's view of it is ModPileupView): 10 planes of P uint32, and eight uint64 totals with the 256 uint64
-// bins of the histogram behind them in one allocation; `used` as the pileup's
-struct ffhip_modpileup {
-    ffhip_engine *eng = nullptr;
-    const ffhip_map_ref *ref = nullptr;
-    ffhip::ModPileupView view{};
-    bool used[4] = { false, false, false, false };
-};
-// a consensus on the device (ffhip_consensus_create; the kernels' view of it is ConsensusView): 37 planes of P uint32 and eight uint64 totals; `used` as the pileup's
-struct ffhip_consensus {
-    ffhip_engine *eng = nullptr;
-    const ffhip_map_ref *ref = nullptr;
-    ffhip::ConsensusView view{};
-    bool used[4] = { false, false, false, false };
-};
-// an error profile on the device (ffhip_errprofile_create; the kernel's view of it is ErrProfileView): kErrWords uint64, the tables and the twelve totals behind them;
-// `used` as the pileup's.  groups: the most workgroups of a launch (the engine's compute units; ffhip_debug_errprofile_groups sets another)
-struct ffhip_errprofile {
-    ffhip_engine *eng = nullptr;
-    ffhip::ErrProfileView view{};
-    int groups = 1;
-    bool used[4] = { false, false, false, false };
-};
+// a pileup (ffhip_pileup_create; the kernel's view of it is PileupView): 12 planes of P uint32 and eight uint64 totals
+struct ffhip_pileup : ffhip_pile { ffhip::PileupView view{}; };
+// a mod pileup (ffhip_modpileup_create; the kernel's view of it is ModPileupView): 10 planes of P uint32, and eight uint64 totals with the 256 uint64 bins of the
+// histogram behind them in one allocation
+struct ffhip_modpileup : ffhip_pile { ffhip::ModPileupView view{}; };
+// a consensus (ffhip_consensus_create; the kernels' view of it is ConsensusView): 37 planes of P uint32 and eight uint64 totals
+struct ffhip_consensus : ffhip_pile { ffhip::ConsensusView view{}; };
+// an error profile (ffhip_errprofile_create; the kernel's view of it is ErrProfileView): kErrWords uint64, the tables and the twelve totals behind them.
+// groups: the most workgroups of a launch (the engine's compute units; ffhip_debug_errprofile_groups sets another)
+struct ffhip_errprofile : ffhip_pile { ffhip::ErrProfileView view{}; int groups = 1; };
 
 // a function or table one file of the library defines for another and the library does not export
 #define FFHIP_LOCAL __attribute__((visibility("hidden")))

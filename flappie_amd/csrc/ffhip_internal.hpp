@@ -296,42 +296,41 @@ void launch_map_stretch(hipStream_t s, const MapRefView &ref, const void *record
 // records[entry.read]: the stretch y_q[tstart : tend] as remap_code's entries (stay | move << 8, alphabet of nbase) at seq + entry.seq, and entry.L and entry.status
 // patched by the header's rule; an entry's room is the read's blocks (tbs[read], or Tb) + 1
 void launch_map_remap_seq(hipStream_t s, const MapRefView &ref, const void *records, RemapRead *list, int count, unsigned short *seq, int nbase, int Tb, const int *tbs);
-// pileup (k_pileup, ffhip_pileup.hip; include/ffhip.h "pileup"): for each of `count` entries of truth's list, from the map record at map_records[entry.read], the
-// truth record at truth_records[entry.read], the K op bytes right-aligned in the entry's cap bytes of `ops` and the call's letters, the read's counts added into the
-// 12 planes of P uint32 [strand][column][position] and the eight uint64 totals { reads, skipped, match, mismatch, del, ins, edge_ins, 0 }.  The entry's m and
-// status are not read.  One launch, a workgroup an entry, atomics only.
-struct PileupView { unsigned *counts; unsigned long long *totals; size_t P; int min_identity; };
+// The run-wide accumulators (ffhip_pile.hpp and the four files below).  What their launches take alike, a finished batch's (ffhip_features.hip pile_args) or one
+// alignment's (pile_op): `count` entries of truth's list, the map records and the truth records (a read's at [entry.read]), the ops buffer (an entry's K op bytes
+// right-aligned in its cap bytes) and the calls' letters (rows of Tb + 1, or as `map` says).  An entry's status is not read.  Atomics only.
+struct PileArgs { const TruthRead *list; int count; const void *map_records; const int *truth_records; const uint8_t *ops; const char *bases; int Tb; ReadMap map; };
+// ... and what the views of the three that count by reference position share: planes of P uint32 at counts, uint64 totals, the identity a read needs in per mille
+struct PileView { unsigned *counts; unsigned long long *totals; size_t P; int min_identity; };
+// pileup (k_pileup, ffhip_pileup.hip; include/ffhip.h "pileup"): the read's counts added into the 12 planes [strand][column][position] and the eight totals
+// { reads, skipped, match, mismatch, del, ins, edge_ins, 0 }.  One launch, a workgroup an entry.
+struct PileupView : PileView {};
 constexpr int kPileupPlanes = 12, kPileupTotals = 8;
-void launch_pileup(hipStream_t s, const MapRefView &ref, const TruthRead *list, int count, const void *map_records, const int *truth_records, const uint8_t *ops,
-                   const char *bases, int Tb, ReadMap map, const PileupView &pv);
-// mod pileup (k_modpileup, ffhip_modpileup.hip; include/ffhip.h "mod pileup"): the same entries, records, ops and letters, and the calls' 5mC bytes `ml` (rows as the
-// letters'): the read's counts at the reference's C (- strand: G) positions added into the 10 planes of P uint32 [strand][mod canon fail diff del][position], the
-// eight uint64 totals { reads, skipped, sites, mod, canon, fail, diff, del } and the 256 uint64 bins of the histogram of the counted bytes.  The reference's letters
-// come from ref.words.  One launch, a workgroup an entry, atomics only.
-struct ModPileupView { unsigned *counts; unsigned long long *totals, *hist; size_t P; int min_identity, lo, hi; };
+void launch_pileup(hipStream_t s, const MapRefView &ref, const PileArgs &a, const PileupView &pv);
+// mod pileup (k_modpileup, ffhip_modpileup.hip; include/ffhip.h "mod pileup"): with the calls' 5mC bytes `ml` (rows as the letters'), the read's counts at the
+// reference's C (- strand: G) positions added into the 10 planes [strand][mod canon fail diff del][position], the eight totals { reads, skipped, sites, mod, canon,
+// fail, diff, del } and the 256 uint64 bins of the histogram of the counted bytes.  The reference's letters come from ref.words.  One launch, a workgroup an entry.
+struct ModPileupView : PileView { unsigned long long *hist; int lo, hi; };
 constexpr int kModPileupColumns = 5, kModPileupPlanes = 2 * kModPileupColumns, kModPileupTotals = 8, kModPileupBins = 256;
-void launch_modpileup(hipStream_t s, const MapRefView &ref, const TruthRead *list, int count, const void *map_records, const int *truth_records, const uint8_t *ops,
-                      const char *bases, const uint8_t *ml, int Tb, ReadMap map, const ModPileupView &pv);
-// consensus (k_consensus and k_consensus_call, ffhip_consensus.hip; include/ffhip.h "consensus"): the same entries, records, ops and letters as the pileup's: the read's
-// forward letters, deletions and inserted letters added into the 37 planes of P uint32 [plane][position] -- A C G T del, then A C G T of each of the 8 minor columns
-// behind the position -- and the eight uint64 totals { reads, skipped, bases, del, ins_bases, long_ins, edge_ins, reserved }.  One launch, a workgroup an entry,
-// atomics only.  launch_consensus_call: a 16-byte ffhip_consensus_cell a position into `cells` (device memory), the reference's letters from ref.words.
-struct ConsensusView { unsigned *counts; unsigned long long *totals; size_t P; int min_identity; };
+void launch_modpileup(hipStream_t s, const MapRefView &ref, const PileArgs &a, const uint8_t *ml, const ModPileupView &pv);
+// consensus (k_consensus and k_consensus_call, ffhip_consensus.hip; include/ffhip.h "consensus"): the read's forward letters, deletions and inserted letters added
+// into the 37 planes [plane][position] -- A C G T del, then A C G T of each of the 8 minor columns behind the position -- and the eight totals { reads, skipped,
+// bases, del, ins_bases, long_ins, edge_ins, reserved }.  One launch, a workgroup an entry.  launch_consensus_call: a 16-byte ffhip_consensus_cell a position into
+// `cells` (device memory), the reference's letters from ref.words.
+struct ConsensusView : PileView {};
 constexpr int kConsensusMinor = 8, kConsensusPlanes = 5 + 4 * kConsensusMinor, kConsensusTotals = 8;
 enum { kConsensusLow = 0, kConsensusSame = 1, kConsensusSub = 2, kConsensusDel = 3, kConsensusIns = 4 };      // a cell's `what` (FFHIP_CONSENSUS_LOW ...: ffhip_consensus_call holds them equal)
-void launch_consensus(hipStream_t s, const MapRefView &ref, const TruthRead *list, int count, const void *map_records, const int *truth_records, const uint8_t *ops,
-                      const char *bases, int Tb, ReadMap map, const ConsensusView &cv);
+void launch_consensus(hipStream_t s, const MapRefView &ref, const PileArgs &a, const ConsensusView &cv);
 void launch_consensus_call(hipStream_t s, const MapRefView &ref, const ConsensusView &cv, unsigned min_depth, void *cells);
-// error profile (k_errprofile, ffhip_errprofile.hip; include/ffhip.h "error profile"): the same entries, truth records, ops and letters, the calls' quality characters
-// `quals` (rows as the letters') and the truths: the read's ops classed into kErrWords uint64 at ev.counts -- sub[4][5], ins[4], qual[94][3], ctx[1024][4],
-// hp[4][16][33], then the twelve totals { reads, skipped, match, mismatch, del, ins, edge_ins, ctx_sites, hp_runs, hp_long, hp_wide, reserved }.  `ref` given: the
-// mode of truth from map -- the map records are read and a truth letter comes from ref's words at the record's span; `seq` is not read.  `ref` null: a set truth --
-// a letter is seq[entry.seq + j] and no map record is read.  One launch of min(count, groups) workgroups, each taking every gridDim.x-th entry; atomics only.
+// error profile (k_errprofile, ffhip_errprofile.hip; include/ffhip.h "error profile"): with the calls' quality characters `quals` (rows as the letters') and the
+// truths, the read's ops classed into kErrWords uint64 at ev.counts -- sub[4][5], ins[4], qual[94][3], ctx[1024][4], hp[4][16][33], then the twelve totals { reads,
+// skipped, match, mismatch, del, ins, edge_ins, ctx_sites, hp_runs, hp_long, hp_wide, reserved }.  `ref` given: the mode of truth from map -- the map records are
+// read and a truth letter comes from ref's words at the record's span; `seq` is not read.  `ref` null: a set truth -- a letter is seq[entry.seq + j] and no map
+// record is read.  One launch of min(count, groups) workgroups, each taking every gridDim.x-th entry.
 struct ErrProfileView { unsigned long long *counts; int min_identity; };
 constexpr int kErrHpMaxRun = 16, kErrHpMaxCalled = 32, kErrHpMaxOps = 64;
 constexpr int kErrAtSub = 0, kErrAtIns = 20, kErrAtQual = 24, kErrAtCtx = 306, kErrAtHp = 4402, kErrTableWords = 6514, kErrTotals = 12, kErrWords = kErrTableWords + kErrTotals;
-void launch_errprofile(hipStream_t s, const MapRefView *ref, const TruthRead *list, int count, int groups, const void *map_records, const int *truth_records,
-                       const uint8_t *ops, const char *bases, const char *quals, const uint8_t *seq, int Tb, ReadMap map, const ErrProfileView &ev);
+void launch_errprofile(hipStream_t s, const MapRefView *ref, const PileArgs &a, int groups, const char *quals, const uint8_t *seq, const ErrProfileView &ev);
 // the signal of every base of a mapped read (k_events, ffhip_events.hip; include/ffhip.h "events"): per listed read whose remap record at records[read] says
 // { status 1, end 0 }, L events of 16 bytes { int32 first, count; float mean, sd } at events[out ..], from the read's samples sig[sig .. sig + n) and its bytes at the
 // read's row of the (Tb + 1)-entry byte buffer `rm`; any other read writes nothing.  One form; the launch comes behind launch_remap on the same stream.

@@ -1,4 +1,4 @@
-// ffhip_seq.hpp -- what the sequence kernels share, each written once: the letters' 2-bit codes, one column of Myers' bit-vector recurrence, the 64-lane
+// ffhip_seq.hpp -- what the sequence kernels share, each written once: the letters' 2-bit codes and a reference's, one column of Myers' bit-vector recurrence, the 64-lane
 // butterfly reductions, the flip-flop state coding of a coded position, and the two-hypothesis window recursion over a read's score rows.  Device code, except the
 // state coding, which the host reads too.  Every result is an integer, or a float with a fixed order of operations: a kernel that calls these computes the same
 // bytes wherever it stands.  Included by ffhip_adapters, _barcodes, _map, _truth, _pileup, _modpileup, _consensus, _errprofile, _polytail, _events, _remap, _sitemods and _variants.hip.
@@ -7,10 +7,17 @@
 #include <math.h>
 #include <type_traits>
 
+#include "ffhip_internal.hpp"
+
 namespace ffhip {
 
 // ---- letters
 __device__ __forceinline__ unsigned seq_code(char c) { return c == 'A' ? 0u : c == 'G' ? 2u : c == 'T' ? 3u : 1u; }      // C and Z: 1 (the call holds A C G T Z only)
+// the letter at position g of a reference's 2-bit words (MapRefView::words: 16 letters a word, kMapPad letters of padding ahead of position 0)
+__device__ __forceinline__ unsigned ref_letter(const unsigned *__restrict__ words, size_t g) {
+    g += (size_t)kMapPad;
+    return (words[g >> 4] >> (2 * (int)(g & 15))) & 3u;
+}
 
 // ---- Myers' bit-vector recurrence (J. ACM 46:395) in Hyyro's block form with a horizontal carry between words, as edlib's calculateBlock
 // the match mask of the letter c among a word's four (all four read first: selects between registers, not branches around loads)
