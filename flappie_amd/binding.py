@@ -1331,7 +1331,8 @@ def map_truth_bound(nblock: int, max_error: int) -> int:
 
 
 def op_remap(engine: Engine, trans: np.ndarray, nbase: int, codes, band: int = 2048) -> tuple:
-    """ffhip_op_remap: (rm uint8 [nblock], score float32) of ONE read's transition scores `trans` [nblock][nstate (nbase + 1)] mapped to `codes` (0 .. nbase - 1, signal order)"""
+    """ffhip_op_remap: (rm uint8 [nblock], score float32) of ONE read's transition scores `trans` [nblock][nstate (nbase + 1)] mapped to `codes` (0 .. nbase - 1, signal order);
+    scores that leave no finite path (the batch's status 2) raise FFHipError with FFHIP_EINVAL"""
     t = np.ascontiguousarray(trans, dtype=np.float32)
     q = np.ascontiguousarray(codes, dtype=np.uint8)
     rm, score = np.zeros(t.shape[0], np.uint8), C.c_float(0.0)

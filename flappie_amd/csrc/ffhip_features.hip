@@ -1304,9 +1304,12 @@ extern "C" int ffhip_op_remap(ffhip_engine *eng, ffhip_mat trans, int nbase, con
     launch_remap(s, form, d_list, 1, d_seq, d_t, (int)trans.stride, band, d_ws, d_rec, d_rm, (int)N, nullptr, ReadMap());
     int rec[4];
     HIP_TRY(hipMemcpyAsync(rec, d_rec, 16, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
+    HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
+    // (L and N were checked above: the kernel's only status 2 is the score's, a property of the input and no failure of the device)
+    if (rec[0] == 2) return set_err(FFHIP_EINVAL, "remap: the score V_N[L - 1] is not finite: the scores leave no finite path (a NaN or an infinity among the entries it reads, or sums past float32)");
+    if (rec[0] != 1 || rec[3] != 0) return set_err(FFHIP_EHIP, "remap: status %d, traceback ended at position %d", rec[0], rec[3]);
     HIP_TRY(hipMemcpyAsync(rm, d_rm, N, hipMemcpyDeviceToHost, s), FFHIP_EHIP);
     HIP_TRY(hipStreamSynchronize(s), FFHIP_EHIP);
-    if (rec[0] != 1 || rec[3] != 0) return set_err(FFHIP_EHIP, "remap: status %d, traceback ended at position %d", rec[0], rec[3]);
     memcpy(score, &rec[2], 4);
     return FFHIP_OK;
 }

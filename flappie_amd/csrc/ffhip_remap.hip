@@ -154,6 +154,12 @@ k_remap(const RemapRead *__restrict__ list, const unsigned short *__restrict__ s
     }
     __threadfence();                                                // the words of every wave, before any thread reads them back
     __syncthreads();
+    // A score that is not finite (a NaN or an infinity on the way: no strict compare need have won) leaves bits that describe no path: not mapped, status 2, and
+    // no traceback.  A finite one was chosen, block by block, from a finite source plus a finite entry, so its bits lead through allowed cells to cell 0.
+    if (!(fabsf(fscore) < INFINITY)) {                              // (uniform: one LDS word)
+        if (tid == 0) rec[read] = make_uint4(2u, (unsigned)L, 0u, 0u);
+        return;
+    }
 
     // ---- traceback
     int th = ((L - 1) % S) / K, kk = ((L - 1) % S) % K, p = L - 1;   // (thread 0's: the slot of cell p as thread and register)

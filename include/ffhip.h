@@ -561,12 +561,17 @@ int ffhip_op_map(ffhip_engine *eng, const ffhip_map_ref *ref, int window, int ma
  *   Path: p_0 .. p_N with p_0 = 0, p_N = L - 1, p_{b+1} - p_b in {0, 1}; it needs 1 <= L <= N + 1.  Its score is
  *     sum_b T[b][trans_lookup(q_{p_b}, q_{p_{b+1}}, nbase)] (decode.c:104-114: to < nbase ? to nstate + from : nbase nstate + from); a stay is from = to.
  *   Band: c(b) = floor(b (L - 1) / N) in 64-bit integers, b = 0 .. N; cell (b, i) is allowed iff 0 <= i <= L - 1 and |i - c(b)| <= W, W >= 0 the band half-width.
- *     The centre line is itself a path, so every W has a solution; W >= L - 1 excludes nothing.
+ *     The centre line is itself a path, so for finite scores every W has a solution; W >= L - 1 excludes nothing.
  *   Recursion, in float32: V_0[0] = 0, V_0[i > 0] = -inf.  For an allowed cell (b + 1, i): stay = V_b[i] + T[b][idx(q_i, q_i)], move = V_b[i-1] + T[b][idx(q_{i-1}, q_i)],
  *     a term being -inf where its source cell is not allowed or i = 0; V_{b+1}[i] = move if move > stay STRICTLY, else stay, and the cell's bit records which won.
  *     Each sum is one rounded add: no fused multiply-add, no re-association, no other arithmetic.  score = V_N[L - 1]; the traceback from (N, L - 1) follows the bits.
+ *   Mapped: a read is mapped (status 1) iff score = V_N[L - 1] is FINITE.  A finite V was chosen from a finite source plus a finite entry, cells that are not allowed
+ *     hold -inf and V_0 is finite at cell 0 alone: the bits under a finite score lead through allowed cells to (0, 0).  With a NaN or an infinity on the way no
+ *     strict compare need have won and the bits need not describe a path, so a score that is NaN, +inf or -inf is status 2, "not mapped: the scores leave no finite
+ *     path", whatever the bits say: the kernel tests the score once, ahead of the traceback, and follows no bit.  Such a read's record is that of every status 2
+ *     read: { 2, L, 0, 0 }, no rm.
  *   Output per read: the score; rm[b] = p_{b+1} - p_b, b = 0 .. N - 1 (N bytes of 0 / 1 whose sum is L - 1); status 0 no sequence given, 1 mapped,
- *     2 not mapped (L > N + 1 or L = 0).
+ *     2 not mapped (L > N + 1, L = 0, or a score that is not finite).
  *   What a caller derives: base i starts at block start[0] = 0, start[i] = 1 + (index of the i-th one); maxdev = max_b |p_b - c(b)| says whether the band was
  *     touched; block b stands for samples [trim_start + b stride, ...) as for ffhip_batch_moves.
  * ffhip_batch_set_remap: the sequences (copied, and coded, at the call) and the band of the batch's later runs with FFHIP_RUN_REMAP; nread = the batch's reads
@@ -575,7 +580,8 @@ int ffhip_op_map(ffhip_engine *eng, const ffhip_map_ref *ref, int window, int ma
  *   codes == NULL detaches.  Not between a run and its finish.
  * ffhip_batch_remap: after ffhip_batch_finish of a run with the flag; rm points into the batch (nblock bytes, valid until the next run), NULL unless status is 1.
  * ffhip_op_remap: the kernel on ONE matrix of scores (nstate (nbase + 1) rows, a column a block) and one sequence; rm: caller-owned, nblock bytes.  L = 0 or
- *   L > nblock + 1, a code >= nbase, band < 0: FFHIP_EINVAL.
+ *   L > nblock + 1, a code >= nbase, band < 0: FFHIP_EINVAL.  It has no status: scores that leave no finite path are FFHIP_EINVAL too, with a text that names the
+ *   score; rm and *score are then left as they were.
  * The traceback workspace (a bit a cell of the window and block, in 64-bit words) is grown by the first run that needs it, sized from the batch's reads and the band,
  * freed with the batch and counted by ffhip_debug_batch_device_bytes; when it cannot be had: FFHIP_ENOMEM with the bytes in the text. */
 typedef struct { int status; size_t L; float score; const uint8_t *rm; size_t nblock; } ffhip_remap_call;
@@ -645,8 +651,10 @@ int ffhip_op_events(ffhip_engine *eng, const float *signal, size_t nsample, int 
  *     positions before i code as in s itself, those after i may change between flip and flop until the run of equal letters ends (CCC codes C c C, CZC codes C Z C).
  *   Recursion over all cells j = lo .. hi, no band, for t = t0 .. t1 - 1: X_t0[lo] = 0, X_t0[j > lo] = -inf; stay = X_t[j] + T[t][idx(q_j, q_j)],
  *     move = X_t[j-1] + T[t][idx(q_{j-1}, q_j)] (-inf for j = lo), idx = remap's trans_lookup.
- *     Best-path mode, in float32, each term ONE rounded add: X_{t+1}[j] = max(stay, move); the score X_t1[hi] is reproducible to the bit.
- *     All-paths mode, in fp64 (T converted exactly): X_{t+1}[j] = m + log1p(exp(-|stay - move|)), m = max(stay, move); m = -inf gives -inf, never a NaN; the
+ *     Best-path mode, in float32, each term ONE rounded add: X_{t+1}[j] = move if move > stay (a strict compare, the rule of "variants") else stay -- max(stay,
+ *     move) on finite and -inf terms; a NaN stay is kept, a NaN move is not taken.  The score X_t1[hi] is reproducible to the bit.
+ *     All-paths mode, in fp64 (T converted exactly), in IEEE arithmetic as written: m = move if move > stay else stay; X_{t+1}[j] = -inf if m == -inf, else
+ *     m + log1p(exp(-|stay - move|)): from finite or -inf scores never a NaN.  A NaN entry, or +inf met by +inf, on a term gives NaN, and the reader sees it.  The
  *     score X_t1[hi] is rounded to float32 once.
  *   Output per site: the 16 bytes { int32 pos = i; int32 nblock = n; float can; float mod; }.  The log-likelihood ratio is can - mod and
  *     p(5mC) = 1 / (1 + exp(can - mod)): both are left to the reader.
@@ -683,7 +691,8 @@ int ffhip_op_site_mods(ffhip_engine *eng, ffhip_mat trans, int nbase, const uint
  *   Recursion: that of "site mods", over each hypothesis's own P positions j = 0 .. P - 1: X_t0[0] = 0, X_t0[j > 0] = -inf; for t = t0 .. t1 - 1:
  *     stay = X_t[j] + T[t][idx(q_j, q_j)], move = X_t[j-1] + T[t][idx(q_{j-1}, q_j)] (-inf for j = 0), idx = remap's trans_lookup.
  *     Best-path mode, in float32, each term ONE rounded add: X_{t+1}[j] = move if move > stay (a strict compare) else stay; reproducible to the bit.
- *     All-paths mode, in fp64 (T converted exactly): X_{t+1}[j] = m + log1p(exp(-|stay - move|)), m = max(stay, move); m = -inf gives -inf, never a NaN; the
+ *     All-paths mode, in fp64 (T converted exactly), in IEEE arithmetic as written: m = move if move > stay else stay; X_{t+1}[j] = -inf if m == -inf, else
+ *     m + log1p(exp(-|stay - move|)): from finite or -inf scores never a NaN.  A NaN entry, or +inf met by +inf, on a term gives NaN, and the reader sees it.  The
  *     score is rounded to float32 once.
  *     The score is X_t1[P - 1].  A hypothesis with n < P - 1 has no path: its score is -inf, which comes out of the recursion and is no special case (the ref
  *     hypothesis always has one: the remap path itself).

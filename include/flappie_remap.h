@@ -3,7 +3,8 @@
  *  The mapping itself is made on the GPU (FFHIP_RUN_REMAP, include/ffhip.h "remap": the flip-flop coding, the band, the recursion and its tie rule); this
  *  header is the reader of the sequences, the derivation of start[] and maxdev from a read's moves, and the line of map.tsv.
  *  refs.fa is a FASTA file: a record's name runs up to the first blank of its header, its sequence stands on one line or several, lower case is upper-cased.
- *  A record with a letter outside the model's alphabet (ACGT, or ACGTZ) is kept as BAD: its read gets status 2.  A read finds its record by its read id
+ *  A record with a letter outside the model's alphabet (ACGT, or ACGTZ) is kept as BAD: its read gets status 2, as does one with more bases than blocks + 1
+ *  and one whose scores leave no finite path (include/ffhip.h "remap").  A read finds its record by its read id
  *  first, then by its file's base name (with or without the extension).  Sequences are in SIGNAL order.
  *  map.tsv, one line per read that had a record, tab-separated:
  *    name  status  nblock  stride  trim_start  L  band  maxdev  score(%.9g)  start[0],start[1],...     (maxdev, score and start[] are * for status 2)

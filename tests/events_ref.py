@@ -83,6 +83,24 @@ def check(got, want, x, where=None):
         assert bad.size == 0, (where, f, bad[:4], got[f][bad[:4]], want[f][bad[:4]], tol[bad[:4]])
 
 
+def check_hostile(got, want, x, where=None):
+    """check's rule for a signal with samples that are not finite: first and count exact; mean and sd NaN exactly where the statement's are, +-inf equal, every
+    finite one within tolerance(x, want) as in check"""
+    got = np.asarray(got)
+    assert got.dtype == EVENT_DTYPE and got.shape == want.shape, (where, got.dtype, got.shape, want.shape)
+    assert np.array_equal(got["first"], want["first"]) and np.array_equal(got["count"], want["count"]), where
+    with np.errstate(invalid="ignore"):
+        tol = tolerance(x, want)
+    for f in ("mean", "sd"):
+        g, w = got[f].astype(np.float64), want[f].astype(np.float64)
+        assert np.array_equal(np.isnan(g), np.isnan(w)), (where, f, np.flatnonzero(np.isnan(g) != np.isnan(w))[:4])
+        inf = np.isinf(w)
+        assert np.array_equal(g[inf], w[inf]), (where, f, g[inf][:4], w[inf][:4])
+        fin = np.isfinite(w)
+        bad = np.flatnonzero(fin)[~(np.abs(g[fin] - w[fin]) <= tol[fin])]
+        assert bad.size == 0, (where, f, bad[:4], got[f][bad[:4]], want[f][bad[:4]], tol[bad[:4]])
+
+
 def rm_of_lengths(blocks):
     """the path of bases that hold these many blocks each (the last may hold none: L = N + 1)"""
     N = int(sum(blocks))

@@ -420,6 +420,9 @@ def record(engine):
     case("op_remap: band -1+code 4", L.ffhip_op_remap(e, m4, 4, s5p, 4, -1, d8, C.byref(sc)))
     case("op_remap: 10 bases for 8 blocks+code 4", L.ffhip_op_remap(e, m4, 4, _u8([0, 4] * 5)[1], 10, 16, d8, C.byref(sc)))
     case("op_remap: nbase 5 for 40 rows+code 4", L.ffhip_op_remap(e, m4, 5, s5p, 4, 16, d8, C.byref(sc)))
+    # (added with the status rule of "remap": scores that leave no finite path are the operator's one refusal that the kernel finds)
+    tnan, mnan = _mat(np.full((8, 40), np.nan, np.float32), 40)
+    case("op_remap: scores of NaN", L.ffhip_op_remap(e, mnan, 4, s4p, 4, 16, d8, C.byref(sc)))
     # 5000 blocks, 5000 bases and a band that does not narrow them: a window of 5000 cells, which no kernel form holds
     tw, mw = _mat(np.zeros((5000, 40), np.float32), 40)
     dw = (C.c_uint8 * 5000)()

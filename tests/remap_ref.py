@@ -1,7 +1,8 @@
 """Restatement of the remap semantics of include/ffhip.h ("remap") in numpy float32, and a brute-force enumerator of all paths for tiny cases.
 
 A read of N blocks with transition scores T [N][nstate (nbase + 1)], a sequence s of L codes 0 .. nbase - 1 in signal order, a band half-width W:
-remap(T, s, nbase, W) -> (score float32, rm uint8 [N]).  One float32 add a term and a strict compare: the result is reproducible to the bit."""
+remap(T, s, nbase, W) -> (score float32, rm uint8 [N]).  One float32 add a term and a strict compare: the result is reproducible to the bit.
+remap_status(T, s, nbase, W) -> (status, score, rm) for scores of any kind: a score that is not finite is status 2 and has no path."""
 import itertools
 
 import numpy as np
@@ -37,7 +38,8 @@ def _indices(s, nbase):
     return stay, move
 
 
-def remap(T, s, nbase, W):
+def _forward(T, s, nbase, W):
+    """the recursion: (V_N, [(a, win)] a block: the first allowed cell and the bits of the allowed cells)"""
     T = np.asarray(T, np.float32)
     N, L = T.shape[0], len(s)
     assert N >= 1 and 1 <= L <= N + 1 and W >= 0
@@ -45,7 +47,7 @@ def remap(T, s, nbase, W):
     V = np.full(L, NEG, np.float32)
     V[0] = np.float32(0.0)
     bits = []
-    with np.errstate(invalid="ignore"):
+    with np.errstate(invalid="ignore", over="ignore"):
         for b in range(N):
             c = centre(b + 1, L, N)
             a, e = max(0, c - W), min(L - 1, c + W)
@@ -61,14 +63,44 @@ def remap(T, s, nbase, W):
             V = np.full(L, NEG, np.float32)
             V[a:e + 1] = np.where(win, move, stay)
             bits.append((a, win))
+    return V, bits
+
+
+def traceback(bits, L):
+    """follow the bits from (N, L - 1): (rm, the position it ends at, whether it stayed on allowed cells, position 0 included).  A cell outside a block's allowed
+    cells has no bit in this restatement (in a kernel: some other cell's); it reads as 0 and the walk is marked as having left."""
+    N = len(bits)
     rm = np.zeros(N, np.uint8)
-    p = L - 1
+    p, inside = L - 1, True
     for b in range(N - 1, -1, -1):
         a, win = bits[b]
-        rm[b] = 1 if win[p - a] else 0
-        p -= int(rm[b])
-    assert p == 0
-    return np.float32(V[L - 1]), rm
+        if p < a or p - a >= win.size:
+            inside = False
+        elif win[p - a]:
+            rm[b] = 1
+            if p == 0:
+                inside = False
+            p -= 1
+    return rm, p, inside
+
+
+def remap(T, s, nbase, W):
+    V, bits = _forward(T, s, nbase, W)
+    rm, p, inside = traceback(bits, len(s))
+    assert p == 0 and inside
+    return np.float32(V[len(s) - 1]), rm
+
+
+def remap_status(T, s, nbase, W):
+    """(status, score, rm) by the rule of "remap": mapped (1, score, rm) iff V_N[L - 1] is finite; otherwise (2, 0.0, None), "not mapped: the scores leave no
+    finite path", and no bit is followed"""
+    V, bits = _forward(T, s, nbase, W)
+    score = np.float32(V[len(s) - 1])
+    if not np.isfinite(score):
+        return 2, np.float32(0.0), None
+    rm, p, inside = traceback(bits, len(s))
+    assert p == 0 and inside
+    return 1, score, rm
 
 
 def brute(T, s, nbase, W):

@@ -166,3 +166,34 @@ def test_library_exports_the_new_entries():
         [0, 0, 1, 1, 2, 3, 3, -1, 3]
     from flappie_amd import binding
     assert binding.RUN_REMAP == 32768 and hasattr(binding.Batch, "set_remap") and hasattr(binding.Batch, "remap") and hasattr(binding, "op_remap")
+
+
+def test_a_finite_score_has_a_path_and_a_score_that_is_not_finite_is_not_mapped():
+    """the status rule of include/ffhip.h "remap" on scores no network emits (hostile_scores.py): under a finite V_N[L - 1] the bits lead through allowed cells to
+    position 0; under a NaN or an infinity they need not, and remap_status follows none of them.  Both directions occur for every sparse style."""
+    import hostile_scores as H
+    seen = {style: [0, 0] for style in H.STYLES}
+    astray = 0
+    for style, nbase, N, L, W, seed in H.remap_cases(H.REMAP_SHAPES[:4]):
+        T, s = H.styled(style, seed, N, nbase), H.sequence(seed, L, nbase)
+        V, bits = R._forward(T, s, nbase, W)
+        rm, p, inside = R.traceback(bits, L)
+        status, score, srm = R.remap_status(T, s, nbase, W)
+        finite = bool(np.isfinite(V[L - 1]))
+        assert status == (1 if finite else 2), (style, nbase, N, L, W)
+        seen[style][status - 1] += 1
+        if finite:
+            assert p == 0 and inside and int(rm.sum()) == L - 1 and R.starts_maxdev(rm, L)[1] <= W, (style, nbase, N, L, W, p, inside)
+            assert score.tobytes() == np.float32(V[L - 1]).tobytes() and np.array_equal(srm, rm)
+            if np.isfinite(T).all():
+                assert (score, rm.tolist()) == (lambda a: (a[0], a[1].tolist()))(R.remap(T, s, nbase, W))      # (remap() is unchanged for finite input)
+        else:
+            assert srm is None and score.tobytes() == b"\0\0\0\0"
+            astray += not (p == 0 and inside)
+    for style in H.SPARSE:
+        assert min(seen[style]) >= 1, (style, seen)
+    for style in ("flat", "quantised"):
+        assert seen[style][1] == 0, (style, seen)
+    for style in ("nan block", "all nan", "all -inf", "all +inf", "+-3e38"):
+        assert seen[style][0] == 0, (style, seen)
+    assert astray >= 20, astray      # why the rule is needed: the bits under such a score often describe no path

@@ -173,3 +173,89 @@ def test_library_exports_the_new_entries():
     from flappie_amd import binding
     assert binding.RUN_REMAP_MODS == 262144 and binding.SITE_MOD_DTYPE == S.SITE_MOD_DTYPE and binding.SITE_MOD_DTYPE.itemsize == 16
     assert hasattr(binding.Batch, "set_remap_mods") and hasattr(binding.Batch, "site_mods") and hasattr(binding, "op_site_mods")
+
+
+def _windows(rng, N, L, c):
+    codes = rng.choice(np.array([0, 1, 1, 4, 4, 2, 3], np.uint8), L)
+    st = S.starts(_path(rng, N, L), L)
+    for i in S.sites(codes):
+        for letter in (S.CAN, S.MOD):
+            yield (S.code_hypothesis(codes, i, letter, NB),) + S.window(st, L, i, c)
+
+
+def _finite_and_neg_inf_scores(rng, N):
+    for k in range(4):
+        T = _scores(rng, N, 2.0)
+        if k == 1:
+            T = np.round(T * 4.0).astype(np.float32) / np.float32(4.0)      # ties
+        elif k >= 2:
+            T[rng.random(T.shape) < (0.02, 0.3)[k - 2]] = -np.inf
+        yield T
+
+
+def test_best_path_strict_compare_is_max_on_finite_and_neg_inf_scores():
+    """include/ffhip.h "site mods": the rule is the strict compare of "variants"; on finite and -inf terms it is max(stay, move), the wording before"""
+    def score_max(T, q, lo, hi, t0, t1):
+        stay_idx, move_idx = S._indices(q, lo, hi, NB)
+        X = np.full(hi - lo + 1, -np.inf, np.float32)
+        X[0] = 0.0
+        for t in range(t0, t1):
+            move = np.full(X.size, -np.inf, np.float32)
+            move[1:] = X[:-1] + T[t][move_idx[1:]]
+            X = np.maximum(X + T[t][stay_idx], move)
+        return np.float32(X[-1])
+    rng = np.random.default_rng(41)
+    n = neg = 0
+    for T in _finite_and_neg_inf_scores(rng, 120):
+        for c in (0, 3, 15):
+            for q, lo, hi, t0, t1 in _windows(rng, 120, 50, c):
+                a, b = S.score_best(T, q, lo, hi, t0, t1, NB), score_max(T, q, lo, hi, t0, t1)
+                assert not np.isnan(a) and a.tobytes() == b.tobytes(), (c, lo, hi, a, b)
+                n += 1
+                neg += bool(np.isneginf(a))
+    assert n >= 400 and 0 < neg < n, (n, neg)
+
+
+def test_all_paths_ieee_rule_is_the_masked_rule_on_finite_and_neg_inf_scores():
+    """include/ffhip.h "site mods": the all-paths rule as IEEE arithmetic gives, bit for bit, what the statement before gave (m = -inf masked ahead of the
+    arithmetic) wherever the scores are finite or -inf -- and never a NaN there"""
+    def score_masked(T, q, lo, hi, t0, t1):
+        T = T.astype(np.float64)
+        stay_idx, move_idx = S._indices(q, lo, hi, NB)
+        X = np.full(hi - lo + 1, -np.inf, np.float64)
+        X[0] = 0.0
+        for t in range(t0, t1):
+            stay = X + T[t][stay_idx]
+            move = np.full(X.size, -np.inf, np.float64)
+            move[1:] = X[:-1] + T[t][move_idx[1:]]
+            m = np.maximum(stay, move)
+            live = m > -np.inf
+            d = np.zeros(X.size, np.float64)
+            d[live] = np.abs(stay[live] - move[live])
+            X = np.where(live, m + np.log1p(np.exp(-d)), -np.inf)
+        return np.float64(X[-1])
+    rng = np.random.default_rng(43)
+    n = neg = 0
+    for T in _finite_and_neg_inf_scores(rng, 120):
+        for c in (0, 3, 15):
+            for q, lo, hi, t0, t1 in _windows(rng, 120, 50, c):
+                a, b = S.score_all(T, q, lo, hi, t0, t1, NB), score_masked(T, q, lo, hi, t0, t1)
+                assert not np.isnan(a) and a.tobytes() == b.tobytes(), (c, lo, hi, a, b)
+                n += 1
+                neg += bool(np.isneginf(a))
+    assert n >= 400 and 0 < neg < n, (n, neg)
+
+
+def test_a_nan_is_seen_in_both_modes_and_the_two_best_path_rules_part_on_it():
+    """with a NaN entry on a term the all-paths score is NaN (the statement before dropped it), and the strict compare keeps a NaN stay where max() also takes a
+    NaN move: the rules differ, which is why the header names one"""
+    rng = np.random.default_rng(47)
+    T = _scores(rng, 300, 2.0)
+    T[rng.random(T.shape) < 0.02] = np.nan
+    nan_all = nan_best = fin_best = 0
+    for q, lo, hi, t0, t1 in _windows(rng, 300, 120, 3):
+        nan_all += bool(np.isnan(S.score_all(T, q, lo, hi, t0, t1, NB)))
+        b = S.score_best(T, q, lo, hi, t0, t1, NB)
+        nan_best += bool(np.isnan(b))
+        fin_best += bool(np.isfinite(b))
+    assert nan_all > 0 and nan_best > 0 and fin_best > 0, (nan_all, nan_best, fin_best)

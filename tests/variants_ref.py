@@ -9,6 +9,7 @@ import numpy as np
 from remap_ref import flipflop_code
 from sitemods_ref import SITE_MOD_DTYPE, brute, score_all, score_best, starts      # noqa: F401 (brute: for the tests)
 from sitemods_ref import check as sitemods_check
+from sitemods_ref import check_hostile as sitemods_check_hostile
 
 VARIANT_DTYPE = np.dtype([("pos", np.int32), ("nref", np.uint8), ("nalt", np.uint8), ("alt", np.uint8, (16,)), ("pad", np.uint8, (2,))])
 VARIANT_CALL_DTYPE = np.dtype([("index", np.int32), ("nblock", np.int32), ("ref", np.float32), ("alt", np.float32)])
@@ -80,3 +81,9 @@ def check(got, want, all_paths, where):
     """sitemods_ref.check's rule on records of the same layout: best path byte for byte; all paths index and nblock equal, ref and alt within 1 float32 ulp, no NaN"""
     assert got.dtype == VARIANT_CALL_DTYPE and want.dtype == VARIANT_CALL_DTYPE, where
     sitemods_check(got.view(SITE_MOD_DTYPE), want.view(SITE_MOD_DTYPE), all_paths, where)
+
+
+def check_hostile(got, want, all_paths, where):
+    """sitemods_ref.check_hostile's rule, for scores of any kind: a NaN equal to a NaN, +-inf equal"""
+    assert got.dtype == VARIANT_CALL_DTYPE and want.dtype == VARIANT_CALL_DTYPE, where
+    sitemods_check_hostile(got.view(SITE_MOD_DTYPE), want.view(SITE_MOD_DTYPE), all_paths, where)
